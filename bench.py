@@ -13,6 +13,12 @@ Workloads:  c3 (default) synthetic 100-edge / 8-generation pedigre
 c4 the C3 topology, 25 windows x 1000 bootstraps per GPU (= 200 windows over 8 GPUs);  g351 the
 reference's golden pedigree (351 rows, T=32) x 1000 bootstraps;  c5s a single-GPU shard of C5 (20100 rows,
 T=125, 4096 bootstraps) in stream mode.
+
+A plain run sets up, warms up, times --steps steps and prints the line (headline figures and the step counters).
+--full adds everything else the line can carry: per-kernel times and the roofline (a second pass of --steps steps),
+the stream probe, the other workloads, the PCIe-inclusive timing, the strict-order price, the pairwise scan and the CPU
+baseline (each of them can still be left out with its --no-* flag).  --dump-outputs DIR writes what the timed path
+handed its caller in its last step as DIR/<name>.npy (float64), so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -31,6 +37,32 @@ sys.path.insert(0, str(ROOT))
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_VALU_PEAK_TFLOPS = 78.6  # 256 CU x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz
 N_SIMDS, CLOCK_HZ = 256 * 4, 2.4e9   # MI355X: 256 CUs x 4 SIMDs; the clock the FP64 vector peak is quoted at
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: at most this much in all
+
+
+def caller_arrays(out):
+    """The arrays a caller of Plan / MultiPlan .download() receives, the fit-info records split into their fields."""
+    arrs = {k: out[k] for k in ("models", "pred", "resid", "raw", "best_start")}
+    for ph in ("info_a", "info_b"):
+        if out[ph] is not None:
+            for f in out[ph].dtype.names:
+                arrs[f"{ph}_{f}"] = out[ph][f]
+    return arrs
+
+
+def dump_outputs(dirname, arrays) -> None:
+    """--dump-outputs: every array as DIR/<name>.npy in float64.  Should they exceed DUMP_LIMIT_BYTES in all, each one
+    is cut to the same fixed, seeded sample of its flattened elements (same arguments -> same sample)."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items() if v is not None}
+    budget = DUMP_LIMIT_BYTES - 256 * len(arrs)          # room for the .npy headers
+    total = sum(a.nbytes for a in arrs.values())
+    for k, a in arrs.items():
+        if total > budget:
+            keep = a.size * budget // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(d / f"{k}.npy", a)
 
 
 def make_workload(name: str, rank: int, world: int):
@@ -289,12 +321,16 @@ def quick_workload(A, ctx, name, seed, steps=3, **options):
     return r
 
 
-def pairwise_bench(A, ctx, shapes=((15, 4_000_000), (15, 32_000_000), (50, 32_000_000), (50, 2_000_000)), reps=5):
+PAIRWISE_SHAPES = ((15, 4_000_000), (15, 32_000_000), (50, 32_000_000), (50, 2_000_000))
+
+
+def pairwise_bench(A, ctx, shapes=PAIRWISE_SHAPES, reps=5, warmup=1, check=True, last=None):
     """SURVEY §8(f).1, `DMatrix::from` (src/pedigree.rs:210-261): pairwise divergence of n samples over L aligned
     sites, codes RESIDENT in HBM (one byte per sample and site).  One pass over the codes is the algorithmic traffic:
     n*L bytes / kernel time against the HBM peak; the pair arithmetic (n(n-1)/2 pairs x L sites) is reported as
     site-pairs/s next to it.  Shapes: the two of round 2 (the last one, 50 x 2 M, is the `pw` line's value) and the same
-    sample counts at genome scale (32 M sites), where a workgroup sees ~40 tiles instead of 2.5."""
+    sample counts at genome scale (32 M sites), where a workgroup sees ~40 tiles instead of 2.5.  `last`, a dict, gets
+    the outputs of the last shape's last call (diff, both, divergence) on the host."""
     import torch
 
     out = []
@@ -309,17 +345,21 @@ def pairwise_bench(A, ctx, shapes=((15, 4_000_000), (15, 32_000_000), (50, 32_00
         both = torch.zeros(npairs, dtype=torch.int64, device="cuda")
         dval = torch.zeros(npairs, dtype=torch.float64, device="cuda")
         torch.cuda.synchronize()
-        ctx.pairwise_divergence_dev(codes.data_ptr(), n, L, diff.data_ptr(), both.data_ptr(), dval.data_ptr())
+        for _ in range(warmup):
+            ctx.pairwise_divergence_dev(codes.data_ptr(), n, L, diff.data_ptr(), both.data_ptr(), dval.data_ptr())
         ms = [ctx.pairwise_divergence_dev(codes.data_ptr(), n, L, diff.data_ptr(), both.data_ptr(), dval.data_ptr())
               for _ in range(reps)]
         best, avg = min(ms), sum(ms) / len(ms)
-        # property check at full size: every pair compares the sites valid in both samples, 0 <= diff <= 2 * both
-        ok = bool(((diff >= 0) & (diff <= 2 * both) & (both > 0) & (both <= L)).all().item())
         gbs = n * L / (avg * 1e-3) / 1e9
         out.append({"samples": n, "sites": L, "pairs": npairs, "kernel_ms_avg": avg, "kernel_ms_min": best,
                     "code_bytes": n * L, "achieved_GBps": gbs, "peak_GBps": HBM_PEAK_GBS, "frac": gbs / HBM_PEAK_GBS,
                     "traffic": (pw_prof or {}).get(f"{n}x{L}"),   # HBM bytes of the scan launch (FETCH_SIZE x 2, stamped profile)
-                    "site_pairs_per_s": npairs * L / (avg * 1e-3), "sane": ok})
+                    "site_pairs_per_s": npairs * L / (avg * 1e-3)})
+        if check:
+            # property check at full size: every pair compares the sites valid in both samples, 0 <= diff <= 2 * both
+            out[-1]["sane"] = bool(((diff >= 0) & (diff <= 2 * both) & (both > 0) & (both <= L)).all().item())
+        if last is not None:
+            last.update(diff=diff.cpu().numpy(), both=both.cpu().numpy(), divergence=dval.cpu().numpy())
         del codes
     return {"kernel": "abn_pairwise_mx_kernel (v_mfma_i32_16x16x64_i8 Gram products) + abn_pairwise_reduce_tiles_kernel", "bound": "hbm", "unit": "GB/s",
             "what": "n*L code bytes (one pass) / HIP-event time of the call's kernels, inputs resident in HBM",
@@ -518,6 +558,8 @@ def single_process_main(args) -> None:
     cnt = m.counters()
     kms = [m.kernel_ms(i) for i in range(n)]
     out = m.download()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, caller_arrays(out))
     N = gens.shape[0]
     # sanity at full size: every row finite; the table does not depend on how it was sharded (tests/test_gpu_multi.py
     # compares it with a plain plan byte for byte)
@@ -569,9 +611,16 @@ def main():
                     help="time abn_multi_* — ONE process driving the devices of --devices, RCCL gather inside the library "
                          "— instead of one process per GPU; n_gpus = number of devices")
     ap.add_argument("--devices", default=None, help="device ordinals for --single-process, e.g. 0,1,2,3 (default 0..gpus-1)")
-    ap.add_argument("--no-c5-full", action="store_true", help="skip the full-size C5 shard (76 GB, ~20 s) of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-kernel times and roofline (a second pass of --steps "
+                         "steps), stream probe, other workloads, PCIe-inclusive timing, strict-order price, pairwise scan, "
+                         "CPU baseline, full-size C5 shard (the --no-* flags below leave single items out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, at most 64 MB "
+                         "in all)")
+    ap.add_argument("--no-c5-full", action="store_true", help="skip the full-size C5 shard (76 GB, ~20 s) of the --full line")
     ap.add_argument("--lanes", type=int, default=0, help="lanes of a wavefront per chain (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline of the --full line")
     ap.add_argument("--execute-stuck-fits", action="store_true",
                     help="abn_options.no_fixed_point_skip = 1: execute the repeated iterations of fits that have reached "
                          "argmin's fixed point, as the reference does (same outputs; default: finish them at once)")
@@ -581,24 +630,30 @@ def main():
     ap.add_argument("--strict-order", action="store_true",
                     help="abn_options.strict_order = 1: every cost sums its residuals serially in row order, as the "
                          "reference does (src/structs.rs:206-213); fits are then bit-equal to the oracle's lanes = 1. "
-                         "The default line reports the price of this mode as `strict_order`")
+                         "The --full line reports the price of this mode as `strict_order`")
     ap.add_argument("--no-stream-probe", action="store_true",
-                    help="skip the short C5-shard run that measures the stream-mode kernel against the HBM roof")
+                    help="skip the short C5-shard run of the --full line that measures the stream-mode kernel against "
+                         "the HBM roof")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N > 1 ranks on one GPU)")
     ap.add_argument("--force-collective", action="store_true",
                     help="initialise the process group and run the gather even with one rank (exercises the "
                          "torch.distributed / RCCL path on a one-GPU box)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the short extra workloads (C2, C4 shard, G351) and the PCIe-inclusive timing")
+                    help="skip the short extra workloads (C2, C4 shard, G351) and the PCIe-inclusive timing of the "
+                         "--full line")
     ap.add_argument("--stream-sweep", action="store_true",
-                    help="also run the stream-mode kernel with a co-resident working set far below / far above the "
-                         "256 MiB Infinity Cache (slow to set up: a 123k-row pedigree)")
+                    help="with --full: also run the stream-mode kernel with a co-resident working set far below / far "
+                         "above the 256 MiB Infinity Cache (slow to set up: a 123k-row pedigree)")
     args = ap.parse_args()
+    if args.stream_sweep and not args.full:
+        ap.error("--stream-sweep is part of the --full line: add --full")
     if args.steps is None:
         args.steps = {"c5": 1, "c5s": 5, "c5p": 5, "g351": 20, "mp": 20, "pw": 20, "ref1000_c3": 20, "ref1000_g351": 20}.get(args.workload, 200)
     if args.warmup is None:
         args.warmup = 1 if args.workload == "c5" else 3
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.single_process:
         return single_process_main(args)
 
@@ -642,12 +697,17 @@ def main():
     seed = 20260101
     if args.workload == "pw":  # the pedigree-construction scan, its own JSON line
         ctx = A.Context(local_rank, stream=torch.cuda.current_stream().cuda_stream)
-        r = pairwise_bench(A, ctx, reps=max(3, args.steps))
+        # a plain run times the headline shape only; --full all four shapes, each checked
+        last = {}
+        r = pairwise_bench(A, ctx, shapes=PAIRWISE_SHAPES if args.full else PAIRWISE_SHAPES[-1:], reps=args.steps,
+                           warmup=args.warmup, check=args.full, last=last if args.dump_outputs else None)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
         big = r["shapes"][-1]
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps({"metric": "pairwise divergence (DMatrix::from) code bytes/s", "value": big["achieved_GBps"],
-                          "unit": "GB/s", "n_gpus": 1, "steps": max(3, args.steps), "warmup": 1,
+                          "unit": "GB/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": big["kernel_ms_avg"], "higher_is_better": True, "scaling": "weak",
                           "vs_baseline": None, "dtype": "u8", "data": "synthetic",
                           "config": {"workload": f"pairwise divergence, {big['samples']} samples x {big['sites']} sites, "
@@ -689,23 +749,29 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    kms = {"fit_starts": 0.0, "select": 0.0, "fit_boot": 0.0}
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     elapsed = time.perf_counter() - t0
-    # per-kernel HIP-event durations (recorded on the launch stream): re-run K steps, reading the events
-    # after each one (reading forces a sync, so this loop is not the timed region)
-    for _ in range(args.steps):
-        plan.run()
-        ms = plan.kernel_ms()
-        for k in kms:
-            kms[k] += ms[k]
-    for k in kms:
-        kms[k] /= max(1, args.steps)
     cnt = plan.counters()
-    out = plan.download()
+    out = plan.download()                        # the last timed step's results (raises if a window failed)
+    if args.dump_outputs and rank == 0:
+        arrs = caller_arrays(out)
+        if collective:                           # a caller of the N-GPU path receives the gathered table
+            arrs["raw"] = raw_all.cpu().numpy()
+        dump_outputs(args.dump_outputs, arrs)
+    if args.full:
+        # per-kernel HIP-event durations (recorded on the launch stream): re-run K steps, reading the events
+        # after each one (reading forces a sync, so this loop is not the timed region)
+        kms = {"fit_starts": 0.0, "select": 0.0, "fit_boot": 0.0}
+        for _ in range(args.steps):
+            plan.run()
+            ms = plan.kernel_ms()
+            for k in kms:
+                kms[k] += ms[k]
+        for k in kms:
+            kms[k] /= max(1, args.steps)
     if collective:
         # the gathered table must hold every rank's shard: compare per-rank checksums
         step()
@@ -742,58 +808,7 @@ def main():
         fits_per_s = tot_fits / (elapsed / args.steps)
         evals_per_s = tot_evals / (elapsed / args.steps)
         lanes = int(out["info_b"]["lanes"][0, 0])
-        K = len({tuple(r) for r in wl["gens"].astype(int).tolist()})
-        T = int(wl["gens"].max())
-        # ---- roofline of the dominant kernel (phase-B fit kernel), per launch on this rank
-        fits_b, evals_b = Wr * B, int(out["info_b"]["evals"].sum()) - cnt["evals_skipped_boot"]
         tree_code = lanes                 # abn_fit_info.lanes: the residual reduction tree of the pedigree
-        stream = ((lanes >> 8) & 0xff) != 0   # row-block code set: the pedigree is streamed every evaluation
-        lanes &= 0xff
-        if stream:
-            # SURVEY.md §8(d) per-evaluation figure (4N + 40: the u32 index stream).  The default stream variant
-            # moves 8N + 40 per evaluation instead (materialised observations, no per-evaluation gather); its
-            # real stream rate is reported beside it as `streamed_*`.
-            alg_bytes = evals_b * (4 * N + 40) + fits_b * 112 + Wr * N * 16 + N * 2 + K * 4 + Wr * 56
-            streamed_bytes = evals_b * (8 * N + 40) + fits_b * (12 * N + 112)  # tid (2 B/row) is L2-resident
-        else:
-            # 4N (index row) + 5 x 32 (start simplex) + 40 (candidate in, cost out) per LDS-resident fit,
-            # shared bytes N (3 + 8 + 8) per window counted once per launch
-            alg_bytes = fits_b * (4 * N + 5 * 32 + 40) + Wr * N * 19
-        kern_s = kms["fit_boot"] * 1e-3
-        achieved = alg_bytes / kern_s / 1e9 if kern_s > 0 else 0.0
-        flops_eval = 45 * T + 53 * K + 4 * N + 60
-        valu_tflops = evals_b * flops_eval / kern_s / 1e12 if kern_s > 0 else 0.0
-        phases, traffic_source = measured_traffic(args.workload)
-        ph_b = (phases or {}).get("fit_boot")
-        traffic = ph_b.get("hbm_bytes_per_launch") if ph_b else None
-        if ph_b:
-            traffic_source = dict(traffic_source, kernel=ph_b.get("kernel"))
-        roofline = {
-            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-            "kernel": ("abn_fit_kernel<64, stream>" if stream else "abn_fit_kernel / abn_fit_refill_kernel (packed)") +
-                      " phase B", "kernel_ms": kms["fit_boot"],
-            "algorithmic_bytes_per_launch": alg_bytes,
-            "mode": "stream" if stream else "resident",
-            **({"streamed_bytes_per_launch": streamed_bytes,
-                "beyond_l2_GBps": streamed_bytes / kern_s / 1e9,
-                "beyond_l2_frac_of_hbm_peak": streamed_bytes / kern_s / 1e9 / HBM_PEAK_GBS} if stream else {}),
-            "note": ("stream mode: `achieved` prices an evaluation at SURVEY's 4N+40 B (index stream); the kernel "
-                     "streams the materialised observations, 8N+40 B per evaluation past L2 (HBM + Infinity Cache): "
-                     "beyond_l2_*" if stream
-                     else "LDS-resident fits: the index row is read once per fit, so the HBM roofline is nominal; "
-                          "the kernel is FP64-VALU/latency bound (see valu_fp64)"),
-            "valu_fp64": {"achieved_tflops": valu_tflops, "peak_tflops": FP64_VALU_PEAK_TFLOPS,
-                          "frac": valu_tflops / FP64_VALU_PEAK_TFLOPS, "flops_per_eval": flops_eval},
-        }
-        # how busy the vector pipe is (the roof the resident kernels actually run under), per phase, from the stamped profile
-        vi = valu_issue(ph_b, kern_s)
-        if vi:
-            roofline["valu_issue"] = vi
-        vi_a = valu_issue((phases or {}).get("fit_starts"), kms["fit_starts"] * 1e-3)
-        if vi_a:
-            roofline["phase_a"] = {"kernel_ms": kms["fit_starts"], "valu_issue": vi_a,
-                                   "traffic": (phases or {}).get("fit_starts", {}).get("hbm_bytes_per_launch")}
         result = {
             "metric": "ABneutral model fits/sec (pedigree x bootstraps x windows)",
             "value": fits_per_s, "unit": "fits/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -809,35 +824,86 @@ def main():
             "evals_not_executed_per_step": tot_skipped,
             "fixed_point_skip": not args.execute_stuck_fits,
             "strict_order_run": bool(args.strict_order),
-            "kernel_ms": kms,
-            "roofline": roofline,
         }
-        if world == 1 and not args.no_stream_probe and args.workload != "c5s":
-            result["roofline_stream"] = stream_probe(A, ctx, seed)
-            if args.stream_sweep:
-                result["roofline_stream_sweep"] = stream_sweep(A, ctx, seed)
-        if world == 1 and not args.no_extras:
-            if Wr == 1:
-                result["pcie_inclusive"] = pcie_inclusive(A, ctx, wl, opts)
-            result["extra_workloads"] = {n: quick_workload(A, ctx, n, seed)
-                                         for n in ("c2", "c4", "c4s", "mp", "g351", "ref1000_c3", "ref1000_g351")
-                                         if n != args.workload}
-            if not args.no_c5_full and args.workload != "c5":
-                result["extra_workloads"]["c5_full_shard"] = c5_full_shard(A, ctx, seed)
-            # what the reference's summation order costs on this workload (not on the streamed C5 shapes: N = 20 100 serial
-            # additions per evaluation take minutes, and with --workload c5 a second 76 GB plan beside the open one)
-            if not args.strict_order and args.workload not in ("c5", "c5s"):
-                so = quick_workload(A, ctx, args.workload, seed, strict_order=1)
-                so["price"] = fits_per_s / so["fits_per_s"]
-                so["what"] = ("abn_options.strict_order = 1 (serial row-order residual sums, bit-equal to the oracle's "
-                              "lanes = 1); price = default fits/s / strict fits/s")
-                result["strict_order"] = so
-            result["pairwise"] = pairwise_bench(A, ctx)
-        if not args.no_cpu_baseline and world == 1:   # the CPU baseline is a one-GPU (rank 0) measurement
-            bs = int(out["best_start"][0])
-            if bs >= 0:
-                result["cpu_baseline"] = cpu_baseline(wl, out["models"][0], out["pred"][0], out["resid"][0], lanes, seed,
-                                                      float(out["info_b"]["evals"][0].mean()))
+        if args.full:
+            stream = ((lanes >> 8) & 0xff) != 0   # row-block code set: the pedigree is streamed every evaluation
+            lanes &= 0xff
+            K = len({tuple(r) for r in wl["gens"].astype(int).tolist()})
+            T = int(wl["gens"].max())
+            # ---- roofline of the dominant kernel (phase-B fit kernel), per launch on this rank
+            fits_b, evals_b = Wr * B, int(out["info_b"]["evals"].sum()) - cnt["evals_skipped_boot"]
+            if stream:
+                # SURVEY.md §8(d) per-evaluation figure (4N + 40: the u32 index stream).  The default stream variant
+                # moves 8N + 40 per evaluation instead (materialised observations, no per-evaluation gather); its
+                # real stream rate is reported beside it as `streamed_*`.
+                alg_bytes = evals_b * (4 * N + 40) + fits_b * 112 + Wr * N * 16 + N * 2 + K * 4 + Wr * 56
+                streamed_bytes = evals_b * (8 * N + 40) + fits_b * (12 * N + 112)  # tid (2 B/row) is L2-resident
+            else:
+                # 4N (index row) + 5 x 32 (start simplex) + 40 (candidate in, cost out) per LDS-resident fit,
+                # shared bytes N (3 + 8 + 8) per window counted once per launch
+                alg_bytes = fits_b * (4 * N + 5 * 32 + 40) + Wr * N * 19
+            kern_s = kms["fit_boot"] * 1e-3
+            achieved = alg_bytes / kern_s / 1e9 if kern_s > 0 else 0.0
+            flops_eval = 45 * T + 53 * K + 4 * N + 60
+            valu_tflops = evals_b * flops_eval / kern_s / 1e12 if kern_s > 0 else 0.0
+            phases, traffic_source = measured_traffic(args.workload)
+            ph_b = (phases or {}).get("fit_boot")
+            traffic = ph_b.get("hbm_bytes_per_launch") if ph_b else None
+            if ph_b:
+                traffic_source = dict(traffic_source, kernel=ph_b.get("kernel"))
+            roofline = {
+                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                "kernel": ("abn_fit_kernel<64, stream>" if stream else "abn_fit_kernel / abn_fit_refill_kernel (packed)") +
+                          " phase B", "kernel_ms": kms["fit_boot"],
+                "algorithmic_bytes_per_launch": alg_bytes,
+                "mode": "stream" if stream else "resident",
+                **({"streamed_bytes_per_launch": streamed_bytes,
+                    "beyond_l2_GBps": streamed_bytes / kern_s / 1e9,
+                    "beyond_l2_frac_of_hbm_peak": streamed_bytes / kern_s / 1e9 / HBM_PEAK_GBS} if stream else {}),
+                "note": ("stream mode: `achieved` prices an evaluation at SURVEY's 4N+40 B (index stream); the kernel "
+                         "streams the materialised observations, 8N+40 B per evaluation past L2 (HBM + Infinity Cache): "
+                         "beyond_l2_*" if stream
+                         else "LDS-resident fits: the index row is read once per fit, so the HBM roofline is nominal; "
+                              "the kernel is FP64-VALU/latency bound (see valu_fp64)"),
+                "valu_fp64": {"achieved_tflops": valu_tflops, "peak_tflops": FP64_VALU_PEAK_TFLOPS,
+                              "frac": valu_tflops / FP64_VALU_PEAK_TFLOPS, "flops_per_eval": flops_eval},
+            }
+            # how busy the vector pipe is (the roof the resident kernels actually run under), per phase, from the stamped profile
+            vi = valu_issue(ph_b, kern_s)
+            if vi:
+                roofline["valu_issue"] = vi
+            vi_a = valu_issue((phases or {}).get("fit_starts"), kms["fit_starts"] * 1e-3)
+            if vi_a:
+                roofline["phase_a"] = {"kernel_ms": kms["fit_starts"], "valu_issue": vi_a,
+                                       "traffic": (phases or {}).get("fit_starts", {}).get("hbm_bytes_per_launch")}
+            result.update(kernel_ms=kms, roofline=roofline)
+            if world == 1 and not args.no_stream_probe and args.workload != "c5s":
+                result["roofline_stream"] = stream_probe(A, ctx, seed)
+                if args.stream_sweep:
+                    result["roofline_stream_sweep"] = stream_sweep(A, ctx, seed)
+            if world == 1 and not args.no_extras:
+                if Wr == 1:
+                    result["pcie_inclusive"] = pcie_inclusive(A, ctx, wl, opts)
+                result["extra_workloads"] = {n: quick_workload(A, ctx, n, seed)
+                                             for n in ("c2", "c4", "c4s", "mp", "g351", "ref1000_c3", "ref1000_g351")
+                                             if n != args.workload}
+                if not args.no_c5_full and args.workload != "c5":
+                    result["extra_workloads"]["c5_full_shard"] = c5_full_shard(A, ctx, seed)
+                # what the reference's summation order costs on this workload (not on the streamed C5 shapes: N = 20 100 serial
+                # additions per evaluation take minutes, and with --workload c5 a second 76 GB plan beside the open one)
+                if not args.strict_order and args.workload not in ("c5", "c5s"):
+                    so = quick_workload(A, ctx, args.workload, seed, strict_order=1)
+                    so["price"] = fits_per_s / so["fits_per_s"]
+                    so["what"] = ("abn_options.strict_order = 1 (serial row-order residual sums, bit-equal to the oracle's "
+                                  "lanes = 1); price = default fits/s / strict fits/s")
+                    result["strict_order"] = so
+                result["pairwise"] = pairwise_bench(A, ctx)
+            if not args.no_cpu_baseline and world == 1:   # the CPU baseline is a one-GPU (rank 0) measurement
+                bs = int(out["best_start"][0])
+                if bs >= 0:
+                    result["cpu_baseline"] = cpu_baseline(wl, out["models"][0], out["pred"][0], out["resid"][0], lanes, seed,
+                                                          float(out["info_b"]["evals"][0].mean()))
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps(result), flush=True)

@@ -29,7 +29,7 @@ for i, flags in enumerate(args or [""]):
         continue
     for w in workloads:
         env = dict(os.environ, ABNEUTRAL_HIP_LIB=str(lib))
-        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", w, "--no-stream-probe",
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--workload", w, "--no-stream-probe",
                             "--no-cpu-baseline", *bench_args], capture_output=True, text=True, env=env)
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])

@@ -9,7 +9,7 @@
 for wl in ${@:-c3 c4}; do
   for cfg in "nohelp 0" "knobs 0" "knobs 1" "nohelp 0" "knobs 1"; do
     set -- $cfg
-    ABNEUTRAL_HIP_LIB=$PWD/build/libabn_$1.so ABN_HELPERS=$2 python bench.py --workload $wl --steps 50 --no-extras --no-stream-probe --no-cpu-baseline 2>/dev/null |
+    ABNEUTRAL_HIP_LIB=$PWD/build/libabn_$1.so ABN_HELPERS=$2 python bench.py --full --workload $wl --steps 50 --no-extras --no-stream-probe --no-cpu-baseline 2>/dev/null |
       python3 -c "import json,sys; j=json.loads(sys.stdin.read()); print('$wl lib=$1 helpers=$2', round(j['value']), 'fits/s', {k: round(v,3) for k,v in j['kernel_ms'].items()})"
   done
 done

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 wl=${1:-c4}; out=${2:-gpurun_out/pmc_sq_$wl}
 rm -rf "$out" && mkdir -p "$out"
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY --output-format csv -d "$out/pmc" -- python3 bench.py --workload $wl --steps 5 --warmup 1 --no-cpu-baseline --no-stream-probe --no-extras > "$out/bench.json" 2> "$out/err.txt"
+rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY --output-format csv -d "$out/pmc" -- python3 bench.py --full --workload $wl --steps 5 --warmup 1 --no-cpu-baseline --no-stream-probe --no-extras > "$out/bench.json" 2> "$out/err.txt"
 python3 - "$out" <<'PY'
 import csv, glob, sys, collections, json
 out = sys.argv[1]

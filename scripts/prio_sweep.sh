@@ -3,7 +3,7 @@
 # (build/libabn_knobs.so, cross-compiled before the call).  ABN_PRIO = mode,t0,t1,t2 (abn_device.hpp: FitArgs::prio_mode).
 run() {  # $1 = label, rest = env assignments
   local label=$1; shift
-  env ABNEUTRAL_HIP_LIB=$PWD/build/libabn_knobs.so "$@" python bench.py --workload ${WL:-c3} --steps ${STEPS:-100} --no-extras --no-stream-probe --no-cpu-baseline 2>/dev/null |
+  env ABNEUTRAL_HIP_LIB=$PWD/build/libabn_knobs.so "$@" python bench.py --full --workload ${WL:-c3} --steps ${STEPS:-100} --no-extras --no-stream-probe --no-cpu-baseline 2>/dev/null |
     python3 -c "import json,sys; j=json.loads(sys.stdin.read()); print('${WL:-c3} $label', round(j['value']), 'fits/s', {k: round(v,3) for k,v in j['kernel_ms'].items()})"
 }
 run base X=1

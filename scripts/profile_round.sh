@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/prof_$wl
 rm -rf "$out" && mkdir -p "$out"
 passes=${PASSES:-kt fetch write sq sq2}
-args="--workload $wl --steps ${STEPS:-20} --warmup ${WARMUP:-2} --no-cpu-baseline --no-stream-probe --no-extras $*"
+args="--full --workload $wl --steps ${STEPS:-20} --warmup ${WARMUP:-2} --no-cpu-baseline --no-stream-probe --no-extras $*"
 for p in $passes; do
   case $p in
     kt) rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -- python3 bench.py $args > "$out/bench_under_rocprof.json" 2> "$out/kt.err";;

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=${1:-gpurun_out/pw_prof}
 rm -rf "$out" && mkdir -p "$out"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -- python3 bench.py --workload pw --steps 5 > "$out/bench.json" 2> "$out/kt.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -- python3 bench.py --full --workload pw --steps 5 > "$out/bench.json" 2> "$out/kt.err"
 python3 - "$out" <<'PY'
 import csv, glob, sys, collections
 out = sys.argv[1]
@@ -26,7 +26,7 @@ for k, v in d.items():      # the bench runs several site counts through the sam
 PY
 # one separate --pmc pass: bytes fetched past L2 per launch (FETCH_SIZE is in KiB; x2 on gfx950 for wide coalesced reads,
 # MI355X_MICROARCH.md) against the n x L code bytes — the kernel reads the codes once
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -- python3 bench.py --workload pw --steps 5 > /dev/null 2> "$out/pmc.err"
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -- python3 bench.py --full --workload pw --steps 5 > /dev/null 2> "$out/pmc.err"
 python3 - "$out" "$GRAFT_REPO_ROOT" "${2:-r04}" <<'PY'
 import csv, glob, sys, collections, json, hashlib, datetime
 from pathlib import Path

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for wl in ref1000_c3 ref1000_g351; do
   out=gpurun_out/prof_$wl
   rm -rf "$out" && mkdir -p "$out"
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -- python3 bench.py --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-stream-probe --no-extras > "$out/bench.json" 2> "$out/kt.err"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -- python3 bench.py --full --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-stream-probe --no-extras > "$out/bench.json" 2> "$out/kt.err"
   echo "== $wl"
   python3 - "$out" <<'PY'
 import csv, glob, sys, collections, json, os

@@ -9,7 +9,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 run_bench() {  # $1 = file stem, rest = bench args
   local stem=$1; shift
-  timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py "$@" > $out/bench_$stem.json 2> $out/bench_$stem.err; echo "bench $stem rc=$?"
+  timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py --full "$@" > $out/bench_$stem.json 2> $out/bench_$stem.err; echo "bench $stem rc=$?"
 }
 case $stage in
 tests)

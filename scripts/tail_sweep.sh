@@ -3,7 +3,7 @@
 # that kernel keeps resident the later workgroups start as earlier ones end), wavefronts and quantum re-swept (knobs build).
 run() {
   local label=$1; shift
-  env ABNEUTRAL_HIP_LIB=$PWD/build/libabn_knobs.so "$@" python bench.py --workload $WL --steps ${STEPS:-30} --no-extras --no-stream-probe --no-cpu-baseline 2>/dev/null |
+  env ABNEUTRAL_HIP_LIB=$PWD/build/libabn_knobs.so "$@" python bench.py --full --workload $WL --steps ${STEPS:-30} --no-extras --no-stream-probe --no-cpu-baseline 2>/dev/null |
     python3 -c "import json,sys; j=json.loads(sys.stdin.read()); print('$WL $label', round(j['value']), 'fits/s', {k: round(v,3) for k,v in j['kernel_ms'].items()})"
 }
 for WL in c3 c4 mp; do

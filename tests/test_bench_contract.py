@@ -4,6 +4,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -11,7 +12,7 @@ ROOT = Path(__file__).resolve().parent.parent
 
 @pytest.mark.gpu
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--no-stream-probe",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-stream-probe",
                         "--no-cpu-baseline", "--no-c5-full"], capture_output=True, text=True, cwd=str(ROOT), timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -43,6 +44,37 @@ def test_bench_json_contract():
     # ... and what the reference's summation order costs
     assert j["strict_order"]["price"] > 1.0 and j["strict_order_run"] is False
     assert all(sh["sane"] and sh["achieved_GBps"] > 100 for sh in j["pairwise"]["shapes"])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run times its steps and prints the headline line, nothing of the --full line; --dump-outputs writes what
+    the last timed step computed (float64 .npy), the same arrays from run to run."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, cwd=str(ROOT), timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in j, k
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "fits/s" and j["dtype"] == "f64"
+        assert j["fits_per_step"] == 10 + 10000 and j["value"] > 1e5 and j["ms_per_step"] > 0
+        for k in ("kernel_ms", "roofline", "roofline_stream", "extra_workloads", "pcie_inclusive", "strict_order",
+                  "pairwise", "cpu_baseline"):
+            assert k not in j, k
+        files = {f.stem: np.load(f) for f in d.glob("*.npy")}
+        assert {"models", "pred", "resid", "raw", "best_start", "info_b_evals"} <= set(files)
+        assert all(a.dtype == np.float64 for a in files.values())
+        assert sum(f.stat().st_size for f in d.glob("*.npy")) <= 64_000_000
+        assert files["raw"].shape == (1, 10000, 7) and np.isfinite(files["raw"]).all()
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True), k
 
 
 @pytest.mark.gpu
@@ -102,3 +134,27 @@ def test_bench_c4_strong_scaling_workload():
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert j["scaling"] == "strong" and j["fits_per_step"] == 200 * 1010 and j["config"]["windows_per_gpu"] == 200
+
+
+def test_dump_outputs_keeps_to_64_mb(tmp_path):
+    """--dump-outputs writes float64 arrays; above 64 MB in all they are cut to a fixed, seeded sample (CPU only)."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    small = {"a": np.arange(12, dtype=np.int32).reshape(3, 4), "b": np.linspace(0.0, 1.0, 5), "none": None}
+    big = {"big": np.arange(9_000_000, dtype=np.float64), "small": np.arange(10, dtype=np.int64)}   # 72 MB
+    bench.dump_outputs(tmp_path / "small", small)
+    got = {f.stem: np.load(f) for f in (tmp_path / "small").glob("*.npy")}
+    assert set(got) == {"a", "b"} and all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["a"], small["a"]) and np.array_equal(got["b"], small["b"])
+    runs = []
+    for i in range(2):
+        bench.dump_outputs(tmp_path / f"big{i}", big)
+        files = sorted((tmp_path / f"big{i}").glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64_000_000
+        runs.append({f.stem: np.load(f) for f in files})
+    assert all(np.array_equal(runs[0][k], runs[1][k]) for k in ("big", "small"))
+    s = runs[0]["big"]
+    assert s.dtype == np.float64 and s.size > 7_000_000 and np.all(np.diff(s) > 0) and np.all(np.isin(s, big["big"]))
