@@ -133,17 +133,27 @@ static int pick_lanes(int n, int requested, int chain_stride) {
   while (g < 64 && (size_t)(kWave / g) * per_chain > kLdsTargetPerBlock) g *= 2;
   return g;
 }
-static bool fit_streams(int n, int chain_stride, int lanes, int strict = 0);
-static bool tree_on_wave_ok(int n_rows, int chain_stride, int tree, int strict);
+// Doubles a chain's LDS region holds beyond the topology's scratch stride when its pedigree is resident: the
+// observations, the triple list of the K distinct triples (even: 16-byte aligned chains) and, in strict order, the rows'
+// terms.  The one residency footprint: launch_fit sizes its launches by it, and every decision taken before a launch
+// (plan, tree, kernel choice) asks it too, so that what is decided is what runs.
+static int resident_extra(int n, int k, int strict) {
+  return ((n + 1) & ~1) + (((k + 1) / 2 + 1) & ~1) + (strict ? ((n + 1) & ~1) : 0);
+}
+static bool resident_fits(int n, int k, int chain_stride, int lanes, int strict) {
+  return (size_t)(kWave / lanes) * (size_t)(chain_stride + resident_extra(n, k, strict)) * sizeof(double) <= kLdsResidentMax;
+}
+static bool fit_streams(int n, int k, int chain_stride, int lanes, int strict = 0);
+static bool tree_on_wave_ok(int n_rows, int k, int chain_stride, int tree, int strict);
 static bool spec_applicable(const FitArgs& a);
 static int launch_fit_spec(abn_ctx* c, FitArgs a, hipStream_t st);
 // The residual reduction tree (FitArgs::tree; abn_fit_info.lanes).  Auto (lanes_per_chain == 0) and the pedigree
 // LDS-resident: the canonical 64-accumulator tree, which every kernel — packed, one wavefront per chain, four
 // wavefronts per chain — runs at its native cost.  Streamed pedigrees and explicit lane counts: one accumulator per
 // lane of the packed kernel.
-static int pick_tree(int n, int requested, int chain_stride, int lanes, int strict = 0) {
+static int pick_tree(int n, int k, int requested, int chain_stride, int lanes, int strict = 0) {
   if (strict) return 1;  // serial row order (abn_options.strict_order): no tree
-  if (requested != 0 || fit_streams(n, chain_stride, lanes, strict)) return lanes;
+  if (requested != 0 || fit_streams(n, k, chain_stride, lanes, strict)) return lanes;
   return kTreeCanon;
 }
 static int pick_rmax(int n, int lanes) {
@@ -221,11 +231,9 @@ static int launch_fit(abn_ctx* c, FitArgs a, int lanes, hipStream_t st, int* kin
   } else if (a.tree != kTreeCanon) {
     a.tree = lanes;
   }
-  // resident observations + this chain's triple list (even: 16-byte aligned chains) (+ strict order: the rows' terms)
-  const int np = ((a.N + 1) & ~1) + (((a.K + 1) / 2 + 1) & ~1) + (a.strict ? ((a.N + 1) & ~1) : 0);
-  if (rmax > 0) {
-    if ((size_t)ng * (size_t)(a.chain_stride + np) * sizeof(double) > kLdsResidentMax) rmax = 0;
-    else a.chain_stride += np;
+  if (rmax > 0) {  // resident: observations + this chain's triple list (+ strict order: the rows' terms) next to the scratch
+    if (!resident_fits(a.N, a.K, a.chain_stride, lanes, a.strict)) rmax = 0;
+    else a.chain_stride += resident_extra(a.N, a.K, a.strict);
   }
   if (rmax <= 0 && a.tree == kTreeCanon)
     return set_err(c, ABN_ERR_INVALID_ARG, "internal: the canonical tree needs an LDS-resident pedigree");
@@ -318,13 +326,11 @@ static int launch_fit(abn_ctx* c, FitArgs a, int lanes, hipStream_t st, int* kin
   return ABN_OK;
 }
 
-// true when launch_fit will use the stream variant for this pedigree / lane count.  Strict order keeps the rows' terms in
-// LDS next to the observations (N more doubles per chain): the same footprint launch_fit computes, so that what a plan
-// decides (and validates) at abn_plan_create is what runs.
-static bool fit_streams(int n, int chain_stride, int lanes, int strict) {
+// true when launch_fit will use the stream variant for this pedigree (n rows, k distinct triples) / lane count: the same
+// footprint launch_fit computes (resident_fits), so that what a plan decides (and validates) at abn_plan_create is what runs.
+static bool fit_streams(int n, int k, int chain_stride, int lanes, int strict) {
   if (pick_rmax(n, lanes) == 0) return true;
-  const int np = ((n + 1) & ~1) + n / 2 + 2 + (strict ? ((n + 1) & ~1) : 0);  // observations + triple list (K <= n) (+ terms)
-  return (size_t)(kWave / lanes) * (size_t)(chain_stride + np) * sizeof(double) > kLdsResidentMax;
+  return !resident_fits(n, k, chain_stride, lanes, strict);
 }
 
 // Speculative kernel (phase A; three evaluation wavefronts + a bookkeeping wavefront per chain): resident mode
@@ -348,19 +354,16 @@ static long long spec_max_chains(const abn_ctx* c, int n_rows, int phase) {
 
 // a wavefront per chain runs the canonical tree (or, strict order, the serial sum) whenever the pedigree is LDS-resident
 // at 64 lanes per chain; an explicit lanes_per_chain tree only when it IS 64 lanes
-static bool tree_on_wave_ok(int n_rows, int chain_stride, int tree, int strict) {
+static bool tree_on_wave_ok(int n_rows, int k, int chain_stride, int tree, int strict) {
   if (!strict && tree != kTreeCanon) return tree == kWave;
-  const int rmax = pick_rmax(n_rows, kWave);
-  if (rmax <= 0) return false;
-  const int np = ((n_rows + 1) & ~1) + n_rows / 2 + 2 + (strict ? ((n_rows + 1) & ~1) : 0);  // strict order: + the terms
-  return (size_t)(chain_stride + np) * sizeof(double) <= kLdsResidentMax;
+  return !fit_streams(n_rows, k, chain_stride, kWave, strict);
 }
 
 static bool spec_applicable(const FitArgs& a) {
   if (a.dmode == 2) return false;  // resident observations only (starts, or bootstraps gathered through the index row)
   const int rmax = pick_rmax(a.N, kWave);
   if (rmax == 0 || rmax > 8) return false;  // 16 rows per lane: the plain resident kernel
-  if (!tree_on_wave_ok(a.N, a.chain_stride, a.tree, a.strict)) return false;
+  if (!tree_on_wave_ok(a.N, a.K, a.chain_stride, a.tree, a.strict)) return false;
   const int np = ((a.N + 1) & ~1) * (a.strict ? 2 : 1);   // observations (+ strict order: the rows' terms)
   return (3 * (size_t)(a.chain_stride + np) + kSpecCommDoubles) * sizeof(double) <= kLdsResidentMax;
 }
@@ -467,8 +470,8 @@ extern "C" int abn_reduction_tree(const abn_options* opts, const double* generat
   if (rc) return rc;
   const int lanes = pick_lanes(n_rows, o.lanes_per_chain, t.chain_stride);
   *tree = o.strict_order ? 1
-          : fit_streams(n_rows, t.chain_stride, lanes) ? (lanes | ((kStreamVec - 1) << 8))
-                                                       : pick_tree(n_rows, o.lanes_per_chain, t.chain_stride, lanes);
+          : fit_streams(n_rows, t.K, t.chain_stride, lanes) ? (lanes | ((kStreamVec - 1) << 8))
+                                                            : pick_tree(n_rows, t.K, o.lanes_per_chain, t.chain_stride, lanes);
   return ABN_OK;
 }
 
@@ -701,7 +704,7 @@ extern "C" int abn_cost_batch(abn_ctx* c, const abn_options* opts, const double*
   a.cand = dcand.p;
   a.M = m;
   a.strict = o.strict_order ? 1 : 0;
-  a.tree = o.strict_order ? lanes : pick_tree(N, o.lanes_per_chain, t.chain_stride, lanes);
+  a.tree = o.strict_order ? lanes : pick_tree(N, t.K, o.lanes_per_chain, t.chain_stride, lanes);
   a.cost = dcost.p;
   a.dt = ddt.p;
   a.puu = dpuu.p;
@@ -805,7 +808,7 @@ extern "C" int abn_fit_batch(abn_ctx* c, const abn_options* opts, const double* 
   a.raw = nullptr;
   const int lanes = pick_lanes(N, o.lanes_per_chain, t.chain_stride);
   a.strict = o.strict_order ? 1 : 0;
-  a.tree = pick_tree(N, o.lanes_per_chain, t.chain_stride, lanes, a.strict);
+  a.tree = pick_tree(N, t.K, o.lanes_per_chain, t.chain_stride, lanes, a.strict);
   rc = launch_fit(c, a, lanes, c->stream);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(best, dbest.p, dbest.bytes(), hipMemcpyDeviceToHost, c->stream));
@@ -895,7 +898,7 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
     return set_err(c, rc, abn_status_string(rc));
   }
   p->lanes = pick_lanes(n_rows, p->opt.lanes_per_chain, p->topo.chain_stride);
-  p->tree = pick_tree(n_rows, p->opt.lanes_per_chain, p->topo.chain_stride, p->lanes, p->opt.strict_order);
+  p->tree = pick_tree(n_rows, p->topo.K, p->opt.lanes_per_chain, p->topo.chain_stride, p->lanes, p->opt.strict_order);
   p->lanes_a = p->lanes;
   // Phase A is latency-bound while its chains fit the machine about twice over (3 wavefronts x 1024 SIMDs): one
   // wavefront per chain then beats packing several chains into a wavefront, and below ~1000 chains the
@@ -905,7 +908,7 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
   // The reduction tree stays the pedigree's (p->tree) whichever kernel runs: results do not depend on the size of
   // the launch, hence not on how a job is sharded over GPUs.
   if (p->opt.lanes_per_chain == 0 && (long long)n_windows * n_starts <= kPhaseAWidePerCu * c->cus &&
-      tree_on_wave_ok(n_rows, p->topo.chain_stride, p->tree, p->opt.strict_order))
+      tree_on_wave_ok(n_rows, p->topo.K, p->topo.chain_stride, p->tree, p->opt.strict_order))
     p->lanes_a = 64;
   // the footprint launch_fit will ask for when the pedigree is streamed (resident launches stay below kLdsResidentMax by
   // construction): the scratch of the workgroup's chains, plus one chunk of terms per chain in strict order — validated
@@ -968,7 +971,8 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
       if (p->susp_list.n < chains + 1) PALLOC(susp_list, chains + 1);  // the tail list of the hand-over to the speculative kernel
     }
   }
-  p->stream_b = n_boot > 0 && fit_streams(n_rows, p->topo.chain_stride, p->lanes, p->opt.strict_order) && p->opt.stream_mode == 0;
+  p->stream_b = n_boot > 0 && fit_streams(n_rows, p->topo.K, p->topo.chain_stride, p->lanes, p->opt.strict_order) &&
+                p->opt.stream_mode == 0;
   if (p->stream_b) PALLOC(dstar, W * B * N);
 #undef PALLOC
   p->raw = p->raw_own.p;
@@ -1118,7 +1122,7 @@ static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
   int lanes_a = p->lanes_a;
 #ifdef ABN_MEASUREMENT_KNOBS  // ABN_PHASE_A_KERNEL = spec | wide | packed  (scripts/phase_a_sweep.py)
   if (const char* e = getenv("ABN_PHASE_A_KERNEL")) {
-    const bool can_wide = p->opt.lanes_per_chain == 0 && tree_on_wave_ok(p->N, p->topo.chain_stride, p->tree, p->opt.strict_order);
+    const bool can_wide = p->opt.lanes_per_chain == 0 && tree_on_wave_ok(p->N, p->topo.K, p->topo.chain_stride, p->tree, p->opt.strict_order);
     if (!strcmp(e, "spec")) spec = can_wide && spec_applicable(a);
     if (!strcmp(e, "wide")) { spec = false; if (can_wide) lanes_a = kWave; }
     if (!strcmp(e, "packed")) { spec = false; lanes_a = p->lanes; }
@@ -1237,11 +1241,11 @@ static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
   // several chains into one (scripts/b_kernel_sweep.py, C3 topology: 2000 bootstraps 1.36 ms against 1.74 ms packed and
   // 1.81 ms speculative; 4000: 1.99 against 1.75; bundled 6-row pedigree, 8 lanes: 2000 bootstraps 1.98 against 1.90)
   if (!spec && a.dmode == 1 && p->opt.lanes_per_chain == 0 && p->lanes < kWave &&
-      (long long)p->W * p->B <= (3LL * c->cus / 4) * p->lanes && tree_on_wave_ok(p->N, p->topo.chain_stride, p->tree, p->opt.strict_order))
+      (long long)p->W * p->B <= (3LL * c->cus / 4) * p->lanes && tree_on_wave_ok(p->N, p->topo.K, p->topo.chain_stride, p->tree, p->opt.strict_order))
     lanes_b = kWave;
 #ifdef ABN_MEASUREMENT_KNOBS  // ABN_PHASE_B_KERNEL = spec | wide | packed
   if (const char* e = getenv("ABN_PHASE_B_KERNEL")) {
-    const bool can_wide = a.dmode == 1 && p->opt.lanes_per_chain == 0 && tree_on_wave_ok(p->N, p->topo.chain_stride, p->tree, p->opt.strict_order);
+    const bool can_wide = a.dmode == 1 && p->opt.lanes_per_chain == 0 && tree_on_wave_ok(p->N, p->topo.K, p->topo.chain_stride, p->tree, p->opt.strict_order);
     if (!strcmp(e, "spec")) spec = can_wide && spec_applicable(a);
     if (!strcmp(e, "wide")) { spec = false; if (can_wide) lanes_b = kWave; }
     if (!strcmp(e, "packed")) spec = false;

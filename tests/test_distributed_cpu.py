@@ -184,6 +184,23 @@ def test_reduction_tree_is_a_function_of_the_pedigree_only(abn):
     big = np.zeros((3000, 3))
     big[:, 1:] = 1.0
     assert abn.reduction_tree(big) == (64 | (3 << 8))
+    # at the LDS-residency boundary (tests/test_gpu_lds_boundary.py): the tree follows the footprint the launch uses,
+    # which counts the pedigree's distinct triples, not an upper bound from its row count
+    from test_gpu_lds_boundary import boundary_cases, boundary_pedigree
+
+    cases = boundary_cases()
+    for name, want in (("auto64_n1000_k200", canon), ("auto64_rmax16_largest", canon), ("auto64_rmax8_largest", canon),
+                       ("spec_under", canon), ("spec_over", canon), ("auto64_rmax16_rows_over", 64 | (3 << 8)),
+                       ("lanes16_under", 16), ("lanes16_over", 16 | (3 << 8)), ("lanes8_under", 8),
+                       ("lanes8_over", 8 | (3 << 8)), ("lanes32_rows_under", 32), ("lanes32_rows_over", 32 | (3 << 8)),
+                       ("strict16_under", 1), ("strict16_over", 1)):
+        n, tmax, k, opts, _ = cases[name]
+        gens = boundary_pedigree(n, tmax, k, seed=7)[:, :3]
+        assert abn.reduction_tree(gens, abn.default_options(**opts)) == want, name
+    # generations saturate at 127 (`as i8`): T = 350 is the topology of T = 127
+    wide = boundary_pedigree(1000, 127, 200, seed=7)[:, :3]
+    wide[wide == 127] = 350
+    assert abn.reduction_tree(wide) == canon
 
 
 def test_bench_refuses_a_gpu_count_it_cannot_run():

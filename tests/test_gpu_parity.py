@@ -417,6 +417,98 @@ def test_deep_pedigree_stream_mode_c5_shape(abn, gpu_ctx, oracle, stream_mode):
     plan.close()
 
 
+@pytest.mark.parametrize("stream_mode", (0, 1))
+def test_deep_pedigree_c5_fits_to_termination(abn, gpu_ctx, oracle, stream_mode):
+    """BASELINE C5's deep pedigree (N = 20100, streamed) with the default iteration budgets and fixed-point skip:
+    2 starts (max_iters_start = 10000) and 8 bootstraps (max_iters_boot = 1000) run to the end, bit-equal to the oracle
+    at the reported tree — status, iterations, evaluations, best vertices, the selected model, pred, resid and the
+    bootstrap rows.  Seed 31 is chosen so that both starts and all 8 bootstraps end by the convergence test (about 800 /
+    600 start iterations, 150-500 bootstrap iterations), not by the cap: the test covers termination, not truncation."""
+    from alphabeta_rs_amd import synthetic
+
+    ped, p0 = synthetic.c5_pedigree()
+    seed, S, B = 31, 2, 8
+    o = abn.default_options(seed=seed, stream_mode=stream_mode)
+    assert o.max_iters_start == 10000 and o.max_iters_boot == 1000 and o.no_fixed_point_skip == 0
+    plan = abn.Plan(gpu_ctx, ped[:, :3], 1, S, B, options=o)
+    plan.set_windows(ped[:, 3][None, :], np.array([p0]))
+    plan.run()
+    out = plan.download()
+    kinds = plan.last_kernels()
+    plan.close()
+    tree = abn.reduction_tree(ped[:, :3], o)
+    assert tree == 64 | (3 << 8) and kinds["starts"][0] == "stream" and kinds["boot"][0] == "stream", kinds
+    assert np.all(out["info_a"]["lanes"] == tree) and np.all(out["info_b"]["lanes"] == tree)
+    s0 = abn.gen_start_simplices(seed, 0, S, ped[:, 3].max())
+    fits = oracle.fit_batch(ped, p0, p0, 1.0, s0, 10000, lanes=tree, table=True, threads=16)
+    for f in ("status", "iters", "evals", "best_cost"):
+        assert np.array_equal(out["info_a"][f][0], fits[f]), f
+    best, info = gpu_ctx.fit_batch(ped, p0, p0, 1.0, s0, 10000, options=o)      # the start vertices themselves
+    assert np.all(info["lanes"] == tree)
+    _assert_fits_equal(best, info, fits)
+    k, model, pred, resid, _ = oracle.select_best(ped, p0, fits["best"])
+    assert out["best_start"][0] == k and np.array_equal(out["models"][0], model)
+    assert np.array_equal(out["pred"][0], pred) and np.array_equal(out["resid"][0], resid)
+    wraw, wres = oracle.boot_model(ped, model, pred, resid, p0, p0, 1.0, seed, 0, 0, B, max_iters=1000, lanes=tree,
+                                   table=True, threads=16)
+    assert np.array_equal(out["raw"][0], wraw)
+    for f in ("status", "iters", "evals"):
+        assert np.array_equal(out["info_b"][f][0], wres[f]), f
+    # to termination: a start and most bootstraps end by the convergence test, not by the iteration cap
+    assert np.any(fits["status"] == abn.FIT_CONVERGED), fits["status"]
+    assert np.sum(wres["status"] == abn.FIT_CONVERGED) > B // 2, wres["status"]
+
+
+def test_deep_pedigree_c5_full_window_properties(abn, gpu_ctx, oracle):
+    """One window of BASELINE C5 at its per-window load — 10 starts + 5000 bootstraps of the deep pedigree, default
+    options — through size-independent properties: idempotence, two half plans (boot_offset 0 and 2500) reproducing
+    the whole, every row finite and internally consistent, pred + resid = the observations, 16 sampled rows (the first
+    and the last among them) bit-equal to the oracle with their evaluation counts, and the skip counters consistent."""
+    from alphabeta_rs_amd import synthetic
+
+    ped, p0 = synthetic.c5_pedigree()
+    seed, S, B = 20260101, 10, 5000
+    o = abn.default_options(seed=seed)
+
+    def run(nb, boot_offset=0):
+        plan = abn.Plan(gpu_ctx, ped[:, :3], 1, S, nb, boot_offset=boot_offset, options=o)
+        plan.set_windows(ped[:, 3][None, :], np.array([p0]))
+        plan.run()
+        res, cnt = plan.download(), plan.counters()
+        plan.close()
+        return res, cnt
+
+    a, cnt = run(B)
+    b, _ = run(B)
+    for f in ("raw", "models", "pred", "resid", "best_start"):
+        assert np.array_equal(a[f], b[f]), f
+    assert a["info_a"].tobytes() == b["info_a"].tobytes() and a["info_b"].tobytes() == b["info_b"].tobytes()
+    h0, _ = run(B // 2, 0)
+    h1, _ = run(B // 2, B // 2)
+    for h in (h0, h1):
+        assert np.array_equal(h["models"], a["models"])
+    assert np.array_equal(np.concatenate([h0["raw"][0], h1["raw"][0]]), a["raw"][0])
+    assert np.concatenate([h0["info_b"][0], h1["info_b"][0]]).tobytes() == a["info_b"][0].tobytes()
+    raw = a["raw"][0]
+    assert np.all(np.isfinite(raw)) and np.all(a["info_b"]["status"] != abn.FIT_NONFINITE)
+    for row in raw:
+        assert np.array_equal(row, oracle.bootstrap_row(row[:4]))
+    assert np.allclose(a["pred"][0] + a["resid"][0], ped[:, 3], rtol=0, atol=1e-17)
+    tree = int(a["info_b"]["lanes"][0, 0])
+    assert tree == abn.reduction_tree(ped[:, :3], o) == 64 | (3 << 8)
+    rows = np.unique(np.concatenate([[0, B - 1], np.random.default_rng(8).choice(B, 14, replace=False)]))
+    for b0 in rows:
+        wraw, wres = oracle.boot_model(ped, a["models"][0], a["pred"][0], a["resid"][0], p0, p0, 1.0, seed, 0, int(b0),
+                                       1, lanes=tree, table=True, threads=1)
+        assert np.array_equal(raw[b0:b0 + 1], wraw), b0
+        assert a["info_b"]["evals"][0, b0] == wres["evals"][0], b0
+    # evaluation counters: "evals" counts every evaluation of every fit, skipped repetitions of a fixed point included
+    assert cnt["fits"] == S + B
+    assert cnt["evals"] == int(a["info_a"]["evals"].sum()) + int(a["info_b"]["evals"].sum())
+    assert 0 <= cnt["evals_skipped_boot"] <= int(a["info_b"]["evals"].sum())
+    assert 0 <= cnt["evals_skipped_starts"] <= int(a["info_a"]["evals"].sum())
+
+
 @pytest.mark.parametrize("stream_mode", [0, 1])
 def test_multi_window_stream_mode_matches_per_window_oracle(abn, gpu_ctx, oracle, stream_mode):
     """VERDICT r02, missing #2: several windows in stream mode — BASELINE C5's per-GPU shard is 63 windows of the deep
