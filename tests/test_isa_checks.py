@@ -8,36 +8,27 @@ comment); this test holds it in place: in every abn_fit_refill_kernel instantiat
 stores and before the sc1 entry store, and no trap instruction is left in the kernel (a lost FIFO entry sets an
 error word instead of aborting the process: the C-ABI never crashes).
 """
-import hashlib
+import importlib.util
 import re
-import subprocess
-import tempfile
 from pathlib import Path
 
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "alphabeta_rs_amd" / "csrc"
+
+def _load(name):
+    spec = importlib.util.spec_from_file_location(name, Path(__file__).resolve().parent / f"{name}.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+_device_isa = _load("_device_isa")
 MARK = "abn: parked state written through"
 
 
 @pytest.fixture(scope="module")
 def device_isa():
-    from alphabeta_rs_amd import build as B
-
-    try:
-        B.hipcc_path()
-    except RuntimeError as e:     # a CPU-only box without ROCm: nothing to check here (the GPU tier builds with hipcc)
-        pytest.skip(str(e))
-    h = hashlib.sha1()
-    for f in sorted(CSRC.glob("*")):
-        h.update(f.read_bytes())
-    out = Path(tempfile.gettempdir()) / f"abn_api_{h.hexdigest()[:16]}.s"
-    if not out.exists():
-        flags = [f for f in B.HIPCC_FLAGS if f not in ("-shared", "-fPIC", "-ldl")]
-        subprocess.run([B.hipcc_path(), "-S", "--cuda-device-only", *flags, "-Wno-unused-command-line-argument", "-o",
-                        str(out), str(CSRC / "abn_api.hip")], check=True, cwd=str(CSRC))
-    return out.read_text()
+    return _device_isa.device_isa()
 
 
 def functions(isa, needle):
