@@ -3,6 +3,7 @@
 // point returns ABN_ERR_NO_DEVICE / ABN_ERR_HIP.
 #include "abn_host.hpp"
 #include "abn_device.hpp"
+#include "abn_route.hpp"
 
 using namespace abn;
 
@@ -59,7 +60,7 @@ static int build_topology(const double* rows, int n, int stride, Topology& t) {
   t.T = tmax;
   t.TP = tmax + 1;
   t.KP = (t.K + 1) & ~1;
-  t.chain_stride = kPw * t.TP + t.KP + 4;  // power table, dt1t2 per triple, 4 per-chain constants
+  t.chain_stride = scratch_stride(t.TP, t.KP);
   return ABN_OK;
 }
 
@@ -77,328 +78,122 @@ static int upload_topology(abn_ctx* c, const Topology& t, DevTopology& d) {
   return ABN_OK;
 }
 
+// the topology fields every kernel's argument struct starts with
+template <class Args>
+static void fill_topology(Args& a, const Topology& t, const DevTopology& d) {
+  a.tri = d.tri.p;
+  a.tid = d.tid.p;
+  a.N = t.N;
+  a.K = t.K;
+  a.T = t.T;
+  a.TP = t.TP;
+}
+
 // ------------------------------------------------------------------------------------------------
-// launch configuration
+// launchers: abn_route.hpp decides, this executes
 // ------------------------------------------------------------------------------------------------
-constexpr size_t kDefaultDynLds = 64 * 1024;   // what a launch may ask for without opting in
-constexpr size_t kMaxDynLds = 160 * 1024;      // gfx950: the whole LDS of a CU, for the one-chain-per-workgroup kernels
-// A workgroup with one chain (stream-mode fits, selection, 64-lane cost) may need more than 64 KiB for pedigrees with
-// thousands of distinct triples: opt the kernel in (hipFuncAttributeMaxDynamicSharedMemorySize) before such a launch.
 static hipError_t allow_lds(const void* kernel, size_t lds) {
   if (lds <= kDefaultDynLds) return hipSuccess;
   return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
-constexpr size_t kLdsResidentMax = 40 * 1024;
-// Launch geometry in wavefronts (or chains) PER CU; the totals in the comments are the MI355X's (256 CUs).
-#ifndef ABN_PERSIST_WAVES_PER_CU
-#define ABN_PERSIST_WAVES_PER_CU 12
-#endif
-constexpr long long kPersistWavesPerCu = ABN_PERSIST_WAVES_PER_CU;  // a persistent launch: 3 per SIMD x 4 SIMDs (3072)
-// A launch that would just about fill the resident wavefronts (2048 < wavefronts <= 3072: C3's 10 000 bootstraps are 2500)
-// runs persistent on 2048 of them instead: the last fifth of the chains waits in the queue, finished groups refill and
-// time slicing evens out the tail (C3 phase B 2.58 -> 2.44 ms; same box: 2.61 -> 2.53 ms, 1792 / 2304 wavefronts 2.71 /
-// 2.82 ms; profiles/r03_persist_waves_sweep.txt)
-#ifndef ABN_PERSIST_WAVES_SMALL_PER_CU
-#define ABN_PERSIST_WAVES_SMALL_PER_CU 8
-#endif
-constexpr long long kPersistWavesSmallPerCu = ABN_PERSIST_WAVES_SMALL_PER_CU;
-static long long persist_waves(const abn_ctx* c) { return kPersistWavesPerCu * c->cus; }
-static long long persist_waves_small(const abn_ctx* c) { return kPersistWavesSmallPerCu * c->cus; }
-static long long persist_waves_for(const abn_ctx* c, long long blocks) {
-  return blocks > persist_waves(c) ? persist_waves(c) : persist_waves_small(c);
-}
-#ifndef ABN_PHASE_A_SPEC_PER_CU
-#define ABN_PHASE_A_SPEC_PER_CU 4
-#endif
-constexpr long long kPhaseASpecPerCu = ABN_PHASE_A_SPEC_PER_CU;  // chains per CU abn_fit_spec_kernel keeps resident at up to two rows per lane (spec_max_chains)
-constexpr long long kPhaseAWidePerCu = 24;                      // ... and up to which it uses one wavefront per chain (6144)
-// Time slicing of persistent launches (FitArgs::quantum): evaluations a chain runs before it yields to waiting chains.
-#ifndef ABN_QUANTUM
-#define ABN_QUANTUM 256
-#endif
-constexpr int kQuantum = ABN_QUANTUM;
-constexpr size_t kSliceStateMax = (size_t)256 << 20;  // bytes of parked state (32 doubles per chain of the launch)
-constexpr int kPhaseACap = 1000;  // first-pass iteration cap of the two-pass phase A
 
-// Lanes of a wavefront per chain.  Auto: by pedigree rows, then widened until the workgroup's LDS
-// (64/G chains x chain_stride doubles) leaves room for >= 8 workgroups per CU (160 KiB LDS).
-constexpr size_t kLdsTargetPerBlock = 20 * 1024;
-static int pick_lanes(int n, int requested, int chain_stride) {
-  if (requested == 8 || requested == 16 || requested == 32 || requested == 64) return requested;
-  int g = 64;
-  if (n <= 32) g = 8;
-  else if (n <= 128) g = 16;
-  else if (n <= 256) g = 32;
-  const size_t per_chain = ((size_t)chain_stride + (size_t)n) * sizeof(double);  // scratch + resident observations
-  while (g < 64 && (size_t)(kWave / g) * per_chain > kLdsTargetPerBlock) g *= 2;
-  return g;
-}
-// Doubles a chain's LDS region holds beyond the topology's scratch stride when its pedigree is resident: the
-// observations, the triple list of the K distinct triples (even: 16-byte aligned chains) and, in strict order, the rows'
-// terms.  The one residency footprint: launch_fit sizes its launches by it, and every decision taken before a launch
-// (plan, tree, kernel choice) asks it too, so that what is decided is what runs.
-static int resident_extra(int n, int k, int strict) {
-  return ((n + 1) & ~1) + (((k + 1) / 2 + 1) & ~1) + (strict ? ((n + 1) & ~1) : 0);
-}
-static bool resident_fits(int n, int k, int chain_stride, int lanes, int strict) {
-  return (size_t)(kWave / lanes) * (size_t)(chain_stride + resident_extra(n, k, strict)) * sizeof(double) <= kLdsResidentMax;
-}
-static bool fit_streams(int n, int k, int chain_stride, int lanes, int strict = 0);
-static bool tree_on_wave_ok(int n_rows, int k, int chain_stride, int tree, int strict);
-static bool spec_applicable(const FitArgs& a);
-static int launch_fit_spec(abn_ctx* c, FitArgs a, hipStream_t st);
-// The residual reduction tree (FitArgs::tree; abn_fit_info.lanes).  Auto (lanes_per_chain == 0) and the pedigree
-// LDS-resident: the canonical 64-accumulator tree, which every kernel — packed, one wavefront per chain, four
-// wavefronts per chain — runs at its native cost.  Streamed pedigrees and explicit lane counts: one accumulator per
-// lane of the packed kernel.
-static int pick_tree(int n, int k, int requested, int chain_stride, int lanes, int strict = 0) {
-  if (strict) return 1;  // serial row order (abn_options.strict_order): no tree
-  if (requested != 0 || fit_streams(n, k, chain_stride, lanes, strict)) return lanes;
-  return kTreeCanon;
-}
-static int pick_rmax(int n, int lanes) {
-  const int per = (n + lanes - 1) / lanes;
-  if (per <= 1) return 1;
-  if (per <= 2) return 2;
-  if (per <= 4) return 4;
-  if (per <= 8) return 8;
-  // 512 < N <= 1024: still LDS-resident with one wavefront per chain (scripts/n_sweep.py, N = 820, 2000 bootstraps:
-  // 5.25 -> 4.0 ms; 32 rows per lane with the triple ids in LDS gained nothing over streaming: not kept)
-  if (per <= 16 && lanes == 64) return 16;
-  return 0;  // stream mode
+// key -> kernel, written once: every fit-path instantiation the library holds (tests/test_kernel_matrix_census.py counts
+// them in the assembly), those no route reaches included (tests/_kernel_matrix.py: UNREACHABLE)
+struct KernelEntry {
+  KernelKey key;
+  const void* fn;
+};
+#define ABN_FIT(G, R, TP, ST) {{kFamFit, G, R, TP, ST, false}, reinterpret_cast<const void*>(&abn_fit_kernel<G, R, TP, ST>)}
+#define ABN_FIT_ROWS(G, TP, ST) ABN_FIT(G, 1, TP, ST), ABN_FIT(G, 2, TP, ST), ABN_FIT(G, 4, TP, ST), ABN_FIT(G, 8, TP, ST), ABN_FIT(G, 0, TP, ST)
+#define ABN_FIT_G(G)                                                                                                   \
+  ABN_FIT_ROWS(G, false, false), ABN_FIT(G, -1, false, false), ABN_FIT_ROWS(G, true, false), ABN_FIT(G, -1, true, false), \
+      ABN_FIT_ROWS(G, false, true)
+#define ABN_REFILL(G, R) {{kFamRefill, G, R, false, false, false}, reinterpret_cast<const void*>(&abn_fit_refill_kernel<G, R>)}
+#define ABN_REFILL_G(G) ABN_REFILL(G, 1), ABN_REFILL(G, 2), ABN_REFILL(G, 4), ABN_REFILL(G, 8)
+#define ABN_SPEC(R, ST, RS) {{kFamSpec, kWave, R, false, ST, RS}, reinterpret_cast<const void*>(&abn_fit_spec_kernel<R, ST, RS>)}
+#define ABN_SPEC_R(R) ABN_SPEC(R, false, false), ABN_SPEC(R, true, false), ABN_SPEC(R, false, true)
+#define ABN_COST(G) {{kFamCost, G, 0, false, false, false}, reinterpret_cast<const void*>(&abn_cost_kernel<G>)}
+static const KernelEntry kKernels[] = {
+    ABN_FIT_G(8), ABN_FIT_G(16), ABN_FIT_G(32), ABN_FIT_G(64),
+    ABN_FIT(64, 16, false, false), ABN_FIT(64, 16, true, false), ABN_FIT(64, 16, false, true),  // one wavefront per chain only
+    ABN_REFILL_G(8), ABN_REFILL_G(16), ABN_REFILL_G(32), ABN_REFILL_G(64),
+    ABN_SPEC_R(1), ABN_SPEC_R(2), ABN_SPEC_R(4), ABN_SPEC_R(8),
+    ABN_COST(8), ABN_COST(16), ABN_COST(32), ABN_COST(64)};
+static_assert(sizeof(kKernels) / sizeof(kKernels[0]) == 103, "the census of tests/test_kernel_matrix_census.py");
+
+template <class Args>
+static int launch_route(abn_ctx* c, const LaunchRoute& r, const Args& a, hipStream_t st) {
+  const void* fn = nullptr;
+  for (const KernelEntry& e : kKernels)
+    if (e.key == r.key) fn = e.fn;
+  if (!fn) return set_err(c, ABN_ERR_INVALID_ARG, "internal: no such kernel instantiation");
+  HIPCHK(c, allow_lds(fn, r.lds));
+  void* argv[] = {const_cast<Args*>(&a)};
+  HIPCHK(c, hipLaunchKernel(fn, dim3(r.grid), dim3(r.block), argv, r.lds, st));
+  return ABN_OK;
 }
 
-template <int G, bool TP, bool STRICT>
-static hipError_t launch_fit_gt(const FitArgs& a, int rmax, dim3 grid, size_t lds, hipStream_t s) {
-  switch (rmax) {
-    case 1: hipLaunchKernelGGL((abn_fit_kernel<G, 1, TP, STRICT>), grid, dim3(kWave), lds, s, a); break;
-    case 2: hipLaunchKernelGGL((abn_fit_kernel<G, 2, TP, STRICT>), grid, dim3(kWave), lds, s, a); break;
-    case 4: hipLaunchKernelGGL((abn_fit_kernel<G, 4, TP, STRICT>), grid, dim3(kWave), lds, s, a); break;
-    case 8: hipLaunchKernelGGL((abn_fit_kernel<G, 8, TP, STRICT>), grid, dim3(kWave), lds, s, a); break;
-    case 16:  // one wavefront per chain only (pick_rmax)
-      hipLaunchKernelGGL((abn_fit_kernel<64, 16, TP, STRICT>), grid, dim3(kWave), lds, s, a);
-      break;
-    case -1:
-      if (STRICT) {  // strict order has one stream variant (chunks of 8 G rows)
-        if (hipError_t e = allow_lds(reinterpret_cast<const void*>(&abn_fit_kernel<G, 0, TP, STRICT>), lds)) return e;
-        hipLaunchKernelGGL((abn_fit_kernel<G, 0, TP, STRICT>), grid, dim3(kWave), lds, s, a);
-        break;
-      }
-      if (hipError_t e = allow_lds(reinterpret_cast<const void*>(&abn_fit_kernel<G, -1, TP, false>), lds)) return e;
-      hipLaunchKernelGGL((abn_fit_kernel<G, -1, TP, false>), grid, dim3(kWave), lds, s, a);
-      break;
-    default:
-      if (hipError_t e = allow_lds(reinterpret_cast<const void*>(&abn_fit_kernel<G, 0, TP, STRICT>), lds)) return e;
-      hipLaunchKernelGGL((abn_fit_kernel<G, 0, TP, STRICT>), grid, dim3(kWave), lds, s, a);
-      break;
-  }
-  return hipGetLastError();
-}
-template <int G>
-static hipError_t launch_fit_refill(const FitArgs& a, int rmax, dim3 grid, size_t lds, hipStream_t s) {
-  switch (rmax) {
-    case 1: hipLaunchKernelGGL((abn_fit_refill_kernel<G, 1>), grid, dim3(kWave), lds, s, a); break;
-    case 2: hipLaunchKernelGGL((abn_fit_refill_kernel<G, 2>), grid, dim3(kWave), lds, s, a); break;
-    case 4: hipLaunchKernelGGL((abn_fit_refill_kernel<G, 4>), grid, dim3(kWave), lds, s, a); break;
-    default: hipLaunchKernelGGL((abn_fit_refill_kernel<G, 8>), grid, dim3(kWave), lds, s, a); break;
-  }
-  return hipGetLastError();
-}
-template <int G>
-static hipError_t launch_fit_g(const FitArgs& a, int rmax, dim3 grid, size_t lds, hipStream_t s, bool refill) {
-  const bool twopass = a.iter_cap > 0 || a.resume != 0;
-  if (refill) return launch_fit_refill<G>(a, rmax, grid, lds, s);
-  if (a.strict) return launch_fit_gt<G, false, true>(a, rmax, grid, lds, s);  // launch_fit: never two-pass, never persistent
-  return twopass ? launch_fit_gt<G, true, false>(a, rmax, grid, lds, s) : launch_fit_gt<G, false, false>(a, rmax, grid, lds, s);
-}
-
-// `a.chain_stride` must be the topology's scratch stride (kPw*TP + KP + 4, even); the resident variant adds an even
-// number of doubles (observations + triple list): every chain's region stays 16-byte aligned for load_matrix.
+// Runs a.W x a.C chains as route_launch decides.  `a` carries the topology's scratch stride and the buffers `offer`
+// promises (queue; park_*, state, susp_list, slice_status); stride, tree, quantum, tail and pass are the route's.
 // kind (nullable): the ABN_KERNEL_* code of what was launched (PERSISTENT: a.slice_status then counts its fits)
-static int launch_fit(abn_ctx* c, FitArgs a, int lanes, hipStream_t st, int* kind = nullptr) {
-  if (kind) *kind = ABN_KERNEL_NONE;
-  const FitArgs a0 = a;  // as the caller set it (topology's scratch stride): the tail's resume launch starts from it
+static int launch_fit(abn_ctx* c, const PedigreeRoute& pr, const PhaseRoute& ph, FitArgs a, const LaunchOffer& offer,
+                      hipStream_t st, int* kind = nullptr) {
   const long long chains = (long long)a.W * a.C;
-  if (chains <= 0) return ABN_OK;
-  const int ng = kWave / lanes;
-  int rmax = pick_rmax(a.N, lanes);
-  // the reduction tree: the canonical one (any resident kernel) or one accumulator per lane; strict order: none (serial)
-  if (a.strict) {
-    if (a.iter_cap > 0 || a.resume != 0)
-      return set_err(c, ABN_ERR_INVALID_ARG, "internal: strict order has no two-pass variant");
-    a.tree = 1;
-    a.queue = nullptr;  // no persistent variant either
-  } else if (a.tree != kTreeCanon) {
-    a.tree = lanes;
-  }
-  if (rmax > 0) {  // resident: observations + this chain's triple list (+ strict order: the rows' terms) next to the scratch
-    if (!resident_fits(a.N, a.K, a.chain_stride, lanes, a.strict)) rmax = 0;
-    else a.chain_stride += resident_extra(a.N, a.K, a.strict);
-  }
-  if (rmax <= 0 && a.tree == kTreeCanon)
-    return set_err(c, ABN_ERR_INVALID_ARG, "internal: the canonical tree needs an LDS-resident pedigree");
-  if (rmax <= 0 && a.strict) a.chain_stride += kStrictRowsPerLane * lanes;  // one chunk of terms
-  // stream mode: rows shorter than one trip of the deep loop (kStreamBlocks x 4 rows x lanes) use the pair-loop variant
-  if (rmax == 0 && a.N < 2 * kStreamBlocks * kStreamVec * lanes) rmax = -1;
-  const size_t lds = (size_t)ng * (size_t)a.chain_stride * sizeof(double);
-  if (lds > (lanes == kWave ? kMaxDynLds : kDefaultDynLds))
-    return set_err(c, ABN_ERR_INVALID_ARG, "pedigree needs more LDS per workgroup than supported (T or K too large)");
-  long long blocks = (chains + ng - 1) / ng;
-  if (blocks > 0x7fffffffLL || chains > 0x7fffffffLL)
-    return set_err(c, ABN_ERR_INVALID_ARG, "too many chains for one launch");
-  // More wavefronts than the GPU holds at once and several chains per wavefront: the persistent kernel, whose
-  // groups take the next chain from a queue when their fit ends (abn_fit_refill_kernel)
-  const bool refill = a.queue != nullptr && rmax > 0 && ng > 1 && a.iter_cap == 0 && a.resume == 0 &&
-                      blocks > persist_waves_small(c);
-  if (refill) blocks = persist_waves_for(c, blocks);
-  if (!refill) a.quantum = 0;
-  // The quantum grows with the queue's depth (chains per lane group of the launch): a deep queue keeps the GPU full whatever
-  // the slicing, every park costs a wavefront ≈ 10 µs of dependent memory traffic, and the tail goes to the speculative
-  // kernel anyway; a shallow one needs short slices to start everybody early.  scripts/quantum_sweep.sh, profiles/r04_quantum_sweep.txt:
-  // C3 (1.2 chains per group) is best at 256, the C4 shard (2.0) at 256-384, the metaprofile shape (2.4) at 384-768, C4's
-  // 200 000 chains (16) at >= 1024.  Results do not depend on it (the persistent kernel is schedule-independent).
-  if (refill && a.quantum > 0) {
-    const long long q = (5LL * kQuantum * chains / (blocks * ng) / 8 + 63) & ~63LL;
-    a.quantum = (int)std::min<long long>(4LL * kQuantum, std::max<long long>(kQuantum, q));
-  }
-#ifdef ABN_MEASUREMENT_KNOBS  // scripts/prio_sweep.sh: wave priority by chain age, wavefronts and quantum of the persistent launch
-  if (refill) {
+  LaunchRoute r = route_launch(pr, ph, chains, c->cus, offer);
+  if (kind) *kind = r.kind;
+  if (r.status) return set_err(c, r.status, r.error);
+  if (r.kind == ABN_KERNEL_NONE) return ABN_OK;
+  const bool persistent = r.kind == ABN_KERNEL_PERSISTENT;
+#ifdef ABN_MEASUREMENT_KNOBS  // scripts/prio_sweep.sh, tail_sweep.sh: wave priority by chain age, wavefronts, quantum and tail of the persistent launch
+  if (persistent) {
     if (const char* e = getenv("ABN_PRIO")) sscanf(e, "%d,%d,%d,%d", &a.prio_mode, &a.prio_t[0], &a.prio_t[1], &a.prio_t[2]);
     if (const char* e = getenv("ABN_PERSIST_WAVES_SMALL_ENV")) {
-      if (blocks == persist_waves_small(c)) blocks = std::max(64, atoi(e));
+      if (r.grid == persist_waves_small(c->cus)) r.grid = (unsigned)std::max(64, atoi(e));
+      if (r.tail_cap > 0) r.tail_cap = tail_cap_for(pr, r.grid, c->cus);
     }
     if (const char* e = getenv("ABN_QUANTUM_ENV")) {
-      if (a.quantum > 0) a.quantum = std::max(16, atoi(e));
+      if (r.quantum > 0) r.quantum = std::max(16, atoi(e));
     }
     // tests/test_gpu_parity.py::test_lost_fifo_entry_is_an_error_at_sync: the first parked chain of FIFO shard 0 is never
     // published — the launch must end (bounded spin), and every way of taking results must report ABN_ERR_HIP
     if (const char* e = getenv("ABN_DROP_FIFO_ENTRY")) a.drop_entry = atoi(e);
+    if (const char* e = getenv("ABN_TAIL_CAP")) {
+      if (r.tail_cap > 0) r.tail_cap = (int)std::min<long long>(chains, std::max(0, atoi(e)));
+    }
   }
 #endif
-  // Tail hand-over (FitArgs::tail_cap): the last chains of a time-sliced launch finish on four wavefronts each instead of one
-  // by one on an emptying GPU at the packed kernel's step time (metaprofile shape, phase A: 12 of 17 ms were such a tail).
-  // As many as abn_fit_spec_kernel keeps resident (four per CU at up to two rows per lane), twice that behind the deep queues
-  // of the 12-wavefronts-per-CU geometry, where the later workgroups start as the first end (scripts/tail_sweep.sh,
-  // profiles/r04_tail_sweep.txt: C3 is best at 1024, the C4 shard and the metaprofile shape at 2048-3072: +3 % / +2 %).
-  // Needs the speculative kernel to apply to the pedigree.
-  a.tail_cap = 0;
-  if (refill && a.quantum > 0 && a.slice_status && a.susp_list && a.tree == kTreeCanon) {
-    FitArgs probe = a0;
-    probe.tree = kTreeCanon;
-    if (spec_applicable(probe))
-      a.tail_cap = (int)((pick_rmax(a.N, kWave) <= 2 ? (blocks == persist_waves(c) ? 8LL : 4LL) : 2LL) * c->cus);
-#ifdef ABN_MEASUREMENT_KNOBS
-    if (const char* e = getenv("ABN_TAIL_CAP")) a.tail_cap = a.tail_cap > 0 ? (int)std::min<long long>(chains, std::max(0, atoi(e))) : 0;
-#endif
-    a.susp_count = reinterpret_cast<int*>(a.slice_status + 3);
-  }
-  if (refill && a.slice_status) HIPCHK(c, hipMemsetAsync(a.slice_status, 0, 4 * sizeof(unsigned), st));
-  if (kind)
-    *kind = refill ? ABN_KERNEL_PERSISTENT
-            : rmax <= 0 ? ABN_KERNEL_STREAM
-            : (a.iter_cap > 0 || a.resume != 0) ? ABN_KERNEL_TWO_PASS : ABN_KERNEL_RESIDENT;
+  a.chain_stride = r.chain_stride;
+  a.tree = r.tree;
+  a.iter_cap = offer.pass == 1 ? kPhaseACap : 0;
+  a.resume = offer.pass == 2 ? 1 : 0;
+  a.quantum = r.quantum;
+  a.tail_cap = r.tail_cap;
+  if (!persistent) a.queue = nullptr;
+  if (a.tail_cap > 0) a.susp_count = reinterpret_cast<int*>(a.slice_status + 3);
+  if (persistent && a.slice_status) HIPCHK(c, hipMemsetAsync(a.slice_status, 0, 4 * sizeof(unsigned), st));
   if (a.quantum > 0) {  // empty FIFO of parked chains: entries -1, head = tail = 0
     HIPCHK(c, hipMemsetAsync(a.parked, 0xff, (size_t)kParkShards * a.park_cap * sizeof(int), st));
     HIPCHK(c, hipMemsetAsync(a.park_ht, 0, (size_t)kParkShards * kParkHeaderInts * sizeof(unsigned), st));
   }
-  dim3 grid((unsigned)blocks);
-  hipError_t e;
-  switch (lanes) {
-    case 8: e = launch_fit_g<8>(a, rmax, grid, lds, st, refill); break;
-    case 16: e = launch_fit_g<16>(a, rmax, grid, lds, st, refill); break;
-    case 32: e = launch_fit_g<32>(a, rmax, grid, lds, st, refill); break;
-    default: e = launch_fit_g<64>(a, rmax, grid, lds, st, refill); break;
-  }
-  HIPCHK(c, e);
+  if (int rc = launch_route(c, r, a, st)) return rc;
   if (a.tail_cap > 0) {  // the parked tail (possibly empty: workgroups beyond *susp_count leave at once)
-    FitArgs r = a0;
-    r.tree = kTreeCanon;
-    r.queue = nullptr;
-    r.quantum = 0;
-    r.spec_resume = 1;
-    r.tail_cap = a.tail_cap;
-    r.state = a.state;
-    r.susp_list = a.susp_list;
-    r.susp_count = a.susp_count;
-    r.slice_status = a.slice_status;
-    if (int rc = launch_fit_spec(c, r, st)) return rc;
+    const LaunchRoute t = route_tail_resume(pr, a.tail_cap);
+    a.chain_stride = t.chain_stride;
+    a.tree = t.tree;
+    a.queue = nullptr;
+    a.quantum = 0;
+    a.spec_resume = 1;
+    return launch_route(c, t, a, st);
   }
   return ABN_OK;
 }
 
-// true when launch_fit will use the stream variant for this pedigree (n rows, k distinct triples) / lane count: the same
-// footprint launch_fit computes (resident_fits), so that what a plan decides (and validates) at abn_plan_create is what runs.
-static bool fit_streams(int n, int k, int chain_stride, int lanes, int strict) {
-  if (pick_rmax(n, lanes) == 0) return true;
-  return !resident_fits(n, k, chain_stride, lanes, strict);
-}
-
-// Speculative kernel (phase A; three evaluation wavefronts + a bookkeeping wavefront per chain): resident mode
-// with one wavefront per candidate only.
-// Chains up to which the speculative kernel is used.  What the GPU holds at once: four workgroups per CU for pedigrees of up
-// to two rows per lane (1024 chains on the MI355X), three beyond (768); workgroups beyond that start as earlier ones end.
-// Phase B (bootstrap chains: similar lengths) up to 1.5 x / 1 x of that; phase A (start chains from random points: lengths
-// differ several-fold, so the queue behind the resident chains drains into slots that free early) up to 4 x / 2.7 x.
-// Speculative / one wavefront per chain / packed, ms (scripts/b_kernel_sweep.py, scripts/a_kernel_sweep.py,
-// profiles/r04_b_kernel_sweep.txt, r04_a_kernel_sweep.txt):
-//   phase B, C3 topology: 1000 chains 0.76 / 1.03 / 1.60, 1500: 1.04 / 1.15 / 1.16, 2000: 1.28 / 1.31 / 1.31, 3000: 1.70 / 1.49 / 1.48;
-//            6-row pedigree 1500: 1.44 / 1.95 / 1.95, 3000: 1.95 / 2.43 / 2.26; 351-row pedigree 500: 1.21 / 1.95 / 1.95, 1000: 2.14 / 1.97 / 1.96
-//   phase A, C3 topology: 1000 chains 1.89 / 2.94 / 4.80, 2000: 2.71 / 3.31 / 4.94, 3000: 3.45 / 3.67 / 5.06, 4000: 4.21 / 4.40 / 6.13,
-//            5000: 5.10 / 5.16 / 6.46, 6000: 6.15 / 5.75 / 6.43; 351-row pedigree 1000: 3.25 / 3.77 / 3.78, 2000: 6.11 / 6.43 / 6.31, 3000: 6.30 / 6.55 / 6.54
-static long long spec_max_chains(const abn_ctx* c, int n_rows, int phase) {
-  const long long mx = kPhaseASpecPerCu * c->cus;   // 1024
-  const bool small = pick_rmax(n_rows, kWave) <= 2;
-  if (phase == 0) return small ? mx * 4 : mx * 2;
-  return small ? mx * 3 / 2 : mx * 3 / 4;
-}
-
-// a wavefront per chain runs the canonical tree (or, strict order, the serial sum) whenever the pedigree is LDS-resident
-// at 64 lanes per chain; an explicit lanes_per_chain tree only when it IS 64 lanes
-static bool tree_on_wave_ok(int n_rows, int k, int chain_stride, int tree, int strict) {
-  if (!strict && tree != kTreeCanon) return tree == kWave;
-  return !fit_streams(n_rows, k, chain_stride, kWave, strict);
-}
-
-static bool spec_applicable(const FitArgs& a) {
-  if (a.dmode == 2) return false;  // resident observations only (starts, or bootstraps gathered through the index row)
-  const int rmax = pick_rmax(a.N, kWave);
-  if (rmax == 0 || rmax > 8) return false;  // 16 rows per lane: the plain resident kernel
-  if (!tree_on_wave_ok(a.N, a.K, a.chain_stride, a.tree, a.strict)) return false;
-  const int np = ((a.N + 1) & ~1) * (a.strict ? 2 : 1);   // observations (+ strict order: the rows' terms)
-  return (3 * (size_t)(a.chain_stride + np) + kSpecCommDoubles) * sizeof(double) <= kLdsResidentMax;
-}
-
-static int launch_fit_spec(abn_ctx* c, FitArgs a, hipStream_t st) {
-  // spec_resume: one workgroup per slot of the tail list (at most tail_cap chains were handed over)
-  const long long chains = a.spec_resume ? (long long)a.tail_cap : (long long)a.W * a.C;
-  if (chains <= 0) return ABN_OK;
-  const int rmax = pick_rmax(a.N, kWave);
-  a.chain_stride += ((a.N + 1) & ~1) * (a.strict ? 2 : 1);
-  const size_t lds = (3 * (size_t)a.chain_stride + kSpecCommDoubles) * sizeof(double);
-  dim3 grid((unsigned)chains), block(4 * kWave);
-  a.tree = a.strict ? 1 : kTreeCanon;  // spec_applicable admitted it
-  if (a.spec_resume) {  // the tail of a persistent launch (never strict)
-    switch (rmax) {
-      case 1: hipLaunchKernelGGL((abn_fit_spec_kernel<1, false, true>), grid, block, lds, st, a); break;
-      case 2: hipLaunchKernelGGL((abn_fit_spec_kernel<2, false, true>), grid, block, lds, st, a); break;
-      case 4: hipLaunchKernelGGL((abn_fit_spec_kernel<4, false, true>), grid, block, lds, st, a); break;
-      default: hipLaunchKernelGGL((abn_fit_spec_kernel<8, false, true>), grid, block, lds, st, a); break;
-    }
-  } else if (a.strict) {
-    switch (rmax) {
-      case 1: hipLaunchKernelGGL((abn_fit_spec_kernel<1, true>), grid, block, lds, st, a); break;
-      case 2: hipLaunchKernelGGL((abn_fit_spec_kernel<2, true>), grid, block, lds, st, a); break;
-      case 4: hipLaunchKernelGGL((abn_fit_spec_kernel<4, true>), grid, block, lds, st, a); break;
-      default: hipLaunchKernelGGL((abn_fit_spec_kernel<8, true>), grid, block, lds, st, a); break;
-    }
-  } else {
-    switch (rmax) {
-      case 1: hipLaunchKernelGGL((abn_fit_spec_kernel<1, false>), grid, block, lds, st, a); break;
-      case 2: hipLaunchKernelGGL((abn_fit_spec_kernel<2, false>), grid, block, lds, st, a); break;
-      case 4: hipLaunchKernelGGL((abn_fit_spec_kernel<4, false>), grid, block, lds, st, a); break;
-      default: hipLaunchKernelGGL((abn_fit_spec_kernel<8, false>), grid, block, lds, st, a); break;
-    }
-  }
+// one model per workgroup, then one workgroup per window over its S sums
+static int launch_select(abn_ctx* c, const SelectArgs& s, size_t lds, hipStream_t st) {
+  HIPCHK(c, allow_lds(reinterpret_cast<const void*>(&abn_select_lse_kernel), lds));
+  HIPCHK(c, allow_lds(reinterpret_cast<const void*>(&abn_select_kernel), lds));
+  hipLaunchKernelGGL(abn_select_lse_kernel, dim3((unsigned)((long long)s.W * s.S)), dim3(kWave), lds, st, s);
+  hipLaunchKernelGGL(abn_select_kernel, dim3((unsigned)s.W), dim3(kWave), lds, st, s);
   HIPCHK(c, hipGetLastError());
   return ABN_OK;
 }
@@ -468,10 +263,7 @@ extern "C" int abn_reduction_tree(const abn_options* opts, const double* generat
   Topology t;
   const int rc = build_topology(generations, n_rows, 3, t);
   if (rc) return rc;
-  const int lanes = pick_lanes(n_rows, o.lanes_per_chain, t.chain_stride);
-  *tree = o.strict_order ? 1
-          : fit_streams(n_rows, t.K, t.chain_stride, lanes) ? (lanes | ((kStreamVec - 1) << 8))
-                                                            : pick_tree(n_rows, t.K, o.lanes_per_chain, t.chain_stride, lanes);
+  *tree = route_pedigree(n_rows, t.K, t.T, o.lanes_per_chain, o.strict_order).reported_tree;
   return ABN_OK;
 }
 
@@ -527,8 +319,8 @@ extern "C" int abn_device_info(const abn_ctx* c, int32_t* out4) {
   if (!c || !out4) return ABN_ERR_INVALID_ARG;
   out4[0] = c->cus;
   out4[1] = (int32_t)(c->lds_per_cu / 1024);
-  out4[2] = (int32_t)persist_waves(c);
-  out4[3] = (int32_t)persist_waves_small(c);
+  out4[2] = (int32_t)persist_waves(c->cus);
+  out4[3] = (int32_t)persist_waves_small(c->cus);
   return ABN_OK;
 }
 
@@ -682,15 +474,11 @@ extern "C" int abn_cost_batch(abn_ctx* c, const abn_options* opts, const double*
   if (dt1t2) HIPCHK(c, ddt.alloc((size_t)m * (size_t)N));
   if (p_uu_inf) HIPCHK(c, dpuu.alloc((size_t)m));
 
-  const int lanes = o.strict_order ? 64 : pick_lanes(N, o.lanes_per_chain, t.chain_stride);
-  const int ng = kWave / lanes;
+  const PedigreeRoute pr = route_pedigree(N, t.K, t.T, o.lanes_per_chain, o.strict_order);
+  if (pr.cost_refusal) return set_err(c, ABN_ERR_INVALID_ARG, pr.cost_refusal);
+  const int ng = kWave / pr.cost_lanes;
   CostArgs a{};
-  a.tri = dt.tri.p;
-  a.tid = dt.tid.p;
-  a.N = N;
-  a.K = t.K;
-  a.T = t.T;
-  a.TP = t.TP;
+  fill_topology(a, t, dt);
   a.chain_stride = t.chain_stride;
   a.p_uu0 = p_uu0;
   a.eqp = eqp;
@@ -703,25 +491,20 @@ extern "C" int abn_cost_batch(abn_ctx* c, const abn_options* opts, const double*
   a.dmode = idx ? 1 : 0;
   a.cand = dcand.p;
   a.M = m;
-  a.strict = o.strict_order ? 1 : 0;
-  a.tree = o.strict_order ? lanes : pick_tree(N, t.K, o.lanes_per_chain, t.chain_stride, lanes);
+  a.strict = pr.strict;
+  a.tree = pr.cost_tree;
   a.cost = dcost.p;
   a.dt = ddt.p;
   a.puu = dpuu.p;
-  size_t lds = ((size_t)ng * t.chain_stride + (o.strict_order ? kSelChunk : 0)) * sizeof(double);
-  if (lds > (lanes == kWave ? kMaxDynLds : kDefaultDynLds))
-    return set_err(c, ABN_ERR_INVALID_ARG, "pedigree needs more LDS than supported");
-  if (lanes == kWave) HIPCHK(c, allow_lds(reinterpret_cast<const void*>(&abn_cost_kernel<64>), lds));
   const long long blocks = (m + ng - 1) / ng;
   if (blocks > 0x7fffffffLL) return set_err(c, ABN_ERR_INVALID_ARG, "too many candidates");
-  dim3 grid((unsigned)blocks);
-  switch (lanes) {
-    case 8: hipLaunchKernelGGL(abn_cost_kernel<8>, grid, dim3(kWave), lds, c->stream, a); break;
-    case 16: hipLaunchKernelGGL(abn_cost_kernel<16>, grid, dim3(kWave), lds, c->stream, a); break;
-    case 32: hipLaunchKernelGGL(abn_cost_kernel<32>, grid, dim3(kWave), lds, c->stream, a); break;
-    default: hipLaunchKernelGGL(abn_cost_kernel<64>, grid, dim3(kWave), lds, c->stream, a); break;
-  }
-  HIPCHK(c, hipGetLastError());
+  LaunchRoute r{};
+  r.key = {kFamCost, pr.cost_lanes, 0, false, false, false};
+  r.grid = (unsigned)blocks;
+  r.block = kWave;
+  r.lds = pr.cost_lds;
+  rc = launch_route(c, r, a, c->stream);
+  if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(cost, dcost.p, dcost.bytes(), hipMemcpyDeviceToHost, c->stream));
   if (dt1t2) HIPCHK(c, hipMemcpyAsync(dt1t2, ddt.p, ddt.bytes(), hipMemcpyDeviceToHost, c->stream));
   if (p_uu_inf) HIPCHK(c, hipMemcpyAsync(p_uu_inf, dpuu.p, dpuu.bytes(), hipMemcpyDeviceToHost, c->stream));
@@ -741,7 +524,7 @@ extern "C" int abn_fit_batch(abn_ctx* c, const abn_options* opts, const double* 
   if (f == 0) return ABN_OK;
   if (const char* oe = options_error(resolve(opts))) return set_err(c, ABN_ERR_INVALID_ARG, oe);
   const abn_options o = resolve_for(opts, n_rows);
-  if (max_iters < 0 || max_iters > (1 << 28)) return set_err(c, ABN_ERR_INVALID_ARG, "max_iters must be in 0 .. 2^28");
+  if (max_iters > (1 << 28)) return set_err(c, ABN_ERR_INVALID_ARG, "max_iters must be in 0 .. 2^28");
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
   Topology t;
@@ -773,13 +556,9 @@ extern "C" int abn_fit_batch(abn_ctx* c, const abn_options* opts, const double* 
   HIPCHK(c, hipMemcpyAsync(dscal.p, scal, sizeof scal, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(dinfo.p, 0, dinfo.bytes(), c->stream));
 
+  const PedigreeRoute pr = route_pedigree(N, t.K, t.T, o.lanes_per_chain, o.strict_order);
   FitArgs a{};
-  a.tri = dt.tri.p;
-  a.tid = dt.tid.p;
-  a.N = N;
-  a.K = t.K;
-  a.T = t.T;
-  a.TP = t.TP;
+  fill_topology(a, t, dt);
   a.chain_stride = t.chain_stride;
   a.p_uu = dscal.p;
   a.eqp = dscal.p + 1;
@@ -806,10 +585,8 @@ extern "C" int abn_fit_batch(abn_ctx* c, const abn_options* opts, const double* 
   a.best = dbest.p;
   a.info = dinfo.p;
   a.raw = nullptr;
-  const int lanes = pick_lanes(N, o.lanes_per_chain, t.chain_stride);
-  a.strict = o.strict_order ? 1 : 0;
-  a.tree = pick_tree(N, t.K, o.lanes_per_chain, t.chain_stride, lanes, a.strict);
-  rc = launch_fit(c, a, lanes, c->stream);
+  a.strict = pr.strict;
+  rc = launch_fit(c, pr, PhaseRoute{false, pr.lanes, false}, a, LaunchOffer{}, c->stream);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(best, dbest.p, dbest.bytes(), hipMemcpyDeviceToHost, c->stream));
   if (info) HIPCHK(c, hipMemcpyAsync(info, dinfo.p, dinfo.bytes(), hipMemcpyDeviceToHost, c->stream));
@@ -827,9 +604,7 @@ struct abn_plan {
   DevTopology dtopo;
   int N = 0, W = 0, S = 0, B = 0;
   uint32_t window_offset = 0, boot_offset = 0;
-  int lanes = 16;    // lanes per chain of the packed (throughput) kernels
-  int tree = 32;     // the pedigree's reduction tree (accumulators): lanes or 2 x lanes (pick_tree)
-  int lanes_a = 64;  // phase A (few chains: latency-bound, one wavefront per chain is fastest)
+  PedigreeRoute route{};  // lanes, tree and what the pedigree admits (abn_route.hpp)
   std::vector<uint32_t> wid_host;  // Philox window ids (abn_plan_set_window_ids); empty = window_offset + w
   DevBuf<uint32_t> wid;
   bool windows_set = false, phase_a_done = false, ran_a = false, ran_b = false;
@@ -897,27 +672,12 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
     delete p;
     return set_err(c, rc, abn_status_string(rc));
   }
-  p->lanes = pick_lanes(n_rows, p->opt.lanes_per_chain, p->topo.chain_stride);
-  p->tree = pick_tree(n_rows, p->topo.K, p->opt.lanes_per_chain, p->topo.chain_stride, p->lanes, p->opt.strict_order);
-  p->lanes_a = p->lanes;
-  // Phase A is latency-bound while its chains fit the machine about twice over (3 wavefronts x 1024 SIMDs): one
-  // wavefront per chain then beats packing several chains into a wavefront, and below ~1000 chains the
-  // four-wavefront speculative kernel beats both (scripts/phase_a_sweep.py, C3 topology: 1000 chains 2.6 / 3.2 /
-  // 4.6 ms for speculative / 64 lanes / 16 lanes, 1500 chains 4.2 / 3.4 / 4.8; 4000 chains - / 4.6 / 5.9 ms;
-  // 8000 chains - / 7.7 / 7.0 ms)
-  // The reduction tree stays the pedigree's (p->tree) whichever kernel runs: results do not depend on the size of
-  // the launch, hence not on how a job is sharded over GPUs.
-  if (p->opt.lanes_per_chain == 0 && (long long)n_windows * n_starts <= kPhaseAWidePerCu * c->cus &&
-      tree_on_wave_ok(n_rows, p->topo.K, p->topo.chain_stride, p->tree, p->opt.strict_order))
-    p->lanes_a = 64;
-  // the footprint launch_fit will ask for when the pedigree is streamed (resident launches stay below kLdsResidentMax by
-  // construction): the scratch of the workgroup's chains, plus one chunk of terms per chain in strict order — validated
-  // here, not at the first run
-  const size_t stream_stride = (size_t)p->topo.chain_stride + (p->opt.strict_order ? (size_t)kStrictRowsPerLane * p->lanes : 0);
-  if ((size_t)(kWave / p->lanes) * stream_stride * sizeof(double) > (p->lanes == kWave ? kMaxDynLds : kDefaultDynLds) ||
-      ((size_t)p->topo.chain_stride + kSelChunk) * sizeof(double) > kMaxDynLds) {
+  // what runs is a function of the pedigree and the options, decided (and refused) here, not at the first run
+  p->route = route_pedigree(n_rows, p->topo.K, p->topo.T, p->opt.lanes_per_chain, p->opt.strict_order);
+  if (p->route.refusal) {
+    const char* why = p->route.refusal;
     delete p;
-    return set_err(c, ABN_ERR_INVALID_ARG, "pedigree needs more LDS per workgroup than supported (T or K too large)");
+    return set_err(c, ABN_ERR_INVALID_ARG, why);
   }
   auto fail = [&](hipError_t e, const char* what) {
     abn_plan_destroy(p);
@@ -950,29 +710,20 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
   PALLOC(raw_own, W * B * 7);
   PALLOC(skipped, 4);
   PALLOC(slice_status, 8);
-  // Phase A with many chains when the repetitions of stuck fits must be executed (no_fixed_point_skip): 7 % of
-  // random starts run into argmin's fixed point and repeat it up to iteration 10000; dispatched late in one launch
-  // such a chain runs alone for tens of milliseconds.  Two passes: every chain for at most kPhaseACap iterations,
-  // then the unfinished ones, compacted, all resident at once.  With the default skip those chains end at once and
-  // one pass is faster (metaprofile shape, 30000 start chains: 14.6 ms against 18.3 ms).
-  p->twopass_a = (long long)n_windows * n_starts > 4096 && p->opt.max_iters_start > kPhaseACap &&
-                 p->opt.no_fixed_point_skip != 0 && p->opt.shrink_on_failed_contraction == 0 && !p->opt.strict_order;
+  p->twopass_a = plan_two_pass((long long)n_windows * n_starts, p->opt.max_iters_start, p->opt.no_fixed_point_skip,
+                               p->opt.shrink_on_failed_contraction, p->opt.strict_order);
   if (p->twopass_a) {
     PALLOC(nm_state, W * S * 32);
     PALLOC(susp_list, W * S + 1);
   }
-  {  // time slicing for launches that outgrow the resident set of the persistent kernel (4 x kPersistWaves chains at 16 lanes)
-    const size_t chains = W * std::max(S, B);
-    if (kQuantum > 0 && p->lanes < kWave && chains > (size_t)persist_waves_small(c) * (size_t)(kWave / p->lanes) &&
-        chains * 32 * sizeof(double) <= kSliceStateMax && chains < (1u << 27) && p->opt.window_groups <= 1) {
-      if (p->nm_state.n < chains * 32) PALLOC(nm_state, chains * 32);
-      p->slice_cap = (unsigned)(chains * 16 / kParkShards + 4096);   // per shard; a full shard just stops parking
-      PALLOC(slice_buf, (size_t)kParkShards * ((size_t)kParkHeaderInts + (size_t)p->slice_cap));
-      if (p->susp_list.n < chains + 1) PALLOC(susp_list, chains + 1);  // the tail list of the hand-over to the speculative kernel
-    }
+  // time slicing for launches that outgrow the resident set of the persistent kernel: parked states, the FIFOs, the tail list
+  if (const size_t chains = plan_sliced_chains(p->route, W * std::max(S, B), c->cus, p->opt.window_groups)) {
+    if (p->nm_state.n < chains * 32) PALLOC(nm_state, chains * 32);
+    p->slice_cap = (unsigned)(chains * 16 / kParkShards + 4096);   // per shard; a full shard just stops parking
+    PALLOC(slice_buf, (size_t)kParkShards * ((size_t)kParkHeaderInts + (size_t)p->slice_cap));
+    if (p->susp_list.n < chains + 1) PALLOC(susp_list, chains + 1);  // the tail list of the hand-over to the speculative kernel
   }
-  p->stream_b = n_boot > 0 && fit_streams(n_rows, p->topo.K, p->topo.chain_stride, p->lanes, p->opt.strict_order) &&
-                p->opt.stream_mode == 0;
+  p->stream_b = n_boot > 0 && p->route.streams && p->opt.stream_mode == 0;
   if (p->stream_b) PALLOC(dstar, W * B * N);
 #undef PALLOC
   p->raw = p->raw_own.p;
@@ -1050,12 +801,7 @@ extern "C" int abn_plan_set_windows(abn_plan* p, const double* d_obs, const doub
 }
 
 static void fill_common(const abn_plan* p, FitArgs& a) {
-  a.tri = p->dtopo.tri.p;
-  a.tid = p->dtopo.tid.p;
-  a.N = p->N;
-  a.K = p->topo.K;
-  a.T = p->topo.T;
-  a.TP = p->topo.TP;
+  fill_topology(a, p->topo, p->dtopo);
   a.chain_stride = p->topo.chain_stride;
   a.p_uu = p->p_uu.p;
   a.eqp = p->eqp.p;
@@ -1070,7 +816,7 @@ static void fill_common(const abn_plan* p, FitArgs& a) {
   a.window_offset = p->window_offset;
   a.boot_offset = p->boot_offset;
   a.wid = p->wid.p;
-  a.tree = p->tree;
+  a.tree = p->route.tree;
   a.strict = p->opt.strict_order ? 1 : 0;
   a.W = p->W;
   a.shrink_variant = p->opt.shrink_on_failed_contraction ? 1 : 0;
@@ -1079,9 +825,59 @@ static void fill_common(const abn_plan* p, FitArgs& a) {
   a.gap_tol = 64.0 * p->opt.sd_tolerance;
 }
 
-// Phase A (starts) + selection for windows [w0, w0+wn) on stream st.  ev != nullptr: record the plan's
-// timing events around the kernels.
-static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool timed, bool refill) {
+// The fit launch(es) of one phase (0 = A, 1 = B) for the windows `a` covers, on stream st.  A launch that covers the whole
+// plan is offered the phase's chain queue, the plan's parking buffers and its status words; window groups on side streams
+// would share them, so they get none (no persistent kernel, nothing to verify).
+static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool timed) {
+  abn_ctx* c = p->ctx;
+  const bool whole = a.W == p->W;
+  const char* force = nullptr;
+#ifdef ABN_MEASUREMENT_KNOBS  // ABN_PHASE_A_KERNEL / ABN_PHASE_B_KERNEL = spec | wide | packed  (scripts/phase_a_sweep.py)
+  force = getenv(phase ? "ABN_PHASE_B_KERNEL" : "ABN_PHASE_A_KERNEL");
+#endif
+  const PhaseRoute ph = route_phase(p->route, phase, (long long)p->W * (phase ? p->B : p->S), c->cus, a.dmode, whole,
+                                    p->twopass_a, force);
+  LaunchOffer offer;
+  offer.queue = whole;
+  offer.parking = whole && p->slice_cap > 0;
+  a.skipped = p->skipped.p + 2 * phase;
+  if (whole) {
+    a.queue = reinterpret_cast<unsigned*>(p->skipped.p + 2 * phase + 1);
+    a.slice_status = p->slice_status.p + 4 * phase;
+  }
+  if (offer.parking) {
+    a.park_cap = p->slice_cap;
+    a.park_ht = reinterpret_cast<unsigned*>(p->slice_buf.p);
+    a.parked = p->slice_buf.p + kParkShards * kParkHeaderInts;
+    a.state = p->nm_state.p;
+    a.susp_list = p->susp_list.p;   // tail hand-over (the route decides whether it applies)
+  }
+  int kind = ABN_KERNEL_NONE, rc;
+  if (ph.two_pass) {
+    int* cnt = p->susp_list.p + (size_t)p->W * (size_t)p->S;
+    HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(int), st));
+    a.state = p->nm_state.p;
+    a.susp_list = p->susp_list.p;
+    a.susp_count = cnt;
+    offer.pass = 1;
+    rc = launch_fit(c, p->route, ph, a, offer, st, &kind);   // everybody, capped
+    offer.pass = 2;
+    if (!rc) rc = launch_fit(c, p->route, ph, a, offer, st);  // the parked chains, to the end
+  } else {
+    rc = launch_fit(c, p->route, ph, a, offer, st, &kind);
+  }
+  if (rc) return rc;
+  if (whole) p->persist_expected[phase] = kind == ABN_KERNEL_PERSISTENT ? (long long)a.W * a.C : 0;
+  if (timed) {
+    p->last_kernels[2 * phase] = kind;
+    p->last_kernels[2 * phase + 1] = ph.lanes;
+  }
+  return ABN_OK;
+}
+
+// Phase A (starts) + selection for windows [w0, w0+wn) on stream st.  timed: record the plan's timing events around
+// the kernels.
+static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool timed) {
   abn_ctx* c = p->ctx;
   const size_t N = (size_t)p->N, S = (size_t)p->S, o = (size_t)w0;
   FitArgs a{};
@@ -1101,69 +897,11 @@ static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
   a.best = p->bestA.p + o * S * 4;
   a.info = p->infoA.p + o * S;
   a.raw = nullptr;
-  a.skipped = p->skipped.p;
-  a.queue = refill ? reinterpret_cast<unsigned*>(p->skipped.p + 1) : nullptr;
-  if (refill && p->slice_cap > 0 && w0 == 0 && wn == p->W) {
-    a.quantum = kQuantum;
-    a.park_cap = p->slice_cap;
-    a.park_ht = reinterpret_cast<unsigned*>(p->slice_buf.p);
-    a.parked = p->slice_buf.p + kParkShards * kParkHeaderInts;
-    a.state = p->nm_state.p;
-    a.susp_list = p->susp_list.p;   // tail hand-over (launch_fit decides whether it applies)
-  }
-  const bool whole = w0 == 0 && wn == p->W;   // window groups on side streams share the plan's status words: unchecked
-  if (whole) a.slice_status = p->slice_status.p;
-  int kind = ABN_KERNEL_NONE;
   if (timed) HIPCHK(c, hipEventRecord(p->ev[0], st));
-  // few chains: latency-bound -> three wavefronts per chain evaluate reflection / expansion / contraction at once,
-  // a fourth keeps the simplex and prepares the next candidates meanwhile (abn_fit_spec_kernel)
-  bool spec = p->lanes_a == 64 && p->opt.lanes_per_chain == 0 &&
-              (long long)p->W * p->S <= spec_max_chains(c, p->N, 0) && spec_applicable(a);
-  int lanes_a = p->lanes_a;
-#ifdef ABN_MEASUREMENT_KNOBS  // ABN_PHASE_A_KERNEL = spec | wide | packed  (scripts/phase_a_sweep.py)
-  if (const char* e = getenv("ABN_PHASE_A_KERNEL")) {
-    const bool can_wide = p->opt.lanes_per_chain == 0 && tree_on_wave_ok(p->N, p->topo.K, p->topo.chain_stride, p->tree, p->opt.strict_order);
-    if (!strcmp(e, "spec")) spec = can_wide && spec_applicable(a);
-    if (!strcmp(e, "wide")) { spec = false; if (can_wide) lanes_a = kWave; }
-    if (!strcmp(e, "packed")) { spec = false; lanes_a = p->lanes; }
-  }
-#endif
-  int rc;
-  if (spec) {
-    rc = launch_fit_spec(c, a, st);
-    kind = ABN_KERNEL_SPECULATIVE;
-  } else if (p->twopass_a && w0 == 0 && wn == p->W) {
-    kind = ABN_KERNEL_TWO_PASS;
-    int* cnt = p->susp_list.p + (size_t)p->W * S;
-    HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(int), st));
-    a.state = p->nm_state.p;
-    a.susp_list = p->susp_list.p;
-    a.susp_count = cnt;
-    a.iter_cap = kPhaseACap;
-    a.resume = 0;
-    rc = launch_fit(c, a, lanes_a, st);             // pass 1: everybody, capped
-    if (!rc) {
-      a.iter_cap = 0;
-      a.resume = 1;
-      rc = launch_fit(c, a, lanes_a, st);           // pass 2: the parked chains, to the end
-    }
-  } else {
-    rc = launch_fit(c, a, lanes_a, st, &kind);
-  }
-  if (rc) return rc;
-  if (whole) p->persist_expected[0] = kind == ABN_KERNEL_PERSISTENT ? (long long)wn * p->S : 0;
-  if (timed) {
-    p->last_kernels[0] = kind;
-    p->last_kernels[1] = spec ? kWave : lanes_a;
-  }
+  if (int rc = launch_phase(p, 0, a, st, timed)) return rc;
   if (timed) HIPCHK(c, hipEventRecord(p->ev[1], st));
   SelectArgs s{};
-  s.tri = a.tri;
-  s.tid = a.tid;
-  s.N = a.N;
-  s.K = a.K;
-  s.T = a.T;
-  s.TP = a.TP;
+  fill_topology(s, p->topo, p->dtopo);
   s.p_uu = a.p_uu;
   s.D = a.D;
   s.models = a.best;
@@ -1175,19 +913,14 @@ static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
   s.pred = p->pred.p + o * N;
   s.resid = p->resid.p + o * N;
   s.best_start = p->best_start.p + o;
-  const size_t lds = ((size_t)kPw * a.TP + p->topo.KP + kSelChunk) * sizeof(double);
   if (timed) HIPCHK(c, hipEventRecord(p->ev[2], st));
-  HIPCHK(c, allow_lds(reinterpret_cast<const void*>(&abn_select_lse_kernel), lds));
-  HIPCHK(c, allow_lds(reinterpret_cast<const void*>(&abn_select_kernel), lds));
-  hipLaunchKernelGGL(abn_select_lse_kernel, dim3((unsigned)((long long)wn * p->S)), dim3(kWave), lds, st, s);
-  hipLaunchKernelGGL(abn_select_kernel, dim3((unsigned)wn), dim3(kWave), lds, st, s);
-  HIPCHK(c, hipGetLastError());
+  if (int rc = launch_select(c, s, p->route.select_lds, st)) return rc;
   if (timed) HIPCHK(c, hipEventRecord(p->ev[3], st));
   return ABN_OK;
 }
 
 // Phase B (bootstraps) for windows [w0, w0+wn) on stream st
-static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool timed, bool refill) {
+static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool timed) {
   abn_ctx* c = p->ctx;
   const size_t N = (size_t)p->N, B = (size_t)p->B, o = (size_t)w0;
   FitArgs a{};
@@ -1209,19 +942,6 @@ static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
   a.best = p->bestB.p + o * B * 4;
   a.info = p->infoB.p + o * B;
   a.raw = p->raw + o * B * 7;
-  a.skipped = p->skipped.p + 2;
-  a.queue = refill ? reinterpret_cast<unsigned*>(p->skipped.p + 3) : nullptr;
-  if (refill && p->slice_cap > 0 && w0 == 0 && wn == p->W) {
-    a.quantum = kQuantum;
-    a.park_cap = p->slice_cap;
-    a.park_ht = reinterpret_cast<unsigned*>(p->slice_buf.p);
-    a.parked = p->slice_buf.p + kParkShards * kParkHeaderInts;
-    a.state = p->nm_state.p;
-    a.susp_list = p->susp_list.p;   // tail hand-over (launch_fit decides whether it applies)
-  }
-  const bool whole = w0 == 0 && wn == p->W;
-  if (whole) a.slice_status = p->slice_status.p + 4;
-  int kind = ABN_KERNEL_SPECULATIVE;
   if (timed) HIPCHK(c, hipEventRecord(p->ev[4], st));
   if (p->stream_b) {  // gather the bootstrap observations once per fit, then stream them
     double* dst = p->dstar.p + o * B * N;
@@ -1233,31 +953,7 @@ static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
     a.dmode = 2;
     a.D = dst;
   }
-  // few bootstraps: latency-bound like phase A -> the speculative kernel (four wavefronts per chain)
-  bool spec = a.dmode == 1 && p->opt.lanes_per_chain == 0 &&
-              (long long)p->W * p->B <= spec_max_chains(c, p->N, 1) && spec_applicable(a);
-  int lanes_b = p->lanes;
-  // ... and up to 192 chains per packed lane (3072 for the 16-lane kernels) a wavefront per chain still beats packing
-  // several chains into one (scripts/b_kernel_sweep.py, C3 topology: 2000 bootstraps 1.36 ms against 1.74 ms packed and
-  // 1.81 ms speculative; 4000: 1.99 against 1.75; bundled 6-row pedigree, 8 lanes: 2000 bootstraps 1.98 against 1.90)
-  if (!spec && a.dmode == 1 && p->opt.lanes_per_chain == 0 && p->lanes < kWave &&
-      (long long)p->W * p->B <= (3LL * c->cus / 4) * p->lanes && tree_on_wave_ok(p->N, p->topo.K, p->topo.chain_stride, p->tree, p->opt.strict_order))
-    lanes_b = kWave;
-#ifdef ABN_MEASUREMENT_KNOBS  // ABN_PHASE_B_KERNEL = spec | wide | packed
-  if (const char* e = getenv("ABN_PHASE_B_KERNEL")) {
-    const bool can_wide = a.dmode == 1 && p->opt.lanes_per_chain == 0 && tree_on_wave_ok(p->N, p->topo.K, p->topo.chain_stride, p->tree, p->opt.strict_order);
-    if (!strcmp(e, "spec")) spec = can_wide && spec_applicable(a);
-    if (!strcmp(e, "wide")) { spec = false; if (can_wide) lanes_b = kWave; }
-    if (!strcmp(e, "packed")) spec = false;
-  }
-#endif
-  int rc = spec ? launch_fit_spec(c, a, st) : launch_fit(c, a, lanes_b, st, &kind);
-  if (rc) return rc;
-  if (whole) p->persist_expected[1] = kind == ABN_KERNEL_PERSISTENT ? (long long)wn * p->B : 0;
-  if (timed) {
-    p->last_kernels[2] = kind;
-    p->last_kernels[3] = spec ? kWave : lanes_b;
-  }
+  if (int rc = launch_phase(p, 1, a, st, timed)) return rc;
   if (timed) HIPCHK(c, hipEventRecord(p->ev[5], st));
   return ABN_OK;
 }
@@ -1274,7 +970,7 @@ static int plan_run_phase(abn_plan* p, int32_t phase, int zero_skipped) {
   }
   if (phase == 0) {
     if (p->S <= 0) return set_err(c, ABN_ERR_STATE, "plan has no starts");
-    int rc = enqueue_phase_a(p, 0, p->W, c->stream, true, true);
+    int rc = enqueue_phase_a(p, 0, p->W, c->stream, true);
     if (rc) return rc;
     p->phase_a_done = true;
     p->ran_a = true;
@@ -1283,7 +979,7 @@ static int plan_run_phase(abn_plan* p, int32_t phase, int zero_skipped) {
   if (phase == 1) {
     if (p->B <= 0) return set_err(c, ABN_ERR_STATE, "plan has no bootstraps");
     if (!p->phase_a_done) return set_err(c, ABN_ERR_STATE, "phase A has not run");
-    int rc = enqueue_phase_b(p, 0, p->W, c->stream, true, true);
+    int rc = enqueue_phase_b(p, 0, p->W, c->stream, true);
     if (rc) return rc;
     p->ran_b = true;
     return ABN_OK;
@@ -1332,8 +1028,8 @@ extern "C" int abn_plan_run(abn_plan* p) {
     const int w0 = (int)((long long)p->W * g / groups), w1 = (int)((long long)p->W * (g + 1) / groups);
     hipStream_t st = c->side[(size_t)g];
     HIPCHK(c, hipStreamWaitEvent(st, p->ev_fork, 0));
-    int rc = enqueue_phase_a(p, w0, w1 - w0, st, g == 0, false);  // groups share the plan's one queue: no
-    if (!rc) rc = enqueue_phase_b(p, w0, w1 - w0, st, g == 0, false);  // persistent kernel
+    int rc = enqueue_phase_a(p, w0, w1 - w0, st, g == 0);  // groups share the plan's one queue: no persistent kernel
+    if (!rc) rc = enqueue_phase_b(p, w0, w1 - w0, st, g == 0);
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(p->ev_join[(size_t)g], st));
   }
@@ -1459,10 +1155,9 @@ extern "C" int abn_plan_failed_windows(abn_plan* p, int32_t* n_failed) {
 }
 
 extern "C" int abn_plan_counters(abn_plan* p, int64_t* out5) {
-  int64_t* out4 = out5;
   if (!p || !out5) return ABN_ERR_INVALID_ARG;
   abn_ctx* c = p->ctx;
-  out4[0] = out4[1] = out4[2] = out4[3] = out4[4] = 0;
+  out5[0] = out5[1] = out5[2] = out5[3] = out5[4] = 0;
   std::vector<FitInfoDev> h;
   auto add = [&](const DevBuf<FitInfoDev>& b, int phase) -> int {
     if (!b.n) return ABN_OK;
@@ -1472,11 +1167,11 @@ extern "C" int abn_plan_counters(abn_plan* p, int64_t* out5) {
     HIPCHK(c, hipMemcpyAsync(&sk, p->skipped.p + 2 * phase, sizeof sk, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (const auto& f : h) {
-      out4[0] += 1;
-      out4[1] += f.evals;
-      out4[2] += f.iters;
+      out5[0] += 1;
+      out5[1] += f.evals;
+      out5[2] += f.iters;
     }
-    out4[3 + phase] = (int64_t)sk;
+    out5[3 + phase] = (int64_t)sk;
     return ABN_OK;
   };
   int rc = ABN_OK;
@@ -1504,7 +1199,7 @@ static int debug_stamps(abn_plan* p, unsigned long long* out8, bool spec) {
   a.info = p->infoA.p;
   a.raw = nullptr;
   a.dbg = d.p;
-  int rc = spec ? launch_fit_spec(c, a, c->stream) : launch_fit(c, a, p->lanes, c->stream);
+  int rc = launch_fit(c, p->route, PhaseRoute{spec, p->route.lanes, false}, a, LaunchOffer{}, c->stream);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(out8, d.p, 64, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1615,8 +1310,8 @@ extern "C" int abn_select_best(abn_ctx* c, const double* pedigree, int32_t n_row
   Topology t;
   int rc = build_topology(pedigree, n_rows, 4, t);
   if (rc) return set_err(c, rc, abn_status_string(rc));
-  const size_t lds = ((size_t)kPw * t.TP + t.KP + kSelChunk) * sizeof(double);
-  if (lds > kMaxDynLds) return set_err(c, ABN_ERR_INVALID_ARG, "pedigree needs more LDS than supported");
+  const PedigreeRoute pr = route_pedigree(n_rows, t.K, t.T, 0, 0);
+  if (pr.select_refusal) return set_err(c, ABN_ERR_INVALID_ARG, pr.select_refusal);
   DevTopology dt;
   rc = upload_topology(c, t, dt);
   if (rc) return rc;
@@ -1640,12 +1335,7 @@ extern "C" int abn_select_best(abn_ctx* c, const double* pedigree, int32_t n_row
   HIPCHK(c, hipMemcpyAsync(dp.p, &p0uu, sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(dinfo.p, 0, dinfo.bytes(), c->stream));  // status 0: every model is a candidate
   SelectArgs a{};
-  a.tri = dt.tri.p;
-  a.tid = dt.tid.p;
-  a.N = n_rows;
-  a.K = t.K;
-  a.T = t.T;
-  a.TP = t.TP;
+  fill_topology(a, t, dt);
   a.p_uu = dp.p;
   a.D = dD.p;
   a.models = dm.p;
@@ -1657,11 +1347,8 @@ extern "C" int abn_select_best(abn_ctx* c, const double* pedigree, int32_t n_row
   a.pred = dpred.p;
   a.resid = dresid.p;
   a.best_start = dbest.p;
-  HIPCHK(c, allow_lds(reinterpret_cast<const void*>(&abn_select_lse_kernel), lds));
-  HIPCHK(c, allow_lds(reinterpret_cast<const void*>(&abn_select_kernel), lds));
-  hipLaunchKernelGGL(abn_select_lse_kernel, dim3((unsigned)a.S), dim3(kWave), lds, c->stream, a);
-  hipLaunchKernelGGL(abn_select_kernel, dim3(1), dim3(kWave), lds, c->stream, a);
-  HIPCHK(c, hipGetLastError());
+  rc = launch_select(c, a, pr.select_lds, c->stream);
+  if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(best_index, dbest.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   if (model) HIPCHK(c, hipMemcpyAsync(model, dmodel.p, dmodel.bytes(), hipMemcpyDeviceToHost, c->stream));
   if (pred) HIPCHK(c, hipMemcpyAsync(pred, dpred.p, dpred.bytes(), hipMemcpyDeviceToHost, c->stream));

@@ -10,8 +10,6 @@ namespace abn {
 // arg-min taken (lowest start index on ties; NaN never wins), then predicted divergence and residuals
 // of the winner written for phase B.  LDS: chain scratch (9*TP + K doubles) + kSelChunk terms.
 // ------------------------------------------------------------------------------------------------
-constexpr int kSelChunk = 512;
-
 struct SelectArgs {
   const uint32_t* tri;
   const uint16_t* tid;

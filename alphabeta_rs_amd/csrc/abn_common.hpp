@@ -24,22 +24,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "abn_constants.hpp"
 #include "abn_philox.h"
 
 namespace abn {
 
-constexpr int kWave = 64;
-constexpr int kPw = 10;  // doubles per entry of the power table in LDS: 9 elements + 1 so that entries are 16-byte aligned
-static_assert(kPw % 2 == 0 && kPw >= 9, "load_matrix reads 16-byte aligned pairs");
-constexpr int kStreamVec = 4;  // consecutive rows per lane and block in stream mode
-#ifndef ABN_STREAM_BLOCKS
-#define ABN_STREAM_BLOCKS 6
-#endif
 #ifndef ABN_STREAM_WAVES
 #define ABN_STREAM_WAVES 2
 #endif
 constexpr int kStreamWaves = ABN_STREAM_WAVES;    // wavefronts per SIMD the stream variant is compiled for
-constexpr int kStreamBlocks = ABN_STREAM_BLOCKS;  // row blocks a lane keeps in flight per loop iteration
 
 // element-aligned vector types: global loads on gfx950 need dword alignment only
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -55,8 +48,6 @@ constexpr int ST_EXPAND = 6;    // evaluating the expanded point
 constexpr int ST_CONTRACT = 7;  // evaluating the contracted point
 constexpr int ST_SHRINK1 = 8;   // 8..11: evaluating shrunk vertex k = st-7
 constexpr int ST_DONE = 12;
-constexpr int kParkHead = 0, kParkTail = 64, kParkAvail = 128, kParkHeaderInts = 192;  // one cache line each
-constexpr int kParkShards = 64;  // independent FIFOs (workgroup b uses b mod 64): a cache line serves ~100 M atomics/s
 constexpr int kFitSuspended = 4;  // internal status between the two passes of a long chain
 constexpr unsigned kSliceErrLostEntry = 1u;  // FitArgs::slice_status[0]
 
@@ -589,7 +580,6 @@ __device__ __forceinline__ double group_sum_dpp(double v) {
 // ------------------------------------------------------------------------------------------------
 // The canonical residual tree (FitArgs::tree == kTreeCanon): 64 accumulators, high lane bits first.
 // ------------------------------------------------------------------------------------------------
-constexpr int kTreeCanon = 0x10040;      // the oracle's `lanes` code: 64 accumulators | mirror-descending steps
 constexpr int kDppRowRor8 = 0x128;       // lane i <- lane i ^ 8 inside each 16 lanes
 constexpr int kDppQuadRev = 0x1B;        // quad_perm:[3,2,1,0]: lane i <-> 3 - i inside each quad
 

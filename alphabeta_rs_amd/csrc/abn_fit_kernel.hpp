@@ -17,7 +17,6 @@ namespace abn {
 // (src/structs.rs:206-213), the oracle's lanes = 1 — instead of with the tree: the lanes write their rows' terms to LDS
 // (resident: N more doubles per chain; stream: chunks of 8 G rows) and every lane of the group adds them up in order
 // (same address in the whole group: an LDS broadcast).  N dependent additions per evaluation: the price of an opt-in mode.
-constexpr int kStrictRowsPerLane = 8;  // rows per lane and chunk of the strict stream variant
 
 template <int G, int RMAX, bool TWOPASS = false, bool STRICT = false>
 __global__ __launch_bounds__(kWave, TWOPASS ? 2 : (RMAX == 0 ? kStreamWaves : 3)) void abn_fit_kernel(const FitArgs a) {

@@ -31,12 +31,6 @@ __device__ __forceinline__ void wave_lds_fence() {  // orders this wavefront's L
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-constexpr int kSpecOutcomes = 10;                                   // r@0..3, e@0, c@0..4
-constexpr int kSpecTabDoubles = kSpecOutcomes * 12;                 // [outcome][candidate r/e/c][dimension]
-constexpr int kSpecPreDoubles = kSpecOutcomes * 3 * 12;             // [outcome][candidate][G (9), penalty, 0.0, pad]
-constexpr int kSpecCommDoubles = 8 + 2 * kSpecTabDoubles + 16 + 2 * kSpecPreDoubles + 16;  // cost exchange, two candidate
-                                                 // tables, shrink points, two tables of prepared inputs, two control blocks
-
 // STRICT (abn_options.strict_order): the evaluation wavefronts sum the residuals serially in row order (terms to LDS, N
 // more doubles per wavefront, then serial_sum_lds) — the reference's order, the oracle's lanes = 1.
 // Registers: 88-135 per lane (the roles' loops are separate, so neither carries the other's state): four workgroups per CU for

@@ -2,6 +2,7 @@
 // to_file and the number formatter without a GPU.  Not part of the product ABI (include/abneutral.h).
 #include <cstring>
 
+#include "../csrc/abn_route.hpp"
 #include "alphabeta.hpp"
 
 extern "C" {
@@ -54,5 +55,44 @@ int abh_write_npy(const char* path, const double* rows, long long n_boot) {
   r.rows.assign(rows, rows + 7 * n_boot);
   r.write_npy(path);
   return 0;
+}
+
+// The launch policy (csrc/abn_route.hpp) as plain integers, for the CPU tier of tests/test_kernel_matrix_census.py.
+// pedigree level -> out[8]: lanes, tree, tree as abn_reduction_tree reports it, streams, a wavefront per chain allowed,
+// speculative kernel applies, lanes of abn_cost_batch, selection LDS bytes; returns 1 when abn_plan_create refuses
+static abn::PedigreeRoute abh_pedigree(int n, int k, int t, int lanes, int strict) {
+  return abn::route_pedigree(n, k, t, lanes, strict);
+}
+int abh_route_pedigree(int n, int k, int t, int lanes, int strict, long long* out) {
+  const abn::PedigreeRoute p = abh_pedigree(n, k, t, lanes, strict);
+  const long long v[8] = {p.lanes, p.tree, p.reported_tree, p.streams, p.wide_ok, p.spec_ok, p.cost_lanes, (long long)p.select_lds};
+  std::memcpy(out, v, sizeof v);
+  return p.refusal ? 1 : 0;
+}
+// phase level (phase 0 = A, 1 = B; plan_chains: windows x starts or bootstraps) -> out[3]: speculative, lanes, two passes
+void abh_route_phase(int n, int k, int t, int lanes, int strict, int phase, long long plan_chains, int cus, int dmode,
+                     int whole, int two_pass, int* out) {
+  const abn::PhaseRoute r = abn::route_phase(abh_pedigree(n, k, t, lanes, strict), phase, plan_chains, cus, dmode, whole != 0, two_pass != 0);
+  out[0] = r.spec;
+  out[1] = r.lanes;
+  out[2] = r.two_pass;
+}
+// launch level (spec, phase_lanes: the phase level's answer; queue, parking, pass: abn::LaunchOffer) -> out[15]: kind, the key
+// (family, G, R, TP, STRICT, RESUME), grid, block, LDS bytes, chain_stride, tree, quantum, tail_cap, RMAX of the tail's
+// resume launch (spec<R, tree, resume>; 0: none); returns the status (the text in err)
+int abh_route_launch(int n, int k, int t, int lanes, int strict, int spec, int phase_lanes, long long chains, int cus,
+                     int queue, int parking, int pass, long long* out, char* err, int errcap) {
+  const abn::PedigreeRoute p = abh_pedigree(n, k, t, lanes, strict);
+  abn::LaunchOffer o;
+  o.queue = queue != 0;
+  o.parking = parking != 0;
+  o.pass = pass;
+  const abn::LaunchRoute r = abn::route_launch(p, abn::PhaseRoute{spec != 0, phase_lanes, false}, chains, cus, o);
+  if (err && errcap > 0) std::strncpy(err, r.error ? r.error : "", (size_t)errcap - 1), err[errcap - 1] = 0;
+  const long long v[15] = {r.kind, r.key.family, r.key.G, r.key.R, r.key.tp, r.key.strict, r.key.resume, r.grid, r.block,
+                           (long long)r.lds, r.chain_stride, r.tree, r.quantum, r.tail_cap,
+                           r.tail_cap > 0 ? abn::route_tail_resume(p, r.tail_cap).key.R : 0};
+  std::memcpy(out, v, sizeof v);
+  return r.status;
 }
 }

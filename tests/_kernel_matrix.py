@@ -32,7 +32,7 @@ def _load(name):
 LDS = _load("test_gpu_lds_boundary")
 WAVE, KPW, CANON = LDS.WAVE, LDS.KPW, LDS.CANON
 STREAM_BLOCKS, STREAM_VEC = 6, 4          # abn_common.hpp: kStreamBlocks, kStreamVec
-DEEP_ROWS = 2 * STREAM_BLOCKS * STREAM_VEC  # launch_fit: N >= 48 G rows take the deep stream loop (RMAX 0), fewer -1
+DEEP_ROWS = 2 * STREAM_BLOCKS * STREAM_VEC  # route_launch: N >= 48 G rows take the deep stream loop (RMAX 0), fewer -1
 LDS_TARGET_PER_BLOCK = 20 * 1024          # pick_lanes' widening target
 SERIAL_SUM_MAX_ROWS = 16                  # resolve_for: auto options sum up to 16 rows serially
 PHASE_A_CAP = 1000                        # kPhaseACap: first-pass iteration cap of the two-pass phase A
@@ -89,7 +89,7 @@ def chain_stride(tmax, k):
 
 
 def pick_lanes(n, requested, cs):
-    """abn_api.hip: pick_lanes (rows first, then widened until 64/G chains' scratch + observations fit 20 KiB)"""
+    """abn_route.hpp: pick_lanes (rows first, then widened until 64/G chains' scratch + observations fit 20 KiB)"""
     if requested:
         return requested
     g = 8 if n <= 32 else 16 if n <= 128 else 32 if n <= 256 else WAVE
@@ -116,7 +116,7 @@ def expected_tree(n, tmax, k, opts):
 
 
 def fit_rmax(n, k, tmax, lanes, strict):
-    """the RMAX template argument launch_fit picks: resident R, or 0 / -1 streamed (strict order streams with 0)"""
+    """the RMAX template argument route_launch (abn_route.hpp) picks: resident R, or 0 / -1 streamed (strict order streams with 0)"""
     cs = chain_stride(tmax, k)
     if not LDS.streams(n, k, cs, lanes, strict):
         return LDS.pick_rmax(n, lanes)
@@ -124,7 +124,7 @@ def fit_rmax(n, k, tmax, lanes, strict):
 
 
 def spec_fits(n, tmax, k, strict):
-    """spec_applicable for a resident pedigree at auto lanes (canonical tree or strict order)"""
+    """route_pedigree's spec_ok for a resident pedigree at auto lanes (canonical tree or strict order)"""
     cs = chain_stride(tmax, k)
     r = LDS.pick_rmax(n, WAVE)
     if r == 0 or r > 8 or LDS.streams(n, k, cs, WAVE, strict):
@@ -262,24 +262,25 @@ def _build():
 
 MATRIX = _build()
 
-# instantiations the dispatch compiles but cannot launch, with the condition in abn_api.hip that rules them out
-_NO_REFILL_64 = ("launch_fit: refill needs ng > 1 (kWave / lanes chains per wavefront), so never at 64 lanes; "
-                 "launch_fit_refill<64> exists only because launch_fit_g<64> instantiates it")
+# instantiations the dispatch compiles but cannot launch, with the condition in abn_route.hpp that rules them out
+_NO_REFILL_64 = ("route_launch (abn_route.hpp): a persistent launch needs several chains per wavefront (persistent_by_size: "
+                 "kWave / lanes > 1), so never 64 lanes; abn_api.hip's kernel table lists refill<64, R> all the same")
 UNREACHABLE = {
     (REFILL, 64, 1, False, False, False): _NO_REFILL_64,
     (REFILL, 64, 2, False, False, False): _NO_REFILL_64,
     (REFILL, 64, 4, False, False, False): _NO_REFILL_64,
     (REFILL, 64, 8, False, False, False): _NO_REFILL_64,
     (SPEC, 64, 8, False, False, True): (
-        "launch_fit: the tail hand-over needs refill (lanes < 64) and a.tree == kTreeCanon (auto lanes); auto lanes "
-        "below 64 means N <= 256 (pick_lanes), so pick_rmax(N, kWave) <= 4 and launch_fit_spec never takes RMAX 8"),
+        "route_launch (abn_route.hpp): the tail hand-over needs a persistent launch (lanes < 64) and the canonical tree "
+        "(tail_cap_for: auto lanes); auto lanes below 64 means N <= 256 (pick_lanes), so pick_rmax(N, kWave) <= 4 and "
+        "route_tail_resume never takes RMAX 8"),
 }
 
 
 def boot_count(case, small_waves, cus):
     """B of a case: 'persistent+37' is 37 chains past what the persistent launch needs at the case's lanes, so that the
     last wavefront is partly filled: more lane groups than persist_waves_small wavefronts hold, and with auto lanes more
-    bootstraps than enqueue_phase_b gives a wavefront each (3 cus / 4 x lanes: 6144 at 32 lanes on 256 CUs)"""
+    bootstraps than route_phase gives a wavefront each (3 cus / 4 x lanes: 6144 at 32 lanes on 256 CUs)"""
     b = case["B"]
     if isinstance(b, int):
         return b

@@ -1,7 +1,7 @@
 """Fit parity at the host's kernel decisions: LDS-resident or streamed, speculative or not, and the 160 KiB opt-in limit.
 
 Every fit launch first decides whether a chain's pedigree fits in LDS (kLdsResidentMax = 40 KiB per workgroup,
-abn_api.hip: resident_fits) and that decision also fixes the reduction tree the oracle has to be told.  The cases
+abn_route.hpp: resident_rows) and that decision also fixes the reduction tree the oracle has to be told.  The cases
 below sit one allocation step either side of each decision — the footprints differ by the smallest amount the
 formula can move (two doubles per chain of the workgroup) — and check which side they landed on through
 Plan.last_kernels(), so that a drift between this file's copy of the formula and the C++ fails loudly.  On every case
@@ -18,7 +18,7 @@ import pytest
 
 from alphabeta_rs_amd import synthetic
 
-# abn_api.hip / abn_common.hpp / abn_aux_kernels.hpp / abn_fit_spec.hpp
+# abn_route.hpp / abn_constants.hpp
 KPW, WAVE = 10, 64
 LDS_RESIDENT_MAX = 40 * 1024
 MAX_DYN_LDS = 160 * 1024
@@ -52,7 +52,7 @@ def pick_rmax(n, lanes):
 
 
 def resident_bytes(n, k, chain_stride, lanes, strict=0):
-    """launch_fit's footprint of a resident workgroup (resident_extra: observations, triple list, strict terms)"""
+    """route_launch's footprint of a resident workgroup (resident_extra: observations, triple list, strict terms)"""
     extra = ((n + 1) & ~1) + (((k + 1) // 2 + 1) & ~1) + (((n + 1) & ~1) if strict else 0)
     return (WAVE // lanes) * (chain_stride + extra) * 8
 
@@ -62,7 +62,7 @@ def streams(n, k, chain_stride, lanes, strict=0):
 
 
 def spec_bytes(n, chain_stride):
-    """spec_applicable's footprint: three evaluation wavefronts' scratch + observations, and the exchange area"""
+    """the speculative kernel's footprint (spec_lds): three evaluation wavefronts' scratch + observations, and the exchange area"""
     return (3 * (chain_stride + ((n + 1) & ~1)) + SPEC_COMM_DOUBLES) * 8
 
 
@@ -109,7 +109,7 @@ def lds_pair(lanes, strict=0):
 
 
 def spec_pair():
-    """(n, tmax, k) just inside / outside spec_applicable's footprint: auto options, 64 lanes, up to 8 rows per lane
+    """(n, tmax, k) just inside / outside the speculative kernel's footprint (spec_lds): auto options, 64 lanes, up to 8 rows per lane
     (pick_rmax <= 8, N in (256, 512]); two rows more move the footprint by 3 x 2 doubles."""
     n_under = 300
     for k in range(n_under, 0, -1):

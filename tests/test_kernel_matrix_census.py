@@ -61,7 +61,7 @@ def test_every_instantiation_has_a_case_or_a_reason(kernels):
         fams[k[0]] = fams.get(k[0], 0) + 1
     assert fams == {KM.FIT: 71, KM.REFILL: 16, KM.SPEC: 12, KM.COST: 4}, fams
     for k, why in KM.UNREACHABLE.items():
-        assert "abn_api.hip" in why or "launch_fit" in why, (KM.label(k), why)
+        assert "abn_route.hpp" in why and "route_launch" in why, (KM.label(k), why)   # a pointer to the host condition
 
 
 def test_census_is_not_vacuous(kernels):
@@ -120,3 +120,154 @@ def test_case_routes_to_its_instantiation_and_tree(abn, key):
     o = abn.default_options(**c["opts"])
     assert abn.reduction_tree(ped[:, :3], o) == KM.expected_tree(c["n"], c["tmax"], c["k"], c["opts"])
     assert key in KM.targets(c), [KM.label(t) for t in KM.targets(c)]
+
+
+# ------------------------------------------------------------------------------------------------ the C++ routing, on the CPU
+# csrc/abn_route.hpp decides every launch in three pure functions; host/host_capi.cpp exports them (abh_route_*).  Below
+# they are asked what they would launch and held against tests/_kernel_matrix.py's and tests/test_gpu_lds_boundary.py's
+# independent restatements of the policy — which stay restatements: nothing here feeds the shim's answers back in.
+CUS = 256
+SMALL_WAVES, BIG_WAVES = 8 * CUS, 12 * CUS      # persistent launches: wavefronts of the small / the full geometry
+FAMILY = (KM.FIT, KM.REFILL, KM.SPEC, KM.COST)
+ERR_INVALID_ARG = 1
+LDS_REFUSAL = b"pedigree needs more LDS per workgroup than supported (T or K too large)"
+
+
+class Route:
+    def __init__(self):
+        import ctypes as C
+
+        from alphabeta_rs_amd import build as B
+
+        B.build_host()
+        L = C.CDLL(str(B.PEDIGREE_LIB))
+        i, ll = C.c_int, C.c_longlong
+        L.abh_route_pedigree.argtypes = [i, i, i, i, i, C.POINTER(ll)]
+        L.abh_route_phase.argtypes = [i, i, i, i, i, i, ll, i, i, i, i, C.POINTER(i)]
+        L.abh_route_launch.argtypes = [i, i, i, i, i, i, i, ll, i, i, i, i, C.POINTER(ll), C.c_char_p, i]
+        self.L, self.p8, self.p3, self.p15, self.err = L, (ll * 8)(), (i * 3)(), (ll * 15)(), C.create_string_buffer(128)
+
+    def pedigree(self, ped):
+        """ped = (n, k, tmax, requested lanes, strict) -> the pedigree level's answers"""
+        refused = self.L.abh_route_pedigree(*ped, self.p8)
+        names = ("lanes", "tree", "reported_tree", "streams", "wide_ok", "spec_ok", "cost_lanes", "select_lds")
+        return dict(zip(names, self.p8), refused=bool(refused))
+
+    def phase(self, ped, phase, plan_chains, dmode, whole=True, two_pass=False):
+        self.L.abh_route_phase(*ped, phase, plan_chains, CUS, dmode, whole, two_pass, self.p3)
+        return tuple(self.p3)   # spec, lanes, two passes
+
+    def launch(self, ped, spec, lanes, chains, queue=False, parking=False, pass_=0):
+        """(status, error text, kind, keys): the launch's key, and its tail's resume launch's if there is one"""
+        status = self.L.abh_route_launch(*ped, spec, lanes, chains, CUS, queue, parking, pass_, self.p15, self.err, 128)
+        v = self.p15
+        keys = []
+        if status == 0 and v[0] != 0:
+            keys.append((FAMILY[v[1]], v[2], v[3], bool(v[4]), bool(v[5]), bool(v[6])))
+            if v[13] > 0:
+                keys.append((KM.SPEC, KM.WAVE, v[14], False, False, True))
+        return status, self.err.value, v[0], keys
+
+    def phase_keys(self, ped, phase, chains, dmode, whole=True, two_pass=False, parking=False):
+        """every key the launches of one phase of a plan take (both passes of a two-pass phase A, a tail's resume launch)"""
+        spec, lanes, two = self.phase(ped, phase, chains, dmode, whole, two_pass)
+        out = []
+        for pass_ in ((1, 2) if two else (0,)):
+            status, err, _, keys = self.launch(ped, spec, lanes, chains, queue=whole, parking=parking, pass_=pass_)
+            assert status == 0, (ped, phase, chains, err)
+            out += keys
+        return out
+
+
+@pytest.fixture(scope="module")
+def route():
+    return Route()
+
+
+def _plan_inputs(c):
+    """what a plan over a MATRIX case's pedigree passes down, by the restatements: (ped, S, B, two-pass, parking, dmode of B)"""
+    n, tmax, k, o = c["n"], c["tmax"], c["k"], c["opts"]
+    req, strict = o.get("lanes_per_chain", 0), KM.strict_of(n, o)
+    cs = KM.chain_stride(tmax, k)
+    lanes = KM.pick_lanes(n, req, cs)
+    S, B = c["S"], KM.boot_count(c, SMALL_WAVES, CUS)
+    two_pass = (S > KM.TWO_PASS_CHAINS and o.get("max_iters_start", 10000) > KM.PHASE_A_CAP and
+                bool(o.get("no_fixed_point_skip", 0)) and not o.get("shrink_on_failed_contraction", 0) and not strict)
+    parking = lanes < KM.WAVE and max(S, B) > SMALL_WAVES * (KM.WAVE // lanes)     # abn_plan_create: time slicing buffers
+    dmode_b = 2 if KM.LDS.streams(n, k, cs, lanes, strict) and not o.get("stream_mode", 0) else 1
+    return (n, k, tmax, req, strict), S, B, two_pass, parking, dmode_b
+
+
+@pytest.mark.parametrize("key", list(KM.MATRIX), ids=KM.label)
+def test_cpp_routes_case_to_its_instantiation(route, key):
+    """what the C++ routes for the case's launches (256 CUs, the chain counts of tests/test_gpu_kernel_matrix.py) contains
+    the case's own key and nothing the restated dispatch does not expect; the pedigree level reports the restated tree"""
+    c = KM.MATRIX[key]
+    o = c["opts"]
+    if c["route"] == "cost":
+        ped = (c["n"], c["k"], c["tmax"], o.get("lanes_per_chain", 0), KM.strict_of(c["n"], o))
+        got = {(KM.COST, route.pedigree(ped)["cost_lanes"], 0, False, False, False)}
+    else:
+        ped, S, B, two_pass, parking, dmode_b = _plan_inputs(c)
+        got = set(route.phase_keys(ped, 0, S, 0, two_pass=two_pass, parking=parking))
+        got |= set(route.phase_keys(ped, 1, B, dmode_b, two_pass=two_pass, parking=parking))
+    assert key in got, [KM.label(k) for k in got]
+    assert got <= KM.targets(c), [KM.label(k) for k in got - KM.targets(c)]
+    assert route.pedigree(ped)["reported_tree"] == KM.expected_tree(c["n"], c["tmax"], c["k"], o)
+    strict_cost = (c["n"], c["k"], c["tmax"], o.get("lanes_per_chain", 0), 1)
+    assert route.pedigree(strict_cost)["cost_lanes"] == KM.WAVE       # abn_cost_batch in strict order: a wavefront per candidate
+
+
+def test_cpp_routing_at_the_lds_boundaries(route):
+    """tests/test_gpu_lds_boundary.py's pairs: resident or streamed as filed, the speculative kernel one step either side of
+    its footprint, and abn_plan_create's refusal one step over limit_k() with acceptance at it"""
+    LDS = KM.LDS
+    for name, (n, tmax, k, o, kind) in LDS.boundary_cases().items():
+        p = route.pedigree((n, k, tmax, o.get("lanes_per_chain", 0), o.get("strict_order", 0)))
+        assert not p["refused"], name
+        assert bool(p["streams"]) == (kind == "stream"), name
+        assert p["reported_tree"] == LDS.expected_tree(n, k, KM.chain_stride(tmax, k), o), name
+        if name.startswith("spec_"):
+            assert bool(p["spec_ok"]) == (name == "spec_under"), name
+    kmax = LDS.limit_k()
+    assert not route.pedigree((kmax + 1, kmax, 127, 0, 0))["refused"]
+    assert route.pedigree((kmax + 3, kmax + 2, 127, 0, 0))["refused"]
+
+
+def test_cpp_routing_sweep_stays_inside_the_census(route, kernels):
+    """The launch level over a grid of pedigrees, options, chain counts either side of every threshold (256 CUs), both
+    phases, with and without the caller's queue and parking buffers: never an UNREACHABLE key, never a key the assembly
+    does not hold, and every MATRIX fit-path key at least once.  Pedigrees no plan accepts are refused with the one text."""
+    peds = []
+    for n in list(range(1, 1101)) + [1500, 2048, 3073, 5000, 20100]:
+        for tmax, k in ((127, min(n, 600)), (3, min(n, 40))):
+            peds += [(n, k, tmax, req, strict) for req in (0, 8, 16, 32, 64) for strict in (0, 1)]
+    own = {}                                      # the MATRIX cases' own inputs: no key depends on the grid's luck
+    for c in KM.MATRIX.values():
+        if c["route"] != "cost":
+            ped, S, B, *_ = _plan_inputs(c)
+            own.setdefault(ped, set()).update((S, B))
+    hits = set()
+    for ped in peds + list(own):
+        n = ped[0]
+        p = route.pedigree(ped)
+        if p["refused"]:      # abn_plan_create refuses; abn_fit_batch reaches the launch level, which refuses the same way
+            status, err, _, _ = route.launch(ped, 0, p["lanes"], 1)
+            assert (status, err) == (ERR_INVALID_ARG, LDS_REFUSAL), ped
+            continue
+        ng = KM.WAVE // p["lanes"]
+        small = KM.LDS.pick_rmax(n, KM.WAVE) <= 2
+        edges = ({1, KM.TWO_PASS_CHAINS, 24 * CUS, SMALL_WAVES * ng, BIG_WAVES * ng, CUS * (16 if small else 8)},
+                 {1, (3 * CUS // 4) * p["lanes"], SMALL_WAVES * ng, BIG_WAVES * ng, CUS * 6 if small else CUS * 3})
+        for phase in (0, 1):
+            for chains in sorted({x + d for x in edges[phase] | own.get(ped, set()) for d in (0, 1)}):
+                for dmode in ((0,) if phase == 0 else (1, 2) if p["streams"] else (1,)):
+                    for whole in (False, True):           # a window group is offered neither queue nor parking buffers
+                        two = phase == 0 and whole and chains > KM.TWO_PASS_CHAINS and not ped[4]
+                        for two_pass in ((False, True) if two else (False,)):
+                            for parking in ((False, True) if whole and ng > 1 and chains > SMALL_WAVES * ng else (False,)):
+                                hits.update(route.phase_keys(ped, phase, chains, dmode, whole, two_pass, parking))
+    assert not hits & set(KM.UNREACHABLE), [KM.label(k) for k in hits & set(KM.UNREACHABLE)]
+    assert hits <= set(kernels), [KM.label(k) for k in hits - set(kernels)]
+    missing = {k for k in KM.MATRIX if k[0] != KM.COST} - hits
+    assert not missing, [KM.label(k) for k in sorted(missing, key=str)]
