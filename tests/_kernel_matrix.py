@@ -10,33 +10,12 @@ A key is (family, G, R, TP, STRICT, RESUME): G lanes per chain (64 for the specu
 stream loop, -1: pair-loop stream; the speculative kernel's RMAX), TP two-pass, STRICT serial row order, RESUME the
 speculative kernel's tail hand-over.  Fields a family has no template argument for are False (cost: R = 0).
 
-The host arithmetic is the restatement in tests/test_gpu_lds_boundary.py (topology, footprints, pick_rmax), loaded
-here, plus pick_lanes, which only auto-lane cases need.
+The host arithmetic is the restatement in tests/_route_model.py (topology, footprints, pick_rmax, pick_lanes).
 """
-import importlib.util
 import re
-from pathlib import Path
 
-import numpy as np
-
-HERE = Path(__file__).resolve().parent
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, HERE / f"{name}.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-LDS = _load("test_gpu_lds_boundary")
-WAVE, KPW, CANON = LDS.WAVE, LDS.KPW, LDS.CANON
-STREAM_BLOCKS, STREAM_VEC = 6, 4          # abn_common.hpp: kStreamBlocks, kStreamVec
-DEEP_ROWS = 2 * STREAM_BLOCKS * STREAM_VEC  # route_launch: N >= 48 G rows take the deep stream loop (RMAX 0), fewer -1
-LDS_TARGET_PER_BLOCK = 20 * 1024          # pick_lanes' widening target
-SERIAL_SUM_MAX_ROWS = 16                  # resolve_for: auto options sum up to 16 rows serially
-PHASE_A_CAP = 1000                        # kPhaseACap: first-pass iteration cap of the two-pass phase A
-TWO_PASS_CHAINS = 4096                    # abn_plan_create: two passes above 4096 start chains
+from _route_model import (DEEP_ROWS, MAX_DYN_LDS, SERIAL_SUM_MAX_ROWS, TWO_PASS_CHAINS, WAVE, boundary_pedigree,
+                          chain_stride, fit_rmax, pick_lanes, pick_rmax, pool_size, spec_fits, streams, strict_of)
 
 FIT, REFILL, SPEC, COST = "fit", "refill", "spec", "cost"
 
@@ -76,63 +55,7 @@ def label(key):
     return f"fit<{g},{r}{',tp' if tp else ''}{',strict' if strict else ''}>"
 
 
-# ------------------------------------------------------------------------------------------------ the host's arithmetic
-def pool_size(tmax):
-    """distinct (t0, t1-t0, t2-t0) triples with max generation <= tmax (t1, t2 <= 127)"""
-    t = np.arange(tmax + 1)
-    t0, ea, eb = np.meshgrid(t, t, t, indexing="ij")
-    return int(((t0 + ea <= 127) & (t0 + eb <= 127)).sum())
-
-
-def chain_stride(tmax, k):
-    return KPW * (tmax + 1) + ((k + 1) & ~1) + 4
-
-
-def pick_lanes(n, requested, cs):
-    """abn_route.hpp: pick_lanes (rows first, then widened until 64/G chains' scratch + observations fit 20 KiB)"""
-    if requested:
-        return requested
-    g = 8 if n <= 32 else 16 if n <= 128 else 32 if n <= 256 else WAVE
-    while g < WAVE and (WAVE // g) * (cs + n) * 8 > LDS_TARGET_PER_BLOCK:
-        g *= 2
-    return g
-
-
-def strict_of(n, opts):
-    """resolve_for: strict_order 0 with auto lanes is serial up to 16 rows"""
-    s = opts.get("strict_order", 0)
-    return 1 if s == 1 or (s == 0 and not opts.get("lanes_per_chain", 0) and n <= SERIAL_SUM_MAX_ROWS) else 0
-
-
-def expected_tree(n, tmax, k, opts):
-    """abn_reduction_tree by this restatement"""
-    cs = chain_stride(tmax, k)
-    lanes = pick_lanes(n, opts.get("lanes_per_chain", 0), cs)
-    if strict_of(n, opts):
-        return 1
-    if LDS.streams(n, k, cs, lanes):
-        return LDS.stream_tree(lanes)
-    return lanes if opts.get("lanes_per_chain", 0) else CANON
-
-
-def fit_rmax(n, k, tmax, lanes, strict):
-    """the RMAX template argument route_launch (abn_route.hpp) picks: resident R, or 0 / -1 streamed (strict order streams with 0)"""
-    cs = chain_stride(tmax, k)
-    if not LDS.streams(n, k, cs, lanes, strict):
-        return LDS.pick_rmax(n, lanes)
-    return 0 if strict or n >= DEEP_ROWS * lanes else -1
-
-
-def spec_fits(n, tmax, k, strict):
-    """route_pedigree's spec_ok for a resident pedigree at auto lanes (canonical tree or strict order)"""
-    cs = chain_stride(tmax, k)
-    r = LDS.pick_rmax(n, WAVE)
-    if r == 0 or r > 8 or LDS.streams(n, k, cs, WAVE, strict):
-        return False
-    np_ = ((n + 1) & ~1) * (2 if strict else 1)
-    return (3 * (cs + np_) + LDS.SPEC_COMM_DOUBLES) * 8 <= LDS.LDS_RESIDENT_MAX
-
-
+# ------------------------------------------------------------------------------------------------ the routes
 def targets(case):
     """the instantiations a case's route launches by this restatement (the case's own key must be among them)"""
     n, tmax, k, o = case["n"], case["tmax"], case["k"], case["opts"]
@@ -150,7 +73,7 @@ def targets(case):
         return {plain, (FIT, plain[1], r, True, False, False)}
     if route == "persistent":
         return {plain, (REFILL, lanes, r, False, False, False)}
-    rs = LDS.pick_rmax(n, WAVE)
+    rs = pick_rmax(n, WAVE)
     if route == "spec":
         return {(SPEC, WAVE, rs, False, bool(strict), False)} if spec_fits(n, tmax, k, strict) else set()
     if route == "tail":
@@ -185,17 +108,17 @@ def _shape(n, g, r, strict, index, want_stream, t_first=None):
         if k > 1 and (k % 2) != (index % 2):
             k -= 1
         cs = chain_stride(tmax, k)
-        if LDS.streams(n, k, cs, g, strict) != want_stream:
+        if streams(n, k, cs, g, strict) != want_stream:
             if want_stream:
                 continue
             # resident wanted: fewer distinct triples may fit
-            while k > 2 and LDS.streams(n, k, cs, g, strict):
+            while k > 2 and streams(n, k, cs, g, strict):
                 k -= 2
                 cs = chain_stride(tmax, k)
-            if LDS.streams(n, k, cs, g, strict):
+            if streams(n, k, cs, g, strict):
                 continue
         stride = cs + (8 * g if strict and want_stream else 0)   # the strict stream variant's chunk of terms
-        if want_stream and (WAVE // g) * stride * 8 > (LDS.MAX_DYN_LDS if g == WAVE else 64 * 1024):
+        if want_stream and (WAVE // g) * stride * 8 > (MAX_DYN_LDS if g == WAVE else 64 * 1024):
             continue
         return tmax, k
     raise AssertionError(f"no shape for N={n} G={g} R={r}")
@@ -290,4 +213,4 @@ def boot_count(case, small_waves, cus):
 
 
 def pedigree(case):
-    return LDS.boundary_pedigree(case["n"], case["tmax"], case["k"], seed=case["seed"])
+    return boundary_pedigree(case["n"], case["tmax"], case["k"], seed=case["seed"])

@@ -172,13 +172,14 @@ def test_reduction_tree_is_a_function_of_the_pedigree_only(abn):
     import oracle as O
     from alphabeta_rs_amd import synthetic
 
-    canon = 0x10040
-    assert abn.reduction_tree(synthetic.c3_pedigree()[0][:, :3]) == canon
+    from _route_model import CANON, boundary_cases, boundary_pedigree
+
+    assert abn.reduction_tree(synthetic.c3_pedigree()[0][:, :3]) == CANON
     bundled = O.load_pedigree(ROOT / "tests" / "golden" / "pedigree_generated.txt")[:, :3]
     assert abn.reduction_tree(bundled) == 1          # up to 16 rows: the reference's serial order by default (free there)
-    assert abn.reduction_tree(bundled, abn.default_options(strict_order=-1)) == canon
-    assert abn.reduction_tree(synthetic.c3_pedigree()[0][:17, :3]) == canon    # 17 rows: the tree
-    assert abn.reduction_tree(O.load_pedigree(ROOT / "tests" / "golden" / "pedigree.txt")[:, :3]) == canon
+    assert abn.reduction_tree(bundled, abn.default_options(strict_order=-1)) == CANON
+    assert abn.reduction_tree(synthetic.c3_pedigree()[0][:17, :3]) == CANON    # 17 rows: the tree
+    assert abn.reduction_tree(O.load_pedigree(ROOT / "tests" / "golden" / "pedigree.txt")[:, :3]) == CANON
     assert abn.reduction_tree(synthetic.c3_pedigree()[0][:, :3], abn.default_options(lanes_per_chain=32)) == 32
     assert abn.reduction_tree(synthetic.c3_pedigree()[0][:, :3], abn.default_options(lanes_per_chain=16)) == 16
     big = np.zeros((3000, 3))
@@ -186,11 +187,9 @@ def test_reduction_tree_is_a_function_of_the_pedigree_only(abn):
     assert abn.reduction_tree(big) == (64 | (3 << 8))
     # at the LDS-residency boundary (tests/test_gpu_lds_boundary.py): the tree follows the footprint the launch uses,
     # which counts the pedigree's distinct triples, not an upper bound from its row count
-    from test_gpu_lds_boundary import boundary_cases, boundary_pedigree
-
     cases = boundary_cases()
-    for name, want in (("auto64_n1000_k200", canon), ("auto64_rmax16_largest", canon), ("auto64_rmax8_largest", canon),
-                       ("spec_under", canon), ("spec_over", canon), ("auto64_rmax16_rows_over", 64 | (3 << 8)),
+    for name, want in (("auto64_n1000_k200", CANON), ("auto64_rmax16_largest", CANON), ("auto64_rmax8_largest", CANON),
+                       ("spec_under", CANON), ("spec_over", CANON), ("auto64_rmax16_rows_over", 64 | (3 << 8)),
                        ("lanes16_under", 16), ("lanes16_over", 16 | (3 << 8)), ("lanes8_under", 8),
                        ("lanes8_over", 8 | (3 << 8)), ("lanes32_rows_under", 32), ("lanes32_rows_over", 32 | (3 << 8)),
                        ("strict16_under", 1), ("strict16_over", 1)):
@@ -200,7 +199,7 @@ def test_reduction_tree_is_a_function_of_the_pedigree_only(abn):
     # generations saturate at 127 (`as i8`): T = 350 is the topology of T = 127
     wide = boundary_pedigree(1000, 127, 200, seed=7)[:, :3]
     wide[wide == 127] = 350
-    assert abn.reduction_tree(wide) == canon
+    assert abn.reduction_tree(wide) == CANON
 
 
 def test_bench_refuses_a_gpu_count_it_cannot_run():

@@ -11,68 +11,25 @@ Every case builds a pedigree with the N, T and K its route needs and asserts
 
 test_cost_kernel_against_fifty_digits checks every abn_cost_kernel<G> against mpmath, independent of the oracle.
 """
-import importlib.util
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from alphabeta_rs_amd import synthetic
 
+import _kernel_matrix as KM
+import _route_model as RM
+from _parity import assert_fits_equal, check_selection_and_boot, run_plan
 
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, Path(__file__).resolve().parent / f"{name}.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-KM = _load("_kernel_matrix")
 P0 = synthetic.TRUE_P0UU
 STATUS_PARKED = 4
 
 
 def _sample(n, lanes, seed=20261016, extra=5):
     """chain indices: first, last, the first chain of the last (partly filled) wavefront, and `extra` seeded others"""
-    ng = KM.WAVE // lanes
+    ng = RM.WAVE // lanes
     pick = {0, n - 1, ((n - 1) // ng) * ng}
     pick |= set(np.random.default_rng(seed).choice(n, min(extra, n), replace=False).tolist())
     return np.array(sorted(pick))
-
-
-def _fits_equal(info, want, label, best=None):
-    for f in ("status", "iters", "evals"):
-        assert np.array_equal(info[f], want[f]), (label, f)
-    ok = want["status"] != 2
-    assert np.array_equal(info["best_cost"][ok], want["best_cost"][ok]), label
-    if best is not None:
-        assert np.array_equal(best[ok], want["best"][ok]), label
-
-
-def _run_plan(abn, ctx, ped, S, B, o, boot_offset=0):
-    plan = abn.Plan(ctx, ped[:, :3], 1, S, B, boot_offset=boot_offset, options=o)
-    plan.set_windows(ped[:, 3][None, :], np.array([P0]))
-    plan.run()
-    out = plan.download()
-    kinds, handed = plan.last_kernels(), plan.tail_handed()
-    plan.close()
-    return out, kinds, handed
-
-
-def _check_selection_and_boot(oracle, ped, out, best_a, c, tree, label, rows=None):
-    """best_start / model / pred / resid from the oracle's selection over `best_a`, then the bootstrap rows (all, or the
-    sampled `rows`) replayed one by one"""
-    o = c["opts"]
-    kk, model, pred, resid, _ = oracle.select_best(ped, P0, best_a)
-    assert out["best_start"][0] == kk and np.array_equal(out["models"][0], model), label
-    assert np.array_equal(out["pred"][0], pred) and np.array_equal(out["resid"][0], resid), label
-    B = out["raw"].shape[1]
-    for b0, nb in ([(0, B)] if rows is None else [(int(b), 1) for b in rows]):
-        raw, res = oracle.boot_model(ped, model, pred, resid, P0, P0, 1.0, c["seed"], 0, b0, nb,
-                                     max_iters=o["max_iters_boot"], lanes=tree, threads=4)
-        assert np.array_equal(out["raw"][0, b0:b0 + nb], raw, equal_nan=True), (label, b0)
-        for f in ("iters", "evals", "status"):
-            assert np.array_equal(out["info_b"][f][0, b0:b0 + nb], res[f]), (label, b0, f)
 
 
 def _check_shards(abn, ctx, ped, c, o, out, lanes, label):
@@ -81,7 +38,7 @@ def _check_shards(abn, ctx, ped, c, o, out, lanes, label):
     B = out["raw"].shape[1]
     half = B // 2
     for off, nb in ((0, half), (half, B - half)):
-        sh, kinds, _ = _run_plan(abn, ctx, ped, c["S"], nb, o, boot_offset=off)
+        sh, kinds, _ = run_plan(abn, ctx, ped, P0, c["S"], nb, o, boot_offset=off)
         assert kinds["boot"][0] == "resident" and kinds["boot"][1] in (lanes, 64 if c["route"] == "tail" else lanes), \
             (label, kinds)
         assert sh["raw"][0].tobytes() == out["raw"][0, off:off + nb].tobytes(), (label, off)
@@ -96,8 +53,8 @@ def test_instantiation_matches_oracle(abn, gpu_ctx, oracle, key):
     ped = KM.pedigree(c)
     o = abn.default_options(seed=c["seed"], **c["opts"])
     tree = abn.reduction_tree(ped[:, :3], o)
-    assert tree == KM.expected_tree(c["n"], c["tmax"], c["k"], c["opts"]), (label, hex(tree))
-    ia, seed = c["opts"].get("max_iters_start"), c["seed"]
+    assert tree == RM.expected_tree(c["n"], c["tmax"], c["k"], c["opts"]), (label, hex(tree))
+    ia, ib, seed = c["opts"].get("max_iters_start"), c["opts"].get("max_iters_boot"), c["seed"]
     route = c["route"]
 
     if route == "cost":
@@ -107,11 +64,11 @@ def test_instantiation_matches_oracle(abn, gpu_ctx, oracle, key):
         assert np.array_equal(cost, np.array([oracle.cost(ped, P0, P0, 1.0, x, lanes=cost_tree) for x in cand])), label
         return
 
-    lanes = key[1] if key[0] in (KM.FIT, KM.REFILL) else KM.pick_lanes(c["n"], 0, KM.chain_stride(c["tmax"], c["k"]))
+    lanes = key[1] if key[0] in (KM.FIT, KM.REFILL) else RM.pick_lanes(c["n"], 0, RM.chain_stride(c["tmax"], c["k"]))
     dev = gpu_ctx.device_info()
     small = dev["persistent_wavefronts_small"]
     B = KM.boot_count(c, small, dev["compute_units"])
-    out, kinds, handed = _run_plan(abn, gpu_ctx, ped, c["S"], B, o)
+    out, kinds, handed = run_plan(abn, gpu_ctx, ped, P0, c["S"], B, o)
     assert np.all(out["info_a"]["lanes"] == tree) and np.all(out["info_b"]["lanes"] == tree), label
     S = c["S"]
     s0 = abn.gen_start_simplices(seed, 0, S, ped[:, 3].max())
@@ -123,17 +80,17 @@ def test_instantiation_matches_oracle(abn, gpu_ctx, oracle, key):
             kind = "stream" if key[2] <= 0 else "resident"
             assert kinds == {"starts": (kind, key[1]), "boot": (kind, key[1])}, (label, kinds)
         fits = oracle.fit_batch(ped, P0, P0, 1.0, s0, ia, lanes=tree, threads=4)
-        _fits_equal(out["info_a"][0], fits, label)
-        _check_selection_and_boot(oracle, ped, out, fits["best"], c, tree, label)
+        assert_fits_equal(None, out["info_a"][0], fits, label)
+        check_selection_and_boot(oracle, ped, P0, out, fits["best"], seed, ib, tree, label)
         if route == "plan":   # per-fit observations (abn_fit_batch, one window per fit): the same instantiation
-            F = 2 * (KM.WAVE // lanes) + 3
+            F = 2 * (RM.WAVE // lanes) + 3
             rng = np.random.default_rng(seed + 1)
             dobs = np.abs(ped[:, 3][None, :] * rng.uniform(0.5, 1.5, (F, ped.shape[0])))
             sf = abn.gen_start_simplices(seed, 1, F, dobs.max())
             best, info = gpu_ctx.fit_batch(ped, P0, P0, 1.0, sf, ia, dobs_rows=dobs, options=o)
             assert np.all(info["lanes"] == tree), label
-            _fits_equal(info, oracle.fit_batch(ped, P0, P0, 1.0, sf, ia, dobs_rows=dobs, lanes=tree, threads=4), label,
-                        best)
+            want = oracle.fit_batch(ped, P0, P0, 1.0, sf, ia, dobs_rows=dobs, lanes=tree, threads=4)
+            assert_fits_equal(best, info, want, label)
         return
 
     if route == "twopass":
@@ -141,25 +98,25 @@ def test_instantiation_matches_oracle(abn, gpu_ctx, oracle, key):
         assert kinds == {"starts": ("two_pass", key[1]), "boot": (kind_b, key[1])}, (label, kinds)
         ia_ = out["info_a"][0]
         assert np.all(ia_["status"] != STATUS_PARKED), label
-        assert (ia_["iters"] > KM.PHASE_A_CAP).sum() > 0, label            # some chains were parked and resumed
+        assert (ia_["iters"] > RM.PHASE_A_CAP).sum() > 0, label            # some chains were parked and resumed
         # the whole table against the one-pass launch of the same starts (abn_fit_batch: fit<G,R>, not two-pass)
         best, info = gpu_ctx.fit_batch(ped, P0, P0, 1.0, s0, ia, options=o)
         assert info.tobytes() == ia_.tobytes(), label
         rows = _sample(S, lanes)
         fits = oracle.fit_batch(ped, P0, P0, 1.0, s0[rows], ia, lanes=tree, threads=4)
-        _fits_equal(ia_[rows], fits, label, best[rows])
-        _check_selection_and_boot(oracle, ped, out, best, c, tree, label)
+        assert_fits_equal(best[rows], ia_[rows], fits, label)
+        check_selection_and_boot(oracle, ped, P0, out, best, seed, ib, tree, label)
         return
 
     # persistent (explicit lanes) and tail hand-over (auto lanes: canonical tree, the tail on the speculative kernel)
     starts = ("speculative", 64) if route == "tail" else ("resident", lanes)
     assert kinds == {"starts": starts, "boot": ("persistent", lanes)}, (label, kinds)
-    assert B > small * (KM.WAVE // lanes) and B % (KM.WAVE // lanes)
+    assert B > small * (RM.WAVE // lanes) and B % (RM.WAVE // lanes)
     if route == "tail":
         assert handed[1] > 0, (label, handed)
     fits = oracle.fit_batch(ped, P0, P0, 1.0, s0, ia, lanes=tree, threads=4)
-    _fits_equal(out["info_a"][0], fits, label)
-    _check_selection_and_boot(oracle, ped, out, fits["best"], c, tree, label, rows=_sample(B, lanes))
+    assert_fits_equal(None, out["info_a"][0], fits, label)
+    check_selection_and_boot(oracle, ped, P0, out, fits["best"], seed, ib, tree, label, rows=_sample(B, lanes))
     _check_shards(abn, gpu_ctx, ped, c, o, out, lanes, label)
 
 
@@ -294,7 +251,7 @@ def test_cost_kernel_against_fifty_digits(abn, gpu_ctx, lanes):
     dts = {}
     for T in range(128):
         ped = _cost_pedigree(T)
-        if lanes < 64 and (64 // lanes) * KM.LDS.topology(ped)[2] * 8 > 64 * 1024:
+        if lanes < 64 and (64 // lanes) * RM.topology(ped)[2] * 8 > 64 * 1024:
             assert lanes == 8 and T >= 80, T
             continue
         _, dt, puu = gpu_ctx.cost_batch(ped, p_uu, p_uu, 1.0, cand, options=o, want_dt=True, want_puu=True)

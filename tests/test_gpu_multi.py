@@ -10,6 +10,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from _route_model import CANON
+
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -31,9 +33,6 @@ def _pedigree(kind, golden):
         d = np.abs(rng.normal(0.01, 0.004, 200))
         return np.stack([t0, t1, t2, d], axis=1).astype(np.float64), 0.8
     return golden["pedigree"], 0.75       # N = 351: tree of 64
-
-
-CANON = 0x10040   # the canonical tree of every LDS-resident pedigree: 64 accumulators, high lane bits first
 
 
 @pytest.mark.parametrize("kind,tree", (("c3", CANON), ("generated", 1), ("generated_tree", CANON), ("mid", CANON),

@@ -8,20 +8,13 @@ under 1-ulp cost differences; wherever a tolerance is used instead it is written
 import numpy as np
 import pytest
 
+from _parity import assert_fits_equal, synthetic_pedigree
+from _route_model import CANON
 from conftest import COST_KNOWN_ANSWER, MODEL_DEFAULT
 
 pytestmark = pytest.mark.gpu
 
 LANES = (8, 16, 32, 64)
-
-
-def synthetic_pedigree(rng, n, tmax, frac_t0=0.3):
-    """random valid (t0,t1,t2,D) rows: t0 <= t1,t2 <= tmax"""
-    t0 = np.where(rng.random(n) < frac_t0, rng.integers(0, max(1, tmax // 2), n), 0)
-    t1 = t0 + rng.integers(0, tmax - t0 + 1)
-    t2 = t0 + rng.integers(0, tmax - t0 + 1)
-    d = np.abs(rng.normal(0.01, 0.004, n))
-    return np.stack([t0, t1, t2, d], axis=1).astype(np.float64)
 
 
 # ------------------------------------------------------------------------------------------------ cost
@@ -110,15 +103,6 @@ def test_bootstrap_indices_bit_exact(abn, gpu_ctx, oracle):
 
 
 # ------------------------------------------------------------------------------------------------ fits
-def _assert_fits_equal(best, info, want):
-    assert np.array_equal(info["status"], want["status"])
-    assert np.array_equal(info["iters"], want["iters"])
-    assert np.array_equal(info["evals"], want["evals"])
-    ok = want["status"] != 2
-    assert np.array_equal(best[ok], want["best"][ok])
-    assert np.array_equal(info["best_cost"][ok], want["best_cost"][ok])
-
-
 @pytest.mark.parametrize("lanes", LANES)
 @pytest.mark.parametrize("variant", (0, 1))
 def test_fit_batch_trajectories_bit_exact(abn, gpu_ctx, golden, oracle, lanes, variant):
@@ -134,7 +118,7 @@ def test_fit_batch_trajectories_bit_exact(abn, gpu_ctx, golden, oracle, lanes, v
         code = int(info["lanes"][0])   # lanes, plus the row-block code when the pedigree is streamed
         assert np.all(info["lanes"] == code) and (code & 0xff) == lanes
         want = oracle.fit_batch(ped, p0, p0, 1.0, s0, iters, shrink_variant=variant, lanes=code)
-        _assert_fits_equal(best, info, want)
+        assert_fits_equal(best, info, want)
 
 
 def test_fit_batch_stream_mode_large_pedigree(abn, gpu_ctx, oracle):
@@ -154,7 +138,7 @@ def test_fit_batch_stream_mode_large_pedigree(abn, gpu_ctx, oracle):
             code = int(info["lanes"][0])          # stream mode: lanes | (rows per block - 1) << 8
             assert code & 0xff == lanes and code >> 8 == expect[lanes]
             want = oracle.fit_batch(ped, 0.75, 0.75, 1.0, s0, 300, lanes=code)
-            _assert_fits_equal(best, info, want)
+            assert_fits_equal(best, info, want)
 
 
 def test_fit_batch_per_fit_observations(abn, gpu_ctx, golden, oracle):
@@ -167,7 +151,7 @@ def test_fit_batch_per_fit_observations(abn, gpu_ctx, golden, oracle):
     best, info = gpu_ctx.fit_batch(ped, p0, p0, 1.0, s0, 1000, dobs_rows=dobs,
                                    options=abn.default_options(lanes_per_chain=16))
     want = oracle.fit_batch(ped, p0, p0, 1.0, s0, 1000, dobs_rows=dobs, lanes=16)
-    _assert_fits_equal(best, info, want)
+    assert_fits_equal(best, info, want)
 
 
 def test_fit_nonfinite_start_reports_status(abn, gpu_ctx, golden, oracle):
@@ -179,7 +163,7 @@ def test_fit_nonfinite_start_reports_status(abn, gpu_ctx, golden, oracle):
     best, info = gpu_ctx.fit_batch(ped, p0, p0, 1.0, s0, 200, options=o)
     want = oracle.fit_batch(ped, p0, p0, 1.0, s0, 200, lanes=8)
     assert info["status"][1] == abn.FIT_NONFINITE
-    _assert_fits_equal(best, info, want)
+    assert_fits_equal(best, info, want)
 
 
 # ------------------------------------------------------------------------------------------------ runs
@@ -201,7 +185,7 @@ def test_ab_neutral_and_boot_model_match_oracle(abn, gpu_ctx, golden, oracle, ca
     model, pred, resid, extra = gpu_ctx.ab_neutral_run(ped, p0, p0, 1.0, n_starts, options=o)
     lanes = int(extra["info"]["lanes"][0])
     k, wmodel, wpred, wresid, wlse, wfits = _oracle_ab_neutral(oracle, abn, ped, p0, p0, 1.0, n_starts, seed, lanes)
-    _assert_fits_equal(extra["models"], extra["info"], wfits)
+    assert_fits_equal(extra["models"], extra["info"], wfits)
     assert np.array_equal(extra["lse"], wlse)
     assert np.array_equal(model, wmodel)                 # north-star bar: 1e-6; held: bit-exact
     assert np.array_equal(pred, wpred) and np.array_equal(resid, wresid)
@@ -406,7 +390,7 @@ def test_deep_pedigree_stream_mode_c5_shape(abn, gpu_ctx, oracle, stream_mode):
     la, lb = int(out["info_a"]["lanes"][0, 0]), int(out["info_b"]["lanes"][0, 0])
     s0 = abn.gen_start_simplices(seed, 0, 3, ped[:, 3].max())
     fits = oracle.fit_batch(ped, p0, p0, 1.0, s0, 60, lanes=la)
-    _assert_fits_equal(out["models"][0:0], out["info_a"][0][:0], fits[:0])  # shape sanity only
+    assert_fits_equal(out["models"][0:0], out["info_a"][0][:0], fits[:0])  # shape sanity only
     assert np.array_equal(out["info_a"]["evals"][0], fits["evals"])
     k, model, pred, resid, _ = oracle.select_best(ped, p0, fits["best"])
     assert out["best_start"][0] == k and np.array_equal(out["models"][0], model)
@@ -445,7 +429,7 @@ def test_deep_pedigree_c5_fits_to_termination(abn, gpu_ctx, oracle, stream_mode)
         assert np.array_equal(out["info_a"][f][0], fits[f]), f
     best, info = gpu_ctx.fit_batch(ped, p0, p0, 1.0, s0, 10000, options=o)      # the start vertices themselves
     assert np.all(info["lanes"] == tree)
-    _assert_fits_equal(best, info, fits)
+    assert_fits_equal(best, info, fits)
     k, model, pred, resid, _ = oracle.select_best(ped, p0, fits["best"])
     assert out["best_start"][0] == k and np.array_equal(out["models"][0], model)
     assert np.array_equal(out["pred"][0], pred) and np.array_equal(out["resid"][0], resid)
@@ -842,7 +826,7 @@ def test_fixed_point_skip_changes_no_output(abn, gpu_ctx, golden, oracle):
         assert np.array_equal(res[0][0], res[1][0], equal_nan=True)
         assert res[0][1].tobytes() == res[1][1].tobytes()
         want = oracle.fit_batch(pedx, 0.7, 0.7, 1.0, s0, iters, lanes=int(res[0][1]["lanes"][0]))
-        _assert_fits_equal(res[0][0], res[0][1], want)
+        assert_fits_equal(res[0][0], res[0][1], want)
 
 
 @pytest.mark.parametrize("order", (-1, 0))   # the canonical tree / the serial default of a six-row pedigree (STRICT variant)
@@ -868,7 +852,7 @@ def test_speculative_phase_a_all_branches(abn, gpu_ctx, golden, oracle, variant,
     out = plan.download(allow_failed_windows=True)
     plan.close()
     la = int(out["info_a"]["lanes"][0, 0])
-    assert la == (0x10040 if order < 0 else 1) == abn.reduction_tree(ped[:, :3], o)   # on four wavefronts per chain
+    assert la == (CANON if order < 0 else 1) == abn.reduction_tree(ped[:, :3], o)   # on four wavefronts per chain
     assert out["best_start"][3] == -1 and np.all(out["info_a"]["status"][3] == 2)
     assert np.all(np.isnan(out["models"][3])) and np.all(np.isnan(out["pred"][3]))
     for w in range(W):
@@ -913,7 +897,7 @@ def test_persistent_refill_kernel_is_schedule_independent(abn, gpu_ctx, golden, 
         else:
             assert handed == (0, 0), handed
     lanes = int(outs[0]["info_b"]["lanes"][0, 0])          # the canonical tree code, whatever the packed lane count
-    assert lanes == abn.reduction_tree(ped[:, :3], abn.default_options(strict_order=-1)) == 0x10040
+    assert lanes == abn.reduction_tree(ped[:, :3], abn.default_options(strict_order=-1)) == CANON
     packed = 8 if case == "generated" else 16
     assert W * B // (64 // packed) > 3072                 # the persistent launch was taken
     for k in ("models", "pred", "resid", "raw", "best_start"):

@@ -8,21 +8,12 @@ comment); this test holds it in place: in every abn_fit_refill_kernel instantiat
 stores and before the sc1 entry store, and no trap instruction is left in the kernel (a lost FIFO entry sets an
 error word instead of aborting the process: the C-ABI never crashes).
 """
-import importlib.util
 import re
-from pathlib import Path
 
 import pytest
 
+import _device_isa
 
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, Path(__file__).resolve().parent / f"{name}.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-_device_isa = _load("_device_isa")
 MARK = "abn: parked state written through"
 
 

@@ -6,22 +6,14 @@ abn_fit_spec_kernel and abn_cost_kernel.  Each one must be in exactly one of tes
 rules it out).  A new instantiation — a new `case` of a dispatch switch, a new template argument — fails here until it
 gets a case or a reason; a table entry the assembly no longer has fails too.
 """
-import importlib.util
 import re
-from pathlib import Path
 
 import pytest
 
+import _device_isa
+import _kernel_matrix as KM
+import _route_model as RM
 
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, Path(__file__).resolve().parent / f"{name}.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-_device_isa = _load("_device_isa")
-KM = _load("_kernel_matrix")
 FAMILIES = ("abn_fit_kernel", "abn_fit_refill_kernel", "abn_fit_spec_kernel", "abn_cost_kernel")
 
 
@@ -115,21 +107,21 @@ def test_case_routes_to_its_instantiation_and_tree(abn, key):
     case expects, and by the restated dispatch its route launches the instantiation it is filed under"""
     c = KM.MATRIX[key]
     ped = KM.pedigree(c)
-    tmax, k, _ = KM.LDS.topology(ped)
+    tmax, k, _ = RM.topology(ped)
     assert (ped.shape[0], tmax, k) == (c["n"], c["tmax"], c["k"])
     o = abn.default_options(**c["opts"])
-    assert abn.reduction_tree(ped[:, :3], o) == KM.expected_tree(c["n"], c["tmax"], c["k"], c["opts"])
+    assert abn.reduction_tree(ped[:, :3], o) == RM.expected_tree(c["n"], c["tmax"], c["k"], c["opts"])
     assert key in KM.targets(c), [KM.label(t) for t in KM.targets(c)]
 
 
 # ------------------------------------------------------------------------------------------------ the C++ routing, on the CPU
 # csrc/abn_route.hpp decides every launch in three pure functions; host/host_capi.cpp exports them (abh_route_*).  Below
-# they are asked what they would launch and held against tests/_kernel_matrix.py's and tests/test_gpu_lds_boundary.py's
-# independent restatements of the policy — which stay restatements: nothing here feeds the shim's answers back in.
+# they are asked what they would launch and held against the independent restatement of the policy in
+# tests/_route_model.py (and tests/_kernel_matrix.py's routes over it) — which stays a restatement: nothing here feeds the
+# shim's answers back in.
 CUS = 256
 SMALL_WAVES, BIG_WAVES = 8 * CUS, 12 * CUS      # persistent launches: wavefronts of the small / the full geometry
 FAMILY = (KM.FIT, KM.REFILL, KM.SPEC, KM.COST)
-ERR_INVALID_ARG = 1
 LDS_REFUSAL = b"pedigree needs more LDS per workgroup than supported (T or K too large)"
 
 
@@ -165,7 +157,7 @@ class Route:
         if status == 0 and v[0] != 0:
             keys.append((FAMILY[v[1]], v[2], v[3], bool(v[4]), bool(v[5]), bool(v[6])))
             if v[13] > 0:
-                keys.append((KM.SPEC, KM.WAVE, v[14], False, False, True))
+                keys.append((KM.SPEC, RM.WAVE, v[14], False, False, True))
         return status, self.err.value, v[0], keys
 
     def phase_keys(self, ped, phase, chains, dmode, whole=True, two_pass=False, parking=False):
@@ -187,14 +179,14 @@ def route():
 def _plan_inputs(c):
     """what a plan over a MATRIX case's pedigree passes down, by the restatements: (ped, S, B, two-pass, parking, dmode of B)"""
     n, tmax, k, o = c["n"], c["tmax"], c["k"], c["opts"]
-    req, strict = o.get("lanes_per_chain", 0), KM.strict_of(n, o)
-    cs = KM.chain_stride(tmax, k)
-    lanes = KM.pick_lanes(n, req, cs)
+    req, strict = o.get("lanes_per_chain", 0), RM.strict_of(n, o)
+    cs = RM.chain_stride(tmax, k)
+    lanes = RM.pick_lanes(n, req, cs)
     S, B = c["S"], KM.boot_count(c, SMALL_WAVES, CUS)
-    two_pass = (S > KM.TWO_PASS_CHAINS and o.get("max_iters_start", 10000) > KM.PHASE_A_CAP and
+    two_pass = (S > RM.TWO_PASS_CHAINS and o.get("max_iters_start", 10000) > RM.PHASE_A_CAP and
                 bool(o.get("no_fixed_point_skip", 0)) and not o.get("shrink_on_failed_contraction", 0) and not strict)
-    parking = lanes < KM.WAVE and max(S, B) > SMALL_WAVES * (KM.WAVE // lanes)     # abn_plan_create: time slicing buffers
-    dmode_b = 2 if KM.LDS.streams(n, k, cs, lanes, strict) and not o.get("stream_mode", 0) else 1
+    parking = lanes < RM.WAVE and max(S, B) > SMALL_WAVES * (RM.WAVE // lanes)     # abn_plan_create: time slicing buffers
+    dmode_b = 2 if RM.streams(n, k, cs, lanes, strict) and not o.get("stream_mode", 0) else 1
     return (n, k, tmax, req, strict), S, B, two_pass, parking, dmode_b
 
 
@@ -205,7 +197,7 @@ def test_cpp_routes_case_to_its_instantiation(route, key):
     c = KM.MATRIX[key]
     o = c["opts"]
     if c["route"] == "cost":
-        ped = (c["n"], c["k"], c["tmax"], o.get("lanes_per_chain", 0), KM.strict_of(c["n"], o))
+        ped = (c["n"], c["k"], c["tmax"], o.get("lanes_per_chain", 0), RM.strict_of(c["n"], o))
         got = {(KM.COST, route.pedigree(ped)["cost_lanes"], 0, False, False, False)}
     else:
         ped, S, B, two_pass, parking, dmode_b = _plan_inputs(c)
@@ -213,23 +205,22 @@ def test_cpp_routes_case_to_its_instantiation(route, key):
         got |= set(route.phase_keys(ped, 1, B, dmode_b, two_pass=two_pass, parking=parking))
     assert key in got, [KM.label(k) for k in got]
     assert got <= KM.targets(c), [KM.label(k) for k in got - KM.targets(c)]
-    assert route.pedigree(ped)["reported_tree"] == KM.expected_tree(c["n"], c["tmax"], c["k"], o)
+    assert route.pedigree(ped)["reported_tree"] == RM.expected_tree(c["n"], c["tmax"], c["k"], o)
     strict_cost = (c["n"], c["k"], c["tmax"], o.get("lanes_per_chain", 0), 1)
-    assert route.pedigree(strict_cost)["cost_lanes"] == KM.WAVE       # abn_cost_batch in strict order: a wavefront per candidate
+    assert route.pedigree(strict_cost)["cost_lanes"] == RM.WAVE       # abn_cost_batch in strict order: a wavefront per candidate
 
 
 def test_cpp_routing_at_the_lds_boundaries(route):
     """tests/test_gpu_lds_boundary.py's pairs: resident or streamed as filed, the speculative kernel one step either side of
     its footprint, and abn_plan_create's refusal one step over limit_k() with acceptance at it"""
-    LDS = KM.LDS
-    for name, (n, tmax, k, o, kind) in LDS.boundary_cases().items():
+    for name, (n, tmax, k, o, kind) in RM.boundary_cases().items():
         p = route.pedigree((n, k, tmax, o.get("lanes_per_chain", 0), o.get("strict_order", 0)))
         assert not p["refused"], name
         assert bool(p["streams"]) == (kind == "stream"), name
-        assert p["reported_tree"] == LDS.expected_tree(n, k, KM.chain_stride(tmax, k), o), name
+        assert p["reported_tree"] == RM.expected_tree(n, tmax, k, o), name
         if name.startswith("spec_"):
             assert bool(p["spec_ok"]) == (name == "spec_under"), name
-    kmax = LDS.limit_k()
+    kmax = RM.limit_k()
     assert not route.pedigree((kmax + 1, kmax, 127, 0, 0))["refused"]
     assert route.pedigree((kmax + 3, kmax + 2, 127, 0, 0))["refused"]
 
@@ -253,17 +244,17 @@ def test_cpp_routing_sweep_stays_inside_the_census(route, kernels):
         p = route.pedigree(ped)
         if p["refused"]:      # abn_plan_create refuses; abn_fit_batch reaches the launch level, which refuses the same way
             status, err, _, _ = route.launch(ped, 0, p["lanes"], 1)
-            assert (status, err) == (ERR_INVALID_ARG, LDS_REFUSAL), ped
+            assert (status, err) == (RM.ERR_INVALID_ARG, LDS_REFUSAL), ped
             continue
-        ng = KM.WAVE // p["lanes"]
-        small = KM.LDS.pick_rmax(n, KM.WAVE) <= 2
-        edges = ({1, KM.TWO_PASS_CHAINS, 24 * CUS, SMALL_WAVES * ng, BIG_WAVES * ng, CUS * (16 if small else 8)},
+        ng = RM.WAVE // p["lanes"]
+        small = RM.pick_rmax(n, RM.WAVE) <= 2
+        edges = ({1, RM.TWO_PASS_CHAINS, 24 * CUS, SMALL_WAVES * ng, BIG_WAVES * ng, CUS * (16 if small else 8)},
                  {1, (3 * CUS // 4) * p["lanes"], SMALL_WAVES * ng, BIG_WAVES * ng, CUS * 6 if small else CUS * 3})
         for phase in (0, 1):
             for chains in sorted({x + d for x in edges[phase] | own.get(ped, set()) for d in (0, 1)}):
                 for dmode in ((0,) if phase == 0 else (1, 2) if p["streams"] else (1,)):
                     for whole in (False, True):           # a window group is offered neither queue nor parking buffers
-                        two = phase == 0 and whole and chains > KM.TWO_PASS_CHAINS and not ped[4]
+                        two = phase == 0 and whole and chains > RM.TWO_PASS_CHAINS and not ped[4]
                         for two_pass in ((False, True) if two else (False,)):
                             for parking in ((False, True) if whole and ng > 1 and chains > SMALL_WAVES * ng else (False,)):
                                 hits.update(route.phase_keys(ped, phase, chains, dmode, whole, two_pass, parking))

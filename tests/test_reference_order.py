@@ -11,6 +11,9 @@ the oracle's lanes = 1 (GPU tests at the end).
 import numpy as np
 import pytest
 
+from _parity import synthetic_pedigree
+from _route_model import CANON
+
 SEED = 20260101
 TOL = 1e-6   # north star: "within 1e-6 of the reference Rust" on alpha, beta, weight and the predicted divergence
 
@@ -72,7 +75,7 @@ def compare(ref, got, raw_same_model, name, max_starts, max_rows, max_frac):
 def test_tree_order_fit_is_within_1e6_of_reference_order(oracle, abn, golden, name):
     ped, p0, S, B, max_starts, max_rows, max_frac = _cases(golden)[name]
     tree = abn.reduction_tree(ped[:, :3], abn.default_options(strict_order=-1))   # the pedigree's tree (host arithmetic)
-    assert tree == 0x10040
+    assert tree == CANON
     # the DEFAULT order: the tree, except for pedigrees of up to 16 rows — the bundled one — which are summed serially
     assert abn.reduction_tree(ped[:, :3]) == (1 if ped.shape[0] <= 16 else tree)
     ref = oracle_pipeline(oracle, ped, p0, S, B, 1)
@@ -118,7 +121,7 @@ def test_hip_auto_options_against_reference_order(oracle, abn, gpu_ctx, golden, 
         topts = abn.default_options(seed=SEED, strict_order=-1)
         tgot = hip_pipeline(abn, gpu_ctx, ped, p0, S, B, topts)
         tsame, _ = gpu_ctx.boot_model_run(ped, ref["model"], ref["pred"], ref["resid"], p0, p0, 1.0, B, options=topts)
-        assert np.all(tgot["res"]["lanes"] == 0x10040)
+        assert np.all(tgot["res"]["lanes"] == CANON)
         compare(ref, tgot, tsame, name + " (tree)", max_starts, max_rows, max_frac)
 
 
@@ -146,8 +149,6 @@ def test_hip_strict_order_is_bit_equal_to_reference_order(oracle, abn, gpu_ctx, 
 def test_hip_strict_order_fit_batch_every_packing(oracle, abn, gpu_ctx, golden, lanes):
     """the serial sum does not depend on how many lanes a chain has: every packing, resident and streamed rows"""
     rng = np.random.default_rng(77 + lanes)
-    from test_gpu_parity import synthetic_pedigree
-
     for ped, p0, F, iters in ((golden["sparse"], golden["r_p0uu"], 37, 300), (golden["generated"], 0.655, 70, 400),
                              (synthetic_pedigree(rng, 700, 30), 0.8, 9, 60), (synthetic_pedigree(rng, 1500, 12), 0.7, 5, 40)):
         s0 = np.stack([oracle.start_simplex(SEED, 3, s, ped[:, 3].max()) for s in range(F)])
