@@ -1,6 +1,8 @@
 // C-ABI of libabneutral_hip.so (include/abneutral.h): host-side glue around the gfx950 kernels of
 // abn_device.hpp.  No CPU compute path exists here by design: if HIP is unusable every compute entry
 // point returns ABN_ERR_NO_DEVICE / ABN_ERR_HIP.
+#include <functional>
+
 #include "abn_host.hpp"
 #include "abn_device.hpp"
 #include "abn_route.hpp"
@@ -69,11 +71,17 @@ struct DevTopology {
   DevBuf<uint16_t> tid;
 };
 
+// allocate `count` elements and copy them from the host, on the context's stream
+template <class T>
+static int upload(abn_ctx* c, DevBuf<T>& buf, const T* host, size_t count) {
+  HIPCHK(c, buf.alloc(count));
+  HIPCHK(c, hipMemcpyAsync(buf.p, host, buf.bytes(), hipMemcpyHostToDevice, c->stream));
+  return ABN_OK;
+}
+
 static int upload_topology(abn_ctx* c, const Topology& t, DevTopology& d) {
-  HIPCHK(c, d.tri.alloc(t.tri.size()));
-  HIPCHK(c, d.tid.alloc(t.tid.size()));
-  HIPCHK(c, hipMemcpyAsync(d.tri.p, t.tri.data(), d.tri.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d.tid.p, t.tid.data(), d.tid.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (int rc = upload(c, d.tri, t.tri.data(), t.tri.size())) return rc;
+  if (int rc = upload(c, d.tid, t.tid.data(), t.tid.size())) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ABN_OK;
 }
@@ -88,6 +96,30 @@ static void fill_topology(Args& a, const Topology& t, const DevTopology& d) {
   a.T = t.T;
   a.TP = t.TP;
 }
+
+// the observed divergences of a four-column pedigree
+static std::vector<double> column3(const double* pedigree, int n) {
+  std::vector<double> d((size_t)n);
+  for (int i = 0; i < n; ++i) d[(size_t)i] = pedigree[(size_t)i * 4 + 3];
+  return d;
+}
+
+// What abn_cost_batch, abn_fit_batch and abn_select_best start with once their arguments are checked: the device, the
+// pool scope of the call, the topology of a four-column pedigree (refused with the status text) and its upload.
+// `check` (optional) runs between the two: what the caller refuses before anything is uploaded.
+struct OneShot {
+  PoolScope pool_scope;
+  Topology t;
+  DevTopology dt;
+  explicit OneShot(abn_ctx* c) : pool_scope(c) {}
+  int open(abn_ctx* c, const double* pedigree, int n_rows, const std::function<int()>& check = nullptr) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = build_topology(pedigree, n_rows, 4, t)) return set_err(c, rc, abn_status_string(rc));
+    if (check)
+      if (int rc = check()) return rc;
+    return upload_topology(c, t, dt);
+  }
+};
 
 // ------------------------------------------------------------------------------------------------
 // launchers: abn_route.hpp decides, this executes
@@ -133,8 +165,8 @@ static int launch_route(abn_ctx* c, const LaunchRoute& r, const Args& a, hipStre
   return ABN_OK;
 }
 
-// Runs a.W x a.C chains as route_launch decides.  `a` carries the topology's scratch stride and the buffers `offer`
-// promises (queue; park_*, state, susp_list, slice_status); stride, tree, quantum, tail and pass are the route's.
+// Runs a.W x a.C chains as route_launch decides.  `a` carries the buffers `offer` promises (queue; park_*, state,
+// susp_list, slice_status); chain_stride, tree, quantum, tail and pass are the route's and are set here.
 // kind (nullable): the ABN_KERNEL_* code of what was launched (PERSISTENT: a.slice_status then counts its fits)
 static int launch_fit(abn_ctx* c, const PedigreeRoute& pr, const PhaseRoute& ph, FitArgs a, const LaunchOffer& offer,
                       hipStream_t st, int* kind = nullptr) {
@@ -169,8 +201,8 @@ static int launch_fit(abn_ctx* c, const PedigreeRoute& pr, const PhaseRoute& ph,
   a.quantum = r.quantum;
   a.tail_cap = r.tail_cap;
   if (!persistent) a.queue = nullptr;
-  if (a.tail_cap > 0) a.susp_count = reinterpret_cast<int*>(a.slice_status + 3);
-  if (persistent && a.slice_status) HIPCHK(c, hipMemsetAsync(a.slice_status, 0, 4 * sizeof(unsigned), st));
+  if (a.tail_cap > 0) a.susp_count = reinterpret_cast<int*>(a.slice_status + kSliceTailFill);
+  if (persistent && a.slice_status) HIPCHK(c, hipMemsetAsync(a.slice_status, 0, kSliceWords * sizeof(unsigned), st));
   if (a.quantum > 0) {  // empty FIFO of parked chains: entries -1, head = tail = 0
     HIPCHK(c, hipMemsetAsync(a.parked, 0xff, (size_t)kParkShards * a.park_cap * sizeof(int), st));
     HIPCHK(c, hipMemsetAsync(a.park_ht, 0, (size_t)kParkShards * kParkHeaderInts * sizeof(unsigned), st));
@@ -234,6 +266,16 @@ static abn_options resolve_for(const abn_options* o, int n_rows) {
   if (d.strict_order == 0 && d.lanes_per_chain == 0 && n_rows <= kSerialSumMaxRows) d.strict_order = 1;
   else if (d.strict_order < 0) d.strict_order = 0;
   return d;
+}
+
+// what every fit launch takes from the resolved options and the pedigree's route
+static void fill_options(FitArgs& a, const abn_options& o, const PedigreeRoute& pr) {
+  a.seed = o.seed;
+  a.shrink_variant = o.shrink_on_failed_contraction ? 1 : 0;
+  a.no_skip = o.no_fixed_point_skip ? 1 : 0;
+  a.sd_tol = o.sd_tolerance;
+  a.gap_tol = kGapTolFactor * o.sd_tolerance;
+  a.strict = pr.strict;  // = (strict_order of resolve_for) != 0: route_pedigree is given that value
 }
 
 // iteration budgets must leave room for the 32-bit evaluation counters (at most 2 evaluations per iteration plus the
@@ -433,53 +475,37 @@ extern "C" int abn_cost_batch(abn_ctx* c, const abn_options* opts, const double*
   if (m == 0) return ABN_OK;
   if (const char* oe = options_error(resolve(opts))) return set_err(c, ABN_ERR_INVALID_ARG, oe);
   const abn_options o = resolve_for(opts, n_rows);
-  HIPCHK(c, hipSetDevice(c->device));
-  PoolScope pool_scope(c);
-  Topology t;
-  int rc = build_topology(pedigree, n_rows, 4, t);
-  if (rc) return set_err(c, rc, abn_status_string(rc));
-  if (idx) {
-    for (int64_t i = 0; i < m; ++i) {
-      const int64_t b = cand_to_boot ? (int64_t)cand_to_boot[i] : i;
-      if (b >= n_boot_rows) return set_err(c, ABN_ERR_INVALID_ARG, "cand_to_boot out of range");
-    }
-  }
-  DevTopology dt;
-  rc = upload_topology(c, t, dt);
+  OneShot s(c);
+  int rc = s.open(c, pedigree, n_rows, [&]() -> int {
+    for (int64_t i = 0; idx && i < m; ++i)
+      if ((cand_to_boot ? (int64_t)cand_to_boot[i] : i) >= n_boot_rows)
+        return set_err(c, ABN_ERR_INVALID_ARG, "cand_to_boot out of range");
+    return ABN_OK;
+  });
   if (rc) return rc;
-  const int N = n_rows;
-  std::vector<double> dcol((size_t)N);
-  for (int i = 0; i < N; ++i) dcol[(size_t)i] = pedigree[(size_t)i * 4 + 3];
+  const size_t N = (size_t)n_rows;
+  const std::vector<double> dcol = column3(pedigree, n_rows);
   DevBuf<double> dD, dpred, dresid, dcand, dcost, ddt, dpuu;
   DevBuf<uint32_t> didx, dc2b;
-  HIPCHK(c, dD.alloc((size_t)N));
-  HIPCHK(c, dcand.alloc((size_t)m * 4));
+  if ((rc = upload(c, dD, dcol.data(), N)) || (rc = upload(c, dcand, candidates, (size_t)m * 4))) return rc;
   HIPCHK(c, dcost.alloc((size_t)m));
-  HIPCHK(c, hipMemcpyAsync(dD.p, dcol.data(), dD.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dcand.p, candidates, dcand.bytes(), hipMemcpyHostToDevice, c->stream));
   if (idx) {
-    HIPCHK(c, dpred.alloc((size_t)N));
-    HIPCHK(c, dresid.alloc((size_t)N));
-    HIPCHK(c, didx.alloc((size_t)n_boot_rows * (size_t)N));
-    HIPCHK(c, hipMemcpyAsync(dpred.p, pred, dpred.bytes(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dresid.p, resid, dresid.bytes(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(didx.p, idx, didx.bytes(), hipMemcpyHostToDevice, c->stream));
-    for (size_t q = 0; q < (size_t)n_boot_rows * (size_t)N; ++q)
+    if ((rc = upload(c, dpred, pred, N)) || (rc = upload(c, dresid, resid, N)) ||
+        (rc = upload(c, didx, idx, (size_t)n_boot_rows * N)))
+      return rc;
+    for (size_t q = 0; q < (size_t)n_boot_rows * N; ++q)
       if (idx[q] >= (uint32_t)N) return set_err(c, ABN_ERR_INVALID_ARG, "bootstrap index out of range");
-    if (cand_to_boot) {
-      HIPCHK(c, dc2b.alloc((size_t)m));
-      HIPCHK(c, hipMemcpyAsync(dc2b.p, cand_to_boot, dc2b.bytes(), hipMemcpyHostToDevice, c->stream));
-    }
+    if (cand_to_boot && (rc = upload(c, dc2b, cand_to_boot, (size_t)m))) return rc;
   }
-  if (dt1t2) HIPCHK(c, ddt.alloc((size_t)m * (size_t)N));
+  if (dt1t2) HIPCHK(c, ddt.alloc((size_t)m * N));
   if (p_uu_inf) HIPCHK(c, dpuu.alloc((size_t)m));
 
-  const PedigreeRoute pr = route_pedigree(N, t.K, t.T, o.lanes_per_chain, o.strict_order);
+  const PedigreeRoute pr = route_pedigree(n_rows, s.t.K, s.t.T, o.lanes_per_chain, o.strict_order);
   if (pr.cost_refusal) return set_err(c, ABN_ERR_INVALID_ARG, pr.cost_refusal);
   const int ng = kWave / pr.cost_lanes;
   CostArgs a{};
-  fill_topology(a, t, dt);
-  a.chain_stride = t.chain_stride;
+  fill_topology(a, s.t, s.dt);
+  a.chain_stride = s.t.chain_stride;
   a.p_uu0 = p_uu0;
   a.eqp = eqp;
   a.eqp_w = eqp_weight;
@@ -525,67 +551,35 @@ extern "C" int abn_fit_batch(abn_ctx* c, const abn_options* opts, const double* 
   if (const char* oe = options_error(resolve(opts))) return set_err(c, ABN_ERR_INVALID_ARG, oe);
   const abn_options o = resolve_for(opts, n_rows);
   if (max_iters > (1 << 28)) return set_err(c, ABN_ERR_INVALID_ARG, "max_iters must be in 0 .. 2^28");
-  HIPCHK(c, hipSetDevice(c->device));
-  PoolScope pool_scope(c);
-  Topology t;
-  int rc = build_topology(pedigree, n_rows, 4, t);
-  if (rc) return set_err(c, rc, abn_status_string(rc));
-  DevTopology dt;
-  rc = upload_topology(c, t, dt);
+  OneShot s(c);
+  int rc = s.open(c, pedigree, n_rows);
   if (rc) return rc;
-  const int N = n_rows;
+  const size_t N = (size_t)n_rows;
   DevBuf<double> dD, ds0, dbest, dscal;
   DevBuf<FitInfoDev> dinfo;
-  std::vector<double> dcol;
-  const double* dsrc = dobs_rows;
-  size_t dcount = (size_t)f * (size_t)N;
-  if (!dobs_rows) {
-    dcol.resize((size_t)N);
-    for (int i = 0; i < N; ++i) dcol[(size_t)i] = pedigree[(size_t)i * 4 + 3];
-    dsrc = dcol.data();
-    dcount = (size_t)N;
-  }
+  const std::vector<double> dcol = dobs_rows ? std::vector<double>() : column3(pedigree, n_rows);
   const double scal[3] = {p_uu0, eqp, eqp_weight};
-  HIPCHK(c, dD.alloc(dcount));
-  HIPCHK(c, ds0.alloc((size_t)f * 20));
+  if ((rc = upload(c, dD, dobs_rows ? dobs_rows : dcol.data(), dobs_rows ? (size_t)f * N : N)) ||
+      (rc = upload(c, ds0, simplex0, (size_t)f * 20)) || (rc = upload(c, dscal, scal, 3)))
+    return rc;
   HIPCHK(c, dbest.alloc((size_t)f * 4));
   HIPCHK(c, dinfo.alloc((size_t)f));
-  HIPCHK(c, dscal.alloc(3));
-  HIPCHK(c, hipMemcpyAsync(dD.p, dsrc, dD.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(ds0.p, simplex0, ds0.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dscal.p, scal, sizeof scal, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(dinfo.p, 0, dinfo.bytes(), c->stream));
 
-  const PedigreeRoute pr = route_pedigree(N, t.K, t.T, o.lanes_per_chain, o.strict_order);
-  FitArgs a{};
-  fill_topology(a, t, dt);
-  a.chain_stride = t.chain_stride;
+  const PedigreeRoute pr = route_pedigree(n_rows, s.t.K, s.t.T, o.lanes_per_chain, o.strict_order);
+  FitArgs a{};  // wstride 0: the one set of scalars for every chain; dmode 0, smode 0: D and simplex0 as given
+  fill_topology(a, s.t, s.dt);
+  fill_options(a, o, pr);
   a.p_uu = dscal.p;
   a.eqp = dscal.p + 1;
   a.eqp_w = dscal.p + 2;
-  a.wstride = 0;
-  a.dmode = 0;
   a.D = dD.p;
-  a.smode = 0;
   a.simplex0 = ds0.p;
-  a.seed = o.seed;
-  if (dobs_rows) {  // one "window" per fit: its own observed divergences
-    a.W = (int)f;
-    a.C = 1;
-  } else {
-    a.W = 1;
-    a.C = (int)f;
-  }
+  a.W = dobs_rows ? (int)f : 1;  // one "window" per fit when each has its own observed divergences
+  a.C = dobs_rows ? 1 : (int)f;
   a.max_iters = max_iters;
-  a.shrink_variant = o.shrink_on_failed_contraction ? 1 : 0;
-  a.no_skip = o.no_fixed_point_skip ? 1 : 0;
-  a.skipped = nullptr;
-  a.sd_tol = o.sd_tolerance;
-  a.gap_tol = 64.0 * o.sd_tolerance;
   a.best = dbest.p;
   a.info = dinfo.p;
-  a.raw = nullptr;
-  a.strict = pr.strict;
   rc = launch_fit(c, pr, PhaseRoute{false, pr.lanes, false}, a, LaunchOffer{}, c->stream);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(best, dbest.p, dbest.bytes(), hipMemcpyDeviceToHost, c->stream));
@@ -597,6 +591,9 @@ extern "C" int abn_fit_batch(abn_ctx* c, const abn_options* opts, const double* 
 // ------------------------------------------------------------------------------------------------
 // (4) device-resident plan
 // ------------------------------------------------------------------------------------------------
+// the plan's timing events: the fit launches of phase A, the selection, the fit launches of phase B
+enum PlanEvent { kEvFitA, kEvFitAEnd, kEvSelect, kEvSelectEnd, kEvFitB, kEvFitBEnd, kPlanEvents };
+
 struct abn_plan {
   abn_ctx* ctx = nullptr;
   abn_options opt{};
@@ -613,21 +610,21 @@ struct abn_plan {
   DevBuf<int32_t> best_start;
   DevBuf<uint32_t> idx;
   DevBuf<double> dstar;  // stream mode: materialised bootstrap observations [W x B x N]
-  DevBuf<double> nm_state;    // two-pass phase A: parked Nelder-Mead states [W x S x 32]
+  DevBuf<double> nm_state;    // two-pass phase A: parked Nelder-Mead states [W x S x kStateDoubles]
   DevBuf<int> susp_list;      // [W x S] + 1 counter at the end
-  // per phase (A, B): [2*ph] evaluations not executed (fixed-point skip), [2*ph+1] chain queue of the persistent kernel
+  // per phase (A, B) kPhaseWords words: kPhaseSkipped evaluations not executed (fixed-point skip), kPhaseQueue the chain
+  // queue of the persistent kernel
   DevBuf<unsigned long long> skipped;
   bool twopass_a = false;
   DevBuf<int> slice_buf;      // time slicing: head, tail, then the FIFO of parked chains
   unsigned slice_cap = 0;
-  DevBuf<unsigned> slice_status;   // per phase four words: error word, fits finished by the persistent launch (and its tail's
-                                   // resume launch), chains handed to the tail, the tail list's fill count (FitArgs::slice_status)
+  DevBuf<unsigned> slice_status;   // per phase kSliceWords words (abn_constants.hpp; FitArgs::slice_status)
   long long persist_expected[2] = {0, 0};  // chains the last persistent launch of phase A / B had to finish (0: none)
   long long tail_handed[2] = {0, 0};       // ... of which its tail handed to the speculative kernel (read at the last sync)
   int32_t last_kernels[4] = {0, 0, 0, 0};  // abn_plan_last_kernels
   bool stream_b = false;
   double* raw = nullptr;  // raw_own.p or caller-bound
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev[kPlanEvents] = {};
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_join;
 };
@@ -657,7 +654,11 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
   }
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
-  abn_plan* p = new (std::nothrow) abn_plan();
+  struct Destroy {
+    void operator()(abn_plan* q) const { abn_plan_destroy(q); }
+  };
+  std::unique_ptr<abn_plan, Destroy> owner(new (std::nothrow) abn_plan());  // every early return below destroys the plan
+  abn_plan* p = owner.get();
   if (!p) return ABN_ERR_HIP;
   p->ctx = c;
   p->opt = resolve_for(opts, n_rows);  // strict_order resolved to 0 / 1 for this pedigree
@@ -668,26 +669,15 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
   p->window_offset = window_offset;
   p->boot_offset = boot_offset;
   int rc = build_topology(generations, n_rows, 3, p->topo);
-  if (rc) {
-    delete p;
-    return set_err(c, rc, abn_status_string(rc));
-  }
+  if (rc) return set_err(c, rc, abn_status_string(rc));
   // what runs is a function of the pedigree and the options, decided (and refused) here, not at the first run
   p->route = route_pedigree(n_rows, p->topo.K, p->topo.T, p->opt.lanes_per_chain, p->opt.strict_order);
-  if (p->route.refusal) {
-    const char* why = p->route.refusal;
-    delete p;
-    return set_err(c, ABN_ERR_INVALID_ARG, why);
-  }
+  if (p->route.refusal) return set_err(c, ABN_ERR_INVALID_ARG, p->route.refusal);
   auto fail = [&](hipError_t e, const char* what) {
-    abn_plan_destroy(p);
     return set_err(c, ABN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
   };
   rc = upload_topology(c, p->topo, p->dtopo);
-  if (rc) {
-    abn_plan_destroy(p);
-    return rc;
-  }
+  if (rc) return rc;
   const size_t W = (size_t)n_windows, N = (size_t)n_rows, S = (size_t)n_starts, B = (size_t)n_boot;
   hipError_t e;
 #define PALLOC(buf, count)                         \
@@ -708,17 +698,17 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
   PALLOC(bestB, W * B * 4);
   PALLOC(infoB, W * B);
   PALLOC(raw_own, W * B * 7);
-  PALLOC(skipped, 4);
-  PALLOC(slice_status, 8);
+  PALLOC(skipped, 2 * kPhaseWords);
+  PALLOC(slice_status, 2 * kSliceWords);
   p->twopass_a = plan_two_pass((long long)n_windows * n_starts, p->opt.max_iters_start, p->opt.no_fixed_point_skip,
                                p->opt.shrink_on_failed_contraction, p->opt.strict_order);
   if (p->twopass_a) {
-    PALLOC(nm_state, W * S * 32);
+    PALLOC(nm_state, W * S * kStateDoubles);
     PALLOC(susp_list, W * S + 1);
   }
   // time slicing for launches that outgrow the resident set of the persistent kernel: parked states, the FIFOs, the tail list
   if (const size_t chains = plan_sliced_chains(p->route, W * std::max(S, B), c->cus, p->opt.window_groups)) {
-    if (p->nm_state.n < chains * 32) PALLOC(nm_state, chains * 32);
+    if (p->nm_state.n < chains * kStateDoubles) PALLOC(nm_state, chains * kStateDoubles);
     p->slice_cap = (unsigned)(chains * 16 / kParkShards + 4096);   // per shard; a full shard just stops parking
     PALLOC(slice_buf, (size_t)kParkShards * ((size_t)kParkHeaderInts + (size_t)p->slice_cap));
     if (p->susp_list.n < chains + 1) PALLOC(susp_list, chains + 1);  // the tail list of the hand-over to the speculative kernel
@@ -729,7 +719,7 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
   p->raw = p->raw_own.p;
   for (auto& ev : p->ev)
     if ((e = hipEventCreate(&ev)) != hipSuccess) return fail(e, "hipEventCreate");
-  *out = p;
+  *out = owner.release();
   return ABN_OK;
 }
 
@@ -763,8 +753,7 @@ extern "C" int abn_plan_set_window_ids(abn_plan* p, const uint32_t* ids) {
     return ABN_OK;
   }
   p->wid_host.assign(ids, ids + p->W);
-  HIPCHK(c, p->wid.alloc((size_t)p->W));
-  HIPCHK(c, hipMemcpyAsync(p->wid.p, p->wid_host.data(), p->wid.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (int rc = upload(c, p->wid, p->wid_host.data(), (size_t)p->W)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ABN_OK;
 }
@@ -800,29 +789,44 @@ extern "C" int abn_plan_set_windows(abn_plan* p, const double* d_obs, const doub
   return ABN_OK;
 }
 
-static void fill_common(const abn_plan* p, FitArgs& a) {
+// element offsets of window w0 in the plan's buffers: per window, per pedigree row, per start and per bootstrap
+struct WindowOffsets {
+  size_t w, rows, starts, boots;
+};
+static WindowOffsets window_offsets(const abn_plan* p, int w0) {
+  const size_t o = (size_t)w0;
+  return {o, o * (size_t)p->N, o * (size_t)p->S, o * (size_t)p->B};
+}
+
+// The FitArgs of windows [w0, w0 + wn) for phase 0 = A (starts) or 1 = B (bootstraps): every slice of the plan's buffers
+// is taken here.  What a launch decides (chain_stride, tree, quantum, ...) is launch_fit's, what it is offered launch_phase's.
+static FitArgs phase_args(const abn_plan* p, int phase, int w0, int wn) {
+  const WindowOffsets o = window_offsets(p, w0);
+  const size_t chains = phase ? o.boots : o.starts;
+  FitArgs a{};
   fill_topology(a, p->topo, p->dtopo);
-  a.chain_stride = p->topo.chain_stride;
-  a.p_uu = p->p_uu.p;
-  a.eqp = p->eqp.p;
-  a.eqp_w = p->eqp_w.p;
+  fill_options(a, p->opt, p->route);
+  a.p_uu = p->p_uu.p + o.w;
+  a.eqp = p->eqp.p + o.w;
+  a.eqp_w = p->eqp_w.p + o.w;
   a.wstride = 1;
-  a.D = p->D.p;
-  a.pred = p->pred.p;
-  a.resid = p->resid.p;
-  a.idx = p->idx.p;
-  a.model = p->model.p;
-  a.seed = p->opt.seed;
-  a.window_offset = p->window_offset;
+  a.D = p->D.p + o.rows;
+  a.pred = p->pred.p + o.rows;
+  a.resid = p->resid.p + o.rows;
+  a.idx = p->idx.p + o.boots * (size_t)p->N;
+  a.model = p->model.p + o.w * 4;
+  a.window_offset = p->window_offset + (uint32_t)w0;
   a.boot_offset = p->boot_offset;
-  a.wid = p->wid.p;
-  a.tree = p->route.tree;
-  a.strict = p->opt.strict_order ? 1 : 0;
-  a.W = p->W;
-  a.shrink_variant = p->opt.shrink_on_failed_contraction ? 1 : 0;
-  a.no_skip = p->opt.no_fixed_point_skip ? 1 : 0;
-  a.sd_tol = p->opt.sd_tolerance;
-  a.gap_tol = 64.0 * p->opt.sd_tolerance;
+  a.wid = p->wid.p ? p->wid.p + o.w : nullptr;
+  a.W = wn;
+  a.C = phase ? p->B : p->S;
+  a.dmode = a.smode = phase;  // A: D and the start simplices as given; B: pred + resampled resid, simplices from Philox
+  a.simplex0 = phase ? nullptr : p->simplexA.p + chains * 20;
+  a.max_iters = phase ? p->opt.max_iters_boot : p->opt.max_iters_start;
+  a.best = (phase ? p->bestB.p : p->bestA.p) + chains * 4;
+  a.info = (phase ? p->infoB.p : p->infoA.p) + chains;
+  a.raw = phase ? p->raw + chains * 7 : nullptr;
+  return a;
 }
 
 // The fit launch(es) of one phase (0 = A, 1 = B) for the windows `a` covers, on stream st.  A launch that covers the whole
@@ -840,10 +844,10 @@ static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool
   LaunchOffer offer;
   offer.queue = whole;
   offer.parking = whole && p->slice_cap > 0;
-  a.skipped = p->skipped.p + 2 * phase;
+  a.skipped = p->skipped.p + kPhaseWords * phase + kPhaseSkipped;
   if (whole) {
-    a.queue = reinterpret_cast<unsigned*>(p->skipped.p + 2 * phase + 1);
-    a.slice_status = p->slice_status.p + 4 * phase;
+    a.queue = reinterpret_cast<unsigned*>(p->skipped.p + kPhaseWords * phase + kPhaseQueue);
+    a.slice_status = p->slice_status.p + kSliceWords * phase;
   }
   if (offer.parking) {
     a.park_cap = p->slice_cap;
@@ -879,27 +883,11 @@ static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool
 // the kernels.
 static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool timed) {
   abn_ctx* c = p->ctx;
-  const size_t N = (size_t)p->N, S = (size_t)p->S, o = (size_t)w0;
-  FitArgs a{};
-  fill_common(p, a);
-  a.p_uu += o;
-  a.eqp += o;
-  a.eqp_w += o;
-  a.D += o * N;
-  a.window_offset += (uint32_t)w0;
-  if (a.wid) a.wid += o;
-  a.W = wn;
-  a.dmode = 0;
-  a.smode = 0;
-  a.simplex0 = p->simplexA.p + o * S * 20;
-  a.C = p->S;
-  a.max_iters = p->opt.max_iters_start;
-  a.best = p->bestA.p + o * S * 4;
-  a.info = p->infoA.p + o * S;
-  a.raw = nullptr;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[0], st));
+  FitArgs a = phase_args(p, 0, w0, wn);
+  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitA], st));
   if (int rc = launch_phase(p, 0, a, st, timed)) return rc;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[1], st));
+  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitAEnd], st));
+  const WindowOffsets o = window_offsets(p, w0);
   SelectArgs s{};
   fill_topology(s, p->topo, p->dtopo);
   s.p_uu = a.p_uu;
@@ -908,43 +896,24 @@ static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
   s.info = a.info;
   s.W = wn;
   s.S = p->S;
-  s.lse = p->lse.p + o * S;
-  s.model = p->model.p + o * 4;
-  s.pred = p->pred.p + o * N;
-  s.resid = p->resid.p + o * N;
-  s.best_start = p->best_start.p + o;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[2], st));
+  s.lse = p->lse.p + o.starts;
+  s.model = p->model.p + o.w * 4;
+  s.pred = p->pred.p + o.rows;
+  s.resid = p->resid.p + o.rows;
+  s.best_start = p->best_start.p + o.w;
+  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvSelect], st));
   if (int rc = launch_select(c, s, p->route.select_lds, st)) return rc;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[3], st));
+  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvSelectEnd], st));
   return ABN_OK;
 }
 
 // Phase B (bootstraps) for windows [w0, w0+wn) on stream st
 static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool timed) {
   abn_ctx* c = p->ctx;
-  const size_t N = (size_t)p->N, B = (size_t)p->B, o = (size_t)w0;
-  FitArgs a{};
-  fill_common(p, a);
-  a.p_uu += o;
-  a.eqp += o;
-  a.eqp_w += o;
-  a.pred += o * N;
-  a.resid += o * N;
-  a.idx += o * B * N;
-  a.model += o * 4;
-  a.window_offset += (uint32_t)w0;
-  if (a.wid) a.wid += o;
-  a.W = wn;
-  a.dmode = 1;
-  a.smode = 1;
-  a.C = p->B;
-  a.max_iters = p->opt.max_iters_boot;
-  a.best = p->bestB.p + o * B * 4;
-  a.info = p->infoB.p + o * B;
-  a.raw = p->raw + o * B * 7;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[4], st));
+  FitArgs a = phase_args(p, 1, w0, wn);
+  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitB], st));
   if (p->stream_b) {  // gather the bootstrap observations once per fit, then stream them
-    double* dst = p->dstar.p + o * B * N;
+    double* dst = p->dstar.p + window_offsets(p, w0).boots * (size_t)p->N;
     const long long total = (long long)wn * p->B * p->N;
     const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 64LL * c->cus);
     hipLaunchKernelGGL(abn_make_dstar_kernel, dim3(blocks), dim3(256), 0, st, dst, a.pred, a.resid, a.idx, p->N,
@@ -954,19 +923,27 @@ static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
     a.D = dst;
   }
   if (int rc = launch_phase(p, 1, a, st, timed)) return rc;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[5], st));
+  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitBEnd], st));
   return ABN_OK;
 }
 
-// zero_skipped: bit 0 / bit 1 = clear the phase-A / phase-B skip counter and chain queue before the launch
-static int plan_run_phase(abn_plan* p, int32_t phase, int zero_skipped) {
+// zero the skip counter and the chain queue (abn_plan::skipped) of `n` phases from phase `first`, in one memset
+static int clear_phase_words(abn_plan* p, int first, int n) {
+  HIPCHK(p->ctx, hipMemsetAsync(p->skipped.p + kPhaseWords * first, 0, (size_t)n * kPhaseWords * sizeof(unsigned long long),
+                                p->ctx->stream));
+  return ABN_OK;
+}
+
+// which of those words a phase's run zeroes before its launch: none (the other phase's run did), its own, or both phases'
+enum ClearWords { kClearNone, kClearOwnPhase, kClearBothPhases };
+static int plan_run_phase(abn_plan* p, int32_t phase, ClearWords clear) {
   abn_ctx* c = p->ctx;
   if (!p->windows_set) return set_err(c, ABN_ERR_STATE, "abn_plan_set_windows has not been called");
   HIPCHK(c, hipSetDevice(c->device));
-  if (zero_skipped == 3) {
-    HIPCHK(c, hipMemsetAsync(p->skipped.p, 0, 4 * sizeof(unsigned long long), c->stream));
-  } else if (zero_skipped) {
-    HIPCHK(c, hipMemsetAsync(p->skipped.p + 2 * (zero_skipped >> 1), 0, 2 * sizeof(unsigned long long), c->stream));
+  if (clear == kClearBothPhases) {
+    if (int rc = clear_phase_words(p, 0, 2)) return rc;
+  } else if (clear == kClearOwnPhase) {
+    if (int rc = clear_phase_words(p, phase == 0 ? 0 : 1, 1)) return rc;
   }
   if (phase == 0) {
     if (p->S <= 0) return set_err(c, ABN_ERR_STATE, "plan has no starts");
@@ -989,7 +966,7 @@ static int plan_run_phase(abn_plan* p, int32_t phase, int zero_skipped) {
 
 extern "C" int abn_plan_run_phase(abn_plan* p, int32_t phase) {
   if (!p) return ABN_ERR_INVALID_ARG;
-  return plan_run_phase(p, phase, phase == 0 ? 1 : 2);
+  return plan_run_phase(p, phase, kClearOwnPhase);
 }
 
 // Whole pass.  opts.window_groups > 1 cuts the plan into contiguous window groups that run A -> select -> B
@@ -1005,9 +982,9 @@ extern "C" int abn_plan_run(abn_plan* p) {
   groups = std::max(1, std::min(groups, p->W));
   if (groups == 1 || p->S <= 0 || p->B <= 0) {
     int rc = ABN_OK;
-    if (p->S > 0) rc = plan_run_phase(p, 0, 3);  // one memset clears both skip counters
+    if (p->S > 0) rc = plan_run_phase(p, 0, kClearBothPhases);  // one memset for both phases
     if (rc) return rc;
-    if (p->B > 0) rc = plan_run_phase(p, 1, p->S > 0 ? 0 : 2);
+    if (p->B > 0) rc = plan_run_phase(p, 1, p->S > 0 ? kClearNone : kClearOwnPhase);
     return rc;
   }
   HIPCHK(c, hipSetDevice(c->device));
@@ -1022,7 +999,7 @@ extern "C" int abn_plan_run(abn_plan* p) {
     HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     p->ev_join.push_back(e);
   }
-  HIPCHK(c, hipMemsetAsync(p->skipped.p, 0, 4 * sizeof(unsigned long long), c->stream));
+  if (int rc = clear_phase_words(p, 0, 2)) return rc;
   HIPCHK(c, hipEventRecord(p->ev_fork, c->stream));
   for (int g = 0; g < groups; ++g) {
     const int w0 = (int)((long long)p->W * g / groups), w1 = (int)((long long)p->W * (g + 1) / groups);
@@ -1051,18 +1028,19 @@ extern "C" int abn_plan_run(abn_plan* p) {
 static int verify_persistent(abn_plan* p) {
   abn_ctx* c = p->ctx;
   HIPCHK(c, hipSetDevice(c->device));
-  unsigned sl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned sl[2][kSliceWords] = {};
   const bool check = p->persist_expected[0] > 0 || p->persist_expected[1] > 0;
   if (check) HIPCHK(c, hipMemcpyAsync(sl, p->slice_status.p, sizeof sl, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int ph = 0; ph < 2 && check; ++ph) {
     if (p->persist_expected[ph] <= 0) continue;
-    p->tail_handed[ph] = (long long)sl[4 * ph + 2];
-    if (sl[4 * ph] != 0 || (long long)sl[4 * ph + 1] != p->persist_expected[ph])
+    const unsigned* s = sl[ph];
+    p->tail_handed[ph] = (long long)s[kSliceHanded];
+    if (s[kSliceError] != 0 || (long long)s[kSliceFinished] != p->persist_expected[ph])
       return set_err(c, ABN_ERR_HIP, std::string("persistent fit launch of phase ") + (ph ? "B" : "A") + " finished " +
-                                         std::to_string(sl[4 * ph + 1]) + " of " + std::to_string(p->persist_expected[ph]) +
-                                         " chains (error word " + std::to_string(sl[4 * ph]) + ", " + std::to_string(sl[4 * ph + 2]) +
-                                         " handed to the speculative kernel, list length " + std::to_string(sl[4 * ph + 3]) +
+                                         std::to_string(s[kSliceFinished]) + " of " + std::to_string(p->persist_expected[ph]) +
+                                         " chains (error word " + std::to_string(s[kSliceError]) + ", " + std::to_string(s[kSliceHanded]) +
+                                         " handed to the speculative kernel, list length " + std::to_string(s[kSliceTailFill]) +
                                          "): results are incomplete");
   }
   return ABN_OK;
@@ -1088,13 +1066,13 @@ extern "C" int abn_plan_kernel_ms(abn_plan* p, double* ms3) {
   ms3[0] = ms3[1] = ms3[2] = 0.0;
   float ms = 0.f;
   if (p->ran_a) {
-    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
+    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[kEvFitA], p->ev[kEvFitAEnd]));
     ms3[0] = ms;
-    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[2], p->ev[3]));
+    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[kEvSelect], p->ev[kEvSelectEnd]));
     ms3[1] = ms;
   }
   if (p->ran_b) {
-    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[4], p->ev[5]));
+    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[kEvFitB], p->ev[kEvFitBEnd]));
     ms3[2] = ms;
   }
   return ABN_OK;
@@ -1164,7 +1142,7 @@ extern "C" int abn_plan_counters(abn_plan* p, int64_t* out5) {
     h.resize(b.n);
     unsigned long long sk = 0;
     HIPCHK(c, hipMemcpyAsync(h.data(), b.p, b.bytes(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&sk, p->skipped.p + 2 * phase, sizeof sk, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&sk, p->skipped.p + kPhaseWords * phase + kPhaseSkipped, sizeof sk, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (const auto& f : h) {
       out5[0] += 1;
@@ -1188,16 +1166,7 @@ static int debug_stamps(abn_plan* p, unsigned long long* out8, bool spec) {
   DevBuf<unsigned long long> d;
   HIPCHK(c, d.alloc(8));
   HIPCHK(c, hipMemsetAsync(d.p, 0, 64, c->stream));
-  FitArgs a{};
-  fill_common(p, a);
-  a.dmode = 0;
-  a.smode = 0;
-  a.simplex0 = p->simplexA.p;
-  a.C = p->S;
-  a.max_iters = p->opt.max_iters_start;
-  a.best = p->bestA.p;
-  a.info = p->infoA.p;
-  a.raw = nullptr;
+  FitArgs a = phase_args(p, 0, 0, p->W);
   a.dbg = d.p;
   int rc = launch_fit(c, p->route, PhaseRoute{spec, p->route.lanes, false}, a, LaunchOffer{}, c->stream);
   if (rc) return rc;
@@ -1234,13 +1203,8 @@ extern "C" int abn_plan_device_bytes(abn_plan* p, int64_t* bytes) {
 // ------------------------------------------------------------------------------------------------
 static void split_pedigree(const double* ped, int n, std::vector<double>& gens, std::vector<double>& d) {
   gens.resize((size_t)n * 3);
-  d.resize((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    gens[(size_t)i * 3 + 0] = ped[(size_t)i * 4 + 0];
-    gens[(size_t)i * 3 + 1] = ped[(size_t)i * 4 + 1];
-    gens[(size_t)i * 3 + 2] = ped[(size_t)i * 4 + 2];
-    d[(size_t)i] = ped[(size_t)i * 4 + 3];
-  }
+  d = column3(ped, n);
+  for (size_t i = 0; i < (size_t)n; ++i) std::copy(ped + i * 4, ped + i * 4 + 3, gens.begin() + i * 3);
 }
 
 extern "C" int abn_ab_neutral_run(abn_ctx* c, const abn_options* opts, const double* pedigree, int32_t n_rows,
@@ -1305,37 +1269,29 @@ extern "C" int abn_select_best(abn_ctx* c, const double* pedigree, int32_t n_row
   if (!c) return ABN_ERR_INVALID_ARG;
   if (!pedigree || n_rows <= 0 || !models || n_models <= 0 || !best_index)
     return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
-  HIPCHK(c, hipSetDevice(c->device));
-  PoolScope pool_scope(c);
-  Topology t;
-  int rc = build_topology(pedigree, n_rows, 4, t);
-  if (rc) return set_err(c, rc, abn_status_string(rc));
-  const PedigreeRoute pr = route_pedigree(n_rows, t.K, t.T, 0, 0);
-  if (pr.select_refusal) return set_err(c, ABN_ERR_INVALID_ARG, pr.select_refusal);
-  DevTopology dt;
-  rc = upload_topology(c, t, dt);
+  OneShot s(c);
+  PedigreeRoute pr{};
+  int rc = s.open(c, pedigree, n_rows, [&]() -> int {
+    pr = route_pedigree(n_rows, s.t.K, s.t.T, 0, 0);
+    return pr.select_refusal ? set_err(c, ABN_ERR_INVALID_ARG, pr.select_refusal) : ABN_OK;
+  });
   if (rc) return rc;
   const size_t N = (size_t)n_rows, S = (size_t)n_models;
-  std::vector<double> dcol(N);
-  for (size_t i = 0; i < N; ++i) dcol[i] = pedigree[i * 4 + 3];
+  const std::vector<double> dcol = column3(pedigree, n_rows);
   DevBuf<double> dD, dm, dlse, dmodel, dpred, dresid, dp;
   DevBuf<FitInfoDev> dinfo;
   DevBuf<int32_t> dbest;
-  HIPCHK(c, dD.alloc(N));
-  HIPCHK(c, dm.alloc(S * 4));
+  if ((rc = upload(c, dD, dcol.data(), N)) || (rc = upload(c, dm, models, S * 4)) || (rc = upload(c, dp, &p0uu, 1)))
+    return rc;
   HIPCHK(c, dlse.alloc(S));
   HIPCHK(c, dmodel.alloc(4));
   HIPCHK(c, dpred.alloc(N));
   HIPCHK(c, dresid.alloc(N));
-  HIPCHK(c, dp.alloc(1));
   HIPCHK(c, dinfo.alloc(S));
   HIPCHK(c, dbest.alloc(1));
-  HIPCHK(c, hipMemcpyAsync(dD.p, dcol.data(), dD.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dm.p, models, dm.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dp.p, &p0uu, sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(dinfo.p, 0, dinfo.bytes(), c->stream));  // status 0: every model is a candidate
   SelectArgs a{};
-  fill_topology(a, t, dt);
+  fill_topology(a, s.t, s.dt);
   a.p_uu = dp.p;
   a.D = dD.p;
   a.models = dm.p;
@@ -1366,9 +1322,8 @@ extern "C" int abn_bootstrap_rows(abn_ctx* c, const double* best, int64_t n_boot
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
   DevBuf<double> db, dr;
-  HIPCHK(c, db.alloc((size_t)n_boot * 4));
+  if (int rc = upload(c, db, best, (size_t)n_boot * 4)) return rc;
   HIPCHK(c, dr.alloc((size_t)n_boot * 7));
-  HIPCHK(c, hipMemcpyAsync(db.p, best, db.bytes(), hipMemcpyHostToDevice, c->stream));
   const unsigned blocks = (unsigned)std::min<long long>((n_boot + 255) / 256, 4096);
   hipLaunchKernelGGL(abn_rows_kernel, dim3(blocks), dim3(256), 0, c->stream, db.p, (long long)n_boot, dr.p);
   HIPCHK(c, hipGetLastError());

@@ -49,7 +49,7 @@ constexpr int ST_CONTRACT = 7;  // evaluating the contracted point
 constexpr int ST_SHRINK1 = 8;   // 8..11: evaluating shrunk vertex k = st-7
 constexpr int ST_DONE = 12;
 constexpr int kFitSuspended = 4;  // internal status between the two passes of a long chain
-constexpr unsigned kSliceErrLostEntry = 1u;  // FitArgs::slice_status[0]
+constexpr unsigned kSliceErrLostEntry = 1u;  // FitArgs::slice_status[kSliceError]
 
 struct FitInfoDev {  // layout of abn_fit_info (include/abneutral.h)
   double best_cost;
@@ -99,13 +99,13 @@ struct FitArgs {
   int W, C;
   int max_iters;
   // Two-pass execution of long chains (abn_api.hip: phase A with many chains).  Pass 1: iter_cap > 0 — a chain
-  // that is still running after iter_cap iterations stores its Nelder-Mead state (32 doubles) and appends its
+  // that is still running after iter_cap iterations stores its Nelder-Mead state (kStateDoubles doubles, abn_constants.hpp) and appends its
   // index to susp_list.  Pass 2: resume != 0 — block b, group g continues chain susp_list[b*NG+g] (for
   // b*NG+g < *susp_count) from the stored state to the end.  Same arithmetic either way: results are
   // bit-identical to an uninterrupted run.
   int iter_cap;          // 0 = unlimited
   int resume;
-  double* state;         // [W*C*32]
+  double* state;         // [W*C*kStateDoubles]
   int* susp_list;        // [W*C]
   int* susp_count;       // [1]
   int shrink_variant;
@@ -118,7 +118,7 @@ struct FitArgs {
   unsigned long long* skipped;
   unsigned* queue;       // abn_fit_refill_kernel: next chain to start (zeroed by the host); nullptr = no persistent launch
   // Time slicing in the persistent kernel (quantum > 0).  A chain that has run `quantum` evaluations while others wait
-  // (unstarted chains in the queue, or parked ones) stores its state (`state`, 32 doubles, as the two-pass hand-over)
+  // (unstarted chains in the queue, or parked ones) stores its state (`state`, kStateDoubles doubles, as the two-pass hand-over)
   // at its next iteration boundary and appends itself to the FIFO `parked`; its group takes the next waiting chain —
   // a fresh one while there are any, else the oldest parked one.  Chains of very different length then advance
   // together and the launch no longer ends with a few long chains on an idle GPU.  Same arithmetic, same bits.
@@ -130,16 +130,18 @@ struct FitArgs {
   unsigned park_cap;     // entries of parked[] PER SHARD (kParkShards shards, each with its own three counters)
   unsigned* park_ht;
   int* parked;
-  // persistent launches: slice_status[0] |= kSliceErrLostEntry when a claimed FIFO entry never appeared (the group goes
-  // idle, the chain's outputs stay unwritten), slice_status[1] += chains finished (results written).  The host compares
-  // the count with W x C after a time-sliced launch: a lost or never-resumed chain is an error, not stale output.
+  // persistent launches (kSliceWords words, abn_constants.hpp): slice_status[kSliceError] |= kSliceErrLostEntry when a
+  // claimed FIFO entry never appeared (the group goes idle, the chain's outputs stay unwritten),
+  // slice_status[kSliceFinished] += chains finished (results written).  The host compares the count with W x C after a
+  // time-sliced launch: a lost or never-resumed chain is an error, not stale output.
   unsigned* slice_status;
   // Tail hand-over of a time-sliced persistent launch (tail_cap > 0): once no chain waits any more (queue and this workgroup's
   // FIFO empty) and at most tail_cap chains of the launch are unfinished, the running chains park at their next iteration
   // boundary — state as for time slicing, index appended to susp_list — and the launch ends; abn_fit_spec_kernel (spec_resume
   // != 0: workgroup b takes chain susp_list[b], b < *susp_count, up from `state`) runs them to the end with four wavefronts
   // per chain: the long chains that would otherwise finish one by one on an emptying GPU at the packed kernel's step time.
-  // Same arithmetic, same bits; slice_status[2] counts the chains handed over.
+  // Same arithmetic, same bits; slice_status[kSliceHanded] counts the chains handed over and susp_count is
+  // slice_status + kSliceTailFill.
   int tail_cap;
   int spec_resume;
 #ifdef ABN_MEASUREMENT_KNOBS
@@ -151,7 +153,7 @@ struct FitArgs {
   int drop_entry;        // fault injection for the tests: FIFO shard 0 never publishes its first entry
 #endif
   double sd_tol;
-  double gap_tol;        // 64 * sd_tol, precomputed on the host so that it stays a scalar (kernarg) operand
+  double gap_tol;        // kGapTolFactor * sd_tol, precomputed on the host so that it stays a scalar (kernarg) operand
   // outputs (fit order)
   double* best;          // [W*C*4]
   FitInfoDev* info;      // [W*C]

@@ -384,18 +384,18 @@ __global__ __launch_bounds__(kWave, TWOPASS ? 2 : (RMAX == 0 ? kStreamWaves : 3)
   } else if (TWOPASS && valid) {
     // continue a suspended chain: simplex (this lane's dimension), costs, best-so-far and counters as stored
     // at an iteration boundary; centroid and reflection are recomputed (same arithmetic, same bits)
-    const double* sp = a.state + (size_t)chain * 32;
+    const double* sp = a.state + (size_t)chain * kStateDoubles;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-      vx[k] = sp[4 * k + dim];
-      c[k] = sp[20 + k];
+      vx[k] = sp[kStateSimplex + 4 * k + dim];
+      c[k] = sp[kStateCosts + k];
     }
-    bx = sp[25 + dim];
-    best_cost = sp[29];
-    const int* ip = reinterpret_cast<const int*>(sp + 30);
-    iter = ip[0];
-    evals = ip[1];
-    have_best = ip[2] != 0;
+    bx = sp[kStateBest + dim];
+    best_cost = sp[kStateBestCost];
+    const int* ip = reinterpret_cast<const int*>(sp + kStateIterEvals);
+    iter = ip[kStateIntIter];
+    evals = ip[kStateIntEvals];
+    have_best = ip[kStateIntHaveBest] != 0;
     double acc = vx[0];
     acc = acc + vx[1];
     acc = acc + vx[2];
@@ -474,21 +474,21 @@ __global__ __launch_bounds__(kWave, TWOPASS ? 2 : (RMAX == 0 ? kStreamWaves : 3)
 #endif
   // ---- first pass of a two-pass run: park the chains that hit the iteration cap
   if (TWOPASS && valid && fin_status == kFitSuspended) {
-    double* sp = a.state + (size_t)chain * 32;
+    double* sp = a.state + (size_t)chain * kStateDoubles;
     if (gl < 4) {
 #pragma unroll
-      for (int k = 0; k < 5; ++k) sp[4 * k + gl] = vx[k];
-      sp[25 + gl] = bx;
+      for (int k = 0; k < 5; ++k) sp[kStateSimplex + 4 * k + gl] = vx[k];
+      sp[kStateBest + gl] = bx;
     }
     if (gl == 0) {
 #pragma unroll
-      for (int k = 0; k < 5; ++k) sp[20 + k] = c[k];
-      sp[29] = best_cost;
-      int* ip = reinterpret_cast<int*>(sp + 30);
-      ip[0] = iter;
-      ip[1] = evals;
-      ip[2] = have_best ? 1 : 0;
-      ip[3] = 0;
+      for (int k = 0; k < 5; ++k) sp[kStateCosts + k] = c[k];
+      sp[kStateBestCost] = best_cost;
+      int* ip = reinterpret_cast<int*>(sp + kStateIterEvals);
+      ip[kStateIntIter] = iter;
+      ip[kStateIntEvals] = evals;
+      ip[kStateIntHaveBest] = have_best ? 1 : 0;
+      ip[kStateIntZero] = 0;
       a.susp_list[atomicAdd(a.susp_count, 1)] = (int)chain;
     }
   }

@@ -161,19 +161,19 @@ __global__ __launch_bounds__(kWave, ABN_REFILL_MIN_WAVES) void abn_fit_refill_ke
         dobs[i] = (a.dmode == 1) ? a.pred[wN + i] + a.resid[wN + idx_row[i]] : a.D[dN + i];
     }
     // agent-scope loads (past the caches, as the parking group's stores): no cache invalidation needed
-    double* sp = a.state + (size_t)chain * 32;
+    double* sp = a.state + (size_t)chain * kStateDoubles;
     auto ld = [&](int i) { return __hip_atomic_load(sp + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-      vx[k] = ld(4 * k + dim);
-      c[k] = ld(20 + k);
+      vx[k] = ld(kStateSimplex + 4 * k + dim);
+      c[k] = ld(kStateCosts + k);
     }
-    bx = ld(25 + dim);
-    best_cost = ld(29);
-    const long long ie = __double_as_longlong(ld(30));
+    bx = ld(kStateBest + dim);
+    best_cost = ld(kStateBestCost);
+    const long long ie = __double_as_longlong(ld(kStateIterEvals));
     iter = (int)(ie & 0xffffffffll);
     evals = (int)(ie >> 32);
-    have_best = __double_as_longlong(ld(31)) != 0;
+    have_best = __double_as_longlong(ld(kStateHaveBest)) != 0;
     fin_status = 2;
     fr = 0.0;
     double acc = vx[0];
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(kWave, ABN_REFILL_MIN_WAVES) void abn_fit_refill_ke
       if (lane == 0) {
         const unsigned fq = __hip_atomic_load(a.queue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int av = __hip_atomic_load(reinterpret_cast<int*>(pht) + kParkAvail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned fin = __hip_atomic_load(a.slice_status + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned fin = __hip_atomic_load(a.slice_status + kSliceFinished, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         t = (gridDim.x * NG + fq >= total && av <= 0 && total - fin <= (unsigned)a.tail_cap) ? 1 : 0;
       }
       tail_mode = __builtin_amdgcn_readfirstlane(t) != 0;
@@ -421,25 +421,25 @@ __global__ __launch_bounds__(kWave, ABN_REFILL_MIN_WAVES) void abn_fit_refill_ke
       const double b0 = dpp_mov<kDppQuadBcast0>(bx), b1 = dpp_mov<kDppQuadBcast1>(bx);
       unsigned nxt = 0xffffffffu;
       const bool parking = fin && fin_status == kFitSuspended;
-      if (parking) {  // time slicing: the chain's state (32 doubles), stored past the caches (agent scope): the group
-        double* sp = a.state + (size_t)chain * 32;  // that takes the chain up again may sit on another XCD
+      if (parking) {  // time slicing: the chain's state (kStateDoubles doubles), stored past the caches (agent scope): the group
+        double* sp = a.state + (size_t)chain * kStateDoubles;  // that takes the chain up again may sit on another XCD
         auto sd = [&](int i, double v) { __hip_atomic_store(sp + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
         if (gl < 4) {
 #pragma unroll
-          for (int k = 0; k < 5; ++k) sd(4 * k + gl, vx[k]);
-          sd(25 + gl, bx);
+          for (int k = 0; k < 5; ++k) sd(kStateSimplex + 4 * k + gl, vx[k]);
+          sd(kStateBest + gl, bx);
         }
         if (gl == 0) {
 #pragma unroll
-          for (int k = 0; k < 5; ++k) sd(20 + k, c[k]);
-          sd(29, best_cost);
-          sd(30, __longlong_as_double((long long)(unsigned)iter | ((long long)evals << 32)));
-          sd(31, __longlong_as_double(have_best ? 1ll : 0ll));
+          for (int k = 0; k < 5; ++k) sd(kStateCosts + k, c[k]);
+          sd(kStateBestCost, best_cost);
+          sd(kStateIterEvals, __longlong_as_double((long long)(unsigned)iter | ((long long)evals << 32)));
+          sd(kStateHaveBest, __longlong_as_double(have_best ? 1ll : 0ll));
         }
       } else if (fin) {
         if (gl < 4) a.best[(size_t)chain * 4 + gl] = bx;
         if (gl == 0) {
-          if (a.slice_status) atomicAdd(a.slice_status + 1, 1u);  // fits finished (no return value: nobody waits for it)
+          if (a.slice_status) atomicAdd(a.slice_status + kSliceFinished, 1u);  // fits finished (no return value: nobody waits for it)
           FitInfoDev fo;
           fo.best_cost = best_cost;
           fo.iters = iter;
@@ -468,7 +468,7 @@ __global__ __launch_bounds__(kWave, ABN_REFILL_MIN_WAVES) void abn_fit_refill_ke
         if (__ballot(parking) != 0ull) asm volatile("s_waitcnt vmcnt(0) ; abn: parked state written through" ::: "memory");
         if (parking && tail_park && gl == 0) {   // to the resume launch of abn_fit_spec_kernel (a kernel boundary away)
           a.susp_list[atomicAdd(a.susp_count, 1)] = (int)chain;
-          atomicAdd(a.slice_status + 2, 1u);
+          atomicAdd(a.slice_status + kSliceHanded, 1u);
         }
         if (parking && !tail_park && gl == 0) {
           const unsigned pos = atomicAdd(pht + kParkTail, 1u);
@@ -521,7 +521,7 @@ __global__ __launch_bounds__(kWave, ABN_REFILL_MIN_WAVES) void abn_fit_refill_ke
               nxt = (unsigned)cpk;
               take_parked = true;
             } else if (a.slice_status) {
-              atomicOr(a.slice_status, kSliceErrLostEntry);
+              atomicOr(a.slice_status + kSliceError, kSliceErrLostEntry);
             }
           }
         }

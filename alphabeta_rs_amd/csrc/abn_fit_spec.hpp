@@ -55,7 +55,7 @@ __global__ __launch_bounds__(4 * kWave, RMAX <= 2 ? 4 : 3) void abn_fit_spec_ker
     chain = __hip_atomic_load(a.susp_list + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   [[maybe_unused]] auto parked = [&](int i) __attribute__((always_inline)) {   // RESUME: word i of the chain's parked state
-    return __hip_atomic_load(a.state + (size_t)chain * 32 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return __hip_atomic_load(a.state + (size_t)chain * kStateDoubles + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
   const int w = (int)(chain / a.C);
   const int N = a.N, K = a.K, TP = a.TP;
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(4 * kWave, RMAX <= 2 ? 4 : 3) void abn_fit_spec_ker
     // evaluation wavefronts through the (still unused) candidate table
     if constexpr (RESUME) {   // the sorted simplex as abn_fit_refill_kernel parked it at an iteration boundary
 #pragma unroll
-      for (int k = 0; k < 5; ++k) vx[k] = parked(4 * k + dim);
+      for (int k = 0; k < 5; ++k) vx[k] = parked(kStateSimplex + 4 * k + dim);
     } else if (a.smode == 0) {
       const double* s0 = a.simplex0 + (size_t)chain * 20;
 #pragma unroll
@@ -432,13 +432,13 @@ __global__ __launch_bounds__(4 * kWave, RMAX <= 2 ? 4 : 3) void abn_fit_spec_ker
     // a chain parked by the persistent kernel at an iteration boundary (IterState::update and the termination test of that
     // iteration are behind it: status < 0): costs, best vertex and counters as stored, then straight to the candidates
 #pragma unroll
-    for (int k = 0; k < 5; ++k) c[k] = parked(20 + k);
-    bx = parked(25 + dim);
-    best_cost = parked(29);
-    const long long ie = __double_as_longlong(parked(30));
+    for (int k = 0; k < 5; ++k) c[k] = parked(kStateCosts + k);
+    bx = parked(kStateBest + dim);
+    best_cost = parked(kStateBestCost);
+    const long long ie = __double_as_longlong(parked(kStateIterEvals));
     iter = (int)(ie & 0xffffffffll);
     evals = (int)(ie >> 32);
-    have_best = __double_as_longlong(parked(31)) != 0;
+    have_best = __double_as_longlong(parked(kStateHaveBest)) != 0;
   } else {
     // Solver::init: the five start costs in input order (3 + 2), stable sort, first termination check
     take(c[0], c[1], c[2]);
@@ -563,9 +563,9 @@ __global__ __launch_bounds__(4 * kWave, RMAX <= 2 ? 4 : 3) void abn_fit_spec_ker
   if (gl < 4) a.best[(size_t)chain * 4 + gl] = bx;
   if (gl == 0) {
 #ifdef ABN_DIAG_RESUME_COUNT   // diagnosis only (scripts/repro_lost_chain.py): the resume launch counts in the upper half of the word
-    if constexpr (RESUME) atomicAdd(a.slice_status + 1, 0x10000u);
+    if constexpr (RESUME) atomicAdd(a.slice_status + kSliceFinished, 0x10000u);
 #else
-    if constexpr (RESUME) atomicAdd(a.slice_status + 1, 1u);  // the persistent launch's count of finished fits
+    if constexpr (RESUME) atomicAdd(a.slice_status + kSliceFinished, 1u);  // the persistent launch's count of finished fits
 #endif
     FitInfoDev fo;
     fo.best_cost = best_cost;

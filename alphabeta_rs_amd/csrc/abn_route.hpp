@@ -56,7 +56,7 @@ constexpr long long kPhaseAWidePerCu = 24;                      // ... and up to
 #define ABN_QUANTUM 256
 #endif
 constexpr int kQuantum = ABN_QUANTUM;
-constexpr size_t kSliceStateMax = (size_t)256 << 20;  // bytes of parked state (32 doubles per chain of the launch)
+constexpr size_t kSliceStateMax = (size_t)256 << 20;  // bytes of parked state (kStateDoubles per chain of the launch)
 constexpr int kPhaseACap = 1000;  // first-pass iteration cap of the two-pass phase A
 constexpr long long kTwoPassChains = 4096;  // ... which needs more start chains than this
 constexpr size_t kLdsTargetPerBlock = 20 * 1024;
@@ -287,7 +287,7 @@ constexpr bool persistent_by_size(int lanes, long long chains, int cus) {
 }
 // chains a whole plan's launches may park (0: no time slicing): those of its larger phase, within kSliceStateMax of state
 constexpr size_t plan_sliced_chains(const PedigreeRoute& p, size_t chains, int cus, int window_groups) {
-  return kQuantum > 0 && persistent_by_size(p.lanes, (long long)chains, cus) && chains * 32 * sizeof(double) <= kSliceStateMax &&
+  return kQuantum > 0 && persistent_by_size(p.lanes, (long long)chains, cus) && chains * kStateDoubles * sizeof(double) <= kSliceStateMax &&
                  chains < (1u << 27) && window_groups <= 1
              ? chains : 0;
 }
