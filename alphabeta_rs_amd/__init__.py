@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "abn_multi_create", "abn_multi_destroy", "abn_multi_last_error", "abn_multi_set_windows", "abn_multi_run",
     "abn_multi_sync", "abn_multi_shard", "abn_multi_raw_device_ptr", "abn_multi_download", "abn_multi_counters",
     "abn_multi_rccl_available", "abn_reduction_tree", "abn_pairwise_divergence_dev", "abn_multi_set_window_ids",
+    "abn_pairwise_divergence_windows", "abn_pairwise_divergence_windows_dev",
     "abn_multi_plan_shard", "abn_plan_last_kernels", "abn_multi_kernel_ms",
 ]
 
@@ -122,6 +123,10 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_pairwise_divergence.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int32, C.c_int64, C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_uint64), dp]
     L.abn_pairwise_divergence_dev.argtypes = [vp, vp, C.c_int32, C.c_int64, vp, vp, vp, dp]
+    i64p = C.POINTER(C.c_int64)
+    L.abn_pairwise_divergence_windows.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int32, C.c_int64, i64p, i64p, C.c_int32,
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
+    L.abn_pairwise_divergence_windows_dev.argtypes = [vp, vp, C.c_int32, C.c_int64, i64p, i64p, C.c_int32, vp, vp, vp, dp]
     L.abn_plan_create.argtypes = [vp, op, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                   C.POINTER(vp)]
     L.abn_plan_destroy.argtypes = [vp]
@@ -364,6 +369,40 @@ class Context:
         self._check(self._L.abn_pairwise_divergence_dev(self._h, C.c_void_p(codes_ptr), n_samples, n_sites,
                                                         C.c_void_p(diff_ptr or None), C.c_void_p(both_ptr or None),
                                                         C.c_void_p(dvalue_ptr or None), C.byref(ms)))
+        return ms.value
+
+    def pairwise_divergence_windows(self, codes, begin, end):
+        """pairwise_divergence of the column ranges [begin[w], end[w]) of one (n_samples, row_stride) code matrix in one
+        batched call (the window loop of src/cli/metaprofile.rs:50-72).  Returns (diff, both, dvalue), each of shape
+        (n_windows, pairs), bit-identical to pairwise_divergence(codes[:, b:e]) per window."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        n, stride = codes.shape
+        b, e = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+        if b.ndim != 1 or b.shape != e.shape:
+            raise ValueError("begin and end are 1-d arrays of one length")
+        W, npairs = b.shape[0], n * (n - 1) // 2
+        diff, both = np.zeros((W, npairs), dtype=np.uint64), np.zeros((W, npairs), dtype=np.uint64)
+        dval = np.zeros((W, npairs))
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.abn_pairwise_divergence_windows(
+            self._h, codes.ctypes.data_as(C.POINTER(C.c_uint8)), n, stride, b.ctypes.data_as(i64p),
+            e.ctypes.data_as(i64p), W, diff.ctypes.data_as(C.POINTER(C.c_uint64)),
+            both.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(dval)))
+        return diff, both, dval
+
+    def pairwise_divergence_windows_dev(self, codes_ptr: int, n_samples: int, row_stride: int, begin, end,
+                                        diff_ptr: int = 0, both_ptr: int = 0, dvalue_ptr: int = 0) -> float:
+        """The same on device-resident buffers: u8 codes [n x row_stride] in, u64 diff / both and f64 dvalue
+        [n_windows x pairs] out (0 = not wanted); begin / end are host arrays.  Returns the kernels' HIP-event ms."""
+        b, e = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+        if b.ndim != 1 or b.shape != e.shape:
+            raise ValueError("begin and end are 1-d arrays of one length")
+        ms = C.c_double(0.0)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.abn_pairwise_divergence_windows_dev(
+            self._h, C.c_void_p(codes_ptr), n_samples, row_stride, b.ctypes.data_as(i64p), e.ctypes.data_as(i64p),
+            b.shape[0], C.c_void_p(diff_ptr or None), C.c_void_p(both_ptr or None), C.c_void_p(dvalue_ptr or None),
+            C.byref(ms)))
         return ms.value
 
     # ---- (3) boot_model::run

@@ -1,7 +1,8 @@
 // Pedigree construction and the host-side analysis: abn_pairwise_divergence*, abn_analyze.
-// The scan kernels are in abn_pairwise_mx.hpp; the fit path (abn_api.hip) does not include them.
+// The scan kernels are in abn_pairwise_mx.hpp and abn_pairwise_windows.hpp; the fit path (abn_api.hip) does not include them.
 #include "abn_host.hpp"
 #include "abn_pairwise_mx.hpp"
+#include "abn_pairwise_windows.hpp"
 
 using namespace abn;
 
@@ -10,6 +11,18 @@ using namespace abn;
 // ------------------------------------------------------------------------------------------------
 // Exact integer Gram products on the matrix pipe (abn_pairwise_mx.hpp): any number of samples, the sample axis tiled in
 // groups of 64; codes already on the device, outputs on the device (any may be null).
+// the two HIP events around a call's kernels (kernel_ms), destroyed on every way out
+struct EventPair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+  ~EventPair() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
 constexpr long long kPmxMaxJobs = 8192;  // jobs per launch: 32 KiB of packed sums each (256 MiB of `partial`)
 
 template <bool AL4>
@@ -71,11 +84,11 @@ static int pairwise_mx_on_device(abn_ctx* c, const uint8_t* dcodes, int n, long 
   const bool al4 = (L % 4 == 0) && ((uintptr_t)dcodes % 4 == 0);
   const int nb = a.ngroups == 1 ? (n + 15) / 16 : 4;
   DevBuf<unsigned long long> pdiag, poff;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  EventPair ev;
   if (kernel_ms) {
-    HIPCHK(c, hipEventCreate(&e0));
-    HIPCHK(c, hipEventCreate(&e1));
-    HIPCHK(c, hipEventRecord(e0, c->stream));
+    HIPCHK(c, hipEventCreate(&ev.e0));
+    HIPCHK(c, hipEventCreate(&ev.e1));
+    HIPCHK(c, hipEventRecord(ev.e0, c->stream));
   }
   // workgroups per CU: two (eight wavefronts streaming per CU) once the scan is long enough to pay for twice the partial
   // rows; one below (50 x 2 M sites: 28.6 against 30.5 us; 50 x 32 M: 304 against 282 us)
@@ -88,13 +101,11 @@ static int pairwise_mx_on_device(abn_ctx* c, const uint8_t* dcodes, int n, long 
   if (!rc) rc = pairwise_mx_family(c, a, false, g * (g - 1) / 2, 4, al4, cu_off, poff, ddiff, dboth, ddval);
   if (rc) return rc;
   if (kernel_ms) {
-    HIPCHK(c, hipEventRecord(e1, c->stream));
-    HIPCHK(c, hipEventSynchronize(e1));
+    HIPCHK(c, hipEventRecord(ev.e1, c->stream));
+    HIPCHK(c, hipEventSynchronize(ev.e1));
     float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
     *kernel_ms = ms;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the partial rows are freed on return
   return ABN_OK;
@@ -129,6 +140,193 @@ extern "C" int abn_pairwise_divergence(abn_ctx* c, const uint8_t* codes, int32_t
   if (n_sites > 0)
     HIPCHK(c, hipMemcpyAsync(dcodes.p, codes, n * (size_t)n_sites, hipMemcpyHostToDevice, c->stream));
   int rc = pairwise_mx_on_device(c, dcodes.p, n_samples, n_sites, ddiff.p, dboth.p, ddv.p, nullptr);
+  if (rc) return rc;
+  if (diff) HIPCHK(c, hipMemcpyAsync(diff, ddiff.p, ddiff.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (both) HIPCHK(c, hipMemcpyAsync(both, dboth.p, dboth.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (dvalue) HIPCHK(c, hipMemcpyAsync(dvalue, ddv.p, ddv.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ABN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the same for many windows of one code matrix (src/cli/metaprofile.rs:50-72 around src/pedigree.rs:210-261)
+// ------------------------------------------------------------------------------------------------
+template <bool AL4>
+static hipError_t launch_pairwise_win(int nb, bool diag, unsigned grid, hipStream_t s, const PairWinArgs& a) {
+  if (!diag) {
+    hipLaunchKernelGGL((abn_pairwise_win_kernel<4, false, AL4>), dim3(grid), dim3(kPmxThreads), 0, s, a);
+  } else {
+    switch (nb) {
+      case 1: hipLaunchKernelGGL((abn_pairwise_win_kernel<1, true, AL4>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+      case 2: hipLaunchKernelGGL((abn_pairwise_win_kernel<2, true, AL4>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+      case 3: hipLaunchKernelGGL((abn_pairwise_win_kernel<3, true, AL4>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+      default: hipLaunchKernelGGL((abn_pairwise_win_kernel<4, true, AL4>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+    }
+  }
+  return hipGetLastError();
+}
+
+// The jobs of one family of super-pairs over all windows, in launches ("slabs") of at most kPmxMaxJobs jobs; the chunks
+// of one (window, super-pair) never straddle two slabs, so a slab's reduce launch finds all rows of its tasks.
+struct PairWinFamily {
+  struct Slab { size_t job0, njobs, task0, ntasks, nrows; };
+  std::vector<PairWinJob> jobs;
+  std::vector<PairWinTask> tasks;
+  std::vector<Slab> slabs;
+  size_t max_rows = 0;
+  DevBuf<PairWinJob> djobs;
+  DevBuf<PairWinTask> dtasks;
+  DevBuf<unsigned long long> partial;
+
+  void plan(long long nsp, const int64_t* begin, const int64_t* end, int W, const std::vector<long long>& chunk) {
+    if (nsp <= 0) return;
+    Slab cur{0, 0, 0, 0, 0};
+    for (int w = 0; w < W; ++w) {
+      const long long L = end[w] - begin[w];
+      const long long nch = std::max<long long>(1, (L + chunk[w] - 1) / chunk[w]);
+      for (long long sp = 0; sp < nsp; ++sp) {
+        if (cur.njobs + (size_t)nch > (size_t)kPmxMaxJobs) {
+          slabs.push_back(cur);
+          cur = Slab{jobs.size(), 0, tasks.size(), 0, 0};
+        }
+        if (nch > 1) {
+          tasks.push_back(PairWinTask{w, (int)sp, (int)cur.nrows, (int)nch, 0});
+          ++cur.ntasks;
+        }
+        for (long long k = 0; k < nch; ++k) {
+          const long long b = begin[w] + k * chunk[w];
+          jobs.push_back(PairWinJob{b, std::min<long long>(b + chunk[w], end[w]), w, (int)sp,
+                                    nch > 1 ? (int)cur.nrows++ : -1});
+        }
+        cur.njobs += (size_t)nch;
+      }
+    }
+    slabs.push_back(cur);
+    for (const Slab& s : slabs) max_rows = std::max(max_rows, s.nrows);
+  }
+  int upload(abn_ctx* c) {
+    HIPCHK(c, djobs.alloc(jobs.size()));
+    HIPCHK(c, dtasks.alloc(tasks.size()));
+    HIPCHK(c, partial.alloc(max_rows * kPmxJobElems));
+    if (!jobs.empty())
+      HIPCHK(c, hipMemcpyAsync(djobs.p, jobs.data(), djobs.bytes(), hipMemcpyHostToDevice, c->stream));
+    if (!tasks.empty())
+      HIPCHK(c, hipMemcpyAsync(dtasks.p, tasks.data(), dtasks.bytes(), hipMemcpyHostToDevice, c->stream));
+    return ABN_OK;
+  }
+  int run(abn_ctx* c, PairWinArgs a, bool diag, int nb, bool al4) {
+    a.partial = partial.p;
+    for (const Slab& s : slabs) {
+      if (s.njobs == 0) continue;
+      a.jobs = djobs.p + s.job0;
+      HIPCHK(c, al4 ? launch_pairwise_win<true>(nb, diag, (unsigned)s.njobs, c->stream, a)
+                    : launch_pairwise_win<false>(nb, diag, (unsigned)s.njobs, c->stream, a));
+      if (s.ntasks == 0) continue;
+      hipLaunchKernelGGL(abn_pairwise_win_reduce_kernel, dim3((unsigned)(s.ntasks * 256)), dim3(16 * kPmxReduceGroups), 0,
+                         c->stream, partial.p, dtasks.p + s.task0, a.n, a.ngroups, diag ? 1 : 0, a.diff, a.both,
+                         a.dvalue);
+      HIPCHK(c, hipGetLastError());
+    }
+    return ABN_OK;
+  }
+};
+
+static int pairwise_windows_check(abn_ctx* c, const void* codes, int32_t n, int64_t row_stride, const int64_t* begin,
+                                  const int64_t* end, int32_t W) {
+  if (!codes || n <= 0 || row_stride < 0 || W < 0 || (W > 0 && (!begin || !end)))
+    return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (n > 65535) return set_err(c, ABN_ERR_INVALID_ARG, "too many samples");
+  for (int w = 0; w < W; ++w)
+    if (begin[w] < 0 || begin[w] > end[w] || end[w] > row_stride)
+      return set_err(c, ABN_ERR_INVALID_ARG, "window " + std::to_string(w) + " is not a column range of the rows");
+  return ABN_OK;
+}
+
+static int pairwise_windows_on_device(abn_ctx* c, const uint8_t* dcodes, int n, long long row_stride,
+                                      const int64_t* begin, const int64_t* end, int W, unsigned long long* ddiff,
+                                      unsigned long long* dboth, double* ddval, double* kernel_ms) {
+  PairWinArgs a{};
+  a.codes = dcodes;
+  a.row_stride = row_stride;
+  a.n = n;
+  a.ngroups = (n + 63) / 64;
+  a.diff = ddiff;
+  a.both = dboth;
+  a.dvalue = ddval;
+  bool al4 = (row_stride % 4 == 0) && ((uintptr_t)dcodes % 4 == 0);
+  // sites per job of each window: kPmxWinChunkSites, more only where a window would otherwise need more rows of
+  // `partial` than one launch keeps
+  std::vector<long long> chunk((size_t)W);
+  for (int w = 0; w < W; ++w) {
+    al4 = al4 && begin[w] % 4 == 0;
+    const long long L = end[w] - begin[w];
+    long long ch = kPmxWinChunkSites;
+    if ((L + ch - 1) / ch > kPmxMaxJobs) ch = ((L + kPmxMaxJobs - 1) / kPmxMaxJobs + 127) / 128 * 128;
+    if (ch >= (1ll << 30)) return set_err(c, ABN_ERR_INVALID_ARG, "window too long");
+    chunk[(size_t)w] = ch;
+  }
+  const int nb = a.ngroups == 1 ? (n + 15) / 16 : 4;
+  const long long g = a.ngroups;
+  PairWinFamily fdiag, foff;  // (their host tables outlive the copies: the stream is synchronised below)
+  fdiag.plan(g, begin, end, W, chunk);
+  foff.plan(g * (g - 1) / 2, begin, end, W, chunk);
+  int rc = fdiag.upload(c);
+  if (!rc) rc = foff.upload(c);
+  if (rc) return rc;
+  EventPair ev;
+  if (kernel_ms) {
+    HIPCHK(c, hipEventCreate(&ev.e0));
+    HIPCHK(c, hipEventCreate(&ev.e1));
+    HIPCHK(c, hipEventRecord(ev.e0, c->stream));
+  }
+  rc = fdiag.run(c, a, true, nb, al4);
+  if (!rc) rc = foff.run(c, a, false, 4, al4);
+  if (rc) return rc;
+  if (kernel_ms) {
+    HIPCHK(c, hipEventRecord(ev.e1, c->stream));
+    HIPCHK(c, hipEventSynchronize(ev.e1));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *kernel_ms = ms;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the job tables and the partial rows are freed on return
+  return ABN_OK;
+}
+
+extern "C" int abn_pairwise_divergence_windows_dev(abn_ctx* c, const void* dev_codes, int32_t n_samples,
+                                                   int64_t row_stride, const int64_t* site_begin,
+                                                   const int64_t* site_end, int32_t n_windows, void* dev_diff,
+                                                   void* dev_both, void* dev_dvalue, double* kernel_ms) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  if (int rc = pairwise_windows_check(c, dev_codes, n_samples, row_stride, site_begin, site_end, n_windows)) return rc;
+  if (n_samples < 2 || n_windows == 0) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  return pairwise_windows_on_device(c, (const uint8_t*)dev_codes, n_samples, row_stride, site_begin, site_end, n_windows,
+                                    (unsigned long long*)dev_diff, (unsigned long long*)dev_both, (double*)dev_dvalue,
+                                    kernel_ms);
+}
+
+extern "C" int abn_pairwise_divergence_windows(abn_ctx* c, const uint8_t* codes, int32_t n_samples, int64_t row_stride,
+                                               const int64_t* site_begin, const int64_t* site_end, int32_t n_windows,
+                                               uint64_t* diff, uint64_t* both, double* dvalue) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  if (int rc = pairwise_windows_check(c, codes, n_samples, row_stride, site_begin, site_end, n_windows)) return rc;
+  if (n_samples < 2 || n_windows == 0) return ABN_OK;
+  const size_t n = (size_t)n_samples, nout = n * (n - 1) / 2 * (size_t)n_windows;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  DevBuf<uint8_t> dcodes;
+  DevBuf<unsigned long long> ddiff, dboth;
+  DevBuf<double> ddv;
+  HIPCHK(c, dcodes.alloc(std::max<size_t>(n * (size_t)row_stride, 4)));
+  if (diff) HIPCHK(c, ddiff.alloc(nout));
+  if (both) HIPCHK(c, dboth.alloc(nout));
+  if (dvalue) HIPCHK(c, ddv.alloc(nout));
+  if (row_stride > 0)
+    HIPCHK(c, hipMemcpyAsync(dcodes.p, codes, n * (size_t)row_stride, hipMemcpyHostToDevice, c->stream));
+  int rc = pairwise_windows_on_device(c, dcodes.p, n_samples, row_stride, site_begin, site_end, n_windows, ddiff.p,
+                                      dboth.p, ddv.p, nullptr);
   if (rc) return rc;
   if (diff) HIPCHK(c, hipMemcpyAsync(diff, ddiff.p, ddiff.bytes(), hipMemcpyDeviceToHost, c->stream));
   if (both) HIPCHK(c, hipMemcpyAsync(both, dboth.p, dboth.bytes(), hipMemcpyDeviceToHost, c->stream));

@@ -113,73 +113,45 @@ __device__ __forceinline__ pmx_u32x4 pmx_load_edge(const uint8_t* codes, size_t 
   return r;
 }
 
+// The scan of one job, shared by the kernels below and in abn_pairwise_windows.hpp.
 // NB: 16-sample blocks of the row group that exist (DIAG: 1..4, the tiles bi <= bj < NB; else 4 x 4 tiles of groups R < C)
 template <int NB, bool DIAG, bool AL4>
-__global__ __launch_bounds__(kPmxThreads, DIAG ? 2 : 1) void abn_pairwise_mx_kernel(const PairMxArgs a) {
+struct PmxScan {
   static_assert(DIAG || NB == 4, "off-diagonal super-pairs are 4 x 4 blocks");
-  constexpr int NF = DIAG ? NB : 8;            // fragments per K step: the blocks of the row group (+ of the column group)
-  constexpr int DSTEPS = pmx_steps(NF);        // K steps per batch
-  constexpr int NT = DIAG ? NB * (NB + 1) / 2 : 16;
-  __shared__ unsigned long long red[kPmxJobElems];
+  static constexpr int NF = DIAG ? NB : 8;            // fragments per K step: the blocks of the row group (+ of the column group)
+  static constexpr int DSTEPS = pmx_steps(NF);        // K steps per batch
+  static constexpr int NT = DIAG ? NB * (NB + 1) / 2 : 16;
+  static constexpr std::false_type kFull{};
+  static constexpr std::true_type kPart{};
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 15, q = lane >> 4;
-  const int g = a.ngroups;
-  // job -> (super-pair, chunk)
-  const long long job = blockIdx.x;
-  const int chunk = (int)(job % a.nchunks);
-  const long long spl = job / a.nchunks;       // super-pair of the launch
-  int R, C;
-  if constexpr (DIAG) R = C = (int)(a.first + spl);
-  else pmx_offdiag(a.first + spl, g, R, C);
+  const uint8_t* codes;
+  size_t roff[NF];           // this lane's byte offset of site 0 in each block's row (the caller's; 16 q is added here)
+  pmx_i32x4 S1[NT], S2[NT];  // V V^T and I I^T + Z Z^T of the wavefront's share
+  int tid, lane, wave, r, q;
 
-  // this lane's byte offset in each block's row: sample (clamped: rows past n give sums nobody reads) x L + 16 q
-  size_t roff[NF];
+  __device__ __forceinline__ PmxScan(const uint8_t* c) : codes(c) {
+    tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    r = lane & 15, q = lane >> 4;
 #pragma unroll
-  for (int b = 0; b < NF; ++b) {
-    const int blk = b < 4 ? 4 * R + b : 4 * C + (b - 4);
-    int s = 16 * blk + r;
-    s = s < a.n ? s : a.n - 1;
-    roff[b] = (size_t)s * (size_t)a.L;
+    for (int t = 0; t < NT; ++t) S1[t] = S2[t] = pmx_i32x4{0, 0, 0, 0};
   }
 
-  pmx_i32x4 S1[NT], S2[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) S1[t] = S2[t] = pmx_i32x4{0, 0, 0, 0};
-
-  // K steps (64 sites each).  "Inner" steps lie inside every row with four bytes to spare (the unaligned loader reads one
-  // dword past the fragment and the last row ends the buffer); the ragged end of the rows — at most two steps of the
-  // whole launch — is staged through LDS after the loop.  The inner steps of the super-pair are split evenly over its
-  // nchunks x 4 wavefronts (shares differ by at most one step), each wavefront a contiguous range.
-  const long long nk_all = (a.L + 63) / 64;
-  const long long nk_inner = AL4 ? a.L / 64 : (a.L >= 4 ? (a.L - 4) / 64 : 0);
-  // The inner steps are split evenly over the super-pair's chunks (jobs); inside a job the four wavefronts take batches of
-  // DSTEPS steps round-robin (together they read 256 DSTEPS contiguous bytes of every row: interleaved batches measured 8 %
-  // faster at 32 M sites than a contiguous range per wavefront) and share what is left of the last round evenly, so that no
-  // wavefront does more than one step more than another.
-  // Chunk boundaries are multiples of two steps: a batch then reads whole 128-byte lines of a row whose start is aligned
-  // (boundaries at odd steps split every line between two wavefronts: measured +10 % time at 32 M sites).
-  const long long nk2 = nk_inner / 2;
-  const long long Ks = 2 * ((long long)chunk * nk2 / a.nchunks);
-  const long long Ke = chunk == a.nchunks - 1 ? nk_inner : 2 * ((long long)(chunk + 1) * nk2 / a.nchunks);
-  const long long nfull = (Ke - Ks) / (kPmxWaves * DSTEPS);
-  const long long R0 = Ks + nfull * (kPmxWaves * DSTEPS);
-  const int rem = (int)(Ke - R0);
-  const int rem_lo = wave * rem / kPmxWaves, rem_hi = (wave + 1) * rem / kPmxWaves;
   // DSTEPS steps from step k (PART: only the first cnt of them; cnt is uniform in the wavefront: scalar branches)
-  auto load_steps = [&](long long k, pmx_u32x4 (&x)[DSTEPS][NF], auto part, int cnt) {
+  template <class Part>
+  __device__ __forceinline__ void load_steps(long long k, pmx_u32x4 (&x)[DSTEPS][NF], Part, int cnt) const {
     const size_t k0 = (size_t)(k * 64 + 16 * q);
 #pragma unroll
     for (int d = 0; d < DSTEPS; ++d)
-      if (!decltype(part)::value || d < cnt) {
+      if (!Part::value || d < cnt) {
 #pragma unroll
-        for (int f = 0; f < NF; ++f) x[d][f] = pmx_load<AL4>(a.codes, roff[f] + k0 + (size_t)(64 * d));
+        for (int f = 0; f < NF; ++f) x[d][f] = pmx_load<AL4>(codes, roff[f] + k0 + (size_t)(64 * d));
       }
-  };
-  auto compute = [&](const pmx_u32x4 (&x)[DSTEPS][NF], auto part, int cnt) {
+  }
+  template <class Part>
+  __device__ __forceinline__ void compute(const pmx_u32x4 (&x)[DSTEPS][NF], Part, int cnt) {
 #pragma unroll
     for (int d = 0; d < DSTEPS; ++d) {
-      if (decltype(part)::value && d >= cnt) break;
+      if (Part::value && d >= cnt) break;
       pmx_i32x4 V[NF], I[NF], Z[NF];
 #pragma unroll
       for (int f = 0; f < NF; ++f)
@@ -219,53 +191,64 @@ __global__ __launch_bounds__(kPmxThreads, DIAG ? 2 : 1) void abn_pairwise_mx_ker
           S2[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Z[fa], Z[fb], S2[t], 0, 0, 0);
         }
     }
-  };
-  constexpr std::false_type kFull{};
-  constexpr std::true_type kPart{};
+  }
 
-  // The wavefront's share of the last round is loaded FIRST and computed LAST (a third register set): the full rounds in
-  // between run without a branch inside a batch — one batch in flight while the previous one is computed, two register
-  // sets, the loop unrolled by two (no copies) — and the partial batch exposes no load latency at the end.
-  {
+  // The K steps [Ks, Ke) of the job — every one of them inside every row with four bytes to spare (the unaligned loader
+  // reads one dword past the fragment and the last row ends the buffer).  The four wavefronts take batches of DSTEPS steps
+  // round-robin (together they read 256 DSTEPS contiguous bytes of every row: interleaved batches measured 8 % faster at
+  // 32 M sites than a contiguous range per wavefront) and share what is left of the last round evenly, so that no
+  // wavefront does more than one step more than another.  Clears `red`, the workgroup's sums, on the way.
+  __device__ __forceinline__ void inner_steps(long long Ks, long long Ke, unsigned long long* red) {
+    const long long nfull = (Ke - Ks) / (kPmxWaves * DSTEPS);
+    const long long R0 = Ks + nfull * (kPmxWaves * DSTEPS);
+    const int rem = (int)(Ke - R0);
+    const int rem_lo = wave * rem / kPmxWaves, rem_hi = (wave + 1) * rem / kPmxWaves;
+    // The wavefront's share of the last round is loaded FIRST and computed LAST (a third register set): the full rounds in
+    // between run without a branch inside a batch — one batch in flight while the previous one is computed, two register
+    // sets, the loop unrolled by two (no copies) — and the partial batch exposes no load latency at the end.
     pmx_u32x4 xt[DSTEPS][NF], xa[DSTEPS][NF], xb[DSTEPS][NF];
     const int ct = rem_hi - rem_lo;
     load_steps(R0 + rem_lo, xt, kPart, ct);
-    auto kfull = [&](long long r) { return Ks + (r * kPmxWaves + wave) * DSTEPS; };
-    long long r = 0;
+    auto kfull = [&](long long rr) { return Ks + (rr * kPmxWaves + wave) * DSTEPS; };
+    long long rr = 0;
     if (nfull > 0) load_steps(kfull(0), xa, kFull, DSTEPS);
     // the workgroup's sums start at zero — cleared behind the first loads (they are in flight meanwhile); the barrier keeps
     // a wavefront that is already at the ragged end (it stages through `red`) from meeting another one's clearing stores
     for (int k = tid; k < kPmxJobElems; k += kPmxThreads) red[k] = 0ull;
     __syncthreads();
-    while (r < nfull) {
-      if (r + 1 < nfull) load_steps(kfull(r + 1), xb, kFull, DSTEPS);
+    while (rr < nfull) {
+      if (rr + 1 < nfull) load_steps(kfull(rr + 1), xb, kFull, DSTEPS);
       compute(xa, kFull, DSTEPS);
-      if (++r >= nfull) break;
-      if (r + 1 < nfull) load_steps(kfull(r + 1), xa, kFull, DSTEPS);
+      if (++rr >= nfull) break;
+      if (rr + 1 < nfull) load_steps(kfull(rr + 1), xa, kFull, DSTEPS);
       compute(xb, kFull, DSTEPS);
-      ++r;
+      ++rr;
     }
     compute(xt, kPart, ct);
   }
-  // the ragged end: byte loads with the sites past L read as filtered, staged through this wavefront's share of `red`
-  // (run-time indices are fine in LDS; in registers they would move the fragment arrays to scratch memory) and cleared
-  // again before the sums go there.  The last wavefront of the super-pair's last chunk takes it.
-  if (chunk == a.nchunks - 1 && wave == kPmxWaves - 1) {
-    pmx_u32x4* stage = reinterpret_cast<pmx_u32x4*>(red) + wave * (NF * 64);
-    for (long long k = nk_inner; k < nk_all; ++k) {
-      const long long k0 = k * 64 + 16 * q;
-      for (int f = 0; f < NF; ++f) stage[f * 64 + lane] = pmx_load_edge(a.codes, roff[f], k0, a.L);
-      pmx_u32x4 xe[DSTEPS][NF];
+
+  // One wavefront's share of `red` as the staging area of the ragged steps (run-time indices are fine in LDS; in
+  // registers they would move the fragment arrays to scratch memory); cleared again before the sums go there.
+  __device__ __forceinline__ pmx_u32x4* stage_of(unsigned long long* red) const {
+    return reinterpret_cast<pmx_u32x4*>(red) + wave * (NF * 64);
+  }
+  // a ragged step k: load(row offset, this lane's first site) gives the fragment with the sites past the end as filtered
+  template <class Load>
+  __device__ __forceinline__ void edge_step(long long k, pmx_u32x4* stage, Load load) {
+    const long long k0 = k * 64 + 16 * q;
+    for (int f = 0; f < NF; ++f) stage[f * 64 + lane] = load(roff[f], k0);
+    pmx_u32x4 xe[DSTEPS][NF];
 #pragma unroll
-      for (int f = 0; f < NF; ++f) xe[0][f] = stage[f * 64 + lane];
-      compute(xe, kPart, 1);
-    }
+    for (int f = 0; f < NF; ++f) xe[0][f] = stage[f * 64 + lane];
+    compute(xe, kPart, 1);
+  }
+  __device__ __forceinline__ void clear_stage(pmx_u32x4* stage) const {
     for (int f = 0; f < NF; ++f) stage[f * 64 + lane] = pmx_u32x4{0u, 0u, 0u, 0u};
   }
 
-  // ---- the workgroup's sums: C/D layout of the 16 x 16 tile: column = lane & 15, row = 4 (lane >> 4) + register
-  __syncthreads();
-  {
+  // the four wavefronts' tiles -> red[tile 4 bi + bj][row][column], both << 32 | diff per element (between two barriers
+  // of the caller).  C/D layout of the 16 x 16 tile: column = lane & 15, row = 4 (lane >> 4) + register
+  __device__ __forceinline__ void fold(unsigned long long* red) const {
     int t = 0;
 #pragma unroll
     for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
@@ -280,62 +263,114 @@ __global__ __launch_bounds__(kPmxThreads, DIAG ? 2 : 1) void abn_pairwise_mx_ker
         }
       }
   }
+  static __device__ __forceinline__ bool tile_used(int k) {  // element k of a job's packed sums belongs to a computed tile
+    const int bi = k >> 10, bj = (k >> 8) & 3;
+    return DIAG ? (bi <= bj && bj < NB) : true;
+  }
+};
+
+template <int NB, bool DIAG, bool AL4>
+__global__ __launch_bounds__(kPmxThreads, DIAG ? 2 : 1) void abn_pairwise_mx_kernel(const PairMxArgs a) {
+  using Scan = PmxScan<NB, DIAG, AL4>;
+  __shared__ unsigned long long red[kPmxJobElems];
+  Scan sc(a.codes);
+  const int g = a.ngroups;
+  // job -> (super-pair, chunk)
+  const long long job = blockIdx.x;
+  const int chunk = (int)(job % a.nchunks);
+  const long long spl = job / a.nchunks;       // super-pair of the launch
+  int R, C;
+  if constexpr (DIAG) R = C = (int)(a.first + spl);
+  else pmx_offdiag(a.first + spl, g, R, C);
+
+  // this lane's byte offset in each block's row: sample (clamped: rows past n give sums nobody reads) x L
+#pragma unroll
+  for (int b = 0; b < Scan::NF; ++b) {
+    const int blk = b < 4 ? 4 * R + b : 4 * C + (b - 4);
+    int s = 16 * blk + sc.r;
+    s = s < a.n ? s : a.n - 1;
+    sc.roff[b] = (size_t)s * (size_t)a.L;
+  }
+
+  // K steps (64 sites each).  "Inner" steps lie inside every row with four bytes to spare; the ragged end of the rows — at
+  // most two steps of the whole launch — is staged through LDS after the loop.
+  const long long nk_all = (a.L + 63) / 64;
+  const long long nk_inner = AL4 ? a.L / 64 : (a.L >= 4 ? (a.L - 4) / 64 : 0);
+  // The inner steps are split evenly over the super-pair's chunks (jobs).
+  // Chunk boundaries are multiples of two steps: a batch then reads whole 128-byte lines of a row whose start is aligned
+  // (boundaries at odd steps split every line between two wavefronts: measured +10 % time at 32 M sites).
+  const long long nk2 = nk_inner / 2;
+  const long long Ks = 2 * ((long long)chunk * nk2 / a.nchunks);
+  const long long Ke = chunk == a.nchunks - 1 ? nk_inner : 2 * ((long long)(chunk + 1) * nk2 / a.nchunks);
+  sc.inner_steps(Ks, Ke, red);
+  // the ragged end: the last wavefront of the super-pair's last chunk takes it
+  if (chunk == a.nchunks - 1 && sc.wave == kPmxWaves - 1) {
+    pmx_u32x4* stage = sc.stage_of(red);
+    for (long long k = nk_inner; k < nk_all; ++k)  // byte loads
+      sc.edge_step(k, stage, [&](size_t row_off, long long k0) { return pmx_load_edge(a.codes, row_off, k0, a.L); });
+    sc.clear_stage(stage);
+  }
+
+  // ---- the workgroup's sums
+  __syncthreads();
+  sc.fold(red);
   __syncthreads();
   unsigned long long* row = a.partial + (spl * a.nchunks + chunk) * kPmxJobElems;
-  for (int k = tid; k < kPmxJobElems; k += kPmxThreads) {
-    const int bi = k >> 10, bj = (k >> 8) & 3;
-    const bool used = DIAG ? (bi <= bj && bj < NB) : true;
-    if (used) row[k] = red[k];
-  }
+  for (int k = sc.tid; k < kPmxJobElems; k += kPmxThreads)
+    if (Scan::tile_used(k)) row[k] = red[k];
 }
 
 // Rows of `partial` -> diff[p], both[p], dvalue[p] = diff / (2 both) (:257; 0 / 0 = NaN like the reference) in the pair
 // order of the reference's nested loops (:214-215).  A workgroup owns one row of one tile (16 elements = 128 contiguous
 // bytes per partial row): 64 thread groups sum the chunks of the super-pair (a strided share each), LDS combines them.
 constexpr int kPmxReduceGroups = 64;
+// row `trow` of tile t of super-pair sp, whose nchunks rows start at `rows`
+__device__ __forceinline__ void pmx_reduce_row(const unsigned long long* rows, int nchunks, int n, int ngroups, int diag,
+                                               long long sp, int t, int trow, unsigned long long* diff,
+                                               unsigned long long* both, double* dvalue) {
+  __shared__ unsigned long long lo[kPmxReduceGroups][16], hi[kPmxReduceGroups][16];
+  const int col = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  int R, C;
+  if (diag) R = C = (int)sp;
+  else pmx_offdiag(sp, ngroups, R, C);
+  const int bi = t >> 2, bj = t & 3;
+  const long long i = 64ll * R + 16 * bi + trow, j0 = 64ll * C + 16 * bj;
+  // the whole workgroup leaves together when its row holds no pair (uniform: nothing below synchronises half a group)
+  if (i >= n || j0 >= n || j0 + 15 <= i) return;
+  const long long j = j0 + col;
+  unsigned long long alo = 0, ahi = 0;
+  const unsigned long long* src = rows + t * 256 + trow * 16 + col;
+#pragma unroll 4
+  for (int c = grp; c < nchunks; c += kPmxReduceGroups) {
+    const unsigned long long v = src[(size_t)c * kPmxJobElems];
+    alo += v & 0xffffffffull;
+    ahi += v >> 32;
+  }
+  lo[grp][col] = alo;
+  hi[grp][col] = ahi;
+  __syncthreads();
+  for (int half = kPmxReduceGroups / 2; half >= 1; half >>= 1) {
+    if (grp < half) {
+      lo[grp][col] += lo[grp + half][col];
+      hi[grp][col] += hi[grp + half][col];
+    }
+    __syncthreads();
+  }
+  if (grp == 0 && i < j && j < n) {
+    const long long p = i * n - i * (i + 1) / 2 + (j - i - 1);
+    const unsigned long long d = lo[0][col], cc = hi[0][col];
+    if (diff) diff[p] = d;
+    if (both) both[p] = cc;
+    if (dvalue) dvalue[p] = (double)d / (2.0 * (double)cc);
+  }
+}
 __global__ __launch_bounds__(16 * kPmxReduceGroups) void abn_pairwise_reduce_tiles_kernel(
     const unsigned long long* partial, int nchunks, int n, int ngroups, int diag, long long first,
     unsigned long long* diff, unsigned long long* both, double* dvalue) {
-  __shared__ unsigned long long lo[kPmxReduceGroups][16], hi[kPmxReduceGroups][16];
-  const int col = threadIdx.x & 15, grp = threadIdx.x >> 4;
   const long long wg = blockIdx.x;
-  const int trow = (int)(wg & 15), t = (int)((wg >> 4) & 15);
   const long long sp = wg >> 8;  // super-pair of the launch (as in the kernel that wrote `partial`)
-  {
-    int R, C;
-    if (diag) R = C = (int)(first + sp);
-    else pmx_offdiag(first + sp, ngroups, R, C);
-    const int bi = t >> 2, bj = t & 3;
-    const long long i = 64ll * R + 16 * bi + trow, j0 = 64ll * C + 16 * bj;
-    // the whole workgroup leaves together when its row holds no pair (uniform: nothing below synchronises half a group)
-    if (i >= n || j0 >= n || j0 + 15 <= i) return;
-    const long long j = j0 + col;
-    unsigned long long alo = 0, ahi = 0;
-    const unsigned long long* src = partial + (sp * nchunks) * kPmxJobElems + t * 256 + trow * 16 + col;
-#pragma unroll 4
-    for (int c = grp; c < nchunks; c += kPmxReduceGroups) {
-      const unsigned long long v = src[(size_t)c * kPmxJobElems];
-      alo += v & 0xffffffffull;
-      ahi += v >> 32;
-    }
-    lo[grp][col] = alo;
-    hi[grp][col] = ahi;
-    __syncthreads();
-    for (int half = kPmxReduceGroups / 2; half >= 1; half >>= 1) {
-      if (grp < half) {
-        lo[grp][col] += lo[grp + half][col];
-        hi[grp][col] += hi[grp + half][col];
-      }
-      __syncthreads();
-    }
-    if (grp == 0 && i < j && j < n) {
-      const long long p = i * n - i * (i + 1) / 2 + (j - i - 1);
-      const unsigned long long d = lo[0][col], cc = hi[0][col];
-      if (diff) diff[p] = d;
-      if (both) both[p] = cc;
-      if (dvalue) dvalue[p] = (double)d / (2.0 * (double)cc);
-    }
-  }
+  pmx_reduce_row(partial + (sp * nchunks) * kPmxJobElems, nchunks, n, ngroups, diag, first + sp, (int)((wg >> 4) & 15),
+                 (int)(wg & 15), diff, both, dvalue);
 }
 
 }  // namespace abn

@@ -24,6 +24,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <functional>
 #include <limits>
@@ -300,6 +301,20 @@ class Pedigree {  // src/pedigree.rs:44-45
   // comparison (DMatrix::from, :210-261) runs on the MI355X (abn_pairwise_divergence); same bits either way.
   static std::pair<Pedigree, double> build(const std::string& nodelist, const std::string& edgelist,
                                            double posterior_max_filter, bool gpu_pairwise = false);
+  // ... for many (nodelist, edgelist) pairs at once (the windows of src/cli/metaprofile.rs:50-72): with gpu_pairwise ONE
+  // abn_pairwise_divergence_windows call per group of entries with the same number of samples, cut only at
+  // kBuildManyCodeBytes of codes per call.  Per entry the pedigree and p0uu, or the text of what build would have thrown.
+  struct Built;
+  static constexpr size_t kBuildManyCodeBytes = (size_t)1 << 30;
+  static std::vector<Built> build_many(const std::vector<std::pair<std::string, std::string>>& lists,
+                                       double posterior_max_filter, bool gpu_pairwise = false);
+};
+struct Pedigree::Built {
+  Pedigree pedigree;
+  double p0uu = 0.0;
+  bool ok = false;
+  std::string error;  // !ok: e.what() of the failure
+  std::string diagnostics;  // what build would have printed for this entry before returning or throwing
 };
 
 // ------------------------------------------------------------------------------------------------

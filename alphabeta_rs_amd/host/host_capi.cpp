@@ -21,6 +21,34 @@ int abh_pedigree_build(const char* nodelist, const char* edgelist, double poster
     return -1;
   }
 }
+// Pedigree::build_many over n (nodelist, edgelist) pairs: per entry the number of rows (-1: failed, its text in
+// errs + i * errcap; -2: more than cap rows), rows (n x cap x 4) and p0uu (n); returns 0, or -1 when the call itself threw
+int abh_pedigree_build_many(const char* const* nodelists, const char* const* edgelists, int n, double posterior_max_filter,
+                            int gpu_pairwise, double* rows, int cap, double* p0uu, int* nrows, char* errs, int errcap) {
+  try {
+    std::vector<std::pair<std::string, std::string>> lists;
+    for (int i = 0; i < n; ++i) lists.push_back({nodelists[i], edgelists[i]});
+    const auto built = alphabeta::Pedigree::build_many(lists, posterior_max_filter, gpu_pairwise != 0);
+    for (int i = 0; i < n; ++i) {
+      const auto& b = built[(size_t)i];
+      char* err = errs + (size_t)i * (size_t)errcap;
+      if (errcap > 0) err[0] = 0;
+      std::fputs(b.diagnostics.c_str(), stdout);
+      if (!b.ok) {
+        if (errcap > 0) std::strncpy(err, b.error.c_str(), (size_t)errcap - 1), err[errcap - 1] = 0;
+        nrows[i] = -1;
+        continue;
+      }
+      const int r = (int)b.pedigree.nrows();
+      nrows[i] = r > cap ? -2 : r;
+      if (r > 0 && r <= cap) std::memcpy(rows + (size_t)i * (size_t)cap * 4, b.pedigree.data.data(), sizeof(double) * 4 * (size_t)r);
+      p0uu[i] = b.p0uu;
+    }
+    return 0;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
 int abh_pedigree_roundtrip(const char* in_path, const char* out_path) {
   try {
     auto ped = alphabeta::Pedigree::from_file(in_path);

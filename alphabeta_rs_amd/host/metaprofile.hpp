@@ -1,7 +1,8 @@
 // metaprofile.hpp — the `alphabeta_multiple` half of the reference's `metaprofile` binary
 // (src/cli/metaprofile.rs:33-114; SURVEY.md §8f row 2, "next"): the SERIAL window loop that calls
 // alphabeta::run once per (region, window) directory becomes ONE batched, device-resident plan
-// (abn_plan_*: W windows x (S starts + B bootstraps) in three kernel launches).  The window extraction
+// (abn_plan_*: W windows x (S starts + B bootstraps) in three kernel launches) behind ONE batched pedigree
+// construction (Pedigree::build_many -> abn_pairwise_divergence_windows).  The window extraction
 // that fills those directories (src/extract.rs, src/windows.rs, src/setup.rs) is out of scope; this driver
 // starts from the directory tree setup.rs writes: <output_dir>/<region>/<window>/{nodelist,edgelist}.txt.
 //
@@ -56,20 +57,28 @@ inline Output alphabeta_multiple(const WindowArgs& args, uint32_t max_gene_lengt
     size_t index;
   };
   std::vector<Win> wins;
-  size_t index = 0;
+  // every (region, window) directory in the reference's order; all pedigrees are built together (Pedigree::build_many:
+  // one batched pairwise scan instead of one per window), then reported in that order, each window's diagnostics first
+  std::vector<std::pair<std::string, std::string>> lists;
+  std::vector<std::string> region_of;
   for (const auto& region : regions) {
     const uint32_t max = args.absolute ? region.second : 100;
-    for (uint32_t window = 0; window < max; window += step, ++index) {
+    for (uint32_t window = 0; window < max; window += step) {
       const fs::path dir = fs::path(args.output_dir) / region.first / std::to_string(window);
-      try {  // alphabeta::run's pedigree build; a failing window is reported and skipped (:64-65)
-        auto [ped, p0uu] = Pedigree::build((dir / "nodelist.txt").string(), (dir / "edgelist.txt").string(),
-                                           args.posterior_max_filter, /*gpu_pairwise=*/true);
-        if (ped.nrows() == 0) throw Error(ABN_ERR_BAD_PEDIGREE, "empty pedigree");
-        wins.push_back(Win{region.first, std::move(ped), p0uu, index});
-      } catch (const std::exception& e) {
-        std::printf("Error: Error while building pedigree: %s\n", e.what());
-      }
+      lists.push_back({(dir / "nodelist.txt").string(), (dir / "edgelist.txt").string()});
+      region_of.push_back(region.first);
     }
+  }
+  std::vector<Pedigree::Built> built = Pedigree::build_many(lists, args.posterior_max_filter, /*gpu_pairwise=*/true);
+  for (size_t index = 0; index < built.size(); ++index) {
+    Pedigree::Built& b = built[index];
+    std::fputs(b.diagnostics.c_str(), stdout);  // where the per-window build printed them: before the window's outcome
+    // alphabeta::run's pedigree build; a failing window is reported and skipped (:64-65)
+    if (b.ok && b.pedigree.nrows() == 0) b.ok = false, b.error = "empty pedigree";
+    if (b.ok)
+      wins.push_back(Win{region_of[index], std::move(b.pedigree), b.p0uu, index});
+    else
+      std::printf("Error: Error while building pedigree: %s\n", b.error.c_str());
   }
   Output out;
   out.iterations = args.iterations;

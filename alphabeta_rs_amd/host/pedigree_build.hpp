@@ -9,6 +9,21 @@
 namespace alphabeta {
 namespace detail {
 
+// The diagnostics the build prints ("Warning: Encountered invalid methylation status", "Lengths do not match") go to
+// stdout as they arise — or, while Pedigree::build_many reads an entry, into that entry's Built::diagnostics, so that its
+// caller can print them where the per-entry loop it replaces printed them.
+inline std::string*& diag_sink() {
+  static thread_local std::string* sink = nullptr;
+  return sink;
+}
+template <class... A>
+inline void diag_printf(const char* fmt, A... a) {
+  char buf[256];
+  std::snprintf(buf, sizeof buf, fmt, a...);
+  if (diag_sink()) *diag_sink() += buf;
+  else std::fputs(buf, stdout);
+}
+
 struct Site {  // the fields of MethylationSite (src/methylation_site.rs:32-45) the pedigree build reads
   double posteriormax;
   uint32_t status_numeric;  // U=0, I=1, M=2 (src/methylation_site.rs:130-136)
@@ -54,7 +69,7 @@ inline bool parse_chromosome(std::string t) {  // src/methylation_site.rs:55-68
 inline uint32_t status_from(char c) {  // src/methylation_site.rs:100-114
   if (c == 'M') return 2;
   if (c == 'I') return 1;
-  if (c != 'U') std::printf("Warning: Encountered invalid methylation status: %c. Parsed as Unmethylated\n", c);
+  if (c != 'U') diag_printf("Warning: Encountered invalid methylation status: %c. Parsed as Unmethylated\n", c);
   return 0;
 }
 
@@ -103,14 +118,25 @@ inline std::string read_file(const std::string& path, const char* what) {
   return ss.str();
 }
 
-}  // namespace detail
+// The first half of Pedigree::build (src/pedigree.rs:92-184): what the input files hold.
+struct EdgeRef { size_t from, to; };  // indices into Inputs::all
+struct Inputs {
+  std::vector<Node> all;       // every row of the nodelist, :98-117
+  std::vector<EdgeRef> edges;  // :124-136
+  std::vector<Node> nodes;     // the sampled ("Y") nodes with their sites, :138-178
+  double p0uu = 0.0;           // :180-184
+  bool same_len() const {      // every sample has the sites of the first: the pairwise scan can take the code bytes
+    for (size_t i = 1; i < nodes.size(); ++i)
+      if (nodes[i].sites.size() != nodes[0].sites.size()) return false;
+    return true;
+  }
+};
 
-inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, const std::string& edgelist,
-                                                   double posterior_max_filter, bool gpu_pairwise) {
-  using namespace detail;
+inline Inputs read_inputs(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter) {
+  Inputs in;
   const std::string nodes_txt = read_file(nodelist, "nodelist"), edges_txt = read_file(edgelist, "edgelist");
   // :98-117
-  std::vector<Node> all;
+  std::vector<Node>& all = in.all;
   {
     const auto lines = split_any(nodes_txt, "\n\r");
     for (size_t li = 1; li < lines.size(); ++li) {
@@ -123,23 +149,21 @@ inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, 
   }
   if (all.empty()) throw Error(ABN_ERR_INVALID_ARG, "No nodes could be parsed from the nodelist");
   // :124-136
-  struct EdgeRef { const Node* from; const Node* to; };
-  std::vector<EdgeRef> edges;
   {
     const auto lines = split_any(edges_txt, "\n\r");
     for (size_t li = 1; li < lines.size(); ++li) {
       const auto e = split_any(lines[li], "\t ,");
       if (e.size() < 2) continue;
-      const Node *f = nullptr, *t = nullptr;
-      for (const auto& n : all) {
-        if (!f && n.name == e[0]) f = &n;
-        if (!t && n.name == e[1]) t = &n;
+      size_t f = all.size(), t = all.size();
+      for (size_t k = 0; k < all.size(); ++k) {
+        if (f == all.size() && all[k].name == e[0]) f = k;
+        if (t == all.size() && all[k].name == e[1]) t = k;
       }
-      if (f && t) edges.push_back(EdgeRef{f, t});
+      if (f < all.size() && t < all.size()) in.edges.push_back(EdgeRef{f, t});
     }
   }
   // :138-178 — load the methylomes of the sampled ("Y") nodes
-  std::vector<Node> nodes;
+  std::vector<Node>& nodes = in.nodes;
   for (const auto& n : all)
     if (n.meth) nodes.push_back(n);
   for (auto& node : nodes) {
@@ -162,62 +186,72 @@ inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, 
   }
   double p0 = 0.0;  // :180-184
   for (const auto& n : nodes) p0 += 1.0 - n.rc_meth_lvl;
-  p0 = p0 / (double)nodes.size();
+  in.p0uu = p0 / (double)nodes.size();
+  return in;
+}
 
-  // DMatrix::from, :210-261 — entry [i][j - i - 1]
+// one byte per (sample, site): status | 0x80 when the posterior is below the filter; sample i's sites at
+// dst[i * row_stride ...] (include/abneutral.h, abn_pairwise_divergence*)
+inline void write_codes(const Inputs& in, double posterior_max_filter, uint8_t* dst, size_t row_stride) {
+  for (size_t i = 0; i < in.nodes.size(); ++i) {
+    const auto& sites = in.nodes[i].sites;
+    for (size_t k = 0; k < sites.size(); ++k)
+      dst[i * row_stride + k] =
+          (uint8_t)(sites[k].status_numeric | (sites[k].posteriormax < posterior_max_filter ? 0x80u : 0u));
+  }
+}
+
+// DMatrix::from, :210-261 — entry [i][j - i - 1] of an nn x nn array
+inline std::vector<double> dmatrix_of_pairs(size_t nn, const double* dvalue) {  // from the scan's pair order
+  std::vector<double> dm(nn * nn, 0.0);
+  size_t p = 0;
+  for (size_t i = 0; i < nn; ++i)
+    for (size_t j = i + 1; j < nn; ++j) dm[i * nn + (j - i - 1)] = dvalue[p++];
+  return dm;
+}
+inline std::vector<double> dmatrix_on_host(const Inputs& in, double posterior_max_filter) {
+  const auto& nodes = in.nodes;
   const size_t nn = nodes.size();
   std::vector<double> dm(nn * nn, 0.0);
-  bool same_len = true;
-  for (size_t i = 1; i < nn; ++i) same_len = same_len && nodes[i].sites.size() == nodes[0].sites.size();
-  if (gpu_pairwise && same_len && nn >= 2) {
-    // one byte per (sample, site): status | 0x80 when the posterior is below the filter
-    const size_t L = nodes[0].sites.size();
-    std::vector<uint8_t> codes(nn * L);
-    for (size_t i = 0; i < nn; ++i)
-      for (size_t k = 0; k < L; ++k)
-        codes[i * L + k] = (uint8_t)(nodes[i].sites[k].status_numeric |
-                                     (nodes[i].sites[k].posteriormax < posterior_max_filter ? 0x80u : 0u));
-    std::vector<double> dv(nn * (nn - 1) / 2);
-    Device& dev = default_device();
-    dev.check(abn_pairwise_divergence(dev.get(), codes.data(), (int32_t)nn, (int64_t)L, nullptr, nullptr, dv.data()),
-              "Pedigree::build (pairwise divergence)");
-    size_t p = 0;
-    for (size_t i = 0; i < nn; ++i)
-      for (size_t j = i + 1; j < nn; ++j) dm[i * nn + (j - i - 1)] = dv[p++];
-  } else {
-    for (size_t i = 0; i < nn; ++i)
-      for (size_t j = i + 1; j < nn; ++j) {
-        const auto &a = nodes[i].sites, &b = nodes[j].sites;
-        if (a.size() != b.size()) {
-          std::printf("Lengths do not match, all bets are off: %zu vs %zu\n", a.size(), b.size());
-          dm[i * nn + (j - i - 1)] = 0.0;
-          continue;
-        }
-        uint64_t div = 0, compared = 0;
-        for (size_t k = 0; k < a.size(); ++k) {
-          if (a[k].posteriormax < posterior_max_filter || b[k].posteriormax < posterior_max_filter) continue;
-          div += a[k].status_numeric > b[k].status_numeric ? a[k].status_numeric - b[k].status_numeric
-                                                           : b[k].status_numeric - a[k].status_numeric;
-          ++compared;
-        }
-        dm[i * nn + (j - i - 1)] = (double)div / (2.0 * (double)compared);
+  for (size_t i = 0; i < nn; ++i)
+    for (size_t j = i + 1; j < nn; ++j) {
+      const auto &a = nodes[i].sites, &b = nodes[j].sites;
+      if (a.size() != b.size()) {
+        diag_printf("Lengths do not match, all bets are off: %zu vs %zu\n", a.size(), b.size());
+        dm[i * nn + (j - i - 1)] = 0.0;
+        continue;
       }
-  }
+      uint64_t div = 0, compared = 0;
+      for (size_t k = 0; k < a.size(); ++k) {
+        if (a[k].posteriormax < posterior_max_filter || b[k].posteriormax < posterior_max_filter) continue;
+        div += a[k].status_numeric > b[k].status_numeric ? a[k].status_numeric - b[k].status_numeric
+                                                         : b[k].status_numeric - a[k].status_numeric;
+        ++compared;
+      }
+      dm[i * nn + (j - i - 1)] = (double)div / (2.0 * (double)compared);
+    }
+  return dm;
+}
 
-  // DMatrix::convert, :263-337 — undirected graph, edge weight = |generation difference|
+// The second half: DMatrix::convert, :263-337 — undirected graph, edge weight = |generation difference|
+inline Pedigree convert(const Inputs& in, const std::vector<double>& dm) {
+  const auto& all = in.all;
+  const auto& edges = in.edges;
+  const auto& nodes = in.nodes;
+  const size_t nn = nodes.size();
   size_t vmax = 0;
-  for (const auto& e : edges) vmax = std::max(vmax, std::max(e.from->id, e.to->id) + 1);
+  for (const auto& e : edges) vmax = std::max(vmax, std::max(all[e.from].id, all[e.to].id) + 1);
   std::vector<std::vector<std::pair<size_t, size_t>>> adj(vmax);
   for (const auto& e : edges) {
-    const size_t w = e.from->generation > e.to->generation ? e.from->generation - e.to->generation
-                                                           : e.to->generation - e.from->generation;
-    adj[e.from->id].push_back({e.to->id, w});
-    adj[e.to->id].push_back({e.from->id, w});
+    const Node &from = all[e.from], &to = all[e.to];
+    const size_t w = from.generation > to.generation ? from.generation - to.generation : to.generation - from.generation;
+    adj[from.id].push_back({to.id, w});
+    adj[to.id].push_back({from.id, w});
   }
   auto generation_of = [&](size_t id) -> uint32_t {  // :298-309
     for (const auto& e : edges) {
-      if (e.from->id == id) return e.from->generation;
-      if (e.to->id == id) return e.to->generation;
+      if (all[e.from].id == id) return all[e.from].generation;
+      if (all[e.to].id == id) return all[e.to].generation;
     }
     throw Error(ABN_ERR_BAD_PEDIGREE, "node on a path is not part of any edge");
   };
@@ -254,7 +288,125 @@ inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, 
         throw Error(ABN_ERR_BAD_PEDIGREE, "path length does not match the generation times");
       ped.push_row((double)t0, t1, t2, dm[i * nn + (j - i - 1)]);
     }
-  return {std::move(ped), p0};
+  return ped;
+}
+
+}  // namespace detail
+
+inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, const std::string& edgelist,
+                                                   double posterior_max_filter, bool gpu_pairwise) {
+  using namespace detail;
+  const Inputs in = read_inputs(nodelist, edgelist, posterior_max_filter);
+  const size_t nn = in.nodes.size();
+  std::vector<double> dm;
+  if (gpu_pairwise && in.same_len() && nn >= 2) {
+    const size_t L = in.nodes[0].sites.size();
+    std::vector<uint8_t> codes(nn * L);
+    write_codes(in, posterior_max_filter, codes.data(), L);
+    std::vector<double> dv(nn * (nn - 1) / 2);
+    Device& dev = default_device();
+    dev.check(abn_pairwise_divergence(dev.get(), codes.data(), (int32_t)nn, (int64_t)L, nullptr, nullptr, dv.data()),
+              "Pedigree::build (pairwise divergence)");
+    dm = dmatrix_of_pairs(nn, dv.data());
+  } else {
+    dm = dmatrix_on_host(in, posterior_max_filter);
+  }
+  return {convert(in, dm), in.p0uu};
+}
+
+// Pedigree::build for many (nodelist, edgelist) pairs — the windows of src/cli/metaprofile.rs:50-72.  Every entry is
+// read first; with gpu_pairwise the entries whose samples all have the same number of sites are grouped by sample
+// count, each group's codes laid side by side in one matrix (a row per sample, an entry's sites a column range) and
+// scanned by ONE abn_pairwise_divergence_windows call; the rest (and everything without gpu_pairwise) takes the host
+// loop as build does.  An entry that fails keeps its error text and never stops the others.  Host memory: the code bytes
+// twice at most (per entry, then the call's matrix: kBuildManyCodeBytes bounds the second) plus the graphs.
+inline std::vector<Pedigree::Built> Pedigree::build_many(const std::vector<std::pair<std::string, std::string>>& lists,
+                                                         double posterior_max_filter, bool gpu_pairwise) {
+  using namespace detail;
+  const size_t W = lists.size();
+  std::vector<Built> out(W);
+  std::vector<Inputs> in(W);
+  std::vector<std::vector<double>> dm(W);
+  std::vector<char> alive(W, 0);
+  auto fail = [&](size_t w, const std::exception& e) {
+    out[w].error = e.what();
+    alive[w] = 0;
+  };
+  std::map<size_t, std::vector<size_t>> by_samples;  // sample count -> entries for the scan, in order
+  // What stays of an entry until the end is its graph (names, ids, generations, edges) and either its D matrix or, for the
+  // scan, its code bytes (one per site and sample; the 24-byte site records are dropped as soon as those are written).
+  std::vector<std::vector<uint8_t>> codes_of(W);  // [sample][site], entries of the scan only
+  std::vector<size_t> sites_of(W, 0);
+  auto drop_sites = [&](size_t w) {
+    for (auto& node : in[w].nodes) std::vector<Site>().swap(node.sites);
+  };
+  for (size_t w = 0; w < W; ++w) {
+    diag_sink() = &out[w].diagnostics;
+    try {
+      in[w] = read_inputs(lists[w].first, lists[w].second, posterior_max_filter);
+      alive[w] = 1;
+      const size_t nn = in[w].nodes.size();
+      if (gpu_pairwise && in[w].same_len() && nn >= 2) {
+        sites_of[w] = in[w].nodes[0].sites.size();
+        codes_of[w].resize(nn * sites_of[w]);
+        write_codes(in[w], posterior_max_filter, codes_of[w].data(), sites_of[w]);
+        by_samples[nn].push_back(w);
+      } else {
+        dm[w] = dmatrix_on_host(in[w], posterior_max_filter);
+      }
+    } catch (const std::exception& e) {
+      fail(w, e);
+    }
+    drop_sites(w);
+    diag_sink() = nullptr;
+  }
+  for (const auto& [nn, members] : by_samples) {
+    // one call per group; a group is cut only to keep a call's code bytes under kBuildManyCodeBytes.  Every entry's
+    // columns start at a multiple of 128 bytes (whole cache lines, the scan's aligned loader); the gaps read as filtered.
+    const size_t npairs = nn * (nn - 1) / 2;
+    for (size_t m0 = 0; m0 < members.size();) {
+      std::vector<int64_t> begin, end;
+      size_t stride = 0, m1 = m0;
+      while (m1 < members.size()) {
+        const size_t L = sites_of[members[m1]], padded = (L + 127) / 128 * 128;
+        if (m1 > m0 && nn * (stride + padded) > kBuildManyCodeBytes) break;
+        begin.push_back((int64_t)stride);
+        end.push_back((int64_t)(stride + L));
+        stride += padded;
+        ++m1;
+      }
+      try {
+        std::vector<uint8_t> codes(nn * stride, (uint8_t)0x80);
+        for (size_t m = m0; m < m1; ++m) {
+          std::vector<uint8_t>& own = codes_of[members[m]];
+          const size_t L = sites_of[members[m]];
+          for (size_t i = 0; i < nn; ++i)
+            if (L) std::memcpy(codes.data() + i * stride + (size_t)begin[m - m0], own.data() + i * L, L);
+          std::vector<uint8_t>().swap(own);
+        }
+        std::vector<double> dv((m1 - m0) * npairs);
+        Device& dev = default_device();
+        dev.check(abn_pairwise_divergence_windows(dev.get(), codes.data(), (int32_t)nn, (int64_t)stride, begin.data(),
+                                                  end.data(), (int32_t)(m1 - m0), nullptr, nullptr, dv.data()),
+                  "Pedigree::build (pairwise divergence)");
+        for (size_t m = m0; m < m1; ++m) dm[members[m]] = dmatrix_of_pairs(nn, dv.data() + (m - m0) * npairs);
+      } catch (const std::exception& e) {
+        for (size_t m = m0; m < m1; ++m) fail(members[m], e);
+      }
+      m0 = m1;
+    }
+  }
+  for (size_t w = 0; w < W; ++w) {
+    if (!alive[w]) continue;
+    try {
+      out[w].pedigree = convert(in[w], dm[w]);
+      out[w].p0uu = in[w].p0uu;
+      out[w].ok = true;
+    } catch (const std::exception& e) {
+      fail(w, e);
+    }
+  }
+  return out;
 }
 
 }  // namespace alphabeta

@@ -203,6 +203,24 @@ int abn_pairwise_divergence(abn_ctx* ctx, const uint8_t* codes, int32_t n_sample
  * kernels of this call on the context's stream.  Returns after the work has completed. */
 int abn_pairwise_divergence_dev(abn_ctx* ctx, const void* dev_codes, int32_t n_samples, int64_t n_sites,
                                 void* dev_diff, void* dev_both, void* dev_dvalue, double* kernel_ms);
+/* The same for MANY column ranges ("windows") of one code matrix in one batched call — the window loop of
+ * src/cli/metaprofile.rs:50-72 around DMatrix::from (src/pedigree.rs:210-261): codes[n_samples x row_stride], window w =
+ * the sites [site_begin[w], site_end[w]) of every sample's row.  Windows may overlap, leave gaps, be empty and begin or
+ * end at any byte; site_begin / site_end are HOST arrays of n_windows entries.  Outputs are [n_windows x pairs], window
+ * w's block in the pair order above; every value is bit-identical to abn_pairwise_divergence on that window's columns
+ * (an empty or wholly filtered window: both = 0, dvalue = NaN).  Any output may be NULL.  The number of kernel launches
+ * does not depend on n_windows (short windows are one launch in all; see DESIGN.md §4 "Pairwise").
+ * ABN_ERR_INVALID_ARG: null codes, n_windows < 0, a window with begin < 0, begin > end or end > row_stride,
+ * n_samples > 65535.  n_windows == 0 or n_samples < 2: ABN_OK, nothing is written. */
+int abn_pairwise_divergence_windows(abn_ctx* ctx, const uint8_t* codes, int32_t n_samples, int64_t row_stride,
+                                    const int64_t* site_begin, const int64_t* site_end, int32_t n_windows,
+                                    uint64_t* diff, uint64_t* both, double* dvalue);
+/* ... and on DEVICE-resident codes and outputs (src/pedigree.rs:210-261, src/cli/metaprofile.rs:50-72): dev_codes
+ * u8[n_samples x row_stride] at any byte alignment; dev_diff / dev_both u64[n_windows x pairs], dev_dvalue
+ * f64[n_windows x pairs], any may be NULL; kernel_ms as above.  Returns after the work has completed. */
+int abn_pairwise_divergence_windows_dev(abn_ctx* ctx, const void* dev_codes, int32_t n_samples, int64_t row_stride,
+                                        const int64_t* site_begin, const int64_t* site_end, int32_t n_windows,
+                                        void* dev_diff, void* dev_both, void* dev_dvalue, double* kernel_ms);
 
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
