@@ -53,6 +53,8 @@ EXPORTED_SYMBOLS = [
     "abn_multi_rccl_available", "abn_reduction_tree", "abn_pairwise_divergence_dev", "abn_multi_set_window_ids",
     "abn_pairwise_divergence_windows", "abn_pairwise_divergence_windows_dev",
     "abn_multi_plan_shard", "abn_plan_last_kernels", "abn_multi_kernel_ms",
+    "abn_packed_row_stride", "abn_pack_codes", "abn_unpack_codes", "abn_pairwise_divergence_packed",
+    "abn_pairwise_divergence_packed_dev",
 ]
 
 
@@ -127,6 +129,14 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_pairwise_divergence_windows.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int32, C.c_int64, i64p, i64p, C.c_int32,
                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
     L.abn_pairwise_divergence_windows_dev.argtypes = [vp, vp, C.c_int32, C.c_int64, i64p, i64p, C.c_int32, vp, vp, vp, dp]
+    u8p = C.POINTER(C.c_uint8)
+    L.abn_packed_row_stride.argtypes = [C.c_int64]
+    L.abn_packed_row_stride.restype = C.c_int64
+    L.abn_pack_codes.argtypes = [u8p, C.c_int32, C.c_int64, C.c_int64, u8p, C.c_int64]
+    L.abn_unpack_codes.argtypes = [u8p, C.c_int32, C.c_int64, C.c_int64, u8p, C.c_int64]
+    L.abn_pairwise_divergence_packed.argtypes = [vp, u8p, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_uint64),
+                                                 C.POINTER(C.c_uint64), dp]
+    L.abn_pairwise_divergence_packed_dev.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, vp, vp, vp, dp]
     L.abn_plan_create.argtypes = [vp, op, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                   C.POINTER(vp)]
     L.abn_plan_destroy.argtypes = [vp]
@@ -209,6 +219,39 @@ def gen_boot_simplices(seed: int, window: int, b0: int, nb: int, params) -> np.n
     if rc:
         raise AbnError(rc)
     return out
+
+
+def packed_row_stride(n_sites: int) -> int:
+    """Bytes per row of 2-bit packed codes for n_sites sites: ceil(n_sites / 256) * 64 (host arithmetic)."""
+    return int(load_library().abn_packed_row_stride(int(n_sites)))
+
+
+def pack_codes(codes, row_stride: int | None = None) -> np.ndarray:
+    """(n_samples, n_sites) u8 codes (status | 0x80 if filtered) -> (n_samples, row_stride) u8 rows of 2-bit fields, the
+    input of Context.pairwise_divergence_packed (format: include/abneutral.h).  row_stride: a multiple of 64, default
+    packed_row_stride(n_sites).  Host arithmetic; a byte that is no code raises AbnError."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    n, L = codes.shape
+    stride = packed_row_stride(L) if row_stride is None else int(row_stride)
+    packed = np.empty((n, max(stride, 0)), dtype=np.uint8)
+    u8p = C.POINTER(C.c_uint8)
+    rc = load_library().abn_pack_codes(codes.ctypes.data_as(u8p), n, L, L, packed.ctypes.data_as(u8p), stride)
+    if rc != 0:
+        raise AbnError(rc, "pack_codes: a byte that is not 0, 1, 2 or 0x80 | status, or a bad row stride")
+    return packed
+
+
+def unpack_codes(packed, n_sites: int) -> np.ndarray:
+    """(n_samples, row_stride) packed rows -> (n_samples, n_sites) u8 codes; filtered sites come back as 0x80."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint8)
+    n, stride = packed.shape
+    codes = np.empty((n, int(n_sites)), dtype=np.uint8)
+    u8p = C.POINTER(C.c_uint8)
+    rc = load_library().abn_unpack_codes(packed.ctypes.data_as(u8p), n, int(n_sites), stride, codes.ctypes.data_as(u8p),
+                                         int(n_sites))
+    if rc != 0:
+        raise AbnError(rc, "unpack_codes: bad row stride")
+    return codes
 
 
 def analyze(raw) -> np.ndarray:
@@ -369,6 +412,31 @@ class Context:
         self._check(self._L.abn_pairwise_divergence_dev(self._h, C.c_void_p(codes_ptr), n_samples, n_sites,
                                                         C.c_void_p(diff_ptr or None), C.c_void_p(both_ptr or None),
                                                         C.c_void_p(dvalue_ptr or None), C.byref(ms)))
+        return ms.value
+
+    def pairwise_divergence_packed(self, packed, n_sites: int):
+        """pairwise_divergence on 2-bit packed codes (pack_codes): packed (n_samples, row_stride) u8, n_sites sites per
+        sample.  The same (diff, both, dvalue), bit for bit."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        n, stride = packed.shape
+        npairs = n * (n - 1) // 2
+        diff, both = np.zeros(npairs, dtype=np.uint64), np.zeros(npairs, dtype=np.uint64)
+        dval = np.zeros(npairs)
+        self._check(self._L.abn_pairwise_divergence_packed(self._h, packed.ctypes.data_as(C.POINTER(C.c_uint8)), n,
+                                                           int(n_sites), stride,
+                                                           diff.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                           both.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(dval)))
+        return diff, both, dval
+
+    def pairwise_divergence_packed_dev(self, packed_ptr: int, n_samples: int, n_sites: int, row_stride: int,
+                                       diff_ptr: int = 0, both_ptr: int = 0, dvalue_ptr: int = 0) -> float:
+        """The same on device-resident buffers: packed rows [n x row_stride] (16-byte aligned) in, u64 diff / both and
+        f64 dvalue [pairs] out (0 = not wanted).  Returns the kernels' HIP-event ms."""
+        ms = C.c_double(0.0)
+        self._check(self._L.abn_pairwise_divergence_packed_dev(self._h, C.c_void_p(packed_ptr), n_samples, n_sites,
+                                                               row_stride, C.c_void_p(diff_ptr or None),
+                                                               C.c_void_p(both_ptr or None),
+                                                               C.c_void_p(dvalue_ptr or None), C.byref(ms)))
         return ms.value
 
     def pairwise_divergence_windows(self, codes, begin, end):

@@ -1,7 +1,8 @@
 // Pedigree construction and the host-side analysis: abn_pairwise_divergence*, abn_analyze.
-// The scan kernels are in abn_pairwise_mx.hpp and abn_pairwise_windows.hpp; the fit path (abn_api.hip) does not include them.
+// The scan kernels are in abn_pairwise_mx.hpp, abn_pairwise_packed.hpp and abn_pairwise_windows.hpp; the fit path (abn_api.hip) does not include them.
 #include "abn_host.hpp"
 #include "abn_pairwise_mx.hpp"
+#include "abn_pairwise_packed.hpp"
 #include "abn_pairwise_windows.hpp"
 
 using namespace abn;
@@ -41,19 +42,19 @@ static hipError_t launch_pairwise_mx(int nb, bool diag, unsigned grid, hipStream
 }
 
 // One family of super-pairs (the ngroups diagonal ones, or the pairs R < C), in slabs of at most kPmxMaxJobs jobs: each
-// slab is a scan launch and a reduce launch that writes its pairs of the result.
-static int pairwise_mx_family(abn_ctx* c, PairMxArgs a, bool diag, long long nsp, int nb, bool al4, long long cu_jobs,
-                              DevBuf<unsigned long long>& partial, unsigned long long* ddiff, unsigned long long* dboth,
-                              double* ddval) {
+// slab is a scan launch and a reduce launch that writes its pairs of the result.  Args: PairMxArgs or PairPackedArgs;
+// `steps`: the 64-byte steps of a row (64 sites of byte codes, 256 of packed ones); launch(diag, grid, args).
+template <class Args, class Launch>
+static int pairwise_family(abn_ctx* c, Args a, long long steps, long long L, bool diag, long long nsp, long long cu_jobs,
+                           DevBuf<unsigned long long>& partial, unsigned long long* ddiff, unsigned long long* dboth,
+                           double* ddval, Launch launch) {
   if (nsp <= 0) return ABN_OK;
-  (void)nb;
-  // chunks per super-pair: enough jobs to fill the GPU (cu_jobs workgroups per CU), every wavefront at least a few K
-  // steps of 64 sites, and no chunk beyond 2^30 sites (the packed 32-bit halves of a job's sums)
-  const long long nk = (a.L + 63) / 64;
+  // chunks per super-pair: enough jobs to fill the GPU (cu_jobs workgroups per CU), every wavefront at least a few
+  // steps (64 bytes of every row each), and no chunk beyond 2^30 sites (the packed 32-bit halves of a job's sums)
   long long nchunks = std::max<long long>(1, ((long long)c->cus * cu_jobs + nsp - 1) / nsp);
-  nchunks = std::min<long long>(nchunks, std::max<long long>(1, nk / (4 * kPmxWaves)));
-  nchunks = std::max<long long>(nchunks, (a.L >> 30) + 1);
-  if (a.L == 0) nchunks = 1;
+  nchunks = std::min<long long>(nchunks, std::max<long long>(1, steps / (4 * kPmxWaves)));
+  nchunks = std::max<long long>(nchunks, (L >> 30) + 1);
+  if (L == 0) nchunks = 1;
   a.nchunks = (int)nchunks;
   const long long slab = std::max<long long>(1, kPmxMaxJobs / nchunks);
   HIPCHK(c, partial.alloc((size_t)std::min(slab, nsp) * (size_t)nchunks * kPmxJobElems));
@@ -61,15 +62,46 @@ static int pairwise_mx_family(abn_ctx* c, PairMxArgs a, bool diag, long long nsp
   for (long long s0 = 0; s0 < nsp; s0 += slab) {
     const long long ns = std::min(slab, nsp - s0);
     a.first = s0;
-    if (a.L > 0)
-      HIPCHK(c, al4 ? launch_pairwise_mx<true>(nb, diag, (unsigned)(ns * nchunks), c->stream, a)
-                    : launch_pairwise_mx<false>(nb, diag, (unsigned)(ns * nchunks), c->stream, a));
+    if (L > 0) HIPCHK(c, launch(diag, (unsigned)(ns * nchunks), a));
     // (no sites: zero rows are summed and every pair is 0 / 0)
     hipLaunchKernelGGL(abn_pairwise_reduce_tiles_kernel, dim3((unsigned)(ns * 256)), dim3(16 * kPmxReduceGroups), 0,
-                       c->stream, partial.p, a.L > 0 ? (int)nchunks : 0, a.n, a.ngroups, diag ? 1 : 0, s0, ddiff, dboth,
+                       c->stream, partial.p, L > 0 ? (int)nchunks : 0, a.n, a.ngroups, diag ? 1 : 0, s0, ddiff, dboth,
                        ddval);
     HIPCHK(c, hipGetLastError());
   }
+  return ABN_OK;
+}
+
+// Both families of a scan between the two events of kernel_ms.  row_bytes: what the scan reads of every row.
+template <class Args, class Launch>
+static int pairwise_scan_on_device(abn_ctx* c, const Args& a, long long steps, long long L, long long row_bytes,
+                                   unsigned long long* ddiff, unsigned long long* dboth, double* ddval,
+                                   double* kernel_ms, Launch launch) {
+  DevBuf<unsigned long long> pdiag, poff;
+  EventPair ev;
+  if (kernel_ms) {
+    HIPCHK(c, hipEventCreate(&ev.e0));
+    HIPCHK(c, hipEventCreate(&ev.e1));
+    HIPCHK(c, hipEventRecord(ev.e0, c->stream));
+  }
+  // workgroups per CU: two (eight wavefronts streaming per CU) once the scan is long enough to pay for twice the partial
+  // rows; one below (byte codes, 50 x 2 M sites: 28.6 against 30.5 us; 50 x 32 M: 304 against 282 us)
+  long long cu_diag = (long long)a.n * row_bytes >= (256ll << 20) ? 2 : 1, cu_off = 1;
+#ifdef ABN_MEASUREMENT_KNOBS
+  if (const char* e = getenv("ABN_PMX_CU_JOBS")) cu_diag = cu_off = std::max(1, atoi(e));
+#endif
+  const long long g = a.ngroups;
+  int rc = pairwise_family(c, a, steps, L, true, g, cu_diag, pdiag, ddiff, dboth, ddval, launch);
+  if (!rc) rc = pairwise_family(c, a, steps, L, false, g * (g - 1) / 2, cu_off, poff, ddiff, dboth, ddval, launch);
+  if (rc) return rc;
+  if (kernel_ms) {
+    HIPCHK(c, hipEventRecord(ev.e1, c->stream));
+    HIPCHK(c, hipEventSynchronize(ev.e1));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *kernel_ms = ms;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the partial rows are freed on return
   return ABN_OK;
 }
 
@@ -83,32 +115,11 @@ static int pairwise_mx_on_device(abn_ctx* c, const uint8_t* dcodes, int n, long 
   a.ngroups = (n + 63) / 64;
   const bool al4 = (L % 4 == 0) && ((uintptr_t)dcodes % 4 == 0);
   const int nb = a.ngroups == 1 ? (n + 15) / 16 : 4;
-  DevBuf<unsigned long long> pdiag, poff;
-  EventPair ev;
-  if (kernel_ms) {
-    HIPCHK(c, hipEventCreate(&ev.e0));
-    HIPCHK(c, hipEventCreate(&ev.e1));
-    HIPCHK(c, hipEventRecord(ev.e0, c->stream));
-  }
-  // workgroups per CU: two (eight wavefronts streaming per CU) once the scan is long enough to pay for twice the partial
-  // rows; one below (50 x 2 M sites: 28.6 against 30.5 us; 50 x 32 M: 304 against 282 us)
-  long long cu_diag = (long long)n * L >= (256ll << 20) ? 2 : 1, cu_off = 1;
-#ifdef ABN_MEASUREMENT_KNOBS
-  if (const char* e = getenv("ABN_PMX_CU_JOBS")) cu_diag = cu_off = std::max(1, atoi(e));
-#endif
-  const long long g = a.ngroups;
-  int rc = pairwise_mx_family(c, a, true, g, nb, al4, cu_diag, pdiag, ddiff, dboth, ddval);
-  if (!rc) rc = pairwise_mx_family(c, a, false, g * (g - 1) / 2, 4, al4, cu_off, poff, ddiff, dboth, ddval);
-  if (rc) return rc;
-  if (kernel_ms) {
-    HIPCHK(c, hipEventRecord(ev.e1, c->stream));
-    HIPCHK(c, hipEventSynchronize(ev.e1));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    *kernel_ms = ms;
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));  // the partial rows are freed on return
-  return ABN_OK;
+  return pairwise_scan_on_device(c, a, (L + 63) / 64, L, L, ddiff, dboth, ddval, kernel_ms,
+                                 [&](bool diag, unsigned grid, const PairMxArgs& args) {
+                                   return al4 ? launch_pairwise_mx<true>(nb, diag, grid, c->stream, args)
+                                              : launch_pairwise_mx<false>(nb, diag, grid, c->stream, args);
+                                 });
 }
 
 extern "C" int abn_pairwise_divergence_dev(abn_ctx* c, const void* dev_codes, int32_t n_samples, int64_t n_sites,
@@ -140,6 +151,88 @@ extern "C" int abn_pairwise_divergence(abn_ctx* c, const uint8_t* codes, int32_t
   if (n_sites > 0)
     HIPCHK(c, hipMemcpyAsync(dcodes.p, codes, n * (size_t)n_sites, hipMemcpyHostToDevice, c->stream));
   int rc = pairwise_mx_on_device(c, dcodes.p, n_samples, n_sites, ddiff.p, dboth.p, ddv.p, nullptr);
+  if (rc) return rc;
+  if (diff) HIPCHK(c, hipMemcpyAsync(diff, ddiff.p, ddiff.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (both) HIPCHK(c, hipMemcpyAsync(both, dboth.p, dboth.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (dvalue) HIPCHK(c, hipMemcpyAsync(dvalue, ddv.p, ddv.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ABN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the same on 2-bit packed codes (src/pedigree.rs:210-261; format: include/abneutral.h, abn_pack_codes)
+// ------------------------------------------------------------------------------------------------
+static hipError_t launch_pairwise_packed(int nb, bool diag, unsigned grid, hipStream_t s, const PairPackedArgs& a) {
+  if (!diag) {
+    hipLaunchKernelGGL((abn_pairwise_packed_kernel<4, false>), dim3(grid), dim3(kPmxThreads), 0, s, a);
+  } else {
+    switch (nb) {
+      case 1: hipLaunchKernelGGL((abn_pairwise_packed_kernel<1, true>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+      case 2: hipLaunchKernelGGL((abn_pairwise_packed_kernel<2, true>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+      case 3: hipLaunchKernelGGL((abn_pairwise_packed_kernel<3, true>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+      default: hipLaunchKernelGGL((abn_pairwise_packed_kernel<4, true>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+    }
+  }
+  return hipGetLastError();
+}
+
+static int pairwise_packed_check(abn_ctx* c, const void* packed, int32_t n, int64_t L, int64_t stride) {
+  if (!packed || n <= 0 || L < 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (stride < 0 || stride % 64 != 0 || stride < abn_packed_row_stride(L))
+    return set_err(c, ABN_ERR_INVALID_ARG, "row_stride_bytes is not a multiple of 64 that holds n_sites fields");
+  if (n > 65535) return set_err(c, ABN_ERR_INVALID_ARG, "too many samples");
+  return ABN_OK;
+}
+
+static int pairwise_packed_on_device(abn_ctx* c, const uint8_t* dpacked, int n, long long L, long long stride,
+                                     unsigned long long* ddiff, unsigned long long* dboth, double* ddval,
+                                     double* kernel_ms) {
+  PairPackedArgs a{};
+  a.packed = dpacked;
+  a.row_stride = stride;
+  a.nk = (L + 255) / 256;
+  a.n = n;
+  a.ngroups = (n + 63) / 64;
+  const int nb = a.ngroups == 1 ? (n + 15) / 16 : 4;
+  // a chunk is a whole number of 64-byte super-steps of every row; the chunk rule is the byte scan's in those steps (a
+  // wavefront's floor of four is then 16 matrix steps): the launch fills the GPU from a quarter of the bytes on
+  return pairwise_scan_on_device(c, a, a.nk, L, 64 * a.nk, ddiff, dboth, ddval, kernel_ms,
+                                 [&](bool diag, unsigned grid, const PairPackedArgs& args) {
+                                   return launch_pairwise_packed(nb, diag, grid, c->stream, args);
+                                 });
+}
+
+extern "C" int abn_pairwise_divergence_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                                  int64_t row_stride_bytes, void* dev_diff, void* dev_both,
+                                                  void* dev_dvalue, double* kernel_ms) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  if (int rc = pairwise_packed_check(c, dev_packed, n_samples, n_sites, row_stride_bytes)) return rc;
+  if ((uintptr_t)dev_packed % 16 != 0) return set_err(c, ABN_ERR_INVALID_ARG, "dev_packed is not 16-byte aligned");
+  if (n_samples < 2) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  return pairwise_packed_on_device(c, (const uint8_t*)dev_packed, n_samples, n_sites, row_stride_bytes,
+                                   (unsigned long long*)dev_diff, (unsigned long long*)dev_both, (double*)dev_dvalue,
+                                   kernel_ms);
+}
+
+extern "C" int abn_pairwise_divergence_packed(abn_ctx* c, const uint8_t* packed, int32_t n_samples, int64_t n_sites,
+                                              int64_t row_stride_bytes, uint64_t* diff, uint64_t* both, double* dvalue) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  if (int rc = pairwise_packed_check(c, packed, n_samples, n_sites, row_stride_bytes)) return rc;
+  const size_t n = (size_t)n_samples, npairs = n * (n - 1) / 2, bytes = n * (size_t)row_stride_bytes;
+  if (npairs == 0) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  DevBuf<uint8_t> dpacked;  // (device allocations are aligned far beyond the 16 bytes the kernel asks for)
+  DevBuf<unsigned long long> ddiff, dboth;
+  DevBuf<double> ddv;
+  HIPCHK(c, dpacked.alloc(std::max<size_t>(bytes, 64)));
+  HIPCHK(c, ddiff.alloc(npairs));
+  HIPCHK(c, dboth.alloc(npairs));
+  HIPCHK(c, ddv.alloc(npairs));
+  if (bytes > 0) HIPCHK(c, hipMemcpyAsync(dpacked.p, packed, bytes, hipMemcpyHostToDevice, c->stream));
+  int rc = pairwise_packed_on_device(c, dpacked.p, n_samples, n_sites, row_stride_bytes, ddiff.p, dboth.p, ddv.p, nullptr);
   if (rc) return rc;
   if (diff) HIPCHK(c, hipMemcpyAsync(diff, ddiff.p, ddiff.bytes(), hipMemcpyDeviceToHost, c->stream));
   if (both) HIPCHK(c, hipMemcpyAsync(both, dboth.p, dboth.bytes(), hipMemcpyDeviceToHost, c->stream));

@@ -68,14 +68,23 @@ __host__ __device__ inline void pmx_offdiag(long long k, int g, int& R, int& C) 
   C = R + 1 + (int)k;
 }
 
-// four sites (one dword of codes) -> one dword of each byte plane
-__device__ __forceinline__ void pmx_planes(uint32_t x, int& v, int& i, int& z) {
-  const uint32_t y = (x | (x >> 5)) & 0x07070707u;  // valid: s (0..2); filtered: 4 + s
+// four table indices (one per byte: 0..2 = valid U / I / M, 3..7 = not valid) -> one dword of each byte plane
+__device__ __forceinline__ void pmx_lookup(uint32_t y, int& v, int& i, int& z) {
   // v_perm_b32: selector bytes 0..3 pick from the second source, 4..7 from the first (zero here)
   v = (int)__builtin_amdgcn_perm(0u, 0x00010101u, y);
   i = (int)__builtin_amdgcn_perm(0u, 0x00000100u, y);
   z = (int)__builtin_amdgcn_perm(0u, 0x00ff0001u, y);
 }
+// four sites (one dword of codes) -> one dword of each byte plane
+__device__ __forceinline__ void pmx_planes(uint32_t x, int& v, int& i, int& z) {
+  pmx_lookup((x | (x >> 5)) & 0x07070707u, v, i, z);  // valid: s (0..2); filtered: 4 + s
+}
+// What a loaded dword holds.  Byte codes: four sites, so a lane's 16-byte fragment is its operand of ONE K = 64 step.
+// (The 2-bit fields of abn_pairwise_packed.hpp hold sixteen: the same fragment feeds SUB = 4 matrix steps.)
+struct PmxByteCodes {
+  static constexpr int SUB = 1;  // K steps a fragment feeds
+  static __device__ __forceinline__ void planes(uint32_t x, int, int& v, int& i, int& z) { pmx_planes(x, v, i, z); }
+};
 
 // 16 bytes of one row at byte offset `off` (fast path: the whole fragment lies inside the buffer with 4 bytes to spare)
 template <bool AL4>
@@ -115,7 +124,8 @@ __device__ __forceinline__ pmx_u32x4 pmx_load_edge(const uint8_t* codes, size_t 
 
 // The scan of one job, shared by the kernels below and in abn_pairwise_windows.hpp.
 // NB: 16-sample blocks of the row group that exist (DIAG: 1..4, the tiles bi <= bj < NB; else 4 x 4 tiles of groups R < C)
-template <int NB, bool DIAG, bool AL4>
+// Codes: the storage format of the rows (a "step" of the loaders below is 64 BYTES of every row: Codes::SUB K steps)
+template <int NB, bool DIAG, bool AL4, class Codes = PmxByteCodes>
 struct PmxScan {
   static_assert(DIAG || NB == 4, "off-diagonal super-pairs are 4 x 4 blocks");
   static constexpr int NF = DIAG ? NB : 8;            // fragments per K step: the blocks of the row group (+ of the column group)
@@ -152,44 +162,47 @@ struct PmxScan {
 #pragma unroll
     for (int d = 0; d < DSTEPS; ++d) {
       if (Part::value && d >= cnt) break;
-      pmx_i32x4 V[NF], I[NF], Z[NF];
 #pragma unroll
-      for (int f = 0; f < NF; ++f)
+      for (int sub = 0; sub < Codes::SUB; ++sub) {  // the K steps the loaded fragments feed
+        pmx_i32x4 V[NF], I[NF], Z[NF];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          int v, i, z;
-          pmx_planes(x[d][f][e], v, i, z);
-          V[f][e] = v;
-          I[f][e] = i;
-          Z[f][e] = z;
-        }
-      // D[row][col] = sum_k A[row][k] B[k][col]: A = the row block's fragment, B = the column block's (same registers
-      // for a diagonal tile).  The three products of a tile are issued a whole round of tiles apart: no dependent pair
-      // of matrix instructions back to back.
-      int t = 0;
+        for (int f = 0; f < NF; ++f)
 #pragma unroll
-      for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
+          for (int e = 0; e < 4; ++e) {
+            int v, i, z;
+            Codes::planes(x[d][f][e], sub, v, i, z);
+            V[f][e] = v;
+            I[f][e] = i;
+            Z[f][e] = z;
+          }
+        // D[row][col] = sum_k A[row][k] B[k][col]: A = the row block's fragment, B = the column block's (same registers
+        // for a diagonal tile).  The three products of a tile are issued a whole round of tiles apart: no dependent pair
+        // of matrix instructions back to back.
+        int t = 0;
 #pragma unroll
-        for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
-          const int fa = bi, fb = DIAG ? bj : 4 + bj;
-          S1[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(V[fa], V[fb], S1[t], 0, 0, 0);
-        }
-      t = 0;
+        for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
 #pragma unroll
-      for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
+          for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
+            const int fa = bi, fb = DIAG ? bj : 4 + bj;
+            S1[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(V[fa], V[fb], S1[t], 0, 0, 0);
+          }
+        t = 0;
 #pragma unroll
-        for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
-          const int fa = bi, fb = DIAG ? bj : 4 + bj;
-          S2[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(I[fa], I[fb], S2[t], 0, 0, 0);
-        }
-      t = 0;
+        for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
 #pragma unroll
-      for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
+          for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
+            const int fa = bi, fb = DIAG ? bj : 4 + bj;
+            S2[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(I[fa], I[fb], S2[t], 0, 0, 0);
+          }
+        t = 0;
 #pragma unroll
-        for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
-          const int fa = bi, fb = DIAG ? bj : 4 + bj;
-          S2[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Z[fa], Z[fb], S2[t], 0, 0, 0);
-        }
+        for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
+#pragma unroll
+          for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
+            const int fa = bi, fb = DIAG ? bj : 4 + bj;
+            S2[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Z[fa], Z[fb], S2[t], 0, 0, 0);
+          }
+      }
     }
   }
 

@@ -298,7 +298,8 @@ class Pedigree {  // src/pedigree.rs:44-45
   }
 
   // src/pedigree.rs:92-193; defined in pedigree_build.hpp.  gpu_pairwise: the O(pairs x sites) status
-  // comparison (DMatrix::from, :210-261) runs on the MI355X (abn_pairwise_divergence); same bits either way.
+  // comparison (DMatrix::from, :210-261) runs on the MI355X, on 2-bit codes packed straight from the site records
+  // (abn_pairwise_divergence_packed); same bits either way.
   static std::pair<Pedigree, double> build(const std::string& nodelist, const std::string& edgelist,
                                            double posterior_max_filter, bool gpu_pairwise = false);
   // ... for many (nodelist, edgelist) pairs at once (the windows of src/cli/metaprofile.rs:50-72): with gpu_pairwise ONE

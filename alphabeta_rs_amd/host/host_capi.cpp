@@ -7,10 +7,11 @@
 
 extern "C" {
 // returns the number of rows (<0 on error); rows (capacity cap x 4) and *p0uu are filled
-int abh_pedigree_build(const char* nodelist, const char* edgelist, double posterior_max_filter, double* rows, int cap,
-                       double* p0uu, char* err, int errcap) {
+static int pedigree_build(const char* nodelist, const char* edgelist, double posterior_max_filter, bool gpu_pairwise,
+                          const char* out_path, double* rows, int cap, double* p0uu, char* err, int errcap) {
   try {
-    auto [ped, p0] = alphabeta::Pedigree::build(nodelist, edgelist, posterior_max_filter);
+    auto [ped, p0] = alphabeta::Pedigree::build(nodelist, edgelist, posterior_max_filter, gpu_pairwise);
+    if (out_path) ped.to_file(out_path);
     const int n = (int)ped.nrows();
     if (n > cap) return -2;
     if (n > 0) std::memcpy(rows, ped.data.data(), sizeof(double) * 4 * (size_t)n);  // an empty pedigree has no buffer
@@ -21,6 +22,17 @@ int abh_pedigree_build(const char* nodelist, const char* edgelist, double poster
     return -1;
   }
 }
+int abh_pedigree_build(const char* nodelist, const char* edgelist, double posterior_max_filter, double* rows, int cap,
+                       double* p0uu, char* err, int errcap) {
+  return pedigree_build(nodelist, edgelist, posterior_max_filter, false, nullptr, rows, cap, p0uu, err, errcap);
+}
+// the same with the scan on the GPU, as the `alphabeta` CLI builds its pedigree; out_path (nullable): Pedigree::to_file
+int abh_pedigree_build_gpu(const char* nodelist, const char* edgelist, double posterior_max_filter, const char* out_path,
+                           double* rows, int cap, double* p0uu, char* err, int errcap) {
+  return pedigree_build(nodelist, edgelist, posterior_max_filter, true, out_path, rows, cap, p0uu, err, errcap);
+}
+// scans Pedigree::build has sent through abn_pairwise_divergence_packed since the library was loaded
+long long abh_packed_scan_calls() { return alphabeta::detail::packed_scan_calls().load(); }
 // Pedigree::build_many over n (nodelist, edgelist) pairs: per entry the number of rows (-1: failed, its text in
 // errs + i * errcap; -2: more than cap rows), rows (n x cap x 4) and p0uu (n); returns 0, or -1 when the call itself threw
 int abh_pedigree_build_many(const char* const* nodelists, const char* const* edgelists, int n, double posterior_max_filter,

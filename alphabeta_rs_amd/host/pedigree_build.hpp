@@ -4,6 +4,8 @@
 // the O(pairs x sites) status comparison is integer work done once per run.
 #pragma once
 
+#include <atomic>
+
 #include "alphabeta.hpp"
 
 namespace alphabeta {
@@ -201,6 +203,26 @@ inline void write_codes(const Inputs& in, double posterior_max_filter, uint8_t* 
   }
 }
 
+// the same as 2-bit fields, straight from the site records (no byte matrix in between): 0 / 1 / 2 = the status, 3 = the
+// posterior is below the filter; site 16 g + 4 j + e in byte 4 g + e of the row at bits 2j..2j+1, every field from the
+// last site to the end of the row 3 (include/abneutral.h, abn_pairwise_divergence_packed).  dst: nodes x row_stride bytes
+inline void write_codes_packed(const Inputs& in, double posterior_max_filter, uint8_t* dst, size_t row_stride) {
+  std::memset(dst, 0xff, in.nodes.size() * row_stride);
+  for (size_t i = 0; i < in.nodes.size(); ++i) {
+    const auto& sites = in.nodes[i].sites;
+    uint8_t* row = dst + i * row_stride;
+    for (size_t k = 0; k < sites.size(); ++k) {
+      const unsigned f = sites[k].posteriormax < posterior_max_filter ? 3u : (sites[k].status_numeric & 3u);
+      row[(k >> 4) * 4 + (k & 3)] ^= (uint8_t)((3u ^ f) << (2 * ((k >> 2) & 3)));  // the field was 3
+    }
+  }
+}
+// scans Pedigree::build has sent through the packed entry (read by the tests through host_capi.cpp)
+inline std::atomic<long long>& packed_scan_calls() {
+  static std::atomic<long long> calls{0};
+  return calls;
+}
+
 // DMatrix::from, :210-261 — entry [i][j - i - 1] of an nn x nn array
 inline std::vector<double> dmatrix_of_pairs(size_t nn, const double* dvalue) {  // from the scan's pair order
   std::vector<double> dm(nn * nn, 0.0);
@@ -301,12 +323,15 @@ inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, 
   std::vector<double> dm;
   if (gpu_pairwise && in.same_len() && nn >= 2) {
     const size_t L = in.nodes[0].sites.size();
-    std::vector<uint8_t> codes(nn * L);
-    write_codes(in, posterior_max_filter, codes.data(), L);
+    const size_t stride = (size_t)abn_packed_row_stride((int64_t)L);
+    std::vector<uint8_t> packed(nn * stride);  // a quarter of the code bytes to hold and to upload
+    write_codes_packed(in, posterior_max_filter, packed.data(), stride);
     std::vector<double> dv(nn * (nn - 1) / 2);
     Device& dev = default_device();
-    dev.check(abn_pairwise_divergence(dev.get(), codes.data(), (int32_t)nn, (int64_t)L, nullptr, nullptr, dv.data()),
+    dev.check(abn_pairwise_divergence_packed(dev.get(), packed.data(), (int32_t)nn, (int64_t)L, (int64_t)stride, nullptr,
+                                             nullptr, dv.data()),
               "Pedigree::build (pairwise divergence)");
+    packed_scan_calls().fetch_add(1, std::memory_order_relaxed);
     dm = dmatrix_of_pairs(nn, dv.data());
   } else {
     dm = dmatrix_on_host(in, posterior_max_filter);

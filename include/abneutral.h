@@ -222,6 +222,45 @@ int abn_pairwise_divergence_windows_dev(abn_ctx* ctx, const void* dev_codes, int
                                         const int64_t* site_begin, const int64_t* site_end, int32_t n_windows,
                                         void* dev_diff, void* dev_both, void* dev_dvalue, double* kernel_ms);
 
+/* ------------------------------------------------------------------ 2-bit packed codes for the scan above
+ * DMatrix::from (src/pedigree.rs:210-261) reads two bits of every code byte: U, I, M, or "filtered for this sample".
+ * The packed format stores just those — a quarter of the bytes to keep, to upload and to read:
+ *   one 2-bit field per (sample, site): 0 = U, 1 = I, 2 = M (status_numeric, src/methylation_site.rs:130-136),
+ *   3 = filtered (posteriormax below the filter, src/pedigree.rs:249-251);
+ *   sites in groups of 16, one little-endian dword per group: site 16 g + 4 j + e (j, e in 0..3) is stored in byte e of
+ *   dword g at bits 2j..2j+1 — so (dword >> 2j) & 0x03030303 is four byte-sized codes;
+ *   sample i's row starts at packed + i * row_stride_bytes; row_stride_bytes is a multiple of 64 (256 sites), at least
+ *   abn_packed_row_stride(n_sites); EVERY field from site n_sites to the end of the row must be 3 (the scan does not
+ *   check it; abn_pack_codes writes it); a device-resident buffer is 16-byte aligned (a host buffer: any alignment).
+ * Not offered on packed codes: the windows entry points (a window that begins at an arbitrary site is not
+ * field-aligned) — abn_pairwise_divergence_windows* and Pedigree::build_many stay on bytes.
+ *
+ * Host arithmetic, no device: bytes per row for n_sites sites — ceil(n_sites / 256) * 64; 0 for n_sites <= 0. */
+int64_t abn_packed_row_stride(int64_t n_sites);
+/* src/pedigree.rs:210-261, the codes of abn_pairwise_divergence -> packed rows (host arithmetic, no device).
+ * codes[n_samples rows of src_row_stride bytes, the first n_sites used]; packed[n_samples x row_stride_bytes], padding
+ * fields included, is written.  ABN_ERR_INVALID_ARG: a null pointer, a negative size, src_row_stride < n_sites, a
+ * row_stride_bytes that is not a multiple of 64 or is below abn_packed_row_stride(n_sites), or a byte that is not 0, 1, 2
+ * or 0x80 | anything (the contents of packed are then unspecified). */
+int abn_pack_codes(const uint8_t* codes, int32_t n_samples, int64_t n_sites, int64_t src_row_stride, uint8_t* packed,
+                   int64_t row_stride_bytes);
+/* ... and back (src/pedigree.rs:210-261): codes[n_samples rows of dst_row_stride bytes] receive 0, 1, 2, or 0x80 for a
+ * filtered site (the status under the flag is not kept).  Same argument rules. */
+int abn_unpack_codes(const uint8_t* packed, int32_t n_samples, int64_t n_sites, int64_t row_stride_bytes, uint8_t* codes,
+                     int64_t dst_row_stride);
+/* abn_pairwise_divergence (src/pedigree.rs:210-261) on packed codes: the same outputs, bit for bit, in the same pair
+ * order, with the same NULL rules.  ABN_ERR_INVALID_ARG: null packed, n_samples <= 0 or > 65535, n_sites < 0, a
+ * row_stride_bytes that is not a multiple of 64 or is below abn_packed_row_stride(n_sites).  n_samples < 2: ABN_OK,
+ * nothing is written.  n_sites == 0: both = diff = 0, dvalue = NaN. */
+int abn_pairwise_divergence_packed(abn_ctx* ctx, const uint8_t* packed, int32_t n_samples, int64_t n_sites,
+                                   int64_t row_stride_bytes, uint64_t* diff, uint64_t* both, double* dvalue);
+/* ... and on DEVICE-resident packed codes and outputs (src/pedigree.rs:210-261), as abn_pairwise_divergence_dev:
+ * dev_packed u8[n_samples x row_stride_bytes], 16-byte aligned (else ABN_ERR_INVALID_ARG); any output may be NULL;
+ * kernel_ms as above.  Returns after the work has completed. */
+int abn_pairwise_divergence_packed_dev(abn_ctx* ctx, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                       int64_t row_stride_bytes, void* dev_diff, void* dev_both, void* dev_dvalue,
+                                       double* kernel_ms);
+
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
  * src/cli/metaprofile.rs:50-72, where every window shares nodelist/edgelist), S starts and B bootstraps
