@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "abn_multi_plan_shard", "abn_plan_last_kernels", "abn_multi_kernel_ms",
     "abn_packed_row_stride", "abn_pack_codes", "abn_unpack_codes", "abn_pairwise_divergence_packed",
     "abn_pairwise_divergence_packed_dev",
+    "abn_pairwise_divergence_windows_packed", "abn_pairwise_divergence_windows_packed_dev",
 ]
 
 
@@ -137,6 +138,10 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_pairwise_divergence_packed.argtypes = [vp, u8p, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_uint64),
                                                  C.POINTER(C.c_uint64), dp]
     L.abn_pairwise_divergence_packed_dev.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, vp, vp, vp, dp]
+    L.abn_pairwise_divergence_windows_packed.argtypes = [vp, u8p, C.c_int32, C.c_int64, C.c_int64, i64p, i64p, C.c_int32,
+                                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
+    L.abn_pairwise_divergence_windows_packed_dev.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, i64p, i64p,
+                                                             C.c_int32, vp, vp, vp, dp]
     L.abn_plan_create.argtypes = [vp, op, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                   C.POINTER(vp)]
     L.abn_plan_destroy.argtypes = [vp]
@@ -471,6 +476,42 @@ class Context:
             self._h, C.c_void_p(codes_ptr), n_samples, row_stride, b.ctypes.data_as(i64p), e.ctypes.data_as(i64p),
             b.shape[0], C.c_void_p(diff_ptr or None), C.c_void_p(both_ptr or None), C.c_void_p(dvalue_ptr or None),
             C.byref(ms)))
+        return ms.value
+
+    def pairwise_divergence_windows_packed(self, packed, n_sites: int, begin, end):
+        """pairwise_divergence_windows on 2-bit packed codes (pack_codes): packed (n_samples, row_stride) u8 with n_sites
+        sites per sample; windows [begin[w], end[w]) in sites, at any site.  Returns (diff, both, dvalue), each of shape
+        (n_windows, pairs), bit-identical to pairwise_divergence_windows on the unpacked codes."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        n, stride = packed.shape
+        b, e = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+        if b.ndim != 1 or b.shape != e.shape:
+            raise ValueError("begin and end are 1-d arrays of one length")
+        W, npairs = b.shape[0], n * (n - 1) // 2
+        diff, both = np.zeros((W, npairs), dtype=np.uint64), np.zeros((W, npairs), dtype=np.uint64)
+        dval = np.zeros((W, npairs))
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.abn_pairwise_divergence_windows_packed(
+            self._h, packed.ctypes.data_as(C.POINTER(C.c_uint8)), n, int(n_sites), stride, b.ctypes.data_as(i64p),
+            e.ctypes.data_as(i64p), W, diff.ctypes.data_as(C.POINTER(C.c_uint64)),
+            both.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(dval)))
+        return diff, both, dval
+
+    def pairwise_divergence_windows_packed_dev(self, packed_ptr: int, n_samples: int, n_sites: int, row_stride: int,
+                                               begin, end, diff_ptr: int = 0, both_ptr: int = 0,
+                                               dvalue_ptr: int = 0) -> float:
+        """The same on device-resident buffers: packed rows [n x row_stride] (16-byte aligned) in, u64 diff / both and
+        f64 dvalue [n_windows x pairs] out (0 = not wanted); begin / end are host arrays.  Returns the kernels'
+        HIP-event ms."""
+        b, e = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+        if b.ndim != 1 or b.shape != e.shape:
+            raise ValueError("begin and end are 1-d arrays of one length")
+        ms = C.c_double(0.0)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.abn_pairwise_divergence_windows_packed_dev(
+            self._h, C.c_void_p(packed_ptr), n_samples, n_sites, row_stride, b.ctypes.data_as(i64p),
+            e.ctypes.data_as(i64p), b.shape[0], C.c_void_p(diff_ptr or None), C.c_void_p(both_ptr or None),
+            C.c_void_p(dvalue_ptr or None), C.byref(ms)))
         return ms.value
 
     # ---- (3) boot_model::run

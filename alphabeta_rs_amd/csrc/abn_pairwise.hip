@@ -1,9 +1,11 @@
 // Pedigree construction and the host-side analysis: abn_pairwise_divergence*, abn_analyze.
-// The scan kernels are in abn_pairwise_mx.hpp, abn_pairwise_packed.hpp and abn_pairwise_windows.hpp; the fit path (abn_api.hip) does not include them.
+// The scan kernels are in abn_pairwise_mx.hpp, abn_pairwise_packed.hpp, abn_pairwise_windows.hpp and
+// abn_pairwise_windows_packed.hpp; the fit path (abn_api.hip) does not include them.
 #include "abn_host.hpp"
 #include "abn_pairwise_mx.hpp"
 #include "abn_pairwise_packed.hpp"
 #include "abn_pairwise_windows.hpp"
+#include "abn_pairwise_windows_packed.hpp"
 
 using namespace abn;
 
@@ -261,6 +263,8 @@ static hipError_t launch_pairwise_win(int nb, bool diag, unsigned grid, hipStrea
 
 // The jobs of one family of super-pairs over all windows, in launches ("slabs") of at most kPmxMaxJobs jobs; the chunks
 // of one (window, super-pair) never straddle two slabs, so a slab's reduce launch finds all rows of its tasks.
+// A window's chunks are cut at multiples of chunk[w] from its begin rounded down to `align` sites (1: byte codes, from the
+// begin itself; 256: packed codes, whole super-steps); launch(diag, grid, args) starts the scan kernel of the format.
 struct PairWinFamily {
   struct Slab { size_t job0, njobs, task0, ntasks, nrows; };
   std::vector<PairWinJob> jobs;
@@ -271,12 +275,13 @@ struct PairWinFamily {
   DevBuf<PairWinTask> dtasks;
   DevBuf<unsigned long long> partial;
 
-  void plan(long long nsp, const int64_t* begin, const int64_t* end, int W, const std::vector<long long>& chunk) {
+  void plan(long long nsp, const int64_t* begin, const int64_t* end, int W, const std::vector<long long>& chunk,
+            long long align) {
     if (nsp <= 0) return;
     Slab cur{0, 0, 0, 0, 0};
     for (int w = 0; w < W; ++w) {
-      const long long L = end[w] - begin[w];
-      const long long nch = std::max<long long>(1, (L + chunk[w] - 1) / chunk[w]);
+      const long long b0 = begin[w] - begin[w] % align;
+      const long long nch = std::max<long long>(1, (end[w] - b0 + chunk[w] - 1) / chunk[w]);
       for (long long sp = 0; sp < nsp; ++sp) {
         if (cur.njobs + (size_t)nch > (size_t)kPmxMaxJobs) {
           slabs.push_back(cur);
@@ -287,8 +292,8 @@ struct PairWinFamily {
           ++cur.ntasks;
         }
         for (long long k = 0; k < nch; ++k) {
-          const long long b = begin[w] + k * chunk[w];
-          jobs.push_back(PairWinJob{b, std::min<long long>(b + chunk[w], end[w]), w, (int)sp,
+          const long long b = b0 + k * chunk[w];
+          jobs.push_back(PairWinJob{std::max<long long>(b, begin[w]), std::min<long long>(b + chunk[w], end[w]), w, (int)sp,
                                     nch > 1 ? (int)cur.nrows++ : -1});
         }
         cur.njobs += (size_t)nch;
@@ -307,13 +312,13 @@ struct PairWinFamily {
       HIPCHK(c, hipMemcpyAsync(dtasks.p, tasks.data(), dtasks.bytes(), hipMemcpyHostToDevice, c->stream));
     return ABN_OK;
   }
-  int run(abn_ctx* c, PairWinArgs a, bool diag, int nb, bool al4) {
+  template <class Launch>
+  int run(abn_ctx* c, PairWinArgs a, bool diag, Launch launch) {
     a.partial = partial.p;
     for (const Slab& s : slabs) {
       if (s.njobs == 0) continue;
       a.jobs = djobs.p + s.job0;
-      HIPCHK(c, al4 ? launch_pairwise_win<true>(nb, diag, (unsigned)s.njobs, c->stream, a)
-                    : launch_pairwise_win<false>(nb, diag, (unsigned)s.njobs, c->stream, a));
+      HIPCHK(c, launch(diag, (unsigned)s.njobs, a));
       if (s.ntasks == 0) continue;
       hipLaunchKernelGGL(abn_pairwise_win_reduce_kernel, dim3((unsigned)(s.ntasks * 256)), dim3(16 * kPmxReduceGroups), 0,
                          c->stream, partial.p, dtasks.p + s.task0, a.n, a.ngroups, diag ? 1 : 0, a.diff, a.both,
@@ -323,6 +328,37 @@ struct PairWinFamily {
     return ABN_OK;
   }
 };
+
+// Both families of a windows scan between the two events of kernel_ms: plan, upload the job tables, run.
+template <class Launch>
+static int pairwise_windows_run(abn_ctx* c, const PairWinArgs& a, const int64_t* begin, const int64_t* end, int W,
+                                const std::vector<long long>& chunk, long long align, double* kernel_ms, Launch launch) {
+  const long long g = a.ngroups;
+  PairWinFamily fdiag, foff;  // (their host tables outlive the copies: the stream is synchronised below)
+  fdiag.plan(g, begin, end, W, chunk, align);
+  foff.plan(g * (g - 1) / 2, begin, end, W, chunk, align);
+  int rc = fdiag.upload(c);
+  if (!rc) rc = foff.upload(c);
+  if (rc) return rc;
+  EventPair ev;
+  if (kernel_ms) {
+    HIPCHK(c, hipEventCreate(&ev.e0));
+    HIPCHK(c, hipEventCreate(&ev.e1));
+    HIPCHK(c, hipEventRecord(ev.e0, c->stream));
+  }
+  rc = fdiag.run(c, a, true, launch);
+  if (!rc) rc = foff.run(c, a, false, launch);
+  if (rc) return rc;
+  if (kernel_ms) {
+    HIPCHK(c, hipEventRecord(ev.e1, c->stream));
+    HIPCHK(c, hipEventSynchronize(ev.e1));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *kernel_ms = ms;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the job tables and the partial rows are freed on return
+  return ABN_OK;
+}
 
 static int pairwise_windows_check(abn_ctx* c, const void* codes, int32_t n, int64_t row_stride, const int64_t* begin,
                                   const int64_t* end, int32_t W) {
@@ -359,31 +395,11 @@ static int pairwise_windows_on_device(abn_ctx* c, const uint8_t* dcodes, int n, 
     chunk[(size_t)w] = ch;
   }
   const int nb = a.ngroups == 1 ? (n + 15) / 16 : 4;
-  const long long g = a.ngroups;
-  PairWinFamily fdiag, foff;  // (their host tables outlive the copies: the stream is synchronised below)
-  fdiag.plan(g, begin, end, W, chunk);
-  foff.plan(g * (g - 1) / 2, begin, end, W, chunk);
-  int rc = fdiag.upload(c);
-  if (!rc) rc = foff.upload(c);
-  if (rc) return rc;
-  EventPair ev;
-  if (kernel_ms) {
-    HIPCHK(c, hipEventCreate(&ev.e0));
-    HIPCHK(c, hipEventCreate(&ev.e1));
-    HIPCHK(c, hipEventRecord(ev.e0, c->stream));
-  }
-  rc = fdiag.run(c, a, true, nb, al4);
-  if (!rc) rc = foff.run(c, a, false, 4, al4);
-  if (rc) return rc;
-  if (kernel_ms) {
-    HIPCHK(c, hipEventRecord(ev.e1, c->stream));
-    HIPCHK(c, hipEventSynchronize(ev.e1));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    *kernel_ms = ms;
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));  // the job tables and the partial rows are freed on return
-  return ABN_OK;
+  return pairwise_windows_run(c, a, begin, end, W, chunk, 1, kernel_ms,
+                              [&](bool diag, unsigned grid, const PairWinArgs& args) {
+                                return al4 ? launch_pairwise_win<true>(nb, diag, grid, c->stream, args)
+                                           : launch_pairwise_win<false>(nb, diag, grid, c->stream, args);
+                              });
 }
 
 extern "C" int abn_pairwise_divergence_windows_dev(abn_ctx* c, const void* dev_codes, int32_t n_samples,
@@ -420,6 +436,120 @@ extern "C" int abn_pairwise_divergence_windows(abn_ctx* c, const uint8_t* codes,
     HIPCHK(c, hipMemcpyAsync(dcodes.p, codes, n * (size_t)row_stride, hipMemcpyHostToDevice, c->stream));
   int rc = pairwise_windows_on_device(c, dcodes.p, n_samples, row_stride, site_begin, site_end, n_windows, ddiff.p,
                                       dboth.p, ddv.p, nullptr);
+  if (rc) return rc;
+  if (diff) HIPCHK(c, hipMemcpyAsync(diff, ddiff.p, ddiff.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (both) HIPCHK(c, hipMemcpyAsync(both, dboth.p, dboth.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (dvalue) HIPCHK(c, hipMemcpyAsync(dvalue, ddv.p, ddv.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ABN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ... and for many windows of one 2-bit packed matrix (src/cli/metaprofile.rs:50-72 around src/pedigree.rs:210-261)
+// ------------------------------------------------------------------------------------------------
+static hipError_t launch_pairwise_win_packed(int nb, bool diag, unsigned grid, hipStream_t s, const PairWinArgs& a) {
+  if (!diag) {
+    hipLaunchKernelGGL((abn_pairwise_win_packed_kernel<4, false>), dim3(grid), dim3(kPmxThreads), 0, s, a);
+  } else {
+    switch (nb) {
+      case 1: hipLaunchKernelGGL((abn_pairwise_win_packed_kernel<1, true>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+      case 2: hipLaunchKernelGGL((abn_pairwise_win_packed_kernel<2, true>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+      case 3: hipLaunchKernelGGL((abn_pairwise_win_packed_kernel<3, true>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+      default: hipLaunchKernelGGL((abn_pairwise_win_packed_kernel<4, true>), dim3(grid), dim3(kPmxThreads), 0, s, a); break;
+    }
+  }
+  return hipGetLastError();
+}
+
+// Sites per job of each window: kPmxWinPackedChunkSites, more (whole super-steps) only where a window would otherwise
+// need more rows of `partial` than one launch keeps.  Counted from the window's begin rounded down to a super-step.
+static int pairwise_windows_packed_chunks(abn_ctx* c, const int64_t* begin, const int64_t* end, int W,
+                                          std::vector<long long>& chunk) {
+  chunk.resize((size_t)W);
+  for (int w = 0; w < W; ++w) {
+    const long long span = end[w] - (begin[w] - begin[w] % kPackedStepSites);
+    long long ch = kPmxWinPackedChunkSites;
+    if ((span + ch - 1) / ch > kPmxMaxJobs)
+      ch = ((span + kPmxMaxJobs - 1) / kPmxMaxJobs + kPackedStepSites - 1) / kPackedStepSites * kPackedStepSites;
+    if (ch >= (1ll << 30)) return set_err(c, ABN_ERR_INVALID_ARG, "window too long");
+    chunk[(size_t)w] = ch;
+  }
+  return ABN_OK;
+}
+
+static int pairwise_windows_packed_check(abn_ctx* c, const void* packed, int32_t n, int64_t L, int64_t stride,
+                                         const int64_t* begin, const int64_t* end, int32_t W,
+                                         std::vector<long long>& chunk) {
+  if (int rc = pairwise_packed_check(c, packed, n, L, stride)) return rc;
+  if (W < 0 || (W > 0 && (!begin || !end))) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  for (int w = 0; w < W; ++w)
+    if (begin[w] < 0 || begin[w] > end[w] || end[w] > L)
+      return set_err(c, ABN_ERR_INVALID_ARG, "window " + std::to_string(w) + " is not a column range of the rows");
+  return pairwise_windows_packed_chunks(c, begin, end, W, chunk);
+}
+
+static int pairwise_windows_packed_on_device(abn_ctx* c, const uint8_t* dpacked, int n, long long stride,
+                                             const int64_t* begin, const int64_t* end, int W,
+                                             const std::vector<long long>& chunk, unsigned long long* ddiff,
+                                             unsigned long long* dboth, double* ddval, double* kernel_ms) {
+  PairWinArgs a{};
+  a.codes = dpacked;
+  a.row_stride = stride;
+  a.n = n;
+  a.ngroups = (n + 63) / 64;
+  a.diff = ddiff;
+  a.both = dboth;
+  a.dvalue = ddval;
+  const int nb = a.ngroups == 1 ? (n + 15) / 16 : 4;
+  return pairwise_windows_run(c, a, begin, end, W, chunk, kPackedStepSites, kernel_ms,
+                              [&](bool diag, unsigned grid, const PairWinArgs& args) {
+                                return launch_pairwise_win_packed(nb, diag, grid, c->stream, args);
+                              });
+}
+
+extern "C" int abn_pairwise_divergence_windows_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples,
+                                                          int64_t n_sites, int64_t row_stride_bytes,
+                                                          const int64_t* site_begin, const int64_t* site_end,
+                                                          int32_t n_windows, void* dev_diff, void* dev_both,
+                                                          void* dev_dvalue, double* kernel_ms) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  std::vector<long long> chunk;
+  if (int rc = pairwise_windows_packed_check(c, dev_packed, n_samples, n_sites, row_stride_bytes, site_begin, site_end,
+                                             n_windows, chunk))
+    return rc;
+  if ((uintptr_t)dev_packed % 16 != 0) return set_err(c, ABN_ERR_INVALID_ARG, "dev_packed is not 16-byte aligned");
+  if (n_samples < 2 || n_windows == 0) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  return pairwise_windows_packed_on_device(c, (const uint8_t*)dev_packed, n_samples, row_stride_bytes, site_begin,
+                                           site_end, n_windows, chunk, (unsigned long long*)dev_diff,
+                                           (unsigned long long*)dev_both, (double*)dev_dvalue, kernel_ms);
+}
+
+extern "C" int abn_pairwise_divergence_windows_packed(abn_ctx* c, const uint8_t* packed, int32_t n_samples,
+                                                      int64_t n_sites, int64_t row_stride_bytes,
+                                                      const int64_t* site_begin, const int64_t* site_end,
+                                                      int32_t n_windows, uint64_t* diff, uint64_t* both,
+                                                      double* dvalue) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  std::vector<long long> chunk;
+  if (int rc = pairwise_windows_packed_check(c, packed, n_samples, n_sites, row_stride_bytes, site_begin, site_end,
+                                             n_windows, chunk))
+    return rc;
+  if (n_samples < 2 || n_windows == 0) return ABN_OK;
+  const size_t n = (size_t)n_samples, nout = n * (n - 1) / 2 * (size_t)n_windows, bytes = n * (size_t)row_stride_bytes;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  DevBuf<uint8_t> dpacked;  // (device allocations are aligned far beyond the 16 bytes the kernel asks for)
+  DevBuf<unsigned long long> ddiff, dboth;
+  DevBuf<double> ddv;
+  HIPCHK(c, dpacked.alloc(std::max<size_t>(bytes, 64)));
+  if (diff) HIPCHK(c, ddiff.alloc(nout));
+  if (both) HIPCHK(c, dboth.alloc(nout));
+  if (dvalue) HIPCHK(c, ddv.alloc(nout));
+  if (bytes > 0) HIPCHK(c, hipMemcpyAsync(dpacked.p, packed, bytes, hipMemcpyHostToDevice, c->stream));
+  int rc = pairwise_windows_packed_on_device(c, dpacked.p, n_samples, row_stride_bytes, site_begin, site_end, n_windows,
+                                             chunk, ddiff.p, dboth.p, ddv.p, nullptr);
   if (rc) return rc;
   if (diff) HIPCHK(c, hipMemcpyAsync(diff, ddiff.p, ddiff.bytes(), hipMemcpyDeviceToHost, c->stream));
   if (both) HIPCHK(c, hipMemcpyAsync(both, dboth.p, dboth.bytes(), hipMemcpyDeviceToHost, c->stream));

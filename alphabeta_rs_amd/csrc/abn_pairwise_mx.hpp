@@ -206,12 +206,30 @@ struct PmxScan {
     }
   }
 
+  // What inner_steps does to a loaded batch before its matrix steps: nothing, unless the kernel passes a `fix`
+  // (abn_pairwise_windows_packed.hpp masks the window's edge steps there): fix(k, x) may change the fragments x[NF] of
+  // step k in registers.  It runs when the batch is COMPUTED, not when it is loaded — the loads stay in flight.
+  struct NoFix {};
+  template <class Fix>
+  __device__ __forceinline__ void fix_steps(long long k, pmx_u32x4 (&x)[DSTEPS][NF], int cnt, Fix& fix) {
+    if constexpr (!std::is_same<Fix, NoFix>::value) {
+#pragma unroll
+      for (int d = 0; d < DSTEPS; ++d)
+        if (d < cnt) fix(k + d, x[d]);
+    }
+  }
+
   // The K steps [Ks, Ke) of the job — every one of them inside every row with four bytes to spare (the unaligned loader
   // reads one dword past the fragment and the last row ends the buffer).  The four wavefronts take batches of DSTEPS steps
   // round-robin (together they read 256 DSTEPS contiguous bytes of every row: interleaved batches measured 8 % faster at
   // 32 M sites than a contiguous range per wavefront) and share what is left of the last round evenly, so that no
   // wavefront does more than one step more than another.  Clears `red`, the workgroup's sums, on the way.
   __device__ __forceinline__ void inner_steps(long long Ks, long long Ke, unsigned long long* red) {
+    NoFix none;
+    inner_steps(Ks, Ke, red, none);
+  }
+  template <class Fix>
+  __device__ __forceinline__ void inner_steps(long long Ks, long long Ke, unsigned long long* red, Fix& fix) {
     const long long nfull = (Ke - Ks) / (kPmxWaves * DSTEPS);
     const long long R0 = Ks + nfull * (kPmxWaves * DSTEPS);
     const int rem = (int)(Ke - R0);
@@ -231,12 +249,15 @@ struct PmxScan {
     __syncthreads();
     while (rr < nfull) {
       if (rr + 1 < nfull) load_steps(kfull(rr + 1), xb, kFull, DSTEPS);
+      fix_steps(kfull(rr), xa, DSTEPS, fix);
       compute(xa, kFull, DSTEPS);
       if (++rr >= nfull) break;
       if (rr + 1 < nfull) load_steps(kfull(rr + 1), xa, kFull, DSTEPS);
+      fix_steps(kfull(rr), xb, DSTEPS, fix);
       compute(xb, kFull, DSTEPS);
       ++rr;
     }
+    fix_steps(R0 + rem_lo, xt, ct, fix);
     compute(xt, kPart, ct);
   }
 

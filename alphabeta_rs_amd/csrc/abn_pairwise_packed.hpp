@@ -20,10 +20,8 @@
 //
 // Rows start at multiples of 64 bytes (256 sites) from a 16-byte aligned base and every field from site L to the end
 // of the row is 3 (filtered): no ragged-edge loader, no unaligned loader, no AL4 variants.  The kernel reads the first
-// ceil(L / 256) super-steps of every row and nothing behind them.
-//
-// Out of scope here: the windows entry points on packed codes (a window that begins at an arbitrary site is not
-// field-aligned), and with them packed input for Pedigree::build_many.
+// ceil(L / 256) super-steps of every row and nothing behind them.  (Many column ranges of one packed matrix in one
+// call: abn_pairwise_windows_packed.hpp.)
 #pragma once
 #include "abn_pairwise_mx.hpp"
 

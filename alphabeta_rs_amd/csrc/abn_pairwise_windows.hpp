@@ -55,6 +55,32 @@ __device__ __forceinline__ long long pmx_win_pair(long long w, long long n, long
   return w * (n * (n - 1) / 2) + i * n - i * (i + 1) / 2 + (j - i - 1);
 }
 
+// The workgroup's folded sums -> the job's partial row (slot >= 0) or, for a window's only job, the window's results.
+// Scan: the PmxScan of the kernel (which tiles exist); red: the folded sums, behind a barrier.
+template <class Scan>
+__device__ __forceinline__ void pmx_win_store(const PairWinArgs& a, const PairWinJob& job, int R, int C,
+                                              const unsigned long long* red, int tid) {
+  if (job.slot >= 0) {
+    unsigned long long* row = a.partial + (size_t)job.slot * kPmxJobElems;
+    for (int k = tid; k < kPmxJobElems; k += kPmxThreads)
+      if (Scan::tile_used(k)) row[k] = red[k];
+  } else {
+    // the window's results: 16 consecutive threads write 16 consecutive pairs (one row of a tile)
+    for (int k = tid; k < kPmxJobElems; k += kPmxThreads) {
+      if (!Scan::tile_used(k)) continue;
+      const int bi = k >> 10, bj = (k >> 8) & 3;
+      const long long i = 64ll * R + 16 * bi + ((k >> 4) & 15), j = 64ll * C + 16 * bj + (k & 15);
+      if (i < j && j < a.n) {
+        const unsigned long long v = red[k], d = v & 0xffffffffull, cc = v >> 32;
+        const long long p = pmx_win_pair(job.window, a.n, i, j);
+        if (a.diff) a.diff[p] = d;
+        if (a.both) a.both[p] = cc;
+        if (a.dvalue) a.dvalue[p] = (double)d / (2.0 * (double)cc);
+      }
+    }
+  }
+}
+
 template <int NB, bool DIAG, bool AL4>
 __global__ __launch_bounds__(kPmxThreads, DIAG ? 2 : 1) void abn_pairwise_win_kernel(const PairWinArgs a) {
   using Scan = PmxScan<NB, DIAG, AL4>;
@@ -103,25 +129,7 @@ __global__ __launch_bounds__(kPmxThreads, DIAG ? 2 : 1) void abn_pairwise_win_ke
   __syncthreads();
   sc.fold(red);
   __syncthreads();
-  if (job.slot >= 0) {
-    unsigned long long* row = a.partial + (size_t)job.slot * kPmxJobElems;
-    for (int k = sc.tid; k < kPmxJobElems; k += kPmxThreads)
-      if (Scan::tile_used(k)) row[k] = red[k];
-  } else {
-    // the window's results: 16 consecutive threads write 16 consecutive pairs (one row of a tile)
-    for (int k = sc.tid; k < kPmxJobElems; k += kPmxThreads) {
-      if (!Scan::tile_used(k)) continue;
-      const int bi = k >> 10, bj = (k >> 8) & 3;
-      const long long i = 64ll * R + 16 * bi + ((k >> 4) & 15), j = 64ll * C + 16 * bj + (k & 15);
-      if (i < j && j < a.n) {
-        const unsigned long long v = red[k], d = v & 0xffffffffull, cc = v >> 32;
-        const long long p = pmx_win_pair(job.window, a.n, i, j);
-        if (a.diff) a.diff[p] = d;
-        if (a.both) a.both[p] = cc;
-        if (a.dvalue) a.dvalue[p] = (double)d / (2.0 * (double)cc);
-      }
-    }
-  }
+  pmx_win_store<Scan>(a, job, R, C, red, sc.tid);
 }
 
 // The partial rows of the chunked windows -> their results: pmx_reduce_row per (task, tile, tile row), as

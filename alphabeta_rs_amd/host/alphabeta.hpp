@@ -303,10 +303,13 @@ class Pedigree {  // src/pedigree.rs:44-45
   static std::pair<Pedigree, double> build(const std::string& nodelist, const std::string& edgelist,
                                            double posterior_max_filter, bool gpu_pairwise = false);
   // ... for many (nodelist, edgelist) pairs at once (the windows of src/cli/metaprofile.rs:50-72): with gpu_pairwise ONE
-  // abn_pairwise_divergence_windows call per group of entries with the same number of samples, cut only at
-  // kBuildManyCodeBytes of codes per call.  Per entry the pedigree and p0uu, or the text of what build would have thrown.
+  // abn_pairwise_divergence_windows_packed call per batch of entries with the same number of samples, on 2-bit codes
+  // packed straight from the site records.  A batch ends at kBuildManyCodeBytes of PACKED codes per call (four sites per
+  // byte), or when the site records waiting for their scan pass kBuildManySiteBytes.  Per entry the pedigree and p0uu, or
+  // the text of what build would have thrown.
   struct Built;
   static constexpr size_t kBuildManyCodeBytes = (size_t)1 << 30;
+  static constexpr size_t kBuildManySiteBytes = (size_t)1 << 30;
   static std::vector<Built> build_many(const std::vector<std::pair<std::string, std::string>>& lists,
                                        double posterior_max_filter, bool gpu_pairwise = false);
 };

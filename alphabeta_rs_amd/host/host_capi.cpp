@@ -33,6 +33,70 @@ int abh_pedigree_build_gpu(const char* nodelist, const char* edgelist, double po
 }
 // scans Pedigree::build has sent through abn_pairwise_divergence_packed since the library was loaded
 long long abh_packed_scan_calls() { return alphabeta::detail::packed_scan_calls().load(); }
+// ... and calls Pedigree::build_many has sent through abn_pairwise_divergence_windows_packed
+long long abh_packed_windows_scan_calls() { return alphabeta::detail::packed_windows_scan_calls().load(); }
+// The layout of Pedigree::build_many's scan calls without a device: the n entries are read, those that the scan takes
+// (samples of equal length, at least two) and that have the first such entry's sample count are cut into calls of at
+// most cap_bytes of packed codes (PackedBatch) and every call is laid out (layout_packed_call).  Per entry: call_of (-1:
+// not in the scan), n_samples, n_sites, begin / end (sites, in its call's rows), codes_off (where its write_codes bytes
+// [samples x sites] start in codes_out).  Per call: stride, packed_off (where its matrix [samples x stride] starts in
+// packed_out).  An entry that cannot be read: n_samples -1.
+// Returns the number of calls; -1: the call itself threw; -2: a buffer is too small.
+int abh_build_many_layout(const char* const* nodelists, const char* const* edgelists, int n, double posterior_max_filter,
+                          long long cap_bytes, int* call_of, int* n_samples, long long* n_sites, long long* begin,
+                          long long* end, long long* codes_off, unsigned char* codes_out, long long codes_cap,
+                          long long* stride, long long* packed_off, unsigned char* packed_out, long long packed_cap) {
+  using namespace alphabeta::detail;
+  try {
+    std::vector<Inputs> in((size_t)n);
+    std::vector<PackedBatch> calls;
+    size_t nn = 0, codes_used = 0;
+    for (int i = 0; i < n; ++i) {
+      call_of[i] = -1;
+      n_samples[i] = -1;
+      n_sites[i] = begin[i] = end[i] = codes_off[i] = 0;
+      try {
+        in[(size_t)i] = read_inputs(nodelists[i], edgelists[i], posterior_max_filter);
+      } catch (const std::exception&) {
+        continue;  // (build_many keeps the text; here the entry is simply not in the scan)
+      }
+      const Inputs& e = in[(size_t)i];
+      n_samples[i] = (int)e.nodes.size();
+      n_sites[i] = e.nodes.empty() ? 0 : (long long)e.nodes[0].sites.size();
+      if (!e.same_len() || e.nodes.size() < 2 || (nn && e.nodes.size() != nn)) continue;
+      nn = e.nodes.size();
+      const size_t L = e.nodes[0].sites.size();
+      if (calls.empty() || !calls.back().takes(L, (size_t)cap_bytes)) {
+        calls.emplace_back();
+        calls.back().nn = nn;
+      }
+      calls.back().add((size_t)i, L);
+      call_of[i] = (int)calls.size() - 1;
+      codes_off[i] = (long long)codes_used;
+      if (codes_used + nn * L > (size_t)codes_cap) return -2;
+      write_codes(e, posterior_max_filter, codes_out + codes_used, L);
+      codes_used += nn * L;
+    }
+    size_t packed_used = 0;
+    for (size_t k = 0; k < calls.size(); ++k) {
+      std::vector<const Inputs*> entries;
+      for (size_t w : calls[k].members) entries.push_back(&in[w]);
+      const PackedCall c = layout_packed_call(calls[k], entries, posterior_max_filter);
+      if (packed_used + c.packed.size() > (size_t)packed_cap) return -2;
+      std::memcpy(packed_out + packed_used, c.packed.data(), c.packed.size());
+      stride[k] = (long long)c.stride;
+      packed_off[k] = (long long)packed_used;
+      packed_used += c.packed.size();
+      for (size_t m = 0; m < calls[k].members.size(); ++m) {
+        begin[calls[k].members[m]] = c.begin[m];
+        end[calls[k].members[m]] = c.end[m];
+      }
+    }
+    return (int)calls.size();
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
 // Pedigree::build_many over n (nodelist, edgelist) pairs: per entry the number of rows (-1: failed, its text in
 // errs + i * errcap; -2: more than cap rows), rows (n x cap x 4) and p0uu (n); returns 0, or -1 when the call itself threw
 int abh_pedigree_build_many(const char* const* nodelists, const char* const* edgelists, int n, double posterior_max_filter,

@@ -2,7 +2,7 @@
 // (src/cli/metaprofile.rs:33-114; SURVEY.md §8f row 2, "next"): the SERIAL window loop that calls
 // alphabeta::run once per (region, window) directory becomes ONE batched, device-resident plan
 // (abn_plan_*: W windows x (S starts + B bootstraps) in three kernel launches) behind ONE batched pedigree
-// construction (Pedigree::build_many -> abn_pairwise_divergence_windows).  The window extraction
+// construction (Pedigree::build_many -> abn_pairwise_divergence_windows_packed).  The window extraction
 // that fills those directories (src/extract.rs, src/windows.rs, src/setup.rs) is out of scope; this driver
 // starts from the directory tree setup.rs writes: <output_dir>/<region>/<window>/{nodelist,edgelist}.txt.
 //

@@ -206,11 +206,19 @@ inline void write_codes(const Inputs& in, double posterior_max_filter, uint8_t* 
 // the same as 2-bit fields, straight from the site records (no byte matrix in between): 0 / 1 / 2 = the status, 3 = the
 // posterior is below the filter; site 16 g + 4 j + e in byte 4 g + e of the row at bits 2j..2j+1, every field from the
 // last site to the end of the row 3 (include/abneutral.h, abn_pairwise_divergence_packed).  dst: nodes x row_stride bytes
+inline void write_codes_packed_at(const Inputs& in, double posterior_max_filter, uint8_t* dst, size_t row_stride,
+                                  size_t byte_offset);
 inline void write_codes_packed(const Inputs& in, double posterior_max_filter, uint8_t* dst, size_t row_stride) {
   std::memset(dst, 0xff, in.nodes.size() * row_stride);
+  write_codes_packed_at(in, posterior_max_filter, dst, row_stride, 0);
+}
+// ... into the columns that begin byte_offset bytes (a multiple of 4: whole dwords of 16 sites) into every row of a
+// matrix whose fields are all 3 already: an entry's column range of the matrix of one Pedigree::build_many call
+inline void write_codes_packed_at(const Inputs& in, double posterior_max_filter, uint8_t* dst, size_t row_stride,
+                                  size_t byte_offset) {
   for (size_t i = 0; i < in.nodes.size(); ++i) {
     const auto& sites = in.nodes[i].sites;
-    uint8_t* row = dst + i * row_stride;
+    uint8_t* row = dst + i * row_stride + byte_offset;
     for (size_t k = 0; k < sites.size(); ++k) {
       const unsigned f = sites[k].posteriormax < posterior_max_filter ? 3u : (sites[k].status_numeric & 3u);
       row[(k >> 4) * 4 + (k & 3)] ^= (uint8_t)((3u ^ f) << (2 * ((k >> 2) & 3)));  // the field was 3
@@ -221,6 +229,56 @@ inline void write_codes_packed(const Inputs& in, double posterior_max_filter, ui
 inline std::atomic<long long>& packed_scan_calls() {
   static std::atomic<long long> calls{0};
   return calls;
+}
+
+// ... and calls Pedigree::build_many has sent through abn_pairwise_divergence_windows_packed
+inline std::atomic<long long>& packed_windows_scan_calls() {
+  static std::atomic<long long> calls{0};
+  return calls;
+}
+
+// The entries of ONE scan call of Pedigree::build_many: entries with the same number of samples, in their order, side
+// by side in one packed matrix (a row per sample).  Every entry's columns start at a multiple of 256 sites (64 bytes:
+// whole super-steps of the scan, whole cache-line halves) and take ceil(sites / 256) * 64 bytes of every row.
+struct PackedBatch {
+  size_t nn = 0;                // samples
+  std::vector<size_t> members;  // the caller's entry indices
+  std::vector<size_t> sites;    // of each member
+  size_t stride = 0;            // bytes per row so far
+  static size_t columns_bytes(size_t L) { return (L + 255) / 256 * 64; }
+  // an entry of L sites still fits a call of at most cap_bytes of packed codes (an empty batch takes any entry)
+  bool takes(size_t L, size_t cap_bytes) const {
+    return members.empty() || nn * (stride + columns_bytes(L)) <= cap_bytes;
+  }
+  void add(size_t w, size_t L) {
+    members.push_back(w);
+    sites.push_back(L);
+    stride += columns_bytes(L);
+  }
+};
+// The batch's packed matrix and window table — what abn_pairwise_divergence_windows_packed takes — straight from the
+// entries' site records: no byte matrix, no device.  entries[m] = the Inputs of member m.  Gaps between the entries and
+// the rows' padding are field 3 (filtered); a batch without a site still gets one super-step per row (the scan refuses
+// a null matrix).
+struct PackedCall {
+  std::vector<uint8_t> packed;  // [nn x stride]
+  size_t stride = 0, n_sites = 0;
+  std::vector<int64_t> begin, end;  // in sites, per member
+};
+inline PackedCall layout_packed_call(const PackedBatch& b, const std::vector<const Inputs*>& entries,
+                                     double posterior_max_filter) {
+  PackedCall c;
+  c.stride = std::max<size_t>(b.stride, 64);
+  c.n_sites = 4 * c.stride;
+  c.packed.assign(b.nn * c.stride, (uint8_t)0xff);
+  size_t off = 0;  // bytes into the row
+  for (size_t m = 0; m < b.members.size(); ++m) {
+    write_codes_packed_at(*entries[m], posterior_max_filter, c.packed.data(), c.stride, off);
+    c.begin.push_back((int64_t)(4 * off));
+    c.end.push_back((int64_t)(4 * off + b.sites[m]));
+    off += PackedBatch::columns_bytes(b.sites[m]);
+  }
+  return c;
 }
 
 // DMatrix::from, :210-261 — entry [i][j - i - 1] of an nn x nn array
@@ -339,12 +397,15 @@ inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, 
   return {convert(in, dm), in.p0uu};
 }
 
-// Pedigree::build for many (nodelist, edgelist) pairs — the windows of src/cli/metaprofile.rs:50-72.  Every entry is
-// read first; with gpu_pairwise the entries whose samples all have the same number of sites are grouped by sample
-// count, each group's codes laid side by side in one matrix (a row per sample, an entry's sites a column range) and
-// scanned by ONE abn_pairwise_divergence_windows call; the rest (and everything without gpu_pairwise) takes the host
-// loop as build does.  An entry that fails keeps its error text and never stops the others.  Host memory: the code bytes
-// twice at most (per entry, then the call's matrix: kBuildManyCodeBytes bounds the second) plus the graphs.
+// Pedigree::build for many (nodelist, edgelist) pairs — the windows of src/cli/metaprofile.rs:50-72.  With gpu_pairwise
+// the entries whose samples all have the same number of sites are batched by sample count: each batch's entries are
+// packed straight from their site records into one 2-bit matrix (layout_packed_call: a row per sample, an entry's sites
+// a column range) and scanned by ONE abn_pairwise_divergence_windows_packed call; the rest (and everything without
+// gpu_pairwise) takes the host loop as build does.  An entry that fails keeps its error text and never stops the others.
+// A batch is scanned when the next entry would take its matrix beyond kBuildManyCodeBytes of packed codes, all open
+// batches when the site records they wait with (24 bytes per site and sample, against a quarter of a byte packed) pass
+// kBuildManySiteBytes, and what is left at the end; entries are never reordered.  Host memory: those site records, one
+// call's packed matrix, and the graphs.
 inline std::vector<Pedigree::Built> Pedigree::build_many(const std::vector<std::pair<std::string, std::string>>& lists,
                                                          double posterior_max_filter, bool gpu_pairwise) {
   using namespace detail;
@@ -357,70 +418,70 @@ inline std::vector<Pedigree::Built> Pedigree::build_many(const std::vector<std::
     out[w].error = e.what();
     alive[w] = 0;
   };
-  std::map<size_t, std::vector<size_t>> by_samples;  // sample count -> entries for the scan, in order
-  // What stays of an entry until the end is its graph (names, ids, generations, edges) and either its D matrix or, for the
-  // scan, its code bytes (one per site and sample; the 24-byte site records are dropped as soon as those are written).
-  std::vector<std::vector<uint8_t>> codes_of(W);  // [sample][site], entries of the scan only
-  std::vector<size_t> sites_of(W, 0);
+  // What stays of an entry until the end is its graph (names, ids, generations, edges) and its D matrix; the site records
+  // are dropped as soon as the D matrix (host loop) or the entry's columns of a call's matrix (scan) are written.
   auto drop_sites = [&](size_t w) {
     for (auto& node : in[w].nodes) std::vector<Site>().swap(node.sites);
   };
+  std::map<size_t, PackedBatch> open;  // sample count -> the entries waiting for their scan, in order
+  size_t waiting_site_bytes = 0;
+  auto scan = [&](PackedBatch& b) {
+    if (b.members.empty()) return;
+    const size_t nn = b.nn, npairs = nn * (nn - 1) / 2, M = b.members.size();
+    try {
+      std::vector<const Inputs*> entries;
+      for (size_t w : b.members) entries.push_back(&in[w]);
+      const PackedCall c = layout_packed_call(b, entries, posterior_max_filter);
+      for (size_t w : b.members) drop_sites(w);
+      std::vector<double> dv(M * npairs);
+      Device& dev = default_device();
+      dev.check(abn_pairwise_divergence_windows_packed(dev.get(), c.packed.data(), (int32_t)nn, (int64_t)c.n_sites,
+                                                       (int64_t)c.stride, c.begin.data(), c.end.data(), (int32_t)M,
+                                                       nullptr, nullptr, dv.data()),
+                "Pedigree::build (pairwise divergence)");
+      packed_windows_scan_calls().fetch_add(1, std::memory_order_relaxed);
+      for (size_t m = 0; m < M; ++m) dm[b.members[m]] = dmatrix_of_pairs(nn, dv.data() + m * npairs);
+    } catch (const std::exception& e) {
+      for (size_t w : b.members) {
+        drop_sites(w);
+        fail(w, e);
+      }
+    }
+    for (size_t L : b.sites) waiting_site_bytes -= nn * L * sizeof(Site);
+    const size_t nn_keep = b.nn;
+    b = PackedBatch{};
+    b.nn = nn_keep;
+  };
   for (size_t w = 0; w < W; ++w) {
     diag_sink() = &out[w].diagnostics;
+    bool waits = false;
     try {
       in[w] = read_inputs(lists[w].first, lists[w].second, posterior_max_filter);
       alive[w] = 1;
       const size_t nn = in[w].nodes.size();
       if (gpu_pairwise && in[w].same_len() && nn >= 2) {
-        sites_of[w] = in[w].nodes[0].sites.size();
-        codes_of[w].resize(nn * sites_of[w]);
-        write_codes(in[w], posterior_max_filter, codes_of[w].data(), sites_of[w]);
-        by_samples[nn].push_back(w);
+        waits = true;
       } else {
         dm[w] = dmatrix_on_host(in[w], posterior_max_filter);
       }
     } catch (const std::exception& e) {
       fail(w, e);
     }
-    drop_sites(w);
     diag_sink() = nullptr;
-  }
-  for (const auto& [nn, members] : by_samples) {
-    // one call per group; a group is cut only to keep a call's code bytes under kBuildManyCodeBytes.  Every entry's
-    // columns start at a multiple of 128 bytes (whole cache lines, the scan's aligned loader); the gaps read as filtered.
-    const size_t npairs = nn * (nn - 1) / 2;
-    for (size_t m0 = 0; m0 < members.size();) {
-      std::vector<int64_t> begin, end;
-      size_t stride = 0, m1 = m0;
-      while (m1 < members.size()) {
-        const size_t L = sites_of[members[m1]], padded = (L + 127) / 128 * 128;
-        if (m1 > m0 && nn * (stride + padded) > kBuildManyCodeBytes) break;
-        begin.push_back((int64_t)stride);
-        end.push_back((int64_t)(stride + L));
-        stride += padded;
-        ++m1;
-      }
-      try {
-        std::vector<uint8_t> codes(nn * stride, (uint8_t)0x80);
-        for (size_t m = m0; m < m1; ++m) {
-          std::vector<uint8_t>& own = codes_of[members[m]];
-          const size_t L = sites_of[members[m]];
-          for (size_t i = 0; i < nn; ++i)
-            if (L) std::memcpy(codes.data() + i * stride + (size_t)begin[m - m0], own.data() + i * L, L);
-          std::vector<uint8_t>().swap(own);
-        }
-        std::vector<double> dv((m1 - m0) * npairs);
-        Device& dev = default_device();
-        dev.check(abn_pairwise_divergence_windows(dev.get(), codes.data(), (int32_t)nn, (int64_t)stride, begin.data(),
-                                                  end.data(), (int32_t)(m1 - m0), nullptr, nullptr, dv.data()),
-                  "Pedigree::build (pairwise divergence)");
-        for (size_t m = m0; m < m1; ++m) dm[members[m]] = dmatrix_of_pairs(nn, dv.data() + (m - m0) * npairs);
-      } catch (const std::exception& e) {
-        for (size_t m = m0; m < m1; ++m) fail(members[m], e);
-      }
-      m0 = m1;
+    if (!waits) {
+      drop_sites(w);
+      continue;
     }
+    const size_t nn = in[w].nodes.size(), L = in[w].nodes[0].sites.size();
+    PackedBatch& b = open[nn];
+    b.nn = nn;
+    if (!b.takes(L, kBuildManyCodeBytes)) scan(b);
+    b.add(w, L);
+    waiting_site_bytes += nn * L * sizeof(Site);
+    if (waiting_site_bytes > kBuildManySiteBytes)
+      for (auto& kv : open) scan(kv.second);
   }
+  for (auto& kv : open) scan(kv.second);
   for (size_t w = 0; w < W; ++w) {
     if (!alive[w]) continue;
     try {

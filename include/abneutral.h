@@ -232,8 +232,9 @@ int abn_pairwise_divergence_windows_dev(abn_ctx* ctx, const void* dev_codes, int
  *   sample i's row starts at packed + i * row_stride_bytes; row_stride_bytes is a multiple of 64 (256 sites), at least
  *   abn_packed_row_stride(n_sites); EVERY field from site n_sites to the end of the row must be 3 (the scan does not
  *   check it; abn_pack_codes writes it); a device-resident buffer is 16-byte aligned (a host buffer: any alignment).
- * Not offered on packed codes: the windows entry points (a window that begins at an arbitrary site is not
- * field-aligned) — abn_pairwise_divergence_windows* and Pedigree::build_many stay on bytes.
+ * Both forms of the scan take packed codes: one whole matrix (abn_pairwise_divergence_packed*) and many column ranges
+ * of one matrix in one call (abn_pairwise_divergence_windows_packed*, below).  A window may begin and end at any site:
+ * the scan reads whole 64-byte steps of the rows and treats the fields outside the window as filtered.
  *
  * Host arithmetic, no device: bytes per row for n_sites sites — ceil(n_sites / 256) * 64; 0 for n_sites <= 0. */
 int64_t abn_packed_row_stride(int64_t n_sites);
@@ -260,6 +261,28 @@ int abn_pairwise_divergence_packed(abn_ctx* ctx, const uint8_t* packed, int32_t 
 int abn_pairwise_divergence_packed_dev(abn_ctx* ctx, const void* dev_packed, int32_t n_samples, int64_t n_sites,
                                        int64_t row_stride_bytes, void* dev_diff, void* dev_both, void* dev_dvalue,
                                        double* kernel_ms);
+
+/* abn_pairwise_divergence_windows (the window loop of src/cli/metaprofile.rs:50-72 around DMatrix::from,
+ * src/pedigree.rs:210-261) on packed codes: packed[n_samples x row_stride_bytes] holds n_sites sites per row in the
+ * format above; window w = the sites [site_begin[w], site_end[w]) of every row, HOST arrays of n_windows entries, in
+ * sites.  Windows may overlap, leave gaps, be empty and begin or end at any site.  Outputs are [n_windows x pairs] in the
+ * order, with the NULL rules and with the bits of abn_pairwise_divergence_windows on the unpacked codes (an empty or
+ * wholly filtered window: diff = both = 0, dvalue = NaN).
+ * ABN_ERR_INVALID_ARG: what abn_pairwise_divergence_packed refuses (null packed, n_samples <= 0 or > 65535, n_sites < 0,
+ * a row_stride_bytes that is not a multiple of 64 or is below abn_packed_row_stride(n_sites)); n_windows < 0; null window
+ * arrays with n_windows > 0; a window with begin < 0, begin > end or end > n_sites; a window so long that
+ * a chunk of it (a job of the scan) would reach 2^30 sites.  n_windows == 0 or n_samples < 2: ABN_OK, nothing is written. */
+int abn_pairwise_divergence_windows_packed(abn_ctx* ctx, const uint8_t* packed, int32_t n_samples, int64_t n_sites,
+                                           int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                                           int32_t n_windows, uint64_t* diff, uint64_t* both, double* dvalue);
+/* ... and on DEVICE-resident packed codes and outputs (src/cli/metaprofile.rs:50-72, src/pedigree.rs:210-261):
+ * dev_packed u8[n_samples x row_stride_bytes], 16-byte aligned (else ABN_ERR_INVALID_ARG); dev_diff / dev_both
+ * u64[n_windows x pairs], dev_dvalue f64[n_windows x pairs], any may be NULL; site_begin / site_end stay HOST arrays;
+ * kernel_ms as above.  Returns after the work has completed. */
+int abn_pairwise_divergence_windows_packed_dev(abn_ctx* ctx, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                               int64_t row_stride_bytes, const int64_t* site_begin,
+                                               const int64_t* site_end, int32_t n_windows, void* dev_diff,
+                                               void* dev_both, void* dev_dvalue, double* kernel_ms);
 
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
