@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "abn_packed_row_stride", "abn_pack_codes", "abn_unpack_codes", "abn_pairwise_divergence_packed",
     "abn_pairwise_divergence_packed_dev",
     "abn_pairwise_divergence_windows_packed", "abn_pairwise_divergence_windows_packed_dev",
+    "abn_analyze_batch", "abn_analyze_batch_dev", "abn_plan_analyze", "abn_multi_analyze",
 ]
 
 
@@ -121,6 +122,10 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_boot_model_run.argtypes = [vp, op, dp, C.c_int32, dp, dp, dp, C.c_double, C.c_double, C.c_double,
                                      C.c_int32, dp, vp]
     L.abn_analyze.argtypes = [dp, C.c_int64, dp]
+    L.abn_analyze_batch.argtypes = [vp, dp, C.c_int32, C.c_int64, dp, C.POINTER(C.c_int32)]
+    L.abn_analyze_batch_dev.argtypes = [vp, vp, C.c_int32, C.c_int64, vp, vp, dp]
+    L.abn_plan_analyze.argtypes = [vp, dp, C.POINTER(C.c_int32)]
+    L.abn_multi_analyze.argtypes = [vp, dp, C.POINTER(C.c_int32)]
     L.abn_select_best.argtypes = [vp, dp, C.c_int32, C.c_double, dp, C.c_int32, C.POINTER(C.c_int32), dp, dp, dp, dp]
     L.abn_bootstrap_rows.argtypes = [vp, dp, C.c_int64, dp]
     L.abn_pairwise_divergence.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int32, C.c_int64, C.POINTER(C.c_uint64),
@@ -272,6 +277,22 @@ def analyze(raw) -> np.ndarray:
     if rc:
         raise AbnError(rc)
     return out.reshape(4, 8)
+
+
+def analyze_batch(ctx: "Context", raw, allow_failed_windows=False):
+    """analyze() of every window of raw (n_windows, n_boot, 7) in one launch on the device (src/analysis.rs:50-98), with
+    the host analysis's bits.  Returns (out (n_windows, 32): mean[8], sd[8], ci_lo[8], ci_hi[8] per window; first_bad
+    (n_windows,) int32: the first bootstrap with a NaN row or a NaN beta / alpha, -1 for none).  A window with
+    first_bad >= 0 is 32 NaN and raises AbnError(ABN_ERR_NO_FINITE_FIT) unless allow_failed_windows."""
+    raw = _f64(raw)
+    if raw.ndim != 3 or raw.shape[2] != 7:
+        raise ValueError("raw is (n_windows, n_boot, 7)")
+    W, B = raw.shape[0], raw.shape[1]
+    out, fb = np.empty((W, 32)), np.full(W, -1, dtype=np.int32)
+    rc = ctx._L.abn_analyze_batch(ctx._h, _dp(raw), W, B, _dp(out), fb.ctypes.data_as(C.POINTER(C.c_int32)))
+    if not (rc == 5 and allow_failed_windows):  # ABN_ERR_NO_FINITE_FIT: every buffer is filled all the same
+        ctx._check(rc)
+    return out, fb
 
 
 class Context:
@@ -514,6 +535,17 @@ class Context:
             C.c_void_p(dvalue_ptr or None), C.byref(ms)))
         return ms.value
 
+    def analyze_batch_dev(self, raw_ptr: int, n_windows: int, n_boot: int, out_ptr: int, first_bad_ptr: int = 0,
+                          allow_failed_windows=False) -> float:
+        """analyze_batch on device-resident buffers (raw device pointers): f64 raw [n_windows x n_boot x 7] in, f64 out
+        [n_windows x 32] and i32 first_bad [n_windows] (0 = not wanted) out.  Returns the kernel's HIP-event ms."""
+        ms = C.c_double(0.0)
+        rc = self._L.abn_analyze_batch_dev(self._h, C.c_void_p(raw_ptr), n_windows, n_boot, C.c_void_p(out_ptr),
+                                           C.c_void_p(first_bad_ptr or None), C.byref(ms))
+        if not (rc == 5 and allow_failed_windows):
+            self._check(rc)
+        return ms.value
+
     # ---- (3) boot_model::run
     def boot_model_run(self, pedigree, model, pred, resid, p0uu, eqp, eqp_weight, n_boot, *,
                        options: Options | None = None):
@@ -615,6 +647,15 @@ class Plan:
             self.ctx._check(rc)
         return {"models": models, "pred": pred, "resid": resid, "raw": raw, "info_a": ia, "info_b": ib,
                 "best_start": bs}
+
+    def analyze(self, allow_failed_windows=False):
+        """The analysis of every window on the device, from the table the plan currently writes (bind_raw included):
+        (out (W, 32), first_bad (W,)) as analyze_batch — W x 32 doubles come back instead of raw (W, B, 7)."""
+        out, fb = np.empty((self.W, 32)), np.full(self.W, -1, dtype=np.int32)
+        rc = self._L.abn_plan_analyze(self._h, _dp(out), fb.ctypes.data_as(C.POINTER(C.c_int32)))
+        if not (rc == 5 and allow_failed_windows):
+            self.ctx._check(rc)
+        return out, fb
 
     def counters(self):
         out = (C.c_int64 * 5)()
@@ -736,6 +777,14 @@ class MultiPlan:
             self._check(rc)
         return {"models": models, "pred": pred, "resid": resid, "raw": raw, "info_a": ia, "info_b": ib,
                 "best_start": bs}
+
+    def analyze(self, allow_failed_windows=False):
+        """Plan.analyze for all W windows, on the first device's gathered table: (out (W, 32), first_bad (W,))"""
+        out, fb = np.empty((self.W, 32)), np.full(self.W, -1, dtype=np.int32)
+        rc = self._L.abn_multi_analyze(self._h, _dp(out), fb.ctypes.data_as(C.POINTER(C.c_int32)))
+        if not (rc == 5 and allow_failed_windows):
+            self._check(rc)
+        return out, fb
 
     def counters(self):
         out = (C.c_int64 * 5)()

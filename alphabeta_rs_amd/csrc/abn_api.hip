@@ -1119,6 +1119,16 @@ extern "C" int abn_plan_download(abn_plan* p, double* models, double* pred, doub
   return ABN_OK;
 }
 
+// src/analysis.rs:50-98 for every window of the table the plan currently writes (its own or the bound one), on the device
+extern "C" int abn_plan_analyze(abn_plan* p, double* out, int32_t* first_bad) {
+  if (!p) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = p->ctx;
+  if (!out) return set_err(c, ABN_ERR_INVALID_ARG, "null out");
+  if (!p->ran_b || p->B <= 0) return set_err(c, ABN_ERR_STATE, "phase B has not run: there is no bootstrap table");
+  if (int rc = verify_persistent(p)) return rc;  // synchronises the stream
+  return analyze_device_table(c, p->raw, p->W, p->B, out, first_bad);
+}
+
 extern "C" int abn_plan_failed_windows(abn_plan* p, int32_t* n_failed) {
   if (!p || !n_failed) return ABN_ERR_INVALID_ARG;
   abn_ctx* c = p->ctx;

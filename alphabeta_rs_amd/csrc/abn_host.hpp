@@ -131,3 +131,10 @@ struct DevBuf {
   }
   size_t bytes() const { return n * sizeof(T); }
 };
+
+namespace abn {
+// abn_pairwise.hip, for abn_plan_analyze (abn_api.hip): the analysis (abn_analyze.hpp) of a device-resident table
+// raw[W x B x 7] on the context's stream, results to the host; returns after completion, ABN_ERR_NO_FINITE_FIT as
+// abn_analyze_batch.
+int analyze_device_table(abn_ctx* c, const double* draw, int32_t W, int64_t B, double* out, int32_t* first_bad);
+}  // namespace abn

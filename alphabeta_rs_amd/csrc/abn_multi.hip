@@ -409,6 +409,31 @@ extern "C" int abn_multi_download(abn_multi* m, double* models, double* pred, do
   return ABN_OK;
 }
 
+// src/analysis.rs:50-98 for all W windows, on the first device's copy of the gathered table
+extern "C" int abn_multi_analyze(abn_multi* m, double* out, int32_t* first_bad) {
+  if (!m) return ABN_ERR_INVALID_ARG;
+  if (!out) return fail(m, ABN_ERR_INVALID_ARG, "null out");
+  if (!m->ran) return fail(m, ABN_ERR_STATE, "abn_multi_run has not been called");
+  int rc = abn_multi_sync(m);
+  if (rc) return rc;
+  void* table = nullptr;
+  rc = abn_multi_raw_device_ptr(m, 0, &table);
+  if (rc) return plan_fail(m, 0, rc, "abn_multi_raw_device_ptr");
+  const size_t W = (size_t)m->W, out_bytes = W * 32 * sizeof(double), fb_bytes = W * sizeof(int32_t);
+  MHIP(m, hipSetDevice(m->dev[0]));
+  char* dev = nullptr;  // out[W x 32], then first_bad[W]
+  MHIP(m, hipMalloc((void**)&dev, out_bytes + fb_bytes));
+  rc = abn_analyze_batch_dev(m->ctx[0], table, m->W, m->B, dev, dev + out_bytes, nullptr);
+  hipError_t e = hipSuccess;
+  if (rc == ABN_OK || rc == ABN_ERR_NO_FINITE_FIT) {  // every buffer is filled either way
+    e = hipMemcpy(out, dev, out_bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && first_bad) e = hipMemcpy(first_bad, dev + out_bytes, fb_bytes, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dev);
+  MHIP(m, e);
+  return rc ? plan_fail(m, 0, rc, "abn_analyze_batch_dev") : ABN_OK;
+}
+
 extern "C" int abn_multi_counters(abn_multi* m, int64_t* out5) {
   if (!m || !out5) return ABN_ERR_INVALID_ARG;
   for (int k = 0; k < 5; ++k) out5[k] = 0;

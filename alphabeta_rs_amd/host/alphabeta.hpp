@@ -191,6 +191,18 @@ struct Analysis {  // src/analysis.rs:15-47
   double sd_alpha, sd_beta, sd_alphabeta, sd_weight, sd_intercept, sd_pr_mm, sd_pr_um, sd_pr_uu;
   CI ci_alpha, ci_beta, ci_alphabeta, ci_weight, ci_intercept, ci_pr_mm, ci_pr_um, ci_pr_uu;
 
+  // from the 32 doubles of abn_analyze / one window's row of abn_analyze_batch: mean[8], sd[8], ci_lo[8], ci_hi[8]
+  static Analysis from_out32(const double* o) {
+    Analysis a{};
+    a.alpha = o[0]; a.beta = o[1]; a.alphabeta = o[2]; a.weight = o[3]; a.intercept = o[4];
+    a.pr_mm = o[5]; a.pr_um = o[6]; a.pr_uu = o[7];
+    a.sd_alpha = o[8]; a.sd_beta = o[9]; a.sd_alphabeta = o[10]; a.sd_weight = o[11]; a.sd_intercept = o[12];
+    a.sd_pr_mm = o[13]; a.sd_pr_um = o[14]; a.sd_pr_uu = o[15];
+    CI* cis[8] = {&a.ci_alpha, &a.ci_beta, &a.ci_alphabeta, &a.ci_weight, &a.ci_intercept, &a.ci_pr_mm, &a.ci_pr_um,
+                  &a.ci_pr_uu};
+    for (int k = 0; k < 8; ++k) *cis[k] = CI{o[16 + k], o[24 + k]};
+    return a;
+  }
   std::string display() const {  // impl Display, src/analysis.rs:147-187
     std::ostringstream o;
     auto kv = [&](const char* k, double v) { o << k << "\t" << fmt_f64(v) << "\n"; };
@@ -226,15 +238,7 @@ struct RawAnalysis {  // src/analysis.rs:12 — n_boot x 7: alpha, beta, weight,
     double o[32];
     int rc = abn_analyze(rows.data(), (int64_t)n_boot, o);
     if (rc) throw Error(rc, "abn_analyze failed");
-    Analysis a{};
-    a.alpha = o[0]; a.beta = o[1]; a.alphabeta = o[2]; a.weight = o[3]; a.intercept = o[4];
-    a.pr_mm = o[5]; a.pr_um = o[6]; a.pr_uu = o[7];
-    a.sd_alpha = o[8]; a.sd_beta = o[9]; a.sd_alphabeta = o[10]; a.sd_weight = o[11]; a.sd_intercept = o[12];
-    a.sd_pr_mm = o[13]; a.sd_pr_um = o[14]; a.sd_pr_uu = o[15];
-    CI* cis[8] = {&a.ci_alpha, &a.ci_beta, &a.ci_alphabeta, &a.ci_weight, &a.ci_intercept, &a.ci_pr_mm, &a.ci_pr_um,
-                  &a.ci_pr_uu};
-    for (int k = 0; k < 8; ++k) *cis[k] = CI{o[16 + k], o[24 + k]};
-    return a;
+    return Analysis::from_out32(o);
   }
   // ndarray_npy::write_npy (src/cli/alphabeta.rs:34): NPY v1.0, C order, <f8, shape (n_boot, 7)
   void write_npy(const std::string& path) const {
@@ -251,6 +255,39 @@ struct RawAnalysis {  // src/analysis.rs:12 — n_boot x 7: alpha, beta, weight,
     f.write(reinterpret_cast<const char*>(rows.data()), (std::streamsize)(rows.size() * sizeof(double)));
   }
 };
+
+// RawAnalysis::analyze (src/analysis.rs:50-98) of every window of a finished run, on the device — abn_plan_analyze /
+// abn_multi_analyze: W x 32 doubles come back instead of the table.  first_bad[w] >= 0: the bootstrap of window w that
+// RawAnalysis::analyze would have refused; that window's Analysis is all NaN, the others are valid.
+struct WindowAnalyses {
+  std::vector<Analysis> windows;
+  std::vector<int32_t> first_bad;
+  // what RawAnalysis::analyze throws for window w's table
+  Error refusal(size_t w) const {
+    return Error(ABN_ERR_NO_FINITE_FIT, "bootstrap " + std::to_string(first_bad[w]) + " has no finite fit: no analysis of this table");
+  }
+};
+template <class Call>
+inline WindowAnalyses analyze_windows_with(size_t n_windows, Call call) {
+  WindowAnalyses r;
+  std::vector<double> out(n_windows * 32);
+  r.first_bad.assign(n_windows, -1);
+  call(out.data(), r.first_bad.data());
+  for (size_t w = 0; w < n_windows; ++w) r.windows.push_back(Analysis::from_out32(&out[w * 32]));
+  return r;
+}
+inline WindowAnalyses analyze_windows(const MultiDevice& md, size_t n_windows) {
+  return analyze_windows_with(n_windows, [&](double* out, int32_t* fb) {
+    const int rc = abn_multi_analyze(md.get(), out, fb);
+    if (rc != ABN_ERR_NO_FINITE_FIT) md.check(rc, "abn_multi_analyze");  // per window: first_bad
+  });
+}
+inline WindowAnalyses analyze_windows(const Device& dev, abn_plan* plan, size_t n_windows) {
+  return analyze_windows_with(n_windows, [&](double* out, int32_t* fb) {
+    const int rc = abn_plan_analyze(plan, out, fb);
+    if (rc != ABN_ERR_NO_FINITE_FIT) dev.check(rc, "abn_plan_analyze");
+  });
+}
 
 // ------------------------------------------------------------------------------------------------
 class Pedigree {  // src/pedigree.rs:44-45

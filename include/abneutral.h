@@ -180,10 +180,28 @@ int abn_boot_model_run(abn_ctx* ctx, const abn_options* opts, const double* pedi
 
 /* src/analysis.rs:50-98 on the host: out[32] = mean[8], sd[8], ci_lo[8], ci_hi[8] in the order
  * alpha, beta, beta/alpha, weight, intercept, pr_mm, pr_um, pr_uu (struct Analysis, :15-47).
- * Precondition: no NaN in raw nor in beta/alpha (rows of fits with status ABN_FIT_NONFINITE): the quantiles sort with `<`
- * (the reference converts to n64, which rejects NaN, :57-58).  The host mirrors (RawAnalysis::analyze, the Python
- * analyze()) check it and refuse such a table with ABN_ERR_NO_FINITE_FIT. */
+ * A table with a NaN in raw or in beta/alpha (rows of fits with status ABN_FIT_NONFINITE) is refused with
+ * ABN_ERR_NO_FINITE_FIT and out32 is not written: the quantiles sort with `<` (the reference converts to n64, which
+ * rejects NaN, :57-58).  +-inf is not refused.  The host mirrors (RawAnalysis::analyze, the Python analyze()) make the
+ * same test first, for a message that names the bootstrap. */
 int abn_analyze(const double* raw, int64_t n_boot, double* out32);
+
+/* ------------------------------------------------------------------ the analysis on the device, all windows at once
+ * src/analysis.rs:50-98 for every window of a bootstrap table in one launch: raw[n_windows x n_boot x 7] (window w's
+ * table as abn_analyze takes it) -> out[n_windows x 32], window w in abn_analyze's layout, every number bit-identical
+ * to abn_analyze on that window's table; first_bad[n_windows] (int32, may be NULL) = the smallest bootstrap index whose
+ * row holds a NaN or whose beta/alpha is NaN (the test of abn_analyze; +-inf is not refused), -1 if there is none.  A
+ * window with first_bad >= 0 gets 32 NaN; the other windows are unaffected.  n_boot = 1: sd is NaN, as on the host.
+ * ABN_ERR_INVALID_ARG: null raw or out, n_windows < 0, n_boot <= 0 or above 2^31 - 1.  n_windows == 0: ABN_OK, nothing
+ * is written.  ABN_ERR_NO_FINITE_FIT — AFTER filling every buffer — when any window has first_bad >= 0 (the
+ * convention of abn_plan_download).  raw, out and first_bad are HOST arrays here. */
+int abn_analyze_batch(abn_ctx* ctx, const double* raw, int32_t n_windows, int64_t n_boot, double* out,
+                      int32_t* first_bad);
+/* src/analysis.rs:50-98 as above on DEVICE-resident buffers (no table crosses PCIe): dev_raw f64[n_windows x n_boot x 7],
+ * dev_out f64[n_windows x 32], dev_first_bad i32[n_windows] (may be NULL).  kernel_ms (nullable): HIP-event time of the
+ * kernel on the context's stream.  Returns after the work has completed, with the statuses above. */
+int abn_analyze_batch_dev(abn_ctx* ctx, const void* dev_raw, int32_t n_windows, int64_t n_boot, void* dev_out,
+                          void* dev_first_bad, double* kernel_ms);
 
 /* ------------------------------------------------------------------ pedigree construction
  * DMatrix::from (src/pedigree.rs:210-261): pairwise divergence of n samples over n_sites aligned sites.
@@ -324,6 +342,12 @@ int abn_plan_bind_raw(abn_plan* plan, void* dev_ptr);
  * window's model, pred, resid and bootstrap rows are NaN, the other windows are valid. */
 int abn_plan_download(abn_plan* plan, double* models, double* pred, double* resid, double* raw,
                       abn_fit_info* info_a, abn_fit_info* info_b, int32_t* best_start);
+/* src/analysis.rs:50-98 of every window of the plan, on the device (abn_analyze_batch_dev on the table the plan currently
+ * writes — its own or the one given to abn_plan_bind_raw — so only W x 32 doubles come back instead of raw[W x B x 7]):
+ * out[W x 32], first_bad[W] (may be NULL) are HOST arrays.  ABN_ERR_STATE when phase B has not run;
+ * ABN_ERR_NO_FINITE_FIT after filling every buffer when a window's table holds a NaN (a window without a finite start
+ * among them).  Synchronises like abn_plan_sync. */
+int abn_plan_analyze(abn_plan* plan, double* out, int32_t* first_bad);
 /* number of windows whose selection found no finite start in the last phase-A run (cheap: W int32 come back) */
 int abn_plan_failed_windows(abn_plan* plan, int32_t* n_failed);
 /* sums over all fits of the last run (for evals/s): out[0] = fits, out[1] = evals (cost() calls of the reference
@@ -382,6 +406,9 @@ int abn_multi_raw_device_ptr(abn_multi* m, int32_t device_index, void** dev_ptr)
  * ABN_ERR_NO_FINITE_FIT after filling every buffer when a window has no finite start */
 int abn_multi_download(abn_multi* m, double* models, double* pred, double* resid, double* raw,
                        abn_fit_info* info_a, abn_fit_info* info_b, int32_t* best_start);
+/* src/analysis.rs:50-98 of all W windows on the first device's gathered table (as abn_plan_analyze; valid after
+ * abn_multi_run, synchronises like abn_multi_sync): out[W x 32], first_bad[W] (may be NULL), HOST arrays */
+int abn_multi_analyze(abn_multi* m, double* out, int32_t* first_bad);
 /* abn_plan_counters summed over the devices (bootstrap-sharded mode: the replicated phase-A fits count per device) */
 int abn_multi_counters(abn_multi* m, int64_t* out5);
 /* *ok = 1 when librccl.so.1 can be loaded and exports every symbol the gather uses */
