@@ -57,6 +57,8 @@ EXPORTED_SYMBOLS = [
     "abn_pairwise_divergence_packed_dev",
     "abn_pairwise_divergence_windows_packed", "abn_pairwise_divergence_windows_packed_dev",
     "abn_analyze_batch", "abn_analyze_batch_dev", "abn_plan_analyze", "abn_multi_analyze",
+    "abn_windows_create", "abn_windows_destroy", "abn_windows_info", "abn_windows_stats", "abn_windows_layout",
+    "abn_windows_packed", "abn_windows_packed_device_ptr", "abn_windows_pairwise",
 ]
 
 
@@ -72,6 +74,19 @@ class Options(C.Structure):
         ("sd_tolerance", C.c_double),
         ("window_groups", C.c_int32),
         ("no_fixed_point_skip", C.c_int32),
+    ]
+
+
+class WindowsParams(C.Structure):
+    """abn_windows_params: arguments::Windows and the window counts of Windows::new (src/windows.rs:28-44)"""
+    _fields_ = [
+        ("cutoff", C.c_uint32),
+        ("step", C.c_uint32),
+        ("size", C.c_uint32),
+        ("absolute", C.c_int32),
+        ("n_upstream", C.c_int32),
+        ("n_gene", C.c_int32),
+        ("n_downstream", C.c_int32),
     ]
 
 
@@ -147,6 +162,15 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
                                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
     L.abn_pairwise_divergence_windows_packed_dev.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, i64p, i64p,
                                                              C.c_int32, vp, vp, vp, dp]
+    L.abn_windows_create.argtypes = [vp, C.POINTER(WindowsParams), C.c_int32, i64p, u32p, u32p, u32p, u8p, u8p, dp,
+                                     C.POINTER(vp)]
+    L.abn_windows_destroy.argtypes = [vp]
+    L.abn_windows_info.argtypes = [vp, C.POINTER(C.c_int32), i64p, i64p]
+    L.abn_windows_stats.argtypes = [vp, i64p, dp, dp, i64p]
+    L.abn_windows_layout.argtypes = [vp, i64p, i64p, C.POINTER(C.c_int32)]
+    L.abn_windows_packed.argtypes = [vp, u8p]
+    L.abn_windows_packed_device_ptr.argtypes = [vp, C.POINTER(vp)]
+    L.abn_windows_pairwise.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
     L.abn_plan_create.argtypes = [vp, op, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                   C.POINTER(vp)]
     L.abn_plan_destroy.argtypes = [vp]
@@ -673,6 +697,88 @@ class Plan:
         out = (C.c_int32 * 4)()
         self.ctx._check(self._L.abn_plan_last_kernels(self._h, out))
         return {"starts": (KERNEL_NAMES.get(out[0], out[0]), out[1]), "boot": (KERNEL_NAMES.get(out[2], out[2]), out[3])}
+
+
+class Windows:
+    """abn_windows: the sites of n_samples methylomes placed into metaprofile windows on the device
+    (MethylationSite::place_in_windows, src/methylation_site.rs:423-490), device-resident as the 2-bit packed matrix of
+    Context.pairwise_divergence_windows_packed.
+
+    site_offset (n_samples + 1,) int64; per site (concatenated over the samples, file order): pos, gene_start, gene_end
+    uint32, flags uint8 (bit 0 antisense, bit 1 has a gene), code uint8 (status | 0x80 when filtered), level float64.
+    cutoff, step, size, absolute: arguments::Windows; counts = (n_upstream, n_gene, n_downstream) of Windows::new."""
+
+    def __init__(self, ctx: Context, site_offset, pos, gene_start, gene_end, flags, code, level, *, cutoff, step, size,
+                 absolute, counts):
+        self.ctx = ctx
+        self._L = ctx._L
+        off = np.ascontiguousarray(site_offset, dtype=np.int64)
+        self.n_samples = off.shape[0] - 1
+        S = int(off[-1]) if off.shape[0] else 0
+        u32 = [np.ascontiguousarray(a, dtype=np.uint32).reshape(S) for a in (pos, gene_start, gene_end)]
+        u8 = [np.ascontiguousarray(a, dtype=np.uint8).reshape(S) for a in (flags, code)]
+        lvl = _f64(level, (S,))
+        p = WindowsParams(cutoff, step, size, 1 if absolute else 0, *map(int, counts))
+        h = C.c_void_p()
+        u8p = C.POINTER(C.c_uint8)
+        ctx._check(self._L.abn_windows_create(ctx._h, C.byref(p), self.n_samples, off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              _u32p(u32[0]), _u32p(u32[1]), _u32p(u32[2]), u8[0].ctypes.data_as(u8p),
+                                              u8[1].ctypes.data_as(u8p), _dp(lvl), C.byref(h)))
+        self._h = h
+        W, stride, ns = C.c_int32(), C.c_int64(), C.c_int64()
+        ctx._check(self._L.abn_windows_info(h, C.byref(W), C.byref(stride), C.byref(ns)))
+        self.W, self.row_stride, self.n_sites = W.value, stride.value, ns.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.abn_windows_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def stats(self):
+        """(count int64, level_sum, level_sum_kept, kept int64), each (n_samples, W)"""
+        shape = (self.n_samples, self.W)
+        count, kept = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int64)
+        ls, lsk = np.zeros(shape), np.zeros(shape)
+        i64p = C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_windows_stats(self._h, count.ctypes.data_as(i64p), _dp(ls), _dp(lsk),
+                                                  kept.ctypes.data_as(i64p)))
+        return count, ls, lsk, kept
+
+    def layout(self):
+        """(begin int64, end int64, ragged int32), each (W,): window w = the fields [begin[w], end[w]) of every row"""
+        b, e = np.zeros(self.W, dtype=np.int64), np.zeros(self.W, dtype=np.int64)
+        r = np.zeros(self.W, dtype=np.int32)
+        i64p = C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_windows_layout(self._h, b.ctypes.data_as(i64p), e.ctypes.data_as(i64p),
+                                                   r.ctypes.data_as(C.POINTER(C.c_int32))))
+        return b, e, r
+
+    def packed(self) -> np.ndarray:
+        """the packed matrix (n_samples, row_stride) uint8, copied to the host"""
+        out = np.empty((self.n_samples, self.row_stride), dtype=np.uint8)
+        self.ctx._check(self._L.abn_windows_packed(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def packed_device_ptr(self) -> int:
+        p = C.c_void_p()
+        self.ctx._check(self._L.abn_windows_packed_device_ptr(self._h, C.byref(p)))
+        return p.value or 0
+
+    def pairwise(self):
+        """(diff, both, dvalue), each (W, pairs): pairwise_divergence of every window, on the resident matrix"""
+        npairs = self.n_samples * (self.n_samples - 1) // 2
+        diff, both = np.zeros((self.W, npairs), dtype=np.uint64), np.zeros((self.W, npairs), dtype=np.uint64)
+        dval = np.zeros((self.W, npairs))
+        u64p = C.POINTER(C.c_uint64)
+        self.ctx._check(self._L.abn_windows_pairwise(self._h, diff.ctypes.data_as(u64p), both.ctypes.data_as(u64p),
+                                                     _dp(dval)))
+        return diff, both, dval
 
 
 def reduction_tree(generations, options: Options | None = None) -> int:

@@ -81,7 +81,8 @@ def build_host(force: bool = False, verbose: bool = False) -> Path:
     """The C++ host layer: the `alphabeta` CLI (reference flags and output files) and a small shared
     library exposing Pedigree::build to the tests.  Both link libabneutral_hip.so via $ORIGIN rpaths."""
     build_hip()
-    srcs = [HOST / "alphabeta_cli.cpp", HOST / "alphabeta.hpp", HOST / "pedigree_build.hpp", HOST / "host_capi.cpp",
+    srcs = [HOST / "alphabeta_cli.cpp", HOST / "alphabeta.hpp", HOST / "pedigree_build.hpp", HOST / "windows_extract.hpp",
+            HOST / "host_capi.cpp",
             HOST / "metaprofile.hpp", HOST / "metaprofile_cli.cpp", HOST / "reference_tests.cpp",
             CSRC / "abn_route.hpp", CSRC / "abn_constants.hpp"]  # host_capi.cpp exports the launch policy to the tests
     newest = max(p.stat().st_mtime for p in srcs)

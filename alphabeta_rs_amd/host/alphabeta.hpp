@@ -493,6 +493,7 @@ inline RunResult run_on_pedigree(Pedigree pedigree, double p0uu, size_t iteratio
 }  // namespace alphabeta
 
 #include "pedigree_build.hpp"
+#include "windows_extract.hpp"
 
 namespace alphabeta {
 // src/alphabeta.rs:23-59

@@ -125,6 +125,55 @@ int abh_pedigree_build_many(const char* const* nodelists, const char* const* edg
     return -1;
   }
 }
+// ---- the host half of the window extraction (windows_extract.hpp), for tests/test_windows_host.py
+// parse_annotation -> the genes of every list as lines "chromosome list start end strand name\n" (list: s / a / c; strand
+// 0 / 1 / 2 = + / - / *), chromosomes ascending (256 = M, 257 = C); out2 = {genes parsed, max gene length}.
+// Returns the text's length, or -1 when it does not fit
+long long abh_annotation_lists(const char* text, long long len, char* out, long long cap, long long* out2) {
+  const auto g = alphabeta::windows::parse_annotation(std::string(text, (size_t)len));
+  std::string s;
+  for (const auto& kv : g.chromosomes) {
+    const std::pair<const char*, const std::vector<alphabeta::windows::Gene>*> lists[3] = {
+        {"s", &kv.second.sense}, {"a", &kv.second.antisense}, {"c", &kv.second.combined}};
+    for (const auto& l : lists)
+      for (const auto& e : *l.second)
+        s += std::to_string(kv.first) + " " + l.first + " " + std::to_string(e.start) + " " + std::to_string(e.end) + " " +
+             std::to_string((int)e.strand) + " " + e.name + "\n";
+  }
+  out2[0] = (long long)g.n_genes;
+  out2[1] = (long long)g.max_gene_length;
+  if ((long long)s.size() + 1 > cap) return -1;
+  std::memcpy(out, s.c_str(), s.size() + 1);
+  return (long long)s.size();
+}
+// choose_genes of one methylome text against an annotation text -> the per-site arrays abn_windows_create takes (capacity
+// cap sites each).  Returns the number of sites, -1 when they do not fit
+long long abh_choose_genes(const char* annotation, long long alen, const char* methylome, long long mlen, unsigned cutoff,
+                           int cutoff_gene_length, double posterior_max_filter, long long cap, unsigned* pos,
+                           unsigned* gene_start, unsigned* gene_end, unsigned char* flags, unsigned char* code,
+                           double* level) {
+  namespace w = alphabeta::windows;
+  const auto g = w::parse_annotation(std::string(annotation, (size_t)alen));
+  const auto s = w::choose_genes(std::string(methylome, (size_t)mlen), g, w::GeneRule{cutoff, cutoff_gene_length != 0},
+                                 posterior_max_filter);
+  const size_t n = s.size();
+  if ((long long)n > cap) return -1;
+  if (n == 0) return 0;
+  std::memcpy(pos, s.pos.data(), 4 * n);
+  std::memcpy(gene_start, s.gene_start.data(), 4 * n);
+  std::memcpy(gene_end, s.gene_end.data(), 4 * n);
+  std::memcpy(flags, s.flags.data(), n);
+  std::memcpy(code, s.code.data(), n);
+  std::memcpy(level, s.level.data(), 8 * n);
+  return (long long)n;
+}
+// window_params -> out3 = the window counts of upstream, gene, downstream (Windows::new)
+void abh_window_counts(unsigned cutoff, unsigned step, unsigned size, int absolute, unsigned max_gene_length, int* out3) {
+  const abn_windows_params p = alphabeta::windows::window_params(cutoff, step, size, absolute != 0, max_gene_length);
+  out3[0] = p.n_upstream;
+  out3[1] = p.n_gene;
+  out3[2] = p.n_downstream;
+}
 int abh_pedigree_roundtrip(const char* in_path, const char* out_path) {
   try {
     auto ped = alphabeta::Pedigree::from_file(in_path);

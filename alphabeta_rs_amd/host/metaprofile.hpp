@@ -2,9 +2,14 @@
 // (src/cli/metaprofile.rs:33-114; SURVEY.md §8f row 2, "next"): the SERIAL window loop that calls
 // alphabeta::run once per (region, window) directory becomes ONE batched, device-resident plan
 // (abn_plan_*: W windows x (S starts + B bootstraps) in three kernel launches) behind ONE batched pedigree
-// construction (Pedigree::build_many -> abn_pairwise_divergence_windows_packed).  The window extraction
-// that fills those directories (src/extract.rs, src/windows.rs, src/setup.rs) is out of scope; this driver
-// starts from the directory tree setup.rs writes: <output_dir>/<region>/<window>/{nodelist,edgelist}.txt.
+// construction (Pedigree::build_many -> abn_pairwise_divergence_windows_packed).  That path starts from the directory
+// tree the reference's `extract` stage writes: <output_dir>/<region>/<window>/{nodelist,edgelist}.txt and the samples'
+// window files (src/setup.rs:35-72, src/windows.rs:259-285).
+//
+// The `extract` stage itself (src/extract.rs:17-155) is extract_in_memory: whole methylome files and a gene annotation
+// in, every site placed into its windows on the device (windows_extract.hpp, abn_windows_*), the packed matrix of the
+// scan written there directly — no file tree in between — and alphabeta_multiple_in_memory runs the scan, the fits and the
+// analysis on it.  --invert and the "load an existing extraction" shortcut (src/windows.rs:178-243) are not part of it.
 //
 // Outputs as the reference: results.txt (:74-99, ';'-separated, one line per successful window) and
 // raw.npy, the (iterations, 7, n_windows) array of :49,68,110.  The metaplot PNG (:113) is not produced.
@@ -12,6 +17,7 @@
 
 #include <filesystem>
 #include <iostream>
+#include <memory>
 
 #include "alphabeta.hpp"
 
@@ -27,6 +33,11 @@ struct WindowArgs {  // the fields of arguments::Windows (src/arguments.rs:6-62)
   bool absolute = false;
   size_t iterations = 100;
   double posterior_max_filter = 0.99;  // AlphaBeta::default (src/arguments.rs:142-152)
+  // extract_in_memory only
+  std::string methylome, genome;  // directory of methylome files, annotation file
+  std::string nodes, edges;       // the one nodelist / edgelist of every window (arguments::AlphaBeta)
+  bool cutoff_gene_length = false;
+  bool invert = false;            // refused
 };
 
 struct WindowResult {
@@ -44,18 +55,20 @@ struct Output {
   std::string results_txt;
 };
 
+struct Win {  // a window whose pedigree was built
+  std::string region;
+  Pedigree ped;
+  double p0uu;
+  size_t index;  // position in the (region, window) enumeration
+};
+inline Output fit_windows(const WindowArgs& args, std::vector<Win> wins, const std::vector<int>& distribution);
+
 // src/cli/metaprofile.rs:33-114
 inline Output alphabeta_multiple(const WindowArgs& args, uint32_t max_gene_length, const std::vector<int>& distribution) {
   namespace fs = std::filesystem;
   const uint32_t step = args.window_step == 0 ? args.window_size : args.window_step;
   const std::vector<std::pair<std::string, uint32_t>> regions = {
       {"upstream", args.cutoff}, {"gene", max_gene_length}, {"downstream", args.cutoff}};  // :34-38
-  struct Win {
-    std::string region;
-    Pedigree ped;
-    double p0uu;
-    size_t index;
-  };
   std::vector<Win> wins;
   // every (region, window) directory in the reference's order; all pedigrees are built together (Pedigree::build_many:
   // one batched pairwise scan instead of one per window), then reported in that order, each window's diagnostics first
@@ -80,6 +93,11 @@ inline Output alphabeta_multiple(const WindowArgs& args, uint32_t max_gene_lengt
     else
       std::printf("Error: Error while building pedigree: %s\n", b.error.c_str());
   }
+  return fit_windows(args, std::move(wins), distribution);
+}
+
+// The windows' fits, analyses and results.txt (src/cli/metaprofile.rs:50-110 behind the pedigree build)
+inline Output fit_windows(const WindowArgs& args, std::vector<Win> wins, const std::vector<int>& distribution) {
   Output out;
   out.iterations = args.iterations;
   if (wins.empty()) return out;
@@ -189,6 +207,195 @@ inline Output alphabeta_multiple(const WindowArgs& args, uint32_t max_gene_lengt
   }
   out.results_txt = print;
   return out;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The `extract` stage without the file tree (src/extract.rs:17-155)
+struct Extraction {
+  std::vector<std::string> names;           // the methylome files, sorted by name (the reference takes read_dir's order)
+  std::unique_ptr<windows::Handle> handle;  // every sample's sites placed, packed and summed, device-resident
+  abn_windows_params params{};
+  uint32_t max_gene_length = 100;
+  std::vector<int> distribution;  // the first methylome's window counts (src/extract.rs:154)
+};
+
+// nodelist and edgelist as detail::read_inputs reads them (src/pedigree.rs:98-136), without opening a methylome
+inline detail::Inputs read_graph(const std::string& nodelist, const std::string& edgelist) {
+  using namespace detail;
+  Inputs in;
+  const std::string nodes_txt = read_file(nodelist, "nodelist"), edges_txt = read_file(edgelist, "edgelist");
+  {
+    const auto lines = split_any(nodes_txt, "\n\r");
+    for (size_t li = 1; li < lines.size(); ++li) {
+      const auto e = split_any(lines[li], ",\t ");
+      if (e.size() < 4) continue;
+      uint32_t gen;
+      if (!parse_u32(e[2], gen)) continue;
+      in.all.push_back(Node{li - 1, e[0], e[1], gen, e[3] == "Y", 0.0, {}});
+    }
+  }
+  if (in.all.empty()) throw Error(ABN_ERR_INVALID_ARG, "No nodes could be parsed from the nodelist");
+  {
+    const auto lines = split_any(edges_txt, "\n\r");
+    for (size_t li = 1; li < lines.size(); ++li) {
+      const auto e = split_any(lines[li], "\t ,");
+      if (e.size() < 2) continue;
+      size_t f = in.all.size(), t = in.all.size();
+      for (size_t k = 0; k < in.all.size(); ++k) {
+        if (f == in.all.size() && in.all[k].name == e[0]) f = k;
+        if (t == in.all.size() && in.all[k].name == e[1]) t = k;
+      }
+      if (f < in.all.size() && t < in.all.size()) in.edges.push_back(EdgeRef{f, t});
+    }
+  }
+  for (const auto& n : in.all)
+    if (n.meth) in.nodes.push_back(n);
+  return in;
+}
+
+// src/extract.rs:17-155: parse the annotation and every methylome once, choose every site's gene on the host, place the
+// sites into windows on the device; write distribution_<name>, distributions.txt, steady_state_methylation.txt and
+// all_steady_state_methylation.txt (:112-151, src/windows.rs:130-176,245-257) into the output directory.
+inline Extraction extract_in_memory(const WindowArgs& args) {
+  namespace fs = std::filesystem;
+  if (args.invert) throw Error(ABN_ERR_INVALID_ARG, "--invert is not supported with --methylome");
+  const uint32_t step = args.window_step == 0 ? args.window_size : args.window_step;  // :26-28
+  if (step == 0) throw Error(ABN_ERR_INVALID_ARG, "window step and window size are both 0");
+  Extraction ex;
+  // files::load_methylome (src/files.rs:23-38): files with an extension other than *tsv* / *fn*
+  {
+    std::error_code ec;
+    fs::directory_iterator it(args.methylome, ec);
+    if (ec) throw Error(ABN_ERR_INVALID_ARG, "could not read the methylome directory " + args.methylome);
+    for (const auto& e : it) {
+      const std::string ext = e.path().extension().string();
+      if (ext.empty() || ext.find("tsv") != std::string::npos || ext.find("fn") != std::string::npos) continue;
+      if (!e.is_regular_file()) continue;
+      ex.names.push_back(e.path().filename().string());
+    }
+    std::sort(ex.names.begin(), ex.names.end());
+  }
+  if (ex.names.empty())
+    throw Error(ABN_ERR_INVALID_ARG, "Could not find any files in the methylome directory. Please check your input. "
+                                     "Files with .tsv or .fn extensions are ignored.");
+  std::string annotation;
+  try {
+    annotation = detail::read_file(args.genome, "annotation");
+  } catch (const Error&) {
+    throw Error(ABN_ERR_INVALID_ARG, "Error while reading genome annotation file: " + args.genome);
+  }
+  const windows::Genome genome = windows::parse_annotation(annotation);
+  if (genome.n_genes == 0)
+    throw Error(ABN_ERR_INVALID_ARG, "Could not parse a single annotation from the annotation file. Please check your "
+                                     "input or add a parser implemenation for your data format.");
+  if (args.absolute) {
+    ex.max_gene_length = genome.max_gene_length;
+    std::printf("The maximum gene length is %u bp\n", ex.max_gene_length);
+  }
+  ex.params = windows::window_params(args.cutoff, step, args.window_size, args.absolute, ex.max_gene_length);
+  std::vector<windows::SampleSites> samples;
+  {
+    std::vector<std::string> texts;
+    for (const auto& name : ex.names) texts.push_back(detail::read_file((fs::path(args.methylome) / name).string(), "methylome"));
+    samples = windows::choose_genes_many(texts, genome, windows::GeneRule{args.cutoff, args.cutoff_gene_length},
+                                         args.posterior_max_filter);
+  }
+  ex.handle = std::make_unique<windows::Handle>(default_device(), ex.params, samples);
+  const windows::Handle& h = *ex.handle;
+  const size_t n = h.n_samples(), W = h.n_windows();
+  for (size_t w = 0; w < W; ++w) ex.distribution.push_back((int)h.count[w]);
+  // the four kinds of side files
+  std::string all_dist, all_meth, avg_txt;
+  std::vector<double> average(W, 0.0);
+  for (size_t s = 0; s < n; ++s) {
+    std::string dist;
+    all_dist += ex.names[s] + ";";
+    all_meth += ex.names[s] + ";";
+    for (size_t w = 0; w < W; ++w) {
+      const long long cnt = (long long)h.count[s * W + w];
+      const double m = h.level_sum[s * W + w] / (double)cnt;  // fold / len, NaN for an empty window (:112)
+      dist += std::to_string((int)cnt) + "\n";
+      all_dist += std::to_string((int)cnt) + ";";
+      all_meth += fmt_f64(m) + ";";
+      average[w] += m / (double)n;  // src/extract.rs:106-110
+    }
+    all_dist += "\n";
+    all_meth += "\n";
+    std::ofstream(fs::path(args.output_dir) / ("distribution_" + ex.names[s]), std::ios::binary) << dist;
+  }
+  for (size_t w = 0; w < W; ++w) avg_txt += fmt_f64(average[w]) + "\n";
+  std::ofstream(fs::path(args.output_dir) / "steady_state_methylation.txt", std::ios::binary) << avg_txt;
+  std::ofstream(fs::path(args.output_dir) / "all_steady_state_methylation.txt", std::ios::binary) << all_meth;
+  std::ofstream(fs::path(args.output_dir) / "distributions.txt", std::ios::binary) << all_dist;
+  return ex;
+}
+
+// alphabeta_multiple (src/cli/metaprofile.rs:33-114) on an Extraction: the pedigrees and p0uu come from the handle — one
+// scan of the resident matrix for all windows, detail::convert once per window on its D values — instead of
+// Pedigree::build_many on window directories.  Window ids stay the position in the (region, window) enumeration of
+// :50-53, which names ceil(max / step) windows per region where Windows::new creates floor(max / step): the window the
+// enumeration names beyond those fails as its missing sample file fails there.  A RAGGED window (the samples' site counts
+// differ) fails too; the reference goes on with D = 0 for its pairs (DESIGN.md §4 "Window placement").
+inline Output alphabeta_multiple_in_memory(const WindowArgs& args, const Extraction& ex) {
+  namespace fs = std::filesystem;
+  const windows::Handle& h = *ex.handle;
+  const size_t n = h.n_samples(), W = h.n_windows(), npairs = n * (n - 1) / 2;
+  const detail::Inputs graph = read_graph(args.nodes, args.edges);
+  const size_t nn = graph.nodes.size();
+  auto base_name = [](const std::string& p) { return p.substr(p.find_last_of('/') == std::string::npos ? 0 : p.find_last_of('/') + 1); };
+  std::vector<size_t> sample_of(nn);
+  for (size_t i = 0; i < nn; ++i) {
+    const auto it = std::find(ex.names.begin(), ex.names.end(), base_name(graph.nodes[i].file));
+    if (it == ex.names.end()) throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " + graph.nodes[i].file);
+    sample_of[i] = (size_t)(it - ex.names.begin());
+  }
+  std::vector<double> dv(std::max<size_t>(W * npairs, 1), 0.0);
+  default_device().check(abn_windows_pairwise(h.get(), nullptr, nullptr, dv.data()), "abn_windows_pairwise");
+  const uint32_t step = ex.params.step;
+  const std::vector<std::tuple<std::string, uint32_t, size_t, size_t>> regions = {
+      {"upstream", args.cutoff, 0, (size_t)ex.params.n_upstream},
+      {"gene", ex.max_gene_length, (size_t)ex.params.n_upstream, (size_t)ex.params.n_gene},
+      {"downstream", args.cutoff, (size_t)ex.params.n_upstream + (size_t)ex.params.n_gene, (size_t)ex.params.n_downstream}};
+  std::vector<Win> wins;
+  size_t index = 0;
+  for (const auto& [region, region_max, first, count] : regions) {
+    const uint32_t max = args.absolute ? region_max : 100;
+    for (uint32_t window = 0, k = 0; window < max; window += step, ++k, ++index) {
+      try {
+        if (k >= count)  // named by the enumeration, not created by Windows::new: no sample file in that directory
+          throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " +
+                                               (fs::path(args.output_dir) / region / std::to_string(window) /
+                                                (nn ? base_name(graph.nodes[0].file) : std::string()))
+                                                   .string());
+        const size_t w = first + k;
+        if (h.ragged[w]) {
+          for (size_t a = 0; a < nn; ++a)
+            for (size_t b = a + 1; b < nn; ++b)
+              if (h.count[sample_of[a] * W + w] != h.count[sample_of[b] * W + w])
+                std::printf("Lengths do not match, all bets are off: %zu vs %zu\n", (size_t)h.count[sample_of[a] * W + w],
+                            (size_t)h.count[sample_of[b] * W + w]);
+          throw Error(ABN_ERR_INVALID_ARG, "the samples' site counts differ in this window");
+        }
+        std::vector<double> dm(nn * nn, 0.0);
+        double p0 = 0.0;
+        for (size_t a = 0; a < nn; ++a) {
+          const size_t sa = sample_of[a];
+          p0 += 1.0 - h.level_sum_kept[sa * W + w] / (double)h.kept[sa * W + w];  // src/pedigree.rs:165-166,180-184
+          for (size_t b = a + 1; b < nn; ++b) {
+            const size_t sb = sample_of[b], i = std::min(sa, sb), j = std::max(sa, sb);
+            dm[a * nn + (b - a - 1)] = i == j ? (h.kept[sa * W + w] > 0 ? 0.0 : std::nan(""))
+                                              : dv[w * npairs + i * n - i * (i + 1) / 2 + (j - i - 1)];
+          }
+        }
+        Pedigree ped = detail::convert(graph, dm);
+        if (ped.nrows() == 0) throw Error(ABN_ERR_BAD_PEDIGREE, "empty pedigree");
+        wins.push_back(Win{region, std::move(ped), p0 / (double)nn, index});
+      } catch (const std::exception& e) {
+        std::printf("Error: Error while building pedigree: %s\n", e.what());
+      }
+    }
+  }
+  return fit_windows(args, std::move(wins), ex.distribution);
 }
 
 // ndarray_npy::write_npy of the (iterations, 7, n_windows) array (:110)

@@ -1,6 +1,8 @@
-// `metaprofile_alphabeta`: the AlphaBeta stage of the reference's `metaprofile` binary
-// (src/cli/metaprofile.rs:33-114) on window directories that already exist
+// `metaprofile_alphabeta`: the reference's `metaprofile` binary (src/cli/metaprofile.rs:33-114).
+// Without --methylome: the AlphaBeta stage on window directories that already exist
 // (<output-dir>/{upstream,gene,downstream}/<window>/{nodelist,edgelist}.txt, as written by src/setup.rs:35-72).
+// With --methylome DIR --genome FILE --nodes FILE --edges FILE: the `extract` stage too (src/extract.rs:17-155), from
+// whole methylome files and a gene annotation, the sites placed into windows on the device and no file tree in between.
 // All windows are fitted by one batched plan on the MI355X.  Flags follow src/arguments.rs:6-62 where they apply.
 #include <cstdlib>
 #include <cstring>
@@ -38,10 +40,18 @@ int main(int argc, char** argv) {
     else if (f == "--seed") seed = std::strtoull(val().c_str(), nullptr, 10);
     else if (f == "--device") device = std::atoi(val().c_str());
     else if (f == "--devices") devices_arg = val();
+    else if (f == "-m" || f == "--methylome") a.methylome = val();
+    else if (f == "-g" || f == "--genome") a.genome = val();
+    else if (f == "--nodes") a.nodes = val();
+    else if (f == "--edges") a.edges = val();
+    else if (f == "--cutoff-gene-length") a.cutoff_gene_length = true;
+    else if (f == "-i" || f == "--invert") a.invert = true;
     else if (f == "-h" || f == "--help") {
       std::puts("Usage: metaprofile_alphabeta -o <output-dir> [--name N] [-s step] [-w size] [-c cutoff] [-a]\n"
                 "       [--iterations 100] [--max-gene-length L] [--distribution FILE] [--seed S] [--device D]\n"
-                "       [--devices A,B,..]   windows sharded over several HIP devices, tables gathered with RCCL");
+                "       [--devices A,B,..]   windows sharded over several HIP devices, tables gathered with RCCL\n"
+                "       [--methylome DIR --genome FILE --nodes FILE --edges FILE [--cutoff-gene-length]]\n"
+                "                            extract the windows from whole methylomes on the device (no window directories)");
       return 0;
     } else {
       std::fprintf(stderr, "error: unexpected argument '%s' found\n", argv[i]);
@@ -50,6 +60,19 @@ int main(int argc, char** argv) {
   }
   if (!std::filesystem::exists(a.output_dir)) {
     std::fprintf(stderr, "error: output directory %s does not exist\n", a.output_dir.c_str());
+    return 2;
+  }
+  const bool in_memory = !a.methylome.empty();
+  if (in_memory && a.invert) {
+    std::fprintf(stderr, "error: --invert is not supported with --methylome\n");
+    return 2;
+  }
+  if (in_memory && (a.genome.empty() || a.nodes.empty() || a.edges.empty())) {
+    std::fprintf(stderr, "error: --methylome needs --genome, --nodes and --edges\n");
+    return 2;
+  }
+  if (!in_memory && (!a.genome.empty() || !a.nodes.empty() || !a.edges.empty() || a.cutoff_gene_length || a.invert)) {
+    std::fprintf(stderr, "error: --genome, --nodes, --edges, --cutoff-gene-length and --invert belong to --methylome\n");
     return 2;
   }
   std::printf("Starting run %s\n", a.name.c_str());
@@ -61,6 +84,14 @@ int main(int argc, char** argv) {
     Device& dev = default_device(device);
     if (device_list().empty()) device_list().push_back(device);
     dev.options.seed = seed;
+    if (in_memory) {
+      const auto ex = metaprofile::extract_in_memory(a);
+      const auto out = metaprofile::alphabeta_multiple_in_memory(a, ex);
+      std::printf("%s\n", out.results_txt.c_str());
+      std::ofstream(std::filesystem::path(a.output_dir) / "results.txt") << out.results_txt;
+      metaprofile::write_raw_npy(out, (std::filesystem::path(a.output_dir) / "raw.npy").string());
+      return 0;
+    }
     std::vector<int> distribution;
     if (!dist_file.empty()) {
       std::ifstream f(dist_file);

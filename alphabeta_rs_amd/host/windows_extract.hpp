@@ -1,0 +1,286 @@
+// windows_extract.hpp — the host half of the reference's `extract` stage (src/extract.rs:17-155): the annotation parser
+// (src/genes.rs:140-217), the full methylome-line parse (src/methylation_site.rs:146-362) and the choice of a gene for
+// every site (src/windows.rs:303-338 around is_in_gene / find_gene, src/methylation_site.rs:368-418).  What follows the
+// gene choice — place_in_windows, the per-window site lists, the packed matrix, the folds — runs on the device
+// (abn_windows_*, csrc/abn_windows.hpp).  The gene choice is a serial dependence of a few integer compares per site (the
+// last_gene cache), so it stays here, one methylome per thread.  Integer arithmetic wraps as the reference's release
+// build does.  Plain C++, no device.
+#pragma once
+
+#include <thread>
+
+#include "alphabeta.hpp"
+
+namespace alphabeta {
+namespace windows {
+
+enum Strand : uint8_t { Sense = 0, Antisense = 1, Unknown = 2 };  // src/genes.rs:13-18
+// Strand::eq (src/genes.rs:88-96): Unknown equals both
+inline bool strand_eq(Strand a, Strand b) { return !((a == Sense && b == Antisense) || (a == Antisense && b == Sense)); }
+
+// Chromosome (src/methylation_site.rs:48-68) as one integer: Numbered(n) = n, Mitochondrial = 256, Chloroplast = 257
+inline bool parse_chromosome_key(std::string t, int& key) {
+  while (t.rfind("chr", 0) == 0) t = t.substr(3);
+  if (t == "M") return key = 256, true;
+  if (t == "C") return key = 257, true;
+  uint32_t n;
+  if (!detail::parse_u32(t, n) || n > 255) return false;
+  return key = (int)n, true;
+}
+
+struct Gene {  // src/genes.rs:117-125 (the annotation column is not kept)
+  int chromosome;
+  uint32_t start, end;
+  Strand strand;
+  std::string name;
+};
+
+// Gene::from_annotation_file_line, src/genes.rs:166-216 (without --invert).  Six fields split at ' ' and '\t'; the first
+// format has the strand last, the second (seqnames start end width strand id) has it fifth; a line whose strand is in
+// the right place but whose numbers do not parse is dropped, not handed to the other format (:203).
+inline bool parse_gene_line(const std::string& line, Gene& out) {
+  const auto f = detail::split_any(line, " \t");
+  if (f.size() != 6) return false;
+  auto correct = [](const std::string& s) { return s == "+" || s == "-" || s == "*"; };
+  auto strand_of = [](const std::string& s) { return s == "+" ? Sense : (s == "-" ? Antisense : Unknown); };
+  size_t strand, name;
+  if (correct(f[5])) strand = 5, name = 3;
+  else if (correct(f[4])) strand = 4, name = 5;
+  else return false;
+  Gene g;
+  if (!parse_chromosome_key(f[0], g.chromosome) || !detail::parse_u32(f[1], g.start) || !detail::parse_u32(f[2], g.end))
+    return false;
+  g.strand = strand_of(f[strand]);
+  g.name = f[name];
+  out = std::move(g);
+  return true;
+}
+
+struct GenesByStrand {  // src/genes.rs:127-163
+  std::vector<Gene> sense, antisense, combined;
+};
+struct Genome {
+  std::map<int, GenesByStrand> chromosomes;
+  size_t n_genes = 0;
+  uint32_t max_gene_length = 0;  // max(end - start), src/extract.rs:53-57
+};
+
+inline std::vector<std::string> lines_of(const std::string& text) {  // BufRead::lines: "\n" or "\r\n" ends a line
+  std::vector<std::string> lines = detail::split_any(text, "\n");
+  if (!lines.empty() && lines.back().empty()) lines.pop_back();
+  for (auto& l : lines)
+    if (!l.empty() && l.back() == '\r') l.pop_back();
+  return lines;
+}
+
+// src/extract.rs:30-67: every line that parses, by chromosome, each list sorted by start with a STABLE sort
+inline Genome parse_annotation(const std::string& text) {
+  Genome g;
+  for (const auto& line : lines_of(text)) {
+    Gene gene;
+    if (!parse_gene_line(line, gene)) continue;
+    g.max_gene_length = std::max(g.max_gene_length, gene.end - gene.start);
+    ++g.n_genes;
+    GenesByStrand& c = g.chromosomes[gene.chromosome];
+    c.combined.push_back(gene);
+    if (gene.strand == Sense) c.sense.push_back(gene);
+    else if (gene.strand == Antisense) c.antisense.push_back(gene);
+  }
+  auto by_start = [](const Gene& a, const Gene& b) { return a.start < b.start; };
+  for (auto& kv : g.chromosomes) {
+    std::stable_sort(kv.second.sense.begin(), kv.second.sense.end(), by_start);
+    std::stable_sort(kv.second.antisense.begin(), kv.second.antisense.end(), by_start);
+    std::stable_sort(kv.second.combined.begin(), kv.second.combined.end(), by_start);
+  }
+  return g;
+}
+
+struct FullSite {  // the fields of MethylationSite (src/methylation_site.rs:32-45) the extraction reads
+  int chromosome;
+  uint32_t start, end;
+  Strand strand;
+  double posteriormax;
+  uint32_t status_numeric;
+  double meth_lvl;
+};
+
+// MethylationSite::from_methylome_file_line (src/methylation_site.rs:146-362, without --invert): detail::parse_site with
+// the coordinates kept.  A single location gets end = start + 1; the 4-field rows (chromatin state, bigwig) have an
+// Unknown strand, posterior 0, status U, level 0.
+inline bool parse_site_full(const std::string& line, FullSite& out) {
+  const auto tab = detail::split_any(line, "\t");
+  auto cg = [&](size_t chrom, size_t s0, int s1, size_t strand, size_t cm, size_t ct, size_t pm, size_t st, size_t ml) {
+    FullSite s;
+    uint32_t u;
+    if (!parse_chromosome_key(tab[chrom], s.chromosome) || !detail::parse_u32(tab[s0], s.start)) return false;
+    s.end = s.start + 1u;
+    if (s1 >= 0 && !detail::parse_u32(tab[(size_t)s1], s.end)) return false;
+    if (!detail::parse_u32(tab[cm], u) || !detail::parse_u32(tab[ct], u) || !detail::parse_f64(tab[pm], s.posteriormax))
+      return false;
+    if (tab[st].empty() || !detail::parse_f64(tab[ml], s.meth_lvl)) return false;
+    s.strand = tab[strand] == "+" ? Sense : Antisense;
+    s.status_numeric = detail::status_from(tab[st][0]);
+    out = s;
+    return true;
+  };
+  if (tab.size() == 9 && tab[3] == "CG" && cg(0, 1, -1, 2, 4, 5, 6, 7, 8)) return true;    // first_format
+  if (tab.size() == 10 && tab[3] == "CG" && cg(0, 1, -1, 2, 4, 5, 6, 7, 8)) return true;   // second_format
+  if (tab.size() == 11 && tab[3] == "CG" && cg(0, 1, 2, 5, 6, 7, 8, 9, 10)) return true;   // third_format
+  const auto ws = detail::split_any(line, "\t ");
+  if (ws.size() == 4) {
+    FullSite s{0, 0, 0, Unknown, 0.0, 0, 0.0};
+    if (parse_chromosome_key(ws[0], s.chromosome) && detail::parse_u32(ws[1], s.start) && detail::parse_u32(ws[2], s.end)) {
+      out = s;
+      return true;
+    }
+  }
+  return false;
+}
+
+struct GeneRule {  // the two arguments is_in_gene and find_gene read
+  uint32_t cutoff = 2048;
+  bool cutoff_gene_length = false;
+};
+
+// src/methylation_site.rs:368-378
+inline bool is_in_gene(const FullSite& s, const Gene& g, const GeneRule& r) {
+  const uint32_t cutoff = r.cutoff_gene_length ? g.end - g.start : r.cutoff;
+  return s.chromosome == g.chromosome && g.start <= s.start + cutoff && s.end <= g.end + cutoff &&
+         strand_eq(s.strand, g.strand);
+}
+
+// src/methylation_site.rs:385-418.  The lists are sorted by start while the search key is end + cutoff, so with nested or
+// equal-keyed genes the answer depends on the probe sequence: this is slice::binary_search_by of the standard library
+// (the `size / 2` form of Rust 1.52 to 1.81), probe for probe.
+inline const Gene* find_gene(const FullSite& s, const Genome& genome, const GeneRule& r) {
+  const auto it = genome.chromosomes.find(s.chromosome);
+  if (it == genome.chromosomes.end()) return nullptr;
+  const std::vector<Gene>& list =
+      s.strand == Sense ? it->second.sense : (s.strand == Antisense ? it->second.antisense : it->second.combined);
+  auto key = [&](const Gene& g) { return r.cutoff_gene_length ? g.end + (g.end - g.start) : g.end + r.cutoff; };
+  size_t size = list.size(), left = 0, right = size, found = size;
+  bool exact = false;
+  while (left < right) {
+    const size_t mid = left + size / 2;
+    const uint32_t k = key(list[mid]);
+    if (k == s.start) {
+      found = mid;
+      exact = true;
+      break;
+    }
+    if (k < s.start) left = mid + 1;
+    else right = mid;
+    size = right - left;
+  }
+  if (!exact) found = left;
+  if (found >= list.size()) return nullptr;
+  return is_in_gene(s, list[found], r) ? &list[found] : nullptr;
+}
+
+// One methylome in the arrays abn_windows_create takes (a sample's slice of them).
+struct SampleSites {
+  std::vector<uint32_t> pos, gene_start, gene_end;
+  std::vector<uint8_t> flags, code;
+  std::vector<double> level;
+  size_t size() const { return pos.size(); }
+};
+
+// The loop of Windows::extract (src/windows.rs:303-338) up to the call of place_in_windows: the header row is skipped
+// (`lines.skip(1)`), a line that is no site is passed over, a site keeps the previous site's gene while is_in_gene holds.
+inline SampleSites choose_genes(const std::string& methylome_text, const Genome& genome, const GeneRule& rule,
+                                double posterior_max_filter) {
+  SampleSites out;
+  const Gene* last = nullptr;
+  const auto lines = lines_of(methylome_text);
+  for (size_t li = 1; li < lines.size(); ++li) {
+    FullSite s;
+    if (!parse_site_full(lines[li], s)) continue;
+    if (!last || !is_in_gene(s, *last, rule)) last = find_gene(s, genome, rule);
+    out.pos.push_back(s.start);
+    out.gene_start.push_back(last ? last->start : 0);
+    out.gene_end.push_back(last ? last->end : 0);
+    out.flags.push_back((uint8_t)((s.strand == Antisense ? 1u : 0u) | (last ? 2u : 0u)));
+    out.code.push_back((uint8_t)(s.status_numeric | (s.posteriormax < posterior_max_filter ? 0x80u : 0u)));
+    out.level.push_back(s.meth_lvl);
+  }
+  return out;
+}
+
+// Windows::new (src/windows.rs:28-44): floor(max / step) windows per region, in the order upstream, gene, downstream
+inline abn_windows_params window_params(uint32_t cutoff, uint32_t step, uint32_t size, bool absolute,
+                                        uint32_t max_gene_length) {
+  abn_windows_params p{};
+  p.cutoff = cutoff;
+  p.step = step;
+  p.size = size;
+  p.absolute = absolute ? 1 : 0;
+  p.n_upstream = p.n_downstream = (int32_t)((absolute ? cutoff : 100u) / step);
+  p.n_gene = (int32_t)((absolute ? max_gene_length : 100u) / step);
+  return p;
+}
+
+// choose_genes for every methylome text, one per thread (at most max_threads at a time), in the order given
+inline std::vector<SampleSites> choose_genes_many(const std::vector<std::string>& texts, const Genome& genome,
+                                                  const GeneRule& rule, double posterior_max_filter,
+                                                  size_t max_threads = 16) {
+  std::vector<SampleSites> out(texts.size());
+  std::atomic<size_t> next{0};
+  auto work = [&]() {
+    for (size_t i; (i = next.fetch_add(1)) < texts.size();) out[i] = choose_genes(texts[i], genome, rule, posterior_max_filter);
+  };
+  const size_t nt = std::max<size_t>(1, std::min(max_threads, texts.size()));
+  std::vector<std::thread> pool;
+  for (size_t t = 1; t < nt; ++t) pool.emplace_back(work);
+  work();
+  for (auto& t : pool) t.join();
+  return out;
+}
+
+// RAII abn_windows over the samples' concatenated arrays
+class Handle {
+ public:
+  Handle(Device& dev, const abn_windows_params& p, const std::vector<SampleSites>& samples) : n_(samples.size()) {
+    std::vector<int64_t> off(n_ + 1, 0);
+    for (size_t s = 0; s < n_; ++s) off[s + 1] = off[s] + (int64_t)samples[s].size();
+    SampleSites all;
+    for (const auto& s : samples) {
+      all.pos.insert(all.pos.end(), s.pos.begin(), s.pos.end());
+      all.gene_start.insert(all.gene_start.end(), s.gene_start.begin(), s.gene_start.end());
+      all.gene_end.insert(all.gene_end.end(), s.gene_end.begin(), s.gene_end.end());
+      all.flags.insert(all.flags.end(), s.flags.begin(), s.flags.end());
+      all.code.insert(all.code.end(), s.code.begin(), s.code.end());
+      all.level.insert(all.level.end(), s.level.begin(), s.level.end());
+    }
+    dev.check(abn_windows_create(dev.get(), &p, (int32_t)n_, off.data(), all.pos.data(), all.gene_start.data(),
+                                 all.gene_end.data(), all.flags.data(), all.code.data(), all.level.data(), &h_),
+              "abn_windows_create");
+    int32_t W = 0;
+    abn_windows_info(h_, &W, nullptr, nullptr);
+    W_ = (size_t)W;
+    count.resize(n_ * W_);
+    kept.resize(n_ * W_);
+    level_sum.resize(n_ * W_);
+    level_sum_kept.resize(n_ * W_);
+    ragged.resize(W_);
+    abn_windows_stats(h_, count.data(), level_sum.data(), level_sum_kept.data(), kept.data());
+    abn_windows_layout(h_, nullptr, nullptr, ragged.data());
+  }
+  ~Handle() {
+    if (h_) abn_windows_destroy(h_);
+  }
+  Handle(const Handle&) = delete;
+  Handle& operator=(const Handle&) = delete;
+  abn_windows* get() const { return h_; }
+  size_t n_samples() const { return n_; }
+  size_t n_windows() const { return W_; }
+  std::vector<int64_t> count, kept;  // [n_samples x W]
+  std::vector<double> level_sum, level_sum_kept;
+  std::vector<int32_t> ragged;  // [W]
+
+ private:
+  abn_windows* h_ = nullptr;
+  size_t n_ = 0, W_ = 0;
+};
+
+}  // namespace windows
+}  // namespace alphabeta

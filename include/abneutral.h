@@ -302,6 +302,56 @@ int abn_pairwise_divergence_windows_packed_dev(abn_ctx* ctx, const void* dev_pac
                                                const int64_t* site_end, int32_t n_windows, void* dev_diff,
                                                void* dev_both, void* dev_dvalue, double* kernel_ms);
 
+/* ------------------------------------------------------------------ window placement (the `extract` stage)
+ * Windows::extract (src/windows.rs:287-343) behind the gene choice: MethylationSite::place_in_windows
+ * (src/methylation_site.rs:423-490) for every site of every sample, on the device, straight into the packed matrix
+ * abn_pairwise_divergence_windows_packed* scans — no <region>/<window>/<sample> file tree (Windows::save,
+ * src/windows.rs:259-285) in between.  The gene of every site (find_gene with the last_gene cache, :303-338) is chosen on
+ * the host; the handle takes its result.  Global window index: upstream 0.., then gene, then downstream. */
+typedef struct abn_windows abn_windows;
+typedef struct abn_windows_params {
+  uint32_t cutoff;       /* arguments::Windows (src/arguments.rs:6-62)                                          */
+  uint32_t step;         /* window_step after the 0 -> window_size default (src/extract.rs:26-28); not 0        */
+  uint32_t size;         /* window_size                                                                         */
+  int32_t absolute;
+  int32_t n_upstream;    /* Windows::new (src/windows.rs:28-44): cutoff / step, or 100 / step when not absolute */
+  int32_t n_gene;        /* max_gene_length / step, or 100 / step                                               */
+  int32_t n_downstream;  /* as n_upstream                                                                       */
+} abn_windows_params;
+/* Replaces the loop of Windows::extract (src/windows.rs:325-339) from place_in_windows on, and Windows::save
+ * (:259-285), for n_samples methylomes.  Struct-of-arrays over all samples, concatenated in file order: sample s owns the
+ * sites [site_offset[s], site_offset[s + 1]) (site_offset[0] = 0; under 2^32 sites per sample).  Per site: pos = start
+ * (src/methylation_site.rs:431); gene_start / gene_end of its gene; flags bit 0 = the site is on the antisense strand
+ * (Unknown counts as sense, :439-443), bit 1 = it has a gene (without: the site is in no window); code = status | 0x80
+ * when the posterior is below the filter (the byte of abn_pairwise_divergence); level = meth_lvl.
+ * Uploads, places, ranks, packs and sums; *out is device-resident until abn_windows_destroy (destroy it before its
+ * context).  W = n_upstream + n_gene + n_downstream windows.  A window in which the samples' site counts differ is
+ * RAGGED: flagged, and given an empty column range (the reference compares such pairs as D = 0, src/pedigree.rs:210-261).
+ * ABN_ERR_INVALID_ARG: null pointers, n_samples <= 0 or > 65535, step 0, negative window counts, a site_offset that is
+ * not ascending from 0. */
+int abn_windows_create(abn_ctx* ctx, const abn_windows_params* params, int32_t n_samples, const int64_t* site_offset,
+                       const uint32_t* pos, const uint32_t* gene_start, const uint32_t* gene_end, const uint8_t* flags,
+                       const uint8_t* code, const double* level, abn_windows** out);
+int abn_windows_destroy(abn_windows* h);
+/* the matrix Windows::save's files (src/windows.rs:259-285) would have been packed into: W, bytes per row, fields per row
+ * (4 x row_stride: the n_sites of abn_pairwise_divergence_windows_packed); any pointer may be NULL */
+int abn_windows_info(const abn_windows* h, int32_t* n_windows, int64_t* row_stride, int64_t* n_sites);
+/* [n_samples x W] each, any may be NULL: count = Windows::distribution (src/windows.rs:158-165); level_sum = the fold of
+ * Windows::steady_state_methylation before its division (:94-128), in push order; level_sum_kept / kept = sum and number
+ * of the levels whose posterior passes the filter (src/pedigree.rs:165-166), in push order */
+int abn_windows_stats(const abn_windows* h, int64_t* count, double* level_sum, double* level_sum_kept, int64_t* kept);
+/* [W] each, any may be NULL: window w's sites are the fields [begin[w], end[w]) of every row (begin a multiple of 256), in
+ * the order Windows::extract pushed them (src/windows.rs:335); ragged[w] = 1: the counts differ, begin[w] == end[w] */
+int abn_windows_layout(const abn_windows* h, int64_t* begin, int64_t* end, int32_t* ragged);
+/* the packed matrix [n_samples x row_stride] (format above; what layout_packed_call of the host layer writes from the
+ * files of src/windows.rs:259-285): copied to the host, or its device pointer (16-byte aligned, owned by the handle) */
+int abn_windows_packed(abn_windows* h, uint8_t* host_out);
+int abn_windows_packed_device_ptr(abn_windows* h, void** dev_ptr);
+/* DMatrix::from (src/pedigree.rs:210-261) of every window (the loop of src/cli/metaprofile.rs:50-72):
+ * abn_pairwise_divergence_windows_packed_dev on the resident matrix with the handle's begin / end.  HOST outputs
+ * [W x pairs], any may be NULL; a ragged or empty window: diff = both = 0, dvalue = NaN.  n_samples < 2: nothing written. */
+int abn_windows_pairwise(abn_windows* h, uint64_t* diff, uint64_t* both, double* dvalue);
+
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
  * src/cli/metaprofile.rs:50-72, where every window shares nodelist/edgelist), S starts and B bootstraps
