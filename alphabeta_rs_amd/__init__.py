@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "abn_analyze_batch", "abn_analyze_batch_dev", "abn_plan_analyze", "abn_multi_analyze",
     "abn_windows_create", "abn_windows_destroy", "abn_windows_info", "abn_windows_stats", "abn_windows_layout",
     "abn_windows_packed", "abn_windows_packed_device_ptr", "abn_windows_pairwise",
+    "abn_sites_parse", "abn_sites_destroy", "abn_sites_info", "abn_sites_fetch", "abn_sites_deferred",
 ]
 
 
@@ -87,6 +88,15 @@ class WindowsParams(C.Structure):
         ("n_upstream", C.c_int32),
         ("n_gene", C.c_int32),
         ("n_downstream", C.c_int32),
+    ]
+
+
+class SitesParams(C.Structure):
+    """abn_sites_params: the slab size of abn_sites_parse (0: the default) and the leading lines it does not parse"""
+    _fields_ = [
+        ("slab_bytes", C.c_int64),
+        ("skip_lines", C.c_int32),
+        ("reserved", C.c_int32),
     ]
 
 
@@ -171,6 +181,11 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_windows_packed.argtypes = [vp, u8p]
     L.abn_windows_packed_device_ptr.argtypes = [vp, C.POINTER(vp)]
     L.abn_windows_pairwise.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
+    L.abn_sites_parse.argtypes = [vp, C.c_char_p, C.c_int64, C.POINTER(SitesParams), C.POINTER(vp)]
+    L.abn_sites_destroy.argtypes = [vp]
+    L.abn_sites_info.argtypes = [vp, i64p, i64p, i64p, dp]
+    L.abn_sites_fetch.argtypes = [vp, i64p, C.POINTER(C.c_int32), u32p, u32p, u8p, dp, u8p, u8p, dp]
+    L.abn_sites_deferred.argtypes = [vp, i64p, i64p, i64p]
     L.abn_plan_create.argtypes = [vp, op, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                   C.POINTER(vp)]
     L.abn_plan_destroy.argtypes = [vp]
@@ -569,6 +584,31 @@ class Context:
         if not (rc == 5 and allow_failed_windows):
             self._check(rc)
         return ms.value
+
+    def parse_sites(self, text: bytes, *, skip_lines: int = 1, slab_bytes: int = 0):
+        """MethylationSite::from_methylome_file_line (src/methylation_site.rs:146-362) for every line of a methylome
+        file's text from line skip_lines on, on the device.  Returns (sites, deferred): sites = a dict of arrays over the
+        accepted sites in file order (line, chromosome, start, end, strand, posteriormax, status, status_flag, meth_lvl;
+        n_lines and kernel_ms beside them); deferred = a dict of line, offset, length of the lines the device leaves to
+        the host's parser (an f64 field it cannot be certain of, a line beyond its staging limit)."""
+        text = bytes(text)
+        p = SitesParams(slab_bytes, skip_lines, 0)
+        h = C.c_void_p()
+        self._check(self._L.abn_sites_parse(self._h, text, len(text), C.byref(p), C.byref(h)))
+        try:
+            n, nd, nl, ms = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+            self._check(self._L.abn_sites_info(h, C.byref(n), C.byref(nd), C.byref(nl), C.byref(ms)))
+            kinds = {"line": np.int64, "chromosome": np.int32, "start": np.uint32, "end": np.uint32, "strand": np.uint8,
+                     "posteriormax": np.float64, "status": np.uint8, "status_flag": np.uint8, "meth_lvl": np.float64}
+            sites = {k: np.zeros(n.value, dtype=t) for k, t in kinds.items()}
+            self._check(self._L.abn_sites_fetch(h, *(a.ctypes.data_as(t) for a, t in
+                                                     zip(sites.values(), self._L.abn_sites_fetch.argtypes[1:]))))
+            deferred = {k: np.zeros(nd.value, dtype=np.int64) for k in ("line", "offset", "length")}
+            self._check(self._L.abn_sites_deferred(h, *(a.ctypes.data_as(C.POINTER(C.c_int64)) for a in deferred.values())))
+            sites["n_lines"], sites["kernel_ms"] = nl.value, ms.value
+            return sites, deferred
+        finally:
+            self._L.abn_sites_destroy(h)
 
     # ---- (3) boot_model::run
     def boot_model_run(self, pedigree, model, pred, resid, p0uu, eqp, eqp_weight, n_boot, *,

@@ -338,7 +338,8 @@ class Pedigree {  // src/pedigree.rs:44-45
   // comparison (DMatrix::from, :210-261) runs on the MI355X, on 2-bit codes packed straight from the site records
   // (abn_pairwise_divergence_packed); same bits either way.
   static std::pair<Pedigree, double> build(const std::string& nodelist, const std::string& edgelist,
-                                           double posterior_max_filter, bool gpu_pairwise = false);
+                                           double posterior_max_filter, bool gpu_pairwise = false,
+                                           bool device_parse = false);  // the methylome files through abn_sites_parse
   // ... for many (nodelist, edgelist) pairs at once (the windows of src/cli/metaprofile.rs:50-72): with gpu_pairwise ONE
   // abn_pairwise_divergence_windows_packed call per batch of entries with the same number of samples, on 2-bit codes
   // packed straight from the site records.  A batch ends at kBuildManyCodeBytes of PACKED codes per call (four sites per
@@ -348,7 +349,8 @@ class Pedigree {  // src/pedigree.rs:44-45
   static constexpr size_t kBuildManyCodeBytes = (size_t)1 << 30;
   static constexpr size_t kBuildManySiteBytes = (size_t)1 << 30;
   static std::vector<Built> build_many(const std::vector<std::pair<std::string, std::string>>& lists,
-                                       double posterior_max_filter, bool gpu_pairwise = false);
+                                       double posterior_max_filter, bool gpu_pairwise = false,
+                                       bool device_parse = false);
 };
 struct Pedigree::Built {
   Pedigree pedigree;
@@ -449,6 +451,7 @@ struct Args {  // arguments::AlphaBeta, src/arguments.rs:93-114
   std::string edges = "./edgelist.txt", nodes = "./nodelist.txt";
   double posterior_max_filter = 0.99;
   std::string output = ".";
+  bool device_parse = false;  // --parse device: the methylome files through abn_sites_parse (not in the reference)
 };
 
 struct RunResult {
@@ -499,7 +502,8 @@ namespace alphabeta {
 // src/alphabeta.rs:23-59
 inline RunResult run(const Args& args) {
   std::printf("Building pedigree...\n");
-  auto [pedigree, p0uu] = Pedigree::build(args.nodes, args.edges, args.posterior_max_filter, /*gpu_pairwise=*/true);
+  auto [pedigree, p0uu] = Pedigree::build(args.nodes, args.edges, args.posterior_max_filter, /*gpu_pairwise=*/true,
+                                          args.device_parse);
   return run_on_pedigree(std::move(pedigree), p0uu, args.iterations, args.output);
 }
 }  // namespace alphabeta

@@ -1,6 +1,6 @@
 // `alphabeta` command-line tool: same flags, console output and output files as the reference binary
 // (src/cli/alphabeta.rs:8-38, src/arguments.rs:93-152), running the ABneutral path on an MI355X through
-// libabneutral_hip.so.  Extra flags (not in the reference): --seed, --device(s), --lanes, --strict-order, and
+// libabneutral_hip.so.  Extra flags (not in the reference): --seed, --device(s), --lanes, --strict-order, --parse, and
 // --pedigree FILE --p0uu X to start from an existing pedigree file instead of nodelist/edgelist.
 #include <cstdlib>
 #include <cstring>
@@ -29,12 +29,14 @@ static void usage() {
       "                                 (src/structs.rs:206-213): bit-equal to a reference-order CPU run, ~1.5x the time\n"
       "      --pedigree <FILE>          use this pedigree file (src/pedigree.rs:62-79 format) instead of building one\n"
       "      --p0uu <X>                 proportion of unmethylated sites at G0 (required with --pedigree)\n"
+      "      --parse <host|device>      where the methylome files are parsed; the same output files [default: device]\n"
       "  -h, --help                     Print help\n"
       "  -V, --version                  Print version");
 }
 
 int main(int argc, char** argv) {
   Args args;
+  args.device_parse = true;  // measured: docs/experiments.md, "Device parsing"
   bool edges_given = false, nodes_given = false;
   std::string ped_file;
   double p0uu_given = -1.0;
@@ -70,6 +72,14 @@ int main(int argc, char** argv) {
     else if (a == "--strict-order") strict_order = true;
     else if (a == "--pedigree") ped_file = val();
     else if (a == "--p0uu") p0uu_given = std::strtod(val().c_str(), nullptr);
+    else if (a == "--parse") {
+      const std::string where = val();
+      if (where != "host" && where != "device") {
+        std::fprintf(stderr, "error: --parse expects host or device\n");
+        return 2;
+      }
+      args.device_parse = where == "device";
+    }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (a == "-V" || a == "--version") { std::puts("alphabeta 0.2.1 (MI355X ABneutral path)"); return 0; }
     else {

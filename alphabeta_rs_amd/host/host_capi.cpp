@@ -1,7 +1,9 @@
 // Tiny C shim over the C++ host layer so that the Python tests can call Pedigree::build / from_file /
 // to_file and the number formatter without a GPU.  Not part of the product ABI (include/abneutral.h).
+#include <chrono>
 #include <cstring>
 
+#include "../csrc/abn_parse.hpp"
 #include "../csrc/abn_route.hpp"
 #include "alphabeta.hpp"
 
@@ -166,6 +168,146 @@ long long abh_choose_genes(const char* annotation, long long alen, const char* m
   std::memcpy(code, s.code.data(), n);
   std::memcpy(level, s.level.data(), 8 * n);
   return (long long)n;
+}
+// ---- the methylome line parser: the host's (parse_site_full) and the one the device shares (csrc/abn_parse.hpp), for
+// tests/test_parse_cpu.py and tests/test_parse_gpu.py
+// parse_sites_host of a text from line `skip_lines` on -> per site (capacity cap): line, chromosome, start, end, strand,
+// posteriormax, status, meth_lvl; *n_warnings = the invalid-status warnings it would have printed.  Returns the number of
+// sites, -1 when they do not fit
+long long abh_parse_sites(const char* text, long long len, long long skip_lines, long long cap, long long* line,
+                          int* chromosome, unsigned* start, unsigned* end, unsigned char* strand, double* posteriormax,
+                          unsigned char* status, double* meth_lvl, long long* n_warnings) {
+  std::string warnings;
+  std::vector<int64_t> lines;
+  alphabeta::detail::diag_sink() = &warnings;
+  const auto sites = alphabeta::windows::parse_sites_host(std::string(text, (size_t)len), (size_t)skip_lines, &lines);
+  alphabeta::detail::diag_sink() = nullptr;
+  if (n_warnings) *n_warnings = (long long)std::count(warnings.begin(), warnings.end(), '\n');
+  if ((long long)sites.size() > cap) return -1;
+  for (size_t i = 0; i < sites.size(); ++i) {
+    line[i] = lines[i];
+    chromosome[i] = sites[i].chromosome;
+    start[i] = sites[i].start;
+    end[i] = sites[i].end;
+    strand[i] = (unsigned char)sites[i].strand;
+    posteriormax[i] = sites[i].posteriormax;
+    status[i] = (unsigned char)sites[i].status_numeric;
+    meth_lvl[i] = sites[i].meth_lvl;
+  }
+  return (long long)sites.size();
+}
+// abn::abn_parse_f64 of one token -> 0 value (in *value), 1 rejected, 2 deferred
+int abh_parse_f64_token(const char* token, long long len, double* value) {
+  const unsigned char* p = (const unsigned char*)token;
+  return abn::abn_parse_f64(p, p + len, *value);
+}
+// abn::abn_parse_line of every line of a text from line `skip_lines` on, as the device walks it (a line per '\n', a last
+// line without one, the '\r' trimmed) -> cls[line - skip_lines] = 0 no site, 1 site, 2 deferred (capacity cap lines), and
+// per site in file order: u6 = chromosome, start, end, strand, status, status_flag; d2 = posteriormax, meth_lvl; its line
+// in site_line.  Returns the number of lines classified, -1 when they do not fit
+long long abh_classify_text(const char* text, long long len, long long skip_lines, long long cap, unsigned char* cls,
+                            long long* site_line, unsigned* u6, double* d2, long long* n_sites) {
+  const unsigned char* t = (const unsigned char*)text;
+  long long li = 0, out = 0, ns = 0;
+  for (long long b = 0; b < len; ++li) {
+    long long e = b;
+    while (e < len && t[e] != '\n') ++e;
+    if (li >= skip_lines) {
+      if (out >= cap) return -1;
+      abn::ParsedSite s{};
+      const int c = abn::abn_parse_line(t + b, abn::abn_line_trim(t + b, t + e), s);
+      cls[out++] = (unsigned char)c;
+      if (c == abn::kLineSite) {
+        site_line[ns] = li;
+        const unsigned u[6] = {(unsigned)s.chromosome, s.start, s.end, s.strand, s.status, s.status_flag};
+        std::memcpy(u6 + 6 * ns, u, sizeof u);
+        d2[2 * ns] = s.posteriormax;
+        d2[2 * ns + 1] = s.meth_lvl;
+        ++ns;
+      }
+    }
+    b = e + 1;
+  }
+  *n_sites = ns;
+  return out;
+}
+// parse_sites_device of a text on the default device (slab_bytes as abn_sites_params) -> the arrays of abh_parse_sites;
+// warnings (capacity wcap) = what it printed.  Returns the number of sites, -1: they do not fit, -2: the call threw
+long long abh_parse_sites_device(const char* text, long long len, long long skip_lines, long long slab_bytes,
+                                 long long cap, long long* line, int* chromosome, unsigned* start, unsigned* end,
+                                 unsigned char* strand, double* posteriormax, unsigned char* status, double* meth_lvl,
+                                 char* warnings_out, long long wcap) {
+  try {
+    std::string warnings;
+    std::vector<int64_t> lines;
+    alphabeta::detail::diag_sink() = &warnings;
+    std::vector<alphabeta::windows::FullSite> sites;
+    try {
+      sites = alphabeta::windows::parse_sites_device(alphabeta::default_device(), std::string(text, (size_t)len),
+                                                     (size_t)skip_lines, slab_bytes, &lines);
+    } catch (...) {
+      alphabeta::detail::diag_sink() = nullptr;
+      throw;
+    }
+    alphabeta::detail::diag_sink() = nullptr;
+    if (warnings_out && wcap > 0) std::strncpy(warnings_out, warnings.c_str(), (size_t)wcap - 1), warnings_out[wcap - 1] = 0;
+    if ((long long)sites.size() > cap) return -1;
+    for (size_t i = 0; i < sites.size(); ++i) {
+      line[i] = lines[i];
+      chromosome[i] = sites[i].chromosome;
+      start[i] = sites[i].start;
+      end[i] = sites[i].end;
+      strand[i] = (unsigned char)sites[i].strand;
+      posteriormax[i] = sites[i].posteriormax;
+      status[i] = (unsigned char)sites[i].status_numeric;
+      meth_lvl[i] = sites[i].meth_lvl;
+    }
+    return (long long)sites.size();
+  } catch (const std::exception&) {
+    return -2;
+  }
+}
+// choose_genes_many against choose_genes_many_device on n methylome texts: 1 when every array of every sample is equal,
+// 0 when not, -1 when a call threw.  ms2 = the wall time of the two (host on `threads` threads; device with upload,
+// kernels, download, deferred merge and gene choice), for scripts/parse_ab.py
+int abh_choose_genes_many_ab(const char* annotation, long long alen, const char* const* texts, const long long* lens,
+                             int n, unsigned cutoff, double posterior_max_filter, int threads, int which,
+                             double* ms2) {
+  namespace w = alphabeta::windows;
+  try {
+    static std::vector<std::string> held;  // the texts of the last call, kept: the timed calls pass n = 0
+    static w::Genome genome;
+    if (n > 0) {
+      held.clear();
+      for (int i = 0; i < n; ++i) held.emplace_back(texts[i], (size_t)lens[i]);
+      genome = w::parse_annotation(std::string(annotation, (size_t)alen));
+    }
+    const w::GeneRule rule{cutoff, false};
+    auto now = []() { return std::chrono::steady_clock::now(); };
+    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    std::vector<w::SampleSites> host, dev;
+    if (which & 1) {
+      const auto t0 = now();
+      host = w::choose_genes_many(held, genome, rule, posterior_max_filter, (size_t)threads);
+      ms2[0] = ms(t0, now());
+    }
+    if (which & 2) {
+      const auto t0 = now();
+      dev = w::choose_genes_many_device(alphabeta::default_device(), held, genome, rule, posterior_max_filter);
+      ms2[1] = ms(t0, now());
+    }
+    if (which != 3) return 1;
+    for (size_t s = 0; s < held.size(); ++s) {
+      const auto &a = host[s], &b = dev[s];
+      if (a.pos != b.pos || a.gene_start != b.gene_start || a.gene_end != b.gene_end || a.flags != b.flags ||
+          a.code != b.code || a.level.size() != b.level.size() ||
+          (!a.level.empty() && std::memcmp(a.level.data(), b.level.data(), 8 * a.level.size()) != 0))
+        return 0;
+    }
+    return 1;
+  } catch (const std::exception&) {
+    return -1;
+  }
 }
 // window_params -> out3 = the window counts of upstream, gene, downstream (Windows::new)
 void abh_window_counts(unsigned cutoff, unsigned step, unsigned size, int absolute, unsigned max_gene_length, int* out3) {

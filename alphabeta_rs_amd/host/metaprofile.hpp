@@ -38,6 +38,7 @@ struct WindowArgs {  // the fields of arguments::Windows (src/arguments.rs:6-62)
   std::string nodes, edges;       // the one nodelist / edgelist of every window (arguments::AlphaBeta)
   bool cutoff_gene_length = false;
   bool invert = false;            // refused
+  bool device_parse = false;      // --parse device: the methylome files through abn_sites_parse (not in the reference)
 };
 
 struct WindowResult {
@@ -82,7 +83,7 @@ inline Output alphabeta_multiple(const WindowArgs& args, uint32_t max_gene_lengt
       region_of.push_back(region.first);
     }
   }
-  std::vector<Pedigree::Built> built = Pedigree::build_many(lists, args.posterior_max_filter, /*gpu_pairwise=*/true);
+  std::vector<Pedigree::Built> built = Pedigree::build_many(lists, args.posterior_max_filter, /*gpu_pairwise=*/true, args.device_parse);
   for (size_t index = 0; index < built.size(); ++index) {
     Pedigree::Built& b = built[index];
     std::fputs(b.diagnostics.c_str(), stdout);  // where the per-window build printed them: before the window's outcome
@@ -297,8 +298,10 @@ inline Extraction extract_in_memory(const WindowArgs& args) {
   {
     std::vector<std::string> texts;
     for (const auto& name : ex.names) texts.push_back(detail::read_file((fs::path(args.methylome) / name).string(), "methylome"));
-    samples = windows::choose_genes_many(texts, genome, windows::GeneRule{args.cutoff, args.cutoff_gene_length},
-                                         args.posterior_max_filter);
+    const windows::GeneRule rule{args.cutoff, args.cutoff_gene_length};
+    samples = args.device_parse
+                  ? windows::choose_genes_many_device(default_device(), texts, genome, rule, args.posterior_max_filter)
+                  : windows::choose_genes_many(texts, genome, rule, args.posterior_max_filter);
   }
   ex.handle = std::make_unique<windows::Handle>(default_device(), ex.params, samples);
   const windows::Handle& h = *ex.handle;

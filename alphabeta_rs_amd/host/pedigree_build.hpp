@@ -134,7 +134,13 @@ struct Inputs {
   }
 };
 
-inline Inputs read_inputs(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter) {
+// the sites of a methylome text, every line read (src/pedigree.rs:147-163), parsed on the device: defined in
+// windows_extract.hpp on windows::parse_sites_device
+inline std::vector<Site> parse_sites_device_reduced(const std::string& text);
+
+// device_parse: the methylome files are parsed by abn_sites_parse instead of the getline loop; the same sites
+inline Inputs read_inputs(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
+                          bool device_parse = false) {
   Inputs in;
   const std::string nodes_txt = read_file(nodelist, "nodelist"), edges_txt = read_file(edgelist, "edgelist");
   // :98-117
@@ -171,11 +177,17 @@ inline Inputs read_inputs(const std::string& nodelist, const std::string& edgeli
   for (auto& node : nodes) {
     std::ifstream f(node.file);
     if (!f) throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " + node.file);
-    std::string line;
-    while (std::getline(f, line)) {
-      if (!line.empty() && line.back() == '\r') line.pop_back();
-      Site s;
-      if (parse_site(line, s)) node.sites.push_back(s);
+    if (device_parse) {
+      std::ostringstream ss;
+      ss << f.rdbuf();
+      node.sites = parse_sites_device_reduced(ss.str());
+    } else {
+      std::string line;
+      while (std::getline(f, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        Site s;
+        if (parse_site(line, s)) node.sites.push_back(s);
+      }
     }
     double sum = 0.0;
     size_t cnt = 0;
@@ -374,9 +386,10 @@ inline Pedigree convert(const Inputs& in, const std::vector<double>& dm) {
 }  // namespace detail
 
 inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, const std::string& edgelist,
-                                                   double posterior_max_filter, bool gpu_pairwise) {
+                                                   double posterior_max_filter, bool gpu_pairwise,
+                                                   bool device_parse) {
   using namespace detail;
-  const Inputs in = read_inputs(nodelist, edgelist, posterior_max_filter);
+  const Inputs in = read_inputs(nodelist, edgelist, posterior_max_filter, device_parse);
   const size_t nn = in.nodes.size();
   std::vector<double> dm;
   if (gpu_pairwise && in.same_len() && nn >= 2) {
@@ -407,7 +420,8 @@ inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, 
 // kBuildManySiteBytes, and what is left at the end; entries are never reordered.  Host memory: those site records, one
 // call's packed matrix, and the graphs.
 inline std::vector<Pedigree::Built> Pedigree::build_many(const std::vector<std::pair<std::string, std::string>>& lists,
-                                                         double posterior_max_filter, bool gpu_pairwise) {
+                                                         double posterior_max_filter, bool gpu_pairwise,
+                                                         bool device_parse) {
   using namespace detail;
   const size_t W = lists.size();
   std::vector<Built> out(W);
@@ -456,7 +470,7 @@ inline std::vector<Pedigree::Built> Pedigree::build_many(const std::vector<std::
     diag_sink() = &out[w].diagnostics;
     bool waits = false;
     try {
-      in[w] = read_inputs(lists[w].first, lists[w].second, posterior_max_filter);
+      in[w] = read_inputs(lists[w].first, lists[w].second, posterior_max_filter, device_parse);
       alive[w] = 1;
       const size_t nn = in[w].nodes.size();
       if (gpu_pairwise && in[w].same_len() && nn >= 2) {

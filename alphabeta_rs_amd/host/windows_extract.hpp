@@ -4,7 +4,8 @@
 // gene choice — place_in_windows, the per-window site lists, the packed matrix, the folds — runs on the device
 // (abn_windows_*, csrc/abn_windows.hpp).  The gene choice is a serial dependence of a few integer compares per site (the
 // last_gene cache), so it stays here, one methylome per thread.  Integer arithmetic wraps as the reference's release
-// build does.  Plain C++, no device.
+// build does.  The line parse also runs on the device (parse_sites_device over abn_sites_parse, csrc/abn_parse.hpp):
+// the same FullSite sequence, fed to the same gene choice.
 #pragma once
 
 #include <thread>
@@ -137,6 +138,82 @@ inline bool parse_site_full(const std::string& line, FullSite& out) {
   return false;
 }
 
+// The sites of a methylome text in file order — the lines from skip_lines on that from_methylome_file_line accepts
+// (src/windows.rs:303-306 skips the header row, src/pedigree.rs:147-163 skips nothing) — parsed on the host.
+// line_numbers (nullable): every site's line, counted from 0 in the text.
+inline std::vector<FullSite> parse_sites_host(const std::string& text, size_t skip_lines = 1,
+                                              std::vector<int64_t>* line_numbers = nullptr) {
+  std::vector<FullSite> out;
+  const auto lines = lines_of(text);
+  for (size_t li = skip_lines; li < lines.size(); ++li) {
+    FullSite s;
+    if (!parse_site_full(lines[li], s)) continue;
+    out.push_back(s);
+    if (line_numbers) line_numbers->push_back((int64_t)li);
+  }
+  return out;
+}
+
+// ... parsed on the device (abn_sites_parse): exactly the sequence parse_sites_host yields.  The records the device
+// accepted are merged by line number with the lines it deferred (an f64 field it cannot be certain of, a line beyond its
+// staging limit), each decided here by parse_site_full; the invalid-status warnings are printed in file order.
+inline std::vector<FullSite> parse_sites_device(Device& dev, const std::string& text, size_t skip_lines = 1,
+                                                int64_t slab_bytes = 0, std::vector<int64_t>* line_numbers = nullptr) {
+  abn_sites_params p{};
+  p.slab_bytes = slab_bytes;
+  p.skip_lines = (int32_t)skip_lines;
+  abn_sites* h = nullptr;
+  dev.check(abn_sites_parse(dev.get(), text.data(), (int64_t)text.size(), &p, &h), "abn_sites_parse");
+  struct Guard {
+    abn_sites* h;
+    ~Guard() { abn_sites_destroy(h); }
+  } guard{h};
+  int64_t n = 0, nd = 0;
+  abn_sites_info(h, &n, &nd, nullptr, nullptr);
+  std::vector<int64_t> line((size_t)n), dline((size_t)nd), doff((size_t)nd), dlen((size_t)nd);
+  std::vector<int32_t> chrom((size_t)n);
+  std::vector<uint32_t> start((size_t)n), end((size_t)n);
+  std::vector<uint8_t> strand((size_t)n), status((size_t)n), flag((size_t)n);
+  std::vector<double> pm((size_t)n), ml((size_t)n);
+  abn_sites_fetch(h, line.data(), chrom.data(), start.data(), end.data(), strand.data(), pm.data(), status.data(),
+                  flag.data(), ml.data());
+  abn_sites_deferred(h, dline.data(), doff.data(), dlen.data());
+  // a flagged record's warning names the status byte: that line is read again here, through an index of the text's line
+  // begins made when the first such record turns up
+  std::vector<size_t> begins;
+  auto warn = [&](int64_t l) {
+    if (begins.empty()) {
+      begins.push_back(0);
+      for (const char* q = text.data(); (q = (const char*)std::memchr(q, '\n', (size_t)(text.data() + text.size() - q)));)
+        begins.push_back((size_t)(++q - text.data()));
+    }
+    const size_t b = begins[(size_t)l], e = (size_t)l + 1 < begins.size() ? begins[(size_t)l + 1] - 1 : text.size();
+    std::string s = text.substr(b, e - b);
+    if (!s.empty() && s.back() == '\r') s.pop_back();
+    FullSite again;
+    parse_site_full(s, again);
+  };
+  std::vector<FullSite> out;
+  out.reserve((size_t)n);
+  size_t i = 0, j = 0;
+  while (i < (size_t)n || j < (size_t)nd) {
+    if (j == (size_t)nd || (i < (size_t)n && line[i] < dline[j])) {
+      if (flag[i]) warn(line[i]);
+      out.push_back(FullSite{chrom[i], start[i], end[i], (Strand)strand[i], pm[i], status[i], ml[i]});
+      if (line_numbers) line_numbers->push_back(line[i]);
+      ++i;
+    } else {
+      FullSite s;
+      if (parse_site_full(text.substr((size_t)doff[j], (size_t)dlen[j]), s)) {
+        out.push_back(s);
+        if (line_numbers) line_numbers->push_back(dline[j]);
+      }
+      ++j;
+    }
+  }
+  return out;
+}
+
 struct GeneRule {  // the two arguments is_in_gene and find_gene read
   uint32_t cutoff = 2048;
   bool cutoff_gene_length = false;
@@ -185,8 +262,21 @@ struct SampleSites {
   size_t size() const { return pos.size(); }
 };
 
+// One step of the loop of Windows::extract (src/windows.rs:325-338) up to the call of place_in_windows: a site keeps the
+// previous site's gene while is_in_gene holds.
+inline void choose_gene(const FullSite& s, const Gene*& last, const Genome& genome, const GeneRule& rule,
+                        double posterior_max_filter, SampleSites& out) {
+  if (!last || !is_in_gene(s, *last, rule)) last = find_gene(s, genome, rule);
+  out.pos.push_back(s.start);
+  out.gene_start.push_back(last ? last->start : 0);
+  out.gene_end.push_back(last ? last->end : 0);
+  out.flags.push_back((uint8_t)((s.strand == Antisense ? 1u : 0u) | (last ? 2u : 0u)));
+  out.code.push_back((uint8_t)(s.status_numeric | (s.posteriormax < posterior_max_filter ? 0x80u : 0u)));
+  out.level.push_back(s.meth_lvl);
+}
+
 // The loop of Windows::extract (src/windows.rs:303-338) up to the call of place_in_windows: the header row is skipped
-// (`lines.skip(1)`), a line that is no site is passed over, a site keeps the previous site's gene while is_in_gene holds.
+// (`lines.skip(1)`), a line that is no site is passed over.
 inline SampleSites choose_genes(const std::string& methylome_text, const Genome& genome, const GeneRule& rule,
                                 double posterior_max_filter) {
   SampleSites out;
@@ -195,14 +285,16 @@ inline SampleSites choose_genes(const std::string& methylome_text, const Genome&
   for (size_t li = 1; li < lines.size(); ++li) {
     FullSite s;
     if (!parse_site_full(lines[li], s)) continue;
-    if (!last || !is_in_gene(s, *last, rule)) last = find_gene(s, genome, rule);
-    out.pos.push_back(s.start);
-    out.gene_start.push_back(last ? last->start : 0);
-    out.gene_end.push_back(last ? last->end : 0);
-    out.flags.push_back((uint8_t)((s.strand == Antisense ? 1u : 0u) | (last ? 2u : 0u)));
-    out.code.push_back((uint8_t)(s.status_numeric | (s.posteriormax < posterior_max_filter ? 0x80u : 0u)));
-    out.level.push_back(s.meth_lvl);
+    choose_gene(s, last, genome, rule, posterior_max_filter, out);
   }
+  return out;
+}
+// ... on the sites already parsed (parse_sites_device, parse_sites_host), in file order
+inline SampleSites choose_genes(const std::vector<FullSite>& sites, const Genome& genome, const GeneRule& rule,
+                                double posterior_max_filter) {
+  SampleSites out;
+  const Gene* last = nullptr;
+  for (const FullSite& s : sites) choose_gene(s, last, genome, rule, posterior_max_filter, out);
   return out;
 }
 
@@ -233,6 +325,30 @@ inline std::vector<SampleSites> choose_genes_many(const std::vector<std::string>
   for (size_t t = 1; t < nt; ++t) pool.emplace_back(work);
   work();
   for (auto& t : pool) t.join();
+  return out;
+}
+
+// ... with the texts parsed on the device, one after the other on the calling thread (a context serves one call at a
+// time); every text's gene choice runs on a thread of its own while the next text is parsed
+inline std::vector<SampleSites> choose_genes_many_device(Device& dev, const std::vector<std::string>& texts,
+                                                         const Genome& genome, const GeneRule& rule,
+                                                         double posterior_max_filter) {
+  std::vector<SampleSites> out(texts.size());
+  std::vector<std::vector<FullSite>> sites(texts.size());
+  std::vector<std::thread> pool;
+  struct Join {
+    std::vector<std::thread>& pool;
+    ~Join() {
+      for (auto& t : pool) t.join();
+    }
+  } join{pool};
+  for (size_t i = 0; i < texts.size(); ++i) {
+    sites[i] = parse_sites_device(dev, texts[i]);
+    pool.emplace_back([&, i]() {
+      out[i] = choose_genes(sites[i], genome, rule, posterior_max_filter);
+      std::vector<FullSite>().swap(sites[i]);
+    });
+  }
   return out;
 }
 
@@ -283,4 +399,13 @@ class Handle {
 };
 
 }  // namespace windows
+
+namespace detail {
+inline std::vector<Site> parse_sites_device_reduced(const std::string& text) {
+  std::vector<Site> out;
+  for (const auto& s : windows::parse_sites_device(default_device(), text, /*skip_lines=*/0))
+    out.push_back(Site{s.posteriormax, s.status_numeric, s.meth_lvl});
+  return out;
+}
+}  // namespace detail
 }  // namespace alphabeta

@@ -352,6 +352,44 @@ int abn_windows_packed_device_ptr(abn_windows* h, void** dev_ptr);
  * [W x pairs], any may be NULL; a ragged or empty window: diff = both = 0, dvalue = NaN.  n_samples < 2: nothing written. */
 int abn_windows_pairwise(abn_windows* h, uint64_t* diff, uint64_t* both, double* dvalue);
 
+/* ------------------------------------------------------------------ methylome text -> site records
+ * MethylationSite::from_methylome_file_line (src/methylation_site.rs:146-362, without --invert) for every line of a
+ * methylome file's text, on the device: a line index (the '\n' bytes, BufRead::lines), a lane per line parsing from LDS,
+ * a stable compaction.  Lines are numbered from 0 in the file (the header row is line 0).  A line is a site, no site, or
+ * DEFERRED: the device gives an f64 field (posteriormax, meth_lvl) a value only where one IEEE operation is certain to
+ * give str::parse::<f64>'s bits — [sign] digits [.] digits [e [sign] digits], at most 19 significant digits, their
+ * integer at most 2^53, a decimal exponent within +-22 — and a line with any other such token that could still be a site
+ * (inf, nan, 20 digits, 1e30 ...), or a line longer than 16 KiB, is handed back for the caller to parse on the host. */
+typedef struct abn_sites abn_sites;
+typedef struct abn_sites_params {
+  int64_t slab_bytes;  /* the text is parsed in slabs of at most this many bytes, cut at line ends (a longer line is a
+                          slab of its own); bounds the device memory of a call.  0: 64 MiB; at most 1 GiB */
+  int32_t skip_lines;  /* leading lines not parsed: 1 for the loop of Windows::extract (`lines.skip(1)`,
+                          src/windows.rs:303-306), 0 for that of Pedigree::build (src/pedigree.rs:147-163) */
+  int32_t reserved;    /* 0 */
+} abn_sites_params;
+/* Replaces the line loops of Windows::extract (src/windows.rs:303-338) and Pedigree::build (src/pedigree.rs:147-163)
+ * up to and including from_methylome_file_line (src/methylation_site.rs:146-362).  text: n_bytes bytes of HOST memory
+ * (no terminator needed; "\n" or "\r\n" ends a line, a last line without one is a line).  params NULL: slab_bytes 0,
+ * skip_lines 1.  The results are on the host when the call returns; *out holds them until abn_sites_destroy.
+ * ABN_ERR_INVALID_ARG: null pointers, n_bytes < 0, slab_bytes outside [0, 2^30], skip_lines < 0, a line of over 2 GiB. */
+int abn_sites_parse(abn_ctx* ctx, const char* text, int64_t n_bytes, const abn_sites_params* params, abn_sites** out);
+int abn_sites_destroy(abn_sites* h);
+/* the counts behind src/windows.rs:303-338: accepted sites, deferred lines, lines of the text (skipped ones included);
+ * kernel_ms = the HIP-event time of the call's kernels, summed over the slabs.  Any pointer may be NULL */
+int abn_sites_info(const abn_sites* h, int64_t* n_sites, int64_t* n_deferred, int64_t* n_lines, double* kernel_ms);
+/* The accepted sites in file order, [n_sites] each, any may be NULL — the fields of MethylationSite
+ * (src/methylation_site.rs:32-45) the extraction and the pedigree build read: line; chromosome (Numbered(n) = n,
+ * Mitochondrial = 256, Chloroplast = 257, src/methylation_site.rs:48-68); start, end; strand (0 Sense, 1 Antisense,
+ * 2 Unknown); posteriormax; status (U 0, I 1, M 2, src/methylation_site.rs:130-136); status_flag (1: the status byte
+ * is none of M, I, U and was parsed as U — the reference prints a warning there, src/methylation_site.rs:107-112);
+ * meth_lvl */
+int abn_sites_fetch(const abn_sites* h, int64_t* line, int32_t* chromosome, uint32_t* start, uint32_t* end,
+                    uint8_t* strand, double* posteriormax, uint8_t* status, uint8_t* status_flag, double* meth_lvl);
+/* The deferred lines in file order, [n_deferred] each, any may be NULL: line, the offset of its first byte in text, its
+ * length without the line end — to be decided by the host's from_methylome_file_line (src/methylation_site.rs:146-362) */
+int abn_sites_deferred(const abn_sites* h, int64_t* line, int64_t* offset, int64_t* length);
+
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
  * src/cli/metaprofile.rs:50-72, where every window shares nodelist/edgelist), S starts and B bootstraps
