@@ -13,7 +13,9 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libabneutral_hip.so"
-SOURCES = [CSRC / "abn_api.hip", CSRC / "abn_pairwise.hip", CSRC / "abn_multi.hip", CSRC / "abn_sites.hip",
+# the one list of the library's sources: scripts/flag_variants.py and scripts/stamps.py build from it too
+SOURCES = [CSRC / "abn_api.hip", CSRC / "abn_pairwise.hip", CSRC / "abn_windows.hip", CSRC / "abn_analyze.hip",
+           CSRC / "abn_multi.hip", CSRC / "abn_sites.hip",
            CSRC / "abn_pack.cpp"]  # host-only: the packed code format (also built alone under the host sanitizers)
 DEPS = [*sorted(CSRC.glob("*.hpp")), CSRC / "abn_philox.h", PKG.parent / "include" / "abneutral.h"]
 HIPCC_FLAGS = [

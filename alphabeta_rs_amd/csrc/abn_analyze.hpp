@@ -1,6 +1,6 @@
 // RawAnalysis::analyze (src/analysis.rs:50-98) for every window of a device-resident bootstrap table in one launch:
 // raw[W x B x 7] -> out[W x 32] (mean[8], sd[8], ci_lo[8], ci_hi[8]) and first_bad[W], every number with the bits of
-// abn_analyze (abn_pairwise.hip) on that window's table.  DESIGN.md §4 "Analysis".
+// abn_analyze (abn_analyze.hip) on that window's table.  DESIGN.md §4 "Analysis".
 //
 // One workgroup of four wavefronts per (window, output column); the wavefronts never wait for one another until the one
 // barrier at the end, each has a job of its own:

@@ -40,7 +40,7 @@ ABN_HOST_DEVICE inline double abn_order_key_value(uint64_t key) {
   return x;
 }
 
-// QuantileExt::quantile_axis_mut with Linear (src/analysis.rs:60-97; abn_analyze, csrc/abn_pairwise.hip): quantile q of
+// QuantileExt::quantile_axis_mut with Linear (src/analysis.rs:60-97; abn_analyze, csrc/abn_analyze.hip): quantile q of
 // n_boot values reads the ascending order statistics lo = floor(fi) and hi = ceil(fi), fi = q (n_boot - 1), and
 // interpolates with frac = fi - trunc(fi): s[lo] + frac * (s[hi] - s[lo]).  hi is lo or lo + 1.
 struct QuantileRank {

@@ -1,5 +1,5 @@
-// The device code of the fit path (abn_api.hip includes this; the pairwise scan of abn_pairwise.hip has its own header,
-// abn_pairwise_mx.hpp).
+// The device code of the fit path (abn_api.hip includes this; the pairwise scans of abn_pairwise.hip, the window
+// placement of abn_windows.hip and the analysis of abn_analyze.hip have headers of their own).
 #pragma once
 #include "abn_common.hpp"
 #include "abn_fit_kernel.hpp"

@@ -1,5 +1,6 @@
-// Host-side infrastructure shared by the translation units of libabneutral_hip.so (abn_api.hip, abn_pairwise.hip): the
-// context, its device-buffer pool, error reporting.  Not part of the C-ABI (include/abneutral.h is).
+// Host-side infrastructure shared by the translation units of libabneutral_hip.so (abn_api.hip, abn_pairwise.hip,
+// abn_windows.hip, abn_analyze.hip, abn_sites.hip): the context, its device-buffer pool, error reporting, the kernel_ms
+// timer.  Not part of the C-ABI (include/abneutral.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -132,9 +133,62 @@ struct DevBuf {
   size_t bytes() const { return n * sizeof(T); }
 };
 
+// The two HIP events around a call's kernels (kernel_ms): created when the time is first wanted, destroyed on every way
+// out.
+struct EventPair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+  ~EventPair() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  // in front of the kernels; nothing where the time is not wanted
+  int begin(abn_ctx* c, bool wanted) {
+    if (!wanted) return ABN_OK;
+    if (!e0) HIPCHK(c, hipEventCreate(&e0));
+    if (!e1) HIPCHK(c, hipEventCreate(&e1));
+    HIPCHK(c, hipEventRecord(e0, c->stream));
+    return ABN_OK;
+  }
+  // behind them: waits for the kernels and writes the milliseconds since begin; nothing for a null kernel_ms
+  int end(abn_ctx* c, double* kernel_ms) {
+    if (!kernel_ms) return ABN_OK;
+    HIPCHK(c, hipEventRecord(e1, c->stream));
+    HIPCHK(c, hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
+    *kernel_ms = ms;
+    return ABN_OK;
+  }
+};
+
+// The tail of a host entry of the pairwise scans: the three outputs on the device — only those the caller wants; the
+// scans take null outputs — around scan(ddiff, dboth, ddvalue), then to the host, and the stream synchronised.
+template <class Scan>
+int pairwise_to_host(abn_ctx* c, size_t count, uint64_t* diff, uint64_t* both, double* dvalue, Scan scan) {
+  DevBuf<unsigned long long> ddiff, dboth;
+  DevBuf<double> ddv;
+  if (diff) HIPCHK(c, ddiff.alloc(count));
+  if (both) HIPCHK(c, dboth.alloc(count));
+  if (dvalue) HIPCHK(c, ddv.alloc(count));
+  if (int rc = scan(ddiff.p, dboth.p, ddv.p)) return rc;
+  if (diff) HIPCHK(c, hipMemcpyAsync(diff, ddiff.p, ddiff.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (both) HIPCHK(c, hipMemcpyAsync(both, dboth.p, dboth.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (dvalue) HIPCHK(c, hipMemcpyAsync(dvalue, ddv.p, ddv.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ABN_OK;
+}
+
 namespace abn {
-// abn_pairwise.hip, for abn_plan_analyze (abn_api.hip): the analysis (abn_analyze.hpp) of a device-resident table
+// abn_analyze.hip, for abn_plan_analyze (abn_api.hip): the analysis (abn_analyze.hpp) of a device-resident table
 // raw[W x B x 7] on the context's stream, results to the host; returns after completion, ABN_ERR_NO_FINITE_FIT as
 // abn_analyze_batch.
 int analyze_device_table(abn_ctx* c, const double* draw, int32_t W, int64_t B, double* out, int32_t* first_bad);
+// abn_pairwise.hip, for abn_windows_pairwise (abn_windows.hip): abn_pairwise_divergence_windows_packed_dev behind its
+// null check of the context.
+int pairwise_windows_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                                int32_t n_windows, void* dev_diff, void* dev_both, void* dev_dvalue, double* kernel_ms);
 }  // namespace abn

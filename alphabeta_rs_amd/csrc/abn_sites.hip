@@ -20,17 +20,6 @@ struct abn_sites {
 
 namespace {
 
-struct ParseEvents {  // the two HIP events around a call's kernels (kernel_ms), destroyed on every way out
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ParseEvents() = default;
-  ParseEvents(const ParseEvents&) = delete;
-  ParseEvents& operator=(const ParseEvents&) = delete;
-  ~ParseEvents() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-};
-
 struct RecordBufs {
   DevBuf<uint32_t> line, meta, start, end, dline, doffset, dlength;
   DevBuf<double> pm, ml;
@@ -63,7 +52,7 @@ size_t slab_end(const char* text, size_t n, size_t from, size_t slab_bytes) {
 
 // one slab [text, text + n): its lines from skip on, appended to h; line numbers and offsets are the file's
 int parse_slab(abn_ctx* c, abn_sites* h, const char* text, size_t n, int64_t skip, int64_t line0, int64_t byte0,
-               ParseEvents& ev) {
+               EventPair& ev) {
   const uint32_t n_pieces = (uint32_t)((n + kParsePieceBytes - 1) / kParsePieceBytes);
   const uint32_t n_blocks = (n_pieces + kParseThreads - 1) / kParseThreads;
   DevBuf<uint4> dtext;
@@ -72,20 +61,21 @@ int parse_slab(abn_ctx* c, abn_sites* h, const char* text, size_t n, int64_t ski
   HIPCHK(c, dblock.alloc((size_t)n_blocks + 1));
   HIPCHK(c, hipMemsetAsync((char*)dtext.p + (size_t)(n_pieces - 1) * kParsePieceBytes, 0, kParsePieceBytes, c->stream));
   HIPCHK(c, hipMemcpyAsync(dtext.p, text, n, hipMemcpyHostToDevice, c->stream));
-  float ms = 0.f;
-  auto elapsed = [&]() {  // after a synchronise
-    if (hipEventElapsedTime(&ms, ev.e0, ev.e1) == hipSuccess) h->kernel_ms += (double)ms;
+  auto timed = [&]() {  // behind the kernels of a phase: their time, added to the handle's
+    double ms = 0.0;
+    const int rc = ev.end(c, &ms);
+    h->kernel_ms += ms;
+    return rc;
   };
-  HIPCHK(c, hipEventRecord(ev.e0, c->stream));
+  if (int rc = ev.begin(c, true)) return rc;
   hipLaunchKernelGGL(abn_parse_count_kernel, dim3(n_blocks), dim3(kParseThreads), 0, c->stream, dtext.p, n_pieces, dblock.p);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(abn_parse_scan_kernel, dim3(1), dim3(kParseScanThreads), 0, c->stream, dblock.p, n_blocks, 0u);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(ev.e1, c->stream));
+  if (int rc = timed()) return rc;
   uint32_t n_newlines = 0;
   HIPCHK(c, hipMemcpyAsync(&n_newlines, dblock.p + n_blocks, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  elapsed();
   const uint32_t n_lines = n_newlines + (text[n - 1] != '\n' ? 1u : 0u);
   h->n_lines += n_lines;
   if ((int64_t)n_lines <= skip) return ABN_OK;
@@ -95,7 +85,7 @@ int parse_slab(abn_ctx* c, abn_sites* h, const char* text, size_t n, int64_t ski
   HIPCHK(c, dbegin.alloc((size_t)n_newlines + 1));
   HIPCHK(c, dcount.alloc((size_t)2 * stride));
   HIPCHK(c, run.alloc((size_t)n_runs * kParseRun, (size_t)n_runs * kParseRun));
-  HIPCHK(c, hipEventRecord(ev.e0, c->stream));
+  if (int rc = ev.begin(c, true)) return rc;
   hipLaunchKernelGGL(abn_parse_index_kernel, dim3(n_blocks), dim3(kParseThreads), 0, c->stream, dtext.p, n_pieces,
                      dblock.p, dbegin.p);
   HIPCHK(c, hipGetLastError());
@@ -104,19 +94,18 @@ int parse_slab(abn_ctx* c, abn_sites* h, const char* text, size_t n, int64_t ski
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(abn_parse_scan_kernel, dim3(2), dim3(kParseScanThreads), 0, c->stream, dcount.p, n_runs, stride);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(ev.e1, c->stream));
+  if (int rc = timed()) return rc;
   uint32_t n_rec = 0, n_def = 0;
   HIPCHK(c, hipMemcpyAsync(&n_rec, dcount.p + n_runs, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(&n_def, dcount.p + stride + n_runs, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  elapsed();
   if (n_rec == 0 && n_def == 0) return ABN_OK;
   HIPCHK(c, out.alloc(n_rec, n_def));
-  HIPCHK(c, hipEventRecord(ev.e0, c->stream));
+  if (int rc = ev.begin(c, true)) return rc;
   hipLaunchKernelGGL(abn_parse_compact_kernel, dim3(n_runs), dim3(kParseThreads), 0, c->stream, run.records(),
                      run.deferred(), dcount.p, stride, out.records(), out.deferred());
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(ev.e1, c->stream));
+  if (int rc = timed()) return rc;
   std::vector<uint32_t> line(n_rec), meta(n_rec), start(n_rec), end(n_rec), dline(n_def), doff(n_def), dlen(n_def);
   const size_t at = h->line.size(), dat = h->dline.size();
   h->posteriormax.resize(at + n_rec);
@@ -135,7 +124,6 @@ int parse_slab(abn_ctx* c, abn_sites* h, const char* text, size_t n, int64_t ski
     HIPCHK(c, hipMemcpyAsync(dlen.data(), out.dlength.p, 4 * (size_t)n_def, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  elapsed();
   h->line.resize(at + n_rec);
   h->chromosome.resize(at + n_rec);
   h->start.insert(h->start.end(), start.begin(), start.end());
@@ -176,9 +164,7 @@ extern "C" int abn_sites_parse(abn_ctx* c, const char* text, int64_t n_bytes, co
   PoolScope pool_scope(c);
   std::unique_ptr<abn_sites> h(new (std::nothrow) abn_sites);
   if (!h) return set_err(c, ABN_ERR_HIP, "out of host memory");
-  ParseEvents ev;
-  HIPCHK(c, hipEventCreate(&ev.e0));
-  HIPCHK(c, hipEventCreate(&ev.e1));
+  EventPair ev;
   try {
     const size_t n = (size_t)n_bytes;
     for (size_t from = 0; from < n;) {

@@ -1,0 +1,252 @@
+// abn_windows_*: the window-placement handle.  Kernels: abn_windows.hpp; the scan of the placed windows
+// (abn_windows_pairwise) is abn_pairwise.hip's.
+#include "abn_host.hpp"
+#include "abn_windows.hpp"
+
+using namespace abn;
+
+// ------------------------------------------------------------------------------------------------
+// window placement: methylome sites -> the packed matrix of the windows scan (src/windows.rs:287-343 behind the gene choice,
+// src/methylation_site.rs:423-490; kernels: abn_windows.hpp)
+// ------------------------------------------------------------------------------------------------
+struct abn_windows {
+  abn_ctx* ctx = nullptr;
+  int n = 0, W = 0;
+  long long stride = 0;  // bytes per row of `packed`; the rows hold 4 * stride fields
+  std::vector<int64_t> begin, end, count, kept;
+  std::vector<int32_t> ragged;
+  std::vector<double> level_sum, level_sum_kept;
+  DevBuf<uint8_t> packed;  // [n x stride], device-resident between calls
+};
+
+static int windows_build(abn_windows* h, const abn_windows_params* p, const int64_t* site_offset, const uint32_t* pos,
+                         const uint32_t* gene_start, const uint32_t* gene_end, const uint8_t* flags, const uint8_t* code,
+                         const double* level) {
+  abn_ctx* c = h->ctx;
+  const int n = h->n, W = h->W;
+  const size_t S = (size_t)site_offset[n], nW = (size_t)n * (size_t)W;
+  WinParams P{};
+  P.cutoff = (double)p->cutoff;
+  P.step = (double)p->step;
+  P.size = (double)p->size;
+  P.absolute = p->absolute ? 1 : 0;
+  P.n_region[0] = p->n_upstream;
+  P.n_region[1] = p->n_gene;
+  P.n_region[2] = p->n_downstream;
+  P.first[0] = 0;
+  P.first[1] = p->n_upstream;
+  P.first[2] = p->n_upstream + p->n_gene;
+  P.W = W;
+  // the rank blocks: kWinBlockSites sites each, never across two samples
+  std::vector<WinBlock> blocks;
+  std::vector<int> block0((size_t)n + 1, 0);
+  std::vector<long long> site0((size_t)n + 1);
+  for (int s = 0; s <= n; ++s) site0[(size_t)s] = site_offset[s];
+  for (int s = 0; s < n; ++s) {
+    for (long long b = site_offset[s]; b < site_offset[s + 1]; b += kWinBlockSites)
+      blocks.push_back(WinBlock{b, (int)std::min<long long>(kWinBlockSites, site_offset[s + 1] - b), s});
+    block0[(size_t)s + 1] = (int)blocks.size();
+  }
+  const size_t NB = blocks.size();
+  if ((double)NB * (double)std::max(W, 1) * 4.0 > 8e9)
+    return set_err(c, ABN_ERR_INVALID_ARG, "too many sites x windows for one handle");
+
+  DevBuf<uint32_t> dpos, dgs, dge, dhist, dlist;
+  DevBuf<uint8_t> dflags, dcode;
+  DevBuf<double> dlevel, dsum, dsumk;
+  DevBuf<int2> dspan;
+  DevBuf<WinBlock> dblocks;
+  DevBuf<int> dblock0;
+  DevBuf<long long> dsite0, dcount, dlistoff, dcol0, dkept;
+  HIPCHK(c, dpos.alloc(S));
+  HIPCHK(c, dgs.alloc(S));
+  HIPCHK(c, dge.alloc(S));
+  HIPCHK(c, dflags.alloc(S));
+  HIPCHK(c, dcode.alloc(std::max<size_t>(S, 1)));
+  HIPCHK(c, dlevel.alloc(std::max<size_t>(S, 1)));
+  HIPCHK(c, dspan.alloc(S));
+  HIPCHK(c, dblocks.alloc(NB));
+  HIPCHK(c, dblock0.alloc((size_t)n + 1));
+  HIPCHK(c, dsite0.alloc((size_t)n + 1));
+  HIPCHK(c, dhist.alloc(std::max<size_t>(NB * (size_t)W, 1)));
+  HIPCHK(c, dcount.alloc(std::max<size_t>(nW, 1)));
+  if (S > 0) {
+    HIPCHK(c, hipMemcpyAsync(dpos.p, pos, S * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dgs.p, gene_start, S * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dge.p, gene_end, S * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dflags.p, flags, S, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dcode.p, code, S, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dlevel.p, level, S * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dblocks.p, blocks.data(), dblocks.bytes(), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(dblock0.p, block0.data(), dblock0.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dsite0.p, site0.data(), dsite0.bytes(), hipMemcpyHostToDevice, c->stream));
+  auto grid_of = [](size_t items) { return dim3((unsigned)((items + kWinThreads - 1) / kWinThreads)); };
+  if (S > 0 && W > 0) {
+    hipLaunchKernelGGL(abn_windows_place_kernel, grid_of(S), dim3(kWinThreads), 0, c->stream, dpos.p, dgs.p, dge.p,
+                       dflags.p, (long long)S, P, dspan.p);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(abn_windows_rank_kernel<0>, dim3((unsigned)NB), dim3(kWinThreads), 0, c->stream, dspan.p,
+                       dblocks.p, (int)NB, W, dhist.p, (const long long*)nullptr, dsite0.p, (uint32_t*)nullptr);
+    HIPCHK(c, hipGetLastError());
+  }
+  h->count.assign(nW, 0);
+  if (nW > 0) {
+    hipLaunchKernelGGL(abn_windows_scan_kernel, grid_of(nW), dim3(kWinThreads), 0, c->stream, dhist.p, dblock0.p,
+                       (int)NB, n, W, dcount.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h->count.data(), dcount.p, nW * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+
+  // the layout of layout_packed_call (host/pedigree_build.hpp): a window's columns begin at a multiple of 256 sites and
+  // take ceil(sites / 256) * 64 bytes of every row; a ragged window takes none; at least one super-step per row
+  std::vector<long long> list_off(nW + 1, 0), col0((size_t)W + 1, 0);
+  for (size_t i = 0; i < nW; ++i) list_off[i + 1] = list_off[i] + h->count[i];
+  h->begin.assign((size_t)W, 0);
+  h->end.assign((size_t)W, 0);
+  h->ragged.assign((size_t)W, 0);
+  long long off = 0;  // bytes into the row
+  for (int w = 0; w < W; ++w) {
+    const long long L0 = h->count[(size_t)w];
+    for (int s = 1; s < n; ++s)
+      if (h->count[(size_t)s * W + w] != L0) h->ragged[(size_t)w] = 1;
+    const long long L = h->ragged[(size_t)w] ? 0 : L0;
+    col0[(size_t)w] = off / 4;
+    h->begin[(size_t)w] = 4 * off;
+    h->end[(size_t)w] = 4 * off + L;
+    off += (L + 255) / 256 * 64;
+  }
+  col0[(size_t)W] = off / 4;
+  h->stride = std::max<long long>(off, 64);
+  const size_t row_dwords = (size_t)h->stride / 4, total = (size_t)list_off[nW];
+  if (((size_t)n * row_dwords + kWinThreads - 1) / kWinThreads > 0x7fffffffull)
+    return set_err(c, ABN_ERR_INVALID_ARG, "packed matrix too large for one handle");
+
+  HIPCHK(c, dlistoff.alloc(nW + 1));
+  HIPCHK(c, dcol0.alloc((size_t)W + 1));
+  HIPCHK(c, dlist.alloc(std::max<size_t>(total, 1)));
+  HIPCHK(c, dsum.alloc(std::max<size_t>(nW, 1)));
+  HIPCHK(c, dsumk.alloc(std::max<size_t>(nW, 1)));
+  HIPCHK(c, dkept.alloc(std::max<size_t>(nW, 1)));
+  HIPCHK(c, h->packed.alloc((size_t)n * (size_t)h->stride));
+  HIPCHK(c, hipMemcpyAsync(dlistoff.p, list_off.data(), dlistoff.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dcol0.p, col0.data(), dcol0.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (S > 0 && W > 0) {
+    hipLaunchKernelGGL(abn_windows_rank_kernel<1>, dim3((unsigned)NB), dim3(kWinThreads), 0, c->stream, dspan.p,
+                       dblocks.p, (int)NB, W, dhist.p, dlistoff.p, dsite0.p, dlist.p);
+    HIPCHK(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(abn_windows_pack_kernel, grid_of((size_t)n * row_dwords), dim3(kWinThreads), 0, c->stream, dcode.p,
+                     dlist.p, dlistoff.p, dcount.p, dsite0.p, dcol0.p, W, n, (long long)row_dwords,
+                     (uint32_t*)h->packed.p);
+  HIPCHK(c, hipGetLastError());
+  h->level_sum.assign(nW, 0.0);
+  h->level_sum_kept.assign(nW, 0.0);
+  h->kept.assign(nW, 0);
+  if (nW > 0) {
+    hipLaunchKernelGGL(abn_windows_sums_kernel, grid_of(nW), dim3(kWinThreads), 0, c->stream, dcode.p, dlevel.p, dlist.p,
+                       dlistoff.p, dcount.p, dsite0.p, W, n, dsum.p, dsumk.p, dkept.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h->level_sum.data(), dsum.p, nW * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h->level_sum_kept.data(), dsumk.p, nW * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h->kept.data(), dkept.p, nW * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the staging buffers are freed on return
+  return ABN_OK;
+}
+
+extern "C" int abn_windows_create(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, const int64_t* site_offset,
+                                  const uint32_t* pos, const uint32_t* gene_start, const uint32_t* gene_end,
+                                  const uint8_t* flags, const uint8_t* code, const double* level, abn_windows** out) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  if (out) *out = nullptr;
+  if (!p || !out || !site_offset || n_samples <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (n_samples > 65535) return set_err(c, ABN_ERR_INVALID_ARG, "too many samples");
+  if (p->step == 0) return set_err(c, ABN_ERR_INVALID_ARG, "window step 0");
+  if (p->n_upstream < 0 || p->n_gene < 0 || p->n_downstream < 0 ||
+      (long long)p->n_upstream + p->n_gene + p->n_downstream > (1 << 20))
+    return set_err(c, ABN_ERR_INVALID_ARG, "window counts");
+  if (site_offset[0] != 0) return set_err(c, ABN_ERR_INVALID_ARG, "site_offset[0] is not 0");
+  for (int s = 0; s < n_samples; ++s)
+    if (site_offset[s + 1] < site_offset[s] || site_offset[s + 1] - site_offset[s] > 0xffffffffLL)
+      return set_err(c, ABN_ERR_INVALID_ARG, "site_offset is not ascending, or a sample of 2^32 sites or more");
+  if (site_offset[n_samples] > 0 && (!pos || !gene_start || !gene_end || !flags || !code || !level))
+    return set_err(c, ABN_ERR_INVALID_ARG, "null site arrays");
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  std::unique_ptr<abn_windows> h(new (std::nothrow) abn_windows);
+  if (!h) return set_err(c, ABN_ERR_HIP, "out of host memory");
+  h->ctx = c;
+  h->n = n_samples;
+  h->W = p->n_upstream + p->n_gene + p->n_downstream;
+  try {
+    if (int rc = windows_build(h.get(), p, site_offset, pos, gene_start, gene_end, flags, code, level)) return rc;
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+  *out = h.release();
+  return ABN_OK;
+}
+
+extern "C" int abn_windows_destroy(abn_windows* h) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  (void)hipSetDevice(h->ctx->device);
+  delete h;
+  return ABN_OK;
+}
+
+extern "C" int abn_windows_info(const abn_windows* h, int32_t* n_windows, int64_t* row_stride, int64_t* n_sites) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (n_windows) *n_windows = h->W;
+  if (row_stride) *row_stride = h->stride;
+  if (n_sites) *n_sites = 4 * h->stride;
+  return ABN_OK;
+}
+
+extern "C" int abn_windows_stats(const abn_windows* h, int64_t* count, double* level_sum, double* level_sum_kept,
+                                 int64_t* kept) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (count) std::copy(h->count.begin(), h->count.end(), count);
+  if (level_sum) std::copy(h->level_sum.begin(), h->level_sum.end(), level_sum);
+  if (level_sum_kept) std::copy(h->level_sum_kept.begin(), h->level_sum_kept.end(), level_sum_kept);
+  if (kept) std::copy(h->kept.begin(), h->kept.end(), kept);
+  return ABN_OK;
+}
+
+extern "C" int abn_windows_layout(const abn_windows* h, int64_t* begin, int64_t* end, int32_t* ragged) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (begin) std::copy(h->begin.begin(), h->begin.end(), begin);
+  if (end) std::copy(h->end.begin(), h->end.end(), end);
+  if (ragged) std::copy(h->ragged.begin(), h->ragged.end(), ragged);
+  return ABN_OK;
+}
+
+extern "C" int abn_windows_packed_device_ptr(abn_windows* h, void** dev_ptr) {
+  if (!h || !dev_ptr) return ABN_ERR_INVALID_ARG;
+  *dev_ptr = h->packed.p;
+  return ABN_OK;
+}
+
+extern "C" int abn_windows_packed(abn_windows* h, uint8_t* host_out) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = h->ctx;
+  if (!host_out) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(host_out, h->packed.p, h->packed.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ABN_OK;
+}
+
+extern "C" int abn_windows_pairwise(abn_windows* h, uint64_t* diff, uint64_t* both, double* dvalue) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = h->ctx;
+  const size_t n = (size_t)h->n, nout = n * (n - 1) / 2 * (size_t)h->W;
+  if (nout == 0) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  return pairwise_to_host(c, nout, diff, both, dvalue, [&](auto* dd, auto* db, auto* dv) {
+    return pairwise_windows_packed_dev(c, h->packed.p, h->n, 4 * h->stride, h->stride, h->begin.data(), h->end.data(),
+                                       h->W, dd, db, dv, nullptr);
+  });
+}

@@ -5,6 +5,8 @@ build (ABNEUTRAL_HIP_LIB points the package at the variant).  Usage:
 import json, os, subprocess, sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+from alphabeta_rs_amd import build as B
 OUT = ROOT / "gpurun_out"
 OUT.mkdir(exist_ok=True)
 args = sys.argv[1:]
@@ -20,10 +22,7 @@ if args and args[0] == "--":
     args = args[1:]
 for i, flags in enumerate(args or [""]):
     lib = OUT / f"libabn_flags_{i}.so"
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC",
-           "-shared", "-ldl", *flags.split(), "-o", str(lib), str(ROOT / "alphabeta_rs_amd/csrc/abn_api.hip"),
-           str(ROOT / "alphabeta_rs_amd/csrc/abn_pairwise.hip"), str(ROOT / "alphabeta_rs_amd/csrc/abn_multi.hip"),
-                str(ROOT / "alphabeta_rs_amd/csrc/abn_pack.cpp")]
+    cmd = [B.hipcc_path(), *B.HIPCC_FLAGS, *flags.split(), "-o", str(lib), *map(str, B.SOURCES)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode:
         print(f"[{flags}] build failed: {r.stderr[-400:]}")

@@ -55,7 +55,7 @@ static int key_order() {
   return 0;
 }
 
-// ---- (2) lo / hi / frac == the formula of abn_analyze (csrc/abn_pairwise.hip), written out again here
+// ---- (2) lo / hi / frac == the formula of abn_analyze (csrc/abn_analyze.hip), written out again here
 static int quantile_formula() {
   std::vector<long long> Bs;
   for (long long B = 1; B <= 300; ++B) Bs.push_back(B);
