@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "abn_windows_create", "abn_windows_destroy", "abn_windows_info", "abn_windows_stats", "abn_windows_layout",
     "abn_windows_packed", "abn_windows_packed_device_ptr", "abn_windows_pairwise",
     "abn_sites_parse", "abn_sites_destroy", "abn_sites_info", "abn_sites_fetch", "abn_sites_deferred",
+    "abn_genes_create", "abn_genes_destroy", "abn_genes_choose", "abn_genes_choose_dev", "abn_windows_create_sites",
 ]
 
 
@@ -88,6 +89,14 @@ class WindowsParams(C.Structure):
         ("n_upstream", C.c_int32),
         ("n_gene", C.c_int32),
         ("n_downstream", C.c_int32),
+    ]
+
+
+class GeneRule(C.Structure):
+    """abn_gene_rule: the two arguments is_in_gene and find_gene read"""
+    _fields_ = [
+        ("cutoff", C.c_uint32),
+        ("cutoff_gene_length", C.c_int32),
     ]
 
 
@@ -186,6 +195,13 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_sites_info.argtypes = [vp, i64p, i64p, i64p, dp]
     L.abn_sites_fetch.argtypes = [vp, i64p, C.POINTER(C.c_int32), u32p, u32p, u8p, dp, u8p, u8p, dp]
     L.abn_sites_deferred.argtypes = [vp, i64p, i64p, i64p]
+    i32p = C.POINTER(C.c_int32)
+    L.abn_genes_create.argtypes = [vp, C.c_int32, i32p, i32p, i64p, u32p, u32p, u8p, C.POINTER(vp)]
+    L.abn_genes_destroy.argtypes = [vp]
+    L.abn_genes_choose.argtypes = [vp, C.POINTER(GeneRule), C.c_int32, i64p, i32p, u32p, u32p, u8p, u32p, u32p, u8p, dp]
+    L.abn_genes_choose_dev.argtypes = [vp, C.POINTER(GeneRule), C.c_int32, i64p, vp, vp, vp, vp, vp, vp, vp, dp]
+    L.abn_windows_create_sites.argtypes = [vp, C.POINTER(WindowsParams), vp, C.POINTER(GeneRule), C.c_int32, i64p, i32p,
+                                           u32p, u32p, u8p, u8p, dp, C.POINTER(vp)]
     L.abn_plan_create.argtypes = [vp, op, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                   C.POINTER(vp)]
     L.abn_plan_destroy.argtypes = [vp]
@@ -610,6 +626,38 @@ class Context:
         finally:
             self._L.abn_sites_destroy(h)
 
+    def choose_genes(self, genes: "Genes", site_offset, chromosome, start, end, strand, *, cutoff,
+                     cutoff_gene_length=False):
+        """The gene of every site (the loop of Windows::extract, src/windows.rs:325-338, with is_in_gene / find_gene and
+        the last_gene cache) for n_samples methylomes, on the device.  site_offset (n_samples + 1,) int64; per site
+        (concatenated over the samples, file order) chromosome int32, start, end uint32, strand uint8 (0 +, 1 -, 2
+        unknown).  Returns (gene_start, gene_end, flags, kernel_ms): what Windows(...) takes, and the three kernels' ms."""
+        off, u = _site_arrays(site_offset, chromosome, start, end, strand)
+        S = int(off[-1])
+        gs, ge, fl = np.zeros(S, dtype=np.uint32), np.zeros(S, dtype=np.uint32), np.zeros(S, dtype=np.uint8)
+        ms = np.zeros(3)
+        rule = GeneRule(cutoff, 1 if cutoff_gene_length else 0)
+        u8p = C.POINTER(C.c_uint8)
+        self._check(self._L.abn_genes_choose(genes._h, C.byref(rule), off.shape[0] - 1, off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             u[0].ctypes.data_as(C.POINTER(C.c_int32)), _u32p(u[1]), _u32p(u[2]),
+                                             u[3].ctypes.data_as(u8p), _u32p(gs), _u32p(ge), fl.ctypes.data_as(u8p), _dp(ms)))
+        return gs, ge, fl, ms
+
+    def choose_genes_dev(self, genes: "Genes", site_offset, chromosome_ptr: int, start_ptr: int, end_ptr: int,
+                         strand_ptr: int, gene_start_ptr: int, gene_end_ptr: int, flags_ptr: int, *, cutoff,
+                         cutoff_gene_length=False) -> np.ndarray:
+        """choose_genes on device-resident arrays (raw device pointers; site_offset stays a host array).  Returns the
+        three kernels' HIP-event ms."""
+        off = np.ascontiguousarray(site_offset, dtype=np.int64)
+        ms = np.zeros(3)
+        rule = GeneRule(cutoff, 1 if cutoff_gene_length else 0)
+        self._check(self._L.abn_genes_choose_dev(genes._h, C.byref(rule), off.shape[0] - 1,
+                                                 off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 *(C.c_void_p(p or None) for p in (chromosome_ptr, start_ptr, end_ptr,
+                                                                                   strand_ptr, gene_start_ptr,
+                                                                                   gene_end_ptr, flags_ptr)), _dp(ms)))
+        return ms
+
     # ---- (3) boot_model::run
     def boot_model_run(self, pedigree, model, pred, resid, p0uu, eqp, eqp_weight, n_boot, *,
                        options: Options | None = None):
@@ -739,6 +787,49 @@ class Plan:
         return {"starts": (KERNEL_NAMES.get(out[0], out[0]), out[1]), "boot": (KERNEL_NAMES.get(out[2], out[2]), out[3])}
 
 
+def _site_arrays(site_offset, chromosome, start, end, strand):
+    off = np.ascontiguousarray(site_offset, dtype=np.int64)
+    S = int(off[-1]) if off.shape[0] else 0
+    return off, [np.ascontiguousarray(a, dtype=t).reshape(S) for a, t in
+                 ((chromosome, np.int32), (start, np.uint32), (end, np.uint32), (strand, np.uint8))]
+
+
+class Genes:
+    """abn_genes: a gene annotation resident on the device.  lists = [(chromosome, kind, start, end, strand), ..]: the
+    genes of one chromosome (0..255, 256 = M, 257 = C) and kind (0 sense, 1 antisense, 2 combined: GenesByStrand,
+    src/genes.rs:127-163) as arrays, each list stably sorted by start as src/extract.rs:61-66 leaves it."""
+
+    def __init__(self, ctx: "Context", lists):
+        self.ctx = ctx
+        self._L = ctx._L
+        lists = list(lists)
+        chrom = np.array([l[0] for l in lists], dtype=np.int32)
+        kind = np.array([l[1] for l in lists], dtype=np.int32)
+        off = np.zeros(len(lists) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(l[2]) for l in lists])
+        cat = lambda k, t: np.ascontiguousarray(np.concatenate([np.asarray(l[k], dtype=t) for l in lists])
+                                                if lists else np.zeros(0, dtype=t))
+        start, end, strand = cat(2, np.uint32), cat(3, np.uint32), cat(4, np.uint8)
+        h = C.c_void_p()
+        i32p = C.POINTER(C.c_int32)
+        ctx._check(self._L.abn_genes_create(ctx._h, len(lists), chrom.ctypes.data_as(i32p), kind.ctypes.data_as(i32p),
+                                            off.ctypes.data_as(C.POINTER(C.c_int64)), _u32p(start), _u32p(end),
+                                            strand.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(h)))
+        self._h = h
+        self.n_genes = int(off[-1])
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.abn_genes_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Windows:
     """abn_windows: the sites of n_samples methylomes placed into metaprofile windows on the device
     (MethylationSite::place_in_windows, src/methylation_site.rs:423-490), device-resident as the 2-bit packed matrix of
@@ -768,6 +859,33 @@ class Windows:
         W, stride, ns = C.c_int32(), C.c_int64(), C.c_int64()
         ctx._check(self._L.abn_windows_info(h, C.byref(W), C.byref(stride), C.byref(ns)))
         self.W, self.row_stride, self.n_sites = W.value, stride.value, ns.value
+
+    @classmethod
+    def from_sites(cls, ctx: Context, genes: Genes, site_offset, chromosome, start, end, strand, code, level, *, cutoff,
+                   cutoff_gene_length=False, step, size, absolute, counts):
+        """The handle from the sites' own fields (chromosome int32, start, end uint32, strand uint8; code, level as
+        above): every site's gene is chosen on the device (Context.choose_genes) and handed to the placement there."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self._L = ctx._L
+        off, u = _site_arrays(site_offset, chromosome, start, end, strand)
+        self.n_samples = off.shape[0] - 1
+        S = int(off[-1]) if off.shape[0] else 0
+        co = np.ascontiguousarray(code, dtype=np.uint8).reshape(S)
+        lvl = _f64(level, (S,))
+        p = WindowsParams(cutoff, step, size, 1 if absolute else 0, *map(int, counts))
+        rule = GeneRule(cutoff, 1 if cutoff_gene_length else 0)
+        h = C.c_void_p()
+        u8p = C.POINTER(C.c_uint8)
+        ctx._check(self._L.abn_windows_create_sites(ctx._h, C.byref(p), genes._h, C.byref(rule), self.n_samples,
+                                                    off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    u[0].ctypes.data_as(C.POINTER(C.c_int32)), _u32p(u[1]), _u32p(u[2]),
+                                                    u[3].ctypes.data_as(u8p), co.ctypes.data_as(u8p), _dp(lvl), C.byref(h)))
+        self._h = h
+        W, stride, ns = C.c_int32(), C.c_int64(), C.c_int64()
+        ctx._check(self._L.abn_windows_info(h, C.byref(W), C.byref(stride), C.byref(ns)))
+        self.W, self.row_stride, self.n_sites = W.value, stride.value, ns.value
+        return self
 
     def close(self):
         if getattr(self, "_h", None):

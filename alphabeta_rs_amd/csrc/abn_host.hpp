@@ -1,6 +1,6 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (abn_api.hip, abn_pairwise.hip,
-// abn_windows.hip, abn_analyze.hip, abn_sites.hip): the context, its device-buffer pool, error reporting, the kernel_ms
-// timer.  Not part of the C-ABI (include/abneutral.h is).
+// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip): the context, its device-buffer pool, error reporting,
+// the kernel_ms timer.  Not part of the C-ABI (include/abneutral.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -191,4 +191,10 @@ int analyze_device_table(abn_ctx* c, const double* draw, int32_t W, int64_t B, d
 int pairwise_windows_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
                                 int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
                                 int32_t n_windows, void* dev_diff, void* dev_both, void* dev_dvalue, double* kernel_ms);
+// abn_genes.hip, for abn_windows_create_sites (abn_windows.hip): abn_genes_choose_dev behind its checks of the
+// arguments, and the context a genes handle belongs to.
+int genes_choose_dev(abn_genes* h, const abn_gene_rule* rule, int32_t n_samples, const int64_t* site_offset,
+                     const int32_t* dchrom, const uint32_t* dstart, const uint32_t* dend, const uint8_t* dstrand,
+                     uint32_t* dgene_start, uint32_t* dgene_end, uint8_t* dflags, double* kernel_ms);
+abn_ctx* genes_ctx(const abn_genes* h);
 }  // namespace abn

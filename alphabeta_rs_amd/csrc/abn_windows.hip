@@ -1,5 +1,5 @@
 // abn_windows_*: the window-placement handle.  Kernels: abn_windows.hpp; the scan of the placed windows
-// (abn_windows_pairwise) is abn_pairwise.hip's.
+// (abn_windows_pairwise) is abn_pairwise.hip's, the gene choice of abn_windows_create_sites abn_genes.hip's.
 #include "abn_host.hpp"
 #include "abn_windows.hpp"
 
@@ -19,9 +19,10 @@ struct abn_windows {
   DevBuf<uint8_t> packed;  // [n x stride], device-resident between calls
 };
 
-static int windows_build(abn_windows* h, const abn_windows_params* p, const int64_t* site_offset, const uint32_t* pos,
-                         const uint32_t* gene_start, const uint32_t* gene_end, const uint8_t* flags, const uint8_t* code,
-                         const double* level) {
+// The handle from DEVICE site arrays ([site_offset[n]] each; none is read when there are no sites): place, rank, pack, sum
+static int windows_build_dev(abn_windows* h, const abn_windows_params* p, const int64_t* site_offset, const uint32_t* dpos,
+                             const uint32_t* dgs, const uint32_t* dge, const uint8_t* dflags, const uint8_t* dcode,
+                             const double* dlevel) {
   abn_ctx* c = h->ctx;
   const int n = h->n, W = h->W;
   const size_t S = (size_t)site_offset[n], nW = (size_t)n * (size_t)W;
@@ -51,40 +52,25 @@ static int windows_build(abn_windows* h, const abn_windows_params* p, const int6
   if ((double)NB * (double)std::max(W, 1) * 4.0 > 8e9)
     return set_err(c, ABN_ERR_INVALID_ARG, "too many sites x windows for one handle");
 
-  DevBuf<uint32_t> dpos, dgs, dge, dhist, dlist;
-  DevBuf<uint8_t> dflags, dcode;
-  DevBuf<double> dlevel, dsum, dsumk;
+  DevBuf<uint32_t> dhist, dlist;
+  DevBuf<double> dsum, dsumk;
   DevBuf<int2> dspan;
   DevBuf<WinBlock> dblocks;
   DevBuf<int> dblock0;
   DevBuf<long long> dsite0, dcount, dlistoff, dcol0, dkept;
-  HIPCHK(c, dpos.alloc(S));
-  HIPCHK(c, dgs.alloc(S));
-  HIPCHK(c, dge.alloc(S));
-  HIPCHK(c, dflags.alloc(S));
-  HIPCHK(c, dcode.alloc(std::max<size_t>(S, 1)));
-  HIPCHK(c, dlevel.alloc(std::max<size_t>(S, 1)));
   HIPCHK(c, dspan.alloc(S));
   HIPCHK(c, dblocks.alloc(NB));
   HIPCHK(c, dblock0.alloc((size_t)n + 1));
   HIPCHK(c, dsite0.alloc((size_t)n + 1));
   HIPCHK(c, dhist.alloc(std::max<size_t>(NB * (size_t)W, 1)));
   HIPCHK(c, dcount.alloc(std::max<size_t>(nW, 1)));
-  if (S > 0) {
-    HIPCHK(c, hipMemcpyAsync(dpos.p, pos, S * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dgs.p, gene_start, S * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dge.p, gene_end, S * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dflags.p, flags, S, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dcode.p, code, S, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dlevel.p, level, S * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dblocks.p, blocks.data(), dblocks.bytes(), hipMemcpyHostToDevice, c->stream));
-  }
+  if (S > 0) HIPCHK(c, hipMemcpyAsync(dblocks.p, blocks.data(), dblocks.bytes(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(dblock0.p, block0.data(), dblock0.bytes(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(dsite0.p, site0.data(), dsite0.bytes(), hipMemcpyHostToDevice, c->stream));
   auto grid_of = [](size_t items) { return dim3((unsigned)((items + kWinThreads - 1) / kWinThreads)); };
   if (S > 0 && W > 0) {
-    hipLaunchKernelGGL(abn_windows_place_kernel, grid_of(S), dim3(kWinThreads), 0, c->stream, dpos.p, dgs.p, dge.p,
-                       dflags.p, (long long)S, P, dspan.p);
+    hipLaunchKernelGGL(abn_windows_place_kernel, grid_of(S), dim3(kWinThreads), 0, c->stream, dpos, dgs, dge,
+                       dflags, (long long)S, P, dspan.p);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(abn_windows_rank_kernel<0>, dim3((unsigned)NB), dim3(kWinThreads), 0, c->stream, dspan.p,
                        dblocks.p, (int)NB, W, dhist.p, (const long long*)nullptr, dsite0.p, (uint32_t*)nullptr);
@@ -137,7 +123,7 @@ static int windows_build(abn_windows* h, const abn_windows_params* p, const int6
                        dblocks.p, (int)NB, W, dhist.p, dlistoff.p, dsite0.p, dlist.p);
     HIPCHK(c, hipGetLastError());
   }
-  hipLaunchKernelGGL(abn_windows_pack_kernel, grid_of((size_t)n * row_dwords), dim3(kWinThreads), 0, c->stream, dcode.p,
+  hipLaunchKernelGGL(abn_windows_pack_kernel, grid_of((size_t)n * row_dwords), dim3(kWinThreads), 0, c->stream, dcode,
                      dlist.p, dlistoff.p, dcount.p, dsite0.p, dcol0.p, W, n, (long long)row_dwords,
                      (uint32_t*)h->packed.p);
   HIPCHK(c, hipGetLastError());
@@ -145,7 +131,7 @@ static int windows_build(abn_windows* h, const abn_windows_params* p, const int6
   h->level_sum_kept.assign(nW, 0.0);
   h->kept.assign(nW, 0);
   if (nW > 0) {
-    hipLaunchKernelGGL(abn_windows_sums_kernel, grid_of(nW), dim3(kWinThreads), 0, c->stream, dcode.p, dlevel.p, dlist.p,
+    hipLaunchKernelGGL(abn_windows_sums_kernel, grid_of(nW), dim3(kWinThreads), 0, c->stream, dcode, dlevel, dlist.p,
                        dlistoff.p, dcount.p, dsite0.p, W, n, dsum.p, dsumk.p, dkept.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h->level_sum.data(), dsum.p, nW * 8, hipMemcpyDeviceToHost, c->stream));
@@ -156,11 +142,68 @@ static int windows_build(abn_windows* h, const abn_windows_params* p, const int6
   return ABN_OK;
 }
 
-extern "C" int abn_windows_create(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, const int64_t* site_offset,
-                                  const uint32_t* pos, const uint32_t* gene_start, const uint32_t* gene_end,
-                                  const uint8_t* flags, const uint8_t* code, const double* level, abn_windows** out) {
-  if (!c) return ABN_ERR_INVALID_ARG;
-  if (out) *out = nullptr;
+// ... from HOST site arrays: the upload in front of windows_build_dev
+static int windows_build(abn_windows* h, const abn_windows_params* p, const int64_t* site_offset, const uint32_t* pos,
+                         const uint32_t* gene_start, const uint32_t* gene_end, const uint8_t* flags, const uint8_t* code,
+                         const double* level) {
+  abn_ctx* c = h->ctx;
+  const size_t S = (size_t)site_offset[h->n];
+  DevBuf<uint32_t> dpos, dgs, dge;
+  DevBuf<uint8_t> dflags, dcode;
+  DevBuf<double> dlevel;
+  HIPCHK(c, dpos.alloc(S));
+  HIPCHK(c, dgs.alloc(S));
+  HIPCHK(c, dge.alloc(S));
+  HIPCHK(c, dflags.alloc(S));
+  HIPCHK(c, dcode.alloc(std::max<size_t>(S, 1)));
+  HIPCHK(c, dlevel.alloc(std::max<size_t>(S, 1)));
+  if (S > 0) {
+    HIPCHK(c, hipMemcpyAsync(dpos.p, pos, S * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dgs.p, gene_start, S * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dge.p, gene_end, S * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dflags.p, flags, S, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dcode.p, code, S, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dlevel.p, level, S * 8, hipMemcpyHostToDevice, c->stream));
+  }
+  return windows_build_dev(h, p, site_offset, dpos.p, dgs.p, dge.p, dflags.p, dcode.p, dlevel.p);
+}
+
+// ... from HOST site fields with the gene of every site chosen on the device (abn_genes.hip) in between
+static int windows_build_sites(abn_windows* h, const abn_windows_params* p, abn_genes* genes, const abn_gene_rule* rule,
+                               const int64_t* site_offset, const int32_t* chromosome, const uint32_t* start,
+                               const uint32_t* end, const uint8_t* strand, const uint8_t* code, const double* level) {
+  abn_ctx* c = h->ctx;
+  const size_t S = (size_t)site_offset[h->n];
+  DevBuf<int32_t> dchrom;
+  DevBuf<uint32_t> dstart, dend, dgs, dge;
+  DevBuf<uint8_t> dstrand, dflags, dcode;
+  DevBuf<double> dlevel;
+  HIPCHK(c, dchrom.alloc(S));
+  HIPCHK(c, dstart.alloc(S));
+  HIPCHK(c, dend.alloc(S));
+  HIPCHK(c, dstrand.alloc(S));
+  HIPCHK(c, dgs.alloc(S));
+  HIPCHK(c, dge.alloc(S));
+  HIPCHK(c, dflags.alloc(S));
+  HIPCHK(c, dcode.alloc(std::max<size_t>(S, 1)));
+  HIPCHK(c, dlevel.alloc(std::max<size_t>(S, 1)));
+  if (S > 0) {
+    HIPCHK(c, hipMemcpyAsync(dchrom.p, chromosome, S * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dstart.p, start, S * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dend.p, end, S * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dstrand.p, strand, S, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dcode.p, code, S, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dlevel.p, level, S * 8, hipMemcpyHostToDevice, c->stream));
+  }
+  if (int rc = genes_choose_dev(genes, rule, h->n, site_offset, dchrom.p, dstart.p, dend.p, dstrand.p, dgs.p, dge.p,
+                                dflags.p, nullptr))
+    return rc;
+  return windows_build_dev(h, p, site_offset, dstart.p, dgs.p, dge.p, dflags.p, dcode.p, dlevel.p);
+}
+
+// the checks of abn_windows_create and abn_windows_create_sites on what they share
+static int windows_check(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, const int64_t* site_offset,
+                         abn_windows** out) {
   if (!p || !out || !site_offset || n_samples <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
   if (n_samples > 65535) return set_err(c, ABN_ERR_INVALID_ARG, "too many samples");
   if (p->step == 0) return set_err(c, ABN_ERR_INVALID_ARG, "window step 0");
@@ -171,8 +214,12 @@ extern "C" int abn_windows_create(abn_ctx* c, const abn_windows_params* p, int32
   for (int s = 0; s < n_samples; ++s)
     if (site_offset[s + 1] < site_offset[s] || site_offset[s + 1] - site_offset[s] > 0xffffffffLL)
       return set_err(c, ABN_ERR_INVALID_ARG, "site_offset is not ascending, or a sample of 2^32 sites or more");
-  if (site_offset[n_samples] > 0 && (!pos || !gene_start || !gene_end || !flags || !code || !level))
-    return set_err(c, ABN_ERR_INVALID_ARG, "null site arrays");
+  return ABN_OK;
+}
+
+// the handle around build(handle): created, built, handed out
+template <class Build>
+static int windows_make(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, abn_windows** out, Build build) {
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
   std::unique_ptr<abn_windows> h(new (std::nothrow) abn_windows);
@@ -181,12 +228,45 @@ extern "C" int abn_windows_create(abn_ctx* c, const abn_windows_params* p, int32
   h->n = n_samples;
   h->W = p->n_upstream + p->n_gene + p->n_downstream;
   try {
-    if (int rc = windows_build(h.get(), p, site_offset, pos, gene_start, gene_end, flags, code, level)) return rc;
+    if (int rc = build(h.get())) return rc;
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
   }
   *out = h.release();
   return ABN_OK;
+}
+
+extern "C" int abn_windows_create_sites(abn_ctx* c, const abn_windows_params* p, abn_genes* genes, const abn_gene_rule* rule,
+                                        int32_t n_samples, const int64_t* site_offset, const int32_t* chromosome,
+                                        const uint32_t* start, const uint32_t* end, const uint8_t* strand,
+                                        const uint8_t* code, const double* level, abn_windows** out) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  if (out) *out = nullptr;
+  if (int rc = windows_check(c, p, n_samples, site_offset, out)) return rc;
+  if (!genes || !rule) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (genes_ctx(genes) != c) return set_err(c, ABN_ERR_INVALID_ARG, "the genes belong to another context");
+  const int64_t S = site_offset[n_samples];
+  if (S > 0 && (!chromosome || !start || !end || !strand || !code || !level))
+    return set_err(c, ABN_ERR_INVALID_ARG, "null site arrays");
+  for (int64_t i = 0; i < S; ++i)
+    if (chromosome[i] < 0 || chromosome[i] >= 258 || strand[i] > 2)  // the table of abn_genes.hpp: 258 chromosome keys
+      return set_err(c, ABN_ERR_INVALID_ARG, "a site's chromosome is outside 0..257, or its strand above 2");
+  return windows_make(c, p, n_samples, out, [&](abn_windows* h) {
+    return windows_build_sites(h, p, genes, rule, site_offset, chromosome, start, end, strand, code, level);
+  });
+}
+
+extern "C" int abn_windows_create(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, const int64_t* site_offset,
+                                  const uint32_t* pos, const uint32_t* gene_start, const uint32_t* gene_end,
+                                  const uint8_t* flags, const uint8_t* code, const double* level, abn_windows** out) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  if (out) *out = nullptr;
+  if (int rc = windows_check(c, p, n_samples, site_offset, out)) return rc;
+  if (site_offset[n_samples] > 0 && (!pos || !gene_start || !gene_end || !flags || !code || !level))
+    return set_err(c, ABN_ERR_INVALID_ARG, "null site arrays");
+  return windows_make(c, p, n_samples, out, [&](abn_windows* h) {
+    return windows_build(h, p, site_offset, pos, gene_start, gene_end, flags, code, level);
+  });
 }
 
 extern "C" int abn_windows_destroy(abn_windows* h) {

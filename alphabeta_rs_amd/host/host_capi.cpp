@@ -2,7 +2,9 @@
 // to_file and the number formatter without a GPU.  Not part of the product ABI (include/abneutral.h).
 #include <chrono>
 #include <cstring>
+#include <memory>
 
+#include "../csrc/abn_genes.hpp"
 #include "../csrc/abn_parse.hpp"
 #include "../csrc/abn_route.hpp"
 #include "alphabeta.hpp"
@@ -305,6 +307,105 @@ int abh_choose_genes_many_ab(const char* annotation, long long alen, const char*
         return 0;
     }
     return 1;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+// ---- the gene choice in blocks (csrc/abn_genes.hpp), for tests/test_genes_cpu.py and scripts/genes_ab.py
+// The three phases the device runs, in their serial form on the host, with blocks of block_sites sites: n methylome texts
+// (the header row skipped) against an annotation text -> gene_start, gene_end, flags over all samples' sites (capacity cap)
+// and site_offset [n + 1].  Returns the number of sites, -1 when they do not fit, -2 for a block length outside 1..65534
+long long abh_choose_genes_blocked(const char* annotation, long long alen, const char* const* texts, const long long* lens,
+                                   int n, unsigned cutoff, int cutoff_gene_length, int block_sites, long long cap,
+                                   long long* site_offset, unsigned* gene_start, unsigned* gene_end, unsigned char* flags) {
+  namespace w = alphabeta::windows;
+  if (block_sites < 1 || block_sites > 65534) return -2;
+  const w::GeneLists l = w::flatten_genome(w::parse_annotation(std::string(annotation, (size_t)alen)));
+  std::vector<std::vector<w::FullSite>> samples;
+  for (int i = 0; i < n; ++i) samples.push_back(w::parse_sites_host(std::string(texts[i], (size_t)lens[i])));
+  const w::SiteArrays a = w::site_arrays(samples, 0.0);
+  const size_t S = a.start.size(), cells = (size_t)abn::kGeneChromosomes * abn::kGeneKinds;
+  for (int i = 0; i <= n; ++i) site_offset[i] = a.offset[(size_t)i];
+  if ((long long)S > cap) return -1;
+  std::vector<uint32_t> off(cells, 0), cnt(cells, 0);
+  std::vector<uint16_t> chrom(l.start.size());
+  for (size_t k = 0; k < l.list_kind.size(); ++k) {
+    const size_t cell = (size_t)l.list_chromosome[k] * abn::kGeneKinds + (size_t)l.list_kind[k];
+    off[cell] = (uint32_t)l.list_offset[k];
+    cnt[cell] = (uint32_t)(l.list_offset[k + 1] - l.list_offset[k]);
+    for (int64_t g = l.list_offset[k]; g < l.list_offset[k + 1]; ++g) chrom[(size_t)g] = (uint16_t)l.list_chromosome[k];
+  }
+  const abn::GeneTable T{off.data(), cnt.data(), chrom.data(), l.start.data(), l.end.data(), l.strand.data()};
+  const abn::GeneSites sites{a.chromosome.data(), a.start.data(), a.end.data(), a.strand.data()};
+  std::vector<uint32_t> F(S);
+  std::vector<uint16_t> next(S), last(S);
+  abn::genes_choose_blocked(sites, a.offset.data(), n, T, abn::GeneRule{cutoff, cutoff_gene_length}, block_sites, F.data(),
+                            next.data(), last.data(), gene_start, gene_end, flags);
+  return (long long)S;
+}
+// The two ways to a windows::Handle from parsed sites, on n methylome texts: choose_genes on `threads` threads and the
+// Handle of its arrays (which & 1), against the Handle that chooses on the device (which & 2).  which == 3: 1 when all
+// that the two handles report and their packed matrices are equal, 0 when not.  ms2 = the wall time of the two from the
+// FullSite vectors to the finished Handle; which & 4: kernel_ms3 = the three kernels' times of abn_genes_choose on the
+// same sites.  The texts are parsed (on the host) when n > 0 and kept: the timed calls pass n = 0.  -1: a call threw
+int abh_windows_handles_ab(const char* annotation, long long alen, const char* const* texts, const long long* lens, int n,
+                           unsigned cutoff, int cutoff_gene_length, double posterior_max_filter, unsigned step,
+                           unsigned size, int absolute, int threads, int which, double* ms2, double* kernel_ms3) {
+  namespace w = alphabeta::windows;
+  try {
+    static std::vector<std::vector<w::FullSite>> sites;
+    static w::Genome genome;
+    if (n > 0) {
+      std::vector<std::string> held;
+      for (int i = 0; i < n; ++i) held.emplace_back(texts[i], (size_t)lens[i]);
+      sites = w::parse_sites_many(held, nullptr, (size_t)threads);
+      genome = w::parse_annotation(std::string(annotation, (size_t)alen));
+    }
+    const w::GeneRule rule{cutoff, cutoff_gene_length != 0};
+    const abn_windows_params p =
+        w::window_params(cutoff, step, size, absolute != 0, absolute ? genome.max_gene_length : 100u);
+    alphabeta::Device& dev = alphabeta::default_device();
+    auto now = []() { return std::chrono::steady_clock::now(); };
+    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    std::unique_ptr<w::Handle> host, device;
+    if (which & 1) {
+      const auto t0 = now();
+      host = std::make_unique<w::Handle>(dev, p, w::choose_genes_many(sites, genome, rule, posterior_max_filter, (size_t)threads));
+      ms2[0] = ms(t0, now());
+    }
+    if (which & 2) {
+      const auto t0 = now();
+      device = std::make_unique<w::Handle>(dev, p, genome, rule, posterior_max_filter, sites);
+      ms2[1] = ms(t0, now());
+    }
+    if (which & 4) {
+      const w::GenesHandle genes(dev, genome);
+      const w::SiteArrays a = w::site_arrays(sites, posterior_max_filter);
+      std::vector<uint32_t> gs(a.start.size()), ge(a.start.size());
+      std::vector<uint8_t> fl(a.start.size());
+      const abn_gene_rule r{cutoff, cutoff_gene_length};
+      dev.check(abn_genes_choose(genes.get(), &r, (int32_t)sites.size(), a.offset.data(), a.chromosome.data(),
+                                 a.start.data(), a.end.data(), a.strand.data(), gs.data(), ge.data(), fl.data(), kernel_ms3),
+                "abn_genes_choose");
+    }
+    if ((which & 3) != 3) return 1;
+    auto same_bits = [](const std::vector<double>& x, const std::vector<double>& y) {
+      return x.size() == y.size() && (x.empty() || std::memcmp(x.data(), y.data(), 8 * x.size()) == 0);
+    };
+    if (host->count != device->count || host->kept != device->kept || host->ragged != device->ragged ||
+        !same_bits(host->level_sum, device->level_sum) || !same_bits(host->level_sum_kept, device->level_sum_kept))
+      return 0;
+    int64_t stride[2] = {0, 0};
+    abn_windows_info(host->get(), nullptr, &stride[0], nullptr);
+    abn_windows_info(device->get(), nullptr, &stride[1], nullptr);
+    if (stride[0] != stride[1]) return 0;
+    std::vector<uint8_t> pa(sites.size() * (size_t)stride[0]), pb(pa.size());
+    dev.check(abn_windows_packed(host->get(), pa.data()), "abn_windows_packed");
+    dev.check(abn_windows_packed(device->get(), pb.data()), "abn_windows_packed");
+    std::vector<int64_t> ba(host->n_windows()), ea(ba.size()), bb(ba.size()), eb(ba.size());
+    abn_windows_layout(host->get(), ba.data(), ea.data(), nullptr);
+    abn_windows_layout(device->get(), bb.data(), eb.data(), nullptr);
+    return pa == pb && ba == bb && ea == eb ? 1 : 0;
   } catch (const std::exception&) {
     return -1;
   }

@@ -39,6 +39,7 @@ struct WindowArgs {  // the fields of arguments::Windows (src/arguments.rs:6-62)
   bool cutoff_gene_length = false;
   bool invert = false;            // refused
   bool device_parse = false;      // --parse device: the methylome files through abn_sites_parse (not in the reference)
+  bool device_genes = false;      // --genes device: every site's gene through abn_windows_create_sites (abn_genes_*)
 };
 
 struct WindowResult {
@@ -254,8 +255,8 @@ inline detail::Inputs read_graph(const std::string& nodelist, const std::string&
   return in;
 }
 
-// src/extract.rs:17-155: parse the annotation and every methylome once, choose every site's gene on the host, place the
-// sites into windows on the device; write distribution_<name>, distributions.txt, steady_state_methylation.txt and
+// src/extract.rs:17-155: parse the annotation and every methylome once, choose every site's gene (on the host, or with
+// device_genes on the device), place the sites into windows on the device; write distribution_<name>, distributions.txt, steady_state_methylation.txt and
 // all_steady_state_methylation.txt (:112-151, src/windows.rs:130-176,245-257) into the output directory.
 inline Extraction extract_in_memory(const WindowArgs& args) {
   namespace fs = std::filesystem;
@@ -294,16 +295,24 @@ inline Extraction extract_in_memory(const WindowArgs& args) {
     std::printf("The maximum gene length is %u bp\n", ex.max_gene_length);
   }
   ex.params = windows::window_params(args.cutoff, step, args.window_size, args.absolute, ex.max_gene_length);
-  std::vector<windows::SampleSites> samples;
   {
     std::vector<std::string> texts;
     for (const auto& name : ex.names) texts.push_back(detail::read_file((fs::path(args.methylome) / name).string(), "methylome"));
     const windows::GeneRule rule{args.cutoff, args.cutoff_gene_length};
-    samples = args.device_parse
-                  ? windows::choose_genes_many_device(default_device(), texts, genome, rule, args.posterior_max_filter)
-                  : windows::choose_genes_many(texts, genome, rule, args.posterior_max_filter);
+    if (args.device_genes) {
+      // the parsed sites (with --parse device: the merged sequence, deferred lines decided here) go up once; the gene of
+      // every site is chosen there
+      const auto sites = windows::parse_sites_many(texts, args.device_parse ? &default_device() : nullptr);
+      std::vector<std::string>().swap(texts);
+      ex.handle = std::make_unique<windows::Handle>(default_device(), ex.params, genome, rule, args.posterior_max_filter, sites);
+    } else {
+      const std::vector<windows::SampleSites> samples =
+          args.device_parse
+              ? windows::choose_genes_many_device(default_device(), texts, genome, rule, args.posterior_max_filter)
+              : windows::choose_genes_many(texts, genome, rule, args.posterior_max_filter);
+      ex.handle = std::make_unique<windows::Handle>(default_device(), ex.params, samples);
+    }
   }
-  ex.handle = std::make_unique<windows::Handle>(default_device(), ex.params, samples);
   const windows::Handle& h = *ex.handle;
   const size_t n = h.n_samples(), W = h.n_windows();
   for (size_t w = 0; w < W; ++w) ex.distribution.push_back((int)h.count[w]);

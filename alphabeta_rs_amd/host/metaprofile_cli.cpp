@@ -15,6 +15,7 @@ using namespace alphabeta;
 int main(int argc, char** argv) {
   metaprofile::WindowArgs a;
   a.device_parse = true;  // measured: docs/experiments.md, "Device parsing"
+  a.device_genes = true;  // measured: docs/experiments.md, "Gene choice on the device"
   uint32_t max_gene_length = 0;
   std::string dist_file;
   uint64_t seed = 20260101ull;
@@ -55,13 +56,22 @@ int main(int argc, char** argv) {
       }
       a.device_parse = where == "device";
     }
+    else if (f == "--genes") {
+      const std::string where = val();
+      if (where != "host" && where != "device") {
+        std::fprintf(stderr, "error: --genes expects host or device\n");
+        return 2;
+      }
+      a.device_genes = where == "device";
+    }
     else if (f == "-h" || f == "--help") {
       std::puts("Usage: metaprofile_alphabeta -o <output-dir> [--name N] [-s step] [-w size] [-c cutoff] [-a]\n"
                 "       [--iterations 100] [--max-gene-length L] [--distribution FILE] [--seed S] [--device D]\n"
                 "       [--devices A,B,..]   windows sharded over several HIP devices, tables gathered with RCCL\n"
                 "       [--methylome DIR --genome FILE --nodes FILE --edges FILE [--cutoff-gene-length]]\n"
                 "                            extract the windows from whole methylomes on the device (no window directories)\n"
-                "       [--parse host|device] where the methylome files are parsed; the same output files [default: device]");
+                "       [--parse host|device] where the methylome files are parsed; the same output files [default: device]\n"
+                "       [--genes host|device] where every site's gene is chosen; the same output files [default: device]");
       return 0;
     } else {
       std::fprintf(stderr, "error: unexpected argument '%s' found\n", argv[i]);

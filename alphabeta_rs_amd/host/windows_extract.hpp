@@ -2,10 +2,12 @@
 // (src/genes.rs:140-217), the full methylome-line parse (src/methylation_site.rs:146-362) and the choice of a gene for
 // every site (src/windows.rs:303-338 around is_in_gene / find_gene, src/methylation_site.rs:368-418).  What follows the
 // gene choice — place_in_windows, the per-window site lists, the packed matrix, the folds — runs on the device
-// (abn_windows_*, csrc/abn_windows.hpp).  The gene choice is a serial dependence of a few integer compares per site (the
-// last_gene cache), so it stays here, one methylome per thread.  Integer arithmetic wraps as the reference's release
-// build does.  The line parse also runs on the device (parse_sites_device over abn_sites_parse, csrc/abn_parse.hpp):
-// the same FullSite sequence, fed to the same gene choice.
+// (abn_windows_*, csrc/abn_windows.hpp).  The gene choice (the last_gene cache: a few integer compares per site, each
+// depending on the site before) runs here, one methylome per thread (choose_genes), or on the device, where the
+// dependence is resolved per block of sites (abn_genes_*, csrc/abn_genes.hpp; the Handle made from FullSite vectors):
+// the same arrays either way.  Integer arithmetic wraps as the reference's release build does.  The line parse also runs
+// on the device (parse_sites_device over abn_sites_parse, csrc/abn_parse.hpp): the same FullSite sequence, fed to either
+// gene choice.
 #pragma once
 
 #include <thread>
@@ -352,9 +354,141 @@ inline std::vector<SampleSites> choose_genes_many_device(Device& dev, const std:
   return out;
 }
 
+// The sites of every methylome text in the order given (parse_sites_host on at most max_threads threads, or
+// parse_sites_device one text after the other: a context serves one call at a time)
+inline std::vector<std::vector<FullSite>> parse_sites_many(const std::vector<std::string>& texts, Device* dev,
+                                                           size_t max_threads = 16) {
+  std::vector<std::vector<FullSite>> out(texts.size());
+  if (dev) {
+    for (size_t i = 0; i < texts.size(); ++i) out[i] = parse_sites_device(*dev, texts[i]);
+    return out;
+  }
+  std::atomic<size_t> next{0};
+  auto work = [&]() {
+    for (size_t i; (i = next.fetch_add(1)) < texts.size();) out[i] = parse_sites_host(texts[i]);
+  };
+  const size_t nt = std::max<size_t>(1, std::min(max_threads, texts.size()));
+  std::vector<std::thread> pool;
+  for (size_t t = 1; t < nt; ++t) pool.emplace_back(work);
+  work();
+  for (auto& t : pool) t.join();
+  return out;
+}
+
+// choose_genes for every sample's parsed sites, one per thread (at most max_threads at a time)
+inline std::vector<SampleSites> choose_genes_many(const std::vector<std::vector<FullSite>>& sites, const Genome& genome,
+                                                  const GeneRule& rule, double posterior_max_filter,
+                                                  size_t max_threads = 16) {
+  std::vector<SampleSites> out(sites.size());
+  std::atomic<size_t> next{0};
+  auto work = [&]() {
+    for (size_t i; (i = next.fetch_add(1)) < sites.size();) out[i] = choose_genes(sites[i], genome, rule, posterior_max_filter);
+  };
+  const size_t nt = std::max<size_t>(1, std::min(max_threads, sites.size()));
+  std::vector<std::thread> pool;
+  for (size_t t = 1; t < nt; ++t) pool.emplace_back(work);
+  work();
+  for (auto& t : pool) t.join();
+  return out;
+}
+
+// The Genome in the arrays abn_genes_create takes: every non-empty list of every chromosome (kind 0 sense, 1 antisense,
+// 2 combined), in the order parse_annotation left it — sorted by start, stably
+struct GeneLists {
+  std::vector<int32_t> list_chromosome, list_kind;
+  std::vector<int64_t> list_offset{0};
+  std::vector<uint32_t> start, end;
+  std::vector<uint8_t> strand;
+};
+inline GeneLists flatten_genome(const Genome& genome) {
+  GeneLists out;
+  for (const auto& kv : genome.chromosomes) {
+    const std::vector<Gene>* lists[3] = {&kv.second.sense, &kv.second.antisense, &kv.second.combined};
+    for (int kind = 0; kind < 3; ++kind) {
+      if (lists[kind]->empty()) continue;
+      out.list_chromosome.push_back(kv.first);
+      out.list_kind.push_back(kind);
+      for (const Gene& g : *lists[kind]) {
+        out.start.push_back(g.start);
+        out.end.push_back(g.end);
+        out.strand.push_back((uint8_t)g.strand);
+      }
+      out.list_offset.push_back((int64_t)out.start.size());
+    }
+  }
+  return out;
+}
+
+// The samples' sites in the arrays abn_genes_choose and abn_windows_create_sites take; code = status | 0x80 when the
+// posterior is below the filter, as choose_gene computes it
+struct SiteArrays {
+  std::vector<int64_t> offset;
+  std::vector<int32_t> chromosome;
+  std::vector<uint32_t> start, end;
+  std::vector<uint8_t> strand, code;
+  std::vector<double> level;
+};
+inline SiteArrays site_arrays(const std::vector<std::vector<FullSite>>& samples, double posterior_max_filter) {
+  SiteArrays a;
+  a.offset.assign(samples.size() + 1, 0);
+  for (size_t s = 0; s < samples.size(); ++s) a.offset[s + 1] = a.offset[s] + (int64_t)samples[s].size();
+  const size_t S = (size_t)a.offset.back();
+  a.chromosome.resize(S);
+  a.start.resize(S);
+  a.end.resize(S);
+  a.strand.resize(S);
+  a.code.resize(S);
+  a.level.resize(S);
+  size_t i = 0;
+  for (const auto& sample : samples)
+    for (const FullSite& s : sample) {
+      a.chromosome[i] = s.chromosome;
+      a.start[i] = s.start;
+      a.end[i] = s.end;
+      a.strand[i] = (uint8_t)s.strand;
+      a.code[i] = (uint8_t)(s.status_numeric | (s.posteriormax < posterior_max_filter ? 0x80u : 0u));
+      a.level[i] = s.meth_lvl;
+      ++i;
+    }
+  return a;
+}
+
+// RAII abn_genes over a Genome
+class GenesHandle {
+ public:
+  GenesHandle(Device& dev, const Genome& genome) {
+    const GeneLists l = flatten_genome(genome);
+    dev.check(abn_genes_create(dev.get(), (int32_t)l.list_kind.size(), l.list_chromosome.data(), l.list_kind.data(),
+                               l.list_offset.data(), l.start.data(), l.end.data(), l.strand.data(), &h_),
+              "abn_genes_create");
+  }
+  ~GenesHandle() {
+    if (h_) abn_genes_destroy(h_);
+  }
+  GenesHandle(const GenesHandle&) = delete;
+  GenesHandle& operator=(const GenesHandle&) = delete;
+  abn_genes* get() const { return h_; }
+
+ private:
+  abn_genes* h_ = nullptr;
+};
+
 // RAII abn_windows over the samples' concatenated arrays
 class Handle {
  public:
+  // ... from the parsed sites: the gene of every site chosen on the device, nothing coming back before the windows are
+  // placed (abn_windows_create_sites)
+  Handle(Device& dev, const abn_windows_params& p, const Genome& genome, const GeneRule& rule, double posterior_max_filter,
+         const std::vector<std::vector<FullSite>>& samples)
+      : n_(samples.size()) {
+    const GenesHandle genes(dev, genome);
+    const SiteArrays a = site_arrays(samples, posterior_max_filter);
+    const abn_gene_rule r{rule.cutoff, rule.cutoff_gene_length ? 1 : 0};
+    dev.check(abn_windows_create_sites(dev.get(), &p, genes.get(), &r, (int32_t)n_, a.offset.data(), a.chromosome.data(),
+                                       a.start.data(), a.end.data(), a.strand.data(), a.code.data(), a.level.data(), &h_),
+              "abn_windows_create_sites");
+    fetch();
+  }
   Handle(Device& dev, const abn_windows_params& p, const std::vector<SampleSites>& samples) : n_(samples.size()) {
     std::vector<int64_t> off(n_ + 1, 0);
     for (size_t s = 0; s < n_; ++s) off[s + 1] = off[s] + (int64_t)samples[s].size();
@@ -370,16 +504,7 @@ class Handle {
     dev.check(abn_windows_create(dev.get(), &p, (int32_t)n_, off.data(), all.pos.data(), all.gene_start.data(),
                                  all.gene_end.data(), all.flags.data(), all.code.data(), all.level.data(), &h_),
               "abn_windows_create");
-    int32_t W = 0;
-    abn_windows_info(h_, &W, nullptr, nullptr);
-    W_ = (size_t)W;
-    count.resize(n_ * W_);
-    kept.resize(n_ * W_);
-    level_sum.resize(n_ * W_);
-    level_sum_kept.resize(n_ * W_);
-    ragged.resize(W_);
-    abn_windows_stats(h_, count.data(), level_sum.data(), level_sum_kept.data(), kept.data());
-    abn_windows_layout(h_, nullptr, nullptr, ragged.data());
+    fetch();
   }
   ~Handle() {
     if (h_) abn_windows_destroy(h_);
@@ -394,6 +519,18 @@ class Handle {
   std::vector<int32_t> ragged;  // [W]
 
  private:
+  void fetch() {  // what the handle reports, to the vectors above
+    int32_t W = 0;
+    abn_windows_info(h_, &W, nullptr, nullptr);
+    W_ = (size_t)W;
+    count.resize(n_ * W_);
+    kept.resize(n_ * W_);
+    level_sum.resize(n_ * W_);
+    level_sum_kept.resize(n_ * W_);
+    ragged.resize(W_);
+    abn_windows_stats(h_, count.data(), level_sum.data(), level_sum_kept.data(), kept.data());
+    abn_windows_layout(h_, nullptr, nullptr, ragged.data());
+  }
   abn_windows* h_ = nullptr;
   size_t n_ = 0, W_ = 0;
 };

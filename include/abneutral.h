@@ -307,7 +307,8 @@ int abn_pairwise_divergence_windows_packed_dev(abn_ctx* ctx, const void* dev_pac
  * (src/methylation_site.rs:423-490) for every site of every sample, on the device, straight into the packed matrix
  * abn_pairwise_divergence_windows_packed* scans — no <region>/<window>/<sample> file tree (Windows::save,
  * src/windows.rs:259-285) in between.  The gene of every site (find_gene with the last_gene cache, :303-338) is chosen on
- * the host; the handle takes its result.  Global window index: upstream 0.., then gene, then downstream. */
+ * the host for abn_windows_create, which takes its result, and on the device for abn_windows_create_sites (abn_genes_*
+ * below).  Global window index: upstream 0.., then gene, then downstream. */
 typedef struct abn_windows abn_windows;
 typedef struct abn_windows_params {
   uint32_t cutoff;       /* arguments::Windows (src/arguments.rs:6-62)                                          */
@@ -351,6 +352,54 @@ int abn_windows_packed_device_ptr(abn_windows* h, void** dev_ptr);
  * abn_pairwise_divergence_windows_packed_dev on the resident matrix with the handle's begin / end.  HOST outputs
  * [W x pairs], any may be NULL; a ragged or empty window: diff = both = 0, dvalue = NaN.  n_samples < 2: nothing written. */
 int abn_windows_pairwise(abn_windows* h, uint64_t* diff, uint64_t* both, double* dvalue);
+
+/* ------------------------------------------------------------------ the gene of every site (the `extract` stage)
+ * The loop of Windows::extract (src/windows.rs:325-338) up to place_in_windows: a site keeps the previous site's gene
+ * while is_in_gene holds (src/methylation_site.rs:368-378), else find_gene (:385-418: slice::binary_search_by over the
+ * list of the site's chromosome and strand, probe for probe, then is_in_gene).  The last_gene cache is resolved on the
+ * device without iteration: per block of 1024 sites every site's find_gene and its chain of misses, one pass per sample
+ * over its blocks for the gene carried into each, then every site's gene (csrc/abn_genes.hpp).  Results equal the serial
+ * loop's, element for element. */
+typedef struct abn_genes abn_genes;
+typedef struct abn_gene_rule {  /* the two arguments is_in_gene and find_gene read (src/arguments.rs:6-62) */
+  uint32_t cutoff;
+  int32_t cutoff_gene_length;   /* not 0: a gene's own length is its cutoff */
+} abn_gene_rule;
+/* The annotation as src/extract.rs:30-67 holds it, device-resident until abn_genes_destroy (destroy it before its
+ * context): n_lists lists, list l = the genes [list_offset[l], list_offset[l + 1]) of gene_start / gene_end / gene_strand
+ * (0 Sense, 1 Antisense, 2 Unknown), belonging to chromosome list_chromosome[l] (Numbered(n) = n, Mitochondrial = 256,
+ * Chloroplast = 257) and kind list_kind[l] (0 sense, 1 antisense, 2 combined: the three lists of GenesByStrand,
+ * src/genes.rs:127-163).  Every list is as :61-66 leaves it, stably sorted by start; the library does not sort.
+ * ABN_ERR_INVALID_ARG: null pointers, n_lists < 0, a chromosome outside 0..257, a kind outside 0..2, a (chromosome, kind)
+ * given twice, a gene_strand above 2, list_offset not ascending from 0 (or beyond 2^32 - 2 genes). */
+int abn_genes_create(abn_ctx* ctx, int32_t n_lists, const int32_t* list_chromosome, const int32_t* list_kind,
+                     const int64_t* list_offset, const uint32_t* gene_start, const uint32_t* gene_end,
+                     const uint8_t* gene_strand, abn_genes** out);
+int abn_genes_destroy(abn_genes* h);
+/* Replaces the loop of Windows::extract (src/windows.rs:325-338) in front of place_in_windows, with is_in_gene and
+ * find_gene (src/methylation_site.rs:368-418), for n_samples methylomes.  Struct-of-arrays over all samples as in
+ * abn_windows_create (site_offset, HOST memory in both forms); per site the fields of abn_sites_fetch: chromosome, start,
+ * end, strand.  Outputs per site, the arrays abn_windows_create takes: gene_start, gene_end (0, 0 without a gene), flags
+ * (bit 0: antisense site, bit 1: has a gene).  The cache starts empty at every sample's first site.  kernel_ms (may be
+ * NULL): double[3], the HIP-event times of the three kernels.  Zero sites, or a sample of zero sites, is fine.
+ * ABN_ERR_INVALID_ARG: null pointers, n_samples <= 0 or > 65535, site_offset not ascending from 0, a site chromosome
+ * outside 0..257 or a strand above 2 (host form: nothing is launched; device form: found by the kernels, the outputs are
+ * then unspecified). */
+int abn_genes_choose(abn_genes* h, const abn_gene_rule* rule, int32_t n_samples, const int64_t* site_offset,
+                     const int32_t* chromosome, const uint32_t* start, const uint32_t* end, const uint8_t* strand,
+                     uint32_t* gene_start, uint32_t* gene_end, uint8_t* flags, double* kernel_ms);
+/* ... on DEVICE-resident site arrays and outputs; returns after the work has completed */
+int abn_genes_choose_dev(abn_genes* h, const abn_gene_rule* rule, int32_t n_samples, const int64_t* site_offset,
+                         const void* dev_chromosome, const void* dev_start, const void* dev_end, const void* dev_strand,
+                         void* dev_gene_start, void* dev_gene_end, void* dev_flags, double* kernel_ms);
+/* abn_windows_create behind abn_genes_choose_dev, nothing coming back in between (src/windows.rs:325-339 whole): the
+ * site fields are uploaded once, the genes chosen on the device and pos = start, gene_start, gene_end, flags handed to
+ * the placement as device arrays.  code and level as in abn_windows_create.  *out is an ordinary abn_windows.
+ * ABN_ERR_INVALID_ARG: as abn_windows_create and abn_genes_choose, and a `genes` of another context. */
+int abn_windows_create_sites(abn_ctx* ctx, const abn_windows_params* params, abn_genes* genes, const abn_gene_rule* rule,
+                             int32_t n_samples, const int64_t* site_offset, const int32_t* chromosome,
+                             const uint32_t* start, const uint32_t* end, const uint8_t* strand, const uint8_t* code,
+                             const double* level, abn_windows** out);
 
 /* ------------------------------------------------------------------ methylome text -> site records
  * MethylationSite::from_methylome_file_line (src/methylation_site.rs:146-362, without --invert) for every line of a
