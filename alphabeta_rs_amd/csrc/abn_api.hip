@@ -614,11 +614,12 @@ struct abn_plan {
   DevBuf<int> susp_list;      // [W x S] + 1 counter at the end
   // per phase (A, B) kPhaseWords words: kPhaseSkipped evaluations not executed (fixed-point skip), kPhaseQueue the chain
   // queue of the persistent kernel
+  // ... one such slot per phase and one for the guarded redo of phase B (kPhaseSlots), then the words of the early
+  // bootstraps (kEarlyWords) and the slots' status words (kSliceWords each): plan_words() lays the buffer out
   DevBuf<unsigned long long> skipped;
   bool twopass_a = false;
   DevBuf<int> slice_buf;      // time slicing: head, tail, then the FIFO of parked chains
   unsigned slice_cap = 0;
-  DevBuf<unsigned> slice_status;   // per phase kSliceWords words (abn_constants.hpp; FitArgs::slice_status)
   long long persist_expected[2] = {0, 0};  // chains the last persistent launch of phase A / B had to finish (0: none)
   long long tail_handed[2] = {0, 0};       // ... of which its tail handed to the speculative kernel (read at the last sync)
   int32_t last_kernels[4] = {0, 0, 0, 0};  // abn_plan_last_kernels
@@ -627,7 +628,32 @@ struct abn_plan {
   hipEvent_t ev[kPlanEvents] = {};
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_join;
+  // Early bootstraps (abn_plan_run; route_early_bootstraps): phase B launched on a quorum of the starts
+  EarlyRoute early{};
+  int early_mode = 1;                 // abn_plan_set_early_bootstraps: 0 off, 1 auto
+  bool early_ran = false;             // the last run of phase B was such a run: the miss word selects the slot of phase B
+  int32_t early_parked = 0, early_miss = 0;   // ... its starts parked at the quorum and its miss word (read at the last sync)
+  DevBuf<double> early_state;         // [S x kStateDoubles] the starts parked at the quorum (phase B parks in nm_state)
+  DevBuf<int> early_list;             // [S] their list
+  DevBuf<double> sel_model, sel_pred, sel_resid;   // the selection over all starts, made beside the early phase B
+  DevBuf<int32_t> sel_best;
 };
+
+// The plan's small words, one allocation so that one memset clears a step's and one copy fetches them (in 32-bit words
+// behind the kPhaseSlots x kPhaseWords 64-bit ones): [kEarlyWords early bootstraps][kPhaseSlots x kSliceWords status]
+constexpr size_t kPlanWords64 = (size_t)kPhaseSlots * kPhaseWords + ((size_t)kEarlyWords + (size_t)kPhaseSlots * kSliceWords + 1) / 2;
+static unsigned* early_words(const abn_plan* p) { return reinterpret_cast<unsigned*>(p->skipped.p + kPhaseSlots * kPhaseWords); }
+static unsigned* slice_words(const abn_plan* p, int slot) { return early_words(p) + kEarlyWords + kSliceWords * slot; }
+// what verify_persistent and abn_plan_counters fetch: the whole of it
+struct PlanWordsHost {
+  unsigned long long phase[kPhaseSlots][kPhaseWords];
+  unsigned early[kEarlyWords];
+  unsigned slice[kPhaseSlots][kSliceWords];
+};
+static_assert(sizeof(PlanWordsHost) <= kPlanWords64 * sizeof(unsigned long long) && sizeof(PlanWordsHost) % 8 == 0 &&
+                  offsetof(PlanWordsHost, early) == kPhaseSlots * kPhaseWords * sizeof(unsigned long long) &&
+                  offsetof(PlanWordsHost, slice) == offsetof(PlanWordsHost, early) + kEarlyWords * sizeof(unsigned),
+              "PlanWordsHost mirrors the plan's words");
 
 extern "C" int abn_plan_destroy(abn_plan* p) {
   if (!p) return ABN_ERR_INVALID_ARG;
@@ -698,8 +724,7 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
   PALLOC(bestB, W * B * 4);
   PALLOC(infoB, W * B);
   PALLOC(raw_own, W * B * 7);
-  PALLOC(skipped, 2 * kPhaseWords);
-  PALLOC(slice_status, 2 * kSliceWords);
+  PALLOC(skipped, kPlanWords64);
   p->twopass_a = plan_two_pass((long long)n_windows * n_starts, p->opt.max_iters_start, p->opt.no_fixed_point_skip,
                                p->opt.shrink_on_failed_contraction, p->opt.strict_order);
   if (p->twopass_a) {
@@ -715,6 +740,23 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
   }
   p->stream_b = n_boot > 0 && p->route.streams && p->opt.stream_mode == 0;
   if (p->stream_b) PALLOC(dstar, W * B * N);
+  p->early = route_early_bootstraps(p->route, n_windows, n_starts, n_boot, c->cus, p->opt.window_groups, p->twopass_a,
+                                    p->slice_cap > 0);
+  // route_early_bootstraps routed phase B on its resident observations (dmode 1).  A plan that materialises them (dmode 2)
+  // streams its pedigree and so never runs persistent — and a phase B that is not persistent has no guard and would run
+  // twice: held here, not left to follow from the route.
+  if (p->stream_b) p->early = EarlyRoute{false, 0};
+#ifdef ABN_MEASUREMENT_KNOBS  // a forced kernel is not what route_early_bootstraps assumed
+  if (getenv("ABN_PHASE_A_KERNEL") || getenv("ABN_PHASE_B_KERNEL")) p->early = EarlyRoute{false, 0};
+#endif
+  if (p->early.eligible) {
+    PALLOC(early_state, S * kStateDoubles);
+    PALLOC(early_list, S);
+    PALLOC(sel_model, W * 4);
+    PALLOC(sel_pred, W * N);
+    PALLOC(sel_resid, W * N);
+    PALLOC(sel_best, W);
+  }
 #undef PALLOC
   p->raw = p->raw_own.p;
   for (auto& ev : p->ev)
@@ -832,8 +874,10 @@ static FitArgs phase_args(const abn_plan* p, int phase, int w0, int wn) {
 // The fit launch(es) of one phase (0 = A, 1 = B) for the windows `a` covers, on stream st.  A launch that covers the whole
 // plan is offered the phase's chain queue, the plan's parking buffers and its status words; window groups on side streams
 // would share them, so they get none (no persistent kernel, nothing to verify).
-static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool timed) {
+// slot: which of the plan's kPhaseSlots sets of words the launch counts in (the phase itself; kSlotRedo: the guarded redo)
+static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool timed, int slot = -1) {
   abn_ctx* c = p->ctx;
+  if (slot < 0) slot = phase;
   const bool whole = a.W == p->W;
   const char* force = nullptr;
 #ifdef ABN_MEASUREMENT_KNOBS  // ABN_PHASE_A_KERNEL / ABN_PHASE_B_KERNEL = spec | wide | packed  (scripts/phase_a_sweep.py)
@@ -844,10 +888,10 @@ static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool
   LaunchOffer offer;
   offer.queue = whole;
   offer.parking = whole && p->slice_cap > 0;
-  a.skipped = p->skipped.p + kPhaseWords * phase + kPhaseSkipped;
+  a.skipped = p->skipped.p + kPhaseWords * slot + kPhaseSkipped;
   if (whole) {
-    a.queue = reinterpret_cast<unsigned*>(p->skipped.p + kPhaseWords * phase + kPhaseQueue);
-    a.slice_status = p->slice_status.p + kSliceWords * phase;
+    a.queue = reinterpret_cast<unsigned*>(p->skipped.p + kPhaseWords * slot + kPhaseQueue);
+    a.slice_status = slice_words(p, slot);
   }
   if (offer.parking) {
     a.park_cap = p->slice_cap;
@@ -855,6 +899,11 @@ static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool
     a.parked = p->slice_buf.p + kParkShards * kParkHeaderInts;
     a.state = p->nm_state.p;
     a.susp_list = p->susp_list.p;   // tail hand-over (the route decides whether it applies)
+  }
+  if (a.quorum_words) {   // early bootstraps: the starts parked at the quorum have buffers of their own (phase B parks meanwhile)
+    a.state = p->early_state.p;
+    a.susp_list = p->early_list.p;
+    a.susp_count = reinterpret_cast<int*>(early_words(p) + kEarlyParked);
   }
   int kind = ABN_KERNEL_NONE, rc;
   if (ph.two_pass) {
@@ -879,21 +928,15 @@ static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool
   return ABN_OK;
 }
 
-// Phase A (starts) + selection for windows [w0, w0+wn) on stream st.  timed: record the plan's timing events around
-// the kernels.
-static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool timed) {
-  abn_ctx* c = p->ctx;
-  FitArgs a = phase_args(p, 0, w0, wn);
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitA], st));
-  if (int rc = launch_phase(p, 0, a, st, timed)) return rc;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitAEnd], st));
+// the selection of windows [w0, w0 + wn) over the fitted starts, into the plan's buffers
+static SelectArgs select_args(const abn_plan* p, int w0, int wn) {
   const WindowOffsets o = window_offsets(p, w0);
   SelectArgs s{};
   fill_topology(s, p->topo, p->dtopo);
-  s.p_uu = a.p_uu;
-  s.D = a.D;
-  s.models = a.best;
-  s.info = a.info;
+  s.p_uu = p->p_uu.p + o.w;
+  s.D = p->D.p + o.rows;
+  s.models = p->bestA.p + o.starts * 4;
+  s.info = p->infoA.p + o.starts;
   s.W = wn;
   s.S = p->S;
   s.lse = p->lse.p + o.starts;
@@ -901,6 +944,23 @@ static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
   s.pred = p->pred.p + o.rows;
   s.resid = p->resid.p + o.rows;
   s.best_start = p->best_start.p + o.w;
+  return s;
+}
+
+// Phase A (starts) + selection for windows [w0, w0+wn) on stream st.  timed: record the plan's timing events around
+// the kernels.  early (abn_plan_run with early bootstraps, one window): the fit launch ends once the plan's quorum of
+// starts has finished — the others park —, and the selection is over the finished ones.
+static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool timed, bool early = false) {
+  abn_ctx* c = p->ctx;
+  FitArgs a = phase_args(p, 0, w0, wn);
+  if (early) {   // W == 1: the counter and the flag are the one window's
+    a.quorum_words = early_words(p) + kEarlyCount;
+    a.quorum = p->early.quorum;
+  }
+  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitA], st));
+  if (int rc = launch_phase(p, 0, a, st, timed)) return rc;
+  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitAEnd], st));
+  const SelectArgs s = select_args(p, w0, wn);
   if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvSelect], st));
   if (int rc = launch_select(c, s, p->route.select_lds, st)) return rc;
   if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvSelectEnd], st));
@@ -908,9 +968,18 @@ static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
 }
 
 // Phase B (bootstraps) for windows [w0, w0+wn) on stream st
-static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool timed) {
+// A guarded launch (abn_plan_run with early bootstraps) stops when (*guard != 0) == guard_stop — the persistent kernel
+// looks every guard_poll steps, the tail's resume launch at its entry — and counts in the words of `slot`.
+struct PhaseGuard {
+  const unsigned* word = nullptr;
+  int stop = 0, poll = 0, slot = -1;
+};
+static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool timed, const PhaseGuard& guard = PhaseGuard{}) {
   abn_ctx* c = p->ctx;
   FitArgs a = phase_args(p, 1, w0, wn);
+  a.guard = guard.word;
+  a.guard_stop = guard.stop;
+  a.guard_poll = guard.poll;
   if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitB], st));
   if (p->stream_b) {  // gather the bootstrap observations once per fit, then stream them
     double* dst = p->dstar.p + window_offsets(p, w0).boots * (size_t)p->N;
@@ -922,15 +991,16 @@ static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
     a.dmode = 2;
     a.D = dst;
   }
-  if (int rc = launch_phase(p, 1, a, st, timed)) return rc;
+  if (int rc = launch_phase(p, 1, a, st, timed, guard.slot)) return rc;
   if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitBEnd], st));
   return ABN_OK;
 }
 
-// zero the skip counter and the chain queue (abn_plan::skipped) of `n` phases from phase `first`, in one memset
+// zero the skip counter and the chain queue (abn_plan::skipped) of `n` phases from phase `first`, in one memset; both
+// phases: all of the plan's words, the redo slot, the early bootstraps' counters and flags and the status words included
 static int clear_phase_words(abn_plan* p, int first, int n) {
-  HIPCHK(p->ctx, hipMemsetAsync(p->skipped.p + kPhaseWords * first, 0, (size_t)n * kPhaseWords * sizeof(unsigned long long),
-                                p->ctx->stream));
+  const size_t words = n == 2 ? kPlanWords64 : (size_t)n * kPhaseWords;
+  HIPCHK(p->ctx, hipMemsetAsync(p->skipped.p + kPhaseWords * first, 0, words * sizeof(unsigned long long), p->ctx->stream));
   return ABN_OK;
 }
 
@@ -959,6 +1029,7 @@ static int plan_run_phase(abn_plan* p, int32_t phase, ClearWords clear) {
     int rc = enqueue_phase_b(p, 0, p->W, c->stream, true);
     if (rc) return rc;
     p->ran_b = true;
+    p->early_ran = false;
     return ABN_OK;
   }
   return set_err(c, ABN_ERR_INVALID_ARG, "phase must be 0 or 1");
@@ -974,10 +1045,100 @@ extern "C" int abn_plan_run_phase(abn_plan* p, int32_t phase) {
 // back into the context's stream with events; results do not depend on the grouping and timing events are
 // recorded for group 0.  Streams share a few in-order hardware queues (4 by default), so more than 4 groups
 // serialise behind each other; see scripts/groups_bench.py for the measured effect.
+static int ensure_fork_join(abn_plan* p, int streams) {
+  abn_ctx* c = p->ctx;
+  while ((int)c->side.size() < streams) {
+    hipStream_t st = nullptr;
+    HIPCHK(c, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    c->side.push_back(st);
+  }
+  if (!p->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
+  while ((int)p->ev_join.size() < streams) {
+    hipEvent_t e = nullptr;
+    HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    p->ev_join.push_back(e);
+  }
+  return ABN_OK;
+}
+
+// Wavefront-steps between two looks of the early phase B at the miss word (a power of two; a step is ~2.7 us on C3)
+constexpr int kGuardPoll = 16;
+
+// abn_plan_run of a plan route_early_bootstraps admits.  No host synchronisation and no wait on a memory value: every
+// launch is enqueued, and those that must not run find that out from the miss word at their entry.
+//   main: clear -> A pass 1 (ends at the quorum) -> select over the finished starts -> fork
+//   side: A resume (the parked starts) -> select over all starts (scratch) -> compare (raises miss) -> join
+//   main: B + its tail (stop once miss is raised) -> wait for the join -> adopt the scratch selection
+//         -> B + its tail again, in the redo slot (run only if miss is raised)
+// The side work is enqueued before B and the join wait behind B's launches, for the reason given in abn_plan_run.
+static int plan_run_early(abn_plan* p) {
+  abn_ctx* c = p->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = ensure_fork_join(p, 1)) return rc;
+  hipStream_t side = c->side[0];
+  unsigned* ew = early_words(p);
+  if (int rc = clear_phase_words(p, 0, 2)) return rc;
+  if (int rc = enqueue_phase_a(p, 0, p->W, c->stream, true, true)) return rc;
+  HIPCHK(c, hipEventRecord(p->ev_fork, c->stream));
+  HIPCHK(c, hipStreamWaitEvent(side, p->ev_fork, 0));
+  {  // the stragglers: one workgroup per slot of their list (at most S - quorum can be running when the flag goes up)
+    FitArgs a = phase_args(p, 0, 0, p->W);
+    const LaunchRoute t = route_tail_resume(p->route, p->S - p->early.quorum);
+    if (t.status) return set_err(c, t.status, t.error);
+    a.chain_stride = t.chain_stride;
+    a.tree = t.tree;
+    a.spec_resume = 1;
+    a.state = p->early_state.p;
+    a.susp_list = p->early_list.p;
+    a.susp_count = reinterpret_cast<int*>(ew + kEarlyParked);
+    a.slice_status = ew + kEarlySink;
+    a.skipped = p->skipped.p + kPhaseSkipped;
+    if (int rc = launch_route(c, t, a, side)) return rc;
+  }
+  const SelectArgs to = select_args(p, 0, p->W);
+  SelectArgs all = to;   // the same rule over all starts: the LSEs are the plan's, the choice goes to scratch
+  all.model = p->sel_model.p;
+  all.pred = p->sel_pred.p;
+  all.resid = p->sel_resid.p;
+  all.best_start = p->sel_best.p;
+  if (int rc = launch_select(c, all, p->route.select_lds, side)) return rc;
+  hipLaunchKernelGGL(abn_early_compare_kernel, dim3(1), dim3(kWave), 0, side, to.best_start, all.best_start, p->W, ew + kEarlyMiss);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(p->ev_join[0], side));
+  PhaseGuard g;
+  g.word = ew + kEarlyMiss;
+  g.stop = 1;
+  g.poll = kGuardPoll;
+  if (int rc = enqueue_phase_b(p, 0, p->W, c->stream, true, g)) return rc;
+  HIPCHK(c, hipStreamWaitEvent(c->stream, p->ev_join[0], 0));
+  hipLaunchKernelGGL(abn_early_adopt_kernel, dim3(1), dim3(256), 0, c->stream, all, to);
+  HIPCHK(c, hipGetLastError());
+  g.stop = 0;
+  g.poll = 0;
+  g.slot = kSlotRedo;
+  if (int rc = enqueue_phase_b(p, 0, p->W, c->stream, false, g)) return rc;
+  HIPCHK(c, hipEventRecord(p->ev[kEvFitBEnd], c->stream));   // fit_boot: from the early launch to the end of the redo
+  p->phase_a_done = true;
+  p->ran_a = true;
+  p->ran_b = true;
+  p->early_ran = true;
+  return ABN_OK;
+}
+
+static bool early_applies(const abn_plan* p) { return p->early.eligible && p->early_mode != 0; }
+
+extern "C" int abn_plan_set_early_bootstraps(abn_plan* p, int32_t mode) {
+  if (!p) return ABN_ERR_INVALID_ARG;
+  if (mode != 0 && mode != 1) return set_err(p->ctx, ABN_ERR_INVALID_ARG, "early bootstraps: mode must be 0 (off) or 1 (auto)");
+  p->early_mode = mode;
+  return ABN_OK;
+}
+
 extern "C" int abn_plan_run(abn_plan* p) {
   if (!p) return ABN_ERR_INVALID_ARG;
   abn_ctx* c = p->ctx;
   if (!p->windows_set) return set_err(c, ABN_ERR_STATE, "abn_plan_set_windows has not been called");
+  if (early_applies(p)) return plan_run_early(p);
   int groups = p->opt.window_groups > 0 ? p->opt.window_groups : 1;
   groups = std::max(1, std::min(groups, p->W));
   if (groups == 1 || p->S <= 0 || p->B <= 0) {
@@ -988,17 +1149,7 @@ extern "C" int abn_plan_run(abn_plan* p) {
     return rc;
   }
   HIPCHK(c, hipSetDevice(c->device));
-  while ((int)c->side.size() < groups) {
-    hipStream_t st = nullptr;
-    HIPCHK(c, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    c->side.push_back(st);
-  }
-  if (!p->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
-  while ((int)p->ev_join.size() < groups) {
-    hipEvent_t e = nullptr;
-    HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    p->ev_join.push_back(e);
-  }
+  if (int rc = ensure_fork_join(p, groups)) return rc;
   if (int rc = clear_phase_words(p, 0, 2)) return rc;
   HIPCHK(c, hipEventRecord(p->ev_fork, c->stream));
   for (int g = 0; g < groups; ++g) {
@@ -1017,6 +1168,7 @@ extern "C" int abn_plan_run(abn_plan* p) {
   p->phase_a_done = true;
   p->ran_a = true;
   p->ran_b = true;
+  p->early_ran = false;
   return ABN_OK;
 }
 
@@ -1028,13 +1180,17 @@ extern "C" int abn_plan_run(abn_plan* p) {
 static int verify_persistent(abn_plan* p) {
   abn_ctx* c = p->ctx;
   HIPCHK(c, hipSetDevice(c->device));
-  unsigned sl[2][kSliceWords] = {};
+  PlanWordsHost h{};
   const bool check = p->persist_expected[0] > 0 || p->persist_expected[1] > 0;
-  if (check) HIPCHK(c, hipMemcpyAsync(sl, p->slice_status.p, sizeof sl, hipMemcpyDeviceToHost, c->stream));
+  if (check || p->early_ran) HIPCHK(c, hipMemcpyAsync(&h, p->skipped.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (p->early_ran) {   // a missed early phase B was stopped: the redo's words are phase B's
+    p->early_parked = (int32_t)h.early[kEarlyParked];
+    p->early_miss = h.early[kEarlyMiss] != 0 ? 1 : 0;
+  }
   for (int ph = 0; ph < 2 && check; ++ph) {
     if (p->persist_expected[ph] <= 0) continue;
-    const unsigned* s = sl[ph];
+    const unsigned* s = h.slice[ph == 1 && p->early_ran && p->early_miss ? kSlotRedo : ph];
     p->tail_handed[ph] = (long long)s[kSliceHanded];
     if (s[kSliceError] != 0 || (long long)s[kSliceFinished] != p->persist_expected[ph])
       return set_err(c, ABN_ERR_HIP, std::string("persistent fit launch of phase ") + (ph ? "B" : "A") + " finished " +
@@ -1056,6 +1212,16 @@ extern "C" int abn_plan_tail_handed(abn_plan* p, int64_t* out2) {
   const int rc = verify_persistent(p);  // synchronises the stream and reads the counts of the last persistent launches
   out2[0] = p->persist_expected[0] > 0 ? p->tail_handed[0] : 0;
   out2[1] = p->persist_expected[1] > 0 ? p->tail_handed[1] : 0;
+  return rc;
+}
+
+extern "C" int abn_plan_early_bootstraps(abn_plan* p, int32_t* out4) {
+  if (!p || !out4) return ABN_ERR_INVALID_ARG;
+  const int rc = verify_persistent(p);  // synchronises the stream and reads the words of the last run
+  out4[0] = p->early.eligible ? 1 : 0;
+  out4[1] = p->early.eligible ? p->early.quorum : 0;
+  out4[2] = p->early_ran ? p->early_parked : 0;
+  out4[3] = p->early_ran ? p->early_miss : 0;
   return rc;
 }
 
@@ -1150,16 +1316,18 @@ extern "C" int abn_plan_counters(abn_plan* p, int64_t* out5) {
   auto add = [&](const DevBuf<FitInfoDev>& b, int phase) -> int {
     if (!b.n) return ABN_OK;
     h.resize(b.n);
-    unsigned long long sk = 0;
+    PlanWordsHost wd{};
     HIPCHK(c, hipMemcpyAsync(h.data(), b.p, b.bytes(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&sk, p->skipped.p + kPhaseWords * phase + kPhaseSkipped, sizeof sk, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&wd, p->skipped.p, sizeof wd, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (const auto& f : h) {
       out5[0] += 1;
       out5[1] += f.evals;
       out5[2] += f.iters;
     }
-    out5[3 + phase] = (int64_t)sk;
+    // early bootstraps: a missed phase B was stopped and redone — the redo's count is that of one complete phase B
+    const int slot = phase == 1 && p->early_ran && wd.early[kEarlyMiss] != 0 ? kSlotRedo : phase;
+    out5[3 + phase] = (int64_t)wd.phase[slot][kPhaseSkipped];
     return ABN_OK;
   };
   int rc = ABN_OK;
@@ -1202,7 +1370,8 @@ extern "C" int abn_plan_device_bytes(abn_plan* p, int64_t* bytes) {
   t += p->simplexA.bytes() + p->bestA.bytes() + p->model.bytes() + p->lse.bytes() + p->bestB.bytes();
   t += p->raw_own.bytes() + p->infoA.bytes() + p->infoB.bytes() + p->best_start.bytes() + p->idx.bytes();
   t += p->dstar.bytes() + p->nm_state.bytes() + p->susp_list.bytes() + p->skipped.bytes() + p->slice_buf.bytes();
-  t += p->slice_status.bytes() + p->wid.bytes();
+  t += p->wid.bytes() + p->early_state.bytes() + p->early_list.bytes() + p->sel_model.bytes() + p->sel_pred.bytes();
+  t += p->sel_resid.bytes() + p->sel_best.bytes();
   t += p->dtopo.tri.bytes() + p->dtopo.tid.bytes();
   *bytes = (int64_t)t;
   return ABN_OK;

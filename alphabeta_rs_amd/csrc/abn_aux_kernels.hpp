@@ -119,6 +119,26 @@ __global__ __launch_bounds__(kWave) void abn_select_kernel(const SelectArgs a) {
   if (lane < 4) a.model[4 * w + lane] = x[lane];
 }
 
+// Early bootstraps (abn_plan_run): the selection ran twice through the two kernels above — over the starts finished at
+// the quorum (into the plan's buffers, which phase B reads) and, beside phase B, over all of them (into scratch buffers).
+// `miss` is raised when the two chose different starts: the early phase B then stops and is redone.
+__global__ __launch_bounds__(kWave) void abn_early_compare_kernel(const int32_t* early, const int32_t* all, int W, unsigned* miss) {
+  for (int w = threadIdx.x; w < W; w += kWave)
+    if (early[w] != all[w]) __hip_atomic_store(miss, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// ... and the selection over all starts becomes the plan's (the same bytes when the two agree)
+__global__ __launch_bounds__(256) void abn_early_adopt_kernel(const SelectArgs from, const SelectArgs to) {
+  const long long rows = (long long)to.W * to.N, n = rows > 4LL * to.W ? rows : 4LL * to.W;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    if (i < rows) {
+      to.pred[i] = from.pred[i];
+      to.resid[i] = from.resid[i];
+    }
+    if (i < 4LL * to.W) to.model[i] = from.model[i];
+    if (i < to.W) to.best_start[i] = from.best_start[i];
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Cost kernel (abn_cost_batch): one group of G lanes per candidate, any N (rows streamed).
 // strict = 1 (G must be 64): serial row-order accumulation, the reference's order exactly.

@@ -144,6 +144,20 @@ struct FitArgs {
   // slice_status + kSliceTailFill.
   int tail_cap;
   int spec_resume;
+  // Early bootstraps (abn_plan_run, one window): phase B starts once `quorum` of the starts have finished.
+  //   quorum_words (abn_fit_spec_kernel, pass 1 of phase A; null in every other launch; ONE window: the launch has W == 1,
+  //   route_early_bootstraps admits no other plan): a chain that finishes adds 1 to quorum_words[kEarlyCount] and, at
+  //   >= quorum, sets quorum_words[kEarlyFlag]; a running chain whose keeper
+  //   reads the flag set parks at that iteration boundary — `state` as for time slicing, index appended to susp_list,
+  //   info.status = kFitSuspended, best = NaN (the selection then passes it over) — and the RESUME launch finishes it.
+  //   guard (abn_fit_refill_kernel and the RESUME launch behind it; null: none): the launch stops when
+  //   (*guard != 0) == (guard_stop != 0).  Both read it at entry; the persistent kernel looks again every guard_poll
+  //   wavefront-steps (0: never) and then lets every group go idle, whatever its chain was doing.
+  unsigned* quorum_words;
+  int quorum;
+  const unsigned* guard;
+  int guard_stop;
+  int guard_poll;
 #ifdef ABN_MEASUREMENT_KNOBS
   // Wave priority by chain age in the persistent kernel (prio_mode != 0): the wavefront's s_setprio level is the number of
   // thresholds prio_t[] that the evaluations of its OLDEST running chain have passed (mode 1), or 3 minus that (mode 2).

@@ -51,6 +51,16 @@ constexpr int kSliceWords = 4;
 constexpr int kPhaseSkipped = 0;    // evaluations not executed (FitArgs::skipped, the fixed-point skip)
 constexpr int kPhaseQueue = 1;      // its low 32 bits: the chain queue of the persistent kernel (FitArgs::queue)
 constexpr int kPhaseWords = 2;
+// Early bootstraps (abn_plan_run on a quorum of starts, abn_api.hip): the plan's slots of those words are phase A, phase B
+// (the early launch) and the guarded redo of phase B, and behind them, zeroed by the same clear, kEarlyWords 32-bit words:
+constexpr int kPhaseSlots = 3, kSlotRedo = 2;
+constexpr int kEarlyCount = 0;      // += starts finished in pass 1 of phase A (FitArgs::quorum_words: count, then flag)
+constexpr int kEarlyFlag = 1;       // != 0: a quorum of them has: the running starts park at their next iteration boundary
+constexpr int kEarlyParked = 2;     // the length of the list of parked starts
+constexpr int kEarlyMiss = 3;       // != 0: the selection over all starts chose another start than the early one
+constexpr int kEarlySink = 4;       // kSliceWords words the stragglers' resume launch counts into (nobody reads them)
+constexpr int kEarlyWords = kEarlySink + kSliceWords;
+static_assert(kEarlyFlag == kEarlyCount + 1, "FitArgs::quorum_words: the flag follows the counter");
 
 // FitArgs::gap_tol = kGapTolFactor x abn_options.sd_tolerance.  The factor is what the convergence shortcut rests on: a
 // cost gap above it can never test as converged (the proof is in begin_iteration, abn_fit_kernel.hpp).

@@ -39,6 +39,11 @@ __global__ __launch_bounds__(kWave, ABN_REFILL_MIN_WAVES) void abn_fit_refill_ke
   constexpr int RR = RMAX;
   extern __shared__ __align__(16) double lds[];
 
+  // a guarded launch (FitArgs::guard: the early or the redone phase B of abn_plan_run) that is not to run leaves here
+  auto guard_says_stop = [&]() {
+    return (__hip_atomic_load(a.guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) == (a.guard_stop != 0);
+  };
+  if (a.guard && guard_says_stop()) return;
   const int lane = threadIdx.x;
   const int g = lane / G;
   const int gl = lane - g * G;
@@ -82,6 +87,7 @@ __global__ __launch_bounds__(kWave, ABN_REFILL_MIN_WAVES) void abn_fit_refill_ke
   bool tail_mode = false;    // tail hand-over: every running chain of this wavefront parks at its next iteration boundary
   bool tail_park = false;    // this chain's park goes to the tail list, not to the FIFO
   unsigned wstep = 0;
+  unsigned gstep = 0;        // guarded launch: wavefront-steps since the start, for the poll of the guard word
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     vx[k] = 0.0;
@@ -341,8 +347,15 @@ __global__ __launch_bounds__(kWave, ABN_REFILL_MIN_WAVES) void abn_fit_refill_ke
       }
       tail_mode = __builtin_amdgcn_readfirstlane(t) != 0;
     }
+    // guarded launch: every guard_poll steps (a power of two) lane 0 reads the guard word — issued ahead of the evaluation,
+    // looked at behind it; once it says stop the wavefront leaves with whatever its chains were doing (nobody takes these
+    // results: the launch that follows redoes every chain)
+    const bool guard_due = a.guard_poll > 0 && (++gstep & (unsigned)(a.guard_poll - 1)) == 0u;
+    int guard_stop_now = 0;
+    if (guard_due && lane == 0) guard_stop_now = guard_says_stop() ? 1 : 0;
     const bool in_init = st < ST_REFLECT;                         // Solver::init: start vertex st - ST_INIT0
     const double f = eval(in_init ? vx[0] : xc);
+    if (guard_due && __builtin_amdgcn_readfirstlane(guard_stop_now) != 0) break;
     // ---- decisions of NelderMead::next_iter as predicates (inert for groups in init or idle)
     const bool is_ref = st == ST_REFLECT, is_exp = st == ST_EXPAND, is_con = st == ST_CONTRACT;
     const bool active = is_ref || is_exp || is_con;

@@ -51,6 +51,8 @@ __global__ __launch_bounds__(4 * kWave, RMAX <= 2 ? 4 : 3) void abn_fit_spec_ker
     // The list, its length and the parked states were written by the wavefronts of the persistent launch on every XCD
     // (device-scope atomics on the counter, write-through stores for the states); a kernel boundary lies in between, and
     // they are read past the caches all the same, like the persistent kernel's own resume path reads them.
+    // a guarded launch (FitArgs::guard: the tail of an early or a redone phase B) that is not to run leaves here
+    if (a.guard && ((__hip_atomic_load(a.guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) == (a.guard_stop != 0))) return;
     if ((int)blockIdx.x >= __hip_atomic_load(a.susp_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;   // uniform in the workgroup, before any barrier
     chain = __hip_atomic_load(a.susp_list + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -449,8 +451,17 @@ __global__ __launch_bounds__(4 * kWave, RMAX <= 2 ? 4 : 3) void abn_fit_spec_ker
     if (improved) bx = vx[0];
   }
   bool done = publish();
+  // FitArgs::quorum_words: once a quorum of the window's starts has finished, this one parks at its next iteration boundary
+  constexpr bool QUORUM = !RESUME && !STRICT;
+  [[maybe_unused]] unsigned quorum_flag = 0u;
+  auto park_on_quorum = [&]() __attribute__((always_inline)) {
+    if constexpr (QUORUM)
+      if (status < 0 && quorum_flag != 0u) status = kFitSuspended;
+  };
 
   while (!done) {
+    if constexpr (QUORUM)  // read once per iteration, well ahead of the update that looks at it
+      if (a.quorum_words) quorum_flag = __hip_atomic_load(a.quorum_words + kEarlyFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     {
       // the candidates of the NEXT iteration for each way this one can end.  Outcome (A, p): the accepted
       // point A replaces the worst vertex and sorts in at rank p; the new order is v0..v3 with A at p.
@@ -517,6 +528,7 @@ __global__ __launch_bounds__(4 * kWave, RMAX <= 2 ? 4 : 3) void abn_fit_spec_ker
       insert_tail<4>(c, vx);
       status = ctl_begin(true, improved);
       if (improved) bx = vx[0];
+      park_on_quorum();
       ctl_write(status);
       xr = t[dim];
       x_e = t[4 + dim];
@@ -532,6 +544,7 @@ __global__ __launch_bounds__(4 * kWave, RMAX <= 2 ? 4 : 3) void abn_fit_spec_ker
         if (a.skipped && gl == 0 && rest > 0) atomicAdd(a.skipped, 2ull * (unsigned long long)rest);
       }
       status = ctl_begin(true, improved);
+      park_on_quorum();
       ctl_write(status);
       par ^= 1;  // same candidates again; the (identical) tables are rebuilt in the other buffers
     } else {
@@ -549,6 +562,7 @@ __global__ __launch_bounds__(4 * kWave, RMAX <= 2 ? 4 : 3) void abn_fit_spec_ker
       sort5(c, vx);
       status = ctl_begin(true, improved);
       if (improved) bx = vx[0];
+      park_on_quorum();
       done = publish();
       continue;
     }
@@ -559,9 +573,49 @@ __global__ __launch_bounds__(4 * kWave, RMAX <= 2 ? 4 : 3) void abn_fit_spec_ker
     }
   }
 
+  if constexpr (QUORUM) {
+    if (status == kFitSuspended) {
+      // parked on the quorum: the state exactly as abn_fit_refill_kernel parks it (the RESUME launch reads either), the
+      // chain on the list; its rows must not look finished to the selection that runs before the RESUME launch — status
+      // suspended whatever an earlier run left there, and a NaN model, whose LSE never wins
+      double* sp = a.state + (size_t)chain * kStateDoubles;
+      auto sd = [&](int i, double v) __attribute__((always_inline)) {
+        __hip_atomic_store(sp + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      };
+      if (gl < 4) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) sd(kStateSimplex + 4 * k + gl, vx[k]);
+        sd(kStateBest + gl, bx);
+        a.best[(size_t)chain * 4 + gl] = __builtin_nan("");
+      }
+      if (gl == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) sd(kStateCosts + k, c[k]);
+        sd(kStateBestCost, best_cost);
+        sd(kStateIterEvals, __longlong_as_double((long long)(unsigned)iter | ((long long)evals << 32)));
+        sd(kStateHaveBest, __longlong_as_double(have_best ? 1ll : 0ll));
+        a.susp_list[atomicAdd(a.susp_count, 1)] = (int)chain;
+        FitInfoDev fo;
+        fo.best_cost = best_cost;
+        fo.iters = iter;
+        fo.evals = evals;
+        fo.status = kFitSuspended;
+        fo.lanes = a.tree;
+        a.info[chain] = fo;
+      }
+      return;
+    }
+  }
   const double b0 = dpp_mov<kDppQuadBcast0>(bx), b1 = dpp_mov<kDppQuadBcast1>(bx);
   if (gl < 4) a.best[(size_t)chain * 4 + gl] = bx;
   if (gl == 0) {
+    if constexpr (QUORUM) {
+      if (a.quorum_words) {   // one more start of the (one) window has finished; the quorum-th raises the flag
+        unsigned* q = a.quorum_words;
+        if (atomicAdd(q + kEarlyCount, 1u) + 1u >= (unsigned)a.quorum)
+          __hip_atomic_store(q + kEarlyFlag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
 #ifdef ABN_DIAG_RESUME_COUNT   // diagnosis only (scripts/repro_lost_chain.py): the resume launch counts in the upper half of the word
     if constexpr (RESUME) atomicAdd(a.slice_status + kSliceFinished, 0x10000u);
 #else

@@ -371,4 +371,32 @@ inline LaunchRoute route_launch(const PedigreeRoute& p, const PhaseRoute& ph, lo
   return r;
 }
 
+// ------------------------------------------------------------------------------------------------
+// plan level: early bootstraps (abn_plan_run)
+// ------------------------------------------------------------------------------------------------
+// Phase B needs the BEST start, not the slowest: on a one-window plan whose starts run on the speculative kernel in one
+// launch, all resident at once, and whose bootstraps run on the time-sliced persistent kernel, abn_plan_run launches phase B
+// once `quorum` of the S starts have finished, lets the stragglers finish beside it and redoes phase B only when one of
+// them turns out best.  Never under strict order, with window groups or with fewer than five starts.
+struct EarlyRoute {
+  bool eligible;
+  int quorum;  // starts that must have finished before phase B is launched: S - max(1, S / 5)
+};
+inline EarlyRoute route_early_bootstraps(const PedigreeRoute& p, int n_windows, int n_starts, int n_boot, int cus,
+                                         int window_groups, bool two_pass, bool parking) {
+  EarlyRoute e{false, 0};
+  if (n_windows != 1 || n_starts < 5 || n_boot <= 0 || p.strict || window_groups > 1) return e;
+  const PhaseRoute pa = route_phase(p, 0, n_starts, cus, 0, true, two_pass);
+  if (!pa.spec || n_starts > (pick_rmax(p.n, kWave) <= 2 ? 4LL : 3LL) * cus) return e;
+  const PhaseRoute pb = route_phase(p, 1, n_boot, cus, 1, true, two_pass);
+  LaunchOffer offer;
+  offer.queue = true;
+  offer.parking = parking;
+  const LaunchRoute lb = route_launch(p, pb, n_boot, cus, offer);
+  if (lb.status != ABN_OK || lb.kind != ABN_KERNEL_PERSISTENT) return e;
+  e.eligible = true;
+  e.quorum = n_starts - std::max(1, n_starts / 5);
+  return e;
+}
+
 }  // namespace abn

@@ -466,6 +466,15 @@ int abn_plan_sync(abn_plan* plan);
  * last chains of such a launch finish on abn_fit_spec_kernel (four wavefronts per chain) instead of one by one on an
  * emptying GPU; 0 when the phase did not run persistent.  Same bits either way.  Synchronises like abn_plan_sync. */
 int abn_plan_tail_handed(abn_plan* plan, int64_t* out2);
+/* Early bootstraps.  Phase B needs a window's BEST start, not its slowest: on a plan of one window with at least five
+ * starts (auto options, no window groups) whose starts run on abn_fit_spec_kernel and whose bootstraps run on the
+ * persistent kernel, abn_plan_run launches phase B once a quorum of the starts has finished; the others finish beside it,
+ * and phase B is stopped and redone when one of them turns out best (a "miss").  Results are the same bytes either way.
+ * mode: 0 = off, 1 = auto (the default).  abn_plan_run_phase never does this. */
+int abn_plan_set_early_bootstraps(abn_plan* plan, int32_t mode);
+/* out4 = the plan is eligible (0 / 1), its quorum, and of the last abn_plan_run (0 when it did not launch phase B early):
+ * starts that were still running at the quorum, miss (0 / 1).  Synchronises like abn_plan_sync. */
+int abn_plan_early_bootstraps(abn_plan* plan, int32_t* out4);
 /* HIP-event time of the most recent launch of each kernel, in milliseconds (fit A, select, fit B) */
 int abn_plan_kernel_ms(abn_plan* plan, double* ms3);
 /* device pointer of raw[W x B x 7] (for an RCCL gather by the caller) and optional rebinding to a
