@@ -33,7 +33,8 @@ STATUS_NAMES = {
     6: "ABN_ERR_STATE",
 }
 FIT_CONVERGED, FIT_MAX_ITERS, FIT_NONFINITE, FIT_TARGET = 0, 1, 2, 3
-KERNEL_NAMES = {0: "none", 1: "speculative", 2: "resident", 3: "persistent", 4: "stream", 5: "two_pass"}
+KERNEL_NAMES = {0: "none", 1: "speculative", 2: "resident", 3: "persistent", 4: "stream", 5: "two_pass",
+                6: "stream_sweep"}
 
 FIT_INFO_DTYPE = np.dtype(
     [("best_cost", "<f8"), ("iters", "<i4"), ("evals", "<i4"), ("status", "<i4"), ("lanes", "<i4")]
@@ -61,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "abn_windows_packed", "abn_windows_packed_device_ptr", "abn_windows_pairwise",
     "abn_sites_parse", "abn_sites_destroy", "abn_sites_info", "abn_sites_fetch", "abn_sites_deferred",
     "abn_genes_create", "abn_genes_destroy", "abn_genes_choose", "abn_genes_choose_dev", "abn_windows_create_sites",
+    "abn_plan_set_stream_sweep", "abn_plan_stream_sweep", "abn_multi_set_stream_sweep", "abn_fit_batch_sweep",
 ]
 
 
@@ -148,6 +150,8 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
                                  u32p, u32p, C.c_int64, dp, dp, dp]
     L.abn_fit_batch.argtypes = [vp, op, dp, C.c_int32, C.c_double, C.c_double, C.c_double, dp, C.c_int64, dp,
                                 C.c_int32, dp, vp]
+    L.abn_fit_batch_sweep.argtypes = [vp, op, dp, C.c_int32, C.c_double, C.c_double, C.c_double, dp, C.c_int64, dp,
+                                      C.c_int32, dp, vp, C.POINTER(C.c_int64)]
     L.abn_gen_start_simplices.argtypes = [C.c_uint64, C.c_uint32, C.c_int32, C.c_double, dp]
     L.abn_gen_boot_simplices.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int64, dp, dp]
     L.abn_gen_boot_indices.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int64, C.c_int32, u32p]
@@ -211,6 +215,9 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_plan_sync.argtypes = [vp]
     L.abn_plan_tail_handed.argtypes = [vp, C.POINTER(C.c_int64)]
     L.abn_plan_set_early_bootstraps.argtypes = [vp, C.c_int32]
+    L.abn_plan_set_stream_sweep.argtypes = [vp, C.c_int32]
+    L.abn_plan_stream_sweep.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.abn_multi_set_stream_sweep.argtypes = [vp, C.c_int32]
     L.abn_plan_early_bootstraps.argtypes = [vp, C.POINTER(C.c_int32)]
     L.abn_plan_kernel_ms.argtypes = [vp, dp]
     L.abn_plan_raw_device_ptr.argtypes = [vp, C.POINTER(vp)]
@@ -437,6 +444,22 @@ class Context:
         self._check(self._L.abn_fit_batch(self._h, C.byref(options) if options else None, _dp(ped), n, p_uu0, eqp,
                                           eqp_weight, _dp(s0), f, _dp(d), max_iters, _dp(best), info.ctypes.data))
         return best, info
+
+    def fit_batch_sweep(self, pedigree, p_uu0, eqp, eqp_weight, simplex0, max_iters, *, dobs_rows=None,
+                        options: Options | None = None):
+        """fit_batch on the sweep kernel (one pass over the rows per iteration): (best, info, passes over the rows).
+        Refused (ABN_ERR_INVALID_ARG) when the pedigree and the options do not route to that kernel."""
+        ped = _f64(pedigree).reshape(-1, 4)
+        s0 = _f64(simplex0).reshape(-1, 20)
+        n, f = ped.shape[0], s0.shape[0]
+        d = None if dobs_rows is None else _f64(dobs_rows, (f, n))
+        best = np.empty((f, 4))
+        info = np.zeros(f, dtype=FIT_INFO_DTYPE)
+        passes = C.c_int64(0)
+        self._check(self._L.abn_fit_batch_sweep(self._h, C.byref(options) if options else None, _dp(ped), n, p_uu0, eqp,
+                                                eqp_weight, _dp(s0), f, _dp(d), max_iters, _dp(best), info.ctypes.data,
+                                                C.byref(passes)))
+        return best, info, int(passes.value)
 
     def gen_boot_indices(self, seed, window, b0, nb, n_rows) -> np.ndarray:
         idx = np.empty((nb, n_rows), dtype=np.uint32)
@@ -742,6 +765,18 @@ class Plan:
         self.ctx._check(self._L.abn_plan_early_bootstraps(self._h, out))
         return {"eligible": bool(out[0]), "quorum": int(out[1]), "parked": int(out[2]), "miss": bool(out[3])}
 
+    def set_stream_sweep(self, mode: int):
+        """0 (default): streamed chains re-read their rows every cost evaluation; 1: once per Nelder-Mead iteration
+        (reflection, expansion and contraction in one pass) where the launch streams with a wavefront per chain — same
+        bytes either way"""
+        self.ctx._check(self._L.abn_plan_set_stream_sweep(self._h, mode))
+
+    def stream_sweep(self):
+        """the mode; whether the last run of each phase used the sweep kernel; passes over the rows those launches counted"""
+        out = (C.c_int64 * 4)()
+        self.ctx._check(self._L.abn_plan_stream_sweep(self._h, out))
+        return {"mode": int(out[0]), "starts": bool(out[1]), "boot": bool(out[2]), "passes": int(out[3])}
+
     def kernel_ms(self):
         ms = np.zeros(3)
         self.ctx._check(self._L.abn_plan_kernel_ms(self._h, _dp(ms)))
@@ -1015,6 +1050,10 @@ class MultiPlan:
     def set_window_ids(self, ids):
         a = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(self.W)
         self._check(self._L.abn_multi_set_window_ids(self._h, _u32p(a)))
+
+    def set_stream_sweep(self, mode: int):
+        """Plan.set_stream_sweep on every device's plan"""
+        self._check(self._L.abn_multi_set_stream_sweep(self._h, mode))
 
     def set_windows(self, d_obs, p0uu, eqp=None, eqp_weight=None):
         d = _f64(d_obs, (self.W, self.N))

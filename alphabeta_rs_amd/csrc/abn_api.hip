@@ -145,13 +145,16 @@ struct KernelEntry {
 #define ABN_SPEC(R, ST, RS) {{kFamSpec, kWave, R, false, ST, RS}, reinterpret_cast<const void*>(&abn_fit_spec_kernel<R, ST, RS>)}
 #define ABN_SPEC_R(R) ABN_SPEC(R, false, false), ABN_SPEC(R, true, false), ABN_SPEC(R, false, true)
 #define ABN_COST(G) {{kFamCost, G, 0, false, false, false}, reinterpret_cast<const void*>(&abn_cost_kernel<G>)}
+#define ABN_SWEEP(R) {{kFamSweep, kWave, R, false, false, false}, reinterpret_cast<const void*>(&abn_sweep_kernel<R>)}
 static const KernelEntry kKernels[] = {
     ABN_FIT_G(8), ABN_FIT_G(16), ABN_FIT_G(32), ABN_FIT_G(64),
     ABN_FIT(64, 16, false, false), ABN_FIT(64, 16, true, false), ABN_FIT(64, 16, false, true),  // one wavefront per chain only
     ABN_REFILL_G(8), ABN_REFILL_G(16), ABN_REFILL_G(32), ABN_REFILL_G(64),
     ABN_SPEC_R(1), ABN_SPEC_R(2), ABN_SPEC_R(4), ABN_SPEC_R(8),
-    ABN_COST(8), ABN_COST(16), ABN_COST(32), ABN_COST(64)};
-static_assert(sizeof(kKernels) / sizeof(kKernels[0]) == 103, "the census of tests/test_kernel_matrix_census.py");
+    ABN_COST(8), ABN_COST(16), ABN_COST(32), ABN_COST(64),
+    ABN_SWEEP(0), ABN_SWEEP(-1)};
+static_assert(sizeof(kKernels) / sizeof(kKernels[0]) == 103 + 2,
+              "the census of tests/test_kernel_matrix_census.py, and the two sweep kernels of tests/test_stream_sweep_cpu.py");
 
 template <class Args>
 static int launch_route(abn_ctx* c, const LaunchRoute& r, const Args& a, hipStream_t st) {
@@ -201,6 +204,7 @@ static int launch_fit(abn_ctx* c, const PedigreeRoute& pr, const PhaseRoute& ph,
   a.quantum = r.quantum;
   a.tail_cap = r.tail_cap;
   if (!persistent) a.queue = nullptr;
+  if (r.kind != ABN_KERNEL_STREAM_SWEEP) a.passes = nullptr;
   if (a.tail_cap > 0) a.susp_count = reinterpret_cast<int*>(a.slice_status + kSliceTailFill);
   if (persistent && a.slice_status) HIPCHK(c, hipMemsetAsync(a.slice_status, 0, kSliceWords * sizeof(unsigned), st));
   if (a.quantum > 0) {  // empty FIFO of parked chains: entries -1, head = tail = 0
@@ -541,10 +545,12 @@ extern "C" int abn_cost_batch(abn_ctx* c, const abn_options* opts, const double*
 // ------------------------------------------------------------------------------------------------
 // Nelder-Mead fit batch (explicit start simplices)
 // ------------------------------------------------------------------------------------------------
-extern "C" int abn_fit_batch(abn_ctx* c, const abn_options* opts, const double* pedigree, int32_t n_rows, double p_uu0,
-                             double eqp, double eqp_weight, const double* simplex0, int64_t f, const double* dobs_rows,
-                             int32_t max_iters, double* best, abn_fit_info* info) {
+// sweep: abn_fit_batch_sweep — the launch must take abn_sweep_kernel, or the call is refused; passes: its counter (nullable)
+static int fit_batch(abn_ctx* c, const abn_options* opts, const double* pedigree, int32_t n_rows, double p_uu0, double eqp,
+                     double eqp_weight, const double* simplex0, int64_t f, const double* dobs_rows, int32_t max_iters,
+                     double* best, abn_fit_info* info, bool sweep, int64_t* passes) {
   if (!c) return ABN_ERR_INVALID_ARG;
+  if (passes) *passes = 0;
   if (!pedigree || n_rows <= 0 || !simplex0 || f < 0 || !best || max_iters < 0 || f > 0x7fffffff)
     return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
   if (f == 0) return ABN_OK;
@@ -580,12 +586,41 @@ extern "C" int abn_fit_batch(abn_ctx* c, const abn_options* opts, const double* 
   a.max_iters = max_iters;
   a.best = dbest.p;
   a.info = dinfo.p;
-  rc = launch_fit(c, pr, PhaseRoute{false, pr.lanes, false}, a, LaunchOffer{}, c->stream);
+  LaunchOffer offer;
+  DevBuf<unsigned long long> dpasses;
+  unsigned long long hpasses = 0;
+  if (sweep) {
+    offer.sweep = true;
+    const LaunchRoute r = route_launch(pr, PhaseRoute{false, pr.lanes, false}, f, c->cus, offer);
+    if (r.status) return set_err(c, r.status, r.error);
+    if (r.kind != ABN_KERNEL_STREAM_SWEEP)
+      return set_err(c, ABN_ERR_INVALID_ARG,
+                     "abn_fit_batch_sweep: this pedigree and these options do not route to the sweep kernel (it takes streamed "
+                     "pedigrees at 64 lanes per chain in tree order, within the LDS of a CU)");
+    HIPCHK(c, dpasses.alloc(1));
+    HIPCHK(c, hipMemsetAsync(dpasses.p, 0, dpasses.bytes(), c->stream));
+    a.passes = dpasses.p;
+  }
+  rc = launch_fit(c, pr, PhaseRoute{false, pr.lanes, false}, a, offer, c->stream);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(best, dbest.p, dbest.bytes(), hipMemcpyDeviceToHost, c->stream));
   if (info) HIPCHK(c, hipMemcpyAsync(info, dinfo.p, dinfo.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (sweep) HIPCHK(c, hipMemcpyAsync(&hpasses, dpasses.p, sizeof hpasses, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (passes) *passes = (int64_t)hpasses;
   return ABN_OK;
+}
+
+extern "C" int abn_fit_batch(abn_ctx* c, const abn_options* opts, const double* pedigree, int32_t n_rows, double p_uu0,
+                             double eqp, double eqp_weight, const double* simplex0, int64_t f, const double* dobs_rows,
+                             int32_t max_iters, double* best, abn_fit_info* info) {
+  return fit_batch(c, opts, pedigree, n_rows, p_uu0, eqp, eqp_weight, simplex0, f, dobs_rows, max_iters, best, info, false, nullptr);
+}
+
+extern "C" int abn_fit_batch_sweep(abn_ctx* c, const abn_options* opts, const double* pedigree, int32_t n_rows, double p_uu0,
+                                   double eqp, double eqp_weight, const double* simplex0, int64_t f, const double* dobs_rows,
+                                   int32_t max_iters, double* best, abn_fit_info* info, int64_t* passes) {
+  return fit_batch(c, opts, pedigree, n_rows, p_uu0, eqp, eqp_weight, simplex0, f, dobs_rows, max_iters, best, info, true, passes);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -637,6 +672,11 @@ struct abn_plan {
   DevBuf<int> early_list;             // [S] their list
   DevBuf<double> sel_model, sel_pred, sel_resid;   // the selection over all starts, made beside the early phase B
   DevBuf<int32_t> sel_best;
+  // Stream sweep (abn_plan_set_stream_sweep): the mode, whether the last run of phase A / B launched abn_sweep_kernel, and
+  // the device counter of its passes over the rows (allocated when the mode is first switched on)
+  int sweep_mode = 0;
+  bool sweep_used[2] = {false, false};
+  DevBuf<unsigned long long> sweep_passes;
 };
 
 // The plan's small words, one allocation so that one memset clears a step's and one copy fetches them (in 32-bit words
@@ -888,6 +928,8 @@ static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool
   LaunchOffer offer;
   offer.queue = whole;
   offer.parking = whole && p->slice_cap > 0;
+  offer.sweep = p->sweep_mode != 0;
+  a.passes = p->sweep_passes.p ? p->sweep_passes.p + phase : nullptr;
   a.skipped = p->skipped.p + kPhaseWords * slot + kPhaseSkipped;
   if (whole) {
     a.queue = reinterpret_cast<unsigned*>(p->skipped.p + kPhaseWords * slot + kPhaseQueue);
@@ -921,6 +963,7 @@ static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool
   }
   if (rc) return rc;
   if (whole) p->persist_expected[phase] = kind == ABN_KERNEL_PERSISTENT ? (long long)a.W * a.C : 0;
+  if (kind == ABN_KERNEL_STREAM_SWEEP) p->sweep_used[phase] = true;
   if (timed) {
     p->last_kernels[2 * phase] = kind;
     p->last_kernels[2 * phase + 1] = ph.lanes;
@@ -1000,6 +1043,11 @@ static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
 // phases: all of the plan's words, the redo slot, the early bootstraps' counters and flags and the status words included
 static int clear_phase_words(abn_plan* p, int first, int n) {
   const size_t words = n == 2 ? kPlanWords64 : (size_t)n * kPhaseWords;
+  // the stream sweep's record (flag and pass counter per phase) is of the last run of each phase
+  for (int ph = first; ph < first + n && ph < 2; ++ph) {
+    p->sweep_used[ph] = false;
+    if (p->sweep_passes.p) HIPCHK(p->ctx, hipMemsetAsync(p->sweep_passes.p + ph, 0, sizeof(unsigned long long), p->ctx->stream));
+  }
   HIPCHK(p->ctx, hipMemsetAsync(p->skipped.p + kPhaseWords * first, 0, words * sizeof(unsigned long long), p->ctx->stream));
   return ABN_OK;
 }
@@ -1132,6 +1180,39 @@ extern "C" int abn_plan_set_early_bootstraps(abn_plan* p, int32_t mode) {
   if (mode != 0 && mode != 1) return set_err(p->ctx, ABN_ERR_INVALID_ARG, "early bootstraps: mode must be 0 (off) or 1 (auto)");
   p->early_mode = mode;
   return ABN_OK;
+}
+
+static int verify_persistent(abn_plan* p);
+
+extern "C" int abn_plan_set_stream_sweep(abn_plan* p, int32_t mode) {
+  if (!p) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = p->ctx;
+  if (mode != 0 && mode != 1) return set_err(c, ABN_ERR_INVALID_ARG, "stream sweep: mode must be 0 (off) or 1 (on)");
+  if (mode == 1 && !p->sweep_passes.p) {
+    HIPCHK(c, hipSetDevice(c->device));
+    PoolScope pool_scope(c);
+    hipError_t e = p->sweep_passes.alloc(2);  // one counter per phase
+    if (e != hipSuccess) return set_err(c, ABN_ERR_HIP, std::string("hipMalloc sweep_passes: ") + hipGetErrorString(e));
+    HIPCHK(c, hipMemsetAsync(p->sweep_passes.p, 0, p->sweep_passes.bytes(), c->stream));
+  }
+  p->sweep_mode = mode;
+  return ABN_OK;
+}
+
+extern "C" int abn_plan_stream_sweep(abn_plan* p, int64_t* out4) {
+  if (!p || !out4) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = p->ctx;
+  unsigned long long passes[2] = {0, 0};
+  if (p->sweep_passes.p) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(passes, p->sweep_passes.p, sizeof passes, hipMemcpyDeviceToHost, c->stream));
+  }
+  const int rc = verify_persistent(p);  // synchronises the stream
+  out4[0] = p->sweep_mode;
+  out4[1] = p->sweep_used[0] ? 1 : 0;
+  out4[2] = p->sweep_used[1] ? 1 : 0;
+  out4[3] = (int64_t)((p->sweep_used[0] ? passes[0] : 0) + (p->sweep_used[1] ? passes[1] : 0));
+  return rc;
 }
 
 extern "C" int abn_plan_run(abn_plan* p) {
@@ -1371,7 +1452,7 @@ extern "C" int abn_plan_device_bytes(abn_plan* p, int64_t* bytes) {
   t += p->raw_own.bytes() + p->infoA.bytes() + p->infoB.bytes() + p->best_start.bytes() + p->idx.bytes();
   t += p->dstar.bytes() + p->nm_state.bytes() + p->susp_list.bytes() + p->skipped.bytes() + p->slice_buf.bytes();
   t += p->wid.bytes() + p->early_state.bytes() + p->early_list.bytes() + p->sel_model.bytes() + p->sel_pred.bytes();
-  t += p->sel_resid.bytes() + p->sel_best.bytes();
+  t += p->sel_resid.bytes() + p->sel_best.bytes() + p->sweep_passes.bytes();
   t += p->dtopo.tri.bytes() + p->dtopo.tid.bytes();
   *bytes = (int64_t)t;
   return ABN_OK;

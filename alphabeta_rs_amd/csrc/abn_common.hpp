@@ -1,9 +1,10 @@
 // Device code of the ABneutral hot path for gfx950 (CDNA4, wave64): what every kernel family shares — launch arguments,
 // the scalar pieces of one cost evaluation (genmatrix, power table, one triple), simplex bookkeeping, reductions.
 // Kernels: abn_fit_kernel.hpp (plain / stream / two-pass / strict), abn_fit_refill.hpp (persistent, time-sliced),
-// abn_fit_spec.hpp (four wavefronts per chain), abn_aux_kernels.hpp (selection, cost batch, rows, observations, indices),
-// abn_pairwise_mx.hpp (pedigree construction).  abn_device.hpp includes them all.  Compiled with -ffp-contract=off:
-// every fused multiply-add below is explicit and corresponds to one the reference executes.
+// abn_fit_spec.hpp (four wavefronts per chain), abn_fit_sweep.hpp (streamed, one pass over the rows per iteration),
+// abn_aux_kernels.hpp (selection, cost batch, rows, observations, indices), abn_pairwise_mx.hpp (pedigree
+// construction).  abn_device.hpp includes them all.  Compiled with -ffp-contract=off: every fused multiply-add below is
+// explicit and corresponds to one the reference executes.
 //
 // Mapping: a Nelder-Mead chain (one fit) is owned by a group of G lanes of one
 // wavefront (G = 64: one wavefront per chain; G < 64 packs 64/G chains into a wavefront for small
@@ -173,6 +174,9 @@ struct FitArgs {
   FitInfoDev* info;      // [W*C]
   double* raw;           // nullable [W*C*7] (src/boot_model.rs:86-91)
   unsigned long long* dbg;  // diagnostic builds only (ABN_STAMPS): per-segment cycle sums of chain 0
+  // abn_sweep_kernel only (nullable): += the chain's passes over its rows, once at its end — 5 for Solver::init, one per
+  // executed iteration, 4 per shrink
+  unsigned long long* passes;
 };
 
 // In-kernel stamps (MI355X guide §7): only in a separate diagnostic build, never in the shipped library.

@@ -12,6 +12,10 @@ constexpr int kStreamVec = 4;  // consecutive rows per lane and block in stream 
 #define ABN_STREAM_BLOCKS 6
 #endif
 constexpr int kStreamBlocks = ABN_STREAM_BLOCKS;  // row blocks a lane keeps in flight per loop iteration
+// abn_sweep_kernel (abn_fit_sweep.hpp) holds one wavefront per SIMD where the per-evaluation stream kernel holds two (its
+// LDS footprint is about twice as large), so its deep loop keeps twice the row blocks of a lane in flight: the bytes in
+// flight per CU stay what they are.  One trip covers kSweepBlocks x kStreamVec x 64 rows; shorter rows take its pair loop.
+constexpr int kSweepBlocks = 2 * kStreamBlocks;
 constexpr int kStrictRowsPerLane = 8;  // rows per lane and chunk of the strict stream variant (abn_fit_kernel.hpp)
 
 constexpr int kParkHead = 0, kParkTail = 64, kParkAvail = 128, kParkHeaderInts = 192;  // one cache line each

@@ -5,4 +5,5 @@
 #include "abn_fit_kernel.hpp"
 #include "abn_fit_refill.hpp"
 #include "abn_fit_spec.hpp"
+#include "abn_fit_sweep.hpp"
 #include "abn_aux_kernels.hpp"

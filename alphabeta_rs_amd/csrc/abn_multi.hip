@@ -254,6 +254,17 @@ extern "C" int abn_multi_set_window_ids(abn_multi* m, const uint32_t* ids) {
   return ABN_OK;
 }
 
+extern "C" int abn_multi_set_stream_sweep(abn_multi* m, int32_t mode) {
+  if (!m) return ABN_ERR_INVALID_ARG;
+  if (mode != 0 && mode != 1) return fail(m, ABN_ERR_INVALID_ARG, "stream sweep: mode must be 0 (off) or 1 (on)");
+  for (int i = 0; i < m->n; ++i) {
+    if (!m->plan[(size_t)i]) continue;
+    const int rc = abn_plan_set_stream_sweep(m->plan[(size_t)i], mode);
+    if (rc) return plan_fail(m, i, rc, "abn_plan_set_stream_sweep");
+  }
+  return ABN_OK;
+}
+
 extern "C" int abn_multi_set_windows(abn_multi* m, const double* d_obs, const double* p0uu, const double* eqp,
                                      const double* eqp_weight) {
   if (!m || !d_obs || !p0uu) return m ? fail(m, ABN_ERR_INVALID_ARG, "null window data") : ABN_ERR_INVALID_ARG;

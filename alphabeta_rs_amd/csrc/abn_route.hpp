@@ -81,6 +81,9 @@ constexpr size_t spec_lds(int chain_stride, int n, int strict) {
 constexpr int stream_stride(int chain_stride, int lanes, int strict) {
   return chain_stride + (strict ? kStrictRowsPerLane * lanes : 0);
 }
+// a streamed chain of abn_sweep_kernel: the scratch, plus two more dt tables (reflection, expansion and contraction each
+// have their own; the power table is shared)
+constexpr int sweep_stride(int chain_stride, int kp) { return chain_stride + 2 * kp; }
 // selection kernels (one model per workgroup): power table, dt1t2, one chunk of terms
 constexpr size_t select_lds(int tp, int kp) { return ((size_t)kPw * tp + kp + kSelChunk) * sizeof(double); }
 
@@ -119,9 +122,10 @@ constexpr int pick_lanes(int n, int requested, int chain_stride) {
 // ------------------------------------------------------------------------------------------------
 // the instantiation key: what tests/_kernel_matrix.py decodes from the mangled names
 // ------------------------------------------------------------------------------------------------
-enum KernelFamily { kFamFit = 0, kFamRefill = 1, kFamSpec = 2, kFamCost = 3 };
+enum KernelFamily { kFamFit = 0, kFamRefill = 1, kFamSpec = 2, kFamCost = 3, kFamSweep = 4 };
 struct KernelKey {
-  int family;  // abn_fit_kernel<G, R, TP, STRICT>, abn_fit_refill_kernel<G, R>, abn_fit_spec_kernel<R, STRICT, RESUME>, abn_cost_kernel<G>
+  int family;  // abn_fit_kernel<G, R, TP, STRICT>, abn_fit_refill_kernel<G, R>, abn_fit_spec_kernel<R, STRICT, RESUME>, abn_cost_kernel<G>,
+               // abn_sweep_kernel<R> (G = 64; R: 0 its deep loop, -1 its pair loop)
   int G;       // lanes per chain (speculative: 64)
   int R;       // rows per lane; fit: 0 the deep stream loop, -1 the pair-loop stream variant; cost: 0
   bool tp, strict, resume;
@@ -263,6 +267,7 @@ struct LaunchOffer {
   bool queue = false;    // a zeroed chain counter (FitArgs::queue): the launch may be persistent
   bool parking = false;  // ... and state, FIFO, tail list and status words: it may time-slice and hand its tail over
   int pass = 0;          // two-pass phase A: 1 = every chain up to kPhaseACap iterations, 2 = the parked ones to the end
+  bool sweep = false;    // opt-in (abn_plan_set_stream_sweep): a streamed launch of one wavefront per chain may take abn_sweep_kernel
 };
 
 struct LaunchRoute {
@@ -343,6 +348,21 @@ inline LaunchRoute route_launch(const PedigreeRoute& p, const PhaseRoute& ph, lo
     // rows shorter than one trip of the deep loop (kStreamBlocks x 4 rows x lanes) use the pair-loop variant; strict
     // order has one stream variant (chunks of 8 G rows)
     rows = (!p.strict && p.n < 2 * kStreamBlocks * kStreamVec * lanes) ? -1 : 0;
+    // Opt-in: one pass over the rows per iteration (abn_fit_sweep.hpp).  One wavefront per chain, tree order, one pass, and
+    // its larger footprint within the limit; every other launch keeps the route it has without the offer.  Same tree, same bits.
+    if (o.sweep && lanes == kWave && !p.strict && o.pass == 0) {
+      const int stride = sweep_stride(p.chain_stride, p.kp);
+      const size_t lds = (size_t)stride * sizeof(double);
+      if (lds <= lds_limit(lanes) && chains <= 0x7fffffffLL) {
+        r.kind = ABN_KERNEL_STREAM_SWEEP;
+        r.key = {kFamSweep, kWave, p.n < kSweepBlocks * kStreamVec * kWave ? -1 : 0, false, false, false};
+        r.chain_stride = stride;
+        r.lds = lds;
+        r.grid = (unsigned)chains;
+        r.block = kWave;
+        return r;
+      }
+    }
   }
   r.lds = (size_t)ng * (size_t)r.chain_stride * sizeof(double);
   if (r.lds > lds_limit(lanes)) return refuse(kLdsRefusal);

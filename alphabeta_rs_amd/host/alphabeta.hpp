@@ -65,7 +65,7 @@ using Progress = std::function<void(size_t)>;
 // ------------------------------------------------------------------------------------------------
 class Device {  // RAII abn_ctx
  public:
-  explicit Device(int ordinal = 0) {
+  explicit Device(int ordinal = 0) : ordinal_(ordinal) {
     int rc = abn_init(ordinal, nullptr, &ctx_);
     if (rc) throw Error(rc, std::string("abn_init: ") + abn_status_string(rc) + " (no CPU fallback exists)");
   }
@@ -75,14 +75,20 @@ class Device {  // RAII abn_ctx
   Device(const Device&) = delete;
   Device& operator=(const Device&) = delete;
   abn_ctx* get() const { return ctx_; }
+  int ordinal() const { return ordinal_; }
   void check(int rc, const char* what) const {
     if (rc) throw Error(rc, std::string(what) + ": " + abn_status_string(rc) + " — " + abn_last_error(ctx_));
   }
   abn_options options;  // seed, lanes, ... (abn_default_options)
+  // --stream-sweep: plans of streamed pedigrees read a chain's rows once per Nelder-Mead iteration
+  // (abn_plan_set_stream_sweep; same bytes).  Honoured where plans are created: run_on_pedigree (for pedigrees that
+  // stream; every other pedigree takes the path it takes without the flag), metaprofile::alphabeta_multiple
+  bool stream_sweep = false;
   void init_options() { abn_default_options(&options); }
 
  private:
   abn_ctx* ctx_ = nullptr;
+  int ordinal_ = 0;
 };
 
 // HIP ordinals the batched entry points spread their work over (--devices a,b,c; default: the one default device).
@@ -473,6 +479,7 @@ inline RunResult run_on_pedigree_multi(Pedigree pedigree, double p0uu, size_t it
     d[i] = pedigree.at(i, 3);
   }
   MultiDevice md(devs, dev.options, gens.data(), n, 1, iterations, iterations);
+  if (dev.stream_sweep) md.check(abn_multi_set_stream_sweep(md.get(), 1), "abn_multi_set_stream_sweep");
   md.check(abn_multi_set_windows(md.get(), d.data(), &p0uu, nullptr, nullptr), "abn_multi_set_windows");  // eqp = p0uu, weight 1
   md.check(abn_multi_run(md.get()), "abn_multi_run");
   double m[4];
@@ -487,6 +494,19 @@ inline RunResult run_on_pedigree_multi(Pedigree pedigree, double p0uu, size_t it
 // src/alphabeta.rs:23-59 with an already built pedigree
 inline RunResult run_on_pedigree(Pedigree pedigree, double p0uu, size_t iterations, const std::string& output) {
   if (device_list().size() > 1) return run_on_pedigree_multi(std::move(pedigree), p0uu, iterations, device_list());
+  if (Device& dev = default_device(); dev.stream_sweep) {
+    // The switch is a plan's, and only a streamed pedigree has launches it applies to (abn_reduction_tree marks those
+    // with the rows of a block in bits 8..15): such a pedigree runs as one plan on the device (same bits); every other
+    // pedigree takes the calls below, as without the flag.
+    const size_t n = pedigree.nrows();
+    std::vector<double> gens(n * 3);
+    for (size_t i = 0; i < n; ++i)
+      for (size_t c = 0; c < 3; ++c) gens[i * 3 + c] = pedigree.at(i, c);
+    int32_t tree = 0;
+    dev.check(abn_reduction_tree(&dev.options, gens.data(), (int32_t)n, &tree), "abn_reduction_tree");
+    if (((tree >> 8) & 0xff) != 0)
+      return run_on_pedigree_multi(std::move(pedigree), p0uu, iterations, {(int32_t)dev.ordinal()});
+  }
   auto [model, pred_div, residuals] = ab_neutral::run(pedigree, p0uu, p0uu, 1.0, iterations);
   auto [analysis, raw] = boot_model::run(pedigree, model, std::move(pred_div), std::move(residuals), p0uu, p0uu, 1.0,
                                          iterations, nullptr, output);

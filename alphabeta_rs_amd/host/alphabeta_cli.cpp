@@ -1,6 +1,6 @@
 // `alphabeta` command-line tool: same flags, console output and output files as the reference binary
 // (src/cli/alphabeta.rs:8-38, src/arguments.rs:93-152), running the ABneutral path on an MI355X through
-// libabneutral_hip.so.  Extra flags (not in the reference): --seed, --device(s), --lanes, --strict-order, --parse, and
+// libabneutral_hip.so.  Extra flags (not in the reference): --seed, --device(s), --lanes, --strict-order, --stream-sweep, --parse, and
 // --pedigree FILE --p0uu X to start from an existing pedigree file instead of nodelist/edgelist.
 #include <cstdlib>
 #include <cstring>
@@ -27,6 +27,8 @@ static void usage() {
       "      --lanes <G>                lanes of a wavefront per Nelder-Mead chain: 0 (auto), 8, 16, 32, 64\n"
       "      --strict-order             sum every cost's residuals serially in row order, exactly as the reference does\n"
       "                                 (src/structs.rs:206-213): bit-equal to a reference-order CPU run, ~1.5x the time\n"
+      "      --stream-sweep             pedigrees too large for the LDS: read a fit's rows once per Nelder-Mead iteration\n"
+      "                                 instead of once per cost evaluation; the same output files\n"
       "      --pedigree <FILE>          use this pedigree file (src/pedigree.rs:62-79 format) instead of building one\n"
       "      --p0uu <X>                 proportion of unmethylated sites at G0 (required with --pedigree)\n"
       "      --parse <host|device>      where the methylome files are parsed; the same output files [default: device]\n"
@@ -42,7 +44,7 @@ int main(int argc, char** argv) {
   double p0uu_given = -1.0;
   uint64_t seed = 20260101ull;
   int device = 0, lanes = 0;
-  bool strict_order = false;
+  bool strict_order = false, stream_sweep = false;
   std::string devices_arg;
   auto need = [&](int& i) -> const char* {
     if (i + 1 >= argc) {
@@ -70,6 +72,7 @@ int main(int argc, char** argv) {
     else if (a == "--devices") devices_arg = val();
     else if (a == "--lanes") lanes = std::atoi(val().c_str());
     else if (a == "--strict-order") strict_order = true;
+    else if (a == "--stream-sweep") stream_sweep = true;
     else if (a == "--pedigree") ped_file = val();
     else if (a == "--p0uu") p0uu_given = std::strtod(val().c_str(), nullptr);
     else if (a == "--parse") {
@@ -118,6 +121,7 @@ int main(int argc, char** argv) {
     dev.options.seed = seed;
     dev.options.lanes_per_chain = lanes;
     dev.options.strict_order = strict_order ? 1 : 0;
+    dev.stream_sweep = stream_sweep;
     RunResult r;
     if (!ped_file.empty()) {
       if (!(p0uu_given > 0.0 && p0uu_given < 1.0)) {

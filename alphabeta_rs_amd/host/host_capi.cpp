@@ -491,4 +491,22 @@ int abh_route_launch(int n, int k, int t, int lanes, int strict, int spec, int p
   std::memcpy(out, v, sizeof v);
   return r.status;
 }
+// abh_route_launch with abn::LaunchOffer::sweep as one more argument (abn_plan_set_stream_sweep); family 4 is the sweep
+// kernel's.  Same out[15].
+int abh_route_launch_sweep(int n, int k, int t, int lanes, int strict, int spec, int phase_lanes, long long chains, int cus,
+                           int queue, int parking, int pass, int sweep, long long* out, char* err, int errcap) {
+  const abn::PedigreeRoute p = abh_pedigree(n, k, t, lanes, strict);
+  abn::LaunchOffer o;
+  o.queue = queue != 0;
+  o.parking = parking != 0;
+  o.pass = pass;
+  o.sweep = sweep != 0;
+  const abn::LaunchRoute r = abn::route_launch(p, abn::PhaseRoute{spec != 0, phase_lanes, false}, chains, cus, o);
+  if (err && errcap > 0) std::strncpy(err, r.error ? r.error : "", (size_t)errcap - 1), err[errcap - 1] = 0;
+  const long long v[15] = {r.kind, r.key.family, r.key.G, r.key.R, r.key.tp, r.key.strict, r.key.resume, r.grid, r.block,
+                           (long long)r.lds, r.chain_stride, r.tree, r.quantum, r.tail_cap,
+                           r.tail_cap > 0 ? abn::route_tail_resume(p, r.tail_cap).key.R : 0};
+  std::memcpy(out, v, sizeof v);
+  return r.status;
+}
 }

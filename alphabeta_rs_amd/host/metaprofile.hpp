@@ -153,6 +153,7 @@ inline Output fit_windows(const WindowArgs& args, std::vector<Win> wins, const s
     {
       MultiDevice md(devs, dev.options, gens.data(), N, W, S, B);
       md.check(abn_multi_set_window_ids(md.get(), ids.data()), "abn_multi_set_window_ids");
+      if (dev.stream_sweep) md.check(abn_multi_set_stream_sweep(md.get(), 1), "abn_multi_set_stream_sweep");
       md.check(abn_multi_set_windows(md.get(), D.data(), p0uu.data(), nullptr, nullptr), "abn_multi_set_windows");
       md.check(abn_multi_run(md.get()), "abn_multi_run");
       int rc = abn_multi_download(md.get(), mod.data(), nullptr, nullptr, raw.data(), nullptr, nullptr, best.data());

@@ -21,6 +21,7 @@ int main(int argc, char** argv) {
   uint64_t seed = 20260101ull;
   int device = 0;
   std::string devices_arg;
+  bool stream_sweep = false;
   for (int i = 1; i < argc; ++i) {
     const std::string f = argv[i];
     auto val = [&]() -> std::string {
@@ -47,6 +48,7 @@ int main(int argc, char** argv) {
     else if (f == "--nodes") a.nodes = val();
     else if (f == "--edges") a.edges = val();
     else if (f == "--cutoff-gene-length") a.cutoff_gene_length = true;
+    else if (f == "--stream-sweep") stream_sweep = true;
     else if (f == "-i" || f == "--invert") a.invert = true;
     else if (f == "--parse") {
       const std::string where = val();
@@ -71,7 +73,9 @@ int main(int argc, char** argv) {
                 "       [--methylome DIR --genome FILE --nodes FILE --edges FILE [--cutoff-gene-length]]\n"
                 "                            extract the windows from whole methylomes on the device (no window directories)\n"
                 "       [--parse host|device] where the methylome files are parsed; the same output files [default: device]\n"
-                "       [--genes host|device] where every site's gene is chosen; the same output files [default: device]");
+                "       [--genes host|device] where every site's gene is chosen; the same output files [default: device]\n"
+                "       [--stream-sweep]     pedigrees too large for the LDS: read a fit's rows once per Nelder-Mead iteration\n"
+                "                            instead of once per cost evaluation; the same output files");
       return 0;
     } else {
       std::fprintf(stderr, "error: unexpected argument '%s' found\n", argv[i]);
@@ -104,6 +108,7 @@ int main(int argc, char** argv) {
     Device& dev = default_device(device);
     if (device_list().empty()) device_list().push_back(device);
     dev.options.seed = seed;
+    dev.stream_sweep = stream_sweep;
     if (in_memory) {
       const auto ex = metaprofile::extract_in_memory(a);
       const auto out = metaprofile::alphabeta_multiple_in_memory(a, ex);

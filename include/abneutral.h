@@ -137,6 +137,13 @@ int abn_cost_batch(abn_ctx* ctx, const abn_options* opts, const double* pedigree
 int abn_fit_batch(abn_ctx* ctx, const abn_options* opts, const double* pedigree, int32_t n_rows,
                   double p_uu0, double eqp, double eqp_weight, const double* simplex0, int64_t f,
                   const double* dobs_rows, int32_t max_iters, double* best, abn_fit_info* info);
+/* The same fits on the sweep kernel (abn_plan_set_stream_sweep): one pass over the rows per Nelder-Mead iteration.  Same
+ * outputs, bit for bit.  passes (nullable): passes over the rows, summed over the fits.  ABN_ERR_INVALID_ARG when the
+ * pedigree and the options do not route to that kernel (an LDS-resident pedigree, strict order, fewer than 64 lanes per
+ * chain, or a footprint beyond the LDS of a CU). */
+int abn_fit_batch_sweep(abn_ctx* ctx, const abn_options* opts, const double* pedigree, int32_t n_rows,
+                        double p_uu0, double eqp, double eqp_weight, const double* simplex0, int64_t f,
+                        const double* dobs_rows, int32_t max_iters, double* best, abn_fit_info* info, int64_t* passes);
 
 /* ------------------------------------------------------------------ deterministic inputs
  * Model::new x5 per start (src/structs.rs:78-96): simplex0[S x 5 x 4] for `window`. Host arithmetic. */
@@ -475,6 +482,15 @@ int abn_plan_set_early_bootstraps(abn_plan* plan, int32_t mode);
 /* out4 = the plan is eligible (0 / 1), its quorum, and of the last abn_plan_run (0 when it did not launch phase B early):
  * starts that were still running at the quorum, miss (0 / 1).  Synchronises like abn_plan_sync. */
 int abn_plan_early_bootstraps(abn_plan* plan, int32_t* out4);
+/* Streamed pedigrees: sweep a chain's rows once per Nelder-Mead iteration instead of once per cost evaluation — the
+ * reflection, the expansion and the contraction of an iteration are evaluated in one pass, each with the additions of the
+ * per-evaluation kernel in the same order.  Results are the same bytes either way.  mode: 0 = off (the default), 1 = both
+ * phases of later abn_plan_run / abn_plan_run_phase calls take the sweep kernel where the launch streams with one wavefront
+ * per chain in tree order and one pass; every other launch runs what it runs at mode 0. */
+int abn_plan_set_stream_sweep(abn_plan* plan, int32_t mode);
+/* out4 = the mode, whether phase A of the last run used the sweep kernel (0 / 1), the same for phase B, and the passes
+ * over the rows its sweep launches counted.  Synchronises like abn_plan_sync. */
+int abn_plan_stream_sweep(abn_plan* plan, int64_t* out4);
 /* HIP-event time of the most recent launch of each kernel, in milliseconds (fit A, select, fit B) */
 int abn_plan_kernel_ms(abn_plan* plan, double* ms3);
 /* device pointer of raw[W x B x 7] (for an RCCL gather by the caller) and optional rebinding to a
@@ -510,6 +526,7 @@ int abn_plan_device_bytes(abn_plan* plan, int64_t* bytes);
 #define ABN_KERNEL_PERSISTENT 3   /* resident, persistent wavefronts with a chain queue and time slicing     */
 #define ABN_KERNEL_STREAM 4       /* rows re-read from HBM every evaluation                                  */
 #define ABN_KERNEL_TWO_PASS 5     /* resident, long chains parked and resumed in a second launch             */
+#define ABN_KERNEL_STREAM_SWEEP 6 /* streamed, rows read once per iteration (abn_plan_set_stream_sweep)      */
 int abn_plan_last_kernels(abn_plan* plan, int32_t* out4);
 
 /* ------------------------------------------------------------------ (5) one process, several GPUs of a node
@@ -532,6 +549,8 @@ int abn_multi_destroy(abn_multi* m);
 const char* abn_multi_last_error(const abn_multi* m);
 /* ids[W] for ALL windows, before abn_multi_set_windows (as abn_plan_set_window_ids); NULL restores the default */
 int abn_multi_set_window_ids(abn_multi* m, const uint32_t* ids);
+/* abn_plan_set_stream_sweep on every device's plan */
+int abn_multi_set_stream_sweep(abn_multi* m, int32_t mode);
 /* D[W x N], p0uu[W], optional eqp[W], eqp_weight[W] for ALL windows (as abn_plan_set_windows) */
 int abn_multi_set_windows(abn_multi* m, const double* d_obs, const double* p0uu, const double* eqp,
                           const double* eqp_weight);
