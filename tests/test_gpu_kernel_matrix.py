@@ -19,17 +19,10 @@ from alphabeta_rs_amd import synthetic
 import _kernel_matrix as KM
 import _route_model as RM
 from _parity import assert_fits_equal, check_selection_and_boot, run_plan
+from _parity import sample_chains as _sample
 
 P0 = synthetic.TRUE_P0UU
 STATUS_PARKED = 4
-
-
-def _sample(n, lanes, seed=20261016, extra=5):
-    """chain indices: first, last, the first chain of the last (partly filled) wavefront, and `extra` seeded others"""
-    ng = RM.WAVE // lanes
-    pick = {0, n - 1, ((n - 1) // ng) * ng}
-    pick |= set(np.random.default_rng(seed).choice(n, min(extra, n), replace=False).tolist())
-    return np.array(sorted(pick))
 
 
 def _check_shards(abn, ctx, ped, c, o, out, lanes, label):

@@ -257,10 +257,16 @@ def test_select_best_and_bootstrap_rows_standalone(abn, gpu_ctx, golden, oracle)
     ped, p0 = golden["sparse"], golden["r_p0uu"]
     rng = np.random.default_rng(12)
     models = np.array([5.8e-05, 6.5e-03, 0.03, 6e-05]) * rng.uniform(0.5, 1.5, (9, 4))
-    models[3] = models[7]                       # an exact tie: the lower index must win (stable sort)
     models[5, 0] = np.nan                       # NaN LSE never wins
+    best = oracle.select_best(ped, p0, models)[0]
+    assert best not in (3, 5, 7)
+    displaced = models[3].copy()
+    models[3] = models[7] = models[best]        # an exact tie AT THE MINIMUM: the lower index must win (stable sort)
+    models[best] = displaced                    # ... and the minimum is nowhere else
     k, model, pred, resid, lse = gpu_ctx.select_best(ped, p0, models)
     wk, wmodel, wpred, wresid, wlse = oracle.select_best(ped, p0, models)
+    others = np.delete(wlse, [3, 5, 7])
+    assert wk == 3 and wlse[3] == wlse[7] and np.all(others > wlse[3])
     assert k == wk and np.array_equal(model, wmodel)
     assert np.array_equal(pred, wpred) and np.array_equal(resid, wresid)
     assert np.array_equal(lse[~np.isnan(wlse)], wlse[~np.isnan(wlse)]) and np.isnan(lse[5])
