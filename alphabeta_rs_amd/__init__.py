@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "abn_windows_packed", "abn_windows_packed_device_ptr", "abn_windows_pairwise",
     "abn_sites_parse", "abn_sites_destroy", "abn_sites_info", "abn_sites_fetch", "abn_sites_deferred",
     "abn_genes_create", "abn_genes_destroy", "abn_genes_choose", "abn_genes_choose_dev", "abn_windows_create_sites",
+    "abn_sites_parse_dev", "abn_sites_flagged", "abn_sites_insert", "abn_windows_create_parsed", "abn_windows_merge_ms",
     "abn_plan_set_stream_sweep", "abn_plan_stream_sweep", "abn_multi_set_stream_sweep", "abn_fit_batch_sweep",
 ]
 
@@ -199,6 +200,12 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_sites_info.argtypes = [vp, i64p, i64p, i64p, dp]
     L.abn_sites_fetch.argtypes = [vp, i64p, C.POINTER(C.c_int32), u32p, u32p, u8p, dp, u8p, u8p, dp]
     L.abn_sites_deferred.argtypes = [vp, i64p, i64p, i64p]
+    L.abn_sites_parse_dev.argtypes = [vp, C.c_char_p, C.c_int64, C.POINTER(SitesParams), C.POINTER(vp)]
+    L.abn_sites_flagged.argtypes = [vp, i64p, i64p]
+    L.abn_sites_insert.argtypes = [vp, C.c_int64, i64p, C.POINTER(C.c_int32), u32p, u32p, u8p, dp, u8p, dp]
+    L.abn_windows_create_parsed.argtypes = [vp, C.POINTER(WindowsParams), vp, C.POINTER(GeneRule), C.c_double, C.c_int32,
+                                            C.POINTER(vp), C.POINTER(vp)]
+    L.abn_windows_merge_ms.argtypes = [vp, dp]
     i32p = C.POINTER(C.c_int32)
     L.abn_genes_create.argtypes = [vp, C.c_int32, i32p, i32p, i64p, u32p, u32p, u8p, C.POINTER(vp)]
     L.abn_genes_destroy.argtypes = [vp]
@@ -636,20 +643,23 @@ class Context:
         p = SitesParams(slab_bytes, skip_lines, 0)
         h = C.c_void_p()
         self._check(self._L.abn_sites_parse(self._h, text, len(text), C.byref(p), C.byref(h)))
+        s = Sites(self, h)
         try:
-            n, nd, nl, ms = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
-            self._check(self._L.abn_sites_info(h, C.byref(n), C.byref(nd), C.byref(nl), C.byref(ms)))
-            kinds = {"line": np.int64, "chromosome": np.int32, "start": np.uint32, "end": np.uint32, "strand": np.uint8,
-                     "posteriormax": np.float64, "status": np.uint8, "status_flag": np.uint8, "meth_lvl": np.float64}
-            sites = {k: np.zeros(n.value, dtype=t) for k, t in kinds.items()}
-            self._check(self._L.abn_sites_fetch(h, *(a.ctypes.data_as(t) for a, t in
-                                                     zip(sites.values(), self._L.abn_sites_fetch.argtypes[1:]))))
-            deferred = {k: np.zeros(nd.value, dtype=np.int64) for k in ("line", "offset", "length")}
-            self._check(self._L.abn_sites_deferred(h, *(a.ctypes.data_as(C.POINTER(C.c_int64)) for a in deferred.values())))
-            sites["n_lines"], sites["kernel_ms"] = nl.value, ms.value
+            sites, deferred = s.fetch(), s.deferred()
+            sites.update(s.info())
+            del sites["n_sites"], sites["n_deferred"]
             return sites, deferred
         finally:
-            self._L.abn_sites_destroy(h)
+            s.close()
+
+    def parse_sites_resident(self, text: bytes, *, skip_lines: int = 1, slab_bytes: int = 0) -> "Sites":
+        """parse_sites with the records left on the device (abn_sites_parse_dev): a Sites handle for Windows.from_parsed.
+        Its deferred() lines are for the caller's parser; those it accepts go back in with insert(), once."""
+        text = bytes(text)
+        p = SitesParams(slab_bytes, skip_lines, 0)
+        h = C.c_void_p()
+        self._check(self._L.abn_sites_parse_dev(self._h, text, len(text), C.byref(p), C.byref(h)))
+        return Sites(self, h)
 
     def choose_genes(self, genes: "Genes", site_offset, chromosome, start, end, strand, *, cutoff,
                      cutoff_gene_length=False):
@@ -842,6 +852,66 @@ def _site_arrays(site_offset, chromosome, start, end, strand):
                  ((chromosome, np.int32), (start, np.uint32), (end, np.uint32), (strand, np.uint8))]
 
 
+class Sites:
+    """abn_sites: the parse results of one methylome text (Context.parse_sites_resident: the records resident on the
+    device until close())."""
+
+    KINDS = {"line": np.int64, "chromosome": np.int32, "start": np.uint32, "end": np.uint32, "strand": np.uint8,
+             "posteriormax": np.float64, "status": np.uint8, "status_flag": np.uint8, "meth_lvl": np.float64}
+
+    def __init__(self, ctx: "Context", handle):
+        self.ctx, self._L, self._h = ctx, ctx._L, handle
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.abn_sites_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{n_sites (the device's records plus the inserted ones), n_deferred, n_lines, kernel_ms}"""
+        n, nd, nl, ms = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+        self.ctx._check(self._L.abn_sites_info(self._h, C.byref(n), C.byref(nd), C.byref(nl), C.byref(ms)))
+        return {"n_sites": n.value, "n_deferred": nd.value, "n_lines": nl.value, "kernel_ms": ms.value}
+
+    def deferred(self):
+        """{line, offset, length} of the lines left to the host's parser, in file order"""
+        out = {k: np.zeros(self.info()["n_deferred"], dtype=np.int64) for k in ("line", "offset", "length")}
+        self.ctx._check(self._L.abn_sites_deferred(self._h, *(a.ctypes.data_as(C.POINTER(C.c_int64)) for a in out.values())))
+        return out
+
+    def flagged(self) -> np.ndarray:
+        """the file lines of the records whose status byte was none of M, I, U, ascending"""
+        n = C.c_int64()
+        self.ctx._check(self._L.abn_sites_flagged(self._h, C.byref(n), None))
+        out = np.zeros(n.value, dtype=np.int64)
+        self.ctx._check(self._L.abn_sites_flagged(self._h, None, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
+    def insert(self, line, chromosome, start, end, strand, posteriormax, status, meth_lvl):
+        """the deferred lines the host's parser accepted, ascending by line; once per handle (abn_sites_insert)"""
+        arrays = [np.ascontiguousarray(a, dtype=t).reshape(-1) for a, t in
+                  zip((line, chromosome, start, end, strand, posteriormax, status, meth_lvl),
+                      (np.int64, np.int32, np.uint32, np.uint32, np.uint8, np.float64, np.uint8, np.float64))]
+        if len({a.shape[0] for a in arrays}) != 1:
+            raise ValueError("the arrays are of one length")
+        self.ctx._check(self._L.abn_sites_insert(self._h, arrays[0].shape[0], *(
+            a.ctypes.data_as(t) for a, t in zip(arrays, self._L.abn_sites_insert.argtypes[2:]))))
+
+    def fetch(self):
+        """the sites in file order as a dict of arrays (Context.parse_sites' fields); a resident handle downloads them and
+        merges the inserted records in by line"""
+        sites = {k: np.zeros(self.info()["n_sites"], dtype=t) for k, t in self.KINDS.items()}
+        self.ctx._check(self._L.abn_sites_fetch(self._h, *(a.ctypes.data_as(t) for a, t in
+                                                           zip(sites.values(), self._L.abn_sites_fetch.argtypes[1:]))))
+        return sites
+
+
 class Genes:
     """abn_genes: a gene annotation resident on the device.  lists = [(chromosome, kind, start, end, strand), ..]: the
     genes of one chromosome (0..255, 256 = M, 257 = C) and kind (0 sense, 1 antisense, 2 combined: GenesByStrand,
@@ -934,6 +1004,35 @@ class Windows:
         ctx._check(self._L.abn_windows_info(h, C.byref(W), C.byref(stride), C.byref(ns)))
         self.W, self.row_stride, self.n_sites = W.value, stride.value, ns.value
         return self
+
+    @classmethod
+    def from_parsed(cls, ctx: Context, genes: Genes, sites_list, *, posterior_max_filter, cutoff,
+                    cutoff_gene_length=False, step, size, absolute, counts):
+        """The handle from resident parse results (Context.parse_sites_resident, one Sites per methylome, their deferred
+        lines decided and inserted): merged in file order, the genes chosen and the windows placed on the device, no site
+        record coming back to the host (abn_windows_create_parsed).  The Sites are not consumed."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self._L = ctx._L
+        sites_list = list(sites_list)
+        self.n_samples = len(sites_list)
+        p = WindowsParams(cutoff, step, size, 1 if absolute else 0, *map(int, counts))
+        rule = GeneRule(cutoff, 1 if cutoff_gene_length else 0)
+        handles = (C.c_void_p * max(self.n_samples, 1))(*(s._h for s in sites_list))
+        h = C.c_void_p()
+        ctx._check(self._L.abn_windows_create_parsed(ctx._h, C.byref(p), genes._h, C.byref(rule), posterior_max_filter,
+                                                     self.n_samples, handles, C.byref(h)))
+        self._h = h
+        W, stride, ns = C.c_int32(), C.c_int64(), C.c_int64()
+        ctx._check(self._L.abn_windows_info(h, C.byref(W), C.byref(stride), C.byref(ns)))
+        self.W, self.row_stride, self.n_sites = W.value, stride.value, ns.value
+        return self
+
+    def merge_ms(self) -> np.ndarray:
+        """the HIP-event ms of from_parsed's two merge kernels (fields, insert); zeros for the other forms"""
+        ms = np.zeros(2)
+        self.ctx._check(self._L.abn_windows_merge_ms(self._h, _dp(ms)))
+        return ms
 
     def close(self):
         if getattr(self, "_h", None):

@@ -86,7 +86,8 @@ def build_host(force: bool = False, verbose: bool = False) -> Path:
     srcs = [HOST / "alphabeta_cli.cpp", HOST / "alphabeta.hpp", HOST / "pedigree_build.hpp", HOST / "windows_extract.hpp",
             HOST / "host_capi.cpp",
             HOST / "metaprofile.hpp", HOST / "metaprofile_cli.cpp", HOST / "reference_tests.cpp",
-            CSRC / "abn_route.hpp", CSRC / "abn_constants.hpp", CSRC / "abn_parse.hpp", CSRC / "abn_genes.hpp"]  # host_capi.cpp exports the launch policy to the tests
+            CSRC / "abn_route.hpp", CSRC / "abn_constants.hpp", CSRC / "abn_parse.hpp", CSRC / "abn_genes.hpp",
+            CSRC / "abn_sites_merge.hpp"]  # host_capi.cpp exports the launch policy to the tests
     newest = max(p.stat().st_mtime for p in srcs)
     CLI.parent.mkdir(exist_ok=True)
     common = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-I", str(PKG.parent / "include")]

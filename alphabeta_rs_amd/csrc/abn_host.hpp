@@ -197,4 +197,12 @@ int genes_choose_dev(abn_genes* h, const abn_gene_rule* rule, int32_t n_samples,
                      const int32_t* dchrom, const uint32_t* dstart, const uint32_t* dend, const uint8_t* dstrand,
                      uint32_t* dgene_start, uint32_t* dgene_end, uint8_t* dflags, double* kernel_ms);
 abn_ctx* genes_ctx(const abn_genes* h);
+// abn_sites.hip, for abn_windows_create_parsed (abn_windows.hip).  The context of a resident handle (null: host form);
+// its sites once the inserted records are in (-1: host form, or deferred lines without abn_sites_insert); and the merge
+// (abn_sites_merge.hpp) of one sample into the arrays at its first site, on the context's stream, nothing waited for:
+// the fields kernel of every chunk (inserted = false) or the insert kernel (true).
+abn_ctx* sites_ctx(const abn_sites* h);
+int64_t sites_merged_count(const abn_sites* h);
+int sites_merge_dev(const abn_sites* h, bool inserted, double filter, int32_t* dchrom, uint32_t* dstart, uint32_t* dend,
+                    uint8_t* dstrand, uint8_t* dcode, double* dlevel);
 }  // namespace abn

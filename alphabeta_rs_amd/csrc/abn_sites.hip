@@ -1,22 +1,15 @@
 // abn_sites_*: methylome text -> site records on the device (src/methylation_site.rs:146-362 for every line of a file,
 // the loops of src/windows.rs:303-338 and src/pedigree.rs:138-178 in front of it).  Kernels: abn_parse_kernels.hpp; the
-// line parser they share with the host: abn_parse.hpp.
+// line parser they share with the host: abn_parse.hpp.  The resident form (abn_sites_parse_dev, abn_sites_insert) keeps the
+// records on the device for abn_windows_create_parsed (abn_windows.hip); its merge kernels: abn_sites_merge.hpp.
 #include "abn_host.hpp"
 #include "abn_parse_kernels.hpp"
+#define ABN_SITES_MERGE_KERNELS
+#include "abn_sites_merge.hpp"
 
 using namespace abn;
 
 constexpr int64_t kSitesDefaultSlab = (int64_t)64 << 20, kSitesMaxSlab = (int64_t)1 << 30;
-
-struct abn_sites {
-  std::vector<int64_t> line, dline, doffset, dlength;
-  std::vector<int32_t> chromosome;
-  std::vector<uint32_t> start, end;
-  std::vector<uint8_t> strand, status, status_flag;
-  std::vector<double> posteriormax, meth_lvl;
-  int64_t n_lines = 0;
-  double kernel_ms = 0.0;
-};
 
 namespace {
 
@@ -35,6 +28,44 @@ struct RecordBufs {
   ParseDeferred deferred() { return ParseDeferred{dline.p, doffset.p, dlength.p}; }
 };
 
+struct SiteChunk {  // a slab's compacted records, resident (abn_sites_parse_dev)
+  RecordBufs rec;
+  int64_t n = 0, line0 = 0, n_lines = 0, before = 0;
+  MergeChunk ref() const {
+    return MergeChunk{rec.line.p, rec.meta.p, rec.start.p, rec.end.p, rec.pm.p, rec.ml.p, n, line0, n_lines, before};
+  }
+};
+
+}  // namespace
+
+// The host form (abn_sites_parse) holds the records in the vectors; the resident form (abn_sites_parse_dev: ctx is set)
+// holds them in `chunks` on the device and, after abn_sites_insert, the host-decided records in the same vectors and in
+// the i* buffers.  The deferred triples, n_lines and kernel_ms are the same in both.
+struct abn_sites {
+  std::vector<int64_t> line, dline, doffset, dlength;
+  std::vector<int32_t> chromosome;
+  std::vector<uint32_t> start, end;
+  std::vector<uint8_t> strand, status, status_flag;
+  std::vector<double> posteriormax, meth_lvl;
+  int64_t n_lines = 0;
+  double kernel_ms = 0.0;
+  // resident form
+  abn_ctx* ctx = nullptr;
+  int device = -1;
+  std::vector<std::unique_ptr<SiteChunk>> chunks;  // one per slab, in file order
+  int64_t n_records = 0;                           // over all chunks
+  std::vector<int64_t> flagged;                    // the file lines of the records with a status_flag
+  bool inserted = false;
+  DevBuf<MergeChunk> dchunks;
+  DevBuf<long long> iline;
+  DevBuf<int32_t> ichunk, ichromosome;
+  DevBuf<uint32_t> istart, iend;
+  DevBuf<uint8_t> istrand, istatus;
+  DevBuf<double> ipm, iml;
+};
+
+namespace {
+
 // where the slab that begins at `from` ends: behind the last '\n' of its slab_bytes bytes, or — a line longer than the
 // slab — behind that line
 size_t slab_end(const char* text, size_t n, size_t from, size_t slab_bytes) {
@@ -50,8 +81,9 @@ size_t slab_end(const char* text, size_t n, size_t from, size_t slab_bytes) {
   return fwd ? (size_t)((const char*)fwd - text) + 1 : n;
 }
 
-// one slab [text, text + n): its lines from skip on, appended to h; line numbers and offsets are the file's
-int parse_slab(abn_ctx* c, abn_sites* h, const char* text, size_t n, int64_t skip, int64_t line0, int64_t byte0,
+// one slab [text, text + n): its lines from skip on, appended to h — to its vectors, or (resident) as one more chunk with
+// only the deferred triples and the flagged records' lines coming back; line numbers and offsets are the file's
+int parse_slab(abn_ctx* c, abn_sites* h, bool resident, const char* text, size_t n, int64_t skip, int64_t line0, int64_t byte0,
                EventPair& ev) {
   const uint32_t n_pieces = (uint32_t)((n + kParsePieceBytes - 1) / kParsePieceBytes);
   const uint32_t n_blocks = (n_pieces + kParseThreads - 1) / kParseThreads;
@@ -78,6 +110,14 @@ int parse_slab(abn_ctx* c, abn_sites* h, const char* text, size_t n, int64_t ski
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint32_t n_lines = n_newlines + (text[n - 1] != '\n' ? 1u : 0u);
   h->n_lines += n_lines;
+  SiteChunk* chunk = nullptr;
+  if (resident) {
+    h->chunks.emplace_back(new SiteChunk);
+    chunk = h->chunks.back().get();
+    chunk->line0 = line0;
+    chunk->n_lines = n_lines;
+    chunk->before = h->n_records;
+  }
   if ((int64_t)n_lines <= skip) return ABN_OK;
   const uint32_t first = (uint32_t)skip, n_runs = (n_lines - first + kParseRun - 1) / kParseRun;
   const uint32_t stride = n_runs + 1;
@@ -100,14 +140,62 @@ int parse_slab(abn_ctx* c, abn_sites* h, const char* text, size_t n, int64_t ski
   HIPCHK(c, hipMemcpyAsync(&n_def, dcount.p + stride + n_runs, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (n_rec == 0 && n_def == 0) return ABN_OK;
-  HIPCHK(c, out.alloc(n_rec, n_def));
+  RecordBufs& rec = resident ? chunk->rec : out;  // the records stay with the handle; the deferred triples never do
+  if (resident) HIPCHK(c, rec.alloc(n_rec, 0));
+  HIPCHK(c, out.alloc(resident ? 0 : n_rec, n_def));
+  const uint32_t flag_blocks =
+      resident ? (uint32_t)std::min<size_t>(kMergeFlagBlocks, ((size_t)n_rec + kMergeThreads - 1) / kMergeThreads) : 0u;
+  DevBuf<uint32_t> dflagged;
+  HIPCHK(c, dflagged.alloc(flag_blocks));
   if (int rc = ev.begin(c, true)) return rc;
   hipLaunchKernelGGL(abn_parse_compact_kernel, dim3(n_runs), dim3(kParseThreads), 0, c->stream, run.records(),
-                     run.deferred(), dcount.p, stride, out.records(), out.deferred());
+                     run.deferred(), dcount.p, stride, rec.records(), out.deferred());
   HIPCHK(c, hipGetLastError());
+  if (flag_blocks) {
+    hipLaunchKernelGGL(abn_sites_flagged_kernel, dim3(flag_blocks), dim3(kMergeThreads), 0, c->stream, rec.meta.p,
+                       (long long)n_rec, dflagged.p);
+    HIPCHK(c, hipGetLastError());
+  }
   if (int rc = timed()) return rc;
-  std::vector<uint32_t> line(n_rec), meta(n_rec), start(n_rec), end(n_rec), dline(n_def), doff(n_def), dlen(n_def);
-  const size_t at = h->line.size(), dat = h->dline.size();
+  std::vector<uint32_t> dline(n_def), doff(n_def), dlen(n_def);
+  const size_t dat = h->dline.size();
+  auto take_deferred = [&]() {
+    h->dline.resize(dat + n_def);
+    h->doffset.resize(dat + n_def);
+    h->dlength.resize(dat + n_def);
+    for (size_t i = 0; i < n_def; ++i) {
+      h->dline[dat + i] = line0 + (int64_t)dline[i];
+      h->doffset[dat + i] = byte0 + (int64_t)doff[i];
+      h->dlength[dat + i] = (int64_t)dlen[i];
+    }
+  };
+  if (resident) {
+    std::vector<uint32_t> partial(flag_blocks);
+    if (flag_blocks)
+      HIPCHK(c, hipMemcpyAsync(partial.data(), dflagged.p, dflagged.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (n_def) {
+      HIPCHK(c, hipMemcpyAsync(dline.data(), out.dline.p, 4 * (size_t)n_def, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(doff.data(), out.doffset.p, 4 * (size_t)n_def, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(dlen.data(), out.dlength.p, 4 * (size_t)n_def, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    chunk->n = n_rec;
+    h->n_records += n_rec;
+    take_deferred();
+    uint64_t n_flagged = 0;
+    for (uint32_t v : partial) n_flagged += v;
+    if (n_flagged) {  // rare: the warning of src/methylation_site.rs:107-112 names these lines
+      std::vector<uint32_t> line(n_rec), meta(n_rec);
+      HIPCHK(c, hipMemcpyAsync(line.data(), rec.line.p, 4 * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(meta.data(), rec.meta.p, 4 * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      for (size_t i = 0; i < n_rec; ++i)
+        if ((meta[i] >> 24) & 0xfu) h->flagged.push_back(line0 + (int64_t)line[i]);
+    }
+    return ABN_OK;
+  }
+  std::vector<uint32_t> line(n_rec), meta(n_rec), start(n_rec), end(n_rec);
+  const size_t at = h->line.size();
   h->posteriormax.resize(at + n_rec);
   h->meth_lvl.resize(at + n_rec);
   if (n_rec) {
@@ -139,21 +227,13 @@ int parse_slab(abn_ctx* c, abn_sites* h, const char* text, size_t n, int64_t ski
     h->status[at + i] = (uint8_t)((m >> 20) & 0xfu);
     h->status_flag[at + i] = (uint8_t)((m >> 24) & 0xfu);
   }
-  h->dline.resize(dat + n_def);
-  h->doffset.resize(dat + n_def);
-  h->dlength.resize(dat + n_def);
-  for (size_t i = 0; i < n_def; ++i) {
-    h->dline[dat + i] = line0 + (int64_t)dline[i];
-    h->doffset[dat + i] = byte0 + (int64_t)doff[i];
-    h->dlength[dat + i] = (int64_t)dlen[i];
-  }
+  take_deferred();
   return ABN_OK;
 }
 
-}  // namespace
-
-extern "C" int abn_sites_parse(abn_ctx* c, const char* text, int64_t n_bytes, const abn_sites_params* params,
-                               abn_sites** out) {
+// abn_sites_parse and abn_sites_parse_dev: the checks, the slabs
+int sites_parse(abn_ctx* c, const char* text, int64_t n_bytes, const abn_sites_params* params, bool resident,
+                abn_sites** out) {
   if (!c) return ABN_ERR_INVALID_ARG;
   if (out) *out = nullptr;
   if (!out || n_bytes < 0 || (n_bytes > 0 && !text)) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
@@ -164,6 +244,7 @@ extern "C" int abn_sites_parse(abn_ctx* c, const char* text, int64_t n_bytes, co
   PoolScope pool_scope(c);
   std::unique_ptr<abn_sites> h(new (std::nothrow) abn_sites);
   if (!h) return set_err(c, ABN_ERR_HIP, "out of host memory");
+  if (resident) h->ctx = c, h->device = c->device;
   EventPair ev;
   try {
     const size_t n = (size_t)n_bytes;
@@ -172,7 +253,7 @@ extern "C" int abn_sites_parse(abn_ctx* c, const char* text, int64_t n_bytes, co
       if (to - from > (size_t)kSitesMaxSlab + (size_t)kSitesMaxSlab)
         return set_err(c, ABN_ERR_INVALID_ARG, "a line of more than 2 GiB");
       const int64_t before = h->n_lines;
-      if (int rc = parse_slab(c, h.get(), text + from, to - from, skip, before, (int64_t)from, ev)) return rc;
+      if (int rc = parse_slab(c, h.get(), resident, text + from, to - from, skip, before, (int64_t)from, ev)) return rc;
       skip = std::max<int64_t>(0, skip - (h->n_lines - before));
       from = to;
     }
@@ -183,8 +264,21 @@ extern "C" int abn_sites_parse(abn_ctx* c, const char* text, int64_t n_bytes, co
   return ABN_OK;
 }
 
+}  // namespace
+
+extern "C" int abn_sites_parse(abn_ctx* c, const char* text, int64_t n_bytes, const abn_sites_params* params,
+                               abn_sites** out) {
+  return sites_parse(c, text, n_bytes, params, false, out);
+}
+
+extern "C" int abn_sites_parse_dev(abn_ctx* c, const char* text, int64_t n_bytes, const abn_sites_params* params,
+                                   abn_sites** out) {
+  return sites_parse(c, text, n_bytes, params, true, out);
+}
+
 extern "C" int abn_sites_destroy(abn_sites* h) {
   if (!h) return ABN_ERR_INVALID_ARG;
+  if (h->ctx) (void)hipSetDevice(h->device);
   delete h;
   return ABN_OK;
 }
@@ -192,10 +286,66 @@ extern "C" int abn_sites_destroy(abn_sites* h) {
 extern "C" int abn_sites_info(const abn_sites* h, int64_t* n_sites, int64_t* n_deferred, int64_t* n_lines,
                               double* kernel_ms) {
   if (!h) return ABN_ERR_INVALID_ARG;
-  if (n_sites) *n_sites = (int64_t)h->line.size();
+  if (n_sites) *n_sites = h->n_records + (int64_t)h->line.size();  // (one of the two is 0 until abn_sites_insert)
   if (n_deferred) *n_deferred = (int64_t)h->dline.size();
   if (n_lines) *n_lines = h->n_lines;
   if (kernel_ms) *kernel_ms = h->kernel_ms;
+  return ABN_OK;
+}
+
+// abn_sites_fetch of a resident handle: every chunk's records come down and are merged by line with the inserted ones
+static int sites_fetch_resident(const abn_sites* h, int64_t* line, int32_t* chromosome, uint32_t* start, uint32_t* end,
+                                uint8_t* strand, double* posteriormax, uint8_t* status, uint8_t* status_flag,
+                                double* meth_lvl) {
+  abn_ctx* c = h->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  try {
+    size_t j = 0, k = 0;  // the next inserted record, the next place
+    const size_t n_ins = h->line.size();
+    auto put_inserted = [&]() {
+      if (line) line[k] = h->line[j];
+      if (chromosome) chromosome[k] = h->chromosome[j];
+      if (start) start[k] = h->start[j];
+      if (end) end[k] = h->end[j];
+      if (strand) strand[k] = h->strand[j];
+      if (posteriormax) posteriormax[k] = h->posteriormax[j];
+      if (status) status[k] = h->status[j];
+      if (status_flag) status_flag[k] = 0;
+      if (meth_lvl) meth_lvl[k] = h->meth_lvl[j];
+      ++j, ++k;
+    };
+    for (const auto& chunk : h->chunks) {
+      const size_t n = (size_t)chunk->n;
+      if (n == 0) continue;
+      std::vector<uint32_t> l(n), m(n), s(n), e(n);
+      std::vector<double> pm(n), ml(n);
+      const RecordBufs& r = chunk->rec;
+      HIPCHK(c, hipMemcpyAsync(l.data(), r.line.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(m.data(), r.meta.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
+      if (start) HIPCHK(c, hipMemcpyAsync(s.data(), r.start.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
+      if (end) HIPCHK(c, hipMemcpyAsync(e.data(), r.end.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
+      if (posteriormax) HIPCHK(c, hipMemcpyAsync(pm.data(), r.pm.p, 8 * n, hipMemcpyDeviceToHost, c->stream));
+      if (meth_lvl) HIPCHK(c, hipMemcpyAsync(ml.data(), r.ml.p, 8 * n, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      for (size_t i = 0; i < n; ++i) {
+        const int64_t li = chunk->line0 + (int64_t)l[i];
+        while (j < n_ins && h->line[j] < li) put_inserted();
+        if (line) line[k] = li;
+        if (chromosome) chromosome[k] = (int32_t)(m[i] & 0xffffu);
+        if (start) start[k] = s[i];
+        if (end) end[k] = e[i];
+        if (strand) strand[k] = (uint8_t)((m[i] >> 16) & 0xfu);
+        if (posteriormax) posteriormax[k] = pm[i];
+        if (status) status[k] = (uint8_t)((m[i] >> 20) & 0xfu);
+        if (status_flag) status_flag[k] = (uint8_t)((m[i] >> 24) & 0xfu);
+        if (meth_lvl) meth_lvl[k] = ml[i];
+        ++k;
+      }
+    }
+    while (j < n_ins) put_inserted();
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
   return ABN_OK;
 }
 
@@ -203,6 +353,7 @@ extern "C" int abn_sites_fetch(const abn_sites* h, int64_t* line, int32_t* chrom
                                uint8_t* strand, double* posteriormax, uint8_t* status, uint8_t* status_flag,
                                double* meth_lvl) {
   if (!h) return ABN_ERR_INVALID_ARG;
+  if (h->ctx) return sites_fetch_resident(h, line, chromosome, start, end, strand, posteriormax, status, status_flag, meth_lvl);
   if (line) std::copy(h->line.begin(), h->line.end(), line);
   if (chromosome) std::copy(h->chromosome.begin(), h->chromosome.end(), chromosome);
   if (start) std::copy(h->start.begin(), h->start.end(), start);
@@ -220,5 +371,118 @@ extern "C" int abn_sites_deferred(const abn_sites* h, int64_t* line, int64_t* of
   if (line) std::copy(h->dline.begin(), h->dline.end(), line);
   if (offset) std::copy(h->doffset.begin(), h->doffset.end(), offset);
   if (length) std::copy(h->dlength.begin(), h->dlength.end(), length);
+  return ABN_OK;
+}
+
+extern "C" int abn_sites_flagged(const abn_sites* h, int64_t* n, int64_t* line) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (!h->ctx) {  // the host form has the flags themselves
+    int64_t k = 0;
+    for (size_t i = 0; i < h->line.size(); ++i)
+      if (h->status_flag[i]) {
+        if (line) line[k] = h->line[i];
+        ++k;
+      }
+    if (n) *n = k;
+    return ABN_OK;
+  }
+  if (n) *n = (int64_t)h->flagged.size();
+  if (line) std::copy(h->flagged.begin(), h->flagged.end(), line);
+  return ABN_OK;
+}
+
+extern "C" int abn_sites_insert(abn_sites* h, int64_t n, const int64_t* line, const int32_t* chromosome,
+                                const uint32_t* start, const uint32_t* end, const uint8_t* strand,
+                                const double* posteriormax, const uint8_t* status, const double* meth_lvl) {
+  if (!h || !h->ctx) return ABN_ERR_INVALID_ARG;  // (a host-form handle has no context to report to)
+  abn_ctx* c = h->ctx;
+  if (h->inserted) return set_err(c, ABN_ERR_INVALID_ARG, "abn_sites_insert was already called on this handle");
+  if (n < 0 || (n > 0 && (!line || !chromosome || !start || !end || !strand || !posteriormax || !status || !meth_lvl)))
+    return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  try {
+    const size_t N = (size_t)n;
+    size_t d = 0;  // both lists ascend: every line is looked for behind the one before
+    for (size_t j = 0; j < N; ++j) {
+      if (j > 0 && line[j] <= line[j - 1]) return set_err(c, ABN_ERR_INVALID_ARG, "the lines are not strictly ascending");
+      while (d < h->dline.size() && h->dline[d] < line[j]) ++d;
+      if (d == h->dline.size() || h->dline[d] != line[j]) return set_err(c, ABN_ERR_INVALID_ARG, "a line that was not deferred");
+      if (chromosome[j] < 0 || chromosome[j] > 257) return set_err(c, ABN_ERR_INVALID_ARG, "a chromosome outside 0..257");
+      if (strand[j] > 2 || status[j] > 2) return set_err(c, ABN_ERR_INVALID_ARG, "a strand or a status above 2");
+    }
+    if (N > 0) {
+      std::vector<MergeChunk> refs;
+      for (const auto& chunk : h->chunks) refs.push_back(chunk->ref());
+      std::vector<long long> l(line, line + N);
+      std::vector<int32_t> pick(N);
+      if (!merge_pick_chunks(refs.data(), (int)refs.size(), l.data(), (long long)N, pick.data()))
+        return set_err(c, ABN_ERR_INVALID_ARG, "a line outside every slab");
+      HIPCHK(c, hipSetDevice(c->device));
+      PoolScope pool_scope(c);
+      HIPCHK(c, h->dchunks.alloc(refs.size()));
+      HIPCHK(c, h->iline.alloc(N));
+      HIPCHK(c, h->ichunk.alloc(N));
+      HIPCHK(c, h->ichromosome.alloc(N));
+      HIPCHK(c, h->istart.alloc(N));
+      HIPCHK(c, h->iend.alloc(N));
+      HIPCHK(c, h->istrand.alloc(N));
+      HIPCHK(c, h->istatus.alloc(N));
+      HIPCHK(c, h->ipm.alloc(N));
+      HIPCHK(c, h->iml.alloc(N));
+      HIPCHK(c, hipMemcpyAsync(h->dchunks.p, refs.data(), h->dchunks.bytes(), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h->iline.p, l.data(), 8 * N, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h->ichunk.p, pick.data(), 4 * N, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h->ichromosome.p, chromosome, 4 * N, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h->istart.p, start, 4 * N, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h->iend.p, end, 4 * N, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h->istrand.p, strand, N, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h->istatus.p, status, N, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h->ipm.p, posteriormax, 8 * N, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h->iml.p, meth_lvl, 8 * N, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's arrays and the staging vectors go on return
+      h->line.assign(line, line + N);  // the host's copy, for abn_sites_fetch
+      h->chromosome.assign(chromosome, chromosome + N);
+      h->start.assign(start, start + N);
+      h->end.assign(end, end + N);
+      h->strand.assign(strand, strand + N);
+      h->posteriormax.assign(posteriormax, posteriormax + N);
+      h->status.assign(status, status + N);
+      h->meth_lvl.assign(meth_lvl, meth_lvl + N);
+    }
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+  h->inserted = true;
+  return ABN_OK;
+}
+
+// ---- for abn_windows_create_parsed (abn_windows.hip)
+abn_ctx* abn::sites_ctx(const abn_sites* h) { return h ? h->ctx : nullptr; }
+
+int64_t abn::sites_merged_count(const abn_sites* h) {
+  if (!h || !h->ctx || (!h->dline.empty() && !h->inserted)) return -1;
+  return h->n_records + (int64_t)h->line.size();
+}
+
+int abn::sites_merge_dev(const abn_sites* h, bool inserted, double filter, int32_t* dchrom, uint32_t* dstart,
+                         uint32_t* dend, uint8_t* dstrand, uint8_t* dcode, double* dlevel) {
+  abn_ctx* c = h->ctx;
+  const MergeOut out{dchrom, dstart, dend, dstrand, dcode, dlevel};
+  const long long n_ins = (long long)h->line.size();
+  if (!inserted) {
+    for (const auto& chunk : h->chunks) {
+      if (chunk->n == 0) continue;
+      const unsigned grid = (unsigned)((chunk->n + kMergeThreads - 1) / kMergeThreads);
+      hipLaunchKernelGGL(abn_sites_fields_kernel, dim3(grid), dim3(kMergeThreads), 0, c->stream, chunk->ref(),
+                         (const long long*)h->iline.p, n_ins, filter, out);
+      HIPCHK(c, hipGetLastError());
+    }
+  } else if (n_ins > 0) {
+    const MergeInserted ins{h->iline.p, h->ichunk.p, h->ichromosome.p, h->istart.p, h->iend.p,
+                            h->istrand.p, h->istatus.p, h->ipm.p, h->iml.p, n_ins};
+    const unsigned grid = (unsigned)((n_ins + kMergeThreads - 1) / kMergeThreads);
+    hipLaunchKernelGGL(abn_sites_insert_kernel, dim3(grid), dim3(kMergeThreads), 0, c->stream,
+                       (const MergeChunk*)h->dchunks.p, ins, filter, out);
+    HIPCHK(c, hipGetLastError());
+  }
   return ABN_OK;
 }

@@ -1,5 +1,6 @@
 // abn_windows_*: the window-placement handle.  Kernels: abn_windows.hpp; the scan of the placed windows
-// (abn_windows_pairwise) is abn_pairwise.hip's, the gene choice of abn_windows_create_sites abn_genes.hip's.
+// (abn_windows_pairwise) is abn_pairwise.hip's, the gene choice of abn_windows_create_sites abn_genes.hip's, the merge of
+// resident parse results in front of abn_windows_create_parsed abn_sites.hip's.
 #include "abn_host.hpp"
 #include "abn_windows.hpp"
 
@@ -16,6 +17,7 @@ struct abn_windows {
   std::vector<int64_t> begin, end, count, kept;
   std::vector<int32_t> ragged;
   std::vector<double> level_sum, level_sum_kept;
+  double merge_ms[2] = {0.0, 0.0};  // abn_windows_create_parsed: its fields and insert kernels
   DevBuf<uint8_t> packed;  // [n x stride], device-resident between calls
 };
 
@@ -201,6 +203,57 @@ static int windows_build_sites(abn_windows* h, const abn_windows_params* p, abn_
   return windows_build_dev(h, p, site_offset, dstart.p, dgs.p, dge.p, dflags.p, dcode.p, dlevel.p);
 }
 
+// ... from RESIDENT parse results (abn_sites_parse_dev, abn_sites_insert): every sample's records and inserted lines
+// merged in file order straight into the arrays the gene choice and the placement read (abn_sites_merge.hpp)
+static int windows_build_parsed(abn_windows* h, const abn_windows_params* p, abn_genes* genes, const abn_gene_rule* rule,
+                                double filter, const int64_t* site_offset, abn_sites* const* samples) {
+  abn_ctx* c = h->ctx;
+  const size_t S = (size_t)site_offset[h->n];
+  DevBuf<int32_t> dchrom;
+  DevBuf<uint32_t> dstart, dend, dgs, dge;
+  DevBuf<uint8_t> dstrand, dflags, dcode;
+  DevBuf<double> dlevel;
+  HIPCHK(c, dchrom.alloc(S));
+  HIPCHK(c, dstart.alloc(S));
+  HIPCHK(c, dend.alloc(S));
+  HIPCHK(c, dstrand.alloc(S));
+  HIPCHK(c, dgs.alloc(S));
+  HIPCHK(c, dge.alloc(S));
+  HIPCHK(c, dflags.alloc(S));
+  HIPCHK(c, dcode.alloc(std::max<size_t>(S, 1)));
+  HIPCHK(c, dlevel.alloc(std::max<size_t>(S, 1)));
+  if (S > 0) {
+    struct Events {
+      hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+      ~Events() {
+        for (hipEvent_t x : e)
+          if (x) (void)hipEventDestroy(x);
+      }
+    } ev;
+    for (int k = 0; k < 3; ++k) HIPCHK(c, hipEventCreate(&ev.e[k]));
+    for (int pass = 0; pass < 2; ++pass) {  // the fields kernels of every sample, then the insert kernels
+      HIPCHK(c, hipEventRecord(ev.e[pass], c->stream));
+      for (int s = 0; s < h->n; ++s) {
+        const size_t o = (size_t)site_offset[s];
+        if (site_offset[s + 1] == site_offset[s]) continue;
+        if (int rc = sites_merge_dev(samples[s], pass == 1, filter, dchrom.p + o, dstart.p + o, dend.p + o, dstrand.p + o,
+                                     dcode.p + o, dlevel.p + o))
+          return rc;
+      }
+    }
+    HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
+    if (int rc = genes_choose_dev(genes, rule, h->n, site_offset, dchrom.p, dstart.p, dend.p, dstrand.p, dgs.p, dge.p,
+                                  dflags.p, nullptr))  // (ends in a synchronisation)
+      return rc;
+    for (int k = 0; k < 2; ++k) {
+      float ms = 0.f;
+      HIPCHK(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+      h->merge_ms[k] = ms;
+    }
+  }
+  return windows_build_dev(h, p, site_offset, dstart.p, dgs.p, dge.p, dflags.p, dcode.p, dlevel.p);
+}
+
 // the checks of abn_windows_create and abn_windows_create_sites on what they share
 static int windows_check(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, const int64_t* site_offset,
                          abn_windows** out) {
@@ -256,6 +309,36 @@ extern "C" int abn_windows_create_sites(abn_ctx* c, const abn_windows_params* p,
   });
 }
 
+extern "C" int abn_windows_create_parsed(abn_ctx* c, const abn_windows_params* p, abn_genes* genes,
+                                         const abn_gene_rule* rule, double posterior_max_filter, int32_t n_samples,
+                                         abn_sites* const* samples, abn_windows** out) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  if (out) *out = nullptr;
+  if (!p || !out || !samples || n_samples <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (n_samples > 65535) return set_err(c, ABN_ERR_INVALID_ARG, "too many samples");
+  std::vector<int64_t> site_offset;
+  try {
+    site_offset.assign((size_t)n_samples + 1, 0);
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+  for (int s = 0; s < n_samples; ++s) {
+    if (!samples[s]) return set_err(c, ABN_ERR_INVALID_ARG, "a null sites handle");
+    if (!sites_ctx(samples[s])) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle in the host form (abn_sites_parse)");
+    if (sites_ctx(samples[s]) != c) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle of another context");
+    const int64_t count = sites_merged_count(samples[s]);
+    if (count < 0)
+      return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle with deferred lines and no abn_sites_insert");
+    site_offset[(size_t)s + 1] = site_offset[(size_t)s] + count;
+  }
+  if (int rc = windows_check(c, p, n_samples, site_offset.data(), out)) return rc;
+  if (!genes || !rule) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (genes_ctx(genes) != c) return set_err(c, ABN_ERR_INVALID_ARG, "the genes belong to another context");
+  return windows_make(c, p, n_samples, out, [&](abn_windows* h) {
+    return windows_build_parsed(h, p, genes, rule, posterior_max_filter, site_offset.data(), samples);
+  });
+}
+
 extern "C" int abn_windows_create(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, const int64_t* site_offset,
                                   const uint32_t* pos, const uint32_t* gene_start, const uint32_t* gene_end,
                                   const uint8_t* flags, const uint8_t* code, const double* level, abn_windows** out) {
@@ -281,6 +364,13 @@ extern "C" int abn_windows_info(const abn_windows* h, int32_t* n_windows, int64_
   if (n_windows) *n_windows = h->W;
   if (row_stride) *row_stride = h->stride;
   if (n_sites) *n_sites = 4 * h->stride;
+  return ABN_OK;
+}
+
+extern "C" int abn_windows_merge_ms(const abn_windows* h, double* ms2) {
+  if (!h || !ms2) return ABN_ERR_INVALID_ARG;
+  ms2[0] = h->merge_ms[0];
+  ms2[1] = h->merge_ms[1];
   return ABN_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "../csrc/abn_genes.hpp"
 #include "../csrc/abn_parse.hpp"
 #include "../csrc/abn_route.hpp"
+#include "../csrc/abn_sites_merge.hpp"
 #include "alphabeta.hpp"
 
 extern "C" {
@@ -400,6 +401,126 @@ int abh_windows_handles_ab(const char* annotation, long long alen, const char* c
     abn_windows_info(device->get(), nullptr, &stride[1], nullptr);
     if (stride[0] != stride[1]) return 0;
     std::vector<uint8_t> pa(sites.size() * (size_t)stride[0]), pb(pa.size());
+    dev.check(abn_windows_packed(host->get(), pa.data()), "abn_windows_packed");
+    dev.check(abn_windows_packed(device->get(), pb.data()), "abn_windows_packed");
+    std::vector<int64_t> ba(host->n_windows()), ea(ba.size()), bb(ba.size()), eb(ba.size());
+    abn_windows_layout(host->get(), ba.data(), ea.data(), nullptr);
+    abn_windows_layout(device->get(), bb.data(), eb.data(), nullptr);
+    return pa == pb && ba == bb && ea == eb ? 1 : 0;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+// ---- the merge of the parser's records with the host-decided lines (csrc/abn_sites_merge.hpp), for
+// tests/test_sites_merge_cpu.py and scripts/resident_ab.py
+// sites_merge_serial of one sample: n_chunks chunks of chunk_n records and chunk_lines lines each, their record arrays
+// concatenated (line: slab-relative; line0 of a chunk = the lines of the chunks in front plus first_line0), and n_ins
+// inserted records (file lines, ascending) -> the six arrays over the merged sequence and the places of the records
+// (dest_record) and of the inserted records (dest_inserted).  Returns 0; -1: an inserted line lies in no chunk's slab or
+// the lines do not ascend
+int abh_sites_merge_serial(int n_chunks, const long long* chunk_n, const long long* chunk_lines, long long first_line0,
+                           const unsigned* line, const unsigned* meta, const unsigned* start, const unsigned* end,
+                           const double* pm, const double* ml, long long n_ins, const long long* iline, const int* ichrom,
+                           const unsigned* istart, const unsigned* iend, const unsigned char* istrand,
+                           const unsigned char* istatus, const double* ipm, const double* iml, double filter,
+                           int* chromosome, unsigned* out_start, unsigned* out_end, unsigned char* strand,
+                           unsigned char* code, double* level, long long* dest_record, long long* dest_inserted) {
+  std::vector<abn::MergeChunk> chunks;
+  long long before = 0, line0 = first_line0;
+  for (int c = 0; c < n_chunks; ++c) {
+    chunks.push_back(abn::MergeChunk{line + before, meta + before, start + before, end + before, pm + before, ml + before,
+                                     chunk_n[c], line0, chunk_lines[c], before});
+    before += chunk_n[c];
+    line0 += chunk_lines[c];
+  }
+  std::vector<int32_t> pick((size_t)n_ins);
+  if (!abn::merge_pick_chunks(chunks.data(), n_chunks, iline, n_ins, pick.data())) return -1;
+  const abn::MergeInserted ins{iline, pick.data(), ichrom, istart, iend, istrand, istatus, ipm, iml, n_ins};
+  abn::sites_merge_serial(chunks.data(), n_chunks, ins, filter,
+                          abn::MergeOut{chromosome, out_start, out_end, strand, code, level}, dest_record, dest_inserted);
+  return 0;
+}
+// parse_sites_resident of a text on the default device -> what abn_sites_fetch gives for its handle, in the arrays of
+// abh_parse_sites; warnings (capacity wcap) = what it printed.  Returns the number of sites, -1: they do not fit, -2: the
+// call threw
+long long abh_parse_sites_resident(const char* text, long long len, long long skip_lines, long long slab_bytes,
+                                   long long cap, long long* line, int* chromosome, unsigned* start, unsigned* end,
+                                   unsigned char* strand, double* posteriormax, unsigned char* status, double* meth_lvl,
+                                   char* warnings_out, long long wcap) {
+  try {
+    std::string warnings;
+    alphabeta::detail::diag_sink() = &warnings;
+    struct Unsink {
+      ~Unsink() { alphabeta::detail::diag_sink() = nullptr; }
+    } unsink;
+    const alphabeta::windows::ResidentSites sites = alphabeta::windows::parse_sites_resident(
+        alphabeta::default_device(), std::string(text, (size_t)len), (size_t)skip_lines, slab_bytes);
+    if (warnings_out && wcap > 0) std::strncpy(warnings_out, warnings.c_str(), (size_t)wcap - 1), warnings_out[wcap - 1] = 0;
+    if ((long long)sites.size() > cap) return -1;
+    static_assert(sizeof(long long) == sizeof(int64_t), "line numbers");
+    alphabeta::default_device().check(
+        abn_sites_fetch(sites.get(), (int64_t*)line, chromosome, start, end, strand, posteriormax, status, nullptr, meth_lvl),
+        "abn_sites_fetch");
+    return (long long)sites.size();
+  } catch (const std::exception&) {
+    return -2;
+  }
+}
+// The two ways from n methylome texts in host memory to a finished windows::Handle with the genes chosen on the device:
+// parse_sites_many on the device and the Handle of its FullSite vectors (which & 1: the records come down, are merged and
+// copied twice on the host and go up again), against parse_sites_resident and the Handle of its ResidentSites (which & 2:
+// the records stay).  which == 3: 1 when all that the two handles report and their packed matrices are equal, 0 when
+// not.  ms2 = the wall time of the two; kernel_ms2 = the HIP-event times of the resident side's two merge kernels.  The
+// texts are kept when n > 0: the timed calls pass n = 0.  -1: a call threw
+int abh_windows_resident_ab(const char* annotation, long long alen, const char* const* texts, const long long* lens, int n,
+                            unsigned cutoff, int cutoff_gene_length, double posterior_max_filter, unsigned step,
+                            unsigned size, int absolute, int which, double* ms2, double* kernel_ms2) {
+  namespace w = alphabeta::windows;
+  try {
+    static std::vector<std::string> held;
+    static w::Genome genome;
+    if (n > 0) {
+      held.clear();
+      for (int i = 0; i < n; ++i) held.emplace_back(texts[i], (size_t)lens[i]);
+      genome = w::parse_annotation(std::string(annotation, (size_t)alen));
+    }
+    const w::GeneRule rule{cutoff, cutoff_gene_length != 0};
+    const abn_windows_params p =
+        w::window_params(cutoff, step, size, absolute != 0, absolute ? genome.max_gene_length : 100u);
+    alphabeta::Device& dev = alphabeta::default_device();
+    auto now = []() { return std::chrono::steady_clock::now(); };
+    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    std::string warnings;  // (both sides print the invalid-status warnings; kept off the console)
+    alphabeta::detail::diag_sink() = &warnings;
+    struct Unsink {
+      ~Unsink() { alphabeta::detail::diag_sink() = nullptr; }
+    } unsink;
+    std::unique_ptr<w::Handle> host, device;
+    if (which & 1) {
+      const auto t0 = now();
+      host = std::make_unique<w::Handle>(dev, p, genome, rule, posterior_max_filter, w::parse_sites_many(held, &dev));
+      ms2[0] = ms(t0, now());
+    }
+    if (which & 2) {
+      const auto t0 = now();
+      std::vector<w::ResidentSites> sites;
+      for (const std::string& text : held) sites.push_back(w::parse_sites_resident(dev, text));
+      device = std::make_unique<w::Handle>(dev, p, genome, rule, posterior_max_filter, sites);
+      ms2[1] = ms(t0, now());
+      abn_windows_merge_ms(device->get(), kernel_ms2);
+    }
+    if ((which & 3) != 3) return 1;
+    auto same_bits = [](const std::vector<double>& x, const std::vector<double>& y) {
+      return x.size() == y.size() && (x.empty() || std::memcmp(x.data(), y.data(), 8 * x.size()) == 0);
+    };
+    if (host->count != device->count || host->kept != device->kept || host->ragged != device->ragged ||
+        !same_bits(host->level_sum, device->level_sum) || !same_bits(host->level_sum_kept, device->level_sum_kept))
+      return 0;
+    int64_t stride[2] = {0, 0};
+    abn_windows_info(host->get(), nullptr, &stride[0], nullptr);
+    abn_windows_info(device->get(), nullptr, &stride[1], nullptr);
+    if (stride[0] != stride[1]) return 0;
+    std::vector<uint8_t> pa(held.size() * (size_t)stride[0]), pb(pa.size());
     dev.check(abn_windows_packed(host->get(), pa.data()), "abn_windows_packed");
     dev.check(abn_windows_packed(device->get(), pb.data()), "abn_windows_packed");
     std::vector<int64_t> ba(host->n_windows()), ea(ba.size()), bb(ba.size()), eb(ba.size());

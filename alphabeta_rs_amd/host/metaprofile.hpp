@@ -40,6 +40,8 @@ struct WindowArgs {  // the fields of arguments::Windows (src/arguments.rs:6-62)
   bool invert = false;            // refused
   bool device_parse = false;      // --parse device: the methylome files through abn_sites_parse (not in the reference)
   bool device_genes = false;      // --genes device: every site's gene through abn_windows_create_sites (abn_genes_*)
+  bool device_sites = false;      // --sites device (with both of the above): the parsed records stay on the device up to
+                                  // the window matrix (abn_sites_parse_dev, abn_windows_create_parsed)
 };
 
 struct WindowResult {
@@ -257,7 +259,8 @@ inline detail::Inputs read_graph(const std::string& nodelist, const std::string&
 }
 
 // src/extract.rs:17-155: parse the annotation and every methylome once, choose every site's gene (on the host, or with
-// device_genes on the device), place the sites into windows on the device; write distribution_<name>, distributions.txt, steady_state_methylation.txt and
+// device_genes on the device; with device_sites the parsed records never leave it), place the sites into windows on the
+// device; write distribution_<name>, distributions.txt, steady_state_methylation.txt and
 // all_steady_state_methylation.txt (:112-151, src/windows.rs:130-176,245-257) into the output directory.
 inline Extraction extract_in_memory(const WindowArgs& args) {
   namespace fs = std::filesystem;
@@ -296,7 +299,17 @@ inline Extraction extract_in_memory(const WindowArgs& args) {
     std::printf("The maximum gene length is %u bp\n", ex.max_gene_length);
   }
   ex.params = windows::window_params(args.cutoff, step, args.window_size, args.absolute, ex.max_gene_length);
-  {
+  if (args.device_sites && !(args.device_parse && args.device_genes))
+    throw Error(ABN_ERR_INVALID_ARG, "--sites device needs --parse device and --genes device");
+  if (args.device_sites) {
+    // every text goes up, its records stay there; it is dropped as soon as its deferred lines are decided
+    const windows::GeneRule rule{args.cutoff, args.cutoff_gene_length};
+    std::vector<windows::ResidentSites> sites;
+    for (const auto& name : ex.names)
+      sites.push_back(windows::parse_sites_resident(default_device(),
+                                                    detail::read_file((fs::path(args.methylome) / name).string(), "methylome")));
+    ex.handle = std::make_unique<windows::Handle>(default_device(), ex.params, genome, rule, args.posterior_max_filter, sites);
+  } else {
     std::vector<std::string> texts;
     for (const auto& name : ex.names) texts.push_back(detail::read_file((fs::path(args.methylome) / name).string(), "methylome"));
     const windows::GeneRule rule{args.cutoff, args.cutoff_gene_length};

@@ -66,6 +66,14 @@ int main(int argc, char** argv) {
       }
       a.device_genes = where == "device";
     }
+    else if (f == "--sites") {
+      const std::string where = val();
+      if (where != "host" && where != "device") {
+        std::fprintf(stderr, "error: --sites expects host or device\n");
+        return 2;
+      }
+      a.device_sites = where == "device";
+    }
     else if (f == "-h" || f == "--help") {
       std::puts("Usage: metaprofile_alphabeta -o <output-dir> [--name N] [-s step] [-w size] [-c cutoff] [-a]\n"
                 "       [--iterations 100] [--max-gene-length L] [--distribution FILE] [--seed S] [--device D]\n"
@@ -74,6 +82,9 @@ int main(int argc, char** argv) {
                 "                            extract the windows from whole methylomes on the device (no window directories)\n"
                 "       [--parse host|device] where the methylome files are parsed; the same output files [default: device]\n"
                 "       [--genes host|device] where every site's gene is chosen; the same output files [default: device]\n"
+                "       [--sites host|device] where the parsed sites wait for the gene choice: device keeps them there from the\n"
+                "                            text to the window matrix (needs --parse device --genes device); the same output\n"
+                "                            files [default: host]\n"
                 "       [--stream-sweep]     pedigrees too large for the LDS: read a fit's rows once per Nelder-Mead iteration\n"
                 "                            instead of once per cost evaluation; the same output files");
       return 0;
@@ -97,6 +108,14 @@ int main(int argc, char** argv) {
   }
   if (!in_memory && (!a.genome.empty() || !a.nodes.empty() || !a.edges.empty() || a.cutoff_gene_length || a.invert)) {
     std::fprintf(stderr, "error: --genome, --nodes, --edges, --cutoff-gene-length and --invert belong to --methylome\n");
+    return 2;
+  }
+  if (a.device_sites && !(a.device_parse && a.device_genes)) {
+    std::fprintf(stderr, "error: --sites device needs --parse device and --genes device\n");
+    return 2;
+  }
+  if (a.device_sites && !in_memory) {
+    std::fprintf(stderr, "error: --sites belongs to --methylome\n");
     return 2;
   }
   std::printf("Starting run %s\n", a.name.c_str());

@@ -7,7 +7,8 @@
 // dependence is resolved per block of sites (abn_genes_*, csrc/abn_genes.hpp; the Handle made from FullSite vectors):
 // the same arrays either way.  Integer arithmetic wraps as the reference's release build does.  The line parse also runs
 // on the device (parse_sites_device over abn_sites_parse, csrc/abn_parse.hpp): the same FullSite sequence, fed to either
-// gene choice.
+// gene choice.  parse_sites_resident leaves that sequence on the device instead (abn_sites_parse_dev, abn_sites_insert),
+// for the Handle made from ResidentSites (abn_windows_create_parsed).
 #pragma once
 
 #include <thread>
@@ -213,6 +214,92 @@ inline std::vector<FullSite> parse_sites_device(Device& dev, const std::string& 
       ++j;
     }
   }
+  return out;
+}
+
+// RAII abn_sites in its resident form: one methylome's records on the device, its deferred lines decided and inserted
+class ResidentSites {
+ public:
+  explicit ResidentSites(abn_sites* h = nullptr) : h_(h) {}
+  ResidentSites(ResidentSites&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  ResidentSites& operator=(ResidentSites&& o) noexcept {
+    std::swap(h_, o.h_);
+    return *this;
+  }
+  ResidentSites(const ResidentSites&) = delete;
+  ResidentSites& operator=(const ResidentSites&) = delete;
+  ~ResidentSites() {
+    if (h_) abn_sites_destroy(h_);
+  }
+  abn_sites* get() const { return h_; }
+  size_t size() const {  // the sites of the merged sequence
+    int64_t n = 0;
+    abn_sites_info(h_, &n, nullptr, nullptr, nullptr);
+    return (size_t)n;
+  }
+
+ private:
+  abn_sites* h_;
+};
+
+// ... parsed on the device and LEFT there (abn_sites_parse_dev): the sequence parse_sites_device yields, as a handle.
+// Only the deferred triples and the flagged records' lines come back; every deferred line is decided here by
+// parse_site_full and the accepted ones go back up (abn_sites_insert).  The invalid-status warnings of the flagged
+// records and of the deferred lines are printed in one walk in file order, as parse_sites_device prints them.
+inline ResidentSites parse_sites_resident(Device& dev, const std::string& text, size_t skip_lines = 1,
+                                          int64_t slab_bytes = 0) {
+  abn_sites_params p{};
+  p.slab_bytes = slab_bytes;
+  p.skip_lines = (int32_t)skip_lines;
+  abn_sites* h = nullptr;
+  dev.check(abn_sites_parse_dev(dev.get(), text.data(), (int64_t)text.size(), &p, &h), "abn_sites_parse_dev");
+  ResidentSites out(h);
+  int64_t nd = 0, nf = 0;
+  abn_sites_info(h, nullptr, &nd, nullptr, nullptr);
+  abn_sites_flagged(h, &nf, nullptr);
+  std::vector<int64_t> flagged((size_t)nf), dline((size_t)nd), doff((size_t)nd), dlen((size_t)nd);
+  abn_sites_flagged(h, nullptr, flagged.data());
+  abn_sites_deferred(h, dline.data(), doff.data(), dlen.data());
+  std::vector<size_t> begins;  // the text's line begins, indexed when the first flagged record turns up
+  auto warn = [&](int64_t l) {
+    if (begins.empty()) {
+      begins.push_back(0);
+      for (const char* q = text.data(); (q = (const char*)std::memchr(q, '\n', (size_t)(text.data() + text.size() - q)));)
+        begins.push_back((size_t)(++q - text.data()));
+    }
+    const size_t b = begins[(size_t)l], e = (size_t)l + 1 < begins.size() ? begins[(size_t)l + 1] - 1 : text.size();
+    std::string s = text.substr(b, e - b);
+    if (!s.empty() && s.back() == '\r') s.pop_back();
+    FullSite again;
+    parse_site_full(s, again);
+  };
+  std::vector<int64_t> line;
+  std::vector<int32_t> chrom;
+  std::vector<uint32_t> start, end;
+  std::vector<uint8_t> strand, status;
+  std::vector<double> pm, ml;
+  size_t i = 0, j = 0;
+  while (i < flagged.size() || j < dline.size()) {
+    if (j == dline.size() || (i < flagged.size() && flagged[i] < dline[j])) {
+      warn(flagged[i++]);
+      continue;
+    }
+    FullSite s;
+    if (parse_site_full(text.substr((size_t)doff[j], (size_t)dlen[j]), s)) {
+      line.push_back(dline[j]);
+      chrom.push_back(s.chromosome);
+      start.push_back(s.start);
+      end.push_back(s.end);
+      strand.push_back((uint8_t)s.strand);
+      pm.push_back(s.posteriormax);
+      status.push_back((uint8_t)s.status_numeric);
+      ml.push_back(s.meth_lvl);
+    }
+    ++j;
+  }
+  dev.check(abn_sites_insert(h, (int64_t)line.size(), line.data(), chrom.data(), start.data(), end.data(), strand.data(),
+                             pm.data(), status.data(), ml.data()),
+            "abn_sites_insert");
   return out;
 }
 
@@ -487,6 +574,19 @@ class Handle {
     dev.check(abn_windows_create_sites(dev.get(), &p, genes.get(), &r, (int32_t)n_, a.offset.data(), a.chromosome.data(),
                                        a.start.data(), a.end.data(), a.strand.data(), a.code.data(), a.level.data(), &h_),
               "abn_windows_create_sites");
+    fetch();
+  }
+  // ... from the resident parse results (parse_sites_resident): merged, chosen and placed on the device, no site record
+  // coming back (abn_windows_create_parsed)
+  Handle(Device& dev, const abn_windows_params& p, const Genome& genome, const GeneRule& rule, double posterior_max_filter,
+         const std::vector<ResidentSites>& samples)
+      : n_(samples.size()) {
+    const GenesHandle genes(dev, genome);
+    const abn_gene_rule r{rule.cutoff, rule.cutoff_gene_length ? 1 : 0};
+    std::vector<abn_sites*> handles;
+    for (const ResidentSites& s : samples) handles.push_back(s.get());
+    dev.check(abn_windows_create_parsed(dev.get(), &p, genes.get(), &r, posterior_max_filter, (int32_t)n_, handles.data(), &h_),
+              "abn_windows_create_parsed");
     fetch();
   }
   Handle(Device& dev, const abn_windows_params& p, const std::vector<SampleSites>& samples) : n_(samples.size()) {

@@ -445,6 +445,38 @@ int abn_sites_fetch(const abn_sites* h, int64_t* line, int32_t* chromosome, uint
 /* The deferred lines in file order, [n_deferred] each, any may be NULL: line, the offset of its first byte in text, its
  * length without the line end — to be decided by the host's from_methylome_file_line (src/methylation_site.rs:146-362) */
 int abn_sites_deferred(const abn_sites* h, int64_t* line, int64_t* offset, int64_t* length);
+/* abn_sites_parse with the records left where the device wrote them (the same lines of src/windows.rs:303-338 and
+ * src/methylation_site.rs:146-362; the same text, slabs, skip_lines, kernels and argument checks): every slab's compacted
+ * record arrays stay on the device, owned by *out until abn_sites_destroy (destroy it before its context).  What comes
+ * back is what the host has to decide or to say: the deferred triples, and the lines of the records whose status_flag is
+ * set.  abn_sites_info (n_sites = the device's records plus the inserted ones), abn_sites_deferred and abn_sites_fetch
+ * (downloads, and merges the inserted records in by line) work on such a RESIDENT handle as on the host form. */
+int abn_sites_parse_dev(abn_ctx* ctx, const char* text, int64_t n_bytes, const abn_sites_params* params, abn_sites** out);
+/* The file lines of the accepted records whose status byte was none of M, I, U — where src/methylation_site.rs:107-112
+ * prints its warning — ascending; *n their number, line [*n]; either may be NULL.  Both forms. */
+int abn_sites_flagged(const abn_sites* h, int64_t* n, int64_t* line);
+/* Hands a RESIDENT handle the deferred lines that the host's from_methylome_file_line (src/methylation_site.rs:146-362)
+ * accepted — the second branch of the merge by line that the loop of src/windows.rs:303-338 performs implicitly — [n]
+ * each, line strictly ascending, every entry one of the handle's deferred lines; status U 0, I 1, M 2.  Uploaded once;
+ * nothing is launched.  At most once per handle; n = 0 is fine (no deferred line was a site).
+ * ABN_ERR_INVALID_ARG: a host-form handle, a second call, null arrays with n > 0, a line that was not deferred, lines not
+ * ascending, a chromosome outside 0..257, a strand or a status above 2. */
+int abn_sites_insert(abn_sites* h, int64_t n, const int64_t* line, const int32_t* chromosome, const uint32_t* start,
+                     const uint32_t* end, const uint8_t* strand, const double* posteriormax, const uint8_t* status,
+                     const double* meth_lvl);
+/* abn_windows_create_sites fed from RESIDENT handles (src/windows.rs:303-339 whole, for n_samples methylomes): sample s is
+ * samples[s]; its records and inserted lines are merged in file order on the device into the arrays the gene choice and
+ * the placement read — chromosome, start, end, strand, code = status | 0x80 when posteriormax < posterior_max_filter
+ * (src/pedigree.rs:165-166), level = meth_lvl — and nothing of per-site size crosses to the host.  The handles are not
+ * consumed.  *out is an ordinary abn_windows.
+ * ABN_ERR_INVALID_ARG: as abn_windows_create_sites, and a null or host-form sample handle, a handle of another context,
+ * a handle with deferred lines on which abn_sites_insert was never called. */
+int abn_windows_create_parsed(abn_ctx* ctx, const abn_windows_params* params, abn_genes* genes, const abn_gene_rule* rule,
+                              double posterior_max_filter, int32_t n_samples, abn_sites* const* samples,
+                              abn_windows** out);
+/* double[2]: the HIP-event times of the two merge kernels of abn_windows_create_parsed (the records' fields, the inserted
+ * lines: the merge of src/windows.rs:303-338), each over all samples; 0, 0 for a handle made any other way */
+int abn_windows_merge_ms(const abn_windows* h, double* ms2);
 
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
