@@ -64,6 +64,8 @@ EXPORTED_SYMBOLS = [
     "abn_genes_create", "abn_genes_destroy", "abn_genes_choose", "abn_genes_choose_dev", "abn_windows_create_sites",
     "abn_sites_parse_dev", "abn_sites_flagged", "abn_sites_insert", "abn_windows_create_parsed", "abn_windows_merge_ms",
     "abn_plan_set_stream_sweep", "abn_plan_stream_sweep", "abn_multi_set_stream_sweep", "abn_fit_batch_sweep",
+    "abn_codes_create_parsed", "abn_codes_destroy", "abn_codes_info", "abn_codes_stats", "abn_codes_packed",
+    "abn_codes_packed_device_ptr", "abn_codes_pairwise", "abn_codes_kernel_ms",
 ]
 
 
@@ -206,6 +208,14 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_windows_create_parsed.argtypes = [vp, C.POINTER(WindowsParams), vp, C.POINTER(GeneRule), C.c_double, C.c_int32,
                                             C.POINTER(vp), C.POINTER(vp)]
     L.abn_windows_merge_ms.argtypes = [vp, dp]
+    L.abn_codes_create_parsed.argtypes = [vp, C.c_double, C.c_int32, C.POINTER(vp), C.POINTER(vp)]
+    L.abn_codes_destroy.argtypes = [vp]
+    L.abn_codes_info.argtypes = [vp, C.POINTER(C.c_int32), i64p, i64p, C.POINTER(C.c_int32)]
+    L.abn_codes_stats.argtypes = [vp, i64p, dp, i64p]
+    L.abn_codes_packed.argtypes = [vp, u8p]
+    L.abn_codes_packed_device_ptr.argtypes = [vp, C.POINTER(vp)]
+    L.abn_codes_pairwise.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
+    L.abn_codes_kernel_ms.argtypes = [vp, dp]
     i32p = C.POINTER(C.c_int32)
     L.abn_genes_create.argtypes = [vp, C.c_int32, i32p, i32p, i64p, u32p, u32p, u8p, C.POINTER(vp)]
     L.abn_genes_destroy.argtypes = [vp]
@@ -1084,6 +1094,81 @@ class Windows:
         self.ctx._check(self._L.abn_windows_pairwise(self._h, diff.ctypes.data_as(u64p), both.ctypes.data_as(u64p),
                                                      _dp(dval)))
         return diff, both, dval
+
+
+class Codes:
+    """abn_codes: what Pedigree::build reads of n_samples methylomes (src/pedigree.rs:147-172, :245-251), made on the device
+    from resident parse results: the 2-bit packed matrix of Context.pairwise_divergence_packed, device-resident, and every
+    sample's rc_meth_lvl fold."""
+
+    @classmethod
+    def from_parsed(cls, ctx: Context, sites_list, *, posterior_max_filter):
+        """From resident parse results (Context.parse_sites_resident with skip_lines 0 for the pedigree build, one Sites
+        per methylome, their deferred lines decided and inserted): merged in file order, packed and folded on the device,
+        no site record coming back to the host (abn_codes_create_parsed).  The Sites are not consumed."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self._L = ctx._L
+        sites_list = list(sites_list)
+        handles = (C.c_void_p * max(len(sites_list), 1))(*(s._h for s in sites_list))
+        h = C.c_void_p()
+        ctx._check(self._L.abn_codes_create_parsed(ctx._h, posterior_max_filter, len(sites_list), handles, C.byref(h)))
+        self._h = h
+        i = self.info()
+        self.n_samples, self.n_sites, self.row_stride, self.same_len = i["n_samples"], i["n_sites"], i["row_stride"], i["same_len"]
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.abn_codes_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{n_samples, n_sites (of the longest sample), row_stride (bytes), same_len (bool)}"""
+        n, same, ns, stride = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        self.ctx._check(self._L.abn_codes_info(self._h, C.byref(n), C.byref(ns), C.byref(stride), C.byref(same)))
+        return {"n_samples": n.value, "n_sites": ns.value, "row_stride": stride.value, "same_len": bool(same.value)}
+
+    def stats(self):
+        """(count int64, level_sum_kept, kept int64), each (n_samples,): a sample's sites, and the sum and number of the
+        levels whose posterior passes the filter (rc_meth_lvl = level_sum_kept / kept)"""
+        count, kept = np.zeros(self.n_samples, dtype=np.int64), np.zeros(self.n_samples, dtype=np.int64)
+        lsk = np.zeros(self.n_samples)
+        i64p = C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_codes_stats(self._h, count.ctypes.data_as(i64p), _dp(lsk), kept.ctypes.data_as(i64p)))
+        return count, lsk, kept
+
+    def packed(self) -> np.ndarray:
+        """the packed matrix (n_samples, row_stride) uint8, copied to the host"""
+        out = np.empty((self.n_samples, self.row_stride), dtype=np.uint8)
+        self.ctx._check(self._L.abn_codes_packed(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def packed_device_ptr(self) -> int:
+        p = C.c_void_p()
+        self.ctx._check(self._L.abn_codes_packed_device_ptr(self._h, C.byref(p)))
+        return p.value or 0
+
+    def pairwise(self):
+        """(diff, both, dvalue), each (pairs,): pairwise_divergence_packed on the resident matrix; refused (AbnError) when
+        the samples differ in length"""
+        npairs = self.n_samples * (self.n_samples - 1) // 2
+        diff, both, dval = np.zeros(npairs, dtype=np.uint64), np.zeros(npairs, dtype=np.uint64), np.zeros(npairs)
+        u64p = C.POINTER(C.c_uint64)
+        self.ctx._check(self._L.abn_codes_pairwise(self._h, diff.ctypes.data_as(u64p), both.ctypes.data_as(u64p), _dp(dval)))
+        return diff, both, dval
+
+    def kernel_ms(self) -> np.ndarray:
+        """the HIP-event ms of from_parsed's kernels: merge of the records, merge of the inserted lines, pack, fold"""
+        ms = np.zeros(4)
+        self.ctx._check(self._L.abn_codes_kernel_ms(self._h, _dp(ms)))
+        return ms
 
 
 def reduction_tree(generations, options: Options | None = None) -> int:

@@ -1,0 +1,182 @@
+// abn_codes_*: the pedigree build's code matrix and rc_meth_lvl folds from resident parse results (src/pedigree.rs:138-178
+// behind from_methylome_file_line, and the status bytes DMatrix::from reads, :210-261).  Kernels and arithmetic:
+// abn_codes.hpp; the merge launches are abn_sites.hip's (the records are its handle's), the scan abn_pairwise.hip's.
+#include "abn_host.hpp"
+#define ABN_CODES_KERNELS
+#include "abn_codes.hpp"
+
+using namespace abn;
+
+struct abn_codes {
+  abn_ctx* ctx = nullptr;
+  int n = 0;
+  long long stride = 0;     // bytes per row of `packed`
+  int64_t max_sites = 0;    // of the longest sample
+  bool same_len = true;
+  std::vector<int64_t> count, kept;  // [n]
+  std::vector<double> level_sum_kept;
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};  // merge records, merge inserted, pack, fold
+  DevBuf<uint8_t> packed;               // [n x stride], device-resident between calls
+};
+
+// merge, pack, fold; the merged arrays (9 bytes per site) live only in here
+static int codes_build(abn_codes* h, double filter, abn_sites* const* samples) {
+  abn_ctx* c = h->ctx;
+  const int n = h->n;
+  std::vector<long long> site_off((size_t)n + 1, 0), code_off((size_t)n + 1, 0);
+  for (int s = 0; s < n; ++s) {
+    site_off[(size_t)s + 1] = site_off[(size_t)s] + h->count[(size_t)s];
+    code_off[(size_t)s + 1] = code_off[(size_t)s] + (h->count[(size_t)s] + 15) / 16 * 16;  // whole 16-byte loads of the pack
+  }
+  h->stride = std::max<long long>(abn_packed_row_stride(h->max_sites), 64);  // no site: still one super-step per row
+  const long long row_dwords = h->stride / 4;
+  if (((long long)n * row_dwords + kCodesThreads - 1) / kCodesThreads > 0x7fffffffLL)
+    return set_err(c, ABN_ERR_INVALID_ARG, "packed matrix too large for one handle");
+
+  DevBuf<uint8_t> dcode;
+  DevBuf<double> dlevel, dsum;
+  DevBuf<long long> dsite_off, dcode_off, dkept;
+  HIPCHK(c, dcode.alloc(std::max<size_t>((size_t)code_off[(size_t)n], 16)));
+  HIPCHK(c, dlevel.alloc(std::max<size_t>((size_t)site_off[(size_t)n], 1)));
+  HIPCHK(c, dsite_off.alloc((size_t)n + 1));
+  HIPCHK(c, dcode_off.alloc((size_t)n + 1));
+  HIPCHK(c, dsum.alloc((size_t)n));
+  HIPCHK(c, dkept.alloc((size_t)n));
+  HIPCHK(c, h->packed.alloc((size_t)n * (size_t)h->stride));
+  HIPCHK(c, hipMemcpyAsync(dsite_off.p, site_off.data(), dsite_off.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dcode_off.p, code_off.data(), dcode_off.bytes(), hipMemcpyHostToDevice, c->stream));
+
+  struct Events {
+    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  for (int k = 0; k < 5; ++k) HIPCHK(c, hipEventCreate(&ev.e[k]));
+  for (int pass = 0; pass < 2; ++pass) {  // the fields kernels of every sample, then the insert kernels
+    HIPCHK(c, hipEventRecord(ev.e[pass], c->stream));
+    for (int s = 0; s < n; ++s) {
+      if (h->count[(size_t)s] == 0) continue;
+      if (int rc = sites_merge_codes_dev(samples[s], pass == 1, filter, dcode.p + code_off[(size_t)s],
+                                         dlevel.p + site_off[(size_t)s]))
+        return rc;
+    }
+  }
+  HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
+  const unsigned grid = (unsigned)(((long long)n * row_dwords + kCodesThreads - 1) / kCodesThreads);
+  hipLaunchKernelGGL(abn_codes_pack_kernel, dim3(grid), dim3(kCodesThreads), 0, c->stream, dcode.p, dcode_off.p, dsite_off.p,
+                     n, row_dwords, (uint32_t*)h->packed.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(ev.e[3], c->stream));
+  hipLaunchKernelGGL(abn_codes_fold_kernel, dim3((unsigned)n), dim3(kCodesWave), 0, c->stream, dcode.p, dlevel.p,
+                     dcode_off.p, dsite_off.p, dsum.p, dkept.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(ev.e[4], c->stream));
+  std::vector<long long> kept((size_t)n);
+  h->level_sum_kept.assign((size_t)n, 0.0);
+  HIPCHK(c, hipMemcpyAsync(h->level_sum_kept.data(), dsum.p, dsum.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(kept.data(), dkept.p, dkept.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the merged arrays are freed on return
+  h->kept.assign(kept.begin(), kept.end());
+  for (int k = 0; k < 4; ++k) {
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+    h->ms[k] = ms;
+  }
+  return ABN_OK;
+}
+
+extern "C" int abn_codes_create_parsed(abn_ctx* c, double posterior_max_filter, int32_t n_samples,
+                                       abn_sites* const* samples, abn_codes** out) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  if (out) *out = nullptr;
+  if (!out || !samples || n_samples <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (n_samples > 65535) return set_err(c, ABN_ERR_INVALID_ARG, "too many samples");
+  std::unique_ptr<abn_codes> h(new (std::nothrow) abn_codes);
+  if (!h) return set_err(c, ABN_ERR_HIP, "out of host memory");
+  h->ctx = c;
+  h->n = n_samples;
+  try {
+    h->count.assign((size_t)n_samples, 0);
+    for (int s = 0; s < n_samples; ++s) {
+      if (!samples[s]) return set_err(c, ABN_ERR_INVALID_ARG, "a null sites handle");
+      if (!sites_ctx(samples[s])) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle in the host form (abn_sites_parse)");
+      if (sites_ctx(samples[s]) != c) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle of another context");
+      const int64_t count = sites_merged_count(samples[s]);
+      if (count < 0)
+        return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle with deferred lines and no abn_sites_insert");
+      h->count[(size_t)s] = count;
+      h->max_sites = std::max(h->max_sites, count);
+      if (count != h->count[0]) h->same_len = false;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    PoolScope pool_scope(c);
+    if (int rc = codes_build(h.get(), posterior_max_filter, samples)) return rc;
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+  *out = h.release();
+  return ABN_OK;
+}
+
+extern "C" int abn_codes_destroy(abn_codes* h) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  (void)hipSetDevice(h->ctx->device);
+  delete h;
+  return ABN_OK;
+}
+
+extern "C" int abn_codes_info(const abn_codes* h, int32_t* n_samples, int64_t* n_sites, int64_t* row_stride_bytes,
+                              int32_t* same_len) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (n_samples) *n_samples = h->n;
+  if (n_sites) *n_sites = h->max_sites;
+  if (row_stride_bytes) *row_stride_bytes = h->stride;
+  if (same_len) *same_len = h->same_len ? 1 : 0;
+  return ABN_OK;
+}
+
+extern "C" int abn_codes_stats(const abn_codes* h, int64_t* count, double* level_sum_kept, int64_t* kept) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (count) std::copy(h->count.begin(), h->count.end(), count);
+  if (level_sum_kept) std::copy(h->level_sum_kept.begin(), h->level_sum_kept.end(), level_sum_kept);
+  if (kept) std::copy(h->kept.begin(), h->kept.end(), kept);
+  return ABN_OK;
+}
+
+extern "C" int abn_codes_packed(abn_codes* h, uint8_t* host_out) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = h->ctx;
+  if (!host_out) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(host_out, h->packed.p, h->packed.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ABN_OK;
+}
+
+extern "C" int abn_codes_packed_device_ptr(abn_codes* h, void** dev_ptr) {
+  if (!h || !dev_ptr) return ABN_ERR_INVALID_ARG;
+  *dev_ptr = h->packed.p;
+  return ABN_OK;
+}
+
+extern "C" int abn_codes_pairwise(abn_codes* h, uint64_t* diff, uint64_t* both, double* dvalue) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = h->ctx;
+  if (!h->same_len)
+    return set_err(c, ABN_ERR_INVALID_ARG, "the samples differ in length: the pairwise scan needs the same number of sites in each");
+  const size_t n = (size_t)h->n, npairs = n * (n - 1) / 2;
+  if (npairs == 0) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  return pairwise_to_host(c, npairs, diff, both, dvalue, [&](auto* dd, auto* db, auto* dv) {
+    return abn_pairwise_divergence_packed_dev(c, h->packed.p, h->n, h->max_sites, h->stride, dd, db, dv, nullptr);
+  });
+}
+
+extern "C" int abn_codes_kernel_ms(const abn_codes* h, double* ms4) {
+  if (!h || !ms4) return ABN_ERR_INVALID_ARG;
+  std::copy(h->ms, h->ms + 4, ms4);
+  return ABN_OK;
+}

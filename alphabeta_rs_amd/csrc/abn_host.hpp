@@ -1,5 +1,5 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (abn_api.hip, abn_pairwise.hip,
-// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip): the context, its device-buffer pool, error reporting,
+// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip): the context, its device-buffer pool, error reporting,
 // the kernel_ms timer.  Not part of the C-ABI (include/abneutral.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -205,4 +205,7 @@ abn_ctx* sites_ctx(const abn_sites* h);
 int64_t sites_merged_count(const abn_sites* h);
 int sites_merge_dev(const abn_sites* h, bool inserted, double filter, int32_t* dchrom, uint32_t* dstart, uint32_t* dend,
                     uint8_t* dstrand, uint8_t* dcode, double* dlevel);
+// ... and for abn_codes_create_parsed (abn_codes.hip): the same merge in its reduced form (abn_codes.hpp), the merged byte
+// and the level of every site
+int sites_merge_codes_dev(const abn_sites* h, bool inserted, double filter, uint8_t* dcode, double* dlevel);
 }  // namespace abn

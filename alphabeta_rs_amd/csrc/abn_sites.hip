@@ -1,11 +1,14 @@
 // abn_sites_*: methylome text -> site records on the device (src/methylation_site.rs:146-362 for every line of a file,
 // the loops of src/windows.rs:303-338 and src/pedigree.rs:138-178 in front of it).  Kernels: abn_parse_kernels.hpp; the
 // line parser they share with the host: abn_parse.hpp.  The resident form (abn_sites_parse_dev, abn_sites_insert) keeps the
-// records on the device for abn_windows_create_parsed (abn_windows.hip); its merge kernels: abn_sites_merge.hpp.
+// records on the device for abn_windows_create_parsed (abn_windows.hip; its merge kernels: abn_sites_merge.hpp) and for
+// abn_codes_create_parsed (abn_codes.hip; its reduced merge kernels: abn_codes.hpp).
 #include "abn_host.hpp"
 #include "abn_parse_kernels.hpp"
 #define ABN_SITES_MERGE_KERNELS
 #include "abn_sites_merge.hpp"
+#define ABN_CODES_MERGE_KERNELS
+#include "abn_codes.hpp"
 
 using namespace abn;
 
@@ -481,6 +484,30 @@ int abn::sites_merge_dev(const abn_sites* h, bool inserted, double filter, int32
                             h->istrand.p, h->istatus.p, h->ipm.p, h->iml.p, n_ins};
     const unsigned grid = (unsigned)((n_ins + kMergeThreads - 1) / kMergeThreads);
     hipLaunchKernelGGL(abn_sites_insert_kernel, dim3(grid), dim3(kMergeThreads), 0, c->stream,
+                       (const MergeChunk*)h->dchunks.p, ins, filter, out);
+    HIPCHK(c, hipGetLastError());
+  }
+  return ABN_OK;
+}
+
+// ---- for abn_codes_create_parsed (abn_codes.hip): the same launches with the reduced writers of abn_codes.hpp
+int abn::sites_merge_codes_dev(const abn_sites* h, bool inserted, double filter, uint8_t* dcode, double* dlevel) {
+  abn_ctx* c = h->ctx;
+  const CodesOut out{dcode, dlevel};
+  const long long n_ins = (long long)h->line.size();
+  if (!inserted) {
+    for (const auto& chunk : h->chunks) {
+      if (chunk->n == 0) continue;
+      const unsigned grid = (unsigned)((chunk->n + kMergeThreads - 1) / kMergeThreads);
+      hipLaunchKernelGGL(abn_codes_fields_kernel, dim3(grid), dim3(kMergeThreads), 0, c->stream, chunk->ref(),
+                         (const long long*)h->iline.p, n_ins, filter, out);
+      HIPCHK(c, hipGetLastError());
+    }
+  } else if (n_ins > 0) {
+    const MergeInserted ins{h->iline.p, h->ichunk.p, h->ichromosome.p, h->istart.p, h->iend.p,
+                            h->istrand.p, h->istatus.p, h->ipm.p, h->iml.p, n_ins};
+    const unsigned grid = (unsigned)((n_ins + kMergeThreads - 1) / kMergeThreads);
+    hipLaunchKernelGGL(abn_codes_insert_kernel, dim3(grid), dim3(kMergeThreads), 0, c->stream,
                        (const MergeChunk*)h->dchunks.p, ins, filter, out);
     HIPCHK(c, hipGetLastError());
   }

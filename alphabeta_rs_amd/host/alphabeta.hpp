@@ -345,7 +345,9 @@ class Pedigree {  // src/pedigree.rs:44-45
   // (abn_pairwise_divergence_packed); same bits either way.
   static std::pair<Pedigree, double> build(const std::string& nodelist, const std::string& edgelist,
                                            double posterior_max_filter, bool gpu_pairwise = false,
-                                           bool device_parse = false);  // the methylome files through abn_sites_parse
+                                           bool device_parse = false,    // the methylome files through abn_sites_parse
+                                           bool device_sites = false);   // (with both of the above) the parsed sites stay
+                                                                         // on the device: abn_codes_create_parsed
   // ... for many (nodelist, edgelist) pairs at once (the windows of src/cli/metaprofile.rs:50-72): with gpu_pairwise ONE
   // abn_pairwise_divergence_windows_packed call per batch of entries with the same number of samples, on 2-bit codes
   // packed straight from the site records.  A batch ends at kBuildManyCodeBytes of PACKED codes per call (four sites per
@@ -458,6 +460,8 @@ struct Args {  // arguments::AlphaBeta, src/arguments.rs:93-114
   double posterior_max_filter = 0.99;
   std::string output = ".";
   bool device_parse = false;  // --parse device: the methylome files through abn_sites_parse (not in the reference)
+  bool device_sites = false;  // --sites device (with --parse device): the parsed sites stay on the device up to the code
+                              // matrix and the rc_meth_lvl folds (abn_sites_parse_dev, abn_codes_create_parsed)
 };
 
 struct RunResult {
@@ -523,7 +527,7 @@ namespace alphabeta {
 inline RunResult run(const Args& args) {
   std::printf("Building pedigree...\n");
   auto [pedigree, p0uu] = Pedigree::build(args.nodes, args.edges, args.posterior_max_filter, /*gpu_pairwise=*/true,
-                                          args.device_parse);
+                                          args.device_parse, args.device_sites);
   return run_on_pedigree(std::move(pedigree), p0uu, args.iterations, args.output);
 }
 }  // namespace alphabeta

@@ -1,6 +1,6 @@
 // `alphabeta` command-line tool: same flags, console output and output files as the reference binary
 // (src/cli/alphabeta.rs:8-38, src/arguments.rs:93-152), running the ABneutral path on an MI355X through
-// libabneutral_hip.so.  Extra flags (not in the reference): --seed, --device(s), --lanes, --strict-order, --stream-sweep, --parse, and
+// libabneutral_hip.so.  Extra flags (not in the reference): --seed, --device(s), --lanes, --strict-order, --stream-sweep, --parse, --sites, and
 // --pedigree FILE --p0uu X to start from an existing pedigree file instead of nodelist/edgelist.
 #include <cstdlib>
 #include <cstring>
@@ -32,6 +32,9 @@ static void usage() {
       "      --pedigree <FILE>          use this pedigree file (src/pedigree.rs:62-79 format) instead of building one\n"
       "      --p0uu <X>                 proportion of unmethylated sites at G0 (required with --pedigree)\n"
       "      --parse <host|device>      where the methylome files are parsed; the same output files [default: device]\n"
+      "      --sites <host|device>      where the parsed sites wait for the pedigree build: device packs the codes and folds\n"
+      "                                 the methylation levels there (needs --parse device); the same output files\n"
+      "                                 [default: host]\n"
       "  -h, --help                     Print help\n"
       "  -V, --version                  Print version");
 }
@@ -83,12 +86,28 @@ int main(int argc, char** argv) {
       }
       args.device_parse = where == "device";
     }
+    else if (a == "--sites") {
+      const std::string where = val();
+      if (where != "host" && where != "device") {
+        std::fprintf(stderr, "error: --sites expects host or device\n");
+        return 2;
+      }
+      args.device_sites = where == "device";
+    }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (a == "-V" || a == "--version") { std::puts("alphabeta 0.2.1 (MI355X ABneutral path)"); return 0; }
     else {
       std::fprintf(stderr, "error: unexpected argument '%s' found\n\nFor more information, try '--help'.\n", argv[i]);
       return 2;
     }
+  }
+  if (args.device_sites && !args.device_parse) {
+    std::fprintf(stderr, "error: --sites device needs --parse device\n");
+    return 2;
+  }
+  if (args.device_sites && !ped_file.empty()) {
+    std::fprintf(stderr, "error: --sites belongs to --nodes and --edges\n");
+    return 2;
   }
   (void)edges_given;
   (void)nodes_given;

@@ -7,6 +7,7 @@
 #include "../csrc/abn_genes.hpp"
 #include "../csrc/abn_parse.hpp"
 #include "../csrc/abn_route.hpp"
+#include "../csrc/abn_codes.hpp"
 #include "../csrc/abn_sites_merge.hpp"
 #include "alphabeta.hpp"
 
@@ -40,6 +41,68 @@ int abh_pedigree_build_gpu(const char* nodelist, const char* edgelist, double po
 long long abh_packed_scan_calls() { return alphabeta::detail::packed_scan_calls().load(); }
 // ... and calls Pedigree::build_many has sent through abn_pairwise_divergence_windows_packed
 long long abh_packed_windows_scan_calls() { return alphabeta::detail::packed_windows_scan_calls().load(); }
+// ... and builds whose codes and rc_meth_lvl folds were made on the device from resident sites (--sites device)
+long long abh_resident_build_calls() { return alphabeta::detail::resident_build_calls().load(); }
+// Pedigree::build as `alphabeta --parse device --sites device` runs it: abh_pedigree_build_gpu's arguments and result
+int abh_pedigree_build_resident(const char* nodelist, const char* edgelist, double posterior_max_filter, const char* out_path,
+                                double* rows, int cap, double* p0uu, char* err, int errcap) {
+  try {
+    auto [ped, p0] = alphabeta::Pedigree::build(nodelist, edgelist, posterior_max_filter, true, true, true);
+    if (out_path) ped.to_file(out_path);
+    const int n = (int)ped.nrows();
+    if (n > cap) return -2;
+    if (n > 0) std::memcpy(rows, ped.data.data(), sizeof(double) * 4 * (size_t)n);
+    *p0uu = p0;
+    return n;
+  } catch (const std::exception& e) {
+    if (err && errcap > 0) std::strncpy(err, e.what(), (size_t)errcap - 1), err[errcap - 1] = 0;
+    return -1;
+  }
+}
+// The two ways of `alphabeta --parse device` from n methylome texts in host memory (the sampled nodes of the nodelist, in
+// its order; the files it names are not opened) to the finished pedigree and p0uu: --sites host (which & 1: the records
+// come down, are copied into Site vectors, folded and packed on the host, and the packed matrix goes up) against
+// --sites device (which & 2: abn_codes_create_parsed).  which == 3: 1 when rows and p0uu are equal bit for bit, 0 when
+// not.  ms2 = the wall time of the two; kernel_ms4 = abn_codes_kernel_ms of the device side.  The texts are kept when
+// n > 0: the timed calls pass n = 0.  -1: a call threw (its text in err)
+int abh_pedigree_build_ab(const char* nodelist, const char* edgelist, const char* const* texts, const long long* lens, int n,
+                          double posterior_max_filter, int which, double* ms2, double* kernel_ms4, char* err, int errcap) {
+  try {
+    static std::vector<std::string> held;
+    if (n > 0) {
+      held.clear();
+      for (int i = 0; i < n; ++i) held.emplace_back(texts[i], (size_t)lens[i]);
+    }
+    auto now = []() { return std::chrono::steady_clock::now(); };
+    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    std::string warnings;  // (both sides print the invalid-status warnings; kept off the console)
+    alphabeta::detail::diag_sink() = &warnings;
+    struct Unsink {
+      ~Unsink() { alphabeta::detail::diag_sink() = nullptr; }
+    } unsink;
+    std::pair<alphabeta::Pedigree, double> host, device;
+    if (which & 1) {
+      const auto t0 = now();
+      host = alphabeta::detail::build_pedigree(nodelist, edgelist, posterior_max_filter, true, true, false, &held);
+      ms2[0] = ms(t0, now());
+    }
+    if (which & 2) {
+      const auto t0 = now();
+      device = alphabeta::detail::build_pedigree(nodelist, edgelist, posterior_max_filter, true, true, true, &held);
+      ms2[1] = ms(t0, now());
+      std::memcpy(kernel_ms4, alphabeta::detail::resident_kernel_ms(), 4 * sizeof(double));
+    }
+    if ((which & 3) != 3) return 1;
+    const auto &a = host.first.data, &b = device.first.data;
+    return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), 8 * a.size()) == 0) &&
+                   std::memcmp(&host.second, &device.second, 8) == 0
+               ? 1
+               : 0;
+  } catch (const std::exception& e) {
+    if (err && errcap > 0) std::strncpy(err, e.what(), (size_t)errcap - 1), err[errcap - 1] = 0;
+    return -1;
+  }
+}
 // The layout of Pedigree::build_many's scan calls without a device: the n entries are read, those that the scan takes
 // (samples of equal length, at least two) and that have the first such entry's sample count are cut into calls of at
 // most cap_bytes of packed codes (PackedBatch) and every call is laid out (layout_packed_call).  Per entry: call_of (-1:
@@ -438,6 +501,31 @@ int abh_sites_merge_serial(int n_chunks, const long long* chunk_n, const long lo
   const abn::MergeInserted ins{iline, pick.data(), ichrom, istart, iend, istrand, istatus, ipm, iml, n_ins};
   abn::sites_merge_serial(chunks.data(), n_chunks, ins, filter,
                           abn::MergeOut{chromosome, out_start, out_end, strand, code, level}, dest_record, dest_inserted);
+  return 0;
+}
+// ---- the pedigree build from resident sites (csrc/abn_codes.hpp), for tests/test_codes_cpu.py
+// codes_build_serial of one sample: the chunks and inserted records of abh_sites_merge_serial, reduced to what the build
+// reads -> the merged bytes and levels over the merged sequence, the sample's packed row [row_stride_bytes], and the fold
+// (sum, kept).  Returns 0; -1: an inserted line lies in no chunk's slab or the lines do not ascend; -2: a row stride that
+// is no multiple of 4 or holds fewer fields than sites
+int abh_codes_build_serial(int n_chunks, const long long* chunk_n, const long long* chunk_lines, long long first_line0,
+                           const unsigned* line, const unsigned* meta, const double* pm, const double* ml, long long n_ins,
+                           const long long* iline, const unsigned char* istatus, const double* ipm, const double* iml,
+                           double filter, long long row_stride_bytes, unsigned char* code, double* level,
+                           unsigned char* row, double* sum, long long* kept) {
+  std::vector<abn::MergeChunk> chunks;
+  long long before = 0, line0 = first_line0;
+  for (int c = 0; c < n_chunks; ++c) {
+    chunks.push_back(abn::MergeChunk{line + before, meta + before, nullptr, nullptr, pm + before, ml + before, chunk_n[c],
+                                     line0, chunk_lines[c], before});
+    before += chunk_n[c];
+    line0 += chunk_lines[c];
+  }
+  if (row_stride_bytes < 0 || row_stride_bytes % 4 != 0 || 4 * row_stride_bytes < before + n_ins) return -2;
+  std::vector<int32_t> pick((size_t)n_ins);
+  if (!abn::merge_pick_chunks(chunks.data(), n_chunks, iline, n_ins, pick.data())) return -1;
+  const abn::MergeInserted ins{iline, pick.data(), nullptr, nullptr, nullptr, nullptr, istatus, ipm, iml, n_ins};
+  abn::codes_build_serial(chunks.data(), n_chunks, ins, filter, abn::CodesOut{code, level}, row, row_stride_bytes, sum, kept);
   return 0;
 }
 // parse_sites_resident of a text on the default device -> what abn_sites_fetch gives for its handle, in the arrays of

@@ -138,9 +138,8 @@ struct Inputs {
 // windows_extract.hpp on windows::parse_sites_device
 inline std::vector<Site> parse_sites_device_reduced(const std::string& text);
 
-// device_parse: the methylome files are parsed by abn_sites_parse instead of the getline loop; the same sites
-inline Inputs read_inputs(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
-                          bool device_parse = false) {
+// the nodelist and the edgelist (src/pedigree.rs:98-136) and the sampled ("Y") nodes, their methylomes not yet read
+inline Inputs read_graph(const std::string& nodelist, const std::string& edgelist) {
   Inputs in;
   const std::string nodes_txt = read_file(nodelist, "nodelist"), edges_txt = read_file(edgelist, "edgelist");
   // :98-117
@@ -170,14 +169,37 @@ inline Inputs read_inputs(const std::string& nodelist, const std::string& edgeli
       if (f < all.size() && t < all.size()) in.edges.push_back(EdgeRef{f, t});
     }
   }
+  for (const auto& n : all)  // :138-146
+    if (n.meth) in.nodes.push_back(n);
+  return in;
+}
+
+// :180-184, from the nodes' rc_meth_lvl
+inline void fold_p0uu(Inputs& in) {
+  double p0 = 0.0;
+  for (const auto& n : in.nodes) p0 += 1.0 - n.rc_meth_lvl;
+  in.p0uu = p0 / (double)in.nodes.size();
+}
+
+// device_parse: the methylome files are parsed by abn_sites_parse instead of the getline loop; the same sites.
+// texts (nullable, with device_parse): the sampled nodes' methylome texts, already in memory, in the nodes' order — the
+// files are not opened (scripts/codes_ab.py times the build without the file reads)
+inline Inputs read_inputs(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
+                          bool device_parse = false, const std::vector<std::string>* texts = nullptr) {
+  Inputs in = read_graph(nodelist, edgelist);
   // :138-178 — load the methylomes of the sampled ("Y") nodes
   std::vector<Node>& nodes = in.nodes;
-  for (const auto& n : all)
-    if (n.meth) nodes.push_back(n);
+  if (texts && (!device_parse || texts->size() != nodes.size()))
+    throw Error(ABN_ERR_INVALID_ARG, "one text per sampled node, with device_parse");
   for (auto& node : nodes) {
-    std::ifstream f(node.file);
-    if (!f) throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " + node.file);
-    if (device_parse) {
+    std::ifstream f;
+    if (!texts) {
+      f.open(node.file);
+      if (!f) throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " + node.file);
+    }
+    if (texts) {
+      node.sites = parse_sites_device_reduced((*texts)[(size_t)(&node - nodes.data())]);
+    } else if (device_parse) {
       std::ostringstream ss;
       ss << f.rdbuf();
       node.sites = parse_sites_device_reduced(ss.str());
@@ -198,10 +220,21 @@ inline Inputs read_inputs(const std::string& nodelist, const std::string& edgeli
       }
     node.rc_meth_lvl = sum / (double)cnt;  // :165-166
   }
-  double p0 = 0.0;  // :180-184
-  for (const auto& n : nodes) p0 += 1.0 - n.rc_meth_lvl;
-  in.p0uu = p0 / (double)nodes.size();
+  fold_p0uu(in);
   return in;
+}
+
+// The same Inputs with the sites left on the device (--sites device; defined in windows_extract.hpp on
+// windows::parse_sites_resident and abn_codes_create_parsed): every sampled node's methylome is parsed into a resident
+// handle, the code matrix is packed and rc_meth_lvl folded there, and the D matrix comes from abn_codes_pairwise — no
+// site reaches the host.  Samples of different length, or fewer than two: the handles are fetched into Inputs and the D
+// matrix is dmatrix_on_host's, with its "Lengths do not match" lines.  dm: DMatrix::from's array.
+inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
+                                   std::vector<double>& dm, const std::vector<std::string>* texts = nullptr);
+// abn_codes_kernel_ms of this thread's last read_inputs_resident (merge records, merge inserted, pack, fold)
+inline double* resident_kernel_ms() {
+  static thread_local double ms[4] = {0.0, 0.0, 0.0, 0.0};
+  return ms;
 }
 
 // one byte per (sample, site): status | 0x80 when the posterior is below the filter; sample i's sites at
@@ -239,6 +272,12 @@ inline void write_codes_packed_at(const Inputs& in, double posterior_max_filter,
 }
 // scans Pedigree::build has sent through the packed entry (read by the tests through host_capi.cpp)
 inline std::atomic<long long>& packed_scan_calls() {
+  static std::atomic<long long> calls{0};
+  return calls;
+}
+
+// ... builds whose codes and rc_meth_lvl folds were made on the device from resident sites (abn_codes_create_parsed)
+inline std::atomic<long long>& resident_build_calls() {
   static std::atomic<long long> calls{0};
   return calls;
 }
@@ -385,11 +424,18 @@ inline Pedigree convert(const Inputs& in, const std::vector<double>& dm) {
 
 }  // namespace detail
 
-inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, const std::string& edgelist,
-                                                   double posterior_max_filter, bool gpu_pairwise,
-                                                   bool device_parse) {
-  using namespace detail;
-  const Inputs in = read_inputs(nodelist, edgelist, posterior_max_filter, device_parse);
+namespace detail {
+// Pedigree::build; texts: as read_inputs
+inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, const std::string& edgelist,
+                                                  double posterior_max_filter, bool gpu_pairwise, bool device_parse,
+                                                  bool device_sites, const std::vector<std::string>* texts = nullptr) {
+  if (device_sites) {
+    if (!device_parse || !gpu_pairwise) throw Error(ABN_ERR_INVALID_ARG, "--sites device needs --parse device");
+    std::vector<double> dm;
+    const Inputs in = read_inputs_resident(nodelist, edgelist, posterior_max_filter, dm, texts);
+    return {convert(in, dm), in.p0uu};
+  }
+  const Inputs in = read_inputs(nodelist, edgelist, posterior_max_filter, device_parse, texts);
   const size_t nn = in.nodes.size();
   std::vector<double> dm;
   if (gpu_pairwise && in.same_len() && nn >= 2) {
@@ -408,6 +454,13 @@ inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, 
     dm = dmatrix_on_host(in, posterior_max_filter);
   }
   return {convert(in, dm), in.p0uu};
+}
+}  // namespace detail
+
+inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, const std::string& edgelist,
+                                                   double posterior_max_filter, bool gpu_pairwise,
+                                                   bool device_parse, bool device_sites) {
+  return detail::build_pedigree(nodelist, edgelist, posterior_max_filter, gpu_pairwise, device_parse, device_sites);
 }
 
 // Pedigree::build for many (nodelist, edgelist) pairs — the windows of src/cli/metaprofile.rs:50-72.  With gpu_pairwise

@@ -644,5 +644,66 @@ inline std::vector<Site> parse_sites_device_reduced(const std::string& text) {
     out.push_back(Site{s.posteriormax, s.status_numeric, s.meth_lvl});
   return out;
 }
+
+inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
+                                   std::vector<double>& dm, const std::vector<std::string>* texts) {
+  Inputs in = read_graph(nodelist, edgelist);
+  std::vector<Node>& nodes = in.nodes;
+  const size_t nn = nodes.size();
+  if (texts && texts->size() != nn) throw Error(ABN_ERR_INVALID_ARG, "one text per sampled node");
+  Device& dev = default_device();
+  std::vector<windows::ResidentSites> sites;  // src/pedigree.rs:147-163: every line is read, the warnings in file order
+  for (const Node& node : nodes) {
+    if (texts) {
+      sites.push_back(windows::parse_sites_resident(dev, (*texts)[sites.size()], /*skip_lines=*/0));
+      continue;
+    }
+    std::ifstream f(node.file);
+    if (!f) throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " + node.file);
+    std::ostringstream ss;
+    ss << f.rdbuf();
+    sites.push_back(windows::parse_sites_resident(dev, ss.str(), /*skip_lines=*/0));
+  }
+  struct Codes {
+    abn_codes* h = nullptr;
+    ~Codes() {
+      if (h) abn_codes_destroy(h);
+    }
+  } codes;
+  int32_t same_len = 1;
+  if (nn > 0) {
+    std::vector<abn_sites*> handles;
+    for (const auto& s : sites) handles.push_back(s.get());
+    dev.check(abn_codes_create_parsed(dev.get(), posterior_max_filter, (int32_t)nn, handles.data(), &codes.h),
+              "abn_codes_create_parsed");
+    resident_build_calls().fetch_add(1, std::memory_order_relaxed);
+    std::vector<double> sum(nn);
+    std::vector<int64_t> kept(nn);
+    abn_codes_stats(codes.h, nullptr, sum.data(), kept.data());
+    abn_codes_info(codes.h, nullptr, nullptr, nullptr, &same_len);
+    abn_codes_kernel_ms(codes.h, resident_kernel_ms());
+    for (size_t i = 0; i < nn; ++i) nodes[i].rc_meth_lvl = sum[i] / (double)kept[i];  // :165-166
+  }
+  fold_p0uu(in);
+  if (same_len && nn >= 2) {
+    std::vector<double> dv(nn * (nn - 1) / 2);
+    dev.check(abn_codes_pairwise(codes.h, nullptr, nullptr, dv.data()), "Pedigree::build (pairwise divergence)");
+    dm = dmatrix_of_pairs(nn, dv.data());
+    return in;
+  }
+  // the reference's answer for samples of different length is per pair (:221-227): the host loop gives it
+  for (size_t i = 0; i < nn; ++i) {
+    const size_t n = sites[i].size();
+    std::vector<double> pm(n), ml(n);
+    std::vector<uint8_t> status(n);
+    dev.check(abn_sites_fetch(sites[i].get(), nullptr, nullptr, nullptr, nullptr, nullptr, pm.data(), status.data(), nullptr,
+                              ml.data()),
+              "abn_sites_fetch");
+    nodes[i].sites.resize(n);
+    for (size_t k = 0; k < n; ++k) nodes[i].sites[k] = Site{pm[k], status[k], ml[k]};
+  }
+  dm = dmatrix_on_host(in, posterior_max_filter);
+  return in;
+}
 }  // namespace detail
 }  // namespace alphabeta

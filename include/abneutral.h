@@ -478,6 +478,43 @@ int abn_windows_create_parsed(abn_ctx* ctx, const abn_windows_params* params, ab
  * lines: the merge of src/windows.rs:303-338), each over all samples; 0, 0 for a handle made any other way */
 int abn_windows_merge_ms(const abn_windows* h, double* ms2);
 
+/* ------------------------------------------------------------------ the pedigree build from RESIDENT handles
+ * What Pedigree::build reads of every site, made on the device from n_samples resident handles (abn_sites_parse_dev with
+ * skip_lines 0, abn_sites_insert) without a host copy of any site: the packed matrix abn_pairwise_divergence_packed_dev
+ * scans, and every sample's rc_meth_lvl fold.  Replaces, behind from_methylome_file_line, the `sites.push` loop and the
+ * fold of src/pedigree.rs:147-172 and the status / posterior reads of DMatrix::from (:210-261). */
+typedef struct abn_codes abn_codes;
+/* src/pedigree.rs:147-172 and :245-251 for n_samples methylomes: sample s is samples[s]; its records and inserted lines
+ * are merged in file order on the device, packed (a site is field 3 when posteriormax < posterior_max_filter, :249, else
+ * its status) and folded (sum and number of the meth_lvl with posteriormax >= posterior_max_filter, :159-172; a NaN
+ * posterior is neither filtered nor counted, as there).  The handles are not consumed.  *out is device-resident until
+ * abn_codes_destroy (destroy it before its context).  Samples may differ in length.
+ * ABN_ERR_INVALID_ARG, and no handle comes back: a null pointer, n_samples <= 0 or > 65535, a null or host-form sample
+ * handle, a handle of another context, a handle with deferred lines on which abn_sites_insert was never called. */
+int abn_codes_create_parsed(abn_ctx* ctx, double posterior_max_filter, int32_t n_samples, abn_sites* const* samples,
+                            abn_codes** out);
+int abn_codes_destroy(abn_codes* h);
+/* the shape of the matrix the loop of src/pedigree.rs:210-261 would read: samples, the sites of the longest one, bytes
+ * per packed row (abn_packed_row_stride of that, at least 64), same_len = 1 when every sample has that many sites (:221
+ * compares the lengths per pair); any pointer may be NULL */
+int abn_codes_info(const abn_codes* h, int32_t* n_samples, int64_t* n_sites, int64_t* row_stride_bytes, int32_t* same_len);
+/* [n_samples] each, any may be NULL: count = the sample's sites (src/pedigree.rs:147-163); level_sum_kept / kept = the
+ * fold of :159-172 before its division, from +0.0 in file order with the host's bits, and the number of its terms */
+int abn_codes_stats(const abn_codes* h, int64_t* count, double* level_sum_kept, int64_t* kept);
+/* the packed matrix [n_samples x row_stride_bytes] (format above; what abn_pack_codes writes from the code bytes of
+ * src/pedigree.rs:245-251, every field behind a sample's last site 3): copied to the host, or its device pointer
+ * (16-byte aligned, owned by the handle) */
+int abn_codes_packed(abn_codes* h, uint8_t* host_out);
+int abn_codes_packed_device_ptr(abn_codes* h, void** dev_ptr);
+/* DMatrix::from (src/pedigree.rs:210-261): abn_pairwise_divergence_packed_dev on the resident matrix; HOST outputs
+ * [pairs] with abn_pairwise_divergence_packed's order and NULL rules.  Samples that differ in length (:221-227 gives such
+ * pairs D = 0 and a message; the caller's business): ABN_ERR_INVALID_ARG with a text that says so, the stats stay valid.
+ * n_samples < 2: ABN_OK, nothing is written. */
+int abn_codes_pairwise(abn_codes* h, uint64_t* diff, uint64_t* both, double* dvalue);
+/* double[4]: the HIP-event times of abn_codes_create_parsed's kernels (the merge of src/pedigree.rs:147-163 — the
+ * records' kernel, the inserted lines' — the pack, the fold), each over all samples */
+int abn_codes_kernel_ms(const abn_codes* h, double* ms4);
+
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
  * src/cli/metaprofile.rs:50-72, where every window shares nodelist/edgelist), S starts and B bootstraps
