@@ -168,11 +168,53 @@ static int launch_route(abn_ctx* c, const LaunchRoute& r, const Args& a, hipStre
   return ABN_OK;
 }
 
+// The buffers the ranges of abn_prepare.hpp lie in, and their lengths in bytes
+struct PrepBases {
+  void* base[kPrepBuffers] = {};
+  size_t bytes[kPrepBuffers] = {};
+};
+
+// Fills the ranges of `l` on stream st: in one launch of abn_step_prepare_kernel, or (one_launch = false) as one memset
+// per range — the same list either way.  A range outside its buffer is refused, not written.
+static int clear_ranges(abn_ctx* c, const PrepList& l, const PrepBases& b, hipStream_t st, bool one_launch = true) {
+  PrepArgs pa{};
+  unsigned long long most = 0;
+  for (int k = 0; k < l.n; ++k) {
+    const PrepRange& r = l.r[k];
+    if (!b.base[r.buffer] || r.offset % 4 || r.bytes % 4 || r.offset + r.bytes > b.bytes[r.buffer])
+      return set_err(c, ABN_ERR_INVALID_ARG, "internal: a step's clear lies outside its buffer");
+    char* at = static_cast<char*>(b.base[r.buffer]) + r.offset;
+    if (!one_launch) {
+      HIPCHK(c, hipMemsetAsync(at, r.fill, r.bytes, st));
+      continue;
+    }
+    pa.r[pa.n].p = reinterpret_cast<unsigned*>(at);
+    pa.r[pa.n].words = r.bytes / 4;
+    pa.r[pa.n].fill = 0x01010101u * r.fill;
+    most = std::max(most, pa.r[pa.n].words / 4);
+    ++pa.n;
+  }
+  if (pa.n == 0) return ABN_OK;
+  const unsigned blocks = (unsigned)std::min<unsigned long long>(1024, std::max<unsigned long long>(1, (most + 255) / 256));
+  hipLaunchKernelGGL(abn_step_prepare_kernel, dim3(blocks), dim3(256), 0, st, pa);
+  HIPCHK(c, hipGetLastError());
+  return ABN_OK;
+}
+
+// What a launch that may be persistent brings along: where its status words and its FIFO lie (abn_prepare.hpp) and which
+// of them the step's head has already cleared.  launch_fit clears what is left, in one launch, once the route is known.
+struct LaunchClear {
+  PrepBases bases;
+  int slot = 0, region = 0;
+  bool status_clean = false, fifo_clean = false;
+};
+
 // Runs a.W x a.C chains as route_launch decides.  `a` carries the buffers `offer` promises (queue; park_*, state,
 // susp_list, slice_status); chain_stride, tree, quantum, tail and pass are the route's and are set here.
 // kind (nullable): the ABN_KERNEL_* code of what was launched (PERSISTENT: a.slice_status then counts its fits)
+// lc: required where the offer admits a persistent launch (status words and FIFO must be clear before it)
 static int launch_fit(abn_ctx* c, const PedigreeRoute& pr, const PhaseRoute& ph, FitArgs a, const LaunchOffer& offer,
-                      hipStream_t st, int* kind = nullptr) {
+                      hipStream_t st, int* kind = nullptr, LaunchClear* lc = nullptr) {
   const long long chains = (long long)a.W * a.C;
   LaunchRoute r = route_launch(pr, ph, chains, c->cus, offer);
   if (kind) *kind = r.kind;
@@ -206,10 +248,15 @@ static int launch_fit(abn_ctx* c, const PedigreeRoute& pr, const PhaseRoute& ph,
   if (!persistent) a.queue = nullptr;
   if (r.kind != ABN_KERNEL_STREAM_SWEEP) a.passes = nullptr;
   if (a.tail_cap > 0) a.susp_count = reinterpret_cast<int*>(a.slice_status + kSliceTailFill);
-  if (persistent && a.slice_status) HIPCHK(c, hipMemsetAsync(a.slice_status, 0, kSliceWords * sizeof(unsigned), st));
-  if (a.quantum > 0) {  // empty FIFO of parked chains: entries -1, head = tail = 0
-    HIPCHK(c, hipMemsetAsync(a.parked, 0xff, (size_t)kParkShards * a.park_cap * sizeof(int), st));
-    HIPCHK(c, hipMemsetAsync(a.park_ht, 0, (size_t)kParkShards * kParkHeaderInts * sizeof(unsigned), st));
+  {  // zeroed status words; an empty FIFO of parked chains (entries -1, head = tail = 0): whatever the head left to do
+    const bool status = persistent && a.slice_status, fifo = a.quantum > 0;
+    if ((status || fifo) && !lc) return set_err(c, ABN_ERR_INVALID_ARG, "internal: a persistent launch without its clears");
+    if (lc) {
+      const PrepList l = prep_launch(lc->slot, status && !lc->status_clean, fifo && !lc->fifo_clean, (unsigned)a.park_cap, lc->region);
+      if (int rc = clear_ranges(c, l, lc->bases, st)) return rc;
+      if (status) lc->status_clean = false;   // used
+      if (fifo) lc->fifo_clean = false;
+    }
   }
   if (int rc = launch_route(c, r, a, st)) return rc;
   if (a.tail_cap > 0) {  // the parked tail (possibly empty: workgroups beyond *susp_count leave at once)
@@ -626,8 +673,12 @@ extern "C" int abn_fit_batch_sweep(abn_ctx* c, const abn_options* opts, const do
 // ------------------------------------------------------------------------------------------------
 // (4) device-resident plan
 // ------------------------------------------------------------------------------------------------
-// the plan's timing events: the fit launches of phase A, the selection, the fit launches of phase B
-enum PlanEvent { kEvFitA, kEvFitAEnd, kEvSelect, kEvSelectEnd, kEvFitB, kEvFitBEnd, kPlanEvents };
+// The plan's timing events: the fit launches of phase A, the selection, the fit launches of phase B.  One record where two
+// spans meet: kEvSelect ends phase A's fits and starts the selection, and where phase B is enqueued right behind the
+// selection (abn_plan_run) kEvFitB ends the selection too.  The phases run on their own (abn_plan_run_phase) do not meet:
+// phase A then records kEvSelectEnd and phase B kEvFitBOwn, so that neither moves the other's span;
+// abn_plan::ev_select_end and ev_b_start say which records bound the last selection and the last phase B.
+enum PlanEvent { kEvFitA, kEvSelect, kEvSelectEnd, kEvFitB, kEvFitBOwn, kEvFitBEnd, kPlanEvents };
 
 struct abn_plan {
   abn_ctx* ctx = nullptr;
@@ -661,6 +712,12 @@ struct abn_plan {
   bool stream_b = false;
   double* raw = nullptr;  // raw_own.p or caller-bound
   hipEvent_t ev[kPlanEvents] = {};
+  int ev_select_end = kEvSelectEnd, ev_b_start = kEvFitB;
+  // What the head of the running step has cleared and no launch has used since (launch_phase hands them to launch_fit,
+  // which clears what is not): the status words per slot, the FIFO per region, the two-pass list's counter
+  bool status_clean[kPhaseSlots] = {false, false, false};
+  bool fifo_clean[2] = {false, false};
+  bool tail_clean = false;
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_join;
   // Early bootstraps (abn_plan_run; route_early_bootstraps): phase B launched on a quorum of the starts
@@ -679,9 +736,7 @@ struct abn_plan {
   DevBuf<unsigned long long> sweep_passes;
 };
 
-// The plan's small words, one allocation so that one memset clears a step's and one copy fetches them (in 32-bit words
-// behind the kPhaseSlots x kPhaseWords 64-bit ones): [kEarlyWords early bootstraps][kPhaseSlots x kSliceWords status]
-constexpr size_t kPlanWords64 = (size_t)kPhaseSlots * kPhaseWords + ((size_t)kEarlyWords + (size_t)kPhaseSlots * kSliceWords + 1) / 2;
+// The plan's small words (abn_prepare.hpp: kPlanWords64, and what a step clears of them)
 static unsigned* early_words(const abn_plan* p) { return reinterpret_cast<unsigned*>(p->skipped.p + kPhaseSlots * kPhaseWords); }
 static unsigned* slice_words(const abn_plan* p, int slot) { return early_words(p) + kEarlyWords + kSliceWords * slot; }
 // what verify_persistent and abn_plan_counters fetch: the whole of it
@@ -690,6 +745,9 @@ struct PlanWordsHost {
   unsigned early[kEarlyWords];
   unsigned slice[kPhaseSlots][kSliceWords];
 };
+static_assert(offsetof(PlanWordsHost, early) == kPlanEarlyOffset && offsetof(PlanWordsHost, slice) == plan_status_offset(0) &&
+                  offsetof(PlanWordsHost, slice[kSlotRedo]) == plan_status_offset(kSlotRedo),
+              "abn_prepare.hpp addresses the same words");
 static_assert(sizeof(PlanWordsHost) <= kPlanWords64 * sizeof(unsigned long long) && sizeof(PlanWordsHost) % 8 == 0 &&
                   offsetof(PlanWordsHost, early) == kPhaseSlots * kPhaseWords * sizeof(unsigned long long) &&
                   offsetof(PlanWordsHost, slice) == offsetof(PlanWordsHost, early) + kEarlyWords * sizeof(unsigned),
@@ -775,7 +833,6 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
   if (const size_t chains = plan_sliced_chains(p->route, W * std::max(S, B), c->cus, p->opt.window_groups)) {
     if (p->nm_state.n < chains * kStateDoubles) PALLOC(nm_state, chains * kStateDoubles);
     p->slice_cap = (unsigned)(chains * 16 / kParkShards + 4096);   // per shard; a full shard just stops parking
-    PALLOC(slice_buf, (size_t)kParkShards * ((size_t)kParkHeaderInts + (size_t)p->slice_cap));
     if (p->susp_list.n < chains + 1) PALLOC(susp_list, chains + 1);  // the tail list of the hand-over to the speculative kernel
   }
   p->stream_b = n_boot > 0 && p->route.streams && p->opt.stream_mode == 0;
@@ -789,6 +846,8 @@ extern "C" int abn_plan_create(abn_ctx* c, const abn_options* opts, const double
 #ifdef ABN_MEASUREMENT_KNOBS  // a forced kernel is not what route_early_bootstraps assumed
   if (getenv("ABN_PHASE_A_KERNEL") || getenv("ABN_PHASE_B_KERNEL")) p->early = EarlyRoute{false, 0};
 #endif
+  // the FIFO: one region, and for an eligible plan a second one of the same size for the guarded redo (abn_prepare.hpp)
+  if (p->slice_cap > 0) PALLOC(slice_buf, fifo_bytes(p->slice_cap, p->early.eligible) / sizeof(int));
   if (p->early.eligible) {
     PALLOC(early_state, S * kStateDoubles);
     PALLOC(early_list, S);
@@ -911,6 +970,19 @@ static FitArgs phase_args(const abn_plan* p, int phase, int w0, int wn) {
   return a;
 }
 
+static PrepBases prep_bases(const abn_plan* p) {
+  PrepBases b;
+  b.base[kPrepWords] = p->skipped.p;
+  b.bytes[kPrepWords] = p->skipped.bytes();
+  b.base[kPrepFifo] = p->slice_buf.p;
+  b.bytes[kPrepFifo] = p->slice_buf.bytes();
+  b.base[kPrepSweep] = p->sweep_passes.p;
+  b.bytes[kPrepSweep] = p->sweep_passes.bytes();
+  b.base[kPrepTail] = p->susp_list.p;
+  b.bytes[kPrepTail] = p->susp_list.bytes();
+  return b;
+}
+
 // The fit launch(es) of one phase (0 = A, 1 = B) for the windows `a` covers, on stream st.  A launch that covers the whole
 // plan is offered the phase's chain queue, the plan's parking buffers and its status words; window groups on side streams
 // would share them, so they get none (no persistent kernel, nothing to verify).
@@ -935,10 +1007,16 @@ static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool
     a.queue = reinterpret_cast<unsigned*>(p->skipped.p + kPhaseWords * slot + kPhaseQueue);
     a.slice_status = slice_words(p, slot);
   }
+  LaunchClear lc;
+  lc.bases = prep_bases(p);
+  lc.slot = slot;
+  lc.region = fifo_region_of(slot, p->early.eligible);
+  lc.status_clean = whole && p->status_clean[slot];
+  lc.fifo_clean = whole && p->fifo_clean[lc.region];
   if (offer.parking) {
     a.park_cap = p->slice_cap;
-    a.park_ht = reinterpret_cast<unsigned*>(p->slice_buf.p);
-    a.parked = p->slice_buf.p + kParkShards * kParkHeaderInts;
+    a.park_ht = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p->slice_buf.p) + fifo_header_offset(p->slice_cap, lc.region));
+    a.parked = reinterpret_cast<int*>(reinterpret_cast<char*>(p->slice_buf.p) + fifo_entries_offset(p->slice_cap, lc.region));
     a.state = p->nm_state.p;
     a.susp_list = p->susp_list.p;   // tail hand-over (the route decides whether it applies)
   }
@@ -950,16 +1028,25 @@ static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool
   int kind = ABN_KERNEL_NONE, rc;
   if (ph.two_pass) {
     int* cnt = p->susp_list.p + (size_t)p->W * (size_t)p->S;
-    HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(int), st));
+    if (!p->tail_clean) {
+      PrepList l;
+      prep_two_pass(l, (size_t)p->W * (size_t)p->S);
+      if ((rc = clear_ranges(c, l, lc.bases, st))) return rc;
+    }
+    p->tail_clean = false;
     a.state = p->nm_state.p;
     a.susp_list = p->susp_list.p;
     a.susp_count = cnt;
     offer.pass = 1;
-    rc = launch_fit(c, p->route, ph, a, offer, st, &kind);   // everybody, capped
+    rc = launch_fit(c, p->route, ph, a, offer, st, &kind, &lc);   // everybody, capped
     offer.pass = 2;
-    if (!rc) rc = launch_fit(c, p->route, ph, a, offer, st);  // the parked chains, to the end
+    if (!rc) rc = launch_fit(c, p->route, ph, a, offer, st, nullptr, &lc);  // the parked chains, to the end
   } else {
-    rc = launch_fit(c, p->route, ph, a, offer, st, &kind);
+    rc = launch_fit(c, p->route, ph, a, offer, st, &kind, &lc);
+  }
+  if (whole) {   // what the launch used is no longer clear
+    p->status_clean[slot] = lc.status_clean;
+    p->fifo_clean[lc.region] = lc.fifo_clean;
   }
   if (rc) return rc;
   if (whole) p->persist_expected[phase] = kind == ABN_KERNEL_PERSISTENT ? (long long)a.W * a.C : 0;
@@ -993,7 +1080,8 @@ static SelectArgs select_args(const abn_plan* p, int w0, int wn) {
 // Phase A (starts) + selection for windows [w0, w0+wn) on stream st.  timed: record the plan's timing events around
 // the kernels.  early (abn_plan_run with early bootstraps, one window): the fit launch ends once the plan's quorum of
 // starts has finished — the others park —, and the selection is over the finished ones.
-static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool timed, bool early = false) {
+// b_follows: phase B is enqueued on st right behind the selection, and its first record closes the selection's span too.
+static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool timed, bool b_follows, bool early = false) {
   abn_ctx* c = p->ctx;
   FitArgs a = phase_args(p, 0, w0, wn);
   if (early) {   // W == 1: the counter and the flag are the one window's
@@ -1002,11 +1090,11 @@ static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
   }
   if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitA], st));
   if (int rc = launch_phase(p, 0, a, st, timed)) return rc;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitAEnd], st));
   const SelectArgs s = select_args(p, w0, wn);
   if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvSelect], st));
   if (int rc = launch_select(c, s, p->route.select_lds, st)) return rc;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvSelectEnd], st));
+  if (timed && !b_follows) HIPCHK(c, hipEventRecord(p->ev[kEvSelectEnd], st));
+  if (timed) p->ev_select_end = b_follows ? kEvFitB : kEvSelectEnd;
   return ABN_OK;
 }
 
@@ -1016,6 +1104,7 @@ static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
 struct PhaseGuard {
   const unsigned* word = nullptr;
   int stop = 0, poll = 0, slot = -1;
+  bool ends_phase = true;   // a timed launch records kEvFitBEnd behind it (the early launch does not: the redo follows)
 };
 static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool timed, const PhaseGuard& guard = PhaseGuard{}) {
   abn_ctx* c = p->ctx;
@@ -1023,7 +1112,7 @@ static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
   a.guard = guard.word;
   a.guard_stop = guard.stop;
   a.guard_poll = guard.poll;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitB], st));
+  if (timed) HIPCHK(c, hipEventRecord(p->ev[p->ev_b_start], st));
   if (p->stream_b) {  // gather the bootstrap observations once per fit, then stream them
     double* dst = p->dstar.p + window_offsets(p, w0).boots * (size_t)p->N;
     const long long total = (long long)wn * p->B * p->N;
@@ -1035,20 +1124,27 @@ static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
     a.D = dst;
   }
   if (int rc = launch_phase(p, 1, a, st, timed, guard.slot)) return rc;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvFitBEnd], st));
+  if (timed && guard.ends_phase) HIPCHK(c, hipEventRecord(p->ev[kEvFitBEnd], st));
   return ABN_OK;
 }
 
-// zero the skip counter and the chain queue (abn_plan::skipped) of `n` phases from phase `first`, in one memset; both
-// phases: all of the plan's words, the redo slot, the early bootstraps' counters and flags and the status words included
-static int clear_phase_words(abn_plan* p, int first, int n) {
-  const size_t words = n == 2 ? kPlanWords64 : (size_t)n * kPhaseWords;
+// The head of a step: everything its launches need cleared, in one launch on the context's stream (abn_prepare.hpp).
+// phase < 0: a whole step (abn_plan_run) — all of the plan's words, the redo slot, the early bootstraps' counters and flags
+// and the status words included, the FIFO, and with `early` the redo's FIFO; phase 0 / 1: that phase's run on its own.
+static int prepare_step(abn_plan* p, int phase, bool early) {
+  const bool sweep = p->sweep_passes.p != nullptr;
+  const size_t list = (size_t)p->W * (size_t)p->S;
+  const bool whole_step = phase < 0;
+  const PrepList l = whole_step ? prep_step(p->slice_cap, early, sweep, p->twopass_a && p->S > 0, list)
+                                : prep_phase(phase, p->slice_cap, sweep, p->twopass_a, list);
+  if (int rc = clear_ranges(p->ctx, l, prep_bases(p), p->ctx->stream)) return rc;
   // the stream sweep's record (flag and pass counter per phase) is of the last run of each phase
-  for (int ph = first; ph < first + n && ph < 2; ++ph) {
-    p->sweep_used[ph] = false;
-    if (p->sweep_passes.p) HIPCHK(p->ctx, hipMemsetAsync(p->sweep_passes.p + ph, 0, sizeof(unsigned long long), p->ctx->stream));
-  }
-  HIPCHK(p->ctx, hipMemsetAsync(p->skipped.p + kPhaseWords * first, 0, words * sizeof(unsigned long long), p->ctx->stream));
+  for (int ph = 0; ph < 2; ++ph)
+    if (whole_step || ph == phase) p->sweep_used[ph] = false;
+  for (int slot = 0; slot < kPhaseSlots; ++slot) p->status_clean[slot] = whole_step || slot == phase;
+  p->fifo_clean[0] = p->slice_cap > 0;
+  p->fifo_clean[1] = p->slice_cap > 0 && whole_step && early;
+  p->tail_clean = p->twopass_a && (whole_step ? p->S > 0 : phase == 0);
   return ABN_OK;
 }
 
@@ -1059,13 +1155,13 @@ static int plan_run_phase(abn_plan* p, int32_t phase, ClearWords clear) {
   if (!p->windows_set) return set_err(c, ABN_ERR_STATE, "abn_plan_set_windows has not been called");
   HIPCHK(c, hipSetDevice(c->device));
   if (clear == kClearBothPhases) {
-    if (int rc = clear_phase_words(p, 0, 2)) return rc;
+    if (int rc = prepare_step(p, -1, false)) return rc;
   } else if (clear == kClearOwnPhase) {
-    if (int rc = clear_phase_words(p, phase == 0 ? 0 : 1, 1)) return rc;
+    if (int rc = prepare_step(p, phase == 0 ? 0 : 1, false)) return rc;
   }
   if (phase == 0) {
     if (p->S <= 0) return set_err(c, ABN_ERR_STATE, "plan has no starts");
-    int rc = enqueue_phase_a(p, 0, p->W, c->stream, true);
+    int rc = enqueue_phase_a(p, 0, p->W, c->stream, true, clear == kClearBothPhases && p->B > 0);
     if (rc) return rc;
     p->phase_a_done = true;
     p->ran_a = true;
@@ -1074,6 +1170,7 @@ static int plan_run_phase(abn_plan* p, int32_t phase, ClearWords clear) {
   if (phase == 1) {
     if (p->B <= 0) return set_err(c, ABN_ERR_STATE, "plan has no bootstraps");
     if (!p->phase_a_done) return set_err(c, ABN_ERR_STATE, "phase A has not run");
+    p->ev_b_start = clear == kClearNone ? kEvFitB : kEvFitBOwn;   // behind the selection of this step, or on its own
     int rc = enqueue_phase_b(p, 0, p->W, c->stream, true);
     if (rc) return rc;
     p->ran_b = true;
@@ -1109,12 +1206,15 @@ static int ensure_fork_join(abn_plan* p, int streams) {
   return ABN_OK;
 }
 
-// Wavefront-steps between two looks of the early phase B at the miss word (a power of two; a step is ~2.7 us on C3)
-constexpr int kGuardPoll = 16;
+// Wavefront-steps between two looks of the early phase B at the miss word (a power of two; a step is ~2.7 us on C3, so a
+// missed phase B stops within ~175 us).  Timed at 16 and at 64: 64 is 0.05 ms of a 3 ms step faster on a hit, three runs
+// each against a spread of 0.013 (docs/experiments.md, "Early bootstraps"); tail mode polls every 64 as well.
+constexpr int kGuardPoll = 64;
 
 // abn_plan_run of a plan route_early_bootstraps admits.  No host synchronisation and no wait on a memory value: every
 // launch is enqueued, and those that must not run find that out from the miss word at their entry.
-//   main: clear -> A pass 1 (ends at the quorum) -> select over the finished starts -> fork
+//   main: prepare (every clear of the step, the redo's FIFO included) -> A pass 1 (ends at the quorum)
+//         -> select over the finished starts -> fork
 //   side: A resume (the parked starts) -> select over all starts (scratch) -> compare (raises miss) -> join
 //   main: B + its tail (stop once miss is raised) -> wait for the join -> adopt the scratch selection
 //         -> B + its tail again, in the redo slot (run only if miss is raised)
@@ -1125,8 +1225,8 @@ static int plan_run_early(abn_plan* p) {
   if (int rc = ensure_fork_join(p, 1)) return rc;
   hipStream_t side = c->side[0];
   unsigned* ew = early_words(p);
-  if (int rc = clear_phase_words(p, 0, 2)) return rc;
-  if (int rc = enqueue_phase_a(p, 0, p->W, c->stream, true, true)) return rc;
+  if (int rc = prepare_step(p, -1, true)) return rc;
+  if (int rc = enqueue_phase_a(p, 0, p->W, c->stream, true, true, true)) return rc;
   HIPCHK(c, hipEventRecord(p->ev_fork, c->stream));
   HIPCHK(c, hipStreamWaitEvent(side, p->ev_fork, 0));
   {  // the stragglers: one workgroup per slot of their list (at most S - quorum can be running when the flag goes up)
@@ -1157,6 +1257,8 @@ static int plan_run_early(abn_plan* p) {
   g.word = ew + kEarlyMiss;
   g.stop = 1;
   g.poll = kGuardPoll;
+  g.ends_phase = false;
+  p->ev_b_start = kEvFitB;
   if (int rc = enqueue_phase_b(p, 0, p->W, c->stream, true, g)) return rc;
   HIPCHK(c, hipStreamWaitEvent(c->stream, p->ev_join[0], 0));
   hipLaunchKernelGGL(abn_early_adopt_kernel, dim3(1), dim3(256), 0, c->stream, all, to);
@@ -1193,7 +1295,9 @@ extern "C" int abn_plan_set_stream_sweep(abn_plan* p, int32_t mode) {
     PoolScope pool_scope(c);
     hipError_t e = p->sweep_passes.alloc(2);  // one counter per phase
     if (e != hipSuccess) return set_err(c, ABN_ERR_HIP, std::string("hipMalloc sweep_passes: ") + hipGetErrorString(e));
-    HIPCHK(c, hipMemsetAsync(p->sweep_passes.p, 0, p->sweep_passes.bytes(), c->stream));
+    PrepList l;   // both pass counters, outside a step: the memset form of the step's description
+    l.add(kPrepSweep, 0, p->sweep_passes.bytes(), 0x00);
+    if (int rc = clear_ranges(c, l, prep_bases(p), c->stream, false)) return rc;
   }
   p->sweep_mode = mode;
   return ABN_OK;
@@ -1224,20 +1328,21 @@ extern "C" int abn_plan_run(abn_plan* p) {
   groups = std::max(1, std::min(groups, p->W));
   if (groups == 1 || p->S <= 0 || p->B <= 0) {
     int rc = ABN_OK;
-    if (p->S > 0) rc = plan_run_phase(p, 0, kClearBothPhases);  // one memset for both phases
+    if (p->S > 0) rc = plan_run_phase(p, 0, kClearBothPhases);  // one clear for both phases
     if (rc) return rc;
     if (p->B > 0) rc = plan_run_phase(p, 1, p->S > 0 ? kClearNone : kClearOwnPhase);
     return rc;
   }
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = ensure_fork_join(p, groups)) return rc;
-  if (int rc = clear_phase_words(p, 0, 2)) return rc;
+  if (int rc = prepare_step(p, -1, false)) return rc;
   HIPCHK(c, hipEventRecord(p->ev_fork, c->stream));
   for (int g = 0; g < groups; ++g) {
     const int w0 = (int)((long long)p->W * g / groups), w1 = (int)((long long)p->W * (g + 1) / groups);
     hipStream_t st = c->side[(size_t)g];
     HIPCHK(c, hipStreamWaitEvent(st, p->ev_fork, 0));
-    int rc = enqueue_phase_a(p, w0, w1 - w0, st, g == 0);  // groups share the plan's one queue: no persistent kernel
+    if (g == 0) p->ev_b_start = kEvFitB;
+    int rc = enqueue_phase_a(p, w0, w1 - w0, st, g == 0, true);  // groups share the plan's one queue: no persistent kernel
     if (!rc) rc = enqueue_phase_b(p, w0, w1 - w0, st, g == 0);
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(p->ev_join[(size_t)g], st));
@@ -1313,13 +1418,13 @@ extern "C" int abn_plan_kernel_ms(abn_plan* p, double* ms3) {
   ms3[0] = ms3[1] = ms3[2] = 0.0;
   float ms = 0.f;
   if (p->ran_a) {
-    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[kEvFitA], p->ev[kEvFitAEnd]));
+    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[kEvFitA], p->ev[kEvSelect]));
     ms3[0] = ms;
-    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[kEvSelect], p->ev[kEvSelectEnd]));
+    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[kEvSelect], p->ev[p->ev_select_end]));
     ms3[1] = ms;
   }
   if (p->ran_b) {
-    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[kEvFitB], p->ev[kEvFitBEnd]));
+    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[p->ev_b_start], p->ev[kEvFitBEnd]));
     ms3[2] = ms;
   }
   return ABN_OK;

@@ -1,6 +1,7 @@
 // Selection (ab_neutral::run :83-135), cost batch, bootstrap rows, materialised observations, bootstrap indices.
 #pragma once
 #include "abn_common.hpp"
+#include "abn_prepare.hpp"
 
 namespace abn {
 
@@ -136,6 +137,34 @@ __global__ __launch_bounds__(256) void abn_early_adopt_kernel(const SelectArgs f
     }
     if (i < 4LL * to.W) to.model[i] = from.model[i];
     if (i < to.W) to.best_start[i] = from.best_start[i];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The clears of a plan's step in one launch (abn_prepare.hpp has the list: plan words, FIFO headers and entries, counters).
+// Every range is filled with its byte by all workgroups in turn — 16 bytes per lane where the range's address allows,
+// 4 otherwise; a range's length is a multiple of 4.  A few MB at most: one store per lane on the benchmark's plan.
+// ------------------------------------------------------------------------------------------------
+struct PrepArgs {
+  int n;
+  struct Range {
+    unsigned* p;
+    unsigned long long words;  // 32-bit words
+    unsigned fill;             // the fill byte in all four bytes
+  } r[kPrepMaxRanges];
+};
+
+__global__ __launch_bounds__(256) void abn_step_prepare_kernel(const PrepArgs a) {
+  const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned long long nt = (unsigned long long)gridDim.x * blockDim.x;
+  for (int k = 0; k < a.n; ++k) {
+    unsigned* p = a.r[k].p;
+    const unsigned f = a.r[k].fill;
+    const unsigned long long words = a.r[k].words;
+    const unsigned long long quads = (reinterpret_cast<unsigned long long>(p) & 15ull) == 0 ? words / 4 : 0;
+    uint4* q = reinterpret_cast<uint4*>(p);
+    for (unsigned long long i = t; i < quads; i += nt) q[i] = make_uint4(f, f, f, f);
+    for (unsigned long long i = 4 * quads + t; i < words; i += nt) p[i] = f;
   }
 }
 

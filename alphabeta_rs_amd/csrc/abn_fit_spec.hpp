@@ -460,8 +460,13 @@ __global__ __launch_bounds__(4 * kWave, RMAX <= 2 ? 4 : 3) void abn_fit_spec_ker
   };
 
   while (!done) {
-    if constexpr (QUORUM)  // read once per iteration, well ahead of the update that looks at it
-      if (a.quorum_words) quorum_flag = __hip_atomic_load(a.quorum_words + kEarlyFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // Read every fourth iteration, ahead of the update that looks at it.  The load leaves the XCD (agent scope) and the
+    // exchange's barrier waits for it: read every iteration it made pass 1 of C3 1.07 us per iteration against 0.97 without
+    // (docs/experiments.md, "Early bootstraps").  A chain that parks up to three iterations later parks the same kind of
+    // state at an iteration boundary, and the resume launch finishes it with the same arithmetic.
+    if constexpr (QUORUM)
+      if (a.quorum_words && (iter & 3) == 0)
+        quorum_flag = __hip_atomic_load(a.quorum_words + kEarlyFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     {
       // the candidates of the NEXT iteration for each way this one can end.  Outcome (A, p): the accepted
       // point A replaces the worst vertex and sorts in at rank p; the new order is v0..v3 with A at p.
