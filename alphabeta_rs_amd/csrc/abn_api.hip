@@ -175,8 +175,10 @@ struct PrepBases {
 };
 
 // Fills the ranges of `l` on stream st: in one launch of abn_step_prepare_kernel, or (one_launch = false) as one memset
-// per range — the same list either way.  A range outside its buffer is refused, not written.
+// per range — the same list either way.  A range outside its buffer is refused, not written, and so is a list that
+// could not hold all of its ranges.
 static int clear_ranges(abn_ctx* c, const PrepList& l, const PrepBases& b, hipStream_t st, bool one_launch = true) {
+  if (l.overflow) return set_err(c, ABN_ERR_INVALID_ARG, "internal: a step's clears do not fit their list");
   PrepArgs pa{};
   unsigned long long most = 0;
   for (int k = 0; k < l.n; ++k) {
@@ -201,13 +203,27 @@ static int clear_ranges(abn_ctx* c, const PrepList& l, const PrepBases& b, hipSt
   return ABN_OK;
 }
 
-// What a launch that may be persistent brings along: where its status words and its FIFO lie (abn_prepare.hpp) and which
-// of them the step's head has already cleared.  launch_fit clears what is left, in one launch, once the route is known.
+// What a launch that may be persistent brings along: the buffers its status words and its FIFO lie in (abn_prepare.hpp),
+// which slot and region are its own, and the plan's record of what is still clear.  launch_fit clears what is not, in one
+// launch, once the route is known, and marks what the launch uses as dirty in that record.
 struct LaunchClear {
   PrepBases bases;
+  PrepClean* clean = nullptr;
   int slot = 0, region = 0;
-  bool status_clean = false, fifo_clean = false;
 };
+
+// The chains parked in a's list (a.susp_list, a.susp_count) resume in the speculative kernel and run to their end: one
+// workgroup per slot of the list up to `cap` (those beyond *a.susp_count leave at once)
+static int launch_tail_resume(abn_ctx* c, const PedigreeRoute& pr, FitArgs a, int cap, hipStream_t st) {
+  const LaunchRoute t = route_tail_resume(pr, cap);
+  if (t.status) return set_err(c, t.status, t.error);
+  a.chain_stride = t.chain_stride;
+  a.tree = t.tree;
+  a.queue = nullptr;
+  a.quantum = 0;
+  a.spec_resume = 1;
+  return launch_route(c, t, a, st);
+}
 
 // Runs a.W x a.C chains as route_launch decides.  `a` carries the buffers `offer` promises (queue; park_*, state,
 // susp_list, slice_status); chain_stride, tree, quantum, tail and pass are the route's and are set here.
@@ -252,22 +268,16 @@ static int launch_fit(abn_ctx* c, const PedigreeRoute& pr, const PhaseRoute& ph,
     const bool status = persistent && a.slice_status, fifo = a.quantum > 0;
     if ((status || fifo) && !lc) return set_err(c, ABN_ERR_INVALID_ARG, "internal: a persistent launch without its clears");
     if (lc) {
-      const PrepList l = prep_launch(lc->slot, status && !lc->status_clean, fifo && !lc->fifo_clean, (unsigned)a.park_cap, lc->region);
+      bool& status_clean = lc->clean->status[lc->slot];
+      bool& fifo_clean = lc->clean->fifo[lc->region];
+      const PrepList l = prep_launch(lc->slot, status && !status_clean, fifo && !fifo_clean, (unsigned)a.park_cap, lc->region);
       if (int rc = clear_ranges(c, l, lc->bases, st)) return rc;
-      if (status) lc->status_clean = false;   // used
-      if (fifo) lc->fifo_clean = false;
+      if (status) status_clean = false;   // used
+      if (fifo) fifo_clean = false;
     }
   }
   if (int rc = launch_route(c, r, a, st)) return rc;
-  if (a.tail_cap > 0) {  // the parked tail (possibly empty: workgroups beyond *susp_count leave at once)
-    const LaunchRoute t = route_tail_resume(pr, a.tail_cap);
-    a.chain_stride = t.chain_stride;
-    a.tree = t.tree;
-    a.queue = nullptr;
-    a.quantum = 0;
-    a.spec_resume = 1;
-    return launch_route(c, t, a, st);
-  }
+  if (a.tail_cap > 0) return launch_tail_resume(c, pr, a, a.tail_cap, st);  // the parked tail (possibly empty)
   return ABN_OK;
 }
 
@@ -676,9 +686,29 @@ extern "C" int abn_fit_batch_sweep(abn_ctx* c, const abn_options* opts, const do
 // The plan's timing events: the fit launches of phase A, the selection, the fit launches of phase B.  One record where two
 // spans meet: kEvSelect ends phase A's fits and starts the selection, and where phase B is enqueued right behind the
 // selection (abn_plan_run) kEvFitB ends the selection too.  The phases run on their own (abn_plan_run_phase) do not meet:
-// phase A then records kEvSelectEnd and phase B kEvFitBOwn, so that neither moves the other's span;
-// abn_plan::ev_select_end and ev_b_start say which records bound the last selection and the last phase B.
+// phase A then records kEvSelectEnd and phase B kEvFitBOwn, so that neither moves the other's span; the spans of
+// PhaseRecord and abn_plan::select_span say which records bound the last run of each.
 enum PlanEvent { kEvFitA, kEvSelect, kEvSelectEnd, kEvFitB, kEvFitBOwn, kEvFitBEnd, kPlanEvents };
+struct EventSpan {
+  int begin, end;  // PlanEvent
+};
+
+// What the last run of a phase (0 = A, 1 = B) did.  prepare_step opens it, launch_phase writes what was launched, end_step
+// closes it; the sync (verify_persistent) adds what the device counted.  Nothing else writes it.
+struct PhaseRecord {
+  EventSpan span;               // the records around its fit launches
+  bool ran = false;
+  int32_t kind = 0, lanes = 0;  // ABN_KERNEL_* and lanes per chain of its last timed launch (abn_plan_last_kernels)
+  long long expected = 0;       // chains its persistent launch had to finish (0: none was persistent)
+  long long handed = 0;         // ... of which its tail handed to the speculative kernel (read at the last sync)
+  bool sweep = false;           // a launch of it took abn_sweep_kernel
+};
+// Early bootstraps: whether the last run of phase B was an early run (the miss word then selects the slot of phase B),
+// its starts parked at the quorum and its miss word (read at the last sync)
+struct EarlyRecord {
+  bool ran = false;
+  int32_t parked = 0, miss = 0;
+};
 
 struct abn_plan {
   abn_ctx* ctx = nullptr;
@@ -690,7 +720,8 @@ struct abn_plan {
   PedigreeRoute route{};  // lanes, tree and what the pedigree admits (abn_route.hpp)
   std::vector<uint32_t> wid_host;  // Philox window ids (abn_plan_set_window_ids); empty = window_offset + w
   DevBuf<uint32_t> wid;
-  bool windows_set = false, phase_a_done = false, ran_a = false, ran_b = false;
+  bool windows_set = false;
+  bool model_ready = false;  // a model is in place for phase B: phase A ran, or the caller uploaded one (plan_upload_model)
   DevBuf<double> D, pred, resid, p_uu, eqp, eqp_w, simplexA, bestA, model, lse, bestB, raw_own;
   DevBuf<FitInfoDev> infoA, infoB;
   DevBuf<int32_t> best_start;
@@ -706,40 +737,34 @@ struct abn_plan {
   bool twopass_a = false;
   DevBuf<int> slice_buf;      // time slicing: head, tail, then the FIFO of parked chains
   unsigned slice_cap = 0;
-  long long persist_expected[2] = {0, 0};  // chains the last persistent launch of phase A / B had to finish (0: none)
-  long long tail_handed[2] = {0, 0};       // ... of which its tail handed to the speculative kernel (read at the last sync)
-  int32_t last_kernels[4] = {0, 0, 0, 0};  // abn_plan_last_kernels
   bool stream_b = false;
   double* raw = nullptr;  // raw_own.p or caller-bound
   hipEvent_t ev[kPlanEvents] = {};
-  int ev_select_end = kEvSelectEnd, ev_b_start = kEvFitB;
-  // What the head of the running step has cleared and no launch has used since (launch_phase hands them to launch_fit,
-  // which clears what is not): the status words per slot, the FIFO per region, the two-pass list's counter
-  bool status_clean[kPhaseSlots] = {false, false, false};
-  bool fifo_clean[2] = {false, false};
-  bool tail_clean = false;
+  PhaseRecord rec[2] = {{{kEvFitA, kEvSelect}}, {{kEvFitB, kEvFitBEnd}}};
+  EventSpan select_span{kEvSelect, kEvSelectEnd};  // the records around the last selection
+  EarlyRecord early_rec;
+  // What the head of the running step has cleared (prep_clean of its list) and no launch has used since: launch_phase
+  // hands it to launch_fit, which clears what is not
+  PrepClean clean;
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_join;
   // Early bootstraps (abn_plan_run; route_early_bootstraps): phase B launched on a quorum of the starts
   EarlyRoute early{};
   int early_mode = 1;                 // abn_plan_set_early_bootstraps: 0 off, 1 auto
-  bool early_ran = false;             // the last run of phase B was such a run: the miss word selects the slot of phase B
-  int32_t early_parked = 0, early_miss = 0;   // ... its starts parked at the quorum and its miss word (read at the last sync)
   DevBuf<double> early_state;         // [S x kStateDoubles] the starts parked at the quorum (phase B parks in nm_state)
   DevBuf<int> early_list;             // [S] their list
   DevBuf<double> sel_model, sel_pred, sel_resid;   // the selection over all starts, made beside the early phase B
   DevBuf<int32_t> sel_best;
-  // Stream sweep (abn_plan_set_stream_sweep): the mode, whether the last run of phase A / B launched abn_sweep_kernel, and
-  // the device counter of its passes over the rows (allocated when the mode is first switched on)
+  // Stream sweep (abn_plan_set_stream_sweep): the mode and the device counter of each phase's passes over the rows
+  // (allocated when the mode is first switched on)
   int sweep_mode = 0;
-  bool sweep_used[2] = {false, false};
   DevBuf<unsigned long long> sweep_passes;
 };
 
 // The plan's small words (abn_prepare.hpp: kPlanWords64, and what a step clears of them)
 static unsigned* early_words(const abn_plan* p) { return reinterpret_cast<unsigned*>(p->skipped.p + kPhaseSlots * kPhaseWords); }
 static unsigned* slice_words(const abn_plan* p, int slot) { return early_words(p) + kEarlyWords + kSliceWords * slot; }
-// what verify_persistent and abn_plan_counters fetch: the whole of it
+// what fetch_words copies: the whole of it
 struct PlanWordsHost {
   unsigned long long phase[kPhaseSlots][kPhaseWords];
   unsigned early[kEarlyWords];
@@ -752,6 +777,17 @@ static_assert(sizeof(PlanWordsHost) <= kPlanWords64 * sizeof(unsigned long long)
                   offsetof(PlanWordsHost, early) == kPhaseSlots * kPhaseWords * sizeof(unsigned long long) &&
                   offsetof(PlanWordsHost, slice) == offsetof(PlanWordsHost, early) + kEarlyWords * sizeof(unsigned),
               "PlanWordsHost mirrors the plan's words");
+// enqueues the copy of the plan's words on the context's stream: h holds them once the caller has synchronised it
+static int fetch_words(const abn_plan* p, PlanWordsHost& h) {
+  abn_ctx* c = p->ctx;
+  HIPCHK(c, hipMemcpyAsync(&h, p->skipped.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  return ABN_OK;
+}
+// The slot whose words are those of the last run of `phase`: the phase's own, but the redo's for a phase B whose early
+// run missed — that launch was stopped, and the redo's words are those of one complete phase B
+static int phase_slot(const abn_plan* p, int phase, const PlanWordsHost& h) {
+  return phase == 1 && p->early_rec.ran && h.early[kEarlyMiss] != 0 ? kSlotRedo : phase;
+}
 
 extern "C" int abn_plan_destroy(abn_plan* p) {
   if (!p) return ABN_ERR_INVALID_ARG;
@@ -878,7 +914,7 @@ static int plan_upload_model(abn_plan* p, const double* model, const double* pre
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   p->windows_set = true;
-  p->phase_a_done = true;
+  p->model_ready = true;
   return ABN_OK;
 }
 
@@ -926,7 +962,7 @@ extern "C" int abn_plan_set_windows(abn_plan* p, const double* d_obs, const doub
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));  // sx / ones are host temporaries
   p->windows_set = true;
-  p->phase_a_done = false;
+  p->model_ready = false;
   return ABN_OK;
 }
 
@@ -987,6 +1023,7 @@ static PrepBases prep_bases(const abn_plan* p) {
 // plan is offered the phase's chain queue, the plan's parking buffers and its status words; window groups on side streams
 // would share them, so they get none (no persistent kernel, nothing to verify).
 // slot: which of the plan's kPhaseSlots sets of words the launch counts in (the phase itself; kSlotRedo: the guarded redo)
+// Writes the launch's part of the phase's record (PhaseRecord); timed: this launch is the one abn_plan_last_kernels names.
 static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool timed, int slot = -1) {
   abn_ctx* c = p->ctx;
   if (slot < 0) slot = phase;
@@ -1007,16 +1044,14 @@ static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool
     a.queue = reinterpret_cast<unsigned*>(p->skipped.p + kPhaseWords * slot + kPhaseQueue);
     a.slice_status = slice_words(p, slot);
   }
-  LaunchClear lc;
-  lc.bases = prep_bases(p);
-  lc.slot = slot;
-  lc.region = fifo_region_of(slot, p->early.eligible);
-  lc.status_clean = whole && p->status_clean[slot];
-  lc.fifo_clean = whole && p->fifo_clean[lc.region];
+  // only a launch of the whole plan may be persistent and use the plan's status words and FIFO
+  const int region = fifo_region_of(slot, p->early.eligible);
+  LaunchClear plan_lc{prep_bases(p), &p->clean, slot, region};
+  LaunchClear* lc = whole ? &plan_lc : nullptr;
   if (offer.parking) {
     a.park_cap = p->slice_cap;
-    a.park_ht = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p->slice_buf.p) + fifo_header_offset(p->slice_cap, lc.region));
-    a.parked = reinterpret_cast<int*>(reinterpret_cast<char*>(p->slice_buf.p) + fifo_entries_offset(p->slice_cap, lc.region));
+    a.park_ht = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p->slice_buf.p) + fifo_header_offset(p->slice_cap, region));
+    a.parked = reinterpret_cast<int*>(reinterpret_cast<char*>(p->slice_buf.p) + fifo_entries_offset(p->slice_cap, region));
     a.state = p->nm_state.p;
     a.susp_list = p->susp_list.p;   // tail hand-over (the route decides whether it applies)
   }
@@ -1028,32 +1063,29 @@ static int launch_phase(abn_plan* p, int phase, FitArgs& a, hipStream_t st, bool
   int kind = ABN_KERNEL_NONE, rc;
   if (ph.two_pass) {
     int* cnt = p->susp_list.p + (size_t)p->W * (size_t)p->S;
-    if (!p->tail_clean) {
+    if (!p->clean.two_pass) {
       PrepList l;
       prep_two_pass(l, (size_t)p->W * (size_t)p->S);
-      if ((rc = clear_ranges(c, l, lc.bases, st))) return rc;
+      if ((rc = clear_ranges(c, l, plan_lc.bases, st))) return rc;
     }
-    p->tail_clean = false;
+    p->clean.two_pass = false;   // used
     a.state = p->nm_state.p;
     a.susp_list = p->susp_list.p;
     a.susp_count = cnt;
     offer.pass = 1;
-    rc = launch_fit(c, p->route, ph, a, offer, st, &kind, &lc);   // everybody, capped
+    rc = launch_fit(c, p->route, ph, a, offer, st, &kind, lc);   // everybody, capped
     offer.pass = 2;
-    if (!rc) rc = launch_fit(c, p->route, ph, a, offer, st, nullptr, &lc);  // the parked chains, to the end
+    if (!rc) rc = launch_fit(c, p->route, ph, a, offer, st, nullptr, lc);  // the parked chains, to the end
   } else {
-    rc = launch_fit(c, p->route, ph, a, offer, st, &kind, &lc);
-  }
-  if (whole) {   // what the launch used is no longer clear
-    p->status_clean[slot] = lc.status_clean;
-    p->fifo_clean[lc.region] = lc.fifo_clean;
+    rc = launch_fit(c, p->route, ph, a, offer, st, &kind, lc);
   }
   if (rc) return rc;
-  if (whole) p->persist_expected[phase] = kind == ABN_KERNEL_PERSISTENT ? (long long)a.W * a.C : 0;
-  if (kind == ABN_KERNEL_STREAM_SWEEP) p->sweep_used[phase] = true;
+  PhaseRecord& rec = p->rec[phase];
+  if (whole) rec.expected = kind == ABN_KERNEL_PERSISTENT ? (long long)a.W * a.C : 0;
+  if (kind == ABN_KERNEL_STREAM_SWEEP) rec.sweep = true;
   if (timed) {
-    p->last_kernels[2 * phase] = kind;
-    p->last_kernels[2 * phase + 1] = ph.lanes;
+    rec.kind = kind;
+    rec.lanes = ph.lanes;
   }
   return ABN_OK;
 }
@@ -1094,11 +1126,11 @@ static int enqueue_phase_a(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
   if (timed) HIPCHK(c, hipEventRecord(p->ev[kEvSelect], st));
   if (int rc = launch_select(c, s, p->route.select_lds, st)) return rc;
   if (timed && !b_follows) HIPCHK(c, hipEventRecord(p->ev[kEvSelectEnd], st));
-  if (timed) p->ev_select_end = b_follows ? kEvFitB : kEvSelectEnd;
   return ABN_OK;
 }
 
-// Phase B (bootstraps) for windows [w0, w0+wn) on stream st
+// Phase B (bootstraps) for windows [w0, w0+wn) on stream st.  timed: its first record is kEvFitB behind the selection
+// of the same step (a_precedes), kEvFitBOwn where it runs on its own.
 // A guarded launch (abn_plan_run with early bootstraps) stops when (*guard != 0) == guard_stop — the persistent kernel
 // looks every guard_poll steps, the tail's resume launch at its entry — and counts in the words of `slot`.
 struct PhaseGuard {
@@ -1106,13 +1138,14 @@ struct PhaseGuard {
   int stop = 0, poll = 0, slot = -1;
   bool ends_phase = true;   // a timed launch records kEvFitBEnd behind it (the early launch does not: the redo follows)
 };
-static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool timed, const PhaseGuard& guard = PhaseGuard{}) {
+static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool timed, bool a_precedes,
+                           const PhaseGuard& guard = PhaseGuard{}) {
   abn_ctx* c = p->ctx;
   FitArgs a = phase_args(p, 1, w0, wn);
   a.guard = guard.word;
   a.guard_stop = guard.stop;
   a.guard_poll = guard.poll;
-  if (timed) HIPCHK(c, hipEventRecord(p->ev[p->ev_b_start], st));
+  if (timed) HIPCHK(c, hipEventRecord(p->ev[a_precedes ? kEvFitB : kEvFitBOwn], st));
   if (p->stream_b) {  // gather the bootstrap observations once per fit, then stream them
     double* dst = p->dstar.p + window_offsets(p, w0).boots * (size_t)p->N;
     const long long total = (long long)wn * p->B * p->N;
@@ -1131,6 +1164,7 @@ static int enqueue_phase_b(abn_plan* p, int w0, int wn, hipStream_t st, bool tim
 // The head of a step: everything its launches need cleared, in one launch on the context's stream (abn_prepare.hpp).
 // phase < 0: a whole step (abn_plan_run) — all of the plan's words, the redo slot, the early bootstraps' counters and flags
 // and the status words included, the FIFO, and with `early` the redo's FIFO; phase 0 / 1: that phase's run on its own.
+// What the list leaves clear is read off the list (prep_clean), and the record of the phases it serves is opened.
 static int prepare_step(abn_plan* p, int phase, bool early) {
   const bool sweep = p->sweep_passes.p != nullptr;
   const size_t list = (size_t)p->W * (size_t)p->S;
@@ -1138,54 +1172,29 @@ static int prepare_step(abn_plan* p, int phase, bool early) {
   const PrepList l = whole_step ? prep_step(p->slice_cap, early, sweep, p->twopass_a && p->S > 0, list)
                                 : prep_phase(phase, p->slice_cap, sweep, p->twopass_a, list);
   if (int rc = clear_ranges(p->ctx, l, prep_bases(p), p->ctx->stream)) return rc;
+  p->clean = prep_clean(l, p->slice_cap, list);
   // the stream sweep's record (flag and pass counter per phase) is of the last run of each phase
   for (int ph = 0; ph < 2; ++ph)
-    if (whole_step || ph == phase) p->sweep_used[ph] = false;
-  for (int slot = 0; slot < kPhaseSlots; ++slot) p->status_clean[slot] = whole_step || slot == phase;
-  p->fifo_clean[0] = p->slice_cap > 0;
-  p->fifo_clean[1] = p->slice_cap > 0 && whole_step && early;
-  p->tail_clean = p->twopass_a && (whole_step ? p->S > 0 : phase == 0);
+    if (whole_step || ph == phase) p->rec[ph].sweep = false;
   return ABN_OK;
 }
 
-// which of those words a phase's run zeroes before its launch: none (the other phase's run did), its own, or both phases'
-enum ClearWords { kClearNone, kClearOwnPhase, kClearBothPhases };
-static int plan_run_phase(abn_plan* p, int32_t phase, ClearWords clear) {
-  abn_ctx* c = p->ctx;
-  if (!p->windows_set) return set_err(c, ABN_ERR_STATE, "abn_plan_set_windows has not been called");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (clear == kClearBothPhases) {
-    if (int rc = prepare_step(p, -1, false)) return rc;
-  } else if (clear == kClearOwnPhase) {
-    if (int rc = prepare_step(p, phase == 0 ? 0 : 1, false)) return rc;
+// The end of a step whose every launch has been enqueued: which phases ran, which records bound their spans (a phase
+// that did not run keeps its own), and whether phase B was an early-bootstraps run.
+static void end_step(abn_plan* p, bool ran_a, bool ran_b, bool early) {
+  if (ran_a) {
+    p->rec[0].ran = true;
+    p->model_ready = true;
+    p->select_span.end = ran_b ? kEvFitB : kEvSelectEnd;   // phase B's first record closes the selection where it follows
   }
-  if (phase == 0) {
-    if (p->S <= 0) return set_err(c, ABN_ERR_STATE, "plan has no starts");
-    int rc = enqueue_phase_a(p, 0, p->W, c->stream, true, clear == kClearBothPhases && p->B > 0);
-    if (rc) return rc;
-    p->phase_a_done = true;
-    p->ran_a = true;
-    return ABN_OK;
+  if (ran_b) {
+    p->rec[1].ran = true;
+    p->rec[1].span.begin = ran_a ? kEvFitB : kEvFitBOwn;
+    p->early_rec.ran = early;
   }
-  if (phase == 1) {
-    if (p->B <= 0) return set_err(c, ABN_ERR_STATE, "plan has no bootstraps");
-    if (!p->phase_a_done) return set_err(c, ABN_ERR_STATE, "phase A has not run");
-    p->ev_b_start = clear == kClearNone ? kEvFitB : kEvFitBOwn;   // behind the selection of this step, or on its own
-    int rc = enqueue_phase_b(p, 0, p->W, c->stream, true);
-    if (rc) return rc;
-    p->ran_b = true;
-    p->early_ran = false;
-    return ABN_OK;
-  }
-  return set_err(c, ABN_ERR_INVALID_ARG, "phase must be 0 or 1");
 }
 
-extern "C" int abn_plan_run_phase(abn_plan* p, int32_t phase) {
-  if (!p) return ABN_ERR_INVALID_ARG;
-  return plan_run_phase(p, phase, kClearOwnPhase);
-}
-
-// Whole pass.  opts.window_groups > 1 cuts the plan into contiguous window groups that run A -> select -> B
+// Window groups (run_step).  opts.window_groups > 1 cuts the plan into contiguous window groups that run A -> select -> B
 // on their own HIP streams (a window's bootstraps need only that window's starts), forking from and joining
 // back into the context's stream with events; results do not depend on the grouping and timing events are
 // recorded for group 0.  Streams share a few in-order hardware queues (4 by default), so more than 4 groups
@@ -1206,6 +1215,49 @@ static int ensure_fork_join(abn_plan* p, int streams) {
   return ABN_OK;
 }
 
+// One step, the same sequence for every entry point: the head's clears (prepare_step(prep)), then for each window group
+// phase A with the selection (run_a) and phase B (run_b), then the record (end_step).  One group runs on the context's
+// stream; more fork from it and join back into it.
+static int run_step(abn_plan* p, int prep, bool run_a, bool run_b) {
+  abn_ctx* c = p->ctx;
+  // window groups need both phases: a phase on its own runs whole
+  const int groups = run_a && run_b ? std::max(1, std::min(p->opt.window_groups, p->W)) : 1;
+  const bool forked = groups > 1;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (forked)
+    if (int rc = ensure_fork_join(p, groups)) return rc;
+  if (int rc = prepare_step(p, prep, false)) return rc;
+  if (forked) HIPCHK(c, hipEventRecord(p->ev_fork, c->stream));
+  for (int g = 0; g < groups; ++g) {
+    const int w0 = (int)((long long)p->W * g / groups), wn = (int)((long long)p->W * (g + 1) / groups) - w0;
+    hipStream_t st = forked ? c->side[(size_t)g] : c->stream;
+    if (forked) HIPCHK(c, hipStreamWaitEvent(st, p->ev_fork, 0));
+    // groups share the plan's one queue: no persistent kernel; timing events are recorded for group 0
+    if (run_a)
+      if (int rc = enqueue_phase_a(p, w0, wn, st, g == 0, run_b)) return rc;
+    if (run_b)
+      if (int rc = enqueue_phase_b(p, w0, wn, st, g == 0, run_a)) return rc;
+    if (forked) HIPCHK(c, hipEventRecord(p->ev_join[(size_t)g], st));
+  }
+  // Join only after every group has been enqueued: HIP multiplexes streams onto a few in-order hardware
+  // queues, and a wait packet of the main stream placed between the launches would hold back whichever side
+  // stream shares its queue (scripts/stream_overlap_test.hip: 10 ms instead of 5 ms for four 5 ms kernels).
+  for (int g = 0; forked && g < groups; ++g) HIPCHK(c, hipStreamWaitEvent(c->stream, p->ev_join[(size_t)g], 0));
+  end_step(p, run_a, run_b, false);
+  return ABN_OK;
+}
+
+extern "C" int abn_plan_run_phase(abn_plan* p, int32_t phase) {
+  if (!p) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = p->ctx;
+  if (!p->windows_set) return set_err(c, ABN_ERR_STATE, "abn_plan_set_windows has not been called");
+  if (phase != 0 && phase != 1) return set_err(c, ABN_ERR_INVALID_ARG, "phase must be 0 or 1");
+  if (phase == 0 && p->S <= 0) return set_err(c, ABN_ERR_STATE, "plan has no starts");
+  if (phase == 1 && p->B <= 0) return set_err(c, ABN_ERR_STATE, "plan has no bootstraps");
+  if (phase == 1 && !p->model_ready) return set_err(c, ABN_ERR_STATE, "phase A has not run");
+  return run_step(p, phase, phase == 0, phase == 1);
+}
+
 // Wavefront-steps between two looks of the early phase B at the miss word (a power of two; a step is ~2.7 us on C3, so a
 // missed phase B stops within ~175 us).  Timed at 16 and at 64: 64 is 0.05 ms of a 3 ms step faster on a hit, three runs
 // each against a spread of 0.013 (docs/experiments.md, "Early bootstraps"); tail mode polls every 64 as well.
@@ -1218,7 +1270,7 @@ constexpr int kGuardPoll = 64;
 //   side: A resume (the parked starts) -> select over all starts (scratch) -> compare (raises miss) -> join
 //   main: B + its tail (stop once miss is raised) -> wait for the join -> adopt the scratch selection
 //         -> B + its tail again, in the redo slot (run only if miss is raised)
-// The side work is enqueued before B and the join wait behind B's launches, for the reason given in abn_plan_run.
+// The side work is enqueued before B and the join wait behind B's launches, for the reason given in run_step.
 static int plan_run_early(abn_plan* p) {
   abn_ctx* c = p->ctx;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1231,17 +1283,12 @@ static int plan_run_early(abn_plan* p) {
   HIPCHK(c, hipStreamWaitEvent(side, p->ev_fork, 0));
   {  // the stragglers: one workgroup per slot of their list (at most S - quorum can be running when the flag goes up)
     FitArgs a = phase_args(p, 0, 0, p->W);
-    const LaunchRoute t = route_tail_resume(p->route, p->S - p->early.quorum);
-    if (t.status) return set_err(c, t.status, t.error);
-    a.chain_stride = t.chain_stride;
-    a.tree = t.tree;
-    a.spec_resume = 1;
     a.state = p->early_state.p;
     a.susp_list = p->early_list.p;
     a.susp_count = reinterpret_cast<int*>(ew + kEarlyParked);
     a.slice_status = ew + kEarlySink;
     a.skipped = p->skipped.p + kPhaseSkipped;
-    if (int rc = launch_route(c, t, a, side)) return rc;
+    if (int rc = launch_tail_resume(c, p->route, a, p->S - p->early.quorum, side)) return rc;
   }
   const SelectArgs to = select_args(p, 0, p->W);
   SelectArgs all = to;   // the same rule over all starts: the LSEs are the plan's, the choice goes to scratch
@@ -1258,20 +1305,16 @@ static int plan_run_early(abn_plan* p) {
   g.stop = 1;
   g.poll = kGuardPoll;
   g.ends_phase = false;
-  p->ev_b_start = kEvFitB;
-  if (int rc = enqueue_phase_b(p, 0, p->W, c->stream, true, g)) return rc;
+  if (int rc = enqueue_phase_b(p, 0, p->W, c->stream, true, true, g)) return rc;
   HIPCHK(c, hipStreamWaitEvent(c->stream, p->ev_join[0], 0));
   hipLaunchKernelGGL(abn_early_adopt_kernel, dim3(1), dim3(256), 0, c->stream, all, to);
   HIPCHK(c, hipGetLastError());
   g.stop = 0;
   g.poll = 0;
   g.slot = kSlotRedo;
-  if (int rc = enqueue_phase_b(p, 0, p->W, c->stream, false, g)) return rc;
+  if (int rc = enqueue_phase_b(p, 0, p->W, c->stream, false, true, g)) return rc;
   HIPCHK(c, hipEventRecord(p->ev[kEvFitBEnd], c->stream));   // fit_boot: from the early launch to the end of the redo
-  p->phase_a_done = true;
-  p->ran_a = true;
-  p->ran_b = true;
-  p->early_ran = true;
+  end_step(p, true, true, true);
   return ABN_OK;
 }
 
@@ -1313,9 +1356,9 @@ extern "C" int abn_plan_stream_sweep(abn_plan* p, int64_t* out4) {
   }
   const int rc = verify_persistent(p);  // synchronises the stream
   out4[0] = p->sweep_mode;
-  out4[1] = p->sweep_used[0] ? 1 : 0;
-  out4[2] = p->sweep_used[1] ? 1 : 0;
-  out4[3] = (int64_t)((p->sweep_used[0] ? passes[0] : 0) + (p->sweep_used[1] ? passes[1] : 0));
+  out4[1] = p->rec[0].sweep ? 1 : 0;
+  out4[2] = p->rec[1].sweep ? 1 : 0;
+  out4[3] = (int64_t)((p->rec[0].sweep ? passes[0] : 0) + (p->rec[1].sweep ? passes[1] : 0));
   return rc;
 }
 
@@ -1324,38 +1367,10 @@ extern "C" int abn_plan_run(abn_plan* p) {
   abn_ctx* c = p->ctx;
   if (!p->windows_set) return set_err(c, ABN_ERR_STATE, "abn_plan_set_windows has not been called");
   if (early_applies(p)) return plan_run_early(p);
-  int groups = p->opt.window_groups > 0 ? p->opt.window_groups : 1;
-  groups = std::max(1, std::min(groups, p->W));
-  if (groups == 1 || p->S <= 0 || p->B <= 0) {
-    int rc = ABN_OK;
-    if (p->S > 0) rc = plan_run_phase(p, 0, kClearBothPhases);  // one clear for both phases
-    if (rc) return rc;
-    if (p->B > 0) rc = plan_run_phase(p, 1, p->S > 0 ? kClearNone : kClearOwnPhase);
-    return rc;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = ensure_fork_join(p, groups)) return rc;
-  if (int rc = prepare_step(p, -1, false)) return rc;
-  HIPCHK(c, hipEventRecord(p->ev_fork, c->stream));
-  for (int g = 0; g < groups; ++g) {
-    const int w0 = (int)((long long)p->W * g / groups), w1 = (int)((long long)p->W * (g + 1) / groups);
-    hipStream_t st = c->side[(size_t)g];
-    HIPCHK(c, hipStreamWaitEvent(st, p->ev_fork, 0));
-    if (g == 0) p->ev_b_start = kEvFitB;
-    int rc = enqueue_phase_a(p, w0, w1 - w0, st, g == 0, true);  // groups share the plan's one queue: no persistent kernel
-    if (!rc) rc = enqueue_phase_b(p, w0, w1 - w0, st, g == 0);
-    if (rc) return rc;
-    HIPCHK(c, hipEventRecord(p->ev_join[(size_t)g], st));
-  }
-  // Join only after every group has been enqueued: HIP multiplexes streams onto a few in-order hardware
-  // queues, and a wait packet of the main stream placed between the launches would hold back whichever side
-  // stream shares its queue (scripts/stream_overlap_test.hip: 10 ms instead of 5 ms for four 5 ms kernels).
-  for (int g = 0; g < groups; ++g) HIPCHK(c, hipStreamWaitEvent(c->stream, p->ev_join[(size_t)g], 0));
-  p->phase_a_done = true;
-  p->ran_a = true;
-  p->ran_b = true;
-  p->early_ran = false;
-  return ABN_OK;
+  const bool run_a = p->S > 0, run_b = p->B > 0;
+  if (!run_a && !run_b) return ABN_OK;
+  if (!run_a && !p->model_ready) return set_err(c, ABN_ERR_STATE, "phase A has not run");
+  return run_step(p, run_a ? -1 : 1, run_a, run_b);   // with phase A: one clear for both phases
 }
 
 // A persistent launch must have finished every chain it was given: a lost FIFO entry or a chain that was parked and never
@@ -1367,20 +1382,21 @@ static int verify_persistent(abn_plan* p) {
   abn_ctx* c = p->ctx;
   HIPCHK(c, hipSetDevice(c->device));
   PlanWordsHost h{};
-  const bool check = p->persist_expected[0] > 0 || p->persist_expected[1] > 0;
-  if (check || p->early_ran) HIPCHK(c, hipMemcpyAsync(&h, p->skipped.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  if (p->rec[0].expected > 0 || p->rec[1].expected > 0 || p->early_rec.ran)
+    if (int rc = fetch_words(p, h)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (p->early_ran) {   // a missed early phase B was stopped: the redo's words are phase B's
-    p->early_parked = (int32_t)h.early[kEarlyParked];
-    p->early_miss = h.early[kEarlyMiss] != 0 ? 1 : 0;
+  if (p->early_rec.ran) {
+    p->early_rec.parked = (int32_t)h.early[kEarlyParked];
+    p->early_rec.miss = h.early[kEarlyMiss] != 0 ? 1 : 0;
   }
-  for (int ph = 0; ph < 2 && check; ++ph) {
-    if (p->persist_expected[ph] <= 0) continue;
-    const unsigned* s = h.slice[ph == 1 && p->early_ran && p->early_miss ? kSlotRedo : ph];
-    p->tail_handed[ph] = (long long)s[kSliceHanded];
-    if (s[kSliceError] != 0 || (long long)s[kSliceFinished] != p->persist_expected[ph])
+  for (int ph = 0; ph < 2; ++ph) {
+    PhaseRecord& rec = p->rec[ph];
+    if (rec.expected <= 0) continue;
+    const unsigned* s = h.slice[phase_slot(p, ph, h)];
+    rec.handed = (long long)s[kSliceHanded];
+    if (s[kSliceError] != 0 || (long long)s[kSliceFinished] != rec.expected)
       return set_err(c, ABN_ERR_HIP, std::string("persistent fit launch of phase ") + (ph ? "B" : "A") + " finished " +
-                                         std::to_string(s[kSliceFinished]) + " of " + std::to_string(p->persist_expected[ph]) +
+                                         std::to_string(s[kSliceFinished]) + " of " + std::to_string(rec.expected) +
                                          " chains (error word " + std::to_string(s[kSliceError]) + ", " + std::to_string(s[kSliceHanded]) +
                                          " handed to the speculative kernel, list length " + std::to_string(s[kSliceTailFill]) +
                                          "): results are incomplete");
@@ -1396,8 +1412,7 @@ extern "C" int abn_plan_sync(abn_plan* p) {
 extern "C" int abn_plan_tail_handed(abn_plan* p, int64_t* out2) {
   if (!p || !out2) return ABN_ERR_INVALID_ARG;
   const int rc = verify_persistent(p);  // synchronises the stream and reads the counts of the last persistent launches
-  out2[0] = p->persist_expected[0] > 0 ? p->tail_handed[0] : 0;
-  out2[1] = p->persist_expected[1] > 0 ? p->tail_handed[1] : 0;
+  for (int ph = 0; ph < 2; ++ph) out2[ph] = p->rec[ph].expected > 0 ? p->rec[ph].handed : 0;
   return rc;
 }
 
@@ -1406,26 +1421,22 @@ extern "C" int abn_plan_early_bootstraps(abn_plan* p, int32_t* out4) {
   const int rc = verify_persistent(p);  // synchronises the stream and reads the words of the last run
   out4[0] = p->early.eligible ? 1 : 0;
   out4[1] = p->early.eligible ? p->early.quorum : 0;
-  out4[2] = p->early_ran ? p->early_parked : 0;
-  out4[3] = p->early_ran ? p->early_miss : 0;
+  out4[2] = p->early_rec.ran ? p->early_rec.parked : 0;
+  out4[3] = p->early_rec.ran ? p->early_rec.miss : 0;
   return rc;
 }
 
 extern "C" int abn_plan_kernel_ms(abn_plan* p, double* ms3) {
   if (!p || !ms3) return ABN_ERR_INVALID_ARG;
   abn_ctx* c = p->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  ms3[0] = ms3[1] = ms3[2] = 0.0;
-  float ms = 0.f;
-  if (p->ran_a) {
-    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[kEvFitA], p->ev[kEvSelect]));
-    ms3[0] = ms;
-    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[kEvSelect], p->ev[p->ev_select_end]));
-    ms3[1] = ms;
-  }
-  if (p->ran_b) {
-    HIPCHK(c, hipEventElapsedTime(&ms, p->ev[p->ev_b_start], p->ev[kEvFitBEnd]));
-    ms3[2] = ms;
+  const EventSpan span[3] = {p->rec[0].span, p->select_span, p->rec[1].span};  // fit_starts, select, fit_boot
+  const bool ran[3] = {p->rec[0].ran, p->rec[0].ran, p->rec[1].ran};
+  for (int k = 0; k < 3; ++k) {
+    float ms = 0.f;
+    if (ran[k]) HIPCHK(c, hipEventElapsedTime(&ms, p->ev[span[k].begin], p->ev[span[k].end]));
+    ms3[k] = ms;
   }
   return ABN_OK;
 }
@@ -1456,13 +1467,13 @@ extern "C" int abn_plan_download(abn_plan* p, double* models, double* pred, doub
   if (info_a && p->S) HIPCHK(c, hipMemcpyAsync(info_a, p->infoA.p, p->infoA.bytes(), hipMemcpyDeviceToHost, s));
   if (info_b && B) HIPCHK(c, hipMemcpyAsync(info_b, p->infoB.p, p->infoB.bytes(), hipMemcpyDeviceToHost, s));
   std::vector<int32_t> bs;
-  if (p->ran_a) {  // the selection's verdict per window, whether or not the caller asked for it
+  if (p->rec[0].ran) {  // the selection's verdict per window, whether or not the caller asked for it
     bs.resize(W);
     HIPCHK(c, hipMemcpyAsync(bs.data(), p->best_start.p, p->best_start.bytes(), hipMemcpyDeviceToHost, s));
   }
   if (int rc = verify_persistent(p)) return rc;  // synchronises the stream
   if (best_start) {
-    if (p->ran_a) std::copy(bs.begin(), bs.end(), best_start);
+    if (p->rec[0].ran) std::copy(bs.begin(), bs.end(), best_start);
     else std::fill(best_start, best_start + W, 0);  // model uploaded by the caller (abn_boot_model_run)
   }
   // every buffer has been filled; windows whose starts all ended non-finite carry NaN and best_start = -1
@@ -1476,7 +1487,7 @@ extern "C" int abn_plan_analyze(abn_plan* p, double* out, int32_t* first_bad) {
   if (!p) return ABN_ERR_INVALID_ARG;
   abn_ctx* c = p->ctx;
   if (!out) return set_err(c, ABN_ERR_INVALID_ARG, "null out");
-  if (!p->ran_b || p->B <= 0) return set_err(c, ABN_ERR_STATE, "phase B has not run: there is no bootstrap table");
+  if (!p->rec[1].ran || p->B <= 0) return set_err(c, ABN_ERR_STATE, "phase B has not run: there is no bootstrap table");
   if (int rc = verify_persistent(p)) return rc;  // synchronises the stream
   return analyze_device_table(c, p->raw, p->W, p->B, out, first_bad);
 }
@@ -1485,7 +1496,7 @@ extern "C" int abn_plan_failed_windows(abn_plan* p, int32_t* n_failed) {
   if (!p || !n_failed) return ABN_ERR_INVALID_ARG;
   abn_ctx* c = p->ctx;
   *n_failed = 0;
-  if (!p->ran_a) return verify_persistent(p);
+  if (!p->rec[0].ran) return verify_persistent(p);
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<int32_t> bs((size_t)p->W);
   HIPCHK(c, hipMemcpyAsync(bs.data(), p->best_start.p, p->best_start.bytes(), hipMemcpyDeviceToHost, c->stream));
@@ -1498,29 +1509,27 @@ extern "C" int abn_plan_counters(abn_plan* p, int64_t* out5) {
   if (!p || !out5) return ABN_ERR_INVALID_ARG;
   abn_ctx* c = p->ctx;
   out5[0] = out5[1] = out5[2] = out5[3] = out5[4] = 0;
-  std::vector<FitInfoDev> h;
-  auto add = [&](const DevBuf<FitInfoDev>& b, int phase) -> int {
-    if (!b.n) return ABN_OK;
-    h.resize(b.n);
-    PlanWordsHost wd{};
-    HIPCHK(c, hipMemcpyAsync(h.data(), b.p, b.bytes(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&wd, p->skipped.p, sizeof wd, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (const auto& f : h) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const DevBuf<FitInfoDev>* info[2] = {&p->infoA, &p->infoB};
+  std::vector<FitInfoDev> h[2];
+  PlanWordsHost wd{};
+  for (int ph = 0; ph < 2; ++ph) {
+    if (!p->rec[ph].ran || !info[ph]->n) continue;
+    h[ph].resize(info[ph]->n);
+    HIPCHK(c, hipMemcpyAsync(h[ph].data(), info[ph]->p, info[ph]->bytes(), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (int rc = fetch_words(p, wd)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int ph = 0; ph < 2; ++ph) {
+    if (h[ph].empty()) continue;
+    for (const auto& f : h[ph]) {
       out5[0] += 1;
       out5[1] += f.evals;
       out5[2] += f.iters;
     }
-    // early bootstraps: a missed phase B was stopped and redone — the redo's count is that of one complete phase B
-    const int slot = phase == 1 && p->early_ran && wd.early[kEarlyMiss] != 0 ? kSlotRedo : phase;
-    out5[3 + phase] = (int64_t)wd.phase[slot][kPhaseSkipped];
-    return ABN_OK;
-  };
-  int rc = ABN_OK;
-  if (p->ran_a) rc = add(p->infoA, 0);
-  if (rc) return rc;
-  if (p->ran_b) rc = add(p->infoB, 1);
-  return rc;
+    out5[3 + ph] = (int64_t)wd.phase[phase_slot(p, ph, wd)][kPhaseSkipped];
+  }
+  return ABN_OK;
 }
 
 #ifdef ABN_STAMPS
@@ -1545,7 +1554,10 @@ extern "C" int abn_plan_debug_stamps_spec(abn_plan* p, unsigned long long* out8)
 
 extern "C" int abn_plan_last_kernels(abn_plan* p, int32_t* out4) {
   if (!p || !out4) return ABN_ERR_INVALID_ARG;
-  for (int k = 0; k < 4; ++k) out4[k] = p->last_kernels[k];
+  for (int ph = 0; ph < 2; ++ph) {
+    out4[2 * ph] = p->rec[ph].kind;
+    out4[2 * ph + 1] = p->rec[ph].lanes;
+  }
   return ABN_OK;
 }
 

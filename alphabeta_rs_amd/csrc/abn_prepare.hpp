@@ -2,6 +2,8 @@
 // host arithmetic in the manner of abn_constants.hpp, no device code, no HIP header (tests/native/step_prepare_main.cpp
 // compiles it alone).  abn_step_prepare_kernel (abn_aux_kernels.hpp) fills a list of these ranges in ONE launch; the
 // memset form of the same list (one hipMemsetAsync per range, abn_api.hip: clear_ranges) serves outside a step.
+// The ranges a persistent launch depends on are named once (status_range, fifo_*_range, two_pass_range): the lists add
+// them, and prep_clean reads off a list which of them it leaves clear (PrepClean, kept in abn_plan::clean).
 //
 // Buffers (PrepBuffer) and what lies in them:
 //   kPrepWords  abn_plan::skipped — kPhaseSlots x kPhaseWords 64-bit words (skip counter, chain queue), then kEarlyWords
@@ -43,29 +45,56 @@ struct PrepRange {
   unsigned char fill;
 };
 
+// The ranges a launch depends on, named once: the lists below add them, prep_clean looks for them
+// the status words of one slot's persistent launch
+constexpr PrepRange status_range(int slot) { return {kPrepWords, plan_status_offset(slot), (size_t)kSliceWords * 4, 0x00}; }
+// an empty FIFO: head = tail = available = 0, every entry -1
+constexpr PrepRange fifo_header_range(unsigned slice_cap, int region) {
+  return {kPrepFifo, fifo_header_offset(slice_cap, region), (size_t)kParkShards * kParkHeaderInts * 4, 0x00};
+}
+constexpr PrepRange fifo_entries_range(unsigned slice_cap, int region) {
+  return {kPrepFifo, fifo_entries_offset(slice_cap, region), (size_t)kParkShards * slice_cap * 4, 0xff};
+}
+// the counter of a two-pass phase A's list of parked starts (behind its W x S entries)
+constexpr PrepRange two_pass_range(size_t list_entries) { return {kPrepTail, list_entries * 4, 4, 0x00}; }
+
 constexpr int kPrepMaxRanges = 8;
 struct PrepList {
   int n = 0;
+  bool overflow = false;  // a range did not fit: the list is incomplete, clear_ranges refuses it and prep_clean claims nothing
   PrepRange r[kPrepMaxRanges] = {};
-  void add(int buffer, size_t offset, size_t bytes, unsigned char fill) {
-    if (bytes > 0 && n < kPrepMaxRanges) r[n++] = PrepRange{buffer, offset, bytes, fill};
+  void add(const PrepRange& x) {
+    if (x.bytes == 0) return;
+    if (n < kPrepMaxRanges) r[n++] = x;
+    else overflow = true;
+  }
+  void add(int buffer, size_t offset, size_t bytes, unsigned char fill) { add(PrepRange{buffer, offset, bytes, fill}); }
+  // every byte of x is written by the list, with x's fill (an empty x: no such range in this plan, never covered)
+  bool covers(const PrepRange& x) const {
+    if (x.bytes == 0 || overflow) return false;
+    size_t at = x.offset;
+    const size_t end = x.offset + x.bytes;
+    for (int k = 0; k < n && at < end; ++k)   // each pass extends the covered prefix or ends the search
+      for (int i = 0; i < n; ++i)
+        if (r[i].buffer == x.buffer && r[i].fill == x.fill && r[i].offset <= at && at < r[i].offset + r[i].bytes) {
+          at = r[i].offset + r[i].bytes;
+          break;
+        }
+    return at >= end;
   }
 };
 
-// an empty FIFO: head = tail = available = 0, every entry -1
 inline void prep_fifo(PrepList& l, unsigned slice_cap, int region) {
-  l.add(kPrepFifo, fifo_header_offset(slice_cap, region), (size_t)kParkShards * kParkHeaderInts * 4, 0x00);
-  l.add(kPrepFifo, fifo_entries_offset(slice_cap, region), (size_t)kParkShards * slice_cap * 4, 0xff);
+  l.add(fifo_header_range(slice_cap, region));
+  l.add(fifo_entries_range(slice_cap, region));
 }
-// the status words of one slot's persistent launch
-inline void prep_status(PrepList& l, int slot) { l.add(kPrepWords, plan_status_offset(slot), (size_t)kSliceWords * 4, 0x00); }
+inline void prep_status(PrepList& l, int slot) { l.add(status_range(slot)); }
 // skip counter and chain queue of one phase (abn_plan_run_phase), with the phase's pass counter of the stream sweep
 inline void prep_phase_words(PrepList& l, int phase, bool sweep_counters) {
   l.add(kPrepWords, (size_t)kPhaseWords * phase * 8, (size_t)kPhaseWords * 8, 0x00);
   if (sweep_counters) l.add(kPrepSweep, (size_t)phase * 8, 8, 0x00);
 }
-// the counter of a two-pass phase A's list of parked starts (behind its W x S entries)
-inline void prep_two_pass(PrepList& l, size_t list_entries) { l.add(kPrepTail, list_entries * 4, 4, 0x00); }
+inline void prep_two_pass(PrepList& l, size_t list_entries) { l.add(two_pass_range(list_entries)); }
 
 // What a run of ONE phase through abn_plan_run_phase clears at its head: the phase's words and everything its launch may
 // use (a launch that turns out not to be persistent leaves the status words and the FIFO unused)
@@ -99,6 +128,26 @@ inline PrepList prep_launch(int slot, bool status, bool fifo, unsigned slice_cap
   if (status) prep_status(l, slot);
   if (fifo) prep_fifo(l, slice_cap, region);
   return l;
+}
+
+// What a persistent launch may find clear and use without a clear of its own: the status words per slot, the FIFO per
+// region, the two-pass list's counter.  A launch marks what it uses as dirty (abn_api.hip: launch_fit, launch_phase).
+constexpr int kFifoRegionsMax = fifo_regions(true);
+struct PrepClean {
+  bool status[kPhaseSlots] = {};
+  bool fifo[kFifoRegionsMax] = {};
+  bool two_pass = false;
+};
+
+// What a list leaves clear — read off the list itself, so that the record cannot claim what was not written: clear exactly
+// when the list covers all of the range with its fill byte.  slice_cap 0: the plan has no FIFO.
+inline PrepClean prep_clean(const PrepList& l, unsigned slice_cap, size_t list_entries) {
+  PrepClean c;
+  for (int slot = 0; slot < kPhaseSlots; ++slot) c.status[slot] = l.covers(status_range(slot));
+  for (int region = 0; region < kFifoRegionsMax; ++region)
+    c.fifo[region] = l.covers(fifo_header_range(slice_cap, region)) && l.covers(fifo_entries_range(slice_cap, region));
+  c.two_pass = l.covers(two_pass_range(list_entries));
+  return c;
 }
 
 }  // namespace abn

@@ -8,6 +8,10 @@
 // own region.  Checked: the bytes after both are the same (the description covers exactly the union of the memsets'
 // ranges, each with its fill byte), no byte is written twice, no range leaves its buffer, every range is a multiple of 4.
 //
+// What a list is said to leave clear (prep_clean: each slot's status words, each FIFO region, the two-pass counter) is set
+// against the bytes the list wrote, for every list above: claimed if and only if every byte of that range was written with
+// its fill, and never for a range the plan does not have.  A list given more ranges than it holds says so.
+//
 // argv[1] = "list": print one line per case instead of checking quietly (the Python test reads them).
 #include <cstdio>
 #include <cstdlib>
@@ -95,6 +99,55 @@ void compare(const Case& k, const Buffers& model, const Buffers& got, bool model
     }
 }
 
+// every byte of [off, off + n) exists in buffer `buf` and was written, with `fill`
+bool written(const Buffers& b, int buf, size_t off, size_t n, unsigned char fill) {
+  if (n == 0 || off + n > b.bytes[buf]) return false;
+  for (size_t i = off; i < off + n; ++i)
+    if (b.hits[buf][i] == 0 || b.mem[buf][i] != fill) return false;
+  return true;
+}
+
+// prep_clean of a list against the bytes that list wrote into g (the ranges written out here, not taken from the header)
+int clean_lists = 0, clean_claims = 0;
+void check_clean(const Case& k, const PrepList& l, const Buffers& g) {
+  const PrepClean c = prep_clean(l, k.slice_cap, k.chains);
+  const size_t status0 = (size_t)kPhaseSlots * kPhaseWords * 8 + (size_t)kEarlyWords * 4;
+  for (int slot = 0; slot < kPhaseSlots; ++slot) {
+    const size_t at = status0 + (size_t)kSliceWords * 4 * slot;
+    const bool is = written(g, kPrepWords, at, (size_t)kSliceWords * 4, 0x00);
+    if (c.status[slot] != is) fail(k, is ? "cleared status words not claimed" : "status words claimed clear that are not", kPrepWords, at);
+    clean_claims += c.status[slot];
+  }
+  const size_t header = (size_t)kParkShards * kParkHeaderInts * 4, entries = (size_t)kParkShards * k.slice_cap * 4;
+  for (int region = 0; region < (int)(sizeof c.fifo / sizeof c.fifo[0]); ++region) {
+    const size_t base = (size_t)region * (header + entries);
+    const bool has = k.slice_cap > 0 && region < (k.eligible ? 2 : 1);
+    const bool is = has && written(g, kPrepFifo, base, header, 0x00) && written(g, kPrepFifo, base + header, entries, 0xff);
+    if (c.fifo[region] != is) fail(k, is ? "cleared FIFO not claimed" : "FIFO claimed clear that is not (or that the plan lacks)", kPrepFifo, base);
+    clean_claims += c.fifo[region];
+  }
+  const bool is = k.two_pass && written(g, kPrepTail, k.chains * 4, 4, 0x00);
+  if (c.two_pass != is) fail(k, is ? "cleared two-pass counter not claimed" : "two-pass counter claimed clear that is not", kPrepTail, k.chains * 4);
+  clean_claims += c.two_pass;
+  if (l.overflow) fail(k, "list overflowed", -1, (size_t)l.n);
+  ++clean_lists;
+}
+
+// a list says when a range did not fit, and then claims nothing clear
+bool check_overflow() {
+  PrepList l;
+  for (int i = 0; i < kPrepMaxRanges; ++i) l.add(kPrepWords, plan_status_offset(0) + 4 * (size_t)i, 4, 0x00);
+  l.add(kPrepWords, 0, 0, 0x00);   // an empty range takes no place
+  if (l.overflow || l.n != kPrepMaxRanges) return false;
+  PrepList full;
+  full.add(kPrepWords, 0, kPlanWords64 * 8, 0x00);
+  if (!prep_clean(full, 0, 0).status[0]) return false;
+  for (int i = 1; i <= kPrepMaxRanges; ++i) full.add(kPrepSweep, 0, 8, 0x00);
+  l.add(kPrepSweep, 0, 8, 0x00);
+  const PrepClean c = prep_clean(full, 0, 0);
+  return l.overflow && l.n == kPrepMaxRanges && full.overflow && !c.status[0] && !c.status[1] && !c.status[kSlotRedo];
+}
+
 // serial model: the memsets of one persistent launch (launch_fit as it was)
 void model_launch(Buffers& m, int slot, unsigned cap, int region, bool status, bool fifo) {
   const size_t early = (size_t)kPhaseSlots * kPhaseWords * 8;
@@ -117,7 +170,9 @@ void check_step(const Case& k) {
   if (k.two_pass) m.set(kPrepTail, k.chains * 4, 0x00, 4);
   model_launch(m, 1, k.slice_cap, 0, true, k.slice_cap > 0);
   if (k.early) model_launch(m, kSlotRedo, k.slice_cap, 1, true, k.slice_cap > 0);
-  apply(k, prep_step(k.slice_cap, k.early, k.sweep, k.two_pass, k.chains), g);
+  const PrepList l = prep_step(k.slice_cap, k.early, k.sweep, k.two_pass, k.chains);
+  apply(k, l, g);
+  check_clean(k, l, g);
   compare(k, m, g, true);   // the status words' memsets repeat the words' clear: that is what the step drops
 }
 
@@ -128,7 +183,9 @@ void check_phase(const Case& k, int phase) {
   if (k.sweep) m.set(kPrepSweep, (size_t)phase * 8, 0x00, 8);
   if (k.two_pass && phase == 0) m.set(kPrepTail, k.chains * 4, 0x00, 4);
   model_launch(m, phase, k.slice_cap, 0, true, k.slice_cap > 0);
-  apply(k, prep_phase(phase, k.slice_cap, k.sweep, k.two_pass, k.chains), g);
+  const PrepList l = prep_phase(phase, k.slice_cap, k.sweep, k.two_pass, k.chains);
+  apply(k, l, g);
+  check_clean(k, l, g);
   compare(k, m, g, false);
 }
 
@@ -142,7 +199,9 @@ void check_launch(const Case& k) {
       if (region >= fifo_regions(k.eligible)) fail(k, "region beyond the plan's", kPrepFifo, (size_t)region);
       Buffers m = sized(k), g = sized(k);
       model_launch(m, slot, k.slice_cap, region, status, fifo);
-      apply(k, prep_launch(slot, status, fifo, k.slice_cap, region), g);
+      const PrepList l = prep_launch(slot, status, fifo, k.slice_cap, region);
+      apply(k, l, g);
+      check_clean(k, l, g);
       compare(k, m, g, false);
     }
 }
@@ -183,6 +242,13 @@ int main(int argc, char** argv) {
       std::printf("FAIL region arithmetic at cap %u\n", cap);
       ++failures;
     }
+  const bool overflow_ok = check_overflow();
+  if (!overflow_ok) {
+    std::printf("FAIL a list given more than %d ranges does not report it\n", kPrepMaxRanges);
+    ++failures;
+  }
+  if (list) std::printf("clean record: %d lists checked, %d ranges claimed clear\noverflow of %d ranges reported: %s\n", clean_lists,
+                        clean_claims, kPrepMaxRanges + 1, overflow_ok ? "ok" : "FAILED");
   if (failures) {
     std::printf("step prepare: %d failure(s) in %d cases\n", failures, cases);
     return 1;

@@ -2,7 +2,8 @@
 abn_step_prepare_kernel fills in one launch, against a serial host model of the memsets that launch replaces — for a sweep
 of chain counts, FIFO capacities, eligible or not, early run or not, two-pass, sweep counters.  The checks are those of
 tests/native/step_prepare_main.cpp (the same union of bytes, each with its fill byte; no byte twice; nothing past a buffer
-whose heap block is exactly its length); here the program is built and run, plain and under the host sanitizers."""
+whose heap block is exactly its length; what each list is said to leave clear against the bytes it wrote; an overflowing
+list reported); here the program is built and run, plain and under the host sanitizers."""
 import re
 import shutil
 import subprocess
@@ -35,6 +36,13 @@ def test_description_matches_the_memsets_it_replaces(tmp_path):
     caps = {int(m.group(1)): int(m.group(2)) for ln in lines
             for m in [re.search(r"chains 10000 cap (\d+) eligible 1 early 1 two_pass 0 sweep 0 fifo_bytes (\d+)", ln)] if m}
     assert caps == {6596: 2 * 64 * (192 + 6596) * 4}, caps
+    # the clean record derived from each list (prep_clean) was set against the bytes that list wrote: prep_step and both
+    # prep_phase lists of every case, and the prep_launch lists of the cases that have them; an overflowing list says so
+    m = re.search(r"clean record: (\d+) lists checked, (\d+) ranges claimed clear", r.stdout)
+    assert m, r.stdout[-1500:]
+    launch_cases = [ln for ln in lines if " early 0 two_pass 0 sweep 0 " in ln]
+    assert int(m.group(1)) >= 3 * len(lines) + 3 * len(launch_cases) and int(m.group(2)) >= int(m.group(1)), m.group(0)
+    assert re.search(r"overflow of \d+ ranges reported: ok", r.stdout), r.stdout[-1500:]
 
 
 def test_description_under_address_and_ub_sanitizers(tmp_path):
