@@ -66,6 +66,8 @@ EXPORTED_SYMBOLS = [
     "abn_plan_set_stream_sweep", "abn_plan_stream_sweep", "abn_multi_set_stream_sweep", "abn_fit_batch_sweep",
     "abn_codes_create_parsed", "abn_codes_destroy", "abn_codes_info", "abn_codes_stats", "abn_codes_packed",
     "abn_codes_packed_device_ptr", "abn_codes_pairwise", "abn_codes_kernel_ms",
+    "abn_sites_common", "abn_sites_common_dev", "abn_windows_create_aligned", "abn_codes_create_aligned",
+    "abn_windows_common", "abn_codes_common",
 ]
 
 
@@ -216,6 +218,12 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_codes_packed_device_ptr.argtypes = [vp, C.POINTER(vp)]
     L.abn_codes_pairwise.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
     L.abn_codes_kernel_ms.argtypes = [vp, dp]
+    L.abn_sites_common.argtypes = [vp, C.c_int32, i64p, C.POINTER(C.c_int32), u32p, u32p, u8p, u8p, i64p]
+    L.abn_sites_common_dev.argtypes = [vp, C.c_int32, i64p, vp, vp, vp, vp, vp, i64p]
+    L.abn_windows_create_aligned.argtypes = L.abn_windows_create_parsed.argtypes
+    L.abn_codes_create_aligned.argtypes = L.abn_codes_create_parsed.argtypes
+    L.abn_windows_common.argtypes = [vp, i64p, i64p, dp]
+    L.abn_codes_common.argtypes = [vp, i64p, i64p, dp]
     i32p = C.POINTER(C.c_int32)
     L.abn_genes_create.argtypes = [vp, C.c_int32, i32p, i32p, i64p, u32p, u32p, u8p, C.POINTER(vp)]
     L.abn_genes_destroy.argtypes = [vp]
@@ -688,6 +696,20 @@ class Context:
                                              u[3].ctypes.data_as(u8p), _u32p(gs), _u32p(ge), fl.ctypes.data_as(u8p), _dp(ms)))
         return gs, ge, fl, ms
 
+    def common_sites(self, site_offset, chromosome, start, end, strand):
+        """The sites every sample shares, by key (chromosome, start, end, strand), on the device (abn_sites_common: lifts
+        the assumption of src/pedigree.rs:240).  Arguments as choose_genes.  Returns (keep uint8 (S,), n_common): keep marks
+        every sample's common sites, n_common of them in each.  AbnError when a sample is not well ordered (a chromosome in
+        two runs, a key not above the one before it) or the samples' common sites come in different orders."""
+        off, u = _site_arrays(site_offset, chromosome, start, end, strand)
+        keep = np.zeros(int(off[-1]), dtype=np.uint8)
+        n_common = C.c_int64(-1)
+        u8p = C.POINTER(C.c_uint8)
+        self._check(self._L.abn_sites_common(self._h, off.shape[0] - 1, off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             u[0].ctypes.data_as(C.POINTER(C.c_int32)), _u32p(u[1]), _u32p(u[2]),
+                                             u[3].ctypes.data_as(u8p), keep.ctypes.data_as(u8p), C.byref(n_common)))
+        return keep, n_common.value
+
     def choose_genes_dev(self, genes: "Genes", site_offset, chromosome_ptr: int, start_ptr: int, end_ptr: int,
                          strand_ptr: int, gene_start_ptr: int, gene_end_ptr: int, flags_ptr: int, *, cutoff,
                          cutoff_gene_length=False) -> np.ndarray:
@@ -1017,10 +1039,11 @@ class Windows:
 
     @classmethod
     def from_parsed(cls, ctx: Context, genes: Genes, sites_list, *, posterior_max_filter, cutoff,
-                    cutoff_gene_length=False, step, size, absolute, counts):
+                    cutoff_gene_length=False, step, size, absolute, counts, align=False):
         """The handle from resident parse results (Context.parse_sites_resident, one Sites per methylome, their deferred
         lines decided and inserted): merged in file order, the genes chosen and the windows placed on the device, no site
-        record coming back to the host (abn_windows_create_parsed).  The Sites are not consumed."""
+        record coming back to the host (abn_windows_create_parsed).  The Sites are not consumed.  align: only the sites
+        every sample shares (Context.common_sites) are placed (abn_windows_create_aligned), so no window is ragged."""
         self = cls.__new__(cls)
         self.ctx = ctx
         self._L = ctx._L
@@ -1030,8 +1053,9 @@ class Windows:
         rule = GeneRule(cutoff, 1 if cutoff_gene_length else 0)
         handles = (C.c_void_p * max(self.n_samples, 1))(*(s._h for s in sites_list))
         h = C.c_void_p()
-        ctx._check(self._L.abn_windows_create_parsed(ctx._h, C.byref(p), genes._h, C.byref(rule), posterior_max_filter,
-                                                     self.n_samples, handles, C.byref(h)))
+        create = self._L.abn_windows_create_aligned if align else self._L.abn_windows_create_parsed
+        ctx._check(create(ctx._h, C.byref(p), genes._h, C.byref(rule), posterior_max_filter, self.n_samples, handles,
+                          C.byref(h)))
         self._h = h
         W, stride, ns = C.c_int32(), C.c_int64(), C.c_int64()
         ctx._check(self._L.abn_windows_info(h, C.byref(W), C.byref(stride), C.byref(ns)))
@@ -1043,6 +1067,14 @@ class Windows:
         ms = np.zeros(2)
         self.ctx._check(self._L.abn_windows_merge_ms(self._h, _dp(ms)))
         return ms
+
+    def common(self):
+        """(before int64 (n_samples,), n_common, ms (4,)): every sample's sites before the alignment, the sites each keeps
+        (-1: not made with align) and the HIP-event ms of the common-site kernels (runs and ends, match, scan and rank,
+        gather; zeros without align)"""
+        before, n_common, ms = np.zeros(self.n_samples, dtype=np.int64), C.c_int64(-1), np.zeros(4)
+        self.ctx._check(self._L.abn_windows_common(self._h, before.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_common), _dp(ms)))
+        return before, n_common.value, ms
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1102,17 +1134,20 @@ class Codes:
     sample's rc_meth_lvl fold."""
 
     @classmethod
-    def from_parsed(cls, ctx: Context, sites_list, *, posterior_max_filter):
+    def from_parsed(cls, ctx: Context, sites_list, *, posterior_max_filter, align=False):
         """From resident parse results (Context.parse_sites_resident with skip_lines 0 for the pedigree build, one Sites
         per methylome, their deferred lines decided and inserted): merged in file order, packed and folded on the device,
-        no site record coming back to the host (abn_codes_create_parsed).  The Sites are not consumed."""
+        no site record coming back to the host (abn_codes_create_parsed).  The Sites are not consumed.  align: only the
+        sites every sample shares (Context.common_sites) are packed and folded (abn_codes_create_aligned): the samples have
+        the same length then, and stats() describes the aligned sites."""
         self = cls.__new__(cls)
         self.ctx = ctx
         self._L = ctx._L
         sites_list = list(sites_list)
         handles = (C.c_void_p * max(len(sites_list), 1))(*(s._h for s in sites_list))
         h = C.c_void_p()
-        ctx._check(self._L.abn_codes_create_parsed(ctx._h, posterior_max_filter, len(sites_list), handles, C.byref(h)))
+        create = self._L.abn_codes_create_aligned if align else self._L.abn_codes_create_parsed
+        ctx._check(create(ctx._h, posterior_max_filter, len(sites_list), handles, C.byref(h)))
         self._h = h
         i = self.info()
         self.n_samples, self.n_sites, self.row_stride, self.same_len = i["n_samples"], i["n_sites"], i["row_stride"], i["same_len"]
@@ -1163,6 +1198,14 @@ class Codes:
         u64p = C.POINTER(C.c_uint64)
         self.ctx._check(self._L.abn_codes_pairwise(self._h, diff.ctypes.data_as(u64p), both.ctypes.data_as(u64p), _dp(dval)))
         return diff, both, dval
+
+    def common(self):
+        """(before int64 (n_samples,), n_common, ms (4,)): every sample's sites before the alignment, the sites each keeps
+        (-1: not made with align) and the HIP-event ms of the common-site kernels (runs and ends, match, scan and rank,
+        gather; zeros without align)"""
+        before, n_common, ms = np.zeros(self.n_samples, dtype=np.int64), C.c_int64(-1), np.zeros(4)
+        self.ctx._check(self._L.abn_codes_common(self._h, before.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_common), _dp(ms)))
+        return before, n_common.value, ms
 
     def kernel_ms(self) -> np.ndarray:
         """the HIP-event ms of from_parsed's kernels: merge of the records, merge of the inserted lines, pack, fold"""

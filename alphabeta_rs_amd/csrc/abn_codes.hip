@@ -1,6 +1,7 @@
 // abn_codes_*: the pedigree build's code matrix and rc_meth_lvl folds from resident parse results (src/pedigree.rs:138-178
 // behind from_methylome_file_line, and the status bytes DMatrix::from reads, :210-261).  Kernels and arithmetic:
-// abn_codes.hpp; the merge launches are abn_sites.hip's (the records are its handle's), the scan abn_pairwise.hip's.
+// abn_codes.hpp; the merge launches are abn_sites.hip's (the records are its handle's), the scan abn_pairwise.hip's, the
+// common-site step of abn_codes_create_aligned abn_sites_common.hip's.
 #include "abn_host.hpp"
 #define ABN_CODES_KERNELS
 #include "abn_codes.hpp"
@@ -16,13 +17,48 @@ struct abn_codes {
   std::vector<int64_t> count, kept;  // [n]
   std::vector<double> level_sum_kept;
   double ms[4] = {0.0, 0.0, 0.0, 0.0};  // merge records, merge inserted, pack, fold
+  std::vector<int64_t> before;          // [n]: every sample's sites as they came (abn_codes_common)
+  int64_t n_common = -1;                // abn_codes_create_aligned: the sites every sample keeps
+  double common_ms[4] = {0.0, 0.0, 0.0, 0.0};
   DevBuf<uint8_t> packed;               // [n x stride], device-resident between calls
 };
 
-// merge, pack, fold; the merged arrays (9 bytes per site) live only in here
-static int codes_build(abn_codes* h, double filter, abn_sites* const* samples) {
+// merge, pack, fold; the merged arrays (9 bytes per site) live only in here.  With `align` the merge is the full one, keys
+// included (and the reduced one behind it, for the merged bytes: merge_code has no kCodeCounted), and the sites every
+// sample shares (abn_sites_common.hpp) are gathered out of it into the arrays the pack and the fold read.
+static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, bool align) {
   abn_ctx* c = h->ctx;
   const int n = h->n;
+  DevBuf<int32_t> mchrom;
+  DevBuf<uint32_t> mstart, mend;
+  DevBuf<uint8_t> mstrand, mcode;
+  DevBuf<double> mlevel;
+  CommonState st;
+  std::vector<int64_t> merged_off((size_t)n + 1, 0);
+  if (align) {
+    for (int s = 0; s < n; ++s) merged_off[(size_t)s + 1] = merged_off[(size_t)s] + h->count[(size_t)s];
+    const size_t S = (size_t)merged_off[(size_t)n];
+    HIPCHK(c, mchrom.alloc(S));
+    HIPCHK(c, mstart.alloc(S));
+    HIPCHK(c, mend.alloc(S));
+    HIPCHK(c, mstrand.alloc(S));
+    HIPCHK(c, mcode.alloc(S));
+    HIPCHK(c, mlevel.alloc(S));
+    for (int pass = 0; pass < 2; ++pass)
+      for (int s = 0; s < n; ++s) {
+        const size_t o = (size_t)merged_off[(size_t)s];
+        if (h->count[(size_t)s] == 0) continue;
+        if (int rc = sites_merge_dev(samples[s], pass == 1, filter, mchrom.p + o, mstart.p + o, mend.p + o, mstrand.p + o,
+                                     mcode.p + o, mlevel.p + o))
+          return rc;
+      }
+    if (int rc = sites_common_match(c, n, merged_off.data(), CommonSites{mchrom.p, mstart.p, mend.p, mstrand.p}, nullptr, st))
+      return rc;
+    h->n_common = st.n_common;
+    h->count.assign((size_t)n, st.n_common);  // from here on the handle is one of n samples of n_common sites
+    h->max_sites = st.n_common;
+    h->same_len = true;
+  }
   std::vector<long long> site_off((size_t)n + 1, 0), code_off((size_t)n + 1, 0);
   for (int s = 0; s < n; ++s) {
     site_off[(size_t)s + 1] = site_off[(size_t)s] + h->count[(size_t)s];
@@ -57,11 +93,19 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples) {
   for (int pass = 0; pass < 2; ++pass) {  // the fields kernels of every sample, then the insert kernels
     HIPCHK(c, hipEventRecord(ev.e[pass], c->stream));
     for (int s = 0; s < n; ++s) {
-      if (h->count[(size_t)s] == 0) continue;
-      if (int rc = sites_merge_codes_dev(samples[s], pass == 1, filter, dcode.p + code_off[(size_t)s],
-                                         dlevel.p + site_off[(size_t)s]))
+      if (h->before[(size_t)s] == 0) continue;
+      if (int rc = align ? sites_merge_codes_dev(samples[s], pass == 1, filter, mcode.p + merged_off[(size_t)s],
+                                                 mlevel.p + merged_off[(size_t)s])
+                         : sites_merge_codes_dev(samples[s], pass == 1, filter, dcode.p + code_off[(size_t)s],
+                                                 dlevel.p + site_off[(size_t)s]))
         return rc;
     }
+  }
+  if (align) {  // (returns after completion; the events below still bracket the pack and the fold)
+    if (int rc = sites_common_gather(c, st, CommonGather{mcode.p, mlevel.p, nullptr, nullptr, nullptr, nullptr, dlevel.p,
+                                                         dcode.p, code_off[1]}))
+      return rc;
+    std::copy(st.ms, st.ms + 4, h->common_ms);
   }
   HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
   const unsigned grid = (unsigned)(((long long)n * row_dwords + kCodesThreads - 1) / kCodesThreads);
@@ -87,8 +131,8 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples) {
   return ABN_OK;
 }
 
-extern "C" int abn_codes_create_parsed(abn_ctx* c, double posterior_max_filter, int32_t n_samples,
-                                       abn_sites* const* samples, abn_codes** out) {
+static int codes_create_parsed(abn_ctx* c, double posterior_max_filter, int32_t n_samples, abn_sites* const* samples,
+                               bool align, abn_codes** out) {
   if (!c) return ABN_ERR_INVALID_ARG;
   if (out) *out = nullptr;
   if (!out || !samples || n_samples <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
@@ -112,11 +156,30 @@ extern "C" int abn_codes_create_parsed(abn_ctx* c, double posterior_max_filter, 
     }
     HIPCHK(c, hipSetDevice(c->device));
     PoolScope pool_scope(c);
-    if (int rc = codes_build(h.get(), posterior_max_filter, samples)) return rc;
+    h->before = h->count;
+    if (int rc = codes_build(h.get(), posterior_max_filter, samples, align)) return rc;
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
   }
   *out = h.release();
+  return ABN_OK;
+}
+
+extern "C" int abn_codes_create_parsed(abn_ctx* c, double posterior_max_filter, int32_t n_samples,
+                                       abn_sites* const* samples, abn_codes** out) {
+  return codes_create_parsed(c, posterior_max_filter, n_samples, samples, false, out);
+}
+
+extern "C" int abn_codes_create_aligned(abn_ctx* c, double posterior_max_filter, int32_t n_samples,
+                                        abn_sites* const* samples, abn_codes** out) {
+  return codes_create_parsed(c, posterior_max_filter, n_samples, samples, true, out);
+}
+
+extern "C" int abn_codes_common(const abn_codes* h, int64_t* before, int64_t* n_common, double* ms4) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (before) std::copy(h->before.begin(), h->before.end(), before);
+  if (n_common) *n_common = h->n_common;
+  if (ms4) std::copy(h->common_ms, h->common_ms + 4, ms4);
   return ABN_OK;
 }
 

@@ -1,5 +1,5 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (abn_api.hip, abn_pairwise.hip,
-// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip): the context, its device-buffer pool, error reporting,
+// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip): the context, its device-buffer pool, error reporting,
 // the kernel_ms timer.  Not part of the C-ABI (include/abneutral.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/abneutral.h"
+#include "abn_sites_common.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // Device-buffer pool of a context.  The drop-in entry points (abn_ab_neutral_run, abn_boot_model_run, abn_cost_batch,
@@ -208,4 +209,28 @@ int sites_merge_dev(const abn_sites* h, bool inserted, double filter, int32_t* d
 // ... and for abn_codes_create_parsed (abn_codes.hip): the same merge in its reduced form (abn_codes.hpp), the merged byte
 // and the level of every site
 int sites_merge_codes_dev(const abn_sites* h, bool inserted, double filter, uint8_t* dcode, double* dlevel);
+// abn_sites_common.hip, for abn_windows_create_aligned and abn_codes_create_aligned: the common-site step
+// (abn_sites_common.hpp) on DEVICE key arrays, in its two halves.  sites_common_match runs the order checks, the match and
+// the ranks, waits, and leaves n_common in the state (dkeep [site_offset[n]], or null: the state's own); the caller sizes
+// its aligned arrays and sites_common_gather fills them (any output of g may be null) and makes the co-ordering check.
+// Either refuses with ABN_ERR_INVALID_ARG and the text of common_refusal_text.  Both return after completion.
+struct CommonState {
+  int n = 0, probe = 0;
+  long long Lp = 0, n_common = 0;
+  std::vector<long long> site_off;
+  CommonSites in{};
+  uint8_t* keep = nullptr;
+  DevBuf<uint8_t> keep_own;
+  DevBuf<long long> dsite_off, run_begin, run_end, err;
+  DevBuf<uint32_t> match, src, block;
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};  // runs and ends; match; scan and rank; gather
+  size_t temp_bytes = 0;                // of the buffers above
+  CommonState() = default;
+  CommonState(const CommonState&) = delete;
+  CommonState& operator=(const CommonState&) = delete;
+  ~CommonState();
+};
+int sites_common_match(abn_ctx* c, int n, const int64_t* site_offset, const CommonSites& in, uint8_t* dkeep, CommonState& st);
+int sites_common_gather(abn_ctx* c, CommonState& st, const CommonGather& g);
 }  // namespace abn

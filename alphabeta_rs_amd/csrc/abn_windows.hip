@@ -1,6 +1,7 @@
 // abn_windows_*: the window-placement handle.  Kernels: abn_windows.hpp; the scan of the placed windows
 // (abn_windows_pairwise) is abn_pairwise.hip's, the gene choice of abn_windows_create_sites abn_genes.hip's, the merge of
-// resident parse results in front of abn_windows_create_parsed abn_sites.hip's.
+// resident parse results in front of abn_windows_create_parsed abn_sites.hip's, the common-site step between that merge and
+// the gene choice of abn_windows_create_aligned abn_sites_common.hip's.
 #include "abn_host.hpp"
 #include "abn_windows.hpp"
 
@@ -18,6 +19,9 @@ struct abn_windows {
   std::vector<int32_t> ragged;
   std::vector<double> level_sum, level_sum_kept;
   double merge_ms[2] = {0.0, 0.0};  // abn_windows_create_parsed: its fields and insert kernels
+  std::vector<int64_t> before;      // [n]: every sample's sites as they came (abn_windows_common)
+  int64_t n_common = -1;            // abn_windows_create_aligned: the sites every sample keeps
+  double common_ms[4] = {0.0, 0.0, 0.0, 0.0};
   DevBuf<uint8_t> packed;  // [n x stride], device-resident between calls
 };
 
@@ -204,11 +208,13 @@ static int windows_build_sites(abn_windows* h, const abn_windows_params* p, abn_
 }
 
 // ... from RESIDENT parse results (abn_sites_parse_dev, abn_sites_insert): every sample's records and inserted lines
-// merged in file order straight into the arrays the gene choice and the placement read (abn_sites_merge.hpp)
+// merged in file order straight into the arrays the gene choice and the placement read (abn_sites_merge.hpp); with
+// `align`, the sites every sample shares (abn_sites_common.hpp) gathered out of them first
 static int windows_build_parsed(abn_windows* h, const abn_windows_params* p, abn_genes* genes, const abn_gene_rule* rule,
-                                double filter, const int64_t* site_offset, abn_sites* const* samples) {
+                                double filter, const int64_t* site_offset, abn_sites* const* samples, bool align) {
   abn_ctx* c = h->ctx;
-  const size_t S = (size_t)site_offset[h->n];
+  const int n = h->n;
+  const size_t S = (size_t)site_offset[n];
   DevBuf<int32_t> dchrom;
   DevBuf<uint32_t> dstart, dend, dgs, dge;
   DevBuf<uint8_t> dstrand, dflags, dcode;
@@ -222,18 +228,18 @@ static int windows_build_parsed(abn_windows* h, const abn_windows_params* p, abn
   HIPCHK(c, dflags.alloc(S));
   HIPCHK(c, dcode.alloc(std::max<size_t>(S, 1)));
   HIPCHK(c, dlevel.alloc(std::max<size_t>(S, 1)));
+  struct Events {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
   if (S > 0) {
-    struct Events {
-      hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-      ~Events() {
-        for (hipEvent_t x : e)
-          if (x) (void)hipEventDestroy(x);
-      }
-    } ev;
     for (int k = 0; k < 3; ++k) HIPCHK(c, hipEventCreate(&ev.e[k]));
     for (int pass = 0; pass < 2; ++pass) {  // the fields kernels of every sample, then the insert kernels
       HIPCHK(c, hipEventRecord(ev.e[pass], c->stream));
-      for (int s = 0; s < h->n; ++s) {
+      for (int s = 0; s < n; ++s) {
         const size_t o = (size_t)site_offset[s];
         if (site_offset[s + 1] == site_offset[s]) continue;
         if (int rc = sites_merge_dev(samples[s], pass == 1, filter, dchrom.p + o, dstart.p + o, dend.p + o, dstrand.p + o,
@@ -242,16 +248,49 @@ static int windows_build_parsed(abn_windows* h, const abn_windows_params* p, abn
       }
     }
     HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
-    if (int rc = genes_choose_dev(genes, rule, h->n, site_offset, dchrom.p, dstart.p, dend.p, dstrand.p, dgs.p, dge.p,
-                                  dflags.p, nullptr))  // (ends in a synchronisation)
+  }
+  // what the gene choice and the placement read: the merged arrays, or their aligned copies (n_common sites per sample;
+  // the gene arrays and the flags, written behind the step, are the merged arrays' own: no longer than those)
+  const int64_t* offset = site_offset;
+  const int32_t* chrom = dchrom.p;
+  const uint32_t *start = dstart.p, *end = dend.p;
+  const uint8_t *strand = dstrand.p, *code = dcode.p;
+  const double* level = dlevel.p;
+  DevBuf<int32_t> achrom;
+  DevBuf<uint32_t> astart, aend;
+  DevBuf<uint8_t> astrand, acode;
+  DevBuf<double> alevel;
+  std::vector<int64_t> aligned_offset((size_t)n + 1, 0);
+  if (align) {  // (no site at all: n_common = 0 through the same path)
+    CommonState st;
+    if (int rc = sites_common_match(c, n, site_offset, CommonSites{dchrom.p, dstart.p, dend.p, dstrand.p}, nullptr, st))
       return rc;
+    const size_t A = (size_t)n * (size_t)st.n_common;
+    HIPCHK(c, achrom.alloc(A));
+    HIPCHK(c, astart.alloc(A));
+    HIPCHK(c, aend.alloc(A));
+    HIPCHK(c, astrand.alloc(A));
+    HIPCHK(c, acode.alloc(std::max<size_t>(A, 1)));
+    HIPCHK(c, alevel.alloc(std::max<size_t>(A, 1)));
+    if (int rc = sites_common_gather(c, st, CommonGather{dcode.p, dlevel.p, achrom.p, astart.p, aend.p, astrand.p, alevel.p,
+                                                         acode.p, st.n_common}))
+      return rc;
+    h->n_common = st.n_common;
+    std::copy(st.ms, st.ms + 4, h->common_ms);
+    for (int s = 0; s <= n; ++s) aligned_offset[(size_t)s] = (int64_t)s * st.n_common;
+    offset = aligned_offset.data();
+    chrom = achrom.p, start = astart.p, end = aend.p, strand = astrand.p, code = acode.p, level = alevel.p;
+  }
+  if (offset[n] > 0)
+    if (int rc = genes_choose_dev(genes, rule, n, offset, chrom, start, end, strand, dgs.p, dge.p, dflags.p, nullptr))
+      return rc;  // (ends in a synchronisation)
+  if (S > 0)
     for (int k = 0; k < 2; ++k) {
       float ms = 0.f;
       HIPCHK(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
       h->merge_ms[k] = ms;
     }
-  }
-  return windows_build_dev(h, p, site_offset, dstart.p, dgs.p, dge.p, dflags.p, dcode.p, dlevel.p);
+  return windows_build_dev(h, p, offset, start, dgs.p, dge.p, dflags.p, code, level);
 }
 
 // the checks of abn_windows_create and abn_windows_create_sites on what they share
@@ -272,7 +311,8 @@ static int windows_check(abn_ctx* c, const abn_windows_params* p, int32_t n_samp
 
 // the handle around build(handle): created, built, handed out
 template <class Build>
-static int windows_make(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, abn_windows** out, Build build) {
+static int windows_make(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, const int64_t* site_offset,
+                        abn_windows** out, Build build) {
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
   std::unique_ptr<abn_windows> h(new (std::nothrow) abn_windows);
@@ -281,6 +321,8 @@ static int windows_make(abn_ctx* c, const abn_windows_params* p, int32_t n_sampl
   h->n = n_samples;
   h->W = p->n_upstream + p->n_gene + p->n_downstream;
   try {
+    h->before.resize((size_t)n_samples);
+    for (int s = 0; s < n_samples; ++s) h->before[(size_t)s] = site_offset[s + 1] - site_offset[s];
     if (int rc = build(h.get())) return rc;
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
@@ -304,14 +346,14 @@ extern "C" int abn_windows_create_sites(abn_ctx* c, const abn_windows_params* p,
   for (int64_t i = 0; i < S; ++i)
     if (chromosome[i] < 0 || chromosome[i] >= 258 || strand[i] > 2)  // the table of abn_genes.hpp: 258 chromosome keys
       return set_err(c, ABN_ERR_INVALID_ARG, "a site's chromosome is outside 0..257, or its strand above 2");
-  return windows_make(c, p, n_samples, out, [&](abn_windows* h) {
+  return windows_make(c, p, n_samples, site_offset, out, [&](abn_windows* h) {
     return windows_build_sites(h, p, genes, rule, site_offset, chromosome, start, end, strand, code, level);
   });
 }
 
-extern "C" int abn_windows_create_parsed(abn_ctx* c, const abn_windows_params* p, abn_genes* genes,
-                                         const abn_gene_rule* rule, double posterior_max_filter, int32_t n_samples,
-                                         abn_sites* const* samples, abn_windows** out) {
+static int windows_create_parsed(abn_ctx* c, const abn_windows_params* p, abn_genes* genes, const abn_gene_rule* rule,
+                                 double posterior_max_filter, int32_t n_samples, abn_sites* const* samples, bool align,
+                                 abn_windows** out) {
   if (!c) return ABN_ERR_INVALID_ARG;
   if (out) *out = nullptr;
   if (!p || !out || !samples || n_samples <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
@@ -334,9 +376,21 @@ extern "C" int abn_windows_create_parsed(abn_ctx* c, const abn_windows_params* p
   if (int rc = windows_check(c, p, n_samples, site_offset.data(), out)) return rc;
   if (!genes || !rule) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
   if (genes_ctx(genes) != c) return set_err(c, ABN_ERR_INVALID_ARG, "the genes belong to another context");
-  return windows_make(c, p, n_samples, out, [&](abn_windows* h) {
-    return windows_build_parsed(h, p, genes, rule, posterior_max_filter, site_offset.data(), samples);
+  return windows_make(c, p, n_samples, site_offset.data(), out, [&](abn_windows* h) {
+    return windows_build_parsed(h, p, genes, rule, posterior_max_filter, site_offset.data(), samples, align);
   });
+}
+
+extern "C" int abn_windows_create_parsed(abn_ctx* c, const abn_windows_params* p, abn_genes* genes,
+                                         const abn_gene_rule* rule, double posterior_max_filter, int32_t n_samples,
+                                         abn_sites* const* samples, abn_windows** out) {
+  return windows_create_parsed(c, p, genes, rule, posterior_max_filter, n_samples, samples, false, out);
+}
+
+extern "C" int abn_windows_create_aligned(abn_ctx* c, const abn_windows_params* p, abn_genes* genes,
+                                          const abn_gene_rule* rule, double posterior_max_filter, int32_t n_samples,
+                                          abn_sites* const* samples, abn_windows** out) {
+  return windows_create_parsed(c, p, genes, rule, posterior_max_filter, n_samples, samples, true, out);
 }
 
 extern "C" int abn_windows_create(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, const int64_t* site_offset,
@@ -347,7 +401,7 @@ extern "C" int abn_windows_create(abn_ctx* c, const abn_windows_params* p, int32
   if (int rc = windows_check(c, p, n_samples, site_offset, out)) return rc;
   if (site_offset[n_samples] > 0 && (!pos || !gene_start || !gene_end || !flags || !code || !level))
     return set_err(c, ABN_ERR_INVALID_ARG, "null site arrays");
-  return windows_make(c, p, n_samples, out, [&](abn_windows* h) {
+  return windows_make(c, p, n_samples, site_offset, out, [&](abn_windows* h) {
     return windows_build(h, p, site_offset, pos, gene_start, gene_end, flags, code, level);
   });
 }
@@ -371,6 +425,14 @@ extern "C" int abn_windows_merge_ms(const abn_windows* h, double* ms2) {
   if (!h || !ms2) return ABN_ERR_INVALID_ARG;
   ms2[0] = h->merge_ms[0];
   ms2[1] = h->merge_ms[1];
+  return ABN_OK;
+}
+
+extern "C" int abn_windows_common(const abn_windows* h, int64_t* before, int64_t* n_common, double* ms4) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (before) std::copy(h->before.begin(), h->before.end(), before);
+  if (n_common) *n_common = h->n_common;
+  if (ms4) std::copy(h->common_ms, h->common_ms + 4, ms4);
   return ABN_OK;
 }
 

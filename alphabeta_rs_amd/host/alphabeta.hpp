@@ -346,8 +346,11 @@ class Pedigree {  // src/pedigree.rs:44-45
   static std::pair<Pedigree, double> build(const std::string& nodelist, const std::string& edgelist,
                                            double posterior_max_filter, bool gpu_pairwise = false,
                                            bool device_parse = false,    // the methylome files through abn_sites_parse
-                                           bool device_sites = false);   // (with both of the above) the parsed sites stay
+                                           bool device_sites = false,    // (with both of the above) the parsed sites stay
                                                                          // on the device: abn_codes_create_parsed
+                                           bool align = false);          // (with all of the above) the samples compared on
+                                                                         // the sites they share: abn_codes_create_aligned;
+                                                                         // p0uu is then the fold over the aligned sites
   // ... for many (nodelist, edgelist) pairs at once (the windows of src/cli/metaprofile.rs:50-72): with gpu_pairwise ONE
   // abn_pairwise_divergence_windows_packed call per batch of entries with the same number of samples, on 2-bit codes
   // packed straight from the site records.  A batch ends at kBuildManyCodeBytes of PACKED codes per call (four sites per
@@ -462,6 +465,7 @@ struct Args {  // arguments::AlphaBeta, src/arguments.rs:93-114
   bool device_parse = false;  // --parse device: the methylome files through abn_sites_parse (not in the reference)
   bool device_sites = false;  // --sites device (with --parse device): the parsed sites stay on the device up to the code
                               // matrix and the rc_meth_lvl folds (abn_sites_parse_dev, abn_codes_create_parsed)
+  bool align = false;         // --align position (with --sites device): the samples are compared on the sites they share
 };
 
 struct RunResult {
@@ -527,7 +531,7 @@ namespace alphabeta {
 inline RunResult run(const Args& args) {
   std::printf("Building pedigree...\n");
   auto [pedigree, p0uu] = Pedigree::build(args.nodes, args.edges, args.posterior_max_filter, /*gpu_pairwise=*/true,
-                                          args.device_parse, args.device_sites);
+                                          args.device_parse, args.device_sites, args.align);
   return run_on_pedigree(std::move(pedigree), p0uu, args.iterations, args.output);
 }
 }  // namespace alphabeta

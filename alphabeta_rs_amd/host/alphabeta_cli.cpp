@@ -35,6 +35,9 @@ static void usage() {
       "      --sites <host|device>      where the parsed sites wait for the pedigree build: device packs the codes and folds\n"
       "                                 the methylation levels there (needs --parse device); the same output files\n"
       "                                 [default: host]\n"
+      "      --align <none|position>    position: compare the samples on the sites they share, by chromosome, start, end\n"
+      "                                 and strand (needs --sites device); D and p0uu then describe the shared sites\n"
+      "                                 [default: none]\n"
       "  -h, --help                     Print help\n"
       "  -V, --version                  Print version");
 }
@@ -94,6 +97,14 @@ int main(int argc, char** argv) {
       }
       args.device_sites = where == "device";
     }
+    else if (a == "--align") {
+      const std::string how = val();
+      if (how != "none" && how != "position") {
+        std::fprintf(stderr, "error: --align expects none or position\n");
+        return 2;
+      }
+      args.align = how == "position";
+    }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (a == "-V" || a == "--version") { std::puts("alphabeta 0.2.1 (MI355X ABneutral path)"); return 0; }
     else {
@@ -103,6 +114,10 @@ int main(int argc, char** argv) {
   }
   if (args.device_sites && !args.device_parse) {
     std::fprintf(stderr, "error: --sites device needs --parse device\n");
+    return 2;
+  }
+  if (args.align && !args.device_sites) {
+    std::fprintf(stderr, "error: --align position needs --sites device\n");
     return 2;
   }
   if (args.device_sites && !ped_file.empty()) {

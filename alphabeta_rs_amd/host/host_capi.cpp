@@ -9,6 +9,7 @@
 #include "../csrc/abn_route.hpp"
 #include "../csrc/abn_codes.hpp"
 #include "../csrc/abn_sites_merge.hpp"
+#include "../csrc/abn_sites_common.hpp"
 #include "alphabeta.hpp"
 
 extern "C" {
@@ -527,6 +528,29 @@ int abh_codes_build_serial(int n_chunks, const long long* chunk_n, const long lo
   const abn::MergeInserted ins{iline, pick.data(), nullptr, nullptr, nullptr, nullptr, istatus, ipm, iml, n_ins};
   abn::codes_build_serial(chunks.data(), n_chunks, ins, filter, abn::CodesOut{code, level}, row, row_stride_bytes, sum, kept);
   return 0;
+}
+// ---- the sites every sample shares, by position (csrc/abn_sites_common.hpp), for tests/test_sites_common_cpu.py
+// sites_common_serial of n samples (site_off [n + 1]; the key fields concatenated) -> keep [site_off[n]] and the return
+// value n_common; or -1 with refusal = {kind (1 split run, 2 not ascending, 3 a key outside its range, 4 not co-ordered),
+// sample, the site's index in it} and, when text (capacity cap) is given, the refusal's words.  -2: a null pointer
+long long abh_sites_common_serial(int n, const long long* site_off, const int* chromosome, const unsigned* start,
+                                  const unsigned* end, const unsigned char* strand, unsigned char* keep,
+                                  long long* refusal, char* text, long long cap) {
+  if (n <= 0 || !site_off || !refusal || (site_off[n] > 0 && (!chromosome || !start || !end || !strand || !keep))) return -2;
+  abn::CommonRefusal r{0, -1, -1};
+  const long long n_common = abn::sites_common_serial(abn::CommonSites{chromosome, start, end, strand}, n, site_off, keep, &r);
+  refusal[0] = r.kind;
+  refusal[1] = r.sample;
+  refusal[2] = r.site;
+  if (text && cap > 0) std::strncpy(text, abn::common_refusal_text(r).c_str(), (size_t)cap - 1), text[cap - 1] = 0;
+  return n_common;
+}
+// the comparator the searches share: 1 when key a = (start, end, strand) is below key b, and 1 in *equal when they are the same
+int abh_sites_common_key_less(unsigned a_start, unsigned a_end, unsigned a_strand, unsigned b_start, unsigned b_end,
+                              unsigned b_strand, int* equal) {
+  const abn::CommonKey a{a_start, a_end, a_strand}, b{b_start, b_end, b_strand};
+  if (equal) *equal = abn::common_key_equal(a, b) ? 1 : 0;
+  return abn::common_key_less(a, b) ? 1 : 0;
 }
 // parse_sites_resident of a text on the default device -> what abn_sites_fetch gives for its handle, in the arrays of
 // abh_parse_sites; warnings (capacity wcap) = what it printed.  Returns the number of sites, -1: they do not fit, -2: the

@@ -74,6 +74,14 @@ int main(int argc, char** argv) {
       }
       a.device_sites = where == "device";
     }
+    else if (f == "--align") {
+      const std::string how = val();
+      if (how != "none" && how != "position") {
+        std::fprintf(stderr, "error: --align expects none or position\n");
+        return 2;
+      }
+      a.align = how == "position";
+    }
     else if (f == "-h" || f == "--help") {
       std::puts("Usage: metaprofile_alphabeta -o <output-dir> [--name N] [-s step] [-w size] [-c cutoff] [-a]\n"
                 "       [--iterations 100] [--max-gene-length L] [--distribution FILE] [--seed S] [--device D]\n"
@@ -85,6 +93,9 @@ int main(int argc, char** argv) {
                 "       [--sites host|device] where the parsed sites wait for the gene choice: device keeps them there from the\n"
                 "                            text to the window matrix (needs --parse device --genes device); the same output\n"
                 "                            files [default: host]\n"
+                "       [--align none|position] position: place only the sites every sample shares, by chromosome, start, end\n"
+                "                            and strand, so that no window is ragged (needs --sites device); the side files\n"
+                "                            then describe the shared sites [default: none]\n"
                 "       [--stream-sweep]     pedigrees too large for the LDS: read a fit's rows once per Nelder-Mead iteration\n"
                 "                            instead of once per cost evaluation; the same output files");
       return 0;
@@ -112,6 +123,10 @@ int main(int argc, char** argv) {
   }
   if (a.device_sites && !(a.device_parse && a.device_genes)) {
     std::fprintf(stderr, "error: --sites device needs --parse device and --genes device\n");
+    return 2;
+  }
+  if (a.align && !a.device_sites) {
+    std::fprintf(stderr, "error: --align position needs --sites device\n");
     return 2;
   }
   if (a.device_sites && !in_memory) {

@@ -229,8 +229,14 @@ inline Inputs read_inputs(const std::string& nodelist, const std::string& edgeli
 // handle, the code matrix is packed and rc_meth_lvl folded there, and the D matrix comes from abn_codes_pairwise — no
 // site reaches the host.  Samples of different length, or fewer than two: the handles are fetched into Inputs and the D
 // matrix is dmatrix_on_host's, with its "Lengths do not match" lines.  dm: DMatrix::from's array.
+// align: the samples are compared on the sites they share, by (chromosome, start, end, strand) — abn_codes_create_aligned,
+// lifting the assumption of src/pedigree.rs:240.  The samples have the same length then, so the different-length fallback
+// is never taken: the D matrix comes from the aligned handle, and rc_meth_lvl, hence p0uu, from its folds — the folds over
+// the ALIGNED sites, which differ from the unaligned ones by design whenever a site was dropped.  One line per sample
+// says how many sites it had and how many were kept.
 inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
-                                   std::vector<double>& dm, const std::vector<std::string>* texts = nullptr);
+                                   std::vector<double>& dm, const std::vector<std::string>* texts = nullptr,
+                                   bool align = false);
 // abn_codes_kernel_ms of this thread's last read_inputs_resident (merge records, merge inserted, pack, fold)
 inline double* resident_kernel_ms() {
   static thread_local double ms[4] = {0.0, 0.0, 0.0, 0.0};
@@ -428,11 +434,13 @@ namespace detail {
 // Pedigree::build; texts: as read_inputs
 inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, const std::string& edgelist,
                                                   double posterior_max_filter, bool gpu_pairwise, bool device_parse,
-                                                  bool device_sites, const std::vector<std::string>* texts = nullptr) {
+                                                  bool device_sites, const std::vector<std::string>* texts = nullptr,
+                                                  bool align = false) {
+  if (align && !device_sites) throw Error(ABN_ERR_INVALID_ARG, "--align position needs --sites device");
   if (device_sites) {
     if (!device_parse || !gpu_pairwise) throw Error(ABN_ERR_INVALID_ARG, "--sites device needs --parse device");
     std::vector<double> dm;
-    const Inputs in = read_inputs_resident(nodelist, edgelist, posterior_max_filter, dm, texts);
+    const Inputs in = read_inputs_resident(nodelist, edgelist, posterior_max_filter, dm, texts, align);
     return {convert(in, dm), in.p0uu};
   }
   const Inputs in = read_inputs(nodelist, edgelist, posterior_max_filter, device_parse, texts);
@@ -459,8 +467,9 @@ inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, c
 
 inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, const std::string& edgelist,
                                                    double posterior_max_filter, bool gpu_pairwise,
-                                                   bool device_parse, bool device_sites) {
-  return detail::build_pedigree(nodelist, edgelist, posterior_max_filter, gpu_pairwise, device_parse, device_sites);
+                                                   bool device_parse, bool device_sites, bool align) {
+  return detail::build_pedigree(nodelist, edgelist, posterior_max_filter, gpu_pairwise, device_parse, device_sites, nullptr,
+                                align);
 }
 
 // Pedigree::build for many (nodelist, edgelist) pairs — the windows of src/cli/metaprofile.rs:50-72.  With gpu_pairwise

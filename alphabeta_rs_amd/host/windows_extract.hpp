@@ -577,16 +577,22 @@ class Handle {
     fetch();
   }
   // ... from the resident parse results (parse_sites_resident): merged, chosen and placed on the device, no site record
-  // coming back (abn_windows_create_parsed)
+  // coming back (abn_windows_create_parsed).  align: only the sites every sample shares, by (chromosome, start, end,
+  // strand), are placed (abn_windows_create_aligned): no window is ragged, and count, kept and the level sums — hence the
+  // side files and every window's p0uu — describe the ALIGNED sites, not each file's own.
   Handle(Device& dev, const abn_windows_params& p, const Genome& genome, const GeneRule& rule, double posterior_max_filter,
-         const std::vector<ResidentSites>& samples)
+         const std::vector<ResidentSites>& samples, bool align = false)
       : n_(samples.size()) {
     const GenesHandle genes(dev, genome);
     const abn_gene_rule r{rule.cutoff, rule.cutoff_gene_length ? 1 : 0};
     std::vector<abn_sites*> handles;
     for (const ResidentSites& s : samples) handles.push_back(s.get());
-    dev.check(abn_windows_create_parsed(dev.get(), &p, genes.get(), &r, posterior_max_filter, (int32_t)n_, handles.data(), &h_),
-              "abn_windows_create_parsed");
+    if (align)
+      dev.check(abn_windows_create_aligned(dev.get(), &p, genes.get(), &r, posterior_max_filter, (int32_t)n_, handles.data(), &h_),
+                "abn_windows_create_aligned");
+    else
+      dev.check(abn_windows_create_parsed(dev.get(), &p, genes.get(), &r, posterior_max_filter, (int32_t)n_, handles.data(), &h_),
+                "abn_windows_create_parsed");
     fetch();
   }
   Handle(Device& dev, const abn_windows_params& p, const std::vector<SampleSites>& samples) : n_(samples.size()) {
@@ -617,6 +623,8 @@ class Handle {
   std::vector<int64_t> count, kept;  // [n_samples x W]
   std::vector<double> level_sum, level_sum_kept;
   std::vector<int32_t> ragged;  // [W]
+  std::vector<int64_t> before;  // [n_samples]: every sample's sites as they came
+  int64_t n_common = -1;        // the sites every sample keeps; -1 without align
 
  private:
   void fetch() {  // what the handle reports, to the vectors above
@@ -630,6 +638,8 @@ class Handle {
     ragged.resize(W_);
     abn_windows_stats(h_, count.data(), level_sum.data(), level_sum_kept.data(), kept.data());
     abn_windows_layout(h_, nullptr, nullptr, ragged.data());
+    before.resize(n_);
+    abn_windows_common(h_, before.data(), &n_common, nullptr);
   }
   abn_windows* h_ = nullptr;
   size_t n_ = 0, W_ = 0;
@@ -646,7 +656,7 @@ inline std::vector<Site> parse_sites_device_reduced(const std::string& text) {
 }
 
 inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
-                                   std::vector<double>& dm, const std::vector<std::string>* texts) {
+                                   std::vector<double>& dm, const std::vector<std::string>* texts, bool align) {
   Inputs in = read_graph(nodelist, edgelist);
   std::vector<Node>& nodes = in.nodes;
   const size_t nn = nodes.size();
@@ -674,8 +684,19 @@ inline Inputs read_inputs_resident(const std::string& nodelist, const std::strin
   if (nn > 0) {
     std::vector<abn_sites*> handles;
     for (const auto& s : sites) handles.push_back(s.get());
-    dev.check(abn_codes_create_parsed(dev.get(), posterior_max_filter, (int32_t)nn, handles.data(), &codes.h),
-              "abn_codes_create_parsed");
+    if (align) {
+      dev.check(abn_codes_create_aligned(dev.get(), posterior_max_filter, (int32_t)nn, handles.data(), &codes.h),
+                "abn_codes_create_aligned");
+      std::vector<int64_t> before(nn);
+      int64_t n_common = 0;
+      abn_codes_common(codes.h, before.data(), &n_common, nullptr);
+      for (size_t i = 0; i < nn; ++i)
+        diag_printf("Aligned by position: %s: %lld sites, %lld kept\n", nodes[i].file.c_str(), (long long)before[i],
+                    (long long)n_common);
+    } else {
+      dev.check(abn_codes_create_parsed(dev.get(), posterior_max_filter, (int32_t)nn, handles.data(), &codes.h),
+                "abn_codes_create_parsed");
+    }
     resident_build_calls().fetch_add(1, std::memory_order_relaxed);
     std::vector<double> sum(nn);
     std::vector<int64_t> kept(nn);

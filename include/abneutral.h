@@ -515,6 +515,53 @@ int abn_codes_pairwise(abn_codes* h, uint64_t* diff, uint64_t* both, double* dva
  * records' kernel, the inserted lines' — the pack, the fold), each over all samples */
 int abn_codes_kernel_ms(const abn_codes* h, double* ms4);
 
+/* ------------------------------------------------------------------ methylomes aligned by position
+ * The reference pairs site k of one methylome with site k of another: src/pedigree.rs:240, "It is assumed that the same
+ * sites are included in the datasets".  The entries below lift that assumption: samples are compared on the sites they
+ * share.  A site's KEY is (chromosome, start, end, strand) as abn_sites_fetch reports them; the posterior and the status
+ * are no part of it, so a filtered site is still a site.  A sample is WELL ORDERED when each chromosome's sites form one
+ * contiguous run in file order (the runs in any order) and (start, end, strand) is strictly ascending inside a run.  The
+ * COMMON SET is the set of keys present in every sample; every sample keeps its common sites in its own file order; the
+ * samples are CO-ORDERED when the k-th common site of every sample has the same key.  One sample: every site is common.
+ * A sample without a site: no site is.
+ *
+ * abn_sites_common lifts src/pedigree.rs:240 for n_samples samples given as HOST arrays (site_offset [n_samples + 1] and
+ * per site chromosome, start, end, strand as abn_windows_create_sites takes them): keep [site_offset[n_samples]] = 1 for
+ * every sample's common sites, 0 elsewhere; *n_common = their number in each sample.  The step alone, on the device.
+ * ABN_ERR_INVALID_ARG: null pointers, n_samples <= 0 or > 65535, site_offset as abn_windows_create, and — with a text
+ * that names the sample, the lowest offending site of the whole input (its index inside the sample) and the kind — a
+ * sample that is not well ordered ("split run", "not ascending"), a chromosome outside 0..257 or a strand above 2, or
+ * samples that are not co-ordered ("not co-ordered"). */
+int abn_sites_common(abn_ctx* ctx, int32_t n_samples, const int64_t* site_offset, const int32_t* chromosome,
+                     const uint32_t* start, const uint32_t* end, const uint8_t* strand, uint8_t* keep /* uint8 [S] out */,
+                     int64_t* n_common /* int64 out */);
+/* abn_sites_common (the same lift of src/pedigree.rs:240) on DEVICE arrays; site_offset and n_common stay on the host.
+ * Returns after completion. */
+int abn_sites_common_dev(abn_ctx* ctx, int32_t n_samples, const int64_t* site_offset, const void* dev_chromosome,
+                         const void* dev_start, const void* dev_end, const void* dev_strand, void* dev_keep,
+                         int64_t* n_common);
+/* abn_windows_create_parsed without the assumption of src/pedigree.rs:240: the merge, then the common-site step, then the
+ * gene choice and the placement on the aligned arrays, so that every sample has the same sites in every window and no
+ * window is ragged.  Arguments and errors as abn_windows_create_parsed, and the refusals of abn_sites_common (no handle
+ * comes back).  The resident handles are neither consumed nor modified.  *out is an ordinary abn_windows; its stats
+ * describe the aligned sites. */
+int abn_windows_create_aligned(abn_ctx* ctx, const abn_windows_params* params, abn_genes* genes, const abn_gene_rule* rule,
+                               double posterior_max_filter, int32_t n_samples, abn_sites* const* samples,
+                               abn_windows** out);
+/* abn_codes_create_parsed without the assumption of src/pedigree.rs:240: the merge (keys included), the common-site step,
+ * then the pack and the fold over the aligned sites.  Arguments and errors as abn_codes_create_parsed, and the refusals of
+ * abn_sites_common.  *out is an ordinary abn_codes with same_len = 1 (abn_codes_pairwise works on it); abn_codes_stats
+ * reports count = n_common and the folds over the ALIGNED sites, so rc_meth_lvl (p0uu) differs from the unaligned
+ * handle's by design. */
+int abn_codes_create_aligned(abn_ctx* ctx, double posterior_max_filter, int32_t n_samples, abn_sites* const* samples,
+                             abn_codes** out);
+/* What the alignment that lifts src/pedigree.rs:240 did to a handle; any pointer may be NULL.  before [n_samples]: every
+ * sample's sites as they came; *n_common: the sites every sample keeps; ms [4]: the HIP-event times of the common-site
+ * kernels (runs and ends; match; scan and rank; gather).  A handle made any other way: before = the sample's own count,
+ * *n_common = -1, ms = zeros. */
+int abn_windows_common(const abn_windows* h, int64_t* before /* int64[n] */, int64_t* n_common, double* ms /* double[4] */);
+int abn_codes_common(const abn_codes* h, int64_t* before /* int64[n] */, int64_t* n_common, double* ms /* double[4] */);
+
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
  * src/cli/metaprofile.rs:50-72, where every window shares nodelist/edgelist), S starts and B bootstraps
