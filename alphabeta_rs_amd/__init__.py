@@ -68,6 +68,8 @@ EXPORTED_SYMBOLS = [
     "abn_codes_packed_device_ptr", "abn_codes_pairwise", "abn_codes_kernel_ms",
     "abn_sites_common", "abn_sites_common_dev", "abn_windows_create_aligned", "abn_codes_create_aligned",
     "abn_windows_common", "abn_codes_common",
+    "abn_sites_union", "abn_sites_union_dev", "abn_windows_create_union", "abn_codes_create_union",
+    "abn_windows_union", "abn_codes_union",
 ]
 
 
@@ -224,6 +226,12 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_codes_create_aligned.argtypes = L.abn_codes_create_parsed.argtypes
     L.abn_windows_common.argtypes = [vp, i64p, i64p, dp]
     L.abn_codes_common.argtypes = [vp, i64p, i64p, dp]
+    L.abn_sites_union.argtypes = [vp, C.c_int32, i64p, C.POINTER(C.c_int32), u32p, u32p, u8p, u32p, i64p]
+    L.abn_sites_union_dev.argtypes = [vp, C.c_int32, i64p, vp, vp, vp, vp, vp, i64p]
+    L.abn_windows_create_union.argtypes = L.abn_windows_create_parsed.argtypes
+    L.abn_codes_create_union.argtypes = L.abn_codes_create_parsed.argtypes
+    L.abn_windows_union.argtypes = [vp, i64p, i64p, dp]
+    L.abn_codes_union.argtypes = [vp, i64p, i64p, dp]
     i32p = C.POINTER(C.c_int32)
     L.abn_genes_create.argtypes = [vp, C.c_int32, i32p, i32p, i64p, u32p, u32p, u8p, C.POINTER(vp)]
     L.abn_genes_destroy.argtypes = [vp]
@@ -710,6 +718,20 @@ class Context:
                                              u[3].ctypes.data_as(u8p), keep.ctypes.data_as(u8p), C.byref(n_common)))
         return keep, n_common.value
 
+    def union_sites(self, site_offset, chromosome, start, end, strand):
+        """The union of the samples' sites, by key (chromosome, start, end, strand), on the device (abn_sites_union: the
+        per-pair comparison of src/pedigree.rs:240-254 for samples that hold different sites).  Arguments as common_sites.
+        Returns (dest uint32 (S,), n_union): every site's rank in the union order, n_union distinct keys.  AbnError when a
+        sample is not well ordered or its chromosomes come in another order than the union's."""
+        off, u = _site_arrays(site_offset, chromosome, start, end, strand)
+        dest = np.zeros(int(off[-1]), dtype=np.uint32)
+        n_union = C.c_int64(-1)
+        u8p = C.POINTER(C.c_uint8)
+        self._check(self._L.abn_sites_union(self._h, off.shape[0] - 1, off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            u[0].ctypes.data_as(C.POINTER(C.c_int32)), _u32p(u[1]), _u32p(u[2]),
+                                            u[3].ctypes.data_as(u8p), _u32p(dest), C.byref(n_union)))
+        return dest, n_union.value
+
     def choose_genes_dev(self, genes: "Genes", site_offset, chromosome_ptr: int, start_ptr: int, end_ptr: int,
                          strand_ptr: int, gene_start_ptr: int, gene_end_ptr: int, flags_ptr: int, *, cutoff,
                          cutoff_gene_length=False) -> np.ndarray:
@@ -877,6 +899,20 @@ class Plan:
         return {"starts": (KERNEL_NAMES.get(out[0], out[0]), out[1]), "boot": (KERNEL_NAMES.get(out[2], out[2]), out[3])}
 
 
+_ALIGN_CREATE = {"none": "abn_{}_create_parsed", "position": "abn_{}_create_aligned", "union": "abn_{}_create_union"}
+
+
+def _align_mode(align) -> str:
+    """from_parsed's align argument -> "none", "position" or "union" (False / None; True or "position"; "union")"""
+    if align is None or align is False or align == "none":
+        return "none"
+    if align is True or align == "position":
+        return "position"
+    if align == "union":
+        return "union"
+    raise ValueError(f"align expects False, True, 'position' or 'union', not {align!r}")
+
+
 def _site_arrays(site_offset, chromosome, start, end, strand):
     off = np.ascontiguousarray(site_offset, dtype=np.int64)
     S = int(off[-1]) if off.shape[0] else 0
@@ -1042,8 +1078,10 @@ class Windows:
                     cutoff_gene_length=False, step, size, absolute, counts, align=False):
         """The handle from resident parse results (Context.parse_sites_resident, one Sites per methylome, their deferred
         lines decided and inserted): merged in file order, the genes chosen and the windows placed on the device, no site
-        record coming back to the host (abn_windows_create_parsed).  The Sites are not consumed.  align: only the sites
-        every sample shares (Context.common_sites) are placed (abn_windows_create_aligned), so no window is ragged."""
+        record coming back to the host (abn_windows_create_parsed).  The Sites are not consumed.  align: True or
+        "position": only the sites every sample shares (Context.common_sites) are placed (abn_windows_create_aligned);
+        "union": every sample gets all the sites any sample holds, filtered placeholders where it lacks one
+        (Context.union_sites, abn_windows_create_union).  Either way no window is ragged."""
         self = cls.__new__(cls)
         self.ctx = ctx
         self._L = ctx._L
@@ -1053,7 +1091,7 @@ class Windows:
         rule = GeneRule(cutoff, 1 if cutoff_gene_length else 0)
         handles = (C.c_void_p * max(self.n_samples, 1))(*(s._h for s in sites_list))
         h = C.c_void_p()
-        create = self._L.abn_windows_create_aligned if align else self._L.abn_windows_create_parsed
+        create = getattr(self._L, _ALIGN_CREATE[_align_mode(align)].format("windows"))
         ctx._check(create(ctx._h, C.byref(p), genes._h, C.byref(rule), posterior_max_filter, self.n_samples, handles,
                           C.byref(h)))
         self._h = h
@@ -1075,6 +1113,14 @@ class Windows:
         before, n_common, ms = np.zeros(self.n_samples, dtype=np.int64), C.c_int64(-1), np.zeros(4)
         self.ctx._check(self._L.abn_windows_common(self._h, before.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_common), _dp(ms)))
         return before, n_common.value, ms
+
+    def union(self):
+        """(before int64 (n_samples,), n_union, ms (8,)): every sample's sites before the alignment, the sites each has
+        behind it, placeholders included (-1: not made with align="union") and the HIP-event ms of the union passes (runs
+        and ends, owner, scan, base, rank, dest, invert, gather; zeros otherwise)"""
+        before, n_union, ms = np.zeros(self.n_samples, dtype=np.int64), C.c_int64(-1), np.zeros(8)
+        self.ctx._check(self._L.abn_windows_union(self._h, before.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_union), _dp(ms)))
+        return before, n_union.value, ms
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1139,14 +1185,16 @@ class Codes:
         per methylome, their deferred lines decided and inserted): merged in file order, packed and folded on the device,
         no site record coming back to the host (abn_codes_create_parsed).  The Sites are not consumed.  align: only the
         sites every sample shares (Context.common_sites) are packed and folded (abn_codes_create_aligned): the samples have
-        the same length then, and stats() describes the aligned sites."""
+        the same length then, and stats() describes the aligned sites.  align="union": every sample gets all the sites any
+        sample holds, filtered placeholders where it lacks one (abn_codes_create_union): count is n_union, kept and the
+        level sums are the unaligned handle's, and a pair is compared on the sites both hold."""
         self = cls.__new__(cls)
         self.ctx = ctx
         self._L = ctx._L
         sites_list = list(sites_list)
         handles = (C.c_void_p * max(len(sites_list), 1))(*(s._h for s in sites_list))
         h = C.c_void_p()
-        create = self._L.abn_codes_create_aligned if align else self._L.abn_codes_create_parsed
+        create = getattr(self._L, _ALIGN_CREATE[_align_mode(align)].format("codes"))
         ctx._check(create(ctx._h, posterior_max_filter, len(sites_list), handles, C.byref(h)))
         self._h = h
         i = self.info()
@@ -1206,6 +1254,14 @@ class Codes:
         before, n_common, ms = np.zeros(self.n_samples, dtype=np.int64), C.c_int64(-1), np.zeros(4)
         self.ctx._check(self._L.abn_codes_common(self._h, before.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_common), _dp(ms)))
         return before, n_common.value, ms
+
+    def union(self):
+        """(before int64 (n_samples,), n_union, ms (8,)): every sample's sites before the alignment, the sites each has
+        behind it, placeholders included (-1: not made with align="union") and the HIP-event ms of the union passes (runs
+        and ends, owner, scan, base, rank, dest, invert, gather; zeros otherwise)"""
+        before, n_union, ms = np.zeros(self.n_samples, dtype=np.int64), C.c_int64(-1), np.zeros(8)
+        self.ctx._check(self._L.abn_codes_union(self._h, before.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_union), _dp(ms)))
+        return before, n_union.value, ms
 
     def kernel_ms(self) -> np.ndarray:
         """the HIP-event ms of from_parsed's kernels: merge of the records, merge of the inserted lines, pack, fold"""

@@ -1,7 +1,8 @@
 // abn_codes_*: the pedigree build's code matrix and rc_meth_lvl folds from resident parse results (src/pedigree.rs:138-178
 // behind from_methylome_file_line, and the status bytes DMatrix::from reads, :210-261).  Kernels and arithmetic:
 // abn_codes.hpp; the merge launches are abn_sites.hip's (the records are its handle's), the scan abn_pairwise.hip's, the
-// common-site step of abn_codes_create_aligned abn_sites_common.hip's.
+// common-site step of abn_codes_create_aligned abn_sites_common.hip's, the union step of abn_codes_create_union
+// abn_sites_union.hip's.
 #include "abn_host.hpp"
 #define ABN_CODES_KERNELS
 #include "abn_codes.hpp"
@@ -20,13 +21,16 @@ struct abn_codes {
   std::vector<int64_t> before;          // [n]: every sample's sites as they came (abn_codes_common)
   int64_t n_common = -1;                // abn_codes_create_aligned: the sites every sample keeps
   double common_ms[4] = {0.0, 0.0, 0.0, 0.0};
+  int64_t n_union = -1;                 // abn_codes_create_union: the sites every sample has, placeholders included
+  double union_ms[kUnionPasses] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   DevBuf<uint8_t> packed;               // [n x stride], device-resident between calls
 };
 
 // merge, pack, fold; the merged arrays (9 bytes per site) live only in here.  With `align` the merge is the full one, keys
 // included (and the reduced one behind it, for the merged bytes: merge_code has no kCodeCounted), and the sites every
-// sample shares (abn_sites_common.hpp) are gathered out of it into the arrays the pack and the fold read.
-static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, bool align) {
+// sample shares (abn_sites_common.hpp; kAlignPosition) or the union of the samples' sites with filtered placeholders
+// (abn_sites_union.hpp; kAlignUnion) are gathered out of it into the arrays the pack and the fold read.
+static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, int align) {
   abn_ctx* c = h->ctx;
   const int n = h->n;
   DevBuf<int32_t> mchrom;
@@ -34,6 +38,7 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, b
   DevBuf<uint8_t> mstrand, mcode;
   DevBuf<double> mlevel;
   CommonState st;
+  UnionState ust;
   std::vector<int64_t> merged_off((size_t)n + 1, 0);
   if (align) {
     for (int s = 0; s < n; ++s) merged_off[(size_t)s + 1] = merged_off[(size_t)s] + h->count[(size_t)s];
@@ -52,11 +57,14 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, b
                                      mcode.p + o, mlevel.p + o))
           return rc;
       }
-    if (int rc = sites_common_match(c, n, merged_off.data(), CommonSites{mchrom.p, mstart.p, mend.p, mstrand.p}, nullptr, st))
+    const CommonSites keys{mchrom.p, mstart.p, mend.p, mstrand.p};
+    if (int rc = align == kAlignUnion ? sites_union_rank(c, n, merged_off.data(), keys, nullptr, ust)
+                                      : sites_common_match(c, n, merged_off.data(), keys, nullptr, st))
       return rc;
-    h->n_common = st.n_common;
-    h->count.assign((size_t)n, st.n_common);  // from here on the handle is one of n samples of n_common sites
-    h->max_sites = st.n_common;
+    const int64_t each = align == kAlignUnion ? ust.n_union : st.n_common;
+    (align == kAlignUnion ? h->n_union : h->n_common) = each;
+    h->count.assign((size_t)n, each);  // from here on the handle is one of n samples of n_common (n_union) sites
+    h->max_sites = each;
     h->same_len = true;
   }
   std::vector<long long> site_off((size_t)n + 1, 0), code_off((size_t)n + 1, 0);
@@ -102,10 +110,10 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, b
     }
   }
   if (align) {  // (returns after completion; the events below still bracket the pack and the fold)
-    if (int rc = sites_common_gather(c, st, CommonGather{mcode.p, mlevel.p, nullptr, nullptr, nullptr, nullptr, dlevel.p,
-                                                         dcode.p, code_off[1]}))
-      return rc;
-    std::copy(st.ms, st.ms + 4, h->common_ms);
+    const CommonGather g{mcode.p, mlevel.p, nullptr, nullptr, nullptr, nullptr, dlevel.p, dcode.p, code_off[1]};
+    if (int rc = align == kAlignUnion ? sites_union_gather(c, ust, g) : sites_common_gather(c, st, g)) return rc;
+    if (align == kAlignUnion) std::copy(ust.ms, ust.ms + kUnionPasses, h->union_ms);
+    else std::copy(st.ms, st.ms + 4, h->common_ms);
   }
   HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
   const unsigned grid = (unsigned)(((long long)n * row_dwords + kCodesThreads - 1) / kCodesThreads);
@@ -132,7 +140,7 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, b
 }
 
 static int codes_create_parsed(abn_ctx* c, double posterior_max_filter, int32_t n_samples, abn_sites* const* samples,
-                               bool align, abn_codes** out) {
+                               int align, abn_codes** out) {
   if (!c) return ABN_ERR_INVALID_ARG;
   if (out) *out = nullptr;
   if (!out || !samples || n_samples <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
@@ -167,12 +175,17 @@ static int codes_create_parsed(abn_ctx* c, double posterior_max_filter, int32_t 
 
 extern "C" int abn_codes_create_parsed(abn_ctx* c, double posterior_max_filter, int32_t n_samples,
                                        abn_sites* const* samples, abn_codes** out) {
-  return codes_create_parsed(c, posterior_max_filter, n_samples, samples, false, out);
+  return codes_create_parsed(c, posterior_max_filter, n_samples, samples, kAlignNone, out);
 }
 
 extern "C" int abn_codes_create_aligned(abn_ctx* c, double posterior_max_filter, int32_t n_samples,
                                         abn_sites* const* samples, abn_codes** out) {
-  return codes_create_parsed(c, posterior_max_filter, n_samples, samples, true, out);
+  return codes_create_parsed(c, posterior_max_filter, n_samples, samples, kAlignPosition, out);
+}
+
+extern "C" int abn_codes_create_union(abn_ctx* c, double posterior_max_filter, int32_t n_samples,
+                                      abn_sites* const* samples, abn_codes** out) {
+  return codes_create_parsed(c, posterior_max_filter, n_samples, samples, kAlignUnion, out);
 }
 
 extern "C" int abn_codes_common(const abn_codes* h, int64_t* before, int64_t* n_common, double* ms4) {
@@ -180,6 +193,14 @@ extern "C" int abn_codes_common(const abn_codes* h, int64_t* before, int64_t* n_
   if (before) std::copy(h->before.begin(), h->before.end(), before);
   if (n_common) *n_common = h->n_common;
   if (ms4) std::copy(h->common_ms, h->common_ms + 4, ms4);
+  return ABN_OK;
+}
+
+extern "C" int abn_codes_union(const abn_codes* h, int64_t* before, int64_t* n_union, double* ms8) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (before) std::copy(h->before.begin(), h->before.end(), before);
+  if (n_union) *n_union = h->n_union;
+  if (ms8) std::copy(h->union_ms, h->union_ms + kUnionPasses, ms8);
   return ABN_OK;
 }
 

@@ -1,5 +1,5 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (abn_api.hip, abn_pairwise.hip,
-// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip): the context, its device-buffer pool, error reporting,
+// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip): the context, its device-buffer pool, error reporting,
 // the kernel_ms timer.  Not part of the C-ABI (include/abneutral.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 
 #include "../../include/abneutral.h"
 #include "abn_sites_common.hpp"
+#include "abn_sites_union.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // Device-buffer pool of a context.  The drop-in entry points (abn_ab_neutral_run, abn_boot_model_run, abn_cost_batch,
@@ -233,4 +234,33 @@ struct CommonState {
 };
 int sites_common_match(abn_ctx* c, int n, const int64_t* site_offset, const CommonSites& in, uint8_t* dkeep, CommonState& st);
 int sites_common_gather(abn_ctx* c, CommonState& st, const CommonGather& g);
+// ... and the launches abn_sites_union.hip shares with it: the runs and ends passes over S sites (tables and err filled by
+// the caller: 0x7f bytes, run_end 0), and the one-workgroup exclusive scan of data[0 .. n) with the sum at data[n]
+int sites_common_tables(abn_ctx* c, const CommonSites& in, const long long* dsite_off, int n, long long S,
+                        long long* run_begin, long long* run_end, long long* err);
+int sites_common_scan(abn_ctx* c, uint32_t* data, uint32_t n);
+// abn_sites_union.hip, for abn_windows_create_union and abn_codes_create_union: the union step (abn_sites_union.hpp) on
+// DEVICE key arrays, in two halves as the common-site step.  sites_union_rank runs the order checks and every pass up to
+// dest, waits in between for the refusals and n_union, and leaves n_union in the state (ddest [site_offset[n]], or null:
+// the state's own); the caller sizes its arrays of n x n_union sites and sites_union_gather fills them (any output of g
+// may be null).  sites_union_rank refuses with ABN_ERR_INVALID_ARG and the text of union_refusal_text.  Both return after
+// completion.
+struct UnionState {
+  int n = 0;
+  long long n_union = 0;
+  std::vector<long long> site_off;
+  CommonSites in{};
+  uint32_t* dest = nullptr;
+  DevBuf<long long> dsite_off, run_begin, run_end, err;
+  DevBuf<uint32_t> dest_own, owner, P, r, block, count, base, inv, own_at;
+  DevBuf<int> order;
+  hipEvent_t ev[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double ms[kUnionPasses] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // runs and ends; owner; scan; base; rank; dest; invert; gather
+  UnionState() = default;
+  UnionState(const UnionState&) = delete;
+  UnionState& operator=(const UnionState&) = delete;
+  ~UnionState();
+};
+int sites_union_rank(abn_ctx* c, int n, const int64_t* site_offset, const CommonSites& in, uint32_t* ddest, UnionState& st);
+int sites_union_gather(abn_ctx* c, UnionState& st, const CommonGather& g);
 }  // namespace abn

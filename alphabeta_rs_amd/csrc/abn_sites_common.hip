@@ -20,6 +20,24 @@ static int common_refuse(abn_ctx* c, const long long* err, int first, int last, 
   return set_err(c, ABN_ERR_INVALID_ARG, "the samples cannot be aligned by position: " + common_refusal_text(r));
 }
 
+int abn::sites_common_tables(abn_ctx* c, const CommonSites& in, const long long* dsite_off, int n, long long S,
+                             long long* run_begin, long long* run_end, long long* err) {
+  if (S <= 0) return ABN_OK;
+  const dim3 grid((unsigned)((S + kCommonThreads - 1) / kCommonThreads)), threads(kCommonThreads);
+  hipLaunchKernelGGL(abn_common_runs_kernel, grid, threads, 0, c->stream, in, dsite_off, n, run_begin, err);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(abn_common_ends_kernel, grid, threads, 0, c->stream, in, dsite_off, n, (const long long*)run_begin,
+                     run_end, err);
+  HIPCHK(c, hipGetLastError());
+  return ABN_OK;
+}
+
+int abn::sites_common_scan(abn_ctx* c, uint32_t* data, uint32_t n) {
+  hipLaunchKernelGGL(abn_common_scan_kernel, dim3(1), dim3(kCommonThreads), 0, c->stream, data, n);
+  HIPCHK(c, hipGetLastError());
+  return ABN_OK;
+}
+
 int abn::sites_common_match(abn_ctx* c, int n, const int64_t* site_offset, const CommonSites& in, uint8_t* dkeep,
                             CommonState& st) {
   st.n = n;
@@ -57,15 +75,7 @@ int abn::sites_common_match(abn_ctx* c, int n, const int64_t* site_offset, const
   HIPCHK(c, hipMemsetAsync(st.block.p, 0, st.block.bytes(), c->stream));  // (no probe site: the total is this 0)
   const dim3 threads(kCommonThreads);
   HIPCHK(c, hipEventRecord(st.ev[0], c->stream));
-  if (S > 0) {
-    const dim3 grid((unsigned)((S + kCommonThreads - 1) / kCommonThreads));
-    hipLaunchKernelGGL(abn_common_runs_kernel, grid, threads, 0, c->stream, in, (const long long*)st.dsite_off.p, n,
-                       st.run_begin.p, st.err.p);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(abn_common_ends_kernel, grid, threads, 0, c->stream, in, (const long long*)st.dsite_off.p, n,
-                       (const long long*)st.run_begin.p, st.run_end.p, st.err.p);
-    HIPCHK(c, hipGetLastError());
-  }
+  if (int rc = sites_common_tables(c, in, st.dsite_off.p, n, S, st.run_begin.p, st.run_end.p, st.err.p)) return rc;
   HIPCHK(c, hipEventRecord(st.ev[1], c->stream));
   uint8_t* probe_keep = dkeep + st.site_off[(size_t)st.probe];
   if (Lp > 0) {
@@ -76,8 +86,7 @@ int abn::sites_common_match(abn_ctx* c, int n, const int64_t* site_offset, const
   }
   HIPCHK(c, hipEventRecord(st.ev[2], c->stream));
   if (Lp > 0) {
-    hipLaunchKernelGGL(abn_common_scan_kernel, dim3(1), threads, 0, c->stream, st.block.p, (uint32_t)blocks);
-    HIPCHK(c, hipGetLastError());
+    if (int rc = sites_common_scan(c, st.block.p, (uint32_t)blocks)) return rc;
     hipLaunchKernelGGL(abn_common_rank_kernel, dim3(blocks, (unsigned)n), threads, 0, c->stream,
                        (const uint8_t*)probe_keep, st.Lp, (const uint32_t*)st.block.p, (const uint32_t*)st.match.p, st.src.p);
     HIPCHK(c, hipGetLastError());

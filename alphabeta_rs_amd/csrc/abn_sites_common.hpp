@@ -313,6 +313,24 @@ inline long long sites_common_serial(const CommonSites& a, int n, const long lon
   return refusal->kind ? -1 : n_common;
 }
 
+#if defined(__HIPCC__) && (defined(ABN_SITES_COMMON_KERNELS) || defined(ABN_SITES_UNION_KERNELS))
+// The exclusive rank of `flag` among the workgroup's lanes, and their number: ballots inside a wavefront, the four
+// wavefronts' counts through LDS.  Every lane of the workgroup calls it.  (Shared with abn_sites_union.hpp's kernels.)
+__device__ inline uint32_t common_block_rank(bool flag, uint32_t* s_wave, uint32_t& total) {
+  const unsigned long long mask = __ballot(flag);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) s_wave[wave] = (uint32_t)__popcll(mask);
+  __syncthreads();
+  uint32_t before = 0;
+  total = 0;
+  for (int w = 0; w < kCommonThreads / 64; ++w) {
+    if (w < wave) before += s_wave[w];
+    total += s_wave[w];
+  }
+  return before + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+}
+#endif
+
 #if defined(__HIPCC__) && defined(ABN_SITES_COMMON_KERNELS)  // (abn_sites_common.hip defines it)
 // ------------------------------------------------------------------------------------------------ kernels
 // grid: ceil(S / kCommonThreads), S = site_off[n] sites
@@ -328,22 +346,6 @@ abn_common_ends_kernel(CommonSites a, const long long* __restrict__ site_off, in
                        long long* __restrict__ run_end, long long* __restrict__ err) {
   const long long i = (long long)blockIdx.x * kCommonThreads + threadIdx.x;
   if (i < site_off[n]) common_ends_lane(a, site_off, common_sample_of(site_off, n, i), i, run_begin, run_end, err);
-}
-
-// The exclusive rank of `flag` among the workgroup's lanes, and their number: ballots inside a wavefront, the four
-// wavefronts' counts through LDS.  Every lane of the workgroup calls it.
-__device__ inline uint32_t common_block_rank(bool flag, uint32_t* s_wave, uint32_t& total) {
-  const unsigned long long mask = __ballot(flag);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_wave[wave] = (uint32_t)__popcll(mask);
-  __syncthreads();
-  uint32_t before = 0;
-  total = 0;
-  for (int w = 0; w < kCommonThreads / 64; ++w) {
-    if (w < wave) before += s_wave[w];
-    total += s_wave[w];
-  }
-  return before + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
 }
 
 // grid: ceil(Lp / kCommonThreads); keep: the probe's flags, at its first site

@@ -1,7 +1,8 @@
 // abn_windows_*: the window-placement handle.  Kernels: abn_windows.hpp; the scan of the placed windows
 // (abn_windows_pairwise) is abn_pairwise.hip's, the gene choice of abn_windows_create_sites abn_genes.hip's, the merge of
 // resident parse results in front of abn_windows_create_parsed abn_sites.hip's, the common-site step between that merge and
-// the gene choice of abn_windows_create_aligned abn_sites_common.hip's.
+// the gene choice of abn_windows_create_aligned abn_sites_common.hip's, the union step in the same place of
+// abn_windows_create_union abn_sites_union.hip's.
 #include "abn_host.hpp"
 #include "abn_windows.hpp"
 
@@ -22,6 +23,8 @@ struct abn_windows {
   std::vector<int64_t> before;      // [n]: every sample's sites as they came (abn_windows_common)
   int64_t n_common = -1;            // abn_windows_create_aligned: the sites every sample keeps
   double common_ms[4] = {0.0, 0.0, 0.0, 0.0};
+  int64_t n_union = -1;             // abn_windows_create_union: the sites every sample has, placeholders included
+  double union_ms[kUnionPasses] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   DevBuf<uint8_t> packed;  // [n x stride], device-resident between calls
 };
 
@@ -209,9 +212,10 @@ static int windows_build_sites(abn_windows* h, const abn_windows_params* p, abn_
 
 // ... from RESIDENT parse results (abn_sites_parse_dev, abn_sites_insert): every sample's records and inserted lines
 // merged in file order straight into the arrays the gene choice and the placement read (abn_sites_merge.hpp); with
-// `align`, the sites every sample shares (abn_sites_common.hpp) gathered out of them first
+// `align`, the sites every sample shares (abn_sites_common.hpp; kAlignPosition) or the union of the samples' sites with
+// filtered placeholders (abn_sites_union.hpp; kAlignUnion) gathered out of them first
 static int windows_build_parsed(abn_windows* h, const abn_windows_params* p, abn_genes* genes, const abn_gene_rule* rule,
-                                double filter, const int64_t* site_offset, abn_sites* const* samples, bool align) {
+                                double filter, const int64_t* site_offset, abn_sites* const* samples, int align) {
   abn_ctx* c = h->ctx;
   const int n = h->n;
   const size_t S = (size_t)site_offset[n];
@@ -250,7 +254,8 @@ static int windows_build_parsed(abn_windows* h, const abn_windows_params* p, abn
     HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
   }
   // what the gene choice and the placement read: the merged arrays, or their aligned copies (n_common sites per sample;
-  // the gene arrays and the flags, written behind the step, are the merged arrays' own: no longer than those)
+  // the gene arrays and the flags, written behind the step, are the merged arrays' own: no longer than those; n_union
+  // sites per sample: the gene arrays and the flags are allocated again)
   const int64_t* offset = site_offset;
   const int32_t* chrom = dchrom.p;
   const uint32_t *start = dstart.p, *end = dend.p;
@@ -263,21 +268,34 @@ static int windows_build_parsed(abn_windows* h, const abn_windows_params* p, abn
   std::vector<int64_t> aligned_offset((size_t)n + 1, 0);
   if (align) {  // (no site at all: n_common = 0 through the same path)
     CommonState st;
-    if (int rc = sites_common_match(c, n, site_offset, CommonSites{dchrom.p, dstart.p, dend.p, dstrand.p}, nullptr, st))
+    UnionState ust;
+    const CommonSites keys{dchrom.p, dstart.p, dend.p, dstrand.p};
+    if (int rc = align == kAlignUnion ? sites_union_rank(c, n, site_offset, keys, nullptr, ust)
+                                      : sites_common_match(c, n, site_offset, keys, nullptr, st))
       return rc;
-    const size_t A = (size_t)n * (size_t)st.n_common;
+    const int64_t each = align == kAlignUnion ? ust.n_union : st.n_common;
+    const size_t A = (size_t)n * (size_t)each;
     HIPCHK(c, achrom.alloc(A));
     HIPCHK(c, astart.alloc(A));
     HIPCHK(c, aend.alloc(A));
     HIPCHK(c, astrand.alloc(A));
     HIPCHK(c, acode.alloc(std::max<size_t>(A, 1)));
     HIPCHK(c, alevel.alloc(std::max<size_t>(A, 1)));
-    if (int rc = sites_common_gather(c, st, CommonGather{dcode.p, dlevel.p, achrom.p, astart.p, aend.p, astrand.p, alevel.p,
-                                                         acode.p, st.n_common}))
-      return rc;
-    h->n_common = st.n_common;
-    std::copy(st.ms, st.ms + 4, h->common_ms);
-    for (int s = 0; s <= n; ++s) aligned_offset[(size_t)s] = (int64_t)s * st.n_common;
+    const CommonGather g{dcode.p, dlevel.p, achrom.p, astart.p, aend.p, astrand.p, alevel.p, acode.p, each};
+    if (int rc = align == kAlignUnion ? sites_union_gather(c, ust, g) : sites_common_gather(c, st, g)) return rc;
+    if (align == kAlignUnion) {
+      h->n_union = each;
+      std::copy(ust.ms, ust.ms + kUnionPasses, h->union_ms);
+      if (A > S) {  // (the gather is complete: the merged arrays' gene arrays and flags have no reader)
+        HIPCHK(c, dgs.alloc(A));
+        HIPCHK(c, dge.alloc(A));
+        HIPCHK(c, dflags.alloc(A));
+      }
+    } else {
+      h->n_common = each;
+      std::copy(st.ms, st.ms + 4, h->common_ms);
+    }
+    for (int s = 0; s <= n; ++s) aligned_offset[(size_t)s] = (int64_t)s * each;
     offset = aligned_offset.data();
     chrom = achrom.p, start = astart.p, end = aend.p, strand = astrand.p, code = acode.p, level = alevel.p;
   }
@@ -352,7 +370,7 @@ extern "C" int abn_windows_create_sites(abn_ctx* c, const abn_windows_params* p,
 }
 
 static int windows_create_parsed(abn_ctx* c, const abn_windows_params* p, abn_genes* genes, const abn_gene_rule* rule,
-                                 double posterior_max_filter, int32_t n_samples, abn_sites* const* samples, bool align,
+                                 double posterior_max_filter, int32_t n_samples, abn_sites* const* samples, int align,
                                  abn_windows** out) {
   if (!c) return ABN_ERR_INVALID_ARG;
   if (out) *out = nullptr;
@@ -384,13 +402,19 @@ static int windows_create_parsed(abn_ctx* c, const abn_windows_params* p, abn_ge
 extern "C" int abn_windows_create_parsed(abn_ctx* c, const abn_windows_params* p, abn_genes* genes,
                                          const abn_gene_rule* rule, double posterior_max_filter, int32_t n_samples,
                                          abn_sites* const* samples, abn_windows** out) {
-  return windows_create_parsed(c, p, genes, rule, posterior_max_filter, n_samples, samples, false, out);
+  return windows_create_parsed(c, p, genes, rule, posterior_max_filter, n_samples, samples, kAlignNone, out);
 }
 
 extern "C" int abn_windows_create_aligned(abn_ctx* c, const abn_windows_params* p, abn_genes* genes,
                                           const abn_gene_rule* rule, double posterior_max_filter, int32_t n_samples,
                                           abn_sites* const* samples, abn_windows** out) {
-  return windows_create_parsed(c, p, genes, rule, posterior_max_filter, n_samples, samples, true, out);
+  return windows_create_parsed(c, p, genes, rule, posterior_max_filter, n_samples, samples, kAlignPosition, out);
+}
+
+extern "C" int abn_windows_create_union(abn_ctx* c, const abn_windows_params* p, abn_genes* genes,
+                                        const abn_gene_rule* rule, double posterior_max_filter, int32_t n_samples,
+                                        abn_sites* const* samples, abn_windows** out) {
+  return windows_create_parsed(c, p, genes, rule, posterior_max_filter, n_samples, samples, kAlignUnion, out);
 }
 
 extern "C" int abn_windows_create(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, const int64_t* site_offset,
@@ -433,6 +457,14 @@ extern "C" int abn_windows_common(const abn_windows* h, int64_t* before, int64_t
   if (before) std::copy(h->before.begin(), h->before.end(), before);
   if (n_common) *n_common = h->n_common;
   if (ms4) std::copy(h->common_ms, h->common_ms + 4, ms4);
+  return ABN_OK;
+}
+
+extern "C" int abn_windows_union(const abn_windows* h, int64_t* before, int64_t* n_union, double* ms8) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (before) std::copy(h->before.begin(), h->before.end(), before);
+  if (n_union) *n_union = h->n_union;
+  if (ms8) std::copy(h->union_ms, h->union_ms + kUnionPasses, ms8);
   return ABN_OK;
 }
 

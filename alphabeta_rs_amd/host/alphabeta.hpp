@@ -46,6 +46,21 @@ struct Error : std::runtime_error {
   Error(int s, const std::string& m) : std::runtime_error(m), status(s) {}
 };
 
+// --align: how samples that do not hold the same sites are compared (not in the reference, which assumes they do:
+// src/pedigree.rs:240).  Position: on the sites every sample shares; Union: pair by pair on the sites both hold, every
+// sample padded to the union of all sites with filtered placeholders (src/pedigree.rs:249-254 skips those per pair).
+enum class Align { None, Position, Union };
+inline const char* align_name(Align a) { return a == Align::Union ? "union" : (a == Align::Position ? "position" : "none"); }
+// the value of --align, or false
+inline bool parse_align(const std::string& how, Align& out) {
+  if (how == "none") out = Align::None;
+  else if (how == "position") out = Align::Position;
+  else if (how == "union") out = Align::Union;
+  else return false;
+  return true;
+}
+constexpr const char* kAlignExpects = "--align expects none or position, or union";
+
 // Rust's `{}` for f64: shortest digits that round-trip, never scientific notation.
 inline std::string fmt_f64(double v) {
   if (std::isnan(v)) return "NaN";
@@ -348,9 +363,11 @@ class Pedigree {  // src/pedigree.rs:44-45
                                            bool device_parse = false,    // the methylome files through abn_sites_parse
                                            bool device_sites = false,    // (with both of the above) the parsed sites stay
                                                                          // on the device: abn_codes_create_parsed
-                                           bool align = false);          // (with all of the above) the samples compared on
-                                                                         // the sites they share: abn_codes_create_aligned;
-                                                                         // p0uu is then the fold over the aligned sites
+                                           Align align = Align::None);   // (with all of the above) Position: the samples
+                                                                         // compared on the sites they share
+                                                                         // (abn_codes_create_aligned), p0uu the fold over
+                                                                         // those; Union: pair by pair on the sites both
+                                                                         // hold (abn_codes_create_union), p0uu unchanged
   // ... for many (nodelist, edgelist) pairs at once (the windows of src/cli/metaprofile.rs:50-72): with gpu_pairwise ONE
   // abn_pairwise_divergence_windows_packed call per batch of entries with the same number of samples, on 2-bit codes
   // packed straight from the site records.  A batch ends at kBuildManyCodeBytes of PACKED codes per call (four sites per
@@ -465,7 +482,8 @@ struct Args {  // arguments::AlphaBeta, src/arguments.rs:93-114
   bool device_parse = false;  // --parse device: the methylome files through abn_sites_parse (not in the reference)
   bool device_sites = false;  // --sites device (with --parse device): the parsed sites stay on the device up to the code
                               // matrix and the rc_meth_lvl folds (abn_sites_parse_dev, abn_codes_create_parsed)
-  bool align = false;         // --align position (with --sites device): the samples are compared on the sites they share
+  Align align = Align::None;  // --align position | union (with --sites device): the samples are compared on the sites they
+                              // all share | pair by pair on the sites both hold
 };
 
 struct RunResult {

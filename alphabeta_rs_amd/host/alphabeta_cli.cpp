@@ -35,8 +35,11 @@ static void usage() {
       "      --sites <host|device>      where the parsed sites wait for the pedigree build: device packs the codes and folds\n"
       "                                 the methylation levels there (needs --parse device); the same output files\n"
       "                                 [default: host]\n"
-      "      --align <none|position>    position: compare the samples on the sites they share, by chromosome, start, end\n"
-      "                                 and strand (needs --sites device); D and p0uu then describe the shared sites\n"
+      "      --align <none|position|union>\n"
+      "                                 position: compare the samples on the sites they all share, by chromosome, start,\n"
+      "                                 end and strand; D and p0uu then describe the shared sites.  union: compare every\n"
+      "                                 pair on the sites both samples hold; p0uu stays each file's own.  Both need\n"
+      "                                 --sites device\n"
       "                                 [default: none]\n"
       "  -h, --help                     Print help\n"
       "  -V, --version                  Print version");
@@ -99,11 +102,10 @@ int main(int argc, char** argv) {
     }
     else if (a == "--align") {
       const std::string how = val();
-      if (how != "none" && how != "position") {
-        std::fprintf(stderr, "error: --align expects none or position\n");
+      if (!alphabeta::parse_align(how, args.align)) {
+        std::fprintf(stderr, "error: %s\n", alphabeta::kAlignExpects);
         return 2;
       }
-      args.align = how == "position";
     }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (a == "-V" || a == "--version") { std::puts("alphabeta 0.2.1 (MI355X ABneutral path)"); return 0; }
@@ -116,8 +118,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "error: --sites device needs --parse device\n");
     return 2;
   }
-  if (args.align && !args.device_sites) {
-    std::fprintf(stderr, "error: --align position needs --sites device\n");
+  if (args.align != alphabeta::Align::None && !args.device_sites) {
+    std::fprintf(stderr, "error: --align %s needs --sites device\n", alphabeta::align_name(args.align));
     return 2;
   }
   if (args.device_sites && !ped_file.empty()) {

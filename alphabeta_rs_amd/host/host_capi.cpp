@@ -10,6 +10,7 @@
 #include "../csrc/abn_codes.hpp"
 #include "../csrc/abn_sites_merge.hpp"
 #include "../csrc/abn_sites_common.hpp"
+#include "../csrc/abn_sites_union.hpp"
 #include "alphabeta.hpp"
 
 extern "C" {
@@ -544,6 +545,36 @@ long long abh_sites_common_serial(int n, const long long* site_off, const int* c
   refusal[2] = r.site;
   if (text && cap > 0) std::strncpy(text, abn::common_refusal_text(r).c_str(), (size_t)cap - 1), text[cap - 1] = 0;
   return n_common;
+}
+// ---- the union of the samples' sites (csrc/abn_sites_union.hpp), for tests/test_sites_union_cpu.py
+// sites_union_serial of n samples (arguments as abh_sites_common_serial) -> dest [site_off[n]] (every site's union rank)
+// and the return value n_union; or -1 with refusal = {kind (1 split run, 2 not ascending, 3 a key outside its range, 5 run
+// order), sample, the site's index in it} and, when text (capacity cap) is given, the refusal's words.  With gathered != 0
+// the gather runs too, into arrays of n x gathered sites (-4 unless gathered = n_union; code_in, level_in [site_off[n]]
+// are the sites' codes and levels; any output may be null).  -2: a null pointer; -3: 2^32 sites or more
+long long abh_sites_union_serial(int n, const long long* site_off, const int* chromosome, const unsigned* start,
+                                 const unsigned* end, const unsigned char* strand, unsigned* dest, long long* refusal,
+                                 char* text, long long cap, long long gathered, const unsigned char* code_in,
+                                 const double* level_in, int* out_chromosome, unsigned* out_start, unsigned* out_end,
+                                 unsigned char* out_strand, unsigned char* out_code, double* out_level) {
+  if (n <= 0 || !site_off || !refusal || (site_off[n] > 0 && (!chromosome || !start || !end || !strand || !dest))) return -2;
+  if (site_off[n] > 0xffffffffLL) return -3;
+  abn::CommonRefusal r{0, -1, -1};
+  bool fits = true;
+  const long long n_union = abn::sites_union_serial(
+      abn::CommonSites{chromosome, start, end, strand}, n, site_off, dest, &r, [&](long long nu) {
+        if (gathered == 0) return abn::CommonGather{};
+        if (gathered != nu) {
+          fits = false;
+          return abn::CommonGather{};
+        }
+        return abn::CommonGather{code_in, level_in, out_chromosome, out_start, out_end, out_strand, out_level, out_code, nu};
+      });
+  refusal[0] = r.kind;
+  refusal[1] = r.sample;
+  refusal[2] = r.site;
+  if (text && cap > 0) std::strncpy(text, abn::union_refusal_text(r).c_str(), (size_t)cap - 1), text[cap - 1] = 0;
+  return fits ? n_union : -4;
 }
 // the comparator the searches share: 1 when key a = (start, end, strand) is below key b, and 1 in *equal when they are the same
 int abh_sites_common_key_less(unsigned a_start, unsigned a_end, unsigned a_strand, unsigned b_start, unsigned b_end,

@@ -42,8 +42,11 @@ struct WindowArgs {  // the fields of arguments::Windows (src/arguments.rs:6-62)
   bool device_genes = false;      // --genes device: every site's gene through abn_windows_create_sites (abn_genes_*)
   bool device_sites = false;      // --sites device (with both of the above): the parsed records stay on the device up to
                                   // the window matrix (abn_sites_parse_dev, abn_windows_create_parsed)
-  bool align = false;             // --align position (with --sites device): only the sites every sample shares are placed
-                                  // (abn_windows_create_aligned): no ragged window; the side files describe those sites
+  Align align = Align::None;      // --align position (with --sites device): only the sites every sample shares are placed
+                                  // (abn_windows_create_aligned): no ragged window; the side files describe those sites.
+                                  // --align union: every sample gets all the sites any sample holds, filtered
+                                  // placeholders where it lacks one (abn_windows_create_union): no ragged window either;
+                                  // the side files count union sites
 };
 
 struct WindowResult {
@@ -303,7 +306,8 @@ inline Extraction extract_in_memory(const WindowArgs& args) {
   ex.params = windows::window_params(args.cutoff, step, args.window_size, args.absolute, ex.max_gene_length);
   if (args.device_sites && !(args.device_parse && args.device_genes))
     throw Error(ABN_ERR_INVALID_ARG, "--sites device needs --parse device and --genes device");
-  if (args.align && !args.device_sites) throw Error(ABN_ERR_INVALID_ARG, "--align position needs --sites device");
+  if (args.align != Align::None && !args.device_sites)
+    throw Error(ABN_ERR_INVALID_ARG, std::string("--align ") + align_name(args.align) + " needs --sites device");
   if (args.device_sites) {
     // every text goes up, its records stay there; it is dropped as soon as its deferred lines are decided
     const windows::GeneRule rule{args.cutoff, args.cutoff_gene_length};
@@ -313,10 +317,14 @@ inline Extraction extract_in_memory(const WindowArgs& args) {
                                                     detail::read_file((fs::path(args.methylome) / name).string(), "methylome")));
     ex.handle = std::make_unique<windows::Handle>(default_device(), ex.params, genome, rule, args.posterior_max_filter, sites,
                                                   args.align);
-    if (args.align)
+    if (args.align == Align::Position)
       for (size_t s = 0; s < ex.names.size(); ++s)
         std::printf("Aligned by position: %s: %lld sites, %lld kept\n", ex.names[s].c_str(),
                     (long long)ex.handle->before[s], (long long)ex.handle->n_common);
+    if (args.align == Align::Union)
+      for (size_t s = 0; s < ex.names.size(); ++s)
+        std::printf("Aligned by union: %s: %lld sites, %lld in the union\n", ex.names[s].c_str(),
+                    (long long)ex.handle->before[s], (long long)ex.handle->n_union);
   } else {
     std::vector<std::string> texts;
     for (const auto& name : ex.names) texts.push_back(detail::read_file((fs::path(args.methylome) / name).string(), "methylome"));
@@ -370,7 +378,7 @@ inline Extraction extract_in_memory(const WindowArgs& args) {
 // :50-53, which names ceil(max / step) windows per region where Windows::new creates floor(max / step): the window the
 // enumeration names beyond those fails as its missing sample file fails there.  A RAGGED window (the samples' site counts
 // differ) fails too; the reference goes on with D = 0 for its pairs (DESIGN.md §4 "Window placement").  With args.align
-// the handle holds only the sites every sample shares, so no window is ragged.
+// the handle holds only the sites every sample shares, or every sample the union of all sites, so no window is ragged.
 inline Output alphabeta_multiple_in_memory(const WindowArgs& args, const Extraction& ex) {
   namespace fs = std::filesystem;
   const windows::Handle& h = *ex.handle;

@@ -76,11 +76,10 @@ int main(int argc, char** argv) {
     }
     else if (f == "--align") {
       const std::string how = val();
-      if (how != "none" && how != "position") {
-        std::fprintf(stderr, "error: --align expects none or position\n");
+      if (!alphabeta::parse_align(how, a.align)) {
+        std::fprintf(stderr, "error: %s\n", alphabeta::kAlignExpects);
         return 2;
       }
-      a.align = how == "position";
     }
     else if (f == "-h" || f == "--help") {
       std::puts("Usage: metaprofile_alphabeta -o <output-dir> [--name N] [-s step] [-w size] [-c cutoff] [-a]\n"
@@ -93,9 +92,11 @@ int main(int argc, char** argv) {
                 "       [--sites host|device] where the parsed sites wait for the gene choice: device keeps them there from the\n"
                 "                            text to the window matrix (needs --parse device --genes device); the same output\n"
                 "                            files [default: host]\n"
-                "       [--align none|position] position: place only the sites every sample shares, by chromosome, start, end\n"
-                "                            and strand, so that no window is ragged (needs --sites device); the side files\n"
-                "                            then describe the shared sites [default: none]\n"
+                "       [--align none|position|union] position: place only the sites every sample shares, by chromosome,\n"
+                "                            start, end and strand; the side files then describe the shared sites.  union: give\n"
+                "                            every sample all the sites any sample holds, filtered placeholders where it lacks\n"
+                "                            one; the side files then count union sites.  Either way no window is ragged (needs\n"
+                "                            --sites device) [default: none]\n"
                 "       [--stream-sweep]     pedigrees too large for the LDS: read a fit's rows once per Nelder-Mead iteration\n"
                 "                            instead of once per cost evaluation; the same output files");
       return 0;
@@ -125,8 +126,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "error: --sites device needs --parse device and --genes device\n");
     return 2;
   }
-  if (a.align && !a.device_sites) {
-    std::fprintf(stderr, "error: --align position needs --sites device\n");
+  if (a.align != alphabeta::Align::None && !a.device_sites) {
+    std::fprintf(stderr, "error: --align %s needs --sites device\n", alphabeta::align_name(a.align));
     return 2;
   }
   if (a.device_sites && !in_memory) {

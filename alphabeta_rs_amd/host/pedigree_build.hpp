@@ -233,10 +233,12 @@ inline Inputs read_inputs(const std::string& nodelist, const std::string& edgeli
 // lifting the assumption of src/pedigree.rs:240.  The samples have the same length then, so the different-length fallback
 // is never taken: the D matrix comes from the aligned handle, and rc_meth_lvl, hence p0uu, from its folds — the folds over
 // the ALIGNED sites, which differ from the unaligned ones by design whenever a site was dropped.  One line per sample
-// says how many sites it had and how many were kept.
+// says how many sites it had and how many were kept.  Align::Union: abn_codes_create_union instead — every sample padded
+// to the union of all sites with filtered placeholders, so a pair is compared on the sites both hold; rc_meth_lvl and p0uu
+// keep the bits of the unaligned build (a placeholder is not counted).
 inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
                                    std::vector<double>& dm, const std::vector<std::string>* texts = nullptr,
-                                   bool align = false);
+                                   Align align = Align::None);
 // abn_codes_kernel_ms of this thread's last read_inputs_resident (merge records, merge inserted, pack, fold)
 inline double* resident_kernel_ms() {
   static thread_local double ms[4] = {0.0, 0.0, 0.0, 0.0};
@@ -435,8 +437,9 @@ namespace detail {
 inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, const std::string& edgelist,
                                                   double posterior_max_filter, bool gpu_pairwise, bool device_parse,
                                                   bool device_sites, const std::vector<std::string>* texts = nullptr,
-                                                  bool align = false) {
-  if (align && !device_sites) throw Error(ABN_ERR_INVALID_ARG, "--align position needs --sites device");
+                                                  Align align = Align::None) {
+  if (align != Align::None && !device_sites)
+    throw Error(ABN_ERR_INVALID_ARG, std::string("--align ") + align_name(align) + " needs --sites device");
   if (device_sites) {
     if (!device_parse || !gpu_pairwise) throw Error(ABN_ERR_INVALID_ARG, "--sites device needs --parse device");
     std::vector<double> dm;
@@ -467,7 +470,7 @@ inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, c
 
 inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, const std::string& edgelist,
                                                    double posterior_max_filter, bool gpu_pairwise,
-                                                   bool device_parse, bool device_sites, bool align) {
+                                                   bool device_parse, bool device_sites, Align align) {
   return detail::build_pedigree(nodelist, edgelist, posterior_max_filter, gpu_pairwise, device_parse, device_sites, nullptr,
                                 align);
 }

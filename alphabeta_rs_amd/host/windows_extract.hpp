@@ -579,15 +579,20 @@ class Handle {
   // ... from the resident parse results (parse_sites_resident): merged, chosen and placed on the device, no site record
   // coming back (abn_windows_create_parsed).  align: only the sites every sample shares, by (chromosome, start, end,
   // strand), are placed (abn_windows_create_aligned): no window is ragged, and count, kept and the level sums — hence the
-  // side files and every window's p0uu — describe the ALIGNED sites, not each file's own.
+  // side files and every window's p0uu — describe the ALIGNED sites, not each file's own.  Align::Union: every sample gets
+  // all the sites any sample holds, filtered placeholders where it lacks one (abn_windows_create_union): no window is
+  // ragged, count counts union sites, kept and level_sum_kept stay each file's own.
   Handle(Device& dev, const abn_windows_params& p, const Genome& genome, const GeneRule& rule, double posterior_max_filter,
-         const std::vector<ResidentSites>& samples, bool align = false)
+         const std::vector<ResidentSites>& samples, Align align = Align::None)
       : n_(samples.size()) {
     const GenesHandle genes(dev, genome);
     const abn_gene_rule r{rule.cutoff, rule.cutoff_gene_length ? 1 : 0};
     std::vector<abn_sites*> handles;
     for (const ResidentSites& s : samples) handles.push_back(s.get());
-    if (align)
+    if (align == Align::Union)
+      dev.check(abn_windows_create_union(dev.get(), &p, genes.get(), &r, posterior_max_filter, (int32_t)n_, handles.data(), &h_),
+                "abn_windows_create_union");
+    else if (align == Align::Position)
       dev.check(abn_windows_create_aligned(dev.get(), &p, genes.get(), &r, posterior_max_filter, (int32_t)n_, handles.data(), &h_),
                 "abn_windows_create_aligned");
     else
@@ -624,7 +629,8 @@ class Handle {
   std::vector<double> level_sum, level_sum_kept;
   std::vector<int32_t> ragged;  // [W]
   std::vector<int64_t> before;  // [n_samples]: every sample's sites as they came
-  int64_t n_common = -1;        // the sites every sample keeps; -1 without align
+  int64_t n_common = -1;        // the sites every sample keeps; -1 without Align::Position
+  int64_t n_union = -1;         // the sites every sample has, placeholders included; -1 without Align::Union
 
  private:
   void fetch() {  // what the handle reports, to the vectors above
@@ -640,6 +646,7 @@ class Handle {
     abn_windows_layout(h_, nullptr, nullptr, ragged.data());
     before.resize(n_);
     abn_windows_common(h_, before.data(), &n_common, nullptr);
+    abn_windows_union(h_, nullptr, &n_union, nullptr);
   }
   abn_windows* h_ = nullptr;
   size_t n_ = 0, W_ = 0;
@@ -656,7 +663,7 @@ inline std::vector<Site> parse_sites_device_reduced(const std::string& text) {
 }
 
 inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
-                                   std::vector<double>& dm, const std::vector<std::string>* texts, bool align) {
+                                   std::vector<double>& dm, const std::vector<std::string>* texts, Align align) {
   Inputs in = read_graph(nodelist, edgelist);
   std::vector<Node>& nodes = in.nodes;
   const size_t nn = nodes.size();
@@ -684,7 +691,16 @@ inline Inputs read_inputs_resident(const std::string& nodelist, const std::strin
   if (nn > 0) {
     std::vector<abn_sites*> handles;
     for (const auto& s : sites) handles.push_back(s.get());
-    if (align) {
+    if (align == Align::Union) {
+      dev.check(abn_codes_create_union(dev.get(), posterior_max_filter, (int32_t)nn, handles.data(), &codes.h),
+                "abn_codes_create_union");
+      std::vector<int64_t> before(nn);
+      int64_t n_union = 0;
+      abn_codes_union(codes.h, before.data(), &n_union, nullptr);
+      for (size_t i = 0; i < nn; ++i)
+        diag_printf("Aligned by union: %s: %lld sites, %lld in the union\n", nodes[i].file.c_str(), (long long)before[i],
+                    (long long)n_union);
+    } else if (align == Align::Position) {
       dev.check(abn_codes_create_aligned(dev.get(), posterior_max_filter, (int32_t)nn, handles.data(), &codes.h),
                 "abn_codes_create_aligned");
       std::vector<int64_t> before(nn);

@@ -562,6 +562,58 @@ int abn_codes_create_aligned(abn_ctx* ctx, double posterior_max_filter, int32_t 
 int abn_windows_common(const abn_windows* h, int64_t* before /* int64[n] */, int64_t* n_common, double* ms /* double[4] */);
 int abn_codes_common(const abn_codes* h, int64_t* before /* int64[n] */, int64_t* n_common, double* ms /* double[4] */);
 
+/* ------------------------------------------------------------------ methylomes aligned on the union of their sites
+ * The common set above shrinks with every sample that lacks a site; the comparison the model needs is per pair.
+ * DMatrix::from (src/pedigree.rs:240-254) skips a site for a pair when either side's posterior is below the filter and
+ * divides by that pair's own compared sites, so a site a sample lacks can stand in its row as a FILTERED PLACEHOLDER.  The
+ * entries below give every sample all the sites any sample holds.  KEY and WELL ORDERED as above.  THE UNION ORDER: inside
+ * a chromosome the distinct keys ascend by (start, end, strand); the chromosomes come in the run order of the REFERENCE
+ * SAMPLE (the one with the most runs, the lowest index among equals), those it lacks behind them in the order they are
+ * first met going through the samples 0 .. n-1, each in its run order.  Every sample's run order must be a subsequence of
+ * that order.  n_union is the number of distinct keys; after the step every sample has n_union sites: site u is the
+ * sample's own site with the key of union rank u, or the placeholder — that key, code 0x80 (status U, filtered; as a
+ * merged byte of the codes form: not counted for rc_meth_lvl), level +0.0.  The result is what the unaligned entries give
+ * on input into which, for every key a sample lacks, a row with that key, status U, posteriormax 0 and level 0 was
+ * inserted at its place in the union order (with a posterior filter above 0).  A sample without a site becomes a row of
+ * placeholders.  All sites together must be fewer than 2^32, hence n_union too.
+ *
+ * abn_sites_union is the step alone for the per-pair comparison of src/pedigree.rs:240-254, on HOST arrays (arguments as
+ * abn_sites_common): dest [site_offset[n_samples]] = every site's union rank, *n_union = the distinct keys.
+ * ABN_ERR_INVALID_ARG: as abn_sites_common for the arguments, "split run", "not ascending" and a key outside its range
+ * (the same texts), and "run order": a run whose chromosome stands in the union order before the chromosome of the
+ * sample's run in front of it, named by its sample and its first site; the lowest offending site of the whole input
+ * decides among several violations of the well-ordering, and among several of the run order. */
+int abn_sites_union(abn_ctx* ctx, int32_t n_samples, const int64_t* site_offset, const int32_t* chromosome,
+                    const uint32_t* start, const uint32_t* end, const uint8_t* strand, uint32_t* dest /* uint32 [S] out */,
+                    int64_t* n_union /* int64 out */);
+/* abn_sites_union (src/pedigree.rs:240-254 per pair) on DEVICE arrays; site_offset and n_union stay on the host.  Returns
+ * after completion. */
+int abn_sites_union_dev(abn_ctx* ctx, int32_t n_samples, const int64_t* site_offset, const void* dev_chromosome,
+                        const void* dev_start, const void* dev_end, const void* dev_strand, void* dev_dest,
+                        int64_t* n_union);
+/* abn_windows_create_parsed for samples that hold different sites, compared pair by pair as src/pedigree.rs:240-254 does:
+ * the merge, then the union step, then the gene choice and the placement on n_samples x n_union sites.  Every sample has
+ * the same sites in every window, so no window is ragged; count counts union sites, kept and level_sum_kept are those of
+ * the sample's own sites, level_sum counts a placeholder as a site of level 0.  Arguments and errors as
+ * abn_windows_create_parsed, and the refusals of abn_sites_union (no handle comes back).  The resident handles are neither
+ * consumed nor modified. */
+int abn_windows_create_union(abn_ctx* ctx, const abn_windows_params* params, abn_genes* genes, const abn_gene_rule* rule,
+                             double posterior_max_filter, int32_t n_samples, abn_sites* const* samples,
+                             abn_windows** out);
+/* abn_codes_create_parsed for samples that hold different sites (src/pedigree.rs:240-254 per pair): the merge (keys
+ * included), the union step, then the pack and the fold over n_union sites per sample.  *out is an ordinary abn_codes with
+ * same_len = 1; abn_codes_stats reports count = n_union, and kept and level_sum_kept with the bits of the unaligned
+ * handle's: a placeholder is not counted.  D of a pair is over the sites both samples hold and both pass the filter.
+ * Arguments and errors as abn_codes_create_parsed, and the refusals of abn_sites_union. */
+int abn_codes_create_union(abn_ctx* ctx, double posterior_max_filter, int32_t n_samples, abn_sites* const* samples,
+                           abn_codes** out);
+/* What the union alignment (src/pedigree.rs:240-254 per pair) did to a handle; any pointer may be NULL.  before
+ * [n_samples]: every sample's sites as they came; *n_union: the sites every sample has now; ms [8]: the HIP-event times
+ * of the passes (runs and ends; owner; scan; base; rank; dest; invert; gather).  A handle made any other way: *n_union =
+ * -1, ms = zeros; abn_windows_common / abn_codes_common report n_common = -1 on a union handle. */
+int abn_windows_union(const abn_windows* h, int64_t* before /* int64[n] */, int64_t* n_union, double* ms /* double[8] */);
+int abn_codes_union(const abn_codes* h, int64_t* before /* int64[n] */, int64_t* n_union, double* ms /* double[8] */);
+
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
  * src/cli/metaprofile.rs:50-72, where every window shares nodelist/edgelist), S starts and B bootstraps

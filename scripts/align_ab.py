@@ -1,21 +1,26 @@
 #!/usr/bin/env python3
-"""The price of aligning methylomes by position (`--align position`), in one process, alternating, from the resident parse
-results of every methylome to the finished window handle:
+"""The price of aligning methylomes (`--align position`, `--align union`), in one process, alternating, from the resident
+parse results of every methylome to the finished window handle:
 
   (a) abn_windows_create_parsed: merge, gene choice, placement — what `--sites device` runs;
   (b) abn_windows_create_aligned: merge, the common-site step of csrc/abn_sites_common.hpp (runs and ends, match, scan and
-      rank, gather), then gene choice and placement on the aligned arrays — what `--sites device --align position` runs.
+      rank, gather), then gene choice and placement on the aligned arrays — what `--sites device --align position` runs;
+  (c) abn_windows_create_union: merge, the union step of csrc/abn_sites_union.hpp (runs and ends, owner, scan, base, rank,
+      dest, invert, gather), then gene choice and placement on n x n_union sites — what `--align union` runs.
 
-Both are timed with a host clock around the call (both end in device synchronisations); the parse, identical on both
+All are timed with a host clock around the call (all end in device synchronisations); the parse, identical on all
 sides, is outside the span.  The HIP-event times of (b)'s common-site kernels (abn_windows_common) are reported beside
 them, and the bytes of the step's temporaries (the formula of sites_common_match: the keep flags, the two tables of runs,
-match and src of 4 bytes per sample and site of the shortest sample, the workgroup counts).  Shapes, those of
+match and src of 4 bytes per sample and site of the shortest sample, the workgroup counts; for (c), abn_windows_union and the formula of sites_union_rank / sites_union_gather: owner, P, r and
+dest of 4 bytes per site, the tables, the workgroup counts, inv of 4 bytes per sample and union site, own_at).  Shapes, those of
 scripts/resident_ab.py with one text for all samples, so that the samples share every site and (b) - (a) is the price of
 the step: `lines` = --samples-lines (15) all-context methylomes of --lines (1 000 000) lines, about one in seven CG;
 `lines_deferring` = the same with the posterior of every 14th CG line spelled with 23 digits, which the device defers and
 the host accepts; `cg` = --samples-cg (8) methylomes of --sites (2 000 000) CG rows on five chromosomes, rows that repeat a
-position removed; `cg_thinned` = the same with 1 % of the rows removed at random per sample.  Before anything is timed
-the two handles of a shape are compared where the samples share every site: counts, sums bit for bit, layout and packed
+position removed; `cg_thinned` = the same with 1 % of the rows removed at random per sample; `lines_lacking7` and `cg_lacking7` = `lines` and
+`cg` with 7 % of the lines removed at random per sample, where the common set shrinks with every sample and the union does
+not.  Before anything is timed
+the three handles of a shape are compared where the samples share every site: counts, sums bit for bit, layout and packed
 bytes.
 
 Prints one JSON line and writes it to --out (default profiles/align_ab.json).
@@ -142,17 +147,26 @@ def main():
             blocks = (shortest + 255) // 256
             info["temporary_bytes"] = S + 8 * (n + 1) + 2 * 8 * 258 * n + 8 * 4 + 2 * 4 * n * shortest + 4 * (blocks + 1)
             info["merged_array_bytes"] = 22 * S                   # what (b) holds beside (a)'s arrays: the unaligned copies
+            u = A.Windows.from_parsed(ctx, genes, sites, align="union", **kw)
+            n_union = int(u.union()[1])
+            info["n_union"] = n_union
+            info["union_temporary_bytes"] = (4 * 4 * S + 4 + 8 * (n + 1) + 2 * 8 * 258 * n + 8 * 4 + 4 * ((S + 255) // 256 + 1) +
+                                             3 * 4 * 258 + 4 * n * n_union + 4 * n_union)
+            info["union_array_bytes"] = 22 * n * n_union          # the arrays the gene choice and the placement read in (c)
             if shared:
-                assert n_common == min(counts) == max(counts)
-                for x, y in zip(a.stats() + a.layout() + (a.packed(),), b.stats() + b.layout() + (b.packed(),)):
-                    assert x.tobytes() == y.tobytes(), name
+                assert n_common == n_union == min(counts) == max(counts)
+                for h in (b, u):
+                    for x, y in zip(a.stats() + a.layout() + (a.packed(),), h.stats() + h.layout() + (h.packed(),)):
+                        assert x.tobytes() == y.tobytes(), name
                 info["equal"] = True
             else:
                 assert 0 < n_common < min(counts) and not b.layout()[2].any()
+                assert n_union > max(counts) and not u.layout()[2].any()
                 info["ragged_windows_unaligned"] = int(a.layout()[2].sum())
             a.close()
             b.close()
-            plain, aligned, kernels = [], [], []
+            u.close()
+            plain, aligned, kernels, union, union_kernels = [], [], [], [], []
             for rep in range(args.warmup + args.reps):
                 t0 = time.perf_counter()
                 h = A.Windows.from_parsed(ctx, genes, sites, **kw)
@@ -163,14 +177,25 @@ def main():
                 t3 = time.perf_counter()
                 k = h.common()[2]
                 h.close()
+                t4 = time.perf_counter()
+                h = A.Windows.from_parsed(ctx, genes, sites, align="union", **kw)
+                t5 = time.perf_counter()
+                ku = h.union()[2]
+                h.close()
                 if rep >= args.warmup:
                     plain.append(1e3 * (t1 - t0))
                     aligned.append(1e3 * (t3 - t2))
+                    union.append(1e3 * (t5 - t4))
                     kernels.append(k)
+                    union_kernels.append(ku)
             info["parsed_ms"], info["aligned_ms"] = stats(plain), stats(aligned)
             info["price_ms_median"] = info["aligned_ms"]["median"] - info["parsed_ms"]["median"]
             for i, kname in enumerate(("runs_ends", "match", "scan_rank", "gather")):
                 info[f"kernel_ms_{kname}"] = stats([k[i] for k in kernels])
+            info["union_ms"] = stats(union)
+            info["union_price_ms_median"] = info["union_ms"]["median"] - info["parsed_ms"]["median"]
+            for i, kname in enumerate(("runs_ends", "owner", "scan", "base", "rank", "dest", "invert", "gather")):
+                info[f"union_kernel_ms_{kname}"] = stats([k[i] for k in union_kernels])
             for s in sites:
                 s.close()
             genes.close()
@@ -181,6 +206,7 @@ def main():
         genes = [(int(f[0]), int(f[1]), int(f[2])) for f in (l.split(b"\t") for l in annotation.splitlines()) if f[0] == b"1"]
         text = parse_ab.methylome(args.lines, 100, genes)
         run("lines", annotation, [text] * args.samples_lines, True)
+        run("lines_lacking7", annotation, [thinned(text, 0.07, 300 + s) for s in range(args.samples_lines)], False)
         text = deferring(text, 14)
         run("lines_deferring", annotation, [text] * args.samples_lines, True)
         span = 24_000_000
@@ -188,6 +214,7 @@ def main():
         text = strictly_ascending(genes_ab.methylome(args.sites, span, 100))
         run("cg", synthetic, [text] * args.samples_cg, True)
         run("cg_thinned", synthetic, [thinned(text, 0.01, 200 + s) for s in range(args.samples_cg)], False)
+        run("cg_lacking7", synthetic, [thinned(text, 0.07, 400 + s) for s in range(args.samples_cg)], False)
     print(json.dumps(result), flush=True)
     args.out.parent.mkdir(parents=True, exist_ok=True)
     args.out.write_text(json.dumps(result) + "\n")
