@@ -70,6 +70,9 @@ EXPORTED_SYMBOLS = [
     "abn_windows_common", "abn_codes_common",
     "abn_sites_union", "abn_sites_union_dev", "abn_windows_create_union", "abn_codes_create_union",
     "abn_windows_union", "abn_codes_union",
+    "abn_tiles_create", "abn_tiles_destroy", "abn_tiles_info", "abn_tiles_runs", "abn_tiles_set_intervals",
+    "abn_tiles_set_fixed", "abn_tiles_intervals", "abn_tiles_layout", "abn_tiles_stats", "abn_tiles_pairwise",
+    "abn_tiles_kernel_ms",
 ]
 
 
@@ -233,6 +236,17 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_windows_union.argtypes = [vp, i64p, i64p, dp]
     L.abn_codes_union.argtypes = [vp, i64p, i64p, dp]
     i32p = C.POINTER(C.c_int32)
+    L.abn_tiles_create.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.POINTER(vp), C.POINTER(vp)]
+    L.abn_tiles_destroy.argtypes = [vp]
+    L.abn_tiles_info.argtypes = [vp, i32p, i64p, i64p, i32p, i64p]
+    L.abn_tiles_runs.argtypes = [vp, i32p, i64p, i64p, u32p]
+    L.abn_tiles_set_intervals.argtypes = [vp, C.c_int64, i32p, i64p, i64p]
+    L.abn_tiles_set_fixed.argtypes = [vp, C.c_int64, C.c_int64]
+    L.abn_tiles_intervals.argtypes = [vp, i32p, i64p, i64p]
+    L.abn_tiles_layout.argtypes = [vp, i64p, i64p]
+    L.abn_tiles_stats.argtypes = [vp, i64p, dp, i64p]
+    L.abn_tiles_pairwise.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
+    L.abn_tiles_kernel_ms.argtypes = [vp, dp]
     L.abn_genes_create.argtypes = [vp, C.c_int32, i32p, i32p, i64p, u32p, u32p, u8p, C.POINTER(vp)]
     L.abn_genes_destroy.argtypes = [vp]
     L.abn_genes_choose.argtypes = [vp, C.POINTER(GeneRule), C.c_int32, i64p, i32p, u32p, u32p, u8p, u32p, u32p, u8p, dp]
@@ -1267,6 +1281,123 @@ class Codes:
         """the HIP-event ms of from_parsed's kernels: merge of the records, merge of the inserted lines, pack, fold"""
         ms = np.zeros(4)
         self.ctx._check(self._L.abn_codes_kernel_ms(self._h, _dp(ms)))
+        return ms
+
+
+class Tiles:
+    """abn_tiles: Pedigree::build (src/pedigree.rs:147-172, :210-261) once per genomic tile — a fixed bin or a listed region
+    (the region rows of src/cli/metaprofile.rs:50-72) — over resident parse results: the aligned code matrix, its columns'
+    keys and every sample's merged bytes and levels stay on the device; a tile is a contiguous column range."""
+
+    ALIGN = {"none": 0, "position": 1, "union": 2}
+
+    @classmethod
+    def from_parsed(cls, ctx: Context, sites_list, *, posterior_max_filter, align=False):
+        """From resident parse results, as Codes.from_parsed (abn_tiles_create).  align False / "none": the reference's
+        assumption that site k is the same site in every sample — the keys are sample 0's and every sample must have its
+        number of sites; True / "position": the sites every sample shares; "union": every site any sample holds, filtered
+        and uncounted placeholders where a sample lacks one."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self._L = ctx._L
+        sites_list = list(sites_list)
+        handles = (C.c_void_p * max(len(sites_list), 1))(*(s._h for s in sites_list))
+        h = C.c_void_p()
+        ctx._check(self._L.abn_tiles_create(ctx._h, posterior_max_filter, cls.ALIGN[_align_mode(align)], len(sites_list),
+                                            handles, C.byref(h)))
+        self._h = h
+        i = self.info()
+        self.n_samples, self.n_columns, self.row_stride, self.n_runs = i["n_samples"], i["n_columns"], i["row_stride"], i["n_runs"]
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.abn_tiles_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{n_samples, n_columns, row_stride (bytes), n_runs, n_tiles (-1 before set_intervals / set_fixed)}"""
+        n, runs, cols, stride, tiles = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        self.ctx._check(self._L.abn_tiles_info(self._h, C.byref(n), C.byref(cols), C.byref(stride), C.byref(runs), C.byref(tiles)))
+        return {"n_samples": n.value, "n_columns": cols.value, "row_stride": stride.value, "n_runs": runs.value,
+                "n_tiles": tiles.value}
+
+    def runs(self):
+        """(chromosome int32, first int64, count int64, last_start uint32), each (n_runs,): the chromosome runs of the
+        columns in run order, and the start of every run's last column"""
+        chrom, last = np.zeros(self.n_runs, dtype=np.int32), np.zeros(self.n_runs, dtype=np.uint32)
+        first, count = np.zeros(self.n_runs, dtype=np.int64), np.zeros(self.n_runs, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_tiles_runs(self._h, chrom.ctypes.data_as(C.POINTER(C.c_int32)), first.ctypes.data_as(i64p),
+                                               count.ctypes.data_as(i64p), _u32p(last)))
+        return chrom, first, count, last
+
+    def set_intervals(self, chromosome, start, end):
+        """the tiles (chromosome 0..257, start, end), half-open on a site's start, bounds in [0, 2^32]: the search and the
+        per-(sample, tile) folds run on the device; a new list replaces the old"""
+        chrom = np.ascontiguousarray(chromosome, dtype=np.int32).ravel()
+        lo, hi = (np.ascontiguousarray(a, dtype=np.int64).ravel() for a in (start, end))
+        if not chrom.shape == lo.shape == hi.shape:
+            raise ValueError("chromosome, start and end differ in length")
+        i64p = C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_tiles_set_intervals(self._h, chrom.shape[0], chrom.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        lo.ctypes.data_as(i64p), hi.ctypes.data_as(i64p)))
+
+    def set_fixed(self, size, step=0):
+        """fixed tiles: for every run in run order [k step, k step + size), k = 0 .. ceil((last_start + 1) / step) - 1
+        (step 0: size)"""
+        self.ctx._check(self._L.abn_tiles_set_fixed(self._h, int(size), int(step)))
+
+    def _n_tiles(self):
+        return max(self.info()["n_tiles"], 0)
+
+    def intervals(self):
+        """(chromosome int32, start int64, end int64), each (n_tiles,)"""
+        T = self._n_tiles()
+        chrom, lo, hi = np.zeros(T, dtype=np.int32), np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_tiles_intervals(self._h, chrom.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    lo.ctypes.data_as(i64p), hi.ctypes.data_as(i64p)))
+        return chrom, lo, hi
+
+    def layout(self):
+        """(begin int64, end int64), each (n_tiles,): every tile's columns [begin, end)"""
+        T = self._n_tiles()
+        begin, end = np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_tiles_layout(self._h, begin.ctypes.data_as(i64p), end.ctypes.data_as(i64p)))
+        return begin, end
+
+    def stats(self):
+        """(count int64 (n_tiles,), level_sum_kept (n_samples, n_tiles), kept int64 (n_samples, n_tiles)): a tile's columns,
+        and per sample the sum and number of the tile's levels whose posterior passes the filter"""
+        T = self._n_tiles()
+        count, kept = np.zeros(T, dtype=np.int64), np.zeros((self.n_samples, T), dtype=np.int64)
+        lsk = np.zeros((self.n_samples, T))
+        i64p = C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_tiles_stats(self._h, count.ctypes.data_as(i64p), _dp(lsk), kept.ctypes.data_as(i64p)))
+        return count, lsk, kept
+
+    def pairwise(self):
+        """(diff, both, dvalue), each (n_tiles, pairs): pairwise_divergence_windows_packed on the resident matrix over the
+        tiles' columns"""
+        T, npairs = self._n_tiles(), self.n_samples * (self.n_samples - 1) // 2
+        diff, both = np.zeros((T, npairs), dtype=np.uint64), np.zeros((T, npairs), dtype=np.uint64)
+        dval = np.zeros((T, npairs))
+        u64p = C.POINTER(C.c_uint64)
+        self.ctx._check(self._L.abn_tiles_pairwise(self._h, diff.ctypes.data_as(u64p), both.ctypes.data_as(u64p), _dp(dval)))
+        return diff, both, dval
+
+    def kernel_ms(self) -> np.ndarray:
+        """the HIP-event ms of the last set_intervals / set_fixed: search, fold"""
+        ms = np.zeros(2)
+        self.ctx._check(self._L.abn_tiles_kernel_ms(self._h, _dp(ms)))
         return ms
 
 

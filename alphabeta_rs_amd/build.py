@@ -16,7 +16,7 @@ LIB = PKG / "libabneutral_hip.so"
 # the one list of the library's sources: scripts/flag_variants.py and scripts/stamps.py build from it too
 SOURCES = [CSRC / "abn_api.hip", CSRC / "abn_pairwise.hip", CSRC / "abn_windows.hip", CSRC / "abn_analyze.hip",
            CSRC / "abn_multi.hip", CSRC / "abn_sites.hip", CSRC / "abn_genes.hip", CSRC / "abn_codes.hip",
-           CSRC / "abn_sites_common.hip", CSRC / "abn_sites_union.hip",
+           CSRC / "abn_sites_common.hip", CSRC / "abn_sites_union.hip", CSRC / "abn_tiles.hip",
            CSRC / "abn_pack.cpp"]  # host-only: the packed code format (also built alone under the host sanitizers)
 DEPS = [*sorted(CSRC.glob("*.hpp")), CSRC / "abn_philox.h", PKG.parent / "include" / "abneutral.h"]
 HIPCC_FLAGS = [
@@ -89,7 +89,7 @@ def build_host(force: bool = False, verbose: bool = False) -> Path:
             HOST / "metaprofile.hpp", HOST / "metaprofile_cli.cpp", HOST / "reference_tests.cpp",
             CSRC / "abn_route.hpp", CSRC / "abn_constants.hpp", CSRC / "abn_parse.hpp", CSRC / "abn_genes.hpp",
             CSRC / "abn_sites_merge.hpp", CSRC / "abn_codes.hpp", CSRC / "abn_sites_common.hpp",
-            CSRC / "abn_sites_union.hpp"]  # host_capi.cpp exports the launch policy to the tests
+            CSRC / "abn_sites_union.hpp", CSRC / "abn_tiles.hpp", HOST / "tiles.hpp"]  # host_capi.cpp exports the launch policy to the tests
     newest = max(p.stat().st_mtime for p in srcs)
     CLI.parent.mkdir(exist_ok=True)
     common = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-I", str(PKG.parent / "include")]

@@ -26,6 +26,16 @@ struct abn_codes {
   DevBuf<uint8_t> packed;               // [n x stride], device-resident between calls
 };
 
+// the pack kernel over n rows of row_dwords dwords (for abn_tiles.hip too): on the context's stream, nothing waited for
+int abn::codes_pack_dev(abn_ctx* c, const uint8_t* dcode, const long long* dcode_off, const long long* dsite_off, int n,
+                        long long row_dwords, uint8_t* dpacked) {
+  const unsigned grid = (unsigned)(((long long)n * row_dwords + kCodesThreads - 1) / kCodesThreads);
+  hipLaunchKernelGGL(abn_codes_pack_kernel, dim3(grid), dim3(kCodesThreads), 0, c->stream, dcode, dcode_off, dsite_off, n,
+                     row_dwords, (uint32_t*)dpacked);
+  HIPCHK(c, hipGetLastError());
+  return ABN_OK;
+}
+
 // merge, pack, fold; the merged arrays (9 bytes per site) live only in here.  With `align` the merge is the full one, keys
 // included (and the reduced one behind it, for the merged bytes: merge_code has no kCodeCounted), and the sites every
 // sample shares (abn_sites_common.hpp; kAlignPosition) or the union of the samples' sites with filtered placeholders
@@ -116,10 +126,7 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, i
     else std::copy(st.ms, st.ms + 4, h->common_ms);
   }
   HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
-  const unsigned grid = (unsigned)(((long long)n * row_dwords + kCodesThreads - 1) / kCodesThreads);
-  hipLaunchKernelGGL(abn_codes_pack_kernel, dim3(grid), dim3(kCodesThreads), 0, c->stream, dcode.p, dcode_off.p, dsite_off.p,
-                     n, row_dwords, (uint32_t*)h->packed.p);
-  HIPCHK(c, hipGetLastError());
+  if (int rc = codes_pack_dev(c, dcode.p, dcode_off.p, dsite_off.p, n, row_dwords, h->packed.p)) return rc;
   HIPCHK(c, hipEventRecord(ev.e[3], c->stream));
   hipLaunchKernelGGL(abn_codes_fold_kernel, dim3((unsigned)n), dim3(kCodesWave), 0, c->stream, dcode.p, dlevel.p,
                      dcode_off.p, dsite_off.p, dsum.p, dkept.p);

@@ -139,38 +139,16 @@ abn_codes_insert_kernel(const MergeChunk* __restrict__ chunks, MergeInserted ins
 }
 #endif
 
-#if defined(__HIPCC__) && defined(ABN_CODES_KERNELS)  // (abn_codes.hip defines it)
-// ------------------------------------------------------------------------------------------------ pack and fold
-// Sample s: its merged bytes at code + code_off[s] (a multiple of 16; the bytes up to the next multiple of 16 behind its
-// last site belong to it and may hold anything), its levels at level + site_off[s], site_off[s + 1] - site_off[s] sites.
-
-// grid: ceil(n_samples * row_dwords / kCodesThreads); a lane per dword of packed [n_samples x 4 row_dwords bytes]
-__global__ void __launch_bounds__(kCodesThreads)
-abn_codes_pack_kernel(const uint8_t* __restrict__ code, const long long* __restrict__ code_off,
-                      const long long* __restrict__ site_off, int n_samples, long long row_dwords,
-                      uint32_t* __restrict__ packed) {
-  const long long at = (long long)blockIdx.x * kCodesThreads + threadIdx.x;
-  if (at >= (long long)n_samples * row_dwords) return;
-  const long long s = at / row_dwords, g = at - s * row_dwords;
-  const long long left = site_off[s + 1] - site_off[s] - 16 * g;
-  const int valid = left >= 16 ? 16 : (left <= 0 ? 0 : (int)left);
-  uint4 v = make_uint4(0, 0, 0, 0);
-  if (valid > 0) v = *(const uint4*)(code + code_off[s] + 16 * g);  // within the sample's bytes, 16-byte aligned
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  packed[at] = codes_pack_dword(w, valid);
-}
-
-// grid: n_samples workgroups of one wavefront.  Per step 64 sites: one coalesced load of their levels and merged bytes —
-// the next step's issued before this step's chain begins, so their latency sits behind the 64 dependent additions — then
-// every lane runs the same chain over the 64 addends, read by constant lane index.  Lane 0 writes sum[s] and kept[s].
-__global__ void __launch_bounds__(kCodesWave)
-abn_codes_fold_kernel(const uint8_t* __restrict__ code, const double* __restrict__ level,
-                      const long long* __restrict__ code_off, const long long* __restrict__ site_off,
-                      double* __restrict__ sum, long long* __restrict__ kept) {
-  const int s = blockIdx.x, lane = threadIdx.x;
-  const long long n = site_off[s + 1] - site_off[s];
-  const uint8_t* c = code + code_off[s];
-  const double* l = level + site_off[s];
+#if defined(__HIPCC__) && (defined(ABN_CODES_KERNELS) || defined(ABN_TILES_KERNELS))
+// ------------------------------------------------------------------------------------------------ the fold of one wavefront
+// The n sites at c (merged bytes) and l (levels), by the 64 lanes of one wavefront: acc = the chain s = s + x from +0.0 in
+// file order, count = the counted sites; every lane ends with both.  Per step 64 sites: one coalesced load of their levels
+// and merged bytes — the next step's issued before this step's chain begins, so their latency sits behind the 64 dependent
+// additions — then every lane runs the same chain over the 64 addends, read by constant lane index.  c and l need no
+// alignment.  (Shared by abn_codes_fold_kernel, a sample per wavefront, and abn_tiles.hpp's abn_tiles_fold_kernel, a
+// (sample, tile) per wavefront.)
+__device__ __forceinline__ void codes_fold_wave(const uint8_t* __restrict__ c, const double* __restrict__ l, long long n,
+                                                int lane, double& acc_out, long long& count_out) {
   double acc = 0.0;
   long long count = 0;
   // A lane behind the last site loads the last site again (an index clamped to n - 1, never out of bounds) and is masked
@@ -192,6 +170,42 @@ abn_codes_fold_kernel(const uint8_t* __restrict__ code, const double* __restrict
     for (int j = 0; j < kCodesWave; ++j)
       acc = acc + __hiloint2double(__builtin_amdgcn_readlane(hi, j), __builtin_amdgcn_readlane(lo, j));
   }
+  acc_out = acc;
+  count_out = count;
+}
+#endif
+
+#if defined(__HIPCC__) && defined(ABN_CODES_KERNELS)  // (abn_codes.hip defines it)
+// ------------------------------------------------------------------------------------------------ pack and fold
+// Sample s: its merged bytes at code + code_off[s] (a multiple of 16; the bytes up to the next multiple of 16 behind its
+// last site belong to it and may hold anything), its levels at level + site_off[s], site_off[s + 1] - site_off[s] sites.
+
+// grid: ceil(n_samples * row_dwords / kCodesThreads); a lane per dword of packed [n_samples x 4 row_dwords bytes]
+__global__ void __launch_bounds__(kCodesThreads)
+abn_codes_pack_kernel(const uint8_t* __restrict__ code, const long long* __restrict__ code_off,
+                      const long long* __restrict__ site_off, int n_samples, long long row_dwords,
+                      uint32_t* __restrict__ packed) {
+  const long long at = (long long)blockIdx.x * kCodesThreads + threadIdx.x;
+  if (at >= (long long)n_samples * row_dwords) return;
+  const long long s = at / row_dwords, g = at - s * row_dwords;
+  const long long left = site_off[s + 1] - site_off[s] - 16 * g;
+  const int valid = left >= 16 ? 16 : (left <= 0 ? 0 : (int)left);
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (valid > 0) v = *(const uint4*)(code + code_off[s] + 16 * g);  // within the sample's bytes, 16-byte aligned
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  packed[at] = codes_pack_dword(w, valid);
+}
+
+// grid: n_samples workgroups of one wavefront: codes_fold_wave (above) over the sample's sites.  Lane 0 writes sum[s] and
+// kept[s].
+__global__ void __launch_bounds__(kCodesWave)
+abn_codes_fold_kernel(const uint8_t* __restrict__ code, const double* __restrict__ level,
+                      const long long* __restrict__ code_off, const long long* __restrict__ site_off,
+                      double* __restrict__ sum, long long* __restrict__ kept) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  double acc;
+  long long count;
+  codes_fold_wave(code + code_off[s], level + site_off[s], site_off[s + 1] - site_off[s], lane, acc, count);
   if (lane == 0) {
     sum[s] = acc;
     kept[s] = count;

@@ -1,5 +1,5 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (abn_api.hip, abn_pairwise.hip,
-// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip): the context, its device-buffer pool, error reporting,
+// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip, abn_tiles.hip): the context, its device-buffer pool, error reporting,
 // the kernel_ms timer.  Not part of the C-ABI (include/abneutral.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -210,6 +210,10 @@ int sites_merge_dev(const abn_sites* h, bool inserted, double filter, int32_t* d
 // ... and for abn_codes_create_parsed (abn_codes.hip): the same merge in its reduced form (abn_codes.hpp), the merged byte
 // and the level of every site
 int sites_merge_codes_dev(const abn_sites* h, bool inserted, double filter, uint8_t* dcode, double* dlevel);
+// abn_codes.hip, for abn_tiles_create (abn_tiles.hip): the pack of n samples' merged bytes (sample s: dcode +
+// dcode_off[s], a multiple of 16; dsite_off[s + 1] - dsite_off[s] sites) into dpacked [n x 4 row_dwords bytes]
+int codes_pack_dev(abn_ctx* c, const uint8_t* dcode, const long long* dcode_off, const long long* dsite_off, int n,
+                   long long row_dwords, uint8_t* dpacked);
 // abn_sites_common.hip, for abn_windows_create_aligned and abn_codes_create_aligned: the common-site step
 // (abn_sites_common.hpp) on DEVICE key arrays, in its two halves.  sites_common_match runs the order checks, the match and
 // the ranks, waits, and leaves n_common in the state (dkeep [site_offset[n]], or null: the state's own); the caller sizes

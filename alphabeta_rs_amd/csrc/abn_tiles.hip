@@ -1,0 +1,376 @@
+// abn_tiles_*: genomic tiles over resident, aligned methylomes — Pedigree::build (src/pedigree.rs:147-172, :210-261) once
+// per fixed bin or listed region.  Kernels, the definition and the serial forms: abn_tiles.hpp.  The build is
+// abn_codes.hip's (merge, optional common-site or union step, gather, pack) with the columns' keys, the merged bytes and the
+// levels kept; the merge launches are abn_sites.hip's, the order checks abn_sites_common.hip's, the scan abn_pairwise.hip's.
+#include "abn_host.hpp"
+#define ABN_TILES_KERNELS
+#include "abn_tiles.hpp"
+
+using namespace abn;
+
+struct abn_tiles {
+  abn_ctx* ctx = nullptr;
+  int n = 0;
+  long long n_columns = 0;
+  long long stride = 0;       // bytes per row of `packed`
+  long long code_stride = 0;  // bytes per sample of `code`: n_columns up to a multiple of 16
+  DevBuf<uint8_t> packed;     // [n x stride]
+  DevBuf<uint8_t> code;       // [n x code_stride] merged bytes
+  DevBuf<double> level;       // [n x n_columns]
+  DevBuf<int32_t> chromosome; // [n_columns] the columns' keys
+  DevBuf<uint32_t> start;
+  DevBuf<long long> run_begin, run_end;  // [kCommonChroms]
+  std::vector<TileRun> runs;
+  bool has_tiles = false;
+  std::vector<int32_t> tchromosome;  // [T] the intervals
+  std::vector<int64_t> tstart, tend;
+  std::vector<int64_t> begin, end;   // [T] their columns
+  std::vector<double> level_sum_kept;  // [n x T]
+  std::vector<int64_t> kept;
+  double ms[2] = {0.0, 0.0};  // search, fold
+};
+
+static int tiles_build(abn_tiles* h, double filter, abn_sites* const* samples, int align, std::vector<int64_t> count) {
+  abn_ctx* c = h->ctx;
+  const int n = h->n;
+  DevBuf<int32_t> mchrom;
+  DevBuf<uint32_t> mstart, mend;
+  DevBuf<uint8_t> mstrand, mcode;
+  DevBuf<double> mlevel;
+  CommonState st;
+  UnionState ust;
+  const std::vector<int64_t> before = count;
+  std::vector<int64_t> merged_off((size_t)n + 1, 0);
+  // the full merge, keys included: of every sample under an alignment, of sample 0 alone without one
+  const int n_keyed = align ? n : 1;
+  for (int s = 0; s < n_keyed; ++s) merged_off[(size_t)s + 1] = merged_off[(size_t)s] + count[(size_t)s];
+  const size_t S = std::max<size_t>((size_t)merged_off[(size_t)n_keyed], 1);
+  HIPCHK(c, mchrom.alloc(S));
+  HIPCHK(c, mstart.alloc(S));
+  HIPCHK(c, mend.alloc(S));
+  HIPCHK(c, mstrand.alloc(S));
+  HIPCHK(c, mcode.alloc(S));
+  HIPCHK(c, mlevel.alloc(S));
+  for (int pass = 0; pass < 2; ++pass)
+    for (int s = 0; s < n_keyed; ++s) {
+      const size_t o = (size_t)merged_off[(size_t)s];
+      if (count[(size_t)s] == 0) continue;
+      if (int rc = sites_merge_dev(samples[s], pass == 1, filter, mchrom.p + o, mstart.p + o, mend.p + o, mstrand.p + o,
+                                   mcode.p + o, mlevel.p + o))
+        return rc;
+    }
+  long long each = count[0];
+  if (align) {
+    const CommonSites keys{mchrom.p, mstart.p, mend.p, mstrand.p};
+    if (int rc = align == kAlignUnion ? sites_union_rank(c, n, merged_off.data(), keys, nullptr, ust)
+                                      : sites_common_match(c, n, merged_off.data(), keys, nullptr, st))
+      return rc;
+    each = align == kAlignUnion ? ust.n_union : st.n_common;
+  }
+  h->n_columns = each;
+  h->code_stride = (each + 15) / 16 * 16;  // whole 16-byte loads of the pack
+  h->stride = std::max<long long>(abn_packed_row_stride(each), 64);
+  const long long row_dwords = h->stride / 4;
+  if (((long long)n * row_dwords + kCodesThreads - 1) / kCodesThreads > 0x7fffffffLL ||
+      (each + kCommonThreads - 1) / kCommonThreads > 0x7fffffffLL)
+    return set_err(c, ABN_ERR_INVALID_ARG, "packed matrix too large for one handle");
+  const size_t E = std::max<size_t>((size_t)each, 1);
+  HIPCHK(c, h->code.alloc(std::max<size_t>((size_t)n * (size_t)h->code_stride, 16)));
+  HIPCHK(c, h->level.alloc((size_t)n * E));
+  HIPCHK(c, h->chromosome.alloc(E));
+  HIPCHK(c, h->start.alloc(E));
+  HIPCHK(c, h->run_begin.alloc(kCommonChroms));
+  HIPCHK(c, h->run_end.alloc(kCommonChroms));
+  HIPCHK(c, h->packed.alloc((size_t)n * (size_t)h->stride));
+
+  // the reduced merge: the merged bytes (merge_code has no kCodeCounted) and the levels
+  for (int pass = 0; pass < 2; ++pass)
+    for (int s = 0; s < n; ++s) {
+      if (before[(size_t)s] == 0) continue;
+      if (int rc = align ? sites_merge_codes_dev(samples[s], pass == 1, filter, mcode.p + merged_off[(size_t)s],
+                                                 mlevel.p + merged_off[(size_t)s])
+                         : sites_merge_codes_dev(samples[s], pass == 1, filter, h->code.p + (size_t)s * (size_t)h->code_stride,
+                                                 h->level.p + (size_t)s * (size_t)each))
+        return rc;
+    }
+  // the columns' four key fields, for the order checks: sample 0's after the gather, or as merged
+  DevBuf<int32_t> gchrom;
+  DevBuf<uint32_t> gstart, gend;
+  DevBuf<uint8_t> gstrand;
+  CommonSites columns{mchrom.p, mstart.p, mend.p, mstrand.p};
+  if (align) {
+    HIPCHK(c, gchrom.alloc((size_t)n * E));
+    HIPCHK(c, gstart.alloc((size_t)n * E));
+    HIPCHK(c, gend.alloc((size_t)n * E));
+    HIPCHK(c, gstrand.alloc((size_t)n * E));
+    const CommonGather g{mcode.p, mlevel.p, gchrom.p, gstart.p, gend.p, gstrand.p, h->level.p, h->code.p, h->code_stride};
+    if (int rc = align == kAlignUnion ? sites_union_gather(c, ust, g) : sites_common_gather(c, st, g)) return rc;
+    columns = CommonSites{gchrom.p, gstart.p, gend.p, gstrand.p};  // (sample 0's are the first `each` of each)
+  }
+  if (each > 0) {
+    HIPCHK(c, hipMemcpyAsync(h->chromosome.p, columns.chromosome, (size_t)each * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h->start.p, columns.start, (size_t)each * 4, hipMemcpyDeviceToDevice, c->stream));
+  }
+  // the runs and ends passes over the columns as one sample: the run tables, and the order checks' refusals
+  const long long col_off[2] = {0, each};
+  DevBuf<long long> dcol_off, derr;
+  DevBuf<uint32_t> dlast;
+  HIPCHK(c, dcol_off.alloc(2));
+  HIPCHK(c, derr.alloc(kCommonErrs));
+  HIPCHK(c, dlast.alloc(kCommonChroms));
+  HIPCHK(c, hipMemcpyAsync(dcol_off.p, col_off, sizeof col_off, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(h->run_begin.p, 0x7f, h->run_begin.bytes(), c->stream));  // kCommonNone
+  HIPCHK(c, hipMemsetAsync(h->run_end.p, 0, h->run_end.bytes(), c->stream));
+  HIPCHK(c, hipMemsetAsync(derr.p, 0x7f, derr.bytes(), c->stream));
+  if (int rc = sites_common_tables(c, columns, dcol_off.p, 1, each, h->run_begin.p, h->run_end.p, derr.p)) return rc;
+  hipLaunchKernelGGL(abn_tiles_last_kernel, dim3((kCommonChroms + kTilesThreads - 1) / kTilesThreads), dim3(kTilesThreads), 0,
+                     c->stream, (const uint32_t*)h->start.p, (const long long*)h->run_begin.p,
+                     (const long long*)h->run_end.p, dlast.p);
+  HIPCHK(c, hipGetLastError());
+  // the pack
+  std::vector<long long> site_off((size_t)n + 1), code_off((size_t)n + 1);
+  for (int s = 0; s <= n; ++s) site_off[(size_t)s] = (long long)s * each, code_off[(size_t)s] = (long long)s * h->code_stride;
+  DevBuf<long long> dsite_off, dcode_off;
+  HIPCHK(c, dsite_off.alloc((size_t)n + 1));
+  HIPCHK(c, dcode_off.alloc((size_t)n + 1));
+  HIPCHK(c, hipMemcpyAsync(dsite_off.p, site_off.data(), dsite_off.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dcode_off.p, code_off.data(), dcode_off.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (int rc = codes_pack_dev(c, h->code.p, dcode_off.p, dsite_off.p, n, row_dwords, h->packed.p)) return rc;
+
+  long long err[kCommonErrs], run_begin[kCommonChroms], run_end[kCommonChroms];
+  uint32_t last[kCommonChroms];
+  HIPCHK(c, hipMemcpyAsync(err, derr.p, sizeof err, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(run_begin, h->run_begin.p, sizeof run_begin, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(run_end, h->run_end.p, sizeof run_end, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(last, dlast.p, sizeof last, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the merged arrays are freed on return
+  const CommonRefusal r = common_refusal(err, kCommonSplitRun, kCommonBadKey, col_off, 1);
+  if (r.kind)
+    return set_err(c, ABN_ERR_INVALID_ARG,
+                   "the sites cannot be cut into tiles: their keys are not well ordered: " + common_refusal_text(r));
+  tiles_runs_from_tables(run_begin, run_end, last, &h->runs);
+  return ABN_OK;
+}
+
+extern "C" int abn_tiles_create(abn_ctx* c, double posterior_max_filter, int32_t align, int32_t n_samples,
+                                abn_sites* const* samples, abn_tiles** out) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  if (out) *out = nullptr;
+  if (!out || !samples || n_samples <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (n_samples > 65535) return set_err(c, ABN_ERR_INVALID_ARG, "too many samples");
+  if (align != kAlignNone && align != kAlignPosition && align != kAlignUnion)
+    return set_err(c, ABN_ERR_INVALID_ARG, "align expects 0 (none), 1 (position) or 2 (union)");
+  std::unique_ptr<abn_tiles> h(new (std::nothrow) abn_tiles);
+  if (!h) return set_err(c, ABN_ERR_HIP, "out of host memory");
+  h->ctx = c;
+  h->n = n_samples;
+  try {
+    std::vector<int64_t> count((size_t)n_samples, 0);
+    for (int s = 0; s < n_samples; ++s) {
+      if (!samples[s]) return set_err(c, ABN_ERR_INVALID_ARG, "a null sites handle");
+      if (!sites_ctx(samples[s])) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle in the host form (abn_sites_parse)");
+      if (sites_ctx(samples[s]) != c) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle of another context");
+      count[(size_t)s] = sites_merged_count(samples[s]);
+      if (count[(size_t)s] < 0)
+        return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle with deferred lines and no abn_sites_insert");
+    }
+    if (align == kAlignNone)
+      for (int s = 1; s < n_samples; ++s)
+        if (count[(size_t)s] != count[0])
+          return set_err(c, ABN_ERR_INVALID_ARG,
+                         "sample " + std::to_string(s) + " has " + std::to_string(count[(size_t)s]) + " sites, sample 0 has " +
+                             std::to_string(count[0]) +
+                             ": tiles need the same sites in every sample; align them with --align position or --align union");
+    HIPCHK(c, hipSetDevice(c->device));
+    PoolScope pool_scope(c);
+    if (int rc = tiles_build(h.get(), posterior_max_filter, samples, align, count)) return rc;
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+  *out = h.release();
+  return ABN_OK;
+}
+
+extern "C" int abn_tiles_destroy(abn_tiles* h) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  (void)hipSetDevice(h->ctx->device);
+  delete h;
+  return ABN_OK;
+}
+
+extern "C" int abn_tiles_info(const abn_tiles* h, int32_t* n_samples, int64_t* n_columns, int64_t* row_stride_bytes,
+                              int32_t* n_runs, int64_t* n_tiles) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (n_samples) *n_samples = h->n;
+  if (n_columns) *n_columns = h->n_columns;
+  if (row_stride_bytes) *row_stride_bytes = h->stride;
+  if (n_runs) *n_runs = (int32_t)h->runs.size();
+  if (n_tiles) *n_tiles = h->has_tiles ? (int64_t)h->tchromosome.size() : -1;
+  return ABN_OK;
+}
+
+extern "C" int abn_tiles_runs(const abn_tiles* h, int32_t* chromosome, int64_t* first, int64_t* count, uint32_t* last_start) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  for (size_t r = 0; r < h->runs.size(); ++r) {
+    if (chromosome) chromosome[r] = h->runs[r].chromosome;
+    if (first) first[r] = h->runs[r].first;
+    if (count) count[r] = h->runs[r].count;
+    if (last_start) last_start[r] = h->runs[r].last_start;
+  }
+  return ABN_OK;
+}
+
+// the search and the folds of the handle's interval list; the list is valid
+static int tiles_run(abn_tiles* h) {
+  abn_ctx* c = h->ctx;
+  const size_t T = h->tchromosome.size(), n = (size_t)h->n;
+  h->begin.assign(T, 0);
+  h->end.assign(T, 0);
+  h->level_sum_kept.assign(n * T, 0.0);
+  h->kept.assign(n * T, 0);
+  h->ms[0] = h->ms[1] = 0.0;
+  h->has_tiles = true;
+  if (T == 0) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  DevBuf<int32_t> dchrom;
+  DevBuf<long long> dpos, dpos_end, dbegin, dend, dkept;
+  DevBuf<double> dsum;
+  HIPCHK(c, dchrom.alloc(T));
+  HIPCHK(c, dpos.alloc(T));
+  HIPCHK(c, dpos_end.alloc(T));
+  HIPCHK(c, dbegin.alloc(T));
+  HIPCHK(c, dend.alloc(T));
+  HIPCHK(c, dsum.alloc(n * T));
+  HIPCHK(c, dkept.alloc(n * T));
+  static_assert(sizeof(long long) == sizeof(int64_t), "positions and columns");
+  HIPCHK(c, hipMemcpyAsync(dchrom.p, h->tchromosome.data(), dchrom.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dpos.p, h->tstart.data(), dpos.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dpos_end.p, h->tend.data(), dpos_end.bytes(), hipMemcpyHostToDevice, c->stream));
+  struct Events {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  for (int k = 0; k < 3; ++k) HIPCHK(c, hipEventCreate(&ev.e[k]));
+  HIPCHK(c, hipEventRecord(ev.e[0], c->stream));
+  hipLaunchKernelGGL(abn_tiles_search_kernel, dim3((unsigned)((T + kTilesThreads - 1) / kTilesThreads)), dim3(kTilesThreads), 0,
+                     c->stream, (const uint32_t*)h->start.p, (const long long*)h->run_begin.p,
+                     (const long long*)h->run_end.p, (long long)T, (const int32_t*)dchrom.p, (const long long*)dpos.p,
+                     (const long long*)dpos_end.p, dbegin.p, dend.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(ev.e[1], c->stream));
+  hipLaunchKernelGGL(abn_tiles_fold_kernel, dim3((unsigned)T, (unsigned)n), dim3(kCodesWave), 0, c->stream,
+                     (const uint8_t*)h->code.p, h->code_stride, (const double*)h->level.p, h->n_columns, (long long)T,
+                     (const long long*)dbegin.p, (const long long*)dend.p, dsum.p, dkept.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
+  HIPCHK(c, hipMemcpyAsync(h->begin.data(), dbegin.p, dbegin.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h->end.data(), dend.p, dend.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h->level_sum_kept.data(), dsum.p, dsum.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h->kept.data(), dkept.p, dkept.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < 2; ++k) {
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+    h->ms[k] = ms;
+  }
+  return ABN_OK;
+}
+
+static int tiles_set(abn_tiles* h, std::vector<int32_t>& chromosome, std::vector<int64_t>& start, std::vector<int64_t>& end) {
+  h->has_tiles = false;
+  h->tchromosome.swap(chromosome);
+  h->tstart.swap(start);
+  h->tend.swap(end);
+  const int rc = tiles_run(h);
+  if (rc) h->has_tiles = false;
+  return rc;
+}
+
+extern "C" int abn_tiles_set_intervals(abn_tiles* h, int64_t n_tiles, const int32_t* chromosome, const int64_t* start,
+                                       const int64_t* end) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = h->ctx;
+  if (n_tiles < 0 || (n_tiles > 0 && (!chromosome || !start || !end))) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (n_tiles > 0x7fffffffLL) return set_err(c, ABN_ERR_INVALID_ARG, "more tiles than INT32_MAX");
+  for (int64_t t = 0; t < n_tiles; ++t)
+    if (!tiles_interval_valid(chromosome[t], start[t], end[t]))
+      return set_err(c, ABN_ERR_INVALID_ARG,
+                     "tile " + std::to_string(t) + ": a chromosome outside 0..257, or a start or end outside [0, 2^32]");
+  try {
+    std::vector<int32_t> tc(chromosome, chromosome + n_tiles);
+    std::vector<int64_t> ts(start, start + n_tiles), te(end, end + n_tiles);
+    return tiles_set(h, tc, ts, te);
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+}
+
+extern "C" int abn_tiles_set_fixed(abn_tiles* h, int64_t size, int64_t step) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = h->ctx;
+  if (size <= 0 || step < 0) return set_err(c, ABN_ERR_INVALID_ARG, "a tile size of 0 or less, or a step below 0");
+  const long long T = tiles_fixed_intervals(h->runs.data(), (int)h->runs.size(), size, step, nullptr, nullptr, nullptr);
+  if (T > 0x7fffffffLL) return set_err(c, ABN_ERR_INVALID_ARG, "more tiles than INT32_MAX");
+  try {
+    std::vector<int32_t> tc((size_t)T);
+    std::vector<int64_t> ts((size_t)T), te((size_t)T);
+    tiles_fixed_intervals(h->runs.data(), (int)h->runs.size(), size, step, tc.data(), (long long*)ts.data(),
+                          (long long*)te.data());
+    return tiles_set(h, tc, ts, te);
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+}
+
+static int tiles_need(const abn_tiles* h) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (!h->has_tiles) return set_err(h->ctx, ABN_ERR_INVALID_ARG, "no tiles yet: abn_tiles_set_intervals or abn_tiles_set_fixed first");
+  return ABN_OK;
+}
+
+extern "C" int abn_tiles_intervals(const abn_tiles* h, int32_t* chromosome, int64_t* start, int64_t* end) {
+  if (int rc = tiles_need(h)) return rc;
+  if (chromosome) std::copy(h->tchromosome.begin(), h->tchromosome.end(), chromosome);
+  if (start) std::copy(h->tstart.begin(), h->tstart.end(), start);
+  if (end) std::copy(h->tend.begin(), h->tend.end(), end);
+  return ABN_OK;
+}
+
+extern "C" int abn_tiles_layout(const abn_tiles* h, int64_t* begin, int64_t* end) {
+  if (int rc = tiles_need(h)) return rc;
+  if (begin) std::copy(h->begin.begin(), h->begin.end(), begin);
+  if (end) std::copy(h->end.begin(), h->end.end(), end);
+  return ABN_OK;
+}
+
+extern "C" int abn_tiles_stats(const abn_tiles* h, int64_t* count, double* level_sum_kept, int64_t* kept) {
+  if (int rc = tiles_need(h)) return rc;
+  if (count)
+    for (size_t t = 0; t < h->begin.size(); ++t) count[t] = h->end[t] - h->begin[t];
+  if (level_sum_kept) std::copy(h->level_sum_kept.begin(), h->level_sum_kept.end(), level_sum_kept);
+  if (kept) std::copy(h->kept.begin(), h->kept.end(), kept);
+  return ABN_OK;
+}
+
+extern "C" int abn_tiles_pairwise(abn_tiles* h, uint64_t* diff, uint64_t* both, double* dvalue) {
+  if (int rc = tiles_need(h)) return rc;
+  abn_ctx* c = h->ctx;
+  const size_t n = (size_t)h->n, npairs = n * (n - 1) / 2, T = h->begin.size();
+  if (npairs == 0 || T == 0) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  return pairwise_to_host(c, T * npairs, diff, both, dvalue, [&](auto* dd, auto* db, auto* dv) {
+    return pairwise_windows_packed_dev(c, h->packed.p, h->n, h->n_columns, h->stride, h->begin.data(), h->end.data(), (int32_t)T,
+                                       dd, db, dv, nullptr);
+  });
+}
+
+extern "C" int abn_tiles_kernel_ms(const abn_tiles* h, double* ms2) {
+  if (!h || !ms2) return ABN_ERR_INVALID_ARG;
+  std::copy(h->ms, h->ms + 2, ms2);
+  return ABN_OK;
+}

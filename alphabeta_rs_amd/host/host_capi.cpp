@@ -11,7 +11,9 @@
 #include "../csrc/abn_sites_merge.hpp"
 #include "../csrc/abn_sites_common.hpp"
 #include "../csrc/abn_sites_union.hpp"
+#include "../csrc/abn_tiles.hpp"
 #include "alphabeta.hpp"
+#include "tiles.hpp"
 
 extern "C" {
 // returns the number of rows (<0 on error); rows (capacity cap x 4) and *p0uu are filled
@@ -575,6 +577,83 @@ long long abh_sites_union_serial(int n, const long long* site_off, const int* ch
   refusal[2] = r.site;
   if (text && cap > 0) std::strncpy(text, abn::union_refusal_text(r).c_str(), (size_t)cap - 1), text[cap - 1] = 0;
   return fits ? n_union : -4;
+}
+// ---- genomic tiles (csrc/abn_tiles.hpp, host/tiles.hpp), for tests/test_tiles_cpu.py
+// tiles_runs_serial of the columns' keys -> the run tables run_begin / run_end [258] and the runs in run order (capacity 258
+// each); returns n_runs, or -1 with refusal = {kind, sample, site} and the refusal's words in text (capacity cap)
+int abh_tiles_runs_serial(long long n_columns, const int* chromosome, const unsigned* start, const unsigned* end,
+                          const unsigned char* strand, long long* run_begin, long long* run_end, int* run_chromosome,
+                          long long* run_first, long long* run_count, unsigned* run_last_start, long long* refusal,
+                          char* text, long long cap) {
+  std::vector<abn::TileRun> runs;
+  abn::CommonRefusal r{0, -1, -1};
+  const bool ok = abn::tiles_runs_serial(abn::CommonSites{chromosome, start, end, strand}, n_columns, run_begin, run_end,
+                                         &runs, &r);
+  refusal[0] = r.kind, refusal[1] = r.sample, refusal[2] = r.site;
+  if (text && cap > 0) std::strncpy(text, abn::common_refusal_text(r).c_str(), (size_t)cap - 1), text[cap - 1] = 0;
+  if (!ok) return -1;
+  for (size_t k = 0; k < runs.size(); ++k) {
+    run_chromosome[k] = runs[k].chromosome, run_first[k] = runs[k].first, run_count[k] = runs[k].count;
+    run_last_start[k] = runs[k].last_start;
+  }
+  return (int)runs.size();
+}
+// tiles_fixed_intervals over a run table -> the number of tiles (-1: size <= 0 or step < 0); null outputs: only counted
+long long abh_tiles_fixed_intervals(int n_runs, const int* run_chromosome, const unsigned* run_last_start, long long size,
+                                    long long step, int* chromosome, long long* start, long long* end) {
+  std::vector<abn::TileRun> runs;
+  for (int k = 0; k < n_runs; ++k) runs.push_back(abn::TileRun{run_chromosome[k], 0, 0, run_last_start[k]});
+  return abn::tiles_fixed_intervals(runs.data(), n_runs, size, step, chromosome, start, end);
+}
+// 1 when (chromosome, start, end) is a tile abn_tiles_set_intervals takes
+int abh_tiles_interval_valid(int chromosome, long long start, long long end) {
+  return abn::tiles_interval_valid(chromosome, start, end) ? 1 : 0;
+}
+void abh_tiles_search_serial(const unsigned* start, const long long* run_begin, const long long* run_end, long long T,
+                             const int* chromosome, const long long* pos, const long long* pos_end, long long* begin,
+                             long long* end) {
+  abn::tiles_search_serial(start, run_begin, run_end, T, chromosome, pos, pos_end, begin, end);
+}
+void abh_tiles_fold_serial(const unsigned char* code, long long code_stride, const double* level, long long n_columns, int n,
+                           long long T, const long long* begin, const long long* end, double* sum, long long* kept) {
+  abn::tiles_fold_serial(code, code_stride, level, n_columns, n, T, begin, end, sum, kept);
+}
+// read_regions of a BED-like text -> the number of tiles (-1: more than cap)
+long long abh_tiles_read_regions(const char* text, long long len, long long cap, int* chromosome, long long* start,
+                                 long long* end) {
+  const alphabeta::metaprofile::TileList l = alphabeta::metaprofile::read_regions(std::string(text, (size_t)len));
+  if ((long long)l.size() > cap) return -1;
+  for (size_t k = 0; k < l.size(); ++k) chromosome[k] = l.chromosome[k], start[k] = l.start[k], end[k] = l.end[k];
+  return (long long)l.size();
+}
+// <chromosome>:<start>-<end> as results.txt spells a tile
+void abh_tiles_region(int chromosome, long long start, long long end, char* text, long long cap) {
+  std::strncpy(text, alphabeta::metaprofile::tile_region(chromosome, start, end).c_str(), (size_t)cap - 1), text[cap - 1] = 0;
+}
+// detail::convert(graph, dm) -> rows_a, and detail::rows_from(detail::convert_times(graph), dm) -> rows_b (capacity cap x 4
+// each; dm [nn x nn] as DMatrix::from fills it); *nn_out = the sampled nodes.  Returns the rows of convert, -1: a call
+// threw (the words in err), -2: they do not fit, -3: the two differ in their number of rows
+int abh_tiles_convert_both(const char* nodelist, const char* edgelist, const double* dm, int* nn_out, double* rows_a,
+                           double* rows_b, int cap, char* err, int errcap) {
+  try {
+    const alphabeta::detail::Inputs graph = alphabeta::detail::read_graph(nodelist, edgelist);
+    const size_t nn = graph.nodes.size();
+    if (nn_out) *nn_out = (int)nn;
+    if (!dm) return 0;
+    const std::vector<double> d(dm, dm + nn * nn);
+    const alphabeta::Pedigree a = alphabeta::detail::convert(graph, d);
+    const alphabeta::Pedigree b = alphabeta::detail::rows_from(alphabeta::detail::convert_times(graph), d, nn);
+    if (a.nrows() != b.nrows()) return -3;
+    if ((int)a.nrows() > cap) return -2;
+    if (a.nrows() > 0) {
+      std::memcpy(rows_a, a.data.data(), sizeof(double) * 4 * a.nrows());
+      std::memcpy(rows_b, b.data.data(), sizeof(double) * 4 * b.nrows());
+    }
+    return (int)a.nrows();
+  } catch (const std::exception& e) {
+    if (err && errcap > 0) std::strncpy(err, e.what(), (size_t)errcap - 1), err[errcap - 1] = 0;
+    return -1;
+  }
 }
 // the comparator the searches share: 1 when key a = (start, end, strand) is below key b, and 1 in *equal when they are the same
 int abh_sites_common_key_less(unsigned a_start, unsigned a_end, unsigned a_strand, unsigned b_start, unsigned b_end,

@@ -72,6 +72,20 @@ struct Win {  // a window whose pedigree was built
 };
 inline Output fit_windows(const WindowArgs& args, std::vector<Win> wins, const std::vector<int>& distribution);
 
+// results.txt (src/cli/metaprofile.rs:74-96): the header, and one window's line
+inline std::string results_header() {
+  return "run;window;cg_count;region;alpha;beta;1/2*(alpha+beta);pred_steady_state;obs_steady_state;sd_alpha;sd_beta;"
+         "ci_alpha_0.025;ci_alpha_0.975;ci_beta_0.025;ci_beta_0.975\n";
+}
+inline std::string results_line(const std::string& name, size_t window, long long cg_count, const WindowResult& r) {
+  const Model& m = r.model;
+  const Analysis& a = r.analysis;
+  return name + ";" + std::to_string(window) + ";" + std::to_string(cg_count) + ";" + r.region + ";" + fmt_f64(m.alpha) +
+         ";" + fmt_f64(m.beta) + ";" + fmt_f64(0.5 * (m.alpha + m.beta)) + ";" + fmt_f64(steady_state(m.alpha, m.beta)) + ";" +
+         fmt_f64(r.obs_meth_lvl) + ";" + fmt_f64(a.sd_alpha) + ";" + fmt_f64(a.sd_beta) + ";" + fmt_f64(a.ci_alpha.lo) + ";" +
+         fmt_f64(a.ci_alpha.hi) + ";" + fmt_f64(a.ci_beta.lo) + ";" + fmt_f64(a.ci_beta.hi) + "\n";
+}
+
 // src/cli/metaprofile.rs:33-114
 inline Output alphabeta_multiple(const WindowArgs& args, uint32_t max_gene_length, const std::vector<int>& distribution) {
   namespace fs = std::filesystem;
@@ -201,20 +215,9 @@ inline Output fit_windows(const WindowArgs& args, std::vector<Win> wins, const s
     }
   }
   // :74-96 — results zipped with `distribution`: the shorter of the two decides the number of lines
-  std::string print =
-      "run;window;cg_count;region;alpha;beta;1/2*(alpha+beta);pred_steady_state;obs_steady_state;sd_alpha;sd_beta;"
-      "ci_alpha_0.025;ci_alpha_0.975;ci_beta_0.025;ci_beta_0.975\n";
+  std::string print = results_header();
   const size_t nl = std::min(out.results.size(), distribution.size());
-  for (size_t i = 0; i < nl; ++i) {
-    const auto& r = out.results[i];
-    const Model& m = r.model;
-    const Analysis& a = r.analysis;
-    print += args.name + ";" + std::to_string(i) + ";" + std::to_string(distribution[i]) + ";" + r.region + ";" +
-             fmt_f64(m.alpha) + ";" + fmt_f64(m.beta) + ";" + fmt_f64(0.5 * (m.alpha + m.beta)) + ";" +
-             fmt_f64(steady_state(m.alpha, m.beta)) + ";" + fmt_f64(r.obs_meth_lvl) + ";" + fmt_f64(a.sd_alpha) + ";" +
-             fmt_f64(a.sd_beta) + ";" + fmt_f64(a.ci_alpha.lo) + ";" + fmt_f64(a.ci_alpha.hi) + ";" +
-             fmt_f64(a.ci_beta.lo) + ";" + fmt_f64(a.ci_beta.hi) + "\n";
-  }
+  for (size_t i = 0; i < nl; ++i) print += results_line(args.name, i, distribution[i], out.results[i]);
   out.results_txt = print;
   return out;
 }

@@ -3,12 +3,15 @@
 // (<output-dir>/{upstream,gene,downstream}/<window>/{nodelist,edgelist}.txt, as written by src/setup.rs:35-72).
 // With --methylome DIR --genome FILE --nodes FILE --edges FILE: the `extract` stage too (src/extract.rs:17-155), from
 // whole methylome files and a gene annotation, the sites placed into windows on the device and no file tree in between.
+// With --methylome DIR --nodes FILE --edges FILE and --tiles SIZE [--tile-step STEP] or --regions FILE: the rates per
+// genomic tile (tiles.hpp) — fixed bins along the genome or the rows of a BED-like list — from whole methylomes kept on the
+// device; no annotation.
 // All windows are fitted by one batched plan on the MI355X.  Flags follow src/arguments.rs:6-62 where they apply.
 #include <cstdlib>
 #include <cstring>
 #include <filesystem>
 
-#include "metaprofile.hpp"
+#include "tiles.hpp"
 
 using namespace alphabeta;
 
@@ -22,6 +25,8 @@ int main(int argc, char** argv) {
   int device = 0;
   std::string devices_arg;
   bool stream_sweep = false;
+  metaprofile::TileArgs tiles;
+  bool tiles_given = false, tile_step_given = false, parse_host = false, sites_host = false;
   for (int i = 1; i < argc; ++i) {
     const std::string f = argv[i];
     auto val = [&]() -> std::string {
@@ -57,6 +62,7 @@ int main(int argc, char** argv) {
         return 2;
       }
       a.device_parse = where == "device";
+      parse_host = !a.device_parse;
     }
     else if (f == "--genes") {
       const std::string where = val();
@@ -73,6 +79,7 @@ int main(int argc, char** argv) {
         return 2;
       }
       a.device_sites = where == "device";
+      sites_host = !a.device_sites;
     }
     else if (f == "--align") {
       const std::string how = val();
@@ -81,6 +88,18 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (f == "--tiles" || f == "--tile-step") {
+      const std::string v = val();
+      char* e = nullptr;
+      const long long n = std::strtoll(v.c_str(), &e, 10);
+      if (v.empty() || *e != 0 || n < (f == "--tiles" ? 1 : 0)) {
+        std::fprintf(stderr, "error: %s expects a number of base pairs%s\n", f.c_str(), f == "--tiles" ? " above 0" : "");
+        return 2;
+      }
+      (f == "--tiles" ? tiles.size : tiles.step) = n;
+      (f == "--tiles" ? tiles_given : tile_step_given) = true;
+    }
+    else if (f == "--regions") tiles.regions = val();
     else if (f == "-h" || f == "--help") {
       std::puts("Usage: metaprofile_alphabeta -o <output-dir> [--name N] [-s step] [-w size] [-c cutoff] [-a]\n"
                 "       [--iterations 100] [--max-gene-length L] [--distribution FILE] [--seed S] [--device D]\n"
@@ -97,6 +116,13 @@ int main(int argc, char** argv) {
                 "                            every sample all the sites any sample holds, filtered placeholders where it lacks\n"
                 "                            one; the side files then count union sites.  Either way no window is ragged (needs\n"
                 "                            --sites device) [default: none]\n"
+                "       --methylome DIR --nodes FILE --edges FILE (--tiles SIZE [--tile-step STEP] | --regions FILE)\n"
+                "                            rates per genomic tile instead of gene-relative windows: fixed tiles of SIZE bp\n"
+                "                            every STEP bp along every chromosome [STEP default: SIZE], or the regions of a\n"
+                "                            BED-like FILE (chromosome, start, end; half-open on a site's start).  Needs no\n"
+                "                            --genome; the methylomes are parsed and kept on the device; --align as above,\n"
+                "                            none expects the same sites in every methylome.  Writes results.txt (window = the\n"
+                "                            tile's index, region = chromosome:start-end), raw.npy and tiles.txt\n"
                 "       [--stream-sweep]     pedigrees too large for the LDS: read a fit's rows once per Nelder-Mead iteration\n"
                 "                            instead of once per cost evaluation; the same output files");
       return 0;
@@ -109,12 +135,27 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "error: output directory %s does not exist\n", a.output_dir.c_str());
     return 2;
   }
+  const bool tile_mode = tiles_given || tile_step_given || !tiles.regions.empty();
+  if (tile_mode) {
+    const char* refused = nullptr;
+    if (tiles_given && !tiles.regions.empty()) refused = "--tiles and --regions exclude each other";
+    else if (!tiles_given && tiles.regions.empty()) refused = "--tile-step belongs to --tiles";
+    else if (a.methylome.empty() || a.nodes.empty() || a.edges.empty()) refused = "--tiles and --regions need --methylome, --nodes and --edges";
+    else if (!a.genome.empty() || a.absolute || a.cutoff_gene_length || a.invert)
+      refused = "--genome, -a, --cutoff-gene-length and --invert do not apply to --tiles and --regions";
+    else if (parse_host || sites_host) refused = "--tiles and --regions keep the sites on the device: --parse host and --sites host do not apply";
+    if (refused) {
+      std::fprintf(stderr, "error: %s\n", refused);
+      return 2;
+    }
+    a.device_sites = true;
+  }
   const bool in_memory = !a.methylome.empty();
   if (in_memory && a.invert) {
     std::fprintf(stderr, "error: --invert is not supported with --methylome\n");
     return 2;
   }
-  if (in_memory && (a.genome.empty() || a.nodes.empty() || a.edges.empty())) {
+  if (in_memory && !tile_mode && (a.genome.empty() || a.nodes.empty() || a.edges.empty())) {
     std::fprintf(stderr, "error: --methylome needs --genome, --nodes and --edges\n");
     return 2;
   }
@@ -144,6 +185,14 @@ int main(int argc, char** argv) {
     if (device_list().empty()) device_list().push_back(device);
     dev.options.seed = seed;
     dev.stream_sweep = stream_sweep;
+    if (tile_mode) {
+      const auto res = metaprofile::alphabeta_multiple_tiles(a, tiles);
+      std::printf("%s\n", res.out.results_txt.c_str());
+      std::ofstream(std::filesystem::path(a.output_dir) / "results.txt") << res.out.results_txt;
+      std::ofstream(std::filesystem::path(a.output_dir) / "tiles.txt") << res.tiles_txt;
+      metaprofile::write_raw_npy(res.out, (std::filesystem::path(a.output_dir) / "raw.npy").string());
+      return 0;
+    }
     if (in_memory) {
       const auto ex = metaprofile::extract_in_memory(a);
       const auto out = metaprofile::alphabeta_multiple_in_memory(a, ex);

@@ -1,0 +1,209 @@
+// tiles.hpp — epimutation rates per GENOMIC TILE: the batched metaprofile fit (metaprofile.hpp: fit_windows) over fixed bins
+// of the genome (--tiles SIZE [--tile-step STEP]) or the rows of a region list (--regions FILE: a BED-like file of TEs,
+// promoters, chromatin states — the 4-column rows src/methylation_site.rs parses anticipate such lists), where the
+// reference asks one pedigree for the whole genome (src/cli/alphabeta.rs) or gene-relative windows
+// (src/cli/metaprofile.rs:33-114).  Every methylome is parsed on the device and stays there (abn_sites_parse_dev);
+// abn_tiles_* (csrc/abn_tiles.hpp) aligns them, finds every tile's columns and folds rc_meth_lvl per (sample, tile); one
+// scan gives every tile's D matrix; every tile is then a window of fit_windows, its Philox streams those of its index in
+// the tile list.  No annotation, no file tree.
+#pragma once
+
+#include "metaprofile.hpp"
+
+namespace alphabeta {
+namespace detail {
+
+// What DMatrix::convert (src/pedigree.rs:263-337) makes of the graph alone: for every row convert would emit, the pair
+// (i, j) of sampled nodes and (t0, t1, t2).  All tiles share one nodelist and edgelist, so the shortest-path searches run
+// once, not once per tile.  (convert itself on a D matrix whose entries are their own indices: the rows it emits and
+// their order are convert's by construction.)
+struct PairTimes {
+  size_t i, j;
+  double t0, t1, t2;
+};
+inline std::vector<PairTimes> convert_times(const Inputs& graph) {
+  const size_t nn = graph.nodes.size();
+  std::vector<double> where(nn * nn, 0.0);
+  for (size_t i = 0; i < nn; ++i)
+    for (size_t j = i + 1; j < nn; ++j) where[i * nn + (j - i - 1)] = (double)(i * nn + j);  // exact: far below 2^53
+  const Pedigree p = convert(graph, where);
+  std::vector<PairTimes> out;
+  for (size_t r = 0; r < p.nrows(); ++r) {
+    const size_t at = (size_t)p.at(r, 3);
+    out.push_back(PairTimes{at / nn, at % nn, p.at(r, 0), p.at(r, 1), p.at(r, 2)});
+  }
+  return out;
+}
+// convert(graph, dm), bit for bit, from convert_times(graph); nn = graph.nodes.size()
+inline Pedigree rows_from(const std::vector<PairTimes>& times, const std::vector<double>& dm, size_t nn) {
+  Pedigree ped;
+  for (const PairTimes& t : times) ped.push_row(t.t0, t.t1, t.t2, dm[t.i * nn + (t.j - t.i - 1)]);
+  return ped;
+}
+
+}  // namespace detail
+
+namespace metaprofile {
+
+struct TileArgs {
+  int64_t size = 0, step = 0;  // --tiles SIZE [--tile-step STEP]: fixed tiles (step 0: size)
+  std::string regions;         // --regions FILE: a list
+  bool fixed() const { return regions.empty(); }
+};
+
+struct TileList {
+  std::vector<int32_t> chromosome;  // Numbered(n) = n, Mitochondrial = 256, Chloroplast = 257
+  std::vector<int64_t> start, end;
+  size_t size() const { return chromosome.size(); }
+};
+
+// a tile bound: decimal digits, at most 2^32
+inline bool parse_tile_bound(const std::string& t, int64_t& v) {
+  if (t.empty() || t.size() > 10) return false;
+  int64_t acc = 0;
+  for (char ch : t) {
+    if (ch < '0' || ch > '9') return false;
+    acc = acc * 10 + (ch - '0');
+  }
+  if (acc > (int64_t)1 << 32) return false;
+  v = acc;
+  return true;
+}
+
+// A BED-like region list: fields split at tab or space, the first three are chromosome, start, end; the chromosome is
+// spelled as in a methylome (src/methylation_site.rs:55-68: `chr` stripped, M, C, a number up to 255).  A line that does
+// not parse (a header, `track`, `#`) is skipped; the tiles keep the file's order.
+inline TileList read_regions(const std::string& text) {
+  TileList out;
+  for (std::string line : detail::split_any(text, "\n")) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    std::vector<std::string> f;
+    for (const std::string& t : detail::split_any(line, "\t "))
+      if (!t.empty()) f.push_back(t);
+    int key;
+    int64_t a, b;
+    if (f.size() < 3 || !windows::parse_chromosome_key(f[0], key) || !parse_tile_bound(f[1], a) || !parse_tile_bound(f[2], b))
+      continue;
+    out.chromosome.push_back(key);
+    out.start.push_back(a);
+    out.end.push_back(b);
+  }
+  return out;
+}
+
+inline std::string chromosome_name(int32_t c) { return c == 256 ? "M" : (c == 257 ? "C" : std::to_string(c)); }
+inline std::string tile_region(int32_t c, int64_t start, int64_t end) {
+  return chromosome_name(c) + ":" + std::to_string(start) + "-" + std::to_string(end);
+}
+
+struct TilesOutput {
+  Output out;             // results_txt: `window` = the tile's index in the list, `cg_count` = the tile's columns
+  std::string tiles_txt;  // tile;chromosome;start;end;cg_count;fitted, every tile of the list
+};
+
+class TilesHandle {  // RAII abn_tiles
+ public:
+  TilesHandle() = default;
+  TilesHandle(const TilesHandle&) = delete;
+  TilesHandle& operator=(const TilesHandle&) = delete;
+  ~TilesHandle() {
+    if (h) abn_tiles_destroy(h);
+  }
+  abn_tiles* h = nullptr;
+};
+
+// The sibling of alphabeta_multiple_in_memory for tiles.  args: methylome (directory), nodes, edges, align, iterations,
+// posterior_max_filter, name.  A tile without a column, with a sampled node that has no counted site, or with a sampled
+// pair that shares no compared site is reported and skipped; the others go on (src/cli/metaprofile.rs:64-65).
+inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileArgs& tiles) {
+  namespace fs = std::filesystem;
+  Device& dev = default_device();
+  const detail::Inputs graph = read_graph(args.nodes, args.edges);
+  const size_t nn = graph.nodes.size(), npairs = nn * (nn - 1) / 2;
+  if (nn == 0) throw Error(ABN_ERR_INVALID_ARG, "the nodelist names no sampled node");
+  TileList list;
+  if (!tiles.fixed()) {
+    list = read_regions(detail::read_file(tiles.regions, "regions"));
+    if (list.size() == 0) throw Error(ABN_ERR_INVALID_ARG, "Could not parse a single region from " + tiles.regions);
+  }
+  auto base_name = [](const std::string& p) { return p.substr(p.find_last_of('/') == std::string::npos ? 0 : p.find_last_of('/') + 1); };
+  // every sampled node's methylome, every line read (src/pedigree.rs:147-163), its records left on the device
+  std::vector<windows::ResidentSites> sites;
+  std::vector<std::string> names;
+  for (const auto& node : graph.nodes) {
+    names.push_back(base_name(node.file));
+    const std::string path = (fs::path(args.methylome) / names.back()).string();
+    if (!std::ifstream(path)) throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " + path);
+    sites.push_back(windows::parse_sites_resident(dev, detail::read_file(path, "methylome"), /*skip_lines=*/0));
+  }
+  std::vector<abn_sites*> handles;
+  for (const auto& s : sites) handles.push_back(s.get());
+  TilesHandle th;
+  const int32_t align = args.align == Align::Union ? 2 : (args.align == Align::Position ? 1 : 0);
+  dev.check(abn_tiles_create(dev.get(), args.posterior_max_filter, align, (int32_t)nn, handles.data(), &th.h), "abn_tiles_create");
+  int64_t n_columns = 0;
+  abn_tiles_info(th.h, nullptr, &n_columns, nullptr, nullptr, nullptr);
+  if (args.align == Align::Position)
+    for (size_t s = 0; s < nn; ++s)
+      std::printf("Aligned by position: %s: %lld sites, %lld kept\n", names[s].c_str(), (long long)sites[s].size(), (long long)n_columns);
+  if (args.align == Align::Union)
+    for (size_t s = 0; s < nn; ++s)
+      std::printf("Aligned by union: %s: %lld sites, %lld in the union\n", names[s].c_str(), (long long)sites[s].size(),
+                  (long long)n_columns);
+  if (tiles.fixed())
+    dev.check(abn_tiles_set_fixed(th.h, tiles.size, tiles.step), "abn_tiles_set_fixed");
+  else
+    dev.check(abn_tiles_set_intervals(th.h, (int64_t)list.size(), list.chromosome.data(), list.start.data(), list.end.data()),
+              "abn_tiles_set_intervals");
+  int64_t n_tiles = 0;
+  abn_tiles_info(th.h, nullptr, nullptr, nullptr, nullptr, &n_tiles);
+  const size_t T = (size_t)n_tiles;
+  if (T == 0) throw Error(ABN_ERR_INVALID_ARG, "no tile: the methylomes hold no site");
+  list.chromosome.resize(T), list.start.resize(T), list.end.resize(T);
+  dev.check(abn_tiles_intervals(th.h, list.chromosome.data(), list.start.data(), list.end.data()), "abn_tiles_intervals");
+  std::vector<int64_t> count(T), kept(nn * T);
+  std::vector<double> sum(nn * T), dv(std::max<size_t>(T * npairs, 1), 0.0);
+  std::vector<uint64_t> both(std::max<size_t>(T * npairs, 1), 0);
+  dev.check(abn_tiles_stats(th.h, count.data(), sum.data(), kept.data()), "abn_tiles_stats");
+  dev.check(abn_tiles_pairwise(th.h, nullptr, both.data(), dv.data()), "abn_tiles_pairwise");
+
+  const std::vector<detail::PairTimes> times = detail::convert_times(graph);
+  std::vector<Win> wins;
+  for (size_t t = 0; t < T; ++t) {
+    const std::string region = tile_region(list.chromosome[t], list.start[t], list.end[t]);
+    try {
+      if (count[t] == 0) throw Error(ABN_ERR_INVALID_ARG, "no site lies in this tile");
+      double p0 = 0.0;
+      for (size_t a = 0; a < nn; ++a) {
+        if (kept[a * T + t] == 0)
+          throw Error(ABN_ERR_INVALID_ARG, names[a] + " has no site above the posterior filter in this tile");
+        p0 += 1.0 - sum[a * T + t] / (double)kept[a * T + t];  // src/pedigree.rs:165-166, 180-184
+      }
+      for (size_t a = 0, p = 0; a < nn; ++a)
+        for (size_t b = a + 1; b < nn; ++b, ++p)
+          if (both[t * npairs + p] == 0)
+            throw Error(ABN_ERR_INVALID_ARG, names[a] + " and " + names[b] + " share no site above the posterior filter in this tile");
+      Pedigree ped = detail::rows_from(times, detail::dmatrix_of_pairs(nn, &dv[t * npairs]), nn);
+      if (ped.nrows() == 0) throw Error(ABN_ERR_BAD_PEDIGREE, "empty pedigree");
+      wins.push_back(Win{region, std::move(ped), p0 / (double)nn, t});
+    } catch (const std::exception& e) {
+      std::printf("Error: Error while building pedigree: tile %zu (%s): %s\n", t, region.c_str(), e.what());
+    }
+  }
+  TilesOutput res;
+  res.out = fit_windows(args, std::move(wins), std::vector<int>());
+  std::vector<char> fitted(T, 0);
+  res.out.results_txt = results_header();
+  for (const WindowResult& r : res.out.results) {
+    fitted[r.window_index] = 1;
+    res.out.results_txt += results_line(args.name, r.window_index, (long long)count[r.window_index], r);
+  }
+  res.tiles_txt = "tile;chromosome;start;end;cg_count;fitted\n";
+  for (size_t t = 0; t < T; ++t)
+    res.tiles_txt += std::to_string(t) + ";" + chromosome_name(list.chromosome[t]) + ";" + std::to_string(list.start[t]) + ";" +
+                     std::to_string(list.end[t]) + ";" + std::to_string(count[t]) + ";" + (fitted[t] ? "1" : "0") + "\n";
+  return res;
+}
+
+}  // namespace metaprofile
+}  // namespace alphabeta

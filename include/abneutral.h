@@ -614,6 +614,47 @@ int abn_codes_create_union(abn_ctx* ctx, double posterior_max_filter, int32_t n_
 int abn_windows_union(const abn_windows* h, int64_t* before /* int64[n] */, int64_t* n_union, double* ms /* double[8] */);
 int abn_codes_union(const abn_codes* h, int64_t* before /* int64[n] */, int64_t* n_union, double* ms /* double[8] */);
 
+/* Genomic tiles: Pedigree::build (src/pedigree.rs:147-172, :210-261) once per tile of the genome — a fixed bin, or a row of
+ * a region list such as the chromatin-state rows src/cli/metaprofile.rs:50-72 reads — over resident parse results.  The
+ * handle does what abn_codes_create_parsed / _aligned / _union do (align 0 none, 1 position, 2 union) and keeps, beside the
+ * packed matrix, the columns' keys (chromosome, start: one copy, all samples share them after the alignment), every
+ * sample's merged bytes and levels, and the chromosome runs of the columns.  align 0 is the reference's assumption
+ * (src/pedigree.rs:240): the keys are sample 0's, every sample must have sample 0's number of sites
+ * (ABN_ERR_INVALID_ARG, the text names --align), and sample 0 must be well ordered (the refusals of abn_sites_common).
+ * Arguments and errors otherwise as abn_codes_create_parsed.
+ *
+ * A tile is (chromosome 0..257, start, end) with start, end in [0, 2^32], half-open on a site's start; the strand is no
+ * part of it.  Its columns [begin, end) come from two lower bounds inside the chromosome's run; begin = end for a
+ * chromosome without a run, for end <= start, and behind the last site.  abn_tiles_set_intervals takes a list,
+ * abn_tiles_set_fixed makes one from the runs: for every run in run order the tiles k = 0 .. ceil((last_start + 1) / step)
+ * - 1, [k step, k step + size) (step 0: size; the end capped at 2^32; tiles overlap when step < size).  Either runs the
+ * search and the per-(sample, tile) folds on the device, may be called again (the new list replaces the old) and refuses
+ * with ABN_ERR_INVALID_ARG: null pointers, n_tiles < 0, a chromosome outside 0..257, a bound outside [0, 2^32], size <= 0,
+ * step < 0, more tiles than INT32_MAX.  The getters of tiles refuse before any set_*.
+ *
+ * abn_tiles_stats: count [T] = the tile's columns; level_sum_kept, kept [n x T] = the fold of src/pedigree.rs:159-172 over
+ * the tile's sites of the sample alone, bit for bit (a union placeholder is filtered and not counted).
+ * abn_tiles_pairwise: abn_pairwise_divergence_windows_packed_dev over the tiles' column ranges, host outputs [T x pairs]
+ * (any may be NULL; fewer than two samples: nothing is written).  abn_tiles_kernel_ms: double[2], the HIP-event times of
+ * the last set_*'s search and fold. */
+typedef struct abn_tiles abn_tiles;
+int abn_tiles_create(abn_ctx* ctx, double posterior_max_filter, int32_t align /* 0 none, 1 position, 2 union */,
+                     int32_t n_samples, abn_sites* const* samples, abn_tiles** out);
+int abn_tiles_destroy(abn_tiles* h);
+int abn_tiles_info(const abn_tiles* h, int32_t* n_samples, int64_t* n_columns, int64_t* row_stride_bytes, int32_t* n_runs,
+                   int64_t* n_tiles /* -1 before any set_* */);
+/* the runs in run order, [n_runs] each: chromosome, first column, columns, the start of the last column */
+int abn_tiles_runs(const abn_tiles* h, int32_t* chromosome, int64_t* first, int64_t* count, uint32_t* last_start);
+int abn_tiles_set_intervals(abn_tiles* h, int64_t n_tiles, const int32_t* chromosome, const int64_t* start,
+                            const int64_t* end);
+int abn_tiles_set_fixed(abn_tiles* h, int64_t size, int64_t step /* 0: size */);
+int abn_tiles_intervals(const abn_tiles* h, int32_t* chromosome, int64_t* start, int64_t* end); /* [n_tiles] */
+int abn_tiles_layout(const abn_tiles* h, int64_t* begin, int64_t* end);                         /* [n_tiles] */
+int abn_tiles_stats(const abn_tiles* h, int64_t* count /* [T] */, double* level_sum_kept /* [n x T] */,
+                    int64_t* kept /* [n x T] */);
+int abn_tiles_pairwise(abn_tiles* h, uint64_t* diff, uint64_t* both, double* dvalue); /* host, [T x pairs] */
+int abn_tiles_kernel_ms(const abn_tiles* h, double* ms2 /* search, fold */);
+
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
  * src/cli/metaprofile.rs:50-72, where every window shares nodelist/edgelist), S starts and B bootstraps

@@ -1,0 +1,239 @@
+"""Genomic tiles without a device: the serial forms of alphabeta_rs_amd/csrc/abn_tiles.hpp (the run table, the tile search,
+the per-(sample, tile) folds, the fixed-tile generator) through the host shim against the Python model of
+tests/_tiles_model.py on the inputs the device tests use; the BED-like region reader and the region's spelling of
+host/tiles.hpp; detail::convert_times + rows_from against detail::convert on the bundled nodelist and edgelist; and the
+stand-alone driver tests/native/tiles_main.cpp, plain and under AddressSanitizer + UndefinedBehaviorSanitizer."""
+import ctypes as C
+import shutil
+import struct
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import _tiles_model as T
+import _windows_model as M
+
+ROOT = Path(__file__).resolve().parent.parent
+GOLDEN = ROOT / "tests" / "golden"
+ALIGNS = ("none", "position", "union")
+
+
+@pytest.fixture(scope="module")
+def L():
+    L = M.hostlib()
+    ll, i32p, u32p, u8p, dp = C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
+    llp = C.POINTER(ll)
+    L.abh_tiles_runs_serial.argtypes = [ll, i32p, u32p, u32p, u8p, llp, llp, i32p, llp, llp, u32p, llp, C.c_char_p, ll]
+    L.abh_tiles_fixed_intervals.argtypes = [C.c_int, i32p, u32p, ll, ll, i32p, llp, llp]
+    L.abh_tiles_fixed_intervals.restype = ll
+    L.abh_tiles_interval_valid.argtypes = [C.c_int, ll, ll]
+    L.abh_tiles_search_serial.argtypes = [u32p, llp, llp, ll, i32p, llp, llp, llp, llp]
+    L.abh_tiles_search_serial.restype = None
+    L.abh_tiles_fold_serial.argtypes = [u8p, ll, dp, ll, C.c_int, ll, llp, llp, dp, llp]
+    L.abh_tiles_fold_serial.restype = None
+    L.abh_tiles_read_regions.argtypes = [C.c_char_p, ll, ll, i32p, llp, llp]
+    L.abh_tiles_read_regions.restype = ll
+    L.abh_tiles_region.argtypes = [C.c_int, ll, ll, C.c_char_p, ll]
+    L.abh_tiles_region.restype = None
+    L.abh_tiles_convert_both.argtypes = [C.c_char_p, C.c_char_p, dp, i32p, dp, dp, C.c_int, C.c_char_p, C.c_int]
+    return L
+
+
+def ptr(a, t):
+    return a.ctypes.data_as(t)
+
+
+def serial_runs(L, chrom, start, end=None, strand=None):
+    """abh_tiles_runs_serial -> (run_begin, run_end, runs as the model lists them) or (refusal, text)"""
+    n = len(chrom)
+    chrom, start = np.ascontiguousarray(chrom, dtype=np.int32), np.ascontiguousarray(start, dtype=np.uint32)
+    end = start.copy() if end is None else np.ascontiguousarray(end, dtype=np.uint32)
+    strand = np.zeros(n, dtype=np.uint8) if strand is None else np.ascontiguousarray(strand, dtype=np.uint8)
+    rb, re = np.zeros(258, dtype=np.int64), np.zeros(258, dtype=np.int64)
+    rc, rl = np.zeros(258, dtype=np.int32), np.zeros(258, dtype=np.uint32)
+    rf, rn, refusal = np.zeros(258, dtype=np.int64), np.zeros(258, dtype=np.int64), np.zeros(3, dtype=np.int64)
+    text = C.create_string_buffer(256)
+    t = L.abh_tiles_runs_serial.argtypes
+    k = L.abh_tiles_runs_serial(n, ptr(chrom, t[1]), ptr(start, t[2]), ptr(end, t[3]), ptr(strand, t[4]), ptr(rb, t[5]),
+                                ptr(re, t[6]), ptr(rc, t[7]), ptr(rf, t[8]), ptr(rn, t[9]), ptr(rl, t[10]), ptr(refusal, t[11]),
+                                text, len(text))
+    if k < 0:
+        return refusal.tolist(), text.value.decode()
+    return rb, re, [(int(rc[i]), int(rf[i]), int(rn[i]), int(rl[i])) for i in range(k)]
+
+
+def serial_search(L, start, rb, re, tiles):
+    chrom, lo, hi = (np.ascontiguousarray(a, dtype=d) for a, d in zip(tiles, (np.int32, np.int64, np.int64)))
+    start = np.ascontiguousarray(start, dtype=np.uint32)
+    begin, end = np.full(len(chrom), -7, dtype=np.int64), np.full(len(chrom), -7, dtype=np.int64)
+    t = L.abh_tiles_search_serial.argtypes
+    L.abh_tiles_search_serial(ptr(start, t[0]), ptr(rb, t[1]), ptr(re, t[2]), len(chrom), ptr(chrom, t[4]), ptr(lo, t[5]),
+                              ptr(hi, t[6]), ptr(begin, t[7]), ptr(end, t[8]))
+    return begin, end
+
+
+def serial_fixed(L, runs, size, step):
+    rc, rl = np.array([r[0] for r in runs], dtype=np.int32), np.array([r[3] for r in runs], dtype=np.uint32)
+    t = L.abh_tiles_fixed_intervals.argtypes
+    n = L.abh_tiles_fixed_intervals(len(runs), ptr(rc, t[1]), ptr(rl, t[2]), size, step, None, None, None)
+    if n < 0:
+        return n
+    chrom, lo, hi = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    assert L.abh_tiles_fixed_intervals(len(runs), ptr(rc, t[1]), ptr(rl, t[2]), size, step, ptr(chrom, t[5]), ptr(lo, t[6]),
+                                       ptr(hi, t[7])) == n
+    return chrom, lo, hi
+
+
+def test_serial_forms_equal_the_model(L):
+    rows = T.master_sites()
+    n = 4
+    values = [T.sample_values(rows, 40 + s, nan_at=700 if s == 1 else None) for s in range(n)]
+    explicit, names = T.tile_list(rows)
+    seen = set()
+    for align in ALIGNS:
+        rng = np.random.default_rng(5)
+        keeps = [list(range(len(rows)))] * n if align == "none" else \
+            [sorted(set(range(len(rows))) - set(rng.choice(699, size=9, replace=False).tolist())) for _ in range(n)]   # (700 stays)
+        chrom, start, strand, cols = T.aligned(rows, values, keeps, align)
+        rb, re, runs = serial_runs(L, chrom, start, strand=strand)
+        assert runs == T.runs_of(chrom, start) and [r[0] for r in runs] == [2, 1, 257]     # run order, not key order
+        for tiles in (explicit, T.fixed_intervals(runs, 1 << 28), T.fixed_intervals(runs, 1 << 30, 1 << 29)):   # (overlapping)
+            begin, end = serial_search(L, start, rb, re, tiles)
+            want_b, want_e = T.search(chrom, start, tiles)
+            assert begin.tolist() == want_b.tolist() and end.tolist() == want_e.tolist(), align
+            assert np.all((0 <= begin) & (begin <= end) & (end <= len(chrom)))
+            ncol, stride = len(chrom), (len(chrom) + 15) // 16 * 16
+            code = np.full((n, stride), 0x7f, dtype=np.uint8)                             # (the padding must not be read)
+            level = np.zeros((n, ncol))
+            for s, c in enumerate(cols):
+                code[s, :ncol], level[s] = c["code"], c["level"]
+            sums, kept = np.full((n, len(begin)), -1.0), np.full((n, len(begin)), -1, dtype=np.int64)
+            t = L.abh_tiles_fold_serial.argtypes
+            L.abh_tiles_fold_serial(ptr(code, t[0]), stride, ptr(level, t[2]), ncol, n, len(begin), ptr(begin, t[6]), ptr(end, t[7]),
+                                    ptr(sums, t[8]), ptr(kept, t[9]))
+            want_sums, want_kept = T.folds(cols, begin, end)
+            assert kept.tolist() == want_kept.tolist(), align
+            assert [[struct.pack("<d", v) for v in row] for row in sums] == want_sums, align
+            if align == "none" and tiles is explicit:
+                seen = set((end - begin).tolist())
+                assert (begin % 16 != 0).any() and (begin % 64 != 0).any() and 0 in begin.tolist()
+                assert end[names.index("run's last column")] == runs[0][2] and begin[names.index("C from 0")] == runs[2][1]
+                assert (end - begin)[names.index("up to 2^32")] >= 1 and (end - begin)[names.index("both strands")] == 2
+                assert (end - begin)[names.index("over the gap")] == 20       # on both sides of the gap
+        if align == "union":                                                  # a placeholder: filtered, and not counted
+            lacking = [i for i in range(len(chrom)) if any(c["code"][i] == 0x80 for c in cols)]
+            assert len(lacking) >= 20
+    assert {0, 1, 63, 64, 65, 200} <= seen, sorted(seen)
+    nan_col = cols[1]                                                          # the NaN posterior: the predicates differ
+    assert any(not c and f < 3 for c, f in zip(nan_col["counted"].tolist(), nan_col["field"].tolist()))
+
+
+def test_fixed_tile_generator(L):
+    small = [(2, 0, 10, 5200), (1, 10, 4, 0), (257, 14, 3, 999)]
+    big = [(7, 0, 2, 12345), (257, 2, 3, T.LAST)]                             # a run that ends at the highest start
+    cases = [(small, size, step) for size, step in ((100, 0), (100, 30), (30, 100), (5201, 0), (5200, 0), (1, 2600), (100, 1 << 62))] + \
+        [(big, size, step) for size, step in ((1 << 31, 0), (3 << 30, 1 << 30), (1 << 28, 0), (1 << 32, 1 << 31))]
+    for runs, size, step in cases:
+        got, want = serial_fixed(L, runs, size, step), T.fixed_intervals(runs, size, step)
+        assert all(g.tolist() == w.tolist() for g, w in zip(got, want)), (size, step)
+        chrom, lo, hi = got
+        st = step or size
+        per_run = [int((chrom == c).sum()) for c, *_ in runs]
+        assert per_run == [-(-(last + 1) // st) for *_, last in runs]
+        assert hi.max() <= T.POS_END and (hi > lo).all()
+        assert all(L.abh_tiles_interval_valid(*t) for t in zip(chrom.tolist(), lo.tolist(), hi.tolist()))
+        for c, _, _, last in runs:                                            # the run's last site lies in its last tile
+            assert lo[chrom == c].max() <= last and (size < st or last < hi[chrom == c].max())
+        if runs is small:
+            assert per_run[1] == 1                                            # a run whose only start is 0
+        else:
+            assert hi.max() == T.POS_END or size == 1 << 28                   # the end is capped, never wraps
+    runs = small
+    assert serial_fixed(L, runs, 0, 0) == -1 and serial_fixed(L, runs, -5, 0) == -1 and serial_fixed(L, runs, 5, -1) == -1
+    assert serial_fixed(L, [], 100, 0)[0].shape == (0,)
+    for bad in ((258, 0, 1), (-1, 0, 1), (0, -1, 1), (0, 0, T.POS_END + 1), (0, T.POS_END + 1, 5)):
+        assert not L.abh_tiles_interval_valid(*bad)
+    assert L.abh_tiles_interval_valid(257, T.POS_END, 0) and L.abh_tiles_interval_valid(0, 0, 0)
+
+
+def test_order_refusals(L):
+    refusal, text = serial_runs(L, [2, 2, 1, 2], [5, 9, 1, 20])
+    assert refusal == [1, 0, 3] and "split run" in text
+    refusal, text = serial_runs(L, [2, 2, 1, 1], [5, 5, 1, 2])
+    assert refusal == [2, 0, 1] and "not ascending" in text
+    refusal, text = serial_runs(L, [2, 300, 1, 1], [5, 6, 1, 2])
+    assert refusal == [3, 0, 1] and "0..257" in text
+    rb, re, runs = serial_runs(L, [2, 2, 1, 1], [5, 5, 1, 2], strand=[0, 1, 0, 0])           # both strands at one start
+    assert runs == [(2, 0, 2, 5), (1, 2, 2, 2)]
+    assert serial_runs(L, [], [])[2] == []
+
+
+def test_region_reader(L):
+    text = ("track name=TEs\n# a comment\nchrom\tstart\tend\n"
+            "chr1\t100\t200\tTE1\t0\t+\n"
+            "2 300 250\n"                                   # space-separated; end < start is kept (an empty tile)
+            "chrM\t0\t4294967296\r\n"
+            "C\t7\t9\n"
+            "chrchr255  10\t\t20\n"                          # runs of separators
+            "256\t1\t2\n"                                    # no chromosome
+            "X\t1\t2\n"
+            "1\t-5\t2\n1\t5\t4294967297\n1\t5\n1\t+5\t7\n1\t1e3\t2000\n"
+            "3\t5\t6")                                       # no line end
+    cap = 32
+    chrom, lo, hi = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64)
+    t = L.abh_tiles_read_regions.argtypes
+    n = L.abh_tiles_read_regions(text.encode(), len(text.encode()), cap, ptr(chrom, t[3]), ptr(lo, t[4]), ptr(hi, t[5]))
+    assert n == 6
+    assert list(zip(chrom[:n].tolist(), lo[:n].tolist(), hi[:n].tolist())) == [
+        (1, 100, 200), (2, 300, 250), (256, 0, 1 << 32), (257, 7, 9), (255, 10, 20), (3, 5, 6)]
+    assert L.abh_tiles_read_regions(b"", 0, cap, ptr(chrom, t[3]), ptr(lo, t[4]), ptr(hi, t[5])) == 0
+    assert L.abh_tiles_read_regions(text.encode(), len(text.encode()), 2, ptr(chrom, t[3]), ptr(lo, t[4]), ptr(hi, t[5])) == -1
+    buf = C.create_string_buffer(64)
+    for key, want in ((1, "1:100-200"), (256, "M:100-200"), (257, "C:100-200")):
+        L.abh_tiles_region(key, 100, 200, buf, len(buf))
+        assert buf.value.decode() == want
+
+
+def test_convert_times_and_rows_from_equal_convert(L, tmp_path):
+    nodes, edges = str(GOLDEN / "data" / "nodelist.txt").encode(), str(GOLDEN / "data" / "edgelist.txt").encode()
+    nn = C.c_int()
+    err = C.create_string_buffer(256)
+    assert L.abh_tiles_convert_both(nodes, edges, None, C.byref(nn), None, None, 0, err, len(err)) == 0 and nn.value == 4
+    rng = np.random.default_rng(3)
+    dp = C.POINTER(C.c_double)
+    for case in range(4):
+        dm = rng.random((4, 4))
+        if case == 1:
+            dm[0, 1], dm[1, 0] = np.nan, -0.0
+        a, b = np.full((16, 4), -1.0), np.full((16, 4), -2.0)
+        n = L.abh_tiles_convert_both(nodes, edges, ptr(dm, dp), None, ptr(a, dp), ptr(b, dp), 16, err, len(err))
+        assert n == 6, err.value
+        assert a[:n].tobytes() == b[:n].tobytes()
+        assert a[:n, 3].tobytes() == np.concatenate([dm[i, :3 - i] for i in range(3)]).tobytes()   # DMatrix::from's entries
+    # a sparser graph: a sampled node no edge reaches has no row in either
+    sparse_nodes = tmp_path / "nodelist.txt"
+    sparse_nodes.write_text((GOLDEN / "data" / "nodelist.txt").read_text() + "\n-,9_9,2,Y\n")
+    dm = rng.random((5, 5))
+    a, b = np.zeros((16, 4)), np.ones((16, 4))
+    n = L.abh_tiles_convert_both(str(sparse_nodes).encode(), edges, ptr(dm, dp), C.byref(nn), ptr(a, dp), ptr(b, dp), 16, err, len(err))
+    assert nn.value == 5 and n == 6 and a[:n].tobytes() == b[:n].tobytes()
+
+
+@pytest.mark.parametrize("sanitize", [False, True])
+def test_standalone_driver(tmp_path, sanitize):
+    """tests/native/tiles_main.cpp, a program of its own (nothing is loaded into Python): plain, and with
+    -fsanitize=address,undefined, every array in a heap block of exactly its length"""
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.fail("g++ is needed for tests/native/tiles_main.cpp")
+    exe = tmp_path / "tiles_main"
+    flags = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if sanitize else []
+    r = subprocess.run([gxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", *flags, "-o", str(exe),
+                        str(ROOT / "tests" / "native" / "tiles_main.cpp")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
+                       env={"UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1", "ASAN_OPTIONS": "abort_on_error=1"})
+    assert r.returncode == 0 and "tiles serial forms ok" in r.stdout, r.stdout[-1500:] + r.stderr[-4000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
