@@ -17,6 +17,7 @@ LIB = PKG / "libabneutral_hip.so"
 SOURCES = [CSRC / "abn_api.hip", CSRC / "abn_pairwise.hip", CSRC / "abn_windows.hip", CSRC / "abn_analyze.hip",
            CSRC / "abn_multi.hip", CSRC / "abn_sites.hip", CSRC / "abn_genes.hip", CSRC / "abn_codes.hip",
            CSRC / "abn_sites_common.hip", CSRC / "abn_sites_union.hip", CSRC / "abn_tiles.hip",
+           CSRC / "abn_resident.hip",  # host-only too: what the builders from resident parse results share
            CSRC / "abn_pack.cpp"]  # host-only: the packed code format (also built alone under the host sanitizers)
 DEPS = [*sorted(CSRC.glob("*.hpp")), CSRC / "abn_philox.h", PKG.parent / "include" / "abneutral.h"]
 HIPCC_FLAGS = [

@@ -2,7 +2,8 @@
 // behind from_methylome_file_line, and the status bytes DMatrix::from reads, :210-261).  Kernels and arithmetic:
 // abn_codes.hpp; the merge launches are abn_sites.hip's (the records are its handle's), the scan abn_pairwise.hip's, the
 // common-site step of abn_codes_create_aligned abn_sites_common.hip's, the union step of abn_codes_create_union
-// abn_sites_union.hip's.
+// abn_sites_union.hip's; the handles' refusals, the merge loops and the alignment's dispatch are abn_resident.hip's, shared
+// with abn_windows.hip and abn_tiles.hip.
 #include "abn_host.hpp"
 #define ABN_CODES_KERNELS
 #include "abn_codes.hpp"
@@ -18,11 +19,7 @@ struct abn_codes {
   std::vector<int64_t> count, kept;  // [n]
   std::vector<double> level_sum_kept;
   double ms[4] = {0.0, 0.0, 0.0, 0.0};  // merge records, merge inserted, pack, fold
-  std::vector<int64_t> before;          // [n]: every sample's sites as they came (abn_codes_common)
-  int64_t n_common = -1;                // abn_codes_create_aligned: the sites every sample keeps
-  double common_ms[4] = {0.0, 0.0, 0.0, 0.0};
-  int64_t n_union = -1;                 // abn_codes_create_union: the sites every sample has, placeholders included
-  double union_ms[kUnionPasses] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  AlignReport report;                   // abn_codes_common, abn_codes_union
   DevBuf<uint8_t> packed;               // [n x stride], device-resident between calls
 };
 
@@ -43,41 +40,19 @@ int abn::codes_pack_dev(abn_ctx* c, const uint8_t* dcode, const long long* dcode
 static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, int align) {
   abn_ctx* c = h->ctx;
   const int n = h->n;
-  DevBuf<int32_t> mchrom;
-  DevBuf<uint32_t> mstart, mend;
-  DevBuf<uint8_t> mstrand, mcode;
-  DevBuf<double> mlevel;
-  CommonState st;
-  UnionState ust;
-  std::vector<int64_t> merged_off((size_t)n + 1, 0);
+  const int64_t* before = h->report.before.data();
+  // the prologue and the alignment: the keyed merge, untimed (ms has no slot for it), and the match or the ranks
+  MergedSites m;
+  Alignment a;
   if (align) {
-    for (int s = 0; s < n; ++s) merged_off[(size_t)s + 1] = merged_off[(size_t)s] + h->count[(size_t)s];
-    const size_t S = (size_t)merged_off[(size_t)n];
-    HIPCHK(c, mchrom.alloc(S));
-    HIPCHK(c, mstart.alloc(S));
-    HIPCHK(c, mend.alloc(S));
-    HIPCHK(c, mstrand.alloc(S));
-    HIPCHK(c, mcode.alloc(S));
-    HIPCHK(c, mlevel.alloc(S));
-    for (int pass = 0; pass < 2; ++pass)
-      for (int s = 0; s < n; ++s) {
-        const size_t o = (size_t)merged_off[(size_t)s];
-        if (h->count[(size_t)s] == 0) continue;
-        if (int rc = sites_merge_dev(samples[s], pass == 1, filter, mchrom.p + o, mstart.p + o, mend.p + o, mstrand.p + o,
-                                     mcode.p + o, mlevel.p + o))
-          return rc;
-      }
-    const CommonSites keys{mchrom.p, mstart.p, mend.p, mstrand.p};
-    if (int rc = align == kAlignUnion ? sites_union_rank(c, n, merged_off.data(), keys, nullptr, ust)
-                                      : sites_common_match(c, n, merged_off.data(), keys, nullptr, st))
-      return rc;
-    const int64_t each = align == kAlignUnion ? ust.n_union : st.n_common;
-    (align == kAlignUnion ? h->n_union : h->n_common) = each;
-    h->count.assign((size_t)n, each);  // from here on the handle is one of n samples of n_common (n_union) sites
-    h->max_sites = each;
+    if (int rc = m.alloc(c, n, before)) return rc;
+    if (int rc = m.merge_keyed(c, samples, filter, nullptr)) return rc;
+    if (int rc = sites_align(c, align, n, m.off.data(), m.keys(), a)) return rc;
+    h->count.assign((size_t)n, a.each);  // from here on the handle is one of n samples of n_common (n_union) sites
+    h->max_sites = a.each;
     h->same_len = true;
   }
-  std::vector<long long> site_off((size_t)n + 1, 0), code_off((size_t)n + 1, 0);
+  std::vector<int64_t> site_off((size_t)n + 1, 0), code_off((size_t)n + 1, 0);
   for (int s = 0; s < n; ++s) {
     site_off[(size_t)s + 1] = site_off[(size_t)s] + h->count[(size_t)s];
     code_off[(size_t)s + 1] = code_off[(size_t)s] + (h->count[(size_t)s] + 15) / 16 * 16;  // whole 16-byte loads of the pack
@@ -90,6 +65,7 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, i
   DevBuf<uint8_t> dcode;
   DevBuf<double> dlevel, dsum;
   DevBuf<long long> dsite_off, dcode_off, dkept;
+  static_assert(sizeof(long long) == sizeof(int64_t), "the offsets on the device");
   HIPCHK(c, dcode.alloc(std::max<size_t>((size_t)code_off[(size_t)n], 16)));
   HIPCHK(c, dlevel.alloc(std::max<size_t>((size_t)site_off[(size_t)n], 1)));
   HIPCHK(c, dsite_off.alloc((size_t)n + 1));
@@ -100,49 +76,33 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, i
   HIPCHK(c, hipMemcpyAsync(dsite_off.p, site_off.data(), dsite_off.bytes(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(dcode_off.p, code_off.data(), dcode_off.bytes(), hipMemcpyHostToDevice, c->stream));
 
-  struct Events {
-    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } ev;
-  for (int k = 0; k < 5; ++k) HIPCHK(c, hipEventCreate(&ev.e[k]));
-  for (int pass = 0; pass < 2; ++pass) {  // the fields kernels of every sample, then the insert kernels
-    HIPCHK(c, hipEventRecord(ev.e[pass], c->stream));
-    for (int s = 0; s < n; ++s) {
-      if (h->before[(size_t)s] == 0) continue;
-      if (int rc = align ? sites_merge_codes_dev(samples[s], pass == 1, filter, mcode.p + merged_off[(size_t)s],
-                                                 mlevel.p + merged_off[(size_t)s])
-                         : sites_merge_codes_dev(samples[s], pass == 1, filter, dcode.p + code_off[(size_t)s],
-                                                 dlevel.p + site_off[(size_t)s]))
-        return rc;
-    }
+  // the reduced merge, timed as ms[0..1]: into the merged arrays under an alignment, else straight into what the pack and
+  // the fold read
+  Events<5> ev;
+  if (int rc = ev.create(c)) return rc;
+  const CodeTargets packed_from{dcode.p, code_off.data(), dlevel.p, site_off.data()};
+  if (int rc = m.merge_codes(c, n, samples, before, filter, align ? nullptr : &packed_from, ev.e)) return rc;
+  if (align) {  // the gather (returns after completion; the events below still bracket the pack and the fold)
+    const CommonGather g{m.code.p, m.level.p, nullptr, nullptr, nullptr, nullptr, dlevel.p, dcode.p, code_off[1]};
+    if (int rc = sites_align_gather(c, a, g)) return rc;
+    sites_align_report(a, h->report);
   }
-  if (align) {  // (returns after completion; the events below still bracket the pack and the fold)
-    const CommonGather g{mcode.p, mlevel.p, nullptr, nullptr, nullptr, nullptr, dlevel.p, dcode.p, code_off[1]};
-    if (int rc = align == kAlignUnion ? sites_union_gather(c, ust, g) : sites_common_gather(c, st, g)) return rc;
-    if (align == kAlignUnion) std::copy(ust.ms, ust.ms + kUnionPasses, h->union_ms);
-    else std::copy(st.ms, st.ms + 4, h->common_ms);
-  }
-  HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
+  // the builder's own: pack and fold
+  if (int rc = ev.record(c, 2)) return rc;
   if (int rc = codes_pack_dev(c, dcode.p, dcode_off.p, dsite_off.p, n, row_dwords, h->packed.p)) return rc;
-  HIPCHK(c, hipEventRecord(ev.e[3], c->stream));
+  if (int rc = ev.record(c, 3)) return rc;
   hipLaunchKernelGGL(abn_codes_fold_kernel, dim3((unsigned)n), dim3(kCodesWave), 0, c->stream, dcode.p, dlevel.p,
                      dcode_off.p, dsite_off.p, dsum.p, dkept.p);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(ev.e[4], c->stream));
+  if (int rc = ev.record(c, 4)) return rc;
   std::vector<long long> kept((size_t)n);
   h->level_sum_kept.assign((size_t)n, 0.0);
   HIPCHK(c, hipMemcpyAsync(h->level_sum_kept.data(), dsum.p, dsum.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(kept.data(), dkept.p, dkept.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the merged arrays are freed on return
   h->kept.assign(kept.begin(), kept.end());
-  for (int k = 0; k < 4; ++k) {
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-    h->ms[k] = ms;
-  }
+  for (int k = 0; k < 4; ++k)
+    if (int rc = ev.elapsed_ms(c, k, &h->ms[k])) return rc;
   return ABN_OK;
 }
 
@@ -158,20 +118,14 @@ static int codes_create_parsed(abn_ctx* c, double posterior_max_filter, int32_t 
   h->n = n_samples;
   try {
     h->count.assign((size_t)n_samples, 0);
-    for (int s = 0; s < n_samples; ++s) {
-      if (!samples[s]) return set_err(c, ABN_ERR_INVALID_ARG, "a null sites handle");
-      if (!sites_ctx(samples[s])) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle in the host form (abn_sites_parse)");
-      if (sites_ctx(samples[s]) != c) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle of another context");
-      const int64_t count = sites_merged_count(samples[s]);
-      if (count < 0)
-        return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle with deferred lines and no abn_sites_insert");
-      h->count[(size_t)s] = count;
+    if (int rc = resident_counts(c, n_samples, samples, h->count.data())) return rc;
+    for (int64_t count : h->count) {
       h->max_sites = std::max(h->max_sites, count);
       if (count != h->count[0]) h->same_len = false;
     }
     HIPCHK(c, hipSetDevice(c->device));
     PoolScope pool_scope(c);
-    h->before = h->count;
+    h->report.before = h->count;
     if (int rc = codes_build(h.get(), posterior_max_filter, samples, align)) return rc;
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
@@ -196,19 +150,11 @@ extern "C" int abn_codes_create_union(abn_ctx* c, double posterior_max_filter, i
 }
 
 extern "C" int abn_codes_common(const abn_codes* h, int64_t* before, int64_t* n_common, double* ms4) {
-  if (!h) return ABN_ERR_INVALID_ARG;
-  if (before) std::copy(h->before.begin(), h->before.end(), before);
-  if (n_common) *n_common = h->n_common;
-  if (ms4) std::copy(h->common_ms, h->common_ms + 4, ms4);
-  return ABN_OK;
+  return h ? h->report.common(before, n_common, ms4) : ABN_ERR_INVALID_ARG;
 }
 
 extern "C" int abn_codes_union(const abn_codes* h, int64_t* before, int64_t* n_union, double* ms8) {
-  if (!h) return ABN_ERR_INVALID_ARG;
-  if (before) std::copy(h->before.begin(), h->before.end(), before);
-  if (n_union) *n_union = h->n_union;
-  if (ms8) std::copy(h->union_ms, h->union_ms + kUnionPasses, ms8);
-  return ABN_OK;
+  return h ? h->report.unite(before, n_union, ms8) : ABN_ERR_INVALID_ARG;
 }
 
 extern "C" int abn_codes_destroy(abn_codes* h) {

@@ -97,10 +97,7 @@ static int genes_check(abn_genes* h, const abn_gene_rule* rule, int32_t n_sample
   abn_ctx* c = h->ctx;
   if (!rule || !site_offset || n_samples <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
   if (n_samples > 65535) return set_err(c, ABN_ERR_INVALID_ARG, "too many samples");
-  if (site_offset[0] != 0) return set_err(c, ABN_ERR_INVALID_ARG, "site_offset[0] is not 0");
-  for (int s = 0; s < n_samples; ++s)
-    if (site_offset[s + 1] < site_offset[s] || site_offset[s + 1] - site_offset[s] > 0xffffffffLL)
-      return set_err(c, ABN_ERR_INVALID_ARG, "site_offset is not ascending, or a sample of 2^32 sites or more");
+  if (int rc = site_offset_check(c, n_samples, site_offset)) return rc;
   if ((site_offset[n_samples] + kGeneBlockSites - 1) / kGeneBlockSites + n_samples > 0x7fffffffLL)
     return set_err(c, ABN_ERR_INVALID_ARG, "too many sites for one call");
   *n_sites = site_offset[n_samples];
@@ -142,43 +139,32 @@ int abn::genes_choose_dev(abn_genes* h, const abn_gene_rule* rule, int32_t n_sam
   HIPCHK(c, dcarry.alloc(NB));
   HIPCHK(c, hipMemcpyAsync(dblocks.p, blocks.data(), dblocks.bytes(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(dblock0.p, block0.data(), dblock0.bytes(), hipMemcpyHostToDevice, c->stream));
-  struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } ev;
-  auto mark = [&](int k) -> hipError_t {
-    if (!kernel_ms) return hipSuccess;
-    if (hipError_t e = hipEventCreate(&ev.e[k])) return e;
-    return hipEventRecord(ev.e[k], c->stream);
-  };
+  Events<4> ev;
+  if (kernel_ms)
+    if (int rc = ev.create(c)) return rc;
+  auto mark = [&](int k) { return kernel_ms ? ev.record(c, k) : ABN_OK; };
   const GeneSites sites{dchrom, dstart, dend, dstrand};
   const GeneTable table = h->table();
   const GeneRule r{rule->cutoff, rule->cutoff_gene_length};
-  HIPCHK(c, mark(0));
+  if (int rc = mark(0)) return rc;
   hipLaunchKernelGGL(abn_genes_find_kernel, dim3((unsigned)NB), dim3(kGeneThreads), 0, c->stream, sites, dblocks.p, table,
                      r, dF.p, dnext.p, dlast.p);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, mark(1));
+  if (int rc = mark(1)) return rc;
   hipLaunchKernelGGL(abn_genes_carry_kernel, dim3((unsigned)n), dim3(kGeneThreads), 0, c->stream, sites, dblocks.p,
                      dblock0.p, table, r, dF.p, dlast.p, dentry.p, dcarry.p, dbad.p);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, mark(2));
+  if (int rc = mark(2)) return rc;
   hipLaunchKernelGGL(abn_genes_write_kernel, dim3((unsigned)NB), dim3(kGeneThreads), 0, c->stream, sites, dblocks.p, table,
                      dF.p, dnext.p, dentry.p, dcarry.p, dgene_start, dgene_end, dflags);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, mark(3));
+  if (int rc = mark(3)) return rc;
   std::vector<int> bad((size_t)n, 0);
   HIPCHK(c, hipMemcpyAsync(bad.data(), dbad.p, dbad.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch buffers are freed on return
   if (kernel_ms)
-    for (int k = 0; k < 3; ++k) {
-      float ms = 0.f;
-      HIPCHK(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-      kernel_ms[k] = ms;
-    }
+    for (int k = 0; k < 3; ++k)
+      if (int rc = ev.elapsed_ms(c, k, &kernel_ms[k])) return rc;
   for (int s = 0; s < n; ++s)
     if (bad[(size_t)s]) return set_err(c, ABN_ERR_INVALID_ARG, "a site's chromosome is outside 0..257, or its strand above 2");
   return ABN_OK;

@@ -1,6 +1,8 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (abn_api.hip, abn_pairwise.hip,
-// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip, abn_tiles.hip): the context, its device-buffer pool, error reporting,
-// the kernel_ms timer.  Not part of the C-ABI (include/abneutral.h is).
+// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip,
+// abn_tiles.hip, abn_resident.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
+// events of a call, and what the consumers of resident methylomes share (abn_resident.hip).  Not part of the C-ABI
+// (include/abneutral.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -135,6 +137,37 @@ struct DevBuf {
   size_t bytes() const { return n * sizeof(T); }
 };
 
+// N timing events of one call, destroyed on every way out; span k runs from event k to event k + 1.  Where a call's
+// kernel_ms is optional and one span is enough, EventPair below creates its events only when the time is wanted.
+template <int N>
+class Events {
+ public:
+  hipEvent_t e[N] = {};
+  Events() = default;
+  Events(const Events&) = delete;
+  Events& operator=(const Events&) = delete;
+  ~Events() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  int create(abn_ctx* c) {
+    for (hipEvent_t& x : e)
+      if (!x) HIPCHK(c, hipEventCreate(&x));
+    return ABN_OK;
+  }
+  int record(abn_ctx* c, int k) {
+    HIPCHK(c, hipEventRecord(e[k], c->stream));
+    return ABN_OK;
+  }
+  // after a synchronisation behind event k + 1
+  int elapsed_ms(abn_ctx* c, int k, double* ms) {
+    float f = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&f, e[k], e[k + 1]));
+    *ms = f;
+    return ABN_OK;
+  }
+};
+
 // The two HIP events around a call's kernels (kernel_ms): created when the time is first wanted, destroyed on every way
 // out.
 struct EventPair {
@@ -199,7 +232,7 @@ int genes_choose_dev(abn_genes* h, const abn_gene_rule* rule, int32_t n_samples,
                      const int32_t* dchrom, const uint32_t* dstart, const uint32_t* dend, const uint8_t* dstrand,
                      uint32_t* dgene_start, uint32_t* dgene_end, uint8_t* dflags, double* kernel_ms);
 abn_ctx* genes_ctx(const abn_genes* h);
-// abn_sites.hip, for abn_windows_create_parsed (abn_windows.hip).  The context of a resident handle (null: host form);
+// abn_sites.hip, for the builders from resident parse results (through abn_resident.hip, below).  The context of a resident handle (null: host form);
 // its sites once the inserted records are in (-1: host form, or deferred lines without abn_sites_insert); and the merge
 // (abn_sites_merge.hpp) of one sample into the arrays at its first site, on the context's stream, nothing waited for:
 // the fields kernel of every chunk (inserted = false) or the insert kernel (true).
@@ -214,35 +247,56 @@ int sites_merge_codes_dev(const abn_sites* h, bool inserted, double filter, uint
 // dcode_off[s], a multiple of 16; dsite_off[s + 1] - dsite_off[s] sites) into dpacked [n x 4 row_dwords bytes]
 int codes_pack_dev(abn_ctx* c, const uint8_t* dcode, const long long* dcode_off, const long long* dsite_off, int n,
                    long long row_dwords, uint8_t* dpacked);
+// The checks every entry point makes of a site_offset [n_samples + 1] it is given
+inline int site_offset_check(abn_ctx* c, int32_t n_samples, const int64_t* site_offset) {
+  if (site_offset[0] != 0) return set_err(c, ABN_ERR_INVALID_ARG, "site_offset[0] is not 0");
+  for (int s = 0; s < n_samples; ++s)
+    if (site_offset[s + 1] < site_offset[s] || site_offset[s + 1] - site_offset[s] > 0xffffffffLL)
+      return set_err(c, ABN_ERR_INVALID_ARG, "site_offset is not ascending, or a sample of 2^32 sites or more");
+  return ABN_OK;
+}
+// abn_sites_common.hip: the run tables of the order checks (abn_sites_common.hpp) — per sample and chromosome key the first
+// site of its run and the end of it — with the samples' offsets on the device and the err entries the checks leave.  The
+// common-site step and the union step make them of their samples, abn_tiles.hip of its columns as one sample, whose tables
+// stay with the handle.  set takes the offsets (host only: nothing is allocated); init allocates, fills (0x7f bytes:
+// kCommonNone; run_end 0) and sends the offsets up; launch is the runs and ends passes over the sites (none: no launch);
+// refusal reads err back, waits for the stream, and gives the first of the entries first .. last that is set (kind 0:
+// none).
+struct RunTables {
+  int n = 0;
+  std::vector<long long> site_off;  // [n + 1]
+  DevBuf<long long> dsite_off, run_begin, run_end, err;
+  long long sites() const { return site_off[(size_t)n]; }
+  void set(int n_samples, const int64_t* site_offset);
+  int init(abn_ctx* c);
+  int launch(abn_ctx* c, const CommonSites& in);
+  int refusal(abn_ctx* c, int first, int last, CommonRefusal* r);
+};
 // abn_sites_common.hip, for abn_windows_create_aligned and abn_codes_create_aligned: the common-site step
 // (abn_sites_common.hpp) on DEVICE key arrays, in its two halves.  sites_common_match runs the order checks, the match and
 // the ranks, waits, and leaves n_common in the state (dkeep [site_offset[n]], or null: the state's own); the caller sizes
 // its aligned arrays and sites_common_gather fills them (any output of g may be null) and makes the co-ordering check.
 // Either refuses with ABN_ERR_INVALID_ARG and the text of common_refusal_text.  Both return after completion.
 struct CommonState {
-  int n = 0, probe = 0;
+  int probe = 0;
   long long Lp = 0, n_common = 0;
-  std::vector<long long> site_off;
   CommonSites in{};
   uint8_t* keep = nullptr;
   DevBuf<uint8_t> keep_own;
-  DevBuf<long long> dsite_off, run_begin, run_end, err;
+  RunTables tab;
   DevBuf<uint32_t> match, src, block;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  Events<6> ev;
   double ms[4] = {0.0, 0.0, 0.0, 0.0};  // runs and ends; match; scan and rank; gather
-  size_t temp_bytes = 0;                // of the buffers above
-  CommonState() = default;
-  CommonState(const CommonState&) = delete;
-  CommonState& operator=(const CommonState&) = delete;
-  ~CommonState();
 };
 int sites_common_match(abn_ctx* c, int n, const int64_t* site_offset, const CommonSites& in, uint8_t* dkeep, CommonState& st);
 int sites_common_gather(abn_ctx* c, CommonState& st, const CommonGather& g);
-// ... and the launches abn_sites_union.hip shares with it: the runs and ends passes over S sites (tables and err filled by
-// the caller: 0x7f bytes, run_end 0), and the one-workgroup exclusive scan of data[0 .. n) with the sum at data[n]
-int sites_common_tables(abn_ctx* c, const CommonSites& in, const long long* dsite_off, int n, long long S,
-                        long long* run_begin, long long* run_end, long long* err);
+// ... and the launch abn_sites_union.hip shares with it beside the run tables': the one-workgroup exclusive scan of
+// data[0 .. n) with the sum at data[n]
 int sites_common_scan(abn_ctx* c, uint32_t* data, uint32_t n);
+// ... and what abn_sites_common* and abn_sites_union* check of their arguments (`out`: keep or dest; `count`: n_common or
+// n_union)
+int sites_keys_check(abn_ctx* c, int32_t n_samples, const int64_t* site_offset, const void* chromosome, const void* start,
+                     const void* end, const void* strand, const void* out, const void* count);
 // abn_sites_union.hip, for abn_windows_create_union and abn_codes_create_union: the union step (abn_sites_union.hpp) on
 // DEVICE key arrays, in two halves as the common-site step.  sites_union_rank runs the order checks and every pass up to
 // dest, waits in between for the refusals and n_union, and leaves n_union in the state (ddest [site_offset[n]], or null:
@@ -250,21 +304,90 @@ int sites_common_scan(abn_ctx* c, uint32_t* data, uint32_t n);
 // may be null).  sites_union_rank refuses with ABN_ERR_INVALID_ARG and the text of union_refusal_text.  Both return after
 // completion.
 struct UnionState {
-  int n = 0;
   long long n_union = 0;
-  std::vector<long long> site_off;
   CommonSites in{};
   uint32_t* dest = nullptr;
-  DevBuf<long long> dsite_off, run_begin, run_end, err;
+  RunTables tab;
   DevBuf<uint32_t> dest_own, owner, P, r, block, count, base, inv, own_at;
   DevBuf<int> order;
-  hipEvent_t ev[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  Events<11> ev;  // 0..3 around the passes in front of the host's read, 4..7 around those behind it, 8..10 around the gather's
   double ms[kUnionPasses] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // runs and ends; owner; scan; base; rank; dest; invert; gather
-  UnionState() = default;
-  UnionState(const UnionState&) = delete;
-  UnionState& operator=(const UnionState&) = delete;
-  ~UnionState();
 };
 int sites_union_rank(abn_ctx* c, int n, const int64_t* site_offset, const CommonSites& in, uint32_t* ddest, UnionState& st);
 int sites_union_gather(abn_ctx* c, UnionState& st, const CommonGather& g);
+
+// ------------------------------------------------------------------------------------------------
+// abn_resident.hip: what the builders of handles from RESIDENT parse results share — windows_build_parsed
+// (abn_windows.hip), codes_build (abn_codes.hip) and tiles_build (abn_tiles.hip).  Each is a prologue (the handles'
+// refusals, the merge), an optional alignment, its gather, and the part that is the builder's own.
+// ------------------------------------------------------------------------------------------------
+// Every sample's sites (sites_merged_count) into counts [n_samples]; refuses, in this order per sample, a null handle, one
+// in the host form, one of another context, one with deferred lines and no abn_sites_insert
+int resident_counts(abn_ctx* c, int32_t n_samples, abn_sites* const* samples, int64_t* counts);
+// The four key arrays of S sites on the device: allocated, or allocated and sent up from the host's (nothing waited for)
+struct SiteKeys {
+  DevBuf<int32_t> chrom;
+  DevBuf<uint32_t> start, end;
+  DevBuf<uint8_t> strand;
+  CommonSites keys() const { return CommonSites{chrom.p, start.p, end.p, strand.p}; }
+  int alloc(abn_ctx* c, size_t S);
+  int upload(abn_ctx* c, size_t S, const int32_t* chromosome, const uint32_t* start_, const uint32_t* end_,
+             const uint8_t* strand_);
+};
+// Where the reduced merge writes: sample s's merged bytes at code + code_off[s], its levels at level + level_off[s]
+struct CodeTargets {
+  uint8_t* code;
+  const int64_t* code_off;
+  double* level;
+  const int64_t* level_off;
+};
+// The merged arrays of the first n_keyed samples, one sample behind the other from off[s] (at least one element each, so
+// that no pointer is null).  merge_keyed is the full merge (sites_merge_dev) of those samples, keys included; merge_codes
+// the reduced one (sites_merge_codes_dev) of n samples — `before`: their sites; a sample without any is skipped — into
+// `to`, or (null) into code and level here, which takes n_keyed = n.  Both launch every sample's fields kernels, then the
+// insert kernels, and wait for nothing; with `marks`, marks[0] and marks[1] are recorded in front of the two passes, and
+// merge_keyed records marks[2] behind them.
+struct MergedSites : SiteKeys {
+  DevBuf<uint8_t> code;
+  DevBuf<double> level;
+  std::vector<int64_t> off;  // [n_keyed + 1]
+  int alloc(abn_ctx* c, int n_keyed, const int64_t* count);
+  int merge_keyed(abn_ctx* c, abn_sites* const* samples, double filter, const hipEvent_t* marks);
+  int merge_codes(abn_ctx* c, int n, abn_sites* const* samples, const int64_t* before, double filter, const CodeTargets* to,
+                  const hipEvent_t* marks);
+};
+// The alignment of n samples' merged arrays in front of a build: the mode (kAlignPosition or kAlignUnion) and the state of
+// its step.  sites_align is sites_common_match or sites_union_rank and leaves `each`, the sites every sample has behind
+// the step (n_common or n_union); the caller sizes its arrays of n x each sites and sites_align_gather fills them
+// (sites_common_gather or sites_union_gather).  Refusals and completion as those.
+struct Alignment {
+  int mode = kAlignNone;
+  int64_t each = 0;
+  CommonState common;
+  UnionState unite;
+};
+int sites_align(abn_ctx* c, int mode, int n, const int64_t* site_offset, const CommonSites& keys, Alignment& a);
+int sites_align_gather(abn_ctx* c, Alignment& a, const CommonGather& g);
+// What a handle reports of its alignment (abn_windows_common / _union, abn_codes_common / _union): every sample's sites as
+// they came, and of the step that ran its count (-1: it did not run) and the HIP-event ms of its passes (after the gather)
+struct AlignReport {
+  std::vector<int64_t> before;  // [n]
+  int64_t n_common = -1;        // ..._create_aligned: the sites every sample keeps
+  double common_ms[4] = {0.0, 0.0, 0.0, 0.0};
+  int64_t n_union = -1;         // ..._create_union: the sites every sample has, placeholders included
+  double union_ms[kUnionPasses] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int common(int64_t* before_out, int64_t* n_common_out, double* ms4) const {
+    if (before_out) std::copy(before.begin(), before.end(), before_out);
+    if (n_common_out) *n_common_out = n_common;
+    if (ms4) std::copy(common_ms, common_ms + 4, ms4);
+    return ABN_OK;
+  }
+  int unite(int64_t* before_out, int64_t* n_union_out, double* ms8) const {
+    if (before_out) std::copy(before.begin(), before.end(), before_out);
+    if (n_union_out) *n_union_out = n_union;
+    if (ms8) std::copy(union_ms, union_ms + kUnionPasses, ms8);
+    return ABN_OK;
+  }
+};
+void sites_align_report(const Alignment& a, AlignReport& r);
 }  // namespace abn

@@ -3,17 +3,13 @@
 // and the serial form: abn_sites_union.hpp.  The step runs in two halves around the caller's allocation, as the
 // common-site step: sites_union_rank (runs, ends, owner, scan; the refusals, n_union and the run tables come to the host,
 // which decides the chromosomes' order; base, rank, dest) and sites_union_gather (invert, gather).
-// abn_windows_create_union (abn_windows.hip) and abn_codes_create_union (abn_codes.hip) call both between their merge and
-// what their _parsed siblings do next.  The runs / ends kernels and the scan kernel are abn_sites_common.hip's.
+// The builders of abn_windows_create_union, abn_codes_create_union and abn_tiles_create reach both through sites_align
+// (abn_resident.hip), between their merge and what their _parsed siblings do next.  The run tables (RunTables: the runs /
+// ends kernels) and the scan kernel are abn_sites_common.hip's.
 #define ABN_SITES_UNION_KERNELS  // (in front of abn_host.hpp, which includes abn_sites_union.hpp for UnionState)
 #include "abn_host.hpp"
 
 using namespace abn;
-
-UnionState::~UnionState() {
-  for (hipEvent_t x : ev)
-    if (x) (void)hipEventDestroy(x);
-}
 
 static int union_refuse(abn_ctx* c, const CommonRefusal& r) {
   if (!r.kind) return ABN_OK;
@@ -22,24 +18,19 @@ static int union_refuse(abn_ctx* c, const CommonRefusal& r) {
 
 int abn::sites_union_rank(abn_ctx* c, int n, const int64_t* site_offset, const CommonSites& in, uint32_t* ddest,
                           UnionState& st) {
-  st.n = n;
+  RunTables& tab = st.tab;
+  tab.set(n, site_offset);
   st.in = in;
-  st.site_off.assign(site_offset, site_offset + n + 1);
   st.n_union = 0;
-  const long long S = st.site_off[(size_t)n];
+  const long long S = tab.sites();
   if (S > 0xffffffffLL)  // (a site's index and n_union <= S fit a uint32_t)
     return set_err(c, ABN_ERR_INVALID_ARG, "too many sites for one alignment: the union holds at most 2^32 - 1");
-  const size_t tables = (size_t)n * kCommonChroms;
   const unsigned blocks = (unsigned)((S + kCommonThreads - 1) / kCommonThreads);
   if (!ddest) {
     HIPCHK(c, st.dest_own.alloc((size_t)S));
     ddest = st.dest_own.p;
   }
   st.dest = ddest;
-  HIPCHK(c, st.dsite_off.alloc((size_t)n + 1));
-  HIPCHK(c, st.run_begin.alloc(tables));
-  HIPCHK(c, st.run_end.alloc(tables));
-  HIPCHK(c, st.err.alloc(kCommonErrs));
   HIPCHK(c, st.owner.alloc((size_t)S));
   HIPCHK(c, st.P.alloc((size_t)S + 1));
   HIPCHK(c, st.r.alloc((size_t)S));
@@ -47,46 +38,41 @@ int abn::sites_union_rank(abn_ctx* c, int n, const int64_t* site_offset, const C
   HIPCHK(c, st.order.alloc(kCommonChroms));
   HIPCHK(c, st.count.alloc(kCommonChroms));
   HIPCHK(c, st.base.alloc(kCommonChroms));
-  for (hipEvent_t& e : st.ev)
-    if (!e) HIPCHK(c, hipEventCreate(&e));
-  HIPCHK(c, hipMemcpyAsync(st.dsite_off.p, st.site_off.data(), st.dsite_off.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(st.run_begin.p, 0x7f, st.run_begin.bytes(), c->stream));  // kCommonNone
-  HIPCHK(c, hipMemsetAsync(st.run_end.p, 0, st.run_end.bytes(), c->stream));
-  HIPCHK(c, hipMemsetAsync(st.err.p, 0x7f, st.err.bytes(), c->stream));
+  if (int rc = st.ev.create(c)) return rc;
+  if (int rc = tab.init(c)) return rc;
   HIPCHK(c, hipMemsetAsync(st.block.p, 0, st.block.bytes(), c->stream));  // (no site: n_union is this 0)
   HIPCHK(c, hipMemsetAsync(st.P.p, 0, 4, c->stream));                     // (no site: P[0] = P[S])
   HIPCHK(c, hipMemsetAsync(st.base.p, 0, st.base.bytes(), c->stream));
   const dim3 threads(kCommonThreads), grid(blocks);
-  const long long* doff = st.dsite_off.p;
-  const long long *rb = st.run_begin.p, *re = st.run_end.p;
-  HIPCHK(c, hipEventRecord(st.ev[0], c->stream));
-  if (int rc = sites_common_tables(c, in, doff, n, S, st.run_begin.p, st.run_end.p, st.err.p)) return rc;
-  HIPCHK(c, hipEventRecord(st.ev[1], c->stream));
+  const long long* doff = tab.dsite_off.p;
+  const long long *rb = tab.run_begin.p, *re = tab.run_end.p;
+  if (int rc = st.ev.record(c, 0)) return rc;
+  if (int rc = tab.launch(c, in)) return rc;
+  if (int rc = st.ev.record(c, 1)) return rc;
   if (S > 0) {
     hipLaunchKernelGGL(abn_union_owner_kernel, grid, threads, 0, c->stream, in, doff, n, rb, re, st.owner.p, st.block.p);
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipEventRecord(st.ev[2], c->stream));
+  if (int rc = st.ev.record(c, 2)) return rc;
   if (S > 0) {
     if (int rc = sites_common_scan(c, st.block.p, (uint32_t)blocks)) return rc;
     hipLaunchKernelGGL(abn_union_prefix_kernel, grid, threads, 0, c->stream, S, (const uint32_t*)st.owner.p,
                        (const uint32_t*)st.block.p, (uint32_t)blocks, st.P.p);
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipEventRecord(st.ev[3], c->stream));
-  long long err[kCommonErrs];
+  if (int rc = st.ev.record(c, 3)) return rc;
   uint32_t total = 0;
-  std::vector<long long> run_begin(tables);
-  HIPCHK(c, hipMemcpyAsync(err, st.err.p, sizeof err, hipMemcpyDeviceToHost, c->stream));
+  std::vector<long long> run_begin(tab.run_begin.n);
+  CommonRefusal refused;
   HIPCHK(c, hipMemcpyAsync(&total, st.block.p + blocks, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(run_begin.data(), st.run_begin.p, st.run_begin.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (int rc = union_refuse(c, common_refusal(err, kCommonSplitRun, kCommonBadKey, st.site_off.data(), n))) return rc;
+  HIPCHK(c, hipMemcpyAsync(run_begin.data(), tab.run_begin.p, tab.run_begin.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = tab.refusal(c, kCommonSplitRun, kCommonBadKey, &refused)) return rc;
+  if (int rc = union_refuse(c, refused)) return rc;
   std::vector<int> order;
-  if (int rc = union_refuse(c, union_order_refusal(run_begin.data(), st.site_off.data(), n, order))) return rc;
+  if (int rc = union_refuse(c, union_order_refusal(run_begin.data(), tab.site_off.data(), n, order))) return rc;
   st.n_union = (long long)total;
   const uint32_t* P = st.P.p;
-  HIPCHK(c, hipEventRecord(st.ev[4], c->stream));
+  if (int rc = st.ev.record(c, 4)) return rc;
   if (!order.empty()) {
     HIPCHK(c, hipMemcpyAsync(st.order.p, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(abn_union_count_kernel, dim3((unsigned)order.size()), threads, 0, c->stream, P, rb, re, n,
@@ -96,70 +82,51 @@ int abn::sites_union_rank(abn_ctx* c, int n, const int64_t* site_offset, const C
                        (const int*)st.order.p, (int)order.size(), st.base.p);
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipEventRecord(st.ev[5], c->stream));
+  if (int rc = st.ev.record(c, 5)) return rc;
   if (S > 0) {
     hipLaunchKernelGGL(abn_union_rank_kernel, grid, threads, 0, c->stream, in, S, n, rb, re, (const uint32_t*)st.owner.p, P,
                        (const uint32_t*)st.base.p, st.r.p);
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipEventRecord(st.ev[6], c->stream));
+  if (int rc = st.ev.record(c, 6)) return rc;
   if (S > 0) {
     hipLaunchKernelGGL(abn_union_dest_kernel, grid, threads, 0, c->stream, S, (const uint32_t*)st.owner.p,
                        (const uint32_t*)st.r.p, ddest);
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipEventRecord(st.ev[7], c->stream));
+  if (int rc = st.ev.record(c, 7)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));  // (`order` is read by the copy above until here)
   for (int k = 0; k < 3; ++k) {
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, st.ev[k], st.ev[k + 1]));
-    st.ms[k] = ms;
-    HIPCHK(c, hipEventElapsedTime(&ms, st.ev[k + 4], st.ev[k + 5]));
-    st.ms[k + 3] = ms;
+    if (int rc = st.ev.elapsed_ms(c, k, &st.ms[k])) return rc;
+    if (int rc = st.ev.elapsed_ms(c, k + 4, &st.ms[k + 3])) return rc;
   }
   return ABN_OK;
 }
 
 int abn::sites_union_gather(abn_ctx* c, UnionState& st, const CommonGather& g) {
-  const long long S = st.site_off[(size_t)st.n];
-  HIPCHK(c, st.inv.alloc((size_t)st.n * (size_t)st.n_union));
+  const long long S = st.tab.sites();
+  HIPCHK(c, st.inv.alloc((size_t)st.tab.n * (size_t)st.n_union));
   HIPCHK(c, st.own_at.alloc((size_t)st.n_union));
-  HIPCHK(c, hipEventRecord(st.ev[8], c->stream));
+  if (int rc = st.ev.record(c, 8)) return rc;
   if (st.n_union > 0) {
     HIPCHK(c, hipMemsetAsync(st.inv.p, 0xff, st.inv.bytes(), c->stream));  // kUnionNone
     hipLaunchKernelGGL(abn_union_invert_kernel, dim3((unsigned)((S + kCommonThreads - 1) / kCommonThreads)),
-                       dim3(kCommonThreads), 0, c->stream, (const long long*)st.dsite_off.p, st.n, st.n_union,
+                       dim3(kCommonThreads), 0, c->stream, (const long long*)st.tab.dsite_off.p, st.tab.n, st.n_union,
                        (const uint32_t*)st.owner.p, (const uint32_t*)st.dest, st.inv.p, st.own_at.p);
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipEventRecord(st.ev[9], c->stream));
+  if (int rc = st.ev.record(c, 9)) return rc;
   if (st.n_union > 0) {
-    const dim3 grid((unsigned)((st.n_union + kCommonThreads - 1) / kCommonThreads), (unsigned)st.n);
+    const dim3 grid((unsigned)((st.n_union + kCommonThreads - 1) / kCommonThreads), (unsigned)st.tab.n);
     hipLaunchKernelGGL(abn_union_gather_kernel, grid, dim3(kCommonThreads), 0, c->stream, st.in,
-                       (const long long*)st.dsite_off.p, st.n_union, (const uint32_t*)st.inv.p,
+                       (const long long*)st.tab.dsite_off.p, st.n_union, (const uint32_t*)st.inv.p,
                        (const uint32_t*)st.own_at.p, g);
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipEventRecord(st.ev[10], c->stream));
+  if (int rc = st.ev.record(c, 10)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int k = 0; k < 2; ++k) {
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, st.ev[k + 8], st.ev[k + 9]));
-    st.ms[k + 6] = ms;
-  }
-  return ABN_OK;
-}
-
-static int union_check(abn_ctx* c, int32_t n_samples, const int64_t* site_offset, const void* chromosome, const void* start,
-                       const void* end, const void* strand, const void* dest, const void* n_union) {
-  if (!site_offset || !n_union || n_samples <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
-  if (n_samples > 65535) return set_err(c, ABN_ERR_INVALID_ARG, "too many samples");
-  if (site_offset[0] != 0) return set_err(c, ABN_ERR_INVALID_ARG, "site_offset[0] is not 0");
-  for (int s = 0; s < n_samples; ++s)
-    if (site_offset[s + 1] < site_offset[s] || site_offset[s + 1] - site_offset[s] > 0xffffffffLL)
-      return set_err(c, ABN_ERR_INVALID_ARG, "site_offset is not ascending, or a sample of 2^32 sites or more");
-  if (site_offset[n_samples] > 0 && (!chromosome || !start || !end || !strand || !dest))
-    return set_err(c, ABN_ERR_INVALID_ARG, "null site arrays");
+  for (int k = 0; k < 2; ++k)
+    if (int rc = st.ev.elapsed_ms(c, k + 8, &st.ms[k + 6])) return rc;
   return ABN_OK;
 }
 
@@ -167,7 +134,7 @@ extern "C" int abn_sites_union_dev(abn_ctx* c, int32_t n_samples, const int64_t*
                                    const void* dstart, const void* dend, const void* dstrand, void* ddest,
                                    int64_t* n_union) {
   if (!c) return ABN_ERR_INVALID_ARG;
-  if (int rc = union_check(c, n_samples, site_offset, dchromosome, dstart, dend, dstrand, ddest, n_union)) return rc;
+  if (int rc = sites_keys_check(c, n_samples, site_offset, dchromosome, dstart, dend, dstrand, ddest, n_union)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
   try {
@@ -188,28 +155,17 @@ extern "C" int abn_sites_union(abn_ctx* c, int32_t n_samples, const int64_t* sit
                                const uint32_t* start, const uint32_t* end, const uint8_t* strand, uint32_t* dest,
                                int64_t* n_union) {
   if (!c) return ABN_ERR_INVALID_ARG;
-  if (int rc = union_check(c, n_samples, site_offset, chromosome, start, end, strand, dest, n_union)) return rc;
+  if (int rc = sites_keys_check(c, n_samples, site_offset, chromosome, start, end, strand, dest, n_union)) return rc;
   const size_t S = (size_t)site_offset[n_samples];
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
-  DevBuf<int32_t> dchrom;
-  DevBuf<uint32_t> dstart, dend, ddest;
-  DevBuf<uint8_t> dstrand;
-  HIPCHK(c, dchrom.alloc(S));
-  HIPCHK(c, dstart.alloc(S));
-  HIPCHK(c, dend.alloc(S));
-  HIPCHK(c, dstrand.alloc(S));
+  SiteKeys key;
+  DevBuf<uint32_t> ddest;
+  if (int rc = key.upload(c, S, chromosome, start, end, strand)) return rc;
   HIPCHK(c, ddest.alloc(S));
-  if (S > 0) {
-    HIPCHK(c, hipMemcpyAsync(dchrom.p, chromosome, S * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dstart.p, start, S * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dend.p, end, S * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dstrand.p, strand, S, hipMemcpyHostToDevice, c->stream));
-  }
   try {
     UnionState st;
-    if (int rc = sites_union_rank(c, n_samples, site_offset, CommonSites{dchrom.p, dstart.p, dend.p, dstrand.p}, ddest.p, st))
-      return rc;
+    if (int rc = sites_union_rank(c, n_samples, site_offset, key.keys(), ddest.p, st)) return rc;
     if (S > 0) HIPCHK(c, hipMemcpyAsync(dest, ddest.p, S * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *n_union = st.n_union;

@@ -1,7 +1,8 @@
 // abn_tiles_*: genomic tiles over resident, aligned methylomes — Pedigree::build (src/pedigree.rs:147-172, :210-261) once
 // per fixed bin or listed region.  Kernels, the definition and the serial forms: abn_tiles.hpp.  The build is
 // abn_codes.hip's (merge, optional common-site or union step, gather, pack) with the columns' keys, the merged bytes and the
-// levels kept; the merge launches are abn_sites.hip's, the order checks abn_sites_common.hip's, the scan abn_pairwise.hip's.
+// levels kept; the front end both share is abn_resident.hip's, the merge launches are abn_sites.hip's, the order checks
+// (RunTables) abn_sites_common.hip's, the scan abn_pairwise.hip's.
 #include "abn_host.hpp"
 #define ABN_TILES_KERNELS
 #include "abn_tiles.hpp"
@@ -19,7 +20,7 @@ struct abn_tiles {
   DevBuf<double> level;       // [n x n_columns]
   DevBuf<int32_t> chromosome; // [n_columns] the columns' keys
   DevBuf<uint32_t> start;
-  DevBuf<long long> run_begin, run_end;  // [kCommonChroms]
+  RunTables tables;           // of the columns as one sample: run_begin, run_end [kCommonChroms]
   std::vector<TileRun> runs;
   bool has_tiles = false;
   std::vector<int32_t> tchromosome;  // [T] the intervals
@@ -30,42 +31,20 @@ struct abn_tiles {
   double ms[2] = {0.0, 0.0};  // search, fold
 };
 
-static int tiles_build(abn_tiles* h, double filter, abn_sites* const* samples, int align, std::vector<int64_t> count) {
+static int tiles_build(abn_tiles* h, double filter, abn_sites* const* samples, int align,
+                       const std::vector<int64_t>& before) {
   abn_ctx* c = h->ctx;
   const int n = h->n;
-  DevBuf<int32_t> mchrom;
-  DevBuf<uint32_t> mstart, mend;
-  DevBuf<uint8_t> mstrand, mcode;
-  DevBuf<double> mlevel;
-  CommonState st;
-  UnionState ust;
-  const std::vector<int64_t> before = count;
-  std::vector<int64_t> merged_off((size_t)n + 1, 0);
-  // the full merge, keys included: of every sample under an alignment, of sample 0 alone without one
-  const int n_keyed = align ? n : 1;
-  for (int s = 0; s < n_keyed; ++s) merged_off[(size_t)s + 1] = merged_off[(size_t)s] + count[(size_t)s];
-  const size_t S = std::max<size_t>((size_t)merged_off[(size_t)n_keyed], 1);
-  HIPCHK(c, mchrom.alloc(S));
-  HIPCHK(c, mstart.alloc(S));
-  HIPCHK(c, mend.alloc(S));
-  HIPCHK(c, mstrand.alloc(S));
-  HIPCHK(c, mcode.alloc(S));
-  HIPCHK(c, mlevel.alloc(S));
-  for (int pass = 0; pass < 2; ++pass)
-    for (int s = 0; s < n_keyed; ++s) {
-      const size_t o = (size_t)merged_off[(size_t)s];
-      if (count[(size_t)s] == 0) continue;
-      if (int rc = sites_merge_dev(samples[s], pass == 1, filter, mchrom.p + o, mstart.p + o, mend.p + o, mstrand.p + o,
-                                   mcode.p + o, mlevel.p + o))
-        return rc;
-    }
-  long long each = count[0];
+  // the prologue and the alignment.  The full merge, keys included: of every sample under an alignment, of sample 0 alone
+  // without one
+  MergedSites m;
+  Alignment a;
+  if (int rc = m.alloc(c, align ? n : 1, before.data())) return rc;
+  if (int rc = m.merge_keyed(c, samples, filter, nullptr)) return rc;
+  long long each = before[0];
   if (align) {
-    const CommonSites keys{mchrom.p, mstart.p, mend.p, mstrand.p};
-    if (int rc = align == kAlignUnion ? sites_union_rank(c, n, merged_off.data(), keys, nullptr, ust)
-                                      : sites_common_match(c, n, merged_off.data(), keys, nullptr, st))
-      return rc;
-    each = align == kAlignUnion ? ust.n_union : st.n_common;
+    if (int rc = sites_align(c, align, n, m.off.data(), m.keys(), a)) return rc;
+    each = a.each;
   }
   h->n_columns = each;
   h->code_stride = (each + 15) / 16 * 16;  // whole 16-byte loads of the pack
@@ -79,72 +58,59 @@ static int tiles_build(abn_tiles* h, double filter, abn_sites* const* samples, i
   HIPCHK(c, h->level.alloc((size_t)n * E));
   HIPCHK(c, h->chromosome.alloc(E));
   HIPCHK(c, h->start.alloc(E));
-  HIPCHK(c, h->run_begin.alloc(kCommonChroms));
-  HIPCHK(c, h->run_end.alloc(kCommonChroms));
   HIPCHK(c, h->packed.alloc((size_t)n * (size_t)h->stride));
+  std::vector<int64_t> site_off((size_t)n + 1), code_off((size_t)n + 1);
+  for (int s = 0; s <= n; ++s) site_off[(size_t)s] = (int64_t)s * each, code_off[(size_t)s] = (int64_t)s * h->code_stride;
 
-  // the reduced merge: the merged bytes (merge_code has no kCodeCounted) and the levels
-  for (int pass = 0; pass < 2; ++pass)
-    for (int s = 0; s < n; ++s) {
-      if (before[(size_t)s] == 0) continue;
-      if (int rc = align ? sites_merge_codes_dev(samples[s], pass == 1, filter, mcode.p + merged_off[(size_t)s],
-                                                 mlevel.p + merged_off[(size_t)s])
-                         : sites_merge_codes_dev(samples[s], pass == 1, filter, h->code.p + (size_t)s * (size_t)h->code_stride,
-                                                 h->level.p + (size_t)s * (size_t)each))
-        return rc;
-    }
+  // the reduced merge: the merged bytes (merge_code has no kCodeCounted) and the levels, into the merged arrays under an
+  // alignment, else straight into the handle's
+  const CodeTargets kept{h->code.p, code_off.data(), h->level.p, site_off.data()};
+  if (int rc = m.merge_codes(c, n, samples, before.data(), filter, align ? nullptr : &kept, nullptr)) return rc;
   // the columns' four key fields, for the order checks: sample 0's after the gather, or as merged
-  DevBuf<int32_t> gchrom;
-  DevBuf<uint32_t> gstart, gend;
-  DevBuf<uint8_t> gstrand;
-  CommonSites columns{mchrom.p, mstart.p, mend.p, mstrand.p};
+  SiteKeys gkey;
+  CommonSites columns = m.keys();
   if (align) {
-    HIPCHK(c, gchrom.alloc((size_t)n * E));
-    HIPCHK(c, gstart.alloc((size_t)n * E));
-    HIPCHK(c, gend.alloc((size_t)n * E));
-    HIPCHK(c, gstrand.alloc((size_t)n * E));
-    const CommonGather g{mcode.p, mlevel.p, gchrom.p, gstart.p, gend.p, gstrand.p, h->level.p, h->code.p, h->code_stride};
-    if (int rc = align == kAlignUnion ? sites_union_gather(c, ust, g) : sites_common_gather(c, st, g)) return rc;
-    columns = CommonSites{gchrom.p, gstart.p, gend.p, gstrand.p};  // (sample 0's are the first `each` of each)
+    if (int rc = gkey.alloc(c, (size_t)n * E)) return rc;
+    const CommonGather g{m.code.p,      m.level.p,  gkey.chrom.p, gkey.start.p,  gkey.end.p,
+                         gkey.strand.p, h->level.p, h->code.p,    h->code_stride};
+    if (int rc = sites_align_gather(c, a, g)) return rc;
+    columns = gkey.keys();  // (sample 0's are the first `each` of each)
   }
+  // the builder's own: the columns' keys, their run tables and the pack
   if (each > 0) {
     HIPCHK(c, hipMemcpyAsync(h->chromosome.p, columns.chromosome, (size_t)each * 4, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(h->start.p, columns.start, (size_t)each * 4, hipMemcpyDeviceToDevice, c->stream));
   }
   // the runs and ends passes over the columns as one sample: the run tables, and the order checks' refusals
-  const long long col_off[2] = {0, each};
-  DevBuf<long long> dcol_off, derr;
+  RunTables& tab = h->tables;
+  const int64_t col_off[2] = {0, each};
   DevBuf<uint32_t> dlast;
-  HIPCHK(c, dcol_off.alloc(2));
-  HIPCHK(c, derr.alloc(kCommonErrs));
+  tab.set(1, col_off);
+  if (int rc = tab.init(c)) return rc;
   HIPCHK(c, dlast.alloc(kCommonChroms));
-  HIPCHK(c, hipMemcpyAsync(dcol_off.p, col_off, sizeof col_off, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(h->run_begin.p, 0x7f, h->run_begin.bytes(), c->stream));  // kCommonNone
-  HIPCHK(c, hipMemsetAsync(h->run_end.p, 0, h->run_end.bytes(), c->stream));
-  HIPCHK(c, hipMemsetAsync(derr.p, 0x7f, derr.bytes(), c->stream));
-  if (int rc = sites_common_tables(c, columns, dcol_off.p, 1, each, h->run_begin.p, h->run_end.p, derr.p)) return rc;
+  if (int rc = tab.launch(c, columns)) return rc;
   hipLaunchKernelGGL(abn_tiles_last_kernel, dim3((kCommonChroms + kTilesThreads - 1) / kTilesThreads), dim3(kTilesThreads), 0,
-                     c->stream, (const uint32_t*)h->start.p, (const long long*)h->run_begin.p,
-                     (const long long*)h->run_end.p, dlast.p);
+                     c->stream, (const uint32_t*)h->start.p, (const long long*)tab.run_begin.p,
+                     (const long long*)tab.run_end.p, dlast.p);
   HIPCHK(c, hipGetLastError());
   // the pack
-  std::vector<long long> site_off((size_t)n + 1), code_off((size_t)n + 1);
-  for (int s = 0; s <= n; ++s) site_off[(size_t)s] = (long long)s * each, code_off[(size_t)s] = (long long)s * h->code_stride;
   DevBuf<long long> dsite_off, dcode_off;
+  static_assert(sizeof(long long) == sizeof(int64_t), "the offsets on the device");
   HIPCHK(c, dsite_off.alloc((size_t)n + 1));
   HIPCHK(c, dcode_off.alloc((size_t)n + 1));
   HIPCHK(c, hipMemcpyAsync(dsite_off.p, site_off.data(), dsite_off.bytes(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(dcode_off.p, code_off.data(), dcode_off.bytes(), hipMemcpyHostToDevice, c->stream));
   if (int rc = codes_pack_dev(c, h->code.p, dcode_off.p, dsite_off.p, n, row_dwords, h->packed.p)) return rc;
 
-  long long err[kCommonErrs], run_begin[kCommonChroms], run_end[kCommonChroms];
+  long long run_begin[kCommonChroms], run_end[kCommonChroms];
   uint32_t last[kCommonChroms];
-  HIPCHK(c, hipMemcpyAsync(err, derr.p, sizeof err, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(run_begin, h->run_begin.p, sizeof run_begin, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(run_end, h->run_end.p, sizeof run_end, hipMemcpyDeviceToHost, c->stream));
+  CommonRefusal r;
+  HIPCHK(c, hipMemcpyAsync(run_begin, tab.run_begin.p, sizeof run_begin, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(run_end, tab.run_end.p, sizeof run_end, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(last, dlast.p, sizeof last, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));  // the merged arrays are freed on return
-  const CommonRefusal r = common_refusal(err, kCommonSplitRun, kCommonBadKey, col_off, 1);
+  if (int rc = tab.refusal(c, kCommonSplitRun, kCommonBadKey, &r)) return rc;  // (waits; the merged arrays are freed on return)
+  tab.dsite_off.release();  // the handle keeps the two tables alone
+  tab.err.release();
   if (r.kind)
     return set_err(c, ABN_ERR_INVALID_ARG,
                    "the sites cannot be cut into tiles: their keys are not well ordered: " + common_refusal_text(r));
@@ -166,14 +132,7 @@ extern "C" int abn_tiles_create(abn_ctx* c, double posterior_max_filter, int32_t
   h->n = n_samples;
   try {
     std::vector<int64_t> count((size_t)n_samples, 0);
-    for (int s = 0; s < n_samples; ++s) {
-      if (!samples[s]) return set_err(c, ABN_ERR_INVALID_ARG, "a null sites handle");
-      if (!sites_ctx(samples[s])) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle in the host form (abn_sites_parse)");
-      if (sites_ctx(samples[s]) != c) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle of another context");
-      count[(size_t)s] = sites_merged_count(samples[s]);
-      if (count[(size_t)s] < 0)
-        return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle with deferred lines and no abn_sites_insert");
-    }
+    if (int rc = resident_counts(c, n_samples, samples, count.data())) return rc;
     if (align == kAlignNone)
       for (int s = 1; s < n_samples; ++s)
         if (count[(size_t)s] != count[0])
@@ -247,36 +206,27 @@ static int tiles_run(abn_tiles* h) {
   HIPCHK(c, hipMemcpyAsync(dchrom.p, h->tchromosome.data(), dchrom.bytes(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(dpos.p, h->tstart.data(), dpos.bytes(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(dpos_end.p, h->tend.data(), dpos_end.bytes(), hipMemcpyHostToDevice, c->stream));
-  struct Events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~Events() {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } ev;
-  for (int k = 0; k < 3; ++k) HIPCHK(c, hipEventCreate(&ev.e[k]));
-  HIPCHK(c, hipEventRecord(ev.e[0], c->stream));
+  Events<3> ev;
+  if (int rc = ev.create(c)) return rc;
+  if (int rc = ev.record(c, 0)) return rc;
   hipLaunchKernelGGL(abn_tiles_search_kernel, dim3((unsigned)((T + kTilesThreads - 1) / kTilesThreads)), dim3(kTilesThreads), 0,
-                     c->stream, (const uint32_t*)h->start.p, (const long long*)h->run_begin.p,
-                     (const long long*)h->run_end.p, (long long)T, (const int32_t*)dchrom.p, (const long long*)dpos.p,
+                     c->stream, (const uint32_t*)h->start.p, (const long long*)h->tables.run_begin.p,
+                     (const long long*)h->tables.run_end.p, (long long)T, (const int32_t*)dchrom.p, (const long long*)dpos.p,
                      (const long long*)dpos_end.p, dbegin.p, dend.p);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(ev.e[1], c->stream));
+  if (int rc = ev.record(c, 1)) return rc;
   hipLaunchKernelGGL(abn_tiles_fold_kernel, dim3((unsigned)T, (unsigned)n), dim3(kCodesWave), 0, c->stream,
                      (const uint8_t*)h->code.p, h->code_stride, (const double*)h->level.p, h->n_columns, (long long)T,
                      (const long long*)dbegin.p, (const long long*)dend.p, dsum.p, dkept.p);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
+  if (int rc = ev.record(c, 2)) return rc;
   HIPCHK(c, hipMemcpyAsync(h->begin.data(), dbegin.p, dbegin.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(h->end.data(), dend.p, dend.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(h->level_sum_kept.data(), dsum.p, dsum.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(h->kept.data(), dkept.p, dkept.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int k = 0; k < 2; ++k) {
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-    h->ms[k] = ms;
-  }
+  for (int k = 0; k < 2; ++k)
+    if (int rc = ev.elapsed_ms(c, k, &h->ms[k])) return rc;
   return ABN_OK;
 }
 

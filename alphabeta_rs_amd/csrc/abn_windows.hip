@@ -1,8 +1,9 @@
 // abn_windows_*: the window-placement handle.  Kernels: abn_windows.hpp; the scan of the placed windows
-// (abn_windows_pairwise) is abn_pairwise.hip's, the gene choice of abn_windows_create_sites abn_genes.hip's, the merge of
-// resident parse results in front of abn_windows_create_parsed abn_sites.hip's, the common-site step between that merge and
-// the gene choice of abn_windows_create_aligned abn_sites_common.hip's, the union step in the same place of
-// abn_windows_create_union abn_sites_union.hip's.
+// (abn_windows_pairwise) is abn_pairwise.hip's, the gene choice of abn_windows_create_sites abn_genes.hip's; what stands in
+// front of the gene choice of abn_windows_create_parsed / _aligned / _union — the resident handles' refusals, the merge of
+// their parse results (abn_sites.hip's launches), and between that merge and the gene choice the common-site step
+// (abn_sites_common.hip) or the union step (abn_sites_union.hip) — is abn_resident.hip's, shared with abn_codes.hip and
+// abn_tiles.hip.
 #include "abn_host.hpp"
 #include "abn_windows.hpp"
 
@@ -20,11 +21,7 @@ struct abn_windows {
   std::vector<int32_t> ragged;
   std::vector<double> level_sum, level_sum_kept;
   double merge_ms[2] = {0.0, 0.0};  // abn_windows_create_parsed: its fields and insert kernels
-  std::vector<int64_t> before;      // [n]: every sample's sites as they came (abn_windows_common)
-  int64_t n_common = -1;            // abn_windows_create_aligned: the sites every sample keeps
-  double common_ms[4] = {0.0, 0.0, 0.0, 0.0};
-  int64_t n_union = -1;             // abn_windows_create_union: the sites every sample has, placeholders included
-  double union_ms[kUnionPasses] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  AlignReport report;               // abn_windows_common, abn_windows_union
   DevBuf<uint8_t> packed;  // [n x stride], device-resident between calls
 };
 
@@ -215,99 +212,65 @@ static int windows_build_sites(abn_windows* h, const abn_windows_params* p, abn_
 // `align`, the sites every sample shares (abn_sites_common.hpp; kAlignPosition) or the union of the samples' sites with
 // filtered placeholders (abn_sites_union.hpp; kAlignUnion) gathered out of them first
 static int windows_build_parsed(abn_windows* h, const abn_windows_params* p, abn_genes* genes, const abn_gene_rule* rule,
-                                double filter, const int64_t* site_offset, abn_sites* const* samples, int align) {
+                                double filter, abn_sites* const* samples, int align) {
   abn_ctx* c = h->ctx;
   const int n = h->n;
-  const size_t S = (size_t)site_offset[n];
-  DevBuf<int32_t> dchrom;
-  DevBuf<uint32_t> dstart, dend, dgs, dge;
-  DevBuf<uint8_t> dstrand, dflags, dcode;
-  DevBuf<double> dlevel;
-  HIPCHK(c, dchrom.alloc(S));
-  HIPCHK(c, dstart.alloc(S));
-  HIPCHK(c, dend.alloc(S));
-  HIPCHK(c, dstrand.alloc(S));
+  // the prologue: every sample merged with its keys, the two passes timed into merge_ms (no site at all: no event); the
+  // gene arrays and the flags beside the merged arrays
+  MergedSites m;
+  DevBuf<uint32_t> dgs, dge;
+  DevBuf<uint8_t> dflags;
+  if (int rc = m.alloc(c, n, h->report.before.data())) return rc;
+  const size_t S = (size_t)m.off[(size_t)n];
   HIPCHK(c, dgs.alloc(S));
   HIPCHK(c, dge.alloc(S));
   HIPCHK(c, dflags.alloc(S));
-  HIPCHK(c, dcode.alloc(std::max<size_t>(S, 1)));
-  HIPCHK(c, dlevel.alloc(std::max<size_t>(S, 1)));
-  struct Events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~Events() {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } ev;
+  Events<3> ev;
   if (S > 0) {
-    for (int k = 0; k < 3; ++k) HIPCHK(c, hipEventCreate(&ev.e[k]));
-    for (int pass = 0; pass < 2; ++pass) {  // the fields kernels of every sample, then the insert kernels
-      HIPCHK(c, hipEventRecord(ev.e[pass], c->stream));
-      for (int s = 0; s < n; ++s) {
-        const size_t o = (size_t)site_offset[s];
-        if (site_offset[s + 1] == site_offset[s]) continue;
-        if (int rc = sites_merge_dev(samples[s], pass == 1, filter, dchrom.p + o, dstart.p + o, dend.p + o, dstrand.p + o,
-                                     dcode.p + o, dlevel.p + o))
-          return rc;
-      }
-    }
-    HIPCHK(c, hipEventRecord(ev.e[2], c->stream));
+    if (int rc = ev.create(c)) return rc;
+    if (int rc = m.merge_keyed(c, samples, filter, ev.e)) return rc;
   }
   // what the gene choice and the placement read: the merged arrays, or their aligned copies (n_common sites per sample;
   // the gene arrays and the flags, written behind the step, are the merged arrays' own: no longer than those; n_union
   // sites per sample: the gene arrays and the flags are allocated again)
-  const int64_t* offset = site_offset;
-  const int32_t* chrom = dchrom.p;
-  const uint32_t *start = dstart.p, *end = dend.p;
-  const uint8_t *strand = dstrand.p, *code = dcode.p;
-  const double* level = dlevel.p;
-  DevBuf<int32_t> achrom;
-  DevBuf<uint32_t> astart, aend;
-  DevBuf<uint8_t> astrand, acode;
+  const int64_t* offset = m.off.data();
+  const int32_t* chrom = m.chrom.p;
+  const uint32_t *start = m.start.p, *end = m.end.p;
+  const uint8_t *strand = m.strand.p, *code = m.code.p;
+  const double* level = m.level.p;
+  SiteKeys akey;
+  DevBuf<uint8_t> acode;
   DevBuf<double> alevel;
   std::vector<int64_t> aligned_offset((size_t)n + 1, 0);
   if (align) {  // (no site at all: n_common = 0 through the same path)
-    CommonState st;
-    UnionState ust;
-    const CommonSites keys{dchrom.p, dstart.p, dend.p, dstrand.p};
-    if (int rc = align == kAlignUnion ? sites_union_rank(c, n, site_offset, keys, nullptr, ust)
-                                      : sites_common_match(c, n, site_offset, keys, nullptr, st))
-      return rc;
-    const int64_t each = align == kAlignUnion ? ust.n_union : st.n_common;
-    const size_t A = (size_t)n * (size_t)each;
-    HIPCHK(c, achrom.alloc(A));
-    HIPCHK(c, astart.alloc(A));
-    HIPCHK(c, aend.alloc(A));
-    HIPCHK(c, astrand.alloc(A));
+    Alignment a;
+    if (int rc = sites_align(c, align, n, offset, m.keys(), a)) return rc;
+    const size_t A = (size_t)n * (size_t)a.each;
+    if (int rc = akey.alloc(c, A)) return rc;
     HIPCHK(c, acode.alloc(std::max<size_t>(A, 1)));
     HIPCHK(c, alevel.alloc(std::max<size_t>(A, 1)));
-    const CommonGather g{dcode.p, dlevel.p, achrom.p, astart.p, aend.p, astrand.p, alevel.p, acode.p, each};
-    if (int rc = align == kAlignUnion ? sites_union_gather(c, ust, g) : sites_common_gather(c, st, g)) return rc;
-    if (align == kAlignUnion) {
-      h->n_union = each;
-      std::copy(ust.ms, ust.ms + kUnionPasses, h->union_ms);
-      if (A > S) {  // (the gather is complete: the merged arrays' gene arrays and flags have no reader)
-        HIPCHK(c, dgs.alloc(A));
-        HIPCHK(c, dge.alloc(A));
-        HIPCHK(c, dflags.alloc(A));
-      }
-    } else {
-      h->n_common = each;
-      std::copy(st.ms, st.ms + 4, h->common_ms);
+    const CommonGather g{m.code.p, m.level.p, akey.chrom.p, akey.start.p, akey.end.p, akey.strand.p, alevel.p, acode.p, a.each};
+    if (int rc = sites_align_gather(c, a, g)) return rc;
+    sites_align_report(a, h->report);
+    // A > S under the union alone (n_common is at most the shortest sample), and only this builder has arrays sized by
+    // the merged sites that are written behind the step (the gather is complete: the merged arrays' gene arrays and
+    // flags have no reader)
+    if (A > S) {
+      HIPCHK(c, dgs.alloc(A));
+      HIPCHK(c, dge.alloc(A));
+      HIPCHK(c, dflags.alloc(A));
     }
-    for (int s = 0; s <= n; ++s) aligned_offset[(size_t)s] = (int64_t)s * each;
+    for (int s = 0; s <= n; ++s) aligned_offset[(size_t)s] = (int64_t)s * a.each;
     offset = aligned_offset.data();
-    chrom = achrom.p, start = astart.p, end = aend.p, strand = astrand.p, code = acode.p, level = alevel.p;
+    chrom = akey.chrom.p, start = akey.start.p, end = akey.end.p, strand = akey.strand.p, code = acode.p, level = alevel.p;
   }
+  // the builder's own: the gene choice and the placement
   if (offset[n] > 0)
     if (int rc = genes_choose_dev(genes, rule, n, offset, chrom, start, end, strand, dgs.p, dge.p, dflags.p, nullptr))
       return rc;  // (ends in a synchronisation)
   if (S > 0)
-    for (int k = 0; k < 2; ++k) {
-      float ms = 0.f;
-      HIPCHK(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-      h->merge_ms[k] = ms;
-    }
+    for (int k = 0; k < 2; ++k)
+      if (int rc = ev.elapsed_ms(c, k, &h->merge_ms[k])) return rc;
   return windows_build_dev(h, p, offset, start, dgs.p, dge.p, dflags.p, code, level);
 }
 
@@ -320,11 +283,7 @@ static int windows_check(abn_ctx* c, const abn_windows_params* p, int32_t n_samp
   if (p->n_upstream < 0 || p->n_gene < 0 || p->n_downstream < 0 ||
       (long long)p->n_upstream + p->n_gene + p->n_downstream > (1 << 20))
     return set_err(c, ABN_ERR_INVALID_ARG, "window counts");
-  if (site_offset[0] != 0) return set_err(c, ABN_ERR_INVALID_ARG, "site_offset[0] is not 0");
-  for (int s = 0; s < n_samples; ++s)
-    if (site_offset[s + 1] < site_offset[s] || site_offset[s + 1] - site_offset[s] > 0xffffffffLL)
-      return set_err(c, ABN_ERR_INVALID_ARG, "site_offset is not ascending, or a sample of 2^32 sites or more");
-  return ABN_OK;
+  return site_offset_check(c, n_samples, site_offset);
 }
 
 // the handle around build(handle): created, built, handed out
@@ -339,8 +298,8 @@ static int windows_make(abn_ctx* c, const abn_windows_params* p, int32_t n_sampl
   h->n = n_samples;
   h->W = p->n_upstream + p->n_gene + p->n_downstream;
   try {
-    h->before.resize((size_t)n_samples);
-    for (int s = 0; s < n_samples; ++s) h->before[(size_t)s] = site_offset[s + 1] - site_offset[s];
+    h->report.before.resize((size_t)n_samples);
+    for (int s = 0; s < n_samples; ++s) h->report.before[(size_t)s] = site_offset[s + 1] - site_offset[s];
     if (int rc = build(h.get())) return rc;
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
@@ -382,20 +341,13 @@ static int windows_create_parsed(abn_ctx* c, const abn_windows_params* p, abn_ge
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
   }
-  for (int s = 0; s < n_samples; ++s) {
-    if (!samples[s]) return set_err(c, ABN_ERR_INVALID_ARG, "a null sites handle");
-    if (!sites_ctx(samples[s])) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle in the host form (abn_sites_parse)");
-    if (sites_ctx(samples[s]) != c) return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle of another context");
-    const int64_t count = sites_merged_count(samples[s]);
-    if (count < 0)
-      return set_err(c, ABN_ERR_INVALID_ARG, "a sites handle with deferred lines and no abn_sites_insert");
-    site_offset[(size_t)s + 1] = site_offset[(size_t)s] + count;
-  }
+  if (int rc = resident_counts(c, n_samples, samples, site_offset.data() + 1)) return rc;
+  for (int s = 0; s < n_samples; ++s) site_offset[(size_t)s + 1] += site_offset[(size_t)s];
   if (int rc = windows_check(c, p, n_samples, site_offset.data(), out)) return rc;
   if (!genes || !rule) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
   if (genes_ctx(genes) != c) return set_err(c, ABN_ERR_INVALID_ARG, "the genes belong to another context");
   return windows_make(c, p, n_samples, site_offset.data(), out, [&](abn_windows* h) {
-    return windows_build_parsed(h, p, genes, rule, posterior_max_filter, site_offset.data(), samples, align);
+    return windows_build_parsed(h, p, genes, rule, posterior_max_filter, samples, align);
   });
 }
 
@@ -453,19 +405,11 @@ extern "C" int abn_windows_merge_ms(const abn_windows* h, double* ms2) {
 }
 
 extern "C" int abn_windows_common(const abn_windows* h, int64_t* before, int64_t* n_common, double* ms4) {
-  if (!h) return ABN_ERR_INVALID_ARG;
-  if (before) std::copy(h->before.begin(), h->before.end(), before);
-  if (n_common) *n_common = h->n_common;
-  if (ms4) std::copy(h->common_ms, h->common_ms + 4, ms4);
-  return ABN_OK;
+  return h ? h->report.common(before, n_common, ms4) : ABN_ERR_INVALID_ARG;
 }
 
 extern "C" int abn_windows_union(const abn_windows* h, int64_t* before, int64_t* n_union, double* ms8) {
-  if (!h) return ABN_ERR_INVALID_ARG;
-  if (before) std::copy(h->before.begin(), h->before.end(), before);
-  if (n_union) *n_union = h->n_union;
-  if (ms8) std::copy(h->union_ms, h->union_ms + kUnionPasses, ms8);
-  return ABN_OK;
+  return h ? h->report.unite(before, n_union, ms8) : ABN_ERR_INVALID_ARG;
 }
 
 extern "C" int abn_windows_stats(const abn_windows* h, int64_t* count, double* level_sum, double* level_sum_kept,

@@ -10,7 +10,8 @@ parse results of every methylome to the finished window handle:
 
 All are timed with a host clock around the call (all end in device synchronisations); the parse, identical on all
 sides, is outside the span.  The HIP-event times of (b)'s common-site kernels (abn_windows_common) are reported beside
-them, and the bytes of the step's temporaries (the formula of sites_common_match: the keep flags, the two tables of runs,
+them, and the bytes of the step's temporaries (the formula of sites_common_match and of the RunTables it fills
+(csrc/abn_sites_common.hip): the keep flags, the two tables of runs,
 match and src of 4 bytes per sample and site of the shortest sample, the workgroup counts; for (c), abn_windows_union and the formula of sites_union_rank / sites_union_gather: owner, P, r and
 dest of 4 bytes per site, the tables, the workgroup counts, inv of 4 bytes per sample and union site, own_at).  Shapes, those of
 scripts/resident_ab.py with one text for all samples, so that the samples share every site and (b) - (a) is the price of

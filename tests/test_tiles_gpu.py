@@ -290,8 +290,70 @@ def test_refusals(abn, gpu_ctx, L, inputs, handles):
         s.close()
 
 
+def test_create_refuses_what_the_codes_entry_refuses(abn, gpu_ctx, L):
+    """abn_tiles_create and Tiles.from_parsed on methylomes of three lines: a null handle in the list, a host-form handle, a
+    handle of a second context and a handle with a deferred line and no insert are ABN_ERR_INVALID_ARG with the very text
+    abn_codes_create_parsed gives; so are n_samples == 0 and an align outside 0..2 (which from_parsed refuses before the
+    entry: its align names no such mode)"""
+    lib = gpu_ctx._L
+    text = (P.HEADER + "\n".join(P.cg_line(pos=str(p)) for p in (5, 6, 7)) + "\n").encode()
+    deferring = (P.HEADER + "\n".join([P.cg_line(pos="5"), P.cg_line(pos="6", pm=LONG), P.cg_line(pos="7")]) + "\n").encode()
+
+    class Raw:                                                                    # what from_parsed reads of a Sites
+        def __init__(self, h):
+            self._h = h
+
+    def last_error(ctx):
+        return (lib.abn_last_error(ctx._h) or b"").decode()
+
+    def refused(samples, ctx=gpu_ctx, align=0):
+        """the raw entry's status and text, the codes entry's, and from_parsed's -> the text"""
+        arr = (C.c_void_p * max(len(samples), 1))(*(s._h.value if isinstance(s._h, C.c_void_p) else s._h for s in samples))
+        w = C.c_void_p(0xdead)
+        assert lib.abn_tiles_create(ctx._h, FLT, align, len(samples), arr, C.byref(w)) == INVALID and not w.value
+        said = last_error(ctx)
+        if 0 <= align <= 2:
+            w = C.c_void_p(0xdead)
+            assert lib.abn_codes_create_parsed(ctx._h, FLT, len(samples), arr, C.byref(w)) == INVALID and not w.value
+            assert said == last_error(ctx) and said
+            with pytest.raises(abn.AbnError) as e:
+                abn.Tiles.from_parsed(ctx, samples, posterior_max_filter=FLT, align=("none", "position", "union")[align])
+            assert e.value.status == INVALID and str(e.value).endswith(": " + said)
+        return said
+
+    good = resident(gpu_ctx, L, text)
+    other = abn.Context(0)
+    host = C.c_void_p()
+    try:
+        assert lib.abn_sites_parse(gpu_ctx._h, text, len(text), None, C.byref(host)) == 0
+        foreign = other.parse_sites_resident(text, skip_lines=0)
+        forgotten = gpu_ctx.parse_sites_resident(deferring, skip_lines=0)
+        assert forgotten.info()["n_deferred"] == 1
+        fine = abn.Tiles.from_parsed(gpu_ctx, [good, good], posterior_max_filter=FLT)   # the good handle is one
+        assert fine.info()["n_columns"] == 3
+        fine.close()
+        texts = [refused([good, bad], align=align) for align in (0, 1, 2)
+                 for bad in (Raw(None), Raw(host), foreign, forgotten)]
+        assert texts[:4] == texts[4:8] == texts[8:] and len(set(texts[:4])) == 4
+        assert [t for t in texts[:4]] == ["a null sites handle", "a sites handle in the host form (abn_sites_parse)",
+                                          "a sites handle of another context",
+                                          "a sites handle with deferred lines and no abn_sites_insert"]
+        assert refused([good], ctx=other) == texts[2]                                # ... and the context's own side of it
+        refused([])                                                                  # n_samples == 0
+        refused([good], align=3), refused([good], align=-1)
+        for align in (3, -1, "both"):
+            with pytest.raises(ValueError):
+                abn.Tiles.from_parsed(gpu_ctx, [good], posterior_max_filter=FLT, align=align)
+        foreign.close(), forgotten.close()
+    finally:
+        if host.value:
+            lib.abn_sites_destroy(host)
+        other.close()
+        good.close()
+
+
 # ---------------------------------------------------------------- the tool
-NAMES = ["G0.txt", "G1_2.txt", "G4_2.txt", "G4_8.txt"]
+NAMES =["G0.txt", "G1_2.txt", "G4_2.txt", "G4_8.txt"]
 TILE, PER_TILE, N_TILES = 1000, 100, 12
 
 
