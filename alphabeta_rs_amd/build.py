@@ -86,7 +86,7 @@ def build_host(force: bool = False, verbose: bool = False) -> Path:
     library exposing Pedigree::build to the tests.  Both link libabneutral_hip.so via $ORIGIN rpaths."""
     build_hip()
     srcs = [HOST / "alphabeta_cli.cpp", HOST / "alphabeta.hpp", HOST / "pedigree_build.hpp", HOST / "windows_extract.hpp",
-            HOST / "host_capi.cpp",
+            HOST / "resident.hpp", HOST / "host_capi.cpp",
             HOST / "metaprofile.hpp", HOST / "metaprofile_cli.cpp", HOST / "reference_tests.cpp",
             CSRC / "abn_route.hpp", CSRC / "abn_constants.hpp", CSRC / "abn_parse.hpp", CSRC / "abn_genes.hpp",
             CSRC / "abn_sites_merge.hpp", CSRC / "abn_codes.hpp", CSRC / "abn_sites_common.hpp",

@@ -49,7 +49,8 @@ struct Error : std::runtime_error {
 // --align: how samples that do not hold the same sites are compared (not in the reference, which assumes they do:
 // src/pedigree.rs:240).  Position: on the sites every sample shares; Union: pair by pair on the sites both hold, every
 // sample padded to the union of all sites with filtered placeholders (src/pedigree.rs:249-254 skips those per pair).
-enum class Align { None, Position, Union };
+// The values are the library's (abn_tiles_create's align) and index resident.hpp's table.
+enum class Align : int32_t { None = 0, Position = 1, Union = 2 };
 inline const char* align_name(Align a) { return a == Align::Union ? "union" : (a == Align::Position ? "position" : "none"); }
 // the value of --align, or false
 inline bool parse_align(const std::string& how, Align& out) {
@@ -104,6 +105,29 @@ class Device {  // RAII abn_ctx
  private:
   abn_ctx* ctx_ = nullptr;
   int ordinal_ = 0;
+};
+
+// The owner of one library handle: a pointer and the abn_*_destroy that ends it.  Moves, never copies.  out(): where a
+// create call of the library leaves the handle (they write null when they fail).
+template <class T, int (*Destroy)(T*)>
+class Owned {
+ public:
+  explicit Owned(T* h = nullptr) : h_(h) {}
+  Owned(Owned&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  Owned& operator=(Owned&& o) noexcept {
+    std::swap(h_, o.h_);
+    return *this;
+  }
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  ~Owned() {
+    if (h_) Destroy(h_);
+  }
+  T* get() const { return h_; }
+  T** out() { return &h_; }
+
+ private:
+  T* h_;
 };
 
 // HIP ordinals the batched entry points spread their work over (--devices a,b,c; default: the one default device).

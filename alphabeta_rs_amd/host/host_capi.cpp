@@ -15,12 +15,33 @@
 #include "alphabeta.hpp"
 #include "tiles.hpp"
 
+namespace {
+// What the host layer would print (detail::diag_printf) goes into `text` while this lives; the sink it found is put back.
+struct DiagCapture {
+  std::string text;
+  std::string* const found = alphabeta::detail::diag_sink();
+  DiagCapture() { alphabeta::detail::diag_sink() = &text; }
+  ~DiagCapture() { alphabeta::detail::diag_sink() = found; }
+};
+struct Stopwatch {  // wall milliseconds since it was made
+  const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+void put_text(char* out, long long cap, const std::string& s) {  // cut to the buffer, always terminated
+  if (out && cap > 0) std::strncpy(out, s.c_str(), (size_t)cap - 1), out[cap - 1] = 0;
+}
+int failed(char* err, int errcap, const std::exception& e) {  // the exception's words for the caller; the shims' -1
+  put_text(err, errcap, e.what());
+  return -1;
+}
+}  // namespace
+
 extern "C" {
-// returns the number of rows (<0 on error); rows (capacity cap x 4) and *p0uu are filled
-static int pedigree_build(const char* nodelist, const char* edgelist, double posterior_max_filter, bool gpu_pairwise,
+// returns the number of rows (<0 on error); rows (capacity cap x 4) and *p0uu are filled.  resident: --parse device --sites device
+static int pedigree_build(const char* nodelist, const char* edgelist, double posterior_max_filter, bool gpu_pairwise, bool resident,
                           const char* out_path, double* rows, int cap, double* p0uu, char* err, int errcap) {
   try {
-    auto [ped, p0] = alphabeta::Pedigree::build(nodelist, edgelist, posterior_max_filter, gpu_pairwise);
+    auto [ped, p0] = alphabeta::Pedigree::build(nodelist, edgelist, posterior_max_filter, gpu_pairwise, resident, resident);
     if (out_path) ped.to_file(out_path);
     const int n = (int)ped.nrows();
     if (n > cap) return -2;
@@ -28,18 +49,17 @@ static int pedigree_build(const char* nodelist, const char* edgelist, double pos
     *p0uu = p0;
     return n;
   } catch (const std::exception& e) {
-    if (err && errcap > 0) std::strncpy(err, e.what(), (size_t)errcap - 1), err[errcap - 1] = 0;
-    return -1;
+    return failed(err, errcap, e);
   }
 }
 int abh_pedigree_build(const char* nodelist, const char* edgelist, double posterior_max_filter, double* rows, int cap,
                        double* p0uu, char* err, int errcap) {
-  return pedigree_build(nodelist, edgelist, posterior_max_filter, false, nullptr, rows, cap, p0uu, err, errcap);
+  return pedigree_build(nodelist, edgelist, posterior_max_filter, false, false, nullptr, rows, cap, p0uu, err, errcap);
 }
 // the same with the scan on the GPU, as the `alphabeta` CLI builds its pedigree; out_path (nullable): Pedigree::to_file
 int abh_pedigree_build_gpu(const char* nodelist, const char* edgelist, double posterior_max_filter, const char* out_path,
                            double* rows, int cap, double* p0uu, char* err, int errcap) {
-  return pedigree_build(nodelist, edgelist, posterior_max_filter, true, out_path, rows, cap, p0uu, err, errcap);
+  return pedigree_build(nodelist, edgelist, posterior_max_filter, true, false, out_path, rows, cap, p0uu, err, errcap);
 }
 // scans Pedigree::build has sent through abn_pairwise_divergence_packed since the library was loaded
 long long abh_packed_scan_calls() { return alphabeta::detail::packed_scan_calls().load(); }
@@ -50,18 +70,7 @@ long long abh_resident_build_calls() { return alphabeta::detail::resident_build_
 // Pedigree::build as `alphabeta --parse device --sites device` runs it: abh_pedigree_build_gpu's arguments and result
 int abh_pedigree_build_resident(const char* nodelist, const char* edgelist, double posterior_max_filter, const char* out_path,
                                 double* rows, int cap, double* p0uu, char* err, int errcap) {
-  try {
-    auto [ped, p0] = alphabeta::Pedigree::build(nodelist, edgelist, posterior_max_filter, true, true, true);
-    if (out_path) ped.to_file(out_path);
-    const int n = (int)ped.nrows();
-    if (n > cap) return -2;
-    if (n > 0) std::memcpy(rows, ped.data.data(), sizeof(double) * 4 * (size_t)n);
-    *p0uu = p0;
-    return n;
-  } catch (const std::exception& e) {
-    if (err && errcap > 0) std::strncpy(err, e.what(), (size_t)errcap - 1), err[errcap - 1] = 0;
-    return -1;
-  }
+  return pedigree_build(nodelist, edgelist, posterior_max_filter, true, true, out_path, rows, cap, p0uu, err, errcap);
 }
 // The two ways of `alphabeta --parse device` from n methylome texts in host memory (the sampled nodes of the nodelist, in
 // its order; the files it names are not opened) to the finished pedigree and p0uu: --sites host (which & 1: the records
@@ -77,23 +86,17 @@ int abh_pedigree_build_ab(const char* nodelist, const char* edgelist, const char
       held.clear();
       for (int i = 0; i < n; ++i) held.emplace_back(texts[i], (size_t)lens[i]);
     }
-    auto now = []() { return std::chrono::steady_clock::now(); };
-    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    std::string warnings;  // (both sides print the invalid-status warnings; kept off the console)
-    alphabeta::detail::diag_sink() = &warnings;
-    struct Unsink {
-      ~Unsink() { alphabeta::detail::diag_sink() = nullptr; }
-    } unsink;
+    DiagCapture quiet;  // (both sides print the invalid-status warnings; kept off the console)
     std::pair<alphabeta::Pedigree, double> host, device;
     if (which & 1) {
-      const auto t0 = now();
+      const Stopwatch watch;
       host = alphabeta::detail::build_pedigree(nodelist, edgelist, posterior_max_filter, true, true, false, &held);
-      ms2[0] = ms(t0, now());
+      ms2[0] = watch.ms();
     }
     if (which & 2) {
-      const auto t0 = now();
+      const Stopwatch watch;
       device = alphabeta::detail::build_pedigree(nodelist, edgelist, posterior_max_filter, true, true, true, &held);
-      ms2[1] = ms(t0, now());
+      ms2[1] = watch.ms();
       std::memcpy(kernel_ms4, alphabeta::detail::resident_kernel_ms(), 4 * sizeof(double));
     }
     if ((which & 3) != 3) return 1;
@@ -103,8 +106,7 @@ int abh_pedigree_build_ab(const char* nodelist, const char* edgelist, const char
                ? 1
                : 0;
   } catch (const std::exception& e) {
-    if (err && errcap > 0) std::strncpy(err, e.what(), (size_t)errcap - 1), err[errcap - 1] = 0;
-    return -1;
+    return failed(err, errcap, e);
   }
 }
 // The layout of Pedigree::build_many's scan calls without a device: the n entries are read, those that the scan takes
@@ -183,7 +185,7 @@ int abh_pedigree_build_many(const char* const* nodelists, const char* const* edg
       if (errcap > 0) err[0] = 0;
       std::fputs(b.diagnostics.c_str(), stdout);
       if (!b.ok) {
-        if (errcap > 0) std::strncpy(err, b.error.c_str(), (size_t)errcap - 1), err[errcap - 1] = 0;
+        put_text(err, errcap, b.error);
         nrows[i] = -1;
         continue;
       }
@@ -239,20 +241,10 @@ long long abh_choose_genes(const char* annotation, long long alen, const char* m
   std::memcpy(level, s.level.data(), 8 * n);
   return (long long)n;
 }
-// ---- the methylome line parser: the host's (parse_site_full) and the one the device shares (csrc/abn_parse.hpp), for
-// tests/test_parse_cpu.py and tests/test_parse_gpu.py
-// parse_sites_host of a text from line `skip_lines` on -> per site (capacity cap): line, chromosome, start, end, strand,
-// posteriormax, status, meth_lvl; *n_warnings = the invalid-status warnings it would have printed.  Returns the number of
-// sites, -1 when they do not fit
-long long abh_parse_sites(const char* text, long long len, long long skip_lines, long long cap, long long* line,
-                          int* chromosome, unsigned* start, unsigned* end, unsigned char* strand, double* posteriormax,
-                          unsigned char* status, double* meth_lvl, long long* n_warnings) {
-  std::string warnings;
-  std::vector<int64_t> lines;
-  alphabeta::detail::diag_sink() = &warnings;
-  const auto sites = alphabeta::windows::parse_sites_host(std::string(text, (size_t)len), (size_t)skip_lines, &lines);
-  alphabeta::detail::diag_sink() = nullptr;
-  if (n_warnings) *n_warnings = (long long)std::count(warnings.begin(), warnings.end(), '\n');
+// parsed sites and their lines into the caller's arrays (capacity cap) -> their number, -1 when they do not fit
+static long long put_sites(const std::vector<alphabeta::windows::FullSite>& sites, const std::vector<int64_t>& lines,
+                           long long cap, long long* line, int* chromosome, unsigned* start, unsigned* end,
+                           unsigned char* strand, double* posteriormax, unsigned char* status, double* meth_lvl) {
   if ((long long)sites.size() > cap) return -1;
   for (size_t i = 0; i < sites.size(); ++i) {
     line[i] = lines[i];
@@ -265,6 +257,20 @@ long long abh_parse_sites(const char* text, long long len, long long skip_lines,
     meth_lvl[i] = sites[i].meth_lvl;
   }
   return (long long)sites.size();
+}
+// ---- the methylome line parser: the host's (parse_site_full) and the one the device shares (csrc/abn_parse.hpp), for
+// tests/test_parse_cpu.py and tests/test_parse_gpu.py
+// parse_sites_host of a text from line `skip_lines` on -> per site (capacity cap): line, chromosome, start, end, strand,
+// posteriormax, status, meth_lvl; *n_warnings = the invalid-status warnings it would have printed.  Returns the number of
+// sites, -1 when they do not fit
+long long abh_parse_sites(const char* text, long long len, long long skip_lines, long long cap, long long* line,
+                          int* chromosome, unsigned* start, unsigned* end, unsigned char* strand, double* posteriormax,
+                          unsigned char* status, double* meth_lvl, long long* n_warnings) {
+  DiagCapture warnings;
+  std::vector<int64_t> lines;
+  const auto sites = alphabeta::windows::parse_sites_host(std::string(text, (size_t)len), (size_t)skip_lines, &lines);
+  if (n_warnings) *n_warnings = (long long)std::count(warnings.text.begin(), warnings.text.end(), '\n');
+  return put_sites(sites, lines, cap, line, chromosome, start, end, strand, posteriormax, status, meth_lvl);
 }
 // abn::abn_parse_f64 of one token -> 0 value (in *value), 1 rejected, 2 deferred
 int abh_parse_f64_token(const char* token, long long len, double* value) {
@@ -308,31 +314,12 @@ long long abh_parse_sites_device(const char* text, long long len, long long skip
                                  unsigned char* strand, double* posteriormax, unsigned char* status, double* meth_lvl,
                                  char* warnings_out, long long wcap) {
   try {
-    std::string warnings;
+    DiagCapture warnings;
     std::vector<int64_t> lines;
-    alphabeta::detail::diag_sink() = &warnings;
-    std::vector<alphabeta::windows::FullSite> sites;
-    try {
-      sites = alphabeta::windows::parse_sites_device(alphabeta::default_device(), std::string(text, (size_t)len),
-                                                     (size_t)skip_lines, slab_bytes, &lines);
-    } catch (...) {
-      alphabeta::detail::diag_sink() = nullptr;
-      throw;
-    }
-    alphabeta::detail::diag_sink() = nullptr;
-    if (warnings_out && wcap > 0) std::strncpy(warnings_out, warnings.c_str(), (size_t)wcap - 1), warnings_out[wcap - 1] = 0;
-    if ((long long)sites.size() > cap) return -1;
-    for (size_t i = 0; i < sites.size(); ++i) {
-      line[i] = lines[i];
-      chromosome[i] = sites[i].chromosome;
-      start[i] = sites[i].start;
-      end[i] = sites[i].end;
-      strand[i] = (unsigned char)sites[i].strand;
-      posteriormax[i] = sites[i].posteriormax;
-      status[i] = (unsigned char)sites[i].status_numeric;
-      meth_lvl[i] = sites[i].meth_lvl;
-    }
-    return (long long)sites.size();
+    const auto sites = alphabeta::windows::parse_sites_device(alphabeta::default_device(), std::string(text, (size_t)len),
+                                                              (size_t)skip_lines, slab_bytes, &lines);
+    put_text(warnings_out, wcap, warnings.text);
+    return put_sites(sites, lines, cap, line, chromosome, start, end, strand, posteriormax, status, meth_lvl);
   } catch (const std::exception&) {
     return -2;
   }
@@ -353,18 +340,16 @@ int abh_choose_genes_many_ab(const char* annotation, long long alen, const char*
       genome = w::parse_annotation(std::string(annotation, (size_t)alen));
     }
     const w::GeneRule rule{cutoff, false};
-    auto now = []() { return std::chrono::steady_clock::now(); };
-    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     std::vector<w::SampleSites> host, dev;
     if (which & 1) {
-      const auto t0 = now();
+      const Stopwatch watch;
       host = w::choose_genes_many(held, genome, rule, posterior_max_filter, (size_t)threads);
-      ms2[0] = ms(t0, now());
+      ms2[0] = watch.ms();
     }
     if (which & 2) {
-      const auto t0 = now();
+      const Stopwatch watch;
       dev = w::choose_genes_many_device(alphabeta::default_device(), held, genome, rule, posterior_max_filter);
-      ms2[1] = ms(t0, now());
+      ms2[1] = watch.ms();
     }
     if (which != 3) return 1;
     for (size_t s = 0; s < held.size(); ++s) {
@@ -411,6 +396,26 @@ long long abh_choose_genes_blocked(const char* annotation, long long alen, const
                             next.data(), last.data(), gene_start, gene_end, flags);
   return (long long)S;
 }
+// 1 when all that two windows::Handle report and their packed matrices are equal (doubles bit for bit), 0 when not
+static int same_handles(alphabeta::Device& dev, const alphabeta::windows::Handle& a, const alphabeta::windows::Handle& b) {
+  auto same_bits = [](const std::vector<double>& x, const std::vector<double>& y) {
+    return x.size() == y.size() && (x.empty() || std::memcmp(x.data(), y.data(), 8 * x.size()) == 0);
+  };
+  if (a.count != b.count || a.kept != b.kept || a.ragged != b.ragged || !same_bits(a.level_sum, b.level_sum) ||
+      !same_bits(a.level_sum_kept, b.level_sum_kept))
+    return 0;
+  int64_t stride[2] = {0, 0};
+  abn_windows_info(a.get(), nullptr, &stride[0], nullptr);
+  abn_windows_info(b.get(), nullptr, &stride[1], nullptr);
+  if (stride[0] != stride[1]) return 0;
+  std::vector<uint8_t> pa(a.n_samples() * (size_t)stride[0]), pb(pa.size());
+  dev.check(abn_windows_packed(a.get(), pa.data()), "abn_windows_packed");
+  dev.check(abn_windows_packed(b.get(), pb.data()), "abn_windows_packed");
+  std::vector<int64_t> ba(a.n_windows()), ea(ba.size()), bb(ba.size()), eb(ba.size());
+  abn_windows_layout(a.get(), ba.data(), ea.data(), nullptr);
+  abn_windows_layout(b.get(), bb.data(), eb.data(), nullptr);
+  return pa == pb && ba == bb && ea == eb ? 1 : 0;
+}
 // The two ways to a windows::Handle from parsed sites, on n methylome texts: choose_genes on `threads` threads and the
 // Handle of its arrays (which & 1), against the Handle that chooses on the device (which & 2).  which == 3: 1 when all
 // that the two handles report and their packed matrices are equal, 0 when not.  ms2 = the wall time of the two from the
@@ -433,18 +438,16 @@ int abh_windows_handles_ab(const char* annotation, long long alen, const char* c
     const abn_windows_params p =
         w::window_params(cutoff, step, size, absolute != 0, absolute ? genome.max_gene_length : 100u);
     alphabeta::Device& dev = alphabeta::default_device();
-    auto now = []() { return std::chrono::steady_clock::now(); };
-    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     std::unique_ptr<w::Handle> host, device;
     if (which & 1) {
-      const auto t0 = now();
+      const Stopwatch watch;
       host = std::make_unique<w::Handle>(dev, p, w::choose_genes_many(sites, genome, rule, posterior_max_filter, (size_t)threads));
-      ms2[0] = ms(t0, now());
+      ms2[0] = watch.ms();
     }
     if (which & 2) {
-      const auto t0 = now();
+      const Stopwatch watch;
       device = std::make_unique<w::Handle>(dev, p, genome, rule, posterior_max_filter, sites);
-      ms2[1] = ms(t0, now());
+      ms2[1] = watch.ms();
     }
     if (which & 4) {
       const w::GenesHandle genes(dev, genome);
@@ -457,23 +460,7 @@ int abh_windows_handles_ab(const char* annotation, long long alen, const char* c
                 "abn_genes_choose");
     }
     if ((which & 3) != 3) return 1;
-    auto same_bits = [](const std::vector<double>& x, const std::vector<double>& y) {
-      return x.size() == y.size() && (x.empty() || std::memcmp(x.data(), y.data(), 8 * x.size()) == 0);
-    };
-    if (host->count != device->count || host->kept != device->kept || host->ragged != device->ragged ||
-        !same_bits(host->level_sum, device->level_sum) || !same_bits(host->level_sum_kept, device->level_sum_kept))
-      return 0;
-    int64_t stride[2] = {0, 0};
-    abn_windows_info(host->get(), nullptr, &stride[0], nullptr);
-    abn_windows_info(device->get(), nullptr, &stride[1], nullptr);
-    if (stride[0] != stride[1]) return 0;
-    std::vector<uint8_t> pa(sites.size() * (size_t)stride[0]), pb(pa.size());
-    dev.check(abn_windows_packed(host->get(), pa.data()), "abn_windows_packed");
-    dev.check(abn_windows_packed(device->get(), pb.data()), "abn_windows_packed");
-    std::vector<int64_t> ba(host->n_windows()), ea(ba.size()), bb(ba.size()), eb(ba.size());
-    abn_windows_layout(host->get(), ba.data(), ea.data(), nullptr);
-    abn_windows_layout(device->get(), bb.data(), eb.data(), nullptr);
-    return pa == pb && ba == bb && ea == eb ? 1 : 0;
+    return same_handles(dev, *host, *device);
   } catch (const std::exception&) {
     return -1;
   }
@@ -545,7 +532,7 @@ long long abh_sites_common_serial(int n, const long long* site_off, const int* c
   refusal[0] = r.kind;
   refusal[1] = r.sample;
   refusal[2] = r.site;
-  if (text && cap > 0) std::strncpy(text, abn::common_refusal_text(r).c_str(), (size_t)cap - 1), text[cap - 1] = 0;
+  put_text(text, cap, abn::common_refusal_text(r));
   return n_common;
 }
 // ---- the union of the samples' sites (csrc/abn_sites_union.hpp), for tests/test_sites_union_cpu.py
@@ -575,7 +562,7 @@ long long abh_sites_union_serial(int n, const long long* site_off, const int* ch
   refusal[0] = r.kind;
   refusal[1] = r.sample;
   refusal[2] = r.site;
-  if (text && cap > 0) std::strncpy(text, abn::union_refusal_text(r).c_str(), (size_t)cap - 1), text[cap - 1] = 0;
+  put_text(text, cap, abn::union_refusal_text(r));
   return fits ? n_union : -4;
 }
 // ---- genomic tiles (csrc/abn_tiles.hpp, host/tiles.hpp), for tests/test_tiles_cpu.py
@@ -590,7 +577,7 @@ int abh_tiles_runs_serial(long long n_columns, const int* chromosome, const unsi
   const bool ok = abn::tiles_runs_serial(abn::CommonSites{chromosome, start, end, strand}, n_columns, run_begin, run_end,
                                          &runs, &r);
   refusal[0] = r.kind, refusal[1] = r.sample, refusal[2] = r.site;
-  if (text && cap > 0) std::strncpy(text, abn::common_refusal_text(r).c_str(), (size_t)cap - 1), text[cap - 1] = 0;
+  put_text(text, cap, abn::common_refusal_text(r));
   if (!ok) return -1;
   for (size_t k = 0; k < runs.size(); ++k) {
     run_chromosome[k] = runs[k].chromosome, run_first[k] = runs[k].first, run_count[k] = runs[k].count;
@@ -628,11 +615,12 @@ long long abh_tiles_read_regions(const char* text, long long len, long long cap,
 }
 // <chromosome>:<start>-<end> as results.txt spells a tile
 void abh_tiles_region(int chromosome, long long start, long long end, char* text, long long cap) {
-  std::strncpy(text, alphabeta::metaprofile::tile_region(chromosome, start, end).c_str(), (size_t)cap - 1), text[cap - 1] = 0;
+  put_text(text, cap, alphabeta::metaprofile::tile_region(chromosome, start, end));
 }
 // detail::convert(graph, dm) -> rows_a, and detail::rows_from(detail::convert_times(graph), dm) -> rows_b (capacity cap x 4
 // each; dm [nn x nn] as DMatrix::from fills it); *nn_out = the sampled nodes.  Returns the rows of convert, -1: a call
-// threw (the words in err), -2: they do not fit, -3: the two differ in their number of rows
+// threw, and when both forms ran, both threw the same words (in err), -2: they do not fit, -3: the two differ in their
+// number of rows, -4: one form threw and the other did not, or in other words
 int abh_tiles_convert_both(const char* nodelist, const char* edgelist, const double* dm, int* nn_out, double* rows_a,
                            double* rows_b, int cap, char* err, int errcap) {
   try {
@@ -641,8 +629,20 @@ int abh_tiles_convert_both(const char* nodelist, const char* edgelist, const dou
     if (nn_out) *nn_out = (int)nn;
     if (!dm) return 0;
     const std::vector<double> d(dm, dm + nn * nn);
-    const alphabeta::Pedigree a = alphabeta::detail::convert(graph, d);
-    const alphabeta::Pedigree b = alphabeta::detail::rows_from(alphabeta::detail::convert_times(graph), d, nn);
+    alphabeta::Pedigree a, b;
+    std::string threw[2];
+    try {
+      a = alphabeta::detail::convert(graph, d);
+    } catch (const alphabeta::Error& e) {
+      threw[0] = e.what();
+    }
+    try {
+      b = alphabeta::detail::rows_from(alphabeta::detail::convert_times(graph), d, nn);
+    } catch (const alphabeta::Error& e) {
+      threw[1] = e.what();
+    }
+    if (threw[0] != threw[1]) return -4;
+    if (!threw[0].empty()) return put_text(err, errcap, threw[0]), -1;
     if (a.nrows() != b.nrows()) return -3;
     if ((int)a.nrows() > cap) return -2;
     if (a.nrows() > 0) {
@@ -651,8 +651,7 @@ int abh_tiles_convert_both(const char* nodelist, const char* edgelist, const dou
     }
     return (int)a.nrows();
   } catch (const std::exception& e) {
-    if (err && errcap > 0) std::strncpy(err, e.what(), (size_t)errcap - 1), err[errcap - 1] = 0;
-    return -1;
+    return failed(err, errcap, e);
   }
 }
 // the comparator the searches share: 1 when key a = (start, end, strand) is below key b, and 1 in *equal when they are the same
@@ -670,14 +669,10 @@ long long abh_parse_sites_resident(const char* text, long long len, long long sk
                                    unsigned char* strand, double* posteriormax, unsigned char* status, double* meth_lvl,
                                    char* warnings_out, long long wcap) {
   try {
-    std::string warnings;
-    alphabeta::detail::diag_sink() = &warnings;
-    struct Unsink {
-      ~Unsink() { alphabeta::detail::diag_sink() = nullptr; }
-    } unsink;
+    DiagCapture warnings;
     const alphabeta::windows::ResidentSites sites = alphabeta::windows::parse_sites_resident(
         alphabeta::default_device(), std::string(text, (size_t)len), (size_t)skip_lines, slab_bytes);
-    if (warnings_out && wcap > 0) std::strncpy(warnings_out, warnings.c_str(), (size_t)wcap - 1), warnings_out[wcap - 1] = 0;
+    put_text(warnings_out, wcap, warnings.text);
     if ((long long)sites.size() > cap) return -1;
     static_assert(sizeof(long long) == sizeof(int64_t), "line numbers");
     alphabeta::default_device().check(
@@ -710,45 +705,23 @@ int abh_windows_resident_ab(const char* annotation, long long alen, const char* 
     const abn_windows_params p =
         w::window_params(cutoff, step, size, absolute != 0, absolute ? genome.max_gene_length : 100u);
     alphabeta::Device& dev = alphabeta::default_device();
-    auto now = []() { return std::chrono::steady_clock::now(); };
-    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    std::string warnings;  // (both sides print the invalid-status warnings; kept off the console)
-    alphabeta::detail::diag_sink() = &warnings;
-    struct Unsink {
-      ~Unsink() { alphabeta::detail::diag_sink() = nullptr; }
-    } unsink;
+    DiagCapture quiet;  // (both sides print the invalid-status warnings; kept off the console)
     std::unique_ptr<w::Handle> host, device;
     if (which & 1) {
-      const auto t0 = now();
+      const Stopwatch watch;
       host = std::make_unique<w::Handle>(dev, p, genome, rule, posterior_max_filter, w::parse_sites_many(held, &dev));
-      ms2[0] = ms(t0, now());
+      ms2[0] = watch.ms();
     }
     if (which & 2) {
-      const auto t0 = now();
+      const Stopwatch watch;
       std::vector<w::ResidentSites> sites;
       for (const std::string& text : held) sites.push_back(w::parse_sites_resident(dev, text));
       device = std::make_unique<w::Handle>(dev, p, genome, rule, posterior_max_filter, sites);
-      ms2[1] = ms(t0, now());
+      ms2[1] = watch.ms();
       abn_windows_merge_ms(device->get(), kernel_ms2);
     }
     if ((which & 3) != 3) return 1;
-    auto same_bits = [](const std::vector<double>& x, const std::vector<double>& y) {
-      return x.size() == y.size() && (x.empty() || std::memcmp(x.data(), y.data(), 8 * x.size()) == 0);
-    };
-    if (host->count != device->count || host->kept != device->kept || host->ragged != device->ragged ||
-        !same_bits(host->level_sum, device->level_sum) || !same_bits(host->level_sum_kept, device->level_sum_kept))
-      return 0;
-    int64_t stride[2] = {0, 0};
-    abn_windows_info(host->get(), nullptr, &stride[0], nullptr);
-    abn_windows_info(device->get(), nullptr, &stride[1], nullptr);
-    if (stride[0] != stride[1]) return 0;
-    std::vector<uint8_t> pa(held.size() * (size_t)stride[0]), pb(pa.size());
-    dev.check(abn_windows_packed(host->get(), pa.data()), "abn_windows_packed");
-    dev.check(abn_windows_packed(device->get(), pb.data()), "abn_windows_packed");
-    std::vector<int64_t> ba(host->n_windows()), ea(ba.size()), bb(ba.size()), eb(ba.size());
-    abn_windows_layout(host->get(), ba.data(), ea.data(), nullptr);
-    abn_windows_layout(device->get(), bb.data(), eb.data(), nullptr);
-    return pa == pb && ba == bb && ea == eb ? 1 : 0;
+    return same_handles(dev, *host, *device);
   } catch (const std::exception&) {
     return -1;
   }
@@ -784,8 +757,7 @@ int abh_analyze(const double* rows, long long n_boot, double* mean_alpha, char* 
     *mean_alpha = r.analyze().alpha;
     return 0;
   } catch (const std::exception& e) {
-    if (err && errcap > 0) std::strncpy(err, e.what(), (size_t)errcap - 1), err[errcap - 1] = 0;
-    return -1;
+    return failed(err, errcap, e);
   }
 }
 int abh_write_npy(const char* path, const double* rows, long long n_boot) {
@@ -827,7 +799,7 @@ int abh_route_launch(int n, int k, int t, int lanes, int strict, int spec, int p
   o.parking = parking != 0;
   o.pass = pass;
   const abn::LaunchRoute r = abn::route_launch(p, abn::PhaseRoute{spec != 0, phase_lanes, false}, chains, cus, o);
-  if (err && errcap > 0) std::strncpy(err, r.error ? r.error : "", (size_t)errcap - 1), err[errcap - 1] = 0;
+  put_text(err, errcap, r.error ? r.error : "");
   const long long v[15] = {r.kind, r.key.family, r.key.G, r.key.R, r.key.tp, r.key.strict, r.key.resume, r.grid, r.block,
                            (long long)r.lds, r.chain_stride, r.tree, r.quantum, r.tail_cap,
                            r.tail_cap > 0 ? abn::route_tail_resume(p, r.tail_cap).key.R : 0};
@@ -845,7 +817,7 @@ int abh_route_launch_sweep(int n, int k, int t, int lanes, int strict, int spec,
   o.pass = pass;
   o.sweep = sweep != 0;
   const abn::LaunchRoute r = abn::route_launch(p, abn::PhaseRoute{spec != 0, phase_lanes, false}, chains, cus, o);
-  if (err && errcap > 0) std::strncpy(err, r.error ? r.error : "", (size_t)errcap - 1), err[errcap - 1] = 0;
+  put_text(err, errcap, r.error ? r.error : "");
   const long long v[15] = {r.kind, r.key.family, r.key.G, r.key.R, r.key.tp, r.key.strict, r.key.resume, r.grid, r.block,
                            (long long)r.lds, r.chain_stride, r.tree, r.quantum, r.tail_cap,
                            r.tail_cap > 0 ? abn::route_tail_resume(p, r.tail_cap).key.R : 0};

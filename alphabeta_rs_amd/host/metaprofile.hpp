@@ -86,24 +86,45 @@ inline std::string results_line(const std::string& name, size_t window, long lon
          fmt_f64(a.ci_alpha.hi) + ";" + fmt_f64(a.ci_beta.lo) + ";" + fmt_f64(a.ci_beta.hi) + "\n";
 }
 
+inline uint32_t window_step(const WindowArgs& args) {  // src/cli/metaprofile.rs:18-20, src/extract.rs:26-28
+  return args.window_step == 0 ? args.window_size : args.window_step;
+}
+
+// The (region, window) enumeration of src/cli/metaprofile.rs:34-53, in its order: `window` = 0, step, .. below the region's
+// max.  It names ceil(max / step) windows per region where Windows::new (src/windows.rs:28-44) creates floor(max / step):
+// created = this one exists, and then w is its place among the created ones (upstream, gene, downstream).
+struct NamedWindow {
+  std::string region;
+  uint32_t window;
+  bool created;
+  size_t w;
+};
+inline std::vector<NamedWindow> enumerate_windows(const WindowArgs& args, uint32_t max_gene_length) {
+  const uint32_t step = window_step(args);
+  const std::pair<const char*, uint32_t> regions[3] = {{"upstream", args.cutoff}, {"gene", max_gene_length}, {"downstream", args.cutoff}};
+  std::vector<NamedWindow> out;
+  size_t first = 0;
+  for (const auto& region : regions) {
+    const uint32_t max = args.absolute ? region.second : 100, count = step ? max / step : 0;
+    for (uint32_t window = 0, k = 0; window < max; window += step, ++k)
+      out.push_back(NamedWindow{region.first, window, k < count, first + k});
+    first += count;
+  }
+  return out;
+}
+
 // src/cli/metaprofile.rs:33-114
 inline Output alphabeta_multiple(const WindowArgs& args, uint32_t max_gene_length, const std::vector<int>& distribution) {
   namespace fs = std::filesystem;
-  const uint32_t step = args.window_step == 0 ? args.window_size : args.window_step;
-  const std::vector<std::pair<std::string, uint32_t>> regions = {
-      {"upstream", args.cutoff}, {"gene", max_gene_length}, {"downstream", args.cutoff}};  // :34-38
   std::vector<Win> wins;
   // every (region, window) directory in the reference's order; all pedigrees are built together (Pedigree::build_many:
   // one batched pairwise scan instead of one per window), then reported in that order, each window's diagnostics first
   std::vector<std::pair<std::string, std::string>> lists;
   std::vector<std::string> region_of;
-  for (const auto& region : regions) {
-    const uint32_t max = args.absolute ? region.second : 100;
-    for (uint32_t window = 0; window < max; window += step) {
-      const fs::path dir = fs::path(args.output_dir) / region.first / std::to_string(window);
-      lists.push_back({(dir / "nodelist.txt").string(), (dir / "edgelist.txt").string()});
-      region_of.push_back(region.first);
-    }
+  for (const NamedWindow& nw : enumerate_windows(args, max_gene_length)) {
+    const fs::path dir = fs::path(args.output_dir) / nw.region / std::to_string(nw.window);
+    lists.push_back({(dir / "nodelist.txt").string(), (dir / "edgelist.txt").string()});
+    region_of.push_back(nw.region);
   }
   std::vector<Pedigree::Built> built = Pedigree::build_many(lists, args.posterior_max_filter, /*gpu_pairwise=*/true, args.device_parse);
   for (size_t index = 0; index < built.size(); ++index) {
@@ -232,40 +253,6 @@ struct Extraction {
   std::vector<int> distribution;  // the first methylome's window counts (src/extract.rs:154)
 };
 
-// nodelist and edgelist as detail::read_inputs reads them (src/pedigree.rs:98-136), without opening a methylome
-inline detail::Inputs read_graph(const std::string& nodelist, const std::string& edgelist) {
-  using namespace detail;
-  Inputs in;
-  const std::string nodes_txt = read_file(nodelist, "nodelist"), edges_txt = read_file(edgelist, "edgelist");
-  {
-    const auto lines = split_any(nodes_txt, "\n\r");
-    for (size_t li = 1; li < lines.size(); ++li) {
-      const auto e = split_any(lines[li], ",\t ");
-      if (e.size() < 4) continue;
-      uint32_t gen;
-      if (!parse_u32(e[2], gen)) continue;
-      in.all.push_back(Node{li - 1, e[0], e[1], gen, e[3] == "Y", 0.0, {}});
-    }
-  }
-  if (in.all.empty()) throw Error(ABN_ERR_INVALID_ARG, "No nodes could be parsed from the nodelist");
-  {
-    const auto lines = split_any(edges_txt, "\n\r");
-    for (size_t li = 1; li < lines.size(); ++li) {
-      const auto e = split_any(lines[li], "\t ,");
-      if (e.size() < 2) continue;
-      size_t f = in.all.size(), t = in.all.size();
-      for (size_t k = 0; k < in.all.size(); ++k) {
-        if (f == in.all.size() && in.all[k].name == e[0]) f = k;
-        if (t == in.all.size() && in.all[k].name == e[1]) t = k;
-      }
-      if (f < in.all.size() && t < in.all.size()) in.edges.push_back(EdgeRef{f, t});
-    }
-  }
-  for (const auto& n : in.all)
-    if (n.meth) in.nodes.push_back(n);
-  return in;
-}
-
 // src/extract.rs:17-155: parse the annotation and every methylome once, choose every site's gene (on the host, or with
 // device_genes on the device; with device_sites the parsed records never leave it), place the sites into windows on the
 // device; write distribution_<name>, distributions.txt, steady_state_methylation.txt and
@@ -273,7 +260,7 @@ inline detail::Inputs read_graph(const std::string& nodelist, const std::string&
 inline Extraction extract_in_memory(const WindowArgs& args) {
   namespace fs = std::filesystem;
   if (args.invert) throw Error(ABN_ERR_INVALID_ARG, "--invert is not supported with --methylome");
-  const uint32_t step = args.window_step == 0 ? args.window_size : args.window_step;  // :26-28
+  const uint32_t step = window_step(args);
   if (step == 0) throw Error(ABN_ERR_INVALID_ARG, "window step and window size are both 0");
   Extraction ex;
   // files::load_methylome (src/files.rs:23-38): files with an extension other than *tsv* / *fn*
@@ -314,20 +301,12 @@ inline Extraction extract_in_memory(const WindowArgs& args) {
   if (args.device_sites) {
     // every text goes up, its records stay there; it is dropped as soon as its deferred lines are decided
     const windows::GeneRule rule{args.cutoff, args.cutoff_gene_length};
-    std::vector<windows::ResidentSites> sites;
-    for (const auto& name : ex.names)
-      sites.push_back(windows::parse_sites_resident(default_device(),
-                                                    detail::read_file((fs::path(args.methylome) / name).string(), "methylome")));
-    ex.handle = std::make_unique<windows::Handle>(default_device(), ex.params, genome, rule, args.posterior_max_filter, sites,
-                                                  args.align);
-    if (args.align == Align::Position)
-      for (size_t s = 0; s < ex.names.size(); ++s)
-        std::printf("Aligned by position: %s: %lld sites, %lld kept\n", ex.names[s].c_str(),
-                    (long long)ex.handle->before[s], (long long)ex.handle->n_common);
-    if (args.align == Align::Union)
-      for (size_t s = 0; s < ex.names.size(); ++s)
-        std::printf("Aligned by union: %s: %lld sites, %lld in the union\n", ex.names[s].c_str(),
-                    (long long)ex.handle->before[s], (long long)ex.handle->n_union);
+    resident::Samples samples{default_device(), /*skip_lines=*/1, {}};
+    for (const auto& name : ex.names) samples.add_text(detail::read_file((fs::path(args.methylome) / name).string(), "methylome"));
+    ex.handle = std::make_unique<windows::Handle>(default_device(), ex.params, genome, rule, args.posterior_max_filter,
+                                                  samples.sites, args.align);
+    for (const std::string& line : resident::align_report(args.align, ex.names, resident::align_counts(*ex.handle, args.align)))
+      std::fputs(line.c_str(), stdout);
   } else {
     std::vector<std::string> texts;
     for (const auto& name : ex.names) texts.push_back(detail::read_file((fs::path(args.methylome) / name).string(), "methylome"));
@@ -375,70 +354,81 @@ inline Extraction extract_in_memory(const WindowArgs& args) {
   return ex;
 }
 
+// One window's (or tile's) pedigree from what a handle reports: level_sum_kept and kept [n_samples x n_windows], and dv,
+// window w's D values for the n_samples * (n_samples - 1) / 2 pairs of samples in the scan's order.  sample_of: the sample
+// of every sampled node; times: detail::convert_times of the graph.  p0uu as src/pedigree.rs:165-166,180-184 folds it.
+// Two nodes that name one sample have no pair in the scan: their D is 0, or NaN when the sample kept no site.
+inline Win window_from_handle(const std::string& region, size_t index, const std::vector<detail::PairTimes>& times,
+                              const std::vector<size_t>& sample_of, size_t n_samples, size_t n_windows, size_t w,
+                              const std::vector<double>& level_sum_kept, const std::vector<int64_t>& kept, const double* dv) {
+  const size_t nn = sample_of.size(), n = n_samples, W = n_windows;
+  std::vector<double> dm(nn * nn, 0.0);
+  double p0 = 0.0;
+  for (size_t a = 0; a < nn; ++a) {
+    const size_t sa = sample_of[a];
+    p0 += 1.0 - level_sum_kept[sa * W + w] / (double)kept[sa * W + w];
+    for (size_t b = a + 1; b < nn; ++b) {
+      const size_t sb = sample_of[b], i = std::min(sa, sb), j = std::max(sa, sb);
+      dm[a * nn + (b - a - 1)] = i == j ? (kept[sa * W + w] > 0 ? 0.0 : std::nan("")) : dv[i * n - i * (i + 1) / 2 + (j - i - 1)];
+    }
+  }
+  Pedigree ped = detail::rows_from(times, dm, nn);
+  if (ped.nrows() == 0) throw Error(ABN_ERR_BAD_PEDIGREE, "empty pedigree");
+  return Win{region, std::move(ped), p0 / (double)nn, index};
+}
+
 // alphabeta_multiple (src/cli/metaprofile.rs:33-114) on an Extraction: the pedigrees and p0uu come from the handle — one
-// scan of the resident matrix for all windows, detail::convert once per window on its D values — instead of
-// Pedigree::build_many on window directories.  Window ids stay the position in the (region, window) enumeration of
-// :50-53, which names ceil(max / step) windows per region where Windows::new creates floor(max / step): the window the
-// enumeration names beyond those fails as its missing sample file fails there.  A RAGGED window (the samples' site counts
-// differ) fails too; the reference goes on with D = 0 for its pairs (DESIGN.md §4 "Window placement").  With args.align
-// the handle holds only the sites every sample shares, or every sample the union of all sites, so no window is ragged.
+// scan of the resident matrix for all windows, detail::convert_times once for the graph they share — instead of
+// Pedigree::build_many on window directories.  Window ids stay the position in the enumeration (enumerate_windows): the
+// window it names beyond those created fails as its missing sample file fails there.  A RAGGED window (the samples' site
+// counts differ) fails too; the reference goes on with D = 0 for its pairs (DESIGN.md §4 "Window placement").  With
+// args.align the handle holds only the sites every sample shares, or every sample the union of all sites, so no window is
+// ragged.  A graph DMatrix::convert refuses is reported at every window that gets as far as the conversion — each window
+// is a run of the reference's, which fails there — and the run goes on to its empty result.
 inline Output alphabeta_multiple_in_memory(const WindowArgs& args, const Extraction& ex) {
   namespace fs = std::filesystem;
   const windows::Handle& h = *ex.handle;
   const size_t n = h.n_samples(), W = h.n_windows(), npairs = n * (n - 1) / 2;
-  const detail::Inputs graph = read_graph(args.nodes, args.edges);
+  const detail::Inputs graph = detail::read_graph(args.nodes, args.edges);
   const size_t nn = graph.nodes.size();
-  auto base_name = [](const std::string& p) { return p.substr(p.find_last_of('/') == std::string::npos ? 0 : p.find_last_of('/') + 1); };
   std::vector<size_t> sample_of(nn);
   for (size_t i = 0; i < nn; ++i) {
-    const auto it = std::find(ex.names.begin(), ex.names.end(), base_name(graph.nodes[i].file));
+    const auto it = std::find(ex.names.begin(), ex.names.end(), resident::base_name(graph.nodes[i].file));
     if (it == ex.names.end()) throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " + graph.nodes[i].file);
     sample_of[i] = (size_t)(it - ex.names.begin());
   }
   std::vector<double> dv(std::max<size_t>(W * npairs, 1), 0.0);
   default_device().check(abn_windows_pairwise(h.get(), nullptr, nullptr, dv.data()), "abn_windows_pairwise");
-  const uint32_t step = ex.params.step;
-  const std::vector<std::tuple<std::string, uint32_t, size_t, size_t>> regions = {
-      {"upstream", args.cutoff, 0, (size_t)ex.params.n_upstream},
-      {"gene", ex.max_gene_length, (size_t)ex.params.n_upstream, (size_t)ex.params.n_gene},
-      {"downstream", args.cutoff, (size_t)ex.params.n_upstream + (size_t)ex.params.n_gene, (size_t)ex.params.n_downstream}};
+  std::vector<detail::PairTimes> times;
+  std::unique_ptr<Error> graph_refused;  // what convert throws from the graph alone
+  try {
+    times = detail::convert_times(graph);
+  } catch (const Error& e) {
+    graph_refused = std::make_unique<Error>(e);
+  }
   std::vector<Win> wins;
-  size_t index = 0;
-  for (const auto& [region, region_max, first, count] : regions) {
-    const uint32_t max = args.absolute ? region_max : 100;
-    for (uint32_t window = 0, k = 0; window < max; window += step, ++k, ++index) {
-      try {
-        if (k >= count)  // named by the enumeration, not created by Windows::new: no sample file in that directory
-          throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " +
-                                               (fs::path(args.output_dir) / region / std::to_string(window) /
-                                                (nn ? base_name(graph.nodes[0].file) : std::string()))
-                                                   .string());
-        const size_t w = first + k;
-        if (h.ragged[w]) {
-          for (size_t a = 0; a < nn; ++a)
-            for (size_t b = a + 1; b < nn; ++b)
-              if (h.count[sample_of[a] * W + w] != h.count[sample_of[b] * W + w])
-                std::printf("Lengths do not match, all bets are off: %zu vs %zu\n", (size_t)h.count[sample_of[a] * W + w],
-                            (size_t)h.count[sample_of[b] * W + w]);
-          throw Error(ABN_ERR_INVALID_ARG, "the samples' site counts differ in this window");
-        }
-        std::vector<double> dm(nn * nn, 0.0);
-        double p0 = 0.0;
-        for (size_t a = 0; a < nn; ++a) {
-          const size_t sa = sample_of[a];
-          p0 += 1.0 - h.level_sum_kept[sa * W + w] / (double)h.kept[sa * W + w];  // src/pedigree.rs:165-166,180-184
-          for (size_t b = a + 1; b < nn; ++b) {
-            const size_t sb = sample_of[b], i = std::min(sa, sb), j = std::max(sa, sb);
-            dm[a * nn + (b - a - 1)] = i == j ? (h.kept[sa * W + w] > 0 ? 0.0 : std::nan(""))
-                                              : dv[w * npairs + i * n - i * (i + 1) / 2 + (j - i - 1)];
-          }
-        }
-        Pedigree ped = detail::convert(graph, dm);
-        if (ped.nrows() == 0) throw Error(ABN_ERR_BAD_PEDIGREE, "empty pedigree");
-        wins.push_back(Win{region, std::move(ped), p0 / (double)nn, index});
-      } catch (const std::exception& e) {
-        std::printf("Error: Error while building pedigree: %s\n", e.what());
+  const std::vector<NamedWindow> named = enumerate_windows(args, ex.max_gene_length);
+  for (size_t index = 0; index < named.size(); ++index) {
+    const NamedWindow& nw = named[index];
+    try {
+      if (!nw.created)  // no sample file in that directory
+        throw Error(ABN_ERR_INVALID_ARG,
+                    "Could not open node file: " + (fs::path(args.output_dir) / nw.region / std::to_string(nw.window) /
+                                                    (nn ? resident::base_name(graph.nodes[0].file) : std::string()))
+                                                       .string());
+      const size_t w = nw.w;
+      if (h.ragged[w]) {
+        for (size_t a = 0; a < nn; ++a)
+          for (size_t b = a + 1; b < nn; ++b)
+            if (h.count[sample_of[a] * W + w] != h.count[sample_of[b] * W + w])
+              std::printf("Lengths do not match, all bets are off: %zu vs %zu\n", (size_t)h.count[sample_of[a] * W + w],
+                          (size_t)h.count[sample_of[b] * W + w]);
+        throw Error(ABN_ERR_INVALID_ARG, "the samples' site counts differ in this window");
       }
+      if (graph_refused) throw *graph_refused;
+      wins.push_back(window_from_handle(nw.region, index, times, sample_of, n, W, w, h.level_sum_kept, h.kept, &dv[w * npairs]));
+    } catch (const std::exception& e) {
+      std::printf("Error: Error while building pedigree: %s\n", e.what());
     }
   }
   return fit_windows(args, std::move(wins), ex.distribution);

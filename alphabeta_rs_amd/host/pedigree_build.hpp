@@ -224,7 +224,7 @@ inline Inputs read_inputs(const std::string& nodelist, const std::string& edgeli
   return in;
 }
 
-// The same Inputs with the sites left on the device (--sites device; defined in windows_extract.hpp on
+// The same Inputs with the sites left on the device (--sites device; defined in resident.hpp on
 // windows::parse_sites_resident and abn_codes_create_parsed): every sampled node's methylome is parsed into a resident
 // handle, the code matrix is packed and rc_meth_lvl folded there, and the D matrix comes from abn_codes_pairwise — no
 // site reaches the host.  Samples of different length, or fewer than two: the handles are fetched into Inputs and the D
@@ -430,9 +430,34 @@ inline Pedigree convert(const Inputs& in, const std::vector<double>& dm) {
   return ped;
 }
 
-}  // namespace detail
+// What convert makes of the graph alone: for every row it would emit, the pair (i, j) of sampled nodes and (t0, t1, t2).
+// The windows, or tiles, of one run share one nodelist and edgelist, so the shortest-path searches run once, not once per
+// window.  (convert itself on a D matrix whose entries are their own indices: the rows it emits and their order are
+// convert's by construction, and so is what it throws.)
+struct PairTimes {
+  size_t i, j;
+  double t0, t1, t2;
+};
+inline std::vector<PairTimes> convert_times(const Inputs& graph) {
+  const size_t nn = graph.nodes.size();
+  std::vector<double> where(nn * nn, 0.0);
+  for (size_t i = 0; i < nn; ++i)
+    for (size_t j = i + 1; j < nn; ++j) where[i * nn + (j - i - 1)] = (double)(i * nn + j);  // exact: far below 2^53
+  const Pedigree p = convert(graph, where);
+  std::vector<PairTimes> out;
+  for (size_t r = 0; r < p.nrows(); ++r) {
+    const size_t at = (size_t)p.at(r, 3);
+    out.push_back(PairTimes{at / nn, at % nn, p.at(r, 0), p.at(r, 1), p.at(r, 2)});
+  }
+  return out;
+}
+// convert(graph, dm), bit for bit, from convert_times(graph); nn = graph.nodes.size()
+inline Pedigree rows_from(const std::vector<PairTimes>& times, const std::vector<double>& dm, size_t nn) {
+  Pedigree ped;
+  for (const PairTimes& t : times) ped.push_row(t.t0, t.t1, t.t2, dm[t.i * nn + (t.j - t.i - 1)]);
+  return ped;
+}
 
-namespace detail {
 // Pedigree::build; texts: as read_inputs
 inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, const std::string& edgelist,
                                                   double posterior_max_filter, bool gpu_pairwise, bool device_parse,

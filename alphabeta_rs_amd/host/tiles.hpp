@@ -11,38 +11,6 @@
 #include "metaprofile.hpp"
 
 namespace alphabeta {
-namespace detail {
-
-// What DMatrix::convert (src/pedigree.rs:263-337) makes of the graph alone: for every row convert would emit, the pair
-// (i, j) of sampled nodes and (t0, t1, t2).  All tiles share one nodelist and edgelist, so the shortest-path searches run
-// once, not once per tile.  (convert itself on a D matrix whose entries are their own indices: the rows it emits and
-// their order are convert's by construction.)
-struct PairTimes {
-  size_t i, j;
-  double t0, t1, t2;
-};
-inline std::vector<PairTimes> convert_times(const Inputs& graph) {
-  const size_t nn = graph.nodes.size();
-  std::vector<double> where(nn * nn, 0.0);
-  for (size_t i = 0; i < nn; ++i)
-    for (size_t j = i + 1; j < nn; ++j) where[i * nn + (j - i - 1)] = (double)(i * nn + j);  // exact: far below 2^53
-  const Pedigree p = convert(graph, where);
-  std::vector<PairTimes> out;
-  for (size_t r = 0; r < p.nrows(); ++r) {
-    const size_t at = (size_t)p.at(r, 3);
-    out.push_back(PairTimes{at / nn, at % nn, p.at(r, 0), p.at(r, 1), p.at(r, 2)});
-  }
-  return out;
-}
-// convert(graph, dm), bit for bit, from convert_times(graph); nn = graph.nodes.size()
-inline Pedigree rows_from(const std::vector<PairTimes>& times, const std::vector<double>& dm, size_t nn) {
-  Pedigree ped;
-  for (const PairTimes& t : times) ped.push_row(t.t0, t.t1, t.t2, dm[t.i * nn + (t.j - t.i - 1)]);
-  return ped;
-}
-
-}  // namespace detail
-
 namespace metaprofile {
 
 struct TileArgs {
@@ -101,24 +69,14 @@ struct TilesOutput {
   std::string tiles_txt;  // tile;chromosome;start;end;cg_count;fitted, every tile of the list
 };
 
-class TilesHandle {  // RAII abn_tiles
- public:
-  TilesHandle() = default;
-  TilesHandle(const TilesHandle&) = delete;
-  TilesHandle& operator=(const TilesHandle&) = delete;
-  ~TilesHandle() {
-    if (h) abn_tiles_destroy(h);
-  }
-  abn_tiles* h = nullptr;
-};
-
 // The sibling of alphabeta_multiple_in_memory for tiles.  args: methylome (directory), nodes, edges, align, iterations,
 // posterior_max_filter, name.  A tile without a column, with a sampled node that has no counted site, or with a sampled
-// pair that shares no compared site is reported and skipped; the others go on (src/cli/metaprofile.rs:64-65).
+// pair that shares no compared site is reported and skipped; the others go on (src/cli/metaprofile.rs:64-65).  A graph
+// DMatrix::convert refuses ends the run.
 inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileArgs& tiles) {
   namespace fs = std::filesystem;
   Device& dev = default_device();
-  const detail::Inputs graph = read_graph(args.nodes, args.edges);
+  const detail::Inputs graph = detail::read_graph(args.nodes, args.edges);
   const size_t nn = graph.nodes.size(), npairs = nn * (nn - 1) / 2;
   if (nn == 0) throw Error(ABN_ERR_INVALID_ARG, "the nodelist names no sampled node");
   TileList list;
@@ -126,46 +84,36 @@ inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileAr
     list = read_regions(detail::read_file(tiles.regions, "regions"));
     if (list.size() == 0) throw Error(ABN_ERR_INVALID_ARG, "Could not parse a single region from " + tiles.regions);
   }
-  auto base_name = [](const std::string& p) { return p.substr(p.find_last_of('/') == std::string::npos ? 0 : p.find_last_of('/') + 1); };
   // every sampled node's methylome, every line read (src/pedigree.rs:147-163), its records left on the device
-  std::vector<windows::ResidentSites> sites;
+  resident::Samples samples{dev, /*skip_lines=*/0, {}};
   std::vector<std::string> names;
+  std::vector<size_t> sample_of;
   for (const auto& node : graph.nodes) {
-    names.push_back(base_name(node.file));
-    const std::string path = (fs::path(args.methylome) / names.back()).string();
-    if (!std::ifstream(path)) throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " + path);
-    sites.push_back(windows::parse_sites_resident(dev, detail::read_file(path, "methylome"), /*skip_lines=*/0));
+    sample_of.push_back(names.size());
+    names.push_back(resident::base_name(node.file));
+    samples.add_file((fs::path(args.methylome) / names.back()).string());
   }
-  std::vector<abn_sites*> handles;
-  for (const auto& s : sites) handles.push_back(s.get());
-  TilesHandle th;
-  const int32_t align = args.align == Align::Union ? 2 : (args.align == Align::Position ? 1 : 0);
-  dev.check(abn_tiles_create(dev.get(), args.posterior_max_filter, align, (int32_t)nn, handles.data(), &th.h), "abn_tiles_create");
-  int64_t n_columns = 0;
-  abn_tiles_info(th.h, nullptr, &n_columns, nullptr, nullptr, nullptr);
-  if (args.align == Align::Position)
-    for (size_t s = 0; s < nn; ++s)
-      std::printf("Aligned by position: %s: %lld sites, %lld kept\n", names[s].c_str(), (long long)sites[s].size(), (long long)n_columns);
-  if (args.align == Align::Union)
-    for (size_t s = 0; s < nn; ++s)
-      std::printf("Aligned by union: %s: %lld sites, %lld in the union\n", names[s].c_str(), (long long)sites[s].size(),
-                  (long long)n_columns);
+  Owned<abn_tiles, abn_tiles_destroy> th;
+  dev.check(abn_tiles_create(dev.get(), args.posterior_max_filter, (int32_t)args.align, (int32_t)nn, samples.pointers().data(), th.out()),
+            "abn_tiles_create");
+  for (const std::string& line : resident::align_report(args.align, names, resident::align_counts(th.get(), samples.sites)))
+    std::fputs(line.c_str(), stdout);
   if (tiles.fixed())
-    dev.check(abn_tiles_set_fixed(th.h, tiles.size, tiles.step), "abn_tiles_set_fixed");
+    dev.check(abn_tiles_set_fixed(th.get(), tiles.size, tiles.step), "abn_tiles_set_fixed");
   else
-    dev.check(abn_tiles_set_intervals(th.h, (int64_t)list.size(), list.chromosome.data(), list.start.data(), list.end.data()),
+    dev.check(abn_tiles_set_intervals(th.get(), (int64_t)list.size(), list.chromosome.data(), list.start.data(), list.end.data()),
               "abn_tiles_set_intervals");
   int64_t n_tiles = 0;
-  abn_tiles_info(th.h, nullptr, nullptr, nullptr, nullptr, &n_tiles);
+  abn_tiles_info(th.get(), nullptr, nullptr, nullptr, nullptr, &n_tiles);
   const size_t T = (size_t)n_tiles;
   if (T == 0) throw Error(ABN_ERR_INVALID_ARG, "no tile: the methylomes hold no site");
   list.chromosome.resize(T), list.start.resize(T), list.end.resize(T);
-  dev.check(abn_tiles_intervals(th.h, list.chromosome.data(), list.start.data(), list.end.data()), "abn_tiles_intervals");
+  dev.check(abn_tiles_intervals(th.get(), list.chromosome.data(), list.start.data(), list.end.data()), "abn_tiles_intervals");
   std::vector<int64_t> count(T), kept(nn * T);
   std::vector<double> sum(nn * T), dv(std::max<size_t>(T * npairs, 1), 0.0);
   std::vector<uint64_t> both(std::max<size_t>(T * npairs, 1), 0);
-  dev.check(abn_tiles_stats(th.h, count.data(), sum.data(), kept.data()), "abn_tiles_stats");
-  dev.check(abn_tiles_pairwise(th.h, nullptr, both.data(), dv.data()), "abn_tiles_pairwise");
+  dev.check(abn_tiles_stats(th.get(), count.data(), sum.data(), kept.data()), "abn_tiles_stats");
+  dev.check(abn_tiles_pairwise(th.get(), nullptr, both.data(), dv.data()), "abn_tiles_pairwise");
 
   const std::vector<detail::PairTimes> times = detail::convert_times(graph);
   std::vector<Win> wins;
@@ -173,19 +121,14 @@ inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileAr
     const std::string region = tile_region(list.chromosome[t], list.start[t], list.end[t]);
     try {
       if (count[t] == 0) throw Error(ABN_ERR_INVALID_ARG, "no site lies in this tile");
-      double p0 = 0.0;
-      for (size_t a = 0; a < nn; ++a) {
+      for (size_t a = 0; a < nn; ++a)
         if (kept[a * T + t] == 0)
           throw Error(ABN_ERR_INVALID_ARG, names[a] + " has no site above the posterior filter in this tile");
-        p0 += 1.0 - sum[a * T + t] / (double)kept[a * T + t];  // src/pedigree.rs:165-166, 180-184
-      }
       for (size_t a = 0, p = 0; a < nn; ++a)
         for (size_t b = a + 1; b < nn; ++b, ++p)
           if (both[t * npairs + p] == 0)
             throw Error(ABN_ERR_INVALID_ARG, names[a] + " and " + names[b] + " share no site above the posterior filter in this tile");
-      Pedigree ped = detail::rows_from(times, detail::dmatrix_of_pairs(nn, &dv[t * npairs]), nn);
-      if (ped.nrows() == 0) throw Error(ABN_ERR_BAD_PEDIGREE, "empty pedigree");
-      wins.push_back(Win{region, std::move(ped), p0 / (double)nn, t});
+      wins.push_back(window_from_handle(region, t, times, sample_of, nn, T, t, sum, kept, &dv[t * npairs]));
     } catch (const std::exception& e) {
       std::printf("Error: Error while building pedigree: tile %zu (%s): %s\n", t, region.c_str(), e.what());
     }

@@ -8,7 +8,8 @@
 // the same arrays either way.  Integer arithmetic wraps as the reference's release build does.  The line parse also runs
 // on the device (parse_sites_device over abn_sites_parse, csrc/abn_parse.hpp): the same FullSite sequence, fed to either
 // gene choice.  parse_sites_resident leaves that sequence on the device instead (abn_sites_parse_dev, abn_sites_insert),
-// for the Handle made from ResidentSites (abn_windows_create_parsed).
+// for the Handle made from ResidentSites (abn_windows_create_parsed); what is built from those handles — the three
+// align modes, their report, the pedigree build of `alphabeta --sites device` — is resident.hpp, included at the end.
 #pragma once
 
 #include <thread>
@@ -167,10 +168,7 @@ inline std::vector<FullSite> parse_sites_device(Device& dev, const std::string& 
   p.skip_lines = (int32_t)skip_lines;
   abn_sites* h = nullptr;
   dev.check(abn_sites_parse(dev.get(), text.data(), (int64_t)text.size(), &p, &h), "abn_sites_parse");
-  struct Guard {
-    abn_sites* h;
-    ~Guard() { abn_sites_destroy(h); }
-  } guard{h};
+  const Owned<abn_sites, abn_sites_destroy> guard(h);
   int64_t n = 0, nd = 0;
   abn_sites_info(h, &n, &nd, nullptr, nullptr);
   std::vector<int64_t> line((size_t)n), dline((size_t)nd), doff((size_t)nd), dlen((size_t)nd);
@@ -217,29 +215,14 @@ inline std::vector<FullSite> parse_sites_device(Device& dev, const std::string& 
   return out;
 }
 
-// RAII abn_sites in its resident form: one methylome's records on the device, its deferred lines decided and inserted
-class ResidentSites {
- public:
-  explicit ResidentSites(abn_sites* h = nullptr) : h_(h) {}
-  ResidentSites(ResidentSites&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
-  ResidentSites& operator=(ResidentSites&& o) noexcept {
-    std::swap(h_, o.h_);
-    return *this;
-  }
-  ResidentSites(const ResidentSites&) = delete;
-  ResidentSites& operator=(const ResidentSites&) = delete;
-  ~ResidentSites() {
-    if (h_) abn_sites_destroy(h_);
-  }
-  abn_sites* get() const { return h_; }
+// abn_sites in its resident form: one methylome's records on the device, its deferred lines decided and inserted
+struct ResidentSites : Owned<abn_sites, abn_sites_destroy> {
+  using Owned::Owned;
   size_t size() const {  // the sites of the merged sequence
     int64_t n = 0;
-    abn_sites_info(h_, &n, nullptr, nullptr, nullptr);
+    abn_sites_info(get(), &n, nullptr, nullptr, nullptr);
     return (size_t)n;
   }
-
- private:
-  abn_sites* h_;
 };
 
 // ... parsed on the device and LEFT there (abn_sites_parse_dev): the sequence parse_sites_device yields, as a handle.
@@ -540,24 +523,14 @@ inline SiteArrays site_arrays(const std::vector<std::vector<FullSite>>& samples,
   return a;
 }
 
-// RAII abn_genes over a Genome
-class GenesHandle {
- public:
+// abn_genes over a Genome
+struct GenesHandle : Owned<abn_genes, abn_genes_destroy> {
   GenesHandle(Device& dev, const Genome& genome) {
     const GeneLists l = flatten_genome(genome);
     dev.check(abn_genes_create(dev.get(), (int32_t)l.list_kind.size(), l.list_chromosome.data(), l.list_kind.data(),
-                               l.list_offset.data(), l.start.data(), l.end.data(), l.strand.data(), &h_),
+                               l.list_offset.data(), l.start.data(), l.end.data(), l.strand.data(), out()),
               "abn_genes_create");
   }
-  ~GenesHandle() {
-    if (h_) abn_genes_destroy(h_);
-  }
-  GenesHandle(const GenesHandle&) = delete;
-  GenesHandle& operator=(const GenesHandle&) = delete;
-  abn_genes* get() const { return h_; }
-
- private:
-  abn_genes* h_ = nullptr;
 };
 
 // RAII abn_windows over the samples' concatenated arrays
@@ -572,7 +545,7 @@ class Handle {
     const SiteArrays a = site_arrays(samples, posterior_max_filter);
     const abn_gene_rule r{rule.cutoff, rule.cutoff_gene_length ? 1 : 0};
     dev.check(abn_windows_create_sites(dev.get(), &p, genes.get(), &r, (int32_t)n_, a.offset.data(), a.chromosome.data(),
-                                       a.start.data(), a.end.data(), a.strand.data(), a.code.data(), a.level.data(), &h_),
+                                       a.start.data(), a.end.data(), a.strand.data(), a.code.data(), a.level.data(), h_.out()),
               "abn_windows_create_sites");
     fetch();
   }
@@ -581,25 +554,10 @@ class Handle {
   // strand), are placed (abn_windows_create_aligned): no window is ragged, and count, kept and the level sums — hence the
   // side files and every window's p0uu — describe the ALIGNED sites, not each file's own.  Align::Union: every sample gets
   // all the sites any sample holds, filtered placeholders where it lacks one (abn_windows_create_union): no window is
-  // ragged, count counts union sites, kept and level_sum_kept stay each file's own.
+  // ragged, count counts union sites, kept and level_sum_kept stay each file's own.  What the alignment made of the
+  // samples: resident::align_counts.  Defined in resident.hpp, on its table of the three create calls.
   Handle(Device& dev, const abn_windows_params& p, const Genome& genome, const GeneRule& rule, double posterior_max_filter,
-         const std::vector<ResidentSites>& samples, Align align = Align::None)
-      : n_(samples.size()) {
-    const GenesHandle genes(dev, genome);
-    const abn_gene_rule r{rule.cutoff, rule.cutoff_gene_length ? 1 : 0};
-    std::vector<abn_sites*> handles;
-    for (const ResidentSites& s : samples) handles.push_back(s.get());
-    if (align == Align::Union)
-      dev.check(abn_windows_create_union(dev.get(), &p, genes.get(), &r, posterior_max_filter, (int32_t)n_, handles.data(), &h_),
-                "abn_windows_create_union");
-    else if (align == Align::Position)
-      dev.check(abn_windows_create_aligned(dev.get(), &p, genes.get(), &r, posterior_max_filter, (int32_t)n_, handles.data(), &h_),
-                "abn_windows_create_aligned");
-    else
-      dev.check(abn_windows_create_parsed(dev.get(), &p, genes.get(), &r, posterior_max_filter, (int32_t)n_, handles.data(), &h_),
-                "abn_windows_create_parsed");
-    fetch();
-  }
+         const std::vector<ResidentSites>& samples, Align align = Align::None);
   Handle(Device& dev, const abn_windows_params& p, const std::vector<SampleSites>& samples) : n_(samples.size()) {
     std::vector<int64_t> off(n_ + 1, 0);
     for (size_t s = 0; s < n_; ++s) off[s + 1] = off[s] + (int64_t)samples[s].size();
@@ -613,42 +571,31 @@ class Handle {
       all.level.insert(all.level.end(), s.level.begin(), s.level.end());
     }
     dev.check(abn_windows_create(dev.get(), &p, (int32_t)n_, off.data(), all.pos.data(), all.gene_start.data(),
-                                 all.gene_end.data(), all.flags.data(), all.code.data(), all.level.data(), &h_),
+                                 all.gene_end.data(), all.flags.data(), all.code.data(), all.level.data(), h_.out()),
               "abn_windows_create");
     fetch();
   }
-  ~Handle() {
-    if (h_) abn_windows_destroy(h_);
-  }
-  Handle(const Handle&) = delete;
-  Handle& operator=(const Handle&) = delete;
-  abn_windows* get() const { return h_; }
+  abn_windows* get() const { return h_.get(); }
   size_t n_samples() const { return n_; }
   size_t n_windows() const { return W_; }
   std::vector<int64_t> count, kept;  // [n_samples x W]
   std::vector<double> level_sum, level_sum_kept;
   std::vector<int32_t> ragged;  // [W]
-  std::vector<int64_t> before;  // [n_samples]: every sample's sites as they came
-  int64_t n_common = -1;        // the sites every sample keeps; -1 without Align::Position
-  int64_t n_union = -1;         // the sites every sample has, placeholders included; -1 without Align::Union
 
  private:
   void fetch() {  // what the handle reports, to the vectors above
     int32_t W = 0;
-    abn_windows_info(h_, &W, nullptr, nullptr);
+    abn_windows_info(get(), &W, nullptr, nullptr);
     W_ = (size_t)W;
     count.resize(n_ * W_);
     kept.resize(n_ * W_);
     level_sum.resize(n_ * W_);
     level_sum_kept.resize(n_ * W_);
     ragged.resize(W_);
-    abn_windows_stats(h_, count.data(), level_sum.data(), level_sum_kept.data(), kept.data());
-    abn_windows_layout(h_, nullptr, nullptr, ragged.data());
-    before.resize(n_);
-    abn_windows_common(h_, before.data(), &n_common, nullptr);
-    abn_windows_union(h_, nullptr, &n_union, nullptr);
+    abn_windows_stats(get(), count.data(), level_sum.data(), level_sum_kept.data(), kept.data());
+    abn_windows_layout(get(), nullptr, nullptr, ragged.data());
   }
-  abn_windows* h_ = nullptr;
+  Owned<abn_windows, abn_windows_destroy> h_;
   size_t n_ = 0, W_ = 0;
 };
 
@@ -661,86 +608,7 @@ inline std::vector<Site> parse_sites_device_reduced(const std::string& text) {
     out.push_back(Site{s.posteriormax, s.status_numeric, s.meth_lvl});
   return out;
 }
-
-inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
-                                   std::vector<double>& dm, const std::vector<std::string>* texts, Align align) {
-  Inputs in = read_graph(nodelist, edgelist);
-  std::vector<Node>& nodes = in.nodes;
-  const size_t nn = nodes.size();
-  if (texts && texts->size() != nn) throw Error(ABN_ERR_INVALID_ARG, "one text per sampled node");
-  Device& dev = default_device();
-  std::vector<windows::ResidentSites> sites;  // src/pedigree.rs:147-163: every line is read, the warnings in file order
-  for (const Node& node : nodes) {
-    if (texts) {
-      sites.push_back(windows::parse_sites_resident(dev, (*texts)[sites.size()], /*skip_lines=*/0));
-      continue;
-    }
-    std::ifstream f(node.file);
-    if (!f) throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " + node.file);
-    std::ostringstream ss;
-    ss << f.rdbuf();
-    sites.push_back(windows::parse_sites_resident(dev, ss.str(), /*skip_lines=*/0));
-  }
-  struct Codes {
-    abn_codes* h = nullptr;
-    ~Codes() {
-      if (h) abn_codes_destroy(h);
-    }
-  } codes;
-  int32_t same_len = 1;
-  if (nn > 0) {
-    std::vector<abn_sites*> handles;
-    for (const auto& s : sites) handles.push_back(s.get());
-    if (align == Align::Union) {
-      dev.check(abn_codes_create_union(dev.get(), posterior_max_filter, (int32_t)nn, handles.data(), &codes.h),
-                "abn_codes_create_union");
-      std::vector<int64_t> before(nn);
-      int64_t n_union = 0;
-      abn_codes_union(codes.h, before.data(), &n_union, nullptr);
-      for (size_t i = 0; i < nn; ++i)
-        diag_printf("Aligned by union: %s: %lld sites, %lld in the union\n", nodes[i].file.c_str(), (long long)before[i],
-                    (long long)n_union);
-    } else if (align == Align::Position) {
-      dev.check(abn_codes_create_aligned(dev.get(), posterior_max_filter, (int32_t)nn, handles.data(), &codes.h),
-                "abn_codes_create_aligned");
-      std::vector<int64_t> before(nn);
-      int64_t n_common = 0;
-      abn_codes_common(codes.h, before.data(), &n_common, nullptr);
-      for (size_t i = 0; i < nn; ++i)
-        diag_printf("Aligned by position: %s: %lld sites, %lld kept\n", nodes[i].file.c_str(), (long long)before[i],
-                    (long long)n_common);
-    } else {
-      dev.check(abn_codes_create_parsed(dev.get(), posterior_max_filter, (int32_t)nn, handles.data(), &codes.h),
-                "abn_codes_create_parsed");
-    }
-    resident_build_calls().fetch_add(1, std::memory_order_relaxed);
-    std::vector<double> sum(nn);
-    std::vector<int64_t> kept(nn);
-    abn_codes_stats(codes.h, nullptr, sum.data(), kept.data());
-    abn_codes_info(codes.h, nullptr, nullptr, nullptr, &same_len);
-    abn_codes_kernel_ms(codes.h, resident_kernel_ms());
-    for (size_t i = 0; i < nn; ++i) nodes[i].rc_meth_lvl = sum[i] / (double)kept[i];  // :165-166
-  }
-  fold_p0uu(in);
-  if (same_len && nn >= 2) {
-    std::vector<double> dv(nn * (nn - 1) / 2);
-    dev.check(abn_codes_pairwise(codes.h, nullptr, nullptr, dv.data()), "Pedigree::build (pairwise divergence)");
-    dm = dmatrix_of_pairs(nn, dv.data());
-    return in;
-  }
-  // the reference's answer for samples of different length is per pair (:221-227): the host loop gives it
-  for (size_t i = 0; i < nn; ++i) {
-    const size_t n = sites[i].size();
-    std::vector<double> pm(n), ml(n);
-    std::vector<uint8_t> status(n);
-    dev.check(abn_sites_fetch(sites[i].get(), nullptr, nullptr, nullptr, nullptr, nullptr, pm.data(), status.data(), nullptr,
-                              ml.data()),
-              "abn_sites_fetch");
-    nodes[i].sites.resize(n);
-    for (size_t k = 0; k < n; ++k) nodes[i].sites[k] = Site{pm[k], status[k], ml[k]};
-  }
-  dm = dmatrix_on_host(in, posterior_max_filter);
-  return in;
-}
 }  // namespace detail
 }  // namespace alphabeta
+
+#include "resident.hpp"

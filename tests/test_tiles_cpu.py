@@ -219,6 +219,15 @@ def test_convert_times_and_rows_from_equal_convert(L, tmp_path):
     a, b = np.zeros((16, 4)), np.ones((16, 4))
     n = L.abh_tiles_convert_both(str(sparse_nodes).encode(), edges, ptr(dm, dp), C.byref(nn), ptr(a, dp), ptr(b, dp), 16, err, len(err))
     assert nn.value == 5 and n == 6 and a[:n].tobytes() == b[:n].tobytes()
+    # a - b - c - d with generations 0, 2, 1, 3: the path a .. c weighs 3 where the generation times give 1.  Both forms
+    # refuse the graph, in the same words (-1; the shim answers -4 when only one of them does, or in other words)
+    bad_nodes, bad_edges = tmp_path / "chain_nodes.txt", tmp_path / "chain_edges.txt"
+    bad_nodes.write_text("filename,node,gen,meth\n" + "".join(f"-,{x},{g},Y\n" for x, g in zip("abcd", (0, 2, 1, 3))))
+    bad_edges.write_text("from\tto\tgendiff\na\tb\t2\nb\tc\t1\nc\td\t2\n")
+    dm = rng.random((4, 4))
+    n = L.abh_tiles_convert_both(str(bad_nodes).encode(), str(bad_edges).encode(), ptr(dm, dp), C.byref(nn), ptr(a, dp), ptr(b, dp),
+                                 16, err, len(err))
+    assert nn.value == 4 and n == -1 and err.value == b"path length does not match the generation times"
 
 
 @pytest.mark.parametrize("sanitize", [False, True])
