@@ -73,6 +73,7 @@ EXPORTED_SYMBOLS = [
     "abn_tiles_create", "abn_tiles_destroy", "abn_tiles_info", "abn_tiles_runs", "abn_tiles_set_intervals",
     "abn_tiles_set_fixed", "abn_tiles_intervals", "abn_tiles_layout", "abn_tiles_stats", "abn_tiles_pairwise",
     "abn_tiles_kernel_ms",
+    "abn_tiles_set_pools", "abn_tiles_pool_segments", "abn_tiles_pool_columns", "abn_tiles_pool_kernel_ms",
 ]
 
 
@@ -247,6 +248,10 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_tiles_stats.argtypes = [vp, i64p, dp, i64p]
     L.abn_tiles_pairwise.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
     L.abn_tiles_kernel_ms.argtypes = [vp, dp]
+    L.abn_tiles_set_pools.argtypes = [vp, C.c_int64, i32p, i64p, i64p, i32p, C.c_int64]
+    L.abn_tiles_pool_segments.argtypes = [vp, i64p, i32p, i32p, i64p, i64p, i64p, i64p]
+    L.abn_tiles_pool_columns.argtypes = [vp, i64p]
+    L.abn_tiles_pool_kernel_ms.argtypes = [vp, dp]
     L.abn_genes_create.argtypes = [vp, C.c_int32, i32p, i32p, i64p, u32p, u32p, u8p, C.POINTER(vp)]
     L.abn_genes_destroy.argtypes = [vp]
     L.abn_genes_choose.argtypes = [vp, C.POINTER(GeneRule), C.c_int32, i64p, i32p, u32p, u32p, u8p, u32p, u32p, u8p, dp]
@@ -1287,7 +1292,8 @@ class Codes:
 class Tiles:
     """abn_tiles: Pedigree::build (src/pedigree.rs:147-172, :210-261) once per genomic tile — a fixed bin or a listed region
     (the region rows of src/cli/metaprofile.rs:50-72) — over resident parse results: the aligned code matrix, its columns'
-    keys and every sample's merged bytes and levels stay on the device; a tile is a contiguous column range."""
+    keys and every sample's merged bytes and levels stay on the device; a tile is a contiguous column range.  set_pools makes
+    a set of intervals one tile: its columns gathered into a pooled matrix (one pedigree per annotation class)."""
 
     ALIGN = {"none": 0, "position": 1, "union": 2}
 
@@ -1353,6 +1359,44 @@ class Tiles:
         """fixed tiles: for every run in run order [k step, k step + size), k = 0 .. ceil((last_start + 1) / step) - 1
         (step 0: size)"""
         self.ctx._check(self._L.abn_tiles_set_fixed(self._h, int(size), int(step)))
+
+    def set_pools(self, chromosome, start, end, pool, n_pools):
+        """pools of intervals (abn_tiles_set_pools): interval k belongs to pool[k] in [0, n_pools); a pool's columns are
+        those inside at least one of its intervals, each once, in column order, gathered into a pooled matrix on the
+        device.  Afterwards the tiles are the pools: layout() is in pooled column space, stats() and pairwise() per pool"""
+        chrom, ids = (np.ascontiguousarray(a, dtype=np.int32).ravel() for a in (chromosome, pool))
+        lo, hi = (np.ascontiguousarray(a, dtype=np.int64).ravel() for a in (start, end))
+        if not chrom.shape == lo.shape == hi.shape == ids.shape:
+            raise ValueError("chromosome, start, end and pool differ in length")
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_tiles_set_pools(self._h, chrom.shape[0], chrom.ctypes.data_as(i32p), lo.ctypes.data_as(i64p),
+                                                    hi.ctypes.data_as(i64p), ids.ctypes.data_as(i32p), int(n_pools)))
+
+    def pool_segments(self):
+        """(pool int32, chromosome int32, start int64, end int64, col_begin int64, col_end int64), each (n_segments,): the
+        pools' merged intervals in segment order and their columns of the handle's own matrix"""
+        n = C.c_int64()
+        self.ctx._check(self._L.abn_tiles_pool_segments(self._h, C.byref(n), None, None, None, None, None, None))
+        pool, chrom = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        lo, hi, cb, ce = (np.zeros(n.value, dtype=np.int64) for _ in range(4))
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_tiles_pool_segments(self._h, None, pool.ctypes.data_as(i32p), chrom.ctypes.data_as(i32p),
+                                                        *(a.ctypes.data_as(i64p) for a in (lo, hi, cb, ce))))
+        return pool, chrom, lo, hi, cb, ce
+
+    def pool_columns(self):
+        """int64 (pooled columns,): every pooled column's source column of the handle's own matrix"""
+        self.ctx._check(self._L.abn_tiles_pool_segments(self._h, None, None, None, None, None, None, None))   # pools, or refused
+        end = self.layout()[1]
+        src = np.zeros(int(end[-1]) if len(end) else 0, dtype=np.int64)
+        self.ctx._check(self._L.abn_tiles_pool_columns(self._h, src.ctypes.data_as(C.POINTER(C.c_int64))))
+        return src
+
+    def pool_kernel_ms(self) -> np.ndarray:
+        """the HIP-event ms of the last set_pools: offsets, map, gather, pack (search and fold: kernel_ms)"""
+        ms = np.zeros(4)
+        self.ctx._check(self._L.abn_tiles_pool_kernel_ms(self._h, _dp(ms)))
+        return ms
 
     def _n_tiles(self):
         return max(self.info()["n_tiles"], 0)

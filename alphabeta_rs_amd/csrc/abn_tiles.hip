@@ -2,7 +2,7 @@
 // per fixed bin or listed region.  Kernels, the definition and the serial forms: abn_tiles.hpp.  The build is
 // abn_codes.hip's (merge, optional common-site or union step, gather, pack) with the columns' keys, the merged bytes and the
 // levels kept; the front end both share is abn_resident.hip's, the merge launches are abn_sites.hip's, the order checks
-// (RunTables) abn_sites_common.hip's, the scan abn_pairwise.hip's.
+// (RunTables) abn_sites_common.hip's, the scan abn_pairwise.hip's, the pack of a pooled matrix abn_codes.hip's.
 #include "abn_host.hpp"
 #define ABN_TILES_KERNELS
 #include "abn_tiles.hpp"
@@ -29,6 +29,25 @@ struct abn_tiles {
   std::vector<double> level_sum_kept;  // [n x T]
   std::vector<int64_t> kept;
   double ms[2] = {0.0, 0.0};  // search, fold
+  // pools (abn_tiles_set_pools): the tiles are the pools, their columns those of the pooled matrix
+  bool pooled = false;
+  long long pool_columns = 0, pool_stride = 0;
+  DevBuf<uint8_t> pool_packed;  // [n x pool_stride]
+  DevBuf<long long> pool_src;   // [pool_columns] every pooled column's source column
+  PoolSegments segments;
+  std::vector<int64_t> seg_begin, seg_end;  // [S] the segments' columns
+  double pool_ms[4] = {0.0, 0.0, 0.0, 0.0};  // offsets, map, gather, pack
+
+  void drop_pools() {
+    pooled = false;
+    pool_columns = pool_stride = 0;
+    pool_packed.release();
+    pool_src.release();
+    segments = PoolSegments{};
+    seg_begin.clear();
+    seg_end.clear();
+    std::fill(pool_ms, pool_ms + 4, 0.0);
+  }
 };
 
 static int tiles_build(abn_tiles* h, double filter, abn_sites* const* samples, int align,
@@ -50,8 +69,7 @@ static int tiles_build(abn_tiles* h, double filter, abn_sites* const* samples, i
   h->code_stride = (each + 15) / 16 * 16;  // whole 16-byte loads of the pack
   h->stride = std::max<long long>(abn_packed_row_stride(each), 64);
   const long long row_dwords = h->stride / 4;
-  if (((long long)n * row_dwords + kCodesThreads - 1) / kCodesThreads > 0x7fffffffLL ||
-      (each + kCommonThreads - 1) / kCommonThreads > 0x7fffffffLL)
+  if (!tiles_matrix_fits(n, each, h->stride))
     return set_err(c, ABN_ERR_INVALID_ARG, "packed matrix too large for one handle");
   const size_t E = std::max<size_t>((size_t)each, 1);
   HIPCHK(c, h->code.alloc(std::max<size_t>((size_t)n * (size_t)h->code_stride, 16)));
@@ -164,7 +182,7 @@ extern "C" int abn_tiles_info(const abn_tiles* h, int32_t* n_samples, int64_t* n
   if (n_columns) *n_columns = h->n_columns;
   if (row_stride_bytes) *row_stride_bytes = h->stride;
   if (n_runs) *n_runs = (int32_t)h->runs.size();
-  if (n_tiles) *n_tiles = h->has_tiles ? (int64_t)h->tchromosome.size() : -1;
+  if (n_tiles) *n_tiles = h->has_tiles ? (int64_t)h->begin.size() : -1;
   return ABN_OK;
 }
 
@@ -232,6 +250,8 @@ static int tiles_run(abn_tiles* h) {
 
 static int tiles_set(abn_tiles* h, std::vector<int32_t>& chromosome, std::vector<int64_t>& start, std::vector<int64_t>& end) {
   h->has_tiles = false;
+  (void)hipSetDevice(h->ctx->device);
+  h->drop_pools();  // back on the handle's own matrix
   h->tchromosome.swap(chromosome);
   h->tstart.swap(start);
   h->tend.swap(end);
@@ -276,6 +296,186 @@ extern "C" int abn_tiles_set_fixed(abn_tiles* h, int64_t size, int64_t step) {
   }
 }
 
+// The pools of a merged segment list (abn_tiles.hpp: pools), one launch chain on the context's stream: search, offsets and
+// ranges; the read of the pooled total, the one wait inside the chain — the pooled arrays are sized from it, and a total
+// beyond the limits of a handle's matrix is refused there, the handle untouched; then map, gather, pack and fold, and the
+// wait for the results.  Behind the refusals the handle leaves what it held; a HIP error leaves it without tiles.
+static int tiles_run_pools(abn_tiles* h, PoolSegments& seg, int32_t n_pools) {
+  abn_ctx* c = h->ctx;
+  const size_t S = seg.size(), P = (size_t)n_pools, n = (size_t)h->n;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  DevBuf<int32_t> dchrom;
+  DevBuf<long long> dpos, dpos_end, dcol_begin, dcol_end, dseg_off, dseg_first, dbegin, dend, dkept;
+  DevBuf<double> dsum;
+  HIPCHK(c, dchrom.alloc(S));
+  HIPCHK(c, dpos.alloc(S));
+  HIPCHK(c, dpos_end.alloc(S));
+  HIPCHK(c, dcol_begin.alloc(S));
+  HIPCHK(c, dcol_end.alloc(S));
+  HIPCHK(c, dseg_off.alloc(S + 1));
+  HIPCHK(c, dseg_first.alloc(P + 1));
+  HIPCHK(c, dbegin.alloc(P));
+  HIPCHK(c, dend.alloc(P));
+  HIPCHK(c, dsum.alloc(n * P));
+  HIPCHK(c, dkept.alloc(n * P));
+  if (S > 0) {
+    HIPCHK(c, hipMemcpyAsync(dchrom.p, seg.chromosome.data(), dchrom.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dpos.p, seg.start.data(), dpos.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dpos_end.p, seg.end.data(), dpos_end.bytes(), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(dseg_first.p, seg.seg_first.data(), dseg_first.bytes(), hipMemcpyHostToDevice, c->stream));
+  Events<8> ev;  // 0..2 around search and offsets, in front of the host's read; 3..7 around map, gather, pack and fold
+  if (int rc = ev.create(c)) return rc;
+  if (int rc = ev.record(c, 0)) return rc;
+  if (S > 0) {
+    hipLaunchKernelGGL(abn_tiles_search_kernel, dim3((unsigned)((S + kTilesThreads - 1) / kTilesThreads)), dim3(kTilesThreads), 0,
+                       c->stream, (const uint32_t*)h->start.p, (const long long*)h->tables.run_begin.p,
+                       (const long long*)h->tables.run_end.p, (long long)S, (const int32_t*)dchrom.p, (const long long*)dpos.p,
+                       (const long long*)dpos_end.p, dcol_begin.p, dcol_end.p);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (int rc = ev.record(c, 1)) return rc;
+  hipLaunchKernelGGL(abn_tiles_pool_offsets_kernel, dim3(1), dim3(kTilesThreads), 0, c->stream, (const long long*)dcol_begin.p,
+                     (const long long*)dcol_end.p, (long long)S, dseg_off.p);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(abn_tiles_pool_ranges_kernel, dim3((unsigned)((P + kTilesThreads - 1) / kTilesThreads)), dim3(kTilesThreads), 0,
+                     c->stream, (const long long*)dseg_off.p, (const long long*)dseg_first.p, (long long)P, dbegin.p, dend.p);
+  HIPCHK(c, hipGetLastError());
+  if (int rc = ev.record(c, 2)) return rc;
+  long long pooled = 0;
+  HIPCHK(c, hipMemcpyAsync(&pooled, dseg_off.p + S, sizeof pooled, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const long long pstride = std::max<long long>(abn_packed_row_stride(pooled), 64), pcode_stride = (pooled + 15) / 16 * 16;
+  if (!tiles_matrix_fits(h->n, pooled, pstride))
+    return set_err(c, ABN_ERR_INVALID_ARG,
+                   "pooled matrix too large for one handle: " + std::to_string(pooled) + " pooled columns");
+
+  // from here on the handle changes
+  h->has_tiles = false;
+  h->drop_pools();
+  h->tchromosome.clear(), h->tstart.clear(), h->tend.clear();
+  DevBuf<uint8_t> pcode;
+  DevBuf<double> plevel;
+  DevBuf<long long> dsite_off, dcode_off;
+  const size_t E = std::max<size_t>((size_t)pooled, 1);
+  HIPCHK(c, pcode.alloc(std::max<size_t>(n * (size_t)pcode_stride, 16)));
+  HIPCHK(c, plevel.alloc(n * E));
+  HIPCHK(c, h->pool_src.alloc(E));
+  HIPCHK(c, h->pool_packed.alloc(n * (size_t)pstride));
+  HIPCHK(c, dsite_off.alloc(n + 1));
+  HIPCHK(c, dcode_off.alloc(n + 1));
+  std::vector<long long> site_off(n + 1), code_off(n + 1);
+  for (size_t s = 0; s <= n; ++s) site_off[s] = (long long)s * pooled, code_off[s] = (long long)s * pcode_stride;
+  HIPCHK(c, hipMemcpyAsync(dsite_off.p, site_off.data(), dsite_off.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dcode_off.p, code_off.data(), dcode_off.bytes(), hipMemcpyHostToDevice, c->stream));
+  const dim3 columns((unsigned)((pooled + kTilesThreads - 1) / kTilesThreads), (unsigned)n);
+  if (int rc = ev.record(c, 3)) return rc;
+  if (pooled > 0) {
+    hipLaunchKernelGGL(abn_tiles_pool_map_kernel, dim3(columns.x), dim3(kTilesThreads), 0, c->stream,
+                       (const long long*)dseg_off.p, (long long)S, (const long long*)dcol_begin.p, pooled, h->pool_src.p);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (int rc = ev.record(c, 4)) return rc;
+  if (pooled > 0) {
+    hipLaunchKernelGGL(abn_tiles_pool_gather_kernel, columns, dim3(kTilesThreads), 0, c->stream, (const uint8_t*)h->code.p,
+                       h->code_stride, (const double*)h->level.p, h->n_columns, (const long long*)h->pool_src.p, pooled, pcode.p,
+                       pcode_stride, plevel.p);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (int rc = ev.record(c, 5)) return rc;
+  if (int rc = codes_pack_dev(c, pcode.p, dcode_off.p, dsite_off.p, h->n, pstride / 4, h->pool_packed.p)) return rc;
+  if (int rc = ev.record(c, 6)) return rc;
+  hipLaunchKernelGGL(abn_tiles_fold_kernel, dim3((unsigned)P, (unsigned)n), dim3(kCodesWave), 0, c->stream,
+                     (const uint8_t*)pcode.p, pcode_stride, (const double*)plevel.p, pooled, (long long)P,
+                     (const long long*)dbegin.p, (const long long*)dend.p, dsum.p, dkept.p);
+  HIPCHK(c, hipGetLastError());
+  if (int rc = ev.record(c, 7)) return rc;
+  h->seg_begin.assign(S, 0), h->seg_end.assign(S, 0);
+  h->begin.assign(P, 0), h->end.assign(P, 0);
+  h->level_sum_kept.assign(n * P, 0.0);
+  h->kept.assign(n * P, 0);
+  static_assert(sizeof(long long) == sizeof(int64_t), "positions and columns");
+  if (S > 0) {
+    HIPCHK(c, hipMemcpyAsync(h->seg_begin.data(), dcol_begin.p, dcol_begin.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h->seg_end.data(), dcol_end.p, dcol_end.bytes(), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(h->begin.data(), dbegin.p, dbegin.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h->end.data(), dend.p, dend.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h->level_sum_kept.data(), dsum.p, dsum.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h->kept.data(), dkept.p, dkept.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int span[6] = {0, 6, 1, 3, 4, 5};  // search, fold; offsets, map, gather, pack
+  for (int k = 0; k < 6; ++k)
+    if (int rc = ev.elapsed_ms(c, span[k], k < 2 ? &h->ms[k] : &h->pool_ms[k - 2])) return rc;
+  h->pool_columns = pooled;
+  h->pool_stride = pstride;
+  h->segments = std::move(seg);
+  h->pooled = h->has_tiles = true;
+  return ABN_OK;
+}
+
+extern "C" int abn_tiles_set_pools(abn_tiles* h, int64_t n_intervals, const int32_t* chromosome, const int64_t* start,
+                                   const int64_t* end, const int32_t* pool, int64_t n_pools) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = h->ctx;
+  if (n_intervals < 0 || (n_intervals > 0 && (!chromosome || !start || !end || !pool)))
+    return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (n_pools <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "n_pools is 0 or less");
+  if (n_pools > 0x7fffffffLL) return set_err(c, ABN_ERR_INVALID_ARG, "more pools than INT32_MAX");
+  for (int64_t k = 0; k < n_intervals; ++k) {
+    if (pool[k] < 0 || pool[k] >= n_pools)
+      return set_err(c, ABN_ERR_INVALID_ARG,
+                     "interval " + std::to_string(k) + ": pool " + std::to_string(pool[k]) + " outside 0.." +
+                         std::to_string(n_pools - 1));
+    if (!tiles_interval_valid(chromosome[k], start[k], end[k]))
+      return set_err(c, ABN_ERR_INVALID_ARG,
+                     "interval " + std::to_string(k) + ": a chromosome outside 0..257, or a start or end outside [0, 2^32]");
+  }
+  try {
+    PoolSegments seg;
+    tiles_pool_merge(h->runs.data(), (int)h->runs.size(), n_intervals, chromosome, (const long long*)start,
+                     (const long long*)end, pool, (int32_t)n_pools, &seg);
+    const int rc = tiles_run_pools(h, seg, (int32_t)n_pools);
+    if (rc && !h->has_tiles) h->drop_pools();
+    return rc;
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+}
+
+extern "C" int abn_tiles_pool_segments(const abn_tiles* h, int64_t* n_segments, int32_t* pool, int32_t* chromosome,
+                                       int64_t* start, int64_t* end, int64_t* col_begin, int64_t* col_end) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (!h->has_tiles || !h->pooled) return set_err(h->ctx, ABN_ERR_INVALID_ARG, "no pools: abn_tiles_set_pools first");
+  const PoolSegments& s = h->segments;
+  if (n_segments) *n_segments = (int64_t)s.size();
+  if (pool) std::copy(s.pool.begin(), s.pool.end(), pool);
+  if (chromosome) std::copy(s.chromosome.begin(), s.chromosome.end(), chromosome);
+  if (start) std::copy(s.start.begin(), s.start.end(), start);
+  if (end) std::copy(s.end.begin(), s.end.end(), end);
+  if (col_begin) std::copy(h->seg_begin.begin(), h->seg_begin.end(), col_begin);
+  if (col_end) std::copy(h->seg_end.begin(), h->seg_end.end(), col_end);
+  return ABN_OK;
+}
+
+extern "C" int abn_tiles_pool_columns(const abn_tiles* h, int64_t* src) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = h->ctx;
+  if (!h->has_tiles || !h->pooled) return set_err(c, ABN_ERR_INVALID_ARG, "no pools: abn_tiles_set_pools first");
+  if (!src || h->pool_columns == 0) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(src, h->pool_src.p, (size_t)h->pool_columns * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ABN_OK;
+}
+
+extern "C" int abn_tiles_pool_kernel_ms(const abn_tiles* h, double* ms4) {
+  if (!h || !ms4) return ABN_ERR_INVALID_ARG;
+  std::copy(h->pool_ms, h->pool_ms + 4, ms4);
+  return ABN_OK;
+}
+
 static int tiles_need(const abn_tiles* h) {
   if (!h) return ABN_ERR_INVALID_ARG;
   if (!h->has_tiles) return set_err(h->ctx, ABN_ERR_INVALID_ARG, "no tiles yet: abn_tiles_set_intervals or abn_tiles_set_fixed first");
@@ -284,6 +484,9 @@ static int tiles_need(const abn_tiles* h) {
 
 extern "C" int abn_tiles_intervals(const abn_tiles* h, int32_t* chromosome, int64_t* start, int64_t* end) {
   if (int rc = tiles_need(h)) return rc;
+  if (h->pooled)
+    return set_err(h->ctx, ABN_ERR_INVALID_ARG,
+                   "the tiles are pools, each a set of segments and no one interval: abn_tiles_pool_segments gives them");
   if (chromosome) std::copy(h->tchromosome.begin(), h->tchromosome.end(), chromosome);
   if (start) std::copy(h->tstart.begin(), h->tstart.end(), start);
   if (end) std::copy(h->tend.begin(), h->tend.end(), end);
@@ -314,6 +517,9 @@ extern "C" int abn_tiles_pairwise(abn_tiles* h, uint64_t* diff, uint64_t* both, 
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
   return pairwise_to_host(c, T * npairs, diff, both, dvalue, [&](auto* dd, auto* db, auto* dv) {
+    if (h->pooled)
+      return pairwise_windows_packed_dev(c, h->pool_packed.p, h->n, h->pool_columns, h->pool_stride, h->begin.data(),
+                                         h->end.data(), (int32_t)T, dd, db, dv, nullptr);
     return pairwise_windows_packed_dev(c, h->packed.p, h->n, h->n_columns, h->stride, h->begin.data(), h->end.data(), (int32_t)T,
                                        dd, db, dv, nullptr);
   });

@@ -19,10 +19,13 @@
 //           n x T independent chains where the whole-sample fold has n.  `begin` is aligned to nothing: the loads are
 //           byte and double loads at begin + lane, the index clamped to the tile's last column.
 //
+//   pools   a set of intervals as ONE tile — a class of an annotation: its non-contiguous columns made a contiguous range of
+//           a pooled matrix (merge, offsets, map, gather: the section "pools" below), which the same fold and scan take.
+//
 // Every output element has one writer, a plain store; no atomics here.
 //
-// The arithmetic and every step in its serial form compile without a HIP header: the host library (host_capi.cpp) and
-// tests/native/tiles_main.cpp include this file as it is.
+// The arithmetic and every step in its serial form compile without a HIP header: the host library (host_capi.cpp),
+// tests/native/tiles_main.cpp and tests/native/tile_pools_main.cpp include this file as it is.
 #pragma once
 #include <algorithm>
 
@@ -135,6 +138,125 @@ inline void tiles_fold_serial(const uint8_t* code, long long code_stride, const 
                         &sum[s * T + t], &kept[s * T + t]);
 }
 
+// the limits of one handle's matrix of n rows of `columns` sites, stride_bytes each: the grids of the pack (a lane per dword)
+// and of the passes with a lane per column
+inline bool tiles_matrix_fits(int n, long long columns, long long stride_bytes) {
+  return ((long long)n * (stride_bytes / 4) + kCodesThreads - 1) / kCodesThreads <= 0x7fffffffLL &&
+         (columns + kCommonThreads - 1) / kCommonThreads <= 0x7fffffffLL;
+}
+
+// ------------------------------------------------------------------------------------------------ pools
+// A POOL is a set of intervals that belong together — every gene, every TE, the segments of one chromatin state: the one
+// rate per annotation class the AlphaBeta analyses report, where a tile is one row of the list.  Its columns are the columns
+// whose (chromosome, start) lies in at least one of its intervals, each once, in ascending column order; gathered side by
+// side they are a contiguous range of a POOLED matrix, and from there on a pool is a tile: the same fold, the same scan.
+//
+//   merge    on the host, pool by pool: the chromosomes in the RUN order of the columns (not in key order), one without a run
+//            dropped, intervals with end <= start dropped, the rest sorted by (start, end), overlapping or touching ones
+//            merged.  A pool's SEGMENTS are therefore disjoint and ascend in column space; seg_first[p] is pool p's first.
+//   search   a segment's column range [col_begin, col_end) is tiles_search_lane's, unchanged; a segment may be empty.
+//   offsets  seg_off [S + 1]: the exclusive prefix of the segments' lengths in segment order, in 64 bits; pool p owns the
+//            pooled columns [seg_off[seg_first[p]], seg_off[seg_first[p + 1]]).
+//   map      a lane per pooled column j: src[j] = col_begin[i] + (j - seg_off[i]), i the LAST segment with seg_off[i] <= j
+//            (an upper bound, so the empty segments in front of it are passed over).
+//   gather   a lane per (sample, pooled column): the merged byte and the level of src[j], into arrays laid out as the
+//            handle's own (rows of pooled_code_stride bytes, of pooled_columns levels), which the pack and the fold take.
+struct PoolSegments {
+  std::vector<int32_t> pool, chromosome;  // [S] in segment order: pool by pool, inside one in column order
+  std::vector<long long> start, end;
+  std::vector<long long> seg_first;       // [n_pools + 1]
+  size_t size() const { return pool.size(); }
+};
+
+// interval k = (chromosome, start, end)[k], valid (tiles_interval_valid), belongs to pool[k] in [0, n_pools)
+inline void tiles_pool_merge(const TileRun* runs, int n_runs, long long n_intervals, const int32_t* chromosome,
+                             const long long* start, const long long* end, const int32_t* pool, int32_t n_pools,
+                             PoolSegments* out) {
+  int rank[kCommonChroms];
+  for (int c = 0; c < kCommonChroms; ++c) rank[c] = -1;
+  for (int r = 0; r < n_runs; ++r) rank[runs[r].chromosome] = r;
+  std::vector<long long> order;
+  for (long long k = 0; k < n_intervals; ++k)
+    if (end[k] > start[k] && rank[chromosome[k]] >= 0) order.push_back(k);
+  std::sort(order.begin(), order.end(), [&](long long a, long long b) {
+    if (pool[a] != pool[b]) return pool[a] < pool[b];
+    if (chromosome[a] != chromosome[b]) return rank[chromosome[a]] < rank[chromosome[b]];
+    if (start[a] != start[b]) return start[a] < start[b];
+    return end[a] < end[b];
+  });
+  *out = PoolSegments{};
+  out->seg_first.assign((size_t)n_pools + 1, 0);
+  for (long long k : order) {
+    const bool joins = !out->pool.empty() && out->pool.back() == pool[k] && out->chromosome.back() == chromosome[k] &&
+                       start[k] <= out->end.back();  // overlaps the segment, or touches it
+    if (joins) {
+      out->end.back() = std::max(out->end.back(), end[k]);
+      continue;
+    }
+    out->pool.push_back(pool[k]), out->chromosome.push_back(chromosome[k]);
+    out->start.push_back(start[k]), out->end.push_back(end[k]);
+    ++out->seg_first[(size_t)pool[k] + 1];
+  }
+  for (size_t p = 0; p < (size_t)n_pools; ++p) out->seg_first[p + 1] += out->seg_first[p];
+}
+
+// The last segment of [lo, hi] whose offset is not above j; seg_off[lo] <= j < seg_off[hi + 1].  (The kernel's lanes call it
+// on a window of seg_off, from LDS where it fits.)
+ABN_HOST_DEVICE inline long long tiles_pool_segment_of(const long long* seg_off, long long lo, long long hi, long long j) {
+  long long a = lo + 1, b = hi + 1;  // the first offset above j lies in [a, b]
+  while (a < b) {
+    const long long mid = a + (b - a) / 2;
+    if (seg_off[mid] > j) b = mid;
+    else a = mid + 1;
+  }
+  return a - 1;
+}
+
+// pooled column j -> its source column; the segment is searched in [lo, hi] (the whole list: 0, S - 1)
+ABN_HOST_DEVICE inline long long tiles_pool_map_lane(const long long* seg_off, long long lo, long long hi,
+                                                     const long long* col_begin, long long j) {
+  const long long i = tiles_pool_segment_of(seg_off, lo, hi, j);
+  return col_begin[i] + (j - seg_off[i]);
+}
+
+// sample s's pooled column j from its source column: the merged byte and the level.  code / level: the handle's arrays
+// (rows of code_stride bytes, of n_columns levels); pcode / plevel: the pooled ones (pcode_stride, pooled)
+ABN_HOST_DEVICE inline void tiles_pool_gather_lane(const uint8_t* code, long long code_stride, const double* level,
+                                                   long long n_columns, long long s, long long j, long long src,
+                                                   uint8_t* pcode, long long pcode_stride, double* plevel,
+                                                   long long pooled) {
+  pcode[s * pcode_stride + j] = code[s * code_stride + src];
+  plevel[s * pooled + j] = level[s * n_columns + src];
+}
+
+// ---- their serial forms
+inline void tiles_pool_offsets_serial(const long long* col_begin, const long long* col_end, long long S, long long* seg_off) {
+  long long run = 0;
+  for (long long i = 0; i < S; ++i) {
+    seg_off[i] = run;
+    run += col_end[i] - col_begin[i];
+  }
+  seg_off[S] = run;
+}
+
+// pool p's range of pooled columns
+inline void tiles_pool_ranges_serial(const long long* seg_off, const long long* seg_first, long long n_pools, long long* begin,
+                                     long long* end) {
+  for (long long p = 0; p < n_pools; ++p) begin[p] = seg_off[seg_first[p]], end[p] = seg_off[seg_first[p + 1]];
+}
+
+inline void tiles_pool_map_serial(const long long* seg_off, long long S, const long long* col_begin, long long* src) {
+  for (long long j = 0; j < seg_off[S]; ++j) src[j] = tiles_pool_map_lane(seg_off, 0, S - 1, col_begin, j);
+}
+
+inline void tiles_pool_gather_serial(const uint8_t* code, long long code_stride, const double* level, long long n_columns,
+                                     int n, const long long* src, long long pooled, uint8_t* pcode, long long pcode_stride,
+                                     double* plevel) {
+  for (int s = 0; s < n; ++s)
+    for (long long j = 0; j < pooled; ++j)
+      tiles_pool_gather_lane(code, code_stride, level, n_columns, s, j, src[j], pcode, pcode_stride, plevel, pooled);
+}
+
 #if defined(__HIPCC__) && defined(ABN_TILES_KERNELS)  // (abn_tiles.hip defines it)
 // ------------------------------------------------------------------------------------------------ kernels
 // grid: ceil(kCommonChroms / kTilesThreads); last_start[c] = the start of the last column of chromosome c's run
@@ -180,6 +302,84 @@ abn_tiles_fold_kernel(const uint8_t* __restrict__ code, long long code_stride, c
     sum[s * T + t] = acc;
     kept[s * T + t] = count;
   }
+}
+
+// ---- pools
+constexpr int kPoolWindow = 128;  // the offsets a wavefront of the map kernel keeps in LDS (4 wavefronts: 4 KiB)
+
+// one workgroup: seg_off[0 .. S) = the exclusive prefix of the segments' lengths, in 64 bits, the sum at seg_off[S] —
+// abn_common_scan_kernel's two levels: every lane its slice of the segments serially, the 256 sums by Hillis-Steele in LDS
+__global__ void __launch_bounds__(kTilesThreads)
+abn_tiles_pool_offsets_kernel(const long long* __restrict__ col_begin, const long long* __restrict__ col_end, long long S,
+                              long long* __restrict__ seg_off) {
+  __shared__ long long s_part[kTilesThreads];
+  const long long per = (S + kTilesThreads - 1) / kTilesThreads;
+  const long long lo = min((long long)threadIdx.x * per, S), hi = min(lo + per, S);
+  long long sum = 0;
+  for (long long i = lo; i < hi; ++i) sum += col_end[i] - col_begin[i];
+  s_part[threadIdx.x] = sum;
+  __syncthreads();
+  for (int d = 1; d < kTilesThreads; d <<= 1) {  // inclusive
+    const long long up = threadIdx.x >= (unsigned)d ? s_part[threadIdx.x - d] : 0;
+    __syncthreads();
+    s_part[threadIdx.x] += up;
+    __syncthreads();
+  }
+  long long run = s_part[threadIdx.x] - sum;
+  for (long long i = lo; i < hi; ++i) {
+    seg_off[i] = run;
+    run += col_end[i] - col_begin[i];
+  }
+  if (threadIdx.x == kTilesThreads - 1) seg_off[S] = s_part[threadIdx.x];
+}
+
+// grid: ceil(n_pools / kTilesThreads); pool p's range of pooled columns, where the fold reads its tiles' ranges
+__global__ void __launch_bounds__(kTilesThreads)
+abn_tiles_pool_ranges_kernel(const long long* __restrict__ seg_off, const long long* __restrict__ seg_first, long long n_pools,
+                             long long* __restrict__ begin, long long* __restrict__ end) {
+  const long long p = (long long)blockIdx.x * kTilesThreads + threadIdx.x;
+  if (p >= n_pools) return;
+  begin[p] = seg_off[seg_first[p]];
+  end[p] = seg_off[seg_first[p + 1]];
+}
+
+// grid: ceil(pooled / kTilesThreads), pooled = seg_off[S] > 0; src[j] = pooled column j's source column.  A wavefront's 64
+// columns ascend, so their segments lie between its first column's and its last's: those two are searched in the whole list
+// (the same two probes in every lane: one broadcast load per step), and every lane then searches that window alone — from
+// LDS where its offsets fit (kPoolWindow), else in seg_off itself, which is what a wavefront over thousands of empty
+// segments does.  Either way the upper bound passes over the empty segments.
+__global__ void __launch_bounds__(kTilesThreads)
+abn_tiles_pool_map_kernel(const long long* __restrict__ seg_off, long long S, const long long* __restrict__ col_begin,
+                          long long pooled, long long* __restrict__ src) {
+  __shared__ long long s_off[kTilesThreads / 64][kPoolWindow];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long j = (long long)blockIdx.x * kTilesThreads + threadIdx.x, first = j - lane;
+  const bool live = first < pooled;  // (wave-uniform)
+  long long lo = 0, hi = 0;
+  if (live) {
+    const long long last = min(first + 63, pooled - 1);
+    lo = tiles_pool_segment_of(seg_off, 0, S - 1, first);
+    hi = tiles_pool_segment_of(seg_off, lo, S - 1, last);
+  }
+  const long long span = hi - lo + 2;  // the offsets lo .. hi + 1
+  const bool fits = live && span <= kPoolWindow;
+  if (fits)
+    for (long long k = lane; k < span; k += 64) s_off[wave][k] = seg_off[lo + k];
+  __syncthreads();
+  if (j >= pooled) return;
+  if (fits) src[j] = tiles_pool_map_lane(s_off[wave], 0, hi - lo, col_begin + lo, j);
+  else src[j] = tiles_pool_map_lane(seg_off, lo, hi, col_begin, j);
+}
+
+// grid: (ceil(pooled / kTilesThreads), n_samples); a lane per (sample, pooled column): src read once, the sample's merged byte
+// and level of that column to the pooled arrays — consecutive lanes, consecutive bytes and doubles, one writer each
+__global__ void __launch_bounds__(kTilesThreads)
+abn_tiles_pool_gather_kernel(const uint8_t* __restrict__ code, long long code_stride, const double* __restrict__ level,
+                             long long n_columns, const long long* __restrict__ src, long long pooled,
+                             uint8_t* __restrict__ pcode, long long pcode_stride, double* __restrict__ plevel) {
+  const long long j = (long long)blockIdx.x * kTilesThreads + threadIdx.x;
+  if (j >= pooled) return;
+  tiles_pool_gather_lane(code, code_stride, level, n_columns, blockIdx.y, j, src[j], pcode, pcode_stride, plevel, pooled);
 }
 #endif  // kernels
 

@@ -617,6 +617,55 @@ long long abh_tiles_read_regions(const char* text, long long len, long long cap,
 void abh_tiles_region(int chromosome, long long start, long long end, char* text, long long cap) {
   put_text(text, cap, alphabeta::metaprofile::tile_region(chromosome, start, end));
 }
+// ---- region pools (csrc/abn_tiles.hpp: pools; host/tiles.hpp: region_pools), for tests/test_tile_pools_cpu.py
+// tiles_pool_merge over a run table (chromosomes in run order) -> the number of segments (-1: more than cap); the segments'
+// pool, chromosome, start, end [cap] and seg_first [n_pools + 1]
+long long abh_tiles_pool_merge(int n_runs, const int* run_chromosome, long long n_intervals, const int* chromosome,
+                               const long long* start, const long long* end, const int* pool, int n_pools, long long cap,
+                               int* seg_pool, int* seg_chromosome, long long* seg_start, long long* seg_end,
+                               long long* seg_first) {
+  std::vector<abn::TileRun> runs;
+  for (int k = 0; k < n_runs; ++k) runs.push_back(abn::TileRun{run_chromosome[k], 0, 0, 0u});
+  abn::PoolSegments s;
+  abn::tiles_pool_merge(runs.data(), n_runs, n_intervals, chromosome, start, end, pool, n_pools, &s);
+  if ((long long)s.size() > cap) return -1;
+  for (size_t k = 0; k < s.size(); ++k)
+    seg_pool[k] = s.pool[k], seg_chromosome[k] = s.chromosome[k], seg_start[k] = s.start[k], seg_end[k] = s.end[k];
+  for (size_t p = 0; p < s.seg_first.size(); ++p) seg_first[p] = s.seg_first[p];
+  return (long long)s.size();
+}
+// seg_off [S + 1] of the segments' columns, the pools' ranges [n_pools] of it, and src [seg_off[S]] when it is given
+void abh_tiles_pool_offsets_map(long long S, const long long* col_begin, const long long* col_end, long long* seg_off,
+                                long long n_pools, const long long* seg_first, long long* begin, long long* end,
+                                long long* src) {
+  abn::tiles_pool_offsets_serial(col_begin, col_end, S, seg_off);
+  if (seg_first) abn::tiles_pool_ranges_serial(seg_off, seg_first, n_pools, begin, end);
+  if (src) abn::tiles_pool_map_serial(seg_off, S, col_begin, src);
+}
+void abh_tiles_pool_gather_serial(const unsigned char* code, long long code_stride, const double* level, long long n_columns,
+                                  int n, const long long* src, long long pooled, unsigned char* pcode, long long pcode_stride,
+                                  double* plevel) {
+  abn::tiles_pool_gather_serial(code, code_stride, level, n_columns, n, src, pooled, pcode, pcode_stride, plevel);
+}
+// 1 when a matrix of n rows of `columns` sites is within a handle's limits (its stride: abn_packed_row_stride, at least 64)
+int abh_tiles_matrix_fits(int n, long long columns) {
+  return abn::tiles_matrix_fits(n, columns, std::max<long long>(abn_packed_row_stride(columns), 64)) ? 1 : 0;
+}
+// read_regions + region_pools of a BED-like text -> the named rows (-1: more than cap, -2: refused, the words in text): their
+// chromosome, start, end, pool [cap]; counts = {pools, skipped rows}; names: the pools' names, '\n' between them
+long long abh_tiles_region_pools(const char* bed, long long len, long long cap, int* chromosome, long long* start,
+                                 long long* end, int* pool, long long* counts, char* text, long long textcap) {
+  const auto p = alphabeta::metaprofile::region_pools(alphabeta::metaprofile::read_regions(std::string(bed, (size_t)len)));
+  if (!p.refused.empty()) return put_text(text, textcap, p.refused), -2;
+  if ((long long)p.rows.size() > cap) return -1;
+  for (size_t k = 0; k < p.rows.size(); ++k)
+    chromosome[k] = p.rows.chromosome[k], start[k] = p.rows.start[k], end[k] = p.rows.end[k], pool[k] = p.pool[k];
+  counts[0] = (long long)p.names.size(), counts[1] = (long long)p.skipped;
+  std::string names;
+  for (size_t k = 0; k < p.names.size(); ++k) names += p.names[k] + ":" + std::to_string(p.intervals[k]) + "\n";
+  put_text(text, textcap, names);
+  return (long long)p.rows.size();
+}
 // detail::convert(graph, dm) -> rows_a, and detail::rows_from(detail::convert_times(graph), dm) -> rows_b (capacity cap x 4
 // each; dm [nn x nn] as DMatrix::from fills it); *nn_out = the sampled nodes.  Returns the rows of convert, -1: a call
 // threw, and when both forms ran, both threw the same words (in err), -2: they do not fit, -3: the two differ in their

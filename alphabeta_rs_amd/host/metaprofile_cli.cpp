@@ -5,7 +5,7 @@
 // whole methylome files and a gene annotation, the sites placed into windows on the device and no file tree in between.
 // With --methylome DIR --nodes FILE --edges FILE and --tiles SIZE [--tile-step STEP] or --regions FILE: the rates per
 // genomic tile (tiles.hpp) — fixed bins along the genome or the rows of a BED-like list — from whole methylomes kept on the
-// device; no annotation.
+// device; no annotation.  With --regions FILE --pool: one pedigree per name in the list's 4th field.
 // All windows are fitted by one batched plan on the MI355X.  Flags follow src/arguments.rs:6-62 where they apply.
 #include <cstdlib>
 #include <cstring>
@@ -100,6 +100,7 @@ int main(int argc, char** argv) {
       (f == "--tiles" ? tiles_given : tile_step_given) = true;
     }
     else if (f == "--regions") tiles.regions = val();
+    else if (f == "--pool") tiles.pool = true;
     else if (f == "-h" || f == "--help") {
       std::puts("Usage: metaprofile_alphabeta -o <output-dir> [--name N] [-s step] [-w size] [-c cutoff] [-a]\n"
                 "       [--iterations 100] [--max-gene-length L] [--distribution FILE] [--seed S] [--device D]\n"
@@ -123,6 +124,10 @@ int main(int argc, char** argv) {
                 "                            --genome; the methylomes are parsed and kept on the device; --align as above,\n"
                 "                            none expects the same sites in every methylome.  Writes results.txt (window = the\n"
                 "                            tile's index, region = chromosome:start-end), raw.npy and tiles.txt\n"
+                "       [--pool]             with --regions: the rows that share a name (4th field) are one pool, one pedigree of\n"
+                "                            every site inside any of them, each site once - one rate per annotation class.\n"
+                "                            Pools are numbered by first appearance; rows without a name are skipped.  Writes\n"
+                "                            results.txt (window = the pool's index, region = its name), raw.npy and pools.txt\n"
                 "       [--stream-sweep]     pedigrees too large for the LDS: read a fit's rows once per Nelder-Mead iteration\n"
                 "                            instead of once per cost evaluation; the same output files");
       return 0;
@@ -133,6 +138,10 @@ int main(int argc, char** argv) {
   }
   if (!std::filesystem::exists(a.output_dir)) {
     std::fprintf(stderr, "error: output directory %s does not exist\n", a.output_dir.c_str());
+    return 2;
+  }
+  if (tiles.pool && tiles.regions.empty()) {
+    std::fprintf(stderr, "error: --pool belongs to --regions\n");
     return 2;
   }
   const bool tile_mode = tiles_given || tile_step_given || !tiles.regions.empty();
@@ -149,6 +158,17 @@ int main(int argc, char** argv) {
       return 2;
     }
     a.device_sites = true;
+  }
+  if (tiles.pool) {  // a name the output files cannot hold is a flag error, before anything runs
+    std::string refused;
+    try {
+      refused = metaprofile::region_pools(metaprofile::read_regions(detail::read_file(tiles.regions, "regions"))).refused;
+    } catch (const Error&) {  // an unreadable list: the run says so
+    }
+    if (!refused.empty()) {
+      std::fprintf(stderr, "error: %s\n", refused.c_str());
+      return 2;
+    }
   }
   const bool in_memory = !a.methylome.empty();
   if (in_memory && a.invert) {
@@ -189,7 +209,8 @@ int main(int argc, char** argv) {
       const auto res = metaprofile::alphabeta_multiple_tiles(a, tiles);
       std::printf("%s\n", res.out.results_txt.c_str());
       std::ofstream(std::filesystem::path(a.output_dir) / "results.txt") << res.out.results_txt;
-      std::ofstream(std::filesystem::path(a.output_dir) / "tiles.txt") << res.tiles_txt;
+      if (tiles.pool) std::ofstream(std::filesystem::path(a.output_dir) / "pools.txt") << res.pools_txt;
+      else std::ofstream(std::filesystem::path(a.output_dir) / "tiles.txt") << res.tiles_txt;
       metaprofile::write_raw_npy(res.out, (std::filesystem::path(a.output_dir) / "raw.npy").string());
       return 0;
     }

@@ -5,8 +5,12 @@
 // (src/cli/metaprofile.rs:33-114).  Every methylome is parsed on the device and stays there (abn_sites_parse_dev);
 // abn_tiles_* (csrc/abn_tiles.hpp) aligns them, finds every tile's columns and folds rc_meth_lvl per (sample, tile); one
 // scan gives every tile's D matrix; every tile is then a window of fit_windows, its Philox streams those of its index in
-// the tile list.  No annotation, no file tree.
+// the tile list.  No annotation, no file tree.  With --pool the rows of the list that share a name are one POOL
+// (abn_tiles_set_pools): one pedigree from every site inside any of them — one rate per annotation class — and from there
+// on a tile like the others.
 #pragma once
+
+#include <unordered_map>
 
 #include "metaprofile.hpp"
 
@@ -16,12 +20,14 @@ namespace metaprofile {
 struct TileArgs {
   int64_t size = 0, step = 0;  // --tiles SIZE [--tile-step STEP]: fixed tiles (step 0: size)
   std::string regions;         // --regions FILE: a list
+  bool pool = false;           // --pool: the rows of the list that share a name are one pool, one pedigree (region_pools)
   bool fixed() const { return regions.empty(); }
 };
 
 struct TileList {
   std::vector<int32_t> chromosome;  // Numbered(n) = n, Mitochondrial = 256, Chloroplast = 257
   std::vector<int64_t> start, end;
+  std::vector<std::string> name;    // the row's 4th field; empty: the row has three
   size_t size() const { return chromosome.size(); }
 };
 
@@ -55,6 +61,43 @@ inline TileList read_regions(const std::string& text) {
     out.chromosome.push_back(key);
     out.start.push_back(a);
     out.end.push_back(b);
+    out.name.push_back(f.size() > 3 ? f[3] : std::string());
+  }
+  return out;
+}
+
+// --pool: the rows of a region list by name — all genes, all TEs, each chromatin state.  The pools are numbered by first
+// appearance in the file; a row without a name (fewer than four fields) is skipped and counted; a name that holds the `;`
+// of results.txt and pools.txt is refused.
+struct RegionPools {
+  TileList rows;                   // the named rows, in file order
+  std::vector<int32_t> pool;       // [rows] the row's pool
+  std::vector<std::string> names;  // [n_pools]
+  std::vector<int64_t> intervals;  // [n_pools] the pool's rows
+  size_t skipped = 0;
+  std::string refused;             // not empty: why the list is not taken
+};
+inline RegionPools region_pools(const TileList& list) {
+  RegionPools out;
+  std::unordered_map<std::string, int32_t> seen;
+  for (size_t k = 0; k < list.size(); ++k) {
+    const std::string& name = list.name[k];
+    if (name.empty()) {
+      ++out.skipped;
+      continue;
+    }
+    if (name.find(';') != std::string::npos) {
+      out.refused = "region " + std::to_string(k) + ": the name '" + name + "' holds a ';', the separator of the output files";
+      return out;
+    }
+    const auto at = seen.emplace(name, (int32_t)out.names.size());
+    if (at.second) out.names.push_back(name), out.intervals.push_back(0);
+    ++out.intervals[(size_t)at.first->second];
+    out.rows.chromosome.push_back(list.chromosome[k]);
+    out.rows.start.push_back(list.start[k]);
+    out.rows.end.push_back(list.end[k]);
+    out.rows.name.push_back(name);
+    out.pool.push_back(at.first->second);
   }
   return out;
 }
@@ -67,6 +110,7 @@ inline std::string tile_region(int32_t c, int64_t start, int64_t end) {
 struct TilesOutput {
   Output out;             // results_txt: `window` = the tile's index in the list, `cg_count` = the tile's columns
   std::string tiles_txt;  // tile;chromosome;start;end;cg_count;fitted, every tile of the list
+  std::string pools_txt;  // --pool, in its place: pool;name;intervals;segments;cg_count;fitted, every pool
 };
 
 // The sibling of alphabeta_multiple_in_memory for tiles.  args: methylome (directory), nodes, edges, align, iterations,
@@ -80,10 +124,18 @@ inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileAr
   const size_t nn = graph.nodes.size(), npairs = nn * (nn - 1) / 2;
   if (nn == 0) throw Error(ABN_ERR_INVALID_ARG, "the nodelist names no sampled node");
   TileList list;
+  RegionPools pools;
   if (!tiles.fixed()) {
     list = read_regions(detail::read_file(tiles.regions, "regions"));
     if (list.size() == 0) throw Error(ABN_ERR_INVALID_ARG, "Could not parse a single region from " + tiles.regions);
   }
+  if (tiles.pool) {
+    pools = region_pools(list);
+    if (!pools.refused.empty()) throw Error(ABN_ERR_INVALID_ARG, pools.refused);
+    if (pools.skipped) std::printf("Skipped %zu regions without a name in the 4th field\n", pools.skipped);
+    if (pools.names.empty()) throw Error(ABN_ERR_INVALID_ARG, "No region of " + tiles.regions + " has a name to pool by");
+  }
+  const char* unit = tiles.pool ? "pool" : "tile";
   // every sampled node's methylome, every line read (src/pedigree.rs:147-163), its records left on the device
   resident::Samples samples{dev, /*skip_lines=*/0, {}};
   std::vector<std::string> names;
@@ -100,6 +152,10 @@ inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileAr
     std::fputs(line.c_str(), stdout);
   if (tiles.fixed())
     dev.check(abn_tiles_set_fixed(th.get(), tiles.size, tiles.step), "abn_tiles_set_fixed");
+  else if (tiles.pool)
+    dev.check(abn_tiles_set_pools(th.get(), (int64_t)pools.rows.size(), pools.rows.chromosome.data(), pools.rows.start.data(),
+                                  pools.rows.end.data(), pools.pool.data(), (int64_t)pools.names.size()),
+              "abn_tiles_set_pools");
   else
     dev.check(abn_tiles_set_intervals(th.get(), (int64_t)list.size(), list.chromosome.data(), list.start.data(), list.end.data()),
               "abn_tiles_set_intervals");
@@ -107,8 +163,17 @@ inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileAr
   abn_tiles_info(th.get(), nullptr, nullptr, nullptr, nullptr, &n_tiles);
   const size_t T = (size_t)n_tiles;
   if (T == 0) throw Error(ABN_ERR_INVALID_ARG, "no tile: the methylomes hold no site");
-  list.chromosome.resize(T), list.start.resize(T), list.end.resize(T);
-  dev.check(abn_tiles_intervals(th.get(), list.chromosome.data(), list.start.data(), list.end.data()), "abn_tiles_intervals");
+  std::vector<int64_t> segments(T, 0);  // --pool: every pool's merged segments
+  if (tiles.pool) {
+    int64_t S = 0;
+    dev.check(abn_tiles_pool_segments(th.get(), &S, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "abn_tiles_pool_segments");
+    std::vector<int32_t> of((size_t)S);
+    dev.check(abn_tiles_pool_segments(th.get(), nullptr, of.data(), nullptr, nullptr, nullptr, nullptr, nullptr), "abn_tiles_pool_segments");
+    for (int32_t p : of) ++segments[(size_t)p];
+  } else {
+    list.chromosome.resize(T), list.start.resize(T), list.end.resize(T);
+    dev.check(abn_tiles_intervals(th.get(), list.chromosome.data(), list.start.data(), list.end.data()), "abn_tiles_intervals");
+  }
   std::vector<int64_t> count(T), kept(nn * T);
   std::vector<double> sum(nn * T), dv(std::max<size_t>(T * npairs, 1), 0.0);
   std::vector<uint64_t> both(std::max<size_t>(T * npairs, 1), 0);
@@ -118,19 +183,19 @@ inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileAr
   const std::vector<detail::PairTimes> times = detail::convert_times(graph);
   std::vector<Win> wins;
   for (size_t t = 0; t < T; ++t) {
-    const std::string region = tile_region(list.chromosome[t], list.start[t], list.end[t]);
+    const std::string region = tiles.pool ? pools.names[t] : tile_region(list.chromosome[t], list.start[t], list.end[t]);
     try {
-      if (count[t] == 0) throw Error(ABN_ERR_INVALID_ARG, "no site lies in this tile");
+      if (count[t] == 0) throw Error(ABN_ERR_INVALID_ARG, std::string("no site lies in this ") + unit);
       for (size_t a = 0; a < nn; ++a)
         if (kept[a * T + t] == 0)
-          throw Error(ABN_ERR_INVALID_ARG, names[a] + " has no site above the posterior filter in this tile");
+          throw Error(ABN_ERR_INVALID_ARG, names[a] + " has no site above the posterior filter in this " + unit);
       for (size_t a = 0, p = 0; a < nn; ++a)
         for (size_t b = a + 1; b < nn; ++b, ++p)
           if (both[t * npairs + p] == 0)
-            throw Error(ABN_ERR_INVALID_ARG, names[a] + " and " + names[b] + " share no site above the posterior filter in this tile");
+            throw Error(ABN_ERR_INVALID_ARG, names[a] + " and " + names[b] + " share no site above the posterior filter in this " + unit);
       wins.push_back(window_from_handle(region, t, times, sample_of, nn, T, t, sum, kept, &dv[t * npairs]));
     } catch (const std::exception& e) {
-      std::printf("Error: Error while building pedigree: tile %zu (%s): %s\n", t, region.c_str(), e.what());
+      std::printf("Error: Error while building pedigree: %s %zu (%s): %s\n", unit, t, region.c_str(), e.what());
     }
   }
   TilesOutput res;
@@ -140,6 +205,13 @@ inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileAr
   for (const WindowResult& r : res.out.results) {
     fitted[r.window_index] = 1;
     res.out.results_txt += results_line(args.name, r.window_index, (long long)count[r.window_index], r);
+  }
+  if (tiles.pool) {
+    res.pools_txt = "pool;name;intervals;segments;cg_count;fitted\n";
+    for (size_t t = 0; t < T; ++t)
+      res.pools_txt += std::to_string(t) + ";" + pools.names[t] + ";" + std::to_string(pools.intervals[t]) + ";" +
+                       std::to_string(segments[t]) + ";" + std::to_string(count[t]) + ";" + (fitted[t] ? "1" : "0") + "\n";
+    return res;
   }
   res.tiles_txt = "tile;chromosome;start;end;cg_count;fitted\n";
   for (size_t t = 0; t < T; ++t)

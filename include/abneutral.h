@@ -655,6 +655,33 @@ int abn_tiles_stats(const abn_tiles* h, int64_t* count /* [T] */, double* level_
 int abn_tiles_pairwise(abn_tiles* h, uint64_t* diff, uint64_t* both, double* dvalue); /* host, [T x pairs] */
 int abn_tiles_kernel_ms(const abn_tiles* h, double* ms2 /* search, fold */);
 
+/* Region pools: one pedigree per annotation CLASS — every gene, every TE, each chromatin state of a list such as the rows
+ * src/cli/metaprofile.rs:50-72 reads — where abn_tiles_set_intervals makes one per row; stands in for cutting every
+ * methylome into per-class files on the host and Pedigree::build (src/pedigree.rs:147-172, :210-261) on each.
+ * abn_tiles_set_pools: interval k = (chromosome, start, end)[k], as a tile's, belongs to pool[k] in [0, n_pools).  A pool's
+ * columns are the handle's columns whose (chromosome, start) lies in at least one of its intervals, each once, in ascending
+ * column order (under align 0: the order of the lines in every sample's file); an interval may belong to several pools by
+ * being listed for each.  Per pool the intervals are merged — chromosomes in the run order of the columns, one without a
+ * run and intervals with end <= start dropped, overlapping or touching intervals joined — into SEGMENTS, whose columns are
+ * gathered on the device into a pooled matrix and pooled merged bytes and levels.  Afterwards the handle's tiles are the
+ * pools: abn_tiles_info reports n_tiles = n_pools, abn_tiles_layout every pool's range in POOLED column space,
+ * abn_tiles_stats and abn_tiles_pairwise the pools' folds and scans, abn_tiles_kernel_ms the search (of the segments) and
+ * the fold, abn_tiles_pool_kernel_ms double[4]: offsets, map, gather, pack.  A pool without a column is an empty tile, no
+ * error.  abn_tiles_intervals refuses on such a handle (ABN_ERR_INVALID_ARG; the text names abn_tiles_pool_segments).
+ * A later abn_tiles_set_intervals / _set_fixed puts the handle back on its own matrix, and the other way round.
+ * ABN_ERR_INVALID_ARG, the handle as it was: null pointers, n_intervals < 0, n_pools <= 0 or above INT32_MAX, a pool id
+ * outside [0, n_pools) (the text names the interval), an interval abn_tiles_set_intervals refuses, a pooled matrix beyond
+ * the limits of a handle's own ("too large for one handle").
+ * abn_tiles_pool_segments: *n_segments and, [n_segments] each in segment order (pool by pool, ascending columns inside
+ * one), the segment's pool, its merged interval and its columns [col_begin, col_end) of the handle's own matrix.
+ * abn_tiles_pool_columns: src [the last pool's layout end] = every pooled column's source column.  Any output may be NULL. */
+int abn_tiles_set_pools(abn_tiles* h, int64_t n_intervals, const int32_t* chromosome, const int64_t* start,
+                        const int64_t* end, const int32_t* pool, int64_t n_pools);
+int abn_tiles_pool_segments(const abn_tiles* h, int64_t* n_segments, int32_t* pool, int32_t* chromosome, int64_t* start,
+                            int64_t* end, int64_t* col_begin, int64_t* col_end);
+int abn_tiles_pool_columns(const abn_tiles* h, int64_t* src);
+int abn_tiles_pool_kernel_ms(const abn_tiles* h, double* ms4 /* offsets, map, gather, pack */);
+
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
  * src/cli/metaprofile.rs:50-72, where every window shares nodelist/edgelist), S starts and B bootstraps
