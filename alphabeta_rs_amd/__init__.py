@@ -779,8 +779,36 @@ class Context:
         return raw, info
 
 
-class Plan:
+class _Handle:
+    """A handle of the library (`_h`, made by the subclass through `_L`) and its end: `_DESTROY` names the entry point that
+    frees it, called once — by close() or when the object is collected."""
+
+    _DESTROY = ""
+    _h = None
+
+    @classmethod
+    def _new(cls, ctx: "Context"):
+        """an instance of ctx, its handle still to be made (the alternative constructors)"""
+        self = cls.__new__(cls)
+        self.ctx, self._L = ctx, ctx._L
+        return self
+
+    def close(self):
+        if self._h:
+            getattr(self._L, self._DESTROY)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Plan(_Handle):
     """abn_plan: device-resident batch of W windows x (S starts + B bootstraps) over one pedigree topology."""
+
+    _DESTROY = "abn_plan_destroy"
 
     def __init__(self, ctx: Context, generations, n_windows, n_starts, n_boot, *, window_offset=0, boot_offset=0,
                  options: Options | None = None):
@@ -792,17 +820,6 @@ class Plan:
         ctx._check(self._L.abn_plan_create(ctx._h, C.byref(options) if options else None, _dp(g), self.N, n_windows,
                                            n_starts, n_boot, window_offset, boot_offset, C.byref(h)))
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.abn_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_window_ids(self, ids):
         """ids[W]: every window's index in the Philox counters (default window_offset + w); before set_windows"""
@@ -939,26 +956,16 @@ def _site_arrays(site_offset, chromosome, start, end, strand):
                  ((chromosome, np.int32), (start, np.uint32), (end, np.uint32), (strand, np.uint8))]
 
 
-class Sites:
+class Sites(_Handle):
     """abn_sites: the parse results of one methylome text (Context.parse_sites_resident: the records resident on the
     device until close())."""
 
+    _DESTROY = "abn_sites_destroy"
     KINDS = {"line": np.int64, "chromosome": np.int32, "start": np.uint32, "end": np.uint32, "strand": np.uint8,
              "posteriormax": np.float64, "status": np.uint8, "status_flag": np.uint8, "meth_lvl": np.float64}
 
     def __init__(self, ctx: "Context", handle):
         self.ctx, self._L, self._h = ctx, ctx._L, handle
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.abn_sites_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         """{n_sites (the device's records plus the inserted ones), n_deferred, n_lines, kernel_ms}"""
@@ -999,10 +1006,12 @@ class Sites:
         return sites
 
 
-class Genes:
+class Genes(_Handle):
     """abn_genes: a gene annotation resident on the device.  lists = [(chromosome, kind, start, end, strand), ..]: the
     genes of one chromosome (0..255, 256 = M, 257 = C) and kind (0 sense, 1 antisense, 2 combined: GenesByStrand,
     src/genes.rs:127-163) as arrays, each list stably sorted by start as src/extract.rs:61-66 leaves it."""
+
+    _DESTROY = "abn_genes_destroy"
 
     def __init__(self, ctx: "Context", lists):
         self.ctx = ctx
@@ -1023,19 +1032,46 @@ class Genes:
         self._h = h
         self.n_genes = int(off[-1])
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.abn_genes_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class _PackedMatrix(_Handle):
+    """What Windows and Codes share: the report of the alignment they were made with, and the packed matrix
+    (n_samples, row_stride) they keep on the device.  `_PREFIX` is the C prefix of their entry points."""
+
+    _PREFIX = ""
+
+    def _entry(self, name):
+        return getattr(self._L, f"{self._PREFIX}_{name}")
+
+    def _aligned(self, entry, n_ms):
+        before, each, ms = np.zeros(self.n_samples, dtype=np.int64), C.c_int64(-1), np.zeros(n_ms)
+        self.ctx._check(self._entry(entry)(self._h, before.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(each), _dp(ms)))
+        return before, each.value, ms
+
+    def common(self):
+        """(before int64 (n_samples,), n_common, ms (4,)): every sample's sites before the alignment, the sites each keeps
+        (-1: not made with align) and the HIP-event ms of the common-site kernels (runs and ends, match, scan and rank,
+        gather; zeros without align)"""
+        return self._aligned("common", 4)
+
+    def union(self):
+        """(before int64 (n_samples,), n_union, ms (8,)): every sample's sites before the alignment, the sites each has
+        behind it, placeholders included (-1: not made with align="union") and the HIP-event ms of the union passes (runs
+        and ends, owner, scan, base, rank, dest, invert, gather; zeros otherwise)"""
+        return self._aligned("union", 8)
+
+    def packed(self) -> np.ndarray:
+        """the packed matrix (n_samples, row_stride) uint8, copied to the host"""
+        out = np.empty((self.n_samples, self.row_stride), dtype=np.uint8)
+        self.ctx._check(self._entry("packed")(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def packed_device_ptr(self) -> int:
+        p = C.c_void_p()
+        self.ctx._check(self._entry("packed_device_ptr")(self._h, C.byref(p)))
+        return p.value or 0
 
 
-class Windows:
+class Windows(_PackedMatrix):
     """abn_windows: the sites of n_samples methylomes placed into metaprofile windows on the device
     (MethylationSite::place_in_windows, src/methylation_site.rs:423-490), device-resident as the 2-bit packed matrix of
     Context.pairwise_divergence_windows_packed.
@@ -1043,6 +1079,8 @@ class Windows:
     site_offset (n_samples + 1,) int64; per site (concatenated over the samples, file order): pos, gene_start, gene_end
     uint32, flags uint8 (bit 0 antisense, bit 1 has a gene), code uint8 (status | 0x80 when filtered), level float64.
     cutoff, step, size, absolute: arguments::Windows; counts = (n_upstream, n_gene, n_downstream) of Windows::new."""
+
+    _DESTROY, _PREFIX = "abn_windows_destroy", "abn_windows"
 
     def __init__(self, ctx: Context, site_offset, pos, gene_start, gene_end, flags, code, level, *, cutoff, step, size,
                  absolute, counts):
@@ -1060,19 +1098,22 @@ class Windows:
         ctx._check(self._L.abn_windows_create(ctx._h, C.byref(p), self.n_samples, off.ctypes.data_as(C.POINTER(C.c_int64)),
                                               _u32p(u32[0]), _u32p(u32[1]), _u32p(u32[2]), u8[0].ctypes.data_as(u8p),
                                               u8[1].ctypes.data_as(u8p), _dp(lvl), C.byref(h)))
+        self._finish(h)
+
+    def _finish(self, h):
+        """the handle taken, and what abn_windows_info says of it"""
         self._h = h
         W, stride, ns = C.c_int32(), C.c_int64(), C.c_int64()
-        ctx._check(self._L.abn_windows_info(h, C.byref(W), C.byref(stride), C.byref(ns)))
+        self.ctx._check(self._L.abn_windows_info(h, C.byref(W), C.byref(stride), C.byref(ns)))
         self.W, self.row_stride, self.n_sites = W.value, stride.value, ns.value
+        return self
 
     @classmethod
     def from_sites(cls, ctx: Context, genes: Genes, site_offset, chromosome, start, end, strand, code, level, *, cutoff,
                    cutoff_gene_length=False, step, size, absolute, counts):
         """The handle from the sites' own fields (chromosome int32, start, end uint32, strand uint8; code, level as
         above): every site's gene is chosen on the device (Context.choose_genes) and handed to the placement there."""
-        self = cls.__new__(cls)
-        self.ctx = ctx
-        self._L = ctx._L
+        self = cls._new(ctx)
         off, u = _site_arrays(site_offset, chromosome, start, end, strand)
         self.n_samples = off.shape[0] - 1
         S = int(off[-1]) if off.shape[0] else 0
@@ -1086,11 +1127,7 @@ class Windows:
                                                     off.ctypes.data_as(C.POINTER(C.c_int64)),
                                                     u[0].ctypes.data_as(C.POINTER(C.c_int32)), _u32p(u[1]), _u32p(u[2]),
                                                     u[3].ctypes.data_as(u8p), co.ctypes.data_as(u8p), _dp(lvl), C.byref(h)))
-        self._h = h
-        W, stride, ns = C.c_int32(), C.c_int64(), C.c_int64()
-        ctx._check(self._L.abn_windows_info(h, C.byref(W), C.byref(stride), C.byref(ns)))
-        self.W, self.row_stride, self.n_sites = W.value, stride.value, ns.value
-        return self
+        return self._finish(h)
 
     @classmethod
     def from_parsed(cls, ctx: Context, genes: Genes, sites_list, *, posterior_max_filter, cutoff,
@@ -1101,9 +1138,7 @@ class Windows:
         "position": only the sites every sample shares (Context.common_sites) are placed (abn_windows_create_aligned);
         "union": every sample gets all the sites any sample holds, filtered placeholders where it lacks one
         (Context.union_sites, abn_windows_create_union).  Either way no window is ragged."""
-        self = cls.__new__(cls)
-        self.ctx = ctx
-        self._L = ctx._L
+        self = cls._new(ctx)
         sites_list = list(sites_list)
         self.n_samples = len(sites_list)
         p = WindowsParams(cutoff, step, size, 1 if absolute else 0, *map(int, counts))
@@ -1113,44 +1148,13 @@ class Windows:
         create = getattr(self._L, _ALIGN_CREATE[_align_mode(align)].format("windows"))
         ctx._check(create(ctx._h, C.byref(p), genes._h, C.byref(rule), posterior_max_filter, self.n_samples, handles,
                           C.byref(h)))
-        self._h = h
-        W, stride, ns = C.c_int32(), C.c_int64(), C.c_int64()
-        ctx._check(self._L.abn_windows_info(h, C.byref(W), C.byref(stride), C.byref(ns)))
-        self.W, self.row_stride, self.n_sites = W.value, stride.value, ns.value
-        return self
+        return self._finish(h)
 
     def merge_ms(self) -> np.ndarray:
         """the HIP-event ms of from_parsed's two merge kernels (fields, insert); zeros for the other forms"""
         ms = np.zeros(2)
         self.ctx._check(self._L.abn_windows_merge_ms(self._h, _dp(ms)))
         return ms
-
-    def common(self):
-        """(before int64 (n_samples,), n_common, ms (4,)): every sample's sites before the alignment, the sites each keeps
-        (-1: not made with align) and the HIP-event ms of the common-site kernels (runs and ends, match, scan and rank,
-        gather; zeros without align)"""
-        before, n_common, ms = np.zeros(self.n_samples, dtype=np.int64), C.c_int64(-1), np.zeros(4)
-        self.ctx._check(self._L.abn_windows_common(self._h, before.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_common), _dp(ms)))
-        return before, n_common.value, ms
-
-    def union(self):
-        """(before int64 (n_samples,), n_union, ms (8,)): every sample's sites before the alignment, the sites each has
-        behind it, placeholders included (-1: not made with align="union") and the HIP-event ms of the union passes (runs
-        and ends, owner, scan, base, rank, dest, invert, gather; zeros otherwise)"""
-        before, n_union, ms = np.zeros(self.n_samples, dtype=np.int64), C.c_int64(-1), np.zeros(8)
-        self.ctx._check(self._L.abn_windows_union(self._h, before.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_union), _dp(ms)))
-        return before, n_union.value, ms
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.abn_windows_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def stats(self):
         """(count int64, level_sum, level_sum_kept, kept int64), each (n_samples, W)"""
@@ -1171,17 +1175,6 @@ class Windows:
                                                    r.ctypes.data_as(C.POINTER(C.c_int32))))
         return b, e, r
 
-    def packed(self) -> np.ndarray:
-        """the packed matrix (n_samples, row_stride) uint8, copied to the host"""
-        out = np.empty((self.n_samples, self.row_stride), dtype=np.uint8)
-        self.ctx._check(self._L.abn_windows_packed(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return out
-
-    def packed_device_ptr(self) -> int:
-        p = C.c_void_p()
-        self.ctx._check(self._L.abn_windows_packed_device_ptr(self._h, C.byref(p)))
-        return p.value or 0
-
     def pairwise(self):
         """(diff, both, dvalue), each (W, pairs): pairwise_divergence of every window, on the resident matrix"""
         npairs = self.n_samples * (self.n_samples - 1) // 2
@@ -1193,10 +1186,12 @@ class Windows:
         return diff, both, dval
 
 
-class Codes:
+class Codes(_PackedMatrix):
     """abn_codes: what Pedigree::build reads of n_samples methylomes (src/pedigree.rs:147-172, :245-251), made on the device
     from resident parse results: the 2-bit packed matrix of Context.pairwise_divergence_packed, device-resident, and every
     sample's rc_meth_lvl fold."""
+
+    _DESTROY, _PREFIX = "abn_codes_destroy", "abn_codes"
 
     @classmethod
     def from_parsed(cls, ctx: Context, sites_list, *, posterior_max_filter, align=False):
@@ -1207,9 +1202,7 @@ class Codes:
         the same length then, and stats() describes the aligned sites.  align="union": every sample gets all the sites any
         sample holds, filtered placeholders where it lacks one (abn_codes_create_union): count is n_union, kept and the
         level sums are the unaligned handle's, and a pair is compared on the sites both hold."""
-        self = cls.__new__(cls)
-        self.ctx = ctx
-        self._L = ctx._L
+        self = cls._new(ctx)
         sites_list = list(sites_list)
         handles = (C.c_void_p * max(len(sites_list), 1))(*(s._h for s in sites_list))
         h = C.c_void_p()
@@ -1219,17 +1212,6 @@ class Codes:
         i = self.info()
         self.n_samples, self.n_sites, self.row_stride, self.same_len = i["n_samples"], i["n_sites"], i["row_stride"], i["same_len"]
         return self
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.abn_codes_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         """{n_samples, n_sites (of the longest sample), row_stride (bytes), same_len (bool)}"""
@@ -1246,17 +1228,6 @@ class Codes:
         self.ctx._check(self._L.abn_codes_stats(self._h, count.ctypes.data_as(i64p), _dp(lsk), kept.ctypes.data_as(i64p)))
         return count, lsk, kept
 
-    def packed(self) -> np.ndarray:
-        """the packed matrix (n_samples, row_stride) uint8, copied to the host"""
-        out = np.empty((self.n_samples, self.row_stride), dtype=np.uint8)
-        self.ctx._check(self._L.abn_codes_packed(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return out
-
-    def packed_device_ptr(self) -> int:
-        p = C.c_void_p()
-        self.ctx._check(self._L.abn_codes_packed_device_ptr(self._h, C.byref(p)))
-        return p.value or 0
-
     def pairwise(self):
         """(diff, both, dvalue), each (pairs,): pairwise_divergence_packed on the resident matrix; refused (AbnError) when
         the samples differ in length"""
@@ -1266,22 +1237,6 @@ class Codes:
         self.ctx._check(self._L.abn_codes_pairwise(self._h, diff.ctypes.data_as(u64p), both.ctypes.data_as(u64p), _dp(dval)))
         return diff, both, dval
 
-    def common(self):
-        """(before int64 (n_samples,), n_common, ms (4,)): every sample's sites before the alignment, the sites each keeps
-        (-1: not made with align) and the HIP-event ms of the common-site kernels (runs and ends, match, scan and rank,
-        gather; zeros without align)"""
-        before, n_common, ms = np.zeros(self.n_samples, dtype=np.int64), C.c_int64(-1), np.zeros(4)
-        self.ctx._check(self._L.abn_codes_common(self._h, before.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_common), _dp(ms)))
-        return before, n_common.value, ms
-
-    def union(self):
-        """(before int64 (n_samples,), n_union, ms (8,)): every sample's sites before the alignment, the sites each has
-        behind it, placeholders included (-1: not made with align="union") and the HIP-event ms of the union passes (runs
-        and ends, owner, scan, base, rank, dest, invert, gather; zeros otherwise)"""
-        before, n_union, ms = np.zeros(self.n_samples, dtype=np.int64), C.c_int64(-1), np.zeros(8)
-        self.ctx._check(self._L.abn_codes_union(self._h, before.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_union), _dp(ms)))
-        return before, n_union.value, ms
-
     def kernel_ms(self) -> np.ndarray:
         """the HIP-event ms of from_parsed's kernels: merge of the records, merge of the inserted lines, pack, fold"""
         ms = np.zeros(4)
@@ -1289,12 +1244,13 @@ class Codes:
         return ms
 
 
-class Tiles:
+class Tiles(_Handle):
     """abn_tiles: Pedigree::build (src/pedigree.rs:147-172, :210-261) once per genomic tile — a fixed bin or a listed region
     (the region rows of src/cli/metaprofile.rs:50-72) — over resident parse results: the aligned code matrix, its columns'
     keys and every sample's merged bytes and levels stay on the device; a tile is a contiguous column range.  set_pools makes
     a set of intervals one tile: its columns gathered into a pooled matrix (one pedigree per annotation class)."""
 
+    _DESTROY = "abn_tiles_destroy"
     ALIGN = {"none": 0, "position": 1, "union": 2}
 
     @classmethod
@@ -1303,9 +1259,7 @@ class Tiles:
         assumption that site k is the same site in every sample — the keys are sample 0's and every sample must have its
         number of sites; True / "position": the sites every sample shares; "union": every site any sample holds, filtered
         and uncounted placeholders where a sample lacks one."""
-        self = cls.__new__(cls)
-        self.ctx = ctx
-        self._L = ctx._L
+        self = cls._new(ctx)
         sites_list = list(sites_list)
         handles = (C.c_void_p * max(len(sites_list), 1))(*(s._h for s in sites_list))
         h = C.c_void_p()
@@ -1315,17 +1269,6 @@ class Tiles:
         i = self.info()
         self.n_samples, self.n_columns, self.row_stride, self.n_runs = i["n_samples"], i["n_columns"], i["row_stride"], i["n_runs"]
         return self
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.abn_tiles_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         """{n_samples, n_columns, row_stride (bytes), n_runs, n_tiles (-1 before set_intervals / set_fixed)}"""
@@ -1471,9 +1414,11 @@ def rccl_available() -> bool:
     return bool(ok.value)
 
 
-class MultiPlan:
+class MultiPlan(_Handle):
     """abn_multi: one process, several GPUs — a plan per device, windows (or, with fewer windows than devices,
     bootstraps) sharded in contiguous blocks, the bootstrap tables gathered with RCCL over xGMI."""
+
+    _DESTROY = "abn_multi_destroy"
 
     def __init__(self, devices, generations, n_windows, n_starts, n_boot, *, options: Options | None = None):
         self._L = load_library()
@@ -1493,17 +1438,6 @@ class MultiPlan:
     def _check(self, rc):
         if rc:
             raise AbnError(rc, (self._L.abn_multi_last_error(self._h) or b"").decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.abn_multi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_window_ids(self, ids):
         a = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(self.W)

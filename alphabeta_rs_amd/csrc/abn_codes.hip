@@ -3,7 +3,8 @@
 // abn_codes.hpp; the merge launches are abn_sites.hip's (the records are its handle's), the scan abn_pairwise.hip's, the
 // common-site step of abn_codes_create_aligned abn_sites_common.hip's, the union step of abn_codes_create_union
 // abn_sites_union.hip's; the handles' refusals, the merge loops and the alignment's dispatch are abn_resident.hip's, shared
-// with abn_windows.hip and abn_tiles.hip.
+// with abn_windows.hip and abn_tiles.hip, and so are the handle's shell (handle_create, handle_destroy, handle_packed) and
+// the upload of the pack's offsets (PackOffsets), abn_host.hpp's.
 #include "abn_host.hpp"
 #define ABN_CODES_KERNELS
 #include "abn_codes.hpp"
@@ -52,7 +53,10 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, i
     h->max_sites = a.each;
     h->same_len = true;
   }
-  std::vector<int64_t> site_off((size_t)n + 1, 0), code_off((size_t)n + 1, 0);
+  PackOffsets off;  // the samples may differ in length: the fold reads the offsets too
+  std::vector<int64_t>& site_off = off.site;
+  std::vector<int64_t>& code_off = off.code;
+  site_off.assign((size_t)n + 1, 0), code_off.assign((size_t)n + 1, 0);
   for (int s = 0; s < n; ++s) {
     site_off[(size_t)s + 1] = site_off[(size_t)s] + h->count[(size_t)s];
     code_off[(size_t)s + 1] = code_off[(size_t)s] + (h->count[(size_t)s] + 15) / 16 * 16;  // whole 16-byte loads of the pack
@@ -64,17 +68,13 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, i
 
   DevBuf<uint8_t> dcode;
   DevBuf<double> dlevel, dsum;
-  DevBuf<long long> dsite_off, dcode_off, dkept;
-  static_assert(sizeof(long long) == sizeof(int64_t), "the offsets on the device");
+  DevBuf<long long> dkept;
   HIPCHK(c, dcode.alloc(std::max<size_t>((size_t)code_off[(size_t)n], 16)));
   HIPCHK(c, dlevel.alloc(std::max<size_t>((size_t)site_off[(size_t)n], 1)));
-  HIPCHK(c, dsite_off.alloc((size_t)n + 1));
-  HIPCHK(c, dcode_off.alloc((size_t)n + 1));
   HIPCHK(c, dsum.alloc((size_t)n));
   HIPCHK(c, dkept.alloc((size_t)n));
   HIPCHK(c, h->packed.alloc((size_t)n * (size_t)h->stride));
-  HIPCHK(c, hipMemcpyAsync(dsite_off.p, site_off.data(), dsite_off.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dcode_off.p, code_off.data(), dcode_off.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (int rc = off.upload(c)) return rc;
 
   // the reduced merge, timed as ms[0..1]: into the merged arrays under an alignment, else straight into what the pack and
   // the fold read
@@ -89,10 +89,10 @@ static int codes_build(abn_codes* h, double filter, abn_sites* const* samples, i
   }
   // the builder's own: pack and fold
   if (int rc = ev.record(c, 2)) return rc;
-  if (int rc = codes_pack_dev(c, dcode.p, dcode_off.p, dsite_off.p, n, row_dwords, h->packed.p)) return rc;
+  if (int rc = codes_pack_dev(c, dcode.p, off.dcode.p, off.dsite.p, n, row_dwords, h->packed.p)) return rc;
   if (int rc = ev.record(c, 3)) return rc;
   hipLaunchKernelGGL(abn_codes_fold_kernel, dim3((unsigned)n), dim3(kCodesWave), 0, c->stream, dcode.p, dlevel.p,
-                     dcode_off.p, dsite_off.p, dsum.p, dkept.p);
+                     off.dcode.p, off.dsite.p, dsum.p, dkept.p);
   HIPCHK(c, hipGetLastError());
   if (int rc = ev.record(c, 4)) return rc;
   std::vector<long long> kept((size_t)n);
@@ -112,26 +112,16 @@ static int codes_create_parsed(abn_ctx* c, double posterior_max_filter, int32_t 
   if (out) *out = nullptr;
   if (!out || !samples || n_samples <= 0) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
   if (n_samples > 65535) return set_err(c, ABN_ERR_INVALID_ARG, "too many samples");
-  std::unique_ptr<abn_codes> h(new (std::nothrow) abn_codes);
-  if (!h) return set_err(c, ABN_ERR_HIP, "out of host memory");
-  h->ctx = c;
-  h->n = n_samples;
-  try {
+  return handle_create(c, n_samples, out, [&](abn_codes* h) {
     h->count.assign((size_t)n_samples, 0);
     if (int rc = resident_counts(c, n_samples, samples, h->count.data())) return rc;
     for (int64_t count : h->count) {
       h->max_sites = std::max(h->max_sites, count);
       if (count != h->count[0]) h->same_len = false;
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    PoolScope pool_scope(c);
     h->report.before = h->count;
-    if (int rc = codes_build(h.get(), posterior_max_filter, samples, align)) return rc;
-  } catch (const std::bad_alloc&) {
-    return set_err(c, ABN_ERR_HIP, "out of host memory");
-  }
-  *out = h.release();
-  return ABN_OK;
+    return codes_build(h, posterior_max_filter, samples, align);
+  });
 }
 
 extern "C" int abn_codes_create_parsed(abn_ctx* c, double posterior_max_filter, int32_t n_samples,
@@ -157,12 +147,7 @@ extern "C" int abn_codes_union(const abn_codes* h, int64_t* before, int64_t* n_u
   return h ? h->report.unite(before, n_union, ms8) : ABN_ERR_INVALID_ARG;
 }
 
-extern "C" int abn_codes_destroy(abn_codes* h) {
-  if (!h) return ABN_ERR_INVALID_ARG;
-  (void)hipSetDevice(h->ctx->device);
-  delete h;
-  return ABN_OK;
-}
+extern "C" int abn_codes_destroy(abn_codes* h) { return handle_destroy(h); }
 
 extern "C" int abn_codes_info(const abn_codes* h, int32_t* n_samples, int64_t* n_sites, int64_t* row_stride_bytes,
                               int32_t* same_len) {
@@ -182,15 +167,7 @@ extern "C" int abn_codes_stats(const abn_codes* h, int64_t* count, double* level
   return ABN_OK;
 }
 
-extern "C" int abn_codes_packed(abn_codes* h, uint8_t* host_out) {
-  if (!h) return ABN_ERR_INVALID_ARG;
-  abn_ctx* c = h->ctx;
-  if (!host_out) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(host_out, h->packed.p, h->packed.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ABN_OK;
-}
+extern "C" int abn_codes_packed(abn_codes* h, uint8_t* host_out) { return handle_packed(h, host_out); }
 
 extern "C" int abn_codes_packed_device_ptr(abn_codes* h, void** dev_ptr) {
   if (!h || !dev_ptr) return ABN_ERR_INVALID_ARG;

@@ -1,8 +1,8 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (abn_api.hip, abn_pairwise.hip,
 // abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip,
 // abn_tiles.hip, abn_resident.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
-// events of a call, and what the consumers of resident methylomes share (abn_resident.hip).  Not part of the C-ABI
-// (include/abneutral.h is).
+// events of a call, the shell of the windows, codes and tiles handles (created, destroyed, their packed matrix read), and
+// what the consumers of resident methylomes share (abn_resident.hip).  Not part of the C-ABI (include/abneutral.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -216,6 +216,45 @@ int pairwise_to_host(abn_ctx* c, size_t count, uint64_t* diff, uint64_t* both, d
   return ABN_OK;
 }
 
+// The shell of the handles that hold a packed matrix — abn_windows, abn_codes, abn_tiles; each has `ctx` and `n` (samples)
+// — behind their entry points' own checks.  handle_create: a handle of context c and n_samples samples around
+// build(handle), on c's device and drawing from its pool; handed out in *out when build returns ABN_OK, else deleted.
+// (abn_genes_create draws from no pool and abn_sites has a host form without a context: they keep their own.)
+template <class H, class Build>
+int handle_create(abn_ctx* c, int32_t n_samples, H** out, Build build) {
+  std::unique_ptr<H> h(new (std::nothrow) H);
+  if (!h) return set_err(c, ABN_ERR_HIP, "out of host memory");
+  h->ctx = c;
+  h->n = n_samples;
+  try {
+    HIPCHK(c, hipSetDevice(c->device));
+    PoolScope pool_scope(c);
+    if (int rc = build(h.get())) return rc;
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+  *out = h.release();
+  return ABN_OK;
+}
+template <class H>
+int handle_destroy(H* h) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  (void)hipSetDevice(h->ctx->device);
+  delete h;
+  return ABN_OK;
+}
+// ... and `packed` of an abn_windows or abn_codes to the host, the stream synchronised
+template <class H>
+int handle_packed(H* h, uint8_t* host_out) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = h->ctx;
+  if (!host_out) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(host_out, h->packed.p, h->packed.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ABN_OK;
+}
+
 namespace abn {
 // abn_analyze.hip, for abn_plan_analyze (abn_api.hip): the analysis (abn_analyze.hpp) of a device-resident table
 // raw[W x B x 7] on the context's stream, results to the host; returns after completion, ABN_ERR_NO_FINITE_FIT as
@@ -232,10 +271,10 @@ int genes_choose_dev(abn_genes* h, const abn_gene_rule* rule, int32_t n_samples,
                      const int32_t* dchrom, const uint32_t* dstart, const uint32_t* dend, const uint8_t* dstrand,
                      uint32_t* dgene_start, uint32_t* dgene_end, uint8_t* dflags, double* kernel_ms);
 abn_ctx* genes_ctx(const abn_genes* h);
-// abn_sites.hip, for the builders from resident parse results (through abn_resident.hip, below).  The context of a resident handle (null: host form);
-// its sites once the inserted records are in (-1: host form, or deferred lines without abn_sites_insert); and the merge
-// (abn_sites_merge.hpp) of one sample into the arrays at its first site, on the context's stream, nothing waited for:
-// the fields kernel of every chunk (inserted = false) or the insert kernel (true).
+// abn_sites.hip, for the builders from resident parse results (through abn_resident.hip, below).  The context of a
+// resident handle (null: host form); its sites once the inserted records are in (-1: host form, or deferred lines without
+// abn_sites_insert); and the merge (abn_sites_merge.hpp) of one sample into the arrays at its first site, on the context's
+// stream, nothing waited for: the fields kernel of every chunk (inserted = false) or the insert kernel (true).
 abn_ctx* sites_ctx(const abn_sites* h);
 int64_t sites_merged_count(const abn_sites* h);
 int sites_merge_dev(const abn_sites* h, bool inserted, double filter, int32_t* dchrom, uint32_t* dstart, uint32_t* dend,
@@ -243,10 +282,25 @@ int sites_merge_dev(const abn_sites* h, bool inserted, double filter, int32_t* d
 // ... and for abn_codes_create_parsed (abn_codes.hip): the same merge in its reduced form (abn_codes.hpp), the merged byte
 // and the level of every site
 int sites_merge_codes_dev(const abn_sites* h, bool inserted, double filter, uint8_t* dcode, double* dlevel);
-// abn_codes.hip, for abn_tiles_create (abn_tiles.hip): the pack of n samples' merged bytes (sample s: dcode +
-// dcode_off[s], a multiple of 16; dsite_off[s + 1] - dsite_off[s] sites) into dpacked [n x 4 row_dwords bytes]
+// abn_codes.hip, for abn_tiles.hip too: the pack of n samples' merged bytes (sample s: dcode + dcode_off[s], a multiple of
+// 16; dsite_off[s + 1] - dsite_off[s] sites) into dpacked [n x 4 row_dwords bytes]
 int codes_pack_dev(abn_ctx* c, const uint8_t* dcode, const long long* dcode_off, const long long* dsite_off, int n,
                    long long row_dwords, uint8_t* dpacked);
+// ... and the two offset arrays it reads, [n + 1] each: the host's, filled by the builder, and upload's copies of them on
+// the device (nothing waited for: the host's stay until the stream has been)
+struct PackOffsets {
+  std::vector<int64_t> site, code;
+  DevBuf<long long> dsite, dcode;
+  int upload(abn_ctx* c) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "the offsets on the device");
+    HIPCHK(c, dsite.alloc(site.size()));
+    HIPCHK(c, dcode.alloc(code.size()));
+    HIPCHK(c, hipMemcpyAsync(dsite.p, site.data(), dsite.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dcode.p, code.data(), dcode.bytes(), hipMemcpyHostToDevice, c->stream));
+    return ABN_OK;
+  }
+  void release() { site.clear(), code.clear(), dsite.release(), dcode.release(); }
+};
 // The checks every entry point makes of a site_offset [n_samples + 1] it is given
 inline int site_offset_check(abn_ctx* c, int32_t n_samples, const int64_t* site_offset) {
   if (site_offset[0] != 0) return set_err(c, ABN_ERR_INVALID_ARG, "site_offset[0] is not 0");

@@ -2,7 +2,8 @@
 // (abn_windows.hip), abn_codes_create_parsed / _aligned / _union (abn_codes.hip) and abn_tiles_create (abn_tiles.hip): the
 // refusals of their abn_sites handles, the merge of every sample's records on the device (its launches are
 // abn_sites.hip's), and the optional alignment of the merged arrays — the common-site step (abn_sites_common.hip) or the
-// union step (abn_sites_union.hip) — with its gather and its report.  Host code only: no kernel is defined here.
+// union step (abn_sites_union.hip) — with its gather and its report.  Host code only: no kernel is defined here.  What
+// they share behind the front end — the handle's shell and the upload of a pack's offsets — is inline in abn_host.hpp.
 #include "abn_host.hpp"
 
 using namespace abn;

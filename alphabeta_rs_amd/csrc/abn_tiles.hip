@@ -1,24 +1,62 @@
 // abn_tiles_*: genomic tiles over resident, aligned methylomes — Pedigree::build (src/pedigree.rs:147-172, :210-261) once
 // per fixed bin or listed region.  Kernels, the definition and the serial forms: abn_tiles.hpp.  The build is
 // abn_codes.hip's (merge, optional common-site or union step, gather, pack) with the columns' keys, the merged bytes and the
-// levels kept; the front end both share is abn_resident.hip's, the merge launches are abn_sites.hip's, the order checks
-// (RunTables) abn_sites_common.hip's, the scan abn_pairwise.hip's, the pack of a pooled matrix abn_codes.hip's.
+// levels kept; the front end both share is abn_resident.hip's, the handle's shell, the pack launch and its offsets
+// (handle_create, codes_pack_dev, PackOffsets) abn_host.hpp's, the merge launches are abn_sites.hip's, the order checks
+// (RunTables) abn_sites_common.hip's, the scan abn_pairwise.hip's.  The handle's own matrix and the pooled one are two
+// TileMatrix records; the tiles run and the pools run are made of the same steps (interval upload, search, fold, results),
+// the pools run with offsets, map, gather and pack in between.
 #include "abn_host.hpp"
 #define ABN_TILES_KERNELS
 #include "abn_tiles.hpp"
 
 using namespace abn;
 
+// A uniform matrix, n rows of `columns` sites, as the pack writes it and the fold and the scan read it.  tiles_matrix_shape
+// gives the strides — false: the matrix is beyond the limits of a handle (tiles_matrix_fits), and the caller refuses it
+// with its own text; alloc takes the shape, allocates the three arrays and sends the pack's offsets up; pack is the
+// launch, nothing waited for.
+struct MatrixShape {
+  long long columns = 0;
+  long long stride = 0;       // bytes per row of `packed`
+  long long code_stride = 0;  // bytes per sample of `code`: columns up to a multiple of 16
+};
+
+static bool tiles_matrix_shape(int n, long long columns, MatrixShape* shape) {
+  *shape = MatrixShape{columns, std::max<long long>(abn_packed_row_stride(columns), 64),
+                       (columns + 15) / 16 * 16};  // (whole 16-byte loads of the pack)
+  return tiles_matrix_fits(n, columns, shape->stride);
+}
+
+struct TileMatrix : MatrixShape {
+  DevBuf<uint8_t> packed;  // [n x stride]
+  DevBuf<uint8_t> code;    // [n x code_stride] merged bytes
+  DevBuf<double> level;    // [n x columns]
+  PackOffsets off;         // sample s: its sites from s x columns, its merged bytes from s x code_stride
+
+  int alloc(abn_ctx* c, int n, const MatrixShape& shape) {
+    MatrixShape::operator=(shape);
+    const size_t rows = (size_t)n;
+    HIPCHK(c, code.alloc(std::max<size_t>(rows * (size_t)code_stride, 16)));
+    HIPCHK(c, level.alloc(rows * std::max<size_t>((size_t)columns, 1)));
+    HIPCHK(c, packed.alloc(rows * (size_t)stride));
+    off.site.resize(rows + 1), off.code.resize(rows + 1);
+    for (size_t s = 0; s <= rows; ++s) off.site[s] = (int64_t)s * columns, off.code[s] = (int64_t)s * code_stride;
+    return off.upload(c);
+  }
+  int pack(abn_ctx* c, int n) { return codes_pack_dev(c, code.p, off.dcode.p, off.dsite.p, n, stride / 4, packed.p); }
+  void release_staging() { code.release(), level.release(), off.release(); }  // what only a build reads: `packed` stays
+  void reset() {
+    MatrixShape::operator=(MatrixShape{});
+    packed.release(), release_staging();
+  }
+};
+
 struct abn_tiles {
   abn_ctx* ctx = nullptr;
   int n = 0;
-  long long n_columns = 0;
-  long long stride = 0;       // bytes per row of `packed`
-  long long code_stride = 0;  // bytes per sample of `code`: n_columns up to a multiple of 16
-  DevBuf<uint8_t> packed;     // [n x stride]
-  DevBuf<uint8_t> code;       // [n x code_stride] merged bytes
-  DevBuf<double> level;       // [n x n_columns]
-  DevBuf<int32_t> chromosome; // [n_columns] the columns' keys
+  TileMatrix own;             // the handle's own matrix, whole
+  DevBuf<int32_t> chromosome; // [own.columns] the columns' keys
   DevBuf<uint32_t> start;
   RunTables tables;           // of the columns as one sample: run_begin, run_end [kCommonChroms]
   std::vector<TileRun> runs;
@@ -31,17 +69,15 @@ struct abn_tiles {
   double ms[2] = {0.0, 0.0};  // search, fold
   // pools (abn_tiles_set_pools): the tiles are the pools, their columns those of the pooled matrix
   bool pooled = false;
-  long long pool_columns = 0, pool_stride = 0;
-  DevBuf<uint8_t> pool_packed;  // [n x pool_stride]
-  DevBuf<long long> pool_src;   // [pool_columns] every pooled column's source column
+  TileMatrix pool;             // the pooled matrix: `packed` alone outlives abn_tiles_set_pools
+  DevBuf<long long> pool_src;  // [pool.columns] every pooled column's source column
   PoolSegments segments;
   std::vector<int64_t> seg_begin, seg_end;  // [S] the segments' columns
   double pool_ms[4] = {0.0, 0.0, 0.0, 0.0};  // offsets, map, gather, pack
 
   void drop_pools() {
     pooled = false;
-    pool_columns = pool_stride = 0;
-    pool_packed.release();
+    pool.reset();
     pool_src.release();
     segments = PoolSegments{};
     seg_begin.clear();
@@ -65,24 +101,17 @@ static int tiles_build(abn_tiles* h, double filter, abn_sites* const* samples, i
     if (int rc = sites_align(c, align, n, m.off.data(), m.keys(), a)) return rc;
     each = a.each;
   }
-  h->n_columns = each;
-  h->code_stride = (each + 15) / 16 * 16;  // whole 16-byte loads of the pack
-  h->stride = std::max<long long>(abn_packed_row_stride(each), 64);
-  const long long row_dwords = h->stride / 4;
-  if (!tiles_matrix_fits(n, each, h->stride))
-    return set_err(c, ABN_ERR_INVALID_ARG, "packed matrix too large for one handle");
+  TileMatrix& own = h->own;
+  MatrixShape shape;
+  if (!tiles_matrix_shape(n, each, &shape)) return set_err(c, ABN_ERR_INVALID_ARG, "packed matrix too large for one handle");
+  if (int rc = own.alloc(c, n, shape)) return rc;
   const size_t E = std::max<size_t>((size_t)each, 1);
-  HIPCHK(c, h->code.alloc(std::max<size_t>((size_t)n * (size_t)h->code_stride, 16)));
-  HIPCHK(c, h->level.alloc((size_t)n * E));
   HIPCHK(c, h->chromosome.alloc(E));
   HIPCHK(c, h->start.alloc(E));
-  HIPCHK(c, h->packed.alloc((size_t)n * (size_t)h->stride));
-  std::vector<int64_t> site_off((size_t)n + 1), code_off((size_t)n + 1);
-  for (int s = 0; s <= n; ++s) site_off[(size_t)s] = (int64_t)s * each, code_off[(size_t)s] = (int64_t)s * h->code_stride;
 
   // the reduced merge: the merged bytes (merge_code has no kCodeCounted) and the levels, into the merged arrays under an
   // alignment, else straight into the handle's
-  const CodeTargets kept{h->code.p, code_off.data(), h->level.p, site_off.data()};
+  const CodeTargets kept{own.code.p, own.off.code.data(), own.level.p, own.off.site.data()};
   if (int rc = m.merge_codes(c, n, samples, before.data(), filter, align ? nullptr : &kept, nullptr)) return rc;
   // the columns' four key fields, for the order checks: sample 0's after the gather, or as merged
   SiteKeys gkey;
@@ -90,7 +119,7 @@ static int tiles_build(abn_tiles* h, double filter, abn_sites* const* samples, i
   if (align) {
     if (int rc = gkey.alloc(c, (size_t)n * E)) return rc;
     const CommonGather g{m.code.p,      m.level.p,  gkey.chrom.p, gkey.start.p,  gkey.end.p,
-                         gkey.strand.p, h->level.p, h->code.p,    h->code_stride};
+                         gkey.strand.p, own.level.p, own.code.p,   own.code_stride};
     if (int rc = sites_align_gather(c, a, g)) return rc;
     columns = gkey.keys();  // (sample 0's are the first `each` of each)
   }
@@ -111,14 +140,7 @@ static int tiles_build(abn_tiles* h, double filter, abn_sites* const* samples, i
                      c->stream, (const uint32_t*)h->start.p, (const long long*)tab.run_begin.p,
                      (const long long*)tab.run_end.p, dlast.p);
   HIPCHK(c, hipGetLastError());
-  // the pack
-  DevBuf<long long> dsite_off, dcode_off;
-  static_assert(sizeof(long long) == sizeof(int64_t), "the offsets on the device");
-  HIPCHK(c, dsite_off.alloc((size_t)n + 1));
-  HIPCHK(c, dcode_off.alloc((size_t)n + 1));
-  HIPCHK(c, hipMemcpyAsync(dsite_off.p, site_off.data(), dsite_off.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dcode_off.p, code_off.data(), dcode_off.bytes(), hipMemcpyHostToDevice, c->stream));
-  if (int rc = codes_pack_dev(c, h->code.p, dcode_off.p, dsite_off.p, n, row_dwords, h->packed.p)) return rc;
+  if (int rc = own.pack(c, n)) return rc;
 
   long long run_begin[kCommonChroms], run_end[kCommonChroms];
   uint32_t last[kCommonChroms];
@@ -129,6 +151,7 @@ static int tiles_build(abn_tiles* h, double filter, abn_sites* const* samples, i
   if (int rc = tab.refusal(c, kCommonSplitRun, kCommonBadKey, &r)) return rc;  // (waits; the merged arrays are freed on return)
   tab.dsite_off.release();  // the handle keeps the two tables alone
   tab.err.release();
+  own.off.release();  // the pack has read its offsets (code and level stay: the folds and the pools read them)
   if (r.kind)
     return set_err(c, ABN_ERR_INVALID_ARG,
                    "the sites cannot be cut into tiles: their keys are not well ordered: " + common_refusal_text(r));
@@ -144,11 +167,7 @@ extern "C" int abn_tiles_create(abn_ctx* c, double posterior_max_filter, int32_t
   if (n_samples > 65535) return set_err(c, ABN_ERR_INVALID_ARG, "too many samples");
   if (align != kAlignNone && align != kAlignPosition && align != kAlignUnion)
     return set_err(c, ABN_ERR_INVALID_ARG, "align expects 0 (none), 1 (position) or 2 (union)");
-  std::unique_ptr<abn_tiles> h(new (std::nothrow) abn_tiles);
-  if (!h) return set_err(c, ABN_ERR_HIP, "out of host memory");
-  h->ctx = c;
-  h->n = n_samples;
-  try {
+  return handle_create(c, n_samples, out, [&](abn_tiles* h) {
     std::vector<int64_t> count((size_t)n_samples, 0);
     if (int rc = resident_counts(c, n_samples, samples, count.data())) return rc;
     if (align == kAlignNone)
@@ -158,29 +177,18 @@ extern "C" int abn_tiles_create(abn_ctx* c, double posterior_max_filter, int32_t
                          "sample " + std::to_string(s) + " has " + std::to_string(count[(size_t)s]) + " sites, sample 0 has " +
                              std::to_string(count[0]) +
                              ": tiles need the same sites in every sample; align them with --align position or --align union");
-    HIPCHK(c, hipSetDevice(c->device));
-    PoolScope pool_scope(c);
-    if (int rc = tiles_build(h.get(), posterior_max_filter, samples, align, count)) return rc;
-  } catch (const std::bad_alloc&) {
-    return set_err(c, ABN_ERR_HIP, "out of host memory");
-  }
-  *out = h.release();
-  return ABN_OK;
+    return tiles_build(h, posterior_max_filter, samples, align, count);
+  });
 }
 
-extern "C" int abn_tiles_destroy(abn_tiles* h) {
-  if (!h) return ABN_ERR_INVALID_ARG;
-  (void)hipSetDevice(h->ctx->device);
-  delete h;
-  return ABN_OK;
-}
+extern "C" int abn_tiles_destroy(abn_tiles* h) { return handle_destroy(h); }
 
 extern "C" int abn_tiles_info(const abn_tiles* h, int32_t* n_samples, int64_t* n_columns, int64_t* row_stride_bytes,
                               int32_t* n_runs, int64_t* n_tiles) {
   if (!h) return ABN_ERR_INVALID_ARG;
   if (n_samples) *n_samples = h->n;
-  if (n_columns) *n_columns = h->n_columns;
-  if (row_stride_bytes) *row_stride_bytes = h->stride;
+  if (n_columns) *n_columns = h->own.columns;
+  if (row_stride_bytes) *row_stride_bytes = h->own.stride;
   if (n_runs) *n_runs = (int32_t)h->runs.size();
   if (n_tiles) *n_tiles = h->has_tiles ? (int64_t)h->begin.size() : -1;
   return ABN_OK;
@@ -197,51 +205,102 @@ extern "C" int abn_tiles_runs(const abn_tiles* h, int32_t* chromosome, int64_t* 
   return ABN_OK;
 }
 
-// the search and the folds of the handle's interval list; the list is valid
-static int tiles_run(abn_tiles* h) {
+// ------------------------------------------------------------------------------------------------
+// The steps the tiles run (tiles_run) and the pools run (tiles_run_pools) are made of, each on the context's stream; none
+// waits, none records an event: the spans of kernel_ms and pool_kernel_ms are their callers'.
+// ------------------------------------------------------------------------------------------------
+// An interval list on the device (no interval: nothing is allocated, nothing sent)
+struct DevIntervals {
+  DevBuf<int32_t> chrom;
+  DevBuf<long long> pos, pos_end;
+  template <class Pos>
+  int upload(abn_ctx* c, const std::vector<int32_t>& chromosome, const std::vector<Pos>& start, const std::vector<Pos>& end) {
+    static_assert(sizeof(Pos) == sizeof(long long), "positions");
+    const size_t count = chromosome.size();
+    HIPCHK(c, chrom.alloc(count));
+    HIPCHK(c, pos.alloc(count));
+    HIPCHK(c, pos_end.alloc(count));
+    if (count == 0) return ABN_OK;
+    HIPCHK(c, hipMemcpyAsync(chrom.p, chromosome.data(), chrom.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pos.p, start.data(), pos.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pos_end.p, end.data(), pos_end.bytes(), hipMemcpyHostToDevice, c->stream));
+    return ABN_OK;
+  }
+};
+
+// The column ranges of T tiles and what the fold makes of them, [n x T], on the device
+struct DevTiles {
+  DevBuf<long long> begin, end, kept;
+  DevBuf<double> sum;
+  int alloc(abn_ctx* c, size_t n, size_t T) {
+    HIPCHK(c, begin.alloc(T));
+    HIPCHK(c, end.alloc(T));
+    HIPCHK(c, sum.alloc(n * T));
+    HIPCHK(c, kept.alloc(n * T));
+    return ABN_OK;
+  }
+};
+
+// the search of the intervals' columns in the handle's own matrix: [iv's count] begin, end (no interval: no launch)
+static int tiles_search(const abn_tiles* h, const DevIntervals& iv, long long* begin, long long* end) {
   abn_ctx* c = h->ctx;
-  const size_t T = h->tchromosome.size(), n = (size_t)h->n;
+  const size_t count = iv.chrom.n;
+  if (count == 0) return ABN_OK;
+  hipLaunchKernelGGL(abn_tiles_search_kernel, dim3((unsigned)((count + kTilesThreads - 1) / kTilesThreads)), dim3(kTilesThreads),
+                     0, c->stream, (const uint32_t*)h->start.p, (const long long*)h->tables.run_begin.p,
+                     (const long long*)h->tables.run_end.p, (long long)count, (const int32_t*)iv.chrom.p,
+                     (const long long*)iv.pos.p, (const long long*)iv.pos_end.p, begin, end);
+  HIPCHK(c, hipGetLastError());
+  return ABN_OK;
+}
+
+// the folds of every sample over the ranges r.begin, r.end [T > 0] of m's columns
+static int tiles_fold(const abn_tiles* h, const TileMatrix& m, size_t T, DevTiles& r) {
+  abn_ctx* c = h->ctx;
+  hipLaunchKernelGGL(abn_tiles_fold_kernel, dim3((unsigned)T, (unsigned)h->n), dim3(kCodesWave), 0, c->stream,
+                     (const uint8_t*)m.code.p, m.code_stride, (const double*)m.level.p, m.columns, (long long)T,
+                     (const long long*)r.begin.p, (const long long*)r.end.p, r.sum.p, r.kept.p);
+  HIPCHK(c, hipGetLastError());
+  return ABN_OK;
+}
+
+// the results of T tiles: the handle's arrays sized, and (T > 0) the copies of r into them queued
+static int tiles_results(abn_tiles* h, size_t T, const DevTiles& r) {
+  abn_ctx* c = h->ctx;
+  const size_t n = (size_t)h->n;
   h->begin.assign(T, 0);
   h->end.assign(T, 0);
   h->level_sum_kept.assign(n * T, 0.0);
   h->kept.assign(n * T, 0);
-  h->ms[0] = h->ms[1] = 0.0;
-  h->has_tiles = true;
   if (T == 0) return ABN_OK;
+  static_assert(sizeof(long long) == sizeof(int64_t), "columns");
+  HIPCHK(c, hipMemcpyAsync(h->begin.data(), r.begin.p, r.begin.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h->end.data(), r.end.p, r.end.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h->level_sum_kept.data(), r.sum.p, r.sum.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h->kept.data(), r.kept.p, r.kept.bytes(), hipMemcpyDeviceToHost, c->stream));
+  return ABN_OK;
+}
+
+// the search and the folds of the handle's interval list; the list is valid
+static int tiles_run(abn_tiles* h) {
+  abn_ctx* c = h->ctx;
+  const size_t T = h->tchromosome.size();
+  h->ms[0] = h->ms[1] = 0.0;
+  if (T == 0) return tiles_results(h, 0, DevTiles{});
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
-  DevBuf<int32_t> dchrom;
-  DevBuf<long long> dpos, dpos_end, dbegin, dend, dkept;
-  DevBuf<double> dsum;
-  HIPCHK(c, dchrom.alloc(T));
-  HIPCHK(c, dpos.alloc(T));
-  HIPCHK(c, dpos_end.alloc(T));
-  HIPCHK(c, dbegin.alloc(T));
-  HIPCHK(c, dend.alloc(T));
-  HIPCHK(c, dsum.alloc(n * T));
-  HIPCHK(c, dkept.alloc(n * T));
-  static_assert(sizeof(long long) == sizeof(int64_t), "positions and columns");
-  HIPCHK(c, hipMemcpyAsync(dchrom.p, h->tchromosome.data(), dchrom.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dpos.p, h->tstart.data(), dpos.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dpos_end.p, h->tend.data(), dpos_end.bytes(), hipMemcpyHostToDevice, c->stream));
+  DevIntervals iv;
+  DevTiles r;
+  if (int rc = iv.upload(c, h->tchromosome, h->tstart, h->tend)) return rc;
+  if (int rc = r.alloc(c, (size_t)h->n, T)) return rc;
   Events<3> ev;
   if (int rc = ev.create(c)) return rc;
   if (int rc = ev.record(c, 0)) return rc;
-  hipLaunchKernelGGL(abn_tiles_search_kernel, dim3((unsigned)((T + kTilesThreads - 1) / kTilesThreads)), dim3(kTilesThreads), 0,
-                     c->stream, (const uint32_t*)h->start.p, (const long long*)h->tables.run_begin.p,
-                     (const long long*)h->tables.run_end.p, (long long)T, (const int32_t*)dchrom.p, (const long long*)dpos.p,
-                     (const long long*)dpos_end.p, dbegin.p, dend.p);
-  HIPCHK(c, hipGetLastError());
+  if (int rc = tiles_search(h, iv, r.begin.p, r.end.p)) return rc;
   if (int rc = ev.record(c, 1)) return rc;
-  hipLaunchKernelGGL(abn_tiles_fold_kernel, dim3((unsigned)T, (unsigned)n), dim3(kCodesWave), 0, c->stream,
-                     (const uint8_t*)h->code.p, h->code_stride, (const double*)h->level.p, h->n_columns, (long long)T,
-                     (const long long*)dbegin.p, (const long long*)dend.p, dsum.p, dkept.p);
-  HIPCHK(c, hipGetLastError());
+  if (int rc = tiles_fold(h, h->own, T, r)) return rc;
   if (int rc = ev.record(c, 2)) return rc;
-  HIPCHK(c, hipMemcpyAsync(h->begin.data(), dbegin.p, dbegin.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h->end.data(), dend.p, dend.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h->level_sum_kept.data(), dsum.p, dsum.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h->kept.data(), dkept.p, dkept.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = tiles_results(h, T, r)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int k = 0; k < 2; ++k)
     if (int rc = ev.elapsed_ms(c, k, &h->ms[k])) return rc;
@@ -256,8 +315,14 @@ static int tiles_set(abn_tiles* h, std::vector<int32_t>& chromosome, std::vector
   h->tstart.swap(start);
   h->tend.swap(end);
   const int rc = tiles_run(h);
-  if (rc) h->has_tiles = false;
+  h->has_tiles = rc == ABN_OK;
   return rc;
+}
+
+// the refusal of the k-th of a list (`what`: "tile" or "interval") that tiles_interval_valid does not take
+static int tiles_interval_refused(abn_ctx* c, const char* what, int64_t k) {
+  return set_err(c, ABN_ERR_INVALID_ARG,
+                 what + (" " + std::to_string(k)) + ": a chromosome outside 0..257, or a start or end outside [0, 2^32]");
 }
 
 extern "C" int abn_tiles_set_intervals(abn_tiles* h, int64_t n_tiles, const int32_t* chromosome, const int64_t* start,
@@ -267,9 +332,7 @@ extern "C" int abn_tiles_set_intervals(abn_tiles* h, int64_t n_tiles, const int3
   if (n_tiles < 0 || (n_tiles > 0 && (!chromosome || !start || !end))) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
   if (n_tiles > 0x7fffffffLL) return set_err(c, ABN_ERR_INVALID_ARG, "more tiles than INT32_MAX");
   for (int64_t t = 0; t < n_tiles; ++t)
-    if (!tiles_interval_valid(chromosome[t], start[t], end[t]))
-      return set_err(c, ABN_ERR_INVALID_ARG,
-                     "tile " + std::to_string(t) + ": a chromosome outside 0..257, or a start or end outside [0, 2^32]");
+    if (!tiles_interval_valid(chromosome[t], start[t], end[t])) return tiles_interval_refused(c, "tile", t);
   try {
     std::vector<int32_t> tc(chromosome, chromosome + n_tiles);
     std::vector<int64_t> ts(start, start + n_tiles), te(end, end + n_tiles);
@@ -302,52 +365,36 @@ extern "C" int abn_tiles_set_fixed(abn_tiles* h, int64_t size, int64_t step) {
 // wait for the results.  Behind the refusals the handle leaves what it held; a HIP error leaves it without tiles.
 static int tiles_run_pools(abn_tiles* h, PoolSegments& seg, int32_t n_pools) {
   abn_ctx* c = h->ctx;
-  const size_t S = seg.size(), P = (size_t)n_pools, n = (size_t)h->n;
+  const size_t S = seg.size(), P = (size_t)n_pools;
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
-  DevBuf<int32_t> dchrom;
-  DevBuf<long long> dpos, dpos_end, dcol_begin, dcol_end, dseg_off, dseg_first, dbegin, dend, dkept;
-  DevBuf<double> dsum;
-  HIPCHK(c, dchrom.alloc(S));
-  HIPCHK(c, dpos.alloc(S));
-  HIPCHK(c, dpos_end.alloc(S));
+  DevIntervals iv;
+  DevTiles r;  // of the pools
+  DevBuf<long long> dcol_begin, dcol_end, dseg_off, dseg_first;
+  if (int rc = iv.upload(c, seg.chromosome, seg.start, seg.end)) return rc;
   HIPCHK(c, dcol_begin.alloc(S));
   HIPCHK(c, dcol_end.alloc(S));
   HIPCHK(c, dseg_off.alloc(S + 1));
   HIPCHK(c, dseg_first.alloc(P + 1));
-  HIPCHK(c, dbegin.alloc(P));
-  HIPCHK(c, dend.alloc(P));
-  HIPCHK(c, dsum.alloc(n * P));
-  HIPCHK(c, dkept.alloc(n * P));
-  if (S > 0) {
-    HIPCHK(c, hipMemcpyAsync(dchrom.p, seg.chromosome.data(), dchrom.bytes(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dpos.p, seg.start.data(), dpos.bytes(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dpos_end.p, seg.end.data(), dpos_end.bytes(), hipMemcpyHostToDevice, c->stream));
-  }
+  if (int rc = r.alloc(c, (size_t)h->n, P)) return rc;
   HIPCHK(c, hipMemcpyAsync(dseg_first.p, seg.seg_first.data(), dseg_first.bytes(), hipMemcpyHostToDevice, c->stream));
   Events<8> ev;  // 0..2 around search and offsets, in front of the host's read; 3..7 around map, gather, pack and fold
   if (int rc = ev.create(c)) return rc;
   if (int rc = ev.record(c, 0)) return rc;
-  if (S > 0) {
-    hipLaunchKernelGGL(abn_tiles_search_kernel, dim3((unsigned)((S + kTilesThreads - 1) / kTilesThreads)), dim3(kTilesThreads), 0,
-                       c->stream, (const uint32_t*)h->start.p, (const long long*)h->tables.run_begin.p,
-                       (const long long*)h->tables.run_end.p, (long long)S, (const int32_t*)dchrom.p, (const long long*)dpos.p,
-                       (const long long*)dpos_end.p, dcol_begin.p, dcol_end.p);
-    HIPCHK(c, hipGetLastError());
-  }
+  if (int rc = tiles_search(h, iv, dcol_begin.p, dcol_end.p)) return rc;  // the segments' columns
   if (int rc = ev.record(c, 1)) return rc;
   hipLaunchKernelGGL(abn_tiles_pool_offsets_kernel, dim3(1), dim3(kTilesThreads), 0, c->stream, (const long long*)dcol_begin.p,
                      (const long long*)dcol_end.p, (long long)S, dseg_off.p);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(abn_tiles_pool_ranges_kernel, dim3((unsigned)((P + kTilesThreads - 1) / kTilesThreads)), dim3(kTilesThreads), 0,
-                     c->stream, (const long long*)dseg_off.p, (const long long*)dseg_first.p, (long long)P, dbegin.p, dend.p);
+                     c->stream, (const long long*)dseg_off.p, (const long long*)dseg_first.p, (long long)P, r.begin.p, r.end.p);
   HIPCHK(c, hipGetLastError());
   if (int rc = ev.record(c, 2)) return rc;
   long long pooled = 0;
   HIPCHK(c, hipMemcpyAsync(&pooled, dseg_off.p + S, sizeof pooled, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const long long pstride = std::max<long long>(abn_packed_row_stride(pooled), 64), pcode_stride = (pooled + 15) / 16 * 16;
-  if (!tiles_matrix_fits(h->n, pooled, pstride))
+  MatrixShape shape;
+  if (!tiles_matrix_shape(h->n, pooled, &shape))
     return set_err(c, ABN_ERR_INVALID_ARG,
                    "pooled matrix too large for one handle: " + std::to_string(pooled) + " pooled columns");
 
@@ -355,21 +402,11 @@ static int tiles_run_pools(abn_tiles* h, PoolSegments& seg, int32_t n_pools) {
   h->has_tiles = false;
   h->drop_pools();
   h->tchromosome.clear(), h->tstart.clear(), h->tend.clear();
-  DevBuf<uint8_t> pcode;
-  DevBuf<double> plevel;
-  DevBuf<long long> dsite_off, dcode_off;
-  const size_t E = std::max<size_t>((size_t)pooled, 1);
-  HIPCHK(c, pcode.alloc(std::max<size_t>(n * (size_t)pcode_stride, 16)));
-  HIPCHK(c, plevel.alloc(n * E));
-  HIPCHK(c, h->pool_src.alloc(E));
-  HIPCHK(c, h->pool_packed.alloc(n * (size_t)pstride));
-  HIPCHK(c, dsite_off.alloc(n + 1));
-  HIPCHK(c, dcode_off.alloc(n + 1));
-  std::vector<long long> site_off(n + 1), code_off(n + 1);
-  for (size_t s = 0; s <= n; ++s) site_off[s] = (long long)s * pooled, code_off[s] = (long long)s * pcode_stride;
-  HIPCHK(c, hipMemcpyAsync(dsite_off.p, site_off.data(), dsite_off.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dcode_off.p, code_off.data(), dcode_off.bytes(), hipMemcpyHostToDevice, c->stream));
-  const dim3 columns((unsigned)((pooled + kTilesThreads - 1) / kTilesThreads), (unsigned)n);
+  const TileMatrix& own = h->own;
+  TileMatrix& pm = h->pool;
+  if (int rc = pm.alloc(c, h->n, shape)) return rc;
+  HIPCHK(c, h->pool_src.alloc(std::max<size_t>((size_t)pooled, 1)));
+  const dim3 columns((unsigned)((pooled + kTilesThreads - 1) / kTilesThreads), (unsigned)h->n);
   if (int rc = ev.record(c, 3)) return rc;
   if (pooled > 0) {
     hipLaunchKernelGGL(abn_tiles_pool_map_kernel, dim3(columns.x), dim3(kTilesThreads), 0, c->stream,
@@ -378,38 +415,28 @@ static int tiles_run_pools(abn_tiles* h, PoolSegments& seg, int32_t n_pools) {
   }
   if (int rc = ev.record(c, 4)) return rc;
   if (pooled > 0) {
-    hipLaunchKernelGGL(abn_tiles_pool_gather_kernel, columns, dim3(kTilesThreads), 0, c->stream, (const uint8_t*)h->code.p,
-                       h->code_stride, (const double*)h->level.p, h->n_columns, (const long long*)h->pool_src.p, pooled, pcode.p,
-                       pcode_stride, plevel.p);
+    hipLaunchKernelGGL(abn_tiles_pool_gather_kernel, columns, dim3(kTilesThreads), 0, c->stream, (const uint8_t*)own.code.p,
+                       own.code_stride, (const double*)own.level.p, own.columns, (const long long*)h->pool_src.p, pooled,
+                       pm.code.p, pm.code_stride, pm.level.p);
     HIPCHK(c, hipGetLastError());
   }
   if (int rc = ev.record(c, 5)) return rc;
-  if (int rc = codes_pack_dev(c, pcode.p, dcode_off.p, dsite_off.p, h->n, pstride / 4, h->pool_packed.p)) return rc;
+  if (int rc = pm.pack(c, h->n)) return rc;
   if (int rc = ev.record(c, 6)) return rc;
-  hipLaunchKernelGGL(abn_tiles_fold_kernel, dim3((unsigned)P, (unsigned)n), dim3(kCodesWave), 0, c->stream,
-                     (const uint8_t*)pcode.p, pcode_stride, (const double*)plevel.p, pooled, (long long)P,
-                     (const long long*)dbegin.p, (const long long*)dend.p, dsum.p, dkept.p);
-  HIPCHK(c, hipGetLastError());
+  if (int rc = tiles_fold(h, pm, P, r)) return rc;
   if (int rc = ev.record(c, 7)) return rc;
   h->seg_begin.assign(S, 0), h->seg_end.assign(S, 0);
-  h->begin.assign(P, 0), h->end.assign(P, 0);
-  h->level_sum_kept.assign(n * P, 0.0);
-  h->kept.assign(n * P, 0);
-  static_assert(sizeof(long long) == sizeof(int64_t), "positions and columns");
+  static_assert(sizeof(long long) == sizeof(int64_t), "columns");
   if (S > 0) {
     HIPCHK(c, hipMemcpyAsync(h->seg_begin.data(), dcol_begin.p, dcol_begin.bytes(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h->seg_end.data(), dcol_end.p, dcol_end.bytes(), hipMemcpyDeviceToHost, c->stream));
   }
-  HIPCHK(c, hipMemcpyAsync(h->begin.data(), dbegin.p, dbegin.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h->end.data(), dend.p, dend.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h->level_sum_kept.data(), dsum.p, dsum.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h->kept.data(), dkept.p, dkept.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = tiles_results(h, P, r)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  pm.release_staging();  // the scan reads `packed` alone
   const int span[6] = {0, 6, 1, 3, 4, 5};  // search, fold; offsets, map, gather, pack
   for (int k = 0; k < 6; ++k)
     if (int rc = ev.elapsed_ms(c, span[k], k < 2 ? &h->ms[k] : &h->pool_ms[k - 2])) return rc;
-  h->pool_columns = pooled;
-  h->pool_stride = pstride;
   h->segments = std::move(seg);
   h->pooled = h->has_tiles = true;
   return ABN_OK;
@@ -428,9 +455,7 @@ extern "C" int abn_tiles_set_pools(abn_tiles* h, int64_t n_intervals, const int3
       return set_err(c, ABN_ERR_INVALID_ARG,
                      "interval " + std::to_string(k) + ": pool " + std::to_string(pool[k]) + " outside 0.." +
                          std::to_string(n_pools - 1));
-    if (!tiles_interval_valid(chromosome[k], start[k], end[k]))
-      return set_err(c, ABN_ERR_INVALID_ARG,
-                     "interval " + std::to_string(k) + ": a chromosome outside 0..257, or a start or end outside [0, 2^32]");
+    if (!tiles_interval_valid(chromosome[k], start[k], end[k])) return tiles_interval_refused(c, "interval", k);
   }
   try {
     PoolSegments seg;
@@ -463,9 +488,9 @@ extern "C" int abn_tiles_pool_columns(const abn_tiles* h, int64_t* src) {
   if (!h) return ABN_ERR_INVALID_ARG;
   abn_ctx* c = h->ctx;
   if (!h->has_tiles || !h->pooled) return set_err(c, ABN_ERR_INVALID_ARG, "no pools: abn_tiles_set_pools first");
-  if (!src || h->pool_columns == 0) return ABN_OK;
+  if (!src || h->pool.columns == 0) return ABN_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(src, h->pool_src.p, (size_t)h->pool_columns * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(src, h->pool_src.p, (size_t)h->pool.columns * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ABN_OK;
 }
@@ -516,12 +541,10 @@ extern "C" int abn_tiles_pairwise(abn_tiles* h, uint64_t* diff, uint64_t* both, 
   if (npairs == 0 || T == 0) return ABN_OK;
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
+  const TileMatrix& m = h->pooled ? h->pool : h->own;
   return pairwise_to_host(c, T * npairs, diff, both, dvalue, [&](auto* dd, auto* db, auto* dv) {
-    if (h->pooled)
-      return pairwise_windows_packed_dev(c, h->pool_packed.p, h->n, h->pool_columns, h->pool_stride, h->begin.data(),
-                                         h->end.data(), (int32_t)T, dd, db, dv, nullptr);
-    return pairwise_windows_packed_dev(c, h->packed.p, h->n, h->n_columns, h->stride, h->begin.data(), h->end.data(), (int32_t)T,
-                                       dd, db, dv, nullptr);
+    return pairwise_windows_packed_dev(c, m.packed.p, h->n, m.columns, m.stride, h->begin.data(), h->end.data(), (int32_t)T, dd,
+                                       db, dv, nullptr);
   });
 }
 

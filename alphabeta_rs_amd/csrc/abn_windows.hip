@@ -3,7 +3,7 @@
 // front of the gene choice of abn_windows_create_parsed / _aligned / _union — the resident handles' refusals, the merge of
 // their parse results (abn_sites.hip's launches), and between that merge and the gene choice the common-site step
 // (abn_sites_common.hip) or the union step (abn_sites_union.hip) — is abn_resident.hip's, shared with abn_codes.hip and
-// abn_tiles.hip.
+// abn_tiles.hip; so is the handle's shell (handle_create, handle_destroy, handle_packed), abn_host.hpp's.
 #include "abn_host.hpp"
 #include "abn_windows.hpp"
 
@@ -290,22 +290,12 @@ static int windows_check(abn_ctx* c, const abn_windows_params* p, int32_t n_samp
 template <class Build>
 static int windows_make(abn_ctx* c, const abn_windows_params* p, int32_t n_samples, const int64_t* site_offset,
                         abn_windows** out, Build build) {
-  HIPCHK(c, hipSetDevice(c->device));
-  PoolScope pool_scope(c);
-  std::unique_ptr<abn_windows> h(new (std::nothrow) abn_windows);
-  if (!h) return set_err(c, ABN_ERR_HIP, "out of host memory");
-  h->ctx = c;
-  h->n = n_samples;
-  h->W = p->n_upstream + p->n_gene + p->n_downstream;
-  try {
+  return handle_create(c, n_samples, out, [&](abn_windows* h) {
+    h->W = p->n_upstream + p->n_gene + p->n_downstream;
     h->report.before.resize((size_t)n_samples);
     for (int s = 0; s < n_samples; ++s) h->report.before[(size_t)s] = site_offset[s + 1] - site_offset[s];
-    if (int rc = build(h.get())) return rc;
-  } catch (const std::bad_alloc&) {
-    return set_err(c, ABN_ERR_HIP, "out of host memory");
-  }
-  *out = h.release();
-  return ABN_OK;
+    return build(h);
+  });
 }
 
 extern "C" int abn_windows_create_sites(abn_ctx* c, const abn_windows_params* p, abn_genes* genes, const abn_gene_rule* rule,
@@ -382,12 +372,7 @@ extern "C" int abn_windows_create(abn_ctx* c, const abn_windows_params* p, int32
   });
 }
 
-extern "C" int abn_windows_destroy(abn_windows* h) {
-  if (!h) return ABN_ERR_INVALID_ARG;
-  (void)hipSetDevice(h->ctx->device);
-  delete h;
-  return ABN_OK;
-}
+extern "C" int abn_windows_destroy(abn_windows* h) { return handle_destroy(h); }
 
 extern "C" int abn_windows_info(const abn_windows* h, int32_t* n_windows, int64_t* row_stride, int64_t* n_sites) {
   if (!h) return ABN_ERR_INVALID_ARG;
@@ -436,15 +421,7 @@ extern "C" int abn_windows_packed_device_ptr(abn_windows* h, void** dev_ptr) {
   return ABN_OK;
 }
 
-extern "C" int abn_windows_packed(abn_windows* h, uint8_t* host_out) {
-  if (!h) return ABN_ERR_INVALID_ARG;
-  abn_ctx* c = h->ctx;
-  if (!host_out) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(host_out, h->packed.p, h->packed.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ABN_OK;
-}
+extern "C" int abn_windows_packed(abn_windows* h, uint8_t* host_out) { return handle_packed(h, host_out); }
 
 extern "C" int abn_windows_pairwise(abn_windows* h, uint64_t* diff, uint64_t* both, double* dvalue) {
   if (!h) return ABN_ERR_INVALID_ARG;

@@ -3,8 +3,9 @@
 five chromosomes of --span (20 000 000) bp, the later samples' statuses drifting from the first's:
 
   kernels  per tile size (100 kb; 2 kb for many short jobs): the HIP-event times of the tile search and the tile fold
-           (Tiles.kernel_ms after set_fixed) and of the windows-packed scan over the tiles' column ranges
-           (pairwise_divergence_windows_packed_dev on the same matrix), --warmup runs dropped, the median of --reps;
+           (Tiles.kernel_ms after set_fixed), the host clock around set_fixed, and the HIP-event time of the windows-packed
+           scan over the tiles' column ranges (pairwise_divergence_windows_packed_dev on the same matrix), --warmup runs
+           dropped, the median of --reps;
   baseline the existing whole-sample fold on the same sites, abn_codes_fold_kernel (Codes.kernel_ms()[3]), alternating with
            the tile folds in one process: n chains where the tile fold has n x T;
   wall     `metaprofile_alphabeta --tiles 100000` next to one `alphabeta --sites device` run on the same files (host
@@ -101,21 +102,24 @@ def main():
             count, _, kept = tiles.stats()
             assert kept.sum(axis=1).tolist() == whole_kept.tolist() and count.sum() == tiles.n_columns
             begin, end = tiles.layout()
-            search, fold, scan = [], [], []
+            search, fold, scan, clock = [], [], [], []
             for rep in range(args.warmup + args.reps):
                 again = A.Codes.from_parsed(ctx, sites, posterior_max_filter=0.99)      # the whole-sample fold, alternating
                 whole = again.kernel_ms()[3]
                 again.close()
+                t0 = time.perf_counter()
                 tiles.set_fixed(size)
+                t1 = time.perf_counter()
                 ms = tiles.kernel_ms()
                 scan_ms = ctx.pairwise_divergence_windows_packed_dev(codes.packed_device_ptr(), args.samples, codes.n_sites,
                                                                      codes.row_stride, begin, end)
                 if rep >= args.warmup:
                     folds["whole_sample"].append(whole)
-                    search.append(ms[0]), fold.append(ms[1]), scan.append(scan_ms)
+                    search.append(ms[0]), fold.append(ms[1]), scan.append(scan_ms), clock.append(t1 - t0)
             result["tiles"][str(size)] = {"n_tiles": int(len(begin)), "fold_jobs": int(len(begin)) * args.samples,
                                           "columns_per_tile_median": float(np.median(count)), "columns_per_tile_max": int(count.max()),
-                                          "search_ms": stats(search), "fold_ms": stats(fold), "scan_ms": stats(scan)}
+                                          "search_ms": stats(search), "fold_ms": stats(fold), "scan_ms": stats(scan),
+                                          "set_fixed_s": stats(clock)}
             print(json.dumps({size: result["tiles"][str(size)]}), file=sys.stderr, flush=True)
         result["whole_sample_fold_ms"] = stats(folds["whole_sample"])
         tiles.close()

@@ -2,7 +2,8 @@
 tests/_tile_pools_model.py: every pool's segments, source columns and pooled range, its per-sample rc_meth_lvl folds bit for
 bit, its pairwise integers against the model and against the sums over its segments of what set_intervals gives; a pool
 against a methylome cut down to the pool's lines; one interval per pool against the tiles of the same list; the switches
-between pools and tiles; the refusals; and `metaprofile_alphabeta --regions F --pool` against the directory path on a tree
+between pools and tiles (a refused tiles call and an empty interval list on a pooled handle among them); pools on handles
+without a column and of one sample; the refusals; and `metaprofile_alphabeta --regions F --pool` against the directory path on a tree
 whose k-th directory holds pool k's lines.
 
 One refusal of abn_tiles_set_pools is not reached here: a pooled matrix beyond a handle's limits needs more than 256 x
@@ -17,6 +18,7 @@ import pytest
 import _tile_pools_model as PM
 import _tiles_model as T
 import _windows_model as M
+from _parse_model import HEADER
 from test_tiles_gpu import (ALIGNS, FLT, INVALID, N, NAMES, NAN_SITE, L, bits, graph_files, handles, inputs, resident,  # noqa: F401
                             run_cli, tool_methylomes)
 
@@ -265,6 +267,84 @@ def test_refusals(abn, gpu_ctx, inputs, handles):
         assert lib.abn_tiles_pool_kernel_ms(t._h, None) == INVALID
     finally:
         t.close()
+
+
+def test_a_refused_tiles_call_leaves_a_pooled_handle_as_it_was(abn, inputs, handles):
+    rows, values, keeps = inputs
+    t = handles["none"]["tiles"]
+    (ic, ilo, ihi, ip), names, _ = PM.pool_list(rows)
+    t.set_pools(ic, ilo, ihi, ip, len(names))
+    info, before = t.info(), everything(t)
+    refused = ((lambda: t.set_intervals([258], [0], [5]), "tile 0:"), (lambda: t.set_fixed(0), "tile size"),
+               (lambda: t.set_fixed(1), "INT32_MAX"))                            # (a site at 4294967295: 2^32 tiles of one bp)
+    for call, words in refused:
+        with pytest.raises(abn.AbnError) as e:
+            call()
+        assert e.value.status == INVALID and words in str(e.value)
+        assert t.info() == info and info["n_tiles"] == len(names)
+        assert_same(everything(t), before)
+
+
+def test_an_empty_interval_list_drops_the_pools(abn, gpu_ctx, inputs, handles):
+    rows, values, keeps = inputs
+    h = handles["position"]
+    (ic, ilo, ihi, ip), names, _ = PM.pool_list(rows)
+    used = h["tiles"]
+    used.set_pools(ic, ilo, ihi, ip, len(names))
+    used.set_intervals([], [], [])                                             # no tile, and the handle's own matrix again
+    assert used.info()["n_tiles"] == 0
+    for getter in (used.pool_segments, used.pool_columns):
+        with pytest.raises(abn.AbnError) as e:
+            getter()
+        assert e.value.status == INVALID and "abn_tiles_set_pools" in str(e.value)
+    assert np.all(used.pool_kernel_ms() == 0) and np.all(used.kernel_ms() == 0)
+    fresh = abn.Tiles.from_parsed(gpu_ctx, h["sites"], posterior_max_filter=FLT, align="position")
+    try:
+        fresh.set_pools(ic, ilo, ihi, ip, len(names))
+        used.set_pools(ic, ilo, ihi, ip, len(names))
+        assert used.info() == fresh.info() and used.info()["n_tiles"] == len(names)
+        assert_same(everything(used), everything(fresh))
+    finally:
+        fresh.close()
+
+
+def test_pools_on_degenerate_handles(abn, gpu_ctx, L, inputs, handles):
+    rows, values, keeps = inputs
+    # two header-only methylomes: no column, no run — every pool is empty
+    empties = [resident(gpu_ctx, L, HEADER.encode()) for _ in range(2)]
+    none = abn.Tiles.from_parsed(gpu_ctx, empties, posterior_max_filter=FLT)
+    try:
+        assert none.info()["n_columns"] == 0 and none.n_runs == 0
+        none.set_pools([1, 2], [0, 5], [T.POS_END, 9], [0, 1], 2)
+        assert none.info()["n_tiles"] == 2 and none.layout()[0].tolist() == none.layout()[1].tolist() == [0, 0]
+        count, lsk, kept = none.stats()
+        assert count.tolist() == [0, 0] and kept.tolist() == [[0, 0]] * 2 and lsk.tolist() == [[0.0, 0.0]] * 2
+        dval = none.pairwise()[2]
+        assert dval.shape == (2, 1) and np.isnan(dval).all()
+        assert all(a.shape == (0,) for a in none.pool_segments()) and none.pool_columns().shape == (0,)
+    finally:
+        none.close()
+        for s in empties:
+            s.close()
+    # one sample: the stats work, the pairwise call writes nothing
+    (ic, ilo, ihi, ip), names, _ = PM.pool_list(rows)
+    n_pools = len(names)
+    single = abn.Tiles.from_parsed(gpu_ctx, handles["none"]["sites"][:1], posterior_max_filter=FLT)
+    try:
+        single.set_pools(ic, ilo, ihi, ip, n_pools)
+        count, lsk, kept = single.stats()
+        assert count.shape == (n_pools,) and lsk.shape == kept.shape == (1, n_pools)
+        want = handles["none"]["tiles"]
+        want.set_pools(ic, ilo, ihi, ip, n_pools)
+        assert count.tobytes() == want.stats()[0].tobytes() and kept[0].tobytes() == want.stats()[2][0].tobytes()
+        filled = [np.full(n_pools, 7, dtype=np.uint64), np.full(n_pools, 7, dtype=np.uint64), np.full(n_pools, 7.0)]
+        u64p = C.POINTER(C.c_uint64)
+        assert gpu_ctx._L.abn_tiles_pairwise(single._h, filled[0].ctypes.data_as(u64p), filled[1].ctypes.data_as(u64p),
+                                             filled[2].ctypes.data_as(C.POINTER(C.c_double))) == 0
+        assert all((a == 7).all() for a in filled)
+        assert all(a.shape == (n_pools, 0) for a in single.pairwise())
+    finally:
+        single.close()
 
 
 # ---------------------------------------------------------------- the tool
