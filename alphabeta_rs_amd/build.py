@@ -14,7 +14,8 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libabneutral_hip.so"
 # the one list of the library's sources: scripts/flag_variants.py and scripts/stamps.py build from it too
-SOURCES = [CSRC / "abn_api.hip", CSRC / "abn_pairwise.hip", CSRC / "abn_windows.hip", CSRC / "abn_analyze.hip",
+SOURCES = [CSRC / "abn_api.hip", CSRC / "abn_context.hip", CSRC / "abn_plan.hip",  # the fit path: kernels and launchers, host-only, the plan
+           CSRC / "abn_pairwise.hip", CSRC / "abn_windows.hip", CSRC / "abn_analyze.hip",
            CSRC / "abn_multi.hip", CSRC / "abn_sites.hip", CSRC / "abn_genes.hip", CSRC / "abn_codes.hip",
            CSRC / "abn_sites_common.hip", CSRC / "abn_sites_union.hip", CSRC / "abn_tiles.hip",
            CSRC / "abn_resident.hip",  # host-only too: what the builders from resident parse results share

@@ -1,4 +1,5 @@
-// Selection (ab_neutral::run :83-135), cost batch, bootstrap rows, materialised observations, bootstrap indices.
+// Selection (ab_neutral::run :83-135), a step's clears, cost batch, bootstrap rows, bootstrap indices: the kernels
+// abn_api.hip launches beside the fit kernels (those of the plan alone: abn_plan_kernels.hpp).
 #pragma once
 #include "abn_common.hpp"
 #include "abn_prepare.hpp"
@@ -9,24 +10,8 @@ namespace abn {
 // Selection kernels: src/ab_neutral.rs:83-135.  The pure LSE of each of the
 // S fitted models is summed SERIALLY in row order (the reference's `.sum::<f64>()`), the stable
 // arg-min taken (lowest start index on ties; NaN never wins), then predicted divergence and residuals
-// of the winner written for phase B.  LDS: chain scratch (9*TP + K doubles) + kSelChunk terms.
+// of the winner written for phase B.  LDS: chain scratch (9*TP + K doubles) + kSelChunk terms.  SelectArgs (abn_common.hpp).
 // ------------------------------------------------------------------------------------------------
-struct SelectArgs {
-  const uint32_t* tri;
-  const uint16_t* tid;
-  int N, K, T, TP;
-  const double* p_uu;   // [W]
-  const double* D;      // [W*N]
-  const double* models; // [W*S*4] fitted start models
-  const FitInfoDev* info;  // [W*S]
-  int W, S;
-  double* lse;          // [W*S]
-  double* model;        // [W*4]
-  double* pred;         // [W*N]
-  double* resid;        // [W*N]
-  int32_t* best_start;  // [W]  (-1: no finite fit)
-};
-
 // P1-P3 of one model for the whole wavefront: power table and dt[K] into LDS
 __device__ __forceinline__ void select_fill_dt(const SelectArgs& a, const double* x, double p_uu0, double* pw,
                                                double* dtab, int lane) {
@@ -118,26 +103,6 @@ __global__ __launch_bounds__(kWave) void abn_select_kernel(const SelectArgs a) {
     a.resid[wN + i] = a.D[wN + i] - p;           // src/ab_neutral.rs:131-135
   }
   if (lane < 4) a.model[4 * w + lane] = x[lane];
-}
-
-// Early bootstraps (abn_plan_run): the selection ran twice through the two kernels above — over the starts finished at
-// the quorum (into the plan's buffers, which phase B reads) and, beside phase B, over all of them (into scratch buffers).
-// `miss` is raised when the two chose different starts: the early phase B then stops and is redone.
-__global__ __launch_bounds__(kWave) void abn_early_compare_kernel(const int32_t* early, const int32_t* all, int W, unsigned* miss) {
-  for (int w = threadIdx.x; w < W; w += kWave)
-    if (early[w] != all[w]) __hip_atomic_store(miss, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// ... and the selection over all starts becomes the plan's (the same bytes when the two agree)
-__global__ __launch_bounds__(256) void abn_early_adopt_kernel(const SelectArgs from, const SelectArgs to) {
-  const long long rows = (long long)to.W * to.N, n = rows > 4LL * to.W ? rows : 4LL * to.W;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    if (i < rows) {
-      to.pred[i] = from.pred[i];
-      to.resid[i] = from.resid[i];
-    }
-    if (i < 4LL * to.W) to.model[i] = from.model[i];
-    if (i < to.W) to.best_start[i] = from.best_start[i];
-  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -289,24 +254,6 @@ __global__ __launch_bounds__(256) void abn_rows_kernel(const double* best, long 
     ro[4] = est_mm(al, be);
     ro[5] = est_um(al, be);
     ro[6] = p_uu_est(al, be);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Residual bootstrap observations, materialised once per fit for the stream mode (src/boot_model.rs:50-57):
-// dstar[(w*B + b)*N + i] = pred[w*N + i] + resid[w*N + idx[(w*B + b)*N + i]].  The index buffer is read
-// once, coalesced; the evaluations then stream dstar (8 B per row) instead of re-gathering through the index
-// row (4 B per row + an 8-byte random gather that, for tables beyond LDS, is bound by L2->L1 sector traffic).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void abn_make_dstar_kernel(double* dstar, const double* pred, const double* resid,
-                                                             const uint32_t* idx, int N, long long rows_per_window,
-                                                             long long total) {
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
-       t += (long long)gridDim.x * blockDim.x) {
-    const long long w = t / rows_per_window;
-    const int i = (int)(t % N);
-    const size_t wN = (size_t)w * (size_t)N;
-    dstar[t] = pred[wN + i] + resid[wN + idx[t]];
   }
 }
 

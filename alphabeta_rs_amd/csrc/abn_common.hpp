@@ -2,8 +2,9 @@
 // the scalar pieces of one cost evaluation (genmatrix, power table, one triple), simplex bookkeeping, reductions.
 // Kernels: abn_fit_kernel.hpp (plain / stream / two-pass / strict), abn_fit_refill.hpp (persistent, time-sliced),
 // abn_fit_spec.hpp (four wavefronts per chain), abn_fit_sweep.hpp (streamed, one pass over the rows per iteration),
-// abn_aux_kernels.hpp (selection, cost batch, rows, observations, indices), abn_pairwise_mx.hpp (pedigree
-// construction).  abn_device.hpp includes them all.  Compiled with -ffp-contract=off: every fused multiply-add below is
+// abn_aux_kernels.hpp (selection, clears, cost batch, rows, indices), abn_plan_kernels.hpp (the plan's own: observations,
+// early bootstraps), abn_pairwise_mx.hpp (pedigree construction).  abn_device.hpp includes the fit path's except the plan's,
+// which abn_plan.hip includes.  Compiled with -ffp-contract=off: every fused multiply-add below is
 // explicit and corresponds to one the reference executes.
 //
 // Mapping: a Nelder-Mead chain (one fit) is owned by a group of G lanes of one
@@ -99,7 +100,7 @@ struct FitArgs {
   // chains: W windows x C chains
   int W, C;
   int max_iters;
-  // Two-pass execution of long chains (abn_api.hip: phase A with many chains).  Pass 1: iter_cap > 0 — a chain
+  // Two-pass execution of long chains (abn_plan.hip: phase A with many chains).  Pass 1: iter_cap > 0 — a chain
   // that is still running after iter_cap iterations stores its Nelder-Mead state (kStateDoubles doubles, abn_constants.hpp) and appends its
   // index to susp_list.  Pass 2: resume != 0 — block b, group g continues chain susp_list[b*NG+g] (for
   // b*NG+g < *susp_count) from the stored state to the end.  Same arithmetic either way: results are
@@ -177,6 +178,24 @@ struct FitArgs {
   // abn_sweep_kernel only (nullable): += the chain's passes over its rows, once at its end — 5 for Solver::init, one per
   // executed iteration, 4 per shrink
   unsigned long long* passes;
+};
+
+// The selection over the fitted starts (abn_aux_kernels.hpp: abn_select_lse_kernel, abn_select_kernel), which the plan
+// fills too (abn_plan.hip)
+struct SelectArgs {
+  const uint32_t* tri;
+  const uint16_t* tid;
+  int N, K, T, TP;
+  const double* p_uu;   // [W]
+  const double* D;      // [W*N]
+  const double* models; // [W*S*4] fitted start models
+  const FitInfoDev* info;  // [W*S]
+  int W, S;
+  double* lse;          // [W*S]
+  double* model;        // [W*4]
+  double* pred;         // [W*N]
+  double* resid;        // [W*N]
+  int32_t* best_start;  // [W]  (-1: no finite fit)
 };
 
 // In-kernel stamps (MI355X guide §7): only in a separate diagnostic build, never in the shipped library.

@@ -44,7 +44,7 @@ static_assert(kStateSimplex == 0 && kStateCosts == kStateSimplex + 5 * 4 && kSta
               "the regions of the parked state tile 0 .. kStateDoubles - 1 exactly");
 static_assert(2 * (kStateDoubles - kStateIterEvals) == kStateIntZero + 1, "the int view covers words 30 and 31");
 
-// Status words of a persistent launch (FitArgs::slice_status; the plan holds kSliceWords per phase, abn_api.hip's
+// Status words of a persistent launch (FitArgs::slice_status; the plan holds kSliceWords per phase, abn_plan.hip's
 // verify_persistent reads them at the next synchronisation):
 constexpr int kSliceError = 0;      // |= kSliceErrLostEntry (abn_common.hpp): a claimed FIFO entry never appeared
 constexpr int kSliceFinished = 1;   // += fits finished (results written), the tail's resume launch included
@@ -55,7 +55,7 @@ constexpr int kSliceWords = 4;
 constexpr int kPhaseSkipped = 0;    // evaluations not executed (FitArgs::skipped, the fixed-point skip)
 constexpr int kPhaseQueue = 1;      // its low 32 bits: the chain queue of the persistent kernel (FitArgs::queue)
 constexpr int kPhaseWords = 2;
-// Early bootstraps (abn_plan_run on a quorum of starts, abn_api.hip): the plan's slots of those words are phase A, phase B
+// Early bootstraps (abn_plan_run on a quorum of starts, abn_plan.hip): the plan's slots of those words are phase A, phase B
 // (the early launch) and the guarded redo of phase B, and behind them, zeroed by the same clear, kEarlyWords 32-bit words:
 constexpr int kPhaseSlots = 3, kSlotRedo = 2;
 constexpr int kEarlyCount = 0;      // += starts finished in pass 1 of phase A (FitArgs::quorum_words: count, then flag)

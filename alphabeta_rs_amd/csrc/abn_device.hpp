@@ -1,5 +1,6 @@
-// The device code of the fit path (abn_api.hip includes this; the pairwise scans of abn_pairwise.hip, the window
-// placement of abn_windows.hip and the analysis of abn_analyze.hip have headers of their own).
+// The device code of the fit path (abn_api.hip includes this, and it alone; the three kernels only the plan launches are
+// abn_plan_kernels.hpp's, for abn_plan.hip; the pairwise scans of abn_pairwise.hip, the window placement of abn_windows.hip
+// and the analysis of abn_analyze.hip have headers of their own).
 #pragma once
 #include "abn_common.hpp"
 #include "abn_fit_kernel.hpp"

@@ -1,6 +1,7 @@
-// Host-side infrastructure shared by the translation units of libabneutral_hip.so (abn_api.hip, abn_pairwise.hip,
-// abn_windows.hip, abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip,
-// abn_tiles.hip, abn_resident.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
+// Host-side infrastructure shared by the translation units of libabneutral_hip.so (the fit path's abn_api.hip,
+// abn_context.hip and abn_plan.hip, which share abn_fit_host.hpp on top of this; abn_pairwise.hip, abn_windows.hip,
+// abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip, abn_tiles.hip,
+// abn_resident.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
 // events of a call, the shell of the windows, codes and tiles handles (created, destroyed, their packed matrix read), and
 // what the consumers of resident methylomes share (abn_resident.hip).  Not part of the C-ABI (include/abneutral.h is).
 #pragma once
@@ -256,7 +257,7 @@ int handle_packed(H* h, uint8_t* host_out) {
 }
 
 namespace abn {
-// abn_analyze.hip, for abn_plan_analyze (abn_api.hip): the analysis (abn_analyze.hpp) of a device-resident table
+// abn_analyze.hip, for abn_plan_analyze (abn_plan.hip): the analysis (abn_analyze.hpp) of a device-resident table
 // raw[W x B x 7] on the context's stream, results to the host; returns after completion, ABN_ERR_NO_FINITE_FIT as
 // abn_analyze_batch.
 int analyze_device_table(abn_ctx* c, const double* draw, int32_t W, int64_t B, double* out, int32_t* first_bad);

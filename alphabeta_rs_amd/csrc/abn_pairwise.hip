@@ -1,7 +1,7 @@
 // Pedigree construction: the four pairwise divergence scans abn_pairwise_divergence* — byte codes
 // or 2-bit packed codes, the whole matrix or many windows of it — each with a host entry and a _dev entry.
 // The scan kernels are in abn_pairwise_mx.hpp, abn_pairwise_packed.hpp, abn_pairwise_windows.hpp and
-// abn_pairwise_windows_packed.hpp; the fit path (abn_api.hip) does not include them.
+// abn_pairwise_windows_packed.hpp; the fit path (abn_api.hip, abn_context.hip, abn_plan.hip) does not include them.
 #include "abn_host.hpp"
 #include "abn_pairwise_mx.hpp"
 #include "abn_pairwise_packed.hpp"

@@ -131,7 +131,7 @@ inline PrepList prep_launch(int slot, bool status, bool fifo, unsigned slice_cap
 }
 
 // What a persistent launch may find clear and use without a clear of its own: the status words per slot, the FIFO per
-// region, the two-pass list's counter.  A launch marks what it uses as dirty (abn_api.hip: launch_fit, launch_phase).
+// region, the two-pass list's counter.  A launch marks what it uses as dirty (abn_api.hip: launch_fit; abn_plan.hip: launch_phase).
 constexpr int kFifoRegionsMax = fifo_regions(true);
 struct PrepClean {
   bool status[kPhaseSlots] = {};

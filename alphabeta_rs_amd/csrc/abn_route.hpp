@@ -1,7 +1,7 @@
 // The launch policy of the fit path, and nothing else: which kernel instantiation runs, with which grid, LDS and reduction
 // tree, for a pedigree, its resolved options and a number of chains.  Pure host arithmetic on plain integers — no context,
-// no launch arguments, no HIP, no allocation — so that the same code decides in libabneutral_hip.so (abn_api.hip executes
-// what it returns) and answers on a machine without a GPU (host/host_capi.cpp: abh_route_*).
+// no launch arguments, no HIP, no allocation — so that the same code decides in libabneutral_hip.so (abn_api.hip's launchers
+// execute what it returns, for the one-shot entries and for abn_plan.hip) and answers on a machine without a GPU (host/host_capi.cpp: abh_route_*).
 //
 // Three levels, each one function returning a plain struct:
 //   route_pedigree   N, K, T, lanes_per_chain, strict order  -> lanes, tree, resident or streamed, what the pedigree admits

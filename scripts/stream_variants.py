@@ -41,7 +41,8 @@ def main():
         lib = OUT / f"libabn_sv_{nb}_{w}.so"
         subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
                         "-fPIC", "-shared", f"-DABN_STREAM_BLOCKS={nb}", f"-DABN_STREAM_WAVES={w}", "-o", str(lib),
-                        str(ROOT / "alphabeta_rs_amd/csrc/abn_api.hip")], check=True)
+                        *(str(ROOT / "alphabeta_rs_amd/csrc" / f) for f in ("abn_api.hip", "abn_context.hip", "abn_plan.hip"))],
+                       check=True)
         r = subprocess.run([sys.executable, __file__, "--worker", str(lib), str(boots)], capture_output=True, text=True)
         print(f"blocks={nb} waves={w} boots={boots}: {r.stdout.strip()} {r.stderr.strip()[-300:]}", flush=True)
 

@@ -1,6 +1,6 @@
 """The fit-path kernel matrix: every compiled instantiation of abn_fit_kernel, abn_fit_refill_kernel, abn_fit_spec_kernel
-and abn_cost_kernel (abn_api.hip), each either in MATRIX — one deterministic case whose inputs route to it — or in
-UNREACHABLE with the host condition that keeps it from launching.
+and abn_cost_kernel (the kernel table of abn_api.hip), each either in MATRIX — one deterministic case whose inputs route
+to it — or in UNREACHABLE with the host condition that keeps it from launching.
 
 Plain data and host arithmetic, no device: tests/test_kernel_matrix_census.py checks on the CPU that the two tables
 partition what the gfx950 assembly holds and that every case's pedigree has the tree the case expects;

@@ -19,7 +19,7 @@ run in any order).  Properties, checked in every reachable state:
   * a ticket never runs past the FIFO's capacity (the park verdict's slack covers the tickets in flight);
   * no chain is ever taken up twice;
   * when all wavefronts have left, every chain is finished or on the tail list, exactly once, the counters add up to
-    what `verify_persistent` (csrc/abn_api.hip) expects, no credit and no entry is left.
+    what `verify_persistent` (csrc/abn_plan.hip) expects, no credit and no entry is left.
 The protocol WITHOUT the look-again of round 4 must fail the last property (the model finds the stranded chain)."""
 import pytest
 
