@@ -74,6 +74,7 @@ EXPORTED_SYMBOLS = [
     "abn_tiles_set_fixed", "abn_tiles_intervals", "abn_tiles_layout", "abn_tiles_stats", "abn_tiles_pairwise",
     "abn_tiles_kernel_ms",
     "abn_tiles_set_pools", "abn_tiles_pool_segments", "abn_tiles_pool_columns", "abn_tiles_pool_kernel_ms",
+    "abn_sites_context", "abn_sites_insert_ctx", "abn_sites_split", "abn_sites_split_ms",
 ]
 
 
@@ -118,8 +119,21 @@ class SitesParams(C.Structure):
     _fields_ = [
         ("slab_bytes", C.c_int64),
         ("skip_lines", C.c_int32),
-        ("reserved", C.c_int32),
+        ("contexts", C.c_int32),
     ]
+
+
+CONTEXTS = ("CG", "CHG", "CHH")  # a site's context code indexes it; code 3: a row without a context
+
+
+def _context_mask(contexts) -> int:
+    """("CG", "CHH") or "CG,CHH" or the mask itself -> abn_sites_params.contexts (1 CG, 2 CHG, 4 CHH)"""
+    if isinstance(contexts, (int, np.integer)):
+        return int(contexts)
+    names = contexts.split(",") if isinstance(contexts, str) else list(contexts)
+    if not names or len(set(names)) != len(names) or any(n not in CONTEXTS for n in names):
+        raise ValueError(f"contexts expects distinct names of {CONTEXTS}, not {contexts!r}")
+    return sum(1 << CONTEXTS.index(n) for n in names)
 
 
 class AbnError(RuntimeError):
@@ -213,6 +227,10 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_sites_parse_dev.argtypes = [vp, C.c_char_p, C.c_int64, C.POINTER(SitesParams), C.POINTER(vp)]
     L.abn_sites_flagged.argtypes = [vp, i64p, i64p]
     L.abn_sites_insert.argtypes = [vp, C.c_int64, i64p, C.POINTER(C.c_int32), u32p, u32p, u8p, dp, u8p, dp]
+    L.abn_sites_insert_ctx.argtypes = [*L.abn_sites_insert.argtypes, u8p]
+    L.abn_sites_context.argtypes = [vp, C.POINTER(C.c_int32), u8p]
+    L.abn_sites_split.argtypes = [vp, C.POINTER(vp)]
+    L.abn_sites_split_ms.argtypes = [vp, dp]
     L.abn_windows_create_parsed.argtypes = [vp, C.POINTER(WindowsParams), vp, C.POINTER(GeneRule), C.c_double, C.c_int32,
                                             C.POINTER(vp), C.POINTER(vp)]
     L.abn_windows_merge_ms.argtypes = [vp, dp]
@@ -678,14 +696,17 @@ class Context:
             self._check(rc)
         return ms.value
 
-    def parse_sites(self, text: bytes, *, skip_lines: int = 1, slab_bytes: int = 0):
+    def parse_sites(self, text: bytes, *, skip_lines: int = 1, slab_bytes: int = 0, contexts=("CG",)):
         """MethylationSite::from_methylome_file_line (src/methylation_site.rs:146-362) for every line of a methylome
         file's text from line skip_lines on, on the device.  Returns (sites, deferred): sites = a dict of arrays over the
         accepted sites in file order (line, chromosome, start, end, strand, posteriormax, status, status_flag, meth_lvl;
         n_lines and kernel_ms beside them); deferred = a dict of line, offset, length of the lines the device leaves to
-        the host's parser (an f64 field it cannot be certain of, a line beyond its staging limit)."""
+        the host's parser (an f64 field it cannot be certain of, a line beyond its staging limit).  contexts: the
+        methylation contexts whose lines are sites (names of CONTEXTS, or the mask); with any other value than CG alone
+        sites gains `context`, every site's code (0 CG, 1 CHG, 2 CHH, 3 a row without one)."""
         text = bytes(text)
-        p = SitesParams(slab_bytes, skip_lines, 0)
+        mask = _context_mask(contexts)
+        p = SitesParams(slab_bytes, skip_lines, 0 if mask == 1 else mask)
         h = C.c_void_p()
         self._check(self._L.abn_sites_parse(self._h, text, len(text), C.byref(p), C.byref(h)))
         s = Sites(self, h)
@@ -693,15 +714,19 @@ class Context:
             sites, deferred = s.fetch(), s.deferred()
             sites.update(s.info())
             del sites["n_sites"], sites["n_deferred"]
+            if mask != 1:
+                sites["context"] = s.contexts()
             return sites, deferred
         finally:
             s.close()
 
-    def parse_sites_resident(self, text: bytes, *, skip_lines: int = 1, slab_bytes: int = 0) -> "Sites":
+    def parse_sites_resident(self, text: bytes, *, skip_lines: int = 1, slab_bytes: int = 0, contexts=("CG",)) -> "Sites":
         """parse_sites with the records left on the device (abn_sites_parse_dev): a Sites handle for Windows.from_parsed.
-        Its deferred() lines are for the caller's parser; those it accepts go back in with insert(), once."""
+        Its deferred() lines are for the caller's parser; those it accepts go back in with insert(), once.  A handle of
+        several contexts gives one handle per context with split()."""
         text = bytes(text)
-        p = SitesParams(slab_bytes, skip_lines, 0)
+        mask = _context_mask(contexts)
+        p = SitesParams(slab_bytes, skip_lines, 0 if mask == 1 else mask)
         h = C.c_void_p()
         self._check(self._L.abn_sites_parse_dev(self._h, text, len(text), C.byref(p), C.byref(h)))
         return Sites(self, h)
@@ -987,15 +1012,46 @@ class Sites(_Handle):
         self.ctx._check(self._L.abn_sites_flagged(self._h, None, out.ctypes.data_as(C.POINTER(C.c_int64))))
         return out
 
-    def insert(self, line, chromosome, start, end, strand, posteriormax, status, meth_lvl):
-        """the deferred lines the host's parser accepted, ascending by line; once per handle (abn_sites_insert)"""
+    def insert(self, line, chromosome, start, end, strand, posteriormax, status, meth_lvl, context=None):
+        """the deferred lines the host's parser accepted, ascending by line; once per handle (abn_sites_insert).  context:
+        every record's code (abn_sites_insert_ctx); None is code 0 for all, which a handle of other contexts than CG
+        refuses."""
         arrays = [np.ascontiguousarray(a, dtype=t).reshape(-1) for a, t in
                   zip((line, chromosome, start, end, strand, posteriormax, status, meth_lvl),
                       (np.int64, np.int32, np.uint32, np.uint32, np.uint8, np.float64, np.uint8, np.float64))]
+        call = self._L.abn_sites_insert
+        if context is not None:
+            arrays.append(np.ascontiguousarray(context, dtype=np.uint8).reshape(-1))
+            call = self._L.abn_sites_insert_ctx
         if len({a.shape[0] for a in arrays}) != 1:
             raise ValueError("the arrays are of one length")
-        self.ctx._check(self._L.abn_sites_insert(self._h, arrays[0].shape[0], *(
-            a.ctypes.data_as(t) for a, t in zip(arrays, self._L.abn_sites_insert.argtypes[2:]))))
+        self.ctx._check(call(self._h, arrays[0].shape[0], *(a.ctypes.data_as(t) for a, t in zip(arrays, call.argtypes[2:]))))
+
+    def mask(self) -> int:
+        """the contexts the handle was parsed under (1 CG, 2 CHG, 4 CHH)"""
+        m = C.c_int32()
+        self.ctx._check(self._L.abn_sites_context(self._h, C.byref(m), None))
+        return m.value
+
+    def contexts(self) -> np.ndarray:
+        """every site's context code in the order of fetch(): 0 CG, 1 CHG, 2 CHH, 3 a row without one"""
+        out = np.zeros(self.info()["n_sites"], dtype=np.uint8)
+        self.ctx._check(self._L.abn_sites_context(self._h, None, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def split(self) -> "dict[str, Sites]":
+        """One resident handle per context of the handle's mask, partitioned on the device (abn_sites_split): each holds
+        what parse_sites_resident of the same text with that context alone, its deferred lines inserted, holds, and goes
+        into Windows.from_parsed, Codes.from_parsed and Tiles as it is.  This handle stays usable."""
+        out = (C.c_void_p * 3)()
+        self.ctx._check(self._L.abn_sites_split(self._h, out))
+        return {name: Sites(self.ctx, C.c_void_p(h)) for name, h in zip(CONTEXTS, out) if h}
+
+    def split_ms(self):
+        """(count kernel ms, scatter kernel ms) of the last split() of this handle, or of the split that made it"""
+        ms = np.zeros(2)
+        self.ctx._check(self._L.abn_sites_split_ms(self._h, _dp(ms)))
+        return float(ms[0]), float(ms[1])
 
     def fetch(self):
         """the sites in file order as a dict of arrays (Context.parse_sites' fields); a resident handle downloads them and

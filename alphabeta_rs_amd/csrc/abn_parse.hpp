@@ -22,6 +22,21 @@ namespace abn {
 
 enum ParseToken : int { kTokValue = 0, kTokReject = 1, kTokDefer = 2 };
 enum ParseLine : int { kLineNone = 0, kLineSite = 1, kLineDeferred = 2 };
+// A site's methylation context: field 3 of the 9-, 10- and 11-field formats; the 4-field rows have none.  A context MASK
+// holds bit 1 << code per accepted context; a row without a context is accepted under every mask.
+enum ParseContext : uint32_t { kCtxCG = 0, kCtxCHG = 1, kCtxCHH = 2, kCtxNone = 3 };
+constexpr uint32_t kContextsCG = 1u, kContextsAll = 7u;
+// where a device record's `meta` word keeps the code: above status_flag << 24, whose readers take four bits
+constexpr int kMetaContextShift = 28;
+ABN_HOST_DEVICE inline uint32_t meta_context(uint32_t meta) { return (meta >> kMetaContextShift) & 3u; }
+
+// field 3 -> its code; kCtxNone: none of CG, CHG, CHH (such a line is no site)
+ABN_HOST_DEVICE inline uint32_t abn_parse_context(const unsigned char* p, const unsigned char* e) {
+  if (e - p == 2 && p[0] == 'C' && p[1] == 'G') return kCtxCG;
+  if (e - p == 3 && p[0] == 'C' && p[1] == 'H' && p[2] == 'G') return kCtxCHG;
+  if (e - p == 3 && p[0] == 'C' && p[1] == 'H' && p[2] == 'H') return kCtxCHH;
+  return kCtxNone;
+}
 
 struct ParsedSite {  // windows::FullSite, and whether status_from would print its warning
   int32_t chromosome;  // Numbered(n) = n, Mitochondrial = 256, Chloroplast = 257
@@ -30,6 +45,7 @@ struct ParsedSite {  // windows::FullSite, and whether status_from would print i
   uint32_t status;       // U = 0, I = 1, M = 2
   uint32_t status_flag;  // 1: the status byte is none of M, I, U (parsed as U, src/methylation_site.rs:107-112)
   double posteriormax, meth_lvl;
+  uint32_t context;  // ParseContext
 };
 
 // str::parse::<u32> (detail::parse_u32): an optional '+', at least one digit, nothing else, at most 4294967295
@@ -123,12 +139,14 @@ ABN_HOST_DEVICE inline const unsigned char* abn_line_trim(const unsigned char* b
   return (e > b && e[-1] == '\r') ? e - 1 : e;
 }
 
-// One line [b, e), already trimmed.  9 or 10 tab fields with field 3 "CG": the first and second format; 11: the third
-// (end from field 2, strand from field 5); else exactly 4 fields under a split at tab or space: the chromatin-state /
+// One line [b, e), already trimmed.  9 or 10 tab fields with field 3 a context of the mask `contexts` (CG alone by
+// default): the first and second format; 11: the third (end from field 2, strand from field 5); a context outside the
+// mask ends the line as no site before any later field is read, so such a line is never deferred; else exactly 4 fields under a split at tab or space: the chromatin-state /
 // bigwig row.  A line of 9 to 11 tab fields has more than 4 fields under the wider split, so the two families never
 // compete for a line.  Empty fields count (str::split).  A field the line is certainly rejected for outweighs a
 // deferred one: such a line is no site whatever strtod says.
-ABN_HOST_DEVICE inline int abn_parse_line(const unsigned char* b, const unsigned char* e, ParsedSite& out) {
+ABN_HOST_DEVICE inline int abn_parse_line(const unsigned char* b, const unsigned char* e, ParsedSite& out,
+                                          uint32_t contexts = kContextsCG) {
   int ntab = 0, nsp = 0;
   for (const unsigned char* p = b; p < e; ++p) {
     ntab += *p == '\t' ? 1 : 0;
@@ -140,6 +158,7 @@ ABN_HOST_DEVICE inline int abn_parse_line(const unsigned char* b, const unsigned
   s.strand = 2;
   s.status = s.status_flag = 0;
   s.posteriormax = s.meth_lvl = 0.0;
+  s.context = kCtxNone;
   if (ntab >= 8 && ntab <= 10) {
     enum { CHROM = 0, START = 1, STRAND = 2, CTX = 3, CM = 4, CT = 5, PM = 6, ST = 7, ML = 8, IGN = 9, END = 10 };
     const bool third = ntab == 10;
@@ -159,7 +178,8 @@ ABN_HOST_DEVICE inline int abn_parse_line(const unsigned char* b, const unsigned
         case END: reject |= !abn_parse_u32(fb, fe, s.end), has_end = true; break;
         case STRAND: s.strand = (fe - fb == 1 && *fb == '+') ? 0u : 1u; break;
         case CTX:
-          if (!(fe - fb == 2 && fb[0] == 'C' && fb[1] == 'G')) return kLineNone;
+          s.context = abn_parse_context(fb, fe);
+          if (s.context == kCtxNone || !((contexts >> s.context) & 1u)) return kLineNone;
           break;
         case CM:
         case CT: reject |= !abn_parse_u32(fb, fe, u); break;

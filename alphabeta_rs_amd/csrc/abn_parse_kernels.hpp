@@ -126,7 +126,8 @@ abn_parse_index_kernel(const uint4* __restrict__ text, uint32_t n_pieces, const 
 
 struct ParseRecords {  // struct of arrays, one entry per accepted site
   uint32_t* line;      // the line's index in the slab
-  uint32_t* meta;      // chromosome | strand << 16 | status << 20 | status_flag << 24
+  uint32_t* meta;      // chromosome | strand << 16 | status << 20 | status_flag << 24 | context << 28 (four bits each
+                       // from bit 16 on; every reader masks the field it takes)
   uint32_t* start;
   uint32_t* end;
   double* posteriormax;
@@ -145,8 +146,8 @@ struct ParseDeferred {  // one entry per deferred line
 // run * kParseRun + (rank in the run), its counts to run_count[run] and run_count[count_stride + run].
 __global__ void __launch_bounds__(kParseThreads)
 abn_parse_lines_kernel(const uint4* __restrict__ text, uint32_t n_bytes, const uint32_t* __restrict__ line_begin,
-                       uint32_t n_newlines, uint32_t n_lines, uint32_t first_line, ParseRecords rec, ParseDeferred def,
-                       uint32_t* __restrict__ run_count, uint32_t count_stride) {
+                       uint32_t n_newlines, uint32_t n_lines, uint32_t first_line, uint32_t contexts, ParseRecords rec,
+                       ParseDeferred def, uint32_t* __restrict__ run_count, uint32_t count_stride) {
   __shared__ uint4 s_stage[kParseStageBytes / kParsePieceBytes];
   __shared__ uint32_t s_begin[kParseRun + 1];
   __shared__ uint32_t s_wave[kParseThreads / 64];
@@ -181,7 +182,7 @@ abn_parse_lines_kernel(const uint4* __restrict__ text, uint32_t n_bytes, const u
     if (fits) {
       const unsigned char* lb = (const unsigned char*)s_stage + (b - base);
       const unsigned char* le = abn_line_trim(lb, lb + (e - b));
-      cls = abn_parse_line(lb, le, site);
+      cls = abn_parse_line(lb, le, site, contexts);
       def_len = (uint32_t)(le - lb);
     }
     s += cnt;
@@ -194,7 +195,8 @@ abn_parse_lines_kernel(const uint4* __restrict__ text, uint32_t n_bytes, const u
   if (cls == kLineSite) {
     const size_t k = slot0 + (ranks & 0xffffu);
     rec.line[k] = line0 + threadIdx.x;
-    rec.meta[k] = (uint32_t)site.chromosome | site.strand << 16 | site.status << 20 | site.status_flag << 24;
+    rec.meta[k] = (uint32_t)site.chromosome | site.strand << 16 | site.status << 20 | site.status_flag << 24 |
+                  site.context << kMetaContextShift;
     rec.start[k] = site.start;
     rec.end[k] = site.end;
     rec.posteriormax[k] = site.posteriormax;

@@ -2,13 +2,17 @@
 // the loops of src/windows.rs:303-338 and src/pedigree.rs:138-178 in front of it).  Kernels: abn_parse_kernels.hpp; the
 // line parser they share with the host: abn_parse.hpp.  The resident form (abn_sites_parse_dev, abn_sites_insert) keeps the
 // records on the device for abn_windows_create_parsed (abn_windows.hip; its merge kernels: abn_sites_merge.hpp) and for
-// abn_codes_create_parsed (abn_codes.hip; its reduced merge kernels: abn_codes.hpp).
+// abn_codes_create_parsed (abn_codes.hip; its reduced merge kernels: abn_codes.hpp).  A handle parsed under a mask of
+// several contexts is partitioned into one ordinary resident handle per context by abn_sites_split (its kernels:
+// abn_sites_split.hpp).
 #include "abn_host.hpp"
 #include "abn_parse_kernels.hpp"
 #define ABN_SITES_MERGE_KERNELS
 #include "abn_sites_merge.hpp"
 #define ABN_CODES_MERGE_KERNELS
 #include "abn_codes.hpp"
+#define ABN_SITES_SPLIT_KERNELS
+#include "abn_sites_split.hpp"
 
 using namespace abn;
 
@@ -43,8 +47,12 @@ struct SiteChunk {  // a slab's compacted records, resident (abn_sites_parse_dev
 
 // The host form (abn_sites_parse) holds the records in the vectors; the resident form (abn_sites_parse_dev: ctx is set)
 // holds them in `chunks` on the device and, after abn_sites_insert, the host-decided records in the same vectors and in
-// the i* buffers.  The deferred triples, n_lines and kernel_ms are the same in both.
+// the i* buffers.  The deferred triples, n_lines and kernel_ms are the same in both.  `context` goes with `line`: the code
+// of every record the vectors hold.
 struct abn_sites {
+  int32_t mask = (int32_t)kContextsCG;  // the contexts the handle was parsed under
+  std::vector<uint8_t> context;
+  mutable double split_ms[2] = {0.0, 0.0};  // abn_sites_split's count and scatter kernels: on the parent and its children
   std::vector<int64_t> line, dline, doffset, dlength;
   std::vector<int32_t> chromosome;
   std::vector<uint32_t> start, end;
@@ -133,7 +141,7 @@ int parse_slab(abn_ctx* c, abn_sites* h, bool resident, const char* text, size_t
                      dblock.p, dbegin.p);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(abn_parse_lines_kernel, dim3(n_runs), dim3(kParseThreads), 0, c->stream, dtext.p, (uint32_t)n,
-                     dbegin.p, n_newlines, n_lines, first, run.records(), run.deferred(), dcount.p, stride);
+                     dbegin.p, n_newlines, n_lines, first, (uint32_t)h->mask, run.records(), run.deferred(), dcount.p, stride);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(abn_parse_scan_kernel, dim3(2), dim3(kParseScanThreads), 0, c->stream, dcount.p, n_runs, stride);
   HIPCHK(c, hipGetLastError());
@@ -222,6 +230,7 @@ int parse_slab(abn_ctx* c, abn_sites* h, bool resident, const char* text, size_t
   h->strand.resize(at + n_rec);
   h->status.resize(at + n_rec);
   h->status_flag.resize(at + n_rec);
+  h->context.resize(at + n_rec);
   for (size_t i = 0; i < n_rec; ++i) {
     const uint32_t m = meta[i];
     h->line[at + i] = line0 + (int64_t)line[i];
@@ -229,6 +238,7 @@ int parse_slab(abn_ctx* c, abn_sites* h, bool resident, const char* text, size_t
     h->strand[at + i] = (uint8_t)((m >> 16) & 0xfu);
     h->status[at + i] = (uint8_t)((m >> 20) & 0xfu);
     h->status_flag[at + i] = (uint8_t)((m >> 24) & 0xfu);
+    h->context[at + i] = (uint8_t)meta_context(m);
   }
   take_deferred();
   return ABN_OK;
@@ -243,11 +253,14 @@ int sites_parse(abn_ctx* c, const char* text, int64_t n_bytes, const abn_sites_p
   int64_t slab = params ? params->slab_bytes : 0, skip = params ? params->skip_lines : 1;
   if (slab < 0 || slab > kSitesMaxSlab || skip < 0) return set_err(c, ABN_ERR_INVALID_ARG, "slab_bytes / skip_lines");
   if (slab == 0) slab = kSitesDefaultSlab;
+  const int32_t contexts = params ? params->contexts : 0;
+  if (contexts < 0 || contexts > (int32_t)kContextsAll) return set_err(c, ABN_ERR_INVALID_ARG, "contexts outside 0..7");
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
   std::unique_ptr<abn_sites> h(new (std::nothrow) abn_sites);
   if (!h) return set_err(c, ABN_ERR_HIP, "out of host memory");
   if (resident) h->ctx = c, h->device = c->device;
+  h->mask = contexts == 0 ? (int32_t)kContextsCG : contexts;
   EventPair ev;
   try {
     const size_t n = (size_t)n_bytes;
@@ -299,7 +312,7 @@ extern "C" int abn_sites_info(const abn_sites* h, int64_t* n_sites, int64_t* n_d
 // abn_sites_fetch of a resident handle: every chunk's records come down and are merged by line with the inserted ones
 static int sites_fetch_resident(const abn_sites* h, int64_t* line, int32_t* chromosome, uint32_t* start, uint32_t* end,
                                 uint8_t* strand, double* posteriormax, uint8_t* status, uint8_t* status_flag,
-                                double* meth_lvl) {
+                                double* meth_lvl, uint8_t* context) {
   abn_ctx* c = h->ctx;
   HIPCHK(c, hipSetDevice(c->device));
   try {
@@ -315,6 +328,7 @@ static int sites_fetch_resident(const abn_sites* h, int64_t* line, int32_t* chro
       if (status) status[k] = h->status[j];
       if (status_flag) status_flag[k] = 0;
       if (meth_lvl) meth_lvl[k] = h->meth_lvl[j];
+      if (context) context[k] = h->context[j];
       ++j, ++k;
     };
     for (const auto& chunk : h->chunks) {
@@ -342,6 +356,7 @@ static int sites_fetch_resident(const abn_sites* h, int64_t* line, int32_t* chro
         if (status) status[k] = (uint8_t)((m[i] >> 20) & 0xfu);
         if (status_flag) status_flag[k] = (uint8_t)((m[i] >> 24) & 0xfu);
         if (meth_lvl) meth_lvl[k] = ml[i];
+        if (context) context[k] = (uint8_t)meta_context(m[i]);
         ++k;
       }
     }
@@ -356,7 +371,8 @@ extern "C" int abn_sites_fetch(const abn_sites* h, int64_t* line, int32_t* chrom
                                uint8_t* strand, double* posteriormax, uint8_t* status, uint8_t* status_flag,
                                double* meth_lvl) {
   if (!h) return ABN_ERR_INVALID_ARG;
-  if (h->ctx) return sites_fetch_resident(h, line, chromosome, start, end, strand, posteriormax, status, status_flag, meth_lvl);
+  if (h->ctx)
+    return sites_fetch_resident(h, line, chromosome, start, end, strand, posteriormax, status, status_flag, meth_lvl, nullptr);
   if (line) std::copy(h->line.begin(), h->line.end(), line);
   if (chromosome) std::copy(h->chromosome.begin(), h->chromosome.end(), chromosome);
   if (start) std::copy(h->start.begin(), h->start.end(), start);
@@ -366,6 +382,16 @@ extern "C" int abn_sites_fetch(const abn_sites* h, int64_t* line, int32_t* chrom
   if (status) std::copy(h->status.begin(), h->status.end(), status);
   if (status_flag) std::copy(h->status_flag.begin(), h->status_flag.end(), status_flag);
   if (meth_lvl) std::copy(h->meth_lvl.begin(), h->meth_lvl.end(), meth_lvl);
+  return ABN_OK;
+}
+
+extern "C" int abn_sites_context(const abn_sites* h, int32_t* mask, uint8_t* context) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  if (mask) *mask = h->mask;
+  if (!context) return ABN_OK;
+  if (h->ctx)
+    return sites_fetch_resident(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, context);
+  std::copy(h->context.begin(), h->context.end(), context);
   return ABN_OK;
 }
 
@@ -394,9 +420,11 @@ extern "C" int abn_sites_flagged(const abn_sites* h, int64_t* n, int64_t* line) 
   return ABN_OK;
 }
 
-extern "C" int abn_sites_insert(abn_sites* h, int64_t n, const int64_t* line, const int32_t* chromosome,
-                                const uint32_t* start, const uint32_t* end, const uint8_t* strand,
-                                const double* posteriormax, const uint8_t* status, const double* meth_lvl) {
+// abn_sites_insert_ctx (context null: every code is 0), and how a child of abn_sites_split gets its share of the parent's
+// inserted records (inherited: it has no deferred lines to look the lines up in)
+static int sites_insert(abn_sites* h, int64_t n, const int64_t* line, const int32_t* chromosome, const uint32_t* start,
+                        const uint32_t* end, const uint8_t* strand, const double* posteriormax, const uint8_t* status,
+                        const double* meth_lvl, const uint8_t* context, bool inherited) {
   if (!h || !h->ctx) return ABN_ERR_INVALID_ARG;  // (a host-form handle has no context to report to)
   abn_ctx* c = h->ctx;
   if (h->inserted) return set_err(c, ABN_ERR_INVALID_ARG, "abn_sites_insert was already called on this handle");
@@ -408,9 +436,13 @@ extern "C" int abn_sites_insert(abn_sites* h, int64_t n, const int64_t* line, co
     for (size_t j = 0; j < N; ++j) {
       if (j > 0 && line[j] <= line[j - 1]) return set_err(c, ABN_ERR_INVALID_ARG, "the lines are not strictly ascending");
       while (d < h->dline.size() && h->dline[d] < line[j]) ++d;
-      if (d == h->dline.size() || h->dline[d] != line[j]) return set_err(c, ABN_ERR_INVALID_ARG, "a line that was not deferred");
+      if (!inherited && (d == h->dline.size() || h->dline[d] != line[j]))
+        return set_err(c, ABN_ERR_INVALID_ARG, "a line that was not deferred");
       if (chromosome[j] < 0 || chromosome[j] > 257) return set_err(c, ABN_ERR_INVALID_ARG, "a chromosome outside 0..257");
       if (strand[j] > 2 || status[j] > 2) return set_err(c, ABN_ERR_INVALID_ARG, "a strand or a status above 2");
+      const uint32_t code = context ? context[j] : (uint32_t)kCtxCG;
+      if (code > kCtxNone || (code < kCtxNone && !(((uint32_t)h->mask >> code) & 1u)))
+        return set_err(c, ABN_ERR_INVALID_ARG, "a context code above 3 or outside the handle's contexts");
     }
     if (N > 0) {
       std::vector<MergeChunk> refs;
@@ -450,11 +482,197 @@ extern "C" int abn_sites_insert(abn_sites* h, int64_t n, const int64_t* line, co
       h->posteriormax.assign(posteriormax, posteriormax + N);
       h->status.assign(status, status + N);
       h->meth_lvl.assign(meth_lvl, meth_lvl + N);
+      if (context) h->context.assign(context, context + N);
+      else h->context.assign(N, (uint8_t)kCtxCG);
     }
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
   }
   h->inserted = true;
+  return ABN_OK;
+}
+
+extern "C" int abn_sites_insert_ctx(abn_sites* h, int64_t n, const int64_t* line, const int32_t* chromosome,
+                                    const uint32_t* start, const uint32_t* end, const uint8_t* strand,
+                                    const double* posteriormax, const uint8_t* status, const double* meth_lvl,
+                                    const uint8_t* context) {
+  if (h && h->ctx && n > 0 && !context) return set_err(h->ctx, ABN_ERR_INVALID_ARG, "null/size");
+  return sites_insert(h, n, line, chromosome, start, end, strand, posteriormax, status, meth_lvl, context, false);
+}
+
+extern "C" int abn_sites_insert(abn_sites* h, int64_t n, const int64_t* line, const int32_t* chromosome,
+                                const uint32_t* start, const uint32_t* end, const uint8_t* strand,
+                                const double* posteriormax, const uint8_t* status, const double* meth_lvl) {
+  if (h && h->ctx && n > 0 && h->mask != (int32_t)kContextsCG)
+    return set_err(h->ctx, ABN_ERR_INVALID_ARG, "the handle holds other contexts than CG: abn_sites_insert_ctx names each record's");
+  return sites_insert(h, n, line, chromosome, start, end, strand, posteriormax, status, meth_lvl, nullptr, false);
+}
+
+// ---- abn_sites_split
+namespace {
+
+// the chunk table on the device: the parent's chunks with their workgroups and (once made) the children's chunks
+int upload_split_chunks(abn_ctx* c, const std::vector<SplitChunk>& table, DevBuf<SplitChunk>& d) {
+  HIPCHK(c, hipMemcpyAsync(d.p, table.data(), d.bytes(), hipMemcpyHostToDevice, c->stream));
+  return ABN_OK;
+}
+
+int sites_split(const abn_sites* h, std::unique_ptr<abn_sites>* kids) {
+  abn_ctx* c = h->ctx;
+  const int n_chunks = (int)h->chunks.size();
+  std::vector<SplitChunk> table((size_t)n_chunks);
+  std::vector<MergeChunk> refs((size_t)n_chunks);
+  long long n_blocks = 0;
+  for (int i = 0; i < n_chunks; ++i) {
+    refs[(size_t)i] = h->chunks[(size_t)i]->ref();
+    table[(size_t)i] = SplitChunk{refs[(size_t)i], n_blocks, {}};
+    n_blocks += split_blocks(h->chunks[(size_t)i]->n);
+  }
+  if (n_blocks >= (long long)1 << 31 || h->n_records >= (int64_t)1 << 32)
+    return set_err(c, ABN_ERR_INVALID_ARG, "abn_sites_split: 2^32 records or more");
+  for (int k = 0; k < kSplitChildren; ++k) {
+    if (!((h->mask >> k) & 1)) continue;
+    kids[k].reset(new abn_sites);
+    kids[k]->ctx = c, kids[k]->device = h->device;
+    kids[k]->mask = 1 << k;
+    kids[k]->n_lines = h->n_lines;
+  }
+  const uint32_t stride = (uint32_t)n_blocks + 1u;
+  std::vector<uint32_t> size((size_t)n_chunks * kSplitChildren, 0u);
+  DevBuf<SplitChunk> dtable;
+  DevBuf<uint32_t> dcount, dsize;
+  EventPair ev;
+  h->split_ms[0] = h->split_ms[1] = 0.0;
+  if (n_blocks > 0) {
+    HIPCHK(c, dtable.alloc((size_t)n_chunks));
+    HIPCHK(c, dcount.alloc((size_t)kSplitChildren * stride));
+    HIPCHK(c, dsize.alloc(size.size()));
+    if (int rc = upload_split_chunks(c, table, dtable)) return rc;
+    if (int rc = ev.begin(c, true)) return rc;
+    hipLaunchKernelGGL(abn_split_count_kernel, dim3((unsigned)n_blocks), dim3(kSplitThreads), 0, c->stream,
+                       (const SplitChunk*)dtable.p, n_chunks, (uint32_t)h->mask, dcount.p, stride);
+    HIPCHK(c, hipGetLastError());
+    if (int rc = ev.end(c, &h->split_ms[0])) return rc;
+    hipLaunchKernelGGL(abn_parse_scan_kernel, dim3(kSplitChildren), dim3(kParseScanThreads), 0, c->stream, dcount.p,
+                       (uint32_t)n_blocks, stride);
+    HIPCHK(c, hipGetLastError());
+    const unsigned size_grid = (unsigned)((size.size() + kSplitThreads - 1) / kSplitThreads);
+    hipLaunchKernelGGL(abn_split_sizes_kernel, dim3(size_grid), dim3(kSplitThreads), 0, c->stream,
+                       (const SplitChunk*)dtable.p, n_chunks, (const uint32_t*)dcount.p, stride, (uint32_t)n_blocks, dsize.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(size.data(), dsize.p, dsize.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  // the children's chunks: a slab keeps its lines, and holds the child's share of its records
+  for (int i = 0; i < n_chunks; ++i)
+    for (int k = 0; k < kSplitChildren; ++k) {
+      if (!kids[k]) continue;  // (a context outside the mask has no child, and the kernels count no record for it)
+      abn_sites* kid = kids[k].get();
+      kid->chunks.emplace_back(new SiteChunk);
+      SiteChunk* chunk = kid->chunks.back().get();
+      chunk->n = size[(size_t)i * kSplitChildren + k];
+      chunk->line0 = h->chunks[(size_t)i]->line0;
+      chunk->n_lines = h->chunks[(size_t)i]->n_lines;
+      chunk->before = kid->n_records;
+      kid->n_records += chunk->n;
+      HIPCHK(c, chunk->rec.alloc((size_t)chunk->n, 0));
+      table[(size_t)i].out[k] = SplitOut{chunk->rec.line.p, chunk->rec.meta.p, chunk->rec.start.p,
+                                         chunk->rec.end.p,  chunk->rec.pm.p,   chunk->rec.ml.p};
+    }
+  for (int i = 0; i < n_chunks; ++i)  // a record counted for a context without a child would have nowhere to go
+    for (int k = 0; k < kSplitChildren; ++k)
+      if (!kids[k] && size[(size_t)i * kSplitChildren + k] != 0)
+        return set_err(c, ABN_ERR_HIP, "abn_sites_split: a record outside the handle's contexts");
+  // the flagged lines: which children inherit each, found on the device
+  const size_t n_flagged = h->flagged.size();
+  std::vector<uint8_t> member(n_flagged, 0);
+  DevBuf<long long> dfline;
+  DevBuf<int32_t> dfchunk;
+  DevBuf<uint8_t> dmember;
+  std::vector<long long> fline(h->flagged.begin(), h->flagged.end());
+  std::vector<int32_t> fchunk(n_flagged);
+  if (n_blocks > 0) {
+    if (int rc = upload_split_chunks(c, table, dtable)) return rc;
+    if (n_flagged) {
+      if (!merge_pick_chunks(refs.data(), n_chunks, fline.data(), (long long)n_flagged, fchunk.data()))
+        return set_err(c, ABN_ERR_HIP, "abn_sites_split: a flagged line outside every slab");
+      HIPCHK(c, dfline.alloc(n_flagged));
+      HIPCHK(c, dfchunk.alloc(n_flagged));
+      HIPCHK(c, dmember.alloc(n_flagged));
+      HIPCHK(c, hipMemcpyAsync(dfline.p, fline.data(), dfline.bytes(), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(dfchunk.p, fchunk.data(), dfchunk.bytes(), hipMemcpyHostToDevice, c->stream));
+    }
+    if (int rc = ev.begin(c, true)) return rc;
+    hipLaunchKernelGGL(abn_split_scatter_kernel, dim3((unsigned)n_blocks), dim3(kSplitThreads), 0, c->stream,
+                       (const SplitChunk*)dtable.p, n_chunks, (uint32_t)h->mask, (const uint32_t*)dcount.p, stride);
+    HIPCHK(c, hipGetLastError());
+    if (int rc = ev.end(c, &h->split_ms[1])) return rc;
+    if (n_flagged) {
+      const unsigned grid = (unsigned)((n_flagged + kSplitThreads - 1) / kSplitThreads);
+      hipLaunchKernelGGL(abn_split_flagged_kernel, dim3(grid), dim3(kSplitThreads), 0, c->stream,
+                         (const SplitChunk*)dtable.p, (const long long*)dfline.p, (const int32_t*)dfchunk.p,
+                         (long long)n_flagged, (uint32_t)h->mask, dmember.p);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(member.data(), dmember.p, n_flagged, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the tables and staging vectors go on return
+  }
+  for (int k = 0; k < kSplitChildren; ++k) {
+    if (!kids[k]) continue;
+    abn_sites* kid = kids[k].get();
+    kid->split_ms[0] = h->split_ms[0], kid->split_ms[1] = h->split_ms[1];
+    for (size_t j = 0; j < n_flagged; ++j)
+      if ((member[j] >> k) & 1u) kid->flagged.push_back(h->flagged[j]);
+    // the parent's inserted records of this membership, uploaded as abn_sites_insert uploads them
+    std::vector<int64_t> line;
+    std::vector<int32_t> chrom;
+    std::vector<uint32_t> start, end;
+    std::vector<uint8_t> strand, status, context;
+    std::vector<double> pm, ml;
+    for (size_t j = 0; j < h->line.size(); ++j) {
+      const uint32_t code = h->context[j];
+      if (code != kCtxNone && code != (uint32_t)k) continue;
+      line.push_back(h->line[j]);
+      chrom.push_back(h->chromosome[j]);
+      start.push_back(h->start[j]);
+      end.push_back(h->end[j]);
+      strand.push_back(h->strand[j]);
+      pm.push_back(h->posteriormax[j]);
+      status.push_back(h->status[j]);
+      ml.push_back(h->meth_lvl[j]);
+      context.push_back((uint8_t)code);
+    }
+    if (int rc = sites_insert(kid, (int64_t)line.size(), line.data(), chrom.data(), start.data(), end.data(), strand.data(),
+                              pm.data(), status.data(), ml.data(), context.data(), true))
+      return rc;
+  }
+  return ABN_OK;
+}
+
+}  // namespace
+
+extern "C" int abn_sites_split(const abn_sites* h, abn_sites** out3) {
+  if (out3) out3[0] = out3[1] = out3[2] = nullptr;
+  if (!h || !h->ctx) return ABN_ERR_INVALID_ARG;  // (a host-form handle has no context to report to)
+  abn_ctx* c = h->ctx;
+  if (!out3) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (!h->dline.empty() && !h->inserted)
+    return set_err(c, ABN_ERR_INVALID_ARG, "abn_sites_split: the handle has deferred lines and abn_sites_insert was never called");
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  std::unique_ptr<abn_sites> kids[kSplitChildren];
+  try {
+    if (int rc = sites_split(h, kids)) return rc;
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+  for (int k = 0; k < kSplitChildren; ++k) out3[k] = kids[k].release();
+  return ABN_OK;
+}
+
+extern "C" int abn_sites_split_ms(const abn_sites* h, double* ms2) {
+  if (!h || !ms2) return ABN_ERR_INVALID_ARG;
+  ms2[0] = h->split_ms[0], ms2[1] = h->split_ms[1];
   return ABN_OK;
 }
 

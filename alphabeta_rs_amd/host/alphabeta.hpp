@@ -387,11 +387,13 @@ class Pedigree {  // src/pedigree.rs:44-45
                                            bool device_parse = false,    // the methylome files through abn_sites_parse
                                            bool device_sites = false,    // (with both of the above) the parsed sites stay
                                                                          // on the device: abn_codes_create_parsed
-                                           Align align = Align::None);   // (with all of the above) Position: the samples
+                                           Align align = Align::None,    // (with all of the above) Position: the samples
                                                                          // compared on the sites they share
                                                                          // (abn_codes_create_aligned), p0uu the fold over
                                                                          // those; Union: pair by pair on the sites both
                                                                          // hold (abn_codes_create_union), p0uu unchanged
+                                           unsigned contexts = 1u);      // (with device_sites) the methylation contexts
+                                                                         // whose lines are sites: 1 CG, 2 CHG, 4 CHH
   // ... for many (nodelist, edgelist) pairs at once (the windows of src/cli/metaprofile.rs:50-72): with gpu_pairwise ONE
   // abn_pairwise_divergence_windows_packed call per batch of entries with the same number of samples, on 2-bit codes
   // packed straight from the site records.  A batch ends at kBuildManyCodeBytes of PACKED codes per call (four sites per
@@ -508,6 +510,8 @@ struct Args {  // arguments::AlphaBeta, src/arguments.rs:93-114
                               // matrix and the rc_meth_lvl folds (abn_sites_parse_dev, abn_codes_create_parsed)
   Align align = Align::None;  // --align position | union (with --sites device): the samples are compared on the sites they
                               // all share | pair by pair on the sites both hold
+  unsigned contexts = 1u;     // --contexts LIST (with --sites device): the methylation contexts fitted, 1 CG | 2 CHG | 4 CHH;
+                              // several: each is a run of its own (run_contexts) on one parse of every methylome
 };
 
 struct RunResult {
@@ -573,7 +577,19 @@ namespace alphabeta {
 inline RunResult run(const Args& args) {
   std::printf("Building pedigree...\n");
   auto [pedigree, p0uu] = Pedigree::build(args.nodes, args.edges, args.posterior_max_filter, /*gpu_pairwise=*/true,
-                                          args.device_parse, args.device_sites, args.align);
+                                          args.device_parse, args.device_sites, args.align, args.contexts);
   return run_on_pedigree(std::move(pedigree), p0uu, args.iterations, args.output);
+}
+
+// `run` once per context of args.contexts, several of them: every methylome is read and parsed once and split on the
+// device (abn_sites_split), then each context is built and fitted as the run under that context alone is — the same
+// pedigree, the same seed, the same bits.  done(c, result) takes context c's result as soon as it is there.
+template <class Done>
+inline void run_contexts(const Args& args, Done done) {
+  std::printf("Building pedigrees...\n");
+  auto built = detail::build_pedigrees_by_context(args.nodes, args.edges, args.posterior_max_filter, args.align, args.contexts);
+  for (size_t c = 0; c < 3; ++c)
+    if ((args.contexts >> c) & 1u)
+      done(c, run_on_pedigree(std::move(built[c].first), built[c].second, args.iterations, args.output));
 }
 }  // namespace alphabeta

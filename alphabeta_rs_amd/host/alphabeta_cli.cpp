@@ -41,14 +41,18 @@ static void usage() {
       "                                 pair on the sites both samples hold; p0uu stays each file's own.  Both need\n"
       "                                 --sites device\n"
       "                                 [default: none]\n"
-      "  -h, --help                     Print help\n"
+      "      --contexts <LIST>          the methylation contexts to fit, a comma-separated subset of CG,CHG,CHH (needs\n"
+      "                                 --sites device).  One: the run on that context's sites.  Several: every methylome\n"
+      "                                 is parsed once and each context is a run of its own, its files in <OUTPUT>/<CTX>/\n"
+      "                                 [default: CG]\n"
+      "  -h, --help                    Print help\n"
       "  -V, --version                  Print version");
 }
 
 int main(int argc, char** argv) {
   Args args;
   args.device_parse = true;  // measured: docs/experiments.md, "Device parsing"
-  bool edges_given = false, nodes_given = false;
+  bool edges_given = false, nodes_given = false, contexts_given = false;
   std::string ped_file;
   double p0uu_given = -1.0;
   uint64_t seed = 20260101ull;
@@ -107,12 +111,23 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--contexts") {
+      if (!resident::parse_contexts(val(), args.contexts)) {
+        std::fprintf(stderr, "error: %s\n", resident::kContextsExpects);
+        return 2;
+      }
+      contexts_given = true;
+    }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (a == "-V" || a == "--version") { std::puts("alphabeta 0.2.1 (MI355X ABneutral path)"); return 0; }
     else {
       std::fprintf(stderr, "error: unexpected argument '%s' found\n\nFor more information, try '--help'.\n", argv[i]);
       return 2;
     }
+  }
+  if (contexts_given && !(args.device_sites && args.device_parse)) {
+    std::fprintf(stderr, "error: --contexts needs --sites device and --parse device\n");
+    return 2;
   }
   if (args.device_sites && !args.device_parse) {
     std::fprintf(stderr, "error: --sites device needs --parse device\n");
@@ -158,6 +173,24 @@ int main(int argc, char** argv) {
     dev.options.lanes_per_chain = lanes;
     dev.options.strict_order = strict_order ? 1 : 0;
     dev.stream_sweep = stream_sweep;
+    // src/cli/alphabeta.rs:19-35
+    auto report = [](const RunResult& r, const fs::path& out) {
+      std::printf("##########\nResults:\n\n%s\n%s\n", r.model.display().c_str(), r.analysis.display().c_str());
+      std::printf("Estimated steady state %s\n", fmt_f64(steady_state(r.model.alpha, r.model.beta)).c_str());
+      std::printf("Observed steady state methylation %s\n##########\n", fmt_f64(r.obs_steady_state).c_str());
+      r.pedigree.to_file((out / "pedigree.txt").string());
+      r.analysis.to_file((out / "analysis.txt").string());
+      r.raw_analysis.write_npy((out / "raw.npy").string());
+    };
+    if (!resident::one_context(args.contexts)) {  // every context a run of its own, its files in <output>/<CTX>/
+      run_contexts(args, [&](size_t c, const RunResult& r) {
+        const fs::path out = fs::path(args.output) / resident::kContextNames[c];
+        fs::create_directories(out);
+        std::printf("Context %s\n", resident::kContextNames[c]);
+        report(r, out);
+      });
+      return 0;
+    }
     RunResult r;
     if (!ped_file.empty()) {
       if (!(p0uu_given > 0.0 && p0uu_given < 1.0)) {
@@ -168,14 +201,7 @@ int main(int argc, char** argv) {
     } else {
       r = run(args);
     }
-    // src/cli/alphabeta.rs:19-35
-    std::printf("##########\nResults:\n\n%s\n%s\n", r.model.display().c_str(), r.analysis.display().c_str());
-    std::printf("Estimated steady state %s\n", fmt_f64(steady_state(r.model.alpha, r.model.beta)).c_str());
-    std::printf("Observed steady state methylation %s\n##########\n", fmt_f64(r.obs_steady_state).c_str());
-    const fs::path out(args.output);
-    r.pedigree.to_file((out / "pedigree.txt").string());
-    r.analysis.to_file((out / "analysis.txt").string());
-    r.raw_analysis.write_npy((out / "raw.npy").string());
+    report(r, fs::path(args.output));
   } catch (const Error& e) {
     std::printf("Error: %s\n", e.what());  // src/cli/alphabeta.rs:17 prints and exits 0; a status is more useful
     return 1;

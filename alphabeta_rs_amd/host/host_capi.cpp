@@ -9,6 +9,7 @@
 #include "../csrc/abn_route.hpp"
 #include "../csrc/abn_codes.hpp"
 #include "../csrc/abn_sites_merge.hpp"
+#include "../csrc/abn_sites_split.hpp"
 #include "../csrc/abn_sites_common.hpp"
 #include "../csrc/abn_sites_union.hpp"
 #include "../csrc/abn_tiles.hpp"
@@ -306,6 +307,85 @@ long long abh_classify_text(const char* text, long long len, long long skip_line
   }
   *n_sites = ns;
   return out;
+}
+// ---- the same two parsers under a context mask (1 CG, 2 CHG, 4 CHH), and the serial form of the partition by context
+// (csrc/abn_sites_split.hpp), for tests/test_sites_split_cpu.py and tests/test_sites_split_gpu.py
+// abh_parse_sites with parse_sites_host's mask; context (capacity cap) = every site's code
+long long abh_parse_sites_ctx(const char* text, long long len, long long skip_lines, unsigned contexts, long long cap,
+                              long long* line, int* chromosome, unsigned* start, unsigned* end, unsigned char* strand,
+                              double* posteriormax, unsigned char* status, double* meth_lvl, unsigned char* context,
+                              long long* n_warnings) {
+  DiagCapture warnings;
+  std::vector<int64_t> lines;
+  const auto sites =
+      alphabeta::windows::parse_sites_host(std::string(text, (size_t)len), (size_t)skip_lines, &lines, contexts);
+  if (n_warnings) *n_warnings = (long long)std::count(warnings.text.begin(), warnings.text.end(), '\n');
+  const long long n = put_sites(sites, lines, cap, line, chromosome, start, end, strand, posteriormax, status, meth_lvl);
+  for (long long i = 0; i < n; ++i) context[i] = sites[(size_t)i].context;
+  return n;
+}
+// abh_classify_text with abn_parse_line's mask; site_context = every site's code
+long long abh_classify_text_ctx(const char* text, long long len, long long skip_lines, unsigned contexts, long long cap,
+                                unsigned char* cls, long long* site_line, unsigned* u6, double* d2,
+                                unsigned char* site_context, long long* n_sites) {
+  const unsigned char* t = (const unsigned char*)text;
+  long long li = 0, out = 0, ns = 0;
+  for (long long b = 0; b < len; ++li) {
+    long long e = b;
+    while (e < len && t[e] != '\n') ++e;
+    if (li >= skip_lines) {
+      if (out >= cap) return -1;
+      abn::ParsedSite s{};
+      const int c = abn::abn_parse_line(t + b, abn::abn_line_trim(t + b, t + e), s, contexts);
+      cls[out++] = (unsigned char)c;
+      if (c == abn::kLineSite) {
+        site_line[ns] = li;
+        const unsigned u[6] = {(unsigned)s.chromosome, s.start, s.end, s.strand, s.status, s.status_flag};
+        std::memcpy(u6 + 6 * ns, u, sizeof u);
+        d2[2 * ns] = s.posteriormax;
+        d2[2 * ns + 1] = s.meth_lvl;
+        site_context[ns] = (unsigned char)s.context;
+        ++ns;
+      }
+    }
+    b = e + 1;
+  }
+  *n_sites = ns;
+  return out;
+}
+// The partition of one sample's records by context under the parent's mask, serially: n_chunks chunks of chunk_n records, their six record arrays
+// concatenated (n records in all) -> size [n_chunks * 3] = the records of chunk c in child k at c * 3 + k, and child k's
+// arrays, its chunks concatenated, from k * n on in the six output arrays (capacity 3 * n each).  Returns the workgroups
+// walked, -1 when the scanned counts and the sizes disagree
+long long abh_sites_split_serial(int n_chunks, unsigned contexts, const long long* chunk_n, const unsigned* line, const unsigned* meta,
+                                 const unsigned* start, const unsigned* end, const double* pm, const double* ml,
+                                 unsigned* size, unsigned* oline, unsigned* ometa, unsigned* ostart, unsigned* oend,
+                                 double* opm, double* oml) {
+  std::vector<abn::SplitChunk> chunks((size_t)n_chunks);
+  long long n = 0, n_blocks = 0;
+  for (int c = 0; c < n_chunks; ++c) {
+    chunks[(size_t)c].src = abn::MergeChunk{line + n, meta + n, start + n, end + n, pm + n, ml + n, chunk_n[c], 0, 0, n};
+    chunks[(size_t)c].block0 = n_blocks;
+    n += chunk_n[c];
+    n_blocks += abn::split_blocks(chunk_n[c]);
+  }
+  const long long stride = n_blocks + 1;
+  std::vector<uint32_t> count((size_t)(abn::kSplitChildren * stride), 0u);
+  abn::split_count_serial(chunks.data(), n_chunks, contexts, count.data(), stride);
+  abn::split_scan_serial(count.data(), n_blocks, stride);
+  long long at[abn::kSplitChildren] = {0, 0, 0};
+  for (int c = 0; c < n_chunks; ++c)
+    for (int k = 0; k < abn::kSplitChildren; ++k) {
+      const uint32_t s = abn::split_chunk_size(chunks.data(), n_chunks, c, k, count.data(), stride, n_blocks);
+      size[c * abn::kSplitChildren + k] = s;
+      const long long o = (long long)k * n + at[k];
+      chunks[(size_t)c].out[k] = abn::SplitOut{oline + o, ometa + o, ostart + o, oend + o, opm + o, oml + o};
+      at[k] += s;
+    }
+  for (int k = 0; k < abn::kSplitChildren; ++k)
+    if (at[k] != (long long)count[(size_t)(k * stride + n_blocks)]) return -1;
+  abn::split_scatter_serial(chunks.data(), n_chunks, contexts, count.data(), stride, n_blocks);
+  return n_blocks;
 }
 // parse_sites_device of a text on the default device (slab_bytes as abn_sites_params) -> the arrays of abh_parse_sites;
 // warnings (capacity wcap) = what it printed.  Returns the number of sites, -1: they do not fit, -2: the call threw

@@ -26,7 +26,8 @@ int main(int argc, char** argv) {
   std::string devices_arg;
   bool stream_sweep = false;
   metaprofile::TileArgs tiles;
-  bool tiles_given = false, tile_step_given = false, parse_host = false, sites_host = false;
+  bool tiles_given = false, tile_step_given = false, parse_host = false, sites_host = false, contexts_given = false;
+  unsigned contexts = 1u;
   for (int i = 1; i < argc; ++i) {
     const std::string f = argv[i];
     auto val = [&]() -> std::string {
@@ -99,6 +100,13 @@ int main(int argc, char** argv) {
       (f == "--tiles" ? tiles.size : tiles.step) = n;
       (f == "--tiles" ? tiles_given : tile_step_given) = true;
     }
+    else if (f == "--contexts") {
+      if (!resident::parse_contexts(val(), contexts)) {
+        std::fprintf(stderr, "error: %s\n", resident::kContextsExpects);
+        return 2;
+      }
+      contexts_given = true;
+    }
     else if (f == "--regions") tiles.regions = val();
     else if (f == "--pool") tiles.pool = true;
     else if (f == "-h" || f == "--help") {
@@ -128,6 +136,10 @@ int main(int argc, char** argv) {
                 "                            every site inside any of them, each site once - one rate per annotation class.\n"
                 "                            Pools are numbered by first appearance; rows without a name are skipped.  Writes\n"
                 "                            results.txt (window = the pool's index, region = its name), raw.npy and pools.txt\n"
+                "       [--contexts LIST]    with --tiles or --regions: the methylation contexts to fit, a comma-separated subset\n"
+                "                            of CG,CHG,CHH [default: CG].  One: the run on that context's sites.  Several: every\n"
+                "                            methylome is parsed once and each context is a run of its own, its files in\n"
+                "                            <output-dir>/<CTX>/\n"
                 "       [--stream-sweep]     pedigrees too large for the LDS: read a fit's rows once per Nelder-Mead iteration\n"
                 "                            instead of once per cost evaluation; the same output files");
       return 0;
@@ -145,6 +157,16 @@ int main(int argc, char** argv) {
     return 2;
   }
   const bool tile_mode = tiles_given || tile_step_given || !tiles.regions.empty();
+  if (contexts_given) {
+    const char* refused = nullptr;
+    if (parse_host || sites_host) refused = "--contexts keeps the sites on the device: --parse host and --sites host do not apply";
+    else if (a.methylome.empty()) refused = "--contexts belongs to --methylome with --tiles or --regions, not to window directories";
+    else if (!tile_mode) refused = "--contexts belongs to --tiles and --regions, not to the gene windows of --genome";
+    if (refused) {
+      std::fprintf(stderr, "error: %s\n", refused);
+      return 2;
+    }
+  }
   if (tile_mode) {
     const char* refused = nullptr;
     if (tiles_given && !tiles.regions.empty()) refused = "--tiles and --regions exclude each other";
@@ -206,12 +228,24 @@ int main(int argc, char** argv) {
     dev.options.seed = seed;
     dev.stream_sweep = stream_sweep;
     if (tile_mode) {
-      const auto res = metaprofile::alphabeta_multiple_tiles(a, tiles);
-      std::printf("%s\n", res.out.results_txt.c_str());
-      std::ofstream(std::filesystem::path(a.output_dir) / "results.txt") << res.out.results_txt;
-      if (tiles.pool) std::ofstream(std::filesystem::path(a.output_dir) / "pools.txt") << res.pools_txt;
-      else std::ofstream(std::filesystem::path(a.output_dir) / "tiles.txt") << res.tiles_txt;
-      metaprofile::write_raw_npy(res.out, (std::filesystem::path(a.output_dir) / "raw.npy").string());
+      auto write = [&](const metaprofile::TilesOutput& res, const std::filesystem::path& dir) {
+        std::printf("%s\n", res.out.results_txt.c_str());
+        std::ofstream(dir / "results.txt") << res.out.results_txt;
+        if (tiles.pool) std::ofstream(dir / "pools.txt") << res.pools_txt;
+        else std::ofstream(dir / "tiles.txt") << res.tiles_txt;
+        metaprofile::write_raw_npy(res.out, (dir / "raw.npy").string());
+      };
+      if (resident::one_context(contexts)) {
+        write(metaprofile::alphabeta_multiple_tiles(a, tiles, contexts), a.output_dir);
+        return 0;
+      }
+      // every context a run of its own on one parse of every methylome, its files in <output-dir>/<CTX>/
+      metaprofile::alphabeta_multiple_tiles_contexts(a, tiles, contexts, [&](size_t c, const metaprofile::TilesOutput& res) {
+        const std::filesystem::path dir = std::filesystem::path(a.output_dir) / resident::kContextNames[c];
+        std::filesystem::create_directories(dir);
+        std::printf("Context %s\n", resident::kContextNames[c]);
+        write(res, dir);
+      });
       return 0;
     }
     if (in_memory) {

@@ -238,7 +238,7 @@ inline Inputs read_inputs(const std::string& nodelist, const std::string& edgeli
 // keep the bits of the unaligned build (a placeholder is not counted).
 inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
                                    std::vector<double>& dm, const std::vector<std::string>* texts = nullptr,
-                                   Align align = Align::None);
+                                   Align align = Align::None, unsigned contexts = 1u);
 // abn_codes_kernel_ms of this thread's last read_inputs_resident (merge records, merge inserted, pack, fold)
 inline double* resident_kernel_ms() {
   static thread_local double ms[4] = {0.0, 0.0, 0.0, 0.0};
@@ -462,13 +462,14 @@ inline Pedigree rows_from(const std::vector<PairTimes>& times, const std::vector
 inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, const std::string& edgelist,
                                                   double posterior_max_filter, bool gpu_pairwise, bool device_parse,
                                                   bool device_sites, const std::vector<std::string>* texts = nullptr,
-                                                  Align align = Align::None) {
+                                                  Align align = Align::None, unsigned contexts = 1u) {
   if (align != Align::None && !device_sites)
     throw Error(ABN_ERR_INVALID_ARG, std::string("--align ") + align_name(align) + " needs --sites device");
+  if (contexts != 1u && !device_sites) throw Error(ABN_ERR_INVALID_ARG, "--contexts needs --sites device");
   if (device_sites) {
     if (!device_parse || !gpu_pairwise) throw Error(ABN_ERR_INVALID_ARG, "--sites device needs --parse device");
     std::vector<double> dm;
-    const Inputs in = read_inputs_resident(nodelist, edgelist, posterior_max_filter, dm, texts, align);
+    const Inputs in = read_inputs_resident(nodelist, edgelist, posterior_max_filter, dm, texts, align, contexts);
     return {convert(in, dm), in.p0uu};
   }
   const Inputs in = read_inputs(nodelist, edgelist, posterior_max_filter, device_parse, texts);
@@ -495,9 +496,9 @@ inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, c
 
 inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, const std::string& edgelist,
                                                    double posterior_max_filter, bool gpu_pairwise,
-                                                   bool device_parse, bool device_sites, Align align) {
+                                                   bool device_parse, bool device_sites, Align align, unsigned contexts) {
   return detail::build_pedigree(nodelist, edgelist, posterior_max_filter, gpu_pairwise, device_parse, device_sites, nullptr,
-                                align);
+                                align, contexts);
 }
 
 // Pedigree::build for many (nodelist, edgelist) pairs — the windows of src/cli/metaprofile.rs:50-72.  With gpu_pairwise

@@ -5,6 +5,8 @@
 // every sample and the line that says so.  Included at the end of windows_extract.hpp.
 #pragma once
 
+#include <array>
+
 #include "windows_extract.hpp"
 
 namespace alphabeta {
@@ -24,17 +26,50 @@ inline std::vector<abn_sites*> pointers(const std::vector<windows::ResidentSites
 // The samples' methylomes in the order added, each parsed as it comes and its text dropped.  skip_lines: 1 passes over the
 // header row as Windows::extract does (src/windows.rs:303-306), 0 reads every line as the pedigree build does
 // (src/pedigree.rs:147-163); the invalid-status warnings appear in file order either way.
+// contexts: the methylation contexts whose lines are sites (1 CG, 2 CHG, 4 CHH; the reference reads CG alone).  Under
+// several, every methylome is still read and parsed once: split() partitions each on the device (abn_sites_split) and hands
+// out one handle set per context, each what a load under that context alone would hold.
 struct Samples {
   Device& dev;
   size_t skip_lines;
   std::vector<windows::ResidentSites> sites;
-  void add_text(const std::string& text) { sites.push_back(windows::parse_sites_resident(dev, text, skip_lines)); }
+  unsigned contexts = 1u;
+  void add_text(const std::string& text) {
+    sites.push_back(windows::parse_sites_resident(dev, text, skip_lines, /*slab_bytes=*/0, contexts));
+  }
   void add_file(const std::string& path) {  // a sampled node's file (src/pedigree.rs:147-150)
     if (!std::ifstream(path)) throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " + path);
     add_text(detail::read_file(path, "methylome"));
   }
   std::vector<abn_sites*> pointers() const { return resident::pointers(sites); }
+  // [c] = every sample's sites of context c, in the samples' order; empty for a context outside the mask
+  std::array<std::vector<windows::ResidentSites>, 3> split() const {
+    std::array<std::vector<windows::ResidentSites>, 3> out;
+    for (const auto& s : sites) {
+      abn_sites* kids[3] = {nullptr, nullptr, nullptr};
+      const int rc = abn_sites_split(s.get(), kids);
+      for (int c = 0; c < 3; ++c)
+        if (kids[c]) out[(size_t)c].emplace_back(kids[c]);
+      dev.check(rc, "abn_sites_split");
+    }
+    return out;
+  }
 };
+
+constexpr const char* kContextNames[3] = {"CG", "CHG", "CHH"};
+constexpr const char* kContextsExpects = "--contexts expects a comma-separated list of distinct names of CG, CHG, CHH";
+// "CG,CHH" -> 5; false: an unknown or repeated name, or none
+inline bool parse_contexts(const std::string& list, unsigned& mask) {
+  mask = 0;
+  for (const std::string& name : detail::split_any(list, ",")) {
+    int c = 0;
+    while (c < 3 && name != kContextNames[c]) ++c;
+    if (c == 3 || ((mask >> c) & 1u)) return false;
+    mask |= 1u << c;
+  }
+  return mask != 0;
+}
+inline bool one_context(unsigned mask) { return (mask & (mask - 1u)) == 0; }
 
 // One row per Align, indexed by its value: the create call for windows and for codes with the name Device::check puts into
 // an error's text, the call that reports what the alignment did, and the two ends of the per-sample line.
@@ -109,25 +144,32 @@ inline Handle::Handle(Device& dev, const abn_windows_params& p, const Genome& ge
 }  // namespace windows
 
 namespace detail {
-inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
-                                   std::vector<double>& dm, const std::vector<std::string>* texts, Align align) {
-  Inputs in = read_graph(nodelist, edgelist);
+// the sampled nodes' methylomes as resident handles, in the nodes' order, parsed under `contexts`
+inline resident::Samples load_resident(const Inputs& in, const std::vector<std::string>* texts, unsigned contexts) {
+  const size_t nn = in.nodes.size();
+  if (texts && texts->size() != nn) throw Error(ABN_ERR_INVALID_ARG, "one text per sampled node");
+  resident::Samples samples{default_device(), /*skip_lines=*/0, {}, contexts};
+  for (size_t i = 0; i < nn; ++i) {
+    if (texts) samples.add_text((*texts)[i]);
+    else samples.add_file(in.nodes[i].file);
+  }
+  return samples;
+}
+
+// read_inputs_resident behind the loader: `in` is the graph, sites[i] node i's methylome
+inline Inputs inputs_of_resident(Inputs in, const std::vector<windows::ResidentSites>& sites, double posterior_max_filter,
+                                 std::vector<double>& dm, Align align) {
   std::vector<Node>& nodes = in.nodes;
   const size_t nn = nodes.size();
-  if (texts && texts->size() != nn) throw Error(ABN_ERR_INVALID_ARG, "one text per sampled node");
   Device& dev = default_device();
-  resident::Samples samples{dev, /*skip_lines=*/0, {}};
   std::vector<std::string> names;
-  for (size_t i = 0; i < nn; ++i) {
-    names.push_back(nodes[i].file);
-    if (texts) samples.add_text((*texts)[i]);
-    else samples.add_file(nodes[i].file);
-  }
+  for (size_t i = 0; i < nn; ++i) names.push_back(nodes[i].file);
   Owned<abn_codes, abn_codes_destroy> codes;
   int32_t same_len = 1;
   if (nn > 0) {
     const resident::AlignMode& m = resident::align_mode(align);
-    dev.check(m.codes_create(dev.get(), posterior_max_filter, (int32_t)nn, samples.pointers().data(), codes.out()), m.codes_name);
+    dev.check(m.codes_create(dev.get(), posterior_max_filter, (int32_t)nn, resident::pointers(sites).data(), codes.out()),
+              m.codes_name);
     for (const std::string& line : resident::align_report(align, names, resident::align_counts(codes.get(), nn, align)))
       diag_printf("%s", line.c_str());
     resident_build_calls().fetch_add(1, std::memory_order_relaxed);
@@ -147,7 +189,7 @@ inline Inputs read_inputs_resident(const std::string& nodelist, const std::strin
   }
   // the reference's answer for samples of different length is per pair (:221-227): the host loop gives it
   for (size_t i = 0; i < nn; ++i) {
-    const windows::ResidentSites& mine = samples.sites[i];
+    const windows::ResidentSites& mine = sites[i];
     const size_t n = mine.size();
     std::vector<double> pm(n), ml(n);
     std::vector<uint8_t> status(n);
@@ -158,6 +200,33 @@ inline Inputs read_inputs_resident(const std::string& nodelist, const std::strin
   }
   dm = dmatrix_on_host(in, posterior_max_filter);
   return in;
+}
+
+inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
+                                   std::vector<double>& dm, const std::vector<std::string>* texts, Align align,
+                                   unsigned contexts) {
+  Inputs in = read_graph(nodelist, edgelist);
+  const resident::Samples samples = load_resident(in, texts, contexts);
+  return inputs_of_resident(std::move(in), samples.sites, posterior_max_filter, dm, align);
+}
+
+// Pedigree::build with --sites device once per context of a mask of SEVERAL contexts: every methylome is read and parsed
+// once and split on the device; [c] = the pedigree and p0uu of context c, what build_pedigree under that context alone
+// gives (an empty pedigree for a context outside the mask).
+inline std::array<std::pair<Pedigree, double>, 3> build_pedigrees_by_context(const std::string& nodelist,
+                                                                             const std::string& edgelist,
+                                                                             double posterior_max_filter, Align align,
+                                                                             unsigned contexts) {
+  const Inputs graph = read_graph(nodelist, edgelist);
+  const auto by_context = load_resident(graph, nullptr, contexts).split();
+  std::array<std::pair<Pedigree, double>, 3> out;
+  for (size_t c = 0; c < 3; ++c) {
+    if (!((contexts >> c) & 1u)) continue;
+    std::vector<double> dm;
+    const Inputs in = inputs_of_resident(graph, by_context[c], posterior_max_filter, dm, align);
+    out[c] = {convert(in, dm), in.p0uu};
+  }
+  return out;
 }
 }  // namespace detail
 }  // namespace alphabeta

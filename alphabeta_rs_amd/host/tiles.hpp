@@ -117,12 +117,34 @@ struct TilesOutput {
 // posterior_max_filter, name.  A tile without a column, with a sampled node that has no counted site, or with a sampled
 // pair that shares no compared site is reported and skipped; the others go on (src/cli/metaprofile.rs:64-65).  A graph
 // DMatrix::convert refuses ends the run.
-inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileArgs& tiles) {
+// The sampled nodes of a tile run and their methylomes: every line read (src/pedigree.rs:147-163) under the context mask,
+// the records left on the device
+struct TileSamples {
+  detail::Inputs graph;
+  std::vector<std::string> names;  // the methylome files' base names, in the nodes' order
+  std::vector<size_t> sample_of;
+  resident::Samples samples;
+};
+inline TileSamples load_tile_samples(const WindowArgs& args, unsigned contexts) {
   namespace fs = std::filesystem;
+  TileSamples s{detail::read_graph(args.nodes, args.edges), {}, {}, resident::Samples{default_device(), /*skip_lines=*/0, {}, contexts}};
+  if (s.graph.nodes.empty()) throw Error(ABN_ERR_INVALID_ARG, "the nodelist names no sampled node");
+  for (const auto& node : s.graph.nodes) {
+    s.sample_of.push_back(s.names.size());
+    s.names.push_back(resident::base_name(node.file));
+    s.samples.add_file((fs::path(args.methylome) / s.names.back()).string());
+  }
+  return s;
+}
+
+// alphabeta_multiple_tiles behind the loader: sites[i] = sampled node i's methylome
+inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tiles, const TileSamples& loaded,
+                                    const std::vector<windows::ResidentSites>& sites) {
   Device& dev = default_device();
-  const detail::Inputs graph = detail::read_graph(args.nodes, args.edges);
+  const detail::Inputs& graph = loaded.graph;
+  const std::vector<std::string>& names = loaded.names;
+  const std::vector<size_t>& sample_of = loaded.sample_of;
   const size_t nn = graph.nodes.size(), npairs = nn * (nn - 1) / 2;
-  if (nn == 0) throw Error(ABN_ERR_INVALID_ARG, "the nodelist names no sampled node");
   TileList list;
   RegionPools pools;
   if (!tiles.fixed()) {
@@ -136,19 +158,11 @@ inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileAr
     if (pools.names.empty()) throw Error(ABN_ERR_INVALID_ARG, "No region of " + tiles.regions + " has a name to pool by");
   }
   const char* unit = tiles.pool ? "pool" : "tile";
-  // every sampled node's methylome, every line read (src/pedigree.rs:147-163), its records left on the device
-  resident::Samples samples{dev, /*skip_lines=*/0, {}};
-  std::vector<std::string> names;
-  std::vector<size_t> sample_of;
-  for (const auto& node : graph.nodes) {
-    sample_of.push_back(names.size());
-    names.push_back(resident::base_name(node.file));
-    samples.add_file((fs::path(args.methylome) / names.back()).string());
-  }
   Owned<abn_tiles, abn_tiles_destroy> th;
-  dev.check(abn_tiles_create(dev.get(), args.posterior_max_filter, (int32_t)args.align, (int32_t)nn, samples.pointers().data(), th.out()),
+  dev.check(abn_tiles_create(dev.get(), args.posterior_max_filter, (int32_t)args.align, (int32_t)nn,
+                             resident::pointers(sites).data(), th.out()),
             "abn_tiles_create");
-  for (const std::string& line : resident::align_report(args.align, names, resident::align_counts(th.get(), samples.sites)))
+  for (const std::string& line : resident::align_report(args.align, names, resident::align_counts(th.get(), sites)))
     std::fputs(line.c_str(), stdout);
   if (tiles.fixed())
     dev.check(abn_tiles_set_fixed(th.get(), tiles.size, tiles.step), "abn_tiles_set_fixed");
@@ -218,6 +232,23 @@ inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileAr
     res.tiles_txt += std::to_string(t) + ";" + chromosome_name(list.chromosome[t]) + ";" + std::to_string(list.start[t]) + ";" +
                      std::to_string(list.end[t]) + ";" + std::to_string(count[t]) + ";" + (fitted[t] ? "1" : "0") + "\n";
   return res;
+}
+
+// contexts: ONE methylation context (1 CG, the reference's; 2 CHG; 4 CHH) — the run on that context's sites
+inline TilesOutput alphabeta_multiple_tiles(const WindowArgs& args, const TileArgs& tiles, unsigned contexts = 1u) {
+  const TileSamples loaded = load_tile_samples(args, contexts);
+  return tiles_of_samples(args, tiles, loaded, loaded.samples.sites);
+}
+
+// ... SEVERAL contexts: every methylome is read and parsed once and split on the device (abn_sites_split); each context is
+// then built and fitted as the run under that context alone is — its own tiles, every tile's random stream at its index
+// among that context's tiles — so each result is that run's, bit for bit.  done(c, result) as each context finishes.
+template <class Done>
+inline void alphabeta_multiple_tiles_contexts(const WindowArgs& args, const TileArgs& tiles, unsigned contexts, Done done) {
+  const TileSamples loaded = load_tile_samples(args, contexts);
+  const auto by_context = loaded.samples.split();
+  for (size_t c = 0; c < 3; ++c)
+    if ((contexts >> c) & 1u) done(c, tiles_of_samples(args, tiles, loaded, by_context[c]));
 }
 
 }  // namespace metaprofile

@@ -107,13 +107,23 @@ struct FullSite {  // the fields of MethylationSite (src/methylation_site.rs:32-
   double posteriormax;
   uint32_t status_numeric;
   double meth_lvl;
+  uint8_t context;  // 0 CG, 1 CHG, 2 CHH; 3: a row without a context field
 };
+
+// field 3 of the 9-, 10- and 11-field formats -> its context code when the mask `contexts` (1 CG, 2 CHG, 4 CHH) holds
+// it, else -1: the line is no site
+inline int context_in_mask(const std::string& field, unsigned contexts) {
+  const int code = field == "CG" ? 0 : (field == "CHG" ? 1 : (field == "CHH" ? 2 : -1));
+  return code >= 0 && ((contexts >> code) & 1u) ? code : -1;
+}
 
 // MethylationSite::from_methylome_file_line (src/methylation_site.rs:146-362, without --invert): detail::parse_site with
 // the coordinates kept.  A single location gets end = start + 1; the 4-field rows (chromatin state, bigwig) have an
-// Unknown strand, posterior 0, status U, level 0.
-inline bool parse_site_full(const std::string& line, FullSite& out) {
+// Unknown strand, posterior 0, status U, level 0, and no context: every mask accepts them.  contexts: the mask of the
+// contexts whose lines are sites; the reference reads CG alone (:150,193), the default.
+inline bool parse_site_full(const std::string& line, FullSite& out, unsigned contexts = 1u) {
   const auto tab = detail::split_any(line, "\t");
+  const int ctx = tab.size() >= 9 && tab.size() <= 11 ? context_in_mask(tab[3], contexts) : -1;
   auto cg = [&](size_t chrom, size_t s0, int s1, size_t strand, size_t cm, size_t ct, size_t pm, size_t st, size_t ml) {
     FullSite s;
     uint32_t u;
@@ -125,15 +135,16 @@ inline bool parse_site_full(const std::string& line, FullSite& out) {
     if (tab[st].empty() || !detail::parse_f64(tab[ml], s.meth_lvl)) return false;
     s.strand = tab[strand] == "+" ? Sense : Antisense;
     s.status_numeric = detail::status_from(tab[st][0]);
+    s.context = (uint8_t)ctx;
     out = s;
     return true;
   };
-  if (tab.size() == 9 && tab[3] == "CG" && cg(0, 1, -1, 2, 4, 5, 6, 7, 8)) return true;    // first_format
-  if (tab.size() == 10 && tab[3] == "CG" && cg(0, 1, -1, 2, 4, 5, 6, 7, 8)) return true;   // second_format
-  if (tab.size() == 11 && tab[3] == "CG" && cg(0, 1, 2, 5, 6, 7, 8, 9, 10)) return true;   // third_format
+  if (tab.size() == 9 && ctx >= 0 && cg(0, 1, -1, 2, 4, 5, 6, 7, 8)) return true;    // first_format
+  if (tab.size() == 10 && ctx >= 0 && cg(0, 1, -1, 2, 4, 5, 6, 7, 8)) return true;   // second_format
+  if (tab.size() == 11 && ctx >= 0 && cg(0, 1, 2, 5, 6, 7, 8, 9, 10)) return true;   // third_format
   const auto ws = detail::split_any(line, "\t ");
   if (ws.size() == 4) {
-    FullSite s{0, 0, 0, Unknown, 0.0, 0, 0.0};
+    FullSite s{0, 0, 0, Unknown, 0.0, 0, 0.0, 3};
     if (parse_chromosome_key(ws[0], s.chromosome) && detail::parse_u32(ws[1], s.start) && detail::parse_u32(ws[2], s.end)) {
       out = s;
       return true;
@@ -146,12 +157,12 @@ inline bool parse_site_full(const std::string& line, FullSite& out) {
 // (src/windows.rs:303-306 skips the header row, src/pedigree.rs:147-163 skips nothing) — parsed on the host.
 // line_numbers (nullable): every site's line, counted from 0 in the text.
 inline std::vector<FullSite> parse_sites_host(const std::string& text, size_t skip_lines = 1,
-                                              std::vector<int64_t>* line_numbers = nullptr) {
+                                              std::vector<int64_t>* line_numbers = nullptr, unsigned contexts = 1u) {
   std::vector<FullSite> out;
   const auto lines = lines_of(text);
   for (size_t li = skip_lines; li < lines.size(); ++li) {
     FullSite s;
-    if (!parse_site_full(lines[li], s)) continue;
+    if (!parse_site_full(lines[li], s, contexts)) continue;
     out.push_back(s);
     if (line_numbers) line_numbers->push_back((int64_t)li);
   }
@@ -230,10 +241,11 @@ struct ResidentSites : Owned<abn_sites, abn_sites_destroy> {
 // parse_site_full and the accepted ones go back up (abn_sites_insert).  The invalid-status warnings of the flagged
 // records and of the deferred lines are printed in one walk in file order, as parse_sites_device prints them.
 inline ResidentSites parse_sites_resident(Device& dev, const std::string& text, size_t skip_lines = 1,
-                                          int64_t slab_bytes = 0) {
+                                          int64_t slab_bytes = 0, unsigned contexts = 1u) {
   abn_sites_params p{};
   p.slab_bytes = slab_bytes;
   p.skip_lines = (int32_t)skip_lines;
+  p.contexts = contexts == 1u ? 0 : (int32_t)contexts;
   abn_sites* h = nullptr;
   dev.check(abn_sites_parse_dev(dev.get(), text.data(), (int64_t)text.size(), &p, &h), "abn_sites_parse_dev");
   ResidentSites out(h);
@@ -254,12 +266,12 @@ inline ResidentSites parse_sites_resident(Device& dev, const std::string& text, 
     std::string s = text.substr(b, e - b);
     if (!s.empty() && s.back() == '\r') s.pop_back();
     FullSite again;
-    parse_site_full(s, again);
+    parse_site_full(s, again, contexts);
   };
   std::vector<int64_t> line;
   std::vector<int32_t> chrom;
   std::vector<uint32_t> start, end;
-  std::vector<uint8_t> strand, status;
+  std::vector<uint8_t> strand, status, context;
   std::vector<double> pm, ml;
   size_t i = 0, j = 0;
   while (i < flagged.size() || j < dline.size()) {
@@ -268,7 +280,7 @@ inline ResidentSites parse_sites_resident(Device& dev, const std::string& text, 
       continue;
     }
     FullSite s;
-    if (parse_site_full(text.substr((size_t)doff[j], (size_t)dlen[j]), s)) {
+    if (parse_site_full(text.substr((size_t)doff[j], (size_t)dlen[j]), s, contexts)) {
       line.push_back(dline[j]);
       chrom.push_back(s.chromosome);
       start.push_back(s.start);
@@ -277,12 +289,13 @@ inline ResidentSites parse_sites_resident(Device& dev, const std::string& text, 
       pm.push_back(s.posteriormax);
       status.push_back((uint8_t)s.status_numeric);
       ml.push_back(s.meth_lvl);
+      context.push_back(s.context);
     }
     ++j;
   }
-  dev.check(abn_sites_insert(h, (int64_t)line.size(), line.data(), chrom.data(), start.data(), end.data(), strand.data(),
-                             pm.data(), status.data(), ml.data()),
-            "abn_sites_insert");
+  dev.check(abn_sites_insert_ctx(h, (int64_t)line.size(), line.data(), chrom.data(), start.data(), end.data(),
+                                 strand.data(), pm.data(), status.data(), ml.data(), context.data()),
+            "abn_sites_insert_ctx");
   return out;
 }
 

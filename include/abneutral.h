@@ -422,13 +422,16 @@ typedef struct abn_sites_params {
                           slab of its own); bounds the device memory of a call.  0: 64 MiB; at most 1 GiB */
   int32_t skip_lines;  /* leading lines not parsed: 1 for the loop of Windows::extract (`lines.skip(1)`,
                           src/windows.rs:303-306), 0 for that of Pedigree::build (src/pedigree.rs:147-163) */
-  int32_t reserved;    /* 0 */
+  int32_t contexts;    /* the methylation contexts whose lines are sites, as a mask: 1 CG, 2 CHG, 4 CHH (field 3 of the
+                          9-, 10- and 11-field formats).  0: CG alone, as the reference (src/methylation_site.rs:150,193);
+                          the 4-field rows have no context and are sites under every mask */
 } abn_sites_params;
 /* Replaces the line loops of Windows::extract (src/windows.rs:303-338) and Pedigree::build (src/pedigree.rs:147-163)
  * up to and including from_methylome_file_line (src/methylation_site.rs:146-362).  text: n_bytes bytes of HOST memory
  * (no terminator needed; "\n" or "\r\n" ends a line, a last line without one is a line).  params NULL: slab_bytes 0,
  * skip_lines 1.  The results are on the host when the call returns; *out holds them until abn_sites_destroy.
- * ABN_ERR_INVALID_ARG: null pointers, n_bytes < 0, slab_bytes outside [0, 2^30], skip_lines < 0, a line of over 2 GiB. */
+ * ABN_ERR_INVALID_ARG: null pointers, n_bytes < 0, slab_bytes outside [0, 2^30], skip_lines < 0, contexts outside
+ * [0, 7], a line of over 2 GiB. */
 int abn_sites_parse(abn_ctx* ctx, const char* text, int64_t n_bytes, const abn_sites_params* params, abn_sites** out);
 int abn_sites_destroy(abn_sites* h);
 /* the counts behind src/windows.rs:303-338: accepted sites, deferred lines, lines of the text (skipped ones included);
@@ -464,6 +467,30 @@ int abn_sites_flagged(const abn_sites* h, int64_t* n, int64_t* line);
 int abn_sites_insert(abn_sites* h, int64_t n, const int64_t* line, const int32_t* chromosome, const uint32_t* start,
                      const uint32_t* end, const uint8_t* strand, const double* posteriormax, const uint8_t* status,
                      const double* meth_lvl);
+/* ---- methylation contexts: one parse, one resident handle per context
+ * A handle parsed with abn_sites_params.contexts keeps every site's CONTEXT CODE — CG 0, CHG 1, CHH 2, and 3 for the
+ * 4-field rows, which have none — beside its record (two bits of the device records' meta word).
+ * abn_sites_context: *mask = the contexts the handle was parsed under (1 for contexts 0), context [n_sites] = every
+ * site's code in the order of abn_sites_fetch; either may be NULL.  Both forms. */
+int abn_sites_context(const abn_sites* h, int32_t* mask, uint8_t* context);
+/* abn_sites_insert with every record's context code.  abn_sites_insert is this call with every code 0, and is refused
+ * (ABN_ERR_INVALID_ARG) with n > 0 on a handle whose mask is not CG alone.
+ * ABN_ERR_INVALID_ARG: as abn_sites_insert, and a code above 3 or a code 0..2 outside the handle's mask. */
+int abn_sites_insert_ctx(abn_sites* h, int64_t n, const int64_t* line, const int32_t* chromosome, const uint32_t* start,
+                         const uint32_t* end, const uint8_t* strand, const double* posteriormax, const uint8_t* status,
+                         const double* meth_lvl, const uint8_t* context);
+/* The stable partition of a RESIDENT handle by context, on the device: for every context c of h's mask out3[c] becomes a
+ * new, ordinary resident handle of mask 1 << c (every other entry NULL) that holds exactly the records of code c or 3, in
+ * file order with their file lines — what abn_sites_parse_dev of the same text with contexts = 1 << c, its deferred lines
+ * inserted, holds.  Its chunks keep their slabs' lines; its inserted records and flagged lines are the parent's of that
+ * membership; it has no deferred lines.  Only the record counts per (slab, context) come to the host.  h is not consumed;
+ * every child is destroyed with abn_sites_destroy (before its context).
+ * ABN_ERR_INVALID_ARG: null pointers, a host-form handle, a handle with deferred lines on which abn_sites_insert(_ctx)
+ * was never called. */
+int abn_sites_split(const abn_sites* h, abn_sites** out3);
+/* double[2]: the HIP-event times of abn_sites_split's count and scatter kernels — of the last split of h, or of the
+ * split that made h; 0, 0 otherwise */
+int abn_sites_split_ms(const abn_sites* h, double* ms2);
 /* abn_windows_create_sites fed from RESIDENT handles (src/windows.rs:303-339 whole, for n_samples methylomes): sample s is
  * samples[s]; its records and inserted lines are merged in file order on the device into the arrays the gene choice and
  * the placement read — chromosome, start, end, strand, code = status | 0x80 when posteriormax < posterior_max_filter
