@@ -47,7 +47,7 @@ ABN_HOST_DEVICE inline uint8_t merge_byte(uint32_t status, double posteriormax, 
 ABN_HOST_DEVICE inline long long codes_write_record(const MergeChunk& c, long long i, const long long* inserted_line,
                                                     long long n_inserted, double filter, const CodesOut& out) {
   const long long d = merge_dest_record(c, i, inserted_line, n_inserted);
-  out.code[d] = merge_byte((c.meta[i] >> 20) & 0xfu, c.posteriormax[i], filter);
+  out.code[d] = merge_byte(meta_status(c.meta[i]), c.posteriormax[i], filter);
   out.level[d] = c.meth_lvl[i];
   return d;
 }

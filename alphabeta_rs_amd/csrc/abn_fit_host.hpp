@@ -1,7 +1,7 @@
 // What the fit path's translation units share on the host — abn_context.hip (topology, options, the context), abn_api.hip
 // (the kernel table, the launchers, the one-shot entries) and abn_plan.hip (the device-resident plan and the drop-in
-// entries on it).  Declarations, with the templates and the copy-out helper that must be visible where they are used, and
-// no kernel header: abn_api.hip alone includes abn_device.hpp.  Not part of the C-ABI.
+// entries on it).  Declarations, with the templates that must be visible where they are used (the copy helpers upload and
+// to_host: abn_host.hpp), and no kernel header: abn_api.hip alone includes abn_device.hpp.  Not part of the C-ABI.
 #pragma once
 #include "abn_host.hpp"
 #include "abn_common.hpp"
@@ -27,25 +27,6 @@ int build_topology(const double* rows, int n, int stride, Topology& t);
 int upload_topology(abn_ctx* c, const Topology& t, DevTopology& d);
 // the observed divergences of a four-column pedigree
 std::vector<double> column3(const double* pedigree, int n);
-
-// allocate `count` elements and copy them from the host, on the context's stream
-template <class T>
-int upload(abn_ctx* c, DevBuf<T>& buf, const T* host, size_t count) {
-  HIPCHK(c, buf.alloc(count));
-  HIPCHK(c, hipMemcpyAsync(buf.p, host, buf.bytes(), hipMemcpyHostToDevice, c->stream));
-  return ABN_OK;
-}
-// ... and back: `bytes` from the device to dst on the context's stream, nothing waited for; a null dst (an output the
-// caller does not want) copies nothing
-inline int to_host(abn_ctx* c, void* dst, const void* src, size_t bytes) {
-  if (!dst) return ABN_OK;
-  HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-  return ABN_OK;
-}
-template <class T>
-int to_host(abn_ctx* c, void* dst, const DevBuf<T>& src) {
-  return to_host(c, dst, src.p, src.bytes());
-}
 
 // the topology fields every kernel's argument struct starts with
 template <class Args>

@@ -30,20 +30,15 @@ static int genes_upload(abn_genes* h, int32_t n_lists, const int32_t* list_chrom
     cnt[cell] = (uint32_t)(list_offset[l + 1] - list_offset[l]);
     for (int64_t g = list_offset[l]; g < list_offset[l + 1]; ++g) chrom[(size_t)g] = (uint16_t)list_chromosome[l];
   }
-  HIPCHK(c, h->list_offset.alloc(cells));
-  HIPCHK(c, h->list_count.alloc(cells));
-  HIPCHK(c, h->start.alloc(std::max<size_t>(G, 1)));
+  int rc;
+  if ((rc = upload(c, h->list_offset, off.data(), cells)) || (rc = upload(c, h->list_count, cnt.data(), cells))) return rc;
+  HIPCHK(c, h->start.alloc(std::max<size_t>(G, 1)));  // (at least one element each, so that no pointer is null)
   HIPCHK(c, h->end.alloc(std::max<size_t>(G, 1)));
   HIPCHK(c, h->chromosome.alloc(std::max<size_t>(G, 1)));
   HIPCHK(c, h->strand.alloc(std::max<size_t>(G, 1)));
-  HIPCHK(c, hipMemcpyAsync(h->list_offset.p, off.data(), cells * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h->list_count.p, cnt.data(), cells * 4, hipMemcpyHostToDevice, c->stream));
-  if (G > 0) {
-    HIPCHK(c, hipMemcpyAsync(h->start.p, gene_start, G * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h->end.p, gene_end, G * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h->chromosome.p, chrom.data(), G * 2, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h->strand.p, gene_strand, G, hipMemcpyHostToDevice, c->stream));
-  }
+  if (G > 0 && ((rc = to_device(c, h->start.p, gene_start, G * 4)) || (rc = to_device(c, h->end.p, gene_end, G * 4)) ||
+                (rc = to_device(c, h->chromosome.p, chrom.data(), G * 2)) || (rc = to_device(c, h->strand.p, gene_strand, G))))
+    return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the staging vectors go on return
   return ABN_OK;
 }
@@ -129,16 +124,14 @@ int abn::genes_choose_dev(abn_genes* h, const abn_gene_rule* rule, int32_t n_sam
   DevBuf<int> dblock0, dbad;
   DevBuf<uint32_t> dF, dcarry;
   DevBuf<uint16_t> dnext, dlast, dentry;
-  HIPCHK(c, dblocks.alloc(NB));
-  HIPCHK(c, dblock0.alloc((size_t)n + 1));
+  if (int rc = upload(c, dblocks, blocks.data(), NB)) return rc;
+  if (int rc = upload(c, dblock0, block0.data(), (size_t)n + 1)) return rc;
   HIPCHK(c, dbad.alloc((size_t)n));
   HIPCHK(c, dF.alloc((size_t)S));
   HIPCHK(c, dnext.alloc((size_t)S));
   HIPCHK(c, dlast.alloc((size_t)S));
   HIPCHK(c, dentry.alloc(NB));
   HIPCHK(c, dcarry.alloc(NB));
-  HIPCHK(c, hipMemcpyAsync(dblocks.p, blocks.data(), dblocks.bytes(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dblock0.p, block0.data(), dblock0.bytes(), hipMemcpyHostToDevice, c->stream));
   Events<4> ev;
   if (kernel_ms)
     if (int rc = ev.create(c)) return rc;
@@ -160,7 +153,7 @@ int abn::genes_choose_dev(abn_genes* h, const abn_gene_rule* rule, int32_t n_sam
   HIPCHK(c, hipGetLastError());
   if (int rc = mark(3)) return rc;
   std::vector<int> bad((size_t)n, 0);
-  HIPCHK(c, hipMemcpyAsync(bad.data(), dbad.p, dbad.bytes(), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = to_host(c, bad.data(), dbad)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch buffers are freed on return
   if (kernel_ms)
     for (int k = 0; k < 3; ++k)
@@ -208,27 +201,21 @@ extern "C" int abn_genes_choose(abn_genes* h, const abn_gene_rule* rule, int32_t
   DevBuf<int32_t> dchrom;
   DevBuf<uint32_t> dstart, dend, dgs, dge;
   DevBuf<uint8_t> dstrand, dflags;
-  HIPCHK(c, dchrom.alloc(S));
-  HIPCHK(c, dstart.alloc(S));
-  HIPCHK(c, dend.alloc(S));
-  HIPCHK(c, dstrand.alloc(S));
+  int rc;
+  if ((rc = upload(c, dchrom, chromosome, S)) || (rc = upload(c, dstart, start, S)) || (rc = upload(c, dend, end, S)) ||
+      (rc = upload(c, dstrand, strand, S)))
+    return rc;
   HIPCHK(c, dgs.alloc(S));
   HIPCHK(c, dge.alloc(S));
   HIPCHK(c, dflags.alloc(S));
-  HIPCHK(c, hipMemcpyAsync(dchrom.p, chromosome, S * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dstart.p, start, S * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dend.p, end, S * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dstrand.p, strand, S, hipMemcpyHostToDevice, c->stream));
   try {
-    if (int rc = genes_choose_dev(h, rule, n_samples, site_offset, dchrom.p, dstart.p, dend.p, dstrand.p, dgs.p, dge.p,
-                                  dflags.p, kernel_ms))
+    if ((rc = genes_choose_dev(h, rule, n_samples, site_offset, dchrom.p, dstart.p, dend.p, dstrand.p, dgs.p, dge.p,
+                               dflags.p, kernel_ms)))
       return rc;
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
   }
-  HIPCHK(c, hipMemcpyAsync(gene_start, dgs.p, S * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(gene_end, dge.p, S * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(flags, dflags.p, S, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = to_host(c, gene_start, dgs)) || (rc = to_host(c, gene_end, dge)) || (rc = to_host(c, flags, dflags))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return ABN_OK;
 }

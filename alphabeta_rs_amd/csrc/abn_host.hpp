@@ -2,8 +2,9 @@
 // abn_context.hip and abn_plan.hip, which share abn_fit_host.hpp on top of this; abn_pairwise.hip, abn_windows.hip,
 // abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip, abn_tiles.hip,
 // abn_resident.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
-// events of a call, the shell of the windows, codes and tiles handles (created, destroyed, their packed matrix read), and
-// what the consumers of resident methylomes share (abn_resident.hip).  Not part of the C-ABI (include/abneutral.h is).
+// events of a call, the copies on the context's stream (upload, to_device, to_host), the shell of the windows, codes and
+// tiles handles (created, destroyed, their packed matrix read), and what the consumers of resident methylomes share
+// (abn_resident.hip).  Not part of the C-ABI (include/abneutral.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -257,6 +258,29 @@ int handle_packed(H* h, uint8_t* host_out) {
 }
 
 namespace abn {
+// The copies on the context's stream, nothing waited for.  upload: `count` elements allocated and sent up from the host
+template <class T>
+int upload(abn_ctx* c, DevBuf<T>& buf, const T* host, size_t count) {
+  HIPCHK(c, buf.alloc(count));
+  HIPCHK(c, hipMemcpyAsync(buf.p, host, buf.bytes(), hipMemcpyHostToDevice, c->stream));
+  return ABN_OK;
+}
+// ... to_device: `bytes` sent up into a buffer that stands
+inline int to_device(abn_ctx* c, void* dst, const void* src, size_t bytes) {
+  HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+  return ABN_OK;
+}
+// ... and to_host: `bytes` from the device to dst; a null dst (an output the caller does not want) copies nothing
+inline int to_host(abn_ctx* c, void* dst, const void* src, size_t bytes) {
+  if (!dst) return ABN_OK;
+  HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  return ABN_OK;
+}
+template <class T>
+int to_host(abn_ctx* c, void* dst, const DevBuf<T>& src) {
+  return to_host(c, dst, src.p, src.bytes());
+}
+
 // abn_analyze.hip, for abn_plan_analyze (abn_plan.hip): the analysis (abn_analyze.hpp) of a device-resident table
 // raw[W x B x 7] on the context's stream, results to the host; returns after completion, ABN_ERR_NO_FINITE_FIT as
 // abn_analyze_batch.

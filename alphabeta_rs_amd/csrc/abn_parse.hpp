@@ -3,6 +3,9 @@
 // MethylationSite::from_methylome_file_line (src/methylation_site.rs:146-362, without --invert).  Plain arithmetic on
 // registers, no array, no HIP header: the kernel, the host library (host_capi.cpp) and the CPU tests
 // (tests/test_parse_cpu.py) all include this file as it is.
+// Beside it the arrays the device keeps its records in (ParseRecords, ParseDeferred) and the fields of their `meta` word,
+// for everything that reads or writes them: abn_parse_kernels.hpp, abn_sites_merge.hpp, abn_codes.hpp, abn_sites_split.hpp
+// and abn_sites.hip.
 //
 // The one thing the device does not decide in general is str::parse::<f64> (strtod on the host): abn_parse_f64 gives a
 // value only where one IEEE operation is certain to give strtod's bits, says "rejected" only where strtod is certain to
@@ -26,9 +29,6 @@ enum ParseLine : int { kLineNone = 0, kLineSite = 1, kLineDeferred = 2 };
 // holds bit 1 << code per accepted context; a row without a context is accepted under every mask.
 enum ParseContext : uint32_t { kCtxCG = 0, kCtxCHG = 1, kCtxCHH = 2, kCtxNone = 3 };
 constexpr uint32_t kContextsCG = 1u, kContextsAll = 7u;
-// where a device record's `meta` word keeps the code: above status_flag << 24, whose readers take four bits
-constexpr int kMetaContextShift = 28;
-ABN_HOST_DEVICE inline uint32_t meta_context(uint32_t meta) { return (meta >> kMetaContextShift) & 3u; }
 
 // field 3 -> its code; kCtxNone: none of CG, CHG, CHH (such a line is no site)
 ABN_HOST_DEVICE inline uint32_t abn_parse_context(const unsigned char* p, const unsigned char* e) {
@@ -46,6 +46,34 @@ struct ParsedSite {  // windows::FullSite, and whether status_from would print i
   uint32_t status_flag;  // 1: the status byte is none of M, I, U (parsed as U, src/methylation_site.rs:107-112)
   double posteriormax, meth_lvl;
   uint32_t context;  // ParseContext
+};
+
+// A device record's `meta` word: chromosome | strand << 16 | status << 20 | status_flag << 24 | context << 28 — sixteen
+// bits, three fields of four and one of two.  The one writer is meta_pack; every reader takes its field through these.
+constexpr int kMetaContextShift = 28;
+ABN_HOST_DEVICE inline int32_t meta_chromosome(uint32_t meta) { return (int32_t)(meta & 0xffffu); }
+ABN_HOST_DEVICE inline uint32_t meta_strand(uint32_t meta) { return (meta >> 16) & 0xfu; }
+ABN_HOST_DEVICE inline uint32_t meta_status(uint32_t meta) { return (meta >> 20) & 0xfu; }
+ABN_HOST_DEVICE inline uint32_t meta_status_flag(uint32_t meta) { return (meta >> 24) & 0xfu; }
+ABN_HOST_DEVICE inline uint32_t meta_context(uint32_t meta) { return (meta >> kMetaContextShift) & 3u; }
+ABN_HOST_DEVICE inline uint32_t meta_pack(const ParsedSite& s) {
+  return (uint32_t)s.chromosome | s.strand << 16 | s.status << 20 | s.status_flag << 24 | s.context << kMetaContextShift;
+}
+
+// The device's records of one slab (abn_parse_kernels.hpp writes them, abn_sites_split.hpp copies them): struct of arrays,
+// one entry per accepted site
+struct ParseRecords {
+  uint32_t* line;  // the line's index in the slab
+  uint32_t* meta;  // (above)
+  uint32_t* start;
+  uint32_t* end;
+  double* posteriormax;
+  double* meth_lvl;
+};
+struct ParseDeferred {  // one entry per deferred line
+  uint32_t* line;
+  uint32_t* offset;  // the line's first byte in the slab
+  uint32_t* length;  // without the line end
 };
 
 // str::parse::<u32> (detail::parse_u32): an optional '+', at least one digit, nothing else, at most 4294967295

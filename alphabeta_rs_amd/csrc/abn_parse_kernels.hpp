@@ -124,22 +124,7 @@ abn_parse_index_kernel(const uint4* __restrict__ text, uint32_t n_pieces, const 
       if (((w[d] >> (8 * k)) & 0xffu) == 0x0au) line_begin[++rank] = piece * kParsePieceBytes + 4 * d + k + 1;
 }
 
-struct ParseRecords {  // struct of arrays, one entry per accepted site
-  uint32_t* line;      // the line's index in the slab
-  uint32_t* meta;      // chromosome | strand << 16 | status << 20 | status_flag << 24 | context << 28 (four bits each
-                       // from bit 16 on; every reader masks the field it takes)
-  uint32_t* start;
-  uint32_t* end;
-  double* posteriormax;
-  double* meth_lvl;
-};
-struct ParseDeferred {  // one entry per deferred line
-  uint32_t* line;
-  uint32_t* offset;  // the line's first byte in the slab
-  uint32_t* length;  // without the line end
-};
-
-// K3.  The slab has n_lines lines, n_newlines of them ended by '\n' (line_begin has n_newlines + 1 entries); the lines
+// K3.  (ParseRecords, ParseDeferred and the meta word: abn_parse.hpp.)  The slab has n_lines lines, n_newlines of them ended by '\n' (line_begin has n_newlines + 1 entries); the lines
 // from first_line on are parsed, kParseRun per workgroup.  Line l is [begin(l), begin(l + 1) - 1), where begin(l) for
 // l > n_newlines is n_bytes + 1 (the last line has no '\n').  A run whose bytes exceed the stage is staged in several
 // cuts of whole lines; a line that alone exceeds it is deferred unread.  The run's records go to rec / def at
@@ -195,8 +180,7 @@ abn_parse_lines_kernel(const uint4* __restrict__ text, uint32_t n_bytes, const u
   if (cls == kLineSite) {
     const size_t k = slot0 + (ranks & 0xffffu);
     rec.line[k] = line0 + threadIdx.x;
-    rec.meta[k] = (uint32_t)site.chromosome | site.strand << 16 | site.status << 20 | site.status_flag << 24 |
-                  site.context << kMetaContextShift;
+    rec.meta[k] = meta_pack(site);
     rec.start[k] = site.start;
     rec.end[k] = site.end;
     rec.posteriormax[k] = site.posteriormax;

@@ -1,10 +1,14 @@
 // abn_sites_*: methylome text -> site records on the device (src/methylation_site.rs:146-362 for every line of a file,
 // the loops of src/windows.rs:303-338 and src/pedigree.rs:138-178 in front of it).  Kernels: abn_parse_kernels.hpp; the
-// line parser they share with the host: abn_parse.hpp.  The resident form (abn_sites_parse_dev, abn_sites_insert) keeps the
-// records on the device for abn_windows_create_parsed (abn_windows.hip; its merge kernels: abn_sites_merge.hpp) and for
-// abn_codes_create_parsed (abn_codes.hip; its reduced merge kernels: abn_codes.hpp).  A handle parsed under a mask of
-// several contexts is partitioned into one ordinary resident handle per context by abn_sites_split (its kernels:
-// abn_sites_split.hpp).
+// line parser they share with the host, the device's record arrays and their meta word: abn_parse.hpp.  The resident form
+// (abn_sites_parse_dev, abn_sites_insert) keeps the records on the device for abn_windows_create_parsed (abn_windows.hip;
+// its merge kernels: abn_sites_merge.hpp) and for abn_codes_create_parsed (abn_codes.hip; its reduced merge kernels:
+// abn_codes.hpp).  A handle parsed under a mask of several contexts is partitioned into one ordinary resident handle per
+// context by abn_sites_split (its kernels: abn_sites_split.hpp).
+//
+// In this file: a site as the host reports it (SiteRecord, SiteOut, SiteIn, SiteColumns); the records on the device
+// (RecordBufs, SiteChunk, InsertedBufs); the handle; the parse; what a handle reports; the insert; the split; the merge
+// launches of the builders.
 #include "abn_host.hpp"
 #include "abn_parse_kernels.hpp"
 #define ABN_SITES_MERGE_KERNELS
@@ -20,6 +24,113 @@ constexpr int64_t kSitesDefaultSlab = (int64_t)64 << 20, kSitesMaxSlab = (int64_
 
 namespace {
 
+// ---- a site on the host: the ten columns of abn_sites_fetch and abn_sites_context
+struct SiteRecord {
+  int64_t line;
+  int32_t chromosome;
+  uint32_t start, end;
+  uint8_t strand;
+  double posteriormax;
+  uint8_t status, status_flag;
+  double meth_lvl;
+  uint8_t context;
+};
+
+// a device record of the slab that begins at file line line0
+SiteRecord site_decode(int64_t line0, uint32_t line, uint32_t meta, uint32_t start, uint32_t end, double pm, double ml) {
+  return SiteRecord{line0 + (int64_t)line, meta_chromosome(meta), start, end, (uint8_t)meta_strand(meta), pm,
+                    (uint8_t)meta_status(meta), (uint8_t)meta_status_flag(meta), ml, (uint8_t)meta_context(meta)};
+}
+
+struct SiteOut {  // where a caller wants the columns: null, not wanted
+  int64_t* line;
+  int32_t* chromosome;
+  uint32_t *start, *end;
+  uint8_t* strand;
+  double* posteriormax;
+  uint8_t *status, *status_flag;
+  double* meth_lvl;
+  uint8_t* context;
+  void put(size_t k, const SiteRecord& r) const {
+    if (line) line[k] = r.line;
+    if (chromosome) chromosome[k] = r.chromosome;
+    if (start) start[k] = r.start;
+    if (end) end[k] = r.end;
+    if (strand) strand[k] = r.strand;
+    if (posteriormax) posteriormax[k] = r.posteriormax;
+    if (status) status[k] = r.status;
+    if (status_flag) status_flag[k] = r.status_flag;
+    if (meth_lvl) meth_lvl[k] = r.meth_lvl;
+    if (context) context[k] = r.context;
+  }
+};
+
+struct SiteIn {  // host-decided records: what abn_sites_insert is given (context null: every code is CG) and keeps
+  const int64_t* line;
+  const int32_t* chromosome;
+  const uint32_t *start, *end;
+  const uint8_t* strand;
+  const double* posteriormax;
+  const uint8_t* status;
+  const double* meth_lvl;
+  const uint8_t* context;
+  bool complete() const { return line && chromosome && start && end && strand && posteriormax && status && meth_lvl; }
+  SiteRecord at(size_t j) const {  // (such a line has no status_flag: the host's parser printed its warning)
+    return SiteRecord{line[j], chromosome[j], start[j], end[j], strand[j], posteriormax[j], status[j], 0, meth_lvl[j],
+                      (uint8_t)(context ? context[j] : kCtxCG)};
+  }
+};
+
+struct SiteColumns {  // the records a handle holds on the host
+  std::vector<int64_t> line;
+  std::vector<int32_t> chromosome;
+  std::vector<uint32_t> start, end;
+  std::vector<uint8_t> strand, status, status_flag, context;
+  std::vector<double> posteriormax, meth_lvl;
+  size_t size() const { return line.size(); }
+  void resize(size_t n) {
+    line.resize(n), chromosome.resize(n), start.resize(n), end.resize(n), strand.resize(n), posteriormax.resize(n);
+    status.resize(n), status_flag.resize(n), meth_lvl.resize(n), context.resize(n);
+  }
+  SiteOut view() {
+    return SiteOut{line.data(), chromosome.data(), start.data(), end.data(), strand.data(), posteriormax.data(),
+                   status.data(), status_flag.data(), meth_lvl.data(), context.data()};
+  }
+  SiteIn in() const {  // (a resident handle's: the inserted records)
+    return SiteIn{line.data(), chromosome.data(), start.data(), end.data(), strand.data(), posteriormax.data(),
+                  status.data(), meth_lvl.data(), context.data()};
+  }
+  // Records at .. at + n of the slab that begins at file line line0, from their line and meta words; start, end and the
+  // two floats come down from the device into place.  Plain column stores: the time of abn_sites_parse rests on this loop
+  void decode(size_t at, size_t n, int64_t line0, const uint32_t* l, const uint32_t* m) {
+    for (size_t i = 0, k = at; i < n; ++i, ++k) {
+      line[k] = line0 + (int64_t)l[i];
+      chromosome[k] = meta_chromosome(m[i]);
+      strand[k] = (uint8_t)meta_strand(m[i]);
+      status[k] = (uint8_t)meta_status(m[i]);
+      status_flag[k] = (uint8_t)meta_status_flag(m[i]);
+      context[k] = (uint8_t)meta_context(m[i]);
+    }
+  }
+  void push(const SiteRecord& r) {
+    resize(size() + 1);
+    view().put(size() - 1, r);
+  }
+  void copy_to(const SiteOut& o) const {  // column by column
+    if (o.line) std::copy(line.begin(), line.end(), o.line);
+    if (o.chromosome) std::copy(chromosome.begin(), chromosome.end(), o.chromosome);
+    if (o.start) std::copy(start.begin(), start.end(), o.start);
+    if (o.end) std::copy(end.begin(), end.end(), o.end);
+    if (o.strand) std::copy(strand.begin(), strand.end(), o.strand);
+    if (o.posteriormax) std::copy(posteriormax.begin(), posteriormax.end(), o.posteriormax);
+    if (o.status) std::copy(status.begin(), status.end(), o.status);
+    if (o.status_flag) std::copy(status_flag.begin(), status_flag.end(), o.status_flag);
+    if (o.meth_lvl) std::copy(meth_lvl.begin(), meth_lvl.end(), o.meth_lvl);
+    if (o.context) std::copy(context.begin(), context.end(), o.context);
+  }
+};
+
+// ---- the records on the device
 struct RecordBufs {
   DevBuf<uint32_t> line, meta, start, end, dline, doffset, dlength;
   DevBuf<double> pm, ml;
@@ -31,8 +142,8 @@ struct RecordBufs {
       return e;
     return hipSuccess;
   }
-  ParseRecords records() { return ParseRecords{line.p, meta.p, start.p, end.p, pm.p, ml.p}; }
-  ParseDeferred deferred() { return ParseDeferred{dline.p, doffset.p, dlength.p}; }
+  ParseRecords records() const { return ParseRecords{line.p, meta.p, start.p, end.p, pm.p, ml.p}; }
+  ParseDeferred deferred() const { return ParseDeferred{dline.p, doffset.p, dlength.p}; }
 };
 
 struct SiteChunk {  // a slab's compacted records, resident (abn_sites_parse_dev)
@@ -43,21 +154,41 @@ struct SiteChunk {  // a slab's compacted records, resident (abn_sites_parse_dev
   }
 };
 
+struct InsertedBufs {  // the host-decided records (abn_sites_insert), with the chunk table their merge kernel reads
+  DevBuf<MergeChunk> chunks;
+  DevBuf<long long> line;
+  DevBuf<int32_t> chunk, chromosome;
+  DevBuf<uint32_t> start, end;
+  DevBuf<uint8_t> strand, status;
+  DevBuf<double> pm, ml;
+  // line: in.line as the kernels read it; pick: the chunk of every line; refs: the handle's chunks.  Nothing waited for
+  int upload(abn_ctx* c, const SiteIn& in, const std::vector<long long>& l, const std::vector<int32_t>& pick,
+             const std::vector<MergeChunk>& refs) {
+    const size_t n = l.size();
+    int rc;
+    if ((rc = abn::upload(c, chunks, refs.data(), refs.size())) || (rc = abn::upload(c, line, l.data(), n)) ||
+        (rc = abn::upload(c, chunk, pick.data(), n)) || (rc = abn::upload(c, chromosome, in.chromosome, n)) ||
+        (rc = abn::upload(c, start, in.start, n)) || (rc = abn::upload(c, end, in.end, n)) ||
+        (rc = abn::upload(c, strand, in.strand, n)) || (rc = abn::upload(c, status, in.status, n)) ||
+        (rc = abn::upload(c, pm, in.posteriormax, n)) || (rc = abn::upload(c, ml, in.meth_lvl, n)))
+      return rc;
+    return ABN_OK;
+  }
+  MergeInserted ref() const {
+    return MergeInserted{line.p, chunk.p, chromosome.p, start.p, end.p, strand.p, status.p, pm.p, ml.p, (long long)line.n};
+  }
+};
+
 }  // namespace
 
-// The host form (abn_sites_parse) holds the records in the vectors; the resident form (abn_sites_parse_dev: ctx is set)
-// holds them in `chunks` on the device and, after abn_sites_insert, the host-decided records in the same vectors and in
-// the i* buffers.  The deferred triples, n_lines and kernel_ms are the same in both.  `context` goes with `line`: the code
-// of every record the vectors hold.
+// The host form (abn_sites_parse) holds the records in `cols`; the resident form (abn_sites_parse_dev: ctx is set) holds
+// them in `chunks` on the device and, after abn_sites_insert, the host-decided records in `cols` and in `ins`.  The
+// deferred triples, n_lines and kernel_ms are the same in both.
 struct abn_sites {
   int32_t mask = (int32_t)kContextsCG;  // the contexts the handle was parsed under
-  std::vector<uint8_t> context;
   mutable double split_ms[2] = {0.0, 0.0};  // abn_sites_split's count and scatter kernels: on the parent and its children
-  std::vector<int64_t> line, dline, doffset, dlength;
-  std::vector<int32_t> chromosome;
-  std::vector<uint32_t> start, end;
-  std::vector<uint8_t> strand, status, status_flag;
-  std::vector<double> posteriormax, meth_lvl;
+  SiteColumns cols;
+  std::vector<int64_t> dline, doffset, dlength;
   int64_t n_lines = 0;
   double kernel_ms = 0.0;
   // resident form
@@ -67,12 +198,16 @@ struct abn_sites {
   int64_t n_records = 0;                           // over all chunks
   std::vector<int64_t> flagged;                    // the file lines of the records with a status_flag
   bool inserted = false;
-  DevBuf<MergeChunk> dchunks;
-  DevBuf<long long> iline;
-  DevBuf<int32_t> ichunk, ichromosome;
-  DevBuf<uint32_t> istart, iend;
-  DevBuf<uint8_t> istrand, istatus;
-  DevBuf<double> ipm, iml;
+  InsertedBufs ins;
+  // one more chunk: the slab of n_lines lines from file line line0, behind the records held so far ...
+  SiteChunk* add_chunk(int64_t line0, int64_t n_lines_) {
+    chunks.emplace_back(new SiteChunk);
+    SiteChunk* chunk = chunks.back().get();
+    chunk->line0 = line0, chunk->n_lines = n_lines_, chunk->before = n_records;
+    return chunk;
+  }
+  // ... and, once known, its records (the last chunk's: `before` of the next one counts them)
+  void chunk_records(SiteChunk* chunk, int64_t n) { chunk->n = n, n_records += n; }
 };
 
 namespace {
@@ -92,7 +227,7 @@ size_t slab_end(const char* text, size_t n, size_t from, size_t slab_bytes) {
   return fwd ? (size_t)((const char*)fwd - text) + 1 : n;
 }
 
-// one slab [text, text + n): its lines from skip on, appended to h — to its vectors, or (resident) as one more chunk with
+// one slab [text, text + n): its lines from skip on, appended to h — to its columns, or (resident) as one more chunk with
 // only the deferred triples and the flagged records' lines coming back; line numbers and offsets are the file's
 int parse_slab(abn_ctx* c, abn_sites* h, bool resident, const char* text, size_t n, int64_t skip, int64_t line0, int64_t byte0,
                EventPair& ev) {
@@ -103,7 +238,7 @@ int parse_slab(abn_ctx* c, abn_sites* h, bool resident, const char* text, size_t
   HIPCHK(c, dtext.alloc(n_pieces));
   HIPCHK(c, dblock.alloc((size_t)n_blocks + 1));
   HIPCHK(c, hipMemsetAsync((char*)dtext.p + (size_t)(n_pieces - 1) * kParsePieceBytes, 0, kParsePieceBytes, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dtext.p, text, n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dtext.p, text, n, hipMemcpyHostToDevice, c->stream));  // (n bytes of n_pieces pieces)
   auto timed = [&]() {  // behind the kernels of a phase: their time, added to the handle's
     double ms = 0.0;
     const int rc = ev.end(c, &ms);
@@ -117,18 +252,11 @@ int parse_slab(abn_ctx* c, abn_sites* h, bool resident, const char* text, size_t
   HIPCHK(c, hipGetLastError());
   if (int rc = timed()) return rc;
   uint32_t n_newlines = 0;
-  HIPCHK(c, hipMemcpyAsync(&n_newlines, dblock.p + n_blocks, 4, hipMemcpyDeviceToHost, c->stream));
+  if (int rc = to_host(c, &n_newlines, dblock.p + n_blocks, 4)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint32_t n_lines = n_newlines + (text[n - 1] != '\n' ? 1u : 0u);
   h->n_lines += n_lines;
-  SiteChunk* chunk = nullptr;
-  if (resident) {
-    h->chunks.emplace_back(new SiteChunk);
-    chunk = h->chunks.back().get();
-    chunk->line0 = line0;
-    chunk->n_lines = n_lines;
-    chunk->before = h->n_records;
-  }
+  SiteChunk* chunk = resident ? h->add_chunk(line0, n_lines) : nullptr;
   if ((int64_t)n_lines <= skip) return ABN_OK;
   const uint32_t first = (uint32_t)skip, n_runs = (n_lines - first + kParseRun - 1) / kParseRun;
   const uint32_t stride = n_runs + 1;
@@ -147,8 +275,8 @@ int parse_slab(abn_ctx* c, abn_sites* h, bool resident, const char* text, size_t
   HIPCHK(c, hipGetLastError());
   if (int rc = timed()) return rc;
   uint32_t n_rec = 0, n_def = 0;
-  HIPCHK(c, hipMemcpyAsync(&n_rec, dcount.p + n_runs, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&n_def, dcount.p + stride + n_runs, 4, hipMemcpyDeviceToHost, c->stream));
+  int rc;
+  if ((rc = to_host(c, &n_rec, dcount.p + n_runs, 4)) || (rc = to_host(c, &n_def, dcount.p + stride + n_runs, 4))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (n_rec == 0 && n_def == 0) return ABN_OK;
   RecordBufs& rec = resident ? chunk->rec : out;  // the records stay with the handle; the deferred triples never do
@@ -168,79 +296,43 @@ int parse_slab(abn_ctx* c, abn_sites* h, bool resident, const char* text, size_t
     HIPCHK(c, hipGetLastError());
   }
   if (int rc = timed()) return rc;
-  std::vector<uint32_t> dline(n_def), doff(n_def), dlen(n_def);
-  const size_t dat = h->dline.size();
-  auto take_deferred = [&]() {
-    h->dline.resize(dat + n_def);
-    h->doffset.resize(dat + n_def);
-    h->dlength.resize(dat + n_def);
-    for (size_t i = 0; i < n_def; ++i) {
-      h->dline[dat + i] = line0 + (int64_t)dline[i];
-      h->doffset[dat + i] = byte0 + (int64_t)doff[i];
-      h->dlength[dat + i] = (int64_t)dlen[i];
-    }
-  };
-  if (resident) {
-    std::vector<uint32_t> partial(flag_blocks);
-    if (flag_blocks)
-      HIPCHK(c, hipMemcpyAsync(partial.data(), dflagged.p, dflagged.bytes(), hipMemcpyDeviceToHost, c->stream));
-    if (n_def) {
-      HIPCHK(c, hipMemcpyAsync(dline.data(), out.dline.p, 4 * (size_t)n_def, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(doff.data(), out.doffset.p, 4 * (size_t)n_def, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(dlen.data(), out.dlength.p, 4 * (size_t)n_def, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    chunk->n = n_rec;
-    h->n_records += n_rec;
-    take_deferred();
-    uint64_t n_flagged = 0;
-    for (uint32_t v : partial) n_flagged += v;
-    if (n_flagged) {  // rare: the warning of src/methylation_site.rs:107-112 names these lines
-      std::vector<uint32_t> line(n_rec), meta(n_rec);
-      HIPCHK(c, hipMemcpyAsync(line.data(), rec.line.p, 4 * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(meta.data(), rec.meta.p, 4 * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      for (size_t i = 0; i < n_rec; ++i)
-        if ((meta[i] >> 24) & 0xfu) h->flagged.push_back(line0 + (int64_t)line[i]);
-    }
+  // What comes back — resident: the partial flag counts; host form: the records, start, end and the two floats into their
+  // columns as they are, line and meta for SiteColumns::decode — then the deferred triples, and one wait for all of it
+  std::vector<uint32_t> partial(flag_blocks), line, meta, dline(n_def), doff(n_def), dlen(n_def);
+  const size_t at = h->cols.size();
+  if (resident && flag_blocks) {
+    if ((rc = to_host(c, partial.data(), dflagged))) return rc;
+  } else if (!resident && n_rec) {
+    SiteColumns& k = h->cols;
+    k.resize(at + n_rec), line.resize(n_rec), meta.resize(n_rec);
+    if ((rc = to_host(c, line.data(), out.line)) || (rc = to_host(c, meta.data(), out.meta)) ||
+        (rc = to_host(c, k.start.data() + at, out.start)) || (rc = to_host(c, k.end.data() + at, out.end)) ||
+        (rc = to_host(c, k.posteriormax.data() + at, out.pm)) || (rc = to_host(c, k.meth_lvl.data() + at, out.ml)))
+      return rc;
+  }
+  if (n_def && ((rc = to_host(c, dline.data(), out.dline)) || (rc = to_host(c, doff.data(), out.doffset)) ||
+                (rc = to_host(c, dlen.data(), out.dlength))))
+    return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < n_def; ++i) {
+    h->dline.push_back(line0 + (int64_t)dline[i]);
+    h->doffset.push_back(byte0 + (int64_t)doff[i]);
+    h->dlength.push_back((int64_t)dlen[i]);
+  }
+  if (!resident) {
+    h->cols.decode(at, n_rec, line0, line.data(), meta.data());
     return ABN_OK;
   }
-  std::vector<uint32_t> line(n_rec), meta(n_rec), start(n_rec), end(n_rec);
-  const size_t at = h->line.size();
-  h->posteriormax.resize(at + n_rec);
-  h->meth_lvl.resize(at + n_rec);
-  if (n_rec) {
-    HIPCHK(c, hipMemcpyAsync(line.data(), out.line.p, 4 * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(meta.data(), out.meta.p, 4 * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(start.data(), out.start.p, 4 * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(end.data(), out.end.p, 4 * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h->posteriormax.data() + at, out.pm.p, 8 * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h->meth_lvl.data() + at, out.ml.p, 8 * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
+  h->chunk_records(chunk, n_rec);
+  uint64_t n_flagged = 0;
+  for (uint32_t v : partial) n_flagged += v;
+  if (n_flagged) {  // rare: the warning of src/methylation_site.rs:107-112 names these lines
+    line.resize(n_rec), meta.resize(n_rec);
+    if ((rc = to_host(c, line.data(), rec.line)) || (rc = to_host(c, meta.data(), rec.meta))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n_rec; ++i)
+      if (meta_status_flag(meta[i])) h->flagged.push_back(line0 + (int64_t)line[i]);
   }
-  if (n_def) {
-    HIPCHK(c, hipMemcpyAsync(dline.data(), out.dline.p, 4 * (size_t)n_def, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(doff.data(), out.doffset.p, 4 * (size_t)n_def, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dlen.data(), out.dlength.p, 4 * (size_t)n_def, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  h->line.resize(at + n_rec);
-  h->chromosome.resize(at + n_rec);
-  h->start.insert(h->start.end(), start.begin(), start.end());
-  h->end.insert(h->end.end(), end.begin(), end.end());
-  h->strand.resize(at + n_rec);
-  h->status.resize(at + n_rec);
-  h->status_flag.resize(at + n_rec);
-  h->context.resize(at + n_rec);
-  for (size_t i = 0; i < n_rec; ++i) {
-    const uint32_t m = meta[i];
-    h->line[at + i] = line0 + (int64_t)line[i];
-    h->chromosome[at + i] = (int32_t)(m & 0xffffu);
-    h->strand[at + i] = (uint8_t)((m >> 16) & 0xfu);
-    h->status[at + i] = (uint8_t)((m >> 20) & 0xfu);
-    h->status_flag[at + i] = (uint8_t)((m >> 24) & 0xfu);
-    h->context[at + i] = (uint8_t)meta_context(m);
-  }
-  take_deferred();
   return ABN_OK;
 }
 
@@ -302,65 +394,46 @@ extern "C" int abn_sites_destroy(abn_sites* h) {
 extern "C" int abn_sites_info(const abn_sites* h, int64_t* n_sites, int64_t* n_deferred, int64_t* n_lines,
                               double* kernel_ms) {
   if (!h) return ABN_ERR_INVALID_ARG;
-  if (n_sites) *n_sites = h->n_records + (int64_t)h->line.size();  // (one of the two is 0 until abn_sites_insert)
+  if (n_sites) *n_sites = h->n_records + (int64_t)h->cols.size();  // (one of the two is 0 until abn_sites_insert)
   if (n_deferred) *n_deferred = (int64_t)h->dline.size();
   if (n_lines) *n_lines = h->n_lines;
   if (kernel_ms) *kernel_ms = h->kernel_ms;
   return ABN_OK;
 }
 
-// abn_sites_fetch of a resident handle: every chunk's records come down and are merged by line with the inserted ones
-static int sites_fetch_resident(const abn_sites* h, int64_t* line, int32_t* chromosome, uint32_t* start, uint32_t* end,
-                                uint8_t* strand, double* posteriormax, uint8_t* status, uint8_t* status_flag,
-                                double* meth_lvl, uint8_t* context) {
+// The wanted columns of every site in file order.  Host form: column by column.  Resident: every chunk's records come down
+// and are merged by line with the inserted ones.
+static int sites_fetch(const abn_sites* h, const SiteOut& out) {
+  if (!h->ctx) {
+    h->cols.copy_to(out);
+    return ABN_OK;
+  }
   abn_ctx* c = h->ctx;
   HIPCHK(c, hipSetDevice(c->device));
   try {
     size_t j = 0, k = 0;  // the next inserted record, the next place
-    const size_t n_ins = h->line.size();
-    auto put_inserted = [&]() {
-      if (line) line[k] = h->line[j];
-      if (chromosome) chromosome[k] = h->chromosome[j];
-      if (start) start[k] = h->start[j];
-      if (end) end[k] = h->end[j];
-      if (strand) strand[k] = h->strand[j];
-      if (posteriormax) posteriormax[k] = h->posteriormax[j];
-      if (status) status[k] = h->status[j];
-      if (status_flag) status_flag[k] = 0;
-      if (meth_lvl) meth_lvl[k] = h->meth_lvl[j];
-      if (context) context[k] = h->context[j];
-      ++j, ++k;
-    };
+    const size_t n_ins = h->cols.size();
+    const SiteIn ins = h->cols.in();
     for (const auto& chunk : h->chunks) {
       const size_t n = (size_t)chunk->n;
       if (n == 0) continue;
       std::vector<uint32_t> l(n), m(n), s(n), e(n);
       std::vector<double> pm(n), ml(n);
       const RecordBufs& r = chunk->rec;
-      HIPCHK(c, hipMemcpyAsync(l.data(), r.line.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(m.data(), r.meta.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
-      if (start) HIPCHK(c, hipMemcpyAsync(s.data(), r.start.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
-      if (end) HIPCHK(c, hipMemcpyAsync(e.data(), r.end.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
-      if (posteriormax) HIPCHK(c, hipMemcpyAsync(pm.data(), r.pm.p, 8 * n, hipMemcpyDeviceToHost, c->stream));
-      if (meth_lvl) HIPCHK(c, hipMemcpyAsync(ml.data(), r.ml.p, 8 * n, hipMemcpyDeviceToHost, c->stream));
+      int rc;
+      if ((rc = to_host(c, l.data(), r.line)) || (rc = to_host(c, m.data(), r.meta)) ||
+          (rc = to_host(c, out.start ? s.data() : nullptr, r.start)) || (rc = to_host(c, out.end ? e.data() : nullptr, r.end)) ||
+          (rc = to_host(c, out.posteriormax ? pm.data() : nullptr, r.pm)) ||
+          (rc = to_host(c, out.meth_lvl ? ml.data() : nullptr, r.ml)))
+        return rc;
       HIPCHK(c, hipStreamSynchronize(c->stream));
       for (size_t i = 0; i < n; ++i) {
-        const int64_t li = chunk->line0 + (int64_t)l[i];
-        while (j < n_ins && h->line[j] < li) put_inserted();
-        if (line) line[k] = li;
-        if (chromosome) chromosome[k] = (int32_t)(m[i] & 0xffffu);
-        if (start) start[k] = s[i];
-        if (end) end[k] = e[i];
-        if (strand) strand[k] = (uint8_t)((m[i] >> 16) & 0xfu);
-        if (posteriormax) posteriormax[k] = pm[i];
-        if (status) status[k] = (uint8_t)((m[i] >> 20) & 0xfu);
-        if (status_flag) status_flag[k] = (uint8_t)((m[i] >> 24) & 0xfu);
-        if (meth_lvl) meth_lvl[k] = ml[i];
-        if (context) context[k] = (uint8_t)meta_context(m[i]);
-        ++k;
+        const SiteRecord site = site_decode(chunk->line0, l[i], m[i], s[i], e[i], pm[i], ml[i]);
+        while (j < n_ins && ins.line[j] < site.line) out.put(k++, ins.at(j++));
+        out.put(k++, site);
       }
     }
-    while (j < n_ins) put_inserted();
+    while (j < n_ins) out.put(k++, ins.at(j++));
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
   }
@@ -371,28 +444,16 @@ extern "C" int abn_sites_fetch(const abn_sites* h, int64_t* line, int32_t* chrom
                                uint8_t* strand, double* posteriormax, uint8_t* status, uint8_t* status_flag,
                                double* meth_lvl) {
   if (!h) return ABN_ERR_INVALID_ARG;
-  if (h->ctx)
-    return sites_fetch_resident(h, line, chromosome, start, end, strand, posteriormax, status, status_flag, meth_lvl, nullptr);
-  if (line) std::copy(h->line.begin(), h->line.end(), line);
-  if (chromosome) std::copy(h->chromosome.begin(), h->chromosome.end(), chromosome);
-  if (start) std::copy(h->start.begin(), h->start.end(), start);
-  if (end) std::copy(h->end.begin(), h->end.end(), end);
-  if (strand) std::copy(h->strand.begin(), h->strand.end(), strand);
-  if (posteriormax) std::copy(h->posteriormax.begin(), h->posteriormax.end(), posteriormax);
-  if (status) std::copy(h->status.begin(), h->status.end(), status);
-  if (status_flag) std::copy(h->status_flag.begin(), h->status_flag.end(), status_flag);
-  if (meth_lvl) std::copy(h->meth_lvl.begin(), h->meth_lvl.end(), meth_lvl);
-  return ABN_OK;
+  return sites_fetch(h, SiteOut{line, chromosome, start, end, strand, posteriormax, status, status_flag, meth_lvl, nullptr});
 }
 
 extern "C" int abn_sites_context(const abn_sites* h, int32_t* mask, uint8_t* context) {
   if (!h) return ABN_ERR_INVALID_ARG;
   if (mask) *mask = h->mask;
   if (!context) return ABN_OK;
-  if (h->ctx)
-    return sites_fetch_resident(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, context);
-  std::copy(h->context.begin(), h->context.end(), context);
-  return ABN_OK;
+  SiteOut out{};
+  out.context = context;
+  return sites_fetch(h, out);
 }
 
 extern "C" int abn_sites_deferred(const abn_sites* h, int64_t* line, int64_t* offset, int64_t* length) {
@@ -407,9 +468,9 @@ extern "C" int abn_sites_flagged(const abn_sites* h, int64_t* n, int64_t* line) 
   if (!h) return ABN_ERR_INVALID_ARG;
   if (!h->ctx) {  // the host form has the flags themselves
     int64_t k = 0;
-    for (size_t i = 0; i < h->line.size(); ++i)
-      if (h->status_flag[i]) {
-        if (line) line[k] = h->line[i];
+    for (size_t i = 0; i < h->cols.size(); ++i)
+      if (h->cols.status_flag[i]) {
+        if (line) line[k] = h->cols.line[i];
         ++k;
       }
     if (n) *n = k;
@@ -420,70 +481,42 @@ extern "C" int abn_sites_flagged(const abn_sites* h, int64_t* n, int64_t* line) 
   return ABN_OK;
 }
 
-// abn_sites_insert_ctx (context null: every code is 0), and how a child of abn_sites_split gets its share of the parent's
-// inserted records (inherited: it has no deferred lines to look the lines up in)
-static int sites_insert(abn_sites* h, int64_t n, const int64_t* line, const int32_t* chromosome, const uint32_t* start,
-                        const uint32_t* end, const uint8_t* strand, const double* posteriormax, const uint8_t* status,
-                        const double* meth_lvl, const uint8_t* context, bool inherited) {
+// abn_sites_insert and abn_sites_insert_ctx, and how a child of abn_sites_split gets its share of the parent's inserted
+// records (inherited: it has no deferred lines to look the lines up in)
+static int sites_insert(abn_sites* h, int64_t n, const SiteIn& in, bool inherited) {
   if (!h || !h->ctx) return ABN_ERR_INVALID_ARG;  // (a host-form handle has no context to report to)
   abn_ctx* c = h->ctx;
   if (h->inserted) return set_err(c, ABN_ERR_INVALID_ARG, "abn_sites_insert was already called on this handle");
-  if (n < 0 || (n > 0 && (!line || !chromosome || !start || !end || !strand || !posteriormax || !status || !meth_lvl)))
-    return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (n < 0 || (n > 0 && !in.complete())) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
   try {
     const size_t N = (size_t)n;
     size_t d = 0;  // both lists ascend: every line is looked for behind the one before
     for (size_t j = 0; j < N; ++j) {
-      if (j > 0 && line[j] <= line[j - 1]) return set_err(c, ABN_ERR_INVALID_ARG, "the lines are not strictly ascending");
-      while (d < h->dline.size() && h->dline[d] < line[j]) ++d;
-      if (!inherited && (d == h->dline.size() || h->dline[d] != line[j]))
+      const SiteRecord r = in.at(j);
+      if (j > 0 && r.line <= in.line[j - 1]) return set_err(c, ABN_ERR_INVALID_ARG, "the lines are not strictly ascending");
+      while (d < h->dline.size() && h->dline[d] < r.line) ++d;
+      if (!inherited && (d == h->dline.size() || h->dline[d] != r.line))
         return set_err(c, ABN_ERR_INVALID_ARG, "a line that was not deferred");
-      if (chromosome[j] < 0 || chromosome[j] > 257) return set_err(c, ABN_ERR_INVALID_ARG, "a chromosome outside 0..257");
-      if (strand[j] > 2 || status[j] > 2) return set_err(c, ABN_ERR_INVALID_ARG, "a strand or a status above 2");
-      const uint32_t code = context ? context[j] : (uint32_t)kCtxCG;
+      if (r.chromosome < 0 || r.chromosome > 257) return set_err(c, ABN_ERR_INVALID_ARG, "a chromosome outside 0..257");
+      if (r.strand > 2 || r.status > 2) return set_err(c, ABN_ERR_INVALID_ARG, "a strand or a status above 2");
+      const uint32_t code = r.context;
       if (code > kCtxNone || (code < kCtxNone && !(((uint32_t)h->mask >> code) & 1u)))
         return set_err(c, ABN_ERR_INVALID_ARG, "a context code above 3 or outside the handle's contexts");
     }
     if (N > 0) {
       std::vector<MergeChunk> refs;
       for (const auto& chunk : h->chunks) refs.push_back(chunk->ref());
-      std::vector<long long> l(line, line + N);
+      std::vector<long long> l(in.line, in.line + N);
       std::vector<int32_t> pick(N);
       if (!merge_pick_chunks(refs.data(), (int)refs.size(), l.data(), (long long)N, pick.data()))
         return set_err(c, ABN_ERR_INVALID_ARG, "a line outside every slab");
       HIPCHK(c, hipSetDevice(c->device));
       PoolScope pool_scope(c);
-      HIPCHK(c, h->dchunks.alloc(refs.size()));
-      HIPCHK(c, h->iline.alloc(N));
-      HIPCHK(c, h->ichunk.alloc(N));
-      HIPCHK(c, h->ichromosome.alloc(N));
-      HIPCHK(c, h->istart.alloc(N));
-      HIPCHK(c, h->iend.alloc(N));
-      HIPCHK(c, h->istrand.alloc(N));
-      HIPCHK(c, h->istatus.alloc(N));
-      HIPCHK(c, h->ipm.alloc(N));
-      HIPCHK(c, h->iml.alloc(N));
-      HIPCHK(c, hipMemcpyAsync(h->dchunks.p, refs.data(), h->dchunks.bytes(), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h->iline.p, l.data(), 8 * N, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h->ichunk.p, pick.data(), 4 * N, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h->ichromosome.p, chromosome, 4 * N, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h->istart.p, start, 4 * N, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h->iend.p, end, 4 * N, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h->istrand.p, strand, N, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h->istatus.p, status, N, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h->ipm.p, posteriormax, 8 * N, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h->iml.p, meth_lvl, 8 * N, hipMemcpyHostToDevice, c->stream));
+      if (int rc = h->ins.upload(c, in, l, pick, refs)) return rc;
       HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's arrays and the staging vectors go on return
-      h->line.assign(line, line + N);  // the host's copy, for abn_sites_fetch
-      h->chromosome.assign(chromosome, chromosome + N);
-      h->start.assign(start, start + N);
-      h->end.assign(end, end + N);
-      h->strand.assign(strand, strand + N);
-      h->posteriormax.assign(posteriormax, posteriormax + N);
-      h->status.assign(status, status + N);
-      h->meth_lvl.assign(meth_lvl, meth_lvl + N);
-      if (context) h->context.assign(context, context + N);
-      else h->context.assign(N, (uint8_t)kCtxCG);
+      h->cols.resize(N);  // the host's copy, for abn_sites_fetch
+      const SiteOut copy = h->cols.view();
+      for (size_t j = 0; j < N; ++j) copy.put(j, in.at(j));
     }
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
@@ -497,7 +530,7 @@ extern "C" int abn_sites_insert_ctx(abn_sites* h, int64_t n, const int64_t* line
                                     const double* posteriormax, const uint8_t* status, const double* meth_lvl,
                                     const uint8_t* context) {
   if (h && h->ctx && n > 0 && !context) return set_err(h->ctx, ABN_ERR_INVALID_ARG, "null/size");
-  return sites_insert(h, n, line, chromosome, start, end, strand, posteriormax, status, meth_lvl, context, false);
+  return sites_insert(h, n, SiteIn{line, chromosome, start, end, strand, posteriormax, status, meth_lvl, context}, false);
 }
 
 extern "C" int abn_sites_insert(abn_sites* h, int64_t n, const int64_t* line, const int32_t* chromosome,
@@ -505,17 +538,11 @@ extern "C" int abn_sites_insert(abn_sites* h, int64_t n, const int64_t* line, co
                                 const double* posteriormax, const uint8_t* status, const double* meth_lvl) {
   if (h && h->ctx && n > 0 && h->mask != (int32_t)kContextsCG)
     return set_err(h->ctx, ABN_ERR_INVALID_ARG, "the handle holds other contexts than CG: abn_sites_insert_ctx names each record's");
-  return sites_insert(h, n, line, chromosome, start, end, strand, posteriormax, status, meth_lvl, nullptr, false);
+  return sites_insert(h, n, SiteIn{line, chromosome, start, end, strand, posteriormax, status, meth_lvl, nullptr}, false);
 }
 
 // ---- abn_sites_split
 namespace {
-
-// the chunk table on the device: the parent's chunks with their workgroups and (once made) the children's chunks
-int upload_split_chunks(abn_ctx* c, const std::vector<SplitChunk>& table, DevBuf<SplitChunk>& d) {
-  HIPCHK(c, hipMemcpyAsync(d.p, table.data(), d.bytes(), hipMemcpyHostToDevice, c->stream));
-  return ABN_OK;
-}
 
 int sites_split(const abn_sites* h, std::unique_ptr<abn_sites>* kids) {
   abn_ctx* c = h->ctx;
@@ -547,7 +574,7 @@ int sites_split(const abn_sites* h, std::unique_ptr<abn_sites>* kids) {
     HIPCHK(c, dtable.alloc((size_t)n_chunks));
     HIPCHK(c, dcount.alloc((size_t)kSplitChildren * stride));
     HIPCHK(c, dsize.alloc(size.size()));
-    if (int rc = upload_split_chunks(c, table, dtable)) return rc;
+    if (int rc = to_device(c, dtable.p, table.data(), dtable.bytes())) return rc;  // the parent's chunks, their workgroups
     if (int rc = ev.begin(c, true)) return rc;
     hipLaunchKernelGGL(abn_split_count_kernel, dim3((unsigned)n_blocks), dim3(kSplitThreads), 0, c->stream,
                        (const SplitChunk*)dtable.p, n_chunks, (uint32_t)h->mask, dcount.p, stride);
@@ -560,24 +587,17 @@ int sites_split(const abn_sites* h, std::unique_ptr<abn_sites>* kids) {
     hipLaunchKernelGGL(abn_split_sizes_kernel, dim3(size_grid), dim3(kSplitThreads), 0, c->stream,
                        (const SplitChunk*)dtable.p, n_chunks, (const uint32_t*)dcount.p, stride, (uint32_t)n_blocks, dsize.p);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(size.data(), dsize.p, dsize.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = to_host(c, size.data(), dsize)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   // the children's chunks: a slab keeps its lines, and holds the child's share of its records
   for (int i = 0; i < n_chunks; ++i)
     for (int k = 0; k < kSplitChildren; ++k) {
       if (!kids[k]) continue;  // (a context outside the mask has no child, and the kernels count no record for it)
-      abn_sites* kid = kids[k].get();
-      kid->chunks.emplace_back(new SiteChunk);
-      SiteChunk* chunk = kid->chunks.back().get();
-      chunk->n = size[(size_t)i * kSplitChildren + k];
-      chunk->line0 = h->chunks[(size_t)i]->line0;
-      chunk->n_lines = h->chunks[(size_t)i]->n_lines;
-      chunk->before = kid->n_records;
-      kid->n_records += chunk->n;
+      SiteChunk* chunk = kids[k]->add_chunk(h->chunks[(size_t)i]->line0, h->chunks[(size_t)i]->n_lines);
+      kids[k]->chunk_records(chunk, size[(size_t)i * kSplitChildren + k]);
       HIPCHK(c, chunk->rec.alloc((size_t)chunk->n, 0));
-      table[(size_t)i].out[k] = SplitOut{chunk->rec.line.p, chunk->rec.meta.p, chunk->rec.start.p,
-                                         chunk->rec.end.p,  chunk->rec.pm.p,   chunk->rec.ml.p};
+      table[(size_t)i].out[k] = chunk->rec.records();
     }
   for (int i = 0; i < n_chunks; ++i)  // a record counted for a context without a child would have nowhere to go
     for (int k = 0; k < kSplitChildren; ++k)
@@ -592,15 +612,13 @@ int sites_split(const abn_sites* h, std::unique_ptr<abn_sites>* kids) {
   std::vector<long long> fline(h->flagged.begin(), h->flagged.end());
   std::vector<int32_t> fchunk(n_flagged);
   if (n_blocks > 0) {
-    if (int rc = upload_split_chunks(c, table, dtable)) return rc;
+    if (int rc = to_device(c, dtable.p, table.data(), dtable.bytes())) return rc;  // ... and the children's chunks
     if (n_flagged) {
       if (!merge_pick_chunks(refs.data(), n_chunks, fline.data(), (long long)n_flagged, fchunk.data()))
         return set_err(c, ABN_ERR_HIP, "abn_sites_split: a flagged line outside every slab");
-      HIPCHK(c, dfline.alloc(n_flagged));
-      HIPCHK(c, dfchunk.alloc(n_flagged));
       HIPCHK(c, dmember.alloc(n_flagged));
-      HIPCHK(c, hipMemcpyAsync(dfline.p, fline.data(), dfline.bytes(), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(dfchunk.p, fchunk.data(), dfchunk.bytes(), hipMemcpyHostToDevice, c->stream));
+      if (int rc = upload(c, dfline, fline.data(), n_flagged)) return rc;
+      if (int rc = upload(c, dfchunk, fchunk.data(), n_flagged)) return rc;
     }
     if (int rc = ev.begin(c, true)) return rc;
     hipLaunchKernelGGL(abn_split_scatter_kernel, dim3((unsigned)n_blocks), dim3(kSplitThreads), 0, c->stream,
@@ -613,7 +631,7 @@ int sites_split(const abn_sites* h, std::unique_ptr<abn_sites>* kids) {
                          (const SplitChunk*)dtable.p, (const long long*)dfline.p, (const int32_t*)dfchunk.p,
                          (long long)n_flagged, (uint32_t)h->mask, dmember.p);
       HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipMemcpyAsync(member.data(), dmember.p, n_flagged, hipMemcpyDeviceToHost, c->stream));
+      if (int rc = to_host(c, member.data(), dmember)) return rc;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the tables and staging vectors go on return
   }
@@ -623,28 +641,10 @@ int sites_split(const abn_sites* h, std::unique_ptr<abn_sites>* kids) {
     kid->split_ms[0] = h->split_ms[0], kid->split_ms[1] = h->split_ms[1];
     for (size_t j = 0; j < n_flagged; ++j)
       if ((member[j] >> k) & 1u) kid->flagged.push_back(h->flagged[j]);
-    // the parent's inserted records of this membership, uploaded as abn_sites_insert uploads them
-    std::vector<int64_t> line;
-    std::vector<int32_t> chrom;
-    std::vector<uint32_t> start, end;
-    std::vector<uint8_t> strand, status, context;
-    std::vector<double> pm, ml;
-    for (size_t j = 0; j < h->line.size(); ++j) {
-      const uint32_t code = h->context[j];
-      if (code != kCtxNone && code != (uint32_t)k) continue;
-      line.push_back(h->line[j]);
-      chrom.push_back(h->chromosome[j]);
-      start.push_back(h->start[j]);
-      end.push_back(h->end[j]);
-      strand.push_back(h->strand[j]);
-      pm.push_back(h->posteriormax[j]);
-      status.push_back(h->status[j]);
-      ml.push_back(h->meth_lvl[j]);
-      context.push_back((uint8_t)code);
-    }
-    if (int rc = sites_insert(kid, (int64_t)line.size(), line.data(), chrom.data(), start.data(), end.data(), strand.data(),
-                              pm.data(), status.data(), ml.data(), context.data(), true))
-      return rc;
+    SiteColumns part;  // the parent's inserted records of this membership, uploaded as abn_sites_insert uploads them
+    for (size_t j = 0; j < h->cols.size(); ++j)
+      if (h->cols.context[j] == kCtxNone || h->cols.context[j] == (uint32_t)k) part.push(h->cols.in().at(j));
+    if (int rc = sites_insert(kid, (int64_t)part.size(), part.in(), true)) return rc;
   }
   return ABN_OK;
 }
@@ -681,53 +681,40 @@ abn_ctx* abn::sites_ctx(const abn_sites* h) { return h ? h->ctx : nullptr; }
 
 int64_t abn::sites_merged_count(const abn_sites* h) {
   if (!h || !h->ctx || (!h->dline.empty() && !h->inserted)) return -1;
-  return h->n_records + (int64_t)h->line.size();
+  return h->n_records + (int64_t)h->cols.size();
+}
+
+// The merge of one sample into `out`, nothing waited for: the fields kernel of every chunk (inserted = false), or the insert
+// kernel over the handle's inserted records (true)
+template <class Fields, class Insert, class Out>
+static int sites_merge(const abn_sites* h, bool inserted, double filter, Fields fields_kernel, Insert insert_kernel,
+                       const Out& out) {
+  abn_ctx* c = h->ctx;
+  const MergeInserted ins = h->ins.ref();
+  if (!inserted) {
+    for (const auto& chunk : h->chunks) {
+      if (chunk->n == 0) continue;
+      const unsigned grid = (unsigned)((chunk->n + kMergeThreads - 1) / kMergeThreads);
+      hipLaunchKernelGGL(fields_kernel, dim3(grid), dim3(kMergeThreads), 0, c->stream, chunk->ref(), ins.line, ins.n, filter,
+                         out);
+      HIPCHK(c, hipGetLastError());
+    }
+  } else if (ins.n > 0) {
+    const unsigned grid = (unsigned)((ins.n + kMergeThreads - 1) / kMergeThreads);
+    hipLaunchKernelGGL(insert_kernel, dim3(grid), dim3(kMergeThreads), 0, c->stream, (const MergeChunk*)h->ins.chunks.p, ins,
+                       filter, out);
+    HIPCHK(c, hipGetLastError());
+  }
+  return ABN_OK;
 }
 
 int abn::sites_merge_dev(const abn_sites* h, bool inserted, double filter, int32_t* dchrom, uint32_t* dstart,
                          uint32_t* dend, uint8_t* dstrand, uint8_t* dcode, double* dlevel) {
-  abn_ctx* c = h->ctx;
-  const MergeOut out{dchrom, dstart, dend, dstrand, dcode, dlevel};
-  const long long n_ins = (long long)h->line.size();
-  if (!inserted) {
-    for (const auto& chunk : h->chunks) {
-      if (chunk->n == 0) continue;
-      const unsigned grid = (unsigned)((chunk->n + kMergeThreads - 1) / kMergeThreads);
-      hipLaunchKernelGGL(abn_sites_fields_kernel, dim3(grid), dim3(kMergeThreads), 0, c->stream, chunk->ref(),
-                         (const long long*)h->iline.p, n_ins, filter, out);
-      HIPCHK(c, hipGetLastError());
-    }
-  } else if (n_ins > 0) {
-    const MergeInserted ins{h->iline.p, h->ichunk.p, h->ichromosome.p, h->istart.p, h->iend.p,
-                            h->istrand.p, h->istatus.p, h->ipm.p, h->iml.p, n_ins};
-    const unsigned grid = (unsigned)((n_ins + kMergeThreads - 1) / kMergeThreads);
-    hipLaunchKernelGGL(abn_sites_insert_kernel, dim3(grid), dim3(kMergeThreads), 0, c->stream,
-                       (const MergeChunk*)h->dchunks.p, ins, filter, out);
-    HIPCHK(c, hipGetLastError());
-  }
-  return ABN_OK;
+  return sites_merge(h, inserted, filter, abn_sites_fields_kernel, abn_sites_insert_kernel,
+                     MergeOut{dchrom, dstart, dend, dstrand, dcode, dlevel});
 }
 
 // ---- for abn_codes_create_parsed (abn_codes.hip): the same launches with the reduced writers of abn_codes.hpp
 int abn::sites_merge_codes_dev(const abn_sites* h, bool inserted, double filter, uint8_t* dcode, double* dlevel) {
-  abn_ctx* c = h->ctx;
-  const CodesOut out{dcode, dlevel};
-  const long long n_ins = (long long)h->line.size();
-  if (!inserted) {
-    for (const auto& chunk : h->chunks) {
-      if (chunk->n == 0) continue;
-      const unsigned grid = (unsigned)((chunk->n + kMergeThreads - 1) / kMergeThreads);
-      hipLaunchKernelGGL(abn_codes_fields_kernel, dim3(grid), dim3(kMergeThreads), 0, c->stream, chunk->ref(),
-                         (const long long*)h->iline.p, n_ins, filter, out);
-      HIPCHK(c, hipGetLastError());
-    }
-  } else if (n_ins > 0) {
-    const MergeInserted ins{h->iline.p, h->ichunk.p, h->ichromosome.p, h->istart.p, h->iend.p,
-                            h->istrand.p, h->istatus.p, h->ipm.p, h->iml.p, n_ins};
-    const unsigned grid = (unsigned)((n_ins + kMergeThreads - 1) / kMergeThreads);
-    hipLaunchKernelGGL(abn_codes_insert_kernel, dim3(grid), dim3(kMergeThreads), 0, c->stream,
-                       (const MergeChunk*)h->dchunks.p, ins, filter, out);
-    HIPCHK(c, hipGetLastError());
-  }
-  return ABN_OK;
+  return sites_merge(h, inserted, filter, abn_codes_fields_kernel, abn_codes_insert_kernel, CodesOut{dcode, dlevel});
 }

@@ -24,22 +24,16 @@
 #pragma once
 #include <stdint.h>
 
-#ifndef ABN_HOST_DEVICE
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define ABN_HOST_DEVICE __host__ __device__
-#else
-#define ABN_HOST_DEVICE
-#endif
-#endif
+#include "abn_parse.hpp"
 
 namespace abn {
 
 constexpr int kMergeThreads = 256;
 constexpr int kMergeFlagBlocks = 256;  // at most this many partial counts per chunk
 
-struct MergeChunk {  // the device records of one slab (ParseRecords of abn_parse_kernels.hpp, read-only)
+struct MergeChunk {  // the device records of one slab (ParseRecords of abn_parse.hpp, read-only)
   const uint32_t* line;  // slab-relative, strictly ascending
-  const uint32_t* meta;  // chromosome | strand << 16 | status << 20 | status_flag << 24
+  const uint32_t* meta;  // (abn_parse.hpp: meta_chromosome and the accessors beside it)
   const uint32_t* start;
   const uint32_t* end;
   const double* posteriormax;
@@ -105,11 +99,11 @@ ABN_HOST_DEVICE inline long long merge_write_record(const MergeChunk& c, long lo
                                                     long long n_inserted, double filter, const MergeOut& out) {
   const long long d = merge_dest_record(c, i, inserted_line, n_inserted);
   const uint32_t m = c.meta[i];
-  out.chromosome[d] = (int32_t)(m & 0xffffu);
+  out.chromosome[d] = meta_chromosome(m);
   out.start[d] = c.start[i];
   out.end[d] = c.end[i];
-  out.strand[d] = (uint8_t)((m >> 16) & 0xfu);
-  out.code[d] = merge_code((m >> 20) & 0xfu, c.posteriormax[i], filter);
+  out.strand[d] = (uint8_t)meta_strand(m);
+  out.code[d] = merge_code(meta_status(m), c.posteriormax[i], filter);
   out.level[d] = c.meth_lvl[i];
   return d;
 }
@@ -178,7 +172,7 @@ abn_sites_flagged_kernel(const uint32_t* __restrict__ meta, long long n, uint32_
   __shared__ uint32_t s_wave[kMergeThreads / 64];
   uint32_t count = 0;
   for (long long i = (long long)blockIdx.x * kMergeThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kMergeThreads)
-    count += ((meta[i] >> 24) & 0xfu) ? 1u : 0u;
+    count += meta_status_flag(meta[i]) ? 1u : 0u;
   for (int d = 32; d > 0; d >>= 1) count += __shfl_down(count, d, 64);
   if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = count;
   __syncthreads();

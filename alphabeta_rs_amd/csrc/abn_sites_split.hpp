@@ -37,14 +37,7 @@ namespace abn {
 constexpr int kSplitThreads = 256;
 constexpr int kSplitChildren = 3;
 
-struct SplitOut {  // one child's chunk (ParseRecords of abn_parse_kernels.hpp)
-  uint32_t* line;
-  uint32_t* meta;
-  uint32_t* start;
-  uint32_t* end;
-  double* posteriormax;
-  double* meth_lvl;
-};
+using SplitOut = ParseRecords;  // one child's chunk
 
 struct SplitChunk {
   MergeChunk src;      // the parent's chunk

@@ -8,6 +8,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import _contexts_model as X
 import _genes_model as G
 import _parse_model as P
 import _windows_model as M
@@ -90,6 +91,80 @@ def test_resident_fetch_equals_host_form(gpu_ctx, L, slab_bytes):
         finally:
             r.close()
     assert 0 < n_inserted < n_deferred          # the torture text: deferred lines of both outcomes
+
+
+# ---------------------------------------------------------------- abn_sites_fetch with some outputs null
+def partial_fetch_texts():
+    """the torture text (deferred lines of both outcomes) and 257 plain lines with the first and last line of two of the
+    300-byte slabs deferred"""
+    d = Deferring(P.plain_text(257, seed=257, cg_every=2).decode())
+    d.slab = 300
+    for chunk in (1, 3):
+        d.mark_chunk_edges(chunk)
+    assert min(d.at_edges()) >= 2
+    return (("torture", P.torture_text()), ("plain 257", d.text()))
+
+
+def check_partial_fetches(lib, r, name):
+    """abn_sites_fetch with one output non-null at a time, and with the three the host layer reads (host/resident.hpp):
+    each column is the full fetch()'s, and no other array is written"""
+    want = r.fetch()
+    n = len(want["line"])
+    assert r.contexts().shape == (n,)
+    kinds = list(r.KINDS.items())
+    types = lib.abn_sites_fetch.argtypes[1:]
+    for asked in [(k,) for k, _ in kinds] + [("posteriormax", "status", "meth_lvl")]:
+        got = {k: np.full(n + 1, 0x5a, dtype=t) for k, t in kinds}      # one element more: nothing is written behind the end
+        rc = lib.abn_sites_fetch(r._h, *(got[k].ctypes.data_as(t) if k in asked else None for (k, _), t in zip(kinds, types)))
+        assert rc == 0, (name, asked)
+        for k, t in kinds:
+            if k in asked:
+                assert got[k].dtype == want[k].dtype and got[k][:n].tobytes() == want[k].tobytes(), (name, asked, k)
+                assert got[k][n] == t(0x5a), (name, asked, k)
+            else:
+                assert np.all(got[k] == t(0x5a)), (name, asked, k)
+    codes = np.full(n + 1, 0x5a, dtype=np.uint8)                         # the tenth column: abn_sites_context
+    assert lib.abn_sites_context(r._h, None, codes.ctypes.data_as(C.POINTER(C.c_uint8))) == 0
+    assert codes[:n].tobytes() == r.contexts().tobytes() and codes[n] == 0x5a, name
+    return n
+
+
+@pytest.mark.parametrize("contexts", [("CG",), X.CONTEXTS])
+def test_fetch_with_some_outputs_null(gpu_ctx, L, contexts):
+    lib = gpu_ctx._L
+    XL = X.hostlib()
+    n_inserted = n_child_inserted = 0
+    for name, text in partial_fetch_texts():
+        r = gpu_ctx.parse_sites_resident(text, slab_bytes=300, contexts=contexts)
+        children = {}
+        try:
+            if len(contexts) == 1:
+                ins = decide(L, text, r.deferred())
+                r.insert(*ins)
+                P.assert_sites_equal(r.fetch(), P.device_sites_merged(L, text, 1, 300)[0])
+            else:
+                ins = X.decide(XL, text, r.deferred(), 7)
+                r.insert(*ins[:8], context=ins[8])
+                host = X.host_sites(XL, text, 7)
+                P.assert_sites_equal(r.fetch(), host)
+                assert r.contexts().tobytes() == host["context"].tobytes(), name
+            assert len(ins[0]) > 0 and len(slabs(text, 300)) > 3, name
+            n_inserted += len(ins[0])
+            assert check_partial_fetches(lib, r, name) == r.info()["n_sites"]
+            if len(contexts) > 1:
+                children = r.split()
+                assert list(children) == list(X.CONTEXTS)
+                codes = r.contexts()
+                for c, child in enumerate(children.values()):
+                    n = check_partial_fetches(lib, child, (name, c))
+                    assert n == np.count_nonzero((codes == c) | (codes == 3)), (name, c)
+                    assert np.all(np.isin(child.contexts(), (c, 3)))
+                    n_child_inserted += int(np.count_nonzero((ins[8] == c) | (ins[8] == 3)))
+        finally:
+            for s in children.values():
+                s.close()
+            r.close()
+    assert n_inserted >= 8 and (len(contexts) == 1 or n_child_inserted >= 8)
 
 
 # ---------------------------------------------------------------- the window handle
