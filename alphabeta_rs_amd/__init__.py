@@ -75,6 +75,9 @@ EXPORTED_SYMBOLS = [
     "abn_tiles_kernel_ms",
     "abn_tiles_set_pools", "abn_tiles_pool_segments", "abn_tiles_pool_columns", "abn_tiles_pool_kernel_ms",
     "abn_sites_context", "abn_sites_insert_ctx", "abn_sites_split", "abn_sites_split_ms",
+    "abn_pairwise_transitions_packed", "abn_pairwise_transitions_packed_dev",
+    "abn_pairwise_transitions_windows_packed", "abn_pairwise_transitions_windows_packed_dev",
+    "abn_codes_transitions", "abn_tiles_transitions",
 ]
 
 
@@ -210,6 +213,15 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
                                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
     L.abn_pairwise_divergence_windows_packed_dev.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, i64p, i64p,
                                                              C.c_int32, vp, vp, vp, dp]
+    u64p = C.POINTER(C.c_uint64)
+    L.abn_pairwise_transitions_packed.argtypes = [vp, u8p, C.c_int32, C.c_int64, C.c_int64, u64p]
+    L.abn_pairwise_transitions_packed_dev.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, vp, dp]
+    L.abn_pairwise_transitions_windows_packed.argtypes = [vp, u8p, C.c_int32, C.c_int64, C.c_int64, i64p, i64p,
+                                                          C.c_int32, u64p]
+    L.abn_pairwise_transitions_windows_packed_dev.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, i64p, i64p,
+                                                              C.c_int32, vp, dp]
+    L.abn_codes_transitions.argtypes = [vp, u64p]
+    L.abn_tiles_transitions.argtypes = [vp, u64p]
     L.abn_windows_create.argtypes = [vp, C.POINTER(WindowsParams), C.c_int32, i64p, u32p, u32p, u32p, u8p, u8p, dp,
                                      C.POINTER(vp)]
     L.abn_windows_destroy.argtypes = [vp]
@@ -683,6 +695,56 @@ class Context:
             self._h, C.c_void_p(packed_ptr), n_samples, n_sites, row_stride, b.ctypes.data_as(i64p),
             e.ctypes.data_as(i64p), b.shape[0], C.c_void_p(diff_ptr or None), C.c_void_p(both_ptr or None),
             C.c_void_p(dvalue_ptr or None), C.byref(ms)))
+        return ms.value
+
+    def pairwise_transitions_packed(self, packed, n_sites: int):
+        """The 3 x 3 state transitions of every pair on 2-bit packed codes (pack_codes): uint64 (pairs, 3, 3), entry
+        [p, x, y] = the sites both samples of pair p = (a, b), a < b, keep with status x in a and y in b (0 = U, 1 = I,
+        2 = M).  Its sum is pairwise_divergence_packed's both, its |x - y|-weighted sum the diff."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        n, stride = packed.shape
+        table = np.zeros((n * (n - 1) // 2, 3, 3), dtype=np.uint64)
+        self._check(self._L.abn_pairwise_transitions_packed(self._h, packed.ctypes.data_as(C.POINTER(C.c_uint8)), n,
+                                                            int(n_sites), stride,
+                                                            table.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return table
+
+    def pairwise_transitions_packed_dev(self, packed_ptr: int, n_samples: int, n_sites: int, row_stride: int,
+                                        table_ptr: int) -> float:
+        """The same on device-resident buffers: packed rows [n x row_stride] (16-byte aligned) in, u64 table
+        [pairs x 9] out.  Returns the kernels' HIP-event ms."""
+        ms = C.c_double(0.0)
+        self._check(self._L.abn_pairwise_transitions_packed_dev(self._h, C.c_void_p(packed_ptr), n_samples, n_sites,
+                                                                row_stride, C.c_void_p(table_ptr or None), C.byref(ms)))
+        return ms.value
+
+    def pairwise_transitions_windows_packed(self, packed, n_sites: int, begin, end):
+        """pairwise_transitions_packed of the column ranges [begin[w], end[w]) (in sites, at any site) of one packed
+        matrix in one batched call: uint64 (n_windows, pairs, 3, 3); an empty window's table is zero."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        n, stride = packed.shape
+        b, e = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+        if b.ndim != 1 or b.shape != e.shape:
+            raise ValueError("begin and end are 1-d arrays of one length")
+        table = np.zeros((b.shape[0], n * (n - 1) // 2, 3, 3), dtype=np.uint64)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.abn_pairwise_transitions_windows_packed(
+            self._h, packed.ctypes.data_as(C.POINTER(C.c_uint8)), n, int(n_sites), stride, b.ctypes.data_as(i64p),
+            e.ctypes.data_as(i64p), b.shape[0], table.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return table
+
+    def pairwise_transitions_windows_packed_dev(self, packed_ptr: int, n_samples: int, n_sites: int, row_stride: int,
+                                                begin, end, table_ptr: int) -> float:
+        """The same on device-resident buffers: packed rows [n x row_stride] (16-byte aligned) in, u64 table
+        [n_windows x pairs x 9] out; begin / end are host arrays.  Returns the kernels' HIP-event ms."""
+        b, e = np.ascontiguousarray(begin, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+        if b.ndim != 1 or b.shape != e.shape:
+            raise ValueError("begin and end are 1-d arrays of one length")
+        ms = C.c_double(0.0)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.abn_pairwise_transitions_windows_packed_dev(
+            self._h, C.c_void_p(packed_ptr), n_samples, n_sites, row_stride, b.ctypes.data_as(i64p),
+            e.ctypes.data_as(i64p), b.shape[0], C.c_void_p(table_ptr or None), C.byref(ms)))
         return ms.value
 
     def analyze_batch_dev(self, raw_ptr: int, n_windows: int, n_boot: int, out_ptr: int, first_bad_ptr: int = 0,
@@ -1293,6 +1355,13 @@ class Codes(_PackedMatrix):
         self.ctx._check(self._L.abn_codes_pairwise(self._h, diff.ctypes.data_as(u64p), both.ctypes.data_as(u64p), _dp(dval)))
         return diff, both, dval
 
+    def transitions(self):
+        """uint64 (pairs, 3, 3): Context.pairwise_transitions_packed on the resident matrix (under a union alignment the
+        placeholder sites count in no entry); refused (AbnError) when the samples differ in length"""
+        table = np.zeros((self.n_samples * (self.n_samples - 1) // 2, 3, 3), dtype=np.uint64)
+        self.ctx._check(self._L.abn_codes_transitions(self._h, table.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return table
+
     def kernel_ms(self) -> np.ndarray:
         """the HIP-event ms of from_parsed's kernels: merge of the records, merge of the inserted lines, pack, fold"""
         ms = np.zeros(4)
@@ -1436,6 +1505,13 @@ class Tiles(_Handle):
         u64p = C.POINTER(C.c_uint64)
         self.ctx._check(self._L.abn_tiles_pairwise(self._h, diff.ctypes.data_as(u64p), both.ctypes.data_as(u64p), _dp(dval)))
         return diff, both, dval
+
+    def transitions(self):
+        """uint64 (n_tiles, pairs, 3, 3): Context.pairwise_transitions_windows_packed on the resident matrix over the
+        tiles' columns (with pools set: the pooled matrix, one table per pool)"""
+        table = np.zeros((self._n_tiles(), self.n_samples * (self.n_samples - 1) // 2, 3, 3), dtype=np.uint64)
+        self.ctx._check(self._L.abn_tiles_transitions(self._h, table.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return table
 
     def kernel_ms(self) -> np.ndarray:
         """the HIP-event ms of the last set_intervals / set_fixed: search, fold"""

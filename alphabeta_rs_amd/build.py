@@ -91,7 +91,8 @@ def build_host(force: bool = False, verbose: bool = False) -> Path:
             HOST / "metaprofile.hpp", HOST / "metaprofile_cli.cpp", HOST / "reference_tests.cpp",
             CSRC / "abn_route.hpp", CSRC / "abn_constants.hpp", CSRC / "abn_parse.hpp", CSRC / "abn_genes.hpp",
             CSRC / "abn_sites_merge.hpp", CSRC / "abn_sites_split.hpp", CSRC / "abn_codes.hpp", CSRC / "abn_sites_common.hpp",
-            CSRC / "abn_sites_union.hpp", CSRC / "abn_tiles.hpp", HOST / "tiles.hpp"]  # host_capi.cpp exports the launch policy to the tests
+            CSRC / "abn_sites_union.hpp", CSRC / "abn_tiles.hpp", HOST / "tiles.hpp",
+            CSRC / "abn_pairwise_transitions.hpp", CSRC / "abn_packed_mask.hpp", HOST / "transitions.hpp"]  # host_capi.cpp exports the launch policy to the tests
     newest = max(p.stat().st_mtime for p in srcs)
     CLI.parent.mkdir(exist_ok=True)
     common = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-I", str(PKG.parent / "include")]

@@ -189,6 +189,18 @@ extern "C" int abn_codes_pairwise(abn_codes* h, uint64_t* diff, uint64_t* both, 
   });
 }
 
+extern "C" int abn_codes_transitions(abn_codes* h, uint64_t* table) {
+  if (!h) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = h->ctx;
+  if (!h->same_len)
+    return set_err(c, ABN_ERR_INVALID_ARG, "the samples differ in length: the pairwise scan needs the same number of sites in each");
+  if (h->n < 2) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  const int64_t begin = 0, end = h->max_sites;  // the whole matrix is one window
+  return transitions_windows_packed_to_host(c, h->packed.p, h->n, h->max_sites, h->stride, &begin, &end, 1, table);
+}
+
 extern "C" int abn_codes_kernel_ms(const abn_codes* h, double* ms4) {
   if (!h || !ms4) return ABN_ERR_INVALID_ARG;
   std::copy(h->ms, h->ms + 4, ms4);

@@ -290,6 +290,17 @@ int analyze_device_table(abn_ctx* c, const double* draw, int32_t W, int64_t B, d
 int pairwise_windows_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
                                 int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
                                 int32_t n_windows, void* dev_diff, void* dev_both, void* dev_dvalue, double* kernel_ms);
+// ... and for abn_codes_transitions (abn_codes.hip) and abn_tiles_transitions (abn_tiles.hip): the entries
+// abn_pairwise_transitions_packed_dev and _windows_packed_dev behind their null check of the context, and the windows
+// one with its table [n_windows][pairs][9] copied to the host (n_samples >= 2 and n_windows >= 1; stream synchronised)
+int transitions_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                           int64_t row_stride_bytes, void* dev_table, double* kernel_ms);
+int transitions_windows_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                   int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                                   int32_t n_windows, void* dev_table, double* kernel_ms);
+int transitions_windows_packed_to_host(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                       int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                                       int32_t n_windows, uint64_t* table);
 // abn_genes.hip, for abn_windows_create_sites (abn_windows.hip): abn_genes_choose_dev behind its checks of the
 // arguments, and the context a genes handle belongs to.
 int genes_choose_dev(abn_genes* h, const abn_gene_rule* rule, int32_t n_samples, const int64_t* site_offset,

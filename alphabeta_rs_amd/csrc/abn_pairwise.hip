@@ -1,10 +1,13 @@
 // Pedigree construction: the four pairwise divergence scans abn_pairwise_divergence* — byte codes
-// or 2-bit packed codes, the whole matrix or many windows of it — each with a host entry and a _dev entry.
+// or 2-bit packed codes, the whole matrix or many windows of it — each with a host entry and a _dev entry — and the
+// state transition tables abn_pairwise_transitions* of the packed two (abn_pairwise_transitions.hpp).
 // The scan kernels are in abn_pairwise_mx.hpp, abn_pairwise_packed.hpp, abn_pairwise_windows.hpp and
 // abn_pairwise_windows_packed.hpp; the fit path (abn_api.hip, abn_context.hip, abn_plan.hip) does not include them.
+#define ABN_TRANSITIONS_KERNELS
 #include "abn_host.hpp"
 #include "abn_pairwise_mx.hpp"
 #include "abn_pairwise_packed.hpp"
+#include "abn_pairwise_transitions.hpp"
 #include "abn_pairwise_windows.hpp"
 #include "abn_pairwise_windows_packed.hpp"
 
@@ -35,6 +38,10 @@ struct Win {
 struct WinPacked {
   template <int NB, bool DIAG>
   static constexpr auto kernel = abn_pairwise_win_packed_kernel<NB, DIAG>;
+};
+struct Trans {
+  template <int NB, bool DIAG>
+  static constexpr auto kernel = abn_pairwise_trans_kernel<NB, DIAG>;
 };
 
 // `grid` jobs of one family of super-pairs: the pairs R < C are 4 x 4 blocks of 16 samples, a diagonal super-pair has nb
@@ -229,9 +236,13 @@ extern "C" int abn_pairwise_divergence_packed(abn_ctx* c, const uint8_t* packed,
 // The jobs of one family of super-pairs over all windows, in launches ("slabs") of at most kPmxMaxJobs jobs; the chunks
 // of one (window, super-pair) never straddle two slabs, so a slab's reduce launch finds all rows of its tasks.
 // A window's chunks are cut at multiples of chunk[w] from its begin rounded down to `align` sites (1: byte codes, from the
-// begin itself; 256: packed codes, whole super-steps); launch(diag, grid, args) starts the scan kernel of the format.
+// begin itself; 256: packed codes, whole super-steps); launch(diag, jobs, args) starts the scan kernel of the format and
+// reduce(diag, tasks, ntasks, args) the kernel that sums a slab's partial rows.  row_words and max_jobs: the 64-bit
+// words of a partial row and the jobs per launch of the scan (the divergence scans' unless set before plan).
 struct PairWinFamily {
   struct Slab { size_t job0, njobs, task0, ntasks, nrows; };
+  size_t row_words = kPmxJobElems;
+  long long max_jobs = kPmxMaxJobs;
   std::vector<PairWinJob> jobs;
   std::vector<PairWinTask> tasks;
   std::vector<Slab> slabs;
@@ -248,7 +259,7 @@ struct PairWinFamily {
       const long long b0 = begin[w] - begin[w] % align;
       const long long nch = std::max<long long>(1, (end[w] - b0 + chunk[w] - 1) / chunk[w]);
       for (long long sp = 0; sp < nsp; ++sp) {
-        if (cur.njobs + (size_t)nch > (size_t)kPmxMaxJobs) {
+        if (cur.njobs + (size_t)nch > (size_t)max_jobs) {
           slabs.push_back(cur);
           cur = Slab{jobs.size(), 0, tasks.size(), 0, 0};
         }
@@ -270,24 +281,22 @@ struct PairWinFamily {
   int upload(abn_ctx* c) {
     HIPCHK(c, djobs.alloc(jobs.size()));
     HIPCHK(c, dtasks.alloc(tasks.size()));
-    HIPCHK(c, partial.alloc(max_rows * kPmxJobElems));
+    HIPCHK(c, partial.alloc(max_rows * row_words));
     if (!jobs.empty())
       HIPCHK(c, hipMemcpyAsync(djobs.p, jobs.data(), djobs.bytes(), hipMemcpyHostToDevice, c->stream));
     if (!tasks.empty())
       HIPCHK(c, hipMemcpyAsync(dtasks.p, tasks.data(), dtasks.bytes(), hipMemcpyHostToDevice, c->stream));
     return ABN_OK;
   }
-  template <class Launch>
-  int run(abn_ctx* c, PairWinArgs a, bool diag, Launch launch) {
-    a.partial = partial.p;
+  template <class Args, class Launch, class Reduce>
+  int run(abn_ctx* c, Args a, bool diag, Launch launch, Reduce reduce) {
+    a.partial = reinterpret_cast<decltype(a.partial)>(partial.p);
     for (const Slab& s : slabs) {
       if (s.njobs == 0) continue;
       a.jobs = djobs.p + s.job0;
       HIPCHK(c, launch(diag, (unsigned)s.njobs, a));
       if (s.ntasks == 0) continue;
-      hipLaunchKernelGGL(abn_pairwise_win_reduce_kernel, dim3((unsigned)(s.ntasks * 256)), dim3(16 * kPmxReduceGroups), 0,
-                         c->stream, partial.p, dtasks.p + s.task0, a.n, a.ngroups, diag ? 1 : 0, a.diff, a.both,
-                         a.dvalue);
+      reduce(diag, dtasks.p + s.task0, (unsigned)s.ntasks, a);
       HIPCHK(c, hipGetLastError());
     }
     return ABN_OK;
@@ -295,11 +304,14 @@ struct PairWinFamily {
 };
 
 // Both families of a windows scan between the two events of kernel_ms: plan, upload the job tables, run.
-template <class Launch>
-static int pairwise_windows_run(abn_ctx* c, const PairWinArgs& a, const int64_t* begin, const int64_t* end, int W,
-                                const std::vector<long long>& chunk, long long align, double* kernel_ms, Launch launch) {
+template <class Args, class Launch, class Reduce>
+static int pairwise_windows_run(abn_ctx* c, const Args& a, const int64_t* begin, const int64_t* end, int W,
+                                const std::vector<long long>& chunk, long long align, double* kernel_ms, Launch launch,
+                                Reduce reduce, size_t row_words = kPmxJobElems, long long max_jobs = kPmxMaxJobs) {
   const long long g = a.ngroups;
   PairWinFamily fdiag, foff;  // (their host tables outlive the copies: the stream is synchronised below)
+  fdiag.row_words = foff.row_words = row_words;
+  fdiag.max_jobs = foff.max_jobs = max_jobs;
   fdiag.plan(g, begin, end, W, chunk, align);
   foff.plan(g * (g - 1) / 2, begin, end, W, chunk, align);
   int rc = fdiag.upload(c);
@@ -307,8 +319,8 @@ static int pairwise_windows_run(abn_ctx* c, const PairWinArgs& a, const int64_t*
   if (rc) return rc;
   EventPair ev;
   if ((rc = ev.begin(c, kernel_ms != nullptr))) return rc;
-  rc = fdiag.run(c, a, true, launch);
-  if (!rc) rc = foff.run(c, a, false, launch);
+  rc = fdiag.run(c, a, true, launch, reduce);
+  if (!rc) rc = foff.run(c, a, false, launch, reduce);
   if (!rc) rc = ev.end(c, kernel_ms);
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the job tables and the partial rows are freed on return
@@ -326,18 +338,25 @@ static int pairwise_windows_in_rows(abn_ctx* c, const int64_t* begin, const int6
 // Sites per job of each window: `sites` (kPmxWinChunkSites, kPmxWinPackedChunkSites), more — whole line pairs of a row and
 // whole steps of `align` sites — only where a window would otherwise need more rows of `partial` than one launch keeps.
 // Counted from the window's begin rounded down to `align` sites (1: byte codes; kPackedStepSites: packed codes).
+// max_jobs: the jobs of one launch (PairWinFamily::max_jobs).
 static int pairwise_windows_chunks(abn_ctx* c, const int64_t* begin, const int64_t* end, int W, long long sites,
-                                   long long align, std::vector<long long>& chunk) {
+                                   long long align, std::vector<long long>& chunk, long long max_jobs = kPmxMaxJobs) {
   const long long unit = std::max<long long>(align, 128);
   chunk.resize((size_t)W);
   for (int w = 0; w < W; ++w) {
     const long long span = end[w] - (begin[w] - begin[w] % align);
     long long ch = sites;
-    if ((span + ch - 1) / ch > kPmxMaxJobs) ch = ((span + kPmxMaxJobs - 1) / kPmxMaxJobs + unit - 1) / unit * unit;
+    if ((span + ch - 1) / ch > max_jobs) ch = ((span + max_jobs - 1) / max_jobs + unit - 1) / unit * unit;
     if (ch >= (1ll << 30)) return set_err(c, ABN_ERR_INVALID_ARG, "window too long");
     chunk[(size_t)w] = ch;
   }
   return ABN_OK;
+}
+
+// the reduce launch of both divergence windows scans
+static void pairwise_win_reduce(abn_ctx* c, bool diag, const PairWinTask* tasks, unsigned ntasks, const PairWinArgs& a) {
+  hipLaunchKernelGGL(abn_pairwise_win_reduce_kernel, dim3(ntasks * 256), dim3(16 * kPmxReduceGroups), 0, c->stream,
+                     a.partial, tasks, a.n, a.ngroups, diag ? 1 : 0, a.diff, a.both, a.dvalue);
 }
 
 // the arguments of both windows scans; nb as pairwise_groups
@@ -375,6 +394,9 @@ static int pairwise_windows_on_device(abn_ctx* c, const uint8_t* dcodes, int n, 
                               [&](bool diag, unsigned grid, const PairWinArgs& args) {
                                 return al4 ? launch_scan<Win<true>>(nb, diag, grid, c->stream, args)
                                            : launch_scan<Win<false>>(nb, diag, grid, c->stream, args);
+                              },
+                              [&](bool diag, const PairWinTask* tasks, unsigned ntasks, const PairWinArgs& args) {
+                                pairwise_win_reduce(c, diag, tasks, ntasks, args);
                               });
 }
 
@@ -417,11 +439,11 @@ extern "C" int abn_pairwise_divergence_windows(abn_ctx* c, const uint8_t* codes,
 // ------------------------------------------------------------------------------------------------
 static int pairwise_windows_packed_check(abn_ctx* c, const void* packed, int32_t n, int64_t L, int64_t stride,
                                          const int64_t* begin, const int64_t* end, int32_t W,
-                                         std::vector<long long>& chunk) {
+                                         std::vector<long long>& chunk, long long max_jobs = kPmxMaxJobs) {
   if (int rc = pairwise_packed_check(c, packed, n, L, stride)) return rc;
   if (W < 0 || (W > 0 && (!begin || !end))) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
   if (int rc = pairwise_windows_in_rows(c, begin, end, W, L)) return rc;
-  return pairwise_windows_chunks(c, begin, end, W, kPmxWinPackedChunkSites, kPackedStepSites, chunk);
+  return pairwise_windows_chunks(c, begin, end, W, kPmxWinPackedChunkSites, kPackedStepSites, chunk, max_jobs);
 }
 
 static int pairwise_windows_packed_on_device(abn_ctx* c, const uint8_t* dpacked, int n, long long stride,
@@ -433,6 +455,9 @@ static int pairwise_windows_packed_on_device(abn_ctx* c, const uint8_t* dpacked,
   return pairwise_windows_run(c, a, begin, end, W, chunk, kPackedStepSites, kernel_ms,
                               [&](bool diag, unsigned grid, const PairWinArgs& args) {
                                 return launch_scan<WinPacked>(nb, diag, grid, c->stream, args);
+                              },
+                              [&](bool diag, const PairWinTask* tasks, unsigned ntasks, const PairWinArgs& args) {
+                                pairwise_win_reduce(c, diag, tasks, ntasks, args);
                               });
 }
 
@@ -483,4 +508,120 @@ extern "C" int abn_pairwise_divergence_windows_packed(abn_ctx* c, const uint8_t*
     return pairwise_windows_packed_on_device(c, dpacked.p, n_samples, row_stride_bytes, site_begin, site_end, n_windows,
                                              chunk, dd, db, dv, nullptr);
   });
+}
+
+// ------------------------------------------------------------------------------------------------
+// the 3 x 3 state transition table of every pair (the joint table behind src/pedigree.rs:236-257), whole packed matrix or
+// many windows of it: abn_pairwise_transitions.hpp
+// ------------------------------------------------------------------------------------------------
+// dtable [W][pairs][9] on the device.  A job of the plan is a (window, super-pair, chunk); the grid has one workgroup
+// per row block of each.  Every pair of every window is written (an empty window: by its one job that runs no step).
+static int transitions_on_device(abn_ctx* c, const uint8_t* dpacked, int n, long long stride, const int64_t* begin,
+                                 const int64_t* end, int W, const std::vector<long long>& chunk,
+                                 unsigned long long* dtable, double* kernel_ms) {
+  PairTransArgs a{};
+  a.codes = dpacked;
+  a.row_stride = stride;
+  a.n = n;
+  int nb;
+  a.ngroups = pairwise_groups(n, nb);
+  a.table = dtable;
+  return pairwise_windows_run(
+      c, a, begin, end, W, chunk, kPackedStepSites, kernel_ms,
+      [&](bool diag, unsigned jobs, const PairTransArgs& args) {
+        return launch_scan<Trans>(nb, diag, jobs * (unsigned)(diag ? nb : 4), c->stream, args);
+      },
+      [&](bool diag, const PairWinTask* tasks, unsigned ntasks, const PairTransArgs& args) {
+        hipLaunchKernelGGL(abn_pairwise_trans_reduce_kernel, dim3(ntasks * 256),
+                           dim3(kTransReduceRow * kTransReduceGroups), 0, c->stream, args.partial, tasks, args.n,
+                           args.ngroups, diag ? 1 : 0, args.table);
+      },
+      (size_t)kTransRowWords / 2, kTransMaxJobs);
+}
+
+int abn::transitions_windows_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                        int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                                        int32_t n_windows, void* dev_table, double* kernel_ms) {
+  std::vector<long long> chunk;
+  if (int rc = pairwise_windows_packed_check(c, dev_packed, n_samples, n_sites, row_stride_bytes, site_begin, site_end,
+                                             n_windows, chunk, kTransMaxJobs))
+    return rc;
+  if ((uintptr_t)dev_packed % 16 != 0) return set_err(c, ABN_ERR_INVALID_ARG, "dev_packed is not 16-byte aligned");
+  if (n_samples < 2 || n_windows == 0) return ABN_OK;
+  if (!dev_table) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  return transitions_on_device(c, (const uint8_t*)dev_packed, n_samples, row_stride_bytes, site_begin, site_end,
+                               n_windows, chunk, (unsigned long long*)dev_table, kernel_ms);
+}
+
+int abn::transitions_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                int64_t row_stride_bytes, void* dev_table, double* kernel_ms) {
+  if (int rc = pairwise_packed_check(c, dev_packed, n_samples, n_sites, row_stride_bytes)) return rc;
+  const int64_t begin = 0, end = n_sites;  // the whole matrix is one window
+  return transitions_windows_packed_dev(c, dev_packed, n_samples, n_sites, row_stride_bytes, &begin, &end, 1, dev_table,
+                                        kernel_ms);
+}
+
+// the table of a host entry: `count` counts on the device around scan(dtable), then to the host, the stream synchronised
+template <class Scan>
+static int transitions_to_host(abn_ctx* c, size_t count, uint64_t* table, Scan scan) {
+  if (!table) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  DevBuf<unsigned long long> dtable;
+  HIPCHK(c, dtable.alloc(count));
+  if (int rc = scan(dtable.p)) return rc;
+  HIPCHK(c, hipMemcpyAsync(table, dtable.p, dtable.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return ABN_OK;
+}
+int abn::transitions_windows_packed_to_host(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                            int64_t row_stride_bytes, const int64_t* site_begin,
+                                            const int64_t* site_end, int32_t n_windows, uint64_t* table) {
+  const size_t n = (size_t)n_samples;
+  return transitions_to_host(c, n * (n - 1) / 2 * (size_t)n_windows * kTransEntries, table, [&](auto* dt) {
+    return transitions_windows_packed_dev(c, dev_packed, n_samples, n_sites, row_stride_bytes, site_begin, site_end,
+                                          n_windows, dt, nullptr);
+  });
+}
+
+extern "C" int abn_pairwise_transitions_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples,
+                                                   int64_t n_sites, int64_t row_stride_bytes, void* dev_table,
+                                                   double* kernel_ms) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  return transitions_packed_dev(c, dev_packed, n_samples, n_sites, row_stride_bytes, dev_table, kernel_ms);
+}
+
+extern "C" int abn_pairwise_transitions_windows_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples,
+                                                           int64_t n_sites, int64_t row_stride_bytes,
+                                                           const int64_t* site_begin, const int64_t* site_end,
+                                                           int32_t n_windows, void* dev_table, double* kernel_ms) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  return transitions_windows_packed_dev(c, dev_packed, n_samples, n_sites, row_stride_bytes, site_begin, site_end,
+                                        n_windows, dev_table, kernel_ms);
+}
+
+extern "C" int abn_pairwise_transitions_windows_packed(abn_ctx* c, const uint8_t* packed, int32_t n_samples,
+                                                       int64_t n_sites, int64_t row_stride_bytes,
+                                                       const int64_t* site_begin, const int64_t* site_end,
+                                                       int32_t n_windows, uint64_t* table) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  std::vector<long long> chunk;
+  if (int rc = pairwise_windows_packed_check(c, packed, n_samples, n_sites, row_stride_bytes, site_begin, site_end,
+                                             n_windows, chunk, kTransMaxJobs))
+    return rc;
+  if (n_samples < 2 || n_windows == 0) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  DevBuf<uint8_t> dpacked;  // (device allocations are aligned far beyond the 16 bytes the kernel asks for)
+  if (int rc = upload_codes(c, dpacked, packed, (size_t)n_samples * (size_t)row_stride_bytes, 64)) return rc;
+  return transitions_windows_packed_to_host(c, dpacked.p, n_samples, n_sites, row_stride_bytes, site_begin, site_end,
+                                            n_windows, table);
+}
+
+extern "C" int abn_pairwise_transitions_packed(abn_ctx* c, const uint8_t* packed, int32_t n_samples, int64_t n_sites,
+                                               int64_t row_stride_bytes, uint64_t* table) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  if (int rc = pairwise_packed_check(c, packed, n_samples, n_sites, row_stride_bytes)) return rc;
+  const int64_t begin = 0, end = n_sites;
+  return abn_pairwise_transitions_windows_packed(c, packed, n_samples, n_sites, row_stride_bytes, &begin, &end, 1, table);
 }

@@ -86,6 +86,83 @@ struct PmxByteCodes {
   static __device__ __forceinline__ void planes(uint32_t x, int, int& v, int& i, int& z) { pmx_planes(x, v, i, z); }
 };
 
+// What a scan sums, the second half of its description (PmxScan's last parameter): the fragments per K step NF, the K
+// steps per batch kBatchSteps, the 64-bit words kRedWords of the workgroup's LDS area, the accumulators, what one K step adds to them (step<Codes>(x, sub): x the
+// loaded fragments of the step, sub the matrix step they feed), and how the four wavefronts' accumulators meet in LDS
+// (fold).  PmxDivSums: both and diff, on every tile of the super-pair.  (The nine sums of the joint state table:
+// abn_pairwise_transitions.hpp.)
+template <int NB, bool DIAG>
+struct PmxDivSums {
+  static constexpr int NF = DIAG ? NB : 8;  // fragments per K step: the blocks of the row group (+ of the column group)
+  static constexpr int NT = DIAG ? NB * (NB + 1) / 2 : 16;
+  static constexpr int kRedWords = kPmxJobElems;
+  static constexpr int kBatchSteps = pmx_steps(NF);
+  pmx_i32x4 S1[NT], S2[NT];  // V V^T and I I^T + Z Z^T of the wavefront's share
+
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) S1[t] = S2[t] = pmx_i32x4{0, 0, 0, 0};
+  }
+  template <class Codes>
+  __device__ __forceinline__ void step(const pmx_u32x4 (&x)[NF], int sub) {
+    pmx_i32x4 V[NF], I[NF], Z[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        int v, i, z;
+        Codes::planes(x[f][e], sub, v, i, z);
+        V[f][e] = v;
+        I[f][e] = i;
+        Z[f][e] = z;
+      }
+    // D[row][col] = sum_k A[row][k] B[k][col]: A = the row block's fragment, B = the column block's (same registers
+    // for a diagonal tile).  The three products of a tile are issued a whole round of tiles apart: no dependent pair
+    // of matrix instructions back to back.
+    int t = 0;
+#pragma unroll
+    for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
+#pragma unroll
+      for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
+        const int fa = bi, fb = DIAG ? bj : 4 + bj;
+        S1[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(V[fa], V[fb], S1[t], 0, 0, 0);
+      }
+    t = 0;
+#pragma unroll
+    for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
+#pragma unroll
+      for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
+        const int fa = bi, fb = DIAG ? bj : 4 + bj;
+        S2[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(I[fa], I[fb], S2[t], 0, 0, 0);
+      }
+    t = 0;
+#pragma unroll
+    for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
+#pragma unroll
+      for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
+        const int fa = bi, fb = DIAG ? bj : 4 + bj;
+        S2[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Z[fa], Z[fb], S2[t], 0, 0, 0);
+      }
+  }
+  // the wavefront's tiles -> red[tile 4 bi + bj][row][column], both << 32 | diff per element.  C/D layout of the 16 x 16
+  // tile: column = lane & 15 (r), row = 4 (lane >> 4) (q) + register
+  __device__ __forceinline__ void fold(unsigned long long* red, int q, int r) const {
+    int t = 0;
+#pragma unroll
+    for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
+#pragma unroll
+      for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const unsigned both = (unsigned)S1[t][e];
+          const unsigned diff = (unsigned)(S1[t][e] - S2[t][e]);
+          if (both | diff)
+            atomicAdd(&red[(4 * bi + bj) * 256 + (4 * q + e) * 16 + r], ((unsigned long long)both << 32) | diff);
+        }
+      }
+  }
+};
+
 // 16 bytes of one row at byte offset `off` (fast path: the whole fragment lies inside the buffer with 4 bytes to spare)
 template <bool AL4>
 __device__ __forceinline__ pmx_u32x4 pmx_load(const uint8_t* codes, size_t off) {
@@ -125,25 +202,24 @@ __device__ __forceinline__ pmx_u32x4 pmx_load_edge(const uint8_t* codes, size_t 
 // The scan of one job, shared by the kernels below and in abn_pairwise_windows.hpp.
 // NB: 16-sample blocks of the row group that exist (DIAG: 1..4, the tiles bi <= bj < NB; else 4 x 4 tiles of groups R < C)
 // Codes: the storage format of the rows (a "step" of the loaders below is 64 BYTES of every row: Codes::SUB K steps)
-template <int NB, bool DIAG, bool AL4, class Codes = PmxByteCodes>
+// Sums: what is summed over the steps (PmxDivSums above)
+template <int NB, bool DIAG, bool AL4, class Codes = PmxByteCodes, template <int, bool> class Sums = PmxDivSums>
 struct PmxScan {
   static_assert(DIAG || NB == 4, "off-diagonal super-pairs are 4 x 4 blocks");
-  static constexpr int NF = DIAG ? NB : 8;            // fragments per K step: the blocks of the row group (+ of the column group)
-  static constexpr int DSTEPS = pmx_steps(NF);        // K steps per batch
-  static constexpr int NT = DIAG ? NB * (NB + 1) / 2 : 16;
+  static constexpr int NF = Sums<NB, DIAG>::NF;       // fragments per K step
+  static constexpr int DSTEPS = Sums<NB, DIAG>::kBatchSteps;  // K steps per batch
   static constexpr std::false_type kFull{};
   static constexpr std::true_type kPart{};
 
   const uint8_t* codes;
-  size_t roff[NF];           // this lane's byte offset of site 0 in each block's row (the caller's; 16 q is added here)
-  pmx_i32x4 S1[NT], S2[NT];  // V V^T and I I^T + Z Z^T of the wavefront's share
+  size_t roff[NF];           // this lane's byte offset of site 0 in each fragment's row (the caller's; 16 q is added here)
+  Sums<NB, DIAG> sums;       // the accumulators of the wavefront's share
   int tid, lane, wave, r, q;
 
   __device__ __forceinline__ PmxScan(const uint8_t* c) : codes(c) {
     tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     r = lane & 15, q = lane >> 4;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) S1[t] = S2[t] = pmx_i32x4{0, 0, 0, 0};
+    sums.clear();
   }
 
   // DSTEPS steps from step k (PART: only the first cnt of them; cnt is uniform in the wavefront: scalar branches)
@@ -163,46 +239,7 @@ struct PmxScan {
     for (int d = 0; d < DSTEPS; ++d) {
       if (Part::value && d >= cnt) break;
 #pragma unroll
-      for (int sub = 0; sub < Codes::SUB; ++sub) {  // the K steps the loaded fragments feed
-        pmx_i32x4 V[NF], I[NF], Z[NF];
-#pragma unroll
-        for (int f = 0; f < NF; ++f)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            int v, i, z;
-            Codes::planes(x[d][f][e], sub, v, i, z);
-            V[f][e] = v;
-            I[f][e] = i;
-            Z[f][e] = z;
-          }
-        // D[row][col] = sum_k A[row][k] B[k][col]: A = the row block's fragment, B = the column block's (same registers
-        // for a diagonal tile).  The three products of a tile are issued a whole round of tiles apart: no dependent pair
-        // of matrix instructions back to back.
-        int t = 0;
-#pragma unroll
-        for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
-#pragma unroll
-          for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
-            const int fa = bi, fb = DIAG ? bj : 4 + bj;
-            S1[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(V[fa], V[fb], S1[t], 0, 0, 0);
-          }
-        t = 0;
-#pragma unroll
-        for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
-#pragma unroll
-          for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
-            const int fa = bi, fb = DIAG ? bj : 4 + bj;
-            S2[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(I[fa], I[fb], S2[t], 0, 0, 0);
-          }
-        t = 0;
-#pragma unroll
-        for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
-#pragma unroll
-          for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
-            const int fa = bi, fb = DIAG ? bj : 4 + bj;
-            S2[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Z[fa], Z[fb], S2[t], 0, 0, 0);
-          }
-      }
+      for (int sub = 0; sub < Codes::SUB; ++sub) sums.template step<Codes>(x[d], sub);  // the K steps the fragments feed
     }
   }
 
@@ -245,7 +282,7 @@ struct PmxScan {
     if (nfull > 0) load_steps(kfull(0), xa, kFull, DSTEPS);
     // the workgroup's sums start at zero — cleared behind the first loads (they are in flight meanwhile); the barrier keeps
     // a wavefront that is already at the ragged end (it stages through `red`) from meeting another one's clearing stores
-    for (int k = tid; k < kPmxJobElems; k += kPmxThreads) red[k] = 0ull;
+    for (int k = tid; k < Sums<NB, DIAG>::kRedWords; k += kPmxThreads) red[k] = 0ull;
     __syncthreads();
     while (rr < nfull) {
       if (rr + 1 < nfull) load_steps(kfull(rr + 1), xb, kFull, DSTEPS);
@@ -280,23 +317,8 @@ struct PmxScan {
     for (int f = 0; f < NF; ++f) stage[f * 64 + lane] = pmx_u32x4{0u, 0u, 0u, 0u};
   }
 
-  // the four wavefronts' tiles -> red[tile 4 bi + bj][row][column], both << 32 | diff per element (between two barriers
-  // of the caller).  C/D layout of the 16 x 16 tile: column = lane & 15, row = 4 (lane >> 4) + register
-  __device__ __forceinline__ void fold(unsigned long long* red) const {
-    int t = 0;
-#pragma unroll
-    for (int bi = 0; bi < (DIAG ? NB : 4); ++bi)
-#pragma unroll
-      for (int bj = (DIAG ? bi : 0); bj < (DIAG ? NB : 4); ++bj, ++t) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const unsigned both = (unsigned)S1[t][e];
-          const unsigned diff = (unsigned)(S1[t][e] - S2[t][e]);
-          if (both | diff)
-            atomicAdd(&red[(4 * bi + bj) * 256 + (4 * q + e) * 16 + r], ((unsigned long long)both << 32) | diff);
-        }
-      }
-  }
+  // the four wavefronts' sums -> red (between two barriers of the caller)
+  __device__ __forceinline__ void fold(unsigned long long* red) const { sums.fold(red, q, r); }
   static __device__ __forceinline__ bool tile_used(int k) {  // element k of a job's packed sums belongs to a computed tile
     const int bi = k >> 10, bj = (k >> 8) & 3;
     return DIAG ? (bi <= bj && bj < NB) : true;

@@ -29,8 +29,10 @@ namespace abn {
 
 struct PmxPackedCodes {
   static constexpr int SUB = 4;  // K steps a fragment feeds: one per shift
+  // the four table indices of shift j of a dword
+  static __device__ __forceinline__ uint32_t index(uint32_t p, int j) { return (p >> (2 * j)) & 0x03030303u; }
   static __device__ __forceinline__ void planes(uint32_t p, int j, int& v, int& i, int& z) {
-    pmx_lookup((p >> (2 * j)) & 0x03030303u, v, i, z);
+    pmx_lookup(index(p, j), v, i, z);
   }
 };
 

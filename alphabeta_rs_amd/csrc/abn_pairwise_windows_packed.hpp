@@ -23,6 +23,34 @@
 
 namespace abn {
 
+// The `fix` of a job [begin, end) on packed rows (Scan: the kernel's PmxScan; q: the lane's quarter of a step).
+// Super-steps [s0(), s1()) of every row; the first and the last of them are masked where the job does not fill them.
+template <class Scan>
+struct PmxPackedWindowFix {
+  long long begin, end;
+  int q;
+  __device__ __forceinline__ long long s0() const { return begin / kPackedStepSites; }
+  __device__ __forceinline__ long long s1() const { return (end + kPackedStepSites - 1) / kPackedStepSites; }
+  __device__ __forceinline__ void operator()(long long k, pmx_u32x4 (&x)[Scan::NF]) const {
+    // ... counted from s0 (a job is below 2^30 sites: an int), -1: no such step
+    const int kf = begin % kPackedStepSites != 0 ? 0 : -1;
+    const int kb = end % kPackedStepSites != 0 ? (int)(s1() - 1 - s0()) : -1;
+    // a step belongs to one wavefront: the compare is made on scalars, the branch around the masking is a scalar one
+    const int ks = __builtin_amdgcn_readfirstlane((int)(k - s0()));
+    if (ks != kf && ks != kb) return;
+    // the job's range counted from the super-step's first site and clamped to the step; this lane's 16 bytes hold the
+    // sites from 64 q on, 16 per dword
+    const long long first = (s0() + ks) * kPackedStepSites, lo64 = begin - first, hi64 = end - first;
+    const int lo = lo64 < 0 ? 0 : (int)lo64, hi = hi64 > kPackedStepSites ? (int)kPackedStepSites : (int)hi64;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {  // (a dword at a time: one mask register)
+      const uint32_t m = abn_packed_window_mask(64 * q + 16 * d, lo, hi);
+#pragma unroll
+      for (int f = 0; f < Scan::NF; ++f) x[f][d] |= m;
+    }
+  }
+};
+
 // a.codes: the packed rows; a.row_stride: bytes per row (a multiple of 64 from a 16-byte aligned base); the jobs' begin
 // and end are sites, end <= 4 row_stride
 template <int NB, bool DIAG>
@@ -43,27 +71,8 @@ __global__ __launch_bounds__(kPmxThreads, DIAG ? 2 : 1) void abn_pairwise_win_pa
     sc.roff[b] = (size_t)s * (size_t)a.row_stride;
   }
 
-  // super-steps [s0, s1) of every row; the first and the last of them are masked where the job does not fill them
-  const long long s0 = job.begin / kPackedStepSites, s1 = (job.end + kPackedStepSites - 1) / kPackedStepSites;
-  // ... counted from s0 (a job is below 2^30 sites: an int), -1: no such step
-  const int kf = job.begin % kPackedStepSites != 0 ? 0 : -1;
-  const int kb = job.end % kPackedStepSites != 0 ? (int)(s1 - 1 - s0) : -1;
-  auto mask_edges = [&](long long k, pmx_u32x4 (&x)[Scan::NF]) {
-    // a step belongs to one wavefront: the compare is made on scalars, the branch around the masking is a scalar one
-    const int ks = __builtin_amdgcn_readfirstlane((int)(k - s0));
-    if (ks != kf && ks != kb) return;
-    // the job's range counted from the super-step's first site and clamped to the step; this lane's 16 bytes hold the
-    // sites from 64 q on, 16 per dword
-    const long long first = (s0 + ks) * kPackedStepSites, lo64 = job.begin - first, hi64 = job.end - first;
-    const int lo = lo64 < 0 ? 0 : (int)lo64, hi = hi64 > kPackedStepSites ? (int)kPackedStepSites : (int)hi64;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {  // (a dword at a time: one mask register)
-      const uint32_t m = abn_packed_window_mask(64 * sc.q + 16 * d, lo, hi);
-#pragma unroll
-      for (int f = 0; f < Scan::NF; ++f) x[f][d] |= m;
-    }
-  };
-  sc.inner_steps(s0, s1, red, mask_edges);
+  PmxPackedWindowFix<Scan> mask_edges{job.begin, job.end, sc.q};
+  sc.inner_steps(mask_edges.s0(), mask_edges.s1(), red, mask_edges);
   // (an empty job that does not sit on a step boundary reads one step and masks all of it: its sums stay zero)
 
   __syncthreads();

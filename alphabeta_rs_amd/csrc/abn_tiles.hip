@@ -548,6 +548,18 @@ extern "C" int abn_tiles_pairwise(abn_tiles* h, uint64_t* diff, uint64_t* both, 
   });
 }
 
+extern "C" int abn_tiles_transitions(abn_tiles* h, uint64_t* table) {
+  if (int rc = tiles_need(h)) return rc;
+  abn_ctx* c = h->ctx;
+  const size_t T = h->begin.size();
+  if (h->n < 2 || T == 0) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  const TileMatrix& m = h->pooled ? h->pool : h->own;
+  return transitions_windows_packed_to_host(c, m.packed.p, h->n, m.columns, m.stride, h->begin.data(), h->end.data(),
+                                            (int32_t)T, table);
+}
+
 extern "C" int abn_tiles_kernel_ms(const abn_tiles* h, double* ms2) {
   if (!h || !ms2) return ABN_ERR_INVALID_ARG;
   std::copy(h->ms, h->ms + 2, ms2);

@@ -45,6 +45,8 @@ static void usage() {
       "                                 --sites device).  One: the run on that context's sites.  Several: every methylome\n"
       "                                 is parsed once and each context is a run of its own, its files in <OUTPUT>/<CTX>/\n"
       "                                 [default: CG]\n"
+      "      --transitions              also write <OUTPUT>/transitions.txt: per pair of sampled nodes the sites both keep,\n"
+      "                                 by status in the first and in the second sample (UU UI UM IU II IM MU MI MM)\n"
       "  -h, --help                    Print help\n"
       "  -V, --version                  Print version");
 }
@@ -118,6 +120,7 @@ int main(int argc, char** argv) {
       }
       contexts_given = true;
     }
+    else if (a == "--transitions") transitions::request().wanted = true;
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (a == "-V" || a == "--version") { std::puts("alphabeta 0.2.1 (MI355X ABneutral path)"); return 0; }
     else {
@@ -135,6 +138,10 @@ int main(int argc, char** argv) {
   }
   if (args.align != alphabeta::Align::None && !args.device_sites) {
     std::fprintf(stderr, "error: --align %s needs --sites device\n", alphabeta::align_name(args.align));
+    return 2;
+  }
+  if (transitions::request().wanted && !ped_file.empty()) {
+    std::fprintf(stderr, "error: --transitions belongs to --nodes and --edges\n");
     return 2;
   }
   if (args.device_sites && !ped_file.empty()) {
@@ -182,12 +189,18 @@ int main(int argc, char** argv) {
       r.analysis.to_file((out / "analysis.txt").string());
       r.raw_analysis.write_npy((out / "raw.npy").string());
     };
+    // --transitions: the k-th pedigree build's table
+    auto report_transitions = [](size_t k, const fs::path& out) {
+      if (transitions::request().wanted) transitions::write_txt((out / "transitions.txt").string(), transitions::request().tables.at(k));
+    };
     if (!resident::one_context(args.contexts)) {  // every context a run of its own, its files in <output>/<CTX>/
+      size_t k = 0;
       run_contexts(args, [&](size_t c, const RunResult& r) {
         const fs::path out = fs::path(args.output) / resident::kContextNames[c];
         fs::create_directories(out);
         std::printf("Context %s\n", resident::kContextNames[c]);
         report(r, out);
+        report_transitions(k++, out);
       });
       return 0;
     }
@@ -202,6 +215,7 @@ int main(int argc, char** argv) {
       r = run(args);
     }
     report(r, fs::path(args.output));
+    report_transitions(0, fs::path(args.output));
   } catch (const Error& e) {
     std::printf("Error: %s\n", e.what());  // src/cli/alphabeta.rs:17 prints and exits 0; a status is more useful
     return 1;

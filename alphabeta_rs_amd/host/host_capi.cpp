@@ -8,6 +8,7 @@
 #include "../csrc/abn_parse.hpp"
 #include "../csrc/abn_route.hpp"
 #include "../csrc/abn_codes.hpp"
+#include "../csrc/abn_pairwise_transitions.hpp"
 #include "../csrc/abn_sites_merge.hpp"
 #include "../csrc/abn_sites_split.hpp"
 #include "../csrc/abn_sites_common.hpp"
@@ -952,5 +953,13 @@ int abh_route_launch_sweep(int n, int k, int t, int lanes, int strict, int spec,
                            r.tail_cap > 0 ? abn::route_tail_resume(p, r.tail_cap).key.R : 0};
   std::memcpy(out, v, sizeof v);
   return r.status;
+}
+// the serial host form of the transitions scan (abn_pairwise_transitions.hpp): table [W][pairs][9] of the windows
+// [begin[w], end[w]) of n packed rows of `stride` bytes
+void abh_transitions_packed(const unsigned char* packed, int n, long long stride, const long long* begin,
+                            const long long* end, int W, unsigned long long* table) {
+  const long long pairs = (long long)n * (n - 1) / 2;
+  for (int w = 0; w < W; ++w)
+    abn::abn_transitions_packed_host(packed, n, stride, begin[w], end[w], (uint64_t*)table + (size_t)w * pairs * 9);
 }
 }

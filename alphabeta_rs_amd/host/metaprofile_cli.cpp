@@ -109,6 +109,7 @@ int main(int argc, char** argv) {
     }
     else if (f == "--regions") tiles.regions = val();
     else if (f == "--pool") tiles.pool = true;
+    else if (f == "--transitions") transitions::request().wanted = true;
     else if (f == "-h" || f == "--help") {
       std::puts("Usage: metaprofile_alphabeta -o <output-dir> [--name N] [-s step] [-w size] [-c cutoff] [-a]\n"
                 "       [--iterations 100] [--max-gene-length L] [--distribution FILE] [--seed S] [--device D]\n"
@@ -140,6 +141,10 @@ int main(int argc, char** argv) {
                 "                            of CG,CHG,CHH [default: CG].  One: the run on that context's sites.  Several: every\n"
                 "                            methylome is parsed once and each context is a run of its own, its files in\n"
                 "                            <output-dir>/<CTX>/\n"
+                "       [--transitions]      with --tiles or --regions: also write transitions.npy (uint64, tiles x pairs x 9: per\n"
+                "                            tile and pair of sampled nodes the sites both keep, by status in the first and in\n"
+                "                            the second sample, UU UI UM IU II IM MU MI MM) and transition_pairs.txt (sample_a,\n"
+                "                            sample_b, generation_a, generation_b per pair); rows as tiles.txt / pools.txt\n"
                 "       [--stream-sweep]     pedigrees too large for the LDS: read a fit's rows once per Nelder-Mead iteration\n"
                 "                            instead of once per cost evaluation; the same output files");
       return 0;
@@ -166,6 +171,10 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "error: %s\n", refused);
       return 2;
     }
+  }
+  if (transitions::request().wanted && !tile_mode) {
+    std::fprintf(stderr, "error: --transitions belongs to --tiles and --regions\n");
+    return 2;
   }
   if (tile_mode) {
     const char* refused = nullptr;
@@ -234,6 +243,7 @@ int main(int argc, char** argv) {
         if (tiles.pool) std::ofstream(dir / "pools.txt") << res.pools_txt;
         else std::ofstream(dir / "tiles.txt") << res.tiles_txt;
         metaprofile::write_raw_npy(res.out, (dir / "raw.npy").string());
+        if (transitions::request().wanted) transitions::write_npy(dir.string(), res.transitions);
       };
       if (resident::one_context(contexts)) {
         write(metaprofile::alphabeta_multiple_tiles(a, tiles, contexts), a.output_dir);

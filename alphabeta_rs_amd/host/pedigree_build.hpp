@@ -7,6 +7,7 @@
 #include <atomic>
 
 #include "alphabeta.hpp"
+#include "transitions.hpp"
 
 namespace alphabeta {
 namespace detail {
@@ -458,6 +459,22 @@ inline Pedigree rows_from(const std::vector<PairTimes>& times, const std::vector
   return ped;
 }
 
+// With --transitions: the table of the build's sampled nodes, appended to transitions::request().  scan(table) fills the
+// [pairs x 9] counts from the code matrix the D matrix came from; samples of different length have no such matrix.
+template <class Scan>
+inline void keep_transitions(const Inputs& in, bool same_len, Scan scan) {
+  if (!transitions::request().wanted) return;
+  if (!same_len) throw Error(ABN_ERR_INVALID_ARG, "--transitions needs the same number of sites in every sample");
+  transitions::Table t;
+  for (const Node& n : in.nodes) {
+    t.names.push_back(n.name);
+    t.generations.push_back(n.generation);
+  }
+  t.counts.assign(t.pairs() * 9, 0);
+  if (t.pairs() > 0) scan(t.counts.data());
+  transitions::request().tables.push_back(std::move(t));
+}
+
 // Pedigree::build; texts: as read_inputs
 inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, const std::string& edgelist,
                                                   double posterior_max_filter, bool gpu_pairwise, bool device_parse,
@@ -487,8 +504,13 @@ inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, c
               "Pedigree::build (pairwise divergence)");
     packed_scan_calls().fetch_add(1, std::memory_order_relaxed);
     dm = dmatrix_of_pairs(nn, dv.data());
+    keep_transitions(in, true, [&](uint64_t* table) {
+      dev.check(abn_pairwise_transitions_packed(dev.get(), packed.data(), (int32_t)nn, (int64_t)L, (int64_t)stride, table),
+                "Pedigree::build (state transitions)");
+    });
   } else {
     dm = dmatrix_on_host(in, posterior_max_filter);
+    keep_transitions(in, in.same_len(), [](uint64_t*) {});  // (fewer than two samples: no pair)
   }
   return {convert(in, dm), in.p0uu};
 }

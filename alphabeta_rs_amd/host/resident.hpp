@@ -185,8 +185,12 @@ inline Inputs inputs_of_resident(Inputs in, const std::vector<windows::ResidentS
     std::vector<double> dv(nn * (nn - 1) / 2);
     dev.check(abn_codes_pairwise(codes.get(), nullptr, nullptr, dv.data()), "Pedigree::build (pairwise divergence)");
     dm = dmatrix_of_pairs(nn, dv.data());
+    keep_transitions(in, true, [&](uint64_t* table) {
+      dev.check(abn_codes_transitions(codes.get(), table), "Pedigree::build (state transitions)");
+    });
     return in;
   }
+  keep_transitions(in, same_len != 0, [](uint64_t*) {});  // (fewer than two samples: no pair)
   // the reference's answer for samples of different length is per pair (:221-227): the host loop gives it
   for (size_t i = 0; i < nn; ++i) {
     const windows::ResidentSites& mine = sites[i];

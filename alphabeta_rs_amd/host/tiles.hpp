@@ -111,6 +111,7 @@ struct TilesOutput {
   Output out;             // results_txt: `window` = the tile's index in the list, `cg_count` = the tile's columns
   std::string tiles_txt;  // tile;chromosome;start;end;cg_count;fitted, every tile of the list
   std::string pools_txt;  // --pool, in its place: pool;name;intervals;segments;cg_count;fitted, every pool
+  transitions::Table transitions;  // --transitions: the table of every tile (pool), fitted or not, in the rows' order
 };
 
 // The sibling of alphabeta_multiple_in_memory for tiles.  args: methylome (directory), nodes, edges, align, iterations,
@@ -194,6 +195,16 @@ inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tile
   dev.check(abn_tiles_stats(th.get(), count.data(), sum.data(), kept.data()), "abn_tiles_stats");
   dev.check(abn_tiles_pairwise(th.get(), nullptr, both.data(), dv.data()), "abn_tiles_pairwise");
 
+  transitions::Table table;
+  if (transitions::request().wanted) {
+    for (const auto& node : graph.nodes) {
+      table.names.push_back(node.name);
+      table.generations.push_back(node.generation);
+    }
+    table.counts.assign(T * npairs * 9, 0);
+    if (npairs > 0) dev.check(abn_tiles_transitions(th.get(), table.counts.data()), "abn_tiles_transitions");
+  }
+
   const std::vector<detail::PairTimes> times = detail::convert_times(graph);
   std::vector<Win> wins;
   for (size_t t = 0; t < T; ++t) {
@@ -213,6 +224,7 @@ inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tile
     }
   }
   TilesOutput res;
+  res.transitions = std::move(table);
   res.out = fit_windows(args, std::move(wins), std::vector<int>());
   std::vector<char> fitted(T, 0);
   res.out.results_txt = results_header();

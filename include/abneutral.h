@@ -309,6 +309,30 @@ int abn_pairwise_divergence_windows_packed_dev(abn_ctx* ctx, const void* dev_pac
                                                const int64_t* site_end, int32_t n_windows, void* dev_diff,
                                                void* dev_both, void* dev_dvalue, double* kernel_ms);
 
+/* The 3 x 3 state transitions of every pair — the joint table behind src/pedigree.rs:236-257, of which `both` and `diff`
+ * are two folds: table[p][3 x + y] = the sites both samples of pair p = (a, b), a < b, keep with status x in sample a and
+ * y in sample b (0 = U, 1 = I, 2 = M), so that both = sum of the nine and diff = sum of |x - y| table[p][3 x + y]; entries 2
+ * (U -> M) and 6 (M -> U) are the observed gains and losses between a and b.  table: uint64 [pairs x 9] in the pair order
+ * above, exact.  Arguments and refusals as abn_pairwise_divergence_packed (nothing is read or written before one); a NULL
+ * table with n_samples >= 2: ABN_ERR_INVALID_ARG.  n_samples < 2: ABN_OK, nothing is written.  n_sites = 0: all zero. */
+int abn_pairwise_transitions_packed(abn_ctx* ctx, const uint8_t* packed, int32_t n_samples, int64_t n_sites,
+                                    int64_t row_stride_bytes, uint64_t* table);
+/* ... on DEVICE-resident packed codes and table: dev_packed 16-byte aligned (else ABN_ERR_INVALID_ARG), dev_table
+ * u64[pairs x 9]; kernel_ms as above.  Returns after the work has completed. */
+int abn_pairwise_transitions_packed_dev(abn_ctx* ctx, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                        int64_t row_stride_bytes, void* dev_table, double* kernel_ms);
+/* ... and of many windows of one packed matrix in one batch (src/cli/metaprofile.rs:50-72): table uint64
+ * [n_windows x pairs x 9], window w's block equal to abn_pairwise_transitions_packed on that window's columns (an empty or
+ * wholly filtered window: all zero).  Arguments and refusals as abn_pairwise_divergence_windows_packed and its _dev form.
+ * n_windows == 0 or n_samples < 2: ABN_OK, nothing is written. */
+int abn_pairwise_transitions_windows_packed(abn_ctx* ctx, const uint8_t* packed, int32_t n_samples, int64_t n_sites,
+                                            int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                                            int32_t n_windows, uint64_t* table);
+int abn_pairwise_transitions_windows_packed_dev(abn_ctx* ctx, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                                int64_t row_stride_bytes, const int64_t* site_begin,
+                                                const int64_t* site_end, int32_t n_windows, void* dev_table,
+                                                double* kernel_ms);
+
 /* ------------------------------------------------------------------ window placement (the `extract` stage)
  * Windows::extract (src/windows.rs:287-343) behind the gene choice: MethylationSite::place_in_windows
  * (src/methylation_site.rs:423-490) for every site of every sample, on the device, straight into the packed matrix
@@ -538,6 +562,9 @@ int abn_codes_packed_device_ptr(abn_codes* h, void** dev_ptr);
  * pairs D = 0 and a message; the caller's business): ABN_ERR_INVALID_ARG with a text that says so, the stats stay valid.
  * n_samples < 2: ABN_OK, nothing is written. */
 int abn_codes_pairwise(abn_codes* h, uint64_t* diff, uint64_t* both, double* dvalue);
+/* ... and abn_pairwise_transitions_packed_dev on it: HOST table uint64 [pairs x 9]; the same refusal of samples that
+ * differ in length.  Under a union alignment the placeholder sites (field 3) count in no entry. */
+int abn_codes_transitions(abn_codes* h, uint64_t* table);
 /* double[4]: the HIP-event times of abn_codes_create_parsed's kernels (the merge of src/pedigree.rs:147-163 — the
  * records' kernel, the inserted lines' — the pack, the fold), each over all samples */
 int abn_codes_kernel_ms(const abn_codes* h, double* ms4);
@@ -680,6 +707,9 @@ int abn_tiles_layout(const abn_tiles* h, int64_t* begin, int64_t* end);         
 int abn_tiles_stats(const abn_tiles* h, int64_t* count /* [T] */, double* level_sum_kept /* [n x T] */,
                     int64_t* kept /* [n x T] */);
 int abn_tiles_pairwise(abn_tiles* h, uint64_t* diff, uint64_t* both, double* dvalue); /* host, [T x pairs] */
+/* abn_pairwise_transitions_windows_packed_dev over the matrix and ranges abn_tiles_pairwise scans (with pools set: the
+ * pooled matrix, one table per pool): HOST table uint64 [T x pairs x 9] */
+int abn_tiles_transitions(abn_tiles* h, uint64_t* table);
 int abn_tiles_kernel_ms(const abn_tiles* h, double* ms2 /* search, fold */);
 
 /* Region pools: one pedigree per annotation CLASS — every gene, every TE, each chromatin state of a list such as the rows
