@@ -78,6 +78,8 @@ EXPORTED_SYMBOLS = [
     "abn_pairwise_transitions_packed", "abn_pairwise_transitions_packed_dev",
     "abn_pairwise_transitions_windows_packed", "abn_pairwise_transitions_windows_packed_dev",
     "abn_codes_transitions", "abn_tiles_transitions",
+    "abn_block_counts", "abn_block_counts_host", "abn_block_resample", "abn_block_resample_dev",
+    "abn_block_resample_host", "abn_tiles_block_bootstrap", "abn_tiles_block_groups", "abn_tiles_block_ms",
 ]
 
 
@@ -282,6 +284,17 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_tiles_pool_segments.argtypes = [vp, i64p, i32p, i32p, i64p, i64p, i64p, i64p]
     L.abn_tiles_pool_columns.argtypes = [vp, i64p]
     L.abn_tiles_pool_kernel_ms.argtypes = [vp, dp]
+    groups = [C.c_int32, i64p, i64p]
+    L.abn_block_counts.argtypes = [vp, C.c_uint64, C.c_int32, u32p, i64p, i64p, C.c_int64, C.c_int64, u8p]
+    L.abn_block_counts_host.argtypes = [*L.abn_block_counts.argtypes[1:], C.c_char_p, C.c_int32]
+    L.abn_block_resample.argtypes = [vp, *groups, C.c_int64, u8p, C.c_int64, C.c_int64, C.c_int32, u64p, u64p, dp, i64p,
+                                     u64p, u64p, dp, dp, i64p]
+    L.abn_block_resample_host.argtypes = [*L.abn_block_resample.argtypes[1:], C.c_char_p, C.c_int32]
+    L.abn_block_resample_dev.argtypes = [vp, *groups, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int32, vp, vp, vp, vp,
+                                         vp, vp, vp, vp, vp, dp]
+    L.abn_tiles_block_bootstrap.argtypes = [vp, C.c_uint64, C.c_int64, u64p, u64p, dp, dp, i64p]
+    L.abn_tiles_block_ms.argtypes = [vp, dp]
+    L.abn_tiles_block_groups.argtypes = [vp, i64p, i64p, i64p, i64p]
     L.abn_genes_create.argtypes = [vp, C.c_int32, i32p, i32p, i64p, u32p, u32p, u8p, C.POINTER(vp)]
     L.abn_genes_destroy.argtypes = [vp]
     L.abn_genes_choose.argtypes = [vp, C.POINTER(GeneRule), C.c_int32, i64p, i32p, u32p, u32p, u8p, u32p, u32p, u8p, dp]
@@ -746,6 +759,44 @@ class Context:
             self._h, C.c_void_p(packed_ptr), n_samples, n_sites, row_stride, b.ctypes.data_as(i64p),
             e.ctypes.data_as(i64p), b.shape[0], C.c_void_p(table_ptr or None), C.byref(ms)))
         return ms.value
+
+    def block_counts(self, seed: int, group_id, group_begin, group_end, n_replicates: int, n_blocks: int) -> np.ndarray:
+        """The block bootstrap's counts, made on the device (abn_block_counts): uint8 (G, n_replicates + 1, n_blocks).
+        Row r < n_replicates of group g is the histogram of T_g draws from the group's blocks [group_begin[g],
+        group_end[g]), a function of (seed, group_id[g], r) alone; the last row is the identity row of ones; zero
+        outside a group's range."""
+        gid, gb, ge = _block_groups(group_begin, group_end, group_id)
+        counts = np.zeros((gb.shape[0], int(n_replicates) + 1 if n_replicates >= 0 else 0, max(int(n_blocks), 0)), dtype=np.uint8)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.abn_block_counts(self._h, int(seed), gb.shape[0], _u32p(gid), gb.ctypes.data_as(i64p),
+                                             ge.ctypes.data_as(i64p), int(n_replicates), int(n_blocks),
+                                             counts.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return counts
+
+    def block_resample(self, group_begin, group_end, counts, both, diff, level_sum_kept, kept):
+        """Every row's sums over its group's blocks (abn_block_resample), exact: counts uint8 (G, rows, T) — drawn by
+        block_counts, or any weights 0 .. 127 such as a jackknife's —, both / diff uint64 (T, pairs), level_sum_kept /
+        kept (n, T).  Returns {both, diff, dvalue: (G, rows, pairs); level, kept: (G, rows, n)}."""
+        a = _block_arguments(group_begin, group_end, counts, both, diff, level_sum_kept, kept)
+        out = _block_outputs(a)
+        self._check(self._L.abn_block_resample(self._h, *_block_pointers(a, out)))
+        return out
+
+    def block_resample_dev(self, group_begin, group_end, rows_per_group: int, counts_ptr: int, n_blocks: int, n_pairs: int,
+                           n_samples: int, both_ptr: int, diff_ptr: int, level_ptr: int, kept_ptr: int, both_out_ptr: int = 0,
+                           diff_out_ptr: int = 0, dvalue_out_ptr: int = 0, level_out_ptr: int = 0,
+                           kept_out_ptr: int = 0) -> np.ndarray:
+        """block_resample on device-resident buffers (raw device pointers; an output of 0 is not wanted).  Returns the
+        HIP-event ms of counts (0 here), digits, product, finish, levels."""
+        _, gb, ge = _block_groups(group_begin, group_end)
+        ms = np.zeros(5)
+        i64p = C.POINTER(C.c_int64)
+        ptr = [C.c_void_p(p or None) for p in (both_ptr, diff_ptr, level_ptr, kept_ptr, both_out_ptr, diff_out_ptr,
+                                                 dvalue_out_ptr, level_out_ptr, kept_out_ptr)]
+        self._check(self._L.abn_block_resample_dev(self._h, gb.shape[0], gb.ctypes.data_as(i64p), ge.ctypes.data_as(i64p),
+                                                   int(rows_per_group), C.c_void_p(counts_ptr or None), int(n_blocks),
+                                                   int(n_pairs), int(n_samples), *ptr, _dp(ms)))
+        return ms
 
     def analyze_batch_dev(self, raw_ptr: int, n_windows: int, n_boot: int, out_ptr: int, first_bad_ptr: int = 0,
                           allow_failed_windows=False) -> float:
@@ -1518,6 +1569,102 @@ class Tiles(_Handle):
         ms = np.zeros(2)
         self.ctx._check(self._L.abn_tiles_kernel_ms(self._h, _dp(ms)))
         return ms
+
+    def block_groups(self):
+        """(group_begin, group_end) of block_bootstrap's groups in block space (abn_tiles_block_groups): with pools set every
+        pool's segments (in pool_segments order), else the one group of all tiles"""
+        G = C.c_int64()
+        self.ctx._check(self._L.abn_tiles_block_groups(self._h, C.byref(G), None, None, None))
+        gb, ge = np.zeros(G.value, dtype=np.int64), np.zeros(G.value, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_tiles_block_groups(self._h, None, None, gb.ctypes.data_as(i64p), ge.ctypes.data_as(i64p)))
+        return gb, ge
+
+    def block_bootstrap(self, seed: int, n_replicates: int):
+        """The block bootstrap of the handle's tiles (abn_tiles_block_bootstrap): the blocks — a pooled handle's merged
+        segments, one group per pool, or the fixed, non-overlapping tiles in one group — drawn with replacement
+        n_replicates times per group; refused on tiles that may overlap.  Returns {both, diff, dvalue: (G, n_replicates +
+        1, pairs); level, kept: (G, n_replicates + 1, n_samples)}; the last row of a group is the observed data."""
+        G = len(self.block_groups()[0])
+        rows, P, n = max(int(n_replicates) + 1, 0), self.n_samples * (self.n_samples - 1) // 2, self.n_samples
+        out = {"both": np.zeros((G, rows, P), dtype=np.uint64), "diff": np.zeros((G, rows, P), dtype=np.uint64),
+               "dvalue": np.zeros((G, rows, P)), "level": np.zeros((G, rows, n)), "kept": np.zeros((G, rows, n), dtype=np.int64)}
+        u64p, i64p = C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
+        self.ctx._check(self._L.abn_tiles_block_bootstrap(self._h, int(seed), int(n_replicates), out["both"].ctypes.data_as(u64p),
+                                                          out["diff"].ctypes.data_as(u64p), _dp(out["dvalue"]), _dp(out["level"]),
+                                                          out["kept"].ctypes.data_as(i64p)))
+        return out
+
+    def block_ms(self) -> np.ndarray:
+        """the HIP-event ms of the last block_bootstrap: counts, digits, product, finish, levels"""
+        ms = np.zeros(5)
+        self.ctx._check(self._L.abn_tiles_block_ms(self._h, _dp(ms)))
+        return ms
+
+
+def _block_groups(group_begin, group_end, group_id=None):
+    gb, ge = (np.ascontiguousarray(a, dtype=np.int64).ravel() for a in (group_begin, group_end))
+    gid = np.arange(gb.shape[0], dtype=np.uint32) if group_id is None else np.ascontiguousarray(group_id, dtype=np.uint32).ravel()
+    if not gb.shape == ge.shape == gid.shape:
+        raise ValueError("group_id, group_begin and group_end differ in length")
+    return gid, gb, ge
+
+
+def _block_arguments(group_begin, group_end, counts, both, diff, level_sum_kept, kept):
+    _, gb, ge = _block_groups(group_begin, group_end)
+    counts = np.ascontiguousarray(counts, dtype=np.uint8)
+    both, diff = np.ascontiguousarray(both, dtype=np.uint64), np.ascontiguousarray(diff, dtype=np.uint64)
+    lsk, kept = _f64(level_sum_kept), np.ascontiguousarray(kept, dtype=np.int64)
+    if counts.ndim != 3 or counts.shape[0] != gb.shape[0]:
+        raise ValueError("counts is (groups, rows, blocks)")
+    T = counts.shape[2]
+    if both.ndim != 2 or both.shape != diff.shape or both.shape[0] != T:
+        raise ValueError("both and diff are (blocks, pairs)")
+    if lsk.ndim != 2 or lsk.shape != kept.shape or lsk.shape[1] != T:
+        raise ValueError("level_sum_kept and kept are (samples, blocks)")
+    return {"gb": gb, "ge": ge, "counts": counts, "both": both, "diff": diff, "lsk": lsk, "kept": kept}
+
+
+def _block_outputs(a):
+    G, rows, _ = a["counts"].shape
+    P, n = a["both"].shape[1], a["lsk"].shape[0]
+    return {"both": np.zeros((G, rows, P), dtype=np.uint64), "diff": np.zeros((G, rows, P), dtype=np.uint64),
+            "dvalue": np.zeros((G, rows, P)), "level": np.zeros((G, rows, n)), "kept": np.zeros((G, rows, n), dtype=np.int64)}
+
+
+def _block_pointers(a, out):
+    """the arguments abn_block_resample and abn_block_resample_host share, behind the context"""
+    i64p, u64p, u8p = C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
+    G, rows, T = a["counts"].shape
+    return (G, a["gb"].ctypes.data_as(i64p), a["ge"].ctypes.data_as(i64p), rows, a["counts"].ctypes.data_as(u8p), T,
+            a["both"].shape[1], a["lsk"].shape[0], a["both"].ctypes.data_as(u64p), a["diff"].ctypes.data_as(u64p),
+            _dp(a["lsk"]), a["kept"].ctypes.data_as(i64p), out["both"].ctypes.data_as(u64p), out["diff"].ctypes.data_as(u64p),
+            _dp(out["dvalue"]), _dp(out["level"]), out["kept"].ctypes.data_as(i64p))
+
+
+def block_resample_host(group_begin, group_end, counts, both, diff, level_sum_kept, kept):
+    """Context.block_resample in its serial host form (abn_block_resample_host): no device needed; the same refusals"""
+    a = _block_arguments(group_begin, group_end, counts, both, diff, level_sum_kept, kept)
+    out = _block_outputs(a)
+    text = C.create_string_buffer(256)
+    rc = load_library().abn_block_resample_host(*_block_pointers(a, out), text, len(text))
+    if rc:
+        raise AbnError(rc, text.value.decode())
+    return out
+
+
+def block_counts_host(seed: int, group_id, group_begin, group_end, n_replicates: int, n_blocks: int) -> np.ndarray:
+    """Context.block_counts in its serial host form (abn_block_counts_host): no device needed; the same refusals"""
+    gid, gb, ge = _block_groups(group_begin, group_end, group_id)
+    counts = np.zeros((gb.shape[0], int(n_replicates) + 1 if n_replicates >= 0 else 0, max(int(n_blocks), 0)), dtype=np.uint8)
+    i64p = C.POINTER(C.c_int64)
+    text = C.create_string_buffer(256)
+    rc = load_library().abn_block_counts_host(int(seed), gb.shape[0], _u32p(gid), gb.ctypes.data_as(i64p), ge.ctypes.data_as(i64p),
+                                              int(n_replicates), int(n_blocks), counts.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              text, len(text))
+    if rc:
+        raise AbnError(rc, text.value.decode())
+    return counts
 
 
 def reduction_tree(generations, options: Options | None = None) -> int:

@@ -17,7 +17,7 @@ LIB = PKG / "libabneutral_hip.so"
 SOURCES = [CSRC / "abn_api.hip", CSRC / "abn_context.hip", CSRC / "abn_plan.hip",  # the fit path: kernels and launchers, host-only, the plan
            CSRC / "abn_pairwise.hip", CSRC / "abn_windows.hip", CSRC / "abn_analyze.hip",
            CSRC / "abn_multi.hip", CSRC / "abn_sites.hip", CSRC / "abn_genes.hip", CSRC / "abn_codes.hip",
-           CSRC / "abn_sites_common.hip", CSRC / "abn_sites_union.hip", CSRC / "abn_tiles.hip",
+           CSRC / "abn_sites_common.hip", CSRC / "abn_sites_union.hip", CSRC / "abn_tiles.hip", CSRC / "abn_blocks.hip",
            CSRC / "abn_resident.hip",  # host-only too: what the builders from resident parse results share
            CSRC / "abn_pack.cpp"]  # host-only: the packed code format (also built alone under the host sanitizers)
 DEPS = [*sorted(CSRC.glob("*.hpp")), CSRC / "abn_philox.h", PKG.parent / "include" / "abneutral.h"]
@@ -87,7 +87,7 @@ def build_host(force: bool = False, verbose: bool = False) -> Path:
     library exposing Pedigree::build to the tests.  Both link libabneutral_hip.so via $ORIGIN rpaths."""
     build_hip()
     srcs = [HOST / "alphabeta_cli.cpp", HOST / "alphabeta.hpp", HOST / "pedigree_build.hpp", HOST / "windows_extract.hpp",
-            HOST / "resident.hpp", HOST / "host_capi.cpp",
+            HOST / "resident.hpp", HOST / "host_capi.cpp", HOST / "block_bootstrap.hpp",
             HOST / "metaprofile.hpp", HOST / "metaprofile_cli.cpp", HOST / "reference_tests.cpp",
             CSRC / "abn_route.hpp", CSRC / "abn_constants.hpp", CSRC / "abn_parse.hpp", CSRC / "abn_genes.hpp",
             CSRC / "abn_sites_merge.hpp", CSRC / "abn_sites_split.hpp", CSRC / "abn_codes.hpp", CSRC / "abn_sites_common.hpp",

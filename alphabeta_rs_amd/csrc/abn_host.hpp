@@ -1,7 +1,7 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (the fit path's abn_api.hip,
 // abn_context.hip and abn_plan.hip, which share abn_fit_host.hpp on top of this; abn_pairwise.hip, abn_windows.hip,
 // abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip, abn_tiles.hip,
-// abn_resident.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
+// abn_resident.hip, abn_blocks.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
 // events of a call, the copies on the context's stream (upload, to_device, to_host), the shell of the windows, codes and
 // tiles handles (created, destroyed, their packed matrix read), and what the consumers of resident methylomes share
 // (abn_resident.hip).  Not part of the C-ABI (include/abneutral.h is).
@@ -301,6 +301,15 @@ int transitions_windows_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n
 int transitions_windows_packed_to_host(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
                                        int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
                                        int32_t n_windows, uint64_t* table);
+// abn_blocks.hip, for abn_tiles_block_bootstrap (abn_tiles.hip): the block bootstrap (abn_blocks.hpp) of DEVICE tables —
+// both, diff [n_blocks x n_pairs], level_sum_kept, kept [n_samples x n_blocks] — behind the checks of the groups: the counts
+// of n_replicates + 1 rows per group made on the device, the sums of every row to the HOST outputs (any may be null), ms5 =
+// the HIP-event times of counts, digits, product, finish and levels.  Returns after completion.
+int blocks_bootstrap_dev(abn_ctx* c, uint64_t seed, int64_t n_groups, const uint32_t* group_id, const int64_t* group_begin,
+                         const int64_t* group_end, int64_t n_replicates, int64_t n_blocks, int64_t n_pairs, int32_t n_samples,
+                         const void* dev_both, const void* dev_diff, const double* dev_level_sum_kept, const int64_t* dev_kept,
+                         uint64_t* both_out, uint64_t* diff_out, double* dvalue_out, double* level_out, int64_t* kept_out,
+                         double* ms5);
 // abn_genes.hip, for abn_windows_create_sites (abn_windows.hip): abn_genes_choose_dev behind its checks of the
 // arguments, and the context a genes handle belongs to.
 int genes_choose_dev(abn_genes* h, const abn_gene_rule* rule, int32_t n_samples, const int64_t* site_offset,

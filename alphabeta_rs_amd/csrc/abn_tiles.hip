@@ -74,6 +74,9 @@ struct abn_tiles {
   PoolSegments segments;
   std::vector<int64_t> seg_begin, seg_end;  // [S] the segments' columns
   double pool_ms[4] = {0.0, 0.0, 0.0, 0.0};  // offsets, map, gather, pack
+  // the block bootstrap (abn_tiles_block_bootstrap): the tiles came from abn_tiles_set_fixed and do not overlap
+  bool fixed_disjoint = false;
+  double block_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // counts, digits, product, finish, levels of the last call
 
   void drop_pools() {
     pooled = false;
@@ -309,6 +312,7 @@ static int tiles_run(abn_tiles* h) {
 
 static int tiles_set(abn_tiles* h, std::vector<int32_t>& chromosome, std::vector<int64_t>& start, std::vector<int64_t>& end) {
   h->has_tiles = false;
+  h->fixed_disjoint = false;
   (void)hipSetDevice(h->ctx->device);
   h->drop_pools();  // back on the handle's own matrix
   h->tchromosome.swap(chromosome);
@@ -353,7 +357,9 @@ extern "C" int abn_tiles_set_fixed(abn_tiles* h, int64_t size, int64_t step) {
     std::vector<int64_t> ts((size_t)T), te((size_t)T);
     tiles_fixed_intervals(h->runs.data(), (int)h->runs.size(), size, step, tc.data(), (long long*)ts.data(),
                           (long long*)te.data());
-    return tiles_set(h, tc, ts, te);
+    const int rc = tiles_set(h, tc, ts, te);
+    h->fixed_disjoint = rc == ABN_OK && (step == 0 || step >= size);
+    return rc;
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
   }
@@ -400,6 +406,7 @@ static int tiles_run_pools(abn_tiles* h, PoolSegments& seg, int32_t n_pools) {
 
   // from here on the handle changes
   h->has_tiles = false;
+  h->fixed_disjoint = false;
   h->drop_pools();
   h->tchromosome.clear(), h->tstart.clear(), h->tend.clear();
   const TileMatrix& own = h->own;
@@ -563,5 +570,73 @@ extern "C" int abn_tiles_transitions(abn_tiles* h, uint64_t* table) {
 extern "C" int abn_tiles_kernel_ms(const abn_tiles* h, double* ms2) {
   if (!h || !ms2) return ABN_ERR_INVALID_ARG;
   std::copy(h->ms, h->ms + 2, ms2);
+  return ABN_OK;
+}
+
+// The groups abn_tiles_block_bootstrap draws in, in block space: every pool's segments, or the one group of all tiles
+extern "C" int abn_tiles_block_groups(const abn_tiles* h, int64_t* n_groups, int64_t* n_blocks, int64_t* group_begin,
+                                      int64_t* group_end) {
+  if (int rc = tiles_need(h)) return rc;
+  const size_t G = h->pooled ? h->begin.size() : 1, S = h->pooled ? h->seg_begin.size() : h->begin.size();
+  if (n_groups) *n_groups = (int64_t)G;
+  if (n_blocks) *n_blocks = (int64_t)S;
+  for (size_t g = 0; g < G; ++g) {
+    if (group_begin) group_begin[g] = h->pooled ? (int64_t)h->segments.seg_first[g] : 0;
+    if (group_end) group_end[g] = h->pooled ? (int64_t)h->segments.seg_first[g + 1] : (int64_t)S;
+  }
+  return ABN_OK;
+}
+
+// The block bootstrap of the handle's tiles (abn_blocks.hpp).  The blocks are the pools' merged segments in segment order,
+// one group per pool, or the fixed tiles in one group; their tables come from the windows scan and the fold over the
+// handle's OWN matrix at the blocks' columns, stay on the device, and go straight into the counts, digits, product, finish
+// and levels chain of blocks_bootstrap_dev: between the scan and the outputs only the flags of the chain cross to the host.
+extern "C" int abn_tiles_block_bootstrap(abn_tiles* h, uint64_t seed, int64_t n_replicates, uint64_t* both_out,
+                                         uint64_t* diff_out, double* dvalue_out, double* level_out, int64_t* kept_out) {
+  if (int rc = tiles_need(h)) return rc;
+  abn_ctx* c = h->ctx;
+  if (!h->pooled && !h->fixed_disjoint)
+    return set_err(c, ABN_ERR_INVALID_ARG,
+                   "the tiles may overlap: the block bootstrap takes pools (abn_tiles_set_pools) or fixed tiles whose step is 0 "
+                   "or at least their size (abn_tiles_set_fixed)");
+  try {
+    const std::vector<int64_t>& bb = h->pooled ? h->seg_begin : h->begin;
+    const std::vector<int64_t>& be = h->pooled ? h->seg_end : h->end;
+    const size_t S = bb.size(), n = (size_t)h->n, P = n * (n - 1) / 2;
+    if (S > 0x7fffffffULL) return set_err(c, ABN_ERR_INVALID_ARG, "more blocks than INT32_MAX");
+    int64_t G = 0;
+    abn_tiles_block_groups(h, &G, nullptr, nullptr, nullptr);
+    std::vector<uint32_t> gid((size_t)G, 0u);
+    std::vector<int64_t> gb((size_t)G, 0), ge((size_t)G, 0);
+    abn_tiles_block_groups(h, nullptr, nullptr, gb.data(), ge.data());
+    for (size_t g = 0; g < gid.size(); ++g) gid[g] = (uint32_t)g;  // group_id = pool (fixed tiles: the one group 0)
+    HIPCHK(c, hipSetDevice(c->device));
+    PoolScope pool_scope(c);
+    DevTiles r;
+    DevBuf<unsigned long long> ddiff, dboth;
+    if (S > 0) {
+      if (int rc = r.alloc(c, n, S)) return rc;
+      if (int rc = to_device(c, r.begin.p, bb.data(), r.begin.bytes())) return rc;
+      if (int rc = to_device(c, r.end.p, be.data(), r.end.bytes())) return rc;
+      if (int rc = tiles_fold(h, h->own, S, r)) return rc;
+      if (P > 0) {
+        HIPCHK(c, ddiff.alloc(S * P));
+        HIPCHK(c, dboth.alloc(S * P));
+        if (int rc = pairwise_windows_packed_dev(c, h->own.packed.p, h->n, h->own.columns, h->own.stride, bb.data(), be.data(),
+                                                 (int32_t)S, ddiff.p, dboth.p, nullptr, nullptr))
+          return rc;
+      }
+    }
+    return blocks_bootstrap_dev(c, seed, (int64_t)gid.size(), gid.data(), gb.data(), ge.data(), n_replicates, (int64_t)S,
+                                (int64_t)P, h->n, dboth.p, ddiff.p, r.sum.p, (const int64_t*)r.kept.p, both_out, diff_out,
+                                dvalue_out, level_out, kept_out, h->block_ms);
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+}
+
+extern "C" int abn_tiles_block_ms(const abn_tiles* h, double* ms5) {
+  if (!h || !ms5) return ABN_ERR_INVALID_ARG;
+  std::copy(h->block_ms, h->block_ms + 5, ms5);
   return ABN_OK;
 }

@@ -26,7 +26,7 @@ int main(int argc, char** argv) {
   std::string devices_arg;
   bool stream_sweep = false;
   metaprofile::TileArgs tiles;
-  bool tiles_given = false, tile_step_given = false, parse_host = false, sites_host = false, contexts_given = false;
+  bool tiles_given = false, tile_step_given = false, block_starts_given = false, parse_host = false, sites_host = false, contexts_given = false;
   unsigned contexts = 1u;
   for (int i = 1; i < argc; ++i) {
     const std::string f = argv[i];
@@ -107,6 +107,18 @@ int main(int argc, char** argv) {
       }
       contexts_given = true;
     }
+    else if (f == "--block-bootstrap" || f == "--block-starts") {
+      const std::string v = val();
+      char* e = nullptr;
+      const long long n = std::strtoll(v.c_str(), &e, 10);
+      const long long most = f == "--block-starts" ? 1000000 : (1ll << 20) - 2;
+      if (v.empty() || *e != 0 || n < 1 || n > most) {
+        std::fprintf(stderr, "error: %s expects a number from 1 to %lld\n", f.c_str(), most);
+        return 2;
+      }
+      if (f == "--block-starts") tiles.block_starts = (int)n, block_starts_given = true;
+      else tiles.block_replicates = n;
+    }
     else if (f == "--regions") tiles.regions = val();
     else if (f == "--pool") tiles.pool = true;
     else if (f == "--transitions") transitions::request().wanted = true;
@@ -145,6 +157,12 @@ int main(int argc, char** argv) {
                 "                            tile and pair of sampled nodes the sites both keep, by status in the first and in\n"
                 "                            the second sample, UU UI UM IU II IM MU MI MM) and transition_pairs.txt (sample_a,\n"
                 "                            sample_b, generation_a, generation_b per pair); rows as tiles.txt / pools.txt\n"
+                "       [--block-bootstrap R [--block-starts S]]  with --regions FILE --pool (one group per pool) or --tiles SIZE\n"
+                "                            whose tiles do not overlap (one group, `genome`): draw the blocks - a pool's merged\n"
+                "                            segments, the genome's tiles - with replacement R times per group, refit every draw\n"
+                "                            from S starts [default 10], and write block_bootstrap.txt (per group alpha and beta\n"
+                "                            of the observed data, sd and percentile CI of the draws) and block_raw.npy (R x 7 x\n"
+                "                            groups); the other files stay as they are; one device\n"
                 "       [--stream-sweep]     pedigrees too large for the LDS: read a fit's rows once per Nelder-Mead iteration\n"
                 "                            instead of once per cost evaluation; the same output files");
       return 0;
@@ -167,6 +185,20 @@ int main(int argc, char** argv) {
     if (parse_host || sites_host) refused = "--contexts keeps the sites on the device: --parse host and --sites host do not apply";
     else if (a.methylome.empty()) refused = "--contexts belongs to --methylome with --tiles or --regions, not to window directories";
     else if (!tile_mode) refused = "--contexts belongs to --tiles and --regions, not to the gene windows of --genome";
+    if (refused) {
+      std::fprintf(stderr, "error: %s\n", refused);
+      return 2;
+    }
+  }
+  if (tiles.block_replicates > 0 || block_starts_given) {
+    const char* refused = nullptr;
+    if (tiles.block_replicates == 0) refused = "--block-starts belongs to --block-bootstrap";
+    else if (!tile_mode) refused = "--block-bootstrap belongs to --regions FILE --pool and to --tiles SIZE";
+    else if (!tiles.regions.empty() && !tiles.pool)
+      refused = "--block-bootstrap with --regions needs --pool: the rows of a region list may overlap";
+    else if (tiles_given && tiles.step != 0 && tiles.step < tiles.size)
+      refused = "--block-bootstrap needs tiles that do not overlap: a --tile-step of at least the tile size";
+    else if (devices_arg.find(',') != std::string::npos) refused = "--block-bootstrap runs on one device: --devices names several";
     if (refused) {
       std::fprintf(stderr, "error: %s\n", refused);
       return 2;
@@ -244,6 +276,10 @@ int main(int argc, char** argv) {
         else std::ofstream(dir / "tiles.txt") << res.tiles_txt;
         metaprofile::write_raw_npy(res.out, (dir / "raw.npy").string());
         if (transitions::request().wanted) transitions::write_npy(dir.string(), res.transitions);
+        if (tiles.block_replicates > 0) {
+          std::ofstream(dir / "block_bootstrap.txt") << res.block.txt;
+          metaprofile::write_block_raw_npy(res.block, (dir / "block_raw.npy").string());
+        }
       };
       if (resident::one_context(contexts)) {
         write(metaprofile::alphabeta_multiple_tiles(a, tiles, contexts), a.output_dir);

@@ -12,6 +12,7 @@
 
 #include <unordered_map>
 
+#include "block_bootstrap.hpp"
 #include "metaprofile.hpp"
 
 namespace alphabeta {
@@ -21,6 +22,8 @@ struct TileArgs {
   int64_t size = 0, step = 0;  // --tiles SIZE [--tile-step STEP]: fixed tiles (step 0: size)
   std::string regions;         // --regions FILE: a list
   bool pool = false;           // --pool: the rows of the list that share a name are one pool, one pedigree (region_pools)
+  int64_t block_replicates = 0;  // --block-bootstrap R (0: none) and --block-starts S (block_bootstrap.hpp)
+  int block_starts = kBlockStartsDefault;
   bool fixed() const { return regions.empty(); }
 };
 
@@ -112,6 +115,7 @@ struct TilesOutput {
   std::string tiles_txt;  // tile;chromosome;start;end;cg_count;fitted, every tile of the list
   std::string pools_txt;  // --pool, in its place: pool;name;intervals;segments;cg_count;fitted, every pool
   transitions::Table transitions;  // --transitions: the table of every tile (pool), fitted or not, in the rows' order
+  BlockBootstrap block;            // --block-bootstrap: block_bootstrap.txt and block_raw.npy
 };
 
 // The sibling of alphabeta_multiple_in_memory for tiles.  args: methylome (directory), nodes, edges, align, iterations,
@@ -226,6 +230,9 @@ inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tile
   TilesOutput res;
   res.transitions = std::move(table);
   res.out = fit_windows(args, std::move(wins), std::vector<int>());
+  if (tiles.block_replicates > 0)  // the blocks drawn with replacement: a pool's segments, or the genome's tiles in one group
+    res.block = block_bootstrap(th.get(), tiles.pool ? pools.names : std::vector<std::string>{"genome"}, times, sample_of, nn,
+                                tiles.block_replicates, tiles.block_starts);
   std::vector<char> fitted(T, 0);
   res.out.results_txt = results_header();
   for (const WindowResult& r : res.out.results) {

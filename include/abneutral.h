@@ -739,6 +739,59 @@ int abn_tiles_pool_segments(const abn_tiles* h, int64_t* n_segments, int32_t* po
 int abn_tiles_pool_columns(const abn_tiles* h, int64_t* src);
 int abn_tiles_pool_kernel_ms(const abn_tiles* h, double* ms4 /* offsets, map, gather, pack */);
 
+/* Block bootstrap: the uncertainty of a rate estimated for a pool of regions or a tiled genome, where the reference has only
+ * the residual bootstrap of one pedigree's rows (src/boot_model.rs:43-57; the observed site counts stay fixed there).  T
+ * blocks in G groups, group g the contiguous ascending block range [group_begin[g], group_end[g]); per group R + 1 rows of
+ * counts, rows 0 .. R - 1 drawn with replacement (draw j of row r: block group_begin + index_from(word j % 4 of
+ * philox4x32_10(j / 4, r, group_id[g], 4, seed_lo, seed_hi), T_g): a row depends on neither R nor G), row R the identity row
+ * of ones.  Every row's sums stand in for DMatrix::from and the rc_meth_lvl fold over the drawn blocks' sites
+ * (src/pedigree.rs:236-257, :159-172): both* = sum_t c both[t], diff* likewise (exact), dvalue* = diff* / (2 both*) (0 / 0 is
+ * NaN), level* = sum_t (double)c level_sum_kept[s][t] serially in ascending t (product, then add), kept* = sum_t c kept[s][t].
+ * Tables: both, diff uint64 [T x P]; level_sum_kept double, kept int64 [n x T].  Counts: uint8 [G x rows x T], group-major,
+ * read inside a group's range alone.  Outputs: both_out, diff_out, dvalue_out [G x rows x P], level_out, kept_out
+ * [G x rows x n]; any may be NULL.  ABN_ERR_INVALID_ARG with a text, before any launch: a table value >= 2^35, a group of
+ * more than 2^21 blocks, R > 2^20 - 2, G > 4096, null pointers, negative sizes, unordered or overlapping group ranges, a
+ * count above 127 (abn_block_counts: raised by the kernel, probability below 1e-200; device arguments: found by the
+ * kernels, the outputs are then no result).  An empty group is no error: sums 0, dvalue NaN.
+ * abn_block_counts: the counts of R replicates and the identity row, made on the device, to the HOST buffer counts
+ * [G x (R + 1) x n_blocks], zero outside a group's range.  abn_block_counts_host: its serial form, no device; `text`
+ * (text_bytes, may be NULL) takes a refusal's text.
+ * abn_block_resample: explicit counts (a jackknife's as well) and HOST buffers.  abn_block_resample_dev: the same on DEVICE
+ * pointers (group_begin and group_end stay host arrays), ms5 (may be NULL): the HIP-event times of counts (0 here), digits,
+ * product, finish, levels.  abn_block_resample_host: the serial form, no device, refusals as abn_block_counts_host. */
+int abn_block_counts(abn_ctx* ctx, uint64_t seed, int32_t n_groups, const uint32_t* group_id, const int64_t* group_begin,
+                     const int64_t* group_end, int64_t n_replicates, int64_t n_blocks, uint8_t* counts);
+int abn_block_counts_host(uint64_t seed, int32_t n_groups, const uint32_t* group_id, const int64_t* group_begin,
+                          const int64_t* group_end, int64_t n_replicates, int64_t n_blocks, uint8_t* counts, char* text,
+                          int32_t text_bytes);
+int abn_block_resample(abn_ctx* ctx, int32_t n_groups, const int64_t* group_begin, const int64_t* group_end,
+                       int64_t rows_per_group, const uint8_t* counts, int64_t n_blocks, int64_t n_pairs, int32_t n_samples,
+                       const uint64_t* both, const uint64_t* diff, const double* level_sum_kept, const int64_t* kept,
+                       uint64_t* both_out, uint64_t* diff_out, double* dvalue_out, double* level_out, int64_t* kept_out);
+int abn_block_resample_dev(abn_ctx* ctx, int32_t n_groups, const int64_t* group_begin, const int64_t* group_end,
+                           int64_t rows_per_group, const void* dev_counts, int64_t n_blocks, int64_t n_pairs,
+                           int32_t n_samples, const void* dev_both, const void* dev_diff, const void* dev_level_sum_kept,
+                           const void* dev_kept, void* dev_both_out, void* dev_diff_out, void* dev_dvalue_out,
+                           void* dev_level_out, void* dev_kept_out, double* ms5);
+int abn_block_resample_host(int32_t n_groups, const int64_t* group_begin, const int64_t* group_end, int64_t rows_per_group,
+                            const uint8_t* counts, int64_t n_blocks, int64_t n_pairs, int32_t n_samples, const uint64_t* both,
+                            const uint64_t* diff, const double* level_sum_kept, const int64_t* kept, uint64_t* both_out,
+                            uint64_t* diff_out, double* dvalue_out, double* level_out, int64_t* kept_out, char* text,
+                            int32_t text_bytes);
+/* The block bootstrap of a tiles handle, HOST outputs [G x (R + 1) x pairs] and [G x (R + 1) x n] (any may be NULL).  With
+ * pools set the blocks are the pools' merged segments in abn_tiles_pool_segments order and the groups the pools (group_id =
+ * pool); after abn_tiles_set_fixed with step 0 or step >= size the blocks are the tiles, one group of id 0.  The blocks'
+ * tables come from the windows scan and the per-(sample, block) fold over the handle's own matrix and never leave the
+ * device.  Refused (ABN_ERR_INVALID_ARG) after abn_tiles_set_intervals and after a fixed tiling with 0 < step < size: the
+ * blocks may overlap.  abn_tiles_block_ms: double[5], the HIP-event times of the last call's counts, digits, product,
+ * finish and levels. */
+int abn_tiles_block_bootstrap(abn_tiles* h, uint64_t seed, int64_t n_replicates, uint64_t* both_out, uint64_t* diff_out,
+                              double* dvalue_out, double* level_out, int64_t* kept_out);
+/* the groups of that call in block space: *n_groups, *n_blocks and [n_groups] the groups' block ranges (any may be NULL) */
+int abn_tiles_block_groups(const abn_tiles* h, int64_t* n_groups, int64_t* n_blocks, int64_t* group_begin,
+                           int64_t* group_end);
+int abn_tiles_block_ms(const abn_tiles* h, double* ms5);
+
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
  * src/cli/metaprofile.rs:50-72, where every window shares nodelist/edgelist), S starts and B bootstraps
