@@ -75,6 +75,7 @@ EXPORTED_SYMBOLS = [
     "abn_tiles_kernel_ms",
     "abn_tiles_set_pools", "abn_tiles_pool_segments", "abn_tiles_pool_columns", "abn_tiles_pool_kernel_ms",
     "abn_sites_context", "abn_sites_insert_ctx", "abn_sites_split", "abn_sites_split_ms",
+    "abn_sites_sort", "abn_sites_sort_order", "abn_sites_sort_info", "abn_sites_sort_keys", "abn_sites_sort_keys_dev",
     "abn_pairwise_transitions_packed", "abn_pairwise_transitions_packed_dev",
     "abn_pairwise_transitions_windows_packed", "abn_pairwise_transitions_windows_packed_dev",
     "abn_codes_transitions", "abn_tiles_transitions",
@@ -245,6 +246,11 @@ def load_library(build_if_missing: bool = False) -> C.CDLL:
     L.abn_sites_context.argtypes = [vp, C.POINTER(C.c_int32), u8p]
     L.abn_sites_split.argtypes = [vp, C.POINTER(vp)]
     L.abn_sites_split_ms.argtypes = [vp, dp]
+    L.abn_sites_sort.argtypes = [vp, C.POINTER(vp)]
+    L.abn_sites_sort_order.argtypes = [vp, i64p, i64p]
+    L.abn_sites_sort_info.argtypes = [vp, i64p, dp]
+    L.abn_sites_sort_keys.argtypes = [vp, C.c_int64, C.POINTER(C.c_int32), u32p, u32p, u8p, i64p, i64p]
+    L.abn_sites_sort_keys_dev.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, i64p, dp]
     L.abn_windows_create_parsed.argtypes = [vp, C.POINTER(WindowsParams), vp, C.POINTER(GeneRule), C.c_double, C.c_int32,
                                             C.POINTER(vp), C.POINTER(vp)]
     L.abn_windows_merge_ms.argtypes = [vp, dp]
@@ -875,6 +881,19 @@ class Context:
                                              u[3].ctypes.data_as(u8p), keep.ctypes.data_as(u8p), C.byref(n_common)))
         return keep, n_common.value
 
+    def sort_sites(self, chromosome, start, end, strand):
+        """The stable permutation of one sample's keys into canonical order — ascending chromosome, start, end, strand — on
+        the device (abn_sites_sort_keys).  Returns (order int64 (n,), info): info = {sites, descents, equal, passes} as
+        Sites.sort_info.  AbnError for a chromosome outside 0..257 or a strand above 2."""
+        n = np.asarray(chromosome).reshape(-1).shape[0]
+        _, u = _site_arrays([0, n], chromosome, start, end, strand)
+        order, info = np.zeros(n, dtype=np.int64), np.zeros(4, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.abn_sites_sort_keys(self._h, n, u[0].ctypes.data_as(C.POINTER(C.c_int32)), _u32p(u[1]), _u32p(u[2]),
+                                                u[3].ctypes.data_as(C.POINTER(C.c_uint8)), order.ctypes.data_as(i64p),
+                                                info.ctypes.data_as(i64p)))
+        return order, {"sites": int(info[0]), "descents": int(info[1]), "equal": int(info[2]), "passes": int(info[3])}
+
     def union_sites(self, site_offset, chromosome, start, end, strand):
         """The union of the samples' sites, by key (chromosome, start, end, strand), on the device (abn_sites_union: the
         per-pair comparison of src/pedigree.rs:240-254 for samples that hold different sites).  Arguments as common_sites.
@@ -1165,6 +1184,30 @@ class Sites(_Handle):
         ms = np.zeros(2)
         self.ctx._check(self._L.abn_sites_split_ms(self._h, _dp(ms)))
         return float(ms[0]), float(ms[1])
+
+    def sort(self) -> "Sites":
+        """A new resident handle with this handle's sites — device records and inserted ones — in canonical order:
+        ascending chromosome key, start, end, strand, equal keys in file order (abn_sites_sort: a stable radix sort on the
+        device).  Its lines are 0 .. n_sites - 1; it goes into Windows.from_parsed, Codes.from_parsed, Tiles and split() as
+        it is.  This handle stays usable."""
+        out = C.c_void_p()
+        self.ctx._check(self._L.abn_sites_sort(self._h, C.byref(out)))
+        return Sites(self.ctx, out)
+
+    def sort_order(self) -> np.ndarray:
+        """of a handle sort() made: the index, in the parent's fetch(), of every site (abn_sites_sort_order)"""
+        n = C.c_int64()
+        self.ctx._check(self._L.abn_sites_sort_order(self._h, C.byref(n), None))
+        order = np.zeros(n.value, dtype=np.int64)
+        self.ctx._check(self._L.abn_sites_sort_order(self._h, None, order.ctypes.data_as(C.POINTER(C.c_int64))))
+        return order
+
+    def sort_info(self):
+        """of a handle sort() made: {sites, descents, equal (neighbours of the input), passes (radix passes run), ms: the
+        HIP-event ms of flatten, check, passes, gather}"""
+        info, ms = np.zeros(4, dtype=np.int64), np.zeros(4)
+        self.ctx._check(self._L.abn_sites_sort_info(self._h, info.ctypes.data_as(C.POINTER(C.c_int64)), _dp(ms)))
+        return {"sites": int(info[0]), "descents": int(info[1]), "equal": int(info[2]), "passes": int(info[3]), "ms": ms}
 
     def fetch(self):
         """the sites in file order as a dict of arrays (Context.parse_sites' fields); a resident handle downloads them and
@@ -1665,6 +1708,34 @@ def block_counts_host(seed: int, group_id, group_begin, group_end, n_replicates:
     if rc:
         raise AbnError(rc, text.value.decode())
     return counts
+
+
+_host_lib = None
+
+
+def load_host_library():
+    """libabneutral_host.so: the C++ host layer's serial forms (host/host_capi.cpp), built beside the HIP library"""
+    global _host_lib
+    if _host_lib is None:
+        from . import build as _build
+        if not _build.PEDIGREE_LIB.exists():
+            _build.build_host()
+        _host_lib = C.CDLL(str(_build.PEDIGREE_LIB))
+    return _host_lib
+
+
+def sort_sites_host(chromosome, start, end, strand):
+    """Context.sort_sites in its serial host form (abn_sites_sort_keys_host): no device needed; the same refusals, and
+    info's passes = the radix passes the device would run"""
+    n = np.asarray(chromosome).reshape(-1).shape[0]
+    _, u = _site_arrays([0, n], chromosome, start, end, strand)
+    order, info = np.zeros(n, dtype=np.int64), np.zeros(4, dtype=np.int64)
+    H = load_host_library()
+    H.abn_sites_sort_keys_host.argtypes = [C.c_longlong] + [C.c_void_p] * 6
+    rc = H.abn_sites_sort_keys_host(n, *(a.ctypes.data for a in (*u, order, info)))
+    if rc:
+        raise AbnError(rc, "a chromosome outside 0..257 or a strand above 2")
+    return order, {"sites": int(info[0]), "descents": int(info[1]), "equal": int(info[2]), "passes": int(info[3])}
 
 
 def reduction_tree(generations, options: Options | None = None) -> int:

@@ -1,7 +1,7 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (the fit path's abn_api.hip,
 // abn_context.hip and abn_plan.hip, which share abn_fit_host.hpp on top of this; abn_pairwise.hip, abn_windows.hip,
 // abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip, abn_tiles.hip,
-// abn_resident.hip, abn_blocks.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
+// abn_resident.hip, abn_blocks.hip, abn_sites_sort.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
 // events of a call, the copies on the context's stream (upload, to_device, to_host), the shell of the windows, codes and
 // tiles handles (created, destroyed, their packed matrix read), and what the consumers of resident methylomes share
 // (abn_resident.hip).  Not part of the C-ABI (include/abneutral.h is).
@@ -21,6 +21,7 @@
 
 #include "../../include/abneutral.h"
 #include "abn_sites_common.hpp"
+#include "abn_sites_sort.hpp"
 #include "abn_sites_union.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -327,6 +328,20 @@ int sites_merge_dev(const abn_sites* h, bool inserted, double filter, int32_t* d
 // ... and for abn_codes_create_parsed (abn_codes.hip): the same merge in its reduced form (abn_codes.hpp), the merged byte
 // and the level of every site
 int sites_merge_codes_dev(const abn_sites* h, bool inserted, double filter, uint8_t* dcode, double* dlevel);
+// abn_sites.hip, for abn_sites_sort.hip: abn_parse_scan_kernel with a workgroup per row — the n counts at data + r * stride
+// scanned in place (exclusive), their sum at entry n — for rows r = 0 .. rows - 1; nothing waited for
+int sites_scan_rows(abn_ctx* c, uint32_t* data, uint32_t rows, uint32_t n, uint32_t stride);
+// abn_sites_sort.hip, for abn_sites_sort (abn_sites.hip), all on the context's stream.  The flatten of one chunk's records
+// and of the inserted records (dcontext: their context codes) into `out`, nothing waited for; sort_flat_dev: the check and
+// the passes over the n flattened records, dorder [n] the permutation, info4 as abn_sites_sort_info, ms2 the HIP-event ms
+// of the check and of the passes — returns after completion; the gather of the n records at dorder into `out`, nothing
+// waited for
+int sort_flatten_records_dev(abn_ctx* c, const MergeChunk& chunk, const long long* dinserted_line, long long n_inserted,
+                             const SortFlat& out);
+int sort_flatten_inserted_dev(abn_ctx* c, const MergeChunk* dchunks, const MergeInserted& ins, const uint8_t* dcontext,
+                              const SortFlat& out);
+int sort_flat_dev(abn_ctx* c, long long n, const SortFlat& flat, uint32_t* dorder, int64_t* info4, double* ms2);
+int sort_gather_dev(abn_ctx* c, const SortFlat& in, const uint32_t* dorder, long long n, const ParseRecords& out);
 // abn_codes.hip, for abn_tiles.hip too: the pack of n samples' merged bytes (sample s: dcode + dcode_off[s], a multiple of
 // 16; dsite_off[s + 1] - dsite_off[s] sites) into dpacked [n x 4 row_dwords bytes]
 int codes_pack_dev(abn_ctx* c, const uint8_t* dcode, const long long* dcode_off, const long long* dsite_off, int n,

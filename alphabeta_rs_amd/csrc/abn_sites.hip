@@ -4,18 +4,19 @@
 // (abn_sites_parse_dev, abn_sites_insert) keeps the records on the device for abn_windows_create_parsed (abn_windows.hip;
 // its merge kernels: abn_sites_merge.hpp) and for abn_codes_create_parsed (abn_codes.hip; its reduced merge kernels:
 // abn_codes.hpp).  A handle parsed under a mask of several contexts is partitioned into one ordinary resident handle per
-// context by abn_sites_split (its kernels: abn_sites_split.hpp).
+// context by abn_sites_split (its kernels: abn_sites_split.hpp), and sorted by genomic position into a new resident handle
+// by abn_sites_sort (its kernels: abn_sites_sort.hpp, launched from abn_sites_sort.hip).
 //
 // In this file: a site as the host reports it (SiteRecord, SiteOut, SiteIn, SiteColumns); the records on the device
-// (RecordBufs, SiteChunk, InsertedBufs); the handle; the parse; what a handle reports; the insert; the split; the merge
-// launches of the builders.
+// (RecordBufs, SiteChunk, InsertedBufs); the handle; the parse; what a handle reports; the insert; the split; the sort;
+// the merge launches of the builders.
+#define ABN_SITES_MERGE_KERNELS  // (in front of abn_host.hpp: it includes abn_sites_merge.hpp through abn_sites_sort.hpp)
+#define ABN_CODES_MERGE_KERNELS
+#define ABN_SITES_SPLIT_KERNELS
 #include "abn_host.hpp"
 #include "abn_parse_kernels.hpp"
-#define ABN_SITES_MERGE_KERNELS
 #include "abn_sites_merge.hpp"
-#define ABN_CODES_MERGE_KERNELS
 #include "abn_codes.hpp"
-#define ABN_SITES_SPLIT_KERNELS
 #include "abn_sites_split.hpp"
 
 using namespace abn;
@@ -199,6 +200,12 @@ struct abn_sites {
   std::vector<int64_t> flagged;                    // the file lines of the records with a status_flag
   bool inserted = false;
   InsertedBufs ins;
+  // a handle abn_sites_sort made: order[k] = the parent's site at its place k; {sites, descents, equal neighbours, passes};
+  // the HIP-event ms of flatten, check, passes, gather
+  bool sorted = false;
+  DevBuf<uint32_t> sort_order;
+  int64_t sort_info[4] = {0, 0, 0, 0};
+  double sort_ms[4] = {0.0, 0.0, 0.0, 0.0};
   // one more chunk: the slab of n_lines lines from file line line0, behind the records held so far ...
   SiteChunk* add_chunk(int64_t line0, int64_t n_lines_) {
     chunks.emplace_back(new SiteChunk);
@@ -673,6 +680,109 @@ extern "C" int abn_sites_split(const abn_sites* h, abn_sites** out3) {
 extern "C" int abn_sites_split_ms(const abn_sites* h, double* ms2) {
   if (!h || !ms2) return ABN_ERR_INVALID_ARG;
   ms2[0] = h->split_ms[0], ms2[1] = h->split_ms[1];
+  return ABN_OK;
+}
+
+// ---- abn_sites_sort (kernels and the sort itself: abn_sites_sort.hpp, abn_sites_sort.hip)
+int abn::sites_scan_rows(abn_ctx* c, uint32_t* data, uint32_t rows, uint32_t n, uint32_t stride) {
+  hipLaunchKernelGGL(abn_parse_scan_kernel, dim3(rows), dim3(kParseScanThreads), 0, c->stream, data, n, stride);
+  HIPCHK(c, hipGetLastError());
+  return ABN_OK;
+}
+
+namespace {
+
+int sites_sort(const abn_sites* h, abn_sites* kid) {
+  abn_ctx* c = h->ctx;
+  const int64_t n = h->n_records + (int64_t)h->cols.size();
+  kid->ctx = c, kid->device = h->device;
+  kid->mask = h->mask;
+  kid->n_lines = n;
+  kid->inserted = kid->sorted = true;
+  SiteChunk* chunk = kid->add_chunk(0, n);
+  kid->chunk_records(chunk, n);
+  kid->sort_info[0] = n;
+  if (n == 0) return ABN_OK;
+  const size_t N = (size_t)n;
+  DevBuf<uint32_t> fmeta, fstart, fend;
+  DevBuf<double> fpm, fml;
+  DevBuf<uint8_t> dcontext;
+  HIPCHK(c, fmeta.alloc(N));
+  HIPCHK(c, fstart.alloc(N));
+  HIPCHK(c, fend.alloc(N));
+  HIPCHK(c, fpm.alloc(N));
+  HIPCHK(c, fml.alloc(N));
+  HIPCHK(c, kid->sort_order.alloc(N));
+  HIPCHK(c, chunk->rec.alloc(N, 0));
+  const SortFlat flat{fmeta.p, fstart.p, fend.p, fpm.p, fml.p};
+  const MergeInserted ins = h->ins.ref();
+  if (ins.n > 0)
+    if (int rc = upload(c, dcontext, h->cols.context.data(), h->cols.context.size())) return rc;
+  EventPair ev;
+  if (int rc = ev.begin(c, true)) return rc;
+  for (const auto& src : h->chunks)
+    if (int rc = sort_flatten_records_dev(c, src->ref(), ins.line, ins.n, flat)) return rc;
+  if (int rc = sort_flatten_inserted_dev(c, h->ins.chunks.p, ins, dcontext.p, flat)) return rc;
+  if (int rc = ev.end(c, &kid->sort_ms[0])) return rc;
+  if (int rc = sort_flat_dev(c, n, flat, kid->sort_order.p, kid->sort_info, &kid->sort_ms[1])) return rc;
+  if (int rc = ev.begin(c, true)) return rc;
+  if (int rc = sort_gather_dev(c, flat, kid->sort_order.p, n, chunk->rec.records())) return rc;
+  if (int rc = ev.end(c, &kid->sort_ms[3])) return rc;
+  if (!h->flagged.empty()) {  // rare: the ranks of the parent's flagged records, from the sorted meta words
+    std::vector<uint32_t> meta(N);
+    if (int rc = to_host(c, meta.data(), chunk->rec.meta)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < N; ++k)
+      if (meta_status_flag(meta[k])) kid->flagged.push_back((int64_t)k);
+  }
+  return ABN_OK;
+}
+
+}  // namespace
+
+extern "C" int abn_sites_sort(const abn_sites* h, abn_sites** out) {
+  if (out) *out = nullptr;
+  if (!h || !h->ctx) return ABN_ERR_INVALID_ARG;  // (a host-form handle has no context to report to)
+  abn_ctx* c = h->ctx;
+  if (!out) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (!h->dline.empty() && !h->inserted)
+    return set_err(c, ABN_ERR_INVALID_ARG, "abn_sites_sort: the handle has deferred lines and abn_sites_insert was never called");
+  if (h->n_records + (int64_t)h->cols.size() >= (int64_t)1 << 32)
+    return set_err(c, ABN_ERR_INVALID_ARG, "abn_sites_sort: 2^32 records or more");
+  HIPCHK(c, hipSetDevice(c->device));
+  PoolScope pool_scope(c);
+  std::unique_ptr<abn_sites> kid(new (std::nothrow) abn_sites);
+  if (!kid) return set_err(c, ABN_ERR_HIP, "out of host memory");
+  try {
+    if (int rc = sites_sort(h, kid.get())) return rc;
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+  *out = kid.release();
+  return ABN_OK;
+}
+
+extern "C" int abn_sites_sort_order(const abn_sites* sorted, int64_t* n, int64_t* order) {
+  if (!sorted || !sorted->sorted) return ABN_ERR_INVALID_ARG;
+  abn_ctx* c = sorted->ctx;
+  if (n) *n = sorted->n_records;
+  if (!order || sorted->n_records == 0) return ABN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  try {
+    std::vector<uint32_t> o((size_t)sorted->n_records);
+    if (int rc = to_host(c, o.data(), sorted->sort_order)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < o.size(); ++k) order[k] = (int64_t)o[k];
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+  return ABN_OK;
+}
+
+extern "C" int abn_sites_sort_info(const abn_sites* sorted, int64_t* info4, double* ms4) {
+  if (!sorted || !sorted->sorted) return ABN_ERR_INVALID_ARG;
+  if (info4) std::copy(sorted->sort_info, sorted->sort_info + 4, info4);
+  if (ms4) std::copy(sorted->sort_ms, sorted->sort_ms + 4, ms4);
   return ABN_OK;
 }
 

@@ -392,8 +392,10 @@ class Pedigree {  // src/pedigree.rs:44-45
                                                                          // (abn_codes_create_aligned), p0uu the fold over
                                                                          // those; Union: pair by pair on the sites both
                                                                          // hold (abn_codes_create_union), p0uu unchanged
-                                           unsigned contexts = 1u);      // (with device_sites) the methylation contexts
+                                           unsigned contexts = 1u,       // (with device_sites) the methylation contexts
                                                                          // whose lines are sites: 1 CG, 2 CHG, 4 CHH
+                                           bool sort = false);           // (with device_sites) every methylome sorted by
+                                                                         // genomic position on the device (abn_sites_sort)
   // ... for many (nodelist, edgelist) pairs at once (the windows of src/cli/metaprofile.rs:50-72): with gpu_pairwise ONE
   // abn_pairwise_divergence_windows_packed call per batch of entries with the same number of samples, on 2-bit codes
   // packed straight from the site records.  A batch ends at kBuildManyCodeBytes of PACKED codes per call (four sites per
@@ -512,6 +514,8 @@ struct Args {  // arguments::AlphaBeta, src/arguments.rs:93-114
                               // all share | pair by pair on the sites both hold
   unsigned contexts = 1u;     // --contexts LIST (with --sites device): the methylation contexts fitted, 1 CG | 2 CHG | 4 CHH;
                               // several: each is a run of its own (run_contexts) on one parse of every methylome
+  bool sort = false;          // --sort (with --sites device): every methylome is sorted by genomic position on the device
+                              // behind its parse (abn_sites_sort), so files in any line order are aligned
 };
 
 struct RunResult {
@@ -577,7 +581,7 @@ namespace alphabeta {
 inline RunResult run(const Args& args) {
   std::printf("Building pedigree...\n");
   auto [pedigree, p0uu] = Pedigree::build(args.nodes, args.edges, args.posterior_max_filter, /*gpu_pairwise=*/true,
-                                          args.device_parse, args.device_sites, args.align, args.contexts);
+                                          args.device_parse, args.device_sites, args.align, args.contexts, args.sort);
   return run_on_pedigree(std::move(pedigree), p0uu, args.iterations, args.output);
 }
 
@@ -587,7 +591,8 @@ inline RunResult run(const Args& args) {
 template <class Done>
 inline void run_contexts(const Args& args, Done done) {
   std::printf("Building pedigrees...\n");
-  auto built = detail::build_pedigrees_by_context(args.nodes, args.edges, args.posterior_max_filter, args.align, args.contexts);
+  auto built = detail::build_pedigrees_by_context(args.nodes, args.edges, args.posterior_max_filter, args.align, args.contexts,
+                                                  args.sort);
   for (size_t c = 0; c < 3; ++c)
     if ((args.contexts >> c) & 1u)
       done(c, run_on_pedigree(std::move(built[c].first), built[c].second, args.iterations, args.output));

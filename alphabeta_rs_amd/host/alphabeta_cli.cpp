@@ -45,6 +45,10 @@ static void usage() {
       "                                 --sites device).  One: the run on that context's sites.  Several: every methylome\n"
       "                                 is parsed once and each context is a run of its own, its files in <OUTPUT>/<CTX>/\n"
       "                                 [default: CG]\n"
+      "      --sort                     sort every methylome by chromosome, start, end and strand on the device behind its\n"
+      "                                 parse, so files in any line order are compared and aligned; a file that was out of\n"
+      "                                 order is named in one line; the same output files as for the files sorted\n"
+      "                                 beforehand (needs --sites device) [default: off]\n"
       "      --transitions              also write <OUTPUT>/transitions.txt: per pair of sampled nodes the sites both keep,\n"
       "                                 by status in the first and in the second sample (UU UI UM IU II IM MU MI MM)\n"
       "  -h, --help                    Print help\n"
@@ -120,6 +124,7 @@ int main(int argc, char** argv) {
       }
       contexts_given = true;
     }
+    else if (a == "--sort") args.sort = true;
     else if (a == "--transitions") transitions::request().wanted = true;
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (a == "-V" || a == "--version") { std::puts("alphabeta 0.2.1 (MI355X ABneutral path)"); return 0; }
@@ -130,6 +135,14 @@ int main(int argc, char** argv) {
   }
   if (contexts_given && !(args.device_sites && args.device_parse)) {
     std::fprintf(stderr, "error: --contexts needs --sites device and --parse device\n");
+    return 2;
+  }
+  if (args.sort && !(args.device_sites && args.device_parse)) {
+    std::fprintf(stderr, "error: --sort needs --sites device and --parse device\n");
+    return 2;
+  }
+  if (args.sort && !ped_file.empty()) {
+    std::fprintf(stderr, "error: --sort belongs to --nodes and --edges: a pedigree file holds no methylome\n");
     return 2;
   }
   if (args.device_sites && !args.device_parse) {

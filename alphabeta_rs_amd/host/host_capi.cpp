@@ -11,6 +11,7 @@
 #include "../csrc/abn_pairwise_transitions.hpp"
 #include "../csrc/abn_sites_merge.hpp"
 #include "../csrc/abn_sites_split.hpp"
+#include "../csrc/abn_sites_sort.hpp"
 #include "../csrc/abn_sites_common.hpp"
 #include "../csrc/abn_sites_union.hpp"
 #include "../csrc/abn_tiles.hpp"
@@ -388,6 +389,40 @@ long long abh_sites_split_serial(int n_chunks, unsigned contexts, const long lon
   abn::split_scatter_serial(chunks.data(), n_chunks, contexts, count.data(), stride, n_blocks);
   return n_blocks;
 }
+// ---- the sort by genomic position (csrc/abn_sites_sort.hpp) in its serial forms, for tests/test_sites_sort_cpu.py,
+// tests/test_sites_sort_gpu.py and scripts/sort_ab.py
+// abn_sites_sort_keys on the host: order [n] = the stable permutation into canonical order, info4 = {n, descents, equal
+// neighbours, the radix passes the device would run}.  1: a chromosome outside 0..257, a strand above 2, n < 0 or >= 2^32
+int abn_sites_sort_keys_host(long long n, const int* chromosome, const unsigned* start, const unsigned* end,
+                             const unsigned char* strand, long long* order, long long* info4) {
+  if (n < 0 || n >= (1ll << 32)) return 1;
+  for (long long i = 0; i < n; ++i)
+    if (!abn::sort_key_valid(chromosome[i], strand[i])) return 1;
+  std::vector<abn::SortPair> pair((size_t)n);
+  const abn::SortCheck check = abn::sort_check_serial(n, chromosome, start, end, strand, pair.data());
+  abn::sort_pairs_serial(pair.data(), n);
+  for (long long k = 0; k < n; ++k) order[k] = pair[(size_t)k].index;
+  info4[0] = n, info4[1] = check.descents, info4[2] = check.equal, info4[3] = abn::sort_passes_needed(check);
+  return 0;
+}
+// ... as the kernels walk it (sort_walk_serial): tile histograms, row scans and the scatter's ranks from per-wavefront
+// counts; skip 0 runs every pass of an input with a descent.  info4[3] = the passes run
+int abh_sites_sort_walk(long long n, const int* chromosome, const unsigned* start, const unsigned* end,
+                        const unsigned char* strand, int skip, long long* order, long long* info4) {
+  std::vector<abn::SortPair> a((size_t)n), b((size_t)n);
+  const abn::SortCheck check = abn::sort_check_serial(n, chromosome, start, end, strand, a.data());
+  int passes = 0;
+  const abn::SortPair* r = abn::sort_walk_serial(a.data(), b.data(), n, check, skip != 0, &passes);
+  for (long long k = 0; k < n; ++k) order[k] = r[k].index;
+  info4[0] = n, info4[1] = check.descents, info4[2] = check.equal, info4[3] = passes;
+  return 0;
+}
+// the digit pass `pass` reads of a key; the scatter kernel's tile; the passes of the whole key
+unsigned abh_sites_sort_digit(int chromosome, unsigned start, unsigned end, unsigned strand, int pass) {
+  return abn::sort_digit(abn::sort_key((unsigned)chromosome, start, end, strand).w, pass);
+}
+int abh_sites_sort_tile() { return abn::kSortTile; }
+int abh_sites_sort_passes() { return abn::kSortPasses; }
 // parse_sites_device of a text on the default device (slab_bytes as abn_sites_params) -> the arrays of abh_parse_sites;
 // warnings (capacity wcap) = what it printed.  Returns the number of sites, -1: they do not fit, -2: the call threw
 long long abh_parse_sites_device(const char* text, long long len, long long skip_lines, long long slab_bytes,

@@ -119,6 +119,7 @@ int main(int argc, char** argv) {
       if (f == "--block-starts") tiles.block_starts = (int)n, block_starts_given = true;
       else tiles.block_replicates = n;
     }
+    else if (f == "--sort") a.sort = true;
     else if (f == "--regions") tiles.regions = val();
     else if (f == "--pool") tiles.pool = true;
     else if (f == "--transitions") transitions::request().wanted = true;
@@ -153,6 +154,11 @@ int main(int argc, char** argv) {
                 "                            of CG,CHG,CHH [default: CG].  One: the run on that context's sites.  Several: every\n"
                 "                            methylome is parsed once and each context is a run of its own, its files in\n"
                 "                            <output-dir>/<CTX>/\n"
+                "       [--sort]             with --tiles or --regions, or with --genome --sites device: sort every methylome by\n"
+                "                            chromosome, start, end and strand on the device behind its parse, so files in any\n"
+                "                            line order (sorted by strand first, contigs in pieces, chromosomes in another order)\n"
+                "                            are tiled and aligned; a file that was out of order is named in one line; the same\n"
+                "                            output files as for the files sorted beforehand [default: off]\n"
                 "       [--transitions]      with --tiles or --regions: also write transitions.npy (uint64, tiles x pairs x 9: per\n"
                 "                            tile and pair of sampled nodes the sites both keep, by status in the first and in\n"
                 "                            the second sample, UU UI UM IU II IM MU MI MM) and transition_pairs.txt (sample_a,\n"
@@ -185,6 +191,16 @@ int main(int argc, char** argv) {
     if (parse_host || sites_host) refused = "--contexts keeps the sites on the device: --parse host and --sites host do not apply";
     else if (a.methylome.empty()) refused = "--contexts belongs to --methylome with --tiles or --regions, not to window directories";
     else if (!tile_mode) refused = "--contexts belongs to --tiles and --regions, not to the gene windows of --genome";
+    if (refused) {
+      std::fprintf(stderr, "error: %s\n", refused);
+      return 2;
+    }
+  }
+  if (a.sort) {
+    const char* refused = nullptr;
+    if (parse_host || sites_host) refused = "--sort sorts the sites on the device: --parse host and --sites host do not apply";
+    else if (a.methylome.empty()) refused = "--sort belongs to --methylome, not to window directories";
+    else if (!tile_mode && !a.device_sites) refused = "--sort with the gene windows of --genome needs --sites device";
     if (refused) {
       std::fprintf(stderr, "error: %s\n", refused);
       return 2;

@@ -29,17 +29,36 @@ inline std::vector<abn_sites*> pointers(const std::vector<windows::ResidentSites
 // contexts: the methylation contexts whose lines are sites (1 CG, 2 CHG, 4 CHH; the reference reads CG alone).  Under
 // several, every methylome is still read and parsed once: split() partitions each on the device (abn_sites_split) and hands
 // out one handle set per context, each what a load under that context alone would hold.
+// sort (--sort): each methylome, parsed and its deferred lines inserted as ever — the warnings name the file's own lines —
+// is then sorted by genomic position on the device (abn_sites_sort) and the parent dropped: only the sorted handle is
+// kept, and a split of it is sorted too (the split is stable).  sort_report gets one line, with its '\n', per sample that
+// had a descent; the driver prints them next to the alignment report.
 struct Samples {
   Device& dev;
   size_t skip_lines;
   std::vector<windows::ResidentSites> sites;
   unsigned contexts = 1u;
-  void add_text(const std::string& text) {
-    sites.push_back(windows::parse_sites_resident(dev, text, skip_lines, /*slab_bytes=*/0, contexts));
+  bool sort = false;
+  std::vector<std::string> sort_report;
+  void add_text(const std::string& text, const std::string& name = std::string()) {
+    windows::ResidentSites parsed = windows::parse_sites_resident(dev, text, skip_lines, /*slab_bytes=*/0, contexts);
+    if (!sort) {
+      sites.push_back(std::move(parsed));
+      return;
+    }
+    abn_sites* sorted = nullptr;
+    dev.check(abn_sites_sort(parsed.get(), &sorted), "abn_sites_sort");
+    sites.emplace_back(sorted);
+    int64_t info[4] = {0, 0, 0, 0};
+    dev.check(abn_sites_sort_info(sorted, info, nullptr), "abn_sites_sort_info");
+    if (info[1] > 0)
+      sort_report.push_back("Sorted by position: " + name + ": " + std::to_string(info[0]) + " sites, " + std::to_string(info[1]) +
+                            " descents\n");
   }
-  void add_file(const std::string& path) {  // a sampled node's file (src/pedigree.rs:147-150)
+  // a sampled node's file (src/pedigree.rs:147-150); name: what the sort's line calls it
+  void add_file(const std::string& path, const std::string& name = std::string()) {
     if (!std::ifstream(path)) throw Error(ABN_ERR_INVALID_ARG, "Could not open node file: " + path);
-    add_text(detail::read_file(path, "methylome"));
+    add_text(detail::read_file(path, "methylome"), name.empty() ? path : name);
   }
   std::vector<abn_sites*> pointers() const { return resident::pointers(sites); }
   // [c] = every sample's sites of context c, in the samples' order; empty for a context outside the mask
@@ -145,14 +164,15 @@ inline Handle::Handle(Device& dev, const abn_windows_params& p, const Genome& ge
 
 namespace detail {
 // the sampled nodes' methylomes as resident handles, in the nodes' order, parsed under `contexts`
-inline resident::Samples load_resident(const Inputs& in, const std::vector<std::string>* texts, unsigned contexts) {
+inline resident::Samples load_resident(const Inputs& in, const std::vector<std::string>* texts, unsigned contexts, bool sort) {
   const size_t nn = in.nodes.size();
   if (texts && texts->size() != nn) throw Error(ABN_ERR_INVALID_ARG, "one text per sampled node");
-  resident::Samples samples{default_device(), /*skip_lines=*/0, {}, contexts};
+  resident::Samples samples{default_device(), /*skip_lines=*/0, {}, contexts, sort};
   for (size_t i = 0; i < nn; ++i) {
-    if (texts) samples.add_text((*texts)[i]);
+    if (texts) samples.add_text((*texts)[i], in.nodes[i].file);
     else samples.add_file(in.nodes[i].file);
   }
+  for (const std::string& line : samples.sort_report) diag_printf("%s", line.c_str());
   return samples;
 }
 
@@ -208,9 +228,9 @@ inline Inputs inputs_of_resident(Inputs in, const std::vector<windows::ResidentS
 
 inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
                                    std::vector<double>& dm, const std::vector<std::string>* texts, Align align,
-                                   unsigned contexts) {
+                                   unsigned contexts, bool sort) {
   Inputs in = read_graph(nodelist, edgelist);
-  const resident::Samples samples = load_resident(in, texts, contexts);
+  const resident::Samples samples = load_resident(in, texts, contexts, sort);
   return inputs_of_resident(std::move(in), samples.sites, posterior_max_filter, dm, align);
 }
 
@@ -220,9 +240,9 @@ inline Inputs read_inputs_resident(const std::string& nodelist, const std::strin
 inline std::array<std::pair<Pedigree, double>, 3> build_pedigrees_by_context(const std::string& nodelist,
                                                                              const std::string& edgelist,
                                                                              double posterior_max_filter, Align align,
-                                                                             unsigned contexts) {
+                                                                             unsigned contexts, bool sort = false) {
   const Inputs graph = read_graph(nodelist, edgelist);
-  const auto by_context = load_resident(graph, nullptr, contexts).split();
+  const auto by_context = load_resident(graph, nullptr, contexts, sort).split();
   std::array<std::pair<Pedigree, double>, 3> out;
   for (size_t c = 0; c < 3; ++c) {
     if (!((contexts >> c) & 1u)) continue;

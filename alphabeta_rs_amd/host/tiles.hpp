@@ -132,13 +132,14 @@ struct TileSamples {
 };
 inline TileSamples load_tile_samples(const WindowArgs& args, unsigned contexts) {
   namespace fs = std::filesystem;
-  TileSamples s{detail::read_graph(args.nodes, args.edges), {}, {}, resident::Samples{default_device(), /*skip_lines=*/0, {}, contexts}};
+  TileSamples s{detail::read_graph(args.nodes, args.edges), {}, {}, resident::Samples{default_device(), /*skip_lines=*/0, {}, contexts, args.sort}};
   if (s.graph.nodes.empty()) throw Error(ABN_ERR_INVALID_ARG, "the nodelist names no sampled node");
   for (const auto& node : s.graph.nodes) {
     s.sample_of.push_back(s.names.size());
     s.names.push_back(resident::base_name(node.file));
-    s.samples.add_file((fs::path(args.methylome) / s.names.back()).string());
+    s.samples.add_file((fs::path(args.methylome) / s.names.back()).string(), s.names.back());
   }
+  for (const std::string& line : s.samples.sort_report) std::fputs(line.c_str(), stdout);
   return s;
 }
 

@@ -515,6 +515,40 @@ int abn_sites_split(const abn_sites* h, abn_sites** out3);
 /* double[2]: the HIP-event times of abn_sites_split's count and scatter kernels — of the last split of h, or of the
  * split that made h; 0, 0 otherwise */
 int abn_sites_split_ms(const abn_sites* h, double* ms2);
+/* ---- sorting a resident methylome by genomic position
+ * The CANONICAL ORDER is ascending in chromosome key (0..255, M = 256, C = 257), then start, then end, then strand
+ * (0 Sense, 1 Antisense, 2 Unknown); equal keys keep their file order.  Inside a chromosome it is the order the
+ * alignments ask for, and the chromosomes come in the order of their keys in every sample.
+ * abn_sites_sort: the stable radix sort of a RESIDENT handle's sites on the device.  *out becomes a new, ordinary resident
+ * handle of h's context and mask that holds exactly h's sites — device records and inserted ones — in canonical order:
+ * with order[k] the index of its k-th site in abn_sites_fetch(h), every field of abn_sites_fetch(*out) and of
+ * abn_sites_context(*out) is h's at order, and the line of site k is k.  It has one chunk of n_lines = n_sites lines, no
+ * deferred lines, counts as inserted, and its flagged lines are the ranks of h's flagged records — what
+ * abn_sites_parse_dev with skip_lines 0 holds for the text of h's accepted lines in canonical order.  An input without a
+ * descent runs no sort pass.  h is not consumed; *out is destroyed with abn_sites_destroy (before its context).
+ * ABN_ERR_INVALID_ARG: null pointers, a host-form handle, a handle with deferred lines on which abn_sites_insert(_ctx)
+ * was never called, 2^32 records or more. */
+int abn_sites_sort(const abn_sites* h, abn_sites** out);
+/* The permutation of a handle abn_sites_sort made: *n its sites, order [*n] the index of every site in the parent's
+ * abn_sites_fetch; either may be NULL.
+ * ABN_ERR_INVALID_ARG: a null handle, a handle abn_sites_sort did not make. */
+int abn_sites_sort_order(const abn_sites* sorted, int64_t* n, int64_t* order);
+/* What the sort that made `sorted` did: info4 = {sites, descents (a key below its predecessor's), equal neighbours — both
+ * of the input —, radix passes run}; ms4 = the HIP-event times of the flatten, the check, the sort passes and the
+ * gather.  Either may be NULL.
+ * ABN_ERR_INVALID_ARG: a null handle, a handle abn_sites_sort did not make. */
+int abn_sites_sort_info(const abn_sites* sorted, int64_t* info4, double* ms4);
+/* The sort itself on one sample's raw key arrays of HOST memory, [n] each: order [n] receives the stable permutation into
+ * canonical order, info4 as abn_sites_sort_info.
+ * ABN_ERR_INVALID_ARG: null pointers with n > 0, a null info4, n < 0 or n >= 2^32, a chromosome outside 0..257 or a
+ * strand above 2 (checked on the host, before any launch). */
+int abn_sites_sort_keys(abn_ctx* ctx, int64_t n, const int32_t* chromosome, const uint32_t* start, const uint32_t* end,
+                        const uint8_t* strand, int64_t* order, int64_t* info4);
+/* ... on DEVICE key arrays (int32, uint32, uint32, uint8); dev_order: uint32 [n] on the device; ms2 (may be NULL) = the
+ * HIP-event times of the check and of the sort passes.  Returns after the work has completed.
+ * ABN_ERR_INVALID_ARG: as abn_sites_sort_keys; the key ranges are checked by the check kernel, and no pass runs then. */
+int abn_sites_sort_keys_dev(abn_ctx* ctx, int64_t n, const void* dev_chromosome, const void* dev_start, const void* dev_end,
+                            const void* dev_strand, void* dev_order, int64_t* info4, double* ms2);
 /* abn_windows_create_sites fed from RESIDENT handles (src/windows.rs:303-339 whole, for n_samples methylomes): sample s is
  * samples[s]; its records and inserted lines are merged in file order on the device into the arrays the gene choice and
  * the placement read — chromosome, start, end, strand, code = status | 0x80 when posteriormax < posterior_max_filter
