@@ -9,11 +9,10 @@ sys.path.insert(0, str(ROOT))
 lib = ROOT / "gpurun_out" / "libabneutral_hip_stamps.so"
 lib.parent.mkdir(exist_ok=True)
 import alphabeta_rs_amd as A
-from alphabeta_rs_amd import build as B
+from alphabeta_rs_amd import _ffi, build as B
 subprocess.run([B.hipcc_path(), *B.HIPCC_FLAGS, "-DABN_STAMPS", "-DABN_MEASUREMENT_KNOBS", "-o", str(lib),
                 *map(str, B.SOURCES)], check=True)
-A.LIB_PATH = lib
-A._lib = None
+_ffi.use_library(lib)
 L = A.load_library()
 L.abn_plan_debug_stamps.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
 from alphabeta_rs_amd import synthetic

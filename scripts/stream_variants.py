@@ -13,9 +13,8 @@ def worker(lib, boots):
     sys.path.insert(0, str(ROOT))
     import numpy as np
     import alphabeta_rs_amd as A
-    from alphabeta_rs_amd import synthetic
-    A.LIB_PATH = Path(lib)
-    A._lib = None
+    from alphabeta_rs_amd import _ffi, synthetic
+    _ffi.use_library(lib)
     ctx = A.Context(0)
     ped, p0 = synthetic.c5_pedigree()
     plan = A.Plan(ctx, ped[:, :3], 1, 4, boots, options=A.default_options())

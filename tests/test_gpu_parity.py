@@ -214,6 +214,7 @@ def test_plan_multi_window_matches_per_window_runs(abn, gpu_ctx, golden, oracle)
     cnt = plan.counters()
     assert cnt["fits"] == W * (S + B)
     assert cnt["evals"] == out["info_a"]["evals"].sum() + out["info_b"]["evals"].sum()
+    assert plan.device_bytes() > 0 and plan.raw_device_ptr() != 0
     for w in range(W):
         pw = ped.copy()
         pw[:, 3] = D[w]
