@@ -6,7 +6,8 @@ library is missing or no HIP device is usable, calls raise.  PyTorch is used by 
 
 Python-level names mirror the reference crate: `Pedigree`, `Model`, `ab_neutral.run`, `boot_model.run`.  The binding
 is one module per handle family — _ffi (prototypes, loaders, helpers), context, plan, sites, matrices, blocks — and this
-module re-exports their names.
+module re-exports their names; alphabeta_rs_amd.dedup (the collapse of repeated sites) is a module of functions, imported
+by its own name.
 """
 from ._ffi import (ABN_OK, EXPORTED_SYMBOLS, FIT_CONVERGED, FIT_INFO_DTYPE, FIT_MAX_ITERS, FIT_NONFINITE, FIT_TARGET,
                    KERNEL_NAMES, LIB_PATH, PKG, STATUS_NAMES, AbnError, GeneRule, Options, SitesParams, WindowsParams,

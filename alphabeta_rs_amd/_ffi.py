@@ -167,6 +167,11 @@ def _prototypes():
         "abn_sites_sort_info": (ci, [vp, i64p, dp]),
         "abn_sites_sort_keys": (ci, [vp, i64, i32p, u32p, u32p, u8p, i64p, i64p]),
         "abn_sites_sort_keys_dev": (ci, [vp, i64, vp, vp, vp, vp, vp, i64p, dp]),
+        "abn_sites_dedup": (ci, [vp, ci, vpp]),
+        "abn_sites_dedup_order": (ci, [vp, i64p, i64p]),
+        "abn_sites_dedup_info": (ci, [vp, i64p, dp]),
+        "abn_sites_dedup_keys": (ci, [vp, i64, i32p, u32p, u32p, u8p, dp, u8p, ci, i64p, i64p]),
+        "abn_sites_dedup_keys_dev": (ci, [vp, i64, vp, vp, vp, vp, vp, vp, ci, vp, i64p, dp]),
         "abn_windows_create_parsed": (ci, [vp, wp, vp, gp, f64, i32, vpp, vpp]),
         "abn_windows_merge_ms": (ci, [vp, dp]),
         "abn_codes_create_parsed": (ci, [vp, f64, i32, vpp, vpp]),

@@ -1,7 +1,7 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (the fit path's abn_api.hip,
 // abn_context.hip and abn_plan.hip, which share abn_fit_host.hpp on top of this; abn_pairwise.hip, abn_windows.hip,
 // abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip, abn_tiles.hip,
-// abn_resident.hip, abn_blocks.hip, abn_sites_sort.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
+// abn_resident.hip, abn_blocks.hip, abn_sites_sort.hip, abn_sites_dedup.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
 // events of a call, the copies on the context's stream (upload, to_device, to_host), the shell of the windows, codes and
 // tiles handles (created, destroyed, their packed matrix read), and what the consumers of resident methylomes share
 // (abn_resident.hip).  Not part of the C-ABI (include/abneutral.h is).
@@ -21,6 +21,7 @@
 
 #include "../../include/abneutral.h"
 #include "abn_sites_common.hpp"
+#include "abn_sites_dedup.hpp"
 #include "abn_sites_sort.hpp"
 #include "abn_sites_union.hpp"
 
@@ -342,6 +343,13 @@ int sort_flatten_inserted_dev(abn_ctx* c, const MergeChunk* dchunks, const Merge
                               const SortFlat& out);
 int sort_flat_dev(abn_ctx* c, long long n, const SortFlat& flat, uint32_t* dorder, int64_t* info4, double* ms2);
 int sort_gather_dev(abn_ctx* c, const SortFlat& in, const uint32_t* dorder, long long n, const ParseRecords& out);
+// abn_sites_dedup.hip, for abn_sites_dedup (abn_sites.hip), on the context's stream.  dedup_flat_dev: the flags and the
+// compaction over the n flattened records under `policy`, dorder (room for n) the kept records' indices, info4 as
+// abn_sites_dedup_info, ms2 the HIP-event ms of the flags and of the compaction — returns after completion; the gather of
+// the `kept` records at dorder, of n_in, into `out`, nothing waited for
+int dedup_flat_dev(abn_ctx* c, long long n, const SortFlat& flat, int policy, uint32_t* dorder, int64_t* info4, double* ms2);
+int dedup_gather_dev(abn_ctx* c, const SortFlat& in, const uint32_t* dorder, long long kept, long long n_in,
+                     const ParseRecords& out);
 // abn_codes.hip, for abn_tiles.hip too: the pack of n samples' merged bytes (sample s: dcode + dcode_off[s], a multiple of
 // 16; dsite_off[s + 1] - dsite_off[s] sites) into dpacked [n x 4 row_dwords bytes]
 int codes_pack_dev(abn_ctx* c, const uint8_t* dcode, const long long* dcode_off, const long long* dsite_off, int n,

@@ -4,11 +4,12 @@
 // (abn_sites_parse_dev, abn_sites_insert) keeps the records on the device for abn_windows_create_parsed (abn_windows.hip;
 // its merge kernels: abn_sites_merge.hpp) and for abn_codes_create_parsed (abn_codes.hip; its reduced merge kernels:
 // abn_codes.hpp).  A handle parsed under a mask of several contexts is partitioned into one ordinary resident handle per
-// context by abn_sites_split (its kernels: abn_sites_split.hpp), and sorted by genomic position into a new resident handle
-// by abn_sites_sort (its kernels: abn_sites_sort.hpp, launched from abn_sites_sort.hip).
+// context by abn_sites_split (its kernels: abn_sites_split.hpp), sorted by genomic position into a new resident handle
+// by abn_sites_sort (its kernels: abn_sites_sort.hpp, launched from abn_sites_sort.hip), and its repeated sites collapsed
+// into another by abn_sites_dedup (abn_sites_dedup.hpp, abn_sites_dedup.hip).
 //
 // In this file: a site as the host reports it (SiteRecord, SiteOut, SiteIn, SiteColumns); the records on the device
-// (RecordBufs, SiteChunk, InsertedBufs); the handle; the parse; what a handle reports; the insert; the split; the sort;
+// (RecordBufs, SiteChunk, InsertedBufs); the handle; the parse; what a handle reports; the insert; the split; the sort and the collapse;
 // the merge launches of the builders.
 #define ABN_SITES_MERGE_KERNELS  // (in front of abn_host.hpp: it includes abn_sites_merge.hpp through abn_sites_sort.hpp)
 #define ABN_CODES_MERGE_KERNELS
@@ -206,6 +207,12 @@ struct abn_sites {
   DevBuf<uint32_t> sort_order;
   int64_t sort_info[4] = {0, 0, 0, 0};
   double sort_ms[4] = {0.0, 0.0, 0.0, 0.0};
+  // a handle abn_sites_dedup made: order[k] = the parent's site kept at its place k, ascending; {sites, kept, repeated
+  // keys, disagreeing neighbours}; the HIP-event ms of flatten, flags, scan, gather
+  bool deduped = false;
+  DevBuf<uint32_t> dedup_order;
+  int64_t dedup_info[4] = {0, 0, 0, 0};
+  double dedup_ms[4] = {0.0, 0.0, 0.0, 0.0};
   // one more chunk: the slab of n_lines lines from file line line0, behind the records held so far ...
   SiteChunk* add_chunk(int64_t line0, int64_t n_lines_) {
     chunks.emplace_back(new SiteChunk);
@@ -692,29 +699,24 @@ int abn::sites_scan_rows(abn_ctx* c, uint32_t* data, uint32_t rows, uint32_t n, 
 
 namespace {
 
-int sites_sort(const abn_sites* h, abn_sites* kid) {
+// What abn_sites_sort and abn_sites_dedup share.  The flattened records of a handle: its sites in file order with their
+// whole record
+struct FlatBufs {
+  DevBuf<uint32_t> meta, start, end;
+  DevBuf<double> pm, ml;
+  SortFlat ref() const { return SortFlat{meta.p, start.p, end.p, pm.p, ml.p}; }
+};
+
+// the flatten of h's N > 0 sites into f; *ms = its HIP-event ms
+int sites_flatten(const abn_sites* h, size_t N, FlatBufs& f, double* ms) {
   abn_ctx* c = h->ctx;
-  const int64_t n = h->n_records + (int64_t)h->cols.size();
-  kid->ctx = c, kid->device = h->device;
-  kid->mask = h->mask;
-  kid->n_lines = n;
-  kid->inserted = kid->sorted = true;
-  SiteChunk* chunk = kid->add_chunk(0, n);
-  kid->chunk_records(chunk, n);
-  kid->sort_info[0] = n;
-  if (n == 0) return ABN_OK;
-  const size_t N = (size_t)n;
-  DevBuf<uint32_t> fmeta, fstart, fend;
-  DevBuf<double> fpm, fml;
   DevBuf<uint8_t> dcontext;
-  HIPCHK(c, fmeta.alloc(N));
-  HIPCHK(c, fstart.alloc(N));
-  HIPCHK(c, fend.alloc(N));
-  HIPCHK(c, fpm.alloc(N));
-  HIPCHK(c, fml.alloc(N));
-  HIPCHK(c, kid->sort_order.alloc(N));
-  HIPCHK(c, chunk->rec.alloc(N, 0));
-  const SortFlat flat{fmeta.p, fstart.p, fend.p, fpm.p, fml.p};
+  HIPCHK(c, f.meta.alloc(N));
+  HIPCHK(c, f.start.alloc(N));
+  HIPCHK(c, f.end.alloc(N));
+  HIPCHK(c, f.pm.alloc(N));
+  HIPCHK(c, f.ml.alloc(N));
+  const SortFlat flat = f.ref();
   const MergeInserted ins = h->ins.ref();
   if (ins.n > 0)
     if (int rc = upload(c, dcontext, h->cols.context.data(), h->cols.context.size())) return rc;
@@ -723,38 +725,103 @@ int sites_sort(const abn_sites* h, abn_sites* kid) {
   for (const auto& src : h->chunks)
     if (int rc = sort_flatten_records_dev(c, src->ref(), ins.line, ins.n, flat)) return rc;
   if (int rc = sort_flatten_inserted_dev(c, h->ins.chunks.p, ins, dcontext.p, flat)) return rc;
-  if (int rc = ev.end(c, &kid->sort_ms[0])) return rc;
-  if (int rc = sort_flat_dev(c, n, flat, kid->sort_order.p, kid->sort_info, &kid->sort_ms[1])) return rc;
-  if (int rc = ev.begin(c, true)) return rc;
-  if (int rc = sort_gather_dev(c, flat, kid->sort_order.p, n, chunk->rec.records())) return rc;
-  if (int rc = ev.end(c, &kid->sort_ms[3])) return rc;
-  if (!h->flagged.empty()) {  // rare: the ranks of the parent's flagged records, from the sorted meta words
-    std::vector<uint32_t> meta(N);
-    if (int rc = to_host(c, meta.data(), chunk->rec.meta)) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t k = 0; k < N; ++k)
-      if (meta_status_flag(meta[k])) kid->flagged.push_back((int64_t)k);
-  }
+  return ev.end(c, ms);  // (waits: dcontext may go)
+}
+
+// the child of h that both make: h's context and mask, one chunk of n lines that are its n records, counted as inserted
+SiteChunk* sites_child(const abn_sites* h, abn_sites* kid, int64_t n) {
+  kid->ctx = h->ctx, kid->device = h->device;
+  kid->mask = h->mask;
+  kid->n_lines = n;
+  kid->inserted = true;
+  SiteChunk* chunk = kid->add_chunk(0, n);
+  kid->chunk_records(chunk, n);
+  return chunk;
+}
+
+// rare: the ranks of the parent's flagged records among the child's N, from the child's meta words
+int sites_child_flagged(const abn_sites* h, abn_sites* kid, const SiteChunk* chunk, size_t N) {
+  if (h->flagged.empty() || N == 0) return ABN_OK;
+  abn_ctx* c = h->ctx;
+  std::vector<uint32_t> meta(N);
+  if (int rc = to_host(c, meta.data(), chunk->rec.meta)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < N; ++k)
+    if (meta_status_flag(meta[k])) kid->flagged.push_back((int64_t)k);
   return ABN_OK;
 }
 
-}  // namespace
+int sites_sort(const abn_sites* h, abn_sites* kid) {
+  abn_ctx* c = h->ctx;
+  const int64_t n = h->n_records + (int64_t)h->cols.size();
+  SiteChunk* chunk = sites_child(h, kid, n);
+  kid->sorted = true;
+  kid->sort_info[0] = n;
+  if (n == 0) return ABN_OK;
+  const size_t N = (size_t)n;
+  FlatBufs f;
+  HIPCHK(c, kid->sort_order.alloc(N));
+  HIPCHK(c, chunk->rec.alloc(N, 0));
+  if (int rc = sites_flatten(h, N, f, &kid->sort_ms[0])) return rc;
+  const SortFlat flat = f.ref();
+  if (int rc = sort_flat_dev(c, n, flat, kid->sort_order.p, kid->sort_info, &kid->sort_ms[1])) return rc;
+  EventPair ev;
+  if (int rc = ev.begin(c, true)) return rc;
+  if (int rc = sort_gather_dev(c, flat, kid->sort_order.p, n, chunk->rec.records())) return rc;
+  if (int rc = ev.end(c, &kid->sort_ms[3])) return rc;
+  return sites_child_flagged(h, kid, chunk, N);
+}
 
-extern "C" int abn_sites_sort(const abn_sites* h, abn_sites** out) {
+// The child's records are allocated once the number kept is known: the flags and the compaction run first, into an order
+// buffer with room for every record; the child keeps a copy of its kept entries
+int sites_dedup(const abn_sites* h, int policy, abn_sites* kid) {
+  abn_ctx* c = h->ctx;
+  const int64_t n = h->n_records + (int64_t)h->cols.size();
+  kid->deduped = true;
+  kid->dedup_info[0] = n;
+  if (n == 0) {
+    sites_child(h, kid, 0);
+    return ABN_OK;
+  }
+  FlatBufs f;
+  DevBuf<uint32_t> dorder;
+  HIPCHK(c, dorder.alloc((size_t)n));
+  if (int rc = sites_flatten(h, (size_t)n, f, &kid->dedup_ms[0])) return rc;
+  const SortFlat flat = f.ref();
+  double ms2[2] = {0.0, 0.0};
+  if (int rc = dedup_flat_dev(c, n, flat, policy, dorder.p, kid->dedup_info, ms2)) return rc;
+  kid->dedup_ms[1] = ms2[0], kid->dedup_ms[2] = ms2[1];
+  const int64_t kept = kid->dedup_info[1];
+  SiteChunk* chunk = sites_child(h, kid, kept);
+  if (kept == 0) return ABN_OK;
+  const size_t K = (size_t)kept;
+  HIPCHK(c, kid->dedup_order.alloc(K));
+  HIPCHK(c, chunk->rec.alloc(K, 0));
+  HIPCHK(c, hipMemcpyAsync(kid->dedup_order.p, dorder.p, K * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+  EventPair ev;
+  if (int rc = ev.begin(c, true)) return rc;
+  if (int rc = dedup_gather_dev(c, flat, kid->dedup_order.p, kept, n, chunk->rec.records())) return rc;
+  if (int rc = ev.end(c, &kid->dedup_ms[3])) return rc;  // (waits: f and dorder may go)
+  return sites_child_flagged(h, kid, chunk, K);
+}
+
+// the shell of abn_sites_sort and abn_sites_dedup (`name`) behind their own checks: a new handle around build(kid)
+template <class Build>
+int sites_child_entry(const abn_sites* h, abn_sites** out, const char* name, Build build) {
   if (out) *out = nullptr;
   if (!h || !h->ctx) return ABN_ERR_INVALID_ARG;  // (a host-form handle has no context to report to)
   abn_ctx* c = h->ctx;
   if (!out) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
   if (!h->dline.empty() && !h->inserted)
-    return set_err(c, ABN_ERR_INVALID_ARG, "abn_sites_sort: the handle has deferred lines and abn_sites_insert was never called");
+    return set_err(c, ABN_ERR_INVALID_ARG, std::string(name) + ": the handle has deferred lines and abn_sites_insert was never called");
   if (h->n_records + (int64_t)h->cols.size() >= (int64_t)1 << 32)
-    return set_err(c, ABN_ERR_INVALID_ARG, "abn_sites_sort: 2^32 records or more");
+    return set_err(c, ABN_ERR_INVALID_ARG, std::string(name) + ": 2^32 records or more");
   HIPCHK(c, hipSetDevice(c->device));
   PoolScope pool_scope(c);
   std::unique_ptr<abn_sites> kid(new (std::nothrow) abn_sites);
   if (!kid) return set_err(c, ABN_ERR_HIP, "out of host memory");
   try {
-    if (int rc = sites_sort(h, kid.get())) return rc;
+    if (int rc = build(kid.get())) return rc;
   } catch (const std::bad_alloc&) {
     return set_err(c, ABN_ERR_HIP, "out of host memory");
   }
@@ -762,15 +829,15 @@ extern "C" int abn_sites_sort(const abn_sites* h, abn_sites** out) {
   return ABN_OK;
 }
 
-extern "C" int abn_sites_sort_order(const abn_sites* sorted, int64_t* n, int64_t* order) {
-  if (!sorted || !sorted->sorted) return ABN_ERR_INVALID_ARG;
-  abn_ctx* c = sorted->ctx;
-  if (n) *n = sorted->n_records;
-  if (!order || sorted->n_records == 0) return ABN_OK;
+// *n = the child's sites, order [*n] = its order buffer on the host; either may be null
+int sites_child_order(const abn_sites* kid, const DevBuf<uint32_t>& dorder, int64_t* n, int64_t* order) {
+  abn_ctx* c = kid->ctx;
+  if (n) *n = kid->n_records;
+  if (!order || kid->n_records == 0) return ABN_OK;
   HIPCHK(c, hipSetDevice(c->device));
   try {
-    std::vector<uint32_t> o((size_t)sorted->n_records);
-    if (int rc = to_host(c, o.data(), sorted->sort_order)) return rc;
+    std::vector<uint32_t> o((size_t)kid->n_records);
+    if (int rc = to_host(c, o.data(), dorder)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (size_t k = 0; k < o.size(); ++k) order[k] = (int64_t)o[k];
   } catch (const std::bad_alloc&) {
@@ -779,10 +846,40 @@ extern "C" int abn_sites_sort_order(const abn_sites* sorted, int64_t* n, int64_t
   return ABN_OK;
 }
 
+}  // namespace
+
+extern "C" int abn_sites_sort(const abn_sites* h, abn_sites** out) {
+  return sites_child_entry(h, out, "abn_sites_sort", [&](abn_sites* kid) { return sites_sort(h, kid); });
+}
+
+extern "C" int abn_sites_sort_order(const abn_sites* sorted, int64_t* n, int64_t* order) {
+  if (!sorted || !sorted->sorted) return ABN_ERR_INVALID_ARG;
+  return sites_child_order(sorted, sorted->sort_order, n, order);
+}
+
 extern "C" int abn_sites_sort_info(const abn_sites* sorted, int64_t* info4, double* ms4) {
   if (!sorted || !sorted->sorted) return ABN_ERR_INVALID_ARG;
   if (info4) std::copy(sorted->sort_info, sorted->sort_info + 4, info4);
   if (ms4) std::copy(sorted->sort_ms, sorted->sort_ms + 4, ms4);
+  return ABN_OK;
+}
+
+// ---- abn_sites_dedup (kernels: abn_sites_dedup.hpp; the collapse itself: abn_sites_dedup.hip)
+extern "C" int abn_sites_dedup(const abn_sites* h, int policy, abn_sites** out) {
+  if (out) *out = nullptr;
+  if (h && h->ctx && !dedup_policy_valid(policy)) return set_err(h->ctx, ABN_ERR_INVALID_ARG, "abn_sites_dedup: a policy outside 0..3");
+  return sites_child_entry(h, out, "abn_sites_dedup", [&](abn_sites* kid) { return sites_dedup(h, policy, kid); });
+}
+
+extern "C" int abn_sites_dedup_order(const abn_sites* child, int64_t* n, int64_t* order) {
+  if (!child || !child->deduped) return ABN_ERR_INVALID_ARG;
+  return sites_child_order(child, child->dedup_order, n, order);
+}
+
+extern "C" int abn_sites_dedup_info(const abn_sites* child, int64_t* info4, double* ms4) {
+  if (!child || !child->deduped) return ABN_ERR_INVALID_ARG;
+  if (info4) std::copy(child->dedup_info, child->dedup_info + 4, info4);
+  if (ms4) std::copy(child->dedup_ms, child->dedup_ms + 4, ms4);
   return ABN_OK;
 }
 

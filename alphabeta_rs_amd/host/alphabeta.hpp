@@ -394,8 +394,10 @@ class Pedigree {  // src/pedigree.rs:44-45
                                                                          // hold (abn_codes_create_union), p0uu unchanged
                                            unsigned contexts = 1u,       // (with device_sites) the methylation contexts
                                                                          // whose lines are sites: 1 CG, 2 CHG, 4 CHH
-                                           bool sort = false);           // (with device_sites) every methylome sorted by
+                                           bool sort = false,            // (with device_sites) every methylome sorted by
                                                                          // genomic position on the device (abn_sites_sort)
+                                           int dedup = -1);              // (with device_sites) an ABN_DEDUP_* policy: sorted,
+                                                                         // and its repeated sites collapsed (abn_sites_dedup)
   // ... for many (nodelist, edgelist) pairs at once (the windows of src/cli/metaprofile.rs:50-72): with gpu_pairwise ONE
   // abn_pairwise_divergence_windows_packed call per batch of entries with the same number of samples, on 2-bit codes
   // packed straight from the site records.  A batch ends at kBuildManyCodeBytes of PACKED codes per call (four sites per
@@ -516,6 +518,8 @@ struct Args {  // arguments::AlphaBeta, src/arguments.rs:93-114
                               // several: each is a run of its own (run_contexts) on one parse of every methylome
   bool sort = false;          // --sort (with --sites device): every methylome is sorted by genomic position on the device
                               // behind its parse (abn_sites_sort), so files in any line order are aligned
+  int dedup = -1;             // --dedup POLICY (with --sites device): an ABN_DEDUP_* policy, -1 none; implies the sort, and every
+                              // run of records with one key is collapsed to at most one on the device (abn_sites_dedup)
 };
 
 struct RunResult {
@@ -581,7 +585,8 @@ namespace alphabeta {
 inline RunResult run(const Args& args) {
   std::printf("Building pedigree...\n");
   auto [pedigree, p0uu] = Pedigree::build(args.nodes, args.edges, args.posterior_max_filter, /*gpu_pairwise=*/true,
-                                          args.device_parse, args.device_sites, args.align, args.contexts, args.sort);
+                                          args.device_parse, args.device_sites, args.align, args.contexts, args.sort,
+                                          args.dedup);
   return run_on_pedigree(std::move(pedigree), p0uu, args.iterations, args.output);
 }
 
@@ -592,7 +597,7 @@ template <class Done>
 inline void run_contexts(const Args& args, Done done) {
   std::printf("Building pedigrees...\n");
   auto built = detail::build_pedigrees_by_context(args.nodes, args.edges, args.posterior_max_filter, args.align, args.contexts,
-                                                  args.sort);
+                                                  args.sort, args.dedup);
   for (size_t c = 0; c < 3; ++c)
     if ((args.contexts >> c) & 1u)
       done(c, run_on_pedigree(std::move(built[c].first), built[c].second, args.iterations, args.output));

@@ -49,6 +49,12 @@ static void usage() {
       "                                 parse, so files in any line order are compared and aligned; a file that was out of\n"
       "                                 order is named in one line; the same output files as for the files sorted\n"
       "                                 beforehand (needs --sites device) [default: off]\n"
+      "      --dedup <POLICY>           collapse the records of a methylome that repeat one (chromosome, start, end, strand)\n"
+      "                                 on the device, behind the sort that --dedup implies: first or last keeps that record\n"
+      "                                 of the file, best the one with the highest posteriormax (ties: the earlier), drop\n"
+      "                                 none of a site called more than once; a file that held repeats is named in one\n"
+      "                                 line (needs --sites device) [default: off; repeats are refused by --align position\n"
+      "                                 and union]\n"
       "      --transitions              also write <OUTPUT>/transitions.txt: per pair of sampled nodes the sites both keep,\n"
       "                                 by status in the first and in the second sample (UU UI UM IU II IM MU MI MM)\n"
       "  -h, --help                    Print help\n"
@@ -125,6 +131,12 @@ int main(int argc, char** argv) {
       contexts_given = true;
     }
     else if (a == "--sort") args.sort = true;
+    else if (a == "--dedup") {
+      if ((args.dedup = resident::parse_dedup(val())) < 0) {
+        std::fprintf(stderr, "error: %s\n", resident::kDedupExpects);
+        return 2;
+      }
+    }
     else if (a == "--transitions") transitions::request().wanted = true;
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (a == "-V" || a == "--version") { std::puts("alphabeta 0.2.1 (MI355X ABneutral path)"); return 0; }
@@ -143,6 +155,14 @@ int main(int argc, char** argv) {
   }
   if (args.sort && !ped_file.empty()) {
     std::fprintf(stderr, "error: --sort belongs to --nodes and --edges: a pedigree file holds no methylome\n");
+    return 2;
+  }
+  if (args.dedup >= 0 && !(args.device_sites && args.device_parse)) {
+    std::fprintf(stderr, "error: --dedup needs --sites device and --parse device\n");
+    return 2;
+  }
+  if (args.dedup >= 0 && !ped_file.empty()) {
+    std::fprintf(stderr, "error: --dedup belongs to --nodes and --edges: a pedigree file holds no methylome\n");
     return 2;
   }
   if (args.device_sites && !args.device_parse) {

@@ -12,6 +12,7 @@
 #include "../csrc/abn_sites_merge.hpp"
 #include "../csrc/abn_sites_split.hpp"
 #include "../csrc/abn_sites_sort.hpp"
+#include "../csrc/abn_sites_dedup.hpp"
 #include "../csrc/abn_sites_common.hpp"
 #include "../csrc/abn_sites_union.hpp"
 #include "../csrc/abn_tiles.hpp"
@@ -423,6 +424,40 @@ unsigned abh_sites_sort_digit(int chromosome, unsigned start, unsigned end, unsi
 }
 int abh_sites_sort_tile() { return abn::kSortTile; }
 int abh_sites_sort_passes() { return abn::kSortPasses; }
+// ---- the collapse of repeated sites (csrc/abn_sites_dedup.hpp) in its serial forms, for tests/test_sites_dedup_cpu.py,
+// tests/test_sites_dedup_gpu.py and scripts/dedup_ab.py
+// abn_sites_dedup_keys on the host: order (room for n) = the kept records' indices, info4 = {n, kept, repeated keys,
+// disagreeing neighbours}.  1: a policy outside 0..3, n < 0 or >= 2^32, a null array with n > 0, a chromosome outside
+// 0..257, a strand above 2, or a descent — *first_descent (may be null) = the first descending site then, else -1
+int abn_sites_dedup_keys_host(long long n, const int* chromosome, const unsigned* start, const unsigned* end,
+                              const unsigned char* strand, const double* posteriormax, const unsigned char* status, int policy,
+                              long long* order, long long* info4, long long* first_descent) {
+  long long descent = -1;
+  if (first_descent) *first_descent = -1;
+  if (n < 0 || n >= (1ll << 32) || !abn::dedup_policy_valid(policy) || !info4) return 1;
+  if (n > 0 && (!chromosome || !start || !end || !strand || !posteriormax || !status || !order)) return 1;
+  const int rc = abn::dedup_serial(abn::DedupArrays{chromosome, start, end, strand, posteriormax, status}, n, policy, order, info4,
+                                   &descent);
+  if (first_descent) *first_descent = descent;
+  return rc;
+}
+// ... as the kernels walk it: the flags lane by lane with the striding of `blocks` workgroups, BEST's walk from the head's
+// lane, the tile counts, their scan and the scatter's ranks.  info4 as above; check4 = the flags' partial records added up:
+// first descent (-1: none), bad keys, repeated keys, disagreeing neighbours.  Nothing is refused: order is what the
+// kernels would write
+int abh_sites_dedup_walk(long long n, const int* chromosome, const unsigned* start, const unsigned* end,
+                         const unsigned char* strand, const double* posteriormax, const unsigned char* status, int policy,
+                         long long blocks, long long* order, long long* info4, long long* check4) {
+  const abn::DedupArrays keys{chromosome, start, end, strand, posteriormax, status};
+  std::vector<uint8_t> keep((size_t)n);
+  std::vector<uint32_t> count((size_t)abn::sort_tiles(n) + 1);
+  const abn::DedupCheck check = abn::dedup_flags_walk(keys, n, policy, blocks, keep.data());
+  const long long kept = abn::dedup_compact_walk(keep.data(), n, count.data(), order);
+  info4[0] = n, info4[1] = kept, info4[2] = check.repeated, info4[3] = check.disagreeing;
+  check4[0] = check.descent == abn::kDedupNoDescent ? -1 : (long long)check.descent;
+  check4[1] = check.bad, check4[2] = check.repeated, check4[3] = check.disagreeing;
+  return 0;
+}
 // parse_sites_device of a text on the default device (slab_bytes as abn_sites_params) -> the arrays of abh_parse_sites;
 // warnings (capacity wcap) = what it printed.  Returns the number of sites, -1: they do not fit, -2: the call threw
 long long abh_parse_sites_device(const char* text, long long len, long long skip_lines, long long slab_bytes,

@@ -44,6 +44,8 @@ struct WindowArgs {  // the fields of arguments::Windows (src/arguments.rs:6-62)
                                   // the window matrix (abn_sites_parse_dev, abn_windows_create_parsed)
   bool sort = false;              // --sort (with --sites device, --tiles or --regions): every methylome is sorted by genomic
                                   // position on the device behind its parse (abn_sites_sort)
+  int dedup = -1;                 // --dedup POLICY (where --sort is accepted): an ABN_DEDUP_* policy, -1 none; implies the sort,
+                                  // and every run of records with one key is collapsed on the device (abn_sites_dedup)
   Align align = Align::None;      // --align position (with --sites device): only the sites every sample shares are placed
                                   // (abn_windows_create_aligned): no ragged window; the side files describe those sites.
                                   // --align union: every sample gets all the sites any sample holds, filtered
@@ -301,10 +303,11 @@ inline Extraction extract_in_memory(const WindowArgs& args) {
   if (args.align != Align::None && !args.device_sites)
     throw Error(ABN_ERR_INVALID_ARG, std::string("--align ") + align_name(args.align) + " needs --sites device");
   if (args.sort && !args.device_sites) throw Error(ABN_ERR_INVALID_ARG, "--sort needs --sites device");
+  if (args.dedup >= 0 && !args.device_sites) throw Error(ABN_ERR_INVALID_ARG, "--dedup needs --sites device");
   if (args.device_sites) {
     // every text goes up, its records stay there; it is dropped as soon as its deferred lines are decided
     const windows::GeneRule rule{args.cutoff, args.cutoff_gene_length};
-    resident::Samples samples{default_device(), /*skip_lines=*/1, {}, 1u, args.sort};
+    resident::Samples samples{default_device(), /*skip_lines=*/1, {}, 1u, args.sort, args.dedup};
     for (const auto& name : ex.names) samples.add_text(detail::read_file((fs::path(args.methylome) / name).string(), "methylome"), name);
     for (const std::string& line : samples.sort_report) std::fputs(line.c_str(), stdout);
     ex.handle = std::make_unique<windows::Handle>(default_device(), ex.params, genome, rule, args.posterior_max_filter,

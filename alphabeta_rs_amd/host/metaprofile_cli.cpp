@@ -120,6 +120,12 @@ int main(int argc, char** argv) {
       else tiles.block_replicates = n;
     }
     else if (f == "--sort") a.sort = true;
+    else if (f == "--dedup") {
+      if ((a.dedup = resident::parse_dedup(val())) < 0) {
+        std::fprintf(stderr, "error: %s\n", resident::kDedupExpects);
+        return 2;
+      }
+    }
     else if (f == "--regions") tiles.regions = val();
     else if (f == "--pool") tiles.pool = true;
     else if (f == "--transitions") transitions::request().wanted = true;
@@ -159,6 +165,11 @@ int main(int argc, char** argv) {
                 "                            line order (sorted by strand first, contigs in pieces, chromosomes in another order)\n"
                 "                            are tiled and aligned; a file that was out of order is named in one line; the same\n"
                 "                            output files as for the files sorted beforehand [default: off]\n"
+                "       [--dedup POLICY]     where --sort is accepted, and implying it: collapse the records of a methylome that\n"
+                "                            repeat one (chromosome, start, end, strand) on the device.  first or last keeps that\n"
+                "                            record of the file, best the one with the highest posteriormax (ties: the earlier),\n"
+                "                            drop none of a site called more than once; a file that held repeats is named in one\n"
+                "                            line [default: off; repeats are refused by --align position and union]\n"
                 "       [--transitions]      with --tiles or --regions: also write transitions.npy (uint64, tiles x pairs x 9: per\n"
                 "                            tile and pair of sampled nodes the sites both keep, by status in the first and in\n"
                 "                            the second sample, UU UI UM IU II IM MU MI MM) and transition_pairs.txt (sample_a,\n"
@@ -201,6 +212,16 @@ int main(int argc, char** argv) {
     if (parse_host || sites_host) refused = "--sort sorts the sites on the device: --parse host and --sites host do not apply";
     else if (a.methylome.empty()) refused = "--sort belongs to --methylome, not to window directories";
     else if (!tile_mode && !a.device_sites) refused = "--sort with the gene windows of --genome needs --sites device";
+    if (refused) {
+      std::fprintf(stderr, "error: %s\n", refused);
+      return 2;
+    }
+  }
+  if (a.dedup >= 0) {
+    const char* refused = nullptr;
+    if (parse_host || sites_host) refused = "--dedup collapses the sites on the device: --parse host and --sites host do not apply";
+    else if (a.methylome.empty()) refused = "--dedup belongs to --methylome, not to window directories";
+    else if (!tile_mode && !a.device_sites) refused = "--dedup with the gene windows of --genome needs --sites device";
     if (refused) {
       std::fprintf(stderr, "error: %s\n", refused);
       return 2;

@@ -238,10 +238,12 @@ inline Inputs read_inputs(const std::string& nodelist, const std::string& edgeli
 // to the union of all sites with filtered placeholders, so a pair is compared on the sites both hold; rc_meth_lvl and p0uu
 // keep the bits of the unaligned build (a placeholder is not counted).
 // sort: every methylome is sorted by genomic position on the device behind its parse (abn_sites_sort), so files in any line
-// order are aligned; one line per sample that was out of order says so.
+// order are aligned; one line per sample that was out of order says so.  dedup (-1: none): an ABN_DEDUP_* policy; implies the
+// sort, and a sample with repeated sites is then collapsed on the device (abn_sites_dedup) and named in one more line.
 inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
                                    std::vector<double>& dm, const std::vector<std::string>* texts = nullptr,
-                                   Align align = Align::None, unsigned contexts = 1u, bool sort = false);
+                                   Align align = Align::None, unsigned contexts = 1u, bool sort = false,
+                                   int dedup = -1);
 // abn_codes_kernel_ms of this thread's last read_inputs_resident (merge records, merge inserted, pack, fold)
 inline double* resident_kernel_ms() {
   static thread_local double ms[4] = {0.0, 0.0, 0.0, 0.0};
@@ -481,15 +483,17 @@ inline void keep_transitions(const Inputs& in, bool same_len, Scan scan) {
 inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, const std::string& edgelist,
                                                   double posterior_max_filter, bool gpu_pairwise, bool device_parse,
                                                   bool device_sites, const std::vector<std::string>* texts = nullptr,
-                                                  Align align = Align::None, unsigned contexts = 1u, bool sort = false) {
+                                                  Align align = Align::None, unsigned contexts = 1u, bool sort = false,
+                                                  int dedup = -1) {
   if (sort && !device_sites) throw Error(ABN_ERR_INVALID_ARG, "--sort needs --sites device");
+  if (dedup >= 0 && !device_sites) throw Error(ABN_ERR_INVALID_ARG, "--dedup needs --sites device");
   if (align != Align::None && !device_sites)
     throw Error(ABN_ERR_INVALID_ARG, std::string("--align ") + align_name(align) + " needs --sites device");
   if (contexts != 1u && !device_sites) throw Error(ABN_ERR_INVALID_ARG, "--contexts needs --sites device");
   if (device_sites) {
     if (!device_parse || !gpu_pairwise) throw Error(ABN_ERR_INVALID_ARG, "--sites device needs --parse device");
     std::vector<double> dm;
-    const Inputs in = read_inputs_resident(nodelist, edgelist, posterior_max_filter, dm, texts, align, contexts, sort);
+    const Inputs in = read_inputs_resident(nodelist, edgelist, posterior_max_filter, dm, texts, align, contexts, sort, dedup);
     return {convert(in, dm), in.p0uu};
   }
   const Inputs in = read_inputs(nodelist, edgelist, posterior_max_filter, device_parse, texts);
@@ -522,9 +526,9 @@ inline std::pair<Pedigree, double> build_pedigree(const std::string& nodelist, c
 inline std::pair<Pedigree, double> Pedigree::build(const std::string& nodelist, const std::string& edgelist,
                                                    double posterior_max_filter, bool gpu_pairwise,
                                                    bool device_parse, bool device_sites, Align align, unsigned contexts,
-                                                   bool sort) {
+                                                   bool sort, int dedup) {
   return detail::build_pedigree(nodelist, edgelist, posterior_max_filter, gpu_pairwise, device_parse, device_sites, nullptr,
-                                align, contexts, sort);
+                                align, contexts, sort, dedup);
 }
 
 // Pedigree::build for many (nodelist, edgelist) pairs — the windows of src/cli/metaprofile.rs:50-72.  With gpu_pairwise

@@ -33,16 +33,31 @@ inline std::vector<abn_sites*> pointers(const std::vector<windows::ResidentSites
 // is then sorted by genomic position on the device (abn_sites_sort) and the parent dropped: only the sorted handle is
 // kept, and a split of it is sorted too (the split is stable).  sort_report gets one line, with its '\n', per sample that
 // had a descent; the driver prints them next to the alignment report.
+// dedup (--dedup POLICY; -1: none): implies the sort; the sorted methylome is then collapsed on the device (abn_sites_dedup:
+// every run of equal keys to at most one record) and the sorted handle dropped, so a split is of the collapsed sites — unless
+// the sort's info says there is nothing to collapse: its equal neighbours are those of its INPUT, so they are the sorted
+// handle's only for an input without a descent, and a sample that was out of order is collapsed to find out (without a
+// repeated key the sorted handle is kept).  sort_report gets one more line per sample that held repeats, behind the sort's.
+constexpr const char* kDedupNames[4] = {"first", "last", "best", "drop"};  // ABN_DEDUP_FIRST .. ABN_DEDUP_DROP
+constexpr const char* kDedupExpects = "--dedup expects one of first, last, best, drop";
+// "best" -> ABN_DEDUP_BEST; -1: no policy's name
+inline int parse_dedup(const std::string& name) {
+  for (int p = 0; p < 4; ++p)
+    if (name == kDedupNames[p]) return p;
+  return -1;
+}
+
 struct Samples {
   Device& dev;
   size_t skip_lines;
   std::vector<windows::ResidentSites> sites;
   unsigned contexts = 1u;
   bool sort = false;
+  int dedup = -1;
   std::vector<std::string> sort_report;
   void add_text(const std::string& text, const std::string& name = std::string()) {
     windows::ResidentSites parsed = windows::parse_sites_resident(dev, text, skip_lines, /*slab_bytes=*/0, contexts);
-    if (!sort) {
+    if (!sort && dedup < 0) {
       sites.push_back(std::move(parsed));
       return;
     }
@@ -54,6 +69,16 @@ struct Samples {
     if (info[1] > 0)
       sort_report.push_back("Sorted by position: " + name + ": " + std::to_string(info[0]) + " sites, " + std::to_string(info[1]) +
                             " descents\n");
+    if (dedup < 0 || (info[1] == 0 && info[2] == 0)) return;  // in order and no equal neighbours: nothing to collapse
+    abn_sites* made = nullptr;
+    dev.check(abn_sites_dedup(sorted, dedup, &made), "abn_sites_dedup");
+    windows::ResidentSites collapsed(made);
+    dev.check(abn_sites_dedup_info(made, info, nullptr), "abn_sites_dedup_info");
+    if (info[2] == 0) return;  // no repeated key: the sorted handle stays
+    sites.back() = std::move(collapsed);
+    sort_report.push_back("Collapsed repeated sites: " + name + ": " + std::to_string(info[0]) + " sites, " +
+                          std::to_string(info[0] - info[1]) + " removed in " + std::to_string(info[2]) + " repeated keys, " +
+                          std::to_string(info[3]) + " disagreeing (" + kDedupNames[dedup] + ")\n");
   }
   // a sampled node's file (src/pedigree.rs:147-150); name: what the sort's line calls it
   void add_file(const std::string& path, const std::string& name = std::string()) {
@@ -164,10 +189,11 @@ inline Handle::Handle(Device& dev, const abn_windows_params& p, const Genome& ge
 
 namespace detail {
 // the sampled nodes' methylomes as resident handles, in the nodes' order, parsed under `contexts`
-inline resident::Samples load_resident(const Inputs& in, const std::vector<std::string>* texts, unsigned contexts, bool sort) {
+inline resident::Samples load_resident(const Inputs& in, const std::vector<std::string>* texts, unsigned contexts, bool sort,
+                                       int dedup) {
   const size_t nn = in.nodes.size();
   if (texts && texts->size() != nn) throw Error(ABN_ERR_INVALID_ARG, "one text per sampled node");
-  resident::Samples samples{default_device(), /*skip_lines=*/0, {}, contexts, sort};
+  resident::Samples samples{default_device(), /*skip_lines=*/0, {}, contexts, sort, dedup};
   for (size_t i = 0; i < nn; ++i) {
     if (texts) samples.add_text((*texts)[i], in.nodes[i].file);
     else samples.add_file(in.nodes[i].file);
@@ -228,9 +254,9 @@ inline Inputs inputs_of_resident(Inputs in, const std::vector<windows::ResidentS
 
 inline Inputs read_inputs_resident(const std::string& nodelist, const std::string& edgelist, double posterior_max_filter,
                                    std::vector<double>& dm, const std::vector<std::string>* texts, Align align,
-                                   unsigned contexts, bool sort) {
+                                   unsigned contexts, bool sort, int dedup) {
   Inputs in = read_graph(nodelist, edgelist);
-  const resident::Samples samples = load_resident(in, texts, contexts, sort);
+  const resident::Samples samples = load_resident(in, texts, contexts, sort, dedup);
   return inputs_of_resident(std::move(in), samples.sites, posterior_max_filter, dm, align);
 }
 
@@ -240,9 +266,10 @@ inline Inputs read_inputs_resident(const std::string& nodelist, const std::strin
 inline std::array<std::pair<Pedigree, double>, 3> build_pedigrees_by_context(const std::string& nodelist,
                                                                              const std::string& edgelist,
                                                                              double posterior_max_filter, Align align,
-                                                                             unsigned contexts, bool sort = false) {
+                                                                             unsigned contexts, bool sort = false,
+                                                                             int dedup = -1) {
   const Inputs graph = read_graph(nodelist, edgelist);
-  const auto by_context = load_resident(graph, nullptr, contexts, sort).split();
+  const auto by_context = load_resident(graph, nullptr, contexts, sort, dedup).split();
   std::array<std::pair<Pedigree, double>, 3> out;
   for (size_t c = 0; c < 3; ++c) {
     if (!((contexts >> c) & 1u)) continue;

@@ -132,7 +132,7 @@ struct TileSamples {
 };
 inline TileSamples load_tile_samples(const WindowArgs& args, unsigned contexts) {
   namespace fs = std::filesystem;
-  TileSamples s{detail::read_graph(args.nodes, args.edges), {}, {}, resident::Samples{default_device(), /*skip_lines=*/0, {}, contexts, args.sort}};
+  TileSamples s{detail::read_graph(args.nodes, args.edges), {}, {}, resident::Samples{default_device(), /*skip_lines=*/0, {}, contexts, args.sort, args.dedup}};
   if (s.graph.nodes.empty()) throw Error(ABN_ERR_INVALID_ARG, "the nodelist names no sampled node");
   for (const auto& node : s.graph.nodes) {
     s.sample_of.push_back(s.names.size());

@@ -549,6 +549,60 @@ int abn_sites_sort_keys(abn_ctx* ctx, int64_t n, const int32_t* chromosome, cons
  * ABN_ERR_INVALID_ARG: as abn_sites_sort_keys; the key ranges are checked by the check kernel, and no pass runs then. */
 int abn_sites_sort_keys_dev(abn_ctx* ctx, int64_t n, const void* dev_chromosome, const void* dev_start, const void* dev_end,
                             const void* dev_strand, void* dev_order, int64_t* info4, double* ms2);
+/* ---- collapsing the repeated sites of a resident methylome
+ * The KEY of a site is (chromosome, start, end, strand), compared as the canonical order compares it.  A RUN is a maximal
+ * stretch of consecutive records with equal keys.  The collapse keeps at most one record of every run, by a POLICY, and
+ * the kept records keep their order; a run of one record is always kept.
+ * PRECONDITION: the input has no descent in canonical order — what abn_sites_sort leaves (its stable sort keeps repeated
+ * keys adjacent and in file order) and what a file already in canonical order has.
+ *   ABN_DEDUP_FIRST, ABN_DEDUP_LAST  keep the first, the last record of the run in input order: behind abn_sites_sort,
+ *                                    in file order
+ *   ABN_DEDUP_BEST                   keeps the record with the highest posteriormax.  The run is walked in input order
+ *                                    from its first record, and a record replaces the best one so far when
+ *                                    better(new, best) = new > best || (isnan(best) && !isnan(new)): ties keep the earlier
+ *                                    record, -0.0 and +0.0 tie, a run of only NaN keeps its first record.  The walk is
+ *                                    serial in the run's length (the number of replicates of a site)
+ *   ABN_DEDUP_DROP                   keeps no record of a run longer than one: a site called twice is not trusted */
+#define ABN_DEDUP_FIRST 0
+#define ABN_DEDUP_LAST 1
+#define ABN_DEDUP_BEST 2
+#define ABN_DEDUP_DROP 3
+/* abn_sites_dedup: the collapse of a RESIDENT handle's sites on the device.  *out becomes a new, ordinary resident handle
+ * of h's context and mask that holds the kept sites of h — device records and inserted ones — in h's order: with order[k]
+ * (strictly ascending) the index of its k-th site in abn_sites_fetch(h), every field of abn_sites_fetch(*out) and of
+ * abn_sites_context(*out) is h's at order, and the line of site k is k.  It has one chunk of n_lines = n_sites lines, no
+ * deferred lines, counts as inserted, and its flagged lines are the ranks of h's flagged records that were kept.  Every
+ * builder and abn_sites_split take it as it is.  h is not consumed; *out is destroyed with abn_sites_destroy (before its
+ * context).
+ * ABN_ERR_INVALID_ARG: null pointers, a host-form handle, a handle with deferred lines on which abn_sites_insert(_ctx)
+ * was never called, a policy outside 0..3, 2^32 records or more (before any launch); a descent — abn_last_error names
+ * the first descending site and says to sort first —, a chromosome outside 0..257 or a strand above 2 (as
+ * abn_sites_sort refuses them). */
+int abn_sites_dedup(const abn_sites* h, int policy, abn_sites** out);
+/* The kept sites of a handle abn_sites_dedup made: *n its sites, order [*n] the index of every site in the parent's
+ * abn_sites_fetch, strictly ascending; either may be NULL.
+ * ABN_ERR_INVALID_ARG: a null handle, a handle abn_sites_dedup did not make. */
+int abn_sites_dedup_order(const abn_sites* child, int64_t* n, int64_t* order);
+/* What the collapse that made `child` did: info4 = {sites of the parent, sites kept, repeated keys (runs longer than
+ * one), disagreeing neighbours (adjacent records of equal key whose status U/I/M differs)}; ms4 = the HIP-event times of
+ * the flatten, the flags (with the walk of ABN_DEDUP_BEST), the scan (tile counts, their scan, the scatter of the kept
+ * indices) and the gather.  Either may be NULL.
+ * ABN_ERR_INVALID_ARG: a null handle, a handle abn_sites_dedup did not make. */
+int abn_sites_dedup_info(const abn_sites* child, int64_t* info4, double* ms4);
+/* The collapse itself on one sample's raw arrays of HOST memory, [n] each: order has room for n entries and receives
+ * info4[1] of them, the kept records' indices, ascending; info4 as abn_sites_dedup_info.
+ * ABN_ERR_INVALID_ARG: null pointers with n > 0, a null info4, n < 0 or n >= 2^32, a policy outside 0..3, a chromosome
+ * outside 0..257 or a strand above 2 (checked on the host, before any launch), a descent. */
+int abn_sites_dedup_keys(abn_ctx* ctx, int64_t n, const int32_t* chromosome, const uint32_t* start, const uint32_t* end,
+                         const uint8_t* strand, const double* posteriormax, const uint8_t* status, int policy,
+                         int64_t* order, int64_t* info4);
+/* ... on DEVICE arrays (int32, uint32, uint32, uint8, double, uint8); dev_order: uint32, room for n, on the device; ms2
+ * (may be NULL) = the HIP-event times of the flags and of the scan.  Returns after the work has completed.
+ * ABN_ERR_INVALID_ARG: as abn_sites_dedup_keys; the key ranges and the descents are found by the flags kernel, and nothing
+ * is written to dev_order then. */
+int abn_sites_dedup_keys_dev(abn_ctx* ctx, int64_t n, const void* dev_chromosome, const void* dev_start, const void* dev_end,
+                             const void* dev_strand, const void* dev_posteriormax, const void* dev_status, int policy,
+                             void* dev_order, int64_t* info4, double* ms2);
 /* abn_windows_create_sites fed from RESIDENT handles (src/windows.rs:303-339 whole, for n_samples methylomes): sample s is
  * samples[s]; its records and inserted lines are merged in file order on the device into the arrays the gene choice and
  * the placement read — chromosome, start, end, strand, code = status | 0x80 when posteriormax < posterior_max_filter
