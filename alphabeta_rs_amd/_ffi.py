@@ -259,6 +259,11 @@ def _prototypes():
         "abn_multi_analyze": (ci, [vp, dp, i32p]),
         "abn_multi_counters": (ci, [vp, i64p]),
         "abn_multi_rccl_available": (ci, [cip]),
+        "abn_sim_thresholds": (ci, [f64, f64, f64, f64, i32, i32p, i32p, u64p, text, i32]),
+        "abn_sim_grid": (ci, [vp, i64, i32p]),
+        "abn_sim_codes": (ci, [vp, u64, i32, i32p, u64p, u8p, i64, u8p, i64]),
+        "abn_sim_codes_dev": (ci, [vp, u64, i32, i32p, u64p, u8p, i64, vp, i64, dp]),
+        "abn_sim_pedigree": (ci, [vp, u64, i32, i32p, i32p, u64p, u8p, i64, dp, dp, dp]),
     }
 
 

@@ -1,7 +1,7 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (the fit path's abn_api.hip,
 // abn_context.hip and abn_plan.hip, which share abn_fit_host.hpp on top of this; abn_pairwise.hip, abn_windows.hip,
 // abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip, abn_tiles.hip,
-// abn_resident.hip, abn_blocks.hip, abn_sites_sort.hip, abn_sites_dedup.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
+// abn_resident.hip, abn_blocks.hip, abn_sites_sort.hip, abn_sites_dedup.hip, abn_sim.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
 // events of a call, the copies on the context's stream (upload, to_device, to_host), the shell of the windows, codes and
 // tiles handles (created, destroyed, their packed matrix read), and what the consumers of resident methylomes share
 // (abn_resident.hip).  Not part of the C-ABI (include/abneutral.h is).

@@ -1,6 +1,6 @@
 // `alphabeta` command-line tool: same flags, console output and output files as the reference binary
 // (src/cli/alphabeta.rs:8-38, src/arguments.rs:93-152), running the ABneutral path on an MI355X through
-// libabneutral_hip.so.  Extra flags (not in the reference): --seed, --device(s), --lanes, --strict-order, --stream-sweep, --parse, --sites, and
+// libabneutral_hip.so.  Extra flags (not in the reference): --seed, --device(s), --lanes, --strict-order, --stream-sweep, --parse, --sites, --simulate, and
 // --pedigree FILE --p0uu X to start from an existing pedigree file instead of nodelist/edgelist.
 #include <cstdlib>
 #include <cstring>
@@ -8,6 +8,7 @@
 #include <iostream>
 
 #include "alphabeta.hpp"
+#include "simulate.hpp"
 
 namespace fs = std::filesystem;
 using namespace alphabeta;
@@ -57,6 +58,13 @@ static void usage() {
       "                                 and union]\n"
       "      --transitions              also write <OUTPUT>/transitions.txt: per pair of sampled nodes the sites both keep,\n"
       "                                 by status in the first and in the second sample (UU UI UM IU II IM MU MI MM)\n"
+      "      --simulate <ALPHA,BETA>    fit methylomes simulated on the device under the ABneutral model at these rates: the\n"
+      "                                 nodelist and the edgelist give the tree (one root, every other node one incoming\n"
+      "                                 edge), the nodes with meth = Y are sampled, no methylome file is opened; needs\n"
+      "                                 --sim-sites; --seed seeds the draws too [default: off]\n"
+      "      --sim-sites <L>            sites of every simulated methylome\n"
+      "      --sim-p0uu <P>             share of unmethylated sites in the founder's generation-0 ancestor [default: 0.75]\n"
+      "      --sim-weight <W>           share of the founder's methylated sites that are epiheterozygous [default: 0.5]\n"
       "  -h, --help                    Print help\n"
       "  -V, --version                  Print version");
 }
@@ -68,6 +76,8 @@ int main(int argc, char** argv) {
   std::string ped_file;
   double p0uu_given = -1.0;
   uint64_t seed = 20260101ull;
+  simulate::Request sim;
+  bool sites_given = false, parse_given = false, align_given = false, sim_option_given = false;
   int device = 0, lanes = 0;
   bool strict_order = false, stream_sweep = false;
   std::string devices_arg;
@@ -100,7 +110,18 @@ int main(int argc, char** argv) {
     else if (a == "--stream-sweep") stream_sweep = true;
     else if (a == "--pedigree") ped_file = val();
     else if (a == "--p0uu") p0uu_given = std::strtod(val().c_str(), nullptr);
+    else if (a == "--simulate") {
+      if (!simulate::parse_rates(val(), sim.alpha, sim.beta)) {
+        std::fprintf(stderr, "error: %s\n", simulate::kSimulateExpects);
+        return 2;
+      }
+      sim.wanted = true;
+    }
+    else if (a == "--sim-sites") { sim.sites = std::strtoll(val().c_str(), nullptr, 10); sim_option_given = true; }
+    else if (a == "--sim-p0uu") { sim.p_uu0 = std::strtod(val().c_str(), nullptr); sim_option_given = true; }
+    else if (a == "--sim-weight") { sim.weight = std::strtod(val().c_str(), nullptr); sim_option_given = true; }
     else if (a == "--parse") {
+      parse_given = true;
       const std::string where = val();
       if (where != "host" && where != "device") {
         std::fprintf(stderr, "error: --parse expects host or device\n");
@@ -109,6 +130,7 @@ int main(int argc, char** argv) {
       args.device_parse = where == "device";
     }
     else if (a == "--sites") {
+      sites_given = true;
       const std::string where = val();
       if (where != "host" && where != "device") {
         std::fprintf(stderr, "error: --sites expects host or device\n");
@@ -117,6 +139,7 @@ int main(int argc, char** argv) {
       args.device_sites = where == "device";
     }
     else if (a == "--align") {
+      align_given = true;
       const std::string how = val();
       if (!alphabeta::parse_align(how, args.align)) {
         std::fprintf(stderr, "error: %s\n", alphabeta::kAlignExpects);
@@ -142,6 +165,28 @@ int main(int argc, char** argv) {
     else if (a == "-V" || a == "--version") { std::puts("alphabeta 0.2.1 (MI355X ABneutral path)"); return 0; }
     else {
       std::fprintf(stderr, "error: unexpected argument '%s' found\n\nFor more information, try '--help'.\n", argv[i]);
+      return 2;
+    }
+  }
+  if (sim_option_given && !sim.wanted) {
+    std::fprintf(stderr, "error: --sim-sites, --sim-p0uu and --sim-weight belong to --simulate\n");
+    return 2;
+  }
+  if (sim.wanted) {  // the methylomes are simulated: nothing that reads, orders or aligns methylome files applies
+    const std::pair<bool, const char*> excluded[] = {
+        {sites_given, "--sites"}, {parse_given, "--parse"}, {contexts_given, "--contexts"}, {args.sort, "--sort"},
+        {args.dedup >= 0, "--dedup"}, {align_given, "--align"}, {!ped_file.empty(), "--pedigree"}};
+    for (const auto& x : excluded)
+      if (x.first) {
+        std::fprintf(stderr, "error: --simulate cannot be combined with %s: the methylomes are simulated\n", x.second);
+        return 2;
+      }
+    if (transitions::request().wanted) {
+      std::fprintf(stderr, "error: --simulate cannot be combined with --transitions\n");
+      return 2;
+    }
+    if (sim.sites < 1) {
+      std::fprintf(stderr, "error: --simulate needs --sim-sites, a positive number of sites\n");
       return 2;
     }
   }
@@ -244,6 +289,10 @@ int main(int argc, char** argv) {
         return 2;
       }
       r = run_on_pedigree(Pedigree::from_file(ped_file), p0uu_given, args.iterations, args.output);
+    } else if (sim.wanted) {
+      std::printf("Simulating pedigree...\n");
+      auto [pedigree, p0uu] = simulate::build(sim, args.nodes, args.edges, seed);
+      r = run_on_pedigree(std::move(pedigree), p0uu, args.iterations, args.output);
     } else {
       r = run(args);
     }

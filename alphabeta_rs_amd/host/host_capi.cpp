@@ -13,6 +13,13 @@
 #include "../csrc/abn_sites_split.hpp"
 #include "../csrc/abn_sites_sort.hpp"
 #include "../csrc/abn_sites_dedup.hpp"
+// hipcc compiles this file as HIP, device pass included: abn_philox.h (through abn_sim.hpp) names a device function of the
+// runtime header there.  (A plain C++ compiler builds this file too, without HIP's include path: tests/test_host_sanitizers.py)
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
+
+#include "../csrc/abn_sim.hpp"
 #include "../csrc/abn_sites_common.hpp"
 #include "../csrc/abn_sites_union.hpp"
 #include "../csrc/abn_tiles.hpp"
@@ -1032,4 +1039,31 @@ void abh_transitions_packed(const unsigned char* packed, int n, long long stride
   for (int w = 0; w < W; ++w)
     abn::abn_transitions_packed_host(packed, n, stride, begin[w], end[w], (uint64_t*)table + (size_t)w * pairs * 9);
 }
+// ---- methylomes simulated down a pedigree (csrc/abn_sim.hpp) in their serial forms, for tests/test_sim_cpu.py,
+// tests/test_sim_gpu.py and scripts/simulate_ab.py
+// abn_sim_codes on the host, site by site: packed [emitted nodes x row_stride].  1 with the refusal's words in `text`
+// (text_bytes, may be null): what abn_sim_codes refuses
+int abn_sim_codes_host(unsigned long long seed, int n_nodes, const int* parent, const unsigned long long* thr,
+                       const unsigned char* emit, long long n_sites, unsigned char* packed, long long row_stride, char* text,
+                       int text_bytes) {
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "thresholds");
+  const std::string why = abn::sim_refusal(n_nodes, parent, (const uint64_t*)thr, emit, n_sites, packed, row_stride);
+  put_text(text, text_bytes, why);
+  if (!why.empty()) return 1;
+  abn::sim_codes_serial(seed, n_nodes, parent, (const uint64_t*)thr, emit, n_sites, packed, row_stride);
+  return 0;
+}
+// ... as the kernel walks it: `blocks` workgroups of lanes grid-strided over the row's dwords, a lane's trip the nodes in
+// index order, unemitted live nodes in scratch rows; lazy = 0: the low words always drawn.  Valid arguments
+int abh_sim_codes_walk(unsigned long long seed, int n_nodes, const int* parent, const unsigned long long* thr,
+                       const unsigned char* emit, long long n_sites, long long blocks, int lazy, unsigned char* packed,
+                       long long row_stride) {
+  const abn::SimPlan plan = abn::sim_plan(n_nodes, parent, emit);
+  std::vector<uint8_t> scratch((size_t)plan.n_scratch * (size_t)abn::sim_row_bytes(n_sites) + 4);
+  if (lazy) abn::sim_codes_walk<true>(seed, n_nodes, plan.nodes.data(), (const uint64_t*)thr, n_sites, blocks, packed, row_stride, scratch.data());
+  else abn::sim_codes_walk<false>(seed, n_nodes, plan.nodes.data(), (const uint64_t*)thr, n_sites, blocks, packed, row_stride, scratch.data());
+  return 0;
+}
+long long abh_sim_grid_blocks(long long n_sites, int cus) { return abn::sim_grid_blocks(abn::sim_row_bytes(n_sites) / 4, cus); }
+int abh_sim_threads() { return abn::kSimThreads; }
 }

@@ -1013,6 +1013,56 @@ int abn_multi_counters(abn_multi* m, int64_t* out5);
 /* *ok = 1 when librccl.so.1 can be loaded and exports every symbol the gather uses */
 int abn_multi_rccl_available(int* ok);
 
+/* ------------------------------------------------------------------ methylomes simulated down a pedigree
+ * The ABneutral model run forwards (src/divergence.rs:33-114): a site of a diploid selfing line is UU, UM or MM (codes 0,
+ * 1, 2: the U / I / M of DMatrix::from, src/pedigree.rs:253-257); one generation applies genmatrix(alpha, beta) (:96-114);
+ * the founder is drawn from [p_uu, w p_mm, (1 - w) p_mm] (:44).  The model's dt1t2 of a pair (:68-89) is E|s_i - s_j| / 2 of
+ * two lineages that split at t0, the quantity DMatrix::from measures.  The reference has no generator: its end-to-end tests
+ * are commented out (src/alphabeta.rs:81-140, src/ab_neutral.rs:144-161).
+ * A tree of n_nodes nodes: parent[0] = -1, 0 <= parent[v] < v; thr uint64 [n_nodes][3][2], thr[v][s][0] <= thr[v][s][1];
+ * emit uint8 [n_nodes].  The draw of site k at node v: u = (uint64)H[k & 3] << 32 | Lw[k & 3], H = philox4x32_10(c0 =
+ * (uint32)(k >> 2), c1 = 0, c2 = v, c3 = 5, seed_lo, seed_hi), Lw the same call with c1 = 1.  The founder's state is
+ * (u >= thr[0][0][0]) + (u >= thr[0][0][1]); any other node's, with s its parent's state at the site,
+ * (u >= thr[v][s][0]) + (u >= thr[v][s][1]).  The r-th emitted node, in node order, is row r of a packed matrix (format
+ * above): the field of site k its state, every field from n_sites to the end of abn_packed_row_stride(n_sites) bytes 3;
+ * bytes of a longer row_stride_bytes are not written.  A row depends on the seed, the node's index, its ancestors and their
+ * thresholds alone.
+ * ABN_ERR_INVALID_ARG with a text, before any launch: null pointers, n_nodes < 1 or > 65535 (what the pairwise scan takes
+ * as samples), a parent outside the rule, thr[..][0] > thr[..][1], no emitted node, n_sites < 0 or > 2^34, a
+ * row_stride_bytes that is not a multiple of 64 or is below abn_packed_row_stride(n_sites).
+ *
+ * abn_sim_thresholds (host arithmetic, no device; src/divergence.rs:16-31, :44, :55, :96-114): thr from rates.  For v > 0
+ * the rows of G^(generation[v] - generation[parent[v]]), G = genmatrix(alpha, beta), the power the reference's
+ * left-accumulated chain (power 0: the identity); the founder's row [p_uu0, w (1 - p_uu0), (1 - w)(1 - p_uu0)] .
+ * G^generation[0].  Of a row p: c0 = p[0], c1 = p[0] + p[1]; threshold(c) = 0 for c <= 0, 2^64 - 1 for c >= 1, else
+ * (uint64)ldexp(c, 64).  A cumulative probability is resolved to 2^-53: a one-generation UU -> MM step at alpha = 4e-9
+ * (1.6e-17) cannot be represented.  `text` (text_bytes, may be NULL) takes a refusal's text.  ABN_ERR_INVALID_ARG: null
+ * pointers, n_nodes < 1 or > 65535, a parent outside the rule, a generation outside 0..127 (the reference's i8,
+ * src/divergence.rs:52), a child older than its parent, alpha, beta, p_uu0 or weight outside [0, 1] or not finite. */
+int abn_sim_thresholds(double alpha, double beta, double p_uu0, double weight, int32_t n_nodes, const int32_t* parent,
+                       const int32_t* generation, uint64_t* thr, char* text, int32_t text_bytes);
+/* The launch abn_sim_codes* makes for n_sites sites on this context (src/divergence.rs:33-114 has no counterpart): grid2 =
+ * {workgroups, lanes per workgroup}; a lane owns one dword (16 sites) of a row per trip of its grid stride. */
+int abn_sim_grid(abn_ctx* ctx, int64_t n_sites, int32_t* grid2);
+/* The simulation (src/divergence.rs:33-114 forwards) to the HOST matrix packed [emitted nodes x row_stride_bytes]. */
+int abn_sim_codes(abn_ctx* ctx, uint64_t seed, int32_t n_nodes, const int32_t* parent, const uint64_t* thr,
+                  const uint8_t* emit, int64_t n_sites, uint8_t* packed, int64_t row_stride_bytes);
+/* ... to the DEVICE matrix dev_packed (16-byte aligned, else ABN_ERR_INVALID_ARG), what
+ * abn_pairwise_divergence_packed_dev reads (src/pedigree.rs:210-261); nothing of per-site size reaches the host.
+ * kernel_ms (may be NULL): the kernel's HIP-event time.  Returns after the work has completed. */
+int abn_sim_codes_dev(abn_ctx* ctx, uint64_t seed, int32_t n_nodes, const int32_t* parent, const uint64_t* thr,
+                      const uint8_t* emit, int64_t n_sites, void* dev_packed, int64_t row_stride_bytes, double* kernel_ms);
+/* Pedigree::build (src/pedigree.rs:92-193) of simulated methylomes: the simulation into a device matrix, DMatrix::from by
+ * abn_pairwise_divergence_packed_dev, and the rows of DMatrix::convert (:281-333) — rows double [pairs x 4] = (t0, t1, t2,
+ * D) for the pairs i < j of the emitted nodes in node order, t0 the generation of the pair's last common ancestor.  *p0uu
+ * (:171-183): a site's level is state / 2, rc_meth_lvl of a sample (double)(n1 + 2 n2) / (2.0 (double)n_sites) from the
+ * sums of abn_pairwise_transitions_packed_dev's table, p0uu the mean of 1 - rc_meth_lvl summed in sample order.  ms2 (may be
+ * NULL): the HIP-event times of the simulation and of the two passes over the matrix behind it (the divergence scan and the
+ * transition table, summed).  ABN_ERR_INVALID_ARG: as abn_sim_codes; a null generation,
+ * rows or p0uu; n_sites < 1; fewer than two emitted nodes. */
+int abn_sim_pedigree(abn_ctx* ctx, uint64_t seed, int32_t n_nodes, const int32_t* parent, const int32_t* generation,
+                     const uint64_t* thr, const uint8_t* emit, int64_t n_sites, double* rows, double* p0uu, double* ms2);
+
 #ifdef __cplusplus
 }
 #endif
