@@ -137,6 +137,8 @@ def _prototypes():
         "abn_pairwise_transitions_packed_dev": (ci, [vp, vp, i32, i64, i64, vp, dp]),
         "abn_pairwise_transitions_windows_packed": (ci, [vp, u8p, i32, i64, i64, i64p, i64p, i32, u64p]),
         "abn_pairwise_transitions_windows_packed_dev": (ci, [vp, vp, i32, i64, i64, i64p, i64p, i32, vp, dp]),
+        "abn_packed_census_windows": (ci, [vp, u8p, i32, i64, i64, i64p, i64p, i32, u64p]),
+        "abn_packed_census_windows_dev": (ci, [vp, vp, i32, i64, i64, i64p, i64p, i32, vp, dp]),
         "abn_windows_create": (ci, [vp, wp, i32, i64p, u32p, u32p, u32p, u8p, u8p, dp, vpp]),
         "abn_windows_destroy": (ci, [vp]),
         "abn_windows_info": (ci, [vp, i32p, i64p, i64p]),
@@ -264,6 +266,10 @@ def _prototypes():
         "abn_sim_codes": (ci, [vp, u64, i32, i32p, u64p, u8p, i64, u8p, i64]),
         "abn_sim_codes_dev": (ci, [vp, u64, i32, i32p, u64p, u8p, i64, vp, i64, dp]),
         "abn_sim_pedigree": (ci, [vp, u64, i32, i32p, i32p, u64p, u8p, i64, dp, dp, dp]),
+        "abn_sim_obs_thresholds": (ci, [dp, dp, u64p, text, i32]),
+        "abn_sim_observe": (ci, [vp, u64, i32, i32p, u64p, i64, u8p, i64, u8p, i64]),
+        "abn_sim_observe_dev": (ci, [vp, u64, i32, i32p, u64p, i64, vp, i64, vp, i64, dp]),
+        "abn_sim_study": (ci, [vp, u64, i32, i32p, i32p, u64p, u8p, u64p, i64, i32, dp, dp, dp, u64p, dp]),
     }
 
 

@@ -94,6 +94,7 @@ def build_host(force: bool = False, verbose: bool = False) -> Path:
             CSRC / "abn_sites_merge.hpp", CSRC / "abn_sites_split.hpp", CSRC / "abn_sites_sort.hpp", CSRC / "abn_sites_dedup.hpp", CSRC / "abn_codes.hpp", CSRC / "abn_sites_common.hpp",
             CSRC / "abn_sites_union.hpp", CSRC / "abn_tiles.hpp", HOST / "tiles.hpp",
             CSRC / "abn_pairwise_transitions.hpp", CSRC / "abn_packed_mask.hpp", HOST / "transitions.hpp", CSRC / "abn_sim.hpp", CSRC / "abn_philox.h",
+            CSRC / "abn_packed_census.hpp",
             HOST / "simulate.hpp"]  # host_capi.cpp exports the launch policy to the tests
     newest = max(p.stat().st_mtime for p in srcs)
     CLI.parent.mkdir(exist_ok=True)

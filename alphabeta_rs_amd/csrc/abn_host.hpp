@@ -303,6 +303,10 @@ int transitions_windows_packed_dev(abn_ctx* c, const void* dev_packed, int32_t n
 int transitions_windows_packed_to_host(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
                                        int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
                                        int32_t n_windows, uint64_t* table);
+// ... and for abn_sim_study (abn_sim.hip): abn_packed_census_windows_dev behind its null check of the context
+int packed_census_windows_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                              int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                              int32_t n_windows, void* dev_counts, double* kernel_ms);
 // abn_blocks.hip, for abn_tiles_block_bootstrap (abn_tiles.hip): the block bootstrap (abn_blocks.hpp) of DEVICE tables —
 // both, diff [n_blocks x n_pairs], level_sum_kept, kept [n_samples x n_blocks] — behind the checks of the groups: the counts
 // of n_replicates + 1 rows per group made on the device, the sums of every row to the HOST outputs (any may be null), ms5 =

@@ -1,10 +1,13 @@
 // Pedigree construction: the four pairwise divergence scans abn_pairwise_divergence* — byte codes
 // or 2-bit packed codes, the whole matrix or many windows of it — each with a host entry and a _dev entry — and the
-// state transition tables abn_pairwise_transitions* of the packed two (abn_pairwise_transitions.hpp).
+// state transition tables abn_pairwise_transitions* of the packed two (abn_pairwise_transitions.hpp), and the state census of
+// a packed matrix per column range abn_packed_census_windows* (abn_packed_census.hpp).
 // The scan kernels are in abn_pairwise_mx.hpp, abn_pairwise_packed.hpp, abn_pairwise_windows.hpp and
 // abn_pairwise_windows_packed.hpp; the fit path (abn_api.hip, abn_context.hip, abn_plan.hip) does not include them.
 #define ABN_TRANSITIONS_KERNELS
+#define ABN_CENSUS_KERNELS
 #include "abn_host.hpp"
+#include "abn_packed_census.hpp"
 #include "abn_pairwise_mx.hpp"
 #include "abn_pairwise_packed.hpp"
 #include "abn_pairwise_transitions.hpp"
@@ -624,4 +627,101 @@ extern "C" int abn_pairwise_transitions_packed(abn_ctx* c, const uint8_t* packed
   if (int rc = pairwise_packed_check(c, packed, n_samples, n_sites, row_stride_bytes)) return rc;
   const int64_t begin = 0, end = n_sites;
   return abn_pairwise_transitions_windows_packed(c, packed, n_samples, n_sites, row_stride_bytes, &begin, &end, 1, table);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the state census of every sample per column range of a packed matrix (src/pedigree.rs:159-175 over a sample's own kept
+// sites): abn_packed_census.hpp
+// ------------------------------------------------------------------------------------------------
+constexpr long long kCensusSlab = 1ll << 20;  // workgroups on x of one launch
+
+// dcounts [W][n][3] on the device; the cuts of the windows are `chunk`'s, the packed windows scan's
+static int census_on_device(abn_ctx* c, const uint8_t* dpacked, int n, long long stride, const int64_t* begin,
+                            const int64_t* end, int W, const std::vector<long long>& chunk, unsigned long long* dcounts,
+                            double* kernel_ms) {
+  std::vector<CensusJob> jobs;
+  std::vector<long long> job_off;
+  census_plan(begin, end, W, chunk.data(), jobs, job_off);
+  const long long J = (long long)jobs.size();
+  DevBuf<CensusJob> djobs;
+  DevBuf<long long> doff;
+  DevBuf<uint32_t> dpartial;
+  EventPair ev;
+  if (J > 0)
+    if (int rc = upload(c, djobs, jobs.data(), (size_t)J)) return rc;
+  if (int rc = upload(c, doff, job_off.data(), job_off.size())) return rc;
+  HIPCHK(c, dpartial.alloc((size_t)n * (size_t)J * 3));
+  if (int rc = ev.begin(c, kernel_ms != nullptr)) return rc;
+  for (long long j0 = 0; j0 < J; j0 += kCensusSlab) {
+    const unsigned grid = (unsigned)std::min(kCensusSlab, J - j0);
+    hipLaunchKernelGGL(abn_packed_census_kernel, dim3(grid, (unsigned)n), dim3(kCensusThreads), 0, c->stream, dpacked, stride,
+                       (const CensusJob*)djobs.p, J, j0, dpartial.p);
+    HIPCHK(c, hipGetLastError());
+  }
+  for (long long w0 = 0; w0 < W; w0 += kCensusSlab) {
+    const unsigned grid = (unsigned)std::min<long long>(kCensusSlab, W - w0);
+    hipLaunchKernelGGL(abn_packed_census_sum_kernel, dim3(grid, (unsigned)n), dim3(kCensusSumThreads), 0, c->stream,
+                       (const uint32_t*)dpartial.p, (const long long*)doff.p, J, w0, dcounts);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (int rc = ev.end(c, kernel_ms)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the host's jobs and offsets stay until the stream has read them
+  return ABN_OK;
+}
+
+int abn::packed_census_windows_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                   int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                                   int32_t n_windows, void* dev_counts, double* kernel_ms) {
+  std::vector<long long> chunk;
+  if (int rc = pairwise_windows_packed_check(c, dev_packed, n_samples, n_sites, row_stride_bytes, site_begin, site_end,
+                                             n_windows, chunk))
+    return rc;
+  if ((uintptr_t)dev_packed % 16 != 0) return set_err(c, ABN_ERR_INVALID_ARG, "dev_packed is not 16-byte aligned");
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (n_windows == 0) return ABN_OK;
+  if (!dev_counts) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  try {
+    HIPCHK(c, hipSetDevice(c->device));
+    PoolScope pool_scope(c);
+    return census_on_device(c, (const uint8_t*)dev_packed, n_samples, row_stride_bytes, site_begin, site_end, n_windows, chunk,
+                            (unsigned long long*)dev_counts, kernel_ms);
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
+}
+
+extern "C" int abn_packed_census_windows_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                             int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                                             int32_t n_windows, void* dev_counts, double* kernel_ms) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  return packed_census_windows_dev(c, dev_packed, n_samples, n_sites, row_stride_bytes, site_begin, site_end, n_windows,
+                                   dev_counts, kernel_ms);
+}
+
+extern "C" int abn_packed_census_windows(abn_ctx* c, const uint8_t* packed, int32_t n_samples, int64_t n_sites,
+                                         int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                                         int32_t n_windows, uint64_t* counts) {
+  if (!c) return ABN_ERR_INVALID_ARG;
+  std::vector<long long> chunk;
+  if (int rc = pairwise_windows_packed_check(c, packed, n_samples, n_sites, row_stride_bytes, site_begin, site_end, n_windows,
+                                             chunk))
+    return rc;
+  if (n_windows == 0) return ABN_OK;
+  if (!counts) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  try {
+    HIPCHK(c, hipSetDevice(c->device));
+    PoolScope pool_scope(c);
+    DevBuf<uint8_t> dpacked;  // (device allocations are aligned far beyond the 16 bytes the kernel asks for)
+    DevBuf<unsigned long long> dcounts;
+    if (int rc = upload_codes(c, dpacked, packed, (size_t)n_samples * (size_t)row_stride_bytes, 64)) return rc;
+    HIPCHK(c, dcounts.alloc((size_t)n_windows * (size_t)n_samples * 3));
+    if (int rc = census_on_device(c, dpacked.p, n_samples, row_stride_bytes, site_begin, site_end, n_windows, chunk, dcounts.p,
+                                  nullptr))
+      return rc;
+    if (int rc = to_host(c, counts, dcounts)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ABN_OK;
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
 }

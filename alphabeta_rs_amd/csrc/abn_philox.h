@@ -21,6 +21,7 @@ constexpr uint32_t kTagJitter = 2u;  // Model::vary draws of the bootstrap simpl
 constexpr uint32_t kTagIdx = 3u;     // residual-bootstrap row indices
 constexpr uint32_t kTagBlock = 4u;   // block-bootstrap draws of genomic blocks (abn_blocks.hpp)
 constexpr uint32_t kTagSim = 5u;     // draws of the simulated methylomes' states (abn_sim.hpp)
+constexpr uint32_t kTagObs = 6u;     // draws of the observation step: miscalls and dropouts of a simulated call (abn_sim.hpp)
 
 ABN_HD void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                           uint32_t out[4]) {

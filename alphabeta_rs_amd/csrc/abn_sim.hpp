@@ -33,6 +33,28 @@
 // wavefront: scalar loads into scalar registers (SimThr), a site's two thresholds chosen from them by compare and select.
 // One H call serves four sites; Lw decides a site only where H[k & 3] equals the high word of one of its two thresholds,
 // so the Lw call is made only for a quad in which some site ties (kLazy) — the same law at half the Philox work.
+//
+// THE OBSERVATION LAW.  What a caller of methylation states sees of a true state: another state (a miscall) or nothing
+// (a call below the posterior filter, which the reference drops per pair, src/pedigree.rs:249-251).  othr is uint64 [3][3],
+// each row non-decreasing.  For the emitted row of node v, site k, true state s in {0, 1, 2}: the draw w(k, v) is built
+// exactly as u(k, v) with c3 = kTagObs = 6; c2 = v is the NODE's index, not the row's, so emit still only selects rows.
+//   observed field = (w >= othr[s][0]) + (w >= othr[s][1]) + (w >= othr[s][2]); the field 3 is "filtered"
+// An input field that already is 3 (the padding behind the last site, or anything else) stays 3; the fields from site L
+// to the end of abn_packed_row_stride(L) bytes are written as 3; bytes beyond abn_packed_row_stride(L) of a row are
+// neither read nor written.  Refused before any launch (sim_observe_refusal): null pointers, fewer than 1 or more than
+// 65535 rows, a node_of_row outside 0..65534, a decreasing othr row, L < 0 or L > 2^34, a stride outside the rule above, an
+// input and an output that overlap other than in place (the same pointer and the same stride).
+//
+// OBSERVATION THRESHOLDS (sim_obs_thresholds; host only).  miscall[3][3]: row s the probabilities that a kept call of a
+// true state s reads 0, 1, 2 (each row sums to 1 within 1e-12); dropout[3]: the probability that a call of a true state s
+// is filtered.  With q = 1 - dropout[s]: c0 = q m[s][0], c1 = q (m[s][0] + m[s][1]), c2 = q; each through threshold(c);
+// then t1 = max(t1, t0), t2 = max(t2, t1).
+//
+// THE OBSERVATION KERNEL.  One lane owns one dword of one row; the rows lie on blockIdx.y, x is grid-strided with
+// sim_grid_blocks as the simulation is.  One H call per quad serves four sites; the Lw call is made only for a quad in
+// which some site's H equals the high word of one of its three thresholds (kLazy; the argument above).  The eighteen
+// threshold words are kernel arguments (ObsThr: a member each, no indexed array), the row's node one scalar load.  One
+// writer per element, no atomics, no LDS, no scratch memory; in place the lane reads its dword before it writes it.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -316,7 +338,175 @@ inline int32_t sim_common_generation(const int32_t* parent, const int32_t* gener
   return generation[a];
 }
 
+// ------------------------------------------------------------------------------------------------ the observation step
+ABN_HD uint64_t sim_obs_draw(uint64_t seed, uint64_t k, uint32_t v) {
+  uint32_t h[4], l[4];
+  philox4x32_10((uint32_t)(k >> 2), 0u, v, kTagObs, (uint32_t)seed, (uint32_t)(seed >> 32), h);
+  philox4x32_10((uint32_t)(k >> 2), 1u, v, kTagObs, (uint32_t)seed, (uint32_t)(seed >> 32), l);
+  return ((uint64_t)h[k & 3] << 32) | l[k & 3];
+}
+ABN_HD uint32_t sim_obs_field(uint64_t w, uint64_t t0, uint64_t t1, uint64_t t2) {
+  return (uint32_t)(w >= t0) + (uint32_t)(w >= t1) + (uint32_t)(w >= t2);
+}
+// othr[0..2][0..2] as eighteen words, each a member of its own (SimThr's reason): hi / lo of the thresholds 0 (a), 1 (b)
+// and 2 (c) under the true states 0, 1, 2.  A kernel argument: the words arrive in scalar registers
+struct ObsThr {
+  uint32_t a0h, a0l, b0h, b0l, c0h, c0l, a1h, a1l, b1h, b1l, c1h, c1l, a2h, a2l, b2h, b2l, c2h, c2l;
+};
+inline ObsThr sim_obs_thr(const uint64_t* t) {
+  auto hi = [&](int i) { return (uint32_t)(t[i] >> 32); };
+  auto lo = [&](int i) { return (uint32_t)t[i]; };
+  return ObsThr{hi(0), lo(0), hi(1), lo(1), hi(2), lo(2), hi(3), lo(3), hi(4), lo(4), hi(5), lo(5),
+                hi(6), lo(6), hi(7), lo(7), hi(8), lo(8)};
+}
+
+// The observed dword g of the row of node v from its true dword: fields of sites 16 g + 4 j + e at bits 8 e + 2 j; an
+// input field of 3 stays 3 (it reads the thresholds of state 2; its field is set afterwards), and so does every field
+// from the dword's n_valid-th site on.
+template <bool kLazy>
+ABN_HD uint32_t sim_obs_lane_dword(uint64_t seed, uint32_t v, uint64_t g, const ObsThr t, uint32_t in, int n_valid) {
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  uint32_t out = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t c0 = (uint32_t)(4 * g + (uint64_t)j);
+    uint32_t h[4];
+    philox4x32_10(c0, 0u, v, kTagObs, k0, k1, h);
+    uint32_t s[4], ah[4], bh[4], ch[4];
+    bool tie = false;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      s[e] = (in >> (8 * e + 2 * j)) & 3u;
+      ah[e] = sim_pick(s[e], t.a0h, t.a1h, t.a2h);
+      bh[e] = sim_pick(s[e], t.b0h, t.b1h, t.b2h);
+      ch[e] = sim_pick(s[e], t.c0h, t.c1h, t.c2h);
+      tie = tie || h[e] == ah[e] || h[e] == bh[e] || h[e] == ch[e];
+    }
+    uint32_t field[4];
+    if (!kLazy || tie) {  // the low words decide
+      uint32_t l[4];
+      philox4x32_10(c0, 1u, v, kTagObs, k0, k1, l);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        field[e] = sim_obs_field(((uint64_t)h[e] << 32) | l[e], ((uint64_t)ah[e] << 32) | sim_pick(s[e], t.a0l, t.a1l, t.a2l),
+                                 ((uint64_t)bh[e] << 32) | sim_pick(s[e], t.b0l, t.b1l, t.b2l),
+                                 ((uint64_t)ch[e] << 32) | sim_pick(s[e], t.c0l, t.c1l, t.c2l));
+    } else {  // no high word equals a threshold's: w >= t exactly when H > the threshold's high word
+#pragma unroll
+      for (int e = 0; e < 4; ++e) field[e] = (uint32_t)(h[e] > ah[e]) + (uint32_t)(h[e] > bh[e]) + (uint32_t)(h[e] > ch[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) out |= field[e] << (8 * e + 2 * j);
+  }
+  const uint32_t was3 = in & (in >> 1) & 0x55555555u;  // bit 2 i of every input field i that is 3
+  return out | was3 | (was3 << 1) | sim_pad_mask(n_valid);  // a field is at most 3: or-ing 3 over it gives 3
+}
+
+// "" or why the arguments of abn_sim_observe* are refused
+inline std::string sim_observe_refusal(int64_t n_rows, const int32_t* node_of_row, const uint64_t* othr, int64_t n_sites,
+                                       const void* in, int64_t in_stride, const void* out, int64_t out_stride) {
+  if (!node_of_row || !othr || !in || !out) return "abn_sim_observe: a null pointer";
+  if (n_rows < 1) return "abn_sim_observe: fewer than one row";
+  if (n_rows > kSimMaxNodes) return "abn_sim_observe: more than 65535 rows";
+  for (int64_t r = 0; r < n_rows; ++r)
+    if (node_of_row[r] < 0 || node_of_row[r] >= kSimMaxNodes)
+      return "abn_sim_observe: node_of_row[" + std::to_string(r) + "] lies outside 0..65534";
+  for (int s = 0; s < 3; ++s)
+    if (othr[3 * s] > othr[3 * s + 1] || othr[3 * s + 1] > othr[3 * s + 2])
+      return "abn_sim_observe: othr[" + std::to_string(s) + "] decreases";
+  if (n_sites < 0 || n_sites > kSimMaxSites) return "abn_sim_observe: n_sites below 0 or above 2^34";
+  for (int64_t stride : {in_stride, out_stride})
+    if (stride < 0 || stride % 64 != 0 || stride < sim_row_bytes(n_sites))
+      return "abn_sim_observe: a row_stride that is not a multiple of 64 or is below abn_packed_row_stride(n_sites)";
+  if (!(in == out && in_stride == out_stride) && n_sites > 0) {
+    const uintptr_t a0 = (uintptr_t)in, a1 = a0 + (uintptr_t)((n_rows - 1) * in_stride + sim_row_bytes(n_sites));
+    const uintptr_t b0 = (uintptr_t)out, b1 = b0 + (uintptr_t)((n_rows - 1) * out_stride + sim_row_bytes(n_sites));
+    if (a0 < b1 && b0 < a1) return "abn_sim_observe: the input and the output overlap other than in place";
+  }
+  return "";
+}
+
+// The law site by site (valid arguments): row r of `in` observed into row r of `out`
+inline void sim_observe_serial(uint64_t seed, int64_t n_rows, const int32_t* node_of_row, const uint64_t* othr, int64_t n_sites,
+                               const uint8_t* in, int64_t in_stride, uint8_t* out, int64_t out_stride) {
+  const int64_t row_bytes = sim_row_bytes(n_sites);
+  for (int64_t r = 0; r < n_rows; ++r) {
+    const uint8_t* src = in + r * in_stride;
+    uint8_t* dst = out + r * out_stride;
+    for (int64_t k = 0; k < 4 * row_bytes; ++k) {
+      const int64_t at = (k >> 4) * 4 + (k & 3);
+      const int shift = 2 * (int)((k >> 2) & 3);
+      const uint32_t s = (src[at] >> shift) & 3u;
+      uint32_t f = 3u;
+      if (k < n_sites && s != 3u) {
+        const uint64_t* t = othr + 3 * s;
+        f = sim_obs_field(sim_obs_draw(seed, (uint64_t)k, (uint32_t)node_of_row[r]), t[0], t[1], t[2]);
+      }
+      dst[at] = (uint8_t)((dst[at] & ~(3u << shift)) | (f << shift));  // (in place: the field read above is this one)
+    }
+  }
+}
+
+// One lane's trip of the observation kernel: the dword g of row r
+template <bool kLazy>
+ABN_HD void sim_obs_lane_trip(uint64_t seed, uint32_t v, const ObsThr t, int64_t n_sites, int64_t g, const uint8_t* in_row,
+                              uint8_t* out_row) {
+  const int64_t left = n_sites - 16 * g;
+  const int n_valid = left >= 16 ? 16 : (left > 0 ? (int)left : 0);
+  const uint32_t x = *reinterpret_cast<const uint32_t*>(in_row + 4 * g);
+  *reinterpret_cast<uint32_t*>(out_row + 4 * g) = sim_obs_lane_dword<kLazy>(seed, v, (uint64_t)g, t, x, n_valid);
+}
+
+// The observation kernel's structure walked on the host: rows on y, `blocks` workgroups of kSimThreads lanes on x, every
+// lane grid-strided over the row's dwords
+template <bool kLazy>
+inline void sim_observe_walk(uint64_t seed, int64_t n_rows, const int32_t* node_of_row, const uint64_t* othr, int64_t n_sites,
+                             int64_t blocks, const uint8_t* in, int64_t in_stride, uint8_t* out, int64_t out_stride) {
+  const int64_t row_dwords = sim_row_bytes(n_sites) / 4, lanes = blocks * kSimThreads;
+  const ObsThr t = sim_obs_thr(othr);
+  for (int64_t r = 0; r < n_rows; ++r)
+    for (int64_t lane = 0; lane < lanes; ++lane)
+      for (int64_t g = lane; g < row_dwords; g += lanes)
+        sim_obs_lane_trip<kLazy>(seed, (uint32_t)node_of_row[r], t, n_sites, g, in + r * in_stride, out + r * out_stride);
+}
+
+// "" or the refusal; othr[3][3] from miscall[3][3] and dropout[3]
+inline std::string sim_obs_thresholds(const double* miscall, const double* dropout, uint64_t* othr) {
+  if (!miscall || !dropout || !othr) return "abn_sim_obs_thresholds: a null pointer";
+  for (int i = 0; i < 9; ++i)
+    if (!(miscall[i] >= 0.0 && miscall[i] <= 1.0)) return "abn_sim_obs_thresholds: miscall and dropout lie in [0, 1]";
+  for (int s = 0; s < 3; ++s)
+    if (!(dropout[s] >= 0.0 && dropout[s] <= 1.0)) return "abn_sim_obs_thresholds: miscall and dropout lie in [0, 1]";
+  for (int s = 0; s < 3; ++s) {
+    const double* m = miscall + 3 * s;
+    const double sum = (m[0] + m[1]) + m[2];
+    if (!(fabs(sum - 1.0) <= 1e-12)) return "abn_sim_obs_thresholds: miscall[" + std::to_string(s) + "] does not sum to 1";
+    const double q = 1.0 - dropout[s];
+    uint64_t* t = othr + 3 * s;
+    t[0] = sim_threshold(q * m[0]);
+    t[1] = sim_threshold(q * (m[0] + m[1]));
+    t[2] = sim_threshold(q);
+    if (t[1] < t[0]) t[1] = t[0];
+    if (t[2] < t[1]) t[2] = t[1];
+  }
+  return "";
+}
+
 #if defined(__HIPCC__) && defined(ABN_SIM_KERNELS)  // (abn_sim.hip defines it)
+// grid: (sim_grid_blocks(row_dwords, cus), n_rows) workgroups of kSimThreads lanes.  Bounds: g < row_dwords = sim_row_bytes(L)
+// / 4, so a row's reads and writes end at sim_row_bytes(L) <= both strides; blockIdx.y < n_rows.
+template <bool kLazy>
+__global__ void __launch_bounds__(kSimThreads)
+abn_sim_observe_kernel(uint64_t seed, const int32_t* __restrict__ node_of_row, const ObsThr t, int64_t n_sites, int64_t row_dwords,
+                       const uint8_t* in, int64_t in_stride, uint8_t* out, int64_t out_stride) {
+  const uint32_t v = (uint32_t)node_of_row[blockIdx.y];
+  const uint8_t* in_row = in + (int64_t)blockIdx.y * in_stride;
+  uint8_t* out_row = out + (int64_t)blockIdx.y * out_stride;
+  const int64_t lanes = (int64_t)gridDim.x * kSimThreads;
+  for (int64_t g = (int64_t)blockIdx.x * kSimThreads + threadIdx.x; g < row_dwords; g += lanes)
+    sim_obs_lane_trip<kLazy>(seed, v, t, n_sites, g, in_row, out_row);
+}
+
 // grid: sim_grid_blocks(row_dwords, cus) workgroups of kSimThreads lanes.  Bounds: g < row_dwords = sim_row_bytes(L) / 4, so a
 // row's writes end at sim_row_bytes(L) <= row_stride; slots are below n_emit and n_scratch by sim_plan.
 template <bool kLazy>

@@ -1,6 +1,6 @@
 // `alphabeta` command-line tool: same flags, console output and output files as the reference binary
 // (src/cli/alphabeta.rs:8-38, src/arguments.rs:93-152), running the ABneutral path on an MI355X through
-// libabneutral_hip.so.  Extra flags (not in the reference): --seed, --device(s), --lanes, --strict-order, --stream-sweep, --parse, --sites, --simulate, and
+// libabneutral_hip.so.  Extra flags (not in the reference): --seed, --device(s), --lanes, --strict-order, --stream-sweep, --parse, --sites, --simulate (--sim-*), and
 // --pedigree FILE --p0uu X to start from an existing pedigree file instead of nodelist/edgelist.
 #include <cstdlib>
 #include <cstring>
@@ -65,6 +65,13 @@ static void usage() {
       "      --sim-sites <L>            sites of every simulated methylome\n"
       "      --sim-p0uu <P>             share of unmethylated sites in the founder's generation-0 ancestor [default: 0.75]\n"
       "      --sim-weight <W>           share of the founder's methylated sites that are epiheterozygous [default: 0.5]\n"
+      "      --sim-replicates <R>       a replicate study: R independent pedigrees of --sim-sites sites from one simulation, all\n"
+      "                                 fitted at once; the usual files are replicate 0's, simulation.txt has the mean, sd and\n"
+      "                                 2.5 / 97.5 percentiles of the recovered rates, simulation_raw.npy every replicate's row\n"
+      "      --sim-starts <S>           start simplices of every replicate's fit [default: 10]\n"
+      "      --sim-miscall <E>          probability that a call differs from the true state, split evenly over the two other\n"
+      "                                 states [default: 0]\n"
+      "      --sim-dropout <F>          probability that a call is filtered, whatever the state [default: 0]\n"
       "  -h, --help                    Print help\n"
       "  -V, --version                  Print version");
 }
@@ -78,6 +85,7 @@ int main(int argc, char** argv) {
   uint64_t seed = 20260101ull;
   simulate::Request sim;
   bool sites_given = false, parse_given = false, align_given = false, sim_option_given = false;
+  bool study_option_given = false, replicates_given = false;
   int device = 0, lanes = 0;
   bool strict_order = false, stream_sweep = false;
   std::string devices_arg;
@@ -120,6 +128,10 @@ int main(int argc, char** argv) {
     else if (a == "--sim-sites") { sim.sites = std::strtoll(val().c_str(), nullptr, 10); sim_option_given = true; }
     else if (a == "--sim-p0uu") { sim.p_uu0 = std::strtod(val().c_str(), nullptr); sim_option_given = true; }
     else if (a == "--sim-weight") { sim.weight = std::strtod(val().c_str(), nullptr); sim_option_given = true; }
+    else if (a == "--sim-replicates") { sim.replicates = std::strtoll(val().c_str(), nullptr, 10); study_option_given = replicates_given = true; }
+    else if (a == "--sim-starts") { sim.starts = std::atoi(val().c_str()); study_option_given = true; }
+    else if (a == "--sim-miscall") { sim.miscall = std::strtod(val().c_str(), nullptr); study_option_given = true; }
+    else if (a == "--sim-dropout") { sim.dropout = std::strtod(val().c_str(), nullptr); study_option_given = true; }
     else if (a == "--parse") {
       parse_given = true;
       const std::string where = val();
@@ -172,6 +184,14 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "error: --sim-sites, --sim-p0uu and --sim-weight belong to --simulate\n");
     return 2;
   }
+  if (study_option_given && !sim.wanted) {
+    std::fprintf(stderr, "error: --sim-replicates, --sim-starts, --sim-miscall and --sim-dropout belong to --simulate\n");
+    return 2;
+  }
+  if (study_option_given && !replicates_given) {
+    std::fprintf(stderr, "error: --sim-starts, --sim-miscall and --sim-dropout belong to --sim-replicates\n");
+    return 2;
+  }
   if (sim.wanted) {  // the methylomes are simulated: nothing that reads, orders or aligns methylome files applies
     const std::pair<bool, const char*> excluded[] = {
         {sites_given, "--sites"}, {parse_given, "--parse"}, {contexts_given, "--contexts"}, {args.sort, "--sort"},
@@ -188,6 +208,13 @@ int main(int argc, char** argv) {
     if (sim.sites < 1) {
       std::fprintf(stderr, "error: --simulate needs --sim-sites, a positive number of sites\n");
       return 2;
+    }
+    if (replicates_given) {
+      const std::string why = simulate::study_refusal(sim);
+      if (!why.empty()) {
+        std::fprintf(stderr, "error: %s\n", why.c_str());
+        return 2;
+      }
     }
   }
   if (contexts_given && !(args.device_sites && args.device_parse)) {
@@ -289,6 +316,13 @@ int main(int argc, char** argv) {
         return 2;
       }
       r = run_on_pedigree(Pedigree::from_file(ped_file), p0uu_given, args.iterations, args.output);
+    } else if (sim.wanted && sim.replicates > 0) {
+      std::printf("Simulating pedigree...\n");
+      simulate::Study st = simulate::study(sim, args.nodes, args.edges, seed);
+      r = run_on_pedigree(std::move(st.pedigree), st.p0uu, args.iterations, args.output);
+      std::printf("Replicates with a finite fit: %zu of %lld\n", st.ok, sim.replicates);
+      std::ofstream((fs::path(args.output) / "simulation.txt").string()) << st.txt;
+      st.raw.write_npy((fs::path(args.output) / "simulation_raw.npy").string());
     } else if (sim.wanted) {
       std::printf("Simulating pedigree...\n");
       auto [pedigree, p0uu] = simulate::build(sim, args.nodes, args.edges, seed);

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #endif
 
+#include "../csrc/abn_packed_census.hpp"
 #include "../csrc/abn_sim.hpp"
 #include "../csrc/abn_sites_common.hpp"
 #include "../csrc/abn_sites_union.hpp"
@@ -1066,4 +1067,42 @@ int abh_sim_codes_walk(unsigned long long seed, int n_nodes, const int* parent, 
 }
 long long abh_sim_grid_blocks(long long n_sites, int cus) { return abn::sim_grid_blocks(abn::sim_row_bytes(n_sites) / 4, cus); }
 int abh_sim_threads() { return abn::kSimThreads; }
+// ---- the observation step and the state census in their host forms, for tests/test_sim_study_cpu.py, test_sim_study_gpu.py
+// abn_sim_observe on the host.  walk_blocks = 0: the law site by site; > 0: the kernel's lane function walked over that
+// many workgroups' grid stride, lazy = 0 with the low words always drawn.  1 with the refusal's words in `text`
+int abn_sim_observe_host(unsigned long long seed, int n_rows, const int* node_of_row, const unsigned long long* othr,
+                         long long n_sites, const unsigned char* packed_in, long long in_stride, unsigned char* packed_out,
+                         long long out_stride, long long walk_blocks, int lazy, char* text, int text_bytes) {
+  const std::string why =
+      abn::sim_observe_refusal(n_rows, node_of_row, (const uint64_t*)othr, n_sites, packed_in, in_stride, packed_out, out_stride);
+  put_text(text, text_bytes, why);
+  if (!why.empty()) return 1;
+  const uint64_t* t = (const uint64_t*)othr;
+  if (walk_blocks <= 0) abn::sim_observe_serial(seed, n_rows, node_of_row, t, n_sites, packed_in, in_stride, packed_out, out_stride);
+  else if (lazy) abn::sim_observe_walk<true>(seed, n_rows, node_of_row, t, n_sites, walk_blocks, packed_in, in_stride, packed_out, out_stride);
+  else abn::sim_observe_walk<false>(seed, n_rows, node_of_row, t, n_sites, walk_blocks, packed_in, in_stride, packed_out, out_stride);
+  return 0;
+}
+// abn_packed_census_windows on the host: counts [n_windows x n_samples x 3].  walk_chunk = 0: field by field; > 0 (a
+// multiple of 256): the kernels' job structure walked with that many sites per job
+int abn_packed_census_windows_host(const unsigned char* packed, int n_samples, long long n_sites, long long row_stride,
+                                   const long long* site_begin, const long long* site_end, int n_windows,
+                                   unsigned long long* counts, long long walk_chunk, char* text, int text_bytes) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "window ranges");
+  std::string why = abn::census_refusal(packed, n_samples, n_sites, row_stride, (const int64_t*)site_begin, (const int64_t*)site_end,
+                                        n_windows, counts);
+  if (why.empty() && (walk_chunk < 0 || walk_chunk % abn::kPackedStepSites != 0 || walk_chunk >= (1ll << 30)))
+    why = "walk_chunk is not a multiple of 256 below 2^30";
+  put_text(text, text_bytes, why);
+  if (!why.empty()) return 1;
+  if (walk_chunk == 0) {
+    abn::census_windows_serial(packed, n_samples, row_stride, (const int64_t*)site_begin, (const int64_t*)site_end, n_windows,
+                               (uint64_t*)counts);
+  } else {
+    const std::vector<long long> chunk((size_t)n_windows, walk_chunk);
+    abn::census_windows_walk(packed, n_samples, row_stride, (const int64_t*)site_begin, (const int64_t*)site_end, n_windows,
+                             chunk.data(), (uint64_t*)counts);
+  }
+  return 0;
+}
 }

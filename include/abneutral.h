@@ -332,6 +332,19 @@ int abn_pairwise_transitions_windows_packed_dev(abn_ctx* ctx, const void* dev_pa
                                                 int64_t row_stride_bytes, const int64_t* site_begin,
                                                 const int64_t* site_end, int32_t n_windows, void* dev_table,
                                                 double* kernel_ms);
+/* The state census of a packed matrix per column range: counts uint64 [n_windows x n_samples x 3], the fields 0, 1 and 2
+ * (U, I, M of src/pedigree.rs:253-257) that each sample holds inside [site_begin[w], site_end[w]) — what rc_meth_lvl over a
+ * sample's OWN kept sites needs (src/pedigree.rs:159-175; the pair tables above count only the sites both samples of a pair
+ * keep).  Exact integers, summed without atomics; an empty window gives zeros.  Arguments and refusals are those of
+ * abn_pairwise_divergence_windows_packed(_dev), but one sample is served.  HOST matrix and counts. */
+int abn_packed_census_windows(abn_ctx* ctx, const uint8_t* packed, int32_t n_samples, int64_t n_sites,
+                              int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                              int32_t n_windows, uint64_t* counts);
+/* ... DEVICE matrix (16-byte aligned) and DEVICE counts, HOST window arrays; kernel_ms (may be NULL): the HIP-event time of
+ * the two kernels.  Returns after the work has completed. */
+int abn_packed_census_windows_dev(abn_ctx* ctx, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                  int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                                  int32_t n_windows, void* dev_counts, double* kernel_ms);
 
 /* ------------------------------------------------------------------ window placement (the `extract` stage)
  * Windows::extract (src/windows.rs:287-343) behind the gene choice: MethylationSite::place_in_windows
@@ -1062,6 +1075,48 @@ int abn_sim_codes_dev(abn_ctx* ctx, uint64_t seed, int32_t n_nodes, const int32_
  * rows or p0uu; n_sites < 1; fewer than two emitted nodes. */
 int abn_sim_pedigree(abn_ctx* ctx, uint64_t seed, int32_t n_nodes, const int32_t* parent, const int32_t* generation,
                      const uint64_t* thr, const uint8_t* emit, int64_t n_sites, double* rows, double* p0uu, double* ms2);
+
+/* ------------------------------------------------------------------ the observation step and replicate studies
+ * What a caller of methylation states sees of a true state: another state (a miscall) or nothing — a call below the
+ * posterior filter, which the reference drops per pair (src/pedigree.rs:249-251) and leaves out of rc_meth_lvl
+ * (src/pedigree.rs:159-175).  othr uint64 [3][3], each row non-decreasing.  For the row of node v, site k, true state s in
+ * {0, 1, 2}: the draw w(k, v) is built exactly as u(k, v) above with c3 = 6 (kTagObs = 6u); c2 = v is the NODE's index, not
+ * the row's.  The observed field is (w >= othr[s][0]) + (w >= othr[s][1]) + (w >= othr[s][2]); the field 3 is "filtered".
+ * An input field that already is 3 stays 3; the fields from n_sites to the end of abn_packed_row_stride(n_sites) bytes are
+ * written as 3; bytes beyond abn_packed_row_stride(n_sites) of a row are neither read nor written.
+ *
+ * abn_sim_obs_thresholds (host arithmetic, no device): othr from miscall[3][3] (row s: the probabilities that a kept call of
+ * a true state s reads 0, 1, 2) and dropout[3] (the probability that a call of a true state s is filtered).  With q = 1 -
+ * dropout[s]: c0 = q m[s][0], c1 = q (m[s][0] + m[s][1]), c2 = q, each through threshold(c) of abn_sim_thresholds, then
+ * t1 = max(t1, t0), t2 = max(t2, t1).  ABN_ERR_INVALID_ARG with `text`: null pointers, a value outside [0, 1] or not
+ * finite, a miscall row whose sum differs from 1 by more than 1e-12. */
+int abn_sim_obs_thresholds(const double miscall[9], const double dropout[3], uint64_t othr[9], char* text, int32_t text_bytes);
+/* The observation of the HOST matrix packed_in [n_rows x in_stride] into packed_out [n_rows x out_stride]; row r belongs to
+ * node node_of_row[r].  packed_in == packed_out with equal strides is allowed, any other overlap refused.
+ * ABN_ERR_INVALID_ARG with a text, before any launch: null pointers, n_rows < 1 or > 65535, a node_of_row outside 0..65534,
+ * a decreasing othr row, n_sites < 0 or > 2^34, a stride that is not a multiple of 64 or is below
+ * abn_packed_row_stride(n_sites).  n_sites == 0: ABN_OK, nothing written. */
+int abn_sim_observe(abn_ctx* ctx, uint64_t seed, int32_t n_rows, const int32_t* node_of_row, const uint64_t* othr,
+                    int64_t n_sites, const uint8_t* packed_in, int64_t in_stride, uint8_t* packed_out, int64_t out_stride);
+/* ... on DEVICE matrices (both 16-byte aligned, else ABN_ERR_INVALID_ARG); kernel_ms (may be NULL): the kernel's HIP-event
+ * time.  Returns after the work has completed. */
+int abn_sim_observe_dev(abn_ctx* ctx, uint64_t seed, int32_t n_rows, const int32_t* node_of_row, const uint64_t* othr,
+                        int64_t n_sites, const void* dev_in, int64_t in_stride, void* dev_out, int64_t out_stride,
+                        double* kernel_ms);
+/* A replicate study: replicate r is the sites [r L, (r + 1) L) of ONE simulation of R L sites (L = n_sites, R =
+ * n_replicates), so its codes are those columns of abn_sim_codes(.., R L).  The chain: the simulation into a device matrix,
+ * the observation in place where othr is given (NULL: no observation step), abn_pairwise_divergence_windows_packed_dev and
+ * abn_packed_census_windows_dev over the R ranges; only the results reach the host.  times double [pairs x 3] = (t0, t1, t2)
+ * of DMatrix::convert (src/pedigree.rs:281-333) as abn_sim_pedigree forms them; dvalue double [R x pairs]; p0uu double [R]:
+ * the mean, in sample order, of 1 - (double)(n1 + 2 n2) / (2.0 (double)(n0 + n1 + n2)) over a sample's kept sites
+ * (src/pedigree.rs:159-183) — a sample that keeps nothing gives the reference's 0 / 0, NaN, which is passed on; census uint64
+ * [R x emitted x 3] (may be NULL); ms4 (may be NULL): the HIP-event times of the simulation, the observation, the scan and the
+ * census.  With R = 1 and othr = NULL, times / dvalue / p0uu are abn_sim_pedigree's bits.  ABN_ERR_INVALID_ARG: as
+ * abn_sim_codes; a null generation, times, dvalue or p0uu; L < 1; R < 1; R L > 2^34; fewer than two emitted nodes; a
+ * decreasing othr row. */
+int abn_sim_study(abn_ctx* ctx, uint64_t seed, int32_t n_nodes, const int32_t* parent, const int32_t* generation,
+                  const uint64_t* thr, const uint8_t* emit, const uint64_t* othr, int64_t n_sites, int32_t n_replicates,
+                  double* times, double* dvalue, double* p0uu, uint64_t* census, double* ms4);
 
 #ifdef __cplusplus
 }
