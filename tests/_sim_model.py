@@ -37,26 +37,33 @@ def philox(c0, c1, c2, c3, k0, k1):
     return [x.astype(np.uint32) for x in c]
 
 
-def draw_words(seed, v, n_sites):
-    """(H word, Lw word) of every site of node v: uint32 (n_sites,) each"""
-    quads = np.arange((n_sites + 3) // 4, dtype=np.uint64)
+def quad_counters(n_sites, first):
+    """the quad counters k >> 2 of the sites [first, first + n_sites); first a multiple of 16"""
+    assert first >= 0 and first % 16 == 0
+    return np.arange(first // 4, first // 4 + (n_sites + 3) // 4, dtype=np.uint64)
+
+
+def draw_words(seed, v, n_sites, first=0):
+    """(H word, Lw word) of the sites [first, first + n_sites) of node v: uint32 (n_sites,) each"""
+    quads = quad_counters(n_sites, first)
     key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
     hi = np.stack(philox(quads, 0, v, TAG_SIM, *key), axis=1).reshape(-1)[:n_sites]
     lo = np.stack(philox(quads, 1, v, TAG_SIM, *key), axis=1).reshape(-1)[:n_sites]
     return hi, lo
 
 
-def draws(seed, v, n_sites):
-    hi, lo = draw_words(seed, v, n_sites)
+def draws(seed, v, n_sites, first=0):
+    hi, lo = draw_words(seed, v, n_sites, first)
     return (hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64)
 
 
-def states(seed, parent, thr, n_sites):
-    """state uint8 (V, n_sites) of every node, emitted or not; thr[v][s][i] are ints"""
+def states(seed, parent, thr, n_sites, first=0):
+    """state uint8 (V, n_sites) of every node, emitted or not, at the sites [first, first + n_sites) (sites are
+    independent: only the quad counter's origin moves); thr[v][s][i] are ints"""
     V = len(parent)
     out = np.zeros((V, n_sites), dtype=np.uint8)
     for v in range(V):
-        u = draws(seed, v, n_sites)
+        u = draws(seed, v, n_sites, first)
         s = np.zeros(n_sites, dtype=np.intp) if v == 0 else out[parent[v]].astype(np.intp)
         t0 = np.array([int(thr[v][k][0]) for k in range(3)], dtype=np.uint64)[s]
         t1 = np.array([int(thr[v][k][1]) for k in range(3)], dtype=np.uint64)[s]
@@ -83,8 +90,10 @@ def pack(fields, stride=None, fill=0xFF):
     return out
 
 
-def model(seed, parent, thr, emit, n_sites, stride=None, fill=0xFF):
-    st = states(seed, parent, thr, n_sites)
+def model(seed, parent, thr, emit, n_sites, stride=None, fill=0xFF, first=0):
+    """the packed rows of the emitted nodes; first > 0: the bytes from byte first / 4 on of rows of first + n_sites sites
+    (the padding is the row's own where first is a multiple of 256)"""
+    st = states(seed, parent, thr, n_sites, first)
     return pack(st[np.flatnonzero(np.asarray(emit))], stride, fill)
 
 

@@ -9,26 +9,28 @@ import _sim_model as M
 TAG_OBS = 6
 
 
-def obs_draw_words(seed, v, n_sites):
-    """(H word, Lw word) of the observation draw of every site of node v: the simulation's draw with c3 = 6"""
-    quads = np.arange((n_sites + 3) // 4, dtype=np.uint64)
+def obs_draw_words(seed, v, n_sites, first=0):
+    """(H word, Lw word) of the observation draw of the sites [first, first + n_sites) of node v: the simulation's draw
+    with c3 = 6"""
+    quads = M.quad_counters(n_sites, first)
     key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
     hi = np.stack(M.philox(quads, 0, v, TAG_OBS, *key), axis=1).reshape(-1)[:n_sites]
     lo = np.stack(M.philox(quads, 1, v, TAG_OBS, *key), axis=1).reshape(-1)[:n_sites]
     return hi, lo
 
 
-def obs_draws(seed, v, n_sites):
-    hi, lo = obs_draw_words(seed, v, n_sites)
+def obs_draws(seed, v, n_sites, first=0):
+    hi, lo = obs_draw_words(seed, v, n_sites, first)
     return (hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64)
 
 
-def observe_fields(seed, fields, nodes, othr):
-    """fields uint8 (rows, L) of 0..3, row r the methylome of node nodes[r]; othr[s][i] ints -> the observed fields"""
+def observe_fields(seed, fields, nodes, othr, first=0):
+    """fields uint8 (rows, L) of 0..3, row r the sites [first, first + L) of the methylome of node nodes[r]; othr[s][i]
+    ints -> the observed fields"""
     out = np.empty_like(fields)
     L = fields.shape[1]
     for r, v in enumerate(nodes):
-        w = obs_draws(seed, int(v), L)
+        w = obs_draws(seed, int(v), L, first)
         s = np.minimum(fields[r], 2).astype(np.intp)
         seen = np.zeros(L, dtype=np.uint8)
         for i in range(3):
@@ -47,9 +49,10 @@ def unpack(packed, L):
     return f.reshape(rows, 4 * least)[:, :L].astype(np.uint8)
 
 
-def observe(seed, packed, nodes, othr, L, stride=None, fill=0):
-    """the observed packed matrix of a packed one: the fields behind L are 3, bytes of a longer stride hold `fill`"""
-    return M.pack(observe_fields(seed, unpack(packed, L), nodes, othr), stride, fill)
+def observe(seed, packed, nodes, othr, L, stride=None, fill=0, first=0):
+    """the observed packed matrix of a packed one: the fields behind L are 3, bytes of a longer stride hold `fill`; first > 0:
+    packed holds the L sites from site `first` on of longer rows"""
+    return M.pack(observe_fields(seed, unpack(packed, L), nodes, othr, first), stride, fill)
 
 
 def obs_thresholds(miscall, dropout):
