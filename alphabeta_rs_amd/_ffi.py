@@ -139,6 +139,9 @@ def _prototypes():
         "abn_pairwise_transitions_windows_packed_dev": (ci, [vp, vp, i32, i64, i64, i64p, i64p, i32, vp, dp]),
         "abn_packed_census_windows": (ci, [vp, u8p, i32, i64, i64, i64p, i64p, i32, u64p]),
         "abn_packed_census_windows_dev": (ci, [vp, vp, i32, i64, i64, i64p, i64p, i32, vp, dp]),
+        "abn_packed_region_states": (ci, [vp, u8p, i32, i64, i64, i64p, i64p, i64, i32p, i64, i64, i64, i64, i64, i64, u8p]),
+        "abn_packed_region_states_dev": (ci, [vp, vp, i32, i64, i64, i64p, i64p, i64, i32p, i64, i64, i64, i64, i64, i64, vp,
+                                              dp]),
         "abn_windows_create": (ci, [vp, wp, i32, i64p, u32p, u32p, u32p, u8p, u8p, dp, vpp]),
         "abn_windows_destroy": (ci, [vp]),
         "abn_windows_info": (ci, [vp, i32p, i64p, i64p]),
@@ -224,6 +227,17 @@ def _prototypes():
         "abn_tiles_block_bootstrap": (ci, [vp, u64, i64, u64p, u64p, dp, dp, i64p]),
         "abn_tiles_block_groups": (ci, [vp, i64p, i64p, i64p, i64p]),
         "abn_tiles_block_ms": (ci, [vp, dp]),
+        "abn_tiles_region_states": (ci, [vp, i64, i64, i64, i64, i32p, i32, vpp]),
+        "abn_regions_destroy": (ci, [vp]),
+        "abn_regions_info": (ci, [vp, i32p, i64p, i64p, i32p]),
+        "abn_regions_layout": (ci, [vp, i64p, i64p]),
+        "abn_regions_order": (ci, [vp, i32p]),
+        "abn_regions_packed": (ci, [vp, u8p]),
+        "abn_regions_packed_device_ptr": (ci, [vp, vpp]),
+        "abn_regions_census": (ci, [vp, u64p]),
+        "abn_regions_pairwise": (ci, [vp, u64p, u64p, dp]),
+        "abn_regions_transitions": (ci, [vp, u64p]),
+        "abn_regions_kernel_ms": (ci, [vp, dp]),
         "abn_plan_create": (ci, [vp, op, dp, i32, i32, i32, i32, u32, u32, vpp]),
         "abn_plan_destroy": (ci, [vp]),
         "abn_plan_set_window_ids": (ci, [vp, u32p]),

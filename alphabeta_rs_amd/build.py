@@ -18,7 +18,7 @@ SOURCES = [CSRC / "abn_api.hip", CSRC / "abn_context.hip", CSRC / "abn_plan.hip"
            CSRC / "abn_pairwise.hip", CSRC / "abn_windows.hip", CSRC / "abn_analyze.hip",
            CSRC / "abn_multi.hip", CSRC / "abn_sites.hip", CSRC / "abn_genes.hip", CSRC / "abn_codes.hip",
            CSRC / "abn_sites_common.hip", CSRC / "abn_sites_union.hip", CSRC / "abn_tiles.hip", CSRC / "abn_blocks.hip",
-           CSRC / "abn_sites_sort.hip", CSRC / "abn_sites_dedup.hip", CSRC / "abn_sim.hip",
+           CSRC / "abn_sites_sort.hip", CSRC / "abn_sites_dedup.hip", CSRC / "abn_sim.hip", CSRC / "abn_regions.hip",
            CSRC / "abn_resident.hip",  # host-only too: what the builders from resident parse results share
            CSRC / "abn_pack.cpp"]  # host-only: the packed code format (also built alone under the host sanitizers)
 DEPS = [*sorted(CSRC.glob("*.hpp")), CSRC / "abn_philox.h", PKG.parent / "include" / "abneutral.h"]
@@ -92,9 +92,9 @@ def build_host(force: bool = False, verbose: bool = False) -> Path:
             HOST / "metaprofile.hpp", HOST / "metaprofile_cli.cpp", HOST / "reference_tests.cpp",
             CSRC / "abn_route.hpp", CSRC / "abn_constants.hpp", CSRC / "abn_parse.hpp", CSRC / "abn_genes.hpp",
             CSRC / "abn_sites_merge.hpp", CSRC / "abn_sites_split.hpp", CSRC / "abn_sites_sort.hpp", CSRC / "abn_sites_dedup.hpp", CSRC / "abn_codes.hpp", CSRC / "abn_sites_common.hpp",
-            CSRC / "abn_sites_union.hpp", CSRC / "abn_tiles.hpp", HOST / "tiles.hpp",
+            CSRC / "abn_sites_union.hpp", CSRC / "abn_tiles.hpp", HOST / "tiles.hpp", HOST / "region_states.hpp",
             CSRC / "abn_pairwise_transitions.hpp", CSRC / "abn_packed_mask.hpp", HOST / "transitions.hpp", CSRC / "abn_sim.hpp", CSRC / "abn_philox.h",
-            CSRC / "abn_packed_census.hpp",
+            CSRC / "abn_packed_census.hpp", CSRC / "abn_regions.hpp",
             HOST / "simulate.hpp"]  # host_capi.cpp exports the launch policy to the tests
     newest = max(p.stat().st_mtime for p in srcs)
     CLI.parent.mkdir(exist_ok=True)

@@ -1,7 +1,7 @@
 // Host-side infrastructure shared by the translation units of libabneutral_hip.so (the fit path's abn_api.hip,
 // abn_context.hip and abn_plan.hip, which share abn_fit_host.hpp on top of this; abn_pairwise.hip, abn_windows.hip,
 // abn_analyze.hip, abn_sites.hip, abn_genes.hip, abn_codes.hip, abn_sites_common.hip, abn_sites_union.hip, abn_tiles.hip,
-// abn_resident.hip, abn_blocks.hip, abn_sites_sort.hip, abn_sites_dedup.hip, abn_sim.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
+// abn_resident.hip, abn_blocks.hip, abn_sites_sort.hip, abn_sites_dedup.hip, abn_sim.hip, abn_regions.hip): the context, its device-buffer pool, error reporting, the kernel_ms timer and the timing
 // events of a call, the copies on the context's stream (upload, to_device, to_host), the shell of the windows, codes and
 // tiles handles (created, destroyed, their packed matrix read), and what the consumers of resident methylomes share
 // (abn_resident.hip).  Not part of the C-ABI (include/abneutral.h is).
@@ -259,6 +259,18 @@ int handle_packed(H* h, uint8_t* host_out) {
   return ABN_OK;
 }
 
+// The region matrix of a tiles handle (abn_tiles_region_states makes it in abn_tiles.hip, abn_regions.hip reads it): n
+// rows of `stride` bytes, `columns` region fields each, the columns grouped into contiguous ranges
+struct abn_regions {
+  abn_ctx* ctx = nullptr;
+  int n = 0;
+  long long columns = 0, stride = 0;  // stride: abn_packed_row_stride(columns), at least 64
+  DevBuf<uint8_t> packed;
+  std::vector<int64_t> group_begin, group_end;  // [G] column ranges
+  std::vector<int32_t> src;                     // [columns] the tile of each column
+  double ms[2] = {0.0, 0.0};                    // the long tiles' census, the kernel
+};
+
 namespace abn {
 // The copies on the context's stream, nothing waited for.  upload: `count` elements allocated and sent up from the host
 template <class T>
@@ -307,6 +319,14 @@ int transitions_windows_packed_to_host(abn_ctx* c, const void* dev_packed, int32
 int packed_census_windows_dev(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites,
                               int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
                               int32_t n_windows, void* dev_counts, double* kernel_ms);
+// abn_regions.hip, for abn_tiles_region_states (abn_tiles.hip): the region states (abn_regions.hpp) of a DEVICE matrix
+// behind the checks of abn_packed_region_states_dev — HOST window and src arrays (src may be null: the identity), the rule
+// valid, long_sites > 0 — into dev_out [n x out_stride]; ms2 (may be null): the long windows' census and the kernel.
+// Returns after completion.
+int region_states_on_device(abn_ctx* c, const void* dev_packed, int32_t n_samples, int64_t n_sites, int64_t row_stride_bytes,
+                            const int64_t* site_begin, const int64_t* site_end, int64_t n_windows, const int32_t* src,
+                            int64_t n_columns, int64_t lo_num, int64_t hi_num, int64_t den, int64_t min_kept, int64_t long_sites,
+                            void* dev_out, int64_t out_stride, double* ms2);
 // abn_blocks.hip, for abn_tiles_block_bootstrap (abn_tiles.hip): the block bootstrap (abn_blocks.hpp) of DEVICE tables —
 // both, diff [n_blocks x n_pairs], level_sum_kept, kept [n_samples x n_blocks] — behind the checks of the groups: the counts
 // of n_replicates + 1 rows per group made on the device, the sums of every row to the HOST outputs (any may be null), ms5 =

@@ -9,6 +9,7 @@
 #include "abn_host.hpp"
 #define ABN_TILES_KERNELS
 #include "abn_tiles.hpp"
+#include "abn_regions.hpp"  // (the plain arithmetic: abn_tiles_region_states checks with it; the kernel is abn_regions.hip's)
 
 using namespace abn;
 
@@ -565,6 +566,65 @@ extern "C" int abn_tiles_transitions(abn_tiles* h, uint64_t* table) {
   const TileMatrix& m = h->pooled ? h->pool : h->own;
   return transitions_windows_packed_to_host(c, m.packed.p, h->n, m.columns, m.stride, h->begin.data(), h->end.data(),
                                             (int32_t)T, table);
+}
+
+// The region matrix of the handle's tiles (abn_regions.hpp): every tile one column, called from the tile's sites of the
+// handle's own matrix; the columns in ascending (group, tile), so that every group is one contiguous column range.  The new
+// handle owns its matrix: nothing of `h` is kept.
+extern "C" int abn_tiles_region_states(abn_tiles* h, int64_t lo_num, int64_t hi_num, int64_t den, int64_t min_kept,
+                                       const int32_t* group, int32_t n_groups, abn_regions** out) {
+  if (out) *out = nullptr;
+  if (int rc = tiles_need(h)) return rc;
+  abn_ctx* c = h->ctx;
+  if (!out) return set_err(c, ABN_ERR_INVALID_ARG, "null/size");
+  if (h->pooled)
+    return set_err(c, ABN_ERR_INVALID_ARG,
+                   "the tiles are pools: a pool is a class of sites, not a region; abn_tiles_set_intervals or "
+                   "abn_tiles_set_fixed first");
+  if (n_groups < 1) return set_err(c, ABN_ERR_INVALID_ARG, "n_groups is below 1");
+  const size_t T = h->begin.size(), G = (size_t)n_groups;
+  try {
+    // the columns: a counting sort of the tiles by group, stable, so ascending (group, tile)
+    std::vector<int64_t> first(G + 1, 0);
+    for (size_t t = 0; t < T; ++t) {
+      const int32_t g = group ? group[t] : 0;
+      if (g < -1 || g >= n_groups)
+        return set_err(c, ABN_ERR_INVALID_ARG,
+                       "tile " + std::to_string(t) + ": group " + std::to_string(g) + " outside -1.." + std::to_string(n_groups - 1));
+      if (g >= 0) ++first[(size_t)g + 1];
+    }
+    for (size_t g = 0; g < G; ++g) first[g + 1] += first[g];
+    const int64_t C = first[G];
+    std::vector<int32_t> src((size_t)C);
+    std::vector<int64_t> at(first.begin(), first.end() - 1);
+    for (size_t t = 0; t < T; ++t) {
+      const int32_t g = group ? group[t] : 0;
+      if (g >= 0) src[(size_t)at[(size_t)g]++] = (int32_t)t;
+    }
+    const TileMatrix& m = h->own;
+    const int32_t none = 0;  // every tile left out: C = 0, an empty matrix and no error — src is then no null pointer either
+    const int32_t* columns = C > 0 ? src.data() : &none;
+    const std::string why = region_refusal(m.packed.p, h->n, m.columns, m.stride, h->begin.data(), h->end.data(), (int64_t)T,
+                                           columns, C, lo_num, hi_num, den, min_kept, 0, m.packed.p);
+    if (!why.empty()) return set_err(c, ABN_ERR_INVALID_ARG, why);
+    return handle_create(c, h->n, out, [&](abn_regions* r) {
+      r->columns = C;
+      r->stride = std::max<long long>(abn_packed_row_stride(C), 64);
+      HIPCHK(c, r->packed.alloc((size_t)h->n * (size_t)r->stride));
+      if (C == 0) HIPCHK(c, hipMemsetAsync(r->packed.p, 0xff, r->packed.bytes(), c->stream));  // one step of filtered fields
+      if (int rc = region_states_on_device(c, m.packed.p, h->n, m.columns, m.stride, h->begin.data(), h->end.data(), (int64_t)T,
+                                           columns, C, lo_num, hi_num, den, min_kept, region_long_sites(0), r->packed.p,
+                                           r->stride, r->ms))
+        return rc;
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      r->group_begin.assign(first.begin(), first.end() - 1);
+      r->group_end.assign(first.begin() + 1, first.end());
+      r->src.swap(src);
+      return (int)ABN_OK;
+    });
+  } catch (const std::bad_alloc&) {
+    return set_err(c, ABN_ERR_HIP, "out of host memory");
+  }
 }
 
 extern "C" int abn_tiles_kernel_ms(const abn_tiles* h, double* ms2) {

@@ -20,6 +20,7 @@
 #endif
 
 #include "../csrc/abn_packed_census.hpp"
+#include "../csrc/abn_regions.hpp"
 #include "../csrc/abn_sim.hpp"
 #include "../csrc/abn_sites_common.hpp"
 #include "../csrc/abn_sites_union.hpp"
@@ -1104,5 +1105,32 @@ int abn_packed_census_windows_host(const unsigned char* packed, int n_samples, l
                              chunk.data(), (uint64_t*)counts);
   }
   return 0;
+}
+// ---- region states (csrc/abn_regions.hpp) in their host forms, for tests/test_regions_cpu.py and test_regions_gpu.py
+// abn_packed_region_states on the host: out [n_samples x abn_packed_row_stride(n_columns)].  walk = 0: the law field by
+// field; else the kernel's lane and workgroup structure, long windows through the census's walk.  1 with the refusal's
+// words in `text`
+int abn_packed_region_states_host(const unsigned char* packed, int n_samples, long long n_sites, long long row_stride,
+                                  const long long* site_begin, const long long* site_end, long long n_windows, const int* src,
+                                  long long n_columns, long long lo_num, long long hi_num, long long den, long long min_kept,
+                                  long long long_sites, unsigned char* out, int walk, char* text, int text_bytes) {
+  const int64_t* b = (const int64_t*)site_begin;
+  const int64_t* e = (const int64_t*)site_end;
+  const std::string why = abn::region_refusal(packed, n_samples, n_sites, row_stride, b, e, n_windows, src, n_columns, lo_num,
+                                              hi_num, den, min_kept, long_sites, out);
+  put_text(text, text_bytes, why);
+  if (!why.empty()) return 1;
+  const abn::RegionRule rule{(uint64_t)lo_num, (uint64_t)hi_num, (uint64_t)den, (uint64_t)min_kept};
+  const long long out_stride = (n_columns + abn::kPackedStepSites - 1) / abn::kPackedStepSites * 64;
+  if (walk) abn::region_states_walk(packed, n_samples, row_stride, b, e, n_windows, src, n_columns, rule,
+                                    abn::region_long_sites(long_sites), out, out_stride);
+  else abn::region_states_serial(packed, n_samples, row_stride, b, e, src, n_columns, rule, out, out_stride);
+  return 0;
+}
+// region_call on planted counts; -1 for a rule outside the law's bounds
+int abn_region_call_host(unsigned long long n0, unsigned long long n1, unsigned long long n2, long long lo_num, long long hi_num,
+                         long long den, long long min_kept) {
+  if (den < 1 || den > (1ll << 20) || lo_num < 0 || lo_num > hi_num || hi_num > den || min_kept < 1) return -1;
+  return (int)abn::region_call(n0, n1, n2, abn::RegionRule{(uint64_t)lo_num, (uint64_t)hi_num, (uint64_t)den, (uint64_t)min_kept});
 }
 }

@@ -5,7 +5,8 @@
 // whole methylome files and a gene annotation, the sites placed into windows on the device and no file tree in between.
 // With --methylome DIR --nodes FILE --edges FILE and --tiles SIZE [--tile-step STEP] or --regions FILE: the rates per
 // genomic tile (tiles.hpp) — fixed bins along the genome or the rows of a BED-like list — from whole methylomes kept on the
-// device; no annotation.  With --regions FILE --pool: one pedigree per name in the list's 4th field.
+// device; no annotation.  With --regions FILE --pool: one pedigree per name in the list's 4th field.  With --region-states
+// LO,HI: every tile or row gets one state per sample and the pedigree is built from the regions' states (region_states.hpp).
 // All windows are fitted by one batched plan on the MI355X.  Flags follow src/arguments.rs:6-62 where they apply.
 #include <cstdlib>
 #include <cstring>
@@ -26,6 +27,7 @@ int main(int argc, char** argv) {
   std::string devices_arg;
   bool stream_sweep = false;
   metaprofile::TileArgs tiles;
+  bool region_min_given = false;
   bool tiles_given = false, tile_step_given = false, block_starts_given = false, parse_host = false, sites_host = false, contexts_given = false;
   unsigned contexts = 1u;
   for (int i = 1; i < argc; ++i) {
@@ -127,6 +129,20 @@ int main(int argc, char** argv) {
       }
     }
     else if (f == "--regions") tiles.regions = val();
+    else if (f == "--region-states") {
+      if (!metaprofile::parse_region_states(val(), tiles.region)) {
+        std::fprintf(stderr, "error: %s\n", metaprofile::kRegionStatesExpects);
+        return 2;
+      }
+      tiles.region.wanted = true;
+    }
+    else if (f == "--region-min-sites") {
+      if (!metaprofile::parse_region_min_sites(val(), tiles.region.min_sites)) {  // digits only, as LO,HI
+        std::fprintf(stderr, "error: --region-min-sites expects a number of sites of at least 1\n");
+        return 2;
+      }
+      region_min_given = true;
+    }
     else if (f == "--pool") tiles.pool = true;
     else if (f == "--transitions") transitions::request().wanted = true;
     else if (f == "-h" || f == "--help") {
@@ -180,6 +196,15 @@ int main(int argc, char** argv) {
                 "                            from S starts [default 10], and write block_bootstrap.txt (per group alpha and beta\n"
                 "                            of the observed data, sd and percentile CI of the draws) and block_raw.npy (R x 7 x\n"
                 "                            groups); the other files stay as they are; one device\n"
+                "       [--region-states LO,HI [--region-min-sites K]]  with --tiles or --regions: region-level analysis.  Every\n"
+                "                            tile or row gets ONE state per sample, called on the device from the sample's sites\n"
+                "                            inside it - their mean level (U 0, I 1/2, M 1) below LO calls U, above HI calls M,\n"
+                "                            else I; fewer than K kept sites [default 1]: filtered - and ONE pedigree is built\n"
+                "                            from all regions' states; with --pool one per name in the 4th field, the rows staying\n"
+                "                            one region each (they may overlap).  LO and HI: decimals in [0, 1], at most six\n"
+                "                            fraction digits, read exactly.  Writes results.txt (window = the group, cg_count = its\n"
+                "                            regions), raw.npy, regions.txt, region_states.npy (uint8, samples x regions) and with\n"
+                "                            --pool groups.txt; not with --block-bootstrap\n"
                 "       [--stream-sweep]     pedigrees too large for the LDS: read a fit's rows once per Nelder-Mead iteration\n"
                 "                            instead of once per cost evaluation; the same output files");
       return 0;
@@ -236,6 +261,16 @@ int main(int argc, char** argv) {
     else if (tiles_given && tiles.step != 0 && tiles.step < tiles.size)
       refused = "--block-bootstrap needs tiles that do not overlap: a --tile-step of at least the tile size";
     else if (devices_arg.find(',') != std::string::npos) refused = "--block-bootstrap runs on one device: --devices names several";
+    if (refused) {
+      std::fprintf(stderr, "error: %s\n", refused);
+      return 2;
+    }
+  }
+  if (tiles.region.wanted || region_min_given) {
+    const char* refused = nullptr;
+    if (!tiles.region.wanted) refused = "--region-min-sites belongs to --region-states";
+    else if (!tile_mode || !a.genome.empty()) refused = "--region-states belongs to --tiles and --regions";
+    else if (tiles.block_replicates > 0) refused = "--region-states does not go with --block-bootstrap: block resampling of regions is not built";
     if (refused) {
       std::fprintf(stderr, "error: %s\n", refused);
       return 2;
@@ -309,7 +344,11 @@ int main(int argc, char** argv) {
       auto write = [&](const metaprofile::TilesOutput& res, const std::filesystem::path& dir) {
         std::printf("%s\n", res.out.results_txt.c_str());
         std::ofstream(dir / "results.txt") << res.out.results_txt;
-        if (tiles.pool) std::ofstream(dir / "pools.txt") << res.pools_txt;
+        if (tiles.region.wanted) {
+          std::ofstream(dir / "regions.txt") << res.regions_txt;
+          if (tiles.pool) std::ofstream(dir / "groups.txt") << res.groups_txt;
+          metaprofile::write_u8_npy(res.region_states, res.region_rows, res.region_columns, (dir / "region_states.npy").string());
+        } else if (tiles.pool) std::ofstream(dir / "pools.txt") << res.pools_txt;
         else std::ofstream(dir / "tiles.txt") << res.tiles_txt;
         metaprofile::write_raw_npy(res.out, (dir / "raw.npy").string());
         if (transitions::request().wanted) transitions::write_npy(dir.string(), res.transitions);

@@ -14,6 +14,7 @@
 
 #include "block_bootstrap.hpp"
 #include "metaprofile.hpp"
+#include "region_states.hpp"
 
 namespace alphabeta {
 namespace metaprofile {
@@ -24,6 +25,7 @@ struct TileArgs {
   bool pool = false;           // --pool: the rows of the list that share a name are one pool, one pedigree (region_pools)
   int64_t block_replicates = 0;  // --block-bootstrap R (0: none) and --block-starts S (block_bootstrap.hpp)
   int block_starts = kBlockStartsDefault;
+  RegionArgs region;             // --region-states LO,HI [--region-min-sites K] (region_states.hpp)
   bool fixed() const { return regions.empty(); }
 };
 
@@ -116,6 +118,12 @@ struct TilesOutput {
   std::string pools_txt;  // --pool, in its place: pool;name;intervals;segments;cg_count;fitted, every pool
   transitions::Table transitions;  // --transitions: the table of every tile (pool), fitted or not, in the rows' order
   BlockBootstrap block;            // --block-bootstrap: block_bootstrap.txt and block_raw.npy
+  // --region-states, in place of tiles.txt / pools.txt: regions.txt (column;tile;chromosome;start;end;cg_count;group, every
+  // column of the region matrix), groups.txt (--pool: group;name;regions;fitted) and region_states.npy (uint8, samples x
+  // columns: the called fields, rows in the nodes' order)
+  std::string regions_txt, groups_txt;
+  std::vector<uint8_t> region_states;
+  size_t region_rows = 0, region_columns = 0;
 };
 
 // The sibling of alphabeta_multiple_in_memory for tiles.  args: methylome (directory), nodes, edges, align, iterations,
@@ -143,6 +151,99 @@ inline TileSamples load_tile_samples(const WindowArgs& args, unsigned contexts) 
   return s;
 }
 
+// --region-states behind the tiles: th's tiles (fixed bins or the rows of `list`) become the columns of a region matrix
+// (abn_tiles_region_states), grouped by `group` (null: one group, "regions"); every group is then a window of fit_windows
+// as a tile is, its level fold the census of the regions' states (sum = n1 / 2 + n2 over kept = n0 + n1 + n2: exact
+// doubles, whatever the order of addition), its D the scan of the region matrix over the group's columns.  count [T]: the
+// tiles' sites.  results.txt: `window` = the group's index, `cg_count` = its regions.
+inline TilesOutput regions_of_tiles(const WindowArgs& args, const TileArgs& tiles, const TileSamples& loaded, abn_tiles* th,
+                                    const TileList& list, const std::vector<int64_t>& count, const int32_t* group,
+                                    const std::vector<std::string>& group_names) {
+  Device& dev = default_device();
+  const detail::Inputs& graph = loaded.graph;
+  const std::vector<std::string>& names = loaded.names;
+  const size_t nn = graph.nodes.size(), npairs = nn * (nn - 1) / 2, G = group_names.size();
+  Owned<abn_regions, abn_regions_destroy> rh;
+  dev.check(abn_tiles_region_states(th, tiles.region.lo_num, tiles.region.hi_num, kRegionDen, tiles.region.min_sites, group,
+                                    (int32_t)G, rh.out()),
+            "abn_tiles_region_states");
+  int64_t C = 0, stride = 0;
+  dev.check(abn_regions_info(rh.get(), nullptr, &C, &stride, nullptr), "abn_regions_info");
+  std::vector<int64_t> gb(G), ge(G);
+  std::vector<int32_t> src((size_t)C);
+  std::vector<uint8_t> packed(nn * (size_t)stride);
+  std::vector<uint64_t> census(G * nn * 3, 0), both(std::max<size_t>(G * npairs, 1), 0);
+  std::vector<double> dv(std::max<size_t>(G * npairs, 1), 0.0);
+  dev.check(abn_regions_layout(rh.get(), gb.data(), ge.data()), "abn_regions_layout");
+  dev.check(abn_regions_order(rh.get(), src.data()), "abn_regions_order");
+  dev.check(abn_regions_packed(rh.get(), packed.data()), "abn_regions_packed");
+  dev.check(abn_regions_census(rh.get(), census.data()), "abn_regions_census");
+  dev.check(abn_regions_pairwise(rh.get(), nullptr, both.data(), dv.data()), "abn_regions_pairwise");
+  std::printf("Called %lld regions in %zu group%s\n", (long long)C, G, G == 1 ? "" : "s");
+
+  TilesOutput res;
+  if (transitions::request().wanted) {
+    for (const auto& node : graph.nodes) {
+      res.transitions.names.push_back(node.name);
+      res.transitions.generations.push_back(node.generation);
+    }
+    res.transitions.counts.assign(G * npairs * 9, 0);
+    if (npairs > 0) dev.check(abn_regions_transitions(rh.get(), res.transitions.counts.data()), "abn_regions_transitions");
+  }
+  std::vector<double> sum(nn * G);
+  std::vector<int64_t> kept(nn * G);
+  for (size_t g = 0; g < G; ++g)
+    for (size_t a = 0; a < nn; ++a) {
+      const uint64_t* k = &census[(g * nn + a) * 3];
+      sum[a * G + g] = 0.5 * (double)k[1] + (double)k[2];
+      kept[a * G + g] = (int64_t)(k[0] + k[1] + k[2]);
+    }
+  const std::vector<detail::PairTimes> times = detail::convert_times(graph);
+  std::vector<Win> wins;
+  for (size_t g = 0; g < G; ++g) {
+    try {
+      if (ge[g] == gb[g]) throw Error(ABN_ERR_INVALID_ARG, "no region lies in this group");
+      for (size_t a = 0; a < nn; ++a)
+        if (kept[a * G + g] == 0) throw Error(ABN_ERR_INVALID_ARG, names[a] + " calls no region in this group");
+      for (size_t a = 0, p = 0; a < nn; ++a)
+        for (size_t b = a + 1; b < nn; ++b, ++p)
+          if (both[g * npairs + p] == 0)
+            throw Error(ABN_ERR_INVALID_ARG, names[a] + " and " + names[b] + " share no called region in this group");
+      wins.push_back(window_from_handle(group_names[g], g, times, loaded.sample_of, nn, G, g, sum, kept, &dv[g * npairs]));
+    } catch (const std::exception& e) {
+      std::printf("Error: Error while building pedigree: group %zu (%s): %s\n", g, group_names[g].c_str(), e.what());
+    }
+  }
+  res.out = fit_windows(args, std::move(wins), std::vector<int>());
+  std::vector<char> fitted(G, 0);
+  res.out.results_txt = results_header();
+  for (const WindowResult& r : res.out.results) {
+    fitted[r.window_index] = 1;
+    res.out.results_txt += results_line(args.name, r.window_index, (long long)(ge[r.window_index] - gb[r.window_index]), r);
+  }
+  res.regions_txt = "column;tile;chromosome;start;end;cg_count;group\n";
+  for (size_t g = 0; g < G; ++g)
+    for (int64_t c = gb[g]; c < ge[g]; ++c) {
+      const size_t t = (size_t)src[(size_t)c];
+      res.regions_txt += std::to_string(c) + ";" + std::to_string(t) + ";" + chromosome_name(list.chromosome[t]) + ";" +
+                         std::to_string(list.start[t]) + ";" + std::to_string(list.end[t]) + ";" + std::to_string(count[t]) + ";" +
+                         std::to_string(g) + "\n";
+    }
+  if (tiles.pool) {
+    res.groups_txt = "group;name;regions;fitted\n";
+    for (size_t g = 0; g < G; ++g)
+      res.groups_txt += std::to_string(g) + ";" + group_names[g] + ";" + std::to_string(ge[g] - gb[g]) + ";" + (fitted[g] ? "1" : "0") + "\n";
+  }
+  res.region_rows = nn, res.region_columns = (size_t)C;
+  res.region_states.resize(nn * (size_t)C);
+  for (size_t a = 0; a < nn; ++a) {
+    const uint8_t* row = packed.data() + loaded.sample_of[a] * (size_t)stride;
+    for (size_t c = 0; c < (size_t)C; ++c)
+      res.region_states[a * (size_t)C + c] = (uint8_t)((row[(c >> 4) * 4 + (c & 3)] >> (2 * ((c >> 2) & 3))) & 3);
+  }
+  return res;
+}
+
 // alphabeta_multiple_tiles behind the loader: sites[i] = sampled node i's methylome
 inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tiles, const TileSamples& loaded,
                                     const std::vector<windows::ResidentSites>& sites) {
@@ -163,7 +264,10 @@ inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tile
     if (pools.skipped) std::printf("Skipped %zu regions without a name in the 4th field\n", pools.skipped);
     if (pools.names.empty()) throw Error(ABN_ERR_INVALID_ARG, "No region of " + tiles.regions + " has a name to pool by");
   }
-  const char* unit = tiles.pool ? "pool" : "tile";
+  // --region-states with --pool: every named row stays a tile of its own, the names are the groups — no sites are pooled
+  const bool pooled = tiles.pool && !tiles.region.wanted;
+  if (tiles.pool && !pooled) list = pools.rows;
+  const char* unit = pooled ? "pool" : "tile";
   Owned<abn_tiles, abn_tiles_destroy> th;
   dev.check(abn_tiles_create(dev.get(), args.posterior_max_filter, (int32_t)args.align, (int32_t)nn,
                              resident::pointers(sites).data(), th.out()),
@@ -172,7 +276,7 @@ inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tile
     std::fputs(line.c_str(), stdout);
   if (tiles.fixed())
     dev.check(abn_tiles_set_fixed(th.get(), tiles.size, tiles.step), "abn_tiles_set_fixed");
-  else if (tiles.pool)
+  else if (pooled)
     dev.check(abn_tiles_set_pools(th.get(), (int64_t)pools.rows.size(), pools.rows.chromosome.data(), pools.rows.start.data(),
                                   pools.rows.end.data(), pools.pool.data(), (int64_t)pools.names.size()),
               "abn_tiles_set_pools");
@@ -184,7 +288,7 @@ inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tile
   const size_t T = (size_t)n_tiles;
   if (T == 0) throw Error(ABN_ERR_INVALID_ARG, "no tile: the methylomes hold no site");
   std::vector<int64_t> segments(T, 0);  // --pool: every pool's merged segments
-  if (tiles.pool) {
+  if (pooled) {
     int64_t S = 0;
     dev.check(abn_tiles_pool_segments(th.get(), &S, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "abn_tiles_pool_segments");
     std::vector<int32_t> of((size_t)S);
@@ -193,6 +297,12 @@ inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tile
   } else {
     list.chromosome.resize(T), list.start.resize(T), list.end.resize(T);
     dev.check(abn_tiles_intervals(th.get(), list.chromosome.data(), list.start.data(), list.end.data()), "abn_tiles_intervals");
+  }
+  if (tiles.region.wanted) {  // of the tiles' own results only their sites are read: no per-tile fold or scan table here
+    std::vector<int64_t> sites(T);
+    dev.check(abn_tiles_stats(th.get(), sites.data(), nullptr, nullptr), "abn_tiles_stats");
+    return regions_of_tiles(args, tiles, loaded, th.get(), list, sites, tiles.pool ? pools.pool.data() : nullptr,
+                            tiles.pool ? pools.names : std::vector<std::string>{"regions"});
   }
   std::vector<int64_t> count(T), kept(nn * T);
   std::vector<double> sum(nn * T), dv(std::max<size_t>(T * npairs, 1), 0.0);
@@ -213,7 +323,7 @@ inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tile
   const std::vector<detail::PairTimes> times = detail::convert_times(graph);
   std::vector<Win> wins;
   for (size_t t = 0; t < T; ++t) {
-    const std::string region = tiles.pool ? pools.names[t] : tile_region(list.chromosome[t], list.start[t], list.end[t]);
+    const std::string region = pooled ? pools.names[t] : tile_region(list.chromosome[t], list.start[t], list.end[t]);
     try {
       if (count[t] == 0) throw Error(ABN_ERR_INVALID_ARG, std::string("no site lies in this ") + unit);
       for (size_t a = 0; a < nn; ++a)
@@ -232,7 +342,7 @@ inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tile
   res.transitions = std::move(table);
   res.out = fit_windows(args, std::move(wins), std::vector<int>());
   if (tiles.block_replicates > 0)  // the blocks drawn with replacement: a pool's segments, or the genome's tiles in one group
-    res.block = block_bootstrap(th.get(), tiles.pool ? pools.names : std::vector<std::string>{"genome"}, times, sample_of, nn,
+    res.block = block_bootstrap(th.get(), pooled ? pools.names : std::vector<std::string>{"genome"}, times, sample_of, nn,
                                 tiles.block_replicates, tiles.block_starts);
   std::vector<char> fitted(T, 0);
   res.out.results_txt = results_header();
@@ -240,7 +350,7 @@ inline TilesOutput tiles_of_samples(const WindowArgs& args, const TileArgs& tile
     fitted[r.window_index] = 1;
     res.out.results_txt += results_line(args.name, r.window_index, (long long)count[r.window_index], r);
   }
-  if (tiles.pool) {
+  if (pooled) {
     res.pools_txt = "pool;name;intervals;segments;cg_count;fitted\n";
     for (size_t t = 0; t < T; ++t)
       res.pools_txt += std::to_string(t) + ";" + pools.names[t] + ";" + std::to_string(pools.intervals[t]) + ";" +

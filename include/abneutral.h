@@ -345,6 +345,32 @@ int abn_packed_census_windows(abn_ctx* ctx, const uint8_t* packed, int32_t n_sam
 int abn_packed_census_windows_dev(abn_ctx* ctx, const void* dev_packed, int32_t n_samples, int64_t n_sites,
                                   int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
                                   int32_t n_windows, void* dev_counts, double* kernel_ms);
+/* Region-level states: one field per (sample, region), called from the sample's single-site fields inside the region and
+ * written in the packed format above, so that every packed scan and the census take the result as a matrix of sites.
+ * THE LAW.  Inputs: packed[n_samples x row_stride_bytes] of n_sites sites (format above); T = n_windows windows
+ * [site_begin[t], site_end[t]), any column ranges of the rows, overlapping or empty; a column map src[C], C = n_columns,
+ * src[c] in [0, T), repeats and omissions allowed (NULL: the identity, and C must be T); a rule of exact integers with
+ * 0 <= lo_num <= hi_num <= den, 1 <= den <= 2^20, min_kept >= 1.  For sample s and window t let n0, n1, n2 be the fields
+ * 0, 1, 2 of row s inside the window (what abn_packed_census_windows counts), kept = n0 + n1 + n2, m = n1 + 2 n2 (twice the
+ * sum of state / 2, the level abn_sim_pedigree and abn_sim_study use).  The region's field is 3 if kept < min_kept (an
+ * empty window is always 3); 0 if m den < lo_num 2 kept; 2 if m den > hi_num 2 kept; 1 otherwise (equality on either side
+ * is 1).  64-bit unsigned arithmetic: n_sites <= 2^34 and den <= 2^20 keep both products below 2^56; no floating point.
+ * Output: out_packed[n_samples x abn_packed_row_stride(C)], column c of row s the field of window src[c], the fields from
+ * C to the end of the stride 3.  One fused kernel counts, calls and packs (one lane per output field); windows of at least
+ * long_sites sites (0: the library's default; else a multiple of 16, at most 2^29) are counted by the census kernels first.
+ * ABN_ERR_INVALID_ARG with a text, before any launch: what abn_packed_census_windows refuses; a rule outside the bounds;
+ * src[c] outside [0, T) (the text names the column); src NULL with n_columns != n_windows; n_windows or n_columns above
+ * INT32_MAX; long_sites negative or no multiple of 16.  n_columns == 0: ABN_OK, nothing is written.  HOST buffers. */
+int abn_packed_region_states(abn_ctx* ctx, const uint8_t* packed, int32_t n_samples, int64_t n_sites,
+                             int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end, int64_t n_windows,
+                             const int32_t* src, int64_t n_columns, int64_t lo_num, int64_t hi_num, int64_t den,
+                             int64_t min_kept, int64_t long_sites, uint8_t* out_packed);
+/* ... DEVICE matrix (16-byte aligned) and DEVICE output, HOST window and src arrays; ms2 (may be NULL): the HIP-event times
+ * of the long windows' census and of the kernel.  Returns after the work has completed. */
+int abn_packed_region_states_dev(abn_ctx* ctx, const void* dev_packed, int32_t n_samples, int64_t n_sites,
+                                 int64_t row_stride_bytes, const int64_t* site_begin, const int64_t* site_end,
+                                 int64_t n_windows, const int32_t* src, int64_t n_columns, int64_t lo_num, int64_t hi_num,
+                                 int64_t den, int64_t min_kept, int64_t long_sites, void* dev_out, double* ms2);
 
 /* ------------------------------------------------------------------ window placement (the `extract` stage)
  * Windows::extract (src/windows.rs:287-343) behind the gene choice: MethylationSite::place_in_windows
@@ -892,6 +918,37 @@ int abn_tiles_block_bootstrap(abn_tiles* h, uint64_t seed, int64_t n_replicates,
 int abn_tiles_block_groups(const abn_tiles* h, int64_t* n_groups, int64_t* n_blocks, int64_t* group_begin,
                            int64_t* group_end);
 int abn_tiles_block_ms(const abn_tiles* h, double* ms5);
+
+/* Region-level states of a tiles handle: abn_packed_region_states_dev (the law above, the library's long_sites) over the
+ * handle's own matrix with the handle's tiles — as abn_tiles_set_intervals or abn_tiles_set_fixed left them — as the
+ * windows.  group [n_tiles] (NULL: all 0) puts tile t into group[t] in [0, n_groups), -1 leaves the tile out; the output
+ * columns are the tiles in ascending (group, tile index), so every group is one contiguous column range — one region-level
+ * pedigree per group.  The new handle owns its matrix and is independent of later changes to h.  ABN_ERR_INVALID_ARG:
+ * before any set_*; with pools set (a pool is a class of sites, not a region); n_groups < 1; a group outside
+ * [-1, n_groups) (the text names the tile); a rule outside the law's bounds.  An empty group is no error: zeros and NaN, as
+ * an empty window gets; nor is a matrix without any column (every tile left out).
+ * abn_regions_info: any output may be NULL; row_stride_bytes = abn_packed_row_stride(n_columns), at least 64.
+ * abn_regions_layout: group_begin, group_end [n_groups], in columns.  abn_regions_order: src [n_columns], the tile of each
+ * column.  abn_regions_packed: the matrix [n_samples x row_stride_bytes] to the host; _device_ptr: where it lives.
+ * abn_regions_census: abn_packed_census_windows_dev over the groups' ranges, HOST counts uint64 [n_groups x n_samples x 3].
+ * abn_regions_pairwise: abn_pairwise_divergence_windows_packed_dev over them, host outputs [n_groups x pairs] (any may be
+ * NULL); abn_regions_transitions: HOST table uint64 [n_groups x pairs x 9].  abn_regions_kernel_ms: double[2], the HIP-event
+ * times of the long tiles' census and of the kernel. */
+typedef struct abn_regions abn_regions;
+int abn_tiles_region_states(abn_tiles* h, int64_t lo_num, int64_t hi_num, int64_t den, int64_t min_kept,
+                            const int32_t* group /* [n_tiles], NULL: all 0; -1: the tile is left out */, int32_t n_groups,
+                            abn_regions** out);
+int abn_regions_destroy(abn_regions* h);
+int abn_regions_info(const abn_regions* h, int32_t* n_samples, int64_t* n_columns, int64_t* row_stride_bytes,
+                     int32_t* n_groups);
+int abn_regions_layout(const abn_regions* h, int64_t* group_begin, int64_t* group_end);
+int abn_regions_order(const abn_regions* h, int32_t* src);
+int abn_regions_packed(abn_regions* h, uint8_t* host_out);
+int abn_regions_packed_device_ptr(abn_regions* h, void** dev_ptr);
+int abn_regions_census(abn_regions* h, uint64_t* counts);
+int abn_regions_pairwise(abn_regions* h, uint64_t* diff, uint64_t* both, double* dvalue);
+int abn_regions_transitions(abn_regions* h, uint64_t* table);
+int abn_regions_kernel_ms(const abn_regions* h, double* ms2);
 
 /* ------------------------------------------------------------------ (4) batched, device-resident plan
  * One pedigree topology (t0,t1,t2 of N rows), W windows that differ in D / p0uu (the metaprofile loop,
